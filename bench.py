@@ -14,7 +14,16 @@ batch is sharded (independent crops) and a step also includes th
 all-gather of the packed (bbox, cls) maps.  Protocol mirrors the reference's own
 (README.md:43, Benchmark.swift:55-77): warm-up calls, then the mean over K timed calls.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0): metric, value, unit, n_gpus, steps, warmup, ms_per_step (one timed step), higher_is_better,
+scaling, vs_baseline, dtype, data, config.  A plain run does only that: set-up, warm-up, the K timed steps, the line.
+  --dump-outputs DIR  after the timed steps, the maps the last timed step returned are written as DIR/bbox.npy (N,4,16,16)
+               and DIR/cls.npy (N,1,16,16), fp32 (N = the global batch; a fixed seeded sample of crops beyond 64 MB).  The
+               inputs are seeded, so two builds run with the same arguments can be compared map for map.
+  --full       everything else this bench measures, in the same process after the timed steps (the --no-* flags switch single
+               legs off): the per-kernel profile of the first warm-up steps and the dominant kernel bracketed with HIP events
+               inside the timed region (for `roofline`), shader clock under load, the two-handle / split-stream / other-math
+               supplementary numbers, the collective alone (N > 1), and the objects below.
+Extra objects (--full):
   roofline     dominant kernel (largest share of device time): algorithmic FLOPs or bytes per launch /
                its average launch duration, measured with HIP events recorded around that kernel on the
                launch stream inside the timed region.
@@ -26,8 +35,9 @@ Prints ONE JSON line (rank 0).  Extra objects:
                (no H.264 decoder exists on the box, profiles/r02_box_probe.txt), ms/frame for the reference-style host crop
                path and for device crop + device post-processing, the CPU-oracle tracker beside it, boxes compared.
 
-`python bench.py --gpus N` with N > 1 and no torch.distributed environment re-executes itself under
-torch.distributed.run (one rank per GPU, 127.0.0.1 rendezvous); the driver's explicit torchrun launch works as before.
+`python bench.py --gpus N` with N > 1 and no torch.distributed environment runs itself as a child under
+torch.distributed.run (one rank per GPU, 127.0.0.1 rendezvous) and exits with its status; the driver's explicit torchrun launch
+works as before.
 """
 from __future__ import annotations
 
@@ -49,6 +59,26 @@ PEAK_HBM_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E spec peak
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 MFMA (no sparsity)
 FLOPS_PER_CROP = 922_787_840    # 2 x 461 393 920 MAC
 BYTES_PER_CROP = 857_088        # compulsory fp32 bytes per crop
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> None:
+    """--dump-outputs: write {name: array} as out_dir/<name>.npy.  The arrays share their first (crop) axis; when together they
+    exceed `limit` bytes, the same fixed sample of crops (seed 0, in crop order) is written of each."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {k} is {a.dtype}, not float32 / float64")
+    n = next(iter(arrays.values())).shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        keep = max(1, n * limit // total)
+        idx = np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
 
 
 def norm_u8(u8_nchw: torch.Tensor) -> torch.Tensor:
@@ -703,14 +733,23 @@ def main() -> None:
     ap.add_argument("--no-pipelined", action="store_true", help="skip the two-handles-on-two-streams supplementary number")
     ap.add_argument("--no-train", action="store_true", help="skip the BASELINE configs[4] object (head training step, first slice)")
     ap.add_argument("--no-fear-m", action="store_true", help="skip the BASELINE configs[3] object (synthetic FEAR-M, bf16, B=512)")
+    ap.add_argument("--full", action="store_true", help="also every supplementary measurement: the per-kernel profile and roofline "
+                    "(HIP events in the warm-up and timed steps), then CPU baseline, other math mode, two-stream numbers, configs[3] / "
+                    "[4], batch-1 latency, ...; the --no-* flags above switch single legs off.  Off: set-up, warm-up, the timed steps "
+                    "and the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the maps of the last timed step as DIR/bbox.npy and DIR/cls.npy (fp32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # plain `python bench.py --gpus N`: become N ranks (one per GPU) under torch.distributed.run on this node
+        # plain `python bench.py --gpus N`: run N ranks (one per GPU) under torch.distributed.run on this node, as a child
         have = torch.cuda.device_count() if torch.cuda.is_available() else 0
         if have < args.gpus:
             raise SystemExit(f"bench.py --gpus {args.gpus} needs {args.gpus} GPUs on this node, {have} visible")
         import socket
+        import subprocess
         with socket.socket() as so:
             so.bind(("127.0.0.1", 0))
             port = so.getsockname()[1]
@@ -718,7 +757,7 @@ def main() -> None:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        raise SystemExit(subprocess.run(cmd).returncode)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -807,58 +846,72 @@ def main() -> None:
             dist.barrier()
         torch.cuda.synchronize()
 
-    # warm-up; the first warm-up steps run with every kernel bracketed to find the dominant one
-    n_prof = min(3, max(1, args.warmup))
-    net.set_profile(True, op=-1)
-    net.profile_reset()
-    for _ in range(n_prof):
-        step()
-    torch.cuda.synchronize()
-    plan = net.plan(256, True)
-    prof = net.profile_read(256, True)
-    net.set_profile(False)
-    per_op = [(ms / max(cnt, 1), cnt) for ms, cnt in prof]
-    launches_per_step = [cnt / n_prof for _, cnt in prof]
-    op_time = [per_op[i][0] * launches_per_step[i] for i in range(len(plan))]
-    # ops with the same name run the same kernel symbol on the same shape (what rocprofv3 --stats groups):
-    # the dominant kernel is the name group with the largest share of the step
-    group_time = {}
-    for i, (nm, _, _) in enumerate(plan):
-        group_time[nm] = group_time.get(nm, 0.0) + op_time[i]
-    dom_name = max(group_time, key=group_time.get)
-    dom_ops = [i for i, (nm, _, _) in enumerate(plan) if nm == dom_name]
-    dom = dom_ops[0]
-    if args.dump_ops and rank == 0:
-        tot = sum(op_time)
-        for i, (name, fl, by) in enumerate(plan):
-            crops_per_launch = B / max(launches_per_step[i], 1)
-            t = per_op[i][0]
-            print(f"{i:3d} {name:28s} {op_time[i]:8.3f} ms/step {100 * op_time[i] / tot:5.1f}%  "
-                  f"{fl * crops_per_launch / (t * 1e-3) / 1e12 if t else 0:7.2f} TF/s "
-                  f"{by * crops_per_launch / (t * 1e-3) / 1e9 if t else 0:8.1f} GB/s", file=sys.stderr)
-        print(f"sum of kernels {tot:.3f} ms/step", file=sys.stderr)
+    # warm-up; with --full (or --dump-ops) the first warm-up steps run with every kernel bracketed to find the dominant one
+    n_prof = min(3, max(1, args.warmup)) if (args.full or args.dump_ops) else 0
+    if n_prof:
+        net.set_profile(True, op=-1)
+        net.profile_reset()
+        for _ in range(n_prof):
+            step()
+        torch.cuda.synchronize()
+        plan = net.plan(256, True)
+        prof = net.profile_read(256, True)
+        net.set_profile(False)
+        per_op = [(ms / max(cnt, 1), cnt) for ms, cnt in prof]
+        launches_per_step = [cnt / n_prof for _, cnt in prof]
+        op_time = [per_op[i][0] * launches_per_step[i] for i in range(len(plan))]
+        # ops with the same name run the same kernel symbol on the same shape (what rocprofv3 --stats groups):
+        # the dominant kernel is the name group with the largest share of the step
+        group_time = {}
+        for i, (nm, _, _) in enumerate(plan):
+            group_time[nm] = group_time.get(nm, 0.0) + op_time[i]
+        dom_name = max(group_time, key=group_time.get)
+        dom_ops = [i for i, (nm, _, _) in enumerate(plan) if nm == dom_name]
+        dom = dom_ops[0]
+        if args.dump_ops and rank == 0:
+            tot = sum(op_time)
+            for i, (name, fl, by) in enumerate(plan):
+                crops_per_launch = B / max(launches_per_step[i], 1)
+                t = per_op[i][0]
+                print(f"{i:3d} {name:28s} {op_time[i]:8.3f} ms/step {100 * op_time[i] / tot:5.1f}%  "
+                      f"{fl * crops_per_launch / (t * 1e-3) / 1e12 if t else 0:7.2f} TF/s "
+                      f"{by * crops_per_launch / (t * 1e-3) / 1e9 if t else 0:8.1f} GB/s", file=sys.stderr)
+            print(f"sum of kernels {tot:.3f} ms/step", file=sys.stderr)
     for _ in range(max(0, args.warmup - n_prof)):
         step()
 
-    # timed region: only the dominant kernel is bracketed with HIP events (2 events per launch)
-    net.profile_reset()
-    net.set_profile(True, op=dom)
+    # timed region; with --full only the dominant kernel is bracketed with HIP events (2 events per launch), a plain run
+    # brackets nothing
+    if args.full:
+        net.profile_reset()
+        net.set_profile(True, op=dom)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     barrier()
     elapsed = time.perf_counter() - t0
-    net.set_profile(False)
-    reads = net.profile_read(256, True)
-    dom_ms = sum(reads[i][0] for i in dom_ops)
-    dom_cnt = sum(reads[i][1] for i in dom_ops)
+    if args.full:
+        net.set_profile(False)
+        reads = net.profile_read(256, True)
+        dom_ms = sum(reads[i][0] for i in dom_ops)
+        dom_cnt = sum(reads[i][1] for i in dom_ops)
+
+    # what the last timed step returned to its caller: the global batch's maps (the gathered packed maps with N > 1), written
+    # out before any supplementary leg of --full reuses the buffers
+    if args.dump_outputs and rank == 0:
+        if use_dist:
+            maps = overlap.finish() if overlap is not None else gathered
+            dump_outputs(args.dump_outputs, {"bbox": maps[:, :4].cpu().numpy(), "cls": maps[:, 4:].cpu().numpy()})
+        else:
+            dump_outputs(args.dump_outputs, {"bbox": bbox.cpu().numpy(), "cls": cls.cpu().numpy()})
 
     gather_ms = None
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if use_dist and args.full:
         # the collective alone (outside the timed region): K all-gathers of the packed maps, barrier-bracketed
         barrier()
         tg = time.perf_counter()
@@ -867,13 +920,13 @@ def main() -> None:
         barrier()
         gather_ms = 1e3 * (time.perf_counter() - tg) / args.steps
 
-    clocks = clocks_under_load(step) if (rank == 0 and not use_dist) else None
+    clocks = clocks_under_load(step) if (args.full and rank == 0 and not use_dist) else None
 
     # supplementary: the same K steps dealt alternately to TWO engine handles on two HIP streams (each step is still one whole
     # batch of B crops through one handle; consecutive independent batches overlap, so one batch's kernel tails are filled by
     # the other's kernels).  What a serving loop with two batches in flight gets; never `value`.
     elapsed_pipe = None
-    if not args.no_pipelined and not use_dist:
+    if args.full and not args.no_pipelined and not use_dist:
         net_b = FEARNetHIP(DEFAULT_WEIGHTS, device=local_rank, max_batch=args.max_batch)
         net_b.set_math(args.math)
         bbox_b, cls_b = torch.empty_like(bbox), torch.empty_like(cls)
@@ -900,7 +953,7 @@ def main() -> None:
     # handle, joined before the call returns to its stream; bit-identical maps — tests/test_gpu_parity.py).  A serving option: `value`
     # stays the single-stream number so that every per-kernel figure of this line is a full-grid launch.
     elapsed_split = None
-    if not args.no_pipelined and not use_dist:
+    if args.full and not args.no_pipelined and not use_dist:
         net.set_split_streams(True)
         for _ in range(max(4, args.warmup // 2)):
             net.track_maps(search, tmpl_feats, out=(bbox, cls))
@@ -915,7 +968,7 @@ def main() -> None:
     # the same K steps in the other arithmetic mode (supplementary number, same protocol)
     other = 1 - args.math
     elapsed_other = None
-    if not args.no_other_math:
+    if args.full and not args.no_other_math:
         net.set_math(other)
         for _ in range(max(3, args.warmup // 2)):
             step()
@@ -947,28 +1000,29 @@ def main() -> None:
     if rank == 0:
         total_crops = world * B * args.steps
         value = total_crops / elapsed
-        name, fl, by = plan[dom]
-        avg_ms = dom_ms / max(dom_cnt, 1)
-        crops_per_launch = B * args.steps * len(dom_ops) / max(dom_cnt, 1)
-        ai = fl / by
-        ridge = PEAK_FP32_MFMA_TFLOPS * 1e12 / (PEAK_HBM_GBS * 1e9)
-        if ai >= ridge:
-            achieved = fl * crops_per_launch / (avg_ms * 1e-3) / 1e12
-            roof = {"bound": "mfma", "achieved": achieved, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                    "frac": achieved / PEAK_FP32_MFMA_TFLOPS}
-        else:
-            achieved = by * crops_per_launch / (avg_ms * 1e-3) / 1e9
-            roof = {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                    "frac": achieved / PEAK_HBM_GBS}
-        traffic, traffic_file = pmc_traffic(name)
-        roof.update({"traffic": traffic, "traffic_source": (f"offline PMC: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                                            f"command, committed as {traffic_file} (not measured in this run)")
-                                                           if traffic is not None else None,
-                     "kernel": name, "avg_launch_ms": avg_ms, "launches": dom_cnt,
-                     "launches_per_step": len(dom_ops) * max(1, -(-B // args.max_batch)),
-                     "share_of_step": group_time[dom_name] / max(sum(op_time), 1e-12),
-                     "whole_path_tflops": value * FLOPS_PER_CROP / 1e12 / world,
-                     "whole_path_frac_of_fp32_peak": value * FLOPS_PER_CROP / 1e12 / world / PEAK_FP32_MFMA_TFLOPS})
+        if args.full:
+            name, fl, by = plan[dom]
+            avg_ms = dom_ms / max(dom_cnt, 1)
+            crops_per_launch = B * args.steps * len(dom_ops) / max(dom_cnt, 1)
+            ai = fl / by
+            ridge = PEAK_FP32_MFMA_TFLOPS * 1e12 / (PEAK_HBM_GBS * 1e9)
+            if ai >= ridge:
+                achieved = fl * crops_per_launch / (avg_ms * 1e-3) / 1e12
+                roof = {"bound": "mfma", "achieved": achieved, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                        "frac": achieved / PEAK_FP32_MFMA_TFLOPS}
+            else:
+                achieved = by * crops_per_launch / (avg_ms * 1e-3) / 1e9
+                roof = {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                        "frac": achieved / PEAK_HBM_GBS}
+            traffic, traffic_file = pmc_traffic(name)
+            roof.update({"traffic": traffic, "traffic_source": (f"offline PMC: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                                                f"command, committed as {traffic_file} (not measured in this run)")
+                                                               if traffic is not None else None,
+                         "kernel": name, "avg_launch_ms": avg_ms, "launches": dom_cnt,
+                         "launches_per_step": len(dom_ops) * max(1, -(-B // args.max_batch)),
+                         "share_of_step": group_time[dom_name] / max(sum(op_time), 1e-12),
+                         "whole_path_tflops": value * FLOPS_PER_CROP / 1e12 / world,
+                         "whole_path_frac_of_fp32_peak": value * FLOPS_PER_CROP / 1e12 / world / PEAK_FP32_MFMA_TFLOPS})
         out = {
             "metric": "search-region crops/sec (FEAR-XS 256x256)",
             "value": value,
@@ -989,8 +1043,9 @@ def main() -> None:
                        "math": ("fp32 MFMA (v_mfma_f32_16x16x4_f32), exact fp32" if args.math == 0 else
                                 "pointwise convs of the fused 16x16 blocks: fp32 activations split into fp16 hi+lo, exact-fp16 "
                                 "weights, v_mfma_f32_16x16x32_f16, fp32 accumulate; everything else fp32")},
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roof
         if elapsed_other is not None:
             out["other_math_mode"] = {
                 "math": ("fp16 hi+lo split activations x exact-fp16 weights on the f16 matrix pipe, fp32 accumulate "
@@ -1015,22 +1070,23 @@ def main() -> None:
             out["config5_train_step_data_parallel"] = ddp_train
         if use_dist:
             out["collective"] = {"backend": "nccl (RCCL)", "ranks": dist.get_world_size(), "op": "all_gather_into_tensor",
-                                 "bytes_per_rank": B * 5 * 16 * 16 * 4, "ms_alone": gather_ms,
-                                 "overlapped_with_next_batch": overlap is not None}
-        if not args.no_cpu_baseline and world == 1:
+                                 "bytes_per_rank": B * 5 * 16 * 16 * 4, "overlapped_with_next_batch": overlap is not None}
+            if gather_ms is not None:
+                out["collective"]["ms_alone"] = gather_ms
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(search_u8, tmpl_u8, DEFAULT_WEIGHTS)
         # (configs[4] before configs[3]: measured order dependence — after the FEAR-M leg AND the two-handle / other-mode legs of this
         #  process the same training step runs 11 % slower (18.7 vs 16.7 ms; neither a cool-down pause nor the host explains it: host issue
         #  10 ms either way), after either of them alone it does not; FEAR-M's own number does not depend on the order)
-        if not args.no_train and world == 1 and not use_dist:
+        if args.full and not args.no_train and world == 1 and not use_dist:
             out["config5_train_step"] = config5_train_step(dev)
             torch.cuda.empty_cache()
-        if not args.no_fear_m and world == 1 and not use_dist:
+        if args.full and not args.no_fear_m and world == 1 and not use_dist:
             del net, search, tmpl_feats
             torch.cuda.empty_cache()
             out["config4_fear_m_bf16"] = config4_fear_m(dev)
             net = search = tmpl_feats = None
-        if not args.no_latency and world == 1 and not use_dist:
+        if args.full and not args.no_latency and world == 1 and not use_dist:
             del net, search, tmpl_feats
             torch.cuda.empty_cache()
             out["latency_batch1"] = latency_batch1(DEFAULT_WEIGHTS)
