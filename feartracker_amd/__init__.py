@@ -1,16 +1,18 @@
 """feartracker_amd — MI355X-native FEAR per-frame inference path.
 
-Hot path only: `FEARTracker.initialize()/update()` on top of
+Hot path only: `FEARTracker.initialize()/update()` — and `FEARMultiTracker` for many targets per frame — on top of
 `FEARNetHIP.get_features()/track()`, whose arithmetic runs in hand-written gfx950 HIP kernels
 behind the C ABI of include/fear_hip.h.
 """
 from .constants import DEFAULT_TRACKING_CONFIG, TARGET_CLASSIFICATION_KEY, TARGET_REGRESSION_LABEL_KEY
 from .box_coder import FEARBoxCoder, TrackerDecodeResult, TrackerEncodeResult
 from .tracker import FEARTracker, Tracker, TrackingState
+from .multi_tracker import FEARMultiTracker, PendingBoxes
 from .hip_backend import FEARNetHIP, FearError, load_library, DEFAULT_WEIGHTS, LIB_PATH
 
 __all__ = [
     "DEFAULT_TRACKING_CONFIG", "TARGET_CLASSIFICATION_KEY", "TARGET_REGRESSION_LABEL_KEY",
     "FEARBoxCoder", "TrackerDecodeResult", "TrackerEncodeResult", "FEARTracker", "Tracker", "TrackingState",
+    "FEARMultiTracker", "PendingBoxes",
     "FEARNetHIP", "FearError", "load_library", "DEFAULT_WEIGHTS", "LIB_PATH",
 ]

@@ -2259,24 +2259,62 @@ int fear_normalize_u8(fear_handle* h, const uint8_t* u8, int n, int hw, float* o
     return FEAR_OK;
 }
 
+// one launch of crop_resize_normalize_kernel: the one-frame entry and the frame-table entry differ only in where a crop's frame comes from
+static int launch_crop(fear_handle* h, CropArgs a, void* stream) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    for (int c = 0; c < 3; ++c) {
+        a.mean[c] = mean[c] * 255.0f;
+        a.inv_std[c] = 1.0f / (stdv[c] * 255.0f);
+    }
+    const long total = (long)a.n * a.S * a.S;
+    hipLaunchKernelGGL(crop_resize_normalize_kernel, dim3((total + 255) / 256), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), a);
+    HIP_TRY(h, hipGetLastError());
+    return FEAR_OK;
+}
+
 int fear_crop_normalize(fear_handle* h, const uint8_t* frame_u8, int frame_h, int frame_w, const int32_t* ctx_xywh,
                         const uint8_t* pad_rgb, int n, int out_hw, float* out, void* stream) {
     if (!h) return FEAR_ERR_NULL;
     if (n < 0 || frame_h < 1 || frame_w < 1 || out_hw < 1 || out_hw > 4096) return FEAR_ERR_SHAPE;
     if (n == 0) return FEAR_OK;
     if (!frame_u8 || !ctx_xywh || !pad_rgb || !out) return FEAR_ERR_NULL;
-    HIP_TRY(h, hipSetDevice(h->device));
     CropArgs a{};
-    a.frame = frame_u8; a.ctx = ctx_xywh; a.pad = pad_rgb; a.out = out;
-    a.H = frame_h; a.W = frame_w; a.S = out_hw; a.n = n;
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    for (int c = 0; c < 3; ++c) {
-        a.mean[c] = mean[c] * 255.0f;
-        a.inv_std[c] = 1.0f / (stdv[c] * 255.0f);
-    }
-    const long total = (long)n * out_hw * out_hw;
-    hipLaunchKernelGGL(crop_resize_normalize_kernel, dim3((total + 255) / 256), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), a);
+    a.one = CropFrame{frame_u8, frame_h, frame_w};
+    a.ctx = ctx_xywh; a.pad = pad_rgb; a.out = out;
+    a.S = out_hw; a.n = n;
+    return launch_crop(h, a, stream);
+}
+
+int fear_crop_normalize_frames(fear_handle* h, const fear_frame* frames, int n_frames, const int32_t* frame_idx,
+                               const int32_t* ctx_xywh, const uint8_t* pad_rgb, int n, int out_hw, float* out, void* stream) {
+    static_assert(sizeof(fear_frame) == sizeof(CropFrame) && offsetof(fear_frame, h) == offsetof(CropFrame, H) &&
+                  offsetof(fear_frame, w) == offsetof(CropFrame, W), "fear_frame and CropFrame must share one layout");
+    if (!h) return FEAR_ERR_NULL;
+    if (n < 0 || n_frames < 1 || out_hw < 1 || out_hw > 4096) return FEAR_ERR_SHAPE;
+    if (n == 0) return FEAR_OK;
+    if (!frames || !frame_idx || !ctx_xywh || !pad_rgb || !out) return FEAR_ERR_NULL;
+    CropArgs a{};
+    a.frames = reinterpret_cast<const CropFrame*>(frames);
+    a.frame_idx = frame_idx; a.n_frames = n_frames;
+    a.ctx = ctx_xywh; a.pad = pad_rgb; a.out = out;
+    a.S = out_hw; a.n = n;
+    return launch_crop(h, a, stream);
+}
+
+int fear_tracker_step(fear_handle* h, const float* cls, const float* bbox, int n, const int32_t* frame_hw, int32_t* box_xywh,
+                      int32_t* ctx_xywh, double* prev_size, int smooth, const double* window, double penalty_k,
+                      double window_influence, double lr, int score_size, int total_stride, int instance_size,
+                      double search_context, double* xywh, float* score, void* stream) {
+    if (!h) return FEAR_ERR_NULL;
+    if (n < 0 || score_size < 1 || score_size > 64 || instance_size < 1) return FEAR_ERR_SHAPE;
+    if (n == 0) return FEAR_OK;
+    if (!cls || !bbox || !frame_hw || !box_xywh || !ctx_xywh || !prev_size || !score || (smooth && !window)) return FEAR_ERR_NULL;
+    HIP_TRY(h, hipSetDevice(h->device));
+    TrackerStepArgs a{cls, bbox, frame_hw, box_xywh, ctx_xywh, prev_size, window, xywh, score, n, score_size, total_stride,
+                      instance_size, smooth ? 1 : 0, penalty_k, window_influence, lr, search_context};
+    hipLaunchKernelGGL(tracker_step_kernel, dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream), a);
     HIP_TRY(h, hipGetLastError());
     return FEAR_OK;
 }

@@ -13,6 +13,7 @@
 //   pw_small_kernel    1x1 conv with Cout<=4 (+exp), NCHW out           (bbox_pred / cls_pred, blocks.py:167-168,186-192)
 //   decode_kernel      sigmoid + arg-max + ltrb->xywh                   (FEARBoxCoder.decode, dataset/box_coder.py:75-107)
 //   decode_smooth_kernel  the smooth=True post-processing              (Tracker._postprocess, base_tracker.py:149-205)
+//   tracker_step_kernel   decode + rescale + clamp + next crop geometry  (FEARTracker.update after net.track; multi_tracker.py)
 //   normalize_kernel   uint8 HWC -> normalised fp32 NCHW                (Tracker._preprocess_image, base_tracker.py:97-103)
 #pragma once
 #include <type_traits>
@@ -478,11 +479,18 @@ struct DecodeArgs {
     int n, S, stride, instance;
 };
 
-__global__ __launch_bounds__(64) void decode_kernel(DecodeArgs a) {
-    const int crop = blockIdx.x;
+// The decode of one crop's maps, shared by decode_kernel, decode_smooth_kernel and tracker_step_kernel (one wave per crop; every
+// lane returns the same result).  x0 / y0 / w / h are the box in search-crop pixels as the reference returns it (smooth: the
+// smoothed size), score = sigmoid(cls) at the arg-max cell.
+struct Decoded {
+    int r, col;
+    double x0, y0, w, h;
+    float score;
+};
+
+__device__ __forceinline__ Decoded decode_wave(const float* c, const float* bb, int S, int stride, int instance) {
     const int lane = threadIdx.x;
-    const int cells = a.S * a.S;
-    const float* c = a.cls + (long)crop * cells;
+    const int cells = S * S;
     float best = -1.f;
     int best_i = 0x7fffffff;
     for (int i = lane; i < cells; i += 64) {
@@ -495,22 +503,36 @@ __global__ __launch_bounds__(64) void decode_kernel(DecodeArgs a) {
         const int oi = __shfl_xor(best_i, off, 64);
         if (ob > best || (ob == best && oi < best_i)) { best = ob; best_i = oi; }
     }
-    if (lane == 0) {
-        // a map of NaNs never satisfies `s > best`: stay inside the map (cell 0 = torch.argmax's answer for an all-NaN map)
-        if ((unsigned)best_i >= (unsigned)cells) best_i = 0;
-        const int r = best_i / a.S, col = best_i % a.S;
-        const double gx = (double)(col - a.S / 2) * a.stride + a.instance / 2;
-        const double gy = (double)(r - a.S / 2) * a.stride + a.instance / 2;
-        const float* bb = a.bbox + (long)crop * 4 * cells + best_i;
-        const double x0 = gx - (double)bb[0], y0 = gy - (double)bb[cells];
-        const double x1 = gx + (double)bb[2 * cells], y1 = gy + (double)bb[3 * cells];
-        a.rc[crop * 2] = r;
-        a.rc[crop * 2 + 1] = col;
-        a.xywh[crop * 4 + 0] = x0;
-        a.xywh[crop * 4 + 1] = y0;
-        a.xywh[crop * 4 + 2] = x1 - x0;
-        a.xywh[crop * 4 + 3] = y1 - y0;
-        a.score[crop] = best;
+    // a map of NaNs never satisfies `s > best`: stay inside the map (cell 0 = torch.argmax's answer for an all-NaN map)
+    if ((unsigned)best_i >= (unsigned)cells) best_i = 0;
+    Decoded d;
+    d.r = best_i / S;
+    d.col = best_i % S;
+    const double gx = (double)(d.col - S / 2) * stride + instance / 2;
+    const double gy = (double)(d.r - S / 2) * stride + instance / 2;
+    const float* b = bb + best_i;
+    const double x0 = gx - (double)b[0], y0 = gy - (double)b[cells];
+    const double x1 = gx + (double)b[2 * cells], y1 = gy + (double)b[3 * cells];
+    d.x0 = x0;
+    d.y0 = y0;
+    d.w = x1 - x0;
+    d.h = y1 - y0;
+    d.score = best;
+    return d;
+}
+
+__global__ __launch_bounds__(64) void decode_kernel(DecodeArgs a) {
+    const int crop = blockIdx.x;
+    const int cells = a.S * a.S;
+    const Decoded d = decode_wave(a.cls + (long)crop * cells, a.bbox + (long)crop * 4 * cells, a.S, a.stride, a.instance);
+    if (threadIdx.x == 0) {
+        a.rc[crop * 2] = d.r;
+        a.rc[crop * 2 + 1] = d.col;
+        a.xywh[crop * 4 + 0] = d.x0;
+        a.xywh[crop * 4 + 1] = d.y0;
+        a.xywh[crop * 4 + 2] = d.w;
+        a.xywh[crop * 4 + 3] = d.h;
+        a.score[crop] = d.score;
     }
 }
 
@@ -577,24 +599,22 @@ __device__ __forceinline__ double smooth_penalty(double w, double h, double pw, 
     return exp(-(r_c * s_c - 1.0) * penalty_k);
 }
 
-__global__ __launch_bounds__(64) void decode_smooth_kernel(DecodeSmoothArgs a) {
-    const int crop = blockIdx.x;
+__device__ __forceinline__ Decoded decode_smooth_wave(const float* c, const float* bb, double pw, double ph, const double* window,
+                                                      int S, int stride, int instance, double penalty_k, double window_influence,
+                                                      double lr_cfg) {
     const int lane = threadIdx.x;
-    const int cells = a.S * a.S;
-    const float* c = a.cls + (long)crop * cells;
-    const float* bb = a.bbox + (long)crop * 4 * cells;
-    const double pw = a.prev_size[crop * 2], ph = a.prev_size[crop * 2 + 1];
+    const int cells = S * S;
     double best = -1.0;
     int best_i = 0x7fffffff;
     for (int i = lane; i < cells; i += 64) {
-        const int r = i / a.S, col = i % a.S;
-        const double gx = (double)(col - a.S / 2) * a.stride + a.instance / 2;
-        const double gy = (double)(r - a.S / 2) * a.stride + a.instance / 2;
+        const int r = i / S, col = i % S;
+        const double gx = (double)(col - S / 2) * stride + instance / 2;
+        const double gy = (double)(r - S / 2) * stride + instance / 2;
         const double x0 = gx - (double)bb[i], y0 = gy - (double)bb[cells + i];
         const double x1 = gx + (double)bb[2 * cells + i], y1 = gy + (double)bb[3 * cells + i];
-        const double pen = smooth_penalty(x1 - x0, y1 - y0, pw, ph, a.penalty_k);
+        const double pen = smooth_penalty(x1 - x0, y1 - y0, pw, ph, penalty_k);
         const float sg = 1.f / (1.f + expf(-c[i]));
-        const double ps = pen * (double)sg * (1.0 - a.window_influence) + a.window[i] * a.window_influence;
+        const double ps = pen * (double)sg * (1.0 - window_influence) + window[i] * window_influence;
         if (ps > best) { best = ps; best_i = i; }       // strictly greater keeps the first index per lane
     }
 #pragma unroll
@@ -603,29 +623,133 @@ __global__ __launch_bounds__(64) void decode_smooth_kernel(DecodeSmoothArgs a) {
         const int oi = __shfl_xor(best_i, off, 64);
         if (ob > best || (ob == best && oi < best_i)) { best = ob; best_i = oi; }
     }
-    if (lane == 0) {
-        // a map of NaNs never satisfies `s > best`: stay inside the map (cell 0 = torch.argmax's answer for an all-NaN map)
-        if ((unsigned)best_i >= (unsigned)cells) best_i = 0;
-        const int r = best_i / a.S, col = best_i % a.S;
-        const double gx = (double)(col - a.S / 2) * a.stride + a.instance / 2;
-        const double gy = (double)(r - a.S / 2) * a.stride + a.instance / 2;
-        const double x0 = gx - (double)bb[best_i], y0 = gy - (double)bb[cells + best_i];
-        const double x1 = gx + (double)bb[2 * cells + best_i], y1 = gy + (double)bb[3 * cells + best_i];
-        const double w = x1 - x0, h = y1 - y0;
-        const double pen = smooth_penalty(w, h, pw, ph, a.penalty_k);
-        const float sg = 1.f / (1.f + expf(-c[best_i]));
-        // lr = fp32(fp32(penalty) * fp32(score)) * fp32(lr), each product rounded to fp32 (base_tracker.py:159)
-        const float lr32 = ((float)pen * sg) * (float)a.lr;
-        const double lr = (double)lr32;
-        // _smooth_size (base_tracker.py:126-139), evaluated as written there
-        const double sw = w * lr, sh = h * lr, qw = pw * (1.0 - lr), qh = ph * (1.0 - lr);
-        a.rc[crop * 2] = r;
-        a.rc[crop * 2 + 1] = col;
-        a.xywh[crop * 4 + 0] = x0;
-        a.xywh[crop * 4 + 1] = y0;
-        a.xywh[crop * 4 + 2] = qw + lr * (sw + qw);
-        a.xywh[crop * 4 + 3] = qh + lr * (sh + qh);
-        a.score[crop] = sg;
+    // a map of NaNs never satisfies `s > best`: stay inside the map (cell 0 = torch.argmax's answer for an all-NaN map)
+    if ((unsigned)best_i >= (unsigned)cells) best_i = 0;
+    Decoded d;
+    d.r = best_i / S;
+    d.col = best_i % S;
+    const double gx = (double)(d.col - S / 2) * stride + instance / 2;
+    const double gy = (double)(d.r - S / 2) * stride + instance / 2;
+    const double x0 = gx - (double)bb[best_i], y0 = gy - (double)bb[cells + best_i];
+    const double x1 = gx + (double)bb[2 * cells + best_i], y1 = gy + (double)bb[3 * cells + best_i];
+    const double w = x1 - x0, h = y1 - y0;
+    const double pen = smooth_penalty(w, h, pw, ph, penalty_k);
+    const float sg = 1.f / (1.f + expf(-c[best_i]));
+    // lr = fp32(fp32(penalty) * fp32(score)) * fp32(lr), each product rounded to fp32 (base_tracker.py:159)
+    const float lr32 = ((float)pen * sg) * (float)lr_cfg;
+    const double lr = (double)lr32;
+    // _smooth_size (base_tracker.py:126-139), evaluated as written there
+    const double sw = w * lr, sh = h * lr, qw = pw * (1.0 - lr), qh = ph * (1.0 - lr);
+    d.x0 = x0;
+    d.y0 = y0;
+    d.w = qw + lr * (sw + qw);
+    d.h = qh + lr * (sh + qh);
+    d.score = sg;
+    return d;
+}
+
+__global__ __launch_bounds__(64) void decode_smooth_kernel(DecodeSmoothArgs a) {
+    const int crop = blockIdx.x;
+    const int cells = a.S * a.S;
+    const Decoded d = decode_smooth_wave(a.cls + (long)crop * cells, a.bbox + (long)crop * 4 * cells, a.prev_size[crop * 2],
+                                         a.prev_size[crop * 2 + 1], a.window, a.S, a.stride, a.instance, a.penalty_k,
+                                         a.window_influence, a.lr);
+    if (threadIdx.x == 0) {
+        a.rc[crop * 2] = d.r;
+        a.rc[crop * 2 + 1] = d.col;
+        a.xywh[crop * 4 + 0] = d.x0;
+        a.xywh[crop * 4 + 1] = d.y0;
+        a.xywh[crop * 4 + 2] = d.w;
+        a.xywh[crop * 4 + 3] = d.h;
+        a.score[crop] = d.score;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// FEARTracker.update after net.track, for n targets at once (feartracker_amd/tracker.py; reference base_tracker.py:83-90,
+// utils.py:29-71, 202-212): decode (plain or smooth, the helpers above), _rescale_bbox into the frame of the context the crop was
+// cut with, clamp_bbox to the target's frame, then crop_geometry of the NEXT frame around that box — its context box and the box's
+// size inside the next search crop (the smooth branch's prev_size) are written back over the inputs, so that the next crop and
+// decode read them without the host.  One wave per target; lane 0 does the geometry.  Every float64 product, quotient and sum is
+// rounded on its own (__dmul_rn / __ddiv_rn / __dadd_rn: hipcc would otherwise contract a * b + c into one fma, which Python
+// never does); integer steps in 64-bit, as Python's unbounded ints.
+struct TrackerStepArgs {
+    const float* cls;        // [n][S*S] logits
+    const float* bbox;       // [n][4][S*S] l, t, r, b
+    const int32_t* frame_hw; // [n][2] H, W of each target's frame
+    int32_t* box;            // [n][4] out: the target's box in this frame
+    int32_t* ctx;            // [n][4] in: the context this frame was cropped with; out: the next frame's
+    double* prev_size;       // [n][2] in: size in this crop (smooth); out: size in the next crop
+    const double* window;    // [S*S] (smooth only)
+    double* xywh;            // [n][4] decoded box in search-crop pixels, or nullptr
+    float* score;            // [n]
+    int n, S, stride, instance, smooth;
+    double penalty_k, window_influence, lr, search_context;
+};
+
+// Python's round() of a float64 (half to even = rint in the default rounding mode), clamped far outside any frame first so that
+// the conversion is defined for every input (Python itself raises on inf / nan)
+__device__ __forceinline__ long long py_round(double v) { return (long long)rint(fmin(fmax(v, -1e15), 1e15)); }
+
+// ensure_bbox_boundaries (geometry.py): the box intersected with an H x W image
+__device__ __forceinline__ void ensure_boundaries(long long& x, long long& y, long long& w, long long& h, long long H, long long W) {
+    const long long x_lo = min(max(0LL, x), W), y_lo = min(max(0LL, y), H);
+    const long long x_hi = min(max(0LL, x_lo + w), W), y_hi = min(max(0LL, y_lo + h), H);
+    x = x_lo; y = y_lo; w = x_hi - x_lo; h = y_hi - y_lo;
+}
+
+__global__ __launch_bounds__(64) void tracker_step_kernel(TrackerStepArgs a) {
+    const int t = blockIdx.x;
+    const int cells = a.S * a.S;
+    const float* c = a.cls + (long)t * cells;
+    const float* bb = a.bbox + (long)t * 4 * cells;
+    const Decoded d = a.smooth ? decode_smooth_wave(c, bb, a.prev_size[t * 2], a.prev_size[t * 2 + 1], a.window, a.S, a.stride,
+                                                    a.instance, a.penalty_k, a.window_influence, a.lr)
+                               : decode_wave(c, bb, a.S, a.stride, a.instance);
+    if (threadIdx.x != 0) return;
+    const long long H = a.frame_hw[t * 2], W = a.frame_hw[t * 2 + 1];
+    const long long cx = a.ctx[t * 4], cy = a.ctx[t * 4 + 1], cw = a.ctx[t * 4 + 2], ch = a.ctx[t * 4 + 3];
+    // _rescale_bbox: separate scales for x / y, round half to even, minimum side 3
+    const double sx = __ddiv_rn((double)cw, (double)a.instance), sy = __ddiv_rn((double)ch, (double)a.instance);
+    long long x = py_round(__dadd_rn(__dmul_rn(d.x0, sx), (double)cx));
+    long long y = py_round(__dadd_rn(__dmul_rn(d.y0, sy), (double)cy));
+    long long w = max(3LL, py_round(__dmul_rn(d.w, sx)));
+    long long h = max(3LL, py_round(__dmul_rn(d.h, sy)));
+    // clamp_bbox: clip to the frame, then a minimum side of 3 with the origin shifted back inside
+    ensure_boundaries(x, y, w, h, H, W);
+    if (w < 3) { w = 3; x -= max(0LL, x + w - W); }
+    if (h < 3) { h = 3; y -= max(0LL, y + h - H); }
+    // crop_geometry(., box, instance, search_context): extend_bbox (float64, truncated toward zero to int32) ...
+    const double o = a.search_context, grow = __dadd_rn(__dadd_rn(1.0, o), o);
+    const long long nx = (int)__dsub_rn((double)x, __dmul_rn((double)w, o));
+    const long long ny = (int)__dsub_rn((double)y, __dmul_rn((double)h, o));
+    const long long nw = (int)__dmul_rn((double)w, grow);
+    const long long nh = (int)__dmul_rn((double)h, grow);
+    // ... the box inside that context, then albumentations' resize of a coco box to instance x instance (_resized_coco_box)
+    long long bx = x - nx, by = y - ny, bw = w, bh = h;
+    ensure_boundaries(bx, by, bw, bh, nh, nw);
+    auto unit = [](double v) { return fmin(fmax(v, 0.0), 1.0); };
+    const double size = (double)a.instance;
+    const double x_min = __dmul_rn(unit(__ddiv_rn((double)bx, (double)nw)), size);
+    const double y_min = __dmul_rn(unit(__ddiv_rn((double)by, (double)nh)), size);
+    const double x_max = __dmul_rn(unit(__ddiv_rn((double)(bx + bw), (double)nw)), size);
+    const double y_max = __dmul_rn(unit(__ddiv_rn((double)(by + bh), (double)nh)), size);
+    a.box[t * 4 + 0] = (int32_t)x;
+    a.box[t * 4 + 1] = (int32_t)y;
+    a.box[t * 4 + 2] = (int32_t)w;
+    a.box[t * 4 + 3] = (int32_t)h;
+    a.ctx[t * 4 + 0] = (int32_t)nx;
+    a.ctx[t * 4 + 1] = (int32_t)ny;
+    a.ctx[t * 4 + 2] = (int32_t)nw;
+    a.ctx[t * 4 + 3] = (int32_t)nh;
+    a.prev_size[t * 2] = __dsub_rn(x_max, x_min);
+    a.prev_size[t * 2 + 1] = __dsub_rn(y_max, y_min);
+    a.score[t] = d.score;
+    if (a.xywh) {
+        a.xywh[t * 4 + 0] = d.x0;
+        a.xywh[t * 4 + 1] = d.y0;
+        a.xywh[t * 4 + 2] = d.w;
+        a.xywh[t * 4 + 3] = d.h;
     }
 }
 
@@ -660,12 +784,19 @@ __global__ __launch_bounds__(256) void normalize_kernel(NormArgs a) {
 // and tracker/base_tracker.py:70-103.  Bit-exact against the host restatement feartracker_amd/geometry.py and against the
 // independent table-driven restatement of resize.cpp the tests carry, cv_ref.c (crop parity against real cv2 is unpinned in this image, see
 // DESIGN.md).  One thread per output pixel.
+struct CropFrame {          // one frame of a crop launch: the layout of fear_frame (include/fear_hip.h)
+    const uint8_t* data;    // [H][W][3] RGB
+    int32_t H, W;
+};
+
 struct CropArgs {
-    const uint8_t* frame;   // [H][W][3] RGB
-    const int* ctx;         // [n][4] context box x, y, w, h (frame coordinates, may leave the frame)
-    const uint8_t* pad;     // [n][3] border colour (already saturate-cast)
-    float* out;             // [n][3][S][S]
-    int H, W, S, n;
+    const CropFrame* frames;  // [n_frames] device table, or nullptr: every crop reads `one`
+    const int* frame_idx;     // [n] the frame each crop reads (index into `frames`); an index outside the table reads no pixel
+    CropFrame one;            // the frame of a one-frame launch (fear_crop_normalize)
+    const int* ctx;           // [n][4] context box x, y, w, h (frame coordinates, may leave the frame)
+    const uint8_t* pad;       // [n][3] border colour (already saturate-cast)
+    float* out;               // [n][3][S][S]
+    int n_frames, S, n;
     float mean[3], inv_std[3];
 };
 
@@ -697,6 +828,12 @@ __global__ __launch_bounds__(256) void crop_resize_normalize_kernel(CropArgs a) 
     const int crop = p / plane, px = p % plane;
     const int dy = px / a.S, dx = px % a.S;
     const int cx = a.ctx[crop * 4], cy = a.ctx[crop * 4 + 1], cw = a.ctx[crop * 4 + 2], ch = a.ctx[crop * 4 + 3];
+    CropFrame fr = a.one;
+    if (a.frames) {
+        const int fi = a.frame_idx[crop];
+        if ((unsigned)fi < (unsigned)a.n_frames) fr = a.frames[fi];
+        else fr = CropFrame{nullptr, 0, 0};             // every sample is border colour then
+    }
     int x0, x1, ax0, ax1, y0, y1, ay0, ay1;
     linear_tap<true>(dx, a.S, cw, x0, x1, ax0, ax1);
     linear_tap<false>(dy, a.S, ch, y0, y1, ay0, ay1);
@@ -704,8 +841,8 @@ __global__ __launch_bounds__(256) void crop_resize_normalize_kernel(CropArgs a) 
     const bool half = (cw == 2 * a.S) && (ch == 2 * a.S);   // cv::resize runs an exact 2x2 decimation as the 2x2 box mean
     auto sample = [&](int sx, int sy, int c) -> int {
         const int fx = cx + sx, fy = cy + sy;
-        if (fx < 0 || fx >= a.W || fy < 0 || fy >= a.H) return a.pad[crop * 3 + c];
-        return a.frame[((long)fy * a.W + fx) * 3 + c];
+        if (fx < 0 || fx >= fr.W || fy < 0 || fy >= fr.H) return a.pad[crop * 3 + c];
+        return fr.data[((long)fy * fr.W + fx) * 3 + c];
     };
 #pragma unroll
     for (int c = 0; c < 3; ++c) {

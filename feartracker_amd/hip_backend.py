@@ -79,6 +79,11 @@ def load_library() -> ctypes.CDLL:
     lib.fear_normalize_u8.restype = i32
     lib.fear_crop_normalize.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, f32p, vp]
     lib.fear_crop_normalize.restype = i32
+    lib.fear_crop_normalize_frames.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, f32p, vp]
+    lib.fear_crop_normalize_frames.restype = i32
+    lib.fear_tracker_step.argtypes = [vp, f32p, f32p, i32, vp, vp, vp, vp, i32, vp, f64, f64, f64, i32, i32, i32, f64, vp, f32p,
+                                      vp]
+    lib.fear_tracker_step.restype = i32
     lib.fear_set_option.argtypes = [vp, i32, i64]
     lib.fear_set_option.restype = i32
     lib.fear_get_option.argtypes = [vp, i32]
@@ -105,7 +110,7 @@ def load_library() -> ctypes.CDLL:
 
 EXPORTED_SYMBOLS = (
     "fear_create", "fear_destroy", "fear_features", "fear_track", "fear_track_packed", "fear_decode", "fear_decode_smooth", "fear_normalize_u8",
-    "fear_crop_normalize",
+    "fear_crop_normalize", "fear_crop_normalize_frames", "fear_tracker_step",
     "fear_set_option", "fear_get_option", "fear_plan_size", "fear_plan_op", "fear_profile_read",
     "fear_profile_reset", "fear_workspace_bytes", "fear_strerror", "fear_last_hip_error", "fear_version",
 )
@@ -478,6 +483,61 @@ class FEARNetHIP:
             self._check(self._lib.fear_crop_normalize(self._h, frame_ptr, rh, rw, meta_ptr, meta_ptr + n * 16, n, int(out_hw),
                                                       out.data_ptr(), self._stream()))
         return out
+
+    def frame_table(self, frames) -> torch.Tensor:
+        """The (n_frames) `fear_frame` table of include/fear_hip.h for device uint8 (H,W,3) contiguous frames, uploaded: 16 bytes
+        per frame, {data pointer, H, W}.  The frames must stay alive until the launches that read the table have run.  The table
+        goes up from pinned memory without waiting for the stream (a pageable copy would wait for all earlier work on it)."""
+        host = torch.empty((len(frames), 2), dtype=torch.int64, pin_memory=True)
+        tab = host.numpy()
+        for i, f in enumerate(frames):
+            if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or not f.is_contiguous() or f.device != self.device:
+                raise ValueError("frames must be contiguous uint8 (H,W,3) tensors on the engine's device")
+            tab[i, 0] = f.data_ptr()
+            tab[i, 1] = int(f.shape[0]) | (int(f.shape[1]) << 32)
+        return host.to(self.device, non_blocking=True)
+
+    @torch.no_grad()
+    def crop_normalize_frames(self, table: torch.Tensor, frame_idx: torch.Tensor, ctx_xywh: torch.Tensor, pad_rgb_u8: torch.Tensor,
+                              out_hw: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fear_crop_normalize_frames: crop i out of frame `frame_idx[i]` of `table` (`frame_table`); every argument a device
+        tensor — frame_idx (n,) int32, ctx_xywh (n,4) int32, pad_rgb_u8 (n,3) uint8 -> (n,3,out_hw,out_hw) fp32."""
+        n = int(frame_idx.shape[0])
+        for t, dt, shape in ((frame_idx, torch.int32, (n,)), (ctx_xywh, torch.int32, (n, 4)), (pad_rgb_u8, torch.uint8, (n, 3))):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"expected a contiguous {dt} {shape} tensor on the engine's device")
+        if out is None:
+            out = torch.empty((n, 3, out_hw, out_hw), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.fear_crop_normalize_frames(self._h, table.data_ptr(), int(table.shape[0]), frame_idx.data_ptr(),
+                                                             ctx_xywh.data_ptr(), pad_rgb_u8.data_ptr(), n, int(out_hw),
+                                                             out.data_ptr(), self._stream()))
+        return out
+
+    @torch.no_grad()
+    def tracker_step(self, cls: torch.Tensor, bbox: torch.Tensor, frame_hw: torch.Tensor, box_xywh: torch.Tensor,
+                     ctx_xywh: torch.Tensor, prev_size: torch.Tensor, score: torch.Tensor, smooth: bool, window: torch.Tensor,
+                     penalty_k: float, window_influence: float, lr: float, score_size: int = 16, total_stride: int = 16,
+                     instance_size: int = 256, search_context: float = 2.0, xywh: Optional[torch.Tensor] = None) -> None:
+        """fear_tracker_step on device tensors, IN PLACE: decode the maps of one `track_maps` call, rescale into each target's
+        context `ctx_xywh` (n,4) int32, clamp to its frame `frame_hw` (n,2) int32 -> `box_xywh` (n,4) int32, and overwrite
+        `ctx_xywh` / `prev_size` (n,2) float64 with the next frame's context and size; `score` (n,) fp32, optional `xywh` (n,4)
+        float64 = the decoded boxes.  `window` (score_size^2) float64 on the device (read when smooth)."""
+        cls = self._prep(cls, "cls")
+        bbox = self._prep(bbox, "bbox")
+        n = int(cls.shape[0])
+        for t, dt, shape in ((frame_hw, torch.int32, (n, 2)), (box_xywh, torch.int32, (n, 4)), (ctx_xywh, torch.int32, (n, 4)),
+                             (prev_size, torch.float64, (n, 2)), (score, torch.float32, (n,)),
+                             (window, torch.float64, (score_size * score_size,))) + \
+                (((xywh, torch.float64, (n, 4)),) if xywh is not None else ()):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"expected a contiguous {dt} {shape} tensor on the engine's device")
+        with torch.cuda.device(self.device):
+            self._check(self._lib.fear_tracker_step(
+                self._h, cls.data_ptr(), bbox.data_ptr(), n, frame_hw.data_ptr(), box_xywh.data_ptr(), ctx_xywh.data_ptr(),
+                prev_size.data_ptr(), 1 if smooth else 0, window.data_ptr(), float(penalty_k), float(window_influence), float(lr),
+                int(score_size), int(total_stride), int(instance_size), float(search_context),
+                xywh.data_ptr() if xywh is not None else None, score.data_ptr(), self._stream()))
 
     # ------------------------------------------------------------------ measurement
     def plan(self, hw: int = 256, with_head: bool = True):

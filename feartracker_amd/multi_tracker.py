@@ -1,0 +1,303 @@
+"""`FEARMultiTracker`: many targets per frame, one batched network pass, tracker state kept on the device.
+
+`FEARTracker` (tracker.py) follows ONE object at batch 1 and waits on the host after every frame.  This tracker follows K
+targets — K objects in one video, one object in each of K videos, or any mix — with the same per-target arithmetic and
+the same config keys (`DEFAULT_TRACKING_CONFIG`, `smooth` included), and runs a frame as
+
+    the frames up (one transfer each, on a copy stream)  ->  fear_crop_normalize_frames (K search crops, one launch)
+    ->  fear_track (K templates)  ->  fear_tracker_step (decode, rescale, clamp, next crop geometry; one launch)
+    ->  boxes and scores down (one non-blocking copy, guarded by an event)
+
+Everything frame t + 1 needs from frame t — each target's context box and previous size — stays in device tensors, so
+`submit` never synchronises (host frames and the small tables go up from pinned memory, non-blocking) and the next frame
+can be submitted before the previous result is read.  Each target's boxes equal an independent `FEARTracker` on the same
+frames (tests/test_multi_tracker.py) — frames the device path reads, see below.
+
+Targets live in "streams": `add(image, rects, stream=s)` starts targets on frame `image` of stream s, and
+`submit(images)` takes one frame (stream 0) or a sequence of frames, `images[s]` being the frame of stream s.  Frames of
+different streams may differ in size.
+
+With a model that lacks the device entry points (a CPU reference network, any torch model), or with `device_crop=False` /
+`device_postprocess=False` in the config, the tracker runs the reference-style host path instead: per target the
+`FEARTracker` crop, post-processing and geometry, around one batched `net.track`.  The path is chosen at construction;
+the device path reads what `fear_crop_normalize` reads — uint8 H x W x >= 3 frames, numpy arrays or device tensors — and
+rejects other frames (float, uint16, grey, CPU tensors) with a TypeError instead of switching paths behind the caller's
+back, where FEARTracker would track them on the host.  A tracker built with `device_crop=False` takes them.
+"""
+from __future__ import annotations
+
+from typing import Any, Dict, List, Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from .constants import TARGET_CLASSIFICATION_KEY, TARGET_REGRESSION_LABEL_KEY
+from .geometry import border_color_u8, clamp_bbox, crop_geometry, get_extended_crop
+from .tracker import FEARTracker
+
+
+class PendingBoxes:
+    """The boxes of one `submit`, possibly still being computed: `result()` waits for that frame's copy only."""
+
+    def __init__(self, ids: Sequence[int], boxes=None, scores=None, host: Optional[torch.Tensor] = None,
+                 event: Optional[torch.cuda.Event] = None) -> None:
+        self.ids = list(ids)
+        self._boxes, self._scores = boxes, scores
+        self._host, self._event = host, event
+
+    def done(self) -> bool:
+        return self._event is None or self._event.query()
+
+    def _resolve(self) -> None:
+        if self._boxes is not None:
+            return
+        k = len(self.ids)
+        if self._event is not None:
+            self._event.synchronize()
+        raw = self._host.numpy()
+        self._boxes = raw[: 16 * k].view(np.int32).reshape(k, 4).astype(np.int64)
+        self._scores = raw[16 * k: 20 * k].view(np.float32).copy()
+        self._host = self._event = None
+
+    def result(self) -> Dict[int, np.ndarray]:
+        """{target id: bbox [x, y, w, h] int ndarray} of this frame."""
+        self._resolve()
+        return {i: self._boxes[j] for j, i in enumerate(self.ids)}
+
+    def scores(self) -> Dict[int, float]:
+        """{target id: score} of this frame: sigmoid(cls) at the chosen cell, as `FEARTracker._postprocess` returns it."""
+        self._resolve()
+        return {i: float(self._scores[j]) for j, i in enumerate(self.ids)}
+
+
+class FEARMultiTracker:
+    """K targets over one or several video streams, one batched pass per frame (see the module docstring)."""
+
+    def __init__(self, model: Any, cuda_id: Union[int, str] = 0, **tracking_config: Any) -> None:
+        self.net = model
+        self.tracking_config = tracking_config
+        # the single-object tracker supplies the config-derived pieces (window, device) and is the host path's per-target unit
+        self._proto = FEARTracker(model, cuda_id, **tracking_config)
+        self.device = self._proto.device
+        cfg = tracking_config
+        self.device_path = (bool(cfg.get("device_crop", True)) and bool(cfg.get("device_postprocess", True)) and
+                            self.device.type == "cuda" and hasattr(model, "crop_normalize_frames") and
+                            hasattr(model, "tracker_step") and hasattr(model, "crop_normalize"))
+        self._next_id = 0
+        self._ids: List[int] = []
+        self._stream = np.zeros(0, dtype=np.int32)          # the stream of each target, host copy
+        if self.device_path:
+            dev = self.device
+            self._window = self._proto.window.to(dev, torch.float64).reshape(-1).contiguous()
+            self._ctx = torch.zeros((0, 4), dtype=torch.int32, device=dev)         # context box of the next crop
+            self._prev = torch.zeros((0, 2), dtype=torch.float64, device=dev)      # box size inside the next crop
+            self._pad = torch.zeros((0, 3), dtype=torch.uint8, device=dev)         # border colour (mean colour of the add frame)
+            self._fidx = torch.zeros(0, dtype=torch.int32, device=dev)             # stream of each target = frame-table index
+            self._tmpl = torch.zeros((0, 256, 8, 8), dtype=torch.float32, device=dev)
+            self._out = torch.zeros(0, dtype=torch.uint8, device=dev)              # [boxes (K,4) int32 | scores (K,) fp32]
+            self._frame_hw = None                                                    # (key, (K,2) int32 tensor)
+            self._copy_stream = None                                                 # host frame uploads (_upload_frames)
+        else:
+            self._slots: List[FEARTracker] = []
+            self._tmpl_host: Optional[torch.Tensor] = None
+
+    # ------------------------------------------------------------------ bookkeeping
+    @property
+    def ids(self) -> List[int]:
+        return list(self._ids)
+
+    def __len__(self) -> int:
+        return len(self._ids)
+
+    def _readable(self, image) -> bool:
+        """The frames fear_crop_normalize reads (FEARTracker._device_crop): uint8 H x W x >= 3, numpy or a device tensor."""
+        if isinstance(image, np.ndarray):
+            return image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] >= 3
+        return isinstance(image, torch.Tensor) and image.is_cuda and image.dtype == torch.uint8 and image.dim() == 3 and \
+            image.shape[2] >= 3
+
+    def _check_frame(self, image) -> None:
+        if self.device_path and not self._readable(image):
+            raise TypeError("the device path reads uint8 (H, W, >=3) frames (numpy arrays or device tensors); construct the tracker "
+                            "with device_crop=False for other frames")
+
+    @staticmethod
+    def _mean_color(image) -> np.ndarray:
+        """np.mean(image, axis=(0, 1)) — for a device frame the same float64 number: the integer channel sums are exact."""
+        if isinstance(image, torch.Tensor):
+            sums = image.to(torch.int64).sum(dim=(0, 1)).cpu().numpy()
+            return sums.astype(np.float64) / float(image.shape[0] * image.shape[1])
+        return np.mean(image, axis=(0, 1))
+
+    def _to_device(self, arr: np.ndarray) -> torch.Tensor:
+        """A host array on the device without waiting for the stream: staged in pinned memory, copied non-blocking (a pageable
+        copy waits for all earlier work on the stream — the whole previous frame).  torch's pinned allocator keeps the staging
+        block until the copy has run."""
+        pinned = torch.empty(arr.shape, dtype=getattr(torch, arr.dtype.name), pin_memory=True)
+        np.copyto(pinned.numpy(), arr)
+        return pinned.to(self.device, non_blocking=True)
+
+    def _upload(self, image) -> torch.Tensor:
+        """A frame as the contiguous device uint8 (H, W, 3) tensor the crop kernel reads: host frames go up whole, in one
+        non-blocking transfer; device frames are used in place."""
+        if isinstance(image, torch.Tensor):
+            return image[:, :, :3].to(self.device).contiguous()
+        return self._to_device(image[:, :, :3])
+
+    def _upload_frames(self, frames) -> List[torch.Tensor]:
+        """The frames of one submit on the device.  Host frames go up on a copy stream of the tracker's own, so that the copy of
+        frame t + 1 runs while frame t's kernels do (on the caller's stream it would wait for them); the caller's stream waits
+        for the copies through an event.  Device frames stay on the caller's stream, where they may have been produced."""
+        main = torch.cuda.current_stream(self.device)
+        out: List[Optional[torch.Tensor]] = [f if isinstance(f, torch.Tensor) else None for f in frames]
+        if any(f is None for f in out):
+            if self._copy_stream is None:
+                self._copy_stream = torch.cuda.Stream(self.device)
+            with torch.cuda.stream(self._copy_stream):
+                for i, f in enumerate(frames):
+                    if out[i] is None:
+                        out[i] = self._upload(f)
+            done = torch.cuda.Event()
+            done.record(self._copy_stream)
+            main.wait_event(done)
+            for i, f in enumerate(frames):
+                if not isinstance(f, torch.Tensor):
+                    out[i].record_stream(main)          # allocated on the copy stream, read on the caller's
+        return [self._upload(f) if isinstance(f, torch.Tensor) else d for f, d in zip(frames, out)]
+
+    # ------------------------------------------------------------------ targets
+    def add(self, image, rects, stream: int = 0) -> List[int]:
+        """Start tracking the [x, y, w, h] boxes `rects` ((4,) or (n, 4)) on `image`, the current frame of stream `stream`.
+        Per target what `FEARTracker.initialize` does (clamp_bbox, the frame's mean colour, the template), with one template
+        crop and one `get_features` for all the rects of the call.  Returns the new targets' ids.  Unlike `submit`, `add` may
+        wait for the stream (the template crop's upload, the mean colour of a device frame)."""
+        cfg = self.tracking_config
+        self._check_frame(image)
+        rects = np.asarray(rects).reshape(-1, 4)
+        n = rects.shape[0]
+        if n == 0:
+            return []
+        if int(stream) < 0:
+            raise ValueError("stream must be >= 0")
+        shape = tuple(image.shape)
+        mean = self._mean_color(image)
+        boxes = [clamp_bbox(r, shape) for r in rects]
+        new_ids = list(range(self._next_id, self._next_id + n))
+        if self.device_path:
+            dev = self.device
+            tctx = np.stack([crop_geometry(shape, b, cfg["template_size"], cfg["template_bbox_offset"])[0] for b in boxes])
+            pad = np.tile(border_color_u8(mean), (n, 1))
+            z = self.net.get_features(self.net.crop_normalize(image[:, :, :3], tctx, pad, cfg["template_size"]))
+            geo = [crop_geometry(shape, b, cfg["instance_size"], cfg["search_context"]) for b in boxes]
+            ctx = np.stack([g[0] for g in geo]).astype(np.int32)
+            prev = np.stack([np.asarray(g[1][2:], dtype=np.float64) for g in geo])
+            self._ctx = torch.cat([self._ctx, torch.from_numpy(ctx).to(dev)])
+            self._prev = torch.cat([self._prev, torch.from_numpy(prev).to(dev)])
+            self._pad = torch.cat([self._pad, torch.from_numpy(pad).to(dev)])
+            self._fidx = torch.cat([self._fidx, torch.full((n,), int(stream), dtype=torch.int32, device=dev)])
+            self._tmpl = torch.cat([self._tmpl, z])
+            self._out = torch.zeros(20 * (len(self._ids) + n), dtype=torch.uint8, device=dev)
+            self._frame_hw = None
+        else:
+            crops = [get_extended_crop(image=image, bbox=b, offset=cfg["template_bbox_offset"], crop_size=cfg["template_size"])[0]
+                     for b in boxes]
+            z = self.net.get_features(torch.cat([self._proto._preprocess_image(c, self._proto._template_transform)
+                                                 for c in crops]))
+            for i, b in enumerate(boxes):
+                slot = FEARTracker(self.net, self._proto.cuda_id, **cfg)
+                st = slot.tracking_state
+                st.bbox = b
+                st.paths.append(b)
+                st.mean_color = mean
+                slot._template_features = z[i:i + 1]
+                self._slots.append(slot)
+            self._tmpl_host = z if self._tmpl_host is None else torch.cat([self._tmpl_host, z])
+        self._ids.extend(new_ids)
+        self._stream = np.concatenate([self._stream, np.full(n, int(stream), dtype=np.int32)])
+        self._next_id += n
+        return new_ids
+
+    def remove(self, ids) -> None:
+        """Stop tracking these targets; the state and template tensors are compacted on the device."""
+        drop = set(int(i) for i in np.atleast_1d(ids))
+        keep = [j for j, i in enumerate(self._ids) if i not in drop]
+        if len(keep) == len(self._ids):
+            return
+        self._ids = [self._ids[j] for j in keep]
+        self._stream = self._stream[keep]
+        if self.device_path:
+            sel = torch.tensor(keep, dtype=torch.int64, device=self.device)
+            self._ctx, self._prev, self._pad, self._fidx, self._tmpl = (
+                t.index_select(0, sel) for t in (self._ctx, self._prev, self._pad, self._fidx, self._tmpl))
+            self._out = torch.zeros(20 * len(keep), dtype=torch.uint8, device=self.device)
+            self._frame_hw = None
+        else:
+            self._slots = [self._slots[j] for j in keep]
+            self._tmpl_host = self._tmpl_host[keep] if keep else None
+
+    # ------------------------------------------------------------------ frames
+    def _frames(self, images) -> list:
+        frames = list(images) if isinstance(images, (list, tuple)) else [images]
+        if len(self._stream) and int(self._stream.max()) >= len(frames):
+            raise ValueError(f"targets on stream {int(self._stream.max())} but only {len(frames)} frame(s) given")
+        for f in frames:
+            self._check_frame(f)
+        return frames
+
+    def submit(self, images) -> PendingBoxes:
+        """Track every target on its stream's frame (`images`: one frame, or a sequence indexed by stream).  On the device
+        path nothing waits for the GPU — every upload is a non-blocking copy from pinned memory, every launch asynchronous
+        (tests/test_multi_tracker.py runs it under torch.cuda.set_sync_debug_mode("error")): the returned `PendingBoxes`
+        resolves when its own copy has landed."""
+        frames = self._frames(images)
+        if not self._ids:
+            return PendingBoxes([], np.zeros((0, 4), np.int64), np.zeros(0, np.float32))
+        if not self.device_path:
+            return self._submit_host(frames)
+        cfg, net, k = self.tracking_config, self.net, len(self._ids)
+        dev = self._upload_frames(frames)
+        table = net.frame_table(dev)
+        key = tuple(tuple(f.shape[:2]) for f in dev)
+        if self._frame_hw is None or self._frame_hw[0] != key:
+            hw = np.array([key[s] for s in self._stream], dtype=np.int32).reshape(k, 2)
+            self._frame_hw = (key, self._to_device(hw))
+        search = net.crop_normalize_frames(table, self._fidx, self._ctx, self._pad, cfg["instance_size"])
+        bbox, cls = net.track_maps(search, self._tmpl)
+        boxes = self._out[: 16 * k].view(torch.int32).view(k, 4)
+        scores = self._out[16 * k:].view(torch.float32)
+        net.tracker_step(cls, bbox, self._frame_hw[1], boxes, self._ctx, self._prev, scores, bool(cfg.get("smooth", False)),
+                         self._window, cfg["penalty_k"], cfg["window_influence"], cfg["lr"], cfg["score_size"],
+                         cfg["total_stride"], cfg["instance_size"], cfg["search_context"])
+        host = torch.empty(20 * k, dtype=torch.uint8, pin_memory=True)
+        host.copy_(self._out, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record(torch.cuda.current_stream(self.device))
+        return PendingBoxes(self._ids, host=host, event=event)
+
+    def _submit_host(self, frames) -> PendingBoxes:
+        """The reference-style path: FEARTracker.update's host branch per target around one batched net.track."""
+        cfg = self.tracking_config
+        crops = []
+        for slot, s in zip(self._slots, self._stream):
+            st = slot.tracking_state
+            crop, box_in_crop, context = get_extended_crop(image=frames[s], bbox=st.bbox, crop_size=cfg["instance_size"],
+                                                           offset=cfg["search_context"], padding_value=st.mean_color)
+            st.mapping = context
+            st.prev_size = box_in_crop[2:]
+            crops.append(slot._preprocess_image(crop, slot._search_transform))
+        out = self.net.track(torch.cat(crops), self._tmpl_host)
+        boxes, scores = [], []
+        for j, (slot, s) in enumerate(zip(self._slots, self._stream)):
+            st = slot.tracking_state
+            pred, score = slot._postprocess(track_result={key: out[key][j:j + 1] for key in
+                                                          (TARGET_CLASSIFICATION_KEY, TARGET_REGRESSION_LABEL_KEY)})
+            pred = clamp_bbox(slot._rescale_bbox(pred, st.mapping), frames[s].shape)
+            st.bbox = pred
+            st.paths.append(pred)
+            boxes.append(np.asarray(pred, dtype=np.int64))
+            scores.append(float(score))
+        return PendingBoxes(self._ids, np.stack(boxes), np.asarray(scores, dtype=np.float32))
+
+    def update(self, images) -> Dict[int, np.ndarray]:
+        """`submit(images).result()`: {target id: bbox} of this frame."""
+        return self.submit(images).result()

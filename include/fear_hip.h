@@ -101,6 +101,43 @@ int fear_normalize_u8(fear_handle* h, const uint8_t* u8, int n, int hw, float* o
 int fear_crop_normalize(fear_handle* h, const uint8_t* frame_u8, int frame_h, int frame_w, const int32_t* ctx_xywh,
                         const uint8_t* pad_rgb, int n, int out_hw, float* out, void* stream);
 
+/* One frame of a multi-frame crop launch: a uint8 RGB (H, W, 3) frame in device memory.  16 bytes, no padding:
+ * { data pointer, H, W }. */
+typedef struct fear_frame {
+    const uint8_t* data;
+    int32_t h;
+    int32_t w;
+} fear_frame;
+
+/* fear_crop_normalize for crops out of SEVERAL frames in one launch (the multi-target tracker: one frame per video stream):
+ * crop i is cut out of frames[frame_idx[i]], frames may differ in size.  Same kernel and arithmetic as fear_crop_normalize, which
+ * is its one-frame case: every crop equals a fear_crop_normalize of its own frame bit for bit.  A frame index outside
+ * [0, n_frames) reads no pixel (the crop is all border colour).
+ *   frames    : (n_frames) fear_frame, device     frame_idx : (n) int32, device
+ *   ctx_xywh, pad_rgb, out : as fear_crop_normalize                                                                     */
+int fear_crop_normalize_frames(fear_handle* h, const fear_frame* frames, int n_frames, const int32_t* frame_idx,
+                               const int32_t* ctx_xywh, const uint8_t* pad_rgb, int n, int out_hw, float* out, void* stream);
+
+/* FEARTracker.update after net.track for n targets at once, on device state (feartracker_amd/multi_tracker.py): the decode of
+ * fear_decode (smooth = 0) or fear_decode_smooth (smooth = 1) on the maps of one fear_track call, then Tracker._rescale_bbox
+ * (base_tracker.py:83-90: float64 scales, round half to even, minimum side 3), clamp_bbox to the target's frame
+ * (utils.py:202-212) and crop_geometry(., instance_size, search_context) of the next frame (extend_bbox truncated to int32,
+ * ensure_bbox_boundaries, albumentations' coco-box resize).  Every float64 operation rounded separately, as Python evaluates it:
+ * boxes, contexts and sizes equal the host tracker's bit for bit.  One wavefront per target.
+ *   cls, bbox  : the (n,1,S,S) / (n,4,S,S) maps of fear_track
+ *   frame_hw   : (n, 2) int32   H, W of each target's frame
+ *   box_xywh   : (n, 4) int32   out: the target's box in this frame
+ *   ctx_xywh   : (n, 4) int32   in: the context box this frame was cropped with; out: the next frame's
+ *   prev_size  : (n, 2) float64 in: the box's size in this search crop (read when smooth); out: its size in the next one
+ *   window, penalty_k, window_influence, lr : as fear_decode_smooth (window only read when smooth; may be NULL otherwise)
+ *   score_size, total_stride, instance_size, search_context : the tracker config values (16 / 16 / 256 / 2)
+ *   xywh       : (n, 4) float64 out, optional (NULL = not written): the decoded box of fear_decode / fear_decode_smooth
+ *   score      : (n)    fp32    out: sigmoid(cls) at the arg-max cell                                                      */
+int fear_tracker_step(fear_handle* h, const float* cls, const float* bbox, int n, const int32_t* frame_hw, int32_t* box_xywh,
+                      int32_t* ctx_xywh, double* prev_size, int smooth, const double* window, double penalty_k,
+                      double window_influence, double lr, int score_size, int total_stride, int instance_size,
+                      double search_context, double* xywh, float* score, void* stream);
+
 /* ---- engine options ------------------------------------------------------------------------- */
 #define FEAR_OPT_MAX_BATCH 1   /* crops processed per internal pass (workspace is sized for it)  */
 #define FEAR_OPT_PROFILE 2     /* 1: bracket kernel launches with hipEvents (fear_profile_*)     */
