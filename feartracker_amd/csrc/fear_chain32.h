@@ -20,9 +20,9 @@
 // the chunk pipeline is ir_tile_v4's: the expansion of chunk c + 1 runs on the matrix pipe BETWEEN the depthwise steps of
 // chunk c (ir16_interval's interleaving) into 32 parked registers, and is stored after the barrier that ends the reads of chunk
 // c: two barriers per chunk around eight ds_write_b128 per lane (measured: the barriers cost nothing, profiles/r06_chain32_kbench.txt).
-// The depthwise of a column half is ONE chain over the wave's four rows (c32_half4; C32_ROWS4 = 0 keeps the two row-pair chains of
-// the first form, c32_sub, for A/Bs); the last chunk of a block is peeled out of the chunk loop; the next block's first weight
-// stages are copied during the current block's last interval.  What each of these is worth: the same file.
+// The depthwise of a column half is ONE chain over the wave's four rows (c32_half4; the first form ran two row-pair chains); the
+// last chunk of a block is peeled out of the chunk loop; the next block's first weight stages are copied during the current
+// block's last interval.  What each of these is worth: the same file.
 //
 // chain32_kernel is the stage as a launch of its own, chain32_16_kernel the stage + chain16's seven blocks + the neck in one launch
 // (the engine's default): the stride-2 block's output fragments are chain16's input fragments.
@@ -32,20 +32,14 @@
 #pragma once
 #include <type_traits>
 
-#ifndef C32_D
-#define C32_D 2        // LDS read-ahead of the stride-1 depthwise chain, in tap steps (one activation + one tap read per step)
-#endif
-#ifndef C32_GS
-#define C32_GS 2       // tap steps per scheduling group of the stride-1 chain ([reads][MFMAs][packed FMAs] per group)
+#ifndef C32_D4
+#define C32_D4 4       // LDS read-ahead of the stride-1 depthwise chain (c32_half4), in tap steps
 #endif
 #ifndef C32_D2
 #define C32_D2 3       // read-ahead of the stride-2 chain (35 steps: 5 columns x 7 input rows)
 #endif
 #ifndef C32_GS2
-#define C32_GS2 1
-#endif
-#ifndef C32_ABL
-#define C32_ABL 0      // tools/kbench ablations (bit mask): 1 no depthwise FMAs, 2 no expansion MFMAs, 4 no projection MFMAs, 8 no LDS read-ahead reloads, 16 no chunk barriers, 32 no tile stores, 64 no weight staging
+#define C32_GS2 1      // tap steps per scheduling group of the stride-2 chain ([reads][MFMAs][packed FMAs] per group)
 #endif
 
 namespace fear {
@@ -81,101 +75,6 @@ __device__ __forceinline__ f32x4 c32_relu(f32x4 v) {
     return v;
 }
 
-// The first D tap steps' reads of a row-pair chain (activation + tap weight per step) and the depthwise bias.
-template <int KS, int D>
-__device__ __forceinline__ void c32_prime(const float* __restrict__ e0, const float* __restrict__ wd, f32x4 (&ev)[D], f32x4 (&wv)[D], f32x4& dbias) {
-    constexpr int PW = C32Geom::PW;
-    dbias = *reinterpret_cast<const f32x4*>(wd + KS * KS * 16);
-#pragma unroll
-    for (int t = 0; t < D; ++t) {
-        const int kx = t / (KS + 1), iy = t % (KS + 1);
-        ev[t] = *reinterpret_cast<const f32x4*>(e0 + (iy * PW + kx) * 4);
-        if (iy < KS) wv[t] = *reinterpret_cast<const f32x4*>(wd + (iy * KS + kx) * 16);
-    }
-}
-
-// One row pair x column half of a stride-1 chunk interval: the depthwise of output rows y0, y0 + 1 (16 columns) as ir16_interval's
-// chain of KS (KS + 1) tap steps (column kx outer, input row iy inner: the tap weight of (iy, kx) feeds row 0 now and row 1 in the
-// next step), its projection into p0 / p1, and — between the steps — the expansion of two m-tiles of the NEXT chunk into a0 / a1
-// (bias-initialised here; ReLU at the store).  e0 = this lane's pixel of the tile at tap (0, 0) of row y0.  The first D steps'
-// reads arrive in ev / wv / dbias (c32_prime: issued by the caller, or by the previous quarter under its projection MFMAs); enext
-// = the next quarter's e0 (nullptr: none).
-template <int KS, int KG, int NTP, bool HAS_A>
-__device__ __forceinline__ void c32_sub(const float* __restrict__ e0, const float* __restrict__ wa, const float* __restrict__ wb,
-                                        const f32x4 (&x0)[KG], const f32x4 (&x1)[KG], f32x4& a0, f32x4& a1, f32x4 (&p0)[NTP],
-                                        f32x4 (&p1)[NTP], int lk, int lane, f32x4 (&ev)[C32_D], f32x4 (&wv)[C32_D], f32x4& dbias, const float* enext) {
-    constexpr int PW = C32Geom::PW, NS = KS * (KS + 1), GS = C32_GS, D = C32_D;
-    constexpr int NU = HAS_A ? KG * 4 : 0;
-    const float* wd = wb + NTP * 256 + lk * 4;
-    f32x4 wfq[2];
-    if (HAS_A) {
-        a0 = a1 = *reinterpret_cast<const f32x4*>(wa + KG * 256 + lk * 4);      // expansion bias
-        wfq[0] = *reinterpret_cast<const f32x4*>(wa + lane * 4);
-    }
-    f32x4 d0 = dbias;
-    f32x4 d1 = d0;
-    f32x4 wprev = (f32x4){0.f, 0.f, 0.f, 0.f}, wpq[2];
-#pragma unroll
-    for (int g = 0; g < NS; g += GS) {
-        f32x4 e[GS], w[GS];
-        if (g == NS - GS) wpq[0] = *reinterpret_cast<const f32x4*>(wb + lane * 4);      // the projection's first A fragment, a group ahead
-#pragma unroll
-        for (int s0 = 0; s0 < GS; ++s0) {
-            const int t = g + s0;
-            e[s0] = ev[t % D];
-            w[s0] = wv[t % D];
-            if (t + D < NS && !(C32_ABL & 8)) {
-                const int kx2 = (t + D) / (KS + 1), iy2 = (t + D) % (KS + 1);
-                ev[t % D] = *reinterpret_cast<const f32x4*>(e0 + (iy2 * PW + kx2) * 4);
-                if (iy2 < KS) wv[t % D] = *reinterpret_cast<const f32x4*>(wd + (iy2 * KS + kx2) * 16);
-            }
-        }
-        if (HAS_A) {
-#pragma unroll
-            for (int u = g * NU / NS; u < (g + GS) * NU / NS; ++u) {
-                const int kg = u / 4, i = u % 4;
-                if (i == 0 && kg + 1 < KG) wfq[(kg + 1) & 1] = *reinterpret_cast<const f32x4*>(wa + (kg + 1) * 256 + lane * 4);
-                if (C32_ABL & 2) continue;
-                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], x0[HAS_A ? kg : 0][i], a0, 0, 0, 0);
-                a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], x1[HAS_A ? kg : 0][i], a1, 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int s0 = 0; s0 < GS; ++s0) {
-            const int iy = (g + s0) % (KS + 1);
-            if (C32_ABL & 1) {
-                asm volatile("" :: "v"(e[s0]), "v"(w[s0]));
-            } else {
-                if (iy < KS) pk_fma4(d0, e[s0], w[s0]);
-                if (iy >= 1) pk_fma4(d1, e[s0], wprev);
-            }
-            wprev = w[s0];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    pk_fma_settle(d0, d1);
-    d0 = c32_relu(d0);
-    d1 = c32_relu(d1);
-    if (enext) c32_prime<KS, D>(enext, wd, ev, wv, dbias);
-#pragma unroll
-    for (int nt = 0; nt < NTP; ++nt) {
-        if (nt + 1 < NTP) wpq[(nt + 1) & 1] = *reinterpret_cast<const f32x4*>(wb + (nt + 1) * 256 + lane * 4);
-        if (C32_ABL & 4) { p0[nt] += d0 * wpq[nt & 1]; p1[nt] += d1 * wpq[nt & 1]; continue; }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            p0[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wpq[nt & 1][i], d0[i], p0[nt], 0, 0, 0);
-            p1[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wpq[nt & 1][i], d1[i], p1[nt], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-#ifndef C32_ROWS4
-#define C32_ROWS4 1    // 1: the stride-1 depthwise as ONE chain over the wave's four rows per column half (c32_half4) instead of two row-pair chains
-#endif
-#ifndef C32_D4
-#define C32_D4 4       // read-ahead of that chain, in tap steps
-#endif
 // The first D steps' reads of a four-row chain (KS + 3 input rows per column).
 template <int KS, int D>
 __device__ __forceinline__ void c32_prime4(const float* __restrict__ e0, const float* __restrict__ wd, f32x4 (&ev)[D], f32x4 (&wv)[D], f32x4& dbias) {
@@ -192,7 +91,11 @@ __device__ __forceinline__ void c32_prime4(const float* __restrict__ e0, const f
 // One column half of a stride-1 chunk interval as ONE depthwise chain over the wave's four rows: KS (KS + 3) tap steps (column kx
 // outer, input row iy inner); the activation read of a step feeds up to four output rows (row r with tap row iy - r), the tap weight
 // read at step iy stays in a four-deep window until row 3 has used it: 8 + 5 LDS reads per column instead of 2 x (6 + 5) —
-// each ds_read_b128 costs ~5 issue cycles of a kernel that is issue-bound (profiles/r06_chain32_kbench.txt).
+// each ds_read_b128 costs ~5 issue cycles of a kernel that is issue-bound (profiles/r06_chain32_kbench.txt).  Its projection goes
+// into p0 .. p3 and — between the steps — the expansion of four m-tiles of the NEXT chunk into a0 .. a3 (bias-initialised here;
+// ReLU at the store).  e0 = this lane's pixel of the tile at tap (0, 0) of the wave's first row.  The first D steps' reads arrive
+// in ev / wv / dbias (c32_prime4: issued by the caller, or by the previous half under its projection MFMAs); enext = the next
+// half's e0 (nullptr: none).
 template <int KS, int KG, int NTP, bool HAS_A>
 __device__ __forceinline__ void c32_half4(const float* __restrict__ e0, const float* __restrict__ wa, const float* __restrict__ wb,
                                           const f32x4 (&x0)[KG], const f32x4 (&x1)[KG], const f32x4 (&x2)[KG], const f32x4 (&x3)[KG],
@@ -217,7 +120,7 @@ __device__ __forceinline__ void c32_half4(const float* __restrict__ e0, const fl
         const f32x4 e = ev[t % D];
         if constexpr (iy < KS) wwin[iy & 3] = wv[t % D];
         if constexpr (t == NS - 1) wpq[0] = *reinterpret_cast<const f32x4*>(wb + lane * 4);      // the projection's first A fragment, a step ahead
-        if constexpr (t + D < NS && !(C32_ABL & 8)) {
+        if constexpr (t + D < NS) {
             constexpr int kx2 = (t + D) / NR, iy2 = (t + D) % NR;
             ev[t % D] = *reinterpret_cast<const f32x4*>(e0 + (iy2 * PW + kx2) * 4);
             if constexpr (iy2 < KS) wv[t % D] = *reinterpret_cast<const f32x4*>(wd + (iy2 * KS + kx2) * 16);
@@ -226,22 +129,16 @@ __device__ __forceinline__ void c32_half4(const float* __restrict__ e0, const fl
             static_for<t * NU / NS, (t + 1) * NU / NS>([&](auto U) {
                 constexpr int u = decltype(U)::value, kg = u / 4, i = u % 4;
                 if constexpr (i == 0 && kg + 1 < KG) wfq[(kg + 1) & 1] = *reinterpret_cast<const f32x4*>(wa + (kg + 1) * 256 + lane * 4);
-                if constexpr (!(C32_ABL & 2)) {
-                    a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], x0[kg][i], a0, 0, 0, 0);
-                    a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], x1[kg][i], a1, 0, 0, 0);
-                    a2 = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], x2[kg][i], a2, 0, 0, 0);
-                    a3 = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], x3[kg][i], a3, 0, 0, 0);
-                }
+                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], x0[kg][i], a0, 0, 0, 0);
+                a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], x1[kg][i], a1, 0, 0, 0);
+                a2 = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], x2[kg][i], a2, 0, 0, 0);
+                a3 = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], x3[kg][i], a3, 0, 0, 0);
             });
         }
-        if constexpr (C32_ABL & 1) {
-            asm volatile("" :: "v"(e));
-        } else {
-            if constexpr (iy < KS) pk_fma4(d0, e, wwin[iy & 3]);
-            if constexpr (iy >= 1 && iy - 1 < KS) pk_fma4(d1, e, wwin[(iy - 1) & 3]);
-            if constexpr (iy >= 2 && iy - 2 < KS) pk_fma4(d2, e, wwin[(iy - 2) & 3]);
-            if constexpr (iy >= 3) pk_fma4(d3, e, wwin[(iy - 3) & 3]);
-        }
+        if constexpr (iy < KS) pk_fma4(d0, e, wwin[iy & 3]);
+        if constexpr (iy >= 1 && iy - 1 < KS) pk_fma4(d1, e, wwin[(iy - 1) & 3]);
+        if constexpr (iy >= 2 && iy - 2 < KS) pk_fma4(d2, e, wwin[(iy - 2) & 3]);
+        if constexpr (iy >= 3) pk_fma4(d3, e, wwin[(iy - 3) & 3]);
         __builtin_amdgcn_sched_barrier(0);
     });
     asm volatile("s_nop 7" : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3));      // (pk_fma_settle: inline-asm FMA results feed MFMAs)
@@ -253,7 +150,6 @@ __device__ __forceinline__ void c32_half4(const float* __restrict__ e0, const fl
 #pragma unroll
     for (int nt = 0; nt < NTP; ++nt) {
         if (nt + 1 < NTP) wpq[(nt + 1) & 1] = *reinterpret_cast<const f32x4*>(wb + (nt + 1) * 256 + lane * 4);
-        if (C32_ABL & 4) { p0[nt] += d0 * wpq[nt & 1]; p1[nt] += d1 * wpq[nt & 1]; p2[nt] += d2 * wpq[nt & 1]; p3[nt] += d3 * wpq[nt & 1]; continue; }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             p0[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wpq[nt & 1][i], d0[i], p0[nt], 0, 0, 0);
@@ -303,7 +199,7 @@ __device__ __forceinline__ void c32_interval_s2(const float* __restrict__ e0, co
             const int t = g + s0;
             e[s0] = ev[t % D];
             w[s0] = (t % NR) < KS ? wv[t % D] : zero4;
-            if (t + D < NS && !(C32_ABL & 8)) {
+            if (t + D < NS) {
                 const int kx2 = (t + D) / NR, rr2 = (t + D) % NR;
                 ev[t % D] = *reinterpret_cast<const f32x4*>(e0 + eoff(t + D));
                 if (rr2 < KS) wv[t % D] = *reinterpret_cast<const f32x4*>(wd + (rr2 * KS + kx2) * 16);
@@ -314,7 +210,6 @@ __device__ __forceinline__ void c32_interval_s2(const float* __restrict__ e0, co
             for (int u = g * NU / NS; u < (g + GS) * NU / NS; ++u) {
                 const int q = u / (KG * 4), kg = (u / 4) % KG, i = u % 4;
                 if (i == 0) wfq[kg & 1] = *reinterpret_cast<const f32x4*>(wa + kg * 256 + lane * 4);
-                if (C32_ABL & 2) continue;
                 park[2 * q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], xin[2 * q][HAS_A ? kg : 0][i], park[2 * q], 0, 0, 0);
                 park[2 * q + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], xin[2 * q + 1][HAS_A ? kg : 0][i], park[2 * q + 1], 0, 0, 0);
             }
@@ -322,12 +217,8 @@ __device__ __forceinline__ void c32_interval_s2(const float* __restrict__ e0, co
 #pragma unroll
         for (int s0 = 0; s0 < GS; ++s0) {
             const int rr = (g + s0) % NR;
-            if (C32_ABL & 1) {
-                asm volatile("" :: "v"(e[s0]), "v"(w[s0]));
-            } else {
-                if (rr < KS) pk_fma4(d0, e[s0], w[s0]);
-                if (rr >= 2) pk_fma4(d1, e[s0], wp2);
-            }
+            if (rr < KS) pk_fma4(d0, e[s0], w[s0]);
+            if (rr >= 2) pk_fma4(d1, e[s0], wp2);
             wp2 = wp1;
             wp1 = w[s0];
             if (rr == NR - 1) { wp1 = zero4; wp2 = zero4; }     // (a new column: the taps restart; the values are not read before they are set)
@@ -342,7 +233,6 @@ __device__ __forceinline__ void c32_interval_s2(const float* __restrict__ e0, co
 #pragma unroll
     for (int nt = 0; nt < NTP; ++nt) {
         if (nt + 1 < NTP) wpq[(nt + 1) & 1] = *reinterpret_cast<const f32x4*>(wb + (nt + 1) * 256 + lane * 4);
-        if (C32_ABL & 4) { accp[0][nt] += d0 * wpq[nt & 1]; accp[1][nt] += d1 * wpq[nt & 1]; continue; }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             accp[0][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wpq[nt & 1][i], d0[i], accp[0][nt], 0, 0, 0);
@@ -421,15 +311,14 @@ __device__ __forceinline__ void chain32_block(const f32x4 (&xin)[8][B::CIN / 16]
     //  interval hipcc's register allocator spills hundreds of registers at the join)
     auto interval = [&](int c, auto more_c) {
         constexpr bool MORE = decltype(more_c)::value;
-        if (c + 2 < NCHUNK && !(C32_ABL & 64)) stage_a(c + 2);
-        if (MORE && !(C32_ABL & 64)) stage_b(c + 1);
+        if (c + 2 < NCHUNK) stage_a(c + 2);
+        if (MORE) stage_b(c + 1);
         const float* wa = WA + ((c + 1) & 1) * L::AP_MAX;
         const float* wb = WB + (c & 1) * L::BP_MAX;
         if constexpr (S2) {
             const float* e0 = E + lk * L::PLANE + (wave * 4 * PW + li) * 4;
             c32_interval_s2<KG, NTP, MORE>(e0, wa, wb, xin, park, accp, lk, lane);
         } else {
-#if C32_ROWS4
             f32x4 ev[C32_D4], wv[C32_D4], dbias;
             const float* eb = E + lk * L::PLANE + ((wave * 4 + PT - P) * PW + li + PT - P) * 4;
             c32_prime4<KS, C32_D4>(eb, wb + NTP * 256 + lk * 4, ev, wv, dbias);
@@ -439,23 +328,10 @@ __device__ __forceinline__ void chain32_block(const f32x4 (&xin)[8][B::CIN / 16]
             c32_half4<KS, KG, NTP, MORE>(eb + 64, wa, wb, xin[4], xin[5], xin[6], xin[7], park[4], park[5], park[6], park[7], accp[4], accp[5],
                                          accp[6], accp[7], lk, lane, ev, wv, dbias, nullptr);
         }
-#else
-            f32x4 ev[C32_D], wv[C32_D], dbias;
-            const float* eb = E + lk * L::PLANE + ((wave * 4 + PT - P) * PW + li + PT - P) * 4;
-            c32_prime<KS, C32_D>(eb, wb + NTP * 256 + lk * 4, ev, wv, dbias);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {      // column half q >> 1, row pair q & 1
-                const float* e0 = eb + ((q & 1) * 2 * PW + (q >> 1) * 16) * 4;
-                const float* en = eb + (((q + 1) & 1) * 2 * PW + ((q + 1) >> 1) * 16) * 4;
-                c32_sub<KS, KG, NTP, MORE>(e0, wa, wb, xin[2 * q], xin[2 * q + 1], park[2 * q], park[2 * q + 1], accp[2 * q], accp[2 * q + 1], lk, lane, ev, wv, dbias, q < 3 ? en : nullptr);
-            }
-        }
-#endif
-        if (!(C32_ABL & 16)) __syncthreads();
+        __syncthreads();
         if constexpr (MORE) {
-            if (!(C32_ABL & 32)) store_park();
-            if (!(C32_ABL & 16)) __syncthreads();
+            store_park();
+            __syncthreads();
         }
     };
     for (int c = 0; c < NCHUNK - 1; ++c) interval(c, std::true_type{});

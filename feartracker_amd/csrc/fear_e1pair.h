@@ -21,19 +21,8 @@
 #include <type_traits>
 #include <vector>
 
-#ifndef E1P_ABL
-#define E1P_ABL 0      // tools/kbench ablations: 1 no block A, 2 no block B, 4 no input loads, 8 stamps
-#endif
 #ifndef E1P_NA
 #define E1P_NA 3       // of a thread's five prefetch loads, [0, E1P_NA) are in flight during block A and the rest during block B
-#endif
-#ifndef E1P_PERM
-#define E1P_PERM 1     // 1: a wave's 64 fill slots are dealt to its lanes with stride 9 (lane 8g + j takes slot 8 ((g + j) mod 8) + j) and the plane
-                       // pairs sit 48 B beyond a multiple of 256 B apart: every 8-lane store group then hits 8 different 16-byte bank slots
-                       // (conflict free; a wave's loads are still one contiguous 1 KB).  0: slots in lane order, pairs 32 B apart: 2-way
-#endif
-#ifndef E1P_SKEW
-#define E1P_SKEW (E1P_PERM ? 12 : 8)     // floats between the plane PAIRS of the input tile beyond a multiple of 256 B (E1PairGeom::xb); 0 = round 4's layout (tools/kbench A/B)
 #endif
 
 namespace fear {
@@ -55,8 +44,8 @@ struct E1PairGeom {
     // 6-way conflict on every group: 1 600 LDS cycles per fill against 300, the whole of the kernel's SQ_LDS_BANK_CONFLICT (0.27 of
     // its LDS cycles, profiles/r05_sq_counters.txt).  The ds_read_b128 groups mix quads (0, 1) and (2, 3) — those pairs must stay a
     // multiple of 256 B apart — and the float2 reads pair the halves of quad 4 and of quad 5; between the PAIRS the distance is free:
-    // 32 B more per pair leaves 2-way conflicts (600 cycles).
-    static constexpr int XSKEW = E1P_SKEW;
+    // 32 B more per pair leaves 2-way conflicts (600 cycles); 48 B with the fill slots of e1_fill_slot none.
+    static constexpr int XSKEW = 12;
     static constexpr int xb(int q) { return q * XPL + (q >> 1) * XSKEW; }
     static constexpr int XT_FLOATS = NQ * XPL + 2 * XSKEW;
     static constexpr int NSLOT = NQ * XW * XW, NIT = (NSLOT + 511) / 512;     // float4 slots of the input tile, per thread
@@ -111,9 +100,11 @@ __device__ __forceinline__ void e1_project(f32x4 d4, f32x2 d2, const f32x4 (&wp)
     }
 }
 
-// which of its wave's 64 consecutive fill slots a thread takes (E1P_PERM)
+// which of its wave's 64 consecutive fill slots a thread takes: stride 9 (lane 8g + j takes slot 8 ((g + j) mod 8) + j).  With the
+// plane pairs 48 B beyond a multiple of 256 B apart (XSKEW) every 8-lane store group then hits 8 different 16-byte bank slots (conflict
+// free; a wave's loads are still one contiguous 1 KB).  Slots in lane order with the pairs 32 B apart (round 4's layout) left 2-way
+// conflicts: profiles/r06_e1pair_perm_kbench.txt.
 __device__ __forceinline__ int e1_fill_slot(int tid) {
-    if (!E1P_PERM) return tid;
     const int l = tid & 63, g = l >> 3, j = l & 7;
     return (tid & ~63) | (8 * ((g + j) & 7) + j);
 }
@@ -142,7 +133,6 @@ __device__ __forceinline__ void e1_issue_loads(const E1PairArgs& a, unsigned tix
         const int py = pix / XW, px = pix - py * XW;
         const int gy = oy0 - 2 + py, gx = ox0 - 2 + px;
         const bool ok = s < G::NSLOT && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-        if (E1P_ABL & 4) { xv[it] = (f32x4){1.f, 2.f, 3.f, 4.f}; continue; }
         xv[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(img, ok ? ((gy * a.W + gx) * C + q * 4) * 4 : (int)0x80000000, 0, 0));
     }
 }
@@ -215,7 +205,7 @@ __global__ __launch_bounds__(512, 4) void e1pair_kernel(E1PairArgs a) {
         // they are used and dropped — the same number of LDS reads as loading all 54 tap registers once per phase, without
         // holding them beside the prefetched tile (round 4's form, one m-tile at a time from register-resident taps, spilled the
         // prefetch to scratch and waited for it on the spot).
-        if (!(E1P_ABL & 1)) {
+        {
             const float* ws = WSl;
             f32x4 wp[4];
             load_wp(0, wp);
@@ -284,7 +274,7 @@ __global__ __launch_bounds__(512, 4) void e1pair_kernel(E1PairArgs a) {
         if (ti + 1 < tpw) { e1_commit_tile<0, NA>(Xt, tid, xv); e1_issue_loads<NA, NIT>(a, tix + 1, tid, xv); }
 
         // ---- block B on the tile's 16 rows (two per wave, sharing their depthwise reads) -> global
-        if (!(E1P_ABL & 2)) {
+        {
             const float* ws = WSl + G::WS;
             f32x4 wp[4];
             load_wp(1, wp);

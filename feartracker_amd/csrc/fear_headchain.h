@@ -2,7 +2,7 @@
 // and runs the branch's four SepConvs back to back — encode (+ pixel-wise correlation, blocks.py:121-123), the correlation
 // SepConv over the 320-channel concat, and the two tower SepConvs (+ the prediction SepConv, blocks.py:167-168,186-192).
 //
-// What the measurements said (tools/headchain_check.hip): in sep16_kernel and in a first chained version
+// What the measurements said: in sep16_kernel and in a first chained version
 // the MFMA stretches run at the instruction rate, but every barrier interval (one per 16-channel input chunk: 16-24 per layer)
 // loses 1 600-2 000 cycles at its start and end, global memory answers in ~3 us under load, and a layer's activation makes a
 // round trip through HBM / MALL.  So this kernel is organised around ONE idea: a wave keeps the depthwise results of its
@@ -23,11 +23,6 @@
 #include <vector>
 #ifndef HC_TS
 #define HC_TS 2        // tap steps of the deferred hand-over per MFMA group (1, 2, 3, 4, 6)
-#endif
-#ifndef HC_ABL
-#define HC_ABL 0       // timing ablations for tools/headchain_check only (bit mask); the product always builds with 0
-                       // 1: no scratch stores of the next layer's depthwise results, 2: no scratch reloads (1 | 2: the parking is
-                       // free), 4: no prologue fetch of the neck output, 8 / 128: time stamps
 #endif
 
 namespace fear {
@@ -52,7 +47,6 @@ struct HeadChainArgs {
     int n_crops;             // launch with 2 * 8 * ceil(n_crops / 8) workgroups (see the id mapping in the kernel)
     int relu_dw, relu_out;
     HeadChainBranch br[2];   // blockIdx.y: 0 = classification, 1 = regression
-    long long* dbg;          // HC_ABL & 8: wall-clock stamps of workgroup (100, 0) (tools/headchain_check)
 };
 
 // Workgroup barrier that does NOT wait for the wave's vector-memory operations (only for its LDS traffic): __syncthreads() waits
@@ -138,13 +132,6 @@ __global__ __launch_bounds__(512) void headchain_kernel(HeadChainArgs a) {
         return reinterpret_cast<f32x4*>(Dws + off);
     };
 
-    int stamp_i = 0;
-    auto stamp = [&] {
-        if ((HC_ABL & 8) && crop == 100 && branch == 0 && (wave == 0 || wave == 4) && lane == 0 && stamp_i < 40)
-            a.dbg[(wave >> 2) * 40 + stamp_i++] = wall_clock64();
-    };
-    stamp();
-
     // the tile's halo is zero for the whole kernel (= the convolutions' padding): only the interior is ever rewritten
     for (int i = tid * 4; i < NTP * EBUF; i += 512 * 4) *reinterpret_cast<f32x4*>(Et + i) = (f32x4){0.f, 0.f, 0.f, 0.f};
     // the weight blocks alternate between Wb[0] and Wb[1] (the next pass's block is copied in during the current GEMM), the template
@@ -209,7 +196,7 @@ __global__ __launch_bounds__(512) void headchain_kernel(HeadChainArgs a) {
         for (int c = 0; c < C / 16; ++c) {
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
-                d[c][mt] = (HC_ABL & 4) ? (f32x4){0.5f, 0.25f, 1.f, 2.f} : *reinterpret_cast<const f32x4*>(X0 + (long)((y0 + mt) * S + li) * a.ldx + c * 16 + lk * 4);
+                d[c][mt] = *reinterpret_cast<const f32x4*>(X0 + (long)((y0 + mt) * S + li) * a.ldx + c * 16 + lk * 4);
             __builtin_amdgcn_sched_barrier(0);     // (in chunk order: hipcc would issue the first chunks last)
         }
         // zero fill done and weight blocks landed: everything but the youngest 32 operations (the input rows).
@@ -236,7 +223,6 @@ __global__ __launch_bounds__(512) void headchain_kernel(HeadChainArgs a) {
             barrier_lds_only();
         }
     }
-    stamp();
 
     f32x4 cacc[2][TZ / 16];             // layer 0: correlation accumulators
     f32x4 pacc[2];                      // layer 3: prediction accumulators
@@ -258,17 +244,12 @@ __global__ __launch_bounds__(512) void headchain_kernel(HeadChainArgs a) {
                 for (int q = 0; q < NTZ; ++q) cacc[mt][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
         if (MODE == 2) pacc[0] = pacc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        int fs_i = 0;
-        auto fstamp = [&](int p) {          // HC_ABL & 128: s_memtime stamps inside passes 2..4 of the third layer
-            if ((HC_ABL & 128) && MODE == 0 && CIN == C && p >= 2 && p < 5 && crop == 100 && branch == 0 && lane == 0 && fs_i < 21)
-                a.dbg[80 + wave * 21 + fs_i++] = __builtin_amdgcn_s_memtime();
-        };
         // The hand-over of pass q (its 32 finished channels = the NEXT layer's input chunks 2q, 2q + 1 are in the tile): the next layer's
         // depthwise of those chunks -> the scratch (DST < 0) or straight into d[DST], d[DST + 1]; layer 3: the prediction head instead.
         auto handoff_out = [&](int q, int nt, const f32x4& n0, const f32x4& n1, auto dst_tag) {
             constexpr int DST = decltype(dst_tag)::value;
             if (MODE != 2) {
-                if (DST < 0) { if (!(HC_ABL & 1)) { *dptr(2 * q + nt, 0) = n0; *dptr(2 * q + nt, 1) = n1; } }
+                if (DST < 0) { *dptr(2 * q + nt, 0) = n0; *dptr(2 * q + nt, 1) = n1; }
                 else { d[DST < 0 ? 0 : DST][0] = n0; d[DST < 0 ? 0 : DST][1] = n1; }
             } else {
                 // prediction SepConv's 1x1 to <= 4 channels on the depthwise of the finished chunk
@@ -295,7 +276,6 @@ __global__ __launch_bounds__(512) void headchain_kernel(HeadChainArgs a) {
             // profiles/r03_issue_probe.txt), operands read one group ahead into rotating registers
             constexpr int TS = HC_TS, GPC = NS / TS + 2, NE = 2 * TS, NW = 2 * TS + 1;
             static_assert(NS % TS == 0 && NG >= 2 * GPC, "hand-over schedule");
-            fstamp(p);
             const float* wb = Wb + (p & 1) * WMAX;
             f32x4 acc[2][NTP];
 #pragma unroll
@@ -380,11 +360,10 @@ __global__ __launch_bounds__(512) void headchain_kernel(HeadChainArgs a) {
                     // (written to the scratch by this lane in the hand-over of pass c / 2 — the one of pass 6 a few groups ago; the
                     // last two chunks come straight from the hand-over below)
 #pragma unroll
-                    for (int mt = 0; mt < 2; ++mt) if (!(HC_ABL & 2)) d[c][mt] = *dptr(c, mt);
+                    for (int mt = 0; mt < 2; ++mt) d[c][mt] = *dptr(c, mt);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            fstamp(p);
             // ---- epilogue: bias / ReLU; the finished fragments are the next layer's input chunks 2p, 2p + 1
             f32x4 v[2][NTP];
 #pragma unroll
@@ -418,11 +397,9 @@ __global__ __launch_bounds__(512) void headchain_kernel(HeadChainArgs a) {
                         }
                 }
             }
-            fstamp(p);
             // B: every wave has read the tile (hand-over of pass p - 1) and this pass's weight block for the last time; the NEXT pass's
             // block (issued early in this pass's GEMM) has landed.  (The hand-over's scratch stores are wave private; they are old by now.)
             __syncthreads();
-            fstamp(p);
 #pragma unroll
             for (int nt = 0; nt < NTP; ++nt) tile_put(nt, v[0][nt], v[1][nt]);
             // between the barriers: the next pass's first fragments into registers — its GEMM starts with its MFMAs
@@ -432,7 +409,6 @@ __global__ __launch_bounds__(512) void headchain_kernel(HeadChainArgs a) {
                 wf1 = *reinterpret_cast<const f32x4*>(wn + 256 + lane * 4);
             }
             barrier_lds_only();                    // A: tile complete
-            fstamp(p);
             if (LAST) {
                 // the layer's last hand-over is not deferred: its results are B fragments of the next layer's first GEMM
 #pragma unroll
@@ -484,7 +460,6 @@ __global__ __launch_bounds__(512) void headchain_kernel(HeadChainArgs a) {
                     }
             }
         }
-        stamp();
     };
 
     layer(integral_constant<int, C>{}, integral_constant<int, 1>{}, b.W[0], b.W[1]);

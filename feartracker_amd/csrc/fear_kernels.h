@@ -23,26 +23,11 @@
 #ifndef IR16_D
 #define IR16_D 4       // LDS read-ahead of ir16_interval, in tap steps
 #endif
-#ifndef IR16H_ASYNC
-#define IR16H_ASYNC 1  // ir16h_fused_kernel (blocks with expansion): packed weights global -> LDS by asynchronous copies (0: through registers, rounds 2-5)
-#endif
 #ifndef IR16H_D
 #define IR16H_D 4      // LDS read-ahead of ir16h_fused_kernel's depthwise, in tap steps (two reads per step and channel half)
 #endif
-#ifndef CHAIN16_PEEL
-#define CHAIN16_PEEL 1     // chain16_block: the last chunk peeled out of the chunk loop (0: a run-time branch inside the loop, rounds 1-5)
-#endif
 #ifndef FEAR_V4_GS
 #define FEAR_V4_GS 2      // tap steps per scheduling group of ir_tile_v4_kernel
-#endif
-#ifndef FEAR_V4_GUARD
-#define FEAR_V4_GUARD 0   // 1: skip the expansion MFMAs of m-tiles beyond the clipped region (a scalar branch per MFMA)
-#endif
-#ifndef FEAR_ABL
-#define FEAR_ABL 0      // timing ablations for tools/kbench only (bit mask); the product always builds with 0
-                        // (tile kernels, round 4: 8192 keep the barrier after the last chunk, 16384 projection bias loaded in the
-                        //  epilogue, 65536 e1 residual re-read from global memory; 4096 = per-phase wall-clock stamps; the other
-                        //  bits are named where they are tested)
 #endif
 
 #include <hip/hip_runtime.h>
@@ -1027,7 +1012,7 @@ __device__ __forceinline__ void ir16_interval(const float* __restrict__ E, float
             const int t = g + s0;
             e[s0] = ev[t % D];
             w[s0] = wv[t % D];
-            if (t + D < NS && !(FEAR_ABL & 4)) {
+            if (t + D < NS) {
                 const int kx2 = (t + D) / (KS + 1), iy2 = (t + D) % (KS + 1);
                 ev[t % D] = *reinterpret_cast<const f32x4*>(e0 + (iy2 * PW + kx2) * ES);
                 if (iy2 < KS) wv[t % D] = *reinterpret_cast<const f32x4*>(wd + (iy2 * KS + kx2) * 16);
@@ -1038,7 +1023,6 @@ __device__ __forceinline__ void ir16_interval(const float* __restrict__ E, float
             for (int u = g * NU / NS; u < (g + GS) * NU / NS; ++u) {
                 const int kg = u / 4, i = u % 4;
                 if (i == 0 && kg + 1 < KG) wfq[(kg + 1) & 1] = *reinterpret_cast<const f32x4*>(wa + (kg + 1) * 256 + lane * 4);
-                if (FEAR_ABL & 8) continue;
                 acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], xf[0][HAS_A ? kg : 0][i], acc[0], 0, 0, 0);
                 acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfq[kg & 1][i], xf[HAS_A ? 1 : 0][HAS_A ? kg : 0][i], acc[1], 0, 0, 0);
             }
@@ -1046,12 +1030,8 @@ __device__ __forceinline__ void ir16_interval(const float* __restrict__ E, float
 #pragma unroll
         for (int s0 = 0; s0 < GS; ++s0) {
             const int iy = (g + s0) % (KS + 1);
-            if (FEAR_ABL & 32) {
-                d0.x += e[s0].x + w[s0].x;
-            } else {
-                if (iy < KS) pk_fma4(d0, e[s0], w[s0]);
-                if (iy >= 1) pk_fma4(d1, e[s0], wprev);
-            }
+            if (iy < KS) pk_fma4(d0, e[s0], w[s0]);
+            if (iy >= 1) pk_fma4(d1, e[s0], wprev);
             wprev = w[s0];
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -1074,7 +1054,6 @@ __device__ __forceinline__ void ir16_interval(const float* __restrict__ E, float
 #pragma unroll
     for (int nt = 0; nt < NTP; ++nt) {
         if (nt + 1 < NTP) wpq[(nt + 1) & 1] = *reinterpret_cast<const f32x4*>(wb + (nt + 1) * 256 + lane * 4);
-        if (FEAR_ABL & 16) { accp[0][nt] += d0 * wpq[nt & 1]; accp[1][nt] += d1 * wpq[nt & 1]; continue; }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             accp[0][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wpq[nt & 1][i], d0[i], accp[0][nt], 0, 0, 0);
@@ -1227,10 +1206,8 @@ __global__ __launch_bounds__(512) void ir16v2_fused_kernel(Ir2Args a) {
         constexpr bool MORE = decltype(more_c)::value;
         // prefetch (registers only): EXPAND: A-part two chunks ahead; !EXPAND: next chunk's activations
         const int ca = EXPAND ? c + 2 : c + 1;
-        if (!(FEAR_ABL & 2)) {
-            if (ca < NCHUNK) load_a(ca);
-            if (MORE) load_b(c + 1);
-        }
+        if (ca < NCHUNK) load_a(ca);
+        if (MORE) load_b(c + 1);
         // (fp32 MFMA executes on the vector ALUs on gfx950 — tools/coexec.hip: an MFMA wave and a VALU wave on one
         //  SIMD take the SUM of their times — so staggering phases between waves buys nothing; what matters is that
         //  neither wave of a SIMD waits on LDS latency)
@@ -1239,11 +1216,9 @@ __global__ __launch_bounds__(512) void ir16v2_fused_kernel(Ir2Args a) {
         const float* wa = WA + ((c + 1) & 1) * AP;
         const float* wb = WB + (c & 1) * BP;
         ir16_interval<KS, PW, ES, KG, NTP, EXPAND && MORE>(Ec, En, wa, wb, xf, accp, y0, li, lk, lane, a.relu_dw);
-        if (!(FEAR_ABL & 2)) {
-            if (ca < NCHUNK) store_a(ca);
-            if (MORE) store_b(c + 1);
-        }
-        if (!(FEAR_ABL & 1)) __syncthreads();
+        if (ca < NCHUNK) store_a(ca);
+        if (MORE) store_b(c + 1);
+        __syncthreads();
     };
     for (int c = 0; c < NCHUNK - 1; ++c) chunk(c, std::true_type{});
     chunk(NCHUNK - 1, std::false_type{});
@@ -1387,8 +1362,7 @@ __global__ __launch_bounds__(512) void sep16_kernel(Ir2Args a) {
     // the steps; PROJ = false for the prologue (nothing to project yet), DW = false for the last interval
     f32x4 d0, d1;                       // depthwise result of the chunk being projected
     auto interval = [&](int c, auto proj_tag, auto dw_tag) {
-        constexpr bool PROJ = decltype(proj_tag)::value && !(FEAR_ABL & 16), DW = decltype(dw_tag)::value && !(FEAR_ABL & 64);
-        if (FEAR_ABL & 64) { d0 = d1 = rx[0]; }
+        constexpr bool PROJ = decltype(proj_tag)::value, DW = decltype(dw_tag)::value;
         const int cd = PROJ ? c + 1 : c;
         const float* wd = WD + (cd & 1) * WDF + lk * 4;
         const float* e0 = Ebuf + (cd & 1) * EBUF + (y0 * PW + li) * EP + lk * EQ;
@@ -1457,21 +1431,18 @@ __global__ __launch_bounds__(512) void sep16_kernel(Ir2Args a) {
     interval(0, std::false_type{}, std::true_type{});
     __syncthreads();                       // E[0] / WD[0] are overwritten at the end of interval 0
 
-    for (int c = 0; c < ((FEAR_ABL & 256) ? 0 : NCHUNK); ++c) {
-        if (!(FEAR_ABL & 2)) {
-            // in flight during this interval: WD[c&1] (last read by the depthwise of chunk c, before the previous barrier),
-            // WP[(c+1)&1] (last read by the projection of chunk c-1)
-            if (c + 2 < NCHUNK) { load_x(c + 2); stage_d(c + 2); }
-            if (c + 1 < NCHUNK) stage_p(c + 1);
-        }
+    for (int c = 0; c < NCHUNK; ++c) {
+        // in flight during this interval: WD[c&1] (last read by the depthwise of chunk c, before the previous barrier),
+        // WP[(c+1)&1] (last read by the projection of chunk c-1)
+        if (c + 2 < NCHUNK) { load_x(c + 2); stage_d(c + 2); }
+        if (c + 1 < NCHUNK) stage_p(c + 1);
         auto commit = [&] {
-            if (FEAR_ABL & 2) return;
             if (c + 2 < NCHUNK) store_x(c + 2);
         };
         if (c + 1 < NCHUNK) interval(c, std::true_type{}, std::true_type{});
         else interval(c, std::true_type{}, std::false_type{});
         commit();      // (committing mid-interval stalls on the global loads: they need most of an interval to land)
-        if (!(FEAR_ABL & 1)) __syncthreads();
+        __syncthreads();
     }
 
     if (SPLITK) {                   // raw partial sums; bias and ReLU belong to splitk_reduce_kernel
@@ -1582,7 +1553,7 @@ __global__ __launch_bounds__(512) void sep16_kernel(Ir2Args a) {
             f32x4 v = accp[mt][nt] + b;
             if (a.R) v += *reinterpret_cast<const f32x4*>(a.R + m * a.ldr + n);
             if (a.relu_out) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-            if (!(FEAR_ABL & 2048) || v.x == 1234.5f) *reinterpret_cast<f32x4*>(a.Y + m * a.ldy + n) = v;      // (ablation: no output stores)
+            *reinterpret_cast<f32x4*>(a.Y + m * a.ldy + n) = v;
             if (CORR) accp[mt][nt] = v;          // the finished feature fragment = B operand of the correlation
         }
     }
@@ -1650,12 +1621,8 @@ struct IrT2Geom {
 // Workgroups of a 1-D grid are dealt round-robin to the 8 XCDs (workgroup b runs on XCD b % 8), each with its own L2.  The tile
 // kernels want neighbouring tiles of a crop — which share their halo rows and columns — behind the SAME L2: logical tile
 // index = (b % 8) * (n / 8) + b / 8 hands every XCD one contiguous eighth of the tile list (whole crops), walked in order.
-// FEAR_XCD_SWIZZLE=0 keeps the linear order (tools/kbench A/B).
-#ifndef FEAR_XCD_SWIZZLE
-#define FEAR_XCD_SWIZZLE 1
-#endif
 __device__ __forceinline__ unsigned xcd_tile_index(unsigned b, unsigned n) {
-    return (FEAR_XCD_SWIZZLE && n % 8 == 0) ? (b & 7) * (n >> 3) + (b >> 3) : b;
+    return n % 8 == 0 ? (b & 7) * (n >> 3) + (b >> 3) : b;
 }
 
 struct IrT2Args {
@@ -1685,7 +1652,6 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
     float* const E = lds;               // [EBUF]
     float* const WS = lds + EBUF;       // [2][AP + BP]
 
-    const long long tk_start = (FEAR_ABL & 4096) ? wall_clock64() : 0;
     const int tid = threadIdx.x, lane = tid & 63;
     // the wave index in an SGPR: the per-m-tile trip counts and every wave-dependent address stay on the scalar unit (a VGPR
     // copy made each `(wave + 8 * i) * 16 >= NPIX` test an exec-mask update with two VALU instructions, 5.8 cycles each on the
@@ -1707,7 +1673,7 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
     const long xbase = (IO & IO_X_BF16) ? crop * t.H * t.W * a.ldx : 0;      // (bf16 input: offsets in elements from a.X)
 
     // stem mode stages the image patch in the E area first (see below) and zeroes the out-of-image positions afterwards
-    if (!STEM && !(FEAR_ABL & 1024))
+    if (!STEM)
         for (int i = tid * 4; i < EBUF; i += 512 * 4) *reinterpret_cast<f32x4*>(E + i) = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     // weights of chunk 0 -> registers (committed after the zero-fill barrier)
@@ -1736,7 +1702,7 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
     // the image) is staged in LDS with aligned 16-byte loads — it aliases the E tile, which is only written after every wave
     // has gathered its im2col fragments (the loop-top barrier) — and the 8 taps per lane (k = kg*16 + 4*lk + j) are
     // ds_read_b32 gathers from it.  (Gathering straight from global memory cost 40 scattered dword loads per lane: 40 % of
-    // the kernel, tools/kbench FEAR_ABL=512.)
+    // the kernel.)
     constexpr int PR = 2 * IHR + 1, PWID = ((2 * IWR + 1 + 3 + 3) / 4) * 4, PF4 = PWID / 4;
     static_assert(!STEM || 3 * PR * PWID <= EBUF, "the image patch must fit in the E tile it aliases");
     int s_off[STEM ? 8 : 1];
@@ -1757,23 +1723,21 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
         // out-of-range offset, for which the hardware returns zeros — the conv's zero padding — without touching memory.  The
         // per-plane part of the address is the instruction's scalar offset: one VGPR offset per row slot.
         f32x4 pv[3][NR];
-        if (!(FEAR_ABL & 512)) {
-            const __amdgpu_buffer_rsrc_t img = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Xc), 0, 3 * img_h * img_w * 4, 0x00020000);
-            const int ix = col0 + 4 * f;
-            const bool xin = rs < RS && ix >= 0 && ix < img_w;
-            const int voff = ((row0 + rs) * img_w + ix) * 4;
-            int vo[NR];
+        const __amdgpu_buffer_rsrc_t img = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Xc), 0, 3 * img_h * img_w * 4, 0x00020000);
+        const int ix = col0 + 4 * f;
+        const bool xin = rs < RS && ix >= 0 && ix < img_w;
+        const int voff = ((row0 + rs) * img_w + ix) * 4;
+        int vo[NR];
 #pragma unroll
-            for (int n = 0; n < NR; ++n) {
-                const int pr = n * RS + rs, iy = row0 + pr;
-                vo[n] = (xin && pr < PR && iy >= 0 && iy < img_h) ? voff + n * RS * img_w * 4 : (int)0x80000000;   // (the range check is on this offset alone: it must not be negative for a valid lane)
-            }
-#pragma unroll
-            for (int ci = 0; ci < 3; ++ci)
-#pragma unroll
-                for (int n = 0; n < NR; ++n)
-                    pv[ci][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(img, vo[n], ci * img_h * img_w * 4, 0));
+        for (int n = 0; n < NR; ++n) {
+            const int pr = n * RS + rs, iy = row0 + pr;
+            vo[n] = (xin && pr < PR && iy >= 0 && iy < img_h) ? voff + n * RS * img_w * 4 : (int)0x80000000;   // (the range check is on this offset alone: it must not be negative for a valid lane)
         }
+#pragma unroll
+        for (int ci = 0; ci < 3; ++ci)
+#pragma unroll
+            for (int n = 0; n < NR; ++n)
+                pv[ci][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(img, vo[n], ci * img_h * img_w * 4, 0));
         // tap j (= MFMA step j) of lane group lk is k = 4 * j + lk = (ci * 3 + ky) * 3 + kx (pack_fused16_host's stem order: the
         // K padding is lane group 3 of step 6 — zero weights, any finite value will do — and step 7, which is never issued);
         // stem pixel (gy, gx) reads image col 2*gx - 1 + kx = col0 + 2*(gx - ix0) + 1 + kx
@@ -1791,7 +1755,7 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
         static constexpr Tab tab{};
 #pragma unroll
         for (int j = 0; j < 8; ++j) s_off[j] = tab.v[lk][j];
-        if (rs < RS && !(FEAR_ABL & 512)) {
+        if (rs < RS) {
 #pragma unroll
             for (int ci = 0; ci < 3; ++ci)
 #pragma unroll
@@ -1895,7 +1859,7 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
     // the projection bias: read in the epilogue it is one more exposed memory round trip at the tail of every tile.  The one- and
     // two-chunk kernels (stem tile, e1 blocks), where that tail is a visible share, fetch it here; the others would pay for the
     // 4 * NTP registers with occupancy (stage 2: 76 -> 84 VGPRs = two workgroups per CU instead of three, +3 %) and keep it late.
-    constexpr bool BIAS_EARLY = !KSPLIT && NCHUNK <= 2 && !(FEAR_ABL & 16384);
+    constexpr bool BIAS_EARLY = !KSPLIT && NCHUNK <= 2;
     f32x4 bpv[NTP];
 #pragma unroll
     for (int nt = 0; nt < NTP; ++nt) {
@@ -1903,15 +1867,11 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
         if (BIAS_EARLY && nt * 16 + lk * 4 < COUT) bpv[nt] = *reinterpret_cast<const f32x4*>(a.bp + nt * 16 + lk * 4);
     }
 
-    const bool res_from_tile = !EXPAND && !KSPLIT && !(FEAR_ABL & 65536) && a.R == a.X && a.ldr == a.ldx && ST == 1 && CIN == COUT;
-    const long long tk_begin = (FEAR_ABL & 4096) ? wall_clock64() : 0;   // kbench -DFEAR_ABL=4096: 10 ns ticks per region
-    long long tm[6] = {0, 0, 0, 0, 0, 0};
-    for (int c = 0; c < ((FEAR_ABL & 256) ? 0 : NCHUNK); ++c) {
+    const bool res_from_tile = !EXPAND && !KSPLIT && a.R == a.X && a.ldr == a.ldx && ST == 1 && CIN == COUT;
+    for (int c = 0; c < NCHUNK; ++c) {
         const float* wa = WS + (c & 1) * CST;
         const float* wb = wa + AP;
-        const long long tk0 = (FEAR_ABL & 4096) ? wall_clock64() : 0;
-        if (EXPAND && !(FEAR_ABL & 1)) __syncthreads();          // stage c&1 committed (first chunk: by store_w(0) above)
-        const long long tk1 = (FEAR_ABL & 4096) ? wall_clock64() : 0;
+        if (EXPAND) __syncthreads();          // stage c&1 committed (first chunk: by store_w(0) above)
         // ---- phase A: E <- relu(expand) (or the raw activations)
         if (EXPAND) {
             f32x4 wf[KG > 0 ? KG : 1];
@@ -1923,10 +1883,8 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
 #pragma unroll
                 for (int kg = 0; kg < KG; ++kg)
 #pragma unroll
-                    for (int q = 0; q < ((KHALF && kg == KG - 1) ? 2 : (STEM && kg == 1) ? 3 : 4); ++q) {
-                        if (FEAR_ABL & 8) { acc += wf[kg] * xf[i][kg][q]; continue; }
+                    for (int q = 0; q < ((KHALF && kg == KG - 1) ? 2 : (STEM && kg == 1) ? 3 : 4); ++q)
                         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[kg][q], xf[i][kg][q], acc, 0, 0, 0);
-                    }
                 acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f);
                 return acc;
             };
@@ -1935,7 +1893,7 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
                 if ((wave + 8 * i) * 16 >= NPIX) break;            // wave-uniform: whole m-tile beyond the clipped region
                 *reinterpret_cast<f32x4*>(E + eoff[i]) = expand_tile(i);
             }
-            if (STEM && (CW < IWR || CH < IHR) && !(FEAR_ABL & 1024)) {
+            if (STEM && (CW < IWR || CH < IHR)) {
                 // border tile: the positions outside the stem-output map (the depthwise's zero padding) still hold patch bytes
                 for (int p = tid; p < IHR * IWR; p += 512) {
                     const int ry = p / IWR, rxx = p - ry * IWR;
@@ -1954,10 +1912,8 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
             }
         }
         // prefetch the next chunk's weights (and activations) while this chunk computes
-        if (c + 1 < NCHUNK && !(FEAR_ABL & 2)) { load_w(c + 1); load_x(c + 1); }
-        const long long tk2 = (FEAR_ABL & 4096) ? wall_clock64() : 0;
-        if (!(FEAR_ABL & 1)) __syncthreads();
-        const long long tk3 = (FEAR_ABL & 4096) ? wall_clock64() : 0;
+        if (c + 1 < NCHUNK) { load_w(c + 1); load_x(c + 1); }
+        __syncthreads();
         // ---- phase B: depthwise from E, weights from the LDS stage
         f32x4 d[MTC];
         {
@@ -1970,12 +1926,10 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
             for (int iy = 0; iy < (MTC - 1) * ST + KS; ++iy) {
 #pragma unroll
                 for (int kx = 0; kx < KS; ++kx) {
-                    if ((FEAR_ABL & 4) && (iy | kx)) continue;
                     const f32x4 v = *reinterpret_cast<const f32x4*>(Ebase + (iy * IWR + kx) * EPX);
 #pragma unroll
                     for (int r = 0; r < MTC; ++r) {
                         const int ky = iy - r * ST;
-                        if (FEAR_ABL & 32) { d[r].x += v.x; continue; }
                         if (ky >= 0 && ky < KS) d[r] += v * *reinterpret_cast<const f32x4*>(wd + (ky * KS + kx) * 16);
                     }
                 }
@@ -1998,7 +1952,6 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
                         accp[r][nt] += *reinterpret_cast<const f32x4*>(E + G::eo(((r0 + r) * ST + P) * IWR + (seg * 16 + li) * ST + P, lk));
                 }
         }
-        const long long tk4 = (FEAR_ABL & 4096) ? wall_clock64() : 0;
         // ---- phase C: projection
 #pragma unroll
         for (int nt = 0; nt < NTP; ++nt) {
@@ -2006,21 +1959,13 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
 #pragma unroll
-                for (int r = 0; r < MTC; ++r) {
-                    if (FEAR_ABL & 16) { accp[r][nt] += wp * d[r][q]; continue; }
+                for (int r = 0; r < MTC; ++r)
                     accp[r][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[q], d[r][q], accp[r][nt], 0, 0, 0);
-                }
         }
-        const long long tk5 = (FEAR_ABL & 4096) ? wall_clock64() : 0;
-        if (c + 1 < NCHUNK && !(FEAR_ABL & 2)) store_w(c + 1);
+        if (c + 1 < NCHUNK) store_w(c + 1);
         // !EXPAND: E is rewritten by the next chunk (EXPAND syncs at loop top); after the last chunk nothing writes LDS any more
-        if (((!EXPAND && c + 1 < NCHUNK) || ((FEAR_ABL & 8192) && c + 1 == NCHUNK)) && !(FEAR_ABL & 1)) __syncthreads();
-        if (FEAR_ABL & 4096) {
-            const long long tk6 = wall_clock64();
-            tm[0] += tk1 - tk0; tm[1] += tk2 - tk1; tm[2] += tk3 - tk2; tm[3] += tk4 - tk3; tm[4] += tk5 - tk4; tm[5] += tk6 - tk5;
-        }
+        if (!EXPAND && c + 1 < NCHUNK) __syncthreads();
     }
-    const long long tk_loop_end = (FEAR_ABL & 4096) ? wall_clock64() : 0;
 
     if (KSPLIT) {
         float* Yp = a.Y + (long)blockIdx.y * a.kc_part_stride;
@@ -2054,14 +1999,8 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v2_kernel(IrT2Args t) {
             if (STEM) v += *reinterpret_cast<const f32x4*>(E + G::eo((r0 + r + P) * IWR + seg * 16 + li + P, lk));   // NTP == 1: n = 4 * lk
             else if (a.R && n_ok && !res_from_tile) v += ld_act4<(IO & IO_R_BF16) != 0>(a.R, mrow * a.ldr + nt * 16 + (long)rlane);
             v.x = fmaxf(v.x, relu_lo); v.y = fmaxf(v.y, relu_lo); v.z = fmaxf(v.z, relu_lo); v.w = fmaxf(v.w, relu_lo);
-            if (n_ok && (!(FEAR_ABL & 2048) || v.x == 1234.5f)) st_act4<(IO & IO_Y_BF16) != 0>(a.Y, mrow * a.ldy + nt * 16 + (long)ylane, v);
+            if (n_ok) st_act4<(IO & IO_Y_BF16) != 0>(a.Y, mrow * a.ldy + nt * 16 + (long)ylane, v);
         }
-    }
-    if ((FEAR_ABL & 4096) && a.P_Y && blockIdx.x == 1000 && lane == 0) {
-        float* dbg = a.P_Y + wave * 10;
-        for (int q = 0; q < 6; ++q) dbg[q] = (float)tm[q];
-        dbg[6] = (float)(tk_begin - tk_start);
-        dbg[7] = (float)(wall_clock64() - tk_loop_end);
     }
 }
 
@@ -2452,7 +2391,7 @@ __global__ __launch_bounds__(512, MINW) void ir_tile_v4_kernel(IrT2Args t) {
                     constexpr int k = single ? w : w >> 1;                      // k-step index within the m-tile, 0 .. MPT - 1
                     if constexpr (!(single && w >= MPT)) {
                         constexpr int kg = k / 4, q = k % 4;
-                        if (!FEAR_V4_GUARD || i < cnt) eacc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[kg][q], xf[i][kg][q], eacc[i], 0, 0, 0);
+                        eacc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[kg][q], xf[i][kg][q], eacc[i], 0, 0, 0);
                     }
                 });
             }
@@ -2703,8 +2642,7 @@ __global__ __launch_bounds__(512) void ir16h_fused_kernel(Ir2Args a) {
     using G = IrHGeom<CIN, CEXP, COUT, KS, EXPAND>;
     constexpr int S = G::S, P = G::P, PW = G::RW, ES = G::ES, NCHUNK = G::NCHUNK, NTP = G::NTP, KG = G::KG;
     constexpr int AP = G::AP, BP = G::BP, EBUF = G::EBUF, CST = AP + BP;
-    constexpr int AP4 = AP / 4, BP4 = BP / 4;
-    constexpr int NRA = (AP4 + 511) / 512, NRB = (BP4 + 511) / 512;
+    constexpr int BP4 = BP / 4, NRB = (BP4 + 511) / 512;
     static_assert(COUT % 16 == 0 && (EXPAND || CIN == CEXP), "shape");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* const Ebuf = lds;                    // [2][EBUF]
@@ -2745,41 +2683,26 @@ __global__ __launch_bounds__(512) void ir16h_fused_kernel(Ir2Args a) {
             }
     }
 
-    f32x4 ra[EXPAND ? (NRA > 0 ? NRA : 1) : 4], rb[NRB];
-    auto load_a = [&](int c) {      // EXPAND: A-part of chunk c; !EXPAND: this lane's 8 channels x 2 pixels of chunk c
-        if (EXPAND) {
+    // blocks without expansion stage through registers: the activations of chunk c (this lane's 8 channels x 2 pixels) -> E[c & 1],
+    // the B part of chunk c's packed weights -> WB[c & 1]
+    f32x4 rx[4], rb[NRB];
+    auto load_x = [&](int c) {
 #pragma unroll
-            for (int r = 0; r < NRA; ++r) {
-                const int idx = tid + r * 512;
-                if (idx < AP4) ra[r] = *reinterpret_cast<const f32x4*>(a.Wpk + (long)c * CST + idx * 4);
-            }
-        } else {
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                const int k = c * 32 + lk * 8;
-                const float* px = Xc + (long)((y0 + mt) * S + li) * a.ldx + k;
-                ra[2 * mt] = ra[2 * mt + 1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (k < CIN) ra[2 * mt] = *reinterpret_cast<const f32x4*>(px);
-                if (k + 4 < CIN) ra[2 * mt + 1] = *reinterpret_cast<const f32x4*>(px + 4);
-            }
+        for (int mt = 0; mt < 2; ++mt) {
+            const int k = c * 32 + lk * 8;
+            const float* px = Xc + (long)((y0 + mt) * S + li) * a.ldx + k;
+            rx[2 * mt] = rx[2 * mt + 1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (k < CIN) rx[2 * mt] = *reinterpret_cast<const f32x4*>(px);
+            if (k + 4 < CIN) rx[2 * mt + 1] = *reinterpret_cast<const f32x4*>(px + 4);
         }
     };
-    auto store_a = [&](int c) {
-        if (EXPAND) {
-            float* dst = WA + (c & 1) * AP;
+    auto store_x = [&](int c) {
+        float* E = Ebuf + (c & 1) * EBUF;
 #pragma unroll
-            for (int r = 0; r < NRA; ++r) {
-                const int idx = tid + r * 512;
-                if (idx < AP4) *reinterpret_cast<f32x4*>(dst + idx * 4) = ra[r];
-            }
-        } else {
-            float* E = Ebuf + (c & 1) * EBUF;
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                float* e = E + ((y0 + mt + P) * PW + li + P) * ES + lk * 4;      // [h][lk][4]: h = 0 | h = 1 at +16
-                *reinterpret_cast<f32x4*>(e) = ra[2 * mt];
-                *reinterpret_cast<f32x4*>(e + 16) = ra[2 * mt + 1];
-            }
+        for (int mt = 0; mt < 2; ++mt) {
+            float* e = E + ((y0 + mt + P) * PW + li + P) * ES + lk * 4;      // [h][lk][4]: h = 0 | h = 1 at +16
+            *reinterpret_cast<f32x4*>(e) = rx[2 * mt];
+            *reinterpret_cast<f32x4*>(e + 16) = rx[2 * mt + 1];
         }
     };
     auto load_b = [&](int c) {
@@ -2815,10 +2738,7 @@ __global__ __launch_bounds__(512) void ir16h_fused_kernel(Ir2Args a) {
             for (int nt = 0; nt < 2; ++nt) {
                 const V8 wf = *reinterpret_cast<const V8*>(wa + (nt * KG + kg) * 256 + lane * 4);
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    if (FEAR_ABL & 8) { acc[mt][nt].x += (float)wf[0]; continue; }
-                    acc[mt][nt] = MX::mma(wf, xhi[mt][kg], xlo[mt][kg], acc[mt][nt]);
-                }
+                for (int mt = 0; mt < 2; ++mt) acc[mt][nt] = MX::mma(wf, xhi[mt][kg], xlo[mt][kg], acc[mt][nt]);
             }
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
@@ -2879,7 +2799,7 @@ __global__ __launch_bounds__(512) void ir16h_fused_kernel(Ir2Args a) {
                 for (int h = 0; h < 2; ++h) {
                     e[h] = ev[t % D][h];
                     w[h] = wv[t % D][h];
-                    if (t + D < NS && !(FEAR_ABL & 4)) {
+                    if (t + D < NS) {
                         const int kx2 = (t + D) / (KS + 1), iy2 = (t + D) % (KS + 1);
                         ev[t % D][h] = *reinterpret_cast<const f32x4*>(e0 + (iy2 * PW + kx2) * ES + h * 16);
                         if (iy2 < KS) wv[t % D][h] = *reinterpret_cast<const f32x4*>(wd + (iy2 * KS + kx2) * 32 + h * 4);
@@ -2887,7 +2807,6 @@ __global__ __launch_bounds__(512) void ir16h_fused_kernel(Ir2Args a) {
                 }
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    if (FEAR_ABL & 32) { d0[h].x += e[h].x + w[h].x; continue; }
                     if (iy < KS) pk_fma4(d0[h], e[h], w[h]);
                     if (iy >= 1) pk_fma4(d1[h], e[h], wprev[h]);
                     wprev[h] = w[h];
@@ -2948,18 +2867,15 @@ __global__ __launch_bounds__(512) void ir16h_fused_kernel(Ir2Args a) {
         for (int nt = 0; nt < NTP; ++nt) {
             const V8 wp = *reinterpret_cast<const V8*>(wb + nt * 256 + lane * 4);
 #pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                if (FEAR_ABL & 16) { accp[r][nt].x += (float)wp[0] + (float)dhi[r][0]; continue; }
-                accp[r][nt] = MX::mma(wp, dhi[r], dlo[r], accp[r][nt]);
-            }
+            for (int r = 0; r < 2; ++r) accp[r][nt] = MX::mma(wp, dhi[r], dlo[r], accp[r][nt]);
         }
     };
 
-    if constexpr (EXPAND && IR16H_ASYNC) {
+    if constexpr (EXPAND) {
         // The packed weights go global -> LDS by asynchronous copies (global_load_lds_dwordx4: no staging registers, no ds_write),
         // as in chain16_block: issued at the top of an interval into the stage the previous interval read last, complete at the
-        // interval's barrier.  (Round 2's form — two or three loads and ds_write_b128 per thread and chunk through `ra` / `rb` —
-        // stays for the blocks without expansion, whose A part is the activation itself.)
+        // interval's barrier.  (Round 2's form — loads and ds_write_b128 per thread and chunk through registers — stays for the
+        // blocks without expansion, whose A part is the activation itself.)
         const int wave_s = __builtin_amdgcn_readfirstlane(wave);
         auto stage_a = [&](int c) { lds_copy_async<AP>(a.Wpk + (long)c * CST, WA + (c & 1) * AP, wave_s, lane); };
         auto stage_b = [&](int c) { lds_copy_async<BP>(a.Wpk + (long)c * CST + AP, WB + (c & 1) * BP, wave_s, lane); };
@@ -2979,32 +2895,23 @@ __global__ __launch_bounds__(512) void ir16h_fused_kernel(Ir2Args a) {
         phase_bc(NCHUNK - 1);
         __syncthreads();
     } else {
-    // ---- prologue: stage A(0), A(1), BC(0); produce E[0]
-    load_a(0);
-    load_b(0);
-    __syncthreads();
-    store_a(0);
-    store_b(0);
-    if (EXPAND) {
-        if (NCHUNK > 1) { load_a(1); store_a(1); }
+        // ---- prologue: stage E[0] and BC(0)
+        load_x(0);
+        load_b(0);
         __syncthreads();
-        phase_a(0);
-    }
-    __syncthreads();
-
-    // (the last chunk is peeled: no run-time branch around the expansion phase inside the loop — chain16_block's change)
-    for (int c = 0; c < NCHUNK - 1; ++c) {
-        const int ca = EXPAND ? c + 2 : c + 1;
-        if (ca < NCHUNK) load_a(ca);
-        load_b(c + 1);
-        if (EXPAND) phase_a(c + 1);
-        phase_bc(c);
-        if (ca < NCHUNK) store_a(ca);
-        store_b(c + 1);
+        store_x(0);
+        store_b(0);
         __syncthreads();
-    }
-    phase_bc(NCHUNK - 1);
-    __syncthreads();
+        for (int c = 0; c < NCHUNK - 1; ++c) {
+            load_x(c + 1);
+            load_b(c + 1);
+            phase_bc(c);
+            store_x(c + 1);
+            store_b(c + 1);
+            __syncthreads();
+        }
+        phase_bc(NCHUNK - 1);
+        __syncthreads();
     }
 
     if (a.pred_cout > 0) {          // prediction head: lanes lk == 0 hold channels 0..3 of their pixel
@@ -3036,7 +2943,7 @@ __global__ __launch_bounds__(512) void ir16h_fused_kernel(Ir2Args a) {
             f32x4 v = accp[mt][nt] + b;
             if (a.R) v += *reinterpret_cast<const f32x4*>(a.R + m * a.ldr + n);
             if (a.relu_out) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-            if (!(FEAR_ABL & 2048) || v.x == 1234.5f) *reinterpret_cast<f32x4*>(a.Y + m * a.ldy + n) = v;
+            *reinterpret_cast<f32x4*>(a.Y + m * a.ldy + n) = v;
         }
     }
 }
@@ -3419,7 +3326,6 @@ __device__ __forceinline__ void chain16_block(const f32x4 (&xin)[2][B::CIN / 16]
     }
     phase_a(0);
     __syncthreads();
-#if CHAIN16_PEEL
     // (the last chunk — nothing left to expand — is peeled instead of branching around two instantiations of the interval inside
     //  the loop: chain32's A/B of the same change, profiles/r06_chain32_kbench.txt)
     for (int c = 0; c < NCHUNK - 1; ++c) {
@@ -3445,19 +3351,6 @@ __device__ __forceinline__ void chain16_block(const f32x4 (&xin)[2][B::CIN / 16]
                                                      WB + (c & 1) * BP_MAX, xin, accp, y0, li, lk, lane, true);
         __syncthreads();
     }
-#else
-    for (int c = 0; c < NCHUNK; ++c) {
-        if (c + 2 < NCHUNK) stage_a(c + 2);
-        if (c + 1 < NCHUNK) stage_b(c + 1);
-        const float* Ec = Ebuf + (c & 1) * EBUF;
-        float* En = Ebuf + ((c + 1) & 1) * EBUF;
-        const float* wa = WA + ((c + 1) & 1) * AP_MAX;
-        const float* wb = WB + (c & 1) * BP_MAX;
-        if (c + 1 < NCHUNK) ir16_interval<B::KS, PW, ES, KG, NTP, true>(Ec, En, wa, wb, xin, accp, y0, li, lk, lane, true);
-        else ir16_interval<B::KS, PW, ES, KG, NTP, false>(Ec, En, wa, wb, xin, accp, y0, li, lk, lane, true);
-        __syncthreads();
-    }
-#endif
 }
 
 // FEAR-XS stride-16 stage: 7 blocks + neck.  (The engine matches the model's block table against this chain.)

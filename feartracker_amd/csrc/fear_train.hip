@@ -1132,9 +1132,6 @@ int col_blocks(long M) { const int r = col_rows_per_block(M); return (int)((M + 
 #ifndef FEAR_WGRAD_ROWS
 #define FEAR_WGRAD_ROWS 1024
 #endif
-#ifndef FEAR_WGRAD_SMALLK
-#define FEAR_WGRAD_SMALLK 1   // 0: every weight gradient on the 64 x 64 tile kernel (A/B)
-#endif
 long wgrad_rows_per_slice(long M) {
     long r = FEAR_WGRAD_ROWS;
     while ((M + r - 1) / r > 256) r *= 2;
@@ -1558,7 +1555,7 @@ static int wgrad_impl(const float* dy, int lddy, long dy_crop_stride, const floa
     }
     a.dy_crop_stride = dy_crop_stride; a.x_crop_stride = x_crop_stride;
     // a narrow dY against a wide X (the projections of the large maps): the operands trade places in pw_wgrad_smallk_kernel<., 2>
-    if (FEAR_WGRAD_SMALLK && crops == 1 && N <= 32 && K > 32 && !stem && !(bn && bn->mask_a) && (!bn || bn->E)) {
+    if (crops == 1 && N <= 32 && K > 32 && !stem && !(bn && bn->mask_a) && (!bn || bn->E)) {
         a.dY = x; a.lddy = ldx; a.N = K; a.X = dy; a.ldx = lddy; a.K = N;
         a.n_tiles = (K + 63) / 64; a.k_tiles = 1;
         a.rows_per_slice = wgrad_rows_per_slice(M);
@@ -1588,19 +1585,16 @@ static int wgrad_impl(const float* dy, int lddy, long dy_crop_stride, const floa
     a.n_tiles = (N + 63) / 64; a.k_tiles = (K + 63) / 64;
     // 128 x 128 tiles with the rows staged through LDS (wgrad_lds_kernel, fear_train_gemm.h) where both sides are wide enough for
     // the sharing to matter and the launch is one problem, not a batch of per-crop ones
-#ifndef FEAR_WGRAD_LDS
-#define FEAR_WGRAD_LDS 1
-#endif
     // (launches of a few thousand rows are a handful of stages per workgroup: the staged kernel's prologue and its two
     //  barriers-per-stage floor — 29 us measured — lose against the 14 us of the register-only kernel there)
-    const bool lds_tile = FEAR_WGRAD_LDS && crops == 1 && K > 32 && N >= 32 && M >= 16384;
+    const bool lds_tile = crops == 1 && K > 32 && N >= 32 && M >= 16384;
     if (lds_tile) { a.n_tiles = (N + 127) / 128; a.k_tiles = (K + 127) / 128; }
     a.rows_per_slice = crops > 1 ? M : wgrad_rows_per_slice(M);
     if (crops == 1) {
         // few output tiles (the 16 x 16 maps' layers: 2-22 tiles x 8-32 slices of 1 024 rows) leave most of the 256 CUs idle while
         // every wave walks its 16 steps of 64 dependent MFMAs: such launches sat on a 31 us floor whatever their size.  Cut the rows
         // finer — down to 256 per slice — until there are ~768 workgroups, as far as the caller's workspace holds the partials.
-        const long tiles = (FEAR_WGRAD_SMALLK && K <= 32) ? a.n_tiles : (long)a.n_tiles * a.k_tiles;
+        const long tiles = K <= 32 ? a.n_tiles : (long)a.n_tiles * a.k_tiles;
         const long want = (768 + tiles - 1) / tiles;
         long cap_ws = workspace ? (long)(ws_bytes / ((size_t)N * K * sizeof(float))) : 1;
         if (cap_ws < 1) cap_ws = 1;      // a workspace smaller than one partial: no finer slicing; the size check below reports it
@@ -1624,9 +1618,9 @@ static int wgrad_impl(const float* dy, int lddy, long dy_crop_stride, const floa
         if (!workspace || ws_bytes < need) return FEAR_TRAIN_ERR_WORKSPACE;
         a.P = workspace;
     }
-    if (FEAR_WGRAD_SMALLK && K <= 16) hipLaunchKernelGGL(pw_wgrad_smallk_kernel<1>, dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
-    else if (FEAR_WGRAD_SMALLK && K <= 32 && stem) hipLaunchKernelGGL((pw_wgrad_smallk_kernel<2, 1>), dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
-    else if (FEAR_WGRAD_SMALLK && K <= 32) hipLaunchKernelGGL(pw_wgrad_smallk_kernel<2>, dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
+    if (K <= 16) hipLaunchKernelGGL(pw_wgrad_smallk_kernel<1>, dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
+    else if (K <= 32 && stem) hipLaunchKernelGGL((pw_wgrad_smallk_kernel<2, 1>), dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
+    else if (K <= 32) hipLaunchKernelGGL(pw_wgrad_smallk_kernel<2>, dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
     else if (lds_tile) hipLaunchKernelGGL(wgrad_lds_kernel<0>, dim3(a.n_tiles * a.k_tiles, slices), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(pw_wgrad_kernel, dim3(a.n_tiles * a.k_tiles, slices, crops), dim3(256), 0, s, a);
     if (slices > 1) {

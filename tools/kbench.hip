@@ -9,15 +9,9 @@
 #include <cstring>
 #include <vector>
 
-#ifndef KHDR
-#define KHDR "../feartracker_amd/csrc/fear_kernels.h"     // -DKHDR='"/path/to/variant.h"' benches a saved variant of the header
-#endif
-#include KHDR
+#include "../feartracker_amd/csrc/fear_kernels.h"
 #include "../feartracker_amd/csrc/fear_e1pair.h"
 #include "../feartracker_amd/csrc/fear_chain32.h"
-#ifdef FEAR_E1PAIR_REF
-#include FEAR_E1PAIR_REF        // round 5's kernel with its symbols renamed (tools/_kb/e1pair_r5.h, made by: git show <rev>:...fear_e1pair.h | sed ...)
-#endif
 
 using namespace fear;
 
@@ -78,10 +72,6 @@ static void bench_tile(const char* tag, int crops, int iters, int hw) {
     CK(hipMalloc(&y, (size_t)crops * ho * ho * COUT * sizeof(float)));
     a.Y = y; a.relu_dw = 1; a.relu_out = 0;
     if (!EXPAND && CIN == COUT && ST == 1) a.R = a.X;     // an e1 block's residual is its input
-    float* dbg;
-    CK(hipMalloc(&dbg, 80 * sizeof(float)));
-    CK(hipMemset(dbg, 0, 80 * sizeof(float)));
-    a.P_Y = dbg;
     t.H = hw; t.W = hw; t.tiles_x = ho / TW; t.tiles_y = ho / TH;
     auto k = ir_tile_v2_kernel<CIN, CEXP, COUT, KS, ST, TW, TH, EXPAND, MINW>;
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
@@ -98,14 +88,6 @@ static void bench_tile(const char* tag, int crops, int iters, int hw) {
     CK(hipEventElapsedTime(&ms, e0, e1));
     const double us = 1e3 * ms / iters;
     printf("%-24s fp32-tile  %8.1f us  %6.1f TF/s  (LDS %d B)\n", tag, us, flops / us * 1e-6, G::LDS_BYTES);
-    if (FEAR_ABL & 4096) {
-        float h[80];
-        CK(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
-        for (int w = 0; w < 8; w += 4)
-            printf("   wave %d (block 1000): prologue %.2f | top barrier %.2f | phase A %.2f | mid barrier %.2f | phase B %.2f | phase C %.2f | end %.2f | epilogue %.2f us\n",
-                   w, h[w * 10 + 6] * 0.01, h[w * 10] * 0.01, h[w * 10 + 1] * 0.01, h[w * 10 + 2] * 0.01, h[w * 10 + 3] * 0.01,
-                   h[w * 10 + 4] * 0.01, h[w * 10 + 5] * 0.01, h[w * 10 + 7] * 0.01);
-    }
 }
 
 // v2 against v4 (phase-overlapped) on the same tile: same inputs and packed weights, outputs compared, both timed
@@ -327,27 +309,6 @@ static void bench_e1pair(int crops, int iters) {
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     std::vector<float> ref(ny), out(ny);
-#ifdef FEAR_E1PAIR_REF
-    std::vector<float> r5(ny);
-    {
-        E1PairR5Args b{};
-        b.X = a.X; b.Wpk = a.Wpk; b.Y = y; b.H = hw; b.W = hw; b.tiles_x = a.tiles_x; b.tiles_y = a.tiles_y;
-        CK(hipFuncSetAttribute(reinterpret_cast<const void*>(e1pair_r5_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, E1PairR5Geom::LDS_BYTES));
-        const dim3 grid((unsigned)crops * 16);
-        for (int rep = 0; rep < 2; ++rep) {
-            for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(e1pair_r5_kernel, grid, dim3(512), E1PairR5Geom::LDS_BYTES, 0, b);
-            CK(hipDeviceSynchronize());
-            CK(hipEventRecord(e0));
-            for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(e1pair_r5_kernel, grid, dim3(512), E1PairR5Geom::LDS_BYTES, 0, b);
-            CK(hipEventRecord(e1));
-            CK(hipEventSynchronize(e1));
-            float ms;
-            CK(hipEventElapsedTime(&ms, e0, e1));
-            printf("e1pair round-5 kernel                                         %8.1f us\n", 1e3 * ms / iters);
-        }
-        CK(hipMemcpy(r5.data(), y, ny * sizeof(float), hipMemcpyDeviceToHost));
-    }
-#endif
     // tiles per workgroup: 1 = one launch slot per tile (round 4's form), 8 = 512 workgroups at 256 crops
     for (int rep = 0; rep < 2; ++rep)
         for (int tpw : {1, 2, 4, 8, 16}) {
@@ -365,16 +326,9 @@ static void bench_e1pair(int crops, int iters) {
             CK(hipEventElapsedTime(&ms, e0, e1));
             CK(hipMemcpy(out.data(), y, ny * sizeof(float), hipMemcpyDeviceToHost));
             size_t bad = 0;
-            if (tpw == 1) {
-                ref = out;
-#ifdef FEAR_E1PAIR_REF
-                size_t b5 = 0;
-                for (size_t i = 0; i < ny; ++i) b5 += memcmp(&r5[i], &out[i], 4) != 0;
-                if (rep == 0) printf("   against the round-5 kernel: %s (%zu of %zu differ)\n", b5 ? "MISMATCH" : "bit-identical", b5, ny);
-#endif
-            }
+            if (tpw == 1) ref = out;
             else for (size_t i = 0; i < ny; ++i) bad += memcmp(&ref[i], &out[i], 4) != 0;
-            printf("e1pair 24ch hw64 (E1P_ABL=%d, E1P_SKEW=%d, E1P_NA=%d) tiles/workgroup %2d  %8.1f us  (LDS %d B)  %s\n", E1P_ABL, E1P_SKEW, E1P_NA, tpw, 1e3 * ms / iters,
+            printf("e1pair 24ch hw64 (E1P_NA=%d) tiles/workgroup %2d  %8.1f us  (LDS %d B)  %s\n", E1P_NA, tpw, 1e3 * ms / iters,
                    G::LDS_BYTES, tpw == 1 ? "" : bad ? "MISMATCH vs 1 tile/workgroup" : "bit-identical to 1 tile/workgroup");
         }
 }
@@ -422,7 +376,6 @@ int main(int argc, char** argv) {
     const int crops = argc > 1 ? atoi(argv[1]) : 256;
     const int iters = argc > 2 ? atoi(argv[2]) : 20;
     const bool all = argc > 3;      // any third argument: also the tile-shape sweep and the 16x16 kernels
-    printf("FEAR_ABL=%d\n", FEAR_ABL);
     // the product's tile table (fear_engine.hip kFusedTile), in plan order
 #ifdef FEAR_E1PAIR_ONLY
     bench_e1pair(crops, iters);
@@ -455,7 +408,7 @@ int main(int argc, char** argv) {
             float ms;
             CK(hipEventElapsedTime(&ms, e0, e1));
             const double us = 1e3 * ms / iters, gf = 25.3 * crops / 256.0;
-            printf("chain32 (C32_D=%d D2=%d GS2=%d ABL=%d)  %8.1f us per %d crops  %6.1f TF/s\n", C32_D, C32_D2, C32_GS2, C32_ABL, us, crops, gf / us * 1e-3);
+            printf("chain32 (C32_D4=%d D2=%d GS2=%d)  %8.1f us per %d crops  %6.1f TF/s\n", C32_D4, C32_D2, C32_GS2, us, crops, gf / us * 1e-3);
         }
     }
     return 0;
@@ -467,13 +420,13 @@ int main(int argc, char** argv) {
             using G = IrHGeom<112, 672, 112, 5, true>;
             Ir2Args a = make_args<112, 112>(crops, (size_t)G::NCHUNK * (G::AP + G::BP));
             const double us = time_kernel(ir16h_fused_kernel<112, 672, 112, 5, true, 2>, G::LDS_BYTES, crops, iters, a);
-            printf("ir16h_112x672x112_k5 bf16 (FEAR_ABL=%d, IR16H_D=%d)  %8.1f us per %d crops\n", FEAR_ABL, IR16H_D, us, crops);
+            printf("ir16h_112x672x112_k5 bf16 (IR16H_D=%d)  %8.1f us per %d crops\n", IR16H_D, us, crops);
         }
         {
             using G = IrHGeom<64, 384, 64, 5, true>;
             Ir2Args a = make_args<64, 64>(crops, (size_t)G::NCHUNK * (G::AP + G::BP));
             const double us = time_kernel(ir16h_fused_kernel<64, 384, 64, 5, true, 2>, G::LDS_BYTES, crops, iters, a);
-            printf("ir16h_64x384x64_k5   bf16 (FEAR_ABL=%d, IR16H_D=%d)  %8.1f us per %d crops\n", FEAR_ABL, IR16H_D, us, crops);
+            printf("ir16h_64x384x64_k5   bf16 (IR16H_D=%d)  %8.1f us per %d crops\n", IR16H_D, us, crops);
         }
     }
     return 0;
