@@ -101,6 +101,10 @@ struct Conv {
     bool is_pw() const { return groups == 1 && k == 1; }
 };
 
+struct Fused16Row;
+struct TileRow;
+struct TileK;
+
 enum OpType { OP_STEM, OP_PW, OP_DW, OP_CORR, OP_PW_SMALL, OP_IR16, OP_IRTILE, OP_CHAIN16, OP_HEADCHAIN, OP_E1PAIR, OP_CHAIN32, OP_CHAIN32_16 };
 
 struct Op {
@@ -119,7 +123,6 @@ struct Op {
     int pred_fused = 0;       // OP_IR16 (sep16): the prediction SepConv that consumes this layer runs in its epilogue
     float* pred_packed = nullptr;
     int pred_conv_p = -1;
-    int small_tiles = 0;      // OP_IRTILE: 1 = kFusedTileSmall (small-batch plan), 2 = kFusedTileTiny (a handful of crops)
     int pw_split = 0;         // OP_PW / OP_CORR: spread the output-channel passes over gridDim.y workgroups (small-batch plan)
     int splitk = 0;           // OP_IR16: > 0 = workgroups per crop (split over expansion chunks) + a reduce launch
     int tiny = 0;             // OP_IR16 (sep16, 16 output channels per workgroup): sep16_tiny_kernel (Fused16::kernel_tiny)
@@ -129,12 +132,14 @@ struct Op {
     int corr_fused = 0;       // OP_IR16 (sep16): the pixel-wise correlation runs in this kernel's epilogue
     int conv_e = -1, conv_d = -1, conv_p = -1;  // OP_IR16: expand (or -1) / depthwise / project convs
     int relu_dw = 0;
-    int fused_id = -1;        // OP_IR16: index into the fused-kernel table
+    const Fused16Row* f16 = nullptr;   // OP_IR16: the registry row of its kernels
+    const TileRow* tile = nullptr;     // OP_IRTILE: the registry row of its kernels ...
+    const TileK* tk = nullptr;         //            ... and the variant this plan runs
     float* d_packed = nullptr; // OP_IR16: per-chunk packed weights (Ir2Geom layout), owned by the handle
-    int math = 0;              // OP_IR16: 1 = fp16-split matrix-pipe kernel
+    int math = 0;              // OP_IR16 / OP_HEADCHAIN: the FEAR_OPT_MATH variant it runs
     int pred_cout = 0;         // OP_IR16 prediction head: real output channels (4 / 1), NCHW external output
     int stem = 0;              // OP_IRTILE: stem conv fused in front (reads the caller's NCHW image)
-    int io_bf16 = 0;           // OP_IRTILE: IO_X_BF16 | IO_Y_BF16 | IO_R_BF16 — which of its tensors are stored in bf16 (kTileBf16)
+    int io_bf16 = 0;           // OP_IRTILE: IO_X_BF16 | IO_Y_BF16 | IO_R_BF16 — which of its tensors are stored in bf16 (TileRow::bf16_io)
     // OP_CHAIN16: per-block packed weights / projection convs, neck fragments
     float* chain_pk[8] = {nullptr};
     int chain_cp[8] = {0};
@@ -160,8 +165,15 @@ struct Op {
     int64_t prof_n = 0;
 };
 
+// the plan kinds of a handle, by the crop count of a pass (plan_kind)
+enum class PlanKind {
+    Throughput,     // full passes
+    Small,          // small passes: split-K 16x16 kernels, smaller tiles, the head's branches on two streams
+    Tiny,           // a handful of crops: the small-batch plan with the deepest split
+    MidSize,        // passes above FEAR_OPT_SMALL_PASS and below FEAR_CHAIN32_MIN_CROPS: the throughput plan without the 32 x 32 chain
+};
+
 struct Plan {
-    int hw = 0;
     bool with_head = false;
     bool small = false;
     std::vector<Op> ops;
@@ -183,7 +195,7 @@ struct fear_handle {
     int profile_op = -1;   // -1: every op, else only this op index of each plan
     int fuse = 1;          // 1: use the fused block kernels where an instantiation exists
     int tiny_sep = 1;      // FEAR_OPT_TINY_SEP: 1 = the tiny plan's 16-channel SepConv slices run sep16_tiny_kernel
-    int tile_v4 = 1;       // FEAR_OPT_TILE_V4: 1 = phase-overlapped tile kernel for the blocks of kFusedTileV4 (throughput plan)
+    int tile_v4 = 1;       // FEAR_OPT_TILE_V4: 1 = phase-overlapped tile kernel for the blocks with a v4 variant in kTiles (throughput plan)
     int chain = 1;         // 1: run the stride-16 trunk stage as one register-resident chain kernel (fp32 mode)
     int bf16_store = 1;    // FEAR_OPT_BF16_STORE: math 2 keeps the activations of the trunk's HBM-bound front in bf16 between kernels
     int chain32 = 2;       // FEAR_OPT_CHAIN32: 1 = the 32 x 32 trunk stage (four blocks) as one register-resident chain kernel (chain32_kernel; fp32 mode, throughput plan), 2 = in one launch with the stride-16 stage + neck (chain32_16_kernel) when FEAR_OPT_CHAIN is on as well
@@ -330,237 +342,6 @@ int pack_weights(fear_handle* h) {
 }
 
 
-// ---------------------------------------------------------------------------------------------
-// Fused 16x16 block kernels (ir16_fused_kernel): one instantiation per (CIN, CEXP, COUT, KS, EXPAND).
-struct Fused16 {
-    int cin, cexp, cout, ks, expand;
-    void (*kernel)(Ir2Args);
-    int lds_bytes;
-    void (*kernel_splitk)(Ir2Args);     // small-batch variant: several workgroups per crop, one chunk range each (or nullptr)
-    int splitk_kc;                      // chunks per workgroup compiled into that variant (0: run-time, Ir2Args::kc_count)
-    void (*kernel_tiny)(Ir2Args);       // 16-channel output slice of kTinyRows map rows per workgroup (sep16_tiny_kernel), a handful of crops
-    int lds_tiny;
-};
-#define FUSED16(CIN, CEXP, COUT, KS, EXP) \
-    {CIN, CEXP, COUT, KS, EXP, ir16v2_fused_kernel<CIN, CEXP, COUT, KS, (EXP) != 0>, Ir2Geom<CIN, CEXP, COUT, KS, (EXP) != 0>::LDS_BYTES, \
-     ir16v2_fused_kernel<CIN, CEXP, COUT, KS, (EXP) != 0, true>, 0}
-#define SEP16(CIN, COUT, KS, KC) \
-    {CIN, CIN, COUT, KS, 0, sep16_kernel<CIN, COUT, KS>, Sep16Geom<CIN, COUT, KS>::LDS_BYTES, sep16_kernel<CIN, COUT, KS, false, false, KC>, KC}
-#ifndef FEAR_TINY_ROWS
-#define FEAR_TINY_ROWS 2
-#endif
-#ifndef FEAR_TINY_KSPLIT
-#define FEAR_TINY_KSPLIT 4
-#endif
-// (batch-1 track call, ms, rows x wave groups: 8x1 0.375 | 4x1 0.357 | 4x2 0.352 | 2x2 0.344 | 2x4 0.342; sep16_kernel<CIN, 16, 3> 0.383)
-constexpr int kTinyRows = FEAR_TINY_ROWS;       // map rows per workgroup of sep16_tiny_kernel (one wave each)
-constexpr int kTinyKSplit = FEAR_TINY_KSPLIT;   // wave groups per workgroup, each over its share of the input chunks
-#define SEP16T(CIN, KS, KC) \
-    {CIN, CIN, 16, KS, 0, sep16_kernel<CIN, 16, KS>, Sep16Geom<CIN, 16, KS>::LDS_BYTES, sep16_kernel<CIN, 16, KS, false, false, KC>, KC, \
-     sep16_tiny_kernel<CIN, KS, kTinyRows, kTinyKSplit>, Sep16TinyGeom<CIN, KS, kTinyRows, kTinyKSplit>::LDS_BYTES}
-const Fused16 kFused16[] = {
-    FUSED16(64, 192, 64, 5, 1),   FUSED16(64, 384, 64, 5, 1),  FUSED16(64, 384, 112, 5, 1),
-    FUSED16(112, 672, 112, 5, 1), FUSED16(112, 336, 112, 5, 1),
-    SEP16(256, 256, 3, 4), SEP16(320, 256, 3, 4),
-    SEP16T(256, 3, 2),                 // bbox_pred / cls_pred: 4 / 1 output channels padded to one 16-channel tile
-    SEP16T(320, 3, 2),                 // N-split slices of the 320 -> 256 SepConv (very small batches)
-};
-
-// Spatially tiled fused block kernels (ir_tile_fused_kernel) for the high-resolution trunk stages.
-struct FusedTile {
-    int cin, cexp, cout, ks, st, expand, hw;   // hw: input map size the tiling was chosen for
-    int tw, th;
-    void (*kernel)(IrT2Args);
-    int lds_bytes;
-    int nw;                                     // waves per workgroup
-};
-#define FTILE(CIN, CEXP, CEXPP, COUT, KS, ST, TW, TH, EXP, MINW, HW)                                             \
-    {CIN, CEXP, COUT, KS, ST, EXP, HW, TW, TH, ir_tile_v2_kernel<CIN, CEXPP, COUT, KS, ST, TW, TH, (EXP) != 0, MINW>, \
-     IrT2Geom<CIN, CEXPP, COUT, KS, ST, TW, TH, (EXP) != 0>::LDS_BYTES, 8}
-const FusedTile kFusedTile[] = {
-    FTILE(16, 16, 16, 16, 3, 1, 32, 16, 0, 4, 128),    // fbnet_c stage 1  (e1, 128x128)
-    FTILE(16, 96, 96, 24, 3, 2, 16, 8, 1, 4, 128),     // stage 2          (e6 s2, 128 -> 64)
-    FTILE(24, 24, 32, 24, 3, 1, 16, 16, 0, 4, 64),     // stages 4, 5      (e1, 64x64; 24 channels padded to 32)
-    FTILE(24, 144, 144, 32, 5, 2, 16, 16, 1, 2, 64),   // stage 6          (e6 s2, 64 -> 32)
-    FTILE(32, 96, 96, 32, 5, 1, 16, 16, 1, 2, 32),     // stage 7  (4 corner tiles: 18x18 clipped region)
-    FTILE(32, 192, 192, 32, 5, 1, 16, 32, 1, 2, 32),   // stage 8  (two 16x32 tiles per map: 4 rows per wave share the depthwise reads)
-    FTILE(32, 192, 192, 32, 3, 1, 32, 32, 1, 2, 32),   // stage 9  (the whole 32x32 map per workgroup: no halo to re-expand)
-    FTILE(32, 192, 192, 64, 5, 2, 16, 16, 1, 2, 32),   // stage 10         (e6 s2, 32 -> 16: the whole 16x16 output map)
-};
-#define FTILEH(CIN, CEXP, CEXPP, COUT, KS, ST, TW, TH, EXP, NW, MINW, HW)                                             \
-    {CIN, CEXP, COUT, KS, ST, EXP, HW, TW, TH,                                                                        \
-     ir_tile_h_kernel<CIN, CEXPP, COUT, KS, ST, TW, TH, (EXP) != 0, NW, MINW>,                                         \
-     IrTHGeom<CIN, CEXPP, COUT, KS, ST, TW, TH, (EXP) != 0, NW>::LDS_BYTES, NW}
-// same blocks, fp16-split operands on the matrix pipe (FEAR_OPT_MATH = 1); tiles sized for the 144 B/pixel LDS tile
-const FusedTile kFusedTileH[] = {
-    FTILEH(16, 16, 32, 16, 3, 1, 32, 8, 0, 8, 2, 128),     // stage 1
-    FTILEH(16, 96, 96, 24, 3, 2, 16, 4, 1, 4, 2, 128),     // stage 2
-    FTILEH(24, 24, 32, 24, 3, 1, 16, 16, 0, 8, 2, 64),     // stages 4, 5
-    FTILEH(24, 144, 160, 32, 5, 2, 16, 4, 1, 4, 2, 64),    // stage 6   (144 -> 160 padded channels)
-    FTILEH(32, 96, 96, 32, 5, 1, 16, 16, 1, 8, 2, 32),     // stage 7
-    FTILEH(32, 192, 192, 32, 5, 1, 16, 16, 1, 8, 2, 32),   // stage 8
-    FTILEH(32, 192, 192, 32, 3, 1, 16, 16, 1, 8, 2, 32),   // stage 9
-    FTILEH(32, 192, 192, 64, 5, 2, 16, 4, 1, 4, 2, 32),    // stage 10
-};
-static_assert(sizeof(kFusedTileH) == sizeof(kFusedTile), "the two tile tables must list the same blocks in the same order");
-#define FTILEB(CIN, CEXP, CEXPP, COUT, KS, ST, TW, TH, EXP, NW, MINW, HW)                                             \
-    {CIN, CEXP, COUT, KS, ST, EXP, HW, TW, TH,                                                                        \
-     ir_tile_h_kernel<CIN, CEXPP, COUT, KS, ST, TW, TH, (EXP) != 0, NW, MINW, 2>,                                      \
-     IrTHGeom<CIN, CEXPP, COUT, KS, ST, TW, TH, (EXP) != 0, NW>::LDS_BYTES, NW}
-// same blocks, bf16 operands (FEAR_OPT_MATH = 2): one matrix-pipe MFMA per product instead of two
-const FusedTile kFusedTileB[] = {
-    FTILEB(16, 16, 32, 16, 3, 1, 32, 8, 0, 8, 2, 128),
-    FTILEB(16, 96, 96, 24, 3, 2, 16, 4, 1, 4, 2, 128),
-    FTILEB(24, 24, 32, 24, 3, 1, 16, 16, 0, 8, 2, 64),
-    FTILEB(24, 144, 160, 32, 5, 2, 16, 4, 1, 4, 2, 64),
-    FTILEB(32, 96, 96, 32, 5, 1, 16, 16, 1, 8, 2, 32),
-    FTILEB(32, 192, 192, 32, 5, 1, 16, 16, 1, 8, 2, 32),
-    FTILEB(32, 192, 192, 32, 3, 1, 16, 16, 1, 8, 2, 32),
-    FTILEB(32, 192, 192, 64, 5, 2, 16, 4, 1, 4, 2, 32),
-};
-static_assert(sizeof(kFusedTileB) == sizeof(kFusedTile), "same blocks, same order");
-
-// stem (3x3 s2, 3 -> 16) fused in front of the first e1 block: one entry, keyed by the block's shape and map size
-const FusedTile kStemTile = {16, 16, 16, 3, 1, 0, 128, 32, 16,
-                             ir_tile_v2_kernel<27, 16, 16, 3, 1, 32, 16, true, 4, true>,
-                             IrT2Geom<27, 16, 16, 3, 1, 32, 16, true>::LDS_BYTES, 8};
-
-// FEAR_OPT_MATH = 2 with FEAR_OPT_BF16_STORE: the HBM-bound front of the trunk keeps its activations in bf16 between kernels (stem
-// output ... input of the 64 -> 32 block).  Storage variants of the tile kernels, keyed by (stem | index into the tile tables) and
-// the IO bits (fear_kernels.h: IO_X_BF16 | IO_Y_BF16 | IO_R_BF16); same tiles and LDS footprints as the entries they stand in for.
-struct TileBf16 { int stem, id, io; void (*kernel)(IrT2Args); };
-const TileBf16 kTileBf16[] = {
-    {1, -1, IO_Y_BF16, ir_tile_v2_kernel<27, 16, 16, 3, 1, 32, 16, true, 4, true, 0, IO_Y_BF16>},
-    {0, 0, IO_X_BF16 | IO_Y_BF16 | IO_R_BF16, ir_tile_v2_kernel<16, 16, 16, 3, 1, 32, 16, false, 4, false, 0, IO_X_BF16 | IO_Y_BF16 | IO_R_BF16>},
-    {0, 0, IO_X_BF16 | IO_Y_BF16, ir_tile_v2_kernel<16, 16, 16, 3, 1, 32, 16, false, 4, false, 0, IO_X_BF16 | IO_Y_BF16>},
-    {0, 1, IO_X_BF16 | IO_Y_BF16, ir_tile_h_kernel<16, 96, 24, 3, 2, 16, 4, true, 4, 2, 2, IO_X_BF16 | IO_Y_BF16>},
-    {0, 2, IO_X_BF16 | IO_Y_BF16 | IO_R_BF16, ir_tile_v2_kernel<24, 32, 24, 3, 1, 16, 16, false, 4, false, 0, IO_X_BF16 | IO_Y_BF16 | IO_R_BF16>},
-    {0, 2, IO_X_BF16 | IO_Y_BF16, ir_tile_v2_kernel<24, 32, 24, 3, 1, 16, 16, false, 4, false, 0, IO_X_BF16 | IO_Y_BF16>},
-    {0, 3, IO_X_BF16, ir_tile_h_kernel<24, 160, 32, 5, 2, 16, 4, true, 4, 2, 2, IO_X_BF16>},
-};
-const TileBf16* find_tile_bf16(int stem, int id, int io) {
-    for (const TileBf16& t : kTileBf16)
-        if (t.stem == stem && (stem || t.id == id) && t.io == io) return &t;
-    return nullptr;
-}
-
-// the same blocks with smaller tiles = more workgroups per crop, for the small-batch plan (same order as kFusedTile)
-const FusedTile kFusedTileSmall[] = {
-    FTILE(16, 16, 16, 16, 3, 1, 32, 16, 0, 4, 128),
-    FTILE(16, 96, 96, 24, 3, 2, 16, 8, 1, 4, 128),
-    FTILE(24, 24, 32, 24, 3, 1, 16, 16, 0, 4, 64),
-    FTILE(24, 144, 144, 32, 5, 2, 16, 8, 1, 4, 64),    // 8 tiles per crop instead of 4
-    FTILE(32, 96, 96, 32, 5, 1, 16, 16, 1, 2, 32),
-    FTILE(32, 192, 192, 32, 5, 1, 16, 16, 1, 2, 32),   // 4 instead of 2
-    FTILE(32, 192, 192, 32, 3, 1, 16, 16, 1, 2, 32),   // 4 instead of 2
-    FTILE(32, 192, 192, 64, 5, 2, 16, 8, 1, 2, 32),    // 2 instead of 1
-};
-static_assert(sizeof(kFusedTileSmall) == sizeof(kFusedTile), "same blocks, same order");
-// a handful of crops (tiny plan): the smallest tiles the kernel supports, a tile's chunk loop is the latency that counts
-const FusedTile kFusedTileTiny[] = {
-    FTILE(16, 16, 16, 16, 3, 1, 32, 16, 0, 4, 128),
-    FTILE(16, 96, 96, 24, 3, 2, 16, 8, 1, 4, 128),
-    FTILE(24, 24, 32, 24, 3, 1, 16, 16, 0, 4, 64),
-    FTILE(24, 144, 144, 32, 5, 2, 16, 8, 1, 4, 64),
-    FTILE(32, 96, 96, 32, 5, 1, 16, 8, 1, 2, 32),      // 8 tiles per crop
-    FTILE(32, 192, 192, 32, 5, 1, 16, 8, 1, 2, 32),    // 8
-    FTILE(32, 192, 192, 32, 3, 1, 16, 8, 1, 2, 32),    // 8
-    FTILE(32, 192, 192, 64, 5, 2, 16, 8, 1, 2, 32),
-};
-static_assert(sizeof(kFusedTileTiny) == sizeof(kFusedTile), "same blocks, same order");
-// split-K variants of tiny-plan tiles (ir_tile_v2_kernel<..., KSPLIT>): the blocks whose chunk loop is the longest serial
-// stretch of a one-crop pass get gridDim.y workgroups per tile + a splitk_reduce launch
-struct TileKSplit {
-    int id, k;                                  // index into kFusedTileTiny, chunks per workgroup
-    void (*kernel)(IrT2Args);
-    int lds_bytes;
-};
-#define TKSPLIT(ID, K, CIN, CEXP, COUT, KS, ST, TW, TH, MINW) \
-    {ID, K, ir_tile_v2_kernel<CIN, CEXP, COUT, KS, ST, TW, TH, true, MINW, false, K>, IrT2Geom<CIN, CEXP, COUT, KS, ST, TW, TH, true>::LDS_BYTES}
-const TileKSplit kTileKSplit[] = {
-    TKSPLIT(3, 3, 24, 144, 32, 5, 2, 16, 8, 4),     // stage 6:  9 chunks -> 3 workgroups per tile
-    TKSPLIT(4, 2, 32, 96, 32, 5, 1, 16, 8, 2),      // stage 7:  6 chunks -> 3
-    TKSPLIT(5, 3, 32, 192, 32, 5, 1, 16, 8, 2),     // stage 8: 12 chunks -> 4
-    TKSPLIT(6, 3, 32, 192, 32, 3, 1, 16, 8, 2),     // stage 9: 12 chunks -> 4
-    TKSPLIT(7, 2, 32, 192, 64, 5, 2, 16, 8, 2),     // stage 10: 12 chunks -> 6 (two tiles per crop)
-};
-const TileKSplit* find_tile_ksplit(int id) {
-    for (const TileKSplit& t : kTileKSplit)
-        if (t.id == id) return &t;
-    return nullptr;
-}
-// Throughput-plan blocks that run the phase-overlapped kernel (ir_tile_v4_kernel: same tile, packed weights, LDS bytes and
-// arguments as their kFusedTile entry) — the tiles whose E tile leaves room for ONE workgroup per CU, where nobody else fills
-// the LDS round trips of the depthwise; kernel = nullptr: the block stays on ir_tile_v2.  tools/kbench A/B, 256 crops
-// (profiles/r03_tile_v4_kbench.txt): stage 6 +5.5 %; stages 7-10 and 2 lose 3-25 % (the overlap costs ~90 more VGPRs: stages
-// 7 / 8 drop from 2-4 workgroups per CU to 1-2, stage 9's 8 rows per wave spill) and keep v2.
-#define FTILE4(CIN, CEXP, COUT, KS, ST, TW, TH, MINW, HW)                                                        \
-    {CIN, CEXP, COUT, KS, ST, 1, HW, TW, TH, ir_tile_v4_kernel<CIN, CEXP, COUT, KS, ST, TW, TH, MINW>,           \
-     IrT4Geom<CIN, CEXP, COUT, KS, ST, TW, TH>::LDS_BYTES, 8}
-const FusedTile kFusedTileV4[] = {
-    {}, {}, {},
-    FTILE4(24, 144, 32, 5, 2, 16, 16, 2, 64),          // stage 6
-    {}, {}, {}, {},
-};
-static_assert(sizeof(kFusedTileV4) == sizeof(kFusedTile), "same blocks, same order");
-const FusedTile& fp32_tile(int small_tiles, int id) {
-    if (small_tiles == 3) return kFusedTileV4[id];
-    return small_tiles == 2 ? kFusedTileTiny[id] : small_tiles ? kFusedTileSmall[id] : kFusedTile[id];
-}
-
-int find_fused_tile(int cin, int cexp, int cout, int ks, int st, int expand, int hw) {
-    for (size_t i = 0; i < sizeof(kFusedTile) / sizeof(kFusedTile[0]); ++i) {
-        const FusedTile& f = kFusedTile[i];
-        if (f.cin == cin && f.cexp == cexp && f.cout == cout && f.ks == ks && f.st == st && f.expand == expand &&
-            f.hw == hw)
-            return (int)i;
-    }
-    return -1;
-}
-
-#define FUSED16H(CIN, CEXP, COUT, KS, EXP) \
-    {CIN, CEXP, COUT, KS, EXP, ir16h_fused_kernel<CIN, CEXP, COUT, KS, (EXP) != 0>, IrHGeom<CIN, CEXP, COUT, KS, (EXP) != 0>::LDS_BYTES}
-// same shapes as kFused16, fp16-split operands on the matrix pipe (FEAR_OPT_MATH = 1)
-const Fused16 kFused16H[] = {
-    FUSED16H(64, 192, 64, 5, 1),   FUSED16H(64, 384, 64, 5, 1),  FUSED16H(64, 384, 112, 5, 1),
-    FUSED16H(112, 672, 112, 5, 1), FUSED16H(112, 336, 112, 5, 1),
-    FUSED16H(256, 256, 256, 3, 0), FUSED16H(320, 320, 256, 3, 0),
-    FUSED16H(256, 256, 16, 3, 0),
-    FUSED16H(320, 320, 16, 3, 0),
-};
-static_assert(sizeof(kFused16H) == sizeof(kFused16), "the two tables must list the same shapes in the same order");
-#define FUSED16B(CIN, CEXP, COUT, KS, EXP) \
-    {CIN, CEXP, COUT, KS, EXP, ir16h_fused_kernel<CIN, CEXP, COUT, KS, (EXP) != 0, 2>, IrHGeom<CIN, CEXP, COUT, KS, (EXP) != 0>::LDS_BYTES}
-// bf16 operands (FEAR_OPT_MATH = 2)
-const Fused16 kFused16B[] = {
-    FUSED16B(64, 192, 64, 5, 1),   FUSED16B(64, 384, 64, 5, 1),  FUSED16B(64, 384, 112, 5, 1),
-    FUSED16B(112, 672, 112, 5, 1), FUSED16B(112, 336, 112, 5, 1),
-    FUSED16B(256, 256, 256, 3, 0), FUSED16B(320, 320, 256, 3, 0),
-    FUSED16B(256, 256, 16, 3, 0),
-    FUSED16B(320, 320, 16, 3, 0),
-};
-static_assert(sizeof(kFused16B) == sizeof(kFused16), "same shapes, same order");
-
-// last tower SepConv + the prediction SepConv in one kernel (fp32 mode)
-auto* const kSep16PredKernel = sep16_kernel<256, 256, 3, false, true>;
-constexpr int kSep16PredLds = Sep16Geom<256, 256, 3>::LDS_BYTES;
-
-
-// encode SepConv + pixel-wise correlation in one kernel (fp32 mode)
-constexpr int kCorrC = 256, kCorrTz = 64;
-auto* const kSep16CorrKernel = sep16_kernel<kCorrC, kCorrC, 3, true>;
-constexpr int kSep16CorrLds = Sep16Geom<kCorrC, kCorrC, 3, true>::LDS_BYTES;
-
-int find_fused16(int cin, int cexp, int cout, int ks, int expand) {
-    if (cout <= 4) cout = 16;     // prediction heads run on the one-tile instantiation
-    for (size_t i = 0; i < sizeof(kFused16) / sizeof(kFused16[0]); ++i) {
-        const Fused16& f = kFused16[i];
-        if (f.cin == cin && f.cexp == cexp && f.cout == cout && f.ks == ks && f.expand == expand) return (int)i;
-    }
-    return -1;
-}
-
-
 // Pack the weights of one fused 16x16 block per 16-channel chunk in the order ir16v2_fused_kernel stages them:
 //   [A-part: KG fragments x 256 | be[16]] [BC-part: NTP fragments x 256 | Wd[k*k][16] | bd[16]]
 // (fragment lane l holds W[row0 + (l&15)][col0 + 4*(l>>4) + 0..3]).
@@ -667,12 +448,163 @@ int pack_fused_h(fear_handle* h, int ce, int cd, int cp, float** out, bool bf16 
     return upload(h, buf, out);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Kernel registry.  One row per block shape the fused kernels were instantiated for; one column per variant, each with its own
+// kernel, dynamic LDS bytes and tile.  run_plan sets the LDS limit of every non-null kernel here (set_lds_limits).
+
+// Fused 16x16 block kernels (ir16v2_fused_kernel / sep16_kernel): one row per (CIN, CEXP, COUT, KS, EXPAND).
+struct F16K {
+    void (*kernel)(Ir2Args);
+    int lds_bytes;
+};
+struct Fused16Row {
+    int cin, cexp, cout, ks, expand;
+    F16K fp32;
+    F16K splitk;        // small-batch variant: several workgroups per crop, one chunk range each
+    int splitk_kc;      // chunks per workgroup compiled into that variant (0: run-time, Ir2Args::kc_count)
+    F16K tiny;          // 16-channel output slice of kTinyRows map rows per workgroup (sep16_tiny_kernel), a handful of crops
+    F16K h, b;          // fp16-split (FEAR_OPT_MATH = 1) / bf16 (FEAR_OPT_MATH = 2) operands on the matrix pipe (ir16h_fused_kernel)
+    const F16K& by_math(int math) const { return math == 2 ? b : math ? h : fp32; }
+};
+#define F16HB(CIN, CEXP, COUT, KS, EXP)                                                                                     \
+    {ir16h_fused_kernel<CIN, CEXP, COUT, KS, (EXP) != 0>, IrHGeom<CIN, CEXP, COUT, KS, (EXP) != 0>::LDS_BYTES},               \
+    {ir16h_fused_kernel<CIN, CEXP, COUT, KS, (EXP) != 0, 2>, IrHGeom<CIN, CEXP, COUT, KS, (EXP) != 0>::LDS_BYTES}
+#define FUSED16(CIN, CEXP, COUT, KS, EXP)                                                                                   \
+    {CIN, CEXP, COUT, KS, EXP, {ir16v2_fused_kernel<CIN, CEXP, COUT, KS, (EXP) != 0>, Ir2Geom<CIN, CEXP, COUT, KS, (EXP) != 0>::LDS_BYTES}, \
+     {ir16v2_fused_kernel<CIN, CEXP, COUT, KS, (EXP) != 0, true>, Ir2Geom<CIN, CEXP, COUT, KS, (EXP) != 0>::LDS_BYTES}, 0, {},   \
+     F16HB(CIN, CEXP, COUT, KS, EXP)}
+#define SEP16(CIN, COUT, KS, KC, TINY)                                                                                      \
+    {CIN, CIN, COUT, KS, 0, {sep16_kernel<CIN, COUT, KS>, Sep16Geom<CIN, COUT, KS>::LDS_BYTES},                              \
+     {sep16_kernel<CIN, COUT, KS, false, false, KC>, Sep16Geom<CIN, COUT, KS>::LDS_BYTES}, KC, TINY, F16HB(CIN, CIN, COUT, KS, 0)}
+#ifndef FEAR_TINY_ROWS
+#define FEAR_TINY_ROWS 2
+#endif
+#ifndef FEAR_TINY_KSPLIT
+#define FEAR_TINY_KSPLIT 4
+#endif
+// (batch-1 track call, ms, rows x wave groups: 8x1 0.375 | 4x1 0.357 | 4x2 0.352 | 2x2 0.344 | 2x4 0.342; sep16_kernel<CIN, 16, 3> 0.383)
+constexpr int kTinyRows = FEAR_TINY_ROWS;       // map rows per workgroup of sep16_tiny_kernel (one wave each)
+constexpr int kTinyKSplit = FEAR_TINY_KSPLIT;   // wave groups per workgroup, each over its share of the input chunks
+#define SEP16TINY(CIN, KS) \
+    {sep16_tiny_kernel<CIN, KS, kTinyRows, kTinyKSplit>, Sep16TinyGeom<CIN, KS, kTinyRows, kTinyKSplit>::LDS_BYTES}
+const Fused16Row kFused16[] = {
+    FUSED16(64, 192, 64, 5, 1),   FUSED16(64, 384, 64, 5, 1),  FUSED16(64, 384, 112, 5, 1),
+    FUSED16(112, 672, 112, 5, 1), FUSED16(112, 336, 112, 5, 1),
+    SEP16(256, 256, 3, 4, {}), SEP16(320, 256, 3, 4, {}),
+    SEP16(256, 16, 3, 2, SEP16TINY(256, 3)),   // bbox_pred / cls_pred: 4 / 1 output channels padded to one 16-channel tile
+    SEP16(320, 16, 3, 2, SEP16TINY(320, 3)),   // N-split slices of the 320 -> 256 SepConv (very small batches)
+};
+
+const Fused16Row* find_fused16(int cin, int cexp, int cout, int ks, int expand) {
+    if (cout <= 4) cout = 16;     // prediction heads run on the one-tile instantiation
+    for (const Fused16Row& f : kFused16)
+        if (f.cin == cin && f.cexp == cexp && f.cout == cout && f.ks == ks && f.expand == expand) return &f;
+    return nullptr;
+}
+
+// Spatially tiled fused block kernels (ir_tile_*_kernel) for the high-resolution trunk stages: one row per block shape.
+struct TileK {
+    void (*kernel)(IrT2Args);
+    int lds_bytes;
+    int tw, th;
+    int nw;             // waves per workgroup
+};
+struct TileRow {
+    int cin, cexp, cout, ks, st, expand, hw;   // hw: input map size the tiling was chosen for
+    TileK fp32;         // throughput plan
+    TileK small;        // the small-batch plan: smaller tiles = more workgroups per crop
+    TileK tiny;         // a handful of crops: the smallest tiles the kernel supports, a tile's chunk loop is the latency that counts
+    TileK v4;           // throughput plan, FEAR_OPT_TILE_V4: phase-overlapped kernel (or empty: the block stays on fp32)
+    TileK h, b;         // fp16-split (FEAR_OPT_MATH = 1) / bf16 (FEAR_OPT_MATH = 2) operands on the matrix pipe (ir_tile_h_kernel)
+    TileK ksplit;       // split-K variant of `tiny` (+ a splitk_reduce launch), or empty
+    int ksplit_k;       //   chunks per workgroup
+    // FEAR_OPT_MATH = 2 with FEAR_OPT_BF16_STORE: storage variants of the kernel this block runs at math 2, keyed by the IO bits
+    // (fear_kernels.h: IO_X_BF16 | IO_Y_BF16 | IO_R_BF16) — same tile and LDS footprint as the variant they stand in for
+    struct { int io; TileK k; } bf16_io[2];
+    const TileK* io_variant(int io) const {
+        for (const auto& v : bf16_io)
+            if (v.k.kernel && v.io == io) return &v.k;
+        return nullptr;
+    }
+};
+#define TV2(CIN, CEXPP, COUT, KS, ST, TW, TH, EXP, MINW, ...)                                                              \
+    {ir_tile_v2_kernel<CIN, CEXPP, COUT, KS, ST, TW, TH, EXP, MINW, ##__VA_ARGS__>,                                        \
+     IrT2Geom<CIN, CEXPP, COUT, KS, ST, TW, TH, EXP>::LDS_BYTES, TW, TH, 8}
+#define TV4(CIN, CEXPP, COUT, KS, ST, TW, TH, MINW) \
+    {ir_tile_v4_kernel<CIN, CEXPP, COUT, KS, ST, TW, TH, MINW>, IrT4Geom<CIN, CEXPP, COUT, KS, ST, TW, TH>::LDS_BYTES, TW, TH, 8}
+#define TH_(CIN, CEXPP, COUT, KS, ST, TW, TH, EXP, NW, MINW, MM, ...)                                                      \
+    {ir_tile_h_kernel<CIN, CEXPP, COUT, KS, ST, TW, TH, EXP, NW, MINW, MM, ##__VA_ARGS__>,                                 \
+     IrTHGeom<CIN, CEXPP, COUT, KS, ST, TW, TH, EXP, NW>::LDS_BYTES, TW, TH, NW}
+constexpr int IO_XY = IO_X_BF16 | IO_Y_BF16, IO_XYR = IO_X_BF16 | IO_Y_BF16 | IO_R_BF16;
+// ir_tile_v4 (profiles/r03_tile_v4_kbench.txt, tools/kbench A/B at 256 crops): only the tiles whose E tile leaves room for ONE
+// workgroup per CU gain, where nobody else fills the LDS round trips of the depthwise — stage 6 +5.5 %; stages 7-10 and 2 lose
+// 3-25 % (the overlap costs ~90 more VGPRs: stages 7 / 8 drop from 2-4 workgroups per CU to 1-2, stage 9's 8 rows per wave spill).
+// The fp16-split / bf16 tiles are sized for the 144 B/pixel LDS tile.  Split-K (tiny plan): the blocks whose chunk loop is the
+// longest serial stretch of a one-crop pass get gridDim.y workgroups per tile.
+const TileRow kTiles[] = {
+    {16, 16, 16, 3, 1, 0, 128,       // fbnet_c stage 1  (e1, 128x128)
+     TV2(16, 16, 16, 3, 1, 32, 16, false, 4), TV2(16, 16, 16, 3, 1, 32, 16, false, 4), TV2(16, 16, 16, 3, 1, 32, 16, false, 4), {},
+     TH_(16, 32, 16, 3, 1, 32, 8, false, 8, 2, 1), TH_(16, 32, 16, 3, 1, 32, 8, false, 8, 2, 2), {}, 0,
+     {{IO_XYR, TV2(16, 16, 16, 3, 1, 32, 16, false, 4, false, 0, IO_XYR)},
+      {IO_XY, TV2(16, 16, 16, 3, 1, 32, 16, false, 4, false, 0, IO_XY)}}},
+    {16, 96, 24, 3, 2, 1, 128,       // stage 2  (e6 s2, 128 -> 64)
+     TV2(16, 96, 24, 3, 2, 16, 8, true, 4), TV2(16, 96, 24, 3, 2, 16, 8, true, 4), TV2(16, 96, 24, 3, 2, 16, 8, true, 4), {},
+     TH_(16, 96, 24, 3, 2, 16, 4, true, 4, 2, 1), TH_(16, 96, 24, 3, 2, 16, 4, true, 4, 2, 2), {}, 0,
+     {{IO_XY, TH_(16, 96, 24, 3, 2, 16, 4, true, 4, 2, 2, IO_XY)}}},
+    {24, 24, 24, 3, 1, 0, 64,        // stages 4, 5  (e1, 64x64; 24 channels padded to 32)
+     TV2(24, 32, 24, 3, 1, 16, 16, false, 4), TV2(24, 32, 24, 3, 1, 16, 16, false, 4), TV2(24, 32, 24, 3, 1, 16, 16, false, 4), {},
+     TH_(24, 32, 24, 3, 1, 16, 16, false, 8, 2, 1), TH_(24, 32, 24, 3, 1, 16, 16, false, 8, 2, 2), {}, 0,
+     {{IO_XYR, TV2(24, 32, 24, 3, 1, 16, 16, false, 4, false, 0, IO_XYR)},
+      {IO_XY, TV2(24, 32, 24, 3, 1, 16, 16, false, 4, false, 0, IO_XY)}}},
+    {24, 144, 32, 5, 2, 1, 64,       // stage 6  (e6 s2, 64 -> 32; small / tiny: 8 tiles per crop instead of 4; fp16 / bf16: 144 -> 160 padded channels)
+     TV2(24, 144, 32, 5, 2, 16, 16, true, 2), TV2(24, 144, 32, 5, 2, 16, 8, true, 4), TV2(24, 144, 32, 5, 2, 16, 8, true, 4),
+     TV4(24, 144, 32, 5, 2, 16, 16, 2),
+     TH_(24, 160, 32, 5, 2, 16, 4, true, 4, 2, 1), TH_(24, 160, 32, 5, 2, 16, 4, true, 4, 2, 2),
+     TV2(24, 144, 32, 5, 2, 16, 8, true, 4, false, 3), 3,          // 9 chunks -> 3 workgroups per tile
+     {{IO_X_BF16, TH_(24, 160, 32, 5, 2, 16, 4, true, 4, 2, 2, IO_X_BF16)}}},
+    {32, 96, 32, 5, 1, 1, 32,        // stage 7  (4 corner tiles: 18x18 clipped region; tiny: 8 tiles per crop)
+     TV2(32, 96, 32, 5, 1, 16, 16, true, 2), TV2(32, 96, 32, 5, 1, 16, 16, true, 2), TV2(32, 96, 32, 5, 1, 16, 8, true, 2), {},
+     TH_(32, 96, 32, 5, 1, 16, 16, true, 8, 2, 1), TH_(32, 96, 32, 5, 1, 16, 16, true, 8, 2, 2),
+     TV2(32, 96, 32, 5, 1, 16, 8, true, 2, false, 2), 2},          // 6 chunks -> 3
+    {32, 192, 32, 5, 1, 1, 32,       // stage 8  (two 16x32 tiles per map: 4 rows per wave share the depthwise reads; small: 4, tiny: 8)
+     TV2(32, 192, 32, 5, 1, 16, 32, true, 2), TV2(32, 192, 32, 5, 1, 16, 16, true, 2), TV2(32, 192, 32, 5, 1, 16, 8, true, 2), {},
+     TH_(32, 192, 32, 5, 1, 16, 16, true, 8, 2, 1), TH_(32, 192, 32, 5, 1, 16, 16, true, 8, 2, 2),
+     TV2(32, 192, 32, 5, 1, 16, 8, true, 2, false, 3), 3},         // 12 chunks -> 4
+    {32, 192, 32, 3, 1, 1, 32,       // stage 9  (the whole 32x32 map per workgroup: no halo to re-expand; small: 4, tiny: 8)
+     TV2(32, 192, 32, 3, 1, 32, 32, true, 2), TV2(32, 192, 32, 3, 1, 16, 16, true, 2), TV2(32, 192, 32, 3, 1, 16, 8, true, 2), {},
+     TH_(32, 192, 32, 3, 1, 16, 16, true, 8, 2, 1), TH_(32, 192, 32, 3, 1, 16, 16, true, 8, 2, 2),
+     TV2(32, 192, 32, 3, 1, 16, 8, true, 2, false, 3), 3},         // 12 chunks -> 4
+    {32, 192, 64, 5, 2, 1, 32,       // stage 10  (e6 s2, 32 -> 16: the whole 16x16 output map; small / tiny: 2 tiles)
+     TV2(32, 192, 64, 5, 2, 16, 16, true, 2), TV2(32, 192, 64, 5, 2, 16, 8, true, 2), TV2(32, 192, 64, 5, 2, 16, 8, true, 2), {},
+     TH_(32, 192, 64, 5, 2, 16, 4, true, 4, 2, 1), TH_(32, 192, 64, 5, 2, 16, 4, true, 4, 2, 2),
+     TV2(32, 192, 64, 5, 2, 16, 8, true, 2, false, 2), 2},         // 12 chunks -> 6 (two tiles per crop)
+};
+// stem (3x3 s2, 3 -> 16) fused in front of the first e1 block: one kernel, keyed by the block's shape and map size
+const TileRow kStemTile = {16, 16, 16, 3, 1, 0, 128, TV2(27, 16, 16, 3, 1, 32, 16, true, 4, true), {}, {}, {}, {}, {}, {}, 0,
+                           {{IO_Y_BF16, TV2(27, 16, 16, 3, 1, 32, 16, true, 4, true, 0, IO_Y_BF16)}}};
+
+const TileRow* find_fused_tile(int cin, int cexp, int cout, int ks, int st, int expand, int hw) {
+    for (const TileRow& f : kTiles)
+        if (f.cin == cin && f.cexp == cexp && f.cout == cout && f.ks == ks && f.st == st && f.expand == expand && f.hw == hw)
+            return &f;
+    return nullptr;
+}
+
+// last tower SepConv + the prediction SepConv in one kernel (fp32 mode)
+auto* const kSep16PredKernel = sep16_kernel<256, 256, 3, false, true>;
+constexpr int kSep16PredLds = Sep16Geom<256, 256, 3>::LDS_BYTES;
+
+// encode SepConv + pixel-wise correlation in one kernel (fp32 mode)
+constexpr int kCorrC = 256, kCorrTz = 64;
+auto* const kSep16CorrKernel = sep16_kernel<kCorrC, kCorrC, 3, true>;
+constexpr int kSep16CorrLds = Sep16Geom<kCorrC, kCorrC, 3, true>::LDS_BYTES;
 
 // ---------------------------------------------------------------------------------------------
-// The stride-16 trunk stage of FEAR-XS (fbnet_c stages 11-17 + AdjustLayer) as one register-resident chain kernel.
-struct ChainShape { int cin, cexp, cout, ks, res; };
-const ChainShape kChainXS[7] = {{64, 192, 64, 5, 1},   {64, 384, 64, 5, 1},   {64, 384, 64, 5, 1}, {64, 384, 112, 5, 0},
-                                {112, 672, 112, 5, 1}, {112, 672, 112, 5, 1}, {112, 336, 112, 5, 1}};
+// Chain kernels: whole trunk stages of FEAR-XS as one register-resident kernel each.
+struct ChainShape { int cin, cexp, cout, ks, stride, res; };
+// the stride-16 stage (fbnet_c stages 11-17) + AdjustLayer
+const ChainShape kChainXS[7] = {{64, 192, 64, 5, 1, 1},   {64, 384, 64, 5, 1, 1},   {64, 384, 64, 5, 1, 1}, {64, 384, 112, 5, 1, 0},
+                                {112, 672, 112, 5, 1, 1}, {112, 672, 112, 5, 1, 1}, {112, 336, 112, 5, 1, 1}};
 constexpr int kChainNeckOut = 256;
 auto* const kChainXSKernel =
     chain16_kernel<ChainBlk<64, 192, 64, 5, true>, ChainBlk<64, 384, 64, 5, true>, ChainBlk<64, 384, 64, 5, true>,
@@ -681,10 +613,8 @@ auto* const kChainXSKernel =
 constexpr int kChainXSLds =
     Chain16Lds<5, Ir2Geom<112, 672, 112, 5, true>::AP, Ir2Geom<112, 672, 112, 5, true>::BP>::FLOATS * 4;
 
-// The 32 x 32 trunk stage of FEAR-XS (fbnet_c stage 3 + the stride-2 block that opens stage 4) as one register-resident chain
-// kernel (fear_chain32.h).
-struct Chain32Shape { int cin, cexp, cout, ks, stride, res; };
-const Chain32Shape kChain32XS[4] = {{32, 96, 32, 5, 1, 1}, {32, 192, 32, 5, 1, 1}, {32, 192, 32, 3, 1, 1}, {32, 192, 64, 5, 2, 0}};
+// the 32 x 32 stage (fbnet_c stage 3 + the stride-2 block that opens stage 4; fear_chain32.h)
+const ChainShape kChain32XS[4] = {{32, 96, 32, 5, 1, 1}, {32, 192, 32, 5, 1, 1}, {32, 192, 32, 3, 1, 1}, {32, 192, 64, 5, 2, 0}};
 auto* const kChain32XSKernel = chain32_kernel<C32Blk<32, 96, 32, 5, 1, true>, C32Blk<32, 192, 32, 5, 1, true>,
                                               C32Blk<32, 192, 32, 3, 1, true>, C32Blk<32, 192, 64, 5, 2, false>>;
 auto* const kChain32_16XSKernel =
@@ -700,6 +630,37 @@ using HeadChainG = HeadChainGeom<3>;
 auto* const kHeadChainBKernel = headchain_b_kernel<3>;      // FEAR_OPT_MATH = 2
 using HeadChainBG = HeadChainBGeom<3>;
 
+// the kernels outside the registry tables that need more than the default LDS limit
+struct KernelLds {
+    const void* kernel;
+    int lds_bytes;
+};
+const KernelLds kSingleKernels[] = {
+    {reinterpret_cast<const void*>(kChainXSKernel), kChainXSLds},
+    {reinterpret_cast<const void*>(kChain32XSKernel), C32Geom::LDS_BYTES},
+    {reinterpret_cast<const void*>(kChain32_16XSKernel), kChain32_16Lds},
+    {reinterpret_cast<const void*>(kHeadChainKernel), HeadChainG::LDS_BYTES},
+    {reinterpret_cast<const void*>(kHeadChainBKernel), HeadChainBG::LDS_BYTES},
+    {reinterpret_cast<const void*>(e1pair_kernel), E1PairGeom::LDS_BYTES},
+    {reinterpret_cast<const void*>(kSep16PredKernel), kSep16PredLds},
+    {reinterpret_cast<const void*>(kSep16CorrKernel), kSep16CorrLds},
+};
+
+int set_lds_limits(fear_handle* h) {
+    std::vector<KernelLds> all(std::begin(kSingleKernels), std::end(kSingleKernels));
+    for (const Fused16Row& f : kFused16)
+        for (const F16K* k : {&f.fp32, &f.splitk, &f.tiny, &f.h, &f.b}) all.push_back({reinterpret_cast<const void*>(k->kernel), k->lds_bytes});
+    std::vector<const TileRow*> rows{&kStemTile};
+    for (const TileRow& r : kTiles) rows.push_back(&r);
+    for (const TileRow* r : rows) {
+        for (const TileK* k : {&r->fp32, &r->small, &r->tiny, &r->v4, &r->h, &r->b, &r->ksplit, &r->bf16_io[0].k, &r->bf16_io[1].k})
+            all.push_back({reinterpret_cast<const void*>(k->kernel), k->lds_bytes});
+    }
+    for (const KernelLds& k : all)
+        if (k.kernel) HIP_TRY(h, hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_bytes));
+    return FEAR_OK;
+}
+
 // neck weights as MFMA fragments [nt][kg][lane][4] (lane l: W[nt*16 + (l&15)][kg*16 + 4*(l>>4) + 0..3])
 int pack_neck_frags(fear_handle* h, int conv, float** out) {
     const Conv& c = h->convs[conv];
@@ -710,6 +671,23 @@ int pack_neck_frags(fear_handle* h, int conv, float** out) {
             for (int l = 0; l < 64; ++l)
                 for (int i = 0; i < 4; ++i) buf.push_back(c.w[(size_t)(nt * 16 + (l & 15)) * k + kg * 16 + (l >> 4) * 4 + i]);
     return upload(h, buf, out);
+}
+
+// the n blocks from index bi on are inverted-residual blocks of these shapes (expand + ReLU, depthwise + ReLU, linear projection)
+bool chain_matches(const fear_handle* h, size_t bi, const ChainShape* shapes, int n) {
+    if (bi + n > h->blocks.size()) return false;
+    for (int j = 0; j < n; ++j) {
+        const FearwBlock& bj = h->blocks[bi + j];
+        if (bj.kind != FEARW_IR || bj.conv[0] < 0) return false;
+        const Conv& e = h->convs[bj.conv[0]];
+        const Conv& d = h->convs[bj.conv[1]];
+        const Conv& p = h->convs[bj.conv[2]];
+        const ChainShape& cs = shapes[j];
+        if (!(e.cin_g == cs.cin && d.cout == cs.cexp && p.cout == cs.cout && d.k == cs.ks && d.stride == cs.stride &&
+              (int)bj.residual == cs.res && e.has_bias && p.has_bias && e.relu && d.relu && !p.relu))
+            return false;
+    }
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -739,453 +717,416 @@ struct T {  // tensor view inside the plan
     int buf = -1, ld = 0, off = 0, C = 0, H = 0, W = 0;
 };
 
-void set_name(Op& op, const char* fmt, int a, int b, int c) { snprintf(op.name, sizeof(op.name), fmt, a, b, c); }
+template <class... A>
+void set_name(Op& op, const char* fmt, A... a) { snprintf(op.name, sizeof(op.name), fmt, a...); }
 
-// small = the small-batch plan (few crops per pass): split-K 16x16 kernels, the head's branches on two streams
-int build_plan_uncached(fear_handle* h, int hw, bool with_head, int mode, Plan** out);
-
-// mode: 0 = throughput plan, 1 = small-batch plan, 2 = the small-batch plan with the deepest split (a handful of crops)
-int build_plan(fear_handle* h, int hw, bool with_head, int mode, Plan** out) {
-    auto it = h->plans.find(std::make_pair(hw, (with_head ? 1 : 0) + 2 * mode));
-    if (it != h->plans.end()) { *out = it->second.get(); return FEAR_OK; }
-    h->building_plan = true;          // packed weights uploaded from here on belong to the plan cache
-    const int st = build_plan_uncached(h, hw, with_head, mode, out);
-    h->building_plan = false;
-    return st;
+// Whether the throughput plan of the search branch runs the 32 x 32 chain (PlanBuilder::chain32), from the options and the block
+// table alone: the map size and channel count in front of every trunk block.
+bool plans_chain32(const fear_handle* h, int hw) {
+    if (!h->fuse || !h->chain32 || h->math) return false;
+    int H = hw / 2, C = h->convs[h->blocks[0].conv[0]].cout;
+    for (size_t i = 1; i < h->blocks.size() && h->blocks[i].kind == FEARW_IR; ++i) {
+        if (H == 32 && C == kChain32XS[0].cin && chain_matches(h, i, kChain32XS, 4)) return true;
+        H /= h->convs[h->blocks[i].conv[1]].stride;
+        C = h->convs[h->blocks[i].conv[2]].cout;
+    }
+    return false;
 }
 
-int build_plan_uncached(fear_handle* h, int hw, bool with_head, int mode, Plan** out) {
-    const bool small = mode == 1 || mode == 2;      // (mode 3: the throughput plan of a mid-size pass — no 32 x 32 chain, see plan_mode)
-    // chunks of a 16x16 block are dealt to at most this many workgroups per crop: every workgroup writes a full partial
-    // output map, so a deep split only pays while the crops are few (batch 1: 0.545 -> 0.512 ms per track call)
-    const int splitk_max = mode == 2 ? 24 : 8;
-    auto key = std::make_pair(hw, (with_head ? 1 : 0) + 2 * mode);
-    if (hw < 32 || hw % 32 != 0 || hw > 1024) return FEAR_ERR_SHAPE;
-    if (with_head && !h->has_head) return FEAR_ERR_NOHEAD;
-    std::unique_ptr<Plan> plan(new Plan);
-    plan->hw = hw;
-    plan->with_head = with_head;
-    plan->small = small;
+struct PlanBuilder {
+    fear_handle* const h;
+    const int hw;
+    const bool with_head;
+    const PlanKind kind;
+    const bool small;          // the small-batch plans: split-K 16x16 kernels, the head's branches on two streams
+    Plan& plan;
+    std::vector<Op>& ops;
     Pool pool;
-    size_t max_elems = 0;
-    auto track = [&](const T& t) {
-        size_t e = (size_t)t.H * t.W * t.ld;
-        if (e > max_elems) max_elems = e;
-    };
-    std::vector<Op>& ops = plan->ops;
+    size_t max_elems = 0;      // floats per crop of the largest pool buffer
+    T cur;                     // the tensor the next stage reads
+    size_t bi = 0;             // the next block of h->blocks
 
-    auto add_pw = [&](int conv, const T& in, T& outT, const T* res, int relu, int out_ld, int out_off, int out_buf) {
+    PlanBuilder(fear_handle* h_, int hw_, bool with_head_, PlanKind kind_, Plan& plan_)
+        : h(h_), hw(hw_), with_head(with_head_), kind(kind_), small(kind_ == PlanKind::Small || kind_ == PlanKind::Tiny),
+          plan(plan_), ops(plan_.ops) {}
+
+    bool tiny() const { return kind == PlanKind::Tiny; }
+    // the fp32 throughput plan of the search branch: where the chain, e1-pair and fused-epilogue kernels run
+    bool throughput_fp32() const { return h->fuse && !h->math && !small && with_head; }
+
+    void track(size_t elems) { if (elems > max_elems) max_elems = elems; }
+    static void read(Op& op, const T& in) { op.in_buf = in.buf; op.in_ld = in.ld; op.in_off = in.off; }
+    static void residual(Op& op, const T* res) { if (res) { op.res_buf = res->buf; op.res_ld = res->ld; } }
+    // append op writing a fresh pool buffer of C channels (row stride ld, default C) at H x W; returns that tensor
+    T emit(Op& op, int C, int H, int W, int ld = 0) {
+        T o;
+        o.buf = pool.acquire(); o.ld = ld > 0 ? ld : C; o.C = C; o.H = H; o.W = W;
+        op.out_buf = o.buf; op.out_ld = o.ld;
+        ops.push_back(op);
+        track((size_t)H * W * o.ld);
+        return o;
+    }
+    // a scratch buffer alive only inside the last op (the next acquire may reuse it)
+    void scratch(size_t elems) {
+        Op& op = ops.back();
+        track(elems);
+        op.part_buf = pool.acquire();
+        pool.release(op.part_buf);
+    }
+
+    T add_pw(int conv, const T& in, const T* res, int relu, int out_ld = 0) {
         const Conv& c = h->convs[conv];
         Op op{};
         op.type = OP_PW; op.conv = conv;
-        op.in_buf = in.buf; op.in_ld = in.ld; op.in_off = in.off;
+        read(op, in);
         op.H = in.H; op.W = in.W; op.Ho = in.H; op.Wo = in.W; op.C = c.cin_g; op.N = c.cout;
         op.relu = relu;
-        outT.buf = out_buf >= 0 ? out_buf : pool.acquire();
-        outT.ld = out_ld > 0 ? out_ld : c.cout; outT.off = out_off; outT.C = c.cout; outT.H = in.H; outT.W = in.W;
-        op.out_buf = outT.buf; op.out_ld = outT.ld; op.out_off = outT.off;
-        if (res) { op.res_buf = res->buf; op.res_ld = res->ld; }
+        residual(op, res);
         set_name(op, "pw_%dx%d_hw%d", c.cin_g, c.cout, in.H);
         const double px = (double)in.H * in.W;
         op.flops = 2.0 * px * c.cin_g * c.cout;
         op.bytes = 4.0 * px * (c.cin_g + c.cout + (res ? c.cout : 0));
-        ops.push_back(op);
-        track(outT);
-    };
-    auto add_dw = [&](int conv, const T& in, T& outT, int relu) {
+        return emit(op, c.cout, in.H, in.W, out_ld);
+    }
+    T add_dw(int conv, const T& in, int relu) {
         const Conv& c = h->convs[conv];
         Op op{};
         op.type = OP_DW; op.conv = conv;
-        op.in_buf = in.buf; op.in_ld = in.ld; op.in_off = in.off;
+        read(op, in);
         op.H = in.H; op.W = in.W; op.Ho = in.H / c.stride; op.Wo = in.W / c.stride; op.C = c.cout; op.N = c.cout;
         op.relu = relu;
-        outT.buf = pool.acquire(); outT.ld = c.cout; outT.off = 0; outT.C = c.cout; outT.H = op.Ho; outT.W = op.Wo;
-        op.out_buf = outT.buf; op.out_ld = outT.ld; op.out_off = 0;
         set_name(op, "dw%d_c%d_hw%d", c.k * 10 + c.stride, c.cout, in.H);
         op.flops = 2.0 * op.Ho * op.Wo * c.cout * c.k * c.k;
         op.bytes = 4.0 * c.cout * ((double)in.H * in.W + (double)op.Ho * op.Wo);
-        ops.push_back(op);
-        track(outT);
-    };
+        return emit(op, c.cout, op.Ho, op.Wo);
+    }
+    int pack_block(int ce, int cd, int cp, int math, float** out) {
+        return math ? pack_fused_h(h, ce, cd, cp, out, math == 2) : pack_fused16(h, ce, cd, cp, out);
+    }
 
     // fused 16x16 block (returns false when no instantiation matches -> caller emits the unfused ops)
-    auto add_fused16 = [&](int ce, int cd, int cp, const T& in, T& outT, const T* res, int relu_dw, int relu_out,
-                           int out_ld, const char* tag) -> bool {
+    bool add_fused16(int ce, int cd, int cp, const T& in, T& out, const T* res, int relu_dw, int relu_out, int out_ld, const char* tag) {
         if (!h->fuse || in.H != 16 || in.W != 16) return false;
         const Conv& d = h->convs[cd];
         const Conv& p = h->convs[cp];
         if (d.stride != 1) return false;
         const int cin = ce >= 0 ? h->convs[ce].cin_g : d.cout;
-        const int id = find_fused16(cin, d.cout, p.cout, d.k, ce >= 0 ? 1 : 0);
-        if (id < 0) return false;
-        if (!p.has_bias) return false;
+        const Fused16Row* f = find_fused16(cin, d.cout, p.cout, d.k, ce >= 0 ? 1 : 0);
+        if (!f || !p.has_bias) return false;
         Op op{};
-        op.type = OP_IR16; op.fused_id = id; op.conv_e = ce; op.conv_d = cd; op.conv_p = cp;
+        op.type = OP_IR16; op.f16 = f; op.conv_e = ce; op.conv_d = cd; op.conv_p = cp;
         op.math = h->math;
         // a handful of crops: a SepConv runs as COUT/16 independent 16-channel output slices, one workgroup each, every one
         // with the whole (cheap) depthwise — finished outputs from one launch instead of split-K partials + a reduce launch
-        const int id16 = (mode == 2 && !h->math && ce < 0 && p.cout > 16 && p.cout % 16 == 0 && d.cout % 16 == 0)
-                             ? find_fused16(cin, d.cout, 16, d.k, 0) : -1;
-        if (id16 >= 0) {
+        const Fused16Row* f16 = tiny() && !h->math && ce < 0 && p.cout > 16 && p.cout % 16 == 0 && d.cout % 16 == 0
+                                    ? find_fused16(cin, d.cout, 16, d.k, 0) : nullptr;
+        if (f16) {
             op.nsplit = p.cout / 16;
-            op.fused_id = id16;
-            op.tiny = h->tiny_sep && kFused16[id16].kernel_tiny ? 1 : 0;
+            op.f16 = f16;
+            op.tiny = h->tiny_sep && f16->tiny.kernel ? 1 : 0;
             if (pack_sep16_nsplit(h, cd, cp, &op.d_packed) != FEAR_OK) return false;
-        } else if ((h->math ? pack_fused_h(h, ce, cd, cp, &op.d_packed, h->math == 2) : pack_fused16(h, ce, cd, cp, &op.d_packed)) != FEAR_OK)
+        } else if (pack_block(ce, cd, cp, h->math, &op.d_packed) != FEAR_OK) {
             return false;
-        op.in_buf = in.buf; op.in_ld = in.ld; op.in_off = in.off;
+        }
+        read(op, in);
         op.H = 16; op.W = 16; op.Ho = 16; op.Wo = 16; op.C = cin; op.N = p.cout;
         op.relu_dw = relu_dw; op.relu = relu_out;
-        outT.buf = pool.acquire(); outT.ld = out_ld > 0 ? out_ld : p.cout; outT.off = 0; outT.C = p.cout; outT.H = 16; outT.W = 16;
-        op.out_buf = outT.buf; op.out_ld = outT.ld;
-        if (res) { op.res_buf = res->buf; op.res_ld = res->ld; }
+        residual(op, res);
         // small passes: one workgroup per crop leaves the GPU idle — split the expansion chunks of a crop over several
-        // workgroups (each projects its own chunks), then add the partial projections up
-        if (!h->math && small && !op.nsplit && kFused16[id].kernel_splitk) {
-            const int nchunk = d.cout / 16;
-            int w = 0;
-            if (kFused16[id].splitk_kc > 0) {
-                w = nchunk / kFused16[id].splitk_kc;              // the variant's chunk count per workgroup is compiled in
+        // workgroups (each projects its own chunks), then add the partial projections up.  Chunks are dealt to at most
+        // splitk_max workgroups per crop: every workgroup writes a full partial output map, so a deep split only pays while the
+        // crops are few (batch 1: 0.545 -> 0.512 ms per track call)
+        if (!h->math && small && !op.nsplit && f->splitk.kernel) {
+            const int nchunk = d.cout / 16, splitk_max = tiny() ? 24 : 8;
+            if (f->splitk_kc > 0) {
+                op.splitk = nchunk / f->splitk_kc;              // the variant's chunk count per workgroup is compiled in
             } else {
-                for (int cand = splitk_max; cand >= 2 && !w; --cand)
-                    if (nchunk % cand == 0 && nchunk / cand >= (mode == 2 ? 1 : 2)) w = cand;
-            }
-            if (w) {
-                op.splitk = w;
-                if ((size_t)w * 256 * p.cout > max_elems) max_elems = (size_t)w * 256 * p.cout;
-                op.part_buf = pool.acquire();
-                pool.release(op.part_buf);          // only alive inside this op (the next acquire may reuse it)
+                for (int cand = splitk_max; cand >= 2 && !op.splitk; --cand)
+                    if (nchunk % cand == 0 && nchunk / cand >= (tiny() ? 1 : 2)) op.splitk = cand;
             }
         }
-        snprintf(op.name, sizeof(op.name), op.splitk ? "%s_splitk_%dx%dx%d_k%d" : op.nsplit ? "%s_nsplit_%dx%dx%d_k%d" : "%s_%dx%dx%d_k%d", tag, cin,
-                 d.cout, p.cout, d.k);
+        set_name(op, op.splitk ? "%s_splitk_%dx%dx%d_k%d" : op.nsplit ? "%s_nsplit_%dx%dx%d_k%d" : "%s_%dx%dx%d_k%d", tag, cin, d.cout,
+                 p.cout, d.k);
         op.flops = 2.0 * 256 * ((ce >= 0 ? (double)cin * d.cout : 0.0) + (double)d.cout * d.k * d.k + (double)d.cout * p.cout);
         op.bytes = 4.0 * 256 * (cin + p.cout + (res ? p.cout : 0));
-        ops.push_back(op);
-        track(outT);
+        out = emit(op, p.cout, 16, 16, out_ld);
+        if (op.splitk) scratch((size_t)op.splitk * 256 * p.cout);
         return true;
-    };
+    }
 
     // prediction head (dw3x3 + 1x1 to 4 / 1 channels [+ exp]) as a fused 16x16 block writing the caller's NCHW map
-    auto add_fused_pred = [&](int cd, int cp, const T& in, int act, int ext) -> bool {
+    bool add_fused_pred(int cd, int cp, const T& in, int act, int ext) {
         if (!h->fuse || in.H != 16 || in.W != 16) return false;
         const Conv& d = h->convs[cd];
         const Conv& p = h->convs[cp];
         if (d.stride != 1 || p.cout > 4 || !p.has_bias) return false;
-        const int id = find_fused16(d.cout, d.cout, p.cout, d.k, 0);
-        if (id < 0) return false;
+        const Fused16Row* f = find_fused16(d.cout, d.cout, p.cout, d.k, 0);
+        if (!f) return false;
         Op op{};
-        op.type = OP_IR16; op.fused_id = id; op.conv_e = -1; op.conv_d = cd; op.conv_p = cp;
+        op.type = OP_IR16; op.f16 = f; op.conv_e = -1; op.conv_d = cd; op.conv_p = cp;
         op.math = h->math;
-        if ((h->math ? pack_fused_h(h, -1, cd, cp, &op.d_packed, h->math == 2) : pack_fused16(h, -1, cd, cp, &op.d_packed)) != FEAR_OK)
-            return false;
-        op.in_buf = in.buf; op.in_ld = in.ld; op.in_off = in.off;
+        if (pack_block(-1, cd, cp, h->math, &op.d_packed) != FEAR_OK) return false;
+        read(op, in);
         op.H = 16; op.W = 16; op.Ho = 16; op.Wo = 16; op.C = d.cout; op.N = p.cout;
         op.pred_cout = p.cout; op.act = act; op.out_external = ext;
-        op.tiny = mode == 2 && !h->math && h->tiny_sep && kFused16[id].kernel_tiny ? 1 : 0;
-        snprintf(op.name, sizeof(op.name), "%s_%dx%d_k%d", ext == 3 ? "cls_pred16" : "bbox_pred16", d.cout, p.cout, d.k);
+        op.tiny = tiny() && !h->math && h->tiny_sep && f->tiny.kernel ? 1 : 0;
+        set_name(op, "%s_%dx%d_k%d", ext == 3 ? "cls_pred16" : "bbox_pred16", d.cout, p.cout, d.k);
         op.flops = 2.0 * 256 * ((double)d.cout * d.k * d.k + (double)d.cout * p.cout);
         op.bytes = 4.0 * 256 * (d.cout + p.cout);
         ops.push_back(op);
         return true;
-    };
+    }
 
-    auto add_fused_tile = [&](int ce, int cd, int cp, const T& in, T& outT, const T* res) -> bool {
+    bool add_fused_tile(int ce, int cd, int cp, const T& in, T& out, const T* res) {
         if (!h->fuse || in.H != in.W) return false;
         const Conv& d = h->convs[cd];
         const Conv& p = h->convs[cp];
         const int cin = ce >= 0 ? h->convs[ce].cin_g : d.cout;
-        const int id = find_fused_tile(cin, d.cout, p.cout, d.k, d.stride, ce >= 0 ? 1 : 0, in.H);
-        if (id < 0) return false;
-        const int use_h = ce >= 0 ? h->math : 0;   // e1 blocks (no expand GEMM) stay on the fp32 kernel
-        // 1 / 2: the small-batch / tiny plans' tiles; 3: the throughput plan's phase-overlapped kernel where the table has one
-        const int small_tiles = small && !use_h ? (mode == 2 ? 2 : 1) : (!small && !use_h && h->tile_v4 && kFusedTileV4[id].kernel ? 3 : 0);
-        const FusedTile& f = use_h == 2 ? kFusedTileB[id] : use_h ? kFusedTileH[id] : fp32_tile(small_tiles, id);
+        const TileRow* r = find_fused_tile(cin, d.cout, p.cout, d.k, d.stride, ce >= 0 ? 1 : 0, in.H);
+        if (!r) return false;
+        const int math = ce >= 0 ? h->math : 0;   // e1 blocks (no expand GEMM) stay on the fp32 kernel
+        const TileK& f = math == 2 ? r->b : math ? r->h : tiny() ? r->tiny : small ? r->small : h->tile_v4 && r->v4.kernel ? r->v4 : r->fp32;
         const int ho = in.H / d.stride;
         if (ho % f.th != 0 || ho % f.tw != 0) return false;
         if (!p.has_bias) return false;
         Op op{};
-        op.type = OP_IRTILE; op.fused_id = id; op.conv_e = ce; op.conv_d = cd; op.conv_p = cp;
-        op.math = use_h;
-        op.small_tiles = small_tiles;
-        if ((use_h ? pack_fused_h(h, ce, cd, cp, &op.d_packed, use_h == 2) : pack_fused16(h, ce, cd, cp, &op.d_packed)) != FEAR_OK)
-            return false;
-        op.in_buf = in.buf; op.in_ld = in.ld; op.in_off = in.off;
+        op.type = OP_IRTILE; op.tile = r; op.tk = &f; op.conv_e = ce; op.conv_d = cd; op.conv_p = cp;
+        if (pack_block(ce, cd, cp, math, &op.d_packed) != FEAR_OK) return false;
+        read(op, in);
         op.H = in.H; op.W = in.W; op.Ho = ho; op.Wo = ho; op.C = cin; op.N = p.cout;
         op.relu_dw = 1; op.relu = 0;
-        outT.buf = pool.acquire(); outT.ld = p.cout; outT.off = 0; outT.C = p.cout; outT.H = ho; outT.W = ho;
-        op.out_buf = outT.buf; op.out_ld = outT.ld;
-        if (res) { op.res_buf = res->buf; op.res_ld = res->ld; }
-        if (small_tiles == 2 && ce >= 0) {
-            if (const TileKSplit* ks = find_tile_ksplit(id)) {
-                op.splitk = d.cout / 16 / ks->k;
-                const size_t pe = (size_t)op.splitk * ho * ho * p.cout;
-                if (pe > max_elems) max_elems = pe;
-                op.part_buf = pool.acquire();
-                pool.release(op.part_buf);          // only alive inside this op
-            }
-        }
-        snprintf(op.name, sizeof(op.name), op.splitk ? "irt_splitk_%dx%dx%d_k%ds%d_hw%d" : "irt_%dx%dx%d_k%ds%d_hw%d", cin, d.cout, p.cout, d.k,
-                 d.stride, in.H);
+        residual(op, res);
+        if (&f == &r->tiny && ce >= 0 && r->ksplit.kernel) op.splitk = d.cout / 16 / r->ksplit_k;
+        set_name(op, op.splitk ? "irt_splitk_%dx%dx%d_k%ds%d_hw%d" : "irt_%dx%dx%d_k%ds%d_hw%d", cin, d.cout, p.cout, d.k, d.stride, in.H);
         op.flops = 2.0 * ((ce >= 0 ? (double)in.H * in.W * cin * d.cout : 0.0) +
                           (double)ho * ho * d.cout * d.k * d.k + (double)ho * ho * d.cout * p.cout);
         op.bytes = 4.0 * ((double)in.H * in.W * cin + (double)ho * ho * p.cout * (res ? 2 : 1));
-        ops.push_back(op);
-        track(outT);
+        out = emit(op, p.cout, ho, ho);
+        if (op.splitk) scratch((size_t)op.splitk * ho * ho * p.cout);
         return true;
-    };
+    }
 
-    T cur;
-    size_t bi = 0;
-    // ---- stem fused with the first inverted-residual block (e1, residual) when the shapes match the instantiation
-    bool stem_fused = false;
-    if (h->fuse && h->blocks.size() > 1 && h->blocks[1].kind == FEARW_IR && h->blocks[1].conv[0] < 0 && h->blocks[1].residual) {
-        const Conv& cs = h->convs[h->blocks[0].conv[0]];
-        const Conv& d = h->convs[h->blocks[1].conv[1]];
-        const Conv& p = h->convs[h->blocks[1].conv[2]];
-        const FusedTile& f = kStemTile;
-        const int ho = hw / 2;
-        if (cs.cout == 16 && d.cout == f.cexp && p.cout == f.cout && d.k == f.ks && d.stride == 1 && ho == f.hw &&
-            p.has_bias && d.relu && !p.relu) {
+    // ---- stem, fused with the first inverted-residual block (e1, residual) when the shapes match kStemTile
+    void stem() {
+        const FearwBlock& b0 = h->blocks[0];
+        if (h->fuse && h->blocks.size() > 1 && h->blocks[1].kind == FEARW_IR && h->blocks[1].conv[0] < 0 && h->blocks[1].residual) {
+            const FearwBlock& b1 = h->blocks[1];
+            const Conv& cs = h->convs[b0.conv[0]];
+            const Conv& d = h->convs[b1.conv[1]];
+            const Conv& p = h->convs[b1.conv[2]];
+            const TileRow& f = kStemTile;
+            const int ho = hw / 2;
             Op op{};
-            op.type = OP_IRTILE; op.fused_id = -1; op.stem = 1;
-            op.conv_e = h->blocks[0].conv[0]; op.conv_d = h->blocks[1].conv[1]; op.conv_p = h->blocks[1].conv[2];
-            if (pack_fused16(h, op.conv_e, op.conv_d, op.conv_p, &op.d_packed) == FEAR_OK) {
+            op.type = OP_IRTILE; op.tile = &f; op.tk = &f.fp32; op.stem = 1;
+            op.conv_e = b0.conv[0]; op.conv_d = b1.conv[1]; op.conv_p = b1.conv[2];
+            if (cs.cout == 16 && d.cout == f.cexp && p.cout == f.cout && d.k == f.ks && d.stride == 1 && ho == f.hw && p.has_bias &&
+                d.relu && !p.relu && pack_fused16(h, op.conv_e, op.conv_d, op.conv_p, &op.d_packed) == FEAR_OK) {
                 op.H = ho; op.W = ho; op.Ho = ho; op.Wo = ho; op.C = 3; op.N = p.cout;
                 op.relu_dw = 1; op.relu = 0;
-                cur.buf = pool.acquire(); cur.ld = p.cout; cur.off = 0; cur.C = p.cout; cur.H = ho; cur.W = ho;
-                op.out_buf = cur.buf; op.out_ld = cur.ld;
-                snprintf(op.name, sizeof(op.name), "stem_irt_3x16x16_k3_hw%d", hw);
+                set_name(op, "stem_irt_3x16x16_k3_hw%d", hw);
                 op.flops = 2.0 * ho * ho * (27.0 * 16 + 16.0 * 9 + 16.0 * 16);
                 op.bytes = 4.0 * (3.0 * hw * hw + (double)ho * ho * 16);
-                ops.push_back(op);
-                track(cur);
-                stem_fused = true;
+                cur = emit(op, p.cout, ho, ho);
                 bi = 2;
+                return;
             }
         }
-    }
-    // ---- stem
-    if (!stem_fused) {
-        const FearwBlock& b = h->blocks[0];
-        const Conv& c = h->convs[b.conv[0]];
+        const Conv& c = h->convs[b0.conv[0]];
         Op op{};
-        op.type = OP_STEM; op.conv = b.conv[0];
+        op.type = OP_STEM; op.conv = b0.conv[0];
         op.H = hw; op.W = hw; op.Ho = hw / 2; op.Wo = hw / 2; op.C = 3; op.N = c.cout; op.relu = 1;
-        cur.buf = pool.acquire(); cur.ld = c.cout; cur.off = 0; cur.C = c.cout; cur.H = hw / 2; cur.W = hw / 2;
-        op.out_buf = cur.buf; op.out_ld = cur.ld;
-        set_name(op, "stem_3x%d_hw%d%.0d", c.cout, hw, 0);
+        set_name(op, "stem_3x%d_hw%d", c.cout, hw);
         op.flops = 2.0 * op.Ho * op.Wo * 27 * c.cout;
         op.bytes = 4.0 * (3.0 * hw * hw + (double)op.Ho * op.Wo * c.cout);
-        ops.push_back(op);
-        track(cur);
+        cur = emit(op, c.cout, hw / 2, hw / 2);
         bi = 1;
     }
-    // ---- trunk + neck
-    for (; bi < h->blocks.size(); ++bi) {
-        const FearwBlock& b = h->blocks[bi];
-        // ---- the whole stride-16 stage + neck as one chain kernel (fp32 arithmetic, search branch)
-        if (h->fuse && h->chain && !h->math && !small && with_head && b.kind == FEARW_IR && cur.H == 16 && cur.W == 16 &&
-            bi + 7 < h->blocks.size() && h->blocks[bi + 7].kind == FEARW_NECK) {
-            bool match = true;
-            for (int j = 0; j < 7 && match; ++j) {
-                const FearwBlock& bj = h->blocks[bi + j];
-                if (bj.kind != FEARW_IR || bj.conv[0] < 0) { match = false; break; }
-                const Conv& e = h->convs[bj.conv[0]];
-                const Conv& d = h->convs[bj.conv[1]];
-                const Conv& p = h->convs[bj.conv[2]];
-                const ChainShape& cs = kChainXS[j];
-                match = e.cin_g == cs.cin && d.cout == cs.cexp && p.cout == cs.cout && d.k == cs.ks && d.stride == 1 &&
-                        (int)bj.residual == cs.res && e.has_bias && p.has_bias && e.relu && d.relu && !p.relu;
-            }
-            const Conv& nk = h->convs[h->blocks[bi + 7].conv[0]];
-            match = match && nk.cin_g == kChainXS[6].cout && nk.cout == kChainNeckOut && nk.has_bias && !nk.relu;
-            if (match) {
-                Op op{};
-                op.type = OP_CHAIN16;
-                bool ok = true;
-                double fl = 0;
-                for (int j = 0; j < 7 && ok; ++j) {
-                    const FearwBlock& bj = h->blocks[bi + j];
-                    ok = pack_fused16(h, bj.conv[0], bj.conv[1], bj.conv[2], &op.chain_pk[j]) == FEAR_OK;
-                    op.chain_cp[j] = bj.conv[2];
-                    const ChainShape& cs = kChainXS[j];
-                    fl += 2.0 * 256 * ((double)cs.cin * cs.cexp + 25.0 * cs.cexp + (double)cs.cexp * cs.cout);
-                }
-                op.neck_conv = h->blocks[bi + 7].conv[0];
-                ok = ok && pack_neck_frags(h, op.neck_conv, &op.neck_pk) == FEAR_OK;
-                if (ok) {
-                    op.in_buf = cur.buf; op.in_ld = cur.ld; op.in_off = cur.off;
-                    op.H = 16; op.W = 16; op.Ho = 16; op.Wo = 16; op.C = kChainXS[0].cin; op.N = kChainNeckOut;
-                    T o;
-                    o.buf = pool.acquire(); o.ld = kChainNeckOut; o.off = 0; o.C = kChainNeckOut; o.H = 16; o.W = 16;
-                    op.out_buf = o.buf; op.out_ld = o.ld;
-                    snprintf(op.name, sizeof(op.name), "chain16_7blocks_neck_%dx%d", op.C, op.N);
-                    op.flops = fl + 2.0 * 256 * kChainXS[6].cout * kChainNeckOut;
-                    op.bytes = 4.0 * 256 * (op.C + op.N);
-                    if (h->chain32 == 2 && !ops.empty() && ops.back().type == OP_CHAIN32 && ops.back().out_buf == op.in_buf && op.in_off == 0) {
-                        // the 32 x 32 stage in front of it is a chain kernel too: one launch for both (chain32_16_kernel), the
-                        // 16 x 16 x 64 map between them stays in registers
-                        Op& f = ops.back();
-                        f.type = OP_CHAIN32_16;
-                        for (int j = 0; j < 7; ++j) { f.chain16_pk[j] = op.chain_pk[j]; f.chain16_cp[j] = op.chain_cp[j]; }
-                        f.neck_conv = op.neck_conv; f.neck_pk = op.neck_pk;
-                        f.out_buf = op.out_buf; f.out_ld = op.out_ld;
-                        f.N = op.N;
-                        snprintf(f.name, sizeof(f.name), "chain32_16_11blocks_neck_%dx%d", f.C, f.N);
-                        f.flops += op.flops;
-                        f.bytes = 4.0 * (1024.0 * f.C + 256.0 * f.N);
-                    } else {
-                        ops.push_back(op);
-                    }
-                    track(o);
-                    pool.release(cur.buf);
-                    cur = o;
-                    bi += 8;
-                    break;      // the neck is consumed: continue with the head
-                }
-            }
+
+    // packs the weights of a matched chain (chain_matches) into pk / cp; returns its FLOPs per crop, or -1
+    double pack_chain(const ChainShape* shapes, int n, double in_px, float** pk, int* cp) {
+        double fl = 0;
+        for (int j = 0; j < n; ++j) {
+            const FearwBlock& bj = h->blocks[bi + j];
+            if (pack_fused16(h, bj.conv[0], bj.conv[1], bj.conv[2], &pk[j]) != FEAR_OK) return -1;
+            cp[j] = bj.conv[2];
+            const ChainShape& cs = shapes[j];
+            const double po = in_px / (cs.stride * cs.stride);
+            fl += 2.0 * (in_px * cs.cin * cs.cexp + po * cs.ks * cs.ks * cs.cexp + po * cs.cexp * cs.cout);
         }
-        // ---- the whole 32 x 32 stage (three blocks + the stride-2 block down to 16 x 16) as one chain kernel (fp32, search branch)
-        if (h->fuse && h->chain32 && mode != 3 && !h->math && !small && with_head && b.kind == FEARW_IR && cur.H == 32 && cur.W == 32 && cur.off == 0 &&
-            bi + 3 < h->blocks.size()) {
-            bool match = cur.C == kChain32XS[0].cin;
-            for (int j = 0; j < 4 && match; ++j) {
-                const FearwBlock& bj = h->blocks[bi + j];
-                if (bj.kind != FEARW_IR || bj.conv[0] < 0) { match = false; break; }
-                const Conv& e = h->convs[bj.conv[0]];
-                const Conv& d = h->convs[bj.conv[1]];
-                const Conv& p = h->convs[bj.conv[2]];
-                const Chain32Shape& cs = kChain32XS[j];
-                match = e.cin_g == cs.cin && d.cout == cs.cexp && p.cout == cs.cout && d.k == cs.ks && d.stride == cs.stride &&
-                        (int)bj.residual == cs.res && e.has_bias && p.has_bias && e.relu && d.relu && !p.relu;
-            }
-            if (match) {
-                Op op{};
-                op.type = OP_CHAIN32;
-                bool ok = true;
-                double fl = 0;
-                for (int j = 0; j < 4 && ok; ++j) {
-                    const FearwBlock& bj = h->blocks[bi + j];
-                    ok = pack_fused16(h, bj.conv[0], bj.conv[1], bj.conv[2], &op.chain_pk[j]) == FEAR_OK;
-                    op.chain_cp[j] = bj.conv[2];
-                    const Chain32Shape& cs = kChain32XS[j];
-                    const double po = 1024.0 / (cs.stride * cs.stride);
-                    fl += 2.0 * (1024.0 * cs.cin * cs.cexp + po * cs.ks * cs.ks * cs.cexp + po * cs.cexp * cs.cout);
-                }
-                if (ok) {
-                    op.in_buf = cur.buf; op.in_ld = cur.ld; op.in_off = 0;
-                    op.H = 32; op.W = 32; op.Ho = 16; op.Wo = 16; op.C = kChain32XS[0].cin; op.N = kChain32XS[3].cout;
-                    T o;
-                    o.buf = pool.acquire(); o.ld = op.N; o.off = 0; o.C = op.N; o.H = 16; o.W = 16;
-                    op.out_buf = o.buf; op.out_ld = o.ld;
-                    snprintf(op.name, sizeof(op.name), "chain32_4blocks_%dx%d_hw32", op.C, op.N);
-                    op.flops = fl;
-                    op.bytes = 4.0 * (1024.0 * op.C + 256.0 * op.N);
-                    ops.push_back(op);
-                    track(o);
-                    pool.release(cur.buf);
-                    cur = o;
-                    bi += 3;        // four blocks consumed (the loop adds the fourth)
-                    continue;
-                }
-            }
+        return fl;
+    }
+
+    // ---- the whole 32 x 32 stage (three blocks + the stride-2 block down to 16 x 16) as one chain kernel (fp32, search branch;
+    //      not in the mid-size plan: plan_kind)
+    bool chain32() {
+        if (!throughput_fp32() || !h->chain32 || kind == PlanKind::MidSize || cur.H != 32 || cur.W != 32 || cur.off != 0 ||
+            cur.C != kChain32XS[0].cin || !chain_matches(h, bi, kChain32XS, 4))
+            return false;
+        Op op{};
+        op.type = OP_CHAIN32;
+        const double fl = pack_chain(kChain32XS, 4, 1024.0, op.chain_pk, op.chain_cp);
+        if (fl < 0) return false;
+        read(op, cur);
+        op.H = 32; op.W = 32; op.Ho = 16; op.Wo = 16; op.C = kChain32XS[0].cin; op.N = kChain32XS[3].cout;
+        set_name(op, "chain32_4blocks_%dx%d_hw32", op.C, op.N);
+        op.flops = fl;
+        op.bytes = 4.0 * (1024.0 * op.C + 256.0 * op.N);
+        const T o = emit(op, op.N, 16, 16);
+        pool.release(cur.buf);
+        cur = o;
+        bi += 4;
+        return true;
+    }
+
+    // ---- the whole stride-16 stage + neck as one chain kernel (fp32 arithmetic, search branch), merged into the 32 x 32 chain in
+    //      front of it when there is one (FEAR_OPT_CHAIN32 = 2)
+    bool chain16_neck() {
+        if (!throughput_fp32() || !h->chain || cur.H != 16 || cur.W != 16 || bi + 7 >= h->blocks.size() ||
+            h->blocks[bi + 7].kind != FEARW_NECK || !chain_matches(h, bi, kChainXS, 7))
+            return false;
+        const int neck = h->blocks[bi + 7].conv[0];
+        const Conv& nk = h->convs[neck];
+        if (nk.cin_g != kChainXS[6].cout || nk.cout != kChainNeckOut || !nk.has_bias || nk.relu) return false;
+        Op op{};
+        op.type = OP_CHAIN16;
+        const double fl = pack_chain(kChainXS, 7, 256.0, op.chain_pk, op.chain_cp);
+        op.neck_conv = neck;
+        if (fl < 0 || pack_neck_frags(h, neck, &op.neck_pk) != FEAR_OK) return false;
+        read(op, cur);
+        op.H = 16; op.W = 16; op.Ho = 16; op.Wo = 16; op.C = kChainXS[0].cin; op.N = kChainNeckOut;
+        set_name(op, "chain16_7blocks_neck_%dx%d", op.C, op.N);
+        op.flops = fl + 2.0 * 256 * kChainXS[6].cout * kChainNeckOut;
+        op.bytes = 4.0 * 256 * (op.C + op.N);
+        const T o = emit(op, kChainNeckOut, 16, 16);
+        Op* f = ops.size() > 1 ? &ops[ops.size() - 2] : nullptr;
+        if (h->chain32 == 2 && f && f->type == OP_CHAIN32 && f->out_buf == op.in_buf && op.in_off == 0) {
+            // the 32 x 32 stage in front of it is a chain kernel too: one launch for both (chain32_16_kernel), the
+            // 16 x 16 x 64 map between them stays in registers
+            f->type = OP_CHAIN32_16;
+            for (int j = 0; j < 7; ++j) { f->chain16_pk[j] = op.chain_pk[j]; f->chain16_cp[j] = op.chain_cp[j]; }
+            f->neck_conv = op.neck_conv; f->neck_pk = op.neck_pk;
+            f->out_buf = op.out_buf; f->out_ld = op.out_ld;
+            f->N = op.N;
+            set_name(*f, "chain32_16_11blocks_neck_%dx%d", f->C, f->N);
+            f->flops += op.flops;
+            f->bytes = 4.0 * (1024.0 * f->C + 256.0 * f->N);
+            ops.pop_back();
         }
-        // ---- two consecutive e1 blocks (no expansion, 24 channels, residual) as one launch: the map between them stays in LDS
-        //      (search branch only: `get_features` keeps one set of kernels for every batch size — its maps are bit-identical
-        //      whatever the batching, tests/test_gpu_parity.py::test_empty_ragged_and_chunked_batches)
-        if (h->fuse && h->e1_pair && !h->math && !small && with_head && b.kind == FEARW_IR && bi + 1 < h->blocks.size() && cur.C == E1PairGeom::C &&
-            cur.ld == E1PairGeom::C && cur.off == 0 && cur.H == cur.W && cur.H % E1PairGeom::T == 0) {
-            auto is_e1 = [&](const FearwBlock& q) {
-                if (q.kind != FEARW_IR || q.conv[0] >= 0 || !q.residual) return false;
-                const Conv& d = h->convs[q.conv[1]];
-                const Conv& p = h->convs[q.conv[2]];
-                return d.k == 3 && d.stride == 1 && d.cout == E1PairGeom::C && p.cin_g == E1PairGeom::C && p.cout == E1PairGeom::C &&
-                       d.relu && !p.relu && p.has_bias;
-            };
-            if (is_e1(b) && is_e1(h->blocks[bi + 1])) {
-                std::vector<float> pk;
-                for (int j = 0; j < 2; ++j) {
-                    const Conv& d = h->convs[h->blocks[bi + j].conv[1]];
-                    const Conv& p = h->convs[h->blocks[bi + j].conv[2]];
-                    e1pair_pack_block(pk, d.w.data(), d.has_bias ? d.b.data() : nullptr, p.w.data(), p.b.data());
-                }
-                Op op{};
-                op.type = OP_E1PAIR;
-                if (upload(h, pk, &op.d_packed) == FEAR_OK) {
-                    op.in_buf = cur.buf; op.in_ld = cur.ld; op.in_off = 0;
-                    op.H = cur.H; op.W = cur.W; op.Ho = cur.H; op.Wo = cur.W; op.C = cur.C; op.N = cur.C;
-                    T o;
-                    o.buf = pool.acquire(); o.ld = cur.C; o.off = 0; o.C = cur.C; o.H = cur.H; o.W = cur.W;
-                    op.out_buf = o.buf; op.out_ld = o.ld;
-                    snprintf(op.name, sizeof(op.name), "e1pair_%dx%d_k3_hw%d", cur.C, cur.C, cur.H);
-                    op.flops = 2.0 * 2.0 * cur.H * cur.W * (9.0 * cur.C + (double)cur.C * cur.C);
-                    op.bytes = 4.0 * 2.0 * cur.H * cur.W * cur.C;
-                    ops.push_back(op);
-                    track(o);
-                    pool.release(cur.buf);
-                    cur = o;
-                    ++bi;           // two blocks consumed (the loop adds the other one)
-                    continue;
-                }
-            }
+        pool.release(cur.buf);
+        cur = o;
+        bi += 8;
+        return true;
+    }
+
+    // ---- two consecutive e1 blocks (no expansion, 24 channels, residual) as one launch: the map between them stays in LDS
+    //      (search branch only: `get_features` keeps one set of kernels for every batch size — its maps are bit-identical
+    //      whatever the batching, tests/test_gpu_parity.py::test_empty_ragged_and_chunked_batches)
+    bool e1_pair() {
+        if (!throughput_fp32() || !h->e1_pair || bi + 1 >= h->blocks.size() || cur.C != E1PairGeom::C || cur.ld != E1PairGeom::C ||
+            cur.off != 0 || cur.H != cur.W || cur.H % E1PairGeom::T != 0)
+            return false;
+        auto is_e1 = [&](const FearwBlock& q) {
+            if (q.kind != FEARW_IR || q.conv[0] >= 0 || !q.residual) return false;
+            const Conv& d = h->convs[q.conv[1]];
+            const Conv& p = h->convs[q.conv[2]];
+            return d.k == 3 && d.stride == 1 && d.cout == E1PairGeom::C && p.cin_g == E1PairGeom::C && p.cout == E1PairGeom::C &&
+                   d.relu && !p.relu && p.has_bias;
+        };
+        if (!is_e1(h->blocks[bi]) || !is_e1(h->blocks[bi + 1])) return false;
+        std::vector<float> pk;
+        for (int j = 0; j < 2; ++j) {
+            const Conv& d = h->convs[h->blocks[bi + j].conv[1]];
+            const Conv& p = h->convs[h->blocks[bi + j].conv[2]];
+            e1pair_pack_block(pk, d.w.data(), d.has_bias ? d.b.data() : nullptr, p.w.data(), p.b.data());
         }
-        if (b.kind == FEARW_IR) {
-            T x = cur, e = cur, d, o;
-            if (add_fused16(b.conv[0], b.conv[1], b.conv[2], x, o, b.residual ? &x : nullptr, 1, 0, 0, "ir16") ||
-                add_fused_tile(b.conv[0], b.conv[1], b.conv[2], x, o, b.residual ? &x : nullptr)) {
-                pool.release(x.buf);
-                cur = o;
-                continue;
-            }
-            if (b.conv[0] >= 0) {
-                add_pw(b.conv[0], x, e, nullptr, 1, 0, 0, -1);
-            }
-            add_dw(b.conv[1], e, d, 1);
-            if (b.conv[0] >= 0) pool.release(e.buf);
-            add_pw(b.conv[2], d, o, b.residual ? &x : nullptr, 0, 0, 0, -1);
-            pool.release(d.buf);
+        Op op{};
+        op.type = OP_E1PAIR;
+        if (upload(h, pk, &op.d_packed) != FEAR_OK) return false;
+        read(op, cur);
+        op.H = cur.H; op.W = cur.W; op.Ho = cur.H; op.Wo = cur.W; op.C = cur.C; op.N = cur.C;
+        set_name(op, "e1pair_%dx%d_k3_hw%d", cur.C, cur.C, cur.H);
+        op.flops = 2.0 * 2.0 * cur.H * cur.W * (9.0 * cur.C + (double)cur.C * cur.C);
+        op.bytes = 4.0 * 2.0 * cur.H * cur.W * cur.C;
+        const T o = emit(op, cur.C, cur.H, cur.W);
+        pool.release(cur.buf);
+        cur = o;
+        bi += 2;
+        return true;
+    }
+
+    // ---- one inverted-residual block: fused 16x16 kernel, else fused tile kernel, else expand / depthwise / project launches
+    void ir_block(const FearwBlock& b) {
+        const T x = cur;
+        const T* res = b.residual ? &x : nullptr;
+        T o;
+        if (add_fused16(b.conv[0], b.conv[1], b.conv[2], x, o, res, 1, 0, 0, "ir16") ||
+            add_fused_tile(b.conv[0], b.conv[1], b.conv[2], x, o, res)) {
             pool.release(x.buf);
             cur = o;
-        } else if (b.kind == FEARW_NECK) {
-            T o;
-            if (!with_head) {
-                // write the features straight to the caller's NCHW tensor
-                const Conv& c = h->convs[b.conv[0]];
-                Op op{};
-                op.type = OP_PW; op.conv = b.conv[0];
-                op.in_buf = cur.buf; op.in_ld = cur.ld; op.in_off = cur.off;
-                op.H = cur.H; op.W = cur.W; op.Ho = cur.H; op.Wo = cur.W; op.C = c.cin_g; op.N = c.cout;
-                op.out_external = 1;
-                set_name(op, "neck_%dx%d_hw%d", c.cin_g, c.cout, cur.H);
-                op.flops = 2.0 * cur.H * cur.W * c.cin_g * c.cout;
-                op.bytes = 4.0 * cur.H * cur.W * (c.cin_g + c.cout);
-                ops.push_back(op);
-                pool.release(cur.buf);
-                cur = T{};
-            } else {
-                add_pw(b.conv[0], cur, o, nullptr, 0, 0, 0, -1);
-                snprintf(ops.back().name, sizeof(ops.back().name), "neck_%dx%d_hw%d", ops.back().C, ops.back().N, cur.H);
-                pool.release(cur.buf);
-                cur = o;
-            }
-            ++bi;
-            break;
-        } else {
-            return FEAR_ERR_FORMAT;
+            return;
         }
+        const T e = b.conv[0] >= 0 ? add_pw(b.conv[0], x, nullptr, 1) : x;
+        const T d = add_dw(b.conv[1], e, 1);
+        if (b.conv[0] >= 0) pool.release(e.buf);
+        cur = add_pw(b.conv[2], d, res, 0);
+        pool.release(d.buf);
+        pool.release(x.buf);
     }
+
+    void neck(const FearwBlock& b) {
+        if (with_head) {
+            const T o = add_pw(b.conv[0], cur, nullptr, 0);
+            set_name(ops.back(), "neck_%dx%d_hw%d", ops.back().C, ops.back().N, cur.H);
+            pool.release(cur.buf);
+            cur = o;
+            return;
+        }
+        // write the features straight to the caller's NCHW tensor
+        const Conv& c = h->convs[b.conv[0]];
+        Op op{};
+        op.type = OP_PW; op.conv = b.conv[0];
+        read(op, cur);
+        op.H = cur.H; op.W = cur.W; op.Ho = cur.H; op.Wo = cur.W; op.C = c.cin_g; op.N = c.cout;
+        op.out_external = 1;
+        set_name(op, "neck_%dx%d_hw%d", c.cin_g, c.cout, cur.H);
+        op.flops = 2.0 * cur.H * cur.W * c.cin_g * c.cout;
+        op.bytes = 4.0 * cur.H * cur.W * (c.cin_g + c.cout);
+        ops.push_back(op);
+        pool.release(cur.buf);
+        cur = T{};
+    }
+
+    // ---- trunk + neck
+    int trunk() {
+        stem();
+        while (bi < h->blocks.size()) {
+            if (chain16_neck()) return FEAR_OK;          // the neck is consumed: continue with the head
+            if (chain32() || e1_pair()) continue;
+            const FearwBlock& b = h->blocks[bi++];
+            if (b.kind == FEARW_IR) {
+                ir_block(b);
+            } else if (b.kind == FEARW_NECK) {
+                neck(b);
+                return FEAR_OK;
+            } else {
+                return FEAR_ERR_FORMAT;
+            }
+        }
+        return FEAR_OK;
+    }
+
     // ---- bf16 activation storage for the HBM-bound front of the trunk (FEAR_OPT_MATH = 2, FEAR_OPT_BF16_STORE): a tile op writes
-    //      bf16 when its output map is at least 64 x 64 and its consumer has a storage variant that reads it (kTileBf16)
-    if (h->math == 2 && h->bf16_store && with_head && hw == 256 && !small && h->fuse) {
+    //      bf16 when its output map is at least 64 x 64 and its consumer has a storage variant that reads it (TileRow::bf16_io)
+    void bf16_storage() {
+        if (!(h->math == 2 && h->bf16_store && with_head && hw == 256 && !small && h->fuse)) return;
         auto reads_bf16 = [&](const Op& op) {      // some variant of this op takes a bf16 input (and residual, if it has one)
             if (op.type != OP_IRTILE || op.stem || op.splitk) return false;
             const int need = IO_X_BF16 | (op.res_buf >= 0 ? IO_R_BF16 : 0);
-            return find_tile_bf16(0, op.fused_id, need) || find_tile_bf16(0, op.fused_id, need | IO_Y_BF16);
+            return op.tile->io_variant(need) || op.tile->io_variant(need | IO_Y_BF16);
         };
         // writes[i]: op i stores its output as bf16.  Start from every candidate, then clear flags until each op has a storage
         // variant for the (input, residual, output) combination it ends up with: a consumer may exist only as "bf16 in AND out"
-        // (kTileBf16 is a list of measured instantiations, not a full cross product), and whether ITS output goes out as bf16
+        // (bf16_io lists measured instantiations, not a full cross product), and whether ITS output goes out as bf16
         // depends on the op behind it.  A combination without a variant is never an error of the plan — this is an optional
         // optimisation — the producer in front of it just keeps fp32.
         std::vector<char> writes(ops.size(), 0);
@@ -1205,7 +1146,7 @@ int build_plan_uncached(fear_handle* h, int hw, bool with_head, int mode, Plan**
                     continue;
                 }
                 const int io = bits(i);
-                if (!io || find_tile_bf16(op.stem, op.fused_id, io)) continue;
+                if (!io || op.tile->io_variant(io)) continue;
                 if (writes[i]) writes[i] = 0;                  // first try this op with an fp32 output ...
                 else if (i > 0 && writes[i - 1]) writes[i - 1] = 0;   // ... then hand it an fp32 input
                 changed = true;
@@ -1214,236 +1155,254 @@ int build_plan_uncached(fear_handle* h, int hw, bool with_head, int mode, Plan**
         for (size_t i = 0; i < ops.size(); ++i)
             if (ops[i].type == OP_IRTILE && !ops[i].splitk) ops[i].io_bf16 = bits(i);
     }
+
     // ---- head (BoxTower.forward, model/blocks.py:174-194)
-    if (with_head) {
+    struct Head {
         const FearwBlock* role[9] = {nullptr};
-        std::vector<const FearwBlock*> bbox_tower, cls_tower;
-        for (; bi < h->blocks.size(); ++bi) {
-            const FearwBlock& b = h->blocks[bi];
-            if (b.kind != FEARW_SEP || b.role < 1 || b.role > 8) return FEAR_ERR_FORMAT;
-            if (b.role == FEARW_BBOX_TOWER) bbox_tower.push_back(&b);
-            else if (b.role == FEARW_CLS_TOWER) cls_tower.push_back(&b);
-            else role[b.role] = &b;
+        std::vector<const FearwBlock*> tower[2];      // [0]: classification, [1]: regression
+        T feat;
+    };
+    static constexpr int kTz = 64;                     // template positions: (128/16)^2, matches fear_track's tmpl shape
+
+    // SepConv + BN + ReLU (depthwise without activation, pointwise with ReLU): one fused 16x16 launch, else the two launches;
+    // `consume`: the input is released once read
+    T sep_conv(const FearwBlock* b, const T& in, bool consume, int out_ld = 0) {
+        T o;
+        if (add_fused16(-1, b->conv[0], b->conv[1], in, o, nullptr, 0, 1, out_ld, "sep16")) {
+            if (consume) pool.release(in.buf);
+            return o;
         }
-        for (int r : {FEARW_CLS_ENCODE, FEARW_REG_ENCODE, FEARW_CLS_CORR, FEARW_REG_CORR, FEARW_BBOX_PRED, FEARW_CLS_PRED})
-            if (!role[r]) return FEAR_ERR_FORMAT;
-        const T feat = cur;
-        const int S = feat.H;               // 16 for a 256 search crop
-        const int tz = 64;                  // template positions: (128/16)^2, matches fear_track's tmpl shape
-        // one branch: encode -> correlation/concat -> corr sep -> towers -> pred
-        auto branch = [&](const FearwBlock* enc, const FearwBlock* corr, const std::vector<const FearwBlock*>& tower,
-                          const FearwBlock* pred, bool is_cls) -> int {
-            const Conv& enc_pw = h->convs[enc->conv[1]];
-            const Conv& corr_dw = h->convs[corr->conv[0]];
-            if (corr_dw.cout != enc_pw.cout + tz) return FEAR_ERR_FORMAT;
-            T d, cat;
-            // encode pointwise writes channels [0, C) of the concat buffer; correlation fills [C, C+64)
-            bool corr_done = false;
-            if (!add_fused16(-1, enc->conv[0], enc->conv[1], feat, cat, nullptr, 0, 1, corr_dw.cout, "sep16")) {
-                add_dw(enc->conv[0], feat, d, 0);
-                add_pw(enc->conv[1], d, cat, nullptr, 1, corr_dw.cout, 0, -1);
-                pool.release(d.buf);
-            } else if (!h->math && !small && enc_pw.cout == kCorrC && h->convs[enc->conv[0]].cout == kCorrC &&
-                       h->convs[enc->conv[0]].k == 3 && tz == kCorrTz) {
-                // the correlation rides in the encode kernel's epilogue: its output fragments are the B operand as they stand
-                Op& eop = ops.back();
-                eop.corr_fused = 1;
-                eop.tmpl_cls = is_cls ? 1 : 0;
-                set_name(eop, is_cls ? "sep16_corr_cls_%dx%d_k%d" : "sep16_corr_reg_%dx%d_k%d", enc_pw.cout, tz, 3);
-                eop.flops += 2.0 * S * S * enc_pw.cout * tz;
-                eop.bytes += 4.0 * (S * S * tz + (double)enc_pw.cout * tz);
-                corr_done = true;
-            }
-            if (!corr_done) {
-                Op op{};
-                op.type = OP_CORR;
-                op.in_buf = cat.buf; op.in_ld = cat.ld; op.in_off = 0;
-                op.out_buf = cat.buf; op.out_ld = cat.ld; op.out_off = enc_pw.cout;
-                op.H = S; op.W = S; op.Ho = S; op.Wo = S; op.C = enc_pw.cout; op.N = tz;
-                op.tmpl_cls = is_cls ? 1 : 0;
-                set_name(op, is_cls ? "corr_cls_%dx%d_hw%d" : "corr_reg_%dx%d_hw%d", op.C, tz, S);
-                op.flops = 2.0 * S * S * op.C * tz;
-                op.bytes = 4.0 * (S * S * (op.C + tz) + (double)op.C * tz);
-                ops.push_back(op);
-            }
-            T catv = cat;
-            catv.C = corr_dw.cout;
-            T x;
-            if (add_fused16(-1, corr->conv[0], corr->conv[1], catv, x, nullptr, 0, 1, 0, "sep16")) {
-                pool.release(cat.buf);
-            } else {
-                add_dw(corr->conv[0], catv, d, 0);
-                pool.release(cat.buf);
-                add_pw(corr->conv[1], d, x, nullptr, 1, 0, 0, -1);
-                pool.release(d.buf);
-            }
-            for (const FearwBlock* tb : tower) {
-                T y;
-                if (add_fused16(-1, tb->conv[0], tb->conv[1], x, y, nullptr, 0, 1, 0, "sep16")) {
-                    pool.release(x.buf);
-                } else {
-                    add_dw(tb->conv[0], x, d, 0);
-                    pool.release(x.buf);
-                    add_pw(tb->conv[1], d, y, nullptr, 1, 0, 0, -1);
-                    pool.release(d.buf);
-                }
-                x = y;
-            }
-            if (h->convs[pred->conv[1]].cout != (is_cls ? 1 : 4)) return FEAR_ERR_FORMAT;
-            // the prediction head rides in the epilogue of the last tower SepConv (its output never reaches HBM)
-            if (h->fuse && !h->math && !small && !ops.empty() && ops.back().type == OP_IR16 && ops.back().out_buf == x.buf &&
-                ops.back().C == 256 && ops.back().N == 256 && !ops.back().corr_fused && ops.back().res_buf < 0 &&
-                h->convs[ops.back().conv_d].k == 3 && h->convs[pred->conv[0]].k == 3 && h->convs[pred->conv[0]].cout == 256 &&
-                h->convs[pred->conv[0]].stride == 1 && h->convs[pred->conv[1]].has_bias && !h->convs[pred->conv[0]].relu) {
-                Op& top = ops.back();
-                if (pack_fused16(h, -1, pred->conv[0], pred->conv[1], &top.pred_packed) == FEAR_OK) {
-                    const Conv& pc = h->convs[pred->conv[1]];
-                    top.pred_fused = 1;
-                    top.pred_conv_p = pred->conv[1];
-                    top.pred_cout = pc.cout; top.act = pred->act; top.out_external = is_cls ? 3 : 2;
-                    set_name(top, is_cls ? "sep16_cls_pred_%dx%dx%d" : "sep16_bbox_pred_%dx%dx%d", 256, 256, pc.cout);
-                    top.flops += 2.0 * 256 * (256.0 * 9 + 256.0 * pc.cout);
-                    top.bytes = 4.0 * 256 * (256 + pc.cout);
-                    pool.release(x.buf);
-                    return FEAR_OK;
-                }
-            }
-            if (add_fused_pred(pred->conv[0], pred->conv[1], x, pred->act, is_cls ? 3 : 2)) {
+        const T d = add_dw(b->conv[0], in, 0);
+        if (consume) pool.release(in.buf);
+        o = add_pw(b->conv[1], d, nullptr, 1, out_ld);
+        pool.release(d.buf);
+        return o;
+    }
+
+    // one branch: encode -> correlation/concat -> corr sep -> towers -> pred
+    int head_branch(const Head& hd, bool is_cls) {
+        const FearwBlock* enc = hd.role[is_cls ? FEARW_CLS_ENCODE : FEARW_REG_ENCODE];
+        const FearwBlock* corr = hd.role[is_cls ? FEARW_CLS_CORR : FEARW_REG_CORR];
+        const FearwBlock* pred = hd.role[is_cls ? FEARW_CLS_PRED : FEARW_BBOX_PRED];
+        const T& feat = hd.feat;
+        const int S = feat.H, tz = kTz;     // S = 16 for a 256 search crop
+        const Conv& enc_pw = h->convs[enc->conv[1]];
+        const Conv& corr_dw = h->convs[corr->conv[0]];
+        if (corr_dw.cout != enc_pw.cout + tz) return FEAR_ERR_FORMAT;
+        // encode pointwise writes channels [0, C) of the concat buffer; correlation fills [C, C+64)
+        const T cat = sep_conv(enc, feat, false, corr_dw.cout);
+        if (ops.back().type == OP_IR16 && throughput_fp32() && enc_pw.cout == kCorrC && h->convs[enc->conv[0]].cout == kCorrC &&
+            h->convs[enc->conv[0]].k == 3 && tz == kCorrTz) {
+            // the correlation rides in the encode kernel's epilogue: its output fragments are the B operand as they stand
+            Op& eop = ops.back();
+            eop.corr_fused = 1;
+            eop.tmpl_cls = is_cls ? 1 : 0;
+            set_name(eop, is_cls ? "sep16_corr_cls_%dx%d_k%d" : "sep16_corr_reg_%dx%d_k%d", enc_pw.cout, tz, 3);
+            eop.flops += 2.0 * S * S * enc_pw.cout * tz;
+            eop.bytes += 4.0 * (S * S * tz + (double)enc_pw.cout * tz);
+        } else {
+            Op op{};
+            op.type = OP_CORR;
+            read(op, cat);
+            op.out_buf = cat.buf; op.out_ld = cat.ld; op.out_off = enc_pw.cout;
+            op.H = S; op.W = S; op.Ho = S; op.Wo = S; op.C = enc_pw.cout; op.N = tz;
+            op.tmpl_cls = is_cls ? 1 : 0;
+            set_name(op, is_cls ? "corr_cls_%dx%d_hw%d" : "corr_reg_%dx%d_hw%d", op.C, tz, S);
+            op.flops = 2.0 * S * S * op.C * tz;
+            op.bytes = 4.0 * (S * S * (op.C + tz) + (double)op.C * tz);
+            ops.push_back(op);
+        }
+        T catv = cat;
+        catv.C = corr_dw.cout;
+        T x = sep_conv(corr, catv, true);
+        for (const FearwBlock* tb : hd.tower[is_cls ? 0 : 1]) x = sep_conv(tb, x, true);
+        const Conv& pd = h->convs[pred->conv[0]];
+        const Conv& pc = h->convs[pred->conv[1]];
+        if (pc.cout != (is_cls ? 1 : 4)) return FEAR_ERR_FORMAT;
+        // the prediction head rides in the epilogue of the last tower SepConv (its output never reaches HBM)
+        if (throughput_fp32() && ops.back().type == OP_IR16 && ops.back().out_buf == x.buf && ops.back().C == 256 &&
+            ops.back().N == 256 && !ops.back().corr_fused && ops.back().res_buf < 0 && h->convs[ops.back().conv_d].k == 3 &&
+            pd.k == 3 && pd.cout == 256 && pd.stride == 1 && pc.has_bias && !pd.relu) {
+            Op& top = ops.back();
+            if (pack_fused16(h, -1, pred->conv[0], pred->conv[1], &top.pred_packed) == FEAR_OK) {
+                top.pred_fused = 1;
+                top.pred_conv_p = pred->conv[1];
+                top.pred_cout = pc.cout; top.act = pred->act; top.out_external = is_cls ? 3 : 2;
+                set_name(top, is_cls ? "sep16_cls_pred_%dx%dx%d" : "sep16_bbox_pred_%dx%dx%d", 256, 256, pc.cout);
+                top.flops += 2.0 * 256 * (256.0 * 9 + 256.0 * pc.cout);
+                top.bytes = 4.0 * 256 * (256 + pc.cout);
                 pool.release(x.buf);
                 return FEAR_OK;
             }
-            add_dw(pred->conv[0], x, d, 0);
+        }
+        if (add_fused_pred(pred->conv[0], pred->conv[1], x, pred->act, is_cls ? 3 : 2)) {
             pool.release(x.buf);
-            {
-                const Conv& c = h->convs[pred->conv[1]];
-                if (c.cout != (is_cls ? 1 : 4)) return FEAR_ERR_FORMAT;
-                Op op{};
-                op.type = OP_PW_SMALL; op.conv = pred->conv[1];
-                op.in_buf = d.buf; op.in_ld = d.ld;
-                op.H = S; op.W = S; op.Ho = S; op.Wo = S; op.C = c.cin_g; op.N = c.cout;
-                op.act = pred->act;
-                op.out_external = is_cls ? 3 : 2;
-                set_name(op, is_cls ? "cls_pred_%dx%d_hw%d" : "bbox_pred_%dx%d_hw%d", c.cin_g, c.cout, S);
-                op.flops = 2.0 * S * S * c.cin_g * c.cout;
-                op.bytes = 4.0 * S * S * (c.cin_g + c.cout);
-                ops.push_back(op);
-            }
-            pool.release(d.buf);
             return FEAR_OK;
+        }
+        const T d = add_dw(pred->conv[0], x, 0);
+        pool.release(x.buf);
+        Op op{};
+        op.type = OP_PW_SMALL; op.conv = pred->conv[1];
+        op.in_buf = d.buf; op.in_ld = d.ld;
+        op.H = S; op.W = S; op.Ho = S; op.Wo = S; op.C = pc.cin_g; op.N = pc.cout;
+        op.act = pred->act;
+        op.out_external = is_cls ? 3 : 2;
+        set_name(op, is_cls ? "cls_pred_%dx%d_hw%d" : "bbox_pred_%dx%d_hw%d", pc.cin_g, pc.cout, S);
+        op.flops = 2.0 * S * S * pc.cin_g * pc.cout;
+        op.bytes = 4.0 * S * S * (pc.cin_g + pc.cout);
+        ops.push_back(op);
+        pool.release(d.buf);
+        return FEAR_OK;
+    }
+
+    // ---- the throughput plan in fp32 / bf16: both branches, all eight SepConvs + correlations + prediction heads in ONE launch
+    bool head_chain(const Head& hd) {
+        const T& feat = hd.feat;
+        const int S = feat.H;
+        if (!h->head_chain || !h->fuse || h->math == 1 || small || S != 16 || feat.C != HeadChainG::C || hd.tower[0].size() != 2 ||
+            hd.tower[1].size() != 2)
+            return false;
+        // a later shape check or upload may still fail (and the plan then falls back to the sep16 launches): whatever this
+        // attempt uploaded is freed again — up to twenty packed weight buffers per branch would otherwise stay booked in
+        // plan_allocs until the plans are dropped, once per plan rebuild
+        const size_t allocs0 = h->plan_allocs.size();
+        auto undo = [&]() {
+            while (h->plan_allocs.size() > allocs0) { hipFree(h->plan_allocs.back()); h->plan_allocs.pop_back(); }
+            return false;
         };
-        // Small batches (one workgroup per crop leaves most CUs idle): the two branches are independent, so the bbox branch is
-        // planned on buffers of its own and run_plan puts it on a second stream next to the cls branch.
-        // The throughput plan does the same when FEAR_OPT_DUAL_HEAD is on (off by default): a sep16 workgroup needs 77 KB of LDS and
-        // 116 VGPRs, so one workgroup of each branch fits on a CU at the same time — measured: no gain, the kernels are ALU-bound.
-        // ---- the throughput plan in fp32: both branches, all eight SepConvs + correlations + prediction heads in ONE launch
-        auto head_chain = [&]() -> bool {
-            if (!h->head_chain || !h->fuse || h->math == 1 || small || S != 16 || feat.C != HeadChainG::C || bbox_tower.size() != 2 ||
-                cls_tower.size() != 2)
-                return false;
-            // a later shape check or upload may still fail (and the plan then falls back to the sep16 launches): whatever this
-            // attempt uploaded is freed again — up to twenty packed weight buffers per branch would otherwise stay booked in
-            // plan_allocs until the plans are dropped, once per plan rebuild
-            const size_t allocs0 = h->plan_allocs.size();
-            auto undo = [&]() {
-                while (h->plan_allocs.size() > allocs0) { hipFree(h->plan_allocs.back()); h->plan_allocs.pop_back(); }
-                return false;
-            };
-            Op op{};
-            op.type = OP_HEADCHAIN;
-            op.math = h->math;          // 0: headchain_kernel (exact fp32) | 2: headchain_b_kernel (bf16 matrix pipe)
-            double fl = 0;
-            for (int br = 0; br < 2; ++br) {
-                const bool is_cls = br == 0;
-                const FearwBlock* seq[4] = {role[is_cls ? FEARW_CLS_ENCODE : FEARW_REG_ENCODE], role[is_cls ? FEARW_CLS_CORR : FEARW_REG_CORR],
-                                            (is_cls ? cls_tower : bbox_tower)[0], (is_cls ? cls_tower : bbox_tower)[1]};
-                const FearwBlock* pred = role[is_cls ? FEARW_CLS_PRED : FEARW_BBOX_PRED];
-                std::vector<float> sep[4];
+        Op op{};
+        op.type = OP_HEADCHAIN;
+        op.math = h->math;          // 0: headchain_kernel (exact fp32) | 2: headchain_b_kernel (bf16 matrix pipe)
+        double fl = 0;
+        for (int br = 0; br < 2; ++br) {
+            const bool is_cls = br == 0;
+            const std::vector<const FearwBlock*>& tower = hd.tower[br];
+            const FearwBlock* seq[4] = {hd.role[is_cls ? FEARW_CLS_ENCODE : FEARW_REG_ENCODE], hd.role[is_cls ? FEARW_CLS_CORR : FEARW_REG_CORR],
+                                        tower[0], tower[1]};
+            const FearwBlock* pred = hd.role[is_cls ? FEARW_CLS_PRED : FEARW_BBOX_PRED];
+            std::vector<float> sep[4];
+            for (int l = 0; l < 4; ++l) {
+                const Conv& d = h->convs[seq[l]->conv[0]];
+                const Conv& pw = h->convs[seq[l]->conv[1]];
+                const int cin = l == 1 ? HeadChainG::CC : HeadChainG::C;
+                // SepConv + BN + ReLU: depthwise 3x3 s1 without activation, pointwise to 256 with bias and ReLU
+                if (!d.is_dw() || !pw.is_pw() || d.k != 3 || d.stride != 1 || d.cout != cin || d.relu || pw.cin_g != cin ||
+                    pw.cout != HeadChainG::C || !pw.has_bias || !pw.relu)
+                    return undo();
+                sep[l] = pack_fused16_host(h, -1, seq[l]->conv[0], seq[l]->conv[1]);
+                fl += 2.0 * 256 * ((double)cin * 9 + (double)cin * HeadChainG::C);
+            }
+            const Conv& pd = h->convs[pred->conv[0]];
+            const Conv& pp = h->convs[pred->conv[1]];
+            if (!pd.is_dw() || !pp.is_pw() || pd.k != 3 || pd.stride != 1 || pd.cout != HeadChainG::C || pd.relu ||
+                pp.cin_g != HeadChainG::C || pp.cout != (is_cls ? 1 : 4) || !pp.has_bias)
+                return undo();
+            if (h->math == 2) {
+                // bf16 fragments in the kernel's k order, fp32 bias / taps; prediction head: taps then 8 fragments of its 1x1
                 for (int l = 0; l < 4; ++l) {
                     const Conv& d = h->convs[seq[l]->conv[0]];
                     const Conv& pw = h->convs[seq[l]->conv[1]];
                     const int cin = l == 1 ? HeadChainG::CC : HeadChainG::C;
-                    // SepConv + BN + ReLU: depthwise 3x3 s1 without activation, pointwise to 256 with bias and ReLU
-                    if (!d.is_dw() || !pw.is_pw() || d.k != 3 || d.stride != 1 || d.cout != cin || d.relu || pw.cin_g != cin ||
-                        pw.cout != HeadChainG::C || !pw.has_bias || !pw.relu)
+                    if (upload(h, headchain_b_pack(pw.w.data(), cin, HeadChainG::C, pw.b.data()), &op.hc_w[br][l]) != FEAR_OK ||
+                        upload(h, headchain_b_taps(d.w.data(), d.has_bias ? d.b.data() : nullptr, cin, 3), &op.hc_taps[br][l]) != FEAR_OK)
                         return undo();
-                    sep[l] = pack_fused16_host(h, -1, seq[l]->conv[0], seq[l]->conv[1]);
-                    fl += 2.0 * 256 * ((double)cin * 9 + (double)cin * HeadChainG::C);
                 }
-                const Conv& pd = h->convs[pred->conv[0]];
-                const Conv& pp = h->convs[pred->conv[1]];
-                if (!pd.is_dw() || !pp.is_pw() || pd.k != 3 || pd.stride != 1 || pd.cout != HeadChainG::C || pd.relu ||
-                    pp.cin_g != HeadChainG::C || pp.cout != (is_cls ? 1 : 4) || !pp.has_bias)
+                std::vector<float> pwk = headchain_b_taps(pd.w.data(), pd.has_bias ? pd.b.data() : nullptr, HeadChainG::C, 3);
+                for (int P = 0; P < HeadChainG::C / 32; ++P) headchain_b_push_frag(pwk, pp.w.data(), HeadChainG::C, pp.cout, 0, P);
+                if (upload(h, pwk, &op.hc_pred[br]) != FEAR_OK) return undo();
+            } else {
+                for (int l = 0; l < 4; ++l) {
+                    const Conv& pw = h->convs[seq[l]->conv[1]];
+                    if (upload(h, headchain_pack(sep[l].data(), l == 1 ? HeadChainG::CC : HeadChainG::C, pw.b.data(),
+                                                 l < 3 ? sep[l + 1].data() : nullptr, 3), &op.hc_w[br][l]) != FEAR_OK)
+                        return undo();
+                }
+                if (upload(h, headchain_pack_dw(sep[0].data(), 0, HeadChainG::C / 16, 3), &op.hc_wd0[br]) != FEAR_OK ||
+                    upload(h, headchain_pack_dw(sep[1].data(), HeadChainG::C / 16, HeadChainG::TZ / 16, 3), &op.hc_wdc[br]) != FEAR_OK ||
+                    pack_fused16(h, -1, pred->conv[0], pred->conv[1], &op.hc_pred[br]) != FEAR_OK)
                     return undo();
-                if (h->math == 2) {
-                    // bf16 fragments in the kernel's k order, fp32 bias / taps; prediction head: taps then 8 fragments of its 1x1
-                    for (int l = 0; l < 4; ++l) {
-                        const Conv& d = h->convs[seq[l]->conv[0]];
-                        const Conv& pw = h->convs[seq[l]->conv[1]];
-                        const int cin = l == 1 ? HeadChainG::CC : HeadChainG::C;
-                        if (upload(h, headchain_b_pack(pw.w.data(), cin, HeadChainG::C, pw.b.data()), &op.hc_w[br][l]) != FEAR_OK ||
-                            upload(h, headchain_b_taps(d.w.data(), d.has_bias ? d.b.data() : nullptr, cin, 3), &op.hc_taps[br][l]) != FEAR_OK)
-                            return undo();
-                    }
-                    std::vector<float> pwk = headchain_b_taps(pd.w.data(), pd.has_bias ? pd.b.data() : nullptr, HeadChainG::C, 3);
-                    for (int P = 0; P < HeadChainG::C / 32; ++P) headchain_b_push_frag(pwk, pp.w.data(), HeadChainG::C, pp.cout, 0, P);
-                    if (upload(h, pwk, &op.hc_pred[br]) != FEAR_OK) return undo();
-                } else {
-                    for (int l = 0; l < 4; ++l) {
-                        const Conv& pw = h->convs[seq[l]->conv[1]];
-                        if (upload(h, headchain_pack(sep[l].data(), l == 1 ? HeadChainG::CC : HeadChainG::C, pw.b.data(),
-                                                     l < 3 ? sep[l + 1].data() : nullptr, 3), &op.hc_w[br][l]) != FEAR_OK)
-                            return undo();
-                    }
-                    if (upload(h, headchain_pack_dw(sep[0].data(), 0, HeadChainG::C / 16, 3), &op.hc_wd0[br]) != FEAR_OK ||
-                        upload(h, headchain_pack_dw(sep[1].data(), HeadChainG::C / 16, HeadChainG::TZ / 16, 3), &op.hc_wdc[br]) != FEAR_OK ||
-                        pack_fused16(h, -1, pred->conv[0], pred->conv[1], &op.hc_pred[br]) != FEAR_OK)
-                        return undo();
-                }
-                op.hc_pred_conv[br] = pred->conv[1];
-                op.hc_pred_act[br] = pred->act;
-                fl += 2.0 * 256 * ((double)HeadChainG::C * HeadChainG::TZ + (double)HeadChainG::C * 9 + (double)HeadChainG::C * pp.cout);
             }
-            op.in_buf = feat.buf; op.in_ld = feat.ld; op.in_off = feat.off;
-            op.H = S; op.W = S; op.Ho = S; op.Wo = S; op.C = feat.C; op.N = 5;
-            op.relu_dw = 0; op.relu = 1;
-            // scratch of the depthwise results, both branches of a crop side by side
-            op.out_buf = pool.acquire();
-            if ((size_t)2 * HeadChainG::D_FLOATS > max_elems) max_elems = (size_t)2 * HeadChainG::D_FLOATS;
-            snprintf(op.name, sizeof(op.name), h->math == 2 ? "headchain_bf16_boxtower_%dx%d" : "headchain_boxtower_%dx%d", feat.C, tz);
-            op.flops = fl;
-            op.bytes = 4.0 * (S * S * feat.C + 2.0 * feat.C * tz + 5.0 * S * S);
-            ops.push_back(op);
-            pool.release(op.out_buf);
-            return true;
-        };
-        if (head_chain()) {
-            pool.release(feat.buf);
-            plan->n_bufs = pool.count;
-            plan->buf_floats_per_crop = (max_elems + 63) & ~(size_t)63;
-            *out = plan.get();
-            h->plans[key] = std::move(plan);
-            return FEAR_OK;
+            op.hc_pred_conv[br] = pred->conv[1];
+            op.hc_pred_act[br] = pred->act;
+            fl += 2.0 * 256 * ((double)HeadChainG::C * HeadChainG::TZ + (double)HeadChainG::C * 9 + (double)HeadChainG::C * pp.cout);
         }
-        const bool dual = small || (h->dual_head && h->fuse && !h->math);
-        const size_t head_first = ops.size();
-        pool.hold = dual;
-        int st = branch(role[FEARW_CLS_ENCODE], role[FEARW_CLS_CORR], cls_tower, role[FEARW_CLS_PRED], true);
-        if (st != FEAR_OK) return st;
-        const size_t reg_first = ops.size();
-        st = branch(role[FEARW_REG_ENCODE], role[FEARW_REG_CORR], bbox_tower, role[FEARW_BBOX_PRED], false);
-        if (st != FEAR_OK) return st;
-        pool.flush();
-        if (dual) {
-            for (size_t i = reg_first; i < ops.size(); ++i) ops[i].lane = 1;
-            plan->head_first = (int)head_first;
-        }
-        pool.release(feat.buf);
+        read(op, feat);
+        op.H = S; op.W = S; op.Ho = S; op.Wo = S; op.C = feat.C; op.N = 5;
+        op.relu_dw = 0; op.relu = 1;
+        // scratch of the depthwise results, both branches of a crop side by side
+        op.out_buf = pool.acquire();
+        track((size_t)2 * HeadChainG::D_FLOATS);
+        set_name(op, h->math == 2 ? "headchain_bf16_boxtower_%dx%d" : "headchain_boxtower_%dx%d", feat.C, kTz);
+        op.flops = fl;
+        op.bytes = 4.0 * (S * S * feat.C + 2.0 * feat.C * kTz + 5.0 * S * S);
+        ops.push_back(op);
+        pool.release(op.out_buf);
+        return true;
     }
-    if (small)
-        for (Op& op : ops)
-            if (op.type == OP_PW || op.type == OP_CORR) op.pw_split = 1;
-    plan->n_bufs = pool.count;
-    plan->buf_floats_per_crop = (max_elems + 63) & ~(size_t)63;
+
+    int head() {
+        Head hd;
+        for (; bi < h->blocks.size(); ++bi) {
+            const FearwBlock& b = h->blocks[bi];
+            if (b.kind != FEARW_SEP || b.role < 1 || b.role > 8) return FEAR_ERR_FORMAT;
+            if (b.role == FEARW_BBOX_TOWER) hd.tower[1].push_back(&b);
+            else if (b.role == FEARW_CLS_TOWER) hd.tower[0].push_back(&b);
+            else hd.role[b.role] = &b;
+        }
+        for (int r : {FEARW_CLS_ENCODE, FEARW_REG_ENCODE, FEARW_CLS_CORR, FEARW_REG_CORR, FEARW_BBOX_PRED, FEARW_CLS_PRED})
+            if (!hd.role[r]) return FEAR_ERR_FORMAT;
+        hd.feat = cur;
+        if (!head_chain(hd)) {
+            // Small batches (one workgroup per crop leaves most CUs idle): the two branches are independent, so the bbox branch is
+            // planned on buffers of its own and run_plan puts it on a second stream next to the cls branch.
+            // The throughput plan does the same when FEAR_OPT_DUAL_HEAD is on (off by default): a sep16 workgroup needs 77 KB of
+            // LDS and 116 VGPRs, so one workgroup of each branch fits on a CU at the same time — measured: no gain, the kernels are
+            // ALU-bound.
+            const bool dual = small || (h->dual_head && h->fuse && !h->math);
+            const size_t head_first = ops.size();
+            pool.hold = dual;
+            int st = head_branch(hd, true);
+            if (st != FEAR_OK) return st;
+            const size_t reg_first = ops.size();
+            st = head_branch(hd, false);
+            if (st != FEAR_OK) return st;
+            pool.flush();
+            if (dual) {
+                for (size_t i = reg_first; i < ops.size(); ++i) ops[i].lane = 1;
+                plan.head_first = (int)head_first;
+            }
+        }
+        pool.release(hd.feat.buf);
+        return FEAR_OK;
+    }
+
+    int build() {
+        plan.with_head = with_head;
+        plan.small = small;
+        int st = trunk();
+        if (st != FEAR_OK) return st;
+        bf16_storage();
+        if (with_head && (st = head()) != FEAR_OK) return st;
+        if (small)
+            for (Op& op : ops)
+                if (op.type == OP_PW || op.type == OP_CORR) op.pw_split = 1;
+        plan.n_bufs = pool.count;
+        plan.buf_floats_per_crop = (max_elems + 63) & ~(size_t)63;
+        return FEAR_OK;
+    }
+};
+
+int build_plan(fear_handle* h, int hw, bool with_head, PlanKind kind, Plan** out) {
+    const auto key = std::make_pair(hw, (with_head ? 1 : 0) + 2 * (int)kind);
+    auto it = h->plans.find(key);
+    if (it != h->plans.end()) { *out = it->second.get(); return FEAR_OK; }
+    if (hw < 32 || hw % 32 != 0 || hw > 1024) return FEAR_ERR_SHAPE;
+    if (with_head && !h->has_head) return FEAR_ERR_NOHEAD;
+    std::unique_ptr<Plan> plan(new Plan);
+    h->building_plan = true;          // packed weights uploaded from here on belong to the plan cache
+    const int st = PlanBuilder(h, hw, with_head, kind, *plan).build();
+    h->building_plan = false;
+    if (st != FEAR_OK) return st;
     *out = plan.get();
     h->plans[key] = std::move(plan);
     return FEAR_OK;
@@ -1526,79 +1485,28 @@ __global__ void delay_kernel(long long ticks) {
     for (int i = 0; i < 100000 && wall_clock64() - t0 < ticks; ++i) __builtin_amdgcn_s_sleep(16);
 }
 
-// crop0 / sub: the second half of a split pass (FEAR_OPT_SPLIT_STREAMS) — its crops use the workspace behind the first half's
-// (every pool buffer is sized for a full pass at the largest per-crop footprint, so crop c0's share starts c0 footprints in), and the
-// caller (track_impl) does the stream bookkeeping around both halves
-int run_plan(fear_handle* h, Plan& p, int n, const Ext& ext, hipStream_t s_main, size_t crop0 = 0, bool sub = false) {
-    if (!h->fused_attr_set) {
-        for (const Fused16& f : kFused16) {
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
-            if (f.kernel_splitk)
-                HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel_splitk),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
-            if (f.kernel_tiny)
-                HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel_tiny),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_tiny));
-        }
-        for (const Fused16& f : kFused16H)
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
-        for (const FusedTile& f : kFusedTileV4)
-            if (f.kernel)
-                HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
-        for (const FusedTile& f : kFusedTile)
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
-        for (const FusedTile& f : kFusedTileSmall)
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
-        for (const FusedTile& f : kFusedTileTiny)
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
-        for (const TileKSplit& f : kTileKSplit)
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
-        for (const FusedTile& f : kFusedTileH)
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
-        for (const FusedTile& f : kFusedTileB)
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
-        for (const Fused16& f : kFused16B)
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_bytes));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kSep16PredKernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kSep16PredLds));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kSep16CorrKernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kSep16CorrLds));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kChainXSKernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kChainXSLds));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kChain32XSKernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, C32Geom::LDS_BYTES));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kChain32_16XSKernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kChain32_16Lds));
-        for (const TileBf16& tb : kTileBf16) {
-            const int lds = tb.stem ? kStemTile.lds_bytes : (tb.id == 1 || tb.id == 3) ? kFusedTileB[tb.id].lds_bytes : kFusedTile[tb.id].lds_bytes;
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(tb.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        }
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(e1pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, E1PairGeom::LDS_BYTES));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kHeadChainKernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, HeadChainG::LDS_BYTES));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kHeadChainBKernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, HeadChainBG::LDS_BYTES));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kStemTile.kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kStemTile.lds_bytes));
-        h->fused_attr_set = true;
-    }
-    // one workspace per handle: a call on another stream than the previous one must not overtake it
-    // (the event was recorded on the previous call's stream at the END of that call, below: the old stream handle is only
-    // compared here, never used — the caller may have destroyed that stream since)
+// One workspace per handle: a call on another stream than the previous one must not overtake it.  `issue` enqueues the call's
+// work on s; the event is recorded on s at the END of the call (also after a failure: whatever was enqueued still uses the
+// workspace), and the old stream handle is only compared, never used — the caller may have destroyed that stream since.
+template <class F>
+int on_caller_stream(fear_handle* h, hipStream_t s, F&& issue) {
     if (!h->stream_switch) HIP_TRY(h, hipEventCreateWithFlags(&h->stream_switch, hipEventDisableTiming));
-    if (!sub) {
-        if (h->last_stream_valid && h->last_stream != s_main) HIP_TRY(h, hipStreamWaitEvent(s_main, h->stream_switch, 0));
-        h->last_stream = s_main;
-        h->last_stream_valid = true;
+    if (h->last_stream_valid && h->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, h->stream_switch, 0));
+    h->last_stream = s;
+    h->last_stream_valid = true;
+    const int st = issue();
+    HIP_TRY(h, hipEventRecord(h->stream_switch, s));
+    return st;
+}
+
+// Enqueue one pass of n crops; the caller wraps it in on_caller_stream.  crop0: the second half of a split pass
+// (FEAR_OPT_SPLIT_STREAMS) — its crops use the workspace behind the first half's (every pool buffer is sized for a full pass at
+// the largest per-crop footprint, so crop c0's share starts c0 footprints in)
+int run_plan(fear_handle* h, Plan& p, int n, const Ext& ext, hipStream_t s_main, size_t crop0 = 0) {
+    if (!h->fused_attr_set) {
+        const int st = set_lds_limits(h);
+        if (st != FEAR_OK) return st;
+        h->fused_attr_set = true;
     }
     const size_t slab = p.buf_floats_per_crop * pass_cap(h, p);
     auto buf = [&](int id) -> float* { return h->workspace + (size_t)id * slab + crop0 * p.buf_floats_per_crop; };
@@ -1708,30 +1616,28 @@ int run_plan(fear_handle* h, Plan& p, int n, const Ext& ext, hipStream_t s_main,
                 break;
             }
             case OP_IR16: {
-                const Fused16& f = op.math == 2 ? kFused16B[op.fused_id] : op.math ? kFused16H[op.fused_id] : kFused16[op.fused_id];
+                const Fused16Row& r = *op.f16;
+                const F16K& f = r.by_math(op.math);
                 Ir2Args a{};
                 a.X = buf(op.in_buf) + op.in_off; a.ldx = op.in_ld;
                 a.Wpk = op.d_packed; a.bp = h->convs[op.conv_p].d_b;
                 a.R = op.res_buf >= 0 ? buf(op.res_buf) : nullptr; a.ldr = op.res_ld;
                 a.Y = op.out_buf >= 0 ? buf(op.out_buf) : nullptr; a.ldy = op.out_ld;
                 a.relu_dw = op.relu_dw; a.relu_out = op.relu;
-                if (op.pred_fused) {
+                if (op.pred_cout > 0) {      // a prediction head writes the caller's map: itself, or in the epilogue (pred_fused)
                     a.pred_cout = op.pred_cout; a.pred_act = op.act;
-                    a.P_Wpk = op.pred_packed; a.P_bp = h->convs[op.pred_conv_p].d_b;
-                    a.P_Y = op.out_external == 3 ? ext.cls_out : ext.bbox_out;
                     a.pred_stride = op.out_external == 3 ? ext.cls_stride : ext.bbox_stride;
-                } else if (op.pred_cout > 0) {
-                    a.pred_cout = op.pred_cout; a.pred_act = op.act;
-                    a.Y = op.out_external == 3 ? ext.cls_out : ext.bbox_out;
-                    a.pred_stride = op.out_external == 3 ? ext.cls_stride : ext.bbox_stride;
+                    float* y = op.out_external == 3 ? ext.cls_out : ext.bbox_out;
+                    if (op.pred_fused) { a.P_Wpk = op.pred_packed; a.P_bp = h->convs[op.pred_conv_p].d_b; a.P_Y = y; }
+                    else a.Y = y;
                 }
                 if (op.nsplit) {
                     const Conv& dconv = h->convs[op.conv_d];
                     a.nsplit_wstride = (long)(dconv.cout / 16) * (256 + dconv.k * dconv.k * 16 + 16);
-                    if (op.tiny) hipLaunchKernelGGL(f.kernel_tiny, dim3(n, op.nsplit, 16 / kTinyRows), dim3(64 * kTinyRows * kTinyKSplit), f.lds_tiny, s, a);
+                    if (op.tiny) hipLaunchKernelGGL(r.tiny.kernel, dim3(n, op.nsplit, 16 / kTinyRows), dim3(64 * kTinyRows * kTinyKSplit), r.tiny.lds_bytes, s, a);
                     else hipLaunchKernelGGL(f.kernel, dim3(n, op.nsplit), dim3(512), f.lds_bytes, s, a);
                 } else if (op.tiny) {
-                    hipLaunchKernelGGL(f.kernel_tiny, dim3(n, 1, 16 / kTinyRows), dim3(64 * kTinyRows * kTinyKSplit), f.lds_tiny, s, a);
+                    hipLaunchKernelGGL(r.tiny.kernel, dim3(n, 1, 16 / kTinyRows), dim3(64 * kTinyRows * kTinyKSplit), r.tiny.lds_bytes, s, a);
                 } else if (op.splitk) {
                     // several workgroups per crop, each over its own chunk range -> partial projections -> reduce
                     Ir2Args pa = a;
@@ -1740,7 +1646,7 @@ int run_plan(fear_handle* h, Plan& p, int n, const Ext& ext, hipStream_t s_main,
                     pa.Y = buf(op.part_buf); pa.ldy = op.N;
                     pa.kc_part_stride = (long)n * 256 * op.N;
                     pa.R = nullptr;
-                    hipLaunchKernelGGL(f.kernel_splitk, dim3(n, op.splitk), dim3(512), f.lds_bytes, s, pa);
+                    hipLaunchKernelGGL(r.splitk.kernel, dim3(n, op.splitk), dim3(512), r.splitk.lds_bytes, s, pa);
                     SplitKReduceArgs ra{};
                     ra.P = pa.Y; ra.bias = a.bp; ra.R = a.R; ra.Y = a.Y; ra.part_stride = pa.kc_part_stride;
                     ra.W = op.splitk; ra.M = n * 256; ra.N = op.N; ra.ldp = op.N; ra.ldr = a.ldr; ra.ldy = a.ldy; ra.relu = a.relu_out;
@@ -1758,8 +1664,7 @@ int run_plan(fear_handle* h, Plan& p, int n, const Ext& ext, hipStream_t s_main,
                 break;
             }
             case OP_IRTILE: {
-                const FusedTile& f = op.stem ? kStemTile : (op.math == 2 ? kFusedTileB[op.fused_id] : op.math ? kFusedTileH[op.fused_id] :
-                                                            fp32_tile(op.small_tiles, op.fused_id));
+                const TileK& f = *op.tk;
                 IrT2Args ta{};
                 Ir2Args& a = ta.b;
                 if (op.stem) { a.X = ext.img; a.ldx = 0; }
@@ -1770,24 +1675,20 @@ int run_plan(fear_handle* h, Plan& p, int n, const Ext& ext, hipStream_t s_main,
                 a.relu_dw = op.relu_dw; a.relu_out = op.relu;
                 ta.H = op.H; ta.W = op.W; ta.tiles_x = op.Wo / f.tw; ta.tiles_y = op.Ho / f.th;
                 if (op.splitk) {
-                    const TileKSplit* ks = find_tile_ksplit(op.fused_id);
+                    const TileK& ks = op.tile->ksplit;
                     SplitKReduceArgs ra{};
                     ra.bias = a.bp; ra.R = a.R; ra.Y = a.Y; ra.W = op.splitk; ra.M = n * op.Ho * op.Wo; ra.N = op.N; ra.ldp = op.N;
                     ra.ldr = a.ldr; ra.ldy = a.ldy; ra.relu = a.relu_out;
                     ra.part_stride = (long)ra.M * op.N;
                     a.Y = buf(op.part_buf); a.ldy = op.N; a.R = nullptr; a.kc_part_stride = ra.part_stride;
                     ra.P = a.Y;
-                    hipLaunchKernelGGL(ks->kernel, dim3((unsigned)n * ta.tiles_x * ta.tiles_y, op.splitk), dim3(512), ks->lds_bytes, s, ta);
+                    hipLaunchKernelGGL(ks.kernel, dim3((unsigned)n * ta.tiles_x * ta.tiles_y, op.splitk), dim3(512), ks.lds_bytes, s, ta);
                     const long total = (long)ra.M * (ra.N / 4);
                     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ra);
                     break;
                 }
-                if (op.io_bf16) {      // same tile, storage variant (plan: bf16 front of the trunk)
-                    const TileBf16* tb = find_tile_bf16(op.stem, op.fused_id, op.io_bf16);
-                    hipLaunchKernelGGL(tb->kernel, dim3((unsigned)n * ta.tiles_x * ta.tiles_y), dim3(64 * f.nw), f.lds_bytes, s, ta);
-                    break;
-                }
-                hipLaunchKernelGGL(f.kernel, dim3((unsigned)n * ta.tiles_x * ta.tiles_y), dim3(64 * f.nw), f.lds_bytes, s, ta);
+                const TileK& k = op.io_bf16 ? *op.tile->io_variant(op.io_bf16) : f;   // same tile, storage variant (bf16 front of the trunk)
+                hipLaunchKernelGGL(k.kernel, dim3((unsigned)n * ta.tiles_x * ta.tiles_y), dim3(64 * k.nw), k.lds_bytes, s, ta);
                 break;
             }
             case OP_E1PAIR: {
@@ -1890,7 +1791,6 @@ int run_plan(fear_handle* h, Plan& p, int n, const Ext& ext, hipStream_t s_main,
         HIP_TRY(h, hipEventRecord(h->branch_join, h->branch_stream));
         HIP_TRY(h, hipStreamWaitEvent(s_main, h->branch_join, 0));
     }
-    if (!sub) HIP_TRY(h, hipEventRecord(h->stream_switch, s_main));      // what a later call on ANOTHER stream waits for (see above)
     HIP_TRY(h, hipGetLastError());
     return FEAR_OK;
 }
@@ -1924,6 +1824,39 @@ int drop_plans(fear_handle* h) {
     for (float* p : h->plan_allocs) hipFree(p);
     h->plan_allocs.clear();
     return FEAR_OK;
+}
+
+// the options of fear_set_option / fear_get_option: the handle field each one sets, its range, and whether a change drops the
+// cached plans (an option that shapes them)
+struct OptionDesc {
+    int option;
+    int fear_handle::*field;
+    int64_t min, max;
+    bool rebuilds_plans;
+};
+const OptionDesc kOptions[] = {
+    {FEAR_OPT_MAX_BATCH, &fear_handle::max_batch, 1, 65536, false},
+    {FEAR_OPT_PROFILE, &fear_handle::profile, 0, 1, false},            // (any value: stored as 0 / 1)
+    {FEAR_OPT_PROFILE_OP, &fear_handle::profile_op, -1, 4096, false},
+    {FEAR_OPT_FUSE, &fear_handle::fuse, 0, 1, true},
+    {FEAR_OPT_MATH, &fear_handle::math, 0, 2, true},
+    {FEAR_OPT_CHAIN, &fear_handle::chain, 0, 1, true},
+    {FEAR_OPT_SMALL_PASS, &fear_handle::small_pass, 0, 65536, false},
+    {FEAR_OPT_PLAN_CROPS, &fear_handle::plan_crops, 0, 65536, false},
+    {FEAR_OPT_DUAL_HEAD, &fear_handle::dual_head, 0, 1, true},
+    {FEAR_OPT_TILE_V4, &fear_handle::tile_v4, 0, 1, true},
+    {FEAR_OPT_TINY_SEP, &fear_handle::tiny_sep, 0, 1, true},
+    {FEAR_OPT_HEAD_STAGGER, &fear_handle::head_stagger_us, 0, 1000, false},
+    {FEAR_OPT_HEAD_CHAIN, &fear_handle::head_chain, 0, 1, true},
+    {FEAR_OPT_E1_PAIR, &fear_handle::e1_pair, 0, 1, true},
+    {FEAR_OPT_CHAIN32, &fear_handle::chain32, 0, 2, true},
+    {FEAR_OPT_BF16_STORE, &fear_handle::bf16_store, 0, 1, true},
+    {FEAR_OPT_SPLIT_STREAMS, &fear_handle::split_streams, 0, 1, false},   // (same plans: only how a pass is issued changes)
+};
+const OptionDesc* find_option(int option) {
+    for (const OptionDesc& d : kOptions)
+        if (d.option == option) return &d;
+    return nullptr;
 }
 
 }  // namespace
@@ -1986,128 +1919,51 @@ int fear_destroy(fear_handle* h) {
 
 int fear_set_option(fear_handle* h, int option, int64_t value) {
     if (!h) return FEAR_ERR_NULL;
-    switch (option) {
-        case FEAR_OPT_MAX_BATCH:
-            if (value < 1 || value > 65536) return FEAR_ERR_SHAPE;
-            h->max_batch = (int)value;
-            return FEAR_OK;
-        case FEAR_OPT_PROFILE:
-            h->profile = value ? 1 : 0;
-            return FEAR_OK;
-        case FEAR_OPT_PROFILE_OP:
-            if (value < -1 || value > 4096) return FEAR_ERR_SHAPE;
-            h->profile_op = (int)value;
-            return FEAR_OK;
-        case FEAR_OPT_FUSE:
-            if (value != 0 && value != 1) return FEAR_ERR_SHAPE;
-            if (h->fuse != (int)value) { h->fuse = (int)value; return drop_plans(h); }
-            return FEAR_OK;
-        case FEAR_OPT_MATH:
-            if (value < 0 || value > 2) return FEAR_ERR_SHAPE;
-            if (h->math != (int)value) { h->math = (int)value; return drop_plans(h); }
-            return FEAR_OK;
-        case FEAR_OPT_CHAIN:
-            if (value != 0 && value != 1) return FEAR_ERR_SHAPE;
-            if (h->chain != (int)value) { h->chain = (int)value; return drop_plans(h); }
-            return FEAR_OK;
-        case FEAR_OPT_SMALL_PASS:
-            if (value < 0 || value > 65536) return FEAR_ERR_SHAPE;
-            h->small_pass = (int)value;
-            return FEAR_OK;
-        case FEAR_OPT_PLAN_CROPS:
-            if (value < 0 || value > 65536) return FEAR_ERR_SHAPE;
-            h->plan_crops = (int)value;
-            return FEAR_OK;
-        case FEAR_OPT_DUAL_HEAD:
-            if (value != 0 && value != 1) return FEAR_ERR_SHAPE;
-            if (h->dual_head != (int)value) { h->dual_head = (int)value; return drop_plans(h); }
-            return FEAR_OK;
-        case FEAR_OPT_TILE_V4:
-            if (value != 0 && value != 1) return FEAR_ERR_SHAPE;
-            if (h->tile_v4 != (int)value) { h->tile_v4 = (int)value; return drop_plans(h); }
-            return FEAR_OK;
-        case FEAR_OPT_TINY_SEP:
-            if (value != 0 && value != 1) return FEAR_ERR_SHAPE;
-            if (h->tiny_sep != (int)value) { h->tiny_sep = (int)value; return drop_plans(h); }
-            return FEAR_OK;
-        case FEAR_OPT_HEAD_STAGGER:
-            if (value < 0 || value > 1000) return FEAR_ERR_SHAPE;
-            h->head_stagger_us = (int)value;
-            return FEAR_OK;
-        case FEAR_OPT_HEAD_CHAIN:
-            if (value != 0 && value != 1) return FEAR_ERR_SHAPE;
-            if (h->head_chain != (int)value) { h->head_chain = (int)value; return drop_plans(h); }
-            return FEAR_OK;
-        case FEAR_OPT_E1_PAIR:
-            if (value != 0 && value != 1) return FEAR_ERR_SHAPE;
-            if (h->e1_pair != (int)value) { h->e1_pair = (int)value; return drop_plans(h); }
-            return FEAR_OK;
-        case FEAR_OPT_CHAIN32:
-            if (value < 0 || value > 2) return FEAR_ERR_SHAPE;
-            if (h->chain32 != (int)value) { h->chain32 = (int)value; return drop_plans(h); }
-            return FEAR_OK;
-        case FEAR_OPT_BF16_STORE:
-            if (value != 0 && value != 1) return FEAR_ERR_SHAPE;
-            if (h->bf16_store != (int)value) { h->bf16_store = (int)value; return drop_plans(h); }
-            return FEAR_OK;
-        case FEAR_OPT_SPLIT_STREAMS:
-            if (value != 0 && value != 1) return FEAR_ERR_SHAPE;
-            h->split_streams = (int)value;      // (same plans: only how a pass is issued changes)
-            return FEAR_OK;
-        default: return FEAR_ERR_SHAPE;
-    }
+    if (option == FEAR_OPT_PROFILE) value = value ? 1 : 0;
+    const OptionDesc* d = find_option(option);
+    if (!d) return FEAR_ERR_SHAPE;
+    if (value < d->min || value > d->max) return FEAR_ERR_SHAPE;
+    int& field = h->*d->field;
+    if (field == (int)value) return FEAR_OK;
+    field = (int)value;
+    return d->rebuilds_plans ? drop_plans(h) : FEAR_OK;
 }
 
 int64_t fear_get_option(fear_handle* h, int option) {
     if (!h) return FEAR_ERR_NULL;
-    switch (option) {
-        case FEAR_OPT_MAX_BATCH: return h->max_batch;
-        case FEAR_OPT_PROFILE: return h->profile;
-        case FEAR_OPT_PROFILE_OP: return h->profile_op;
-        case FEAR_OPT_FUSE: return h->fuse;
-        case FEAR_OPT_MATH: return h->math;
-        case FEAR_OPT_CHAIN: return h->chain;
-        case FEAR_OPT_SMALL_PASS: return h->small_pass;
-        case FEAR_OPT_PLAN_CROPS: return h->plan_crops;
-        case FEAR_OPT_DUAL_HEAD: return h->dual_head;
-        case FEAR_OPT_HEAD_STAGGER: return h->head_stagger_us;
-        case FEAR_OPT_TILE_V4: return h->tile_v4;
-        case FEAR_OPT_TINY_SEP: return h->tiny_sep;
-        case FEAR_OPT_HEAD_CHAIN: return h->head_chain;
-        case FEAR_OPT_E1_PAIR: return h->e1_pair;
-        case FEAR_OPT_CHAIN32: return h->chain32;
-        case FEAR_OPT_BF16_STORE: return h->bf16_store;
-        case FEAR_OPT_SPLIT_STREAMS: return h->split_streams;
-        default: return FEAR_ERR_SHAPE;
-    }
+    const OptionDesc* d = find_option(option);
+    return d ? h->*d->field : FEAR_ERR_SHAPE;
 }
 
-// the plan a pass of nb crops runs on (build_plan's mode)
+// the plan a pass of nb crops of the template branch runs on
 // ms per track call (profiles/r03_plan_sweep.txt), crops: tiny plan 1: 0.30  4: 0.34  8: 0.40  12: 0.50  16: 0.59  24: 0.78  32: 0.95
 //                                                          small plan 1: 0.53  4: 0.54  8: 0.56  12: 0.59  16: 0.61  24: 0.68  32: 0.75
 #ifndef FEAR_TINY_PASS
 #define FEAR_TINY_PASS 16
 #endif
 constexpr int kTinyPass = FEAR_TINY_PASS;
-static int small_pass(const fear_handle* h, int nb) { return h->fuse && nb <= h->small_pass ? (nb <= kTinyPass ? 2 : 1) : 0; }
+static PlanKind small_pass(const fear_handle* h, int nb) {
+    return h->fuse && nb <= h->small_pass ? (nb <= kTinyPass ? PlanKind::Tiny : PlanKind::Small) : PlanKind::Throughput;
+}
 
-// build_plan's mode for a pass of nb crops: small_pass's, or 3 for a MID-SIZE pass of the throughput plan — the chained 32 x 32 stage
+// the plan a pass of nb search crops runs on: small_pass's, or MidSize for a mid-size pass of the throughput plan — the chained 32 x 32 stage
 // is one workgroup per crop for ~250 us whatever the crop count, while the four tile launches it replaces scale with it: up to 128
 // crops the tiles win (1.507 vs 1.523 ms at 104 crops, 1.558 vs 1.572 at 128; 1.983 vs 1.940 at 143 / 144, 2.008 vs 1.964 at 160, 2.226 vs 2.167 at 256:
 // profiles/r06_chain32_midsize.txt).  Only while the automatic plan selection is on (FEAR_OPT_SMALL_PASS > 0): with 0 the caller
-// asks for THE throughput plan at every size (A/Bs, tests).
+// asks for THE throughput plan at every size (A/Bs, tests).  Where the throughput plan has no 32 x 32 chain (other FEAR_OPT_MATH,
+// fuse or chain32 settings, another block table) the two would be the same plan: a mid-size pass runs the throughput plan itself.
 #ifndef FEAR_CHAIN32_MIN_CROPS
 #define FEAR_CHAIN32_MIN_CROPS 129
 #endif
-static int plan_mode(const fear_handle* h, int nb) {
-    const int sm = small_pass(h, nb);
-    return sm == 0 && h->small_pass > 0 && h->chain32 && nb < FEAR_CHAIN32_MIN_CROPS ? 3 : sm;
+static PlanKind plan_kind(const fear_handle* h, int nb, int hw) {
+    const PlanKind k = small_pass(h, nb);
+    return k == PlanKind::Throughput && h->small_pass > 0 && nb < FEAR_CHAIN32_MIN_CROPS && plans_chain32(h, hw) ? PlanKind::MidSize : k;
 }
 
 // the plan fear_plan_* / fear_profile_read describe: that of a pass of FEAR_OPT_PLAN_CROPS crops (default: a full pass)
-static int introspected_small(const fear_handle* h, bool with_head = true) {
+static int introspected_plan(fear_handle* h, int hw, int with_head, Plan** out) {
     const int nb = h->plan_crops > 0 ? h->plan_crops : h->max_batch;
-    return with_head ? plan_mode(h, nb) : small_pass(h, nb);
+    return build_plan(h, hw, with_head != 0, with_head ? plan_kind(h, nb, hw) : small_pass(h, nb), out);
 }
 
 int fear_features(fear_handle* h, const float* img, int n, int hw, float* out, void* stream) {
@@ -2127,7 +1983,8 @@ int fear_features(fear_handle* h, const float* img, int n, int hw, float* out, v
         Ext ext{};
         ext.img = img + (size_t)b0 * 3 * hw * hw;
         ext.feat_out = out + (size_t)b0 * h->feat_channels * fhw;
-        st = run_plan(h, *p, nb, ext, static_cast<hipStream_t>(stream));
+        const hipStream_t s = static_cast<hipStream_t>(stream);
+        st = on_caller_stream(h, s, [&] { return run_plan(h, *p, nb, ext, s); });
         if (st != FEAR_OK) return st;
     }
     return FEAR_OK;
@@ -2142,21 +1999,25 @@ static int track_impl(fear_handle* h, const float* search, const float* tmpl, co
     HIP_TRY(h, hipSetDevice(h->device));
     const int hw = 256;
     const size_t tz = (size_t)h->feat_channels * 64;
+    auto ext_at = [&](size_t c0) {      // the caller's tensors from crop c0 on
+        Ext e{};
+        e.img = search + c0 * 3 * hw * hw;
+        e.tmpl = tmpl + c0 * tz;
+        e.tmpl_cls = tmpl_cls ? tmpl_cls + c0 * tz : nullptr;
+        e.bbox_out = bbox + c0 * bbox_stride;
+        e.cls_out = cls + c0 * cls_stride;
+        e.bbox_stride = bbox_stride;
+        e.cls_stride = cls_stride;
+        return e;
+    };
     for (int b0 = 0; b0 < n; b0 += h->max_batch) {
         const int nb = n - b0 < h->max_batch ? n - b0 : h->max_batch;
         Plan* p = nullptr;
-        int st = build_plan(h, hw, true, plan_mode(h, nb), &p);
+        int st = build_plan(h, hw, true, plan_kind(h, nb, hw), &p);
         if (st != FEAR_OK) return st;
         st = ensure_workspace(h, *p);
         if (st != FEAR_OK) return st;
-        Ext ext{};
-        ext.img = search + (size_t)b0 * 3 * hw * hw;
-        ext.tmpl = tmpl + (size_t)b0 * tz;
-        ext.tmpl_cls = tmpl_cls ? tmpl_cls + (size_t)b0 * tz : nullptr;
-        ext.bbox_out = bbox + (size_t)b0 * bbox_stride;
-        ext.cls_out = cls + (size_t)b0 * cls_stride;
-        ext.bbox_stride = bbox_stride;
-        ext.cls_stride = cls_stride;
+        const Ext ext = ext_at(b0);
         hipStream_t s_main = static_cast<hipStream_t>(stream);
         // FEAR_OPT_SPLIT_STREAMS: the pass as two half-batches, the second on the handle's own stream.  The crops of a batch are
         // independent and every kernel computes a crop the same way whatever its neighbours (tests: batch invariance, bit for bit),
@@ -2164,39 +2025,25 @@ static int track_impl(fear_handle* h, const float* search, const float* tmpl, co
         // the other half's ALU-bound stretches.  Only when both halves still run the throughput plan, and never while profiling
         // (per-op events assume one stream).
         const int nA = (nb + 1) / 2, nB = nb - nA;
-        if (h->split_streams && !h->profile && small_pass(h, nb) == 0 && nB > 0 && small_pass(h, nB) == 0) {
-            if (!h->split_stream) {
-                HIP_TRY(h, hipStreamCreateWithFlags(&h->split_stream, hipStreamNonBlocking));
-                HIP_TRY(h, hipEventCreateWithFlags(&h->split_fork, hipEventDisableTiming));
-                HIP_TRY(h, hipEventCreateWithFlags(&h->split_join, hipEventDisableTiming));
-            }
-            // per-call bookkeeping of run_plan, done here around both halves: a previous call on another stream is waited for
-            if (!h->stream_switch) HIP_TRY(h, hipEventCreateWithFlags(&h->stream_switch, hipEventDisableTiming));
-            if (h->last_stream_valid && h->last_stream != s_main) HIP_TRY(h, hipStreamWaitEvent(s_main, h->stream_switch, 0));
-            h->last_stream = s_main;
-            h->last_stream_valid = true;
+        const bool split = h->split_streams && !h->profile && small_pass(h, nb) == PlanKind::Throughput && nB > 0 &&
+                           small_pass(h, nB) == PlanKind::Throughput;
+        if (split && !h->split_stream) {
+            HIP_TRY(h, hipStreamCreateWithFlags(&h->split_stream, hipStreamNonBlocking));
+            HIP_TRY(h, hipEventCreateWithFlags(&h->split_fork, hipEventDisableTiming));
+            HIP_TRY(h, hipEventCreateWithFlags(&h->split_join, hipEventDisableTiming));
+        }
+        st = on_caller_stream(h, s_main, [&]() -> int {
+            if (!split) return run_plan(h, *p, nb, ext, s_main);
             HIP_TRY(h, hipEventRecord(h->split_fork, s_main));               // inputs ready, the workspace free
             HIP_TRY(h, hipStreamWaitEvent(h->split_stream, h->split_fork, 0));
-            st = run_plan(h, *p, nA, ext, s_main, 0, true);
-            int st_b = FEAR_OK;
-            if (st == FEAR_OK) {
-                Ext eb = ext;
-                eb.img = ext.img + (size_t)nA * 3 * hw * hw;
-                eb.tmpl = ext.tmpl + (size_t)nA * tz;
-                eb.tmpl_cls = ext.tmpl_cls ? ext.tmpl_cls + (size_t)nA * tz : nullptr;
-                eb.bbox_out = ext.bbox_out + (size_t)nA * bbox_stride;
-                eb.cls_out = ext.cls_out + (size_t)nA * cls_stride;
-                st_b = run_plan(h, *p, nB, eb, h->split_stream, (size_t)nA, true);
-            }
+            int st_a = run_plan(h, *p, nA, ext, s_main);
+            if (st_a == FEAR_OK) st_a = run_plan(h, *p, nB, ext_at((size_t)b0 + nA), h->split_stream, (size_t)nA);
             // join even when a half failed: whatever it did enqueue on the handle's stream still uses the shared workspace, and a
             // later call must not start before it has drained
             HIP_TRY(h, hipEventRecord(h->split_join, h->split_stream));      // the caller's stream continues once both halves are done
             HIP_TRY(h, hipStreamWaitEvent(s_main, h->split_join, 0));
-            HIP_TRY(h, hipEventRecord(h->stream_switch, s_main));
-            if (st == FEAR_OK) st = st_b;
-        } else {
-            st = run_plan(h, *p, nb, ext, s_main);
-        }
+            return st_a;
+        });
         if (st != FEAR_OK) return st;
     }
     return FEAR_OK;
@@ -2322,7 +2169,7 @@ int fear_tracker_step(fear_handle* h, const float* cls, const float* bbox, int n
 int fear_plan_size(fear_handle* h, int hw, int with_head) {
     if (!h) return FEAR_ERR_NULL;
     Plan* p = nullptr;
-    int st = build_plan(h, hw, with_head != 0, introspected_small(h, with_head != 0), &p);
+    int st = introspected_plan(h, hw, with_head, &p);
     if (st != FEAR_OK) return st;
     return (int)p->ops.size();
 }
@@ -2331,7 +2178,7 @@ int fear_plan_op(fear_handle* h, int hw, int with_head, int i, char* name64, dou
                  double* bytes_per_crop) {
     if (!h) return FEAR_ERR_NULL;
     Plan* p = nullptr;
-    int st = build_plan(h, hw, with_head != 0, introspected_small(h, with_head != 0), &p);
+    int st = introspected_plan(h, hw, with_head, &p);
     if (st != FEAR_OK) return st;
     if (i < 0 || i >= (int)p->ops.size()) return FEAR_ERR_SHAPE;
     const Op& op = p->ops[i];
@@ -2344,7 +2191,7 @@ int fear_plan_op(fear_handle* h, int hw, int with_head, int i, char* name64, dou
 int fear_profile_read(fear_handle* h, int hw, int with_head, int i, double* total_ms, int64_t* launches) {
     if (!h) return FEAR_ERR_NULL;
     Plan* p = nullptr;
-    int st = build_plan(h, hw, with_head != 0, introspected_small(h, with_head != 0), &p);
+    int st = introspected_plan(h, hw, with_head, &p);
     if (st != FEAR_OK) return st;
     if (i < 0 || i >= (int)p->ops.size()) return FEAR_ERR_SHAPE;
     st = drain_events(h);

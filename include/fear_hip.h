@@ -174,7 +174,7 @@ int fear_tracker_step(fear_handle* h, const float* cls, const float* bbox, int n
 #define FEAR_OPT_HEAD_STAGGER 10 /* with two head streams (FEAR_OPT_DUAL_HEAD, or a small pass): microseconds (0..1000, default 0) the  */
                                /*   second branch's first kernel is held back, so that the co-resident kernels of the two branches  */
                                /*   run out of phase and one's prologue / output burst overlaps the other's MFMA stretch            */
-#define FEAR_OPT_TILE_V4 11    /* 1 (default): the throughput plan runs the blocks listed in the engine's kFusedTileV4 (stage 6) on the   */
+#define FEAR_OPT_TILE_V4 11    /* 1 (default): the throughput plan runs the blocks with a v4 variant in the engine's kTiles (stage 6) on  */
                                /*   phase-overlapped tile kernel (depthwise taps of chunk c interleaved with the expansion MFMAs of      */
                                /*   chunk c + 1); 0: every tiled block on ir_tile_v2 (A/B)                                              */
 #define FEAR_OPT_TINY_SEP 12   /* 1 (default): in the plan of a handful of crops (<= 16) the head's 16-channel SepConv slices and the      */

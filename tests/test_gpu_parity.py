@@ -575,6 +575,29 @@ def test_mid_size_passes_run_the_tile_kernels_instead_of_the_32x32_chain():
     assert_maps_close(b_mid, c_mid, b_ch.cpu().numpy(), c_ch.cpu().numpy())
 
 
+def test_mid_size_pass_shares_the_throughput_plan_without_a_32x32_chain():
+    """A mid-size pass gets a plan of its own only where the throughput plan runs the 32 x 32 chain.  With FEAR_OPT_MATH = 2 it
+    has none, so a pass of 100 crops and a pass of 256 crops run the same plan and book their launches on it."""
+    from feartracker_amd import FEARNetHIP
+    from conftest import WEIGHTS
+    net = FEARNetHIP(WEIGHTS, device=0, max_batch=256)
+    net.set_math(2)
+    g = torch.Generator().manual_seed(82)
+    x = norm_u8(torch.randint(0, 256, (256, 3, 256, 256), dtype=torch.uint8, generator=g)).cuda()
+    z = net.get_features(norm_u8(torch.randint(0, 256, (256, 3, 128, 128), dtype=torch.uint8, generator=g)).cuda())
+    net.set_profile(True)
+    net.profile_reset()
+    net.track_maps(x[:100], z[:100])
+    net.track_maps(x, z)
+    net.set_plan_crops(256)
+    counts = [c for _, c in net.profile_read(256, True)]
+    net.set_profile(False)
+    assert counts and all(c == 2 for c in counts)
+    full = net.plan(256, True)
+    net.set_plan_crops(100)
+    assert net.plan(256, True) == full
+
+
 def test_head_chain_bf16_mode_against_the_bf16_sepconv_launches_and_fp32():
     """FEAR_OPT_MATH = 2 (BASELINE configs[3]): the one-launch head on v_mfma_f32_16x16x32_bf16 (headchain_b_kernel) rounds the same
     values to bf16 as the sep16 `*_h` launches it replaces — depthwise outputs, template features, weights — so the two agree far

@@ -376,7 +376,7 @@ int main(int argc, char** argv) {
     const int crops = argc > 1 ? atoi(argv[1]) : 256;
     const int iters = argc > 2 ? atoi(argv[2]) : 20;
     const bool all = argc > 3;      // any third argument: also the tile-shape sweep and the 16x16 kernels
-    // the product's tile table (fear_engine.hip kFusedTile), in plan order
+    // the product's tile kernels (fear_engine.hip kTiles, fp32 column), in plan order
 #ifdef FEAR_E1PAIR_ONLY
     bench_e1pair(crops, iters);
     return 0;
