@@ -2,10 +2,11 @@
 
 Hot path only: `FEARTracker.initialize()/update()` — and `FEARMultiTracker` for many targets per frame — on top of
 `FEARNetHIP.get_features()/track()`, whose arithmetic runs in hand-written gfx950 HIP kernels
-behind the C ABI of include/fear_hip.h.
+behind the C ABI of include/fear_hip.h.  Both trackers take packed RGB frames or NV12 / I420 video frames (`YUVFrame`).
 """
 from .constants import DEFAULT_TRACKING_CONFIG, TARGET_CLASSIFICATION_KEY, TARGET_REGRESSION_LABEL_KEY
 from .box_coder import FEARBoxCoder, TrackerDecodeResult, TrackerEncodeResult
+from .frames import YUVFrame
 from .tracker import FEARTracker, Tracker, TrackingState
 from .multi_tracker import FEARMultiTracker, PendingBoxes
 from .hip_backend import FEARNetHIP, FearError, load_library, DEFAULT_WEIGHTS, LIB_PATH
@@ -13,6 +14,6 @@ from .hip_backend import FEARNetHIP, FearError, load_library, DEFAULT_WEIGHTS, L
 __all__ = [
     "DEFAULT_TRACKING_CONFIG", "TARGET_CLASSIFICATION_KEY", "TARGET_REGRESSION_LABEL_KEY",
     "FEARBoxCoder", "TrackerDecodeResult", "TrackerEncodeResult", "FEARTracker", "Tracker", "TrackingState",
-    "FEARMultiTracker", "PendingBoxes",
+    "FEARMultiTracker", "PendingBoxes", "YUVFrame",
     "FEARNetHIP", "FearError", "load_library", "DEFAULT_WEIGHTS", "LIB_PATH",
 ]

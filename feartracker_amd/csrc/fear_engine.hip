@@ -26,6 +26,7 @@
 #include "fear_headchain_b.h"
 #include "fear_e1pair.h"
 #include "fear_chain32.h"
+#include "fear_yuv.h"
 #ifndef FEAR_E1PAIR_TPW_MAX
 #define FEAR_E1PAIR_TPW_MAX 1      // e1pair_kernel: at most this many consecutive tiles per workgroup (more measured no faster: fear_e1pair.h)
 #endif
@@ -2107,13 +2108,18 @@ int fear_normalize_u8(fear_handle* h, const uint8_t* u8, int n, int hw, float* o
 }
 
 // one launch of crop_resize_normalize_kernel: the one-frame entry and the frame-table entry differ only in where a crop's frame comes from
-static int launch_crop(fear_handle* h, CropArgs a, void* stream) {
-    HIP_TRY(h, hipSetDevice(h->device));
+// the ImageNet normalisation of the crop kernels, as (px - mean) * inv_std per channel
+static void crop_normalisation(float* mean255, float* inv_std) {
     const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     for (int c = 0; c < 3; ++c) {
-        a.mean[c] = mean[c] * 255.0f;
-        a.inv_std[c] = 1.0f / (stdv[c] * 255.0f);
+        mean255[c] = mean[c] * 255.0f;
+        inv_std[c] = 1.0f / (stdv[c] * 255.0f);
     }
+}
+
+static int launch_crop(fear_handle* h, CropArgs a, void* stream) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    crop_normalisation(a.mean, a.inv_std);
     const long total = (long)a.n * a.S * a.S;
     hipLaunchKernelGGL(crop_resize_normalize_kernel, dim3((total + 255) / 256), dim3(256), 0,
                        static_cast<hipStream_t>(stream), a);
@@ -2148,6 +2154,50 @@ int fear_crop_normalize_frames(fear_handle* h, const fear_frame* frames, int n_f
     a.ctx = ctx_xywh; a.pad = pad_rgb; a.out = out;
     a.S = out_hw; a.n = n;
     return launch_crop(h, a, stream);
+}
+
+static_assert(sizeof(fear_frame_planar) == sizeof(PlanarFrame) && offsetof(fear_frame_planar, pitch) == offsetof(PlanarFrame, pitch) &&
+              offsetof(fear_frame_planar, h) == offsetof(PlanarFrame, H) && offsetof(fear_frame_planar, w) == offsetof(PlanarFrame, W) &&
+              offsetof(fear_frame_planar, format) == offsetof(PlanarFrame, format),
+              "fear_frame_planar and PlanarFrame must share one layout");
+static_assert(FEAR_FMT_RGB == kFmtRGB && FEAR_FMT_NV12 == kFmtNV12 && FEAR_FMT_I420 == kFmtI420, "format codes");
+
+int fear_yuv_to_rgb(fear_handle* h, const fear_frame_planar* frame, uint8_t* rgb, void* stream) {
+    if (!h || !frame || !rgb) return FEAR_ERR_NULL;
+    const fear_frame_planar& f = *frame;
+    if (f.format != FEAR_FMT_NV12 && f.format != FEAR_FMT_I420) return FEAR_ERR_SHAPE;
+    if (f.h < 2 || f.w < 2 || (f.h & 1) || (f.w & 1)) return FEAR_ERR_SHAPE;
+    if (!f.plane[0] || !f.plane[1] || (f.format == FEAR_FMT_I420 && !f.plane[2])) return FEAR_ERR_NULL;
+    const int chroma_row = f.format == FEAR_FMT_NV12 ? f.w : f.w / 2;
+    if (f.pitch[0] < f.w || f.pitch[1] < chroma_row || (f.format == FEAR_FMT_I420 && f.pitch[2] < chroma_row)) return FEAR_ERR_SHAPE;
+    HIP_TRY(h, hipSetDevice(h->device));
+    YuvToRgbArgs a{};
+    std::memcpy(&a.f, &f, sizeof(PlanarFrame));
+    a.rgb = rgb;
+    const long blocks = (long)(f.h / 2) * (f.w / 2);
+    hipLaunchKernelGGL(yuv_to_rgb_kernel, dim3((blocks + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    HIP_TRY(h, hipGetLastError());
+    return FEAR_OK;
+}
+
+int fear_crop_normalize_planar(fear_handle* h, const fear_frame_planar* frames, int n_frames, const int32_t* frame_idx,
+                               const int32_t* ctx_xywh, const uint8_t* pad_rgb, int n, int out_hw, float* out, void* stream) {
+    if (!h) return FEAR_ERR_NULL;
+    if (n < 0 || n_frames < 1 || out_hw < 1 || out_hw > 4096) return FEAR_ERR_SHAPE;
+    if (n == 0) return FEAR_OK;
+    if (!frames || !frame_idx || !ctx_xywh || !pad_rgb || !out) return FEAR_ERR_NULL;
+    HIP_TRY(h, hipSetDevice(h->device));
+    PlanarCropArgs a{};
+    a.frames = reinterpret_cast<const PlanarFrame*>(frames);
+    a.frame_idx = frame_idx; a.n_frames = n_frames;
+    a.ctx = ctx_xywh; a.pad = pad_rgb; a.out = out;
+    a.S = out_hw; a.n = n;
+    crop_normalisation(a.mean, a.inv_std);
+    const long total = (long)n * out_hw * out_hw;
+    hipLaunchKernelGGL(crop_resize_normalize_planar_kernel, dim3((total + 255) / 256), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), a);
+    HIP_TRY(h, hipGetLastError());
+    return FEAR_OK;
 }
 
 int fear_tracker_step(fear_handle* h, const float* cls, const float* bbox, int n, const int32_t* frame_hw, int32_t* box_xywh,

@@ -21,6 +21,7 @@ import numpy as np
 import torch  # must be imported before the library so that both share one libamdhip64
 
 from .constants import TARGET_CLASSIFICATION_KEY, TARGET_REGRESSION_LABEL_KEY
+from .frames import FMT_NV12, FMT_RGB, YUVFrame
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FEAR_LIB", os.path.join(_PKG, "libfear_hip.so"))   # FEAR_LIB: development builds (tools/)
@@ -81,6 +82,10 @@ def load_library() -> ctypes.CDLL:
     lib.fear_crop_normalize.restype = i32
     lib.fear_crop_normalize_frames.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, f32p, vp]
     lib.fear_crop_normalize_frames.restype = i32
+    lib.fear_yuv_to_rgb.argtypes = [vp, vp, vp, vp]
+    lib.fear_yuv_to_rgb.restype = i32
+    lib.fear_crop_normalize_planar.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, f32p, vp]
+    lib.fear_crop_normalize_planar.restype = i32
     lib.fear_tracker_step.argtypes = [vp, f32p, f32p, i32, vp, vp, vp, vp, i32, vp, f64, f64, f64, i32, i32, i32, f64, vp, f32p,
                                       vp]
     lib.fear_tracker_step.restype = i32
@@ -110,10 +115,34 @@ def load_library() -> ctypes.CDLL:
 
 EXPORTED_SYMBOLS = (
     "fear_create", "fear_destroy", "fear_features", "fear_track", "fear_track_packed", "fear_decode", "fear_decode_smooth", "fear_normalize_u8",
-    "fear_crop_normalize", "fear_crop_normalize_frames", "fear_tracker_step",
+    "fear_crop_normalize", "fear_crop_normalize_frames", "fear_tracker_step", "fear_yuv_to_rgb", "fear_crop_normalize_planar",
     "fear_set_option", "fear_get_option", "fear_plan_size", "fear_plan_op", "fear_profile_read",
     "fear_profile_reset", "fear_workspace_bytes", "fear_strerror", "fear_last_hip_error", "fear_version",
 )
+
+
+# fear_frame_planar (include/fear_hip.h): 48 bytes, no padding
+PLANAR_FRAME_DTYPE = np.dtype([("plane", "<u8", (3,)), ("pitch", "<i4", (3,)), ("h", "<i4"), ("w", "<i4"), ("format", "<i4")])
+assert PLANAR_FRAME_DTYPE.itemsize == 48
+
+
+def _fill_planar_entry(entry, frame, device: torch.device) -> None:
+    """One fear_frame_planar for a device frame: a YUVFrame, or a uint8 (H, W, 3) RGB tensor whose rows may be pitched."""
+    if isinstance(frame, YUVFrame):
+        if not frame.is_cuda or frame.device != device:
+            raise ValueError("YUVFrame planes must be tensors on the engine's device (YUVFrame.to(device) uploads host planes)")
+        ptrs = [p.data_ptr() for p in frame.planes]
+        entry["plane"] = ptrs + [0] * (3 - len(ptrs))
+        entry["pitch"] = frame.pitches()
+        entry["h"], entry["w"], entry["format"] = frame.height, frame.width, frame.format
+        return
+    f = frame
+    if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or f.device != device or \
+            f.stride(2) != 1 or f.stride(1) != 3 or f.stride(0) < 3 * f.shape[1]:
+        raise ValueError("RGB frames must be uint8 (H,W,3) tensors on the engine's device with contiguous rows")
+    entry["plane"] = [f.data_ptr(), 0, 0]
+    entry["pitch"] = [f.stride(0), 0, 0]
+    entry["h"], entry["w"], entry["format"] = f.shape[0], f.shape[1], FMT_RGB
 
 
 class FearError(RuntimeError):
@@ -512,6 +541,115 @@ class FEARNetHIP:
             self._check(self._lib.fear_crop_normalize_frames(self._h, table.data_ptr(), int(table.shape[0]), frame_idx.data_ptr(),
                                                              ctx_xywh.data_ptr(), pad_rgb_u8.data_ptr(), n, int(out_hw),
                                                              out.data_ptr(), self._stream()))
+        return out
+
+    # ------------------------------------------------------------------ YUV frames (feartracker_amd/frames.py)
+    @torch.no_grad()
+    def yuv_to_rgb(self, frame: YUVFrame, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fear_yuv_to_rgb: an NV12 / I420 `YUVFrame` -> (H, W, 3) uint8 RGB on the device (host planes are uploaded first)."""
+        if not isinstance(frame, YUVFrame):
+            raise TypeError("frame must be a YUVFrame")
+        if not frame.is_cuda or frame.device != self.device:
+            frame = frame.to(self.device)
+        if out is None:
+            out = torch.empty(frame.shape, dtype=torch.uint8, device=self.device)
+        elif tuple(out.shape) != frame.shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous uint8 (H,W,3) tensor on the engine's device")
+        desc = np.zeros(1, dtype=PLANAR_FRAME_DTYPE)
+        _fill_planar_entry(desc[0], frame, self.device)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.fear_yuv_to_rgb(self._h, desc.ctypes.data, out.data_ptr(), self._stream()))
+        return out
+
+    def frame_table_planar(self, frames) -> torch.Tensor:
+        """The (n_frames) `fear_frame_planar` table of include/fear_hip.h, uploaded: 48 bytes per frame, for device frames of any
+        format — `YUVFrame`s and uint8 (H,W,3) RGB tensors (rows may be pitched).  The frames must stay alive until the launches
+        that read the table have run.  Like `frame_table` it goes up from pinned memory without waiting for the stream."""
+        host = torch.empty(len(frames) * PLANAR_FRAME_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
+        tab = host.numpy().view(PLANAR_FRAME_DTYPE)
+        for i, f in enumerate(frames):
+            _fill_planar_entry(tab[i], f, self.device)
+        return host.to(self.device, non_blocking=True)
+
+    @torch.no_grad()
+    def crop_normalize_planar(self, table: torch.Tensor, frame_idx: torch.Tensor, ctx_xywh: torch.Tensor, pad_rgb_u8: torch.Tensor,
+                              out_hw: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fear_crop_normalize_planar: `crop_normalize_frames` over a `frame_table_planar` table (RGB, NV12 and I420 frames mixed);
+        every argument a device tensor — frame_idx (n,) int32, ctx_xywh (n,4) int32, pad_rgb_u8 (n,3) uint8 -> (n,3,out_hw,out_hw)."""
+        n = int(frame_idx.shape[0])
+        for t, dt, shape in ((frame_idx, torch.int32, (n,)), (ctx_xywh, torch.int32, (n, 4)), (pad_rgb_u8, torch.uint8, (n, 3))):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"expected a contiguous {dt} {shape} tensor on the engine's device")
+        n_frames = table.numel() // PLANAR_FRAME_DTYPE.itemsize
+        if table.dtype != torch.uint8 or table.numel() != n_frames * PLANAR_FRAME_DTYPE.itemsize or n_frames < 1:
+            raise ValueError("table must be the uint8 tensor frame_table_planar returns")
+        if out is None:
+            out = torch.empty((n, 3, out_hw, out_hw), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.fear_crop_normalize_planar(self._h, table.data_ptr(), n_frames, frame_idx.data_ptr(),
+                                                             ctx_xywh.data_ptr(), pad_rgb_u8.data_ptr(), n, int(out_hw),
+                                                             out.data_ptr(), self._stream()))
+        return out
+
+    @torch.no_grad()
+    def crop_normalize_yuv(self, frame: YUVFrame, ctx_xywh, pad_rgb_u8, out_hw: int) -> torch.Tensor:
+        """`crop_normalize` for a `YUVFrame`: the crops of its RGB conversion, bit for bit, cut from the planes by
+        fear_crop_normalize_planar.  Of a HOST frame only the rectangle the context boxes can sample goes up (`context_rectangle`,
+        widened to even coordinates so that every pixel keeps its chroma sample), its planes and the small tables in ONE
+        transfer; device planes are read in place."""
+        if not isinstance(frame, YUVFrame):
+            raise TypeError("frame must be a YUVFrame")
+        ctx_np = np.ascontiguousarray(np.asarray(ctx_xywh, dtype=np.int32).reshape(-1, 4))
+        pad_np = np.ascontiguousarray(np.asarray(pad_rgb_u8, dtype=np.uint8).reshape(-1, 3))
+        n = ctx_np.shape[0]
+        if pad_np.shape[0] != n:
+            raise ValueError("one border colour per context box")
+        tab_b = PLANAR_FRAME_DTYPE.itemsize
+        meta_bytes = (tab_b + n * 4 + n * 16 + n * 3 + 15) // 16 * 16     # [table | n x frame index 0 | n x 4 int32 | n x 3 uint8]
+        planes = []
+        if frame.is_cuda:
+            if frame.device != self.device:
+                frame = frame.to(self.device)
+            total = meta_bytes
+        else:
+            fh, fw = frame.height, frame.width
+            x0, y0, x1, y1 = context_rectangle(fh, fw, ctx_np)
+            x0, y0, x1, y1 = x0 & ~1, y0 & ~1, x1 + (x1 & 1), y1 + (y1 & 1)     # even: the rectangle keeps the chroma siting
+            if (x0, y0) != (0, 0):
+                ctx_np = ctx_np.copy()
+                ctx_np[:, 0] -= x0
+                ctx_np[:, 1] -= y0
+            rh, rw = y1 - y0, x1 - x0
+            src = frame.planes
+            if frame.format == FMT_NV12:
+                planes = [src[0][y0:y1, x0:x1], np.asarray(src[1]).reshape(fh // 2, fw)[y0 // 2:y1 // 2, x0:x1]]
+            else:
+                planes = [src[0][y0:y1, x0:x1], src[1][y0 // 2:y1 // 2, x0 // 2:x1 // 2],
+                          src[2][y0 // 2:y1 // 2, x0 // 2:x1 // 2]]
+            total = meta_bytes + sum(p.size for p in planes)
+        dev = torch.empty(total, dtype=torch.uint8, device=self.device)
+        base = dev.data_ptr()
+        host = np.zeros(total, dtype=np.uint8)
+        entry = host[:tab_b].view(PLANAR_FRAME_DTYPE)[0]
+        if frame.is_cuda:
+            _fill_planar_entry(entry, frame, self.device)
+        else:
+            off, ptrs = meta_bytes, []
+            for p in planes:
+                ptrs.append(base + off)
+                host[off: off + p.size].reshape(p.shape)[...] = p
+                off += p.size
+            entry["plane"] = ptrs + [0] * (3 - len(ptrs))
+            entry["pitch"] = [p.shape[1] for p in planes] + [0] * (3 - len(planes))
+            entry["h"], entry["w"], entry["format"] = rh, rw, frame.format
+        host[tab_b + n * 4: tab_b + n * 20] = ctx_np.view(np.uint8).reshape(-1)      # the frame indices stay 0
+        host[tab_b + n * 20: tab_b + n * 23] = pad_np.reshape(-1)
+        dev.copy_(torch.from_numpy(host))
+        out = torch.empty((n, 3, out_hw, out_hw), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.fear_crop_normalize_planar(self._h, base, 1, base + tab_b, base + tab_b + n * 4,
+                                                             base + tab_b + n * 20, n, int(out_hw), out.data_ptr(),
+                                                             self._stream()))
         return out
 
     @torch.no_grad()

@@ -23,6 +23,13 @@ With a model that lacks the device entry points (a CPU reference network, any to
 the device path reads what `fear_crop_normalize` reads — uint8 H x W x >= 3 frames, numpy arrays or device tensors — and
 rejects other frames (float, uint16, grey, CPU tensors) with a TypeError instead of switching paths behind the caller's
 back, where FEARTracker would track them on the host.  A tracker built with `device_crop=False` takes them.
+
+NV12 / I420 video frames (`YUVFrame`, host planes or device planes) are taken by both paths.  On the device path host planes go up
+on the copy stream (half the bytes of the RGB frame).  A submit whose frames are all RGB runs `frame_table` +
+`fear_crop_normalize_frames` as above.  A submit with any `YUVFrame` and fewer than `PLANAR_CROP_MAX_TARGETS` targets runs one
+`fear_crop_normalize_planar` launch over a `frame_table_planar` table, which reads the planes directly; with more targets each
+YUV frame is converted once (`fear_yuv_to_rgb`) and the RGB launch runs, which measured faster there.
+Both give the same crops bit for bit.  The host path tracks the frames' RGB conversion.
 """
 from __future__ import annotations
 
@@ -32,8 +39,14 @@ import numpy as np
 import torch
 
 from .constants import TARGET_CLASSIFICATION_KEY, TARGET_REGRESSION_LABEL_KEY
+from .frames import YUVFrame, host_rgb, mean_color
 from .geometry import border_color_u8, clamp_bbox, crop_geometry, get_extended_crop
 from .tracker import FEARTracker
+
+# A submit with YUV frames and fewer targets than this crops from the planes (fear_crop_normalize_planar); from here on, one
+# fear_yuv_to_rgb per frame + the RGB crop launch is faster (1080p, MI355X: planar 15 us against 24 us at K = 16, 178 against
+# 156 us at K = 256; profiles/multi_track_yuv_bench.json)
+PLANAR_CROP_MAX_TARGETS = 32
 
 
 class PendingBoxes:
@@ -86,6 +99,8 @@ class FEARMultiTracker:
         self._next_id = 0
         self._ids: List[int] = []
         self._stream = np.zeros(0, dtype=np.int32)          # the stream of each target, host copy
+        self._planar = self.device_path and all(hasattr(model, a) for a in ("frame_table_planar", "crop_normalize_planar",
+                                                                             "crop_normalize_yuv"))
         if self.device_path:
             dev = self.device
             self._window = self._proto.window.to(dev, torch.float64).reshape(-1).contiguous()
@@ -110,7 +125,10 @@ class FEARMultiTracker:
         return len(self._ids)
 
     def _readable(self, image) -> bool:
-        """The frames fear_crop_normalize reads (FEARTracker._device_crop): uint8 H x W x >= 3, numpy or a device tensor."""
+        """The frames fear_crop_normalize reads (FEARTracker._device_crop): uint8 H x W x >= 3, numpy or a device tensor; and
+        `YUVFrame`s when the model has the planar entry points."""
+        if isinstance(image, YUVFrame):
+            return self._planar
         if isinstance(image, np.ndarray):
             return image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] >= 3
         return isinstance(image, torch.Tensor) and image.is_cuda and image.dtype == torch.uint8 and image.dim() == 3 and \
@@ -118,12 +136,13 @@ class FEARMultiTracker:
 
     def _check_frame(self, image) -> None:
         if self.device_path and not self._readable(image):
-            raise TypeError("the device path reads uint8 (H, W, >=3) frames (numpy arrays or device tensors); construct the tracker "
-                            "with device_crop=False for other frames")
+            raise TypeError("the device path reads uint8 (H, W, >=3) frames (numpy arrays or device tensors) and YUVFrames; "
+                            "construct the tracker with device_crop=False for other frames")
 
-    @staticmethod
-    def _mean_color(image) -> np.ndarray:
+    def _mean_color(self, image) -> np.ndarray:
         """np.mean(image, axis=(0, 1)) — for a device frame the same float64 number: the integer channel sums are exact."""
+        if isinstance(image, YUVFrame):
+            return mean_color(image, self.net)
         if isinstance(image, torch.Tensor):
             sums = image.to(torch.int64).sum(dim=(0, 1)).cpu().numpy()
             return sums.astype(np.float64) / float(image.shape[0] * image.shape[1])
@@ -137,9 +156,14 @@ class FEARMultiTracker:
         np.copyto(pinned.numpy(), arr)
         return pinned.to(self.device, non_blocking=True)
 
-    def _upload(self, image) -> torch.Tensor:
+    def _upload(self, image):
         """A frame as the contiguous device uint8 (H, W, 3) tensor the crop kernel reads: host frames go up whole, in one
-        non-blocking transfer; device frames are used in place."""
+        non-blocking transfer; device frames are used in place.  A host `YUVFrame` goes up as its planes (one transfer each),
+        a device one is used in place."""
+        if isinstance(image, YUVFrame):
+            if image.is_cuda:
+                return image if image.device == self.device else image.to(self.device)
+            return YUVFrame(image.format, tuple(self._to_device(p) for p in image.planes), image.height, image.width)
         if isinstance(image, torch.Tensor):
             return image[:, :, :3].to(self.device).contiguous()
         return self._to_device(image[:, :, :3])
@@ -149,7 +173,8 @@ class FEARMultiTracker:
         frame t + 1 runs while frame t's kernels do (on the caller's stream it would wait for them); the caller's stream waits
         for the copies through an event.  Device frames stay on the caller's stream, where they may have been produced."""
         main = torch.cuda.current_stream(self.device)
-        out: List[Optional[torch.Tensor]] = [f if isinstance(f, torch.Tensor) else None for f in frames]
+        on_device = [isinstance(f, torch.Tensor) or (isinstance(f, YUVFrame) and f.is_cuda) for f in frames]
+        out: list = [f if d else None for f, d in zip(frames, on_device)]
         if any(f is None for f in out):
             if self._copy_stream is None:
                 self._copy_stream = torch.cuda.Stream(self.device)
@@ -161,9 +186,10 @@ class FEARMultiTracker:
             done.record(self._copy_stream)
             main.wait_event(done)
             for i, f in enumerate(frames):
-                if not isinstance(f, torch.Tensor):
-                    out[i].record_stream(main)          # allocated on the copy stream, read on the caller's
-        return [self._upload(f) if isinstance(f, torch.Tensor) else d for f, d in zip(frames, out)]
+                if not on_device[i]:                    # allocated on the copy stream, read on the caller's
+                    for t in (out[i].planes if isinstance(out[i], YUVFrame) else (out[i],)):
+                        t.record_stream(main)
+        return [self._upload(f) if d else u for f, d, u in zip(frames, on_device, out)]
 
     # ------------------------------------------------------------------ targets
     def add(self, image, rects, stream: int = 0) -> List[int]:
@@ -173,6 +199,8 @@ class FEARMultiTracker:
         wait for the stream (the template crop's upload, the mean colour of a device frame)."""
         cfg = self.tracking_config
         self._check_frame(image)
+        if isinstance(image, YUVFrame) and not self.device_path:
+            image = host_rgb(image, self.net)
         rects = np.asarray(rects).reshape(-1, 4)
         n = rects.shape[0]
         if n == 0:
@@ -187,7 +215,11 @@ class FEARMultiTracker:
             dev = self.device
             tctx = np.stack([crop_geometry(shape, b, cfg["template_size"], cfg["template_bbox_offset"])[0] for b in boxes])
             pad = np.tile(border_color_u8(mean), (n, 1))
-            z = self.net.get_features(self.net.crop_normalize(image[:, :, :3], tctx, pad, cfg["template_size"]))
+            if isinstance(image, YUVFrame):
+                crop = self.net.crop_normalize_yuv(image, tctx, pad, cfg["template_size"])
+            else:
+                crop = self.net.crop_normalize(image[:, :, :3], tctx, pad, cfg["template_size"])
+            z = self.net.get_features(crop)
             geo = [crop_geometry(shape, b, cfg["instance_size"], cfg["search_context"]) for b in boxes]
             ctx = np.stack([g[0] for g in geo]).astype(np.int32)
             prev = np.stack([np.asarray(g[1][2:], dtype=np.float64) for g in geo])
@@ -256,12 +288,17 @@ class FEARMultiTracker:
             return self._submit_host(frames)
         cfg, net, k = self.tracking_config, self.net, len(self._ids)
         dev = self._upload_frames(frames)
-        table = net.frame_table(dev)
+        planar = any(isinstance(f, YUVFrame) for f in dev)          # all-RGB submits keep the RGB table and kernel
+        if planar and k >= PLANAR_CROP_MAX_TARGETS:
+            dev = [net.yuv_to_rgb(f) if isinstance(f, YUVFrame) else f for f in dev]
+            planar = False
+        table = net.frame_table_planar(dev) if planar else net.frame_table(dev)
         key = tuple(tuple(f.shape[:2]) for f in dev)
         if self._frame_hw is None or self._frame_hw[0] != key:
             hw = np.array([key[s] for s in self._stream], dtype=np.int32).reshape(k, 2)
             self._frame_hw = (key, self._to_device(hw))
-        search = net.crop_normalize_frames(table, self._fidx, self._ctx, self._pad, cfg["instance_size"])
+        crop = net.crop_normalize_planar if planar else net.crop_normalize_frames
+        search = crop(table, self._fidx, self._ctx, self._pad, cfg["instance_size"])
         bbox, cls = net.track_maps(search, self._tmpl)
         boxes = self._out[: 16 * k].view(torch.int32).view(k, 4)
         scores = self._out[16 * k:].view(torch.float32)
@@ -277,6 +314,7 @@ class FEARMultiTracker:
     def _submit_host(self, frames) -> PendingBoxes:
         """The reference-style path: FEARTracker.update's host branch per target around one batched net.track."""
         cfg = self.tracking_config
+        frames = [host_rgb(f, self.net) if isinstance(f, YUVFrame) else f for f in frames]
         crops = []
         for slot, s in zip(self._slots, self._stream):
             st = slot.tracking_state

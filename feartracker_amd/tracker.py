@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from .box_coder import FEARBoxCoder, TrackerDecodeResult
+from .frames import YUVFrame, host_rgb, mean_color
 from .constants import TARGET_CLASSIFICATION_KEY, TARGET_REGRESSION_LABEL_KEY
 from .geometry import border_color_u8, clamp_bbox, crop_geometry, get_extended_crop, normalize_image
 
@@ -191,13 +192,26 @@ class FEARTracker(Tracker):
         return FEARBoxCoder(tracker_config=tracking_config)
 
     def initialize(self, image: np.ndarray, rect: np.ndarray, **kwargs) -> None:
-        """image: HxWx3 uint8 RGB; rect: [x, y, w, h], 0-based."""
+        """image: HxWx3 uint8 RGB, or an NV12 / I420 `YUVFrame`; rect: [x, y, w, h], 0-based."""
+        image = self._host_frame(image)
         rect = clamp_bbox(rect, image.shape)
         st = self.tracking_state
         st.bbox = rect
         st.paths = deque([rect], maxlen=10)
-        st.mean_color = np.mean(image, axis=(0, 1))
+        st.mean_color = mean_color(image, self.net) if isinstance(image, YUVFrame) else np.mean(image, axis=(0, 1))
         self._template_features = self.get_template_features(image, rect)
+
+    def _host_frame(self, image):
+        """A `YUVFrame` the device crop cannot take (`device_crop=False`, a model without `crop_normalize_yuv`) becomes its RGB
+        conversion on the host, and the frame then takes the host path as any RGB frame does; everything else is returned as is."""
+        if isinstance(image, YUVFrame) and not self._device_crop(image):
+            return host_rgb(image, self.net)
+        return image
+
+    def _crop_on_device(self, image, ctx, pad, size: int) -> torch.Tensor:
+        if isinstance(image, YUVFrame):
+            return self.net.crop_normalize_yuv(image, ctx, pad, size)
+        return self.net.crop_normalize(image[:, :, :3], ctx, pad, size)
 
     def _device_crop(self, image: np.ndarray) -> bool:
         """Crop + border + resize + normalise on the GPU (`fear_crop_normalize`) whenever the model offers
@@ -206,15 +220,20 @@ class FEARTracker(Tracker):
         (bench.py `latency_batch1`).  Any other frame (float, uint16, grey) takes the reference-style host path, as does
         `device_crop=False` in the tracking config (not a key of the reference config; the reference always crops on the
         host with cv2, utils.py:215-253)."""
-        return bool(self.tracking_config.get("device_crop", True)) and hasattr(self.net, "crop_normalize") and \
+        if not self.tracking_config.get("device_crop", True):
+            return False
+        if isinstance(image, YUVFrame):          # cut from the planes by fear_crop_normalize_planar (DESIGN.md section 10)
+            return hasattr(self.net, "crop_normalize_yuv")
+        return hasattr(self.net, "crop_normalize") and \
             isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] >= 3
 
     def get_template_features(self, image: np.ndarray, rect: np.ndarray):
         cfg = self.tracking_config
+        image = self._host_frame(image)
         if self._device_crop(image):
             ctx, _ = crop_geometry(image.shape, rect, cfg["template_size"], cfg["template_bbox_offset"])
-            pad = border_color_u8(np.mean(image, axis=(0, 1)))
-            x = self.net.crop_normalize(image[:, :, :3], ctx, pad, cfg["template_size"])
+            mean = mean_color(image, self.net) if isinstance(image, YUVFrame) else np.mean(image, axis=(0, 1))
+            x = self._crop_on_device(image, ctx, border_color_u8(mean), cfg["template_size"])
             return self.net.get_features(x)
         crop, _, _ = get_extended_crop(image=image, bbox=rect, offset=cfg["template_bbox_offset"],
                                        crop_size=cfg["template_size"])
@@ -222,11 +241,12 @@ class FEARTracker(Tracker):
 
     def update(self, image: np.ndarray, *kw) -> Dict[str, Any]:
         cfg, st = self.tracking_config, self.tracking_state
+        image = self._host_frame(image)
         if self._device_crop(image):
             context, box_in_crop = crop_geometry(image.shape, st.bbox, cfg["instance_size"], cfg["search_context"])
             st.mapping = context
             st.prev_size = box_in_crop[2:]
-            search = self.net.crop_normalize(image[:, :, :3], context, border_color_u8(st.mean_color), cfg["instance_size"])
+            search = self._crop_on_device(image, context, border_color_u8(st.mean_color), cfg["instance_size"])
             pred, _ = self._postprocess(track_result=self.net.track(search, self._template_features))
             pred = clamp_bbox(self._rescale_bbox(pred, st.mapping), image.shape)
             st.bbox = pred

@@ -118,6 +118,43 @@ typedef struct fear_frame {
 int fear_crop_normalize_frames(fear_handle* h, const fear_frame* frames, int n_frames, const int32_t* frame_idx,
                                const int32_t* ctx_xywh, const uint8_t* pad_rgb, int n, int out_hw, float* out, void* stream);
 
+/* ---- video frames: 4:2:0 YUV planes as decoders deliver them ------------------------------------------------------------
+ * Colour conversion is OpenCV 4.x's cvtColor(COLOR_YUV2RGB_NV12 / COLOR_YUV2RGB_I420): BT.601 limited range in 20-bit integer
+ * arithmetic, nearest chroma (pixel (x, y) takes chroma sample (x / 2, y / 2)); DESIGN.md section 10 states it.            */
+#define FEAR_FMT_RGB 0     /* plane[0] = (h, w, 3) uint8 RGB rows, pitch[0] >= 3 w                                              */
+#define FEAR_FMT_NV12 1    /* plane[0] = Y (h, w), plane[1] = interleaved UV (h / 2, w / 2 pairs); pitch[0], pitch[1] >= w         */
+#define FEAR_FMT_I420 2    /* plane[0] = Y (h, w), plane[1] = U, plane[2] = V (h / 2, w / 2); pitch[0] >= w, pitch[1], pitch[2] >= w / 2 */
+
+/* One frame of a planar crop launch or conversion: device plane pointers with a byte pitch each (a decoder's pitched surface is
+ * read in place), the frame size in pixels and a FEAR_FMT_* code.  h and w are even for NV12 / I420.  48 bytes, no padding. */
+typedef struct fear_frame_planar {
+    const uint8_t* plane[3];
+    int32_t pitch[3];
+    int32_t h;
+    int32_t w;
+    int32_t format;
+} fear_frame_planar;
+#ifdef __cplusplus
+static_assert(sizeof(fear_frame_planar) == 48, "fear_frame_planar is 48 bytes");
+#else
+_Static_assert(sizeof(fear_frame_planar) == 48, "fear_frame_planar is 48 bytes");
+#endif
+
+/* Full-frame NV12 / I420 -> contiguous (h, w, 3) uint8 RGB, the conversion above.
+ *   frame : HOST pointer to the descriptor (its planes on the device)     rgb : (h, w, 3) uint8, device
+ * FEAR_ERR_SHAPE for another format, odd or < 2 h / w, or a pitch shorter than a plane row; FEAR_ERR_NULL for a missing plane. */
+int fear_yuv_to_rgb(fear_handle* h, const fear_frame_planar* frame, uint8_t* rgb, void* stream);
+
+/* fear_crop_normalize_frames over a table of frames of any FEAR_FMT_* format, mixed formats in one launch allowed: crop i is cut
+ * out of frames[frame_idx[i]].  Each bilinear tap is converted to its RGB bytes once (border taps take pad_rgb), then the RGB
+ * kernel's resize and normalisation run unchanged, so every crop equals fear_crop_normalize_frames on the fear_yuv_to_rgb output
+ * bit for bit.  A frame index outside [0, n_frames), and a table entry with an unknown format, a null plane, odd h / w (NV12 /
+ * I420) or a pitch shorter than a plane row, read no pixel: the crop is all border colour.
+ *   frames    : (n_frames) fear_frame_planar, device     frame_idx : (n) int32, device
+ *   ctx_xywh, pad_rgb, out : as fear_crop_normalize                                                                     */
+int fear_crop_normalize_planar(fear_handle* h, const fear_frame_planar* frames, int n_frames, const int32_t* frame_idx,
+                               const int32_t* ctx_xywh, const uint8_t* pad_rgb, int n, int out_hw, float* out, void* stream);
+
 /* FEARTracker.update after net.track for n targets at once, on device state (feartracker_amd/multi_tracker.py): the decode of
  * fear_decode (smooth = 0) or fear_decode_smooth (smooth = 1) on the maps of one fear_track call, then Tracker._rescale_bbox
  * (base_tracker.py:83-90: float64 scales, round half to even, minimum side 3), clamp_bbox to the target's frame

@@ -9,6 +9,14 @@ For each K it reports ms per frame and target-updates/s of
   track_only  fear_track of the same K search crops and templates, back to back: the floor the tracker is measured against
 Usage: python tools/multi_track_bench.py [--ks 1,16,64,256,1024] [--frames 40] [--out profiles/....json] [--no-singles]
        [--submit-only]
+
+Video frames: `--format rgb,nv12,i420` times the pipelined submit loop on the same frames as packed RGB,
+NV12 and I420 (`YUVFrame`; the YUV frames are the RGB frames through tests/yuvgen.rgb_to_yuv420), host frames, and with
+`--device-frames` device frames as well; on device YUV frames also what a caller without the planar crop does: fear_yuv_to_rgb
+per frame, then the RGB path.  It then times the crop launches alone at each K with device events: fear_crop_normalize_frames on
+the RGB frame, fear_crop_normalize_planar on the NV12 and I420 frames, fear_yuv_to_rgb of one frame.  Default output
+profiles/multi_track_yuv_bench.json (with --out: that file).
+       python tools/multi_track_bench.py --format rgb,nv12,i420 --device-frames [--ks 1,16,64,256] [--frames 40]
 """
 import argparse
 import json
@@ -24,7 +32,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from clipgen import demo_clip  # noqa: E402
-from feartracker_amd import DEFAULT_TRACKING_CONFIG, DEFAULT_WEIGHTS, FEARMultiTracker, FEARNetHIP, FEARTracker  # noqa: E402
+from feartracker_amd import DEFAULT_TRACKING_CONFIG, DEFAULT_WEIGHTS, FEARMultiTracker, FEARNetHIP, FEARTracker, YUVFrame  # noqa: E402
+from yuvgen import rgb_to_yuv420  # noqa: E402
 
 
 def hd_frames(n):
@@ -55,6 +64,91 @@ def timed(fn, n, sync):
     return 1e3 * (time.perf_counter() - t0) / n
 
 
+def event_ms(fn, n):
+    """Device time per call of `fn` over n back-to-back calls, between two events."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fn()
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / n
+
+
+def yuv_frames(planes, fmt):
+    return [YUVFrame.nv12(y, np.stack([u, v], -1).reshape(u.shape[0], -1)) if fmt == "nv12" else YUVFrame.i420(y, u, v)
+            for y, u, v in planes]
+
+
+def pipelined_ms(net, cfg, first, frames, boxes, n, prep=None):
+    """ms per frame of the pipelined submit loop over frames[4:4 + n] (frames[1:4] warm up)."""
+    prep = prep or (lambda f: f)
+    mt = FEARMultiTracker(net, cuda_id=0, **cfg)
+    mt.add(first, boxes)
+    for f in frames[1:4]:
+        mt.update(prep(f))
+    state = {"p": None}
+
+    def step(i):
+        nxt = mt.submit(prep(frames[4 + i]))
+        if state["p"] is not None:
+            state["p"].result()
+        state["p"] = nxt
+
+    ms = timed(step, n, torch.cuda.synchronize)
+    state["p"].result()
+    return ms
+
+
+def yuv_main(args):
+    """--format: pipelined submit on RGB / NV12 / I420 frames, host and device, and the crop launches alone."""
+    fmts = [f.strip().lower() for f in args.format.split(",")]
+    rgb = hd_frames(args.frames + 4)
+    planes = [rgb_to_yuv420(f, seed=t) for t, f in enumerate(rgb)] if set(fmts) - {"rgb"} else []
+    frames = {f: (list(rgb) if f == "rgb" else yuv_frames(planes, f)) for f in fmts}
+    net = FEARNetHIP(DEFAULT_WEIGHTS, device=0, max_batch=args.max_batch)
+    cfg = DEFAULT_TRACKING_CONFIG
+    dev = torch.device("cuda:0")
+    on_dev = {f: ([torch.from_numpy(x).to(dev) for x in v] if f == "rgb" else [x.to(dev) for x in v]) for f, v in frames.items()}
+    res = {"frame_shape": list(rgb[0].shape), "frames_timed": args.frames, "max_batch": args.max_batch,
+           "device": torch.cuda.get_device_name(0), "formats": fmts, "per_k": []}
+    for k in (int(v) for v in args.ks.split(",")):
+        boxes = target_boxes(k)
+        row = {"k": k}
+        for f in fmts:
+            row[f"submit_host_{f}_ms"] = pipelined_ms(net, cfg, frames[f][0], frames[f], boxes, args.frames)
+            if args.device_frames:
+                row[f"submit_device_{f}_ms"] = pipelined_ms(net, cfg, on_dev[f][0], on_dev[f], boxes, args.frames)
+                if f != "rgb":
+                    row[f"submit_device_{f}_via_yuv_to_rgb_ms"] = pipelined_ms(net, cfg, on_dev[f][0], on_dev[f], boxes,
+                                                                               args.frames, prep=net.yuv_to_rgb)
+        # the crop launches alone, on one device frame per format: the search crops of the K targets' first frame
+        mt = FEARMultiTracker(net, cuda_id=0, **cfg)
+        mt.add(rgb[0], boxes)
+        fidx, ctx, pad = mt._fidx, mt._ctx, mt._pad
+        S = cfg["instance_size"]
+        out = torch.empty((k, 3, S, S), dtype=torch.float32, device=dev)
+        if "rgb" in fmts:
+            tab = net.frame_table([on_dev["rgb"][0]])
+            row["crop_rgb_us"] = 1e3 * event_ms(lambda: net.crop_normalize_frames(tab, fidx, ctx, pad, S, out=out), 50)
+        for f in fmts:
+            if f == "rgb":
+                continue
+            tab_p = net.frame_table_planar([on_dev[f][0]])
+            rgb_buf = torch.empty(rgb[0].shape, dtype=torch.uint8, device=dev)
+            tab_c = net.frame_table([rgb_buf])
+            row[f"crop_planar_{f}_us"] = 1e3 * event_ms(lambda: net.crop_normalize_planar(tab_p, fidx, ctx, pad, S, out=out), 50)
+            row[f"yuv_to_rgb_{f}_us"] = 1e3 * event_ms(lambda: net.yuv_to_rgb(on_dev[f][0], out=rgb_buf), 50)
+            row[f"yuv_to_rgb_then_crop_{f}_us"] = 1e3 * event_ms(
+                lambda: (net.yuv_to_rgb(on_dev[f][0], out=rgb_buf), net.crop_normalize_frames(tab_c, fidx, ctx, pad, S, out=out)),
+                50)
+        res["per_k"].append(row)
+        print(json.dumps(row), flush=True)
+    with open(args.out or os.path.join(ROOT, "profiles", "multi_track_yuv_bench.json"), "w") as fh:
+        json.dump(res, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ks", default="1,16,64,256,1024")
@@ -63,7 +157,11 @@ def main():
     ap.add_argument("--no-singles", action="store_true")
     ap.add_argument("--submit-only", action="store_true", help="time only the pipelined submit loop (for a kernel trace of it)")
     ap.add_argument("--out", default="")
+    ap.add_argument("--format", default="", help="rgb,nv12,i420: time video frames (see the module docstring)")
+    ap.add_argument("--device-frames", action="store_true", help="with --format: device frames too")
     args = ap.parse_args()
+    if args.format:
+        return yuv_main(args)
     sync = torch.cuda.synchronize
     frames = hd_frames(args.frames + 4)
     net = FEARNetHIP(DEFAULT_WEIGHTS, device=0, max_batch=args.max_batch)
