@@ -2238,3 +2238,4 @@ int fear_adam_step(float* param, const float* grad, float* exp_avg, float* exp_a
 }  // extern "C"
 
 #include "fear_train_block.h"
+#include "fear_train_data.h"

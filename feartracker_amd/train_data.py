@@ -1,0 +1,497 @@
+"""Training pairs from frames on the GPU: the data stage in front of `FEARNetTrainHIP.step`.
+
+`TrainPairBuilder` turns (frames, template box, search box) into exactly the five tensors the step takes, the way the reference's
+`SiameseTrackingDataset._transform` does per pair on the CPU (model_training/dataset/siam_dataset.py:33-61):
+
+* template  `get_extended_crop(frame, box, 128, offset=0.2)`, padded with the frame's mean colour   (tracking_dataset.py:139-156)
+* search    `get_extended_crop(frame, box, 512, offset=u)`, u = random() * 3 + 2.5, then `BBoxCropWithOffsets` (scale 0.35,
+            shift 48): a jittered square of the 512 crop warped to 256 x 256 by `cv2.warpAffine` (tracking_dataset.py:107-137,
+            aug.py:52-143); the box follows through `apply_to_bbox`, `ensure_bbox_boundaries`, `handle_empty_bbox`
+* colour    `OneOf([ToGray, ToSepia], p=0.05)` and, at p = 0.5, one of RandomBrightnessContrast / RandomGamma / RGBShift — drawn once
+            per pair and applied to both crops (siam_dataset.py:64-67; the subset is DESIGN.md section 11's)
+* targets   `FEARBoxCoder.encode(search_bbox)` and `get_regression_weight_label(search_bbox, 256, 16)`, zeros without presence
+
+Every scalar per-pair step runs here on the host, vectorised over the batch: the draws (`draw`), the context boxes (`extend_bbox`,
+`crop_geometry` of geometry.py), the jittered box, `apply_to_bbox` with its truncations, the inverse warp matrix (cv2's order of
+operations, float64) and the colour lookup tables.  The device (include/fear_train.h: `fear_frame_border_u8`, `fear_train_pairs`)
+does the per-pixel and per-cell work.  `build_host` restates the device arithmetic in numpy; `build` equals it bit for bit.
+
+The reference calls cv2 (`copyMakeBorder`, `resize`, `warpAffine`, `cvtColor`) and albumentations, neither of which is installed
+here: the restatements follow OpenCV 4.x's 8u code paths and albumentations' uint8 lookup-table forms, but parity with the real
+libraries is unpinned (as for the crop).  What pins the geometry and the targets is the reference's own
+Python run on recorded draws (tests/golden/train_pairs_geometry.npz, tools/make_train_pairs_golden.py).
+"""
+from __future__ import annotations
+
+import ctypes
+from collections import namedtuple
+from dataclasses import dataclass
+from typing import Any, Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .geometry import _INV_STD, _MEAN, _linear_taps, border_color_u8, extend_bbox  # noqa: F401  (extend_bbox: the scalar form)
+
+TEMPLATE_SIZE, CONTEXT_SIZE, SEARCH_SIZE, SCORE_SIZE, TOTAL_STRIDE = 128, 512, 256, 16, 16
+
+# (the values of config/dataset/got10k_train.yaml and config/tracker/siam_tracker.yaml)
+DEFAULT_TRAIN_DATA_CONFIG: Dict[str, Any] = dict(
+    template_bbox_offset=0.2,
+    search_context=2,            # the dataset doubles it: offsets u in [2 * 2 - 3 / 2, 2 * 2 + 3 / 2)
+    context_range=3,
+    search_image_scale=0.35,
+    search_image_shift=48,
+    r_pos=2,
+    tone_p=0.05,                 # OneOf([ToGray, ToSepia])
+    colour_p=0.5,                # OneOf([RandomBrightnessContrast, RandomGamma, RGBShift])
+    brightness_limit=0.2, contrast_limit=0.2, gamma_limit=(0.8, 1.2), rgb_shift_limit=20.0,
+)
+
+TONE_NONE, TONE_GRAY, TONE_SEPIA = 0, 1, 2
+COLOUR_NONE, COLOUR_BRIGHTNESS_CONTRAST, COLOUR_GAMMA, COLOUR_RGB_SHIFT = 0, 1, 2, 3
+
+# columns of the pairs table
+PAIR_COLUMNS = ("template_frame", "tx", "ty", "tw", "th", "search_frame", "sx", "sy", "sw", "sh", "presence")
+
+TrainBatch = namedtuple("TrainBatch", ["template", "search", "gt_reg", "gt_cls", "gt_weight", "search_bbox"])
+
+_SEPIA = np.array([[0.393, 0.769, 0.189], [0.349, 0.686, 0.168], [0.272, 0.534, 0.131]], dtype=np.float32)
+
+GEOM_DTYPE = np.dtype([("t_frame", "<i4"), ("s_frame", "<i4"), ("t_ctx", "<i4", 4), ("s_ctx", "<i4", 4), ("box", "<i4", 4),
+                       ("presence", "<i4"), ("tone", "<i4"), ("inv", "<f8", 4)])
+assert GEOM_DTYPE.itemsize == 96
+FRAME_DTYPE = np.dtype([("data", "<u8"), ("h", "<i4"), ("w", "<i4")])        # fear_frame
+
+
+@dataclass
+class TrainPairParams:
+    """Every random parameter of one batch (a replayable host record).  Per pair: the search context offset, the jitter
+    (scale_x, scale_y, shift_x, shift_y), the tone branch, the colour branch and the values of all three colour members (only the
+    drawn branch's are used)."""
+    context: np.ndarray          # (B,) float64
+    jitter: np.ndarray           # (B, 4) float64
+    tone: np.ndarray             # (B,) int32, TONE_*
+    colour: np.ndarray           # (B,) int32, COLOUR_*
+    alpha: np.ndarray            # (B,) contrast
+    beta: np.ndarray             # (B,) brightness
+    gamma: np.ndarray            # (B,)
+    shift: np.ndarray            # (B, 3) RGB shift
+    frame_shapes: Tuple[Tuple[int, int], ...]
+
+
+def _pairs_array(pairs) -> np.ndarray:
+    p = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
+    p = np.asarray(p, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != len(PAIR_COLUMNS):
+        raise ValueError(f"pairs must be (B, {len(PAIR_COLUMNS)}): {', '.join(PAIR_COLUMNS)}")
+    return p
+
+
+# --------------------------------------------------------------------------------------------------------------------- geometry
+def _extend(box: np.ndarray, offset) -> np.ndarray:
+    """extend_bbox over rows: [x - w o, y - h o, w (1 + o + o), h (1 + o + o)] truncated to int32 (utils.py:29-57)."""
+    x, y, w, h = box.T
+    o = np.asarray(offset, dtype=np.float64)
+    grow = (1.0 + o) + o
+    return np.stack([x - w * o, y - h * o, w * grow, h * grow], axis=1).astype(np.int32)
+
+
+def _ensure(box: np.ndarray, h, w) -> np.ndarray:
+    """ensure_bbox_boundaries over rows (utils.py:60-71)."""
+    x, y, bw, bh = box.T
+    x_lo = np.minimum(np.maximum(0, x), w)
+    y_lo = np.minimum(np.maximum(0, y), h)
+    x_hi = np.minimum(np.maximum(0, x_lo + bw), w)
+    y_hi = np.minimum(np.maximum(0, y_lo + bh), h)
+    return np.stack([x_lo, y_lo, x_hi - x_lo, y_hi - y_lo], axis=1).astype(np.int32)
+
+
+def _box_in_crop(box: np.ndarray, ctx: np.ndarray, size: int) -> np.ndarray:
+    """get_extended_crop's box output over rows: the box in the padded context, then albumentations' coco Resize (float64)."""
+    rel = np.stack([box[:, 0] - ctx[:, 0], box[:, 1] - ctx[:, 1], box[:, 2], box[:, 3]], axis=1)
+    cw, ch = ctx[:, 2].astype(np.float64), ctx[:, 3].astype(np.float64)
+    b = _ensure(rel, ctx[:, 3], ctx[:, 2])
+    x_min, y_min = np.clip(b[:, 0] / cw, 0.0, 1.0), np.clip(b[:, 1] / ch, 0.0, 1.0)
+    x_max, y_max = np.clip((b[:, 0] + b[:, 2]) / cw, 0.0, 1.0), np.clip((b[:, 1] + b[:, 3]) / ch, 0.0, 1.0)
+    x_min, x_max, y_min, y_max = x_min * size, x_max * size, y_min * size, y_max * size
+    return np.stack([x_min, y_min, x_max - x_min, y_max - y_min], axis=1)
+
+
+def jittered_crop(jitter: np.ndarray, scale_shift_box=(128, 128, 256, 256), img: int = CONTEXT_SIZE) -> np.ndarray:
+    """BBoxCropWithOffsets.get_params_dependent_on_targets (aug.py:88-107) over rows: the modified crop box, float64 xywh."""
+    x, y, w, h = scale_shift_box
+    sx, sy, tx, ty = jitter.T
+    nx = np.maximum(0, x - sx * w / 2 + tx)
+    ny = np.maximum(0, y - sy * h / 2 + ty)
+    nw = np.minimum(img, nx + w + sx * w) - nx
+    nh = np.minimum(img, ny + h + sy * h) - ny
+    return np.stack([nx, ny, nw, nh], axis=1)
+
+
+def apply_to_bbox(box: np.ndarray, crop: np.ndarray, size: int = SEARCH_SIZE) -> np.ndarray:
+    """BBoxCropWithOffsets.apply_to_bbox (aug.py:109-129) over rows, int truncation at the end: int64 xywh."""
+    nx = (box[:, 0] - crop[:, 0]) * size / crop[:, 2]
+    ny = (box[:, 1] - crop[:, 1]) * size / crop[:, 3]
+    nw = box[:, 2] * size / crop[:, 2]
+    nh = box[:, 3] * size / crop[:, 3]
+    nw = np.where(nx < 0, nw + nx, nw)
+    nx = np.where(nx < 0, 0.0, nx)
+    nh = np.where(ny < 0, nh + ny, nh)
+    ny = np.where(ny < 0, 0.0, ny)
+    nw = np.minimum(size, nx + nw) - nx
+    nh = np.minimum(size, ny + nh) - ny
+    return np.trunc(np.stack([nx, ny, nw, nh], axis=1)).astype(np.int64)
+
+
+def warp_matrix(crop: np.ndarray, out_size: int = SEARCH_SIZE) -> np.ndarray:
+    """affine_crop's forward matrices (aug.py:131-143) over rows: (B, 2, 3) [[a, 0, c], [0, b, d]], a = (out - 1) / w, c = -a x."""
+    a = (out_size - 1) / crop[:, 2]
+    b = (out_size - 1) / crop[:, 3]
+    c = -a * crop[:, 0]
+    d = -b * crop[:, 1]
+    z = np.zeros_like(a)
+    return np.stack([np.stack([a, z, c], axis=1), np.stack([z, b, d], axis=1)], axis=1)
+
+
+def invert_affine(M: np.ndarray) -> np.ndarray:
+    """cv2.warpAffine's inversion of a forward matrix (imgwarp.cpp, no WARP_INVERSE_MAP), in its float64 order of operations.
+    M (..., 2, 3) -> (..., 2, 3)."""
+    M = np.asarray(M, dtype=np.float64)
+    m0, m1, m2, m3, m4, m5 = (M[..., i // 3, i % 3] for i in range(6))
+    D = m0 * m4 - m1 * m3
+    with np.errstate(divide="ignore"):
+        D = np.where(D != 0, 1.0 / np.where(D != 0, D, 1.0), 0.0)
+    a11, a22 = m4 * D, m0 * D
+    i0, i1, i3, i4 = a11, m1 * -D, m3 * -D, a22
+    b1 = -i0 * m2 - i1 * m5
+    b2 = -i3 * m2 - i4 * m5
+    return np.stack([np.stack([i0, i1, b1], axis=-1), np.stack([i3, i4, b2], axis=-1)], axis=-2)
+
+
+def _bilinear_tab() -> np.ndarray:
+    """initInterTab2D(INTER_LINEAR, fixed point) -> (1024, 4) int64 weights (w00, w01, w10, w11) of entry fy * 32 + fx: the
+    products (1 - fy/32 | fy/32) (1 - fx/32 | fx/32) * 32768 are exact; entry 0's 32768 saturates to 32767 and the table's sum
+    correction puts the missing 1 on its (1, 1) weight."""
+    f = np.arange(32, dtype=np.int64)
+    fy, fx = np.meshgrid(f, f, indexing="ij")
+    tab = np.stack([(32 - fy) * (32 - fx), (32 - fy) * fx, fy * (32 - fx), fy * fx], axis=-1).reshape(1024, 4) * 32
+    tab[0] = (32767, 0, 0, 1)
+    return tab
+
+
+_TAB = _bilinear_tab()
+
+
+def remap_affine_u8(src: np.ndarray, Minv: np.ndarray, dsize: Tuple[int, int]) -> np.ndarray:
+    """cv2.warpAffine(src, M, dsize, INTER_LINEAR, BORDER_CONSTANT, 0) for uint8 (H, W, C), given the INVERTED matrix: OpenCV
+    4.x's fixed point (AB_BITS 10, INTER_BITS 5, round_delta 16, row term and column delta rounded separately, half to even), the
+    15-bit weight table, `(sum + (1 << 14)) >> 15`; taps outside the source read 0."""
+    out_w, out_h = dsize
+    m0, m1, m2, m3, m4, m5 = (float(Minv[i // 3][i % 3]) for i in range(6))
+    ys = np.arange(out_h, dtype=np.float64)
+    xs = np.arange(out_w, dtype=np.float64)
+    X0 = np.rint((m1 * ys + m2) * 1024).astype(np.int64) + 16
+    Y0 = np.rint((m4 * ys + m5) * 1024).astype(np.int64) + 16
+    adelta = np.rint(m0 * xs * 1024).astype(np.int64)
+    bdelta = np.rint(m3 * xs * 1024).astype(np.int64)
+    X = (X0[:, None] + adelta[None, :]) >> 5
+    Y = (Y0[:, None] + bdelta[None, :]) >> 5
+    sx, sy = X >> 5, Y >> 5
+    w = _TAB[(Y & 31) * 32 + (X & 31)]                                     # (out_h, out_w, 4)
+    h, wd = src.shape[:2]
+    img = src.reshape(h, wd, -1).astype(np.int64)
+    acc = np.zeros((out_h, out_w, img.shape[2]), dtype=np.int64)
+    for k, (oy, ox) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+        yy, xx = sy + oy, sx + ox
+        inside = (xx >= 0) & (xx < wd) & (yy >= 0) & (yy < h)
+        v = img[np.clip(yy, 0, h - 1), np.clip(xx, 0, wd - 1)] * inside[..., None]
+        acc += v * w[..., k:k + 1]
+    return ((acc + (1 << 14)) >> 15).astype(np.uint8).reshape((out_h, out_w) + src.shape[2:])
+
+
+def warp_affine_u8(src: np.ndarray, M: np.ndarray, dsize: Tuple[int, int]) -> np.ndarray:
+    """cv2.warpAffine(src, M, dsize, flags=INTER_LINEAR, borderMode=BORDER_CONSTANT, borderValue=0) on uint8 (forward M)."""
+    return remap_affine_u8(src, invert_affine(M), dsize)
+
+
+def crop_u8(frame: Optional[np.ndarray], pad: Sequence[int], ctx: Sequence[int], size: int) -> np.ndarray:
+    """resize_bilinear_u8(copy_make_border(frame's part of ctx, pad), size, size) (geometry.get_extended_crop's pixels) computed
+    per tap, without the padded context: what the device kernels compute.  `frame` None: a frame with no pixels."""
+    cx, cy, cw, ch = (int(v) for v in ctx)
+    fh, fw = (frame.shape[0], frame.shape[1]) if frame is not None else (0, 0)
+    padv = np.asarray(pad, dtype=np.int64).reshape(3)
+
+    def sample(ys, xs):            # (len(ys), len(xs), 3) int64 context pixels
+        fy, fx = cy + ys[:, None], cx + xs[None, :]
+        inside = (fx >= 0) & (fx < fw) & (fy >= 0) & (fy < fh)
+        out = np.broadcast_to(padv, inside.shape + (3,)).copy()
+        if frame is not None and inside.any():
+            out[inside] = frame[np.clip(fy, 0, fh - 1), np.clip(fx, 0, fw - 1)][inside]
+        return out
+
+    if cw == size and ch == size:
+        return sample(np.arange(size), np.arange(size)).astype(np.uint8)
+    if cw == 2 * size and ch == 2 * size:
+        e, o = np.arange(0, 2 * size, 2), np.arange(1, 2 * size, 2)
+        return ((sample(e, e) + sample(e, o) + sample(o, e) + sample(o, o) + 2) >> 2).astype(np.uint8)
+    ix, ax0, ax1 = _linear_taps(size, cw, clamp=True)
+    iy, ay0, ay1 = _linear_taps(size, ch, clamp=False)
+    ix1 = np.minimum(ix + 1, cw - 1)
+    iy0, iy1 = np.clip(iy, 0, ch - 1), np.clip(iy + 1, 0, ch - 1)
+    r0 = sample(iy0, ix) * ax0[None, :, None] + sample(iy0, ix1) * ax1[None, :, None]
+    r1 = sample(iy1, ix) * ax0[None, :, None] + sample(iy1, ix1) * ax1[None, :, None]
+    out = (((ay0[:, None, None] * (r0 >> 4)) >> 16) + ((ay1[:, None, None] * (r1 >> 4)) >> 16) + 2) >> 2
+    return np.clip(out, 0, 255).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------------------------------ colour
+def colour_luts(params: TrainPairParams) -> np.ndarray:
+    """(B, 3, 256) uint8 lookup tables of the drawn colour members, albumentations' uint8 forms:
+    brightness / contrast  trunc(clip(fp32(v) * fp32(alpha) + fp32(beta * 255), 0, 255))
+    gamma                  trunc((v / 255) ** gamma * 255), float64
+    RGB shift              trunc(clip(fp32(v) + fp32(shift_c), 0, 255))
+    and the identity where no member was drawn."""
+    B = len(params.colour)
+    v32 = np.arange(256, dtype=np.float32)
+    lut = np.broadcast_to(np.arange(256, dtype=np.uint8), (B, 3, 256)).copy()
+    kind = np.asarray(params.colour)
+    sel = kind == COLOUR_BRIGHTNESS_CONTRAST
+    if sel.any():
+        t = v32[None, :] * params.alpha[sel].astype(np.float32)[:, None]
+        t = t + (params.beta[sel] * 255.0).astype(np.float32)[:, None]
+        lut[sel] = np.clip(t, 0, 255).astype(np.uint8)[:, None, :]
+    sel = kind == COLOUR_GAMMA
+    if sel.any():
+        t = (np.arange(256, dtype=np.float64)[None, :] / 255.0) ** params.gamma[sel][:, None] * 255.0
+        lut[sel] = t.astype(np.uint8)[:, None, :]
+    sel = kind == COLOUR_RGB_SHIFT
+    if sel.any():
+        t = v32[None, None, :] + params.shift[sel].astype(np.float32)[:, :, None]
+        lut[sel] = np.clip(t, 0, 255).astype(np.uint8)
+    return lut
+
+
+def apply_tone(rgb: np.ndarray, tone: int) -> np.ndarray:
+    """The tone stage on uint8 (..., 3): cv2 RGB2GRAY (14-bit fixed point) to all channels, or albumentations' sepia matrix
+    accumulated in fp32 (j = 0, 1, 2), rounded half to even and saturated."""
+    if tone == TONE_GRAY:
+        v = rgb.astype(np.int64)
+        g = (4899 * v[..., 0] + 9617 * v[..., 1] + 1868 * v[..., 2] + 8192) >> 14
+        return np.repeat(g[..., None], 3, axis=-1).astype(np.uint8)
+    if tone == TONE_SEPIA:
+        v = rgb.astype(np.float32)
+        out = []
+        for i in range(3):
+            acc = _SEPIA[i, 0] * v[..., 0]
+            acc = acc + _SEPIA[i, 1] * v[..., 1]
+            acc = acc + _SEPIA[i, 2] * v[..., 2]
+            out.append(np.clip(np.rint(acc), 0, 255))
+        return np.stack(out, axis=-1).astype(np.uint8)
+    return rgb
+
+
+def _colour_normalise(rgb: np.ndarray, tone: int, lut: np.ndarray) -> np.ndarray:
+    """(H, W, 3) uint8 -> tone -> lut -> normalised fp32 (3, H, W)."""
+    v = apply_tone(rgb, tone)
+    v = np.stack([lut[c][v[..., c]] for c in range(3)], axis=-1).astype(np.float32)
+    v -= _MEAN
+    v *= _INV_STD
+    return np.ascontiguousarray(v.transpose(2, 0, 1))
+
+
+def encode_targets(search_bbox: np.ndarray, presence: np.ndarray, r_pos: int = 2):
+    """FEARBoxCoder.encode + get_regression_weight_label(bbox, 256, 16) over rows, zeros where presence == 0:
+    gt_reg (B, 4, 16, 16), gt_cls (B, 1, 16, 16), gt_weight (B, 16, 16), fp32."""
+    ticks = (np.arange(SCORE_SIZE) - np.floor(float(SCORE_SIZE // 2))) * TOTAL_STRIDE + SEARCH_SIZE // 2
+    gx, gy = np.meshgrid(ticks, ticks)
+    b = search_bbox.astype(np.float64)[:, :, None, None]
+    x0, y0 = b[:, 0], b[:, 1]
+    reg = np.stack([gx - x0, gy - y0, (x0 + b[:, 2]) - gx, (y0 + b[:, 3]) - gy], axis=1).astype(np.float32)
+    cls = (reg.min(axis=1, keepdims=True) > 0).astype(np.float32)
+    c_x = search_bbox[:, 0] + search_bbox[:, 2] // 2
+    c_y = search_bbox[:, 1] + search_bbox[:, 3] // 2
+    sz_x = np.floor(c_x / SEARCH_SIZE * SCORE_SIZE)
+    sz_y = np.floor(c_y / SEARCH_SIZE * SCORE_SIZE)
+    jj, ii = np.meshgrid(np.arange(SCORE_SIZE), np.arange(SCORE_SIZE))
+    dist = np.abs(jj[None] - sz_x[:, None, None]) + np.abs(ii[None] - sz_y[:, None, None])
+    wgt = (dist <= r_pos).astype(np.float32)
+    keep = (np.asarray(presence) != 0).astype(np.float32)
+    return reg * keep[:, None, None, None], cls * keep[:, None, None, None], wgt * keep[:, None, None]
+
+
+# ----------------------------------------------------------------------------------------------------------------------- builder
+class TrainPairBuilder:
+    """Builds the step's inputs from frames.  `pairs` is a (B, 11) table (PAIR_COLUMNS): template frame index, template box xywh,
+    search frame index, search box xywh, presence.  Which frames a pair uses is the caller's business."""
+
+    def __init__(self, config: Optional[Dict[str, Any]] = None, device: int = 0, seed: Optional[int] = None):
+        self.config = dict(DEFAULT_TRAIN_DATA_CONFIG)
+        if config:
+            unknown = set(config) - set(self.config)
+            if unknown:
+                raise KeyError(f"unknown train-data config keys {sorted(unknown)}")
+            self.config.update(config)
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        self.generator = np.random.default_rng(seed)
+        self._lib = None
+
+    # ------------------------------------------------------------------ draws
+    def draw(self, pairs, frame_shapes: Sequence[Tuple[int, ...]], generator: Optional[np.random.Generator] = None) -> TrainPairParams:
+        """Every random parameter of a batch, vectorised, from `generator` (the builder's own when None).  The draws mirror the
+        reference's: u = U * range + (2 context - range / 2) (tracking_dataset.py:102-105); scale ~ U(-0.35, 0.35), shift ~
+        U(-48, 48) (aug.py:90-93); tone at p = 0.05, colour at p = 0.5, each picking uniformly among its members."""
+        p = _pairs_array(pairs)
+        rng = self.generator if generator is None else generator
+        cfg = self.config
+        B = p.shape[0]
+        rng_ctx = float(cfg["context_range"])
+        min_ctx = 2 * float(cfg["search_context"]) - rng_ctx / 2
+        context = rng.random(B) * rng_ctx + min_ctx
+        sc, sh = float(cfg["search_image_scale"]), float(cfg["search_image_shift"])
+        jitter = np.concatenate([rng.uniform(-sc, sc, size=(B, 2)), rng.uniform(-sh, sh, size=(B, 2))], axis=1)
+        tone = np.where(rng.random(B) < cfg["tone_p"], 1 + rng.integers(0, 2, size=B), TONE_NONE).astype(np.int32)
+        colour = np.where(rng.random(B) < cfg["colour_p"], 1 + rng.integers(0, 3, size=B), COLOUR_NONE).astype(np.int32)
+        alpha = 1.0 + rng.uniform(-cfg["contrast_limit"], cfg["contrast_limit"], size=B)
+        beta = rng.uniform(-cfg["brightness_limit"], cfg["brightness_limit"], size=B)
+        gamma = rng.uniform(cfg["gamma_limit"][0], cfg["gamma_limit"][1], size=B)
+        shift = rng.uniform(-cfg["rgb_shift_limit"], cfg["rgb_shift_limit"], size=(B, 3))
+        shapes = tuple((int(s[0]), int(s[1])) for s in frame_shapes)
+        return TrainPairParams(context, jitter, tone, colour, alpha, beta, gamma, shift, shapes)
+
+    # ------------------------------------------------------------------ host tables
+    def tables(self, pairs, params: TrainPairParams) -> Dict[str, np.ndarray]:
+        """The per-pair host work: context boxes, the 512-crop box, the jittered crop, the moved box (search_bbox), the warp and its
+        inverse, the lookup tables and the FearPairGeom records."""
+        p = _pairs_array(pairs)
+        B = p.shape[0]
+        if len(params.context) != B:
+            raise ValueError(f"params were drawn for {len(params.context)} pairs, the table has {B}")
+        t_box, s_box = p[:, 1:5], p[:, 6:10]
+        t_ctx = _extend(t_box, float(self.config["template_bbox_offset"]))
+        s_ctx = _extend(s_box, params.context)
+        box512 = _box_in_crop(s_box, s_ctx, CONTEXT_SIZE)
+        crop = jittered_crop(params.jitter)
+        moved = apply_to_bbox(box512, crop)
+        b = _ensure(moved, SEARCH_SIZE, SEARCH_SIZE)
+        b[:, 2:] = np.maximum(b[:, 2:], 3)                                   # handle_empty_bbox
+        search_bbox = _ensure(b, SEARCH_SIZE, SEARCH_SIZE)                    # _transform's final ensure_bbox_boundaries
+        M = warp_matrix(crop)
+        Minv = invert_affine(M)
+        geom = np.zeros(B, dtype=GEOM_DTYPE)
+        geom["t_frame"], geom["s_frame"] = p[:, 0].astype(np.int32), p[:, 5].astype(np.int32)
+        geom["t_ctx"], geom["s_ctx"], geom["box"] = t_ctx, s_ctx, search_bbox
+        geom["presence"] = (p[:, 10] != 0).astype(np.int32)
+        geom["tone"] = params.tone
+        geom["inv"] = np.stack([Minv[:, 0, 0], Minv[:, 0, 2], Minv[:, 1, 1], Minv[:, 1, 2]], axis=1)
+        return dict(t_ctx=t_ctx, s_ctx=s_ctx, box512=box512, crop=crop, moved=moved, search_bbox=search_bbox, M=M, Minv=Minv,
+                    lut=colour_luts(params), geom=geom)
+
+    def _params(self, pairs, frames, params):
+        shapes = tuple((int(f.shape[0]), int(f.shape[1])) for f in frames)
+        if params is None:
+            return self.draw(pairs, shapes)
+        if params.frame_shapes and tuple(params.frame_shapes) != shapes:
+            raise ValueError("params were drawn for other frame shapes")
+        return params
+
+    # ------------------------------------------------------------------ host restatement
+    def build_host(self, frames: Sequence, pairs, params: Optional[TrainPairParams] = None) -> TrainBatch:
+        """numpy restatement of `build` (same arithmetic, term for term): the reference `build` is tested against."""
+        host = [f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f) for f in frames]
+        params = self._params(pairs, host, params)
+        tab = self.tables(pairs, params)
+        geom, lut = tab["geom"], tab["lut"]
+        borders = [border_color_u8(np.mean(f[:, :, :3], axis=(0, 1))) if f.shape[0] > 0 and f.shape[1] > 0 else np.zeros(3, np.uint8)
+                   for f in host]
+        B = len(geom)
+        tmpl = np.empty((B, 3, TEMPLATE_SIZE, TEMPLATE_SIZE), dtype=np.float32)
+        srch = np.empty((B, 3, SEARCH_SIZE, SEARCH_SIZE), dtype=np.float32)
+
+        def frame_of(i):
+            if 0 <= i < len(host):
+                return np.ascontiguousarray(host[i][:, :, :3]), borders[i]
+            return None, np.zeros(3, np.uint8)
+
+        for k in range(B):
+            f, pad = frame_of(int(geom["t_frame"][k]))
+            t = crop_u8(f, pad, geom["t_ctx"][k], TEMPLATE_SIZE)
+            tmpl[k] = _colour_normalise(t, int(geom["tone"][k]), lut[k])
+            f, pad = frame_of(int(geom["s_frame"][k]))
+            c512 = crop_u8(f, pad, geom["s_ctx"][k], CONTEXT_SIZE)
+            s = remap_affine_u8(c512, tab["Minv"][k], (SEARCH_SIZE, SEARCH_SIZE))
+            srch[k] = _colour_normalise(s, int(geom["tone"][k]), lut[k])
+        reg, cls, wgt = encode_targets(tab["search_bbox"], geom["presence"], int(self.config["r_pos"]))
+        return TrainBatch(tmpl, srch, reg, cls, wgt, tab["search_bbox"].astype(np.int32))
+
+    # ------------------------------------------------------------------ device
+    def _library(self):
+        if self._lib is None:
+            from .train_head import load_train_library
+            self._lib = load_train_library()
+        return self._lib
+
+    @torch.no_grad()
+    def build(self, frames: Sequence, pairs, params: Optional[TrainPairParams] = None) -> TrainBatch:
+        """The batch on the GPU: template (B,3,128,128), search (B,3,256,256), gt_reg (B,4,16,16), gt_cls (B,1,16,16),
+        gt_weight (B,16,16) fp32 and search_bbox (B,4) int32, on the current stream, in the layouts `FEARNetTrainHIP.step` takes.
+        Frames are uint8 (H, W, 3) numpy arrays or device tensors.  Host frames and the per-pair tables go up non-blocking from
+        pinned memory; with device frames the call never waits for the GPU."""
+        lib = self._library()
+        dev = self.device
+        params = self._params(pairs, frames, params)
+        tab = self.tables(pairs, params)
+        geom, lut = tab["geom"], tab["lut"]
+        B, F = len(geom), len(frames)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            dframes = [self._frame_on_device(f) for f in frames]
+            # one staging buffer, one transfer: frame table | geometry | lookup tables | search_bbox
+            o_geom = 16 * F
+            o_lut = o_geom + 96 * B
+            o_box = o_lut + 768 * B
+            total = o_box + 16 * B
+            pinned = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True)
+            hv = pinned.numpy()
+            ftab = np.zeros(F, dtype=FRAME_DTYPE)
+            for i, f in enumerate(dframes):
+                ftab[i] = (f.data_ptr(), f.shape[0], f.shape[1])
+            hv[:o_geom] = ftab.view(np.uint8)
+            hv[o_geom:o_lut] = geom.view(np.uint8)
+            hv[o_lut:o_box] = lut.reshape(-1)
+            hv[o_box:total] = tab["search_bbox"].astype(np.int32).view(np.uint8).reshape(-1)
+            staged = pinned.to(dev, non_blocking=True)
+            base = staged.data_ptr()
+            border = torch.empty((max(F, 1), 3), dtype=torch.uint8, device=dev)
+            tmpl = torch.empty((B, 3, TEMPLATE_SIZE, TEMPLATE_SIZE), dtype=torch.float32, device=dev)
+            srch = torch.empty((B, 3, SEARCH_SIZE, SEARCH_SIZE), dtype=torch.float32, device=dev)
+            reg = torch.empty((B, 4, SCORE_SIZE, SCORE_SIZE), dtype=torch.float32, device=dev)
+            cls = torch.empty((B, 1, SCORE_SIZE, SCORE_SIZE), dtype=torch.float32, device=dev)
+            wgt = torch.empty((B, SCORE_SIZE, SCORE_SIZE), dtype=torch.float32, device=dev)
+            st = ctypes.c_void_p(stream.cuda_stream)
+            rc = lib.fear_frame_border_u8(ctypes.c_void_p(base), F, ctypes.c_void_p(border.data_ptr()), st)
+            if rc != 0:
+                raise RuntimeError(f"fear_frame_border_u8 failed with status {rc}")
+            rc = lib.fear_train_pairs(ctypes.c_void_p(base), F, ctypes.c_void_p(border.data_ptr()), ctypes.c_void_p(base + o_geom),
+                                      ctypes.c_void_p(base + o_lut), B, ctypes.c_void_p(tmpl.data_ptr()),
+                                      ctypes.c_void_p(srch.data_ptr()), ctypes.c_void_p(reg.data_ptr()),
+                                      ctypes.c_void_p(cls.data_ptr()), ctypes.c_void_p(wgt.data_ptr()), st)
+            if rc != 0:
+                raise RuntimeError(f"fear_train_pairs failed with status {rc}")
+            for f in dframes:                          # host frames were allocated here; device frames may live on another stream
+                f.record_stream(stream)
+            box = staged[o_box:total].view(torch.int32).view(B, 4)
+        return TrainBatch(tmpl, srch, reg, cls, wgt, box)
+
+    def _frame_on_device(self, f) -> torch.Tensor:
+        if isinstance(f, torch.Tensor):
+            if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] < 3:
+                raise ValueError("device frames must be uint8 (H, W, 3)")
+            return f[:, :, :3].to(self.device).contiguous()
+        arr = np.asarray(f)
+        if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] < 3:
+            raise ValueError("host frames must be uint8 (H, W, 3)")
+        arr = arr[:, :, :3]
+        pinned = torch.empty(arr.shape, dtype=torch.uint8, pin_memory=True)
+        np.copyto(pinned.numpy(), arr)
+        return pinned.to(self.device, non_blocking=True)

@@ -83,6 +83,9 @@ TRAIN_SYMBOLS = {
     "fear_sepbn_train_backward": ([_P, _P, _P, _i, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _P, _sz, _P, _P], _i),
     # SyncBatchNorm hook of the block-fused operators: (stream, FearSync*)
     "fear_train_sync_bind": ([_P, _P], _i),
+    # training pairs from frames (train_data.TrainPairBuilder)
+    "fear_frame_border_u8": ([_P, _i, _P, _P], _i),
+    "fear_train_pairs": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _P, _P], _i),
 }
 
 

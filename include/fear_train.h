@@ -23,6 +23,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "fear_hip.h"   /* fear_frame */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -316,6 +318,50 @@ int fear_sepbn_train_forward(const FearSepLayer* layer, const float* x, int ldx,
 int fear_sepbn_train_backward(const FearSepLayer* layer, const FearSepGrads* grads, const float* x, int ldx, const float* d,
                               const float* raw, const float* vec, const float* dy, float* dd, float* coef, float* dx, int B, int H,
                               int W, float* workspace, size_t ws_bytes, void* stream, void* wgrad_stream);
+
+/* ---- training pairs from frames: the data stage in front of the step (feartracker_amd/train_data.py) ----
+ * SiameseTrackingDataset._transform of the reference (model_training/dataset/siam_dataset.py:33-61) for a batch of pairs, with the
+ * scalar per-pair work (context boxes, jitter, the moved box, the inverse warp, the colour lookup tables) done on the host and
+ * handed in as one FearPairGeom per pair.  Frames are fear_frame (include/fear_hip.h): uint8 RGB (h, w, 3), any sizes. */
+#define FEAR_TP_TEMPLATE 128    /* template crop side                                        */
+#define FEAR_TP_CONTEXT 512     /* stage-1 search crop side (get_extended_crop, 2 x search)  */
+#define FEAR_TP_SEARCH 256      /* search crop side after the jitter warp                     */
+#define FEAR_TP_SCORE 16        /* target map side; cell centres (k - 8) * 16 + 128           */
+
+/* One pair.  96 bytes, no padding. */
+typedef struct FearPairGeom {
+    int32_t t_frame, s_frame;   /* frame-table indices of the template and the search frame; outside [0, n_frames): all-zero crop */
+    int32_t t_ctx[4];           /* template context box x, y, w, h in frame pixels (extend_bbox(box, 0.2); may leave the frame)   */
+    int32_t s_ctx[4];           /* search context box, resized to the 512 x 512 stage-1 crop                                        */
+    int32_t box[4];             /* search_bbox inside the 256 x 256 search crop, xywh (the targets are encoded from it)            */
+    int32_t presence;           /* 0: gt_reg, gt_cls, gt_weight are zeros                                                           */
+    int32_t tone;               /* 0 none, 1 gray (cv2 RGB2GRAY), 2 sepia (albumentations ToSepia)                                  */
+    double inv[4];              /* inverse warp 512 -> 256 (cv2.warpAffine's inverted matrix): x_src = inv[0] x + inv[1],
+                                   y_src = inv[2] y + inv[3]                                                                        */
+} FearPairGeom;
+#ifdef __cplusplus
+static_assert(sizeof(FearPairGeom) == 96, "FearPairGeom is 96 bytes");
+#else
+_Static_assert(sizeof(FearPairGeom) == 96, "FearPairGeom is 96 bytes");
+#endif
+
+/* The frames' mean colours as cv2.copyMakeBorder writes them: per frame exact integer channel sums, then sum / (h w) in double,
+ * rounded half to even and saturated (border_color_u8(np.mean(frame, (0, 1))) bit for bit).  One launch for all frames.  A frame
+ * with no pixels (null data, h or w < 1) gets (0, 0, 0).
+ *   frames : (n_frames) fear_frame, device     out_rgb_u8 : (n_frames, 3) uint8, device                                         */
+int fear_frame_border_u8(const fear_frame* frames, int n_frames, uint8_t* out_rgb_u8, void* stream);
+
+/* Template crop, search crop and targets of n pairs (one launch):
+ *   template_out (n, 3, 128, 128) : get_extended_crop of frames[t_frame] (border border_rgb[t_frame]) -> colour -> normalise
+ *   search_out   (n, 3, 256, 256) : get_extended_crop of frames[s_frame] to 512 (computed per tap, never stored) -> cv2.warpAffine
+ *                                   INTER_LINEAR, BORDER_CONSTANT 0 (10-bit AB, 5-bit table, 15-bit weights) -> colour -> normalise
+ *   gt_reg (n, 4, 16, 16), gt_cls (n, 1, 16, 16), gt_weight (n, 16, 16) : FEARBoxCoder.encode / get_regression_weight_label(r_pos 2)
+ * The colour stage acts on a pixel's uint8 RGB: the pair's tone (gray / sepia), then lut[pair][channel][value].  Normalisation is
+ * fear_normalize_u8's (px - 255 mean) * (1 / (255 std)), fp32 NCHW.  All outputs are fp32.
+ *   frames : (n_frames) fear_frame, device     border_rgb : (n_frames, 3) uint8, device (fear_frame_border_u8)
+ *   geom : (n) FearPairGeom, device            lut : (n, 3, 256) uint8, device                                                   */
+int fear_train_pairs(const fear_frame* frames, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom, const uint8_t* lut,
+                     int n, float* template_out, float* search_out, float* gt_reg, float* gt_cls, float* gt_weight, void* stream);
 
 #ifdef __cplusplus
 }
