@@ -1973,7 +1973,6 @@ int fear_features(fear_handle* h, const float* img, int n, int hw, float* out, v
     if (n == 0) return FEAR_OK;   // empty batch: nothing to read or write, null tensors are fine
     if (!img || !out) return FEAR_ERR_NULL;
     HIP_TRY(h, hipSetDevice(h->device));
-    const int fhw = (hw / 16) * (hw / 16);
     for (int b0 = 0; b0 < n; b0 += h->max_batch) {
         const int nb = n - b0 < h->max_batch ? n - b0 : h->max_batch;
         Plan* p = nullptr;
@@ -1981,9 +1980,13 @@ int fear_features(fear_handle* h, const float* img, int n, int hw, float* out, v
         if (st != FEAR_OK) return st;
         st = ensure_workspace(h, *p);
         if (st != FEAR_OK) return st;
+        // floats per crop of the output: the neck's map as the plan computed it (the trunk's total stride is the weight file's,
+        // not necessarily 16)
+        const Op& neck = p->ops.back();
+        const size_t per_crop = (size_t)neck.N * neck.Ho * neck.Wo;
         Ext ext{};
         ext.img = img + (size_t)b0 * 3 * hw * hw;
-        ext.feat_out = out + (size_t)b0 * h->feat_channels * fhw;
+        ext.feat_out = out + (size_t)b0 * per_crop;
         const hipStream_t s = static_cast<hipStream_t>(stream);
         st = on_caller_stream(h, s, [&] { return run_plan(h, *p, nb, ext, s); });
         if (st != FEAR_OK) return st;

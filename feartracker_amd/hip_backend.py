@@ -170,6 +170,25 @@ def context_rectangle(frame_h: int, frame_w: int, ctx_xywh: np.ndarray) -> Tuple
     return x0, y0, x1, y1
 
 
+def _trunk_geometry(blob: bytes) -> Tuple[int, Tuple[int, ...]]:
+    """(neck output channels, strides of the trunk in order) of a `.fearw` blob (include/fearw_format.h): the stem's 2, then
+    the depthwise conv's stride of every inverted-residual block in front of the neck.  fear_create has validated the tables."""
+    import struct
+    _, _, n_convs, n_blocks, _, _ = struct.unpack_from("<8s4IQ", blob, 0)
+    convs = [struct.unpack_from("<8I", blob, 64 + 72 * i) for i in range(n_convs)]   # cout, cin_g, groups, k, stride, ...
+    boff = 64 + 72 * n_convs
+    strides = []
+    for i in range(n_blocks):
+        kind, _, c0, c1, _ = struct.unpack_from("<2I3i", blob, boff + 32 * i)
+        if kind == 0:                       # FEARW_STEM: 3x3 s2 (the plan builder halves the crop)
+            strides.append(2)
+        elif kind == 1:                     # FEARW_IR: the depthwise conv carries the stride
+            strides.append(convs[c1][4])
+        elif kind == 2:                     # FEARW_NECK
+            return convs[c0][0], tuple(strides)
+    raise ValueError("weight file without a neck")
+
+
 class FEARNetHIP:
     """FEAR network running on one MI355X through libfear_hip.so.
 
@@ -190,7 +209,7 @@ class FEARNetHIP:
             self._check(self._lib.fear_create(blob, len(blob), int(device), ctypes.byref(self._h)))
         self.weights_path = weights_path
         self.set_max_batch(max_batch)
-        self.feat_channels = 256
+        self.feat_channels, self.trunk_strides = _trunk_geometry(blob)
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, status: int) -> None:
@@ -305,14 +324,23 @@ class FEARNetHIP:
         self._check(self._lib.fear_set_option(self._h, FEAR_OPT_PROFILE, 1 if on else 0))
 
     # ------------------------------------------------------------------ reference API
+    def feature_size(self, hw: int) -> int:
+        """Side of the feature map of an hw x hw crop: hw halved by the stem, then divided by each block's depthwise stride
+        (the plan builder's integer steps)."""
+        for s in self.trunk_strides:
+            hw //= s
+        return hw
+
     @torch.no_grad()
     def get_features(self, crop: torch.Tensor) -> torch.Tensor:
-        """(N,3,H,H) normalised fp32 -> (N,256,H/16,H/16); fear_net.py:63-66."""
+        """(N,3,H,H) normalised fp32 -> (N,C,H/s,H/s), C the neck's channels and s the trunk's total stride (FEAR-XS: 256, 16);
+        fear_net.py:63-66."""
         crop = self._prep(crop, "crop")
         if crop.dim() != 4 or crop.shape[1] != 3 or crop.shape[2] != crop.shape[3]:
             raise ValueError(f"crop must be (N,3,H,H), got {tuple(crop.shape)}")
         n, hw = crop.shape[0], crop.shape[2]
-        out = torch.empty((n, self.feat_channels, hw // 16, hw // 16), dtype=torch.float32, device=self.device)
+        fhw = self.feature_size(hw)
+        out = torch.empty((n, self.feat_channels, fhw, fhw), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             self._check(self._lib.fear_features(self._h, crop.data_ptr(), n, hw, out.data_ptr(), self._stream()))
         return out

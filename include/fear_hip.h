@@ -51,7 +51,8 @@ int fear_destroy(fear_handle* h);
 
 /* FEARNet.get_features (fear_net.py:63-66): trunk + 1x1 neck.
  *   img   : (n, 3, hw, hw) fp32 NCHW, already normalised; hw a multiple of 32 (128 template / 256 search)
- *   out   : (n, 256, hw/16, hw/16) fp32 NCHW                                                  */
+ *   out   : (n, C, hw/s, hw/s) fp32 NCHW: C = the neck's output channels, s = the trunk's total stride (the stem's 2 times
+ *           the depthwise strides of the blocks); FEAR-XS: (n, 256, hw/16, hw/16)                  */
 int fear_features(fear_handle* h, const float* img, int n, int hw, float* out, void* stream);
 
 /* FEARNet.track (fear_net.py:90-96) == get_features(search) + BoxTower (model/blocks.py:174-194).

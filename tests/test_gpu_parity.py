@@ -690,7 +690,8 @@ def test_tracker_device_postprocess_clip(hip_net, golden_dir, smooth):
 
 
 def test_repeated_launches_are_bit_identical():
-    """Race detector: the same B=256 batch through the whole plan 40 times (both arithmetic modes) must give bit-identical
+    """Race detector: the same B=256 batch through the whole plan 40 times (all three arithmetic modes: mode 2 runs the bf16-only
+    kernels, headchain_b, the IO_*_BF16 storage variants of the tile kernels and pw_h_kernel<..., 2>) must give bit-identical
     maps every time — the fused kernels hand data between waves through LDS tiles, barriers and asynchronous copies."""
     from feartracker_amd import FEARNetHIP
     from conftest import WEIGHTS
@@ -698,7 +699,7 @@ def test_repeated_launches_are_bit_identical():
     g = torch.Generator().manual_seed(2024)
     x = norm_u8(torch.randint(0, 256, (256, 3, 256, 256), dtype=torch.uint8, generator=g)).cuda()
     z = net.get_features(norm_u8(torch.randint(0, 256, (256, 3, 128, 128), dtype=torch.uint8, generator=g)).cuda())
-    for mode in (0, 1):
+    for mode in (0, 1, 2):
         net.set_math(mode)
         b0, c0 = net.track_maps(x, z)
         b0, c0 = b0.clone(), c0.clone()
@@ -1096,3 +1097,23 @@ def test_fear_m_at_the_config_size_512_crops():
     # — bf16 storage of the trunk's first activations adds its roundings to the mode's; the identity itself holds on every one of them)
     assert int(need.sum()) >= B // 8
     assert torch.equal(c2.reshape(B, -1).argmax(dim=1)[need], flat.argmax(dim=1)[need])
+
+
+@pytest.mark.parametrize("weights", ("fear_xs", "fear_m"))
+def test_bf16_mode_small_passes_are_batch_invariant(weights):
+    """FEAR_OPT_MATH = 2 on the tiny and small-batch plans (the batch-1 latency path: split tiles, dual-stream sep16 `*_h` head):
+    crop i tracked alone gives the same maps, bit for bit, as crop i in a pass of 3 (tiny plan) and of 17 (small plan) — no
+    kernel may let one crop's data or the pass size reach another crop's arithmetic."""
+    from feartracker_amd import FEARNetHIP
+    from feartracker_amd.hip_backend import WEIGHTS_FEAR_M
+    from conftest import WEIGHTS
+    net = FEARNetHIP(WEIGHTS if weights == "fear_xs" else WEIGHTS_FEAR_M, device=0, max_batch=64)
+    net.set_math(2)
+    g = torch.Generator().manual_seed(77)
+    x = norm_u8(torch.randint(0, 256, (17, 3, 256, 256), dtype=torch.uint8, generator=g)).cuda()
+    z = net.get_features(norm_u8(torch.randint(0, 256, (17, 3, 128, 128), dtype=torch.uint8, generator=g)).cuda())
+    for n in (3, 17):
+        b, c = net.track_maps(x[:n], z[:n])
+        for i in (0, 1, n - 1):
+            bi, ci = net.track_maps(x[i:i + 1], z[i:i + 1])
+            assert torch.equal(bi, b[i:i + 1]) and torch.equal(ci, c[i:i + 1]), (n, i)
