@@ -5,19 +5,16 @@ JIT-compiled at run time.
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(PKG_DIR, "csrc", "fear_engine.hip")
-SRC_TRAIN = os.path.join(PKG_DIR, "csrc", "fear_train.hip")       # head training-step operators, #included by fear_engine.hip
-DEPS = [SRC, SRC_TRAIN, os.path.join(PKG_DIR, "csrc", "fear_chain32.h"), os.path.join(PKG_DIR, "csrc", "fear_train_block.h"), os.path.join(PKG_DIR, "csrc", "fear_train_gemm.h"),
-        os.path.join(PKG_DIR, "csrc", "fear_kernels.h"), os.path.join(PKG_DIR, "csrc", "fear_headchain.h"), os.path.join(PKG_DIR, "csrc", "fear_headchain_b.h"), os.path.join(PKG_DIR, "csrc", "fear_e1pair.h"),
-        os.path.join(PKG_DIR, "csrc", "fear_yuv.h"), os.path.join(PKG_DIR, "csrc", "fear_train_data.h"),
-        os.path.join(os.path.dirname(PKG_DIR), "include", "fear_hip.h"),
-        os.path.join(os.path.dirname(PKG_DIR), "include", "fear_train.h"),
-        os.path.join(os.path.dirname(PKG_DIR), "include", "fearw_format.h")]
+# everything the one translation unit is made of: a header added under csrc/ or include/ is a dependency without being named here
+DEPS = sorted(glob.glob(os.path.join(PKG_DIR, "csrc", "*.h")) + glob.glob(os.path.join(PKG_DIR, "csrc", "*.hip")) +
+              glob.glob(os.path.join(os.path.dirname(PKG_DIR), "include", "*.h")))
 LIB = os.path.join(PKG_DIR, "libfear_hip.so")
 # kernels allowed to spill, and how many VGPRs at most (mangled-name substring -> cap): everything else warns
 KNOWN_SPILLS = {"headchain_kernel": 16, "headchain_b_kernel": 16,

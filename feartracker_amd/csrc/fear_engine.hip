@@ -1430,15 +1430,9 @@ int ensure_workspace(fear_handle* h, const Plan& p) {
 
 template <int MT, bool WKN>
 void launch_pw_nt(int nt, dim3 grid, hipStream_t s, const PwArgs& a) {
-    switch (nt) {
-        case 1: hipLaunchKernelGGL((pw_mfma_kernel<MT, 1, WKN, FEAR_PW_KU(1)>), grid, dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((pw_mfma_kernel<MT, 2, WKN, FEAR_PW_KU(2)>), grid, dim3(256), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((pw_mfma_kernel<MT, 3, WKN, FEAR_PW_KU(3)>), grid, dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((pw_mfma_kernel<MT, 4, WKN, FEAR_PW_KU(4)>), grid, dim3(256), 0, s, a); break;
-        case 6: hipLaunchKernelGGL((pw_mfma_kernel<MT, 6, WKN, FEAR_PW_KU(6)>), grid, dim3(256), 0, s, a); break;
-        case 7: hipLaunchKernelGGL((pw_mfma_kernel<MT, 7, WKN, FEAR_PW_KU(7)>), grid, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL((pw_mfma_kernel<MT, 8, WKN, FEAR_PW_KU(8)>), grid, dim3(256), 0, s, a); break;
-    }
+    dispatch_nt(nt, [&](auto NT) {
+        hipLaunchKernelGGL((pw_mfma_kernel<MT, NT(), WKN, FEAR_PW_KU(NT())>), grid, dim3(256), 0, s, a);
+    });
 }
 
 // FEAR_OPT_MATH = 1 / 2: the same GEMM on the matrix pipe (pw_h_kernel); 4, 2 or 1 channel tiles per pass
@@ -1463,9 +1457,8 @@ int pick_nt(int n_tiles) {
     return 1;
 }
 
-template <int KS, int S>
-void launch_dw(dim3 grid, hipStream_t s, const DwArgs& a) {
-    hipLaunchKernelGGL((dw_conv_kernel<KS, S, 4>), grid, dim3(256), 0, s, a);
+void launch_dw(int k, int stride, dim3 grid, hipStream_t s, const DwArgs& a) {
+    dispatch_ks(k, stride, [&](auto KS, auto S) { hipLaunchKernelGGL((dw_conv_kernel<KS(), S(), 4>), grid, dim3(256), 0, s, a); });
 }
 
 struct Ext {
@@ -1610,10 +1603,7 @@ int run_plan(fear_handle* h, Plan& p, int n, const Ext& ext, hipStream_t s_main,
                 const long strips = (op.Ho + 3) / 4;
                 const long total = (long)n * strips * op.Wo * (op.C / 4);
                 dim3 grid((total + 255) / 256);
-                if (c->k == 3 && c->stride == 1) launch_dw<3, 1>(grid, s, a);
-                else if (c->k == 3 && c->stride == 2) launch_dw<3, 2>(grid, s, a);
-                else if (c->k == 5 && c->stride == 1) launch_dw<5, 1>(grid, s, a);
-                else launch_dw<5, 2>(grid, s, a);
+                launch_dw(c->k, c->stride, grid, s, a);
                 break;
             }
             case OP_IR16: {

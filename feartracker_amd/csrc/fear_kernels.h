@@ -2033,6 +2033,33 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
+// The host's counterparts: a run-time kernel choice handed to `f` as compile-time constants, so that every launcher names its
+// kernel template once — f(std::integral_constant<int, KS>{}, std::integral_constant<int, S>{}) for a depthwise conv's
+// (kernel size, stride) in {3, 5} x {1, 2}, f(std::integral_constant<int, NT>{}) for a pointwise GEMM's channel tiles per pass
+// ({8, 7, 6, 4, 3, 2, 1}: pick_nt).  A new depthwise shape or tile count is added here and nowhere else.
+template <class F>
+inline void dispatch_ks(int k, int stride, F&& f) {
+    using std::integral_constant;
+    if (k == 3 && stride == 1) f(integral_constant<int, 3>{}, integral_constant<int, 1>{});
+    else if (k == 3) f(integral_constant<int, 3>{}, integral_constant<int, 2>{});
+    else if (stride == 1) f(integral_constant<int, 5>{}, integral_constant<int, 1>{});
+    else f(integral_constant<int, 5>{}, integral_constant<int, 2>{});
+}
+
+template <class F>
+inline void dispatch_nt(int nt, F&& f) {
+    using std::integral_constant;
+    switch (nt) {
+        case 1: f(integral_constant<int, 1>{}); break;
+        case 2: f(integral_constant<int, 2>{}); break;
+        case 3: f(integral_constant<int, 3>{}); break;
+        case 4: f(integral_constant<int, 4>{}); break;
+        case 6: f(integral_constant<int, 6>{}); break;
+        case 7: f(integral_constant<int, 7>{}); break;
+        default: f(integral_constant<int, 8>{}); break;
+    }
+}
+
 // ================================================================================================
 // sep16 for a handful of crops (the batch-1 tracker): one 16-channel output slice of ROWS map rows per workgroup — the N-split
 // launch of sep16_kernel<CIN, 16, KS> cut once more, over rows — with one row per wave and nothing fetched inside the chunk loop.

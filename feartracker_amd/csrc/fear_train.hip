@@ -1100,19 +1100,17 @@ dim3 train_pw_grid(long M, int n_tiles, int* nt_out) {
 
 template <bool WKN>
 void launch_pw(int nt, dim3 grid, hipStream_t s, const PwArgs& a) {
-    switch (nt) {
-        case 1: hipLaunchKernelGGL((pw_mfma_kernel<2, 1, WKN, FEAR_PW_KU(1)>), grid, dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((pw_mfma_kernel<2, 2, WKN, FEAR_PW_KU(2)>), grid, dim3(256), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((pw_mfma_kernel<2, 3, WKN, FEAR_PW_KU(3)>), grid, dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((pw_mfma_kernel<2, 4, WKN, FEAR_PW_KU(4)>), grid, dim3(256), 0, s, a); break;
-        case 6: hipLaunchKernelGGL((pw_mfma_kernel<2, 6, WKN, FEAR_PW_KU(6)>), grid, dim3(256), 0, s, a); break;
-        case 7: hipLaunchKernelGGL((pw_mfma_kernel<2, 7, WKN, FEAR_PW_KU(7)>), grid, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL((pw_mfma_kernel<2, 8, WKN, FEAR_PW_KU(8)>), grid, dim3(256), 0, s, a); break;
-    }
+    dispatch_nt(nt, [&](auto NT) {
+        hipLaunchKernelGGL((pw_mfma_kernel<2, NT(), WKN, FEAR_PW_KU(NT())>), grid, dim3(256), 0, s, a);
+    });
 }
 
 // rows are read and written as float4s: every leading dimension is a multiple of 4 floats and covers its row
 bool ld_ok(int ld, int cols) { return ld >= cols && ld % 4 == 0; }
+// M rows of C channels for the column reductions (a workgroup holds a row's float4 quads: at most 256 of them)
+bool bn_shape_ok(long M, int C) { return M > 0 && C >= 4 && C % 4 == 0 && C <= 1024; }
+// M rows through a pointwise conv of K input and N output channels (float4 loads of both operands)
+bool pw_shape_ok(long M, int K, int N) { return M > 0 && K >= 4 && K % 4 == 0 && N >= 4 && N % 4 == 0; }
 
 #ifndef FEAR_COL_BLOCKS
 #define FEAR_COL_BLOCKS 1024   // most workgroups a column reduction is cut into (2048 measured no faster, and slows the depthwise weight gradient's slice sums)
@@ -1126,6 +1124,34 @@ int col_rows_per_block(long M) {
     return r;
 }
 int col_blocks(long M) { const int r = col_rows_per_block(M); return (int)((M + r - 1) / r); }
+size_t col_partial_bytes(long M, int C) { return (size_t)col_blocks(M) * 2 * C * sizeof(double); }
+
+// The two launches of a column reduction: their grid arithmetic lives in these two helpers and nowhere else.
+// launch_col_reduce: `a` holds the operands of MODE; the sums of the col_blocks(M) workgroups go to partial [blocks][2][C] float64.
+// Returns the blocks, which is what the finalize behind it adds up.
+template <int MODE>
+int launch_col_reduce(ColArgs a, double* partial, long M, int C, hipStream_t s) {
+    a.partial = partial; a.M = M; a.C = C; a.rpb = col_rows_per_block(M);
+    const int blocks = col_blocks(M);
+    hipLaunchKernelGGL(col_reduce_kernel<MODE>, dim3(blocks), dim3(256), 0, s, a);
+    return blocks;
+}
+// launch_col_finalize: partial [f.blocks][2][f.C] -> the outputs of f.mode (ColFinArgs), 16 columns per workgroup
+void launch_col_finalize(const ColFinArgs& f, hipStream_t s) {
+    hipLaunchKernelGGL(col_finalize_kernel, dim3((f.C + 15) / 16), dim3(1024), 0, s, f);
+}
+// the fields every mode reads (M = the row count behind the sums: modes 0 and 4 divide by it); the caller adds its mode's outputs
+ColFinArgs col_fin(const double* partial, int blocks, int C, int mode, double M) {
+    ColFinArgs f{};
+    f.partial = partial; f.blocks = blocks; f.C = C; f.mode = mode; f.M = M;
+    return f;
+}
+// column-sum partials -> the two float64 sums [2][C] (what a later finalize, or the ranks' all-reduce in front of it, takes)
+void finalize_sums(const double* partial, int blocks, int C, double* sums, hipStream_t s) {
+    ColFinArgs f = col_fin(partial, blocks, C, 3, 0.0);
+    f.dsum = sums;
+    launch_col_finalize(f, s);
+}
 
 // row slices of the pointwise weight gradient: 1024 rows each, but never more than 256 slices (the partials are
 // [slices][N][K] floats; at the trunk's 128x128 maps a batch has millions of rows)
@@ -1138,6 +1164,26 @@ long wgrad_rows_per_slice(long M) {
     return r;
 }
 int wgrad_slices(long M) { const long r = wgrad_rows_per_slice(M); return (int)((M + r - 1) / r); }
+
+// Row slices of one weight-gradient launch over M rows.  Few output tiles (the 16 x 16 maps' layers: 2-22 tiles x 8-32 slices of
+// 1 024 rows) leave most of the 256 CUs idle while every wave walks its 16 steps of 64 dependent MFMAs: such launches sat on a 31 us
+// floor whatever their size.  So the rows are cut finer than wgrad_rows_per_slice — down to 256 per slice — until `tiles` x slices
+// is ~768 workgroups, up to `max_slices` slices and as many as `ws_bytes` of workspace hold partials of `partial_elems` floats.
+struct WgradPlan { long rows_per_slice; int slices; };
+WgradPlan wgrad_plan(long M, long tiles, size_t partial_elems, long max_slices, size_t ws_bytes) {
+    long rows = wgrad_rows_per_slice(M);
+    const long want = (768 + tiles - 1) / tiles;
+    long cap_ws = (long)(ws_bytes / (partial_elems * sizeof(float)));
+    if (cap_ws < 1) cap_ws = 1;      // a workspace smaller than one partial: no finer slicing; the caller's size check reports it
+    long sl = (M + rows - 1) / rows;
+    if (want > sl) sl = want;
+    if (sl > max_slices) sl = max_slices;
+    if (sl > cap_ws) sl = cap_ws;
+    long rps = ((M + sl - 1) / sl + 63) / 64 * 64;
+    if (rps < 256) rps = 256;
+    if (rps < rows) rows = rps;
+    return WgradPlan{rows, (int)((M + rows - 1) / rows)};
+}
 
 // ================================================================================================
 // Fused conv + BatchNorm operators of the trunk's training step.
@@ -1478,6 +1524,10 @@ __global__ __launch_bounds__(256) void bn_act_kernel(BnActArgs a) {
     *reinterpret_cast<f32x4*>(a.Y + r * a.ldy + c) = y;
 }
 
+void launch_pw_stat(const PwStatArgs& a, dim3 grid, int nt, hipStream_t s) {
+    dispatch_nt(nt, [&](auto NT) { hipLaunchKernelGGL((pw_stat_kernel<NT()>), grid, dim3(256), 0, s, a); });
+}
+
 #include "fear_train_gemm.h"
 
 }  // namespace
@@ -1496,7 +1546,7 @@ int fear_pw_forward(const float* x, int ldx, const float* w, const float* bias, 
                     void* stream) {
     if (M == 0) return FEAR_TRAIN_OK;
     if (!x || !w || !y) return FEAR_TRAIN_ERR_NULL;
-    if (M < 0 || K < 4 || K % 4 || N < 4 || N % 4 || M > 0x7fffffffL || !ld_ok(ldx, K) || !ld_ok(ldy, N)) return FEAR_TRAIN_ERR_SHAPE;
+    if (!pw_shape_ok(M, K, N) || M > 0x7fffffffL || !ld_ok(ldx, K) || !ld_ok(ldy, N)) return FEAR_TRAIN_ERR_SHAPE;
     if (gemm_lds_applies(M, K, N)) {      // the head's 256 / 320-channel GEMMs at 16 x 16: LDS-staged, pipelined (fear_train_gemm.h)
         GemmArgs g{};
         g.X = x; g.ldx = ldx; g.W = w; g.bias = bias; g.Y = y; g.ldy = ldy; g.M = (int)M; g.K = K; g.N = N;
@@ -1517,7 +1567,7 @@ int fear_pw_backward_data(const float* dy, int lddy, const float* w, const float
                           int K, int N, void* stream) {
     if (M == 0) return FEAR_TRAIN_OK;
     if (!dy || !w || !dx) return FEAR_TRAIN_ERR_NULL;
-    if (M < 0 || K < 4 || K % 4 || N < 4 || N % 4 || M > 0x7fffffffL || !ld_ok(lddy, N) || !ld_ok(lddx, K) || (add && !ld_ok(ldadd, K)))
+    if (!pw_shape_ok(M, K, N) || M > 0x7fffffffL || !ld_ok(lddy, N) || !ld_ok(lddx, K) || (add && !ld_ok(ldadd, K)))
         return FEAR_TRAIN_ERR_SHAPE;
     // dX[m][k] = sum_n dY[m][n] W[n][k]: a pointwise conv with "input channels" N, "output channels" K and the weight matrix
     // read K-major (W[n][k] row-major IS the K-major layout of that conv)
@@ -1558,18 +1608,9 @@ static int wgrad_impl(const float* dy, int lddy, long dy_crop_stride, const floa
     if (crops == 1 && N <= 32 && K > 32 && !stem && !(bn && bn->mask_a) && (!bn || bn->E)) {
         a.dY = x; a.lddy = ldx; a.N = K; a.X = dy; a.ldx = lddy; a.K = N;
         a.n_tiles = (K + 63) / 64; a.k_tiles = 1;
-        a.rows_per_slice = wgrad_rows_per_slice(M);
-        const long want = (768 + a.n_tiles - 1) / a.n_tiles;
-        long cap_ws = workspace ? (long)(ws_bytes / ((size_t)N * K * sizeof(float))) : 1;
-        if (cap_ws < 1) cap_ws = 1;
-        long sl = (M + a.rows_per_slice - 1) / a.rows_per_slice;
-        if (want > sl) sl = want;
-        if (sl > 1024) sl = 1024;
-        if (sl > cap_ws) sl = cap_ws;
-        long rps = ((M + sl - 1) / sl + 63) / 64 * 64;
-        if (rps < 256) rps = 256;
-        if (rps < a.rows_per_slice) a.rows_per_slice = rps;
-        const int slices = (int)((M + a.rows_per_slice - 1) / a.rows_per_slice);
+        const WgradPlan plan = wgrad_plan(M, a.n_tiles, (size_t)N * K, 1024, workspace ? ws_bytes : 0);
+        a.rows_per_slice = plan.rows_per_slice;
+        const int slices = plan.slices;
         if (slices == 1) {
             a.P = dw;
         } else {
@@ -1589,28 +1630,15 @@ static int wgrad_impl(const float* dy, int lddy, long dy_crop_stride, const floa
     //  barriers-per-stage floor — 29 us measured — lose against the 14 us of the register-only kernel there)
     const bool lds_tile = crops == 1 && K > 32 && N >= 32 && M >= 16384;
     if (lds_tile) { a.n_tiles = (N + 127) / 128; a.k_tiles = (K + 127) / 128; }
-    a.rows_per_slice = crops > 1 ? M : wgrad_rows_per_slice(M);
-    if (crops == 1) {
-        // few output tiles (the 16 x 16 maps' layers: 2-22 tiles x 8-32 slices of 1 024 rows) leave most of the 256 CUs idle while
-        // every wave walks its 16 steps of 64 dependent MFMAs: such launches sat on a 31 us floor whatever their size.  Cut the rows
-        // finer — down to 256 per slice — until there are ~768 workgroups, as far as the caller's workspace holds the partials.
-        const long tiles = K <= 32 ? a.n_tiles : (long)a.n_tiles * a.k_tiles;
-        const long want = (768 + tiles - 1) / tiles;
-        long cap_ws = workspace ? (long)(ws_bytes / ((size_t)N * K * sizeof(float))) : 1;
-        if (cap_ws < 1) cap_ws = 1;      // a workspace smaller than one partial: no finer slicing; the size check below reports it
-        long sl = (M + a.rows_per_slice - 1) / a.rows_per_slice;
-        if (want > sl) sl = want;
-        // at most 256 slices — 1 024 where the partial is small (N * K <= 8 192: the stem and the 16-32-channel layers of the
-        // 128 x 128 / 64 x 64 maps): those layers have millions of rows and ONE or two output tiles, 256 workgroups streamed them
-        // at 1.1 TB/s (the stem's weight gradient: 425 us for 500 MB)
-        const long max_sl = (long)N * K <= 8192 ? 1024 : 256;
-        if (sl > max_sl) sl = max_sl;
-        if (sl > cap_ws) sl = cap_ws;
-        long rps = ((M + sl - 1) / sl + 63) / 64 * 64;
-        if (rps < 256) rps = 256;
-        if (rps < a.rows_per_slice) a.rows_per_slice = rps;
-    }
-    const int slices = (int)((M + a.rows_per_slice - 1) / a.rows_per_slice);
+    // (per-crop problems are one slice each; one problem is cut by wgrad_plan)
+    // at most 256 slices — 1 024 where the partial is small (N * K <= 8 192: the stem and the 16-32-channel layers of the
+    // 128 x 128 / 64 x 64 maps): those layers have millions of rows and ONE or two output tiles, 256 workgroups streamed them
+    // at 1.1 TB/s (the stem's weight gradient: 425 us for 500 MB)
+    const WgradPlan plan = crops > 1 ? WgradPlan{M, 1}
+                                     : wgrad_plan(M, K <= 32 ? a.n_tiles : (long)a.n_tiles * a.k_tiles, (size_t)N * K,
+                                                  (long)N * K <= 8192 ? 1024 : 256, workspace ? ws_bytes : 0);
+    a.rows_per_slice = plan.rows_per_slice;
+    const int slices = plan.slices;
     const size_t need = (size_t)slices * crops * N * K * sizeof(float);
     if (slices == 1) {
         a.P = dw;
@@ -1634,23 +1662,22 @@ static int wgrad_impl(const float* dy, int lddy, long dy_crop_stride, const floa
 int fear_pw_backward_weight(const float* dy, int lddy, const float* x, int ldx, float* dw, float* workspace, size_t ws_bytes,
                             long M, int K, int N, void* stream) {
     if (!dy || !x || !dw) return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || K < 4 || K % 4 || N < 4 || N % 4 || !ld_ok(lddy, N) || !ld_ok(ldx, K)) return FEAR_TRAIN_ERR_SHAPE;    // float4 loads of both operands
+    if (!pw_shape_ok(M, K, N) || !ld_ok(lddy, N) || !ld_ok(ldx, K)) return FEAR_TRAIN_ERR_SHAPE;    // float4 loads of both operands
     return wgrad_impl(dy, lddy, 0, x, ldx, 0, dw, workspace, ws_bytes, M, K, N, 1, static_cast<hipStream_t>(stream));
 }
 
 int fear_col_sum(const float* dy, int lddy, float* out, float* workspace, size_t ws_bytes, long M, int C, void* stream) {
     if (!dy || !out || !workspace) return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || C < 4 || C % 4 || C > 1024) return FEAR_TRAIN_ERR_SHAPE;
+    if (!bn_shape_ok(M, C)) return FEAR_TRAIN_ERR_SHAPE;
     if (!ld_ok(lddy, C)) return FEAR_TRAIN_ERR_SHAPE;      // float4 rows
-    const int blocks = col_blocks(M);
-    if (ws_bytes < (size_t)blocks * 2 * C * sizeof(double)) return FEAR_TRAIN_ERR_WORKSPACE;
+    if (ws_bytes < col_partial_bytes(M, C)) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    double* partial = reinterpret_cast<double*>(workspace);
     ColArgs a{};
-    a.A = dy; a.lda = lddy; a.partial = reinterpret_cast<double*>(workspace); a.M = M; a.C = C; a.rpb = col_rows_per_block(M);
-    hipLaunchKernelGGL(col_reduce_kernel<2>, dim3(blocks), dim3(256), 0, s, a);
-    ColFinArgs f{};
-    f.partial = reinterpret_cast<const double*>(workspace); f.out1 = out; f.out2 = nullptr; f.blocks = blocks; f.C = C; f.mode = 2; f.M = (double)M; f.rpb = col_rows_per_block(M);
-    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(1024), 0, s, f);
+    a.A = dy; a.lda = lddy;
+    ColFinArgs f = col_fin(partial, launch_col_reduce<2>(a, partial, M, C, s), C, 2, (double)M);
+    f.out1 = out;
+    launch_col_finalize(f, s);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }
@@ -1663,10 +1690,7 @@ static int dw_impl(const float* x, int ldx, const float* w, const float* bias, f
     const long strips = (a.Ho + 3) / 4;
     const long total = (long)B * strips * a.Wo * (C / 4);
     dim3 grid((unsigned)((total + 255) / 256));
-    if (k == 3 && stride == 1) hipLaunchKernelGGL((dw_conv_kernel<3, 1, 4>), grid, dim3(256), 0, s, a);
-    else if (k == 3) hipLaunchKernelGGL((dw_conv_kernel<3, 2, 4>), grid, dim3(256), 0, s, a);
-    else if (stride == 1) hipLaunchKernelGGL((dw_conv_kernel<5, 1, 4>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((dw_conv_kernel<5, 2, 4>), grid, dim3(256), 0, s, a);
+    dispatch_ks(k, stride, [&](auto KS, auto S) { hipLaunchKernelGGL((dw_conv_kernel<KS(), S(), 4>), grid, dim3(256), 0, s, a); });
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }
@@ -1691,10 +1715,7 @@ static int dw_dgrad_impl(const float* dy, int lddy, const float* w_taps, float* 
     a.dY = dy; a.Wt = w_taps; a.dX = dx; a.H = H; a.W = W; a.Ho = H / stride; a.Wo = W / stride; a.C = C; a.lddy = lddy; a.lddx = lddx;
     a.total = (long)B * H * W * (C / 4);
     dim3 grid((unsigned)((a.total + 255) / 256));
-    if (k == 3 && stride == 1) hipLaunchKernelGGL((dw_dgrad_kernel<3, 1>), grid, dim3(256), 0, s, a);
-    else if (k == 3) hipLaunchKernelGGL((dw_dgrad_kernel<3, 2>), grid, dim3(256), 0, s, a);
-    else if (stride == 1) hipLaunchKernelGGL((dw_dgrad_kernel<5, 1>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((dw_dgrad_kernel<5, 2>), grid, dim3(256), 0, s, a);
+    dispatch_ks(k, stride, [&](auto KS, auto S) { hipLaunchKernelGGL((dw_dgrad_kernel<KS(), S()>), grid, dim3(256), 0, s, a); });
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }
@@ -1718,10 +1739,7 @@ static int dw_wgrad_impl(const float* dy, int lddy, const float* x, int ldx, flo
     DwWgradArgs a{};
     a.dY = dy; a.X = x; a.partial = workspace; a.pixels = pixels; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.C = C; a.lddy = lddy; a.ldx = ldx; a.rpb = col_rows_per_block(pixels);
     a.act_a = act_a; a.act_b = act_b; a.act_relu = act_relu;
-    if (k == 3 && stride == 1) hipLaunchKernelGGL((dw_wgrad_kernel<3, 1>), dim3(blocks), dim3(256), 0, s, a);
-    else if (k == 3) hipLaunchKernelGGL((dw_wgrad_kernel<3, 2>), dim3(blocks), dim3(256), 0, s, a);
-    else if (stride == 1) hipLaunchKernelGGL((dw_wgrad_kernel<5, 1>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((dw_wgrad_kernel<5, 2>), dim3(blocks), dim3(256), 0, s, a);
+    dispatch_ks(k, stride, [&](auto KS, auto S) { hipLaunchKernelGGL((dw_wgrad_kernel<KS(), S()>), dim3(blocks), dim3(256), 0, s, a); });
     launch_slice_sum(workspace, dw_taps, count, blocks, s);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
@@ -1751,18 +1769,16 @@ int fear_bn_train_forward(const float* x, int ldx, const float* gamma, const flo
                           float* rstd, float* running_mean, float* running_var, double momentum, double eps, long M, int C,
                           int relu, float* workspace, size_t ws_bytes, void* stream) {
     if (!x || !gamma || !beta || !y || !mean || !rstd || !workspace) return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || C < 4 || C % 4 || C > 1024) return FEAR_TRAIN_ERR_SHAPE;
+    if (!bn_shape_ok(M, C)) return FEAR_TRAIN_ERR_SHAPE;
     if (!ld_ok(ldx, C) || !ld_ok(ldy, C)) return FEAR_TRAIN_ERR_SHAPE;      // float4 rows
-    const int blocks = col_blocks(M);
-    if (ws_bytes < (size_t)blocks * 2 * C * sizeof(double)) return FEAR_TRAIN_ERR_WORKSPACE;
+    if (ws_bytes < col_partial_bytes(M, C)) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    double* partial = reinterpret_cast<double*>(workspace);
     ColArgs a{};
-    a.A = x; a.lda = ldx; a.partial = reinterpret_cast<double*>(workspace); a.M = M; a.C = C; a.rpb = col_rows_per_block(M);
-    hipLaunchKernelGGL(col_reduce_kernel<0>, dim3(blocks), dim3(256), 0, s, a);
-    ColFinArgs f{};
-    f.partial = reinterpret_cast<const double*>(workspace); f.out1 = mean; f.out2 = rstd; f.running_mean = running_mean; f.running_var = running_var;
-    f.blocks = blocks; f.C = C; f.mode = 0; f.M = (double)M; f.rpb = col_rows_per_block(M); f.eps = eps; f.momentum = momentum;
-    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(1024), 0, s, f);
+    a.A = x; a.lda = ldx;
+    ColFinArgs f = col_fin(partial, launch_col_reduce<0>(a, partial, M, C, s), C, 0, (double)M);
+    f.out1 = mean; f.out2 = rstd; f.running_mean = running_mean; f.running_var = running_var; f.eps = eps; f.momentum = momentum;
+    launch_col_finalize(f, s);
     BnApplyArgs b{};
     b.X = x; b.mean = mean; b.rstd = rstd; b.gamma = gamma; b.beta = beta; b.Y = y; b.M = M; b.C = C; b.ldx = ldx; b.ldy = ldy;
     b.relu = relu;
@@ -1776,18 +1792,16 @@ int fear_bn_train_backward(const float* dy, int lddy, const float* y_act, int ld
                            const float* rstd, const float* gamma, float* dx, int lddx, float* dgamma, float* dbeta, long M,
                            int C, float* workspace, size_t ws_bytes, void* stream) {
     if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || !workspace) return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || C < 4 || C % 4 || C > 1024) return FEAR_TRAIN_ERR_SHAPE;
+    if (!bn_shape_ok(M, C)) return FEAR_TRAIN_ERR_SHAPE;
     if (!ld_ok(lddy, C) || !ld_ok(ldx, C) || !ld_ok(lddx, C) || (y_act && !ld_ok(ldy, C))) return FEAR_TRAIN_ERR_SHAPE;      // float4 rows
-    const int blocks = col_blocks(M);
-    if (ws_bytes < (size_t)blocks * 2 * C * sizeof(double)) return FEAR_TRAIN_ERR_WORKSPACE;
+    if (ws_bytes < col_partial_bytes(M, C)) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    double* partial = reinterpret_cast<double*>(workspace);
     ColArgs a{};
     a.A = dy; a.lda = lddy; a.Yact = y_act; a.ldy = ldy; a.X = x; a.ldx = ldx; a.mean = mean; a.rstd = rstd;
-    a.partial = reinterpret_cast<double*>(workspace); a.M = M; a.C = C; a.rpb = col_rows_per_block(M);
-    hipLaunchKernelGGL(col_reduce_kernel<1>, dim3(blocks), dim3(256), 0, s, a);
-    ColFinArgs f{};
-    f.partial = reinterpret_cast<const double*>(workspace); f.out1 = dbeta; f.out2 = dgamma; f.blocks = blocks; f.C = C; f.mode = 1; f.M = (double)M; f.rpb = col_rows_per_block(M);
-    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(1024), 0, s, f);
+    ColFinArgs f = col_fin(partial, launch_col_reduce<1>(a, partial, M, C, s), C, 1, (double)M);
+    f.out1 = dbeta; f.out2 = dgamma;
+    launch_col_finalize(f, s);
     BnBwdArgs b{};
     b.dY = dy; b.Yact = y_act; b.X = x; b.mean = mean; b.rstd = rstd; b.gamma = gamma; b.sum_g = dbeta; b.sum_gx = dgamma;
     b.dX = dx; b.M = M; b.C = C; b.lddy = lddy; b.ldy = ldy; b.ldx = ldx; b.lddx = lddx;
@@ -1798,17 +1812,10 @@ int fear_bn_train_backward(const float* dy, int lddy, const float* y_act, int ld
 }
 
 // ---- fused conv + BatchNorm operators (see "Fused conv + BatchNorm operators" above) ----------------------------------------
-static int finalize_sums(const double* partial, int blocks, int C, double* sums, hipStream_t s) {
-    ColFinArgs f{};
-    f.partial = partial; f.dsum = sums; f.blocks = blocks; f.C = C; f.mode = 3;
-    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(1024), 0, s, f);
-    return 0;
-}
-
 int fear_pw_forward_stats(const float* x, int ldx, const float* in_a, const float* in_b, int in_relu, const float* w, float* y,
                           int ldy, long M, int K, int N, double* sums, float* workspace, size_t ws_bytes, void* stream) {
     if (!x || !w || !y || !sums || !workspace || (in_a && !in_b)) return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || K < 4 || K % 4 || N < 4 || N % 4 || N > 1024 || M > 0x7fffffffL || !ld_ok(ldx, K) || !ld_ok(ldy, N)) return FEAR_TRAIN_ERR_SHAPE;
+    if (!pw_shape_ok(M, K, N) || N > 1024 || M > 0x7fffffffL || !ld_ok(ldx, K) || !ld_ok(ldy, N)) return FEAR_TRAIN_ERR_SHAPE;
     const int blocks = (int)((M + 127) / 128);
     if (ws_bytes < (size_t)blocks * 2 * N * sizeof(double)) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1817,15 +1824,7 @@ int fear_pw_forward_stats(const float* x, int ldx, const float* in_a, const floa
     a.in.a = in_a; a.in.b = in_b; a.in.relu = in_relu;
     a.partial = reinterpret_cast<double*>(workspace);
     dim3 grid((unsigned)blocks);
-    switch (train_pick_nt((N + 15) / 16)) {
-        case 1: hipLaunchKernelGGL((pw_stat_kernel<1>), grid, dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((pw_stat_kernel<2>), grid, dim3(256), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((pw_stat_kernel<3>), grid, dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((pw_stat_kernel<4>), grid, dim3(256), 0, s, a); break;
-        case 6: hipLaunchKernelGGL((pw_stat_kernel<6>), grid, dim3(256), 0, s, a); break;
-        case 7: hipLaunchKernelGGL((pw_stat_kernel<7>), grid, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL((pw_stat_kernel<8>), grid, dim3(256), 0, s, a); break;
-    }
+    launch_pw_stat(a, grid, train_pick_nt((N + 15) / 16), s);
     finalize_sums(a.partial, blocks, N, sums, s);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
@@ -1847,10 +1846,7 @@ int fear_dw_forward_stats(const float* x, int ldx, const float* in_a, const floa
     a.partial = reinterpret_cast<double*>(workspace);
     hipStream_t s = static_cast<hipStream_t>(stream);
     dim3 grid((unsigned)blocks);
-    if (k == 3 && stride == 1) hipLaunchKernelGGL((dw_stat_kernel<3, 1, 4>), grid, dim3(256), 0, s, a);
-    else if (k == 3) hipLaunchKernelGGL((dw_stat_kernel<3, 2, 4>), grid, dim3(256), 0, s, a);
-    else if (stride == 1) hipLaunchKernelGGL((dw_stat_kernel<5, 1, 4>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((dw_stat_kernel<5, 2, 4>), grid, dim3(256), 0, s, a);
+    dispatch_ks(k, stride, [&](auto KS, auto S) { hipLaunchKernelGGL((dw_stat_kernel<KS(), S(), 4>), grid, dim3(256), 0, s, a); });
     finalize_sums(a.partial, (int)blocks, C, sums, s);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
@@ -1893,16 +1889,14 @@ int fear_bn_backward_reduce_x(const float* dy, int lddy, const float* x, int ldx
                               const float* mean, const float* rstd, double* sums, long M, int C, float* workspace, size_t ws_bytes,
                               void* stream) {
     if (!dy || !x || !mean || !rstd || !sums || !workspace || (relu && (!act_a || !act_b))) return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || C < 4 || C % 4 || C > 1024 || !ld_ok(lddy, C) || !ld_ok(ldx, C)) return FEAR_TRAIN_ERR_SHAPE;
-    const int blocks = col_blocks(M);
-    if (ws_bytes < (size_t)blocks * 2 * C * sizeof(double)) return FEAR_TRAIN_ERR_WORKSPACE;
+    if (!bn_shape_ok(M, C) || !ld_ok(lddy, C) || !ld_ok(ldx, C)) return FEAR_TRAIN_ERR_SHAPE;
+    if (ws_bytes < col_partial_bytes(M, C)) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     ColArgs a{};
     a.A = dy; a.lda = lddy; a.X = x; a.ldx = ldx; a.mean = mean; a.rstd = rstd;
     a.act_a = relu ? act_a : nullptr; a.act_b = relu ? act_b : nullptr;
-    a.partial = reinterpret_cast<double*>(workspace); a.M = M; a.C = C; a.rpb = col_rows_per_block(M);
-    hipLaunchKernelGGL(col_reduce_kernel<1>, dim3(blocks), dim3(256), 0, s, a);
-    finalize_sums(a.partial, blocks, C, sums, s);
+    double* partial = reinterpret_cast<double*>(workspace);
+    finalize_sums(partial, launch_col_reduce<1>(a, partial, M, C, s), C, sums, s);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }
@@ -1914,7 +1908,7 @@ int fear_bn_backward_apply_x(const float* dy, int lddy, const float* x, int ldx,
     if (!dy || !x || !mean || !rstd || !gamma || !sums_all || !sums_local || !dx || !dgamma || !dbeta || !workspace ||
         (relu && (!act_a || !act_b)))
         return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || C < 4 || C % 4 || C > 1024 || !(count >= (double)M) || !ld_ok(lddy, C) || !ld_ok(ldx, C) || !ld_ok(lddx, C))
+    if (!bn_shape_ok(M, C) || !(count >= (double)M) || !ld_ok(lddy, C) || !ld_ok(ldx, C) || !ld_ok(lddx, C))
         return FEAR_TRAIN_ERR_SHAPE;
     if (ws_bytes < (size_t)2 * C * sizeof(float)) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1935,7 +1929,7 @@ int fear_bn_backward_apply_x(const float* dy, int lddy, const float* x, int ldx,
 int fear_pw_backward_weight_act(const float* dy, int lddy, const float* x, int ldx, const float* in_a, const float* in_b, int in_relu,
                                 float* dw, float* workspace, size_t ws_bytes, long M, int K, int N, void* stream) {
     if (!dy || !x || !dw || (in_a && !in_b)) return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || K < 4 || K % 4 || N < 4 || N % 4 || !ld_ok(lddy, N) || !ld_ok(ldx, K)) return FEAR_TRAIN_ERR_SHAPE;
+    if (!pw_shape_ok(M, K, N) || !ld_ok(lddy, N) || !ld_ok(ldx, K)) return FEAR_TRAIN_ERR_SHAPE;
     return wgrad_impl(dy, lddy, 0, x, ldx, 0, dw, workspace, ws_bytes, M, K, N, 1, static_cast<hipStream_t>(stream), in_a, in_b, in_relu);
 }
 
@@ -1957,18 +1951,16 @@ int fear_bn_train_forward_ab(const float* x, int ldx, const float* gamma, const 
                              float* running_var, double momentum, double eps, long M, int C, float* workspace, size_t ws_bytes,
                              void* stream) {
     if (!x || !gamma || !beta || !y || !mean || !rstd || !a_out || !b_out || !workspace) return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || C < 4 || C % 4 || C > 1024 || !ld_ok(ldx, C) || !ld_ok(ldy, C) || (residual && !ld_ok(ldr, C))) return FEAR_TRAIN_ERR_SHAPE;
-    const int blocks = col_blocks(M);
-    if (ws_bytes < (size_t)blocks * 2 * C * sizeof(double)) return FEAR_TRAIN_ERR_WORKSPACE;
+    if (!bn_shape_ok(M, C) || !ld_ok(ldx, C) || !ld_ok(ldy, C) || (residual && !ld_ok(ldr, C))) return FEAR_TRAIN_ERR_SHAPE;
+    if (ws_bytes < col_partial_bytes(M, C)) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    double* partial = reinterpret_cast<double*>(workspace);
     ColArgs a{};
-    a.A = x; a.lda = ldx; a.partial = reinterpret_cast<double*>(workspace); a.M = M; a.C = C; a.rpb = col_rows_per_block(M);
-    hipLaunchKernelGGL(col_reduce_kernel<0>, dim3(blocks), dim3(256), 0, s, a);
-    ColFinArgs f{};
-    f.partial = reinterpret_cast<const double*>(workspace); f.out1 = mean; f.out2 = rstd; f.running_mean = running_mean; f.running_var = running_var;
+    a.A = x; a.lda = ldx;
+    ColFinArgs f = col_fin(partial, launch_col_reduce<0>(a, partial, M, C, s), C, 0, (double)M);
+    f.out1 = mean; f.out2 = rstd; f.running_mean = running_mean; f.running_var = running_var; f.eps = eps; f.momentum = momentum;
     f.gamma = gamma; f.beta = beta; f.out_a = a_out; f.out_b = b_out;
-    f.blocks = blocks; f.C = C; f.mode = 0; f.M = (double)M; f.rpb = a.rpb; f.eps = eps; f.momentum = momentum;
-    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(1024), 0, s, f);
+    launch_col_finalize(f, s);
     BnActArgs k{};
     k.X = x; k.R = residual; k.Y = y; k.in.a = a_out; k.in.b = b_out; k.in.relu = relu; k.M = M; k.C = C; k.ldx = ldx; k.ldr = ldr; k.ldy = ldy;
     const long n4 = M * (C / 4);
@@ -1982,18 +1974,16 @@ int fear_bn_train_backward_x(const float* dy, int lddy, const float* x, int ldx,
                              long M, int C, float* workspace, size_t ws_bytes, void* stream) {
     if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || !workspace || (relu && (!act_a || !act_b)))
         return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || C < 4 || C % 4 || C > 1024 || !ld_ok(lddy, C) || !ld_ok(ldx, C) || !ld_ok(lddx, C)) return FEAR_TRAIN_ERR_SHAPE;
-    const int blocks = col_blocks(M);
-    if (ws_bytes < (size_t)blocks * 2 * C * sizeof(double)) return FEAR_TRAIN_ERR_WORKSPACE;
+    if (!bn_shape_ok(M, C) || !ld_ok(lddy, C) || !ld_ok(ldx, C) || !ld_ok(lddx, C)) return FEAR_TRAIN_ERR_SHAPE;
+    if (ws_bytes < col_partial_bytes(M, C)) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     ColArgs a{};
     a.A = dy; a.lda = lddy; a.X = x; a.ldx = ldx; a.mean = mean; a.rstd = rstd;
     a.act_a = relu ? act_a : nullptr; a.act_b = relu ? act_b : nullptr;
-    a.partial = reinterpret_cast<double*>(workspace); a.M = M; a.C = C; a.rpb = col_rows_per_block(M);
-    hipLaunchKernelGGL(col_reduce_kernel<1>, dim3(blocks), dim3(256), 0, s, a);
-    ColFinArgs f{};
-    f.partial = reinterpret_cast<const double*>(workspace); f.out1 = dbeta; f.out2 = dgamma; f.blocks = blocks; f.C = C; f.mode = 1; f.M = (double)M; f.rpb = a.rpb;
-    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(1024), 0, s, f);
+    double* partial = reinterpret_cast<double*>(workspace);
+    ColFinArgs f = col_fin(partial, launch_col_reduce<1>(a, partial, M, C, s), C, 1, (double)M);
+    f.out1 = dbeta; f.out2 = dgamma;
+    launch_col_finalize(f, s);
     BnBwdArgs b{};
     b.dY = dy; b.X = x; b.mean = mean; b.rstd = rstd; b.gamma = gamma; b.sum_g = dbeta; b.sum_gx = dgamma;
     b.dX = dx; b.M = M; b.C = C; b.lddy = lddy; b.ldx = ldx; b.lddx = lddx;
@@ -2008,18 +1998,14 @@ int fear_bn_train_backward_x(const float* dy, int lddy, const float* x, int ldx,
 // BatchNorm as separate operators, so that the caller can all-reduce the float64 sums between them.
 int fear_bn_reduce(const float* x, int ldx, double* sums, long M, int C, float* workspace, size_t ws_bytes, void* stream) {
     if (!x || !sums || !workspace) return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || C < 4 || C % 4 || C > 1024) return FEAR_TRAIN_ERR_SHAPE;
+    if (!bn_shape_ok(M, C)) return FEAR_TRAIN_ERR_SHAPE;
     if (!ld_ok(ldx, C)) return FEAR_TRAIN_ERR_SHAPE;      // float4 rows
-    const int blocks = col_blocks(M);
-    if (ws_bytes < (size_t)blocks * 2 * C * sizeof(double)) return FEAR_TRAIN_ERR_WORKSPACE;
+    if (ws_bytes < col_partial_bytes(M, C)) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    double* partial = reinterpret_cast<double*>(workspace);
     ColArgs a{};
-    a.A = x; a.lda = ldx; a.partial = reinterpret_cast<double*>(workspace); a.M = M; a.C = C; a.rpb = col_rows_per_block(M);
-    hipLaunchKernelGGL(col_reduce_kernel<0>, dim3(blocks), dim3(256), 0, s, a);
-    ColFinArgs f{};
-    f.partial = reinterpret_cast<const double*>(workspace); f.dsum = sums; f.blocks = blocks; f.C = C; f.mode = 3; f.M = (double)M;
-    f.rpb = a.rpb;
-    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(1024), 0, s, f);
+    a.A = x; a.lda = ldx;
+    finalize_sums(partial, launch_col_reduce<0>(a, partial, M, C, s), C, sums, s);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }
@@ -2028,7 +2014,7 @@ int fear_bn_forward_from_sums(const float* x, int ldx, const double* sums, doubl
                               float* y, int ldy, float* mean, float* rstd, float* running_mean, float* running_var,
                               double momentum, double eps, long M, int C, int relu, void* stream) {
     if (!x || !sums || !gamma || !beta || !y || !mean || !rstd) return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || C < 4 || C % 4 || C > 1024 || !(count >= (double)M)) return FEAR_TRAIN_ERR_SHAPE;
+    if (!bn_shape_ok(M, C) || !(count >= (double)M)) return FEAR_TRAIN_ERR_SHAPE;
     if (!ld_ok(ldx, C) || !ld_ok(ldy, C)) return FEAR_TRAIN_ERR_SHAPE;      // float4 rows
     hipStream_t s = static_cast<hipStream_t>(stream);
     BnFromSumsArgs f{};
@@ -2047,19 +2033,14 @@ int fear_bn_forward_from_sums(const float* x, int ldx, const double* sums, doubl
 int fear_bn_backward_reduce(const float* dy, int lddy, const float* y_act, int ldy, const float* x, int ldx, const float* mean,
                             const float* rstd, double* sums, long M, int C, float* workspace, size_t ws_bytes, void* stream) {
     if (!dy || !x || !mean || !rstd || !sums || !workspace) return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || C < 4 || C % 4 || C > 1024) return FEAR_TRAIN_ERR_SHAPE;
+    if (!bn_shape_ok(M, C)) return FEAR_TRAIN_ERR_SHAPE;
     if (!ld_ok(lddy, C) || !ld_ok(ldx, C) || (y_act && !ld_ok(ldy, C))) return FEAR_TRAIN_ERR_SHAPE;      // float4 rows
-    const int blocks = col_blocks(M);
-    if (ws_bytes < (size_t)blocks * 2 * C * sizeof(double)) return FEAR_TRAIN_ERR_WORKSPACE;
+    if (ws_bytes < col_partial_bytes(M, C)) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     ColArgs a{};
     a.A = dy; a.lda = lddy; a.Yact = y_act; a.ldy = ldy; a.X = x; a.ldx = ldx; a.mean = mean; a.rstd = rstd;
-    a.partial = reinterpret_cast<double*>(workspace); a.M = M; a.C = C; a.rpb = col_rows_per_block(M);
-    hipLaunchKernelGGL(col_reduce_kernel<1>, dim3(blocks), dim3(256), 0, s, a);
-    ColFinArgs f{};
-    f.partial = reinterpret_cast<const double*>(workspace); f.dsum = sums; f.blocks = blocks; f.C = C; f.mode = 3; f.M = (double)M;
-    f.rpb = a.rpb;
-    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(1024), 0, s, f);
+    double* partial = reinterpret_cast<double*>(workspace);
+    finalize_sums(partial, launch_col_reduce<1>(a, partial, M, C, s), C, sums, s);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }
@@ -2070,7 +2051,7 @@ int fear_bn_backward_from_sums(const float* dy, int lddy, const float* y_act, in
                                size_t ws_bytes, long M, int C, void* stream) {
     if (!dy || !x || !mean || !rstd || !gamma || !sums_all || !sums_local || !dx || !dgamma || !dbeta || !workspace)
         return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || C < 4 || C % 4 || C > 1024 || !(count >= (double)M)) return FEAR_TRAIN_ERR_SHAPE;
+    if (!bn_shape_ok(M, C) || !(count >= (double)M)) return FEAR_TRAIN_ERR_SHAPE;
     if (!ld_ok(lddy, C) || !ld_ok(ldx, C) || !ld_ok(lddx, C) || (y_act && !ld_ok(ldy, C))) return FEAR_TRAIN_ERR_SHAPE;      // float4 rows
     if (ws_bytes < (size_t)2 * C * sizeof(float)) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2149,11 +2130,10 @@ int fear_exp_head_backward(const float* p, const float* adjust, const float* bbo
     hipLaunchKernelGGL(exp_head_bwd_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, a);
     for (int pass = 0; pass < 2; ++pass) {
         ColArgs c{};
-        c.A = pass == 0 ? T : U; c.lda = 4; c.partial = part; c.M = M; c.C = 4; c.rpb = col_rows_per_block(M);
-        hipLaunchKernelGGL(col_reduce_kernel<2>, dim3(blocks), dim3(256), 0, s, c);
-        ColFinArgs f{};
-        f.partial = part; f.out1 = pass == 0 ? dbias4 : u4; f.blocks = blocks; f.C = 4; f.mode = 2; f.M = (double)M; f.rpb = col_rows_per_block(M);
-        hipLaunchKernelGGL(col_finalize_kernel, dim3(1), dim3(1024), 0, s, f);
+        c.A = pass == 0 ? T : U; c.lda = 4;
+        ColFinArgs f = col_fin(part, launch_col_reduce<2>(c, part, M, 4, s), 4, 2, (double)M);
+        f.out1 = pass == 0 ? dbias4 : u4;
+        launch_col_finalize(f, s);
     }
     // d adjust = the four per-channel sums of dbbox * bbox * p added up (adjust is one scalar shared by the four channels)
     hipLaunchKernelGGL(sum4_kernel, dim3(1), dim3(1), 0, s, u4, dadjust);

@@ -1050,27 +1050,7 @@ __global__ __launch_bounds__(256, 2) void dw_fwd_kernel(DwFwdArgs a) {
 
 template <bool MS>
 void launch_pw_bwd(const PwBwdArgs& a, dim3 grid, int nt, hipStream_t s) {
-    switch (nt) {
-        case 1: hipLaunchKernelGGL((pw_bwd_kernel<1, MS>), grid, dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((pw_bwd_kernel<2, MS>), grid, dim3(256), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((pw_bwd_kernel<3, MS>), grid, dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((pw_bwd_kernel<4, MS>), grid, dim3(256), 0, s, a); break;
-        case 6: hipLaunchKernelGGL((pw_bwd_kernel<6, MS>), grid, dim3(256), 0, s, a); break;
-        case 7: hipLaunchKernelGGL((pw_bwd_kernel<7, MS>), grid, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL((pw_bwd_kernel<8, MS>), grid, dim3(256), 0, s, a); break;
-    }
-}
-
-void launch_pw_stat(const PwStatArgs& a, dim3 grid, int nt, hipStream_t s) {
-    switch (nt) {
-        case 1: hipLaunchKernelGGL((pw_stat_kernel<1>), grid, dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((pw_stat_kernel<2>), grid, dim3(256), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((pw_stat_kernel<3>), grid, dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((pw_stat_kernel<4>), grid, dim3(256), 0, s, a); break;
-        case 6: hipLaunchKernelGGL((pw_stat_kernel<6>), grid, dim3(256), 0, s, a); break;
-        case 7: hipLaunchKernelGGL((pw_stat_kernel<7>), grid, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL((pw_stat_kernel<8>), grid, dim3(256), 0, s, a); break;
-    }
+    dispatch_nt(nt, [&](auto NT) { hipLaunchKernelGGL((pw_bwd_kernel<NT(), MS>), grid, dim3(256), 0, s, a); });
 }
 
 // the workspace of one block call, cut into the regions its kernels use side by side
@@ -1157,39 +1137,35 @@ void sync_all_reduce(const FearSync& sy, long n, int is_f32, hipStream_t s) {
 // column-sum partials [blocks][2][C] -> mean | rstd | a | b (vec) + running statistics
 void finalize_forward(const double* partial, int blocks, int C, double count, const float* gamma, const float* beta, float* vec,
                       float* running_mean, float* running_var, double momentum, double eps, hipStream_t s, const float* mean_shift = nullptr) {
-    ColFinArgs f{};
-    f.mean_shift = mean_shift;
-    f.partial = partial; f.out1 = vec; f.out2 = vec + C; f.out_a = vec + 2 * C; f.out_b = vec + 3 * C; f.gamma = gamma; f.beta = beta;
-    f.running_mean = running_mean; f.running_var = running_var; f.blocks = blocks; f.C = C; f.mode = 0; f.M = count; f.eps = eps; f.momentum = momentum;
+    ColFinArgs f = col_fin(partial, blocks, C, 0, count);
+    f.out1 = vec; f.out2 = vec + C; f.out_a = vec + 2 * C; f.out_b = vec + 3 * C; f.gamma = gamma; f.beta = beta;
+    f.running_mean = running_mean; f.running_var = running_var; f.mean_shift = mean_shift; f.eps = eps; f.momentum = momentum;
     FearSync sy;
     if (sync_of(s, &sy)) {
         // SyncBatchNorm: this rank's float64 sums -> the ranks' all-reduce -> statistics of all ranks' rows
-        ColFinArgs r{};
-        r.partial = partial; r.blocks = blocks; r.C = C; r.mode = 3; r.dsum = sy.buf;
-        hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(1024), 0, s, r);
+        finalize_sums(partial, blocks, C, sy.buf, s);
         sync_all_reduce(sy, 2L * C, 0, s);
         f.partial = sy.buf; f.blocks = 1; f.M = count * sy.world;
     }
-    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(1024), 0, s, f);
+    launch_col_finalize(f, s);
 }
 
 // column-sum partials of (g, g * xhat) -> d beta, d gamma, BnbIn coefficients
 void finalize_backward(const double* partial, int blocks, int C, double count, const float* gamma, const float* vec, float* dgamma, float* dbeta,
                        float* coef, hipStream_t s) {
-    ColFinArgs f{};
-    f.partial = partial; f.out1 = dbeta; f.out2 = dgamma; f.gamma = gamma; f.mean_in = vec; f.rstd_in = vec + C; f.coef = coef;
-    f.blocks = blocks; f.C = C; f.mode = 4; f.M = count;
+    ColFinArgs f = col_fin(partial, blocks, C, 4, count);
+    f.out1 = dbeta; f.out2 = dgamma; f.gamma = gamma; f.mean_in = vec; f.rstd_in = vec + C; f.coef = coef;
     FearSync sy;
     if (sync_of(s, &sy)) {
         // SyncBatchNorm: d beta / d gamma from this rank's sums (they are averaged with every other gradient), the input gradient's
         // coefficients from all ranks' — the split torch.nn.SyncBatchNorm makes
         ColFinArgs r = f;
         r.mode = 6; r.dsum = sy.buf;
-        hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(1024), 0, s, r);
+        launch_col_finalize(r, s);
         sync_all_reduce(sy, 2L * C, 0, s);
         f.partial = sy.buf; f.blocks = 1; f.out1 = nullptr; f.out2 = nullptr; f.M = count * sy.world;
     }
-    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(1024), 0, s, f);
+    launch_col_finalize(f, s);
 }
 
 // Grid of the row-tiled GEMMs with a statistics epilogue: train_pw_grid's, with the row blocks of the large maps fattened to
@@ -1255,10 +1231,7 @@ void bn_backward_sums(const float* dy, int lddy, const float* raw, int ldx, cons
     ColArgs a{};
     a.A = dy; a.lda = lddy; a.X = raw; a.ldx = ldx; a.mean = vec; a.rstd = vec + C;
     a.act_a = relu ? vec + 2 * C : nullptr; a.act_b = relu ? vec + 3 * C : nullptr;
-    a.partial = col; a.M = M; a.C = C; a.rpb = col_rows_per_block(M);
-    const int blocks = col_blocks(M);
-    hipLaunchKernelGGL(col_reduce_kernel<1>, dim3(blocks), dim3(256), 0, s, a);
-    finalize_backward(col, blocks, C, (double)M, gamma, vec, dgamma, dbeta, coef, s);
+    finalize_backward(col, launch_col_reduce<1>(a, col, M, C, s), C, (double)M, gamma, vec, dgamma, dbeta, coef, s);
 }
 
 // The E-free form of an expansion's backward (BnbIn, fear_train.hip): from BN1's coefficients [A | s1 | mu | Q] and the expansion
@@ -1521,10 +1494,7 @@ int fear_irb_train_forward(const FearIrbBlock* b, const FearIrbSaved* sv, const 
             else if (b->cin <= 16) hipLaunchKernelGGL((dw_fwd_kernel<5, 2, 8, 1>), grid, dim3(256), 0, s, a);
             else hipLaunchKernelGGL((dw_fwd_kernel<5, 2, 8, 2>), grid, dim3(256), 0, s, a);
         } else if (small_map) hipLaunchKernelGGL((dw_fwd_kernel<5, 1, 8, 0, 8>), grid, dim3(256), 0, s, a);
-        else if (b->k == 3 && b->stride == 1) launch_dw_fwd_ks<3, 1>(a, sq, grid, s);
-        else if (b->k == 3) launch_dw_fwd_ks<3, 2>(a, sq, grid, s);
-        else if (b->stride == 1) launch_dw_fwd_ks<5, 1>(a, sq, grid, s);
-        else launch_dw_fwd_ks<5, 2>(a, sq, grid, s);
+        else dispatch_ks(b->k, b->stride, [&](auto KS, auto S) { launch_dw_fwd_ks<KS(), S()>(a, sq, grid, s); });
         finalize_forward(ws.col, a.wgs_per_slab, b->cexp, (double)rows_out, b->gamma[1], b->beta[1], sv->vec[1], b->running_mean[1],
                          b->running_var[1], momentum, eps, s);
     }
@@ -1637,10 +1607,7 @@ int fear_irb_train_backward(const FearIrbBlock* b, const FearIrbSaved* sv, const
             else if (cin <= 16) hipLaunchKernelGGL((dw_bwd_kernel<5, 2, 8, true, 1>), grid, dim3(256), 0, s, a);
             else hipLaunchKernelGGL((dw_bwd_kernel<5, 2, 8, true, 2>), grid, dim3(256), 0, s, a);
         } else if (small_map) hipLaunchKernelGGL((dw_bwd_kernel<5, 1, 8, true, 0, 8>), grid, dim3(256), 0, s, a);
-        else if (b->k == 3 && b->stride == 1) launch_dw_bwd_ks<3, 1>(a, sq, b->expand != 0, grid, s);
-        else if (b->k == 3) launch_dw_bwd_ks<3, 2>(a, sq, b->expand != 0, grid, s);
-        else if (b->stride == 1) launch_dw_bwd_ks<5, 1>(a, sq, b->expand != 0, grid, s);
-        else launch_dw_bwd_ks<5, 2>(a, sq, b->expand != 0, grid, s);
+        else dispatch_ks(b->k, b->stride, [&](auto KS, auto S) { launch_dw_bwd_ks<KS(), S()>(a, sq, b->expand != 0, grid, s); });
         if (b->expand)
             finalize_backward(ws.col, a.wgs_per_slab, cexp, (double)rows_in, b->gamma[0], sv->vec[0], gr->gamma[0], gr->beta[0], coef1, s);
         // the tap gradients' final sum is a weight gradient too: off the chain (the partials live in the call's private scratch)
@@ -1758,7 +1725,7 @@ int fear_pwbn_train_forward(const float* x, int ldx, const float* w, const float
                             float* running_var, float* raw, float* vec, int relu, float* out, long M, int K, int N, double momentum, double eps,
                             float* workspace, size_t ws_bytes, void* stream) {
     if (!x || !w || !gamma || !beta || !raw || !vec || !out || !workspace) return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || K < 4 || K % 4 || N < 4 || N % 4 || N > 1024 || M > 0x7fffffffL || !ld_ok(ldx, K)) return FEAR_TRAIN_ERR_SHAPE;
+    if (!pw_shape_ok(M, K, N) || N > 1024 || M > 0x7fffffffL || !ld_ok(ldx, K)) return FEAR_TRAIN_ERR_SHAPE;
     const BlockWs ws = block_ws(M, M, K, N, N, 3, workspace);
     if (ws_bytes < ws.total) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1775,7 +1742,7 @@ int fear_pwbn_train_backward(const float* dy, const float* raw, const float* vec
                              const float* gamma, float* dw, float* dgamma, float* dbeta, float* dx, long M, int K, int N, float* workspace,
                              size_t ws_bytes, void* stream, void* wgrad_stream) {
     if (!dy || !raw || !vec || !x || !w || !gamma || !dw || !dgamma || !dbeta || !workspace) return FEAR_TRAIN_ERR_NULL;
-    if (M <= 0 || K < 4 || K % 4 || N < 4 || N % 4 || N > 1024 || M > 0x7fffffffL || !ld_ok(ldx, K)) return FEAR_TRAIN_ERR_SHAPE;
+    if (!pw_shape_ok(M, K, N) || N > 1024 || M > 0x7fffffffL || !ld_ok(ldx, K)) return FEAR_TRAIN_ERR_SHAPE;
     const BlockWs ws = block_ws(M, M, K, N, N, 3, workspace);
     if (ws_bytes < ws.total) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -22,7 +22,7 @@ from typing import Dict, Tuple
 
 import torch
 
-from .train_head import TrainError, _p, load_train_library
+from .train_abi import TrainError, _p, load_train_library
 
 
 class AdamHIP:

@@ -1,0 +1,136 @@
+"""ctypes declaration of the training ABI (include/fear_train.h): the prototypes of every training operator in libfear_hip.so, the
+mirrors of its structs, and the few helpers every module that calls them shares.  `train_head`, `train_net`, `optim` and
+`train_data` sequence these operators; none of them declares a prototype of its own."""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+import torch
+
+from .hip_backend import load_library
+
+_P = ctypes.c_void_p
+_i, _l, _f, _d, _sz = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
+
+TRAIN_SYMBOLS = {
+    "fear_train_workspace_bytes": ([_l, _i], _sz),
+    "fear_pw_forward": ([_P, _i, _P, _P, _P, _i, _l, _i, _i, _P], _i),
+    "fear_pw_backward_data": ([_P, _i, _P, _P, _i, _P, _i, _l, _i, _i, _P], _i),
+    "fear_pw_backward_weight": ([_P, _i, _P, _i, _P, _P, _sz, _l, _i, _i, _P], _i),
+    "fear_col_sum": ([_P, _i, _P, _P, _sz, _l, _i, _P], _i),
+    "fear_dw_forward": ([_P, _i, _P, _P, _P, _i, _i, _i, _i, _i, _i, _i, _P], _i),
+    "fear_dw_backward_data": ([_P, _i, _P, _P, _i, _i, _i, _i, _i, _i, _i, _P], _i),
+    "fear_dw_backward_weight": ([_P, _i, _P, _i, _P, _P, _sz, _i, _i, _i, _i, _i, _i, _P], _i),
+    "fear_stem_im2col": ([_P, _P, _l, _i, _i, _P], _i),
+    "fear_bn_train_forward": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _d, _d, _l, _i, _i, _P, _sz, _P], _i),
+    "fear_bn_train_backward": ([_P, _i, _P, _i, _P, _i, _P, _P, _P, _P, _i, _P, _P, _l, _i, _P, _sz, _P], _i),
+    "fear_bn_reduce": ([_P, _i, _P, _l, _i, _P, _sz, _P], _i),
+    "fear_bn_forward_from_sums": ([_P, _i, _P, _d, _P, _P, _P, _i, _P, _P, _P, _P, _d, _d, _l, _i, _i, _P], _i),
+    "fear_bn_backward_reduce": ([_P, _i, _P, _i, _P, _i, _P, _P, _P, _l, _i, _P, _sz, _P], _i),
+    "fear_bn_backward_from_sums": ([_P, _i, _P, _i, _P, _i, _P, _P, _P, _P, _d, _P, _P, _i, _P, _P, _P, _sz, _l, _i, _P], _i),
+    "fear_pw_forward_stats": ([_P, _i, _P, _P, _i, _P, _P, _i, _l, _i, _i, _P, _P, _sz, _P], _i),
+    "fear_dw_forward_stats": ([_P, _i, _P, _P, _i, _P, _P, _i, _i, _i, _i, _i, _i, _i, _P, _P, _sz, _P], _i),
+    "fear_train_stats_workspace_bytes": ([_l, _i], _sz),
+    "fear_bn_finalize": ([_P, _d, _P, _P, _P, _P, _P, _P, _P, _P, _d, _d, _i, _P], _i),
+    "fear_bn_act": ([_P, _i, _P, _P, _i, _P, _i, _P, _i, _l, _i, _P], _i),
+    "fear_bn_backward_reduce_x": ([_P, _i, _P, _i, _P, _P, _i, _P, _P, _P, _l, _i, _P, _sz, _P], _i),
+    "fear_bn_backward_apply_x": ([_P, _i, _P, _i, _P, _P, _i, _P, _P, _P, _P, _d, _P, _P, _i, _P, _P, _P, _sz, _l, _i, _P], _i),
+    "fear_bn_train_forward_ab": ([_P, _i, _P, _P, _i, _P, _i, _P, _i, _P, _P, _P, _P, _P, _P, _d, _d, _l, _i, _P, _sz, _P], _i),
+    "fear_bn_train_backward_x": ([_P, _i, _P, _i, _P, _P, _i, _P, _P, _P, _P, _i, _P, _P, _l, _i, _P, _sz, _P], _i),
+    "fear_pw_backward_weight_act": ([_P, _i, _P, _i, _P, _P, _i, _P, _P, _sz, _l, _i, _i, _P], _i),
+    "fear_dw_backward_weight_act": ([_P, _i, _P, _i, _P, _P, _i, _P, _P, _sz, _i, _i, _i, _i, _i, _i, _P], _i),
+    "fear_xcorr_forward": ([_P, _i, _P, _P, _i, _i, _i, _i, _i, _P], _i),
+    "fear_xcorr_backward": ([_P, _i, _P, _i, _P, _P, _i, _P, _i, _P, _i, _i, _i, _i, _P], _i),
+    "fear_exp_head_forward": ([_P, _P, _P, _P, _l, _P], _i),
+    "fear_exp_head_backward": ([_P, _P, _P, _P, _P, _P, _P, _P, _sz, _l, _P], _i),
+    "fear_head_loss": ([_P, _P, _P, _P, _P, _f, _f, _P, _P, _P, _P, _sz, _l, _P], _i),
+    "fear_nchw_to_nhwc": ([_P, _P, _l, _i, _i, _i, _i, _P], _i),
+    "fear_nhwc_to_nchw": ([_P, _P, _l, _i, _i, _i, _i, _P], _i),
+    "fear_scale_column": ([_P, _i, _i, _f, _P, _i, _i, _l, _P], _i),
+    "fear_add": ([_P, _P, _P, _l, _P], _i),
+    "fear_adam_step": ([_P, _P, _P, _P, _l, _d, _d, _d, _d, _d, _i, _P], _i),
+    # block-fused trunk operators (structs below mirror include/fear_train.h)
+    "fear_irb_workspace_bytes": ([_P, _i, _i, _i], _sz),
+    "fear_irb_scratch_floats": ([_P, _i, _i, _i], _sz),
+    "fear_irb_virtual_ok": ([_P], _i),
+    "fear_irb_train_forward": ([_P, _P, _P, _P, _i, _i, _i, _d, _d, _P, _sz, _P], _i),
+    "fear_irb_train_backward": ([_P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _P, _sz, _P, _P], _i),
+    "fear_bn_running_update": ([_P, _d, _P, _P, _d, _d, _i, _P], _i),
+    "fear_bn_running_update_multi": ([_P, _i, _d, _d, _P], _i),
+    "fear_pwbn_workspace_bytes": ([_l, _i, _i], _sz),
+    "fear_pwbn_train_forward": ([_P, _i, _P, _P, _P, _P, _P, _P, _P, _i, _P, _l, _i, _i, _d, _d, _P, _sz, _P], _i),
+    "fear_pwbn_train_backward": ([_P, _P, _P, _i, _P, _i, _P, _P, _P, _P, _P, _P, _l, _i, _i, _P, _sz, _P, _P], _i),
+    "fear_stem_workspace_bytes": ([_l, _i, _i], _sz),
+    "fear_stem_train_forward": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _l, _i, _i, _d, _d, _P, _sz, _P], _i),
+    "fear_stem_train_backward": ([_P, _P, _P, _P, _P, _P, _P, _P, _l, _i, _i, _P, _sz, _P, _P], _i),
+    # the head's SepConv + BatchNorm + ReLU layer, one call per direction
+    "fear_sepbn_workspace_bytes": ([_P, _i, _i, _i], _sz),
+    "fear_sepbn_train_forward": ([_P, _P, _i, _P, _P, _P, _P, _i, _i, _i, _i, _d, _d, _P, _sz, _P], _i),
+    "fear_sepbn_train_backward": ([_P, _P, _P, _i, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _P, _sz, _P, _P], _i),
+    # SyncBatchNorm hook of the block-fused operators: (stream, FearSync*)
+    "fear_train_sync_bind": ([_P, _P], _i),
+    # training pairs from frames (train_data.TrainPairBuilder)
+    "fear_frame_border_u8": ([_P, _i, _P, _P], _i),
+    "fear_train_pairs": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _P, _P], _i),
+}
+
+
+class FearIrbBlock(ctypes.Structure):
+    """include/fear_train.h: one inverted-residual block's shape and parameters (device pointers, kernel layouts)."""
+    _fields_ = [("cin", _i), ("cexp", _i), ("cout", _i), ("k", _i), ("stride", _i), ("expand", _i), ("residual", _i), ("flags", _i),
+                ("w_pw", _P), ("w_dw", _P), ("w_pwl", _P), ("gamma", _P * 3), ("beta", _P * 3), ("running_mean", _P * 3), ("running_var", _P * 3)]
+
+
+class FearIrbSaved(ctypes.Structure):
+    _fields_ = [("e", _P), ("d", _P), ("p", _P), ("vec", _P * 3)]
+
+
+class FearIrbGrads(ctypes.Structure):
+    _fields_ = [("w_pw", _P), ("w_dw", _P), ("w_pwl", _P), ("gamma", _P * 3), ("beta", _P * 3)]
+
+
+class FearBnRunning(ctypes.Structure):
+    _fields_ = [("vec", _P), ("running_mean", _P), ("running_var", _P), ("C", _i), ("count", _d)]
+
+
+class FearSepLayer(ctypes.Structure):
+    """include/fear_train.h: one SepConv + BatchNorm + ReLU layer of the head (device pointers, kernel layouts)."""
+    _fields_ = [("cin", _i), ("cout", _i), ("w_dw", _P), ("b_dw", _P), ("w_pw", _P), ("b_pw", _P), ("gamma", _P), ("beta", _P),
+                ("running_mean", _P), ("running_var", _P)]
+
+
+class FearSepGrads(ctypes.Structure):
+    _fields_ = [("w_dw", _P), ("w_pw", _P), ("gamma", _P), ("beta", _P)]
+
+
+_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p)
+FEAR_SYNC_BUF_BYTES = 16384
+
+
+class FearSync(ctypes.Structure):
+    """include/fear_train.h: the all-reduce hook a stream is bound to (fear_train_sync_bind)."""
+    _fields_ = [("all_reduce", _ALLREDUCE_FN), ("user", _P), ("buf", _P), ("buf_bytes", _sz), ("world", _i)]
+
+
+_bound = None
+
+
+def load_train_library() -> ctypes.CDLL:
+    """The training operators live in the same libfear_hip.so; declare their prototypes (include/fear_train.h)."""
+    global _bound
+    if _bound is None:
+        lib = load_library()
+        for name, (args, res) in TRAIN_SYMBOLS.items():
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = args, res
+        _bound = lib
+    return _bound
+
+
+class TrainError(RuntimeError):
+    pass
+
+
+def _p(t: Optional[torch.Tensor], offset: int = 0):
+    return None if t is None else ctypes.c_void_p(t.data_ptr() + 4 * offset)

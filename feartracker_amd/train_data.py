@@ -427,7 +427,7 @@ class TrainPairBuilder:
     # ------------------------------------------------------------------ device
     def _library(self):
         if self._lib is None:
-            from .train_head import load_train_library
+            from .train_abi import load_train_library
             self._lib = load_train_library()
         return self._lib
 

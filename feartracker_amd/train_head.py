@@ -21,109 +21,9 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from .hip_backend import load_library
-
-_P = ctypes.c_void_p
-_i, _l, _f, _d, _sz = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
-
-TRAIN_SYMBOLS = {
-    "fear_train_workspace_bytes": ([_l, _i], _sz),
-    "fear_pw_forward": ([_P, _i, _P, _P, _P, _i, _l, _i, _i, _P], _i),
-    "fear_pw_backward_data": ([_P, _i, _P, _P, _i, _P, _i, _l, _i, _i, _P], _i),
-    "fear_pw_backward_weight": ([_P, _i, _P, _i, _P, _P, _sz, _l, _i, _i, _P], _i),
-    "fear_col_sum": ([_P, _i, _P, _P, _sz, _l, _i, _P], _i),
-    "fear_dw_forward": ([_P, _i, _P, _P, _P, _i, _i, _i, _i, _i, _i, _i, _P], _i),
-    "fear_dw_backward_data": ([_P, _i, _P, _P, _i, _i, _i, _i, _i, _i, _i, _P], _i),
-    "fear_dw_backward_weight": ([_P, _i, _P, _i, _P, _P, _sz, _i, _i, _i, _i, _i, _i, _P], _i),
-    "fear_stem_im2col": ([_P, _P, _l, _i, _i, _P], _i),
-    "fear_bn_train_forward": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _d, _d, _l, _i, _i, _P, _sz, _P], _i),
-    "fear_bn_train_backward": ([_P, _i, _P, _i, _P, _i, _P, _P, _P, _P, _i, _P, _P, _l, _i, _P, _sz, _P], _i),
-    "fear_bn_reduce": ([_P, _i, _P, _l, _i, _P, _sz, _P], _i),
-    "fear_bn_forward_from_sums": ([_P, _i, _P, _d, _P, _P, _P, _i, _P, _P, _P, _P, _d, _d, _l, _i, _i, _P], _i),
-    "fear_bn_backward_reduce": ([_P, _i, _P, _i, _P, _i, _P, _P, _P, _l, _i, _P, _sz, _P], _i),
-    "fear_bn_backward_from_sums": ([_P, _i, _P, _i, _P, _i, _P, _P, _P, _P, _d, _P, _P, _i, _P, _P, _P, _sz, _l, _i, _P], _i),
-    "fear_pw_forward_stats": ([_P, _i, _P, _P, _i, _P, _P, _i, _l, _i, _i, _P, _P, _sz, _P], _i),
-    "fear_dw_forward_stats": ([_P, _i, _P, _P, _i, _P, _P, _i, _i, _i, _i, _i, _i, _i, _P, _P, _sz, _P], _i),
-    "fear_train_stats_workspace_bytes": ([_l, _i], _sz),
-    "fear_bn_finalize": ([_P, _d, _P, _P, _P, _P, _P, _P, _P, _P, _d, _d, _i, _P], _i),
-    "fear_bn_act": ([_P, _i, _P, _P, _i, _P, _i, _P, _i, _l, _i, _P], _i),
-    "fear_bn_backward_reduce_x": ([_P, _i, _P, _i, _P, _P, _i, _P, _P, _P, _l, _i, _P, _sz, _P], _i),
-    "fear_bn_backward_apply_x": ([_P, _i, _P, _i, _P, _P, _i, _P, _P, _P, _P, _d, _P, _P, _i, _P, _P, _P, _sz, _l, _i, _P], _i),
-    "fear_bn_train_forward_ab": ([_P, _i, _P, _P, _i, _P, _i, _P, _i, _P, _P, _P, _P, _P, _P, _d, _d, _l, _i, _P, _sz, _P], _i),
-    "fear_bn_train_backward_x": ([_P, _i, _P, _i, _P, _P, _i, _P, _P, _P, _P, _i, _P, _P, _l, _i, _P, _sz, _P], _i),
-    "fear_pw_backward_weight_act": ([_P, _i, _P, _i, _P, _P, _i, _P, _P, _sz, _l, _i, _i, _P], _i),
-    "fear_dw_backward_weight_act": ([_P, _i, _P, _i, _P, _P, _i, _P, _P, _sz, _i, _i, _i, _i, _i, _i, _P], _i),
-    "fear_xcorr_forward": ([_P, _i, _P, _P, _i, _i, _i, _i, _i, _P], _i),
-    "fear_xcorr_backward": ([_P, _i, _P, _i, _P, _P, _i, _P, _i, _P, _i, _i, _i, _i, _P], _i),
-    "fear_exp_head_forward": ([_P, _P, _P, _P, _l, _P], _i),
-    "fear_exp_head_backward": ([_P, _P, _P, _P, _P, _P, _P, _P, _sz, _l, _P], _i),
-    "fear_head_loss": ([_P, _P, _P, _P, _P, _f, _f, _P, _P, _P, _P, _sz, _l, _P], _i),
-    "fear_nchw_to_nhwc": ([_P, _P, _l, _i, _i, _i, _i, _P], _i),
-    "fear_nhwc_to_nchw": ([_P, _P, _l, _i, _i, _i, _i, _P], _i),
-    "fear_scale_column": ([_P, _i, _i, _f, _P, _i, _i, _l, _P], _i),
-    "fear_add": ([_P, _P, _P, _l, _P], _i),
-    "fear_adam_step": ([_P, _P, _P, _P, _l, _d, _d, _d, _d, _d, _i, _P], _i),
-    # block-fused trunk operators (structs below mirror include/fear_train.h)
-    "fear_irb_workspace_bytes": ([_P, _i, _i, _i], _sz),
-    "fear_irb_scratch_floats": ([_P, _i, _i, _i], _sz),
-    "fear_irb_virtual_ok": ([_P], _i),
-    "fear_irb_train_forward": ([_P, _P, _P, _P, _i, _i, _i, _d, _d, _P, _sz, _P], _i),
-    "fear_irb_train_backward": ([_P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _P, _sz, _P, _P], _i),
-    "fear_bn_running_update": ([_P, _d, _P, _P, _d, _d, _i, _P], _i),
-    "fear_bn_running_update_multi": ([_P, _i, _d, _d, _P], _i),
-    "fear_pwbn_workspace_bytes": ([_l, _i, _i], _sz),
-    "fear_pwbn_train_forward": ([_P, _i, _P, _P, _P, _P, _P, _P, _P, _i, _P, _l, _i, _i, _d, _d, _P, _sz, _P], _i),
-    "fear_pwbn_train_backward": ([_P, _P, _P, _i, _P, _i, _P, _P, _P, _P, _P, _P, _l, _i, _i, _P, _sz, _P, _P], _i),
-    "fear_stem_workspace_bytes": ([_l, _i, _i], _sz),
-    "fear_stem_train_forward": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _l, _i, _i, _d, _d, _P, _sz, _P], _i),
-    "fear_stem_train_backward": ([_P, _P, _P, _P, _P, _P, _P, _P, _l, _i, _i, _P, _sz, _P, _P], _i),
-    # the head's SepConv + BatchNorm + ReLU layer, one call per direction
-    "fear_sepbn_workspace_bytes": ([_P, _i, _i, _i], _sz),
-    "fear_sepbn_train_forward": ([_P, _P, _i, _P, _P, _P, _P, _i, _i, _i, _i, _d, _d, _P, _sz, _P], _i),
-    "fear_sepbn_train_backward": ([_P, _P, _P, _i, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _P, _sz, _P, _P], _i),
-    # SyncBatchNorm hook of the block-fused operators: (stream, FearSync*)
-    "fear_train_sync_bind": ([_P, _P], _i),
-    # training pairs from frames (train_data.TrainPairBuilder)
-    "fear_frame_border_u8": ([_P, _i, _P, _P], _i),
-    "fear_train_pairs": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _P, _P], _i),
-}
-
-
-class FearIrbBlock(ctypes.Structure):
-    """include/fear_train.h: one inverted-residual block's shape and parameters (device pointers, kernel layouts)."""
-    _fields_ = [("cin", _i), ("cexp", _i), ("cout", _i), ("k", _i), ("stride", _i), ("expand", _i), ("residual", _i), ("flags", _i),
-                ("w_pw", _P), ("w_dw", _P), ("w_pwl", _P), ("gamma", _P * 3), ("beta", _P * 3), ("running_mean", _P * 3), ("running_var", _P * 3)]
-
-
-class FearIrbSaved(ctypes.Structure):
-    _fields_ = [("e", _P), ("d", _P), ("p", _P), ("vec", _P * 3)]
-
-
-class FearIrbGrads(ctypes.Structure):
-    _fields_ = [("w_pw", _P), ("w_dw", _P), ("w_pwl", _P), ("gamma", _P * 3), ("beta", _P * 3)]
-
-
-class FearBnRunning(ctypes.Structure):
-    _fields_ = [("vec", _P), ("running_mean", _P), ("running_var", _P), ("C", _i), ("count", _d)]
-
-
-class FearSepLayer(ctypes.Structure):
-    """include/fear_train.h: one SepConv + BatchNorm + ReLU layer of the head (device pointers, kernel layouts)."""
-    _fields_ = [("cin", _i), ("cout", _i), ("w_dw", _P), ("b_dw", _P), ("w_pw", _P), ("b_pw", _P), ("gamma", _P), ("beta", _P),
-                ("running_mean", _P), ("running_var", _P)]
-
-
-class FearSepGrads(ctypes.Structure):
-    _fields_ = [("w_dw", _P), ("w_pw", _P), ("gamma", _P), ("beta", _P)]
-
-
-_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p)
-FEAR_SYNC_BUF_BYTES = 16384
-
-
-class FearSync(ctypes.Structure):
-    """include/fear_train.h: the all-reduce hook a stream is bound to (fear_train_sync_bind)."""
-    _fields_ = [("all_reduce", _ALLREDUCE_FN), ("user", _P), ("buf", _P), ("buf_bytes", _sz), ("world", _i)]
+# (the declaration of the training ABI lives in train_abi; its names stay importable from this module)
+from .train_abi import (FEAR_SYNC_BUF_BYTES, TRAIN_SYMBOLS, FearBnRunning, FearIrbBlock, FearIrbGrads, FearIrbSaved,  # noqa: F401
+                        FearSepGrads, FearSepLayer, FearSync, TrainError, _ALLREDUCE_FN, _p, load_train_library)
 
 
 class GradDict(dict):
@@ -161,28 +61,6 @@ class GradDict(dict):
         if self._rebound or any(k not in self or self[k]._version != ver for k, ver in self._sealed.items()):
             return None
         return self.flat
-
-_bound = None
-
-
-def load_train_library() -> ctypes.CDLL:
-    """The training operators live in the same libfear_hip.so; declare their prototypes (include/fear_train.h)."""
-    global _bound
-    if _bound is None:
-        lib = load_library()
-        for name, (args, res) in TRAIN_SYMBOLS.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, res
-        _bound = lib
-    return _bound
-
-
-class TrainError(RuntimeError):
-    pass
-
-
-def _p(t: Optional[torch.Tensor], offset: int = 0):
-    return None if t is None else ctypes.c_void_p(t.data_ptr() + 4 * offset)
 
 
 class SyncBN:
@@ -287,6 +165,44 @@ def bn_backward(lib, st, ws, wsb, sync: Optional["SyncBN"], dy, lddy, y_act, ldy
                                           float(M) * sync.world, _p(local), _p(dx), lddx, _p(dgamma), _p(dbeta), ws, wsb, M, C, st)
 
 
+class _TrainPlumbing:
+    """What a class that sequences training operators keeps between them (BoxTowerTrainHIP, train_net.FEARNetTrainHIP): the status
+    check, the current stream, allocation, and one growing buffer per (kind, stream lane).  Expects `lib`, `device`, `hook` (a
+    `SyncHook` or None) and `_lane` (the lane the caller is issuing on) on the instance."""
+
+    def _init_plumbing(self) -> None:
+        self._ws = {}                # (kind, lane) -> buffer
+        self._lane = 0
+
+    def _check(self, st: int) -> None:
+        if st != 0:
+            err = self.hook.error if self.hook is not None else None
+            if st == -8 and err is not None:            # FEAR_TRAIN_ERR_SYNC: the all-reduce callback raised
+                self.hook.error = None
+                raise TrainError("the SyncBatchNorm all-reduce of a block-fused operator failed") from err
+            raise TrainError(f"libfear_hip training operator failed with status {st}")
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _new(self, *shape) -> torch.Tensor:
+        return torch.empty(shape, dtype=torch.float32, device=self.device)
+
+    def _lane_buffer(self, kind: str, floats: int) -> torch.Tensor:
+        """This lane's buffer of `kind`, grown to at least `floats` floats (the old one is dropped before the new one is made)."""
+        key = (kind, self._lane)
+        buf = self._ws.get(key)
+        if buf is None or buf.numel() < floats:
+            self._ws[key] = None
+            buf = self._ws[key] = torch.empty(floats, dtype=torch.float32, device=self.device)
+        return buf
+
+    def _lane_workspace(self, need: int, kind: str = "ws"):
+        """(pointer, bytes) of this lane's workspace of at least `need` bytes."""
+        ws = self._lane_buffer(kind, (need + 3) // 4)
+        return _p(ws), ws.numel() * 4
+
+
 class _Sep:
     """One SepConv (+ optional BatchNorm + ReLU) with its parameters in kernel layout and its saved activations."""
 
@@ -314,7 +230,7 @@ class _Sep:
             self.running_var = sd[bn_prefix + ".running_var"].float().clone().to(dev)
 
 
-class BoxTowerTrainHIP:
+class BoxTowerTrainHIP(_TrainPlumbing):
     """BoxTower(towernum=2, inchannels=256, outchannels=256, mobile=True) in training mode + FEARLoss, on HIP operators."""
 
     S, TZ = 16, 8           # search feature map 16x16, template feature map 8x8 (256 / 128 px crops, stride 16)
@@ -345,8 +261,7 @@ class BoxTowerTrainHIP:
         self.adjust = sd["adjust"].float().reshape(1).to(self.device)
         self.bias4 = sd["bias"].float().reshape(4).to(self.device)
         self.hook = SyncHook(self.lib, self.sync, self.device) if (self.sync is not None and self.fused) else None
-        self._ws = {}                # per stream lane
-        self._lane = 0
+        self._init_plumbing()
         self._galloc = None          # set by FEARNetTrainHIP: gradient tensors are views of its flat gradient buffer
         # a second HIP stream for the regression branch: the two towers are independent between the shared input features and the
         # loss (forward) and between the loss gradient and the sum of their input gradients (backward), and every kernel of a 16 x 16
@@ -385,29 +300,10 @@ class BoxTowerTrainHIP:
         """Storage of the gradient of parameter `name` (kernel layout)."""
         return self._galloc(name, *shape) if self._galloc is not None else self._new(*shape)
 
-    # ------------------------------------------------------------------ plumbing
-    def _check(self, st: int) -> None:
-        if st != 0:
-            err = self.hook.error if self.hook is not None else None
-            if st == -8 and err is not None:            # FEAR_TRAIN_ERR_SYNC: the all-reduce callback raised
-                self.hook.error = None
-                raise TrainError("the SyncBatchNorm all-reduce of a block-fused operator failed") from err
-            raise TrainError(f"libfear_hip training operator failed with status {st}")
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _new(self, *shape) -> torch.Tensor:
-        return torch.empty(shape, dtype=torch.float32, device=self.device)
-
+    # ------------------------------------------------------------------ plumbing (_TrainPlumbing)
     def _workspace(self, rows: int):
         need = int(self.lib.fear_train_workspace_bytes(rows, 320))
-        need = max(need, (8 * rows + rows // 8 + 4096) * 4)
-        ws = self._ws.get(self._lane)
-        if ws is None or ws.numel() * 4 < need:
-            self._ws[self._lane] = None
-            ws = self._ws[self._lane] = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
-        return _p(ws), ws.numel() * 4
+        return self._lane_workspace(max(need, (8 * rows + rows // 8 + 4096) * 4))
 
     # ------------------------------------------------------------------ one SepConv [+ BN + ReLU]
     def _sep_desc(self, L: _Sep) -> "FearSepLayer":
@@ -423,12 +319,7 @@ class BoxTowerTrainHIP:
         need = int(self.lib.fear_sepbn_workspace_bytes(ctypes.byref(self._sep_desc(L)), B, self.S, self.S))
         if need == 0:
             raise TrainError(f"{L.prefix}: shape not supported by fear_sepbn_train_*")
-        key = ("sep", self._lane)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() * 4 < need:
-            self._ws[key] = None
-            ws = self._ws[key] = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
-        return _p(ws), ws.numel() * 4
+        return self._lane_workspace(need, "sep")
 
     def _sep_forward(self, L: _Sep, x: torch.Tensor, ldx: int, B: int, out: Optional[torch.Tensor] = None, ld_out: int = 0):
         lib, st, M = self.lib, self._stream(), B * self.S * self.S

@@ -32,8 +32,8 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from .train_head import (BoxTowerTrainHIP, FearBnRunning, FearIrbBlock, FearIrbGrads, FearIrbSaved, GradDict, SyncBN, TrainError, _p,
-                         load_train_library)
+from .train_abi import FearBnRunning, FearIrbBlock, FearIrbGrads, FearIrbSaved, TrainError, _p, load_train_library
+from .train_head import BoxTowerTrainHIP, GradDict, _TrainPlumbing
 
 # (cin, cexp, cout, k, stride, expand, residual): fbnet_c stages[1:18]
 TRUNK_BLOCKS = [
@@ -117,7 +117,27 @@ class _ConvBN:
 FEAR_IRB_VIRTUAL_E = 4        # include/fear_train.h
 
 
-class FEARNetTrainHIP:
+# Three implementations of the trunk's conv + BatchNorm units, the same arithmetic (tests/test_train_head.py pins each against
+# autograd):
+#   "block"      (default on one rank) one C-ABI call per inverted-residual block and direction, csrc/fear_train_block.h:
+#                statistics in the producing pass, BatchNorm / its backward / ReLU masks formed on load, the two
+#                BatchNorms around the depthwise conv and its three gradients in one LDS-tiled pass
+#                With SyncBatchNorm (round 6) the ranks' all-reduces are made by the library's hook between a producer's
+#                float64 sums and their finalize (train_head.SyncHook, include/fear_train.h fear_train_sync_bind)
+#   "layerwise"  (fused=False) one operator per layer and direction; SyncBatchNorm: all-reduces between the reductions and the applies
+#   "fused"      (fused=True) round 3's per-unit fused operators, the memory-saving form of "layerwise"
+def _resolve_mode(mode: Optional[str], fused: Optional[bool], sync_bn) -> str:
+    """`mode=` as given, else the legacy tri-state `fused=` (True / False / None = "fused" / "layerwise" / "block")."""
+    if mode is None:
+        mode = "fused" if fused else ("layerwise" if fused is False else "block")
+    if mode not in ("block", "layerwise", "fused"):
+        raise ValueError(f"unknown mode {mode!r}")
+    if mode == "fused" and sync_bn:
+        raise ValueError("mode='fused' has no SyncBatchNorm form; use mode='block' (default) or 'layerwise' with sync_bn")
+    return mode
+
+
+class FEARNetTrainHIP(_TrainPlumbing):
     def __init__(self, state_dict: Dict[str, "np.ndarray | torch.Tensor"], device: int = 0, momentum: float = 0.1, eps: float = 1e-5,
                  coef_cls: float = 1.0, coef_reg: float = 1.0, sync_bn: bool = False, group=None, fused: Optional[bool] = None,
                  two_streams: bool = True, mode: Optional[str] = None, virtual_expansion: int = 32):
@@ -126,26 +146,10 @@ class FEARNetTrainHIP:
         self.lib = load_train_library()
         self.device = torch.device(f"cuda:{int(device)}")
         self.momentum, self.eps = momentum, eps
-        # Three implementations of the trunk's conv + BatchNorm units, the same arithmetic (tests/test_train_head.py pins each
-        # against autograd):
-        #   "block"      (default on one rank) one C-ABI call per inverted-residual block and direction, csrc/fear_train_block.h:
-        #                statistics in the producing pass, BatchNorm / its backward / ReLU masks formed on load, the two
-        #                BatchNorms around the depthwise conv and its three gradients in one LDS-tiled pass
-        #                With SyncBatchNorm (round 6) the ranks' all-reduces are made by the library's hook between a producer's
-        #                float64 sums and their finalize (train_head.SyncHook, include/fear_train.h fear_train_sync_bind)
-        #   "layerwise"  (fused=False) one operator per layer and direction; SyncBatchNorm: all-reduces between the reductions and the applies
-        #   "fused"      (fused=True) round 3's per-unit fused operators, the memory-saving form of "layerwise"
-        if mode is None:
-            mode = "fused" if fused else ("layerwise" if fused is False else "block")
-        if mode not in ("block", "layerwise", "fused"):
-            raise ValueError(f"unknown mode {mode!r}")
-        if mode == "fused" and sync_bn:
-            raise ValueError("mode='fused' has no SyncBatchNorm form; use mode='block' (default) or 'layerwise' with sync_bn")
-        self.mode = mode
+        self.mode = mode = _resolve_mode(mode, fused, sync_bn)
         # block mode: expansions of up to this many input channels are never written where the library has the kernels for it
         # (FEAR_IRB_VIRTUAL_E, include/fear_train.h: the stride-2 blocks); 0 keeps every expansion saved
         self.virtual_expansion = 32 if virtual_expansion is True else int(virtual_expansion)
-        fused = mode == "fused"
         # fused=True: the trunk runs on the fused conv + BatchNorm operators of include/fear_train.h — a BatchNorm'd activation
         # is never written, consumers apply it on load: 11 instead of 16 passes over every saved tensor and 13.7 instead of
         # 21.7 GB at 128 pairs, the same gradients (tests/test_train_head.py) — and, measured, NOT faster: 33.8 vs 31.6 ms of
@@ -154,7 +158,7 @@ class FEARNetTrainHIP:
         # arithmetic added to the weight-gradient loads costs more (+1.9 ms) than the two removed passes save, and the
         # producers' per-workgroup partial sums add finalisation work.  So the default stays one kernel per layer and
         # direction; fused is the memory-saving mode (larger per-rank batches).
-        self.fused = bool(fused)
+        self.fused = mode == "fused"
         # two_streams: the BACKWARD of the template pass (a quarter of the search pass's work, the same launches) runs on a second
         # HIP stream next to the search pass's — the two are independent between the head and the final add of the shared
         # parameters' gradients, and their small kernels fill each other's tails.  Each lane has its own workspace.  SyncBatchNorm:
@@ -163,8 +167,7 @@ class FEARNetTrainHIP:
         self.two_streams = bool(two_streams) and (not sync_bn or mode == "block")
         self._side = None
         self._aux = None
-        self._lane = 0
-        self._ws_lanes = {}
+        self._init_plumbing()
         self.timing = None        # layerwise / fused modes: a list — every pointwise weight-gradient launch is bracketed with events and appended (no effect in block mode: its weight gradients are issued by the C side)
         sd = {k: torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v.detach().cpu() for k, v in state_dict.items()}
         dev = self.device
@@ -218,32 +221,16 @@ class FEARNetTrainHIP:
             layers += [L for L in (blk["pw"], blk["dw"], blk["pwl"]) if L is not None]
         return layers + [self.neck]
 
-    # ------------------------------------------------------------------ plumbing
-    def _check(self, st: int) -> None:
-        if st != 0:
-            self.head._check(st)
-
-    def _stream(self):
-        import ctypes
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _new(self, *shape) -> torch.Tensor:
-        return torch.empty(shape, dtype=torch.float32, device=self.device)
-
+    # ------------------------------------------------------------------ plumbing (_TrainPlumbing)
     def _workspace(self, rows: int):
         return self._lane_workspace(int(self.lib.fear_train_workspace_bytes(rows, 672)))
 
-    def _lane_workspace(self, need: int):
-        ws = self._ws_lanes.get(self._lane)
-        if ws is None or ws.numel() * 4 < need:
-            self._ws_lanes[self._lane] = None
-            ws = self._ws_lanes[self._lane] = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
-        return _p(ws), ws.numel() * 4
-
     # ------------------------------------------------------------------ one conv + BN [+ ReLU]
-    def _fwd(self, L: _ConvBN, x: torch.Tensor, B: int, H: int, saved: list, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x: NHWC rows [B*H*H][cin] (stem: the im2col rows of the output grid).  Returns the activation rows (+ `residual`, the
-        block input, when given: the skip connection is added by the BatchNorm's own apply kernel)."""
+    def _fwd(self, L: _ConvBN, x: torch.Tensor, x_act, B: int, H: int, saved: list, residual: Optional[torch.Tensor] = None,
+             materialise: bool = True):
+        """x: NHWC rows [B*H*H][cin] (stem: the im2col rows of the output grid).  Returns (the activation rows (+ `residual`, the
+        block input, when given: the skip connection is added by the BatchNorm's own apply kernel), None) — the pair `_fwd_f`
+        returns, with nothing left to apply on load: every unit writes its activation (`x_act` is None, `materialise` moot)."""
         lib, st = self.lib, self._stream()
         Ho = H // L.stride if L.kind == "dw" else H
         M = B * Ho * Ho
@@ -273,7 +260,7 @@ class FEARNetTrainHIP:
             self._check(lib.fear_bn_act(_p(pre), L.cout, _p(ab[0]), _p(ab[1]), 1 if L.relu else 0, _p(residual), L.cout, _p(out), L.cout,
                                         M, L.cout, st))
         saved.append((L, x, pre, out, mean, rstd, B, H, ab))
-        return out
+        return out, None
 
     def _gslot(self, gbuf: torch.Tensor, key: str, *shape) -> torch.Tensor:
         n = int(np.prod(shape))
@@ -303,10 +290,21 @@ class FEARNetTrainHIP:
             self._check(lib.fear_bn_backward_apply_x(_p(dy), L.cout, _p(pre), L.cout, _p(ab[0]), _p(ab[1]), 1 if L.relu else 0, _p(mean),
                                                      _p(rstd), _p(L.gamma), _p(sums), float(M) * self.sync.world, _p(local), _p(dpre), L.cout,
                                                      _p(dgamma), _p(dbeta), ws, wsb, M, L.cout, st))
+        return self._bwd_conv(L, x, None, dpre, gbuf, B, H, ws, wsb, need_dx, add)
+
+    def _bwd_conv(self, L: _ConvBN, x: torch.Tensor, x_act, dpre: torch.Tensor, gbuf: torch.Tensor, B: int, H: int, ws, wsb,
+                  need_dx: bool, add: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """The convolution behind a unit's BatchNorm backward: weight gradient into its slot of `gbuf`, then (need_dx) the input
+        gradient with `add` joined — a pass of its own behind the depthwise dgrad, inside the GEMM for pointwise units.
+        `x_act` = (a, b, relu): `x` is a producer's raw output and the activation is applied as it is loaded; None: `x` as it is."""
+        lib, st = self.lib, self._stream()
+        M = dpre.shape[0]
+        ia, ib, irelu = (_p(x_act[0]), _p(x_act[1]), int(x_act[2])) if x_act is not None else (None, None, 0)
         dx = None
         if L.kind == "dw":
             dtaps = self._gslot(gbuf, L.conv_key, L.k * L.k, L.cout)
-            self._check(lib.fear_dw_backward_weight(_p(dpre), L.cout, _p(x), L.cin, _p(dtaps), ws, wsb, B, H, H, L.cin, L.k, L.stride, st))
+            self._check(lib.fear_dw_backward_weight_act(_p(dpre), L.cout, _p(x), L.cin, ia, ib, irelu, _p(dtaps), ws, wsb, B, H, H, L.cin,
+                                                        L.k, L.stride, st))
             if need_dx:
                 dx = self._new(B * H * H, L.cin)
                 self._check(lib.fear_dw_backward_data(_p(dpre), L.cout, _p(L.w), _p(dx), L.cin, B, H, H, L.cin, L.k, L.stride, st))
@@ -317,16 +315,15 @@ class FEARNetTrainHIP:
             if self.timing is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-            self._check(lib.fear_pw_backward_weight(_p(dpre), L.cout, _p(x), L.cin, _p(dw), ws, wsb, M, L.cin, L.cout, st))
+            self._check(lib.fear_pw_backward_weight_act(_p(dpre), L.cout, _p(x), L.cin, ia, ib, irelu, _p(dw), ws, wsb, M, L.cin, L.cout, st))
             if self.timing is not None:
                 e1.record()
                 # algorithmic bytes of dW[n][k] = sum_m dY[m][n] X[m][k]: both operands read once, dW written once
                 self.timing.append((e0, e1, 4.0 * (M * L.cout + M * L.cin + L.cout * L.cin), 2.0 * M * L.cout * L.cin))
-            if L.kind != "stem":
-                if need_dx:
-                    dx = self._new(M, L.cin)
-                    self._check(lib.fear_pw_backward_data(_p(dpre), L.cout, _p(L.w), _p(add), L.cin if add is not None else 0, _p(dx),
-                                                          L.cin, M, L.cin, L.cout, st))
+            if L.kind != "stem" and need_dx:
+                dx = self._new(M, L.cin)
+                self._check(lib.fear_pw_backward_data(_p(dpre), L.cout, _p(L.w), _p(add), L.cin if add is not None else 0, _p(dx), L.cin,
+                                                      M, L.cin, L.cout, st))
         return dx
 
     def _add(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -339,10 +336,12 @@ class FEARNetTrainHIP:
         return self._lane_workspace(max(int(self.lib.fear_train_stats_workspace_bytes(rows, channels)),
                                         int(self.lib.fear_train_workspace_bytes(rows, 672))))
 
-    def _fwd_f(self, L: _ConvBN, x: torch.Tensor, x_act, B: int, H: int, saved: list):
+    def _fwd_f(self, L: _ConvBN, x: torch.Tensor, x_act, B: int, H: int, saved: list, residual: Optional[torch.Tensor] = None,
+               materialise: bool = False):
         """One conv + BatchNorm unit on the fused operators.  x: rows [B*H*H][cin] — a previous unit's RAW conv output when
         `x_act` = (a, b, relu) names the activation to apply on load, else a plain tensor.  Writes this unit's raw output and
-        returns (raw, (a, b, relu)): whoever consumes it applies the BatchNorm [+ ReLU] itself."""
+        returns (raw, (a, b, relu)): whoever consumes it applies the BatchNorm [+ ReLU] itself — or, with `materialise` (block
+        outputs: what a skip connection adds back), (the activation (+ `residual`) as a real tensor, None)."""
         lib, st = self.lib, self._stream()
         Ho = H // L.stride if L.kind == "dw" else H
         M = B * Ho * Ho
@@ -365,7 +364,7 @@ class FEARNetTrainHIP:
                                          _p(L.running_var), self.momentum, self.eps, L.cout, st))
         act = (a, b, 1 if L.relu else 0)
         saved.append(dict(L=L, x=x, x_act=x_act, pre=pre, mean=mean, rstd=rstd, act=act, B=B, H=H))
-        return pre, act
+        return (self._materialise(pre, act, residual), None) if materialise else (pre, act)
 
     def _materialise(self, pre: torch.Tensor, act, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         out = self._new(*pre.shape)
@@ -396,57 +395,7 @@ class FEARNetTrainHIP:
         dgamma, dbeta = self._gslot(gbuf, L.bn_key + ".weight", L.cout), self._gslot(gbuf, L.bn_key + ".bias", L.cout)
         self._check(lib.fear_bn_backward_apply_x(_p(dy), L.cout, _p(pre), L.cout, _p(a), _p(b), relu, _p(mean), _p(rstd), _p(L.gamma),
                                                  _p(sums), count, _p(local), _p(dpre), L.cout, _p(dgamma), _p(dbeta), ws, wsb, M, L.cout, st))
-        ia, ib, irelu = (_p(x_act[0]), _p(x_act[1]), int(x_act[2])) if x_act is not None else (None, None, 0)
-        dx = None
-        if L.kind == "dw":
-            dtaps = self._gslot(gbuf, L.conv_key, L.k * L.k, L.cout)
-            self._check(lib.fear_dw_backward_weight_act(_p(dpre), L.cout, _p(x), L.cin, ia, ib, irelu, _p(dtaps), ws, wsb, B, H, H, L.cin,
-                                                        L.k, L.stride, st))
-            if need_dx:
-                dx = self._new(B * H * H, L.cin)
-                self._check(lib.fear_dw_backward_data(_p(dpre), L.cout, _p(L.w), _p(dx), L.cin, B, H, H, L.cin, L.k, L.stride, st))
-                if add is not None:
-                    self._check(lib.fear_add(_p(dx), _p(add), _p(dx), dx.numel(), st))
-        else:
-            dw = self._gslot(gbuf, L.conv_key, L.cout, L.cin)
-            self._check(lib.fear_pw_backward_weight_act(_p(dpre), L.cout, _p(x), L.cin, ia, ib, irelu, _p(dw), ws, wsb, M, L.cin, L.cout, st))
-            if L.kind != "stem" and need_dx:
-                dx = self._new(M, L.cin)
-                self._check(lib.fear_pw_backward_data(_p(dpre), L.cout, _p(L.w), _p(add), L.cin if add is not None else 0, _p(dx), L.cin,
-                                                      M, L.cin, L.cout, st))
-        return dx
-
-    def _features_forward_f(self, img: torch.Tensor):
-        """Fused form of `_features_forward`: img (B,3,H,H) NCHW -> (feature rows [B*(H/16)^2][256], context for the backward)."""
-        B, H = img.shape[0], img.shape[2]
-        saved: list = []
-        h = H // 2
-        col = self._new(B * h * h, 28)
-        self._check(self.lib.fear_stem_im2col(_p(img), _p(col), B, H, H, self._stream()))
-        pre, act = self._fwd_f(self.stem, col, None, B, h, saved)
-        x = self._materialise(pre, act)                              # block 1 adds it back as its residual: a real tensor
-        block_recs = []
-        for blk in self.blocks:
-            start = len(saved)
-            y, yact = x, None
-            if blk["pw"] is not None:
-                y, yact = self._fwd_f(blk["pw"], y, yact, B, h, saved)
-            y, yact = self._fwd_f(blk["dw"], y, yact, B, h, saved)
-            h = h // blk["dw"].stride
-            y, yact = self._fwd_f(blk["pwl"], y, yact, B, h, saved)
-            x = self._materialise(y, yact, x if blk["residual"] else None)     # BN of the projection (+ residual): the block output
-            block_recs.append((start, len(saved), blk["residual"]))
-        pre, act = self._fwd_f(self.neck, x, None, B, h, saved)
-        return self._materialise(pre, act), (saved, block_recs, B, h)
-
-    def _features_backward_f(self, ctx, dfeat: torch.Tensor, gbuf: torch.Tensor) -> None:
-        saved, block_recs, B, h = ctx
-        d = self._bwd_f(saved[-1], dfeat, gbuf)                      # neck
-        for start, end, residual in reversed(block_recs):
-            dres = d if residual else None
-            for i in range(end - 1, start - 1, -1):
-                d = self._bwd_f(saved[i], d, gbuf, add=dres if i == start else None)     # the block's first unit also takes the skip's gradient
-        self._bwd_f(saved[0], d, gbuf, need_dx=False)                # stem: the image needs no gradient
+        return self._bwd_conv(L, x, x_act, dpre, gbuf, B, H, ws, wsb, need_dx, add)
 
     # ------------------------------------------------------------------ block-fused trunk (mode "block")
     def _irb_descriptors(self):
@@ -487,12 +436,7 @@ class FEARNetTrainHIP:
             h //= d.stride
         need = max(need, int(lib.fear_pwbn_workspace_bytes(B * h * h, 112, 256)))
         ws, wsb = self._lane_workspace(need)
-        key = ("scratch", self._lane)
-        sc = self._ws_lanes.get(key)
-        if sc is None or sc.numel() < scratch:
-            self._ws_lanes[key] = None
-            sc = self._ws_lanes[key] = torch.empty(scratch, dtype=torch.float32, device=self.device)
-        return ws, wsb, sc
+        return ws, wsb, self._lane_buffer("scratch", scratch)
 
     def _features_forward_b(self, img: torch.Tensor, defer_running: bool = False):
         """Block-fused form of `_features_forward`: one call per block (csrc/fear_train_block.h).  `defer_running`: leave the
@@ -581,11 +525,7 @@ class FEARNetTrainHIP:
             for desc in self._irb_descriptors():
                 sizes.append((int(lib.fear_irb_scratch_floats(ctypes.byref(desc), B, h, h)) + 63) // 64 * 64)
                 h //= desc.stride
-            key = ("scratch_all", self._lane)
-            big = self._ws_lanes.get(key)
-            if big is None or big.numel() < sum(sizes):
-                self._ws_lanes[key] = None
-                big = self._ws_lanes[key] = torch.empty(sum(sizes), dtype=torch.float32, device=self.device)
+            big = self._lane_buffer("scratch_all", sum(sizes))
             offs = np.cumsum([0] + sizes)
             per_block = [big[offs[i]: offs[i + 1]] for i in range(len(sizes))]
             big.record_stream(aux)
@@ -627,46 +567,44 @@ class FEARNetTrainHIP:
         # the stem's weight gradient in line as well, on a workspace of its own: the last blocks' weight gradients are still running on
         # the weight-gradient stream (on the shared workspace's row-slice region) when the chain of input gradients ends here — the
         # pass's last kernel runs beside them instead of behind them
-        key = ("stem", self._lane)
-        need = int(lib.fear_stem_workspace_bytes(B, H, H))
-        sw = self._ws_lanes.get(key)
-        if sw is None or sw.numel() * 4 < need:
-            self._ws_lanes[key] = None
-            sw = self._ws_lanes[key] = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
+        sw, swb = self._lane_workspace(int(lib.fear_stem_workspace_bytes(B, H, H)), "stem")
         self._check(lib.fear_stem_train_backward(_p(d), _p(stem_raw), _p(stem_vec), _p(c["img"]), _p(S.gamma), g(S.conv_key, 16 * 28),
-                                                 g(S.bn_key + ".weight", 16), g(S.bn_key + ".bias", 16), B, H, H, _p(sw), sw.numel() * 4, st, None))
+                                                 g(S.bn_key + ".weight", 16), g(S.bn_key + ".bias", 16), B, H, H, sw, swb, st, None))
 
     # ------------------------------------------------------------------ trunk + neck
     def _features_forward(self, img: torch.Tensor):
-        """img (B,3,H,H) NCHW -> (feature rows [B*(H/16)^2][256], saved records for the backward)."""
+        """img (B,3,H,H) NCHW -> (feature rows [B*(H/16)^2][256], saved records for the backward), one operator per layer
+        (`_fwd`) or on the fused units (`_fwd_f`: only the block outputs — what a skip connection adds back — are materialised).
+        A value between two units is (rows, the activation its consumer applies on load or None)."""
+        fwd = self._fwd_f if self.fused else self._fwd
         B, H = img.shape[0], img.shape[2]
         saved: list = []
         h = H // 2
         col = self._new(B * h * h, 28)
         self._check(self.lib.fear_stem_im2col(_p(img), _p(col), B, H, H, self._stream()))
-        x = self._fwd(self.stem, col, B, h, saved)
+        x, _ = fwd(self.stem, col, None, B, h, saved, materialise=True)
         block_recs = []
         for blk in self.blocks:
             start = len(saved)
-            y = x
+            y, yact = x, None
             if blk["pw"] is not None:
-                y = self._fwd(blk["pw"], y, B, h, saved)
-            y = self._fwd(blk["dw"], y, B, h, saved)
+                y, yact = fwd(blk["pw"], y, yact, B, h, saved)
+            y, yact = fwd(blk["dw"], y, yact, B, h, saved)
             h = h // blk["dw"].stride
-            y = self._fwd(blk["pwl"], y, B, h, saved, residual=x if blk["residual"] else None)
+            x, _ = fwd(blk["pwl"], y, yact, B, h, saved, residual=x if blk["residual"] else None, materialise=True)
             block_recs.append((start, len(saved), blk["residual"]))
-            x = y
-        feats = self._fwd(self.neck, x, B, h, saved)
+        feats, _ = fwd(self.neck, x, None, B, h, saved, materialise=True)
         return feats, (saved, block_recs, B, h)
 
     def _features_backward(self, ctx, dfeat: torch.Tensor, gbuf: torch.Tensor) -> None:
+        bwd = self._bwd_f if self.fused else self._bwd
         saved, block_recs, B, h = ctx
-        d = self._bwd(saved[-1], dfeat, gbuf)                        # neck
+        d = bwd(saved[-1], dfeat, gbuf)                              # neck
         for start, end, residual in reversed(block_recs):
             dres = d if residual else None
             for i in range(end - 1, start - 1, -1):
-                d = self._bwd(saved[i], d, gbuf, add=dres if i == start else None)     # the block's first unit also takes the skip's gradient
-        self._bwd(saved[0], d, gbuf, need_dx=False)                  # stem: the image needs no gradient
+                d = bwd(saved[i], d, gbuf, add=dres if i == start else None)     # the block's first unit also takes the skip's gradient
+        bwd(saved[0], d, gbuf, need_dx=False)                        # stem: the image needs no gradient
 
     # ------------------------------------------------------------------ the step
     @torch.no_grad()
@@ -696,8 +634,8 @@ class FEARNetTrainHIP:
         dev = self.device
         if True:
             st = self._stream()
-            ffwd = {"block": self._features_forward_b, "fused": self._features_forward_f, "layerwise": self._features_forward}[self.mode]
-            fbwd = {"block": self._features_backward_b, "fused": self._features_backward_f, "layerwise": self._features_backward}[self.mode]
+            ffwd = self._features_forward_b if self.mode == "block" else self._features_forward
+            fbwd = self._features_backward_b if self.mode == "block" else self._features_backward
             # every gradient of the step lives in one buffer in param_flat's layout (the template pass's trunk gradients behind it)
             gall = torch.zeros(self._ptotal + self._gtotal, dtype=torch.float32, device=dev)      # fresh per step: the caller keeps `grads`
             gflat = (gall[: self._ptotal], gall[self._ptotal:])
