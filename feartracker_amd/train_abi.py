@@ -73,6 +73,8 @@ TRAIN_SYMBOLS = {
     # training pairs from frames (train_data.TrainPairBuilder)
     "fear_frame_border_u8": ([_P, _i, _P, _P], _i),
     "fear_train_pairs": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _P, _P], _i),
+    # step metrics (metrics.TrainMetrics)
+    "fear_train_metrics": ([_P, _P, _P, _P, _P, _i, _i, _P, _P, _P, _P], _i),
 }
 
 

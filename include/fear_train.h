@@ -363,6 +363,23 @@ int fear_frame_border_u8(const fear_frame* frames, int n_frames, uint8_t* out_rg
 int fear_train_pairs(const fear_frame* frames, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom, const uint8_t* lut,
                      int n, float* template_out, float* search_out, float* gt_reg, float* gt_cls, float* gt_weight, void* stream);
 
+/* ---- step metrics: the training telemetry of the reference's `_training_step` (train/fear_lightning_model.py:66-87) on the device
+ * (feartracker_amd/metrics.py).  Per pair: FEARBoxCoder.decode of the step's own output maps (fear_decode's
+ * arithmetic: fp32 sigmoid, first maximum, float64 grid), box_convert(xywh -> xyxy) of the decoded and the ground-truth box, and
+ * torchvision's box_iou of the two in float64, every operation rounded on its own.  Then BoxIoUMetric / TrackingFailureRateMetric
+ * (metrics/tracking.py) and DatasetAwareMetric (metrics/dataset_aware_metric.py), summed in pair-index order (two launches, no atomics):
+ *   cls (B,1,16,16), bbox (B,4,16,16) fp32 : the step's outputs          gt_box (B,4) int32 xywh in the 256 x 256 search crop
+ *   visible (B) int32 : 0 = the pair takes no part                        dataset_id (B) int32 in [0, n_datasets)
+ *   iou (B) float64 out : the pair's IoU, -1 for an invisible pair
+ *   step3 (3) float64 out : mean IoU over the visible pairs | failure rate = 1 - count_nonzero(iou) / n_visible | n_visible
+ *   accum (3 + 2 n_datasets) float64, updated in place (zero it to start an epoch):
+ *       sum of step mean IoUs | sum of step failure rates | steps counted | per dataset sum of IoUs | per dataset pair count
+ * A step with NO visible pair makes the reference take a mean over nothing (NaN, which then stays in its epoch mean); here such a
+ * step writes step3 = {0, 0, 0} and adds nothing to any accumulator — the same kind of deliberate deviation as fear_head_loss's. */
+#define FEAR_METRICS_MAX_DATASETS 64
+int fear_train_metrics(const float* cls, const float* bbox, const int32_t* gt_box, const int32_t* visible, const int32_t* dataset_id,
+                       int B, int n_datasets, double* iou, double* step3, double* accum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
