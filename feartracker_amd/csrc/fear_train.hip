@@ -1589,54 +1589,54 @@ int fear_pw_backward_data(const float* dy, int lddy, const float* w, const float
     return FEAR_TRAIN_OK;
 }
 
-static int wgrad_impl(const float* dy, int lddy, long dy_crop_stride, const float* x, int ldx, long x_crop_stride, float* dw,
-                      float* workspace, size_t ws_bytes, long M, int K, int N, int crops, hipStream_t s, const float* act_a = nullptr,
-                      const float* act_b = nullptr, int act_relu = 0, const BnbIn* bn = nullptr, const StemIn* stem = nullptr) {
+// one pointwise weight-gradient problem dW[N][K] = dY'^T X' over M rows (per crop): what wgrad_impl takes, filled by member name
+struct WgradCall {
+    const float* dy; int lddy; long dy_crop_stride;      // [M][lddy] per crop
+    const float* x; int ldx; long x_crop_stride;         // [M][ldx] per crop (null with `stem`: the rows are gathered from the image)
+    float* dw; float* workspace; size_t ws_bytes;
+    long M; int K, N, crops = 1;
+    hipStream_t s;
+    const float* act_a; const float* act_b; int act_relu;      // optional: X' = act(a X + b)
+    const BnbIn* bn;                                      // optional: dY' = the BatchNorm backward of dY, formed on load
+    const StemIn* stem;                                   // optional: X' = the stem's im2col rows of an NCHW image
+};
+static int wgrad_impl(const WgradCall& c) {
+    const long M = c.M;
+    const int K = c.K, N = c.N, crops = c.crops;
+    float *const dw = c.dw, *const workspace = c.workspace;
+    const size_t ws_bytes = c.ws_bytes; const BnbIn* bn = c.bn; const StemIn* stem = c.stem; hipStream_t s = c.s;
     WgradArgs a{};
     if (stem) {
         if (crops != 1 || K != 28) return FEAR_TRAIN_ERR_SHAPE;
         a.stem = *stem;
     }
-    a.dY = dy; a.X = x; a.lddy = lddy; a.ldx = ldx; a.N = N; a.K = K; a.M = M; a.crops = crops;
-    a.act_a = act_a; a.act_b = act_b; a.act_relu = act_relu;
+    a.dY = c.dy; a.X = c.x; a.lddy = c.lddy; a.ldx = c.ldx; a.N = N; a.K = K; a.M = M; a.crops = crops;
+    a.act_a = c.act_a; a.act_b = c.act_b; a.act_relu = c.act_relu;
     if (bn) {
         if (crops != 1) return FEAR_TRAIN_ERR_SHAPE;
         a.bn = *bn;
     }
-    a.dy_crop_stride = dy_crop_stride; a.x_crop_stride = x_crop_stride;
+    a.dy_crop_stride = c.dy_crop_stride; a.x_crop_stride = c.x_crop_stride;
     // a narrow dY against a wide X (the projections of the large maps): the operands trade places in pw_wgrad_smallk_kernel<., 2>
-    if (crops == 1 && N <= 32 && K > 32 && !stem && !(bn && bn->mask_a) && (!bn || bn->E)) {
-        a.dY = x; a.lddy = ldx; a.N = K; a.X = dy; a.ldx = lddy; a.K = N;
-        a.n_tiles = (K + 63) / 64; a.k_tiles = 1;
-        const WgradPlan plan = wgrad_plan(M, a.n_tiles, (size_t)N * K, 1024, workspace ? ws_bytes : 0);
-        a.rows_per_slice = plan.rows_per_slice;
-        const int slices = plan.slices;
-        if (slices == 1) {
-            a.P = dw;
-        } else {
-            if (!workspace || ws_bytes < (size_t)slices * N * K * sizeof(float)) return FEAR_TRAIN_ERR_WORKSPACE;
-            a.P = workspace;
-        }
-        if (N <= 16) hipLaunchKernelGGL((pw_wgrad_smallk_kernel<1, 2>), dim3(a.n_tiles, slices, 1), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((pw_wgrad_smallk_kernel<2, 2>), dim3(a.n_tiles, slices, 1), dim3(256), 0, s, a);
-        if (slices > 1) launch_slice_sum(workspace, dw, (long)N * K, slices, s);
-        LAUNCH_CHECK();
-        return FEAR_TRAIN_OK;
-    }
-    a.n_tiles = (N + 63) / 64; a.k_tiles = (K + 63) / 64;
+    const bool swapped = crops == 1 && N <= 32 && K > 32 && !stem && !(bn && bn->mask_a) && (!bn || bn->E);
     // 128 x 128 tiles with the rows staged through LDS (wgrad_lds_kernel, fear_train_gemm.h) where both sides are wide enough for
     // the sharing to matter and the launch is one problem, not a batch of per-crop ones
     // (launches of a few thousand rows are a handful of stages per workgroup: the staged kernel's prologue and its two
     //  barriers-per-stage floor — 29 us measured — lose against the 14 us of the register-only kernel there)
-    const bool lds_tile = crops == 1 && K > 32 && N >= 32 && M >= 16384;
+    const bool lds_tile = !swapped && crops == 1 && K > 32 && N >= 32 && M >= 16384;
+    a.n_tiles = (N + 63) / 64; a.k_tiles = (K + 63) / 64;
     if (lds_tile) { a.n_tiles = (N + 127) / 128; a.k_tiles = (K + 127) / 128; }
+    if (swapped) {
+        a.dY = c.x; a.lddy = c.ldx; a.N = K; a.X = c.dy; a.ldx = c.lddy; a.K = N;
+        a.n_tiles = (K + 63) / 64; a.k_tiles = 1;
+    }
     // (per-crop problems are one slice each; one problem is cut by wgrad_plan)
     // at most 256 slices — 1 024 where the partial is small (N * K <= 8 192: the stem and the 16-32-channel layers of the
-    // 128 x 128 / 64 x 64 maps): those layers have millions of rows and ONE or two output tiles, 256 workgroups streamed them
-    // at 1.1 TB/s (the stem's weight gradient: 425 us for 500 MB)
+    // 128 x 128 / 64 x 64 maps) or the operands are swapped: those layers have millions of rows and ONE or two output tiles, 256
+    // workgroups streamed them at 1.1 TB/s (the stem's weight gradient: 425 us for 500 MB)
     const WgradPlan plan = crops > 1 ? WgradPlan{M, 1}
                                      : wgrad_plan(M, K <= 32 ? a.n_tiles : (long)a.n_tiles * a.k_tiles, (size_t)N * K,
-                                                  (long)N * K <= 8192 ? 1024 : 256, workspace ? ws_bytes : 0);
+                                                  swapped || (long)N * K <= 8192 ? 1024 : 256, workspace ? ws_bytes : 0);
     a.rows_per_slice = plan.rows_per_slice;
     const int slices = plan.slices;
     const size_t need = (size_t)slices * crops * N * K * sizeof(float);
@@ -1646,15 +1646,14 @@ static int wgrad_impl(const float* dy, int lddy, long dy_crop_stride, const floa
         if (!workspace || ws_bytes < need) return FEAR_TRAIN_ERR_WORKSPACE;
         a.P = workspace;
     }
-    if (K <= 16) hipLaunchKernelGGL(pw_wgrad_smallk_kernel<1>, dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
+    if (swapped && N <= 16) hipLaunchKernelGGL((pw_wgrad_smallk_kernel<1, 2>), dim3(a.n_tiles, slices, 1), dim3(256), 0, s, a);
+    else if (swapped) hipLaunchKernelGGL((pw_wgrad_smallk_kernel<2, 2>), dim3(a.n_tiles, slices, 1), dim3(256), 0, s, a);
+    else if (K <= 16) hipLaunchKernelGGL(pw_wgrad_smallk_kernel<1>, dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
     else if (K <= 32 && stem) hipLaunchKernelGGL((pw_wgrad_smallk_kernel<2, 1>), dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
     else if (K <= 32) hipLaunchKernelGGL(pw_wgrad_smallk_kernel<2>, dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
     else if (lds_tile) hipLaunchKernelGGL(wgrad_lds_kernel<0>, dim3(a.n_tiles * a.k_tiles, slices), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(pw_wgrad_kernel, dim3(a.n_tiles * a.k_tiles, slices, crops), dim3(256), 0, s, a);
-    if (slices > 1) {
-        const long count = (long)crops * N * K;
-        launch_slice_sum(workspace, dw, count, slices, s);
-    }
+    if (slices > 1) launch_slice_sum(workspace, dw, (long)crops * N * K, slices, s);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }
@@ -1663,7 +1662,8 @@ int fear_pw_backward_weight(const float* dy, int lddy, const float* x, int ldx, 
                             long M, int K, int N, void* stream) {
     if (!dy || !x || !dw) return FEAR_TRAIN_ERR_NULL;
     if (!pw_shape_ok(M, K, N) || !ld_ok(lddy, N) || !ld_ok(ldx, K)) return FEAR_TRAIN_ERR_SHAPE;    // float4 loads of both operands
-    return wgrad_impl(dy, lddy, 0, x, ldx, 0, dw, workspace, ws_bytes, M, K, N, 1, static_cast<hipStream_t>(stream));
+    return wgrad_impl({.dy = dy, .lddy = lddy, .x = x, .ldx = ldx, .dw = dw, .workspace = workspace, .ws_bytes = ws_bytes, .M = M, .K = K, .N = N,
+                       .s = static_cast<hipStream_t>(stream)});
 }
 
 int fear_col_sum(const float* dy, int lddy, float* out, float* workspace, size_t ws_bytes, long M, int C, void* stream) {
@@ -1930,7 +1930,8 @@ int fear_pw_backward_weight_act(const float* dy, int lddy, const float* x, int l
                                 float* dw, float* workspace, size_t ws_bytes, long M, int K, int N, void* stream) {
     if (!dy || !x || !dw || (in_a && !in_b)) return FEAR_TRAIN_ERR_NULL;
     if (!pw_shape_ok(M, K, N) || !ld_ok(lddy, N) || !ld_ok(ldx, K)) return FEAR_TRAIN_ERR_SHAPE;
-    return wgrad_impl(dy, lddy, 0, x, ldx, 0, dw, workspace, ws_bytes, M, K, N, 1, static_cast<hipStream_t>(stream), in_a, in_b, in_relu);
+    return wgrad_impl({.dy = dy, .lddy = lddy, .x = x, .ldx = ldx, .dw = dw, .workspace = workspace, .ws_bytes = ws_bytes, .M = M, .K = K, .N = N,
+                       .s = static_cast<hipStream_t>(stream), .act_a = in_a, .act_b = in_b, .act_relu = in_relu});
 }
 
 int fear_dw_backward_weight_act(const float* dy, int lddy, const float* x, int ldx, const float* in_a, const float* in_b, int in_relu,
@@ -2100,7 +2101,8 @@ int fear_xcorr_backward(const float* ds, int ldds, const float* x, int ldx, cons
     dim3 grid((unsigned)((a.M + 127) / 128));
     launch_pw<false>(train_pick_nt((C + 15) / 16), grid, s, a);
     LAUNCH_CHECK();
-    return wgrad_impl(x, ldx, (long)P * ldx, ds, ldds, (long)P * ldds, dz_nchw, nullptr, 0, P, J, C, B, s);
+    return wgrad_impl({.dy = x, .lddy = ldx, .dy_crop_stride = (long)P * ldx, .x = ds, .ldx = ldds, .x_crop_stride = (long)P * ldds, .dw = dz_nchw, .M = P,
+                       .K = J, .N = C, .crops = B, .s = s});
 }
 
 int fear_exp_head_forward(const float* p, const float* adjust, const float* bias4, float* bbox, long M, void* stream) {

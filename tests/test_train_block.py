@@ -158,6 +158,7 @@ def _irb_case(cfg, B, H, flags, biased):
     assert lib.fear_irb_train_backward(ctypes.byref(blk), ctypes.byref(sv), ctypes.byref(gr), _p(xd), _p(D(rows(dout))), _p(dx), _p(scratch),
                                        B, H, H, _p(ws), ws.numel() * 4, None, None) == 0
     torch.cuda.synchronize()
+    first_gb = [t.clone() for t in gg + gb]
     errs["dx"] = _rel(dx, rows(x.grad))
     errs["d w_dw"] = _rel(gw_dw, p["w_dw"].grad)
     errs["d w_pwl"] = _rel(gw_pwl, p["w_pwl"].grad)
@@ -185,6 +186,18 @@ def _irb_case(cfg, B, H, flags, biased):
     torch.cuda.synchronize()
     assert torch.equal(dx2, dx) and torch.equal(gw2, gw_dw) and torch.equal(gw_pwl2, gw_pwl)
     assert not expand or torch.equal(gw_pw2, gw_pw)
+    if not expand:
+        return      # (without an expansion dx is the depthwise pass's own output: dx = NULL is FEAR_TRAIN_ERR_NULL by design)
+    # ... and without the input gradient (dx = NULL): every weight, gamma and beta gradient as in the first call
+    first = [gw_dw, gw_pwl, gw_pw] + first_gb
+    third = [torch.full_like(t, float("nan")) for t in first]
+    gr.w_dw, gr.w_pwl, gr.w_pw = (t.data_ptr() for t in third[:3])
+    for i in range(3):
+        gr.gamma[i], gr.beta[i] = third[3 + i].data_ptr(), third[6 + i].data_ptr()
+    assert lib.fear_irb_train_backward(ctypes.byref(blk), ctypes.byref(sv), ctypes.byref(gr), _p(xd), _p(keep[-1]), None, _p(scratch),
+                                       B, H, H, _p(ws), ws.numel() * 4, None, None) == 0
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(third, first))
 
 
 @pytest.mark.gpu
