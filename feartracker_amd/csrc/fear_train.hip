@@ -24,12 +24,10 @@ namespace {
 
 using namespace fear;
 
-// (sync_failed: a SyncBatchNorm all-reduce callback of this host thread reported an error since the last check — the finalize helpers
-//  that call it return nothing, fear_train_block.h)
-thread_local int sync_failed = 0;
+// (a failed SyncBatchNorm all-reduce is no state of the thread: the finalize helpers of fear_train_block.h return it to their entry
+//  point, which returns FEAR_TRAIN_ERR_SYNC before anything reads the un-reduced buffer)
 #define LAUNCH_CHECK()                                        \
     do {                                                      \
-        if (sync_failed) { sync_failed = 0; return FEAR_TRAIN_ERR_SYNC; } \
         if (hipGetLastError() != hipSuccess) return FEAR_TRAIN_ERR_HIP; \
     } while (0)
 

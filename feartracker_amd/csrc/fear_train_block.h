@@ -154,13 +154,14 @@ bool sync_of(hipStream_t s, FearSync* out) {
         if (e.used && e.s == s) { *out = e.sy; return true; }
     return false;
 }
-// the caller's all-reduce of n elements of the sync buffer; a failure is reported by the entry point's LAUNCH_CHECK
-void sync_all_reduce(const FearSync& sy, long n, int is_f32, hipStream_t s) {
-    if ((size_t)n * (is_f32 ? 4 : 8) > sy.buf_bytes || sy.all_reduce(sy.user, sy.buf, n, is_f32, s) != 0) sync_failed = 1;
+// the caller's all-reduce of n elements of the sync buffer; false: the callback failed or the buffer is too small — the caller
+// launches nothing that consumes the buffer and its entry point returns FEAR_TRAIN_ERR_SYNC at once
+[[nodiscard]] bool sync_all_reduce(const FearSync& sy, long n, int is_f32, hipStream_t s) {
+    return (size_t)n * (is_f32 ? 4 : 8) <= sy.buf_bytes && sy.all_reduce(sy.user, sy.buf, n, is_f32, s) == 0;
 }
 
-// column-sum partials [blocks][2][C] -> mean | rstd | a | b (vec) + running statistics
-void finalize_forward(const double* partial, int blocks, int C, double count, const float* gamma, const float* beta, float* vec,
+// column-sum partials [blocks][2][C] -> mean | rstd | a | b (vec) + running statistics; false: the all-reduce failed, neither is written
+[[nodiscard]] bool finalize_forward(const double* partial, int blocks, int C, double count, const float* gamma, const float* beta, float* vec,
                       float* running_mean, float* running_var, double momentum, double eps, hipStream_t s, const float* mean_shift = nullptr) {
     ColFinArgs f = col_fin(partial, blocks, C, 0, count);
     f.out1 = vec; f.out2 = vec + C; f.out_a = vec + 2 * C; f.out_b = vec + 3 * C; f.gamma = gamma; f.beta = beta;
@@ -169,14 +170,15 @@ void finalize_forward(const double* partial, int blocks, int C, double count, co
     if (sync_of(s, &sy)) {
         // SyncBatchNorm: this rank's float64 sums -> the ranks' all-reduce -> statistics of all ranks' rows
         finalize_sums(partial, blocks, C, sy.buf, s);
-        sync_all_reduce(sy, 2L * C, 0, s);
+        if (!sync_all_reduce(sy, 2L * C, 0, s)) return false;
         f.partial = sy.buf; f.blocks = 1; f.M = count * sy.world;
     }
     launch_col_finalize(f, s);
+    return true;
 }
 
-// column-sum partials of (g, g * xhat) -> d beta, d gamma, BnbIn coefficients
-void finalize_backward(const double* partial, int blocks, int C, double count, const float* gamma, const float* vec, float* dgamma, float* dbeta,
+// column-sum partials of (g, g * xhat) -> d beta, d gamma, BnbIn coefficients; false: the all-reduce failed, coef is not written
+[[nodiscard]] bool finalize_backward(const double* partial, int blocks, int C, double count, const float* gamma, const float* vec, float* dgamma, float* dbeta,
                        float* coef, hipStream_t s) {
     ColFinArgs f = col_fin(partial, blocks, C, 4, count);
     f.out1 = dbeta; f.out2 = dgamma; f.gamma = gamma; f.mean_in = vec; f.rstd_in = vec + C; f.coef = coef;
@@ -187,10 +189,11 @@ void finalize_backward(const double* partial, int blocks, int C, double count, c
         ColFinArgs r = f;
         r.mode = 6; r.dsum = sy.buf;
         launch_col_finalize(r, s);
-        sync_all_reduce(sy, 2L * C, 0, s);
+        if (!sync_all_reduce(sy, 2L * C, 0, s)) return false;
         f.partial = sy.buf; f.blocks = 1; f.out1 = nullptr; f.out2 = nullptr; f.M = count * sy.world;
     }
     launch_col_finalize(f, s);
+    return true;
 }
 
 // input-gradient GEMM (reduction over Kred, Nout output columns): when the reduction side is the wide one (an expansion's
@@ -226,8 +229,8 @@ void launch_dw_fwd_ks(const DwFwdArgs& a, int sq, dim3 grid, hipStream_t s) {
     else hipLaunchKernelGGL((dw_fwd_kernel<KS, S, 4>), grid, dim3(256), 0, s, a);
 }
 
-// Y = act(X) W^T + sums -> vec:  the forward producer of a pointwise unit
-void pw_forward_unit(const float* x, int ldx, const float* in_vec, int in_relu, const float* w, float* y, long M, int K, int N, const float* gamma,
+// Y = act(X) W^T + sums -> vec:  the forward producer of a pointwise unit (false: finalize_forward's)
+[[nodiscard]] bool pw_forward_unit(const float* x, int ldx, const float* in_vec, int in_relu, const float* w, float* y, long M, int K, int N, const float* gamma,
                      const float* beta, float* vec, float* rm, float* rv, double momentum, double eps, double* col, hipStream_t s,
                      const float* mean_shift = nullptr) {
     int blocks = 0;
@@ -246,16 +249,16 @@ void pw_forward_unit(const float* x, int ldx, const float* in_vec, int in_relu, 
         launch_pw_stat(a, grid, nt, s);
         blocks = (int)grid.x;
     }
-    finalize_forward(col, blocks, N, (double)M, gamma, beta, vec, rm, rv, momentum, eps, s, mean_shift);
+    return finalize_forward(col, blocks, N, (double)M, gamma, beta, vec, rm, rv, momentum, eps, s, mean_shift);
 }
 
-// sums of (g, g * xhat) over rows of (dy, x_raw) [mask: a ReLU behind the BatchNorm] -> d beta, d gamma, coef
-void bn_backward_sums(const float* dy, int lddy, const float* raw, int ldx, const float* vec, int relu, const float* gamma, float* dgamma,
+// sums of (g, g * xhat) over rows of (dy, x_raw) [mask: a ReLU behind the BatchNorm] -> d beta, d gamma, coef (false: finalize_backward's)
+[[nodiscard]] bool bn_backward_sums(const float* dy, int lddy, const float* raw, int ldx, const float* vec, int relu, const float* gamma, float* dgamma,
                       float* dbeta, float* coef, long M, int C, double* col, hipStream_t s) {
     ColArgs a{};
     a.A = dy; a.lda = lddy; a.X = raw; a.ldx = ldx; a.mean = vec; a.rstd = vec + C;
     a.act_a = relu ? vec + 2 * C : nullptr; a.act_b = relu ? vec + 3 * C : nullptr;
-    finalize_backward(col, launch_col_reduce<1>(a, col, M, C, s), C, (double)M, gamma, vec, dgamma, dbeta, coef, s);
+    return finalize_backward(col, launch_col_reduce<1>(a, col, M, C, s), C, (double)M, gamma, vec, dgamma, dbeta, coef, s);
 }
 
 template <int KS, int S>
@@ -486,7 +489,7 @@ int fear_irb_train_forward(const FearIrbBlock* b, const FearIrbSaved* sv, const 
         if (sync_of(s, &sy)) {
             // SyncBatchNorm: the expansion's statistics are linear in (G, column sums) — those are what the ranks add up
             if (hipMemcpyAsync(sy.buf, ws.coef, per * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return FEAR_TRAIN_ERR_HIP;
-            sync_all_reduce(sy, per, 1, s);
+            if (!sync_all_reduce(sy, per, 1, s)) return FEAR_TRAIN_ERR_SYNC;
             if (hipMemcpyAsync(ws.coef, sy.buf, per * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return FEAR_TRAIN_ERR_HIP;
             count1 *= sy.world;
         }
@@ -495,9 +498,10 @@ int fear_irb_train_forward(const FearIrbBlock* b, const FearIrbSaved* sv, const 
                            momentum);
     }
     // expand 1x1 (+ statistics)
-    if (b->expand && !virt)
-        pw_forward_unit(x, b->cin, nullptr, 0, b->w_pw, sv->e, rows_in, b->cin, b->cexp, b->gamma[0], b->beta[0], sv->vec[0], b->running_mean[0],
-                        b->running_var[0], momentum, eps, ws.col, s);
+    if (b->expand && !virt &&
+        !pw_forward_unit(x, b->cin, nullptr, 0, b->w_pw, sv->e, rows_in, b->cin, b->cexp, b->gamma[0], b->beta[0], sv->vec[0], b->running_mean[0],
+                         b->running_var[0], momentum, eps, ws.col, s))
+        return FEAR_TRAIN_ERR_SYNC;
     // depthwise over act1(e) (or over the block input) (+ statistics)
     {
         const DwGeom geo = dw_fwd_geom(b, B, H, W);
@@ -513,12 +517,14 @@ int fear_irb_train_forward(const FearIrbBlock* b, const FearIrbSaved* sv, const 
             dispatch_k_nc(b->k, b->cin, [&](auto KS, auto NC) { hipLaunchKernelGGL((dw_fwd_kernel<KS(), 2, 8, NC()>), grid, dim3(256), 0, s, a); });
         } else if (geo.small_map) hipLaunchKernelGGL((dw_fwd_kernel<5, 1, 8, 0, 8>), grid, dim3(256), 0, s, a);
         else dispatch_ks(b->k, b->stride, [&](auto KS, auto S) { launch_dw_fwd_ks<KS(), S()>(a, geo.sq, grid, s); });
-        finalize_forward(ws.col, geo.wgs_per_slab, b->cexp, (double)rows_out, b->gamma[1], b->beta[1], sv->vec[1], b->running_mean[1],
-                         b->running_var[1], momentum, eps, s);
+        if (!finalize_forward(ws.col, geo.wgs_per_slab, b->cexp, (double)rows_out, b->gamma[1], b->beta[1], sv->vec[1], b->running_mean[1],
+                              b->running_var[1], momentum, eps, s))
+            return FEAR_TRAIN_ERR_SYNC;
     }
     // project 1x1 over act2(d) (+ statistics)
-    pw_forward_unit(sv->d, b->cexp, sv->vec[1], 1, b->w_pwl, sv->p, rows_out, b->cexp, b->cout, b->gamma[2], b->beta[2], sv->vec[2],
-                    b->running_mean[2], b->running_var[2], momentum, eps, ws.col, s);
+    if (!pw_forward_unit(sv->d, b->cexp, sv->vec[1], 1, b->w_pwl, sv->p, rows_out, b->cexp, b->cout, b->gamma[2], b->beta[2], sv->vec[2],
+                         b->running_mean[2], b->running_var[2], momentum, eps, ws.col, s))
+        return FEAR_TRAIN_ERR_SYNC;
     // block output = BN3(p) [+ x]
     launch_bn_act(sv->p, b->residual ? x : nullptr, out, sv->vec[2], 0, rows_out, b->cout, b->cout, b->cin, b->cout, s);
     LAUNCH_CHECK();
@@ -545,7 +551,8 @@ int fear_irb_train_backward(const FearIrbBlock* b, const FearIrbSaved* sv, const
     // backward — every kernel of a 16 x 16 map is a few hundred workgroups and leaves most of the device idle on its own
     hipStream_t sw = wgrad_stream ? static_cast<hipStream_t>(wgrad_stream) : s;
     // BN3 (no ReLU): sums over (dout, p)
-    bn_backward_sums(dout, cout, sv->p, cout, sv->vec[2], 0, b->gamma[2], gr->gamma[2], gr->beta[2], sc.coef3, rows_out, cout, ws.col, s);
+    if (!bn_backward_sums(dout, cout, sv->p, cout, sv->vec[2], 0, b->gamma[2], gr->gamma[2], gr->beta[2], sc.coef3, rows_out, cout, ws.col, s))
+        return FEAR_TRAIN_ERR_SYNC;
     BnbIn bn3{};
     bn3.E = sv->p; bn3.coef = sc.coef3; bn3.lde = cout; bn3.C = cout;
     // g2 = (dp W3) masked by act2(d) > 0, + sums of (g2, dhat)
@@ -554,7 +561,8 @@ int fear_irb_train_backward(const FearIrbBlock* b, const FearIrbSaved* sv, const
                                         .D = sv->d, .ldd = cexp, .dvec = sv->vec[1], .partial = ws.col, .partial_bytes = ws.col_bytes, .p3 = sc.w3g},
                                        s, &w3g_slices);
     if (blocks < 0) return blocks;
-    finalize_backward(ws.col, blocks, cexp, (double)rows_out, b->gamma[1], sv->vec[1], gr->gamma[1], gr->beta[1], sc.coef2, s);
+    if (!finalize_backward(ws.col, blocks, cexp, (double)rows_out, b->gamma[1], sv->vec[1], gr->gamma[1], gr->beta[1], sc.coef2, s))
+        return FEAR_TRAIN_ERR_SYNC;
     // dW3 = dp^T act2(d)
     if (sw != s && !stream_follow(sw, s)) return FEAR_TRAIN_ERR_HIP;      // coef3 exists
     if (w3g_slices) {
@@ -591,8 +599,9 @@ int fear_irb_train_backward(const FearIrbBlock* b, const FearIrbSaved* sv, const
             });
         } else if (geo.small_map) hipLaunchKernelGGL((dw_bwd_kernel<5, 1, 8, true, 0, 8>), grid, dim3(256), 0, s, a);
         else dispatch_ks(b->k, b->stride, [&](auto KS, auto S) { launch_dw_bwd_ks<KS(), S()>(a, geo.sq, b->expand != 0, grid, s); });
-        if (b->expand)
-            finalize_backward(ws.col, a.wgs_per_slab, cexp, (double)rows_in, b->gamma[0], sv->vec[0], gr->gamma[0], gr->beta[0], sc.coef1, s);
+        if (b->expand &&
+            !finalize_backward(ws.col, a.wgs_per_slab, cexp, (double)rows_in, b->gamma[0], sv->vec[0], gr->gamma[0], gr->beta[0], sc.coef1, s))
+            return FEAR_TRAIN_ERR_SYNC;
         // the tap gradients' final sum is a weight gradient too: off the chain (the partials live in the call's private scratch)
         if (sw != s && !stream_follow(sw, s)) return FEAR_TRAIN_ERR_HIP;          // the partials, g1 and coef1 exist
         launch_slice_sum(sc.taps, gr->w_dw, (long)b->k * b->k * cexp, a.wgs_per_slab, sw);
@@ -655,13 +664,16 @@ int fear_bn_running_update(const float* vec, double count, float* running_mean, 
 int fear_bn_running_update_multi(const FearBnRunning* items, int n, double momentum, double eps, void* stream) {
     if (!items || n < 0) return FEAR_TRAIN_ERR_NULL;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int i = 0; i < n; ++i) {      // every item before the first launch: an error leaves all n BatchNorms as they were
+        const FearBnRunning& it = items[i];
+        if (!it.vec || !it.running_mean || !it.running_var) return FEAR_TRAIN_ERR_NULL;
+        if (it.C < 1 || !(it.count >= 1.0)) return FEAR_TRAIN_ERR_SHAPE;
+    }
     for (int i0 = 0; i0 < n; i0 += 64) {
         BnRunMulti t{};
         const int m = n - i0 < 64 ? n - i0 : 64;
         for (int i = 0; i < m; ++i) {
             const FearBnRunning& it = items[i0 + i];
-            if (!it.vec || !it.running_mean || !it.running_var) return FEAR_TRAIN_ERR_NULL;
-            if (it.C < 1 || !(it.count >= 1.0)) return FEAR_TRAIN_ERR_SHAPE;
             t.vec[i] = it.vec; t.rm[i] = it.running_mean; t.rv[i] = it.running_var; t.C[i] = it.C; t.count[i] = it.count;
         }
         hipLaunchKernelGGL(bn_running_update_multi_kernel, dim3((unsigned)m), dim3(256), 0, s, t, momentum, eps);
@@ -683,7 +695,8 @@ int fear_pwbn_train_forward(const float* x, int ldx, const float* w, const float
     const BlockWs ws = block_ws(M, M, K, N, N, 3, workspace);
     if (ws_bytes < ws.total) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    pw_forward_unit(x, ldx, nullptr, 0, w, raw, M, K, N, gamma, beta, vec, running_mean, running_var, momentum, eps, ws.col, s);
+    if (!pw_forward_unit(x, ldx, nullptr, 0, w, raw, M, K, N, gamma, beta, vec, running_mean, running_var, momentum, eps, ws.col, s))
+        return FEAR_TRAIN_ERR_SYNC;
     launch_bn_act(raw, nullptr, out, vec, relu, M, N, N, 0, N, s);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
@@ -701,7 +714,7 @@ int fear_pwbn_train_backward(const float* dy, const float* raw, const float* vec
     // (this unit's coefficient vectors live in the shared workspace: whatever an earlier call left running on the weight-gradient
     //  stream may still read them — it is waited for first)
     if (sw != s && !stream_follow(s, sw)) return FEAR_TRAIN_ERR_HIP;
-    bn_backward_sums(dy, N, raw, N, vec, relu, gamma, dgamma, dbeta, ws.coef, M, N, ws.col, s);
+    if (!bn_backward_sums(dy, N, raw, N, vec, relu, gamma, dgamma, dbeta, ws.coef, M, N, ws.col, s)) return FEAR_TRAIN_ERR_SYNC;
     BnbIn bn{};
     bn.E = raw; bn.coef = ws.coef; bn.lde = N; bn.C = N;
     if (relu) { bn.mask_a = vec + 2 * N; bn.mask_b = vec + 3 * N; }
@@ -751,8 +764,9 @@ int fear_sepbn_train_forward(const FearSepLayer* L, const float* x, int ldx, flo
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = dw_impl(x, ldx, L->w_dw, L->b_dw, d, K, B, H, W, K, 3, 1, s);
     if (rc != FEAR_TRAIN_OK) return rc;
-    pw_forward_unit(d, K, nullptr, 0, L->w_pw, raw, M, K, N, L->gamma, L->beta, vec, L->running_mean, L->running_var, momentum, eps, ws.col, s,
-                    L->b_pw);
+    if (!pw_forward_unit(d, K, nullptr, 0, L->w_pw, raw, M, K, N, L->gamma, L->beta, vec, L->running_mean, L->running_var, momentum, eps, ws.col, s,
+                         L->b_pw))
+        return FEAR_TRAIN_ERR_SYNC;
     launch_bn_act(raw, nullptr, out, vec, 1, M, N, N, 0, ldo, s);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
@@ -771,7 +785,7 @@ int fear_sepbn_train_backward(const FearSepLayer* L, const FearSepGrads* gr, con
     if (ws_bytes < ws.total) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipStream_t sw = wgrad_stream ? static_cast<hipStream_t>(wgrad_stream) : s;
-    bn_backward_sums(dy, N, raw, N, vec, 1, L->gamma, gr->gamma, gr->beta, coef, M, N, ws.col, s);
+    if (!bn_backward_sums(dy, N, raw, N, vec, 1, L->gamma, gr->gamma, gr->beta, coef, M, N, ws.col, s)) return FEAR_TRAIN_ERR_SYNC;
     BnbIn bn{};
     bn.E = raw; bn.coef = coef; bn.lde = N; bn.C = N; bn.mask_a = vec + 2 * N; bn.mask_b = vec + 3 * N;
     launch_bnb_gemm({.X = dy, .ldx = N, .bn = bn, .W = L->w_pw, .Y = dd, .ldy = K, .M = M, .K = N, .N = K}, s);
@@ -813,7 +827,7 @@ int fear_stem_train_forward(const float* x_nchw, const float* w, const float* ga
     const dim3 grid = stat_grid(M, 28, 16, &nt, &a.row_tiles);      // (16 output channels: one column tile, nt = 1)
     if (nt != 1 || (size_t)grid.x * 2 * 16 * sizeof(double) > ws.col_bytes) return FEAR_TRAIN_ERR_WORKSPACE;
     hipLaunchKernelGGL((pw_stat_kernel<1, true>), grid, dim3(256), 0, s, a);
-    finalize_forward(ws.col, (int)grid.x, 16, (double)M, gamma, beta, vec, running_mean, running_var, momentum, eps, s);
+    if (!finalize_forward(ws.col, (int)grid.x, 16, (double)M, gamma, beta, vec, running_mean, running_var, momentum, eps, s)) return FEAR_TRAIN_ERR_SYNC;
     launch_bn_act(raw, nullptr, out, vec, 1, M, 16, 16, 0, 16, s);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
@@ -830,7 +844,7 @@ int fear_stem_train_backward(const float* dy, const float* raw, const float* vec
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipStream_t sw = wgrad_stream ? static_cast<hipStream_t>(wgrad_stream) : s;
     if (sw != s && !stream_follow(s, sw)) return FEAR_TRAIN_ERR_HIP;      // (the coefficient vectors live in the shared workspace, as in fear_pwbn_train_backward)
-    bn_backward_sums(dy, 16, raw, 16, vec, 1, gamma, dgamma, dbeta, ws.coef, M, 16, ws.col, s);
+    if (!bn_backward_sums(dy, 16, raw, 16, vec, 1, gamma, dgamma, dbeta, ws.coef, M, 16, ws.col, s)) return FEAR_TRAIN_ERR_SYNC;
     BnbIn bn{};
     bn.E = raw; bn.coef = ws.coef; bn.lde = 16; bn.C = 16; bn.mask_a = vec + 2 * 16; bn.mask_b = vec + 3 * 16;
     if (sw != s && !stream_follow(sw, s)) return FEAR_TRAIN_ERR_HIP;

@@ -35,6 +35,11 @@ extern "C" {
 #define FEAR_TRAIN_ERR_HIP (-4)
 #define FEAR_TRAIN_ERR_WORKSPACE (-7)   /* workspace missing or too small */
 #define FEAR_TRAIN_ERR_SYNC (-8)        /* the SyncBatchNorm all-reduce callback failed, or its buffer is too small (fear_train_sync_bind) */
+/* After FEAR_TRAIN_ERR_SYNC a caller may rely on this: the call returned right after the failed all-reduce, without launching what
+ * would have read the un-reduced buffer — running_mean, running_var and `vec` of the failed BatchNorm and of every BatchNorm behind it
+ * in the call are NOT written (a block's BatchNorms that completed before it keep their update); every other output of the call
+ * (raw tensors, local d gamma / d beta, scratch, workspace) is unspecified.  The failure is not remembered: the next call on the same
+ * host thread, bound or not, starts clean, so the step can be retried once the collective works again. */
 
 size_t fear_train_workspace_bytes(long rows, int max_channels);
 

@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from syncref import pwbn_autograd, sepbn_autograd, stem_autograd
+
 
 def _rel(a, b):
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
@@ -61,7 +63,7 @@ ALL_CASES = [(c, b, h, 0) for c, b, h in CASES] + LIN_CASES
 @pytest.mark.parametrize("cfg,B,H,flags", ALL_CASES,
                          ids=[f"{c[0]}x{c[1]}x{c[2]}k{c[3]}s{c[4]}_b{b}h{h}" + {0: "", 1: "_lin", 2: "_nolin", 4: "_virtual", 8: "_fusew3"}[f] for c, b, h, f in ALL_CASES])
 def test_irb_block_forward_backward_vs_autograd(cfg, B, H, flags):
-    _irb_case(cfg, B, H, flags, biased=False)
+    _irb_case(cfg, B, H, H, flags, biased=False)
 
 
 BIASED_CASES = [((16, 96, 24, 3, 2, 1, 0), 3, 32, 4), ((24, 144, 32, 5, 2, 1, 0), 2, 32, 4), ((32, 192, 64, 5, 2, 1, 0), 2, 32, 4),
@@ -75,19 +77,34 @@ def test_irb_block_on_biased_correlated_inputs(cfg, B, H, flags):
     above feed zero-mean uncorrelated inputs, the benign case.  Real block inputs are post-ReLU / residual: here every channel is
     relu(noise) + 3 plus a component shared by all channels (mean ~ 4 x the spread, channels correlated at 0.5), on the virtual
     blocks, an E-free one and a plain one — the same 2e-4 against float64 autograd, running statistics included."""
-    _irb_case(cfg, B, H, flags, biased=True)
+    _irb_case(cfg, B, H, H, flags, biased=True)
 
 
-def _irb_case(cfg, B, H, flags, biased):
+# Rectangular maps (the ABI takes H and W separately and irb_shape_ok accepts any pair): wide and tall, a stride-2 virtual expansion,
+# the 8-row small-map kernel with a 16-wide map, the fused projection weight gradient — a swapped H / W in a tile count, a halo index
+# or Ho / Wo shows in none of the square cases above
+RECT_CASES = [((16, 96, 24, 3, 2, 1, 0), 2, 16, 48, 0), ((16, 96, 24, 3, 2, 1, 0), 2, 16, 48, 4), ((32, 192, 32, 5, 1, 1, 1), 2, 24, 8, 0),
+              ((112, 672, 112, 5, 1, 1, 1), 2, 8, 16, 0), ((16, 16, 16, 3, 1, 0, 1), 2, 40, 24, 0), ((16, 16, 16, 3, 1, 0, 1), 2, 40, 24, 8),
+              ((24, 144, 32, 5, 2, 1, 0), 2, 32, 16, 4)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg,B,H,W,flags", RECT_CASES,
+                         ids=[f"{c[0]}x{c[1]}x{c[2]}k{c[3]}s{c[4]}_b{b}h{h}w{w}" + {0: "", 4: "_virtual", 8: "_fusew3"}[f] for c, b, h, w, f in RECT_CASES])
+def test_irb_block_on_rectangular_maps(cfg, B, H, W, flags):
+    _irb_case(cfg, B, H, W, flags, biased=False)
+
+
+def _irb_case(cfg, B, H, W, flags, biased):
     from feartracker_amd.train_head import FearIrbBlock, FearIrbGrads, FearIrbSaved, _p, load_train_library
     lib = load_train_library()
     dev = torch.device("cuda:0")
     cin, cexp, cout, k, stride, expand, residual = cfg
     g = torch.Generator().manual_seed(100 + cin + cexp + k + stride + H)
-    Ho = H // stride
-    x = torch.randn(B, cin, H, H, generator=g, dtype=torch.float64)
+    Ho, Wo = H // stride, W // stride
+    x = torch.randn(B, cin, H, W, generator=g, dtype=torch.float64)
     if biased:
-        shared = torch.randn(B, 1, H, H, generator=g, dtype=torch.float64)
+        shared = torch.randn(B, 1, H, W, generator=g, dtype=torch.float64)
         x = (torch.relu(x) * 0.7 + shared * 0.7 + 3.0)
     x.requires_grad_(True)
     p = {"w_dw": torch.randn(k * k, cexp, generator=g, dtype=torch.float64) * (2.0 / (k * k)) ** 0.5,
@@ -126,21 +143,21 @@ def _irb_case(cfg, B, H, flags, biased):
         gam.append(D(p[f"g{i}"])); bet.append(D(p[f"b{i}"]))
         rm.append(torch.zeros(chans[i], device=dev)); rv.append(torch.ones(chans[i], device=dev))
         blk.gamma[i], blk.beta[i], blk.running_mean[i], blk.running_var[i] = gam[i].data_ptr(), bet[i].data_ptr(), rm[i].data_ptr(), rv[i].data_ptr()
-    wsb = int(lib.fear_irb_workspace_bytes(ctypes.byref(blk), B, H, H))
+    wsb = int(lib.fear_irb_workspace_bytes(ctypes.byref(blk), B, H, W))
     assert wsb > 0
     ws = torch.empty(wsb // 4 + 64, device=dev)
-    scratch = torch.empty(int(lib.fear_irb_scratch_floats(ctypes.byref(blk), B, H, H)) + 64, device=dev)
+    scratch = torch.empty(int(lib.fear_irb_scratch_floats(ctypes.byref(blk), B, H, W)) + 64, device=dev)
     sv = FearIrbSaved()
-    e = torch.empty(B * H * H, cexp, device=dev) if expand and not flags & 4 else None
+    e = torch.empty(B * H * W, cexp, device=dev) if expand and not flags & 4 else None
     assert not flags & 4 or lib.fear_irb_virtual_ok(ctypes.byref(blk)) == 1
-    d, pp = torch.empty(B * Ho * Ho, cexp, device=dev), torch.empty(B * Ho * Ho, cout, device=dev)
+    d, pp = torch.empty(B * Ho * Wo, cexp, device=dev), torch.empty(B * Ho * Wo, cout, device=dev)
     vec = [torch.empty(4 * c, device=dev) for c in chans]
     sv.e, sv.d, sv.p = (e.data_ptr() if e is not None else None), d.data_ptr(), pp.data_ptr()
     for i in range(3):
         sv.vec[i] = vec[i].data_ptr()
     xd = D(rows(x))
-    out = torch.empty(B * Ho * Ho, cout, device=dev)
-    assert lib.fear_irb_train_forward(ctypes.byref(blk), ctypes.byref(sv), _p(xd), _p(out), B, H, H, 0.1, 1e-5, _p(ws), ws.numel() * 4, None) == 0
+    out = torch.empty(B * Ho * Wo, cout, device=dev)
+    assert lib.fear_irb_train_forward(ctypes.byref(blk), ctypes.byref(sv), _p(xd), _p(out), B, H, W, 0.1, 1e-5, _p(ws), ws.numel() * 4, None) == 0
     torch.cuda.synchronize()
     errs = {"out": _rel(out, rows(ref))}
     for i in range(0 if expand else 1, 3):
@@ -154,9 +171,9 @@ def _irb_case(cfg, B, H, flags, biased):
     for i in range(3):
         gg.append(torch.full((chans[i],), float("nan"), device=dev)); gb.append(torch.full((chans[i],), float("nan"), device=dev))
         gr.gamma[i], gr.beta[i] = gg[i].data_ptr(), gb[i].data_ptr()
-    dx = torch.full((B * H * H, cin), float("nan"), device=dev)
+    dx = torch.full((B * H * W, cin), float("nan"), device=dev)
     assert lib.fear_irb_train_backward(ctypes.byref(blk), ctypes.byref(sv), ctypes.byref(gr), _p(xd), _p(D(rows(dout))), _p(dx), _p(scratch),
-                                       B, H, H, _p(ws), ws.numel() * 4, None, None) == 0
+                                       B, H, W, _p(ws), ws.numel() * 4, None, None) == 0
     torch.cuda.synchronize()
     first_gb = [t.clone() for t in gg + gb]
     errs["dx"] = _rel(dx, rows(x.grad))
@@ -182,7 +199,7 @@ def _irb_case(cfg, B, H, flags, biased):
         gr.w_pw = gw_pw2.data_ptr()
     aux = torch.cuda.Stream()
     assert lib.fear_irb_train_backward(ctypes.byref(blk), ctypes.byref(sv), ctypes.byref(gr), _p(xd), _p(keep[-1]), _p(dx2), _p(scratch),
-                                       B, H, H, _p(ws), ws.numel() * 4, None, ctypes.c_void_p(aux.cuda_stream)) == 0
+                                       B, H, W, _p(ws), ws.numel() * 4, None, ctypes.c_void_p(aux.cuda_stream)) == 0
     torch.cuda.synchronize()
     assert torch.equal(dx2, dx) and torch.equal(gw2, gw_dw) and torch.equal(gw_pwl2, gw_pwl)
     assert not expand or torch.equal(gw_pw2, gw_pw)
@@ -195,7 +212,7 @@ def _irb_case(cfg, B, H, flags, biased):
     for i in range(3):
         gr.gamma[i], gr.beta[i] = third[3 + i].data_ptr(), third[6 + i].data_ptr()
     assert lib.fear_irb_train_backward(ctypes.byref(blk), ctypes.byref(sv), ctypes.byref(gr), _p(xd), _p(keep[-1]), None, _p(scratch),
-                                       B, H, H, _p(ws), ws.numel() * 4, None, None) == 0
+                                       B, H, W, _p(ws), ws.numel() * 4, None, None) == 0
     torch.cuda.synchronize()
     assert all(torch.equal(a, b) for a, b in zip(third, first))
 
@@ -208,15 +225,12 @@ def test_pwbn_unit_forward_backward_vs_autograd(M, K, N, relu, need_dx):
     lib = load_train_library()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(5 + K + N)
-    x = torch.randn(M, K, generator=g, dtype=torch.float64, requires_grad=True)
-    w = (torch.randn(N, K, generator=g, dtype=torch.float64) * 0.3).requires_grad_(True)
-    gamma = (torch.rand(N, generator=g, dtype=torch.float64) + 0.5).requires_grad_(True)
-    beta = (torch.randn(N, generator=g, dtype=torch.float64) * 0.3).requires_grad_(True)
-    rm_ref, rv_ref = torch.zeros(N, dtype=torch.float64), torch.ones(N, dtype=torch.float64)
-    y = F.batch_norm((x @ w.t()).t().reshape(1, N, M, 1), rm_ref, rv_ref, gamma, beta, True, 0.1, 1e-5).reshape(N, M).t()
-    y = F.relu(y) if relu else y
+    x = torch.randn(M, K, generator=g, dtype=torch.float64)
+    w = torch.randn(N, K, generator=g, dtype=torch.float64) * 0.3
+    gamma = torch.rand(N, generator=g, dtype=torch.float64) + 0.5
+    beta = torch.randn(N, generator=g, dtype=torch.float64) * 0.3
     dy = torch.randn(M, N, generator=g, dtype=torch.float64)
-    y.backward(dy)
+    ref = pwbn_autograd(x, w, gamma, beta, relu, dy)      # (tests/syncref.py: the two-rank tests compare with the same reference)
     D = lambda t: t.detach().to(dev, torch.float32).contiguous()
     xd, wd, gd, bd, dyd = D(x), D(w), D(gamma), D(beta), D(dy)
     rm, rv = torch.zeros(N, device=dev), torch.ones(N, device=dev)
@@ -229,10 +243,10 @@ def test_pwbn_unit_forward_backward_vs_autograd(M, K, N, relu, need_dx):
     assert lib.fear_pwbn_train_backward(_p(dyd), _p(raw), _p(vec), relu, _p(xd), K, _p(wd), _p(gd), _p(dw), _p(dg), _p(db), _p(dx), M, K, N,
                                         _p(ws), ws.numel() * 4, None, None) == 0
     torch.cuda.synchronize()
-    errs = {"out": _rel(out, y), "running_mean": _rel(rm, rm_ref), "running_var": _rel(rv, rv_ref), "dw": _rel(dw, w.grad),
-            "dgamma": _rel(dg, gamma.grad), "dbeta": _rel(db, beta.grad)}
+    errs = {"out": _rel(out, ref["out"]), "running_mean": _rel(rm, ref["running_mean"]), "running_var": _rel(rv, ref["running_var"]),
+            "dw": _rel(dw, ref["d w"]), "dgamma": _rel(dg, ref["d gamma"]), "dbeta": _rel(db, ref["d beta"])}
     if need_dx:
-        errs["dx"] = _rel(dx, x.grad)
+        errs["dx"] = _rel(dx, ref["dx"])
     print({k_: f"{v:.1e}" for k_, v in errs.items()})
     bad = {k_: v for k_, v in errs.items() if not v < 2e-4}
     assert not bad, bad
@@ -242,6 +256,15 @@ def test_pwbn_unit_forward_backward_vs_autograd(M, K, N, relu, need_dx):
 @pytest.mark.parametrize("B,H,cin,cout,bias,ldx_pad,ldo_pad", [(3, 16, 256, 256, True, 0, 0), (2, 16, 320, 256, True, 0, 64), (2, 8, 64, 48, False, 16, 0),
                                                             (40, 16, 256, 256, True, 0, 0)])
 def test_sepbn_layer_forward_backward_vs_autograd(B, H, cin, cout, bias, ldx_pad, ldo_pad):
+    _sepbn_case(B, H, H, cin, cout, bias, ldx_pad, ldo_pad)
+
+
+@pytest.mark.gpu
+def test_sepbn_layer_on_a_rectangular_map():
+    _sepbn_case(2, 8, 24, 64, 48, False, 16, 0)
+
+
+def _sepbn_case(B, H, W, cin, cout, bias, ldx_pad, ldo_pad):
     """The head's layer — SepConv (3x3 depthwise + pointwise, with or without biases) + BatchNorm + ReLU, model_training/model/
     blocks.py:97-101 / 115-119 / 151-161 — as one call per direction; input / output rows with a pitch (the [encode | correlation]
     concatenation); the weight gradients on a second stream are bit-identical to the in-line ones.  The last case's 10 240 rows reach
@@ -250,21 +273,18 @@ def test_sepbn_layer_forward_backward_vs_autograd(B, H, cin, cout, bias, ldx_pad
     lib = load_train_library()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(11 + cin + cout + B)
-    M = B * H * H
+    M = B * H * W
     R = lambda *s, scale=1.0: (torch.randn(*s, generator=g, dtype=torch.float64) * scale)
-    x = R(B, cin, H, H).requires_grad_(True)
-    taps = R(9, cin, scale=0.4).requires_grad_(True)
-    w = R(cout, cin, scale=(2.0 / cin) ** 0.5).requires_grad_(True)
-    b_dw = R(cin, scale=0.3).requires_grad_(True) if bias else None
-    b_pw = R(cout, scale=0.3).requires_grad_(True) if bias else None
-    gamma = (torch.rand(cout, generator=g, dtype=torch.float64) + 0.5).requires_grad_(True)
-    beta = R(cout, scale=0.3).requires_grad_(True)
-    rm_ref, rv_ref = torch.zeros(cout, dtype=torch.float64), torch.ones(cout, dtype=torch.float64)
-    d_ref = F.conv2d(x, taps.t().reshape(cin, 1, 3, 3), b_dw, padding=1, groups=cin)
-    y = F.relu(F.batch_norm(F.conv2d(d_ref, w.view(cout, cin, 1, 1), b_pw), rm_ref, rv_ref, gamma, beta, True, 0.1, 1e-5))
-    dy = R(B, cout, H, H)
-    y.backward(dy)
+    x = R(B, cin, H, W)
+    taps = R(9, cin, scale=0.4)
+    w = R(cout, cin, scale=(2.0 / cin) ** 0.5)
+    b_dw = R(cin, scale=0.3) if bias else None
+    b_pw = R(cout, scale=0.3) if bias else None
+    gamma = torch.rand(cout, generator=g, dtype=torch.float64) + 0.5
+    beta = R(cout, scale=0.3)
+    dy = R(B, cout, H, W)
     rows = lambda t: t.detach().permute(0, 2, 3, 1).reshape(M, -1)
+    ref = sepbn_autograd(x, taps, w, b_dw, b_pw, gamma, beta, rows(dy))      # (tests/syncref.py, shared with the two-rank tests)
     D = lambda t: None if t is None else t.detach().to(dev, torch.float32).contiguous()
     ldx, ldo = cin + ldx_pad, cout + ldo_pad
     xd = torch.zeros(M, ldx, device=dev)
@@ -273,10 +293,10 @@ def test_sepbn_layer_forward_backward_vs_autograd(B, H, cin, cout, bias, ldx_pad
     rm, rv = torch.zeros(cout, device=dev), torch.ones(cout, device=dev)
     ptr = lambda t: None if t is None else t.data_ptr()
     L = FearSepLayer(cin, cout, ptr(td), ptr(bdw), ptr(wd), ptr(bpw), ptr(gd), ptr(bd), ptr(rm), ptr(rv))
-    ws = torch.empty(int(lib.fear_sepbn_workspace_bytes(ctypes.byref(L), B, H, H)) // 4 + 64, device=dev)
+    ws = torch.empty(int(lib.fear_sepbn_workspace_bytes(ctypes.byref(L), B, H, W)) // 4 + 64, device=dev)
     d, raw, vec = torch.empty(M, cin, device=dev), torch.empty(M, cout, device=dev), torch.empty(4 * cout, device=dev)
     out = torch.full((M, ldo), 7.0, device=dev)
-    assert lib.fear_sepbn_train_forward(ctypes.byref(L), _p(xd), ldx, _p(d), _p(raw), _p(vec), _p(out), ldo, B, H, H, 0.1, 1e-5, _p(ws),
+    assert lib.fear_sepbn_train_forward(ctypes.byref(L), _p(xd), ldx, _p(d), _p(raw), _p(vec), _p(out), ldo, B, H, W, 0.1, 1e-5, _p(ws),
                                         ws.numel() * 4, None) == 0
 
     def backward(aux):
@@ -284,20 +304,20 @@ def test_sepbn_layer_forward_backward_vs_autograd(B, H, cin, cout, bias, ldx_pad
         dd, coef, dx = torch.empty(M, cin, device=dev), torch.empty(4 * cout, device=dev), torch.empty(M, cin, device=dev)
         G = FearSepGrads(gt.data_ptr(), gw.data_ptr(), gg.data_ptr(), gb.data_ptr())
         assert lib.fear_sepbn_train_backward(ctypes.byref(L), ctypes.byref(G), _p(xd), ldx, _p(d), _p(raw), _p(vec), _p(dyd), _p(dd), _p(coef),
-                                             _p(dx), B, H, H, _p(ws), ws.numel() * 4, None,
+                                             _p(dx), B, H, W, _p(ws), ws.numel() * 4, None,
                                              ctypes.c_void_p(aux.cuda_stream) if aux is not None else None) == 0
         torch.cuda.synchronize()
         return gt, gw, gg, gb, dx
     gt, gw, gg, gb, dx = backward(None)
-    errs = {"out": _rel(out[:, :cout], rows(y)), "running_mean": _rel(rm, rm_ref), "running_var": _rel(rv, rv_ref), "d": _rel(d, rows(d_ref)),
-            "dtaps": _rel(gt, taps.grad), "dw": _rel(gw, w.grad), "dgamma": _rel(gg, gamma.grad), "dbeta": _rel(gb, beta.grad),
-            "dx": _rel(dx, rows(x.grad))}
+    errs = {"out": _rel(out[:, :cout], ref["out"]), "running_mean": _rel(rm, ref["running_mean"]), "running_var": _rel(rv, ref["running_var"]),
+            "d": _rel(d, ref["d"]), "dtaps": _rel(gt, ref["d taps"]), "dw": _rel(gw, ref["d w"]), "dgamma": _rel(gg, ref["d gamma"]),
+            "dbeta": _rel(gb, ref["d beta"]), "dx": _rel(dx, ref["dx"])}
     print({k_: f"{v:.1e}" for k_, v in errs.items()})
     bad = {k_: v for k_, v in errs.items() if not v < 2e-4}
     assert not bad, bad
     assert ldo_pad == 0 or bool((out[:, cout:] == 7.0).all())        # nothing written beyond the layer's own columns
     if bias:                                                          # the biases' gradients vanish in front of the BatchNorm
-        assert float(b_pw.grad.abs().max()) < 1e-9 and float(b_dw.grad.abs().max()) < 1e-9
+        assert all(float(t.abs().max()) < 1e-9 for t in ref["bias grads"])
     torch.cuda.synchronize()
     again = backward(torch.cuda.Stream(device=dev))
     for a, b in zip((gt, gw, gg, gb, dx), again):
@@ -307,6 +327,16 @@ def test_sepbn_layer_forward_backward_vs_autograd(B, H, cin, cout, bias, ldx_pad
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,H", [(3, 64), (2, 256), (5, 30)])
 def test_stem_on_the_image_forward_backward_vs_autograd(n, H):
+    _stem_case(n, H, H)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,H,W", [(2, 24, 40), (3, 52, 30)])
+def test_stem_on_a_rectangular_image(n, H, W):
+    _stem_case(n, H, W)
+
+
+def _stem_case(n, H, W):
     """The stem — 3x3 stride-2 conv 3 -> 16 + BatchNorm + ReLU — with its im2col rows gathered from the NCHW image by the GEMM and by the
     weight gradient (fear_stem_train_*): same numbers as the materialised rows (fear_stem_im2col + fear_pwbn_train_*), bit for bit
     in the forward, and autograd's gradients."""
@@ -314,29 +344,27 @@ def test_stem_on_the_image_forward_backward_vs_autograd(n, H):
     lib = load_train_library()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(21 + n + H)
-    x = torch.randn(n, 3, H, H, generator=g, dtype=torch.float64)
-    w = (torch.randn(16, 3, 3, 3, generator=g, dtype=torch.float64) * 0.3).requires_grad_(True)
-    gamma = (torch.rand(16, generator=g, dtype=torch.float64) + 0.5).requires_grad_(True)
-    beta = (torch.randn(16, generator=g, dtype=torch.float64) * 0.3).requires_grad_(True)
-    rm_ref, rv_ref = torch.zeros(16, dtype=torch.float64), torch.ones(16, dtype=torch.float64)
-    y = F.relu(F.batch_norm(F.conv2d(x, w, stride=2, padding=1), rm_ref, rv_ref, gamma, beta, True, 0.1, 1e-5))
-    Ho = H // 2
-    M = n * Ho * Ho
-    dy = torch.randn(n, 16, Ho, Ho, generator=g, dtype=torch.float64)
-    y.backward(dy)
+    x = torch.randn(n, 3, H, W, generator=g, dtype=torch.float64)
+    w = torch.randn(16, 3, 3, 3, generator=g, dtype=torch.float64) * 0.3
+    gamma = torch.rand(16, generator=g, dtype=torch.float64) + 0.5
+    beta = torch.randn(16, generator=g, dtype=torch.float64) * 0.3
+    Ho, Wo = H // 2, W // 2
+    M = n * Ho * Wo
+    dy = torch.randn(n, 16, Ho, Wo, generator=g, dtype=torch.float64)
     rows = lambda t: t.detach().permute(0, 2, 3, 1).reshape(M, -1)
+    ref = stem_autograd(x, w, gamma, beta, rows(dy))      # (tests/syncref.py, shared with the two-rank tests)
     D = lambda t: t.detach().to(dev, torch.float32).contiguous()
     xd, gd, bd, dyd = D(x), D(gamma), D(beta), D(rows(dy))
     w28 = torch.zeros(16, 28, device=dev)
     w28[:, :27] = D(w).reshape(16, 27)
-    ws = torch.empty(int(lib.fear_stem_workspace_bytes(n, H, H)) // 4 + 64, device=dev)
+    ws = torch.empty(int(lib.fear_stem_workspace_bytes(n, H, W)) // 4 + 64, device=dev)
     rm, rv = torch.zeros(16, device=dev), torch.ones(16, device=dev)
     raw, vec, out = torch.empty(M, 16, device=dev), torch.empty(64, device=dev), torch.empty(M, 16, device=dev)
-    assert lib.fear_stem_train_forward(_p(xd), _p(w28), _p(gd), _p(bd), _p(rm), _p(rv), _p(raw), _p(vec), _p(out), n, H, H, 0.1, 1e-5,
+    assert lib.fear_stem_train_forward(_p(xd), _p(w28), _p(gd), _p(bd), _p(rm), _p(rv), _p(raw), _p(vec), _p(out), n, H, W, 0.1, 1e-5,
                                        _p(ws), ws.numel() * 4, None) == 0
     # the materialised form
     col = torch.empty(M, 28, device=dev)
-    assert lib.fear_stem_im2col(_p(xd), _p(col), n, H, H, None) == 0
+    assert lib.fear_stem_im2col(_p(xd), _p(col), n, H, W, None) == 0
     rm2, rv2 = torch.zeros(16, device=dev), torch.ones(16, device=dev)
     raw2, vec2, out2 = torch.empty(M, 16, device=dev), torch.empty(64, device=dev), torch.empty(M, 16, device=dev)
     assert lib.fear_pwbn_train_forward(_p(col), 28, _p(w28), _p(gd), _p(bd), _p(rm2), _p(rv2), _p(raw2), _p(vec2), 1, _p(out2), M, 28, 16,
@@ -344,15 +372,15 @@ def test_stem_on_the_image_forward_backward_vs_autograd(n, H):
     torch.cuda.synchronize()
     assert torch.equal(raw, raw2) and torch.equal(out, out2) and torch.equal(vec, vec2)
     dw, dg, db = torch.empty(16, 28, device=dev), torch.empty(16, device=dev), torch.empty(16, device=dev)
-    assert lib.fear_stem_train_backward(_p(dyd), _p(raw), _p(vec), _p(xd), _p(gd), _p(dw), _p(dg), _p(db), n, H, H, _p(ws), ws.numel() * 4,
+    assert lib.fear_stem_train_backward(_p(dyd), _p(raw), _p(vec), _p(xd), _p(gd), _p(dw), _p(dg), _p(db), n, H, W, _p(ws), ws.numel() * 4,
                                         None, None) == 0
     dw2, dg2, db2 = torch.empty(16, 28, device=dev), torch.empty(16, device=dev), torch.empty(16, device=dev)
     assert lib.fear_pwbn_train_backward(_p(dyd), _p(raw2), _p(vec2), 1, _p(col), 28, _p(w28), _p(gd), _p(dw2), _p(dg2), _p(db2), None, M, 28, 16,
                                         _p(ws), ws.numel() * 4, None, None) == 0
     torch.cuda.synchronize()
     assert torch.equal(dw, dw2) and torch.equal(dg, dg2) and torch.equal(db, db2)
-    errs = {"out": _rel(out, rows(y)), "running_mean": _rel(rm, rm_ref), "running_var": _rel(rv, rv_ref),
-            "dw": _rel(dw[:, :27].reshape(16, 3, 3, 3), w.grad), "dgamma": _rel(dg, gamma.grad), "dbeta": _rel(db, beta.grad)}
+    errs = {"out": _rel(out, ref["out"]), "running_mean": _rel(rm, ref["running_mean"]), "running_var": _rel(rv, ref["running_var"]),
+            "dw": _rel(dw[:, :27].reshape(16, 3, 3, 3), ref["d w"]), "dgamma": _rel(dg, ref["d gamma"]), "dbeta": _rel(db, ref["d beta"])}
     print({k_: f"{v:.1e}" for k_, v in errs.items()})
     bad = {k_: v for k_, v in errs.items() if not v < 2e-4}
     assert not bad, bad

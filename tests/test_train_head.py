@@ -162,6 +162,9 @@ def test_head_training_step_matches_reference_autograd(golden_dir):
         assert torch.equal(out["grads"][n], out2["grads"][n]), n
 
 
+RECT_DW_CASES = ((2, 8, 20, 64, 5, 1), (2, 12, 32, 96, 3, 2), (1, 40, 6, 144, 5, 2))       # B, H, W, C, k, stride
+
+
 @pytest.mark.gpu
 def test_training_operators_individually_vs_torch():
     """Each heavy operator against the same operator written with torch ops on the GPU tensors' CPU copies (fp32 reference
@@ -199,24 +202,32 @@ def test_training_operators_individually_vs_torch():
         db = torch.empty(N, device=dev)
         assert lib.fear_col_sum(_p(dyd), N, _p(db), _p(ws), wsb, M, N, st) == 0
         _close(db, dy.sum(0), "bias grad", 1e-5)
-    for B, H, C, k, st_ in ((3, 16, 320, 3, 1), (2, 8, 64, 5, 1), (2, 32, 96, 3, 2), (2, 16, 144, 5, 2)):
-        x = torch.randn(B, C, H, H, generator=g, requires_grad=True)
+    def dw_case(B, H, W, C, k, st_, g):
+        x = torch.randn(B, C, H, W, generator=g, requires_grad=True)
         w = torch.randn(C, 1, k, k, generator=g, requires_grad=True)
         y = F.conv2d(x, w, None, stride=st_, padding=k // 2, groups=C)
-        Ho = H // st_
+        Ho, Wo = H // st_, W // st_
         dy = torch.randn(y.shape, generator=g)
         y.backward(dy)
         rows = lambda t: t.detach().permute(0, 2, 3, 1).reshape(-1, C).contiguous()
         taps = D(w.detach().reshape(C, k * k).t())
-        yd = torch.empty(B * Ho * Ho, C, device=dev)
-        assert lib.fear_dw_forward(_p(D(rows(x))), C, _p(taps), None, _p(yd), C, B, H, H, C, k, st_, st) == 0
-        _close(yd, rows(y), "dw forward", 1e-5)
-        dxd = torch.empty(B * H * H, C, device=dev)
-        assert lib.fear_dw_backward_data(_p(D(rows(dy))), C, _p(taps), _p(dxd), C, B, H, H, C, k, st_, st) == 0
-        _close(dxd, rows(x.grad), "dw dgrad", 1e-5)
+        yd = torch.empty(B * Ho * Wo, C, device=dev)
+        assert lib.fear_dw_forward(_p(D(rows(x))), C, _p(taps), None, _p(yd), C, B, H, W, C, k, st_, st) == 0
+        _close(yd, rows(y), f"dw forward {H}x{W}", 1e-5)
+        dxd = torch.empty(B * H * W, C, device=dev)
+        assert lib.fear_dw_backward_data(_p(D(rows(dy))), C, _p(taps), _p(dxd), C, B, H, W, C, k, st_, st) == 0
+        _close(dxd, rows(x.grad), f"dw dgrad {H}x{W}", 1e-5)
         dtaps = torch.empty(k * k, C, device=dev)
-        assert lib.fear_dw_backward_weight(_p(D(rows(dy))), C, _p(D(rows(x))), C, _p(dtaps), _p(ws), wsb, B, H, H, C, k, st_, st) == 0
-        _close(dtaps, w.grad.reshape(C, k * k).t(), "dw wgrad", 1e-5)
+        assert lib.fear_dw_backward_weight(_p(D(rows(dy))), C, _p(D(rows(x))), C, _p(dtaps), _p(ws), wsb, B, H, W, C, k, st_, st) == 0
+        _close(dtaps, w.grad.reshape(C, k * k).t(), f"dw wgrad {H}x{W}", 1e-5)
+
+    for B, H, C, k, st_ in ((3, 16, 320, 3, 1), (2, 8, 64, 5, 1), (2, 32, 96, 3, 2), (2, 16, 144, 5, 2)):
+        dw_case(B, H, H, C, k, st_, g)
+    # ... and on rectangular maps (H != W: tile counts, halo indices and Ho / Wo must not be swapped anywhere) — from a generator of
+    # their own, so that the draws of the sections below stay what they were
+    g_rect = torch.Generator().manual_seed(33)
+    for B, H, W, C, k, st_ in RECT_DW_CASES:
+        dw_case(B, H, W, C, k, st_, g_rect)
     for M, C, relu in ((1024, 256, 1), (777, 112, 0)):
         x = (torch.randn(M, C, generator=g) * 2 + 0.5).requires_grad_(True)
         gamma, beta = (torch.rand(C, generator=g) + 0.5).requires_grad_(True), torch.randn(C, generator=g).requires_grad_(True)
@@ -457,21 +468,24 @@ def test_fused_conv_bn_operators_individually_vs_torch():
         yd = y.cpu().double()
         np.testing.assert_allclose(sums.cpu().numpy(), torch.cat([yd.sum(0), (yd * yd).sum(0)]).numpy(), rtol=2e-6, atol=1e-6)
     # ---- depthwise producer
-    for B, H, C, k, st_, relu in ((3, 16, 96, 3, 2, 1), (2, 8, 64, 5, 1, 1), (2, 32, 16, 3, 1, None), (1, 16, 144, 5, 2, 0), (2, 16, 672, 5, 1, 1)):
-        x = torch.randn(B, C, H, H, generator=g)
+    def dw_producer_case(B, H, W, C, k, st_, relu, g):
+        x = torch.randn(B, C, H, W, generator=g)
         wt = torch.randn(C, 1, k, k, generator=g) * 0.3
         a, b = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.3
         xr = D(x.permute(0, 2, 3, 1).reshape(-1, C))
         taps = D(wt.reshape(C, k * k).t())
-        Ho = H // st_
-        y, sums = torch.empty(B * Ho * Ho, C, device=dev), torch.empty(2 * C, dtype=torch.float64, device=dev)
+        Ho, Wo = H // st_, W // st_
+        y, sums = torch.empty(B * Ho * Wo, C, device=dev), torch.empty(2 * C, dtype=torch.float64, device=dev)
         ia, ib = (None, None) if relu is None else (_p(D(a)), _p(D(b)))
-        assert lib.fear_dw_forward_stats(_p(xr), C, ia, ib, int(bool(relu)), _p(taps), _p(y), C, B, H, H, C, k, st_, _p(sums), _p(ws), wsb, None) == 0
+        assert lib.fear_dw_forward_stats(_p(xr), C, ia, ib, int(bool(relu)), _p(taps), _p(y), C, B, H, W, C, k, st_, _p(sums), _p(ws), wsb, None) == 0
         xin = x if relu is None else act(x, a.view(1, C, 1, 1), b.view(1, C, 1, 1), relu)
         ref = F.conv2d(xin, wt, stride=st_, padding=k // 2, groups=C).permute(0, 2, 3, 1).reshape(-1, C)
-        _close(y, ref, f"dw producer {B}x{C}x{H} k{k}s{st_}", 2e-5)
+        _close(y, ref, f"dw producer {B}x{C}x{H}x{W} k{k}s{st_}", 2e-5)
         yd = y.cpu().double()
         np.testing.assert_allclose(sums.cpu().numpy(), torch.cat([yd.sum(0), (yd * yd).sum(0)]).numpy(), rtol=2e-6, atol=1e-6)
+
+    for B, H, C, k, st_, relu in ((3, 16, 96, 3, 2, 1), (2, 8, 64, 5, 1, 1), (2, 32, 16, 3, 1, None), (1, 16, 144, 5, 2, 0), (2, 16, 672, 5, 1, 1)):
+        dw_producer_case(B, H, H, C, k, st_, relu, g)
     # ---- finalize + act + backward pair on one BatchNorm (+ReLU), vs autograd
     for M, C, relu in ((777, 96, 1), (1024, 24, 0)):
         x = torch.randn(M, C, generator=g) * 2 + 0.5
@@ -517,17 +531,24 @@ def test_fused_conv_bn_operators_individually_vs_torch():
         dw = torch.empty(N, K, device=dev)
         assert lib.fear_pw_backward_weight_act(_p(D(dy)), N, _p(D(x)), K, _p(D(a)), _p(D(b)), relu, _p(dw), _p(ws), wsb, M, K, N, None) == 0
         _close(dw, dy.t() @ act(x, a, b, relu), f"pw wgrad act K={K}", 2e-5)
-    for B, H, C, k, st_ in ((2, 16, 96, 3, 2), (2, 8, 64, 5, 1), (3, 12, 32, 3, 1)):
-        x = torch.randn(B, C, H, H, generator=g)
+    def dw_wgrad_act_case(B, H, W, C, k, st_, g):
+        x = torch.randn(B, C, H, W, generator=g)
         a, b = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.3
         wt = torch.zeros(C, 1, k, k, requires_grad=True)
-        Ho = H // st_
-        dyt = torch.randn(B, C, Ho, Ho, generator=g)
+        dyt = torch.randn(B, C, H // st_, W // st_, generator=g)
         F.conv2d(act(x, a.view(1, C, 1, 1), b.view(1, C, 1, 1), 1), wt, stride=st_, padding=k // 2, groups=C).backward(dyt)
         dtaps = torch.empty(k * k, C, device=dev)
         assert lib.fear_dw_backward_weight_act(_p(D(dyt.permute(0, 2, 3, 1).reshape(-1, C))), C, _p(D(x.permute(0, 2, 3, 1).reshape(-1, C))), C,
-                                               _p(D(a)), _p(D(b)), 1, _p(dtaps), _p(ws), wsb, B, H, H, C, k, st_, None) == 0
-        _close(dtaps, wt.grad.reshape(C, k * k).t(), f"dw wgrad act k{k}s{st_}", 2e-5)
+                                               _p(D(a)), _p(D(b)), 1, _p(dtaps), _p(ws), wsb, B, H, W, C, k, st_, None) == 0
+        _close(dtaps, wt.grad.reshape(C, k * k).t(), f"dw wgrad act {H}x{W} k{k}s{st_}", 2e-5)
+
+    for B, H, C, k, st_ in ((2, 16, 96, 3, 2), (2, 8, 64, 5, 1), (3, 12, 32, 3, 1)):
+        dw_wgrad_act_case(B, H, H, C, k, st_, g)
+    # ---- the `_stats` / `_act` depthwise forms on rectangular maps (a generator of their own: the draws above stay what they were)
+    g_rect = torch.Generator().manual_seed(34)
+    for B, H, W, C, k, st_ in RECT_DW_CASES:
+        dw_producer_case(B, H, W, C, k, st_, 1, g_rect)
+        dw_wgrad_act_case(B, H, W, C, k, st_, g_rect)
     torch.cuda.synchronize()
 
 
@@ -657,3 +678,36 @@ def test_deferred_running_statistics_in_one_launch_equal_the_per_batchnorm_updat
         assert torch.equal(a, a2) and torch.equal(b, b2)
     items[3].count = 0.0
     assert lib.fear_bn_running_update_multi(items, len(Cs), 0.1, 1e-5, None) == -2
+
+
+@pytest.mark.gpu
+def test_deferred_running_statistics_with_an_invalid_late_item_update_nothing():
+    """fear_bn_running_update_multi launches one kernel per 64 items: every item is validated before the first launch, so an invalid
+    item in the SECOND chunk (item 66 of 70 with C = 0) returns FEAR_TRAIN_ERR_SHAPE with all 70 BatchNorms bit-equal to before —
+    and with the item repaired the call equals 70 single fear_bn_running_update calls bit for bit."""
+    import ctypes
+    from feartracker_amd.train_head import FearBnRunning, _p, load_train_library
+    lib = load_train_library()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(13)
+    n, C = 70, 8
+    vecs = [torch.cat([torch.randn(C, generator=g), torch.rand(C, generator=g) + 0.5, torch.zeros(2 * C)]).to(dev) for _ in range(n)]
+    rm = [torch.randn(C, generator=g).to(dev) for _ in range(n)]
+    rv = [(torch.rand(C, generator=g) + 0.5).to(dev) for _ in range(n)]
+    rm0, rv0 = [t.clone() for t in rm], [t.clone() for t in rv]
+    counts = [float(50 + 3 * i) for i in range(n)]
+    items = (FearBnRunning * n)()
+    for it, v, a, b, cnt in zip(items, vecs, rm, rv, counts):
+        it.vec, it.running_mean, it.running_var, it.C, it.count = v.data_ptr(), a.data_ptr(), b.data_ptr(), C, cnt
+    items[66].C = 0
+    assert lib.fear_bn_running_update_multi(items, n, 0.1, 1e-5, None) == -2
+    torch.cuda.synchronize()
+    changed = [i for i in range(n) if not (torch.equal(rm[i], rm0[i]) and torch.equal(rv[i], rv0[i]))]
+    assert not changed, changed
+    items[66].C = C
+    assert lib.fear_bn_running_update_multi(items, n, 0.1, 1e-5, None) == 0
+    for v, a, b, cnt in zip(vecs, rm0, rv0, counts):
+        assert lib.fear_bn_running_update(_p(v), cnt, _p(a), _p(b), 0.1, 1e-5, C, None) == 0
+    torch.cuda.synchronize()
+    for i in range(n):
+        assert torch.equal(rm[i], rm0[i]) and torch.equal(rv[i], rv0[i]), i
