@@ -8,6 +8,8 @@
 * `TopKCheckpoints` — the checkpoint callback's `save_top_k: 3` (train/callbacks.py:52-64), writing deployable `.fearw` files with
   `export_training_state` instead of Lightning checkpoints.
 * `EarlyStopping` — `early_stopping: 20` (train/callbacks.py:72-82: pytorch_lightning's EarlyStopping with min_delta 0).
+* `save_training_checkpoint` / `load_training_checkpoint` — what Lightning's own checkpoints add to the weights: the optimiser state
+  and the BatchNorm running statistics, so that a run can be continued (`TopKCheckpoints` exports inference weights only).
 
     schedule, keep, stop = PlateauSchedule(opt), TopKCheckpoints("checkpoints"), EarlyStopping()
     for epoch in ...:
@@ -131,3 +133,23 @@ class EarlyStopping:
         else:
             self.wait += 1
         return self.wait >= self.patience
+
+
+def save_training_checkpoint(path: str, net: Any, opt: Any, **extra: Any) -> None:
+    """Everything a run needs to continue, in one `torch.save` file — what the reference's Lightning checkpoints carry next to the
+    weights: `net.state_dict()` (parameters and BatchNorm running statistics), `opt.state_dict()` (moments / momentum buffer, step
+    count, hyper-parameters with `lr` as the schedule left it) and the caller's `extra` values (epoch, schedule counters, ...)."""
+    import torch
+    torch.save({"model": net.state_dict(), "optimizer": opt.state_dict(), "optimizer_class": type(opt).__name__, "extra": dict(extra)}, path)
+
+
+def load_training_checkpoint(path: str, net: Any, opt: Any) -> Dict[str, Any]:
+    """Restore `net` (in place: `FEARNetTrainHIP.load_state_dict`) and `opt` from a file of `save_training_checkpoint`; returns its
+    `extra` values.  The optimiser must be of the class that was saved."""
+    import torch
+    ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    if ckpt["optimizer_class"] != type(opt).__name__:
+        raise ValueError(f"the checkpoint holds the state of {ckpt['optimizer_class']}, not of {type(opt).__name__}")
+    net.load_state_dict(ckpt["model"])
+    opt.load_state_dict(ckpt["optimizer"])
+    return ckpt["extra"]

@@ -50,6 +50,11 @@ TRAIN_SYMBOLS = {
     "fear_scale_column": ([_P, _i, _i, _f, _P, _i, _i, _l, _P], _i),
     "fear_add": ([_P, _P, _P, _l, _P], _i),
     "fear_adam_step": ([_P, _P, _P, _P, _l, _d, _d, _d, _d, _d, _i, _P], _i),
+    # the optimiser family and gradient-norm clipping (optim.py; FearOptim below)
+    "fear_grad_sumsq_partials": ([_l], _l),
+    "fear_grad_sumsq": ([_P, _l, _P, _P], _i),
+    "fear_grad_norm_finalize": ([_P, _l, _d, _P, _P], _i),
+    "fear_optim_step": ([_P, _P, _P, _P, _P, _l, _i, _P, _P], _i),
     # block-fused trunk operators (structs below mirror include/fear_train.h)
     "fear_irb_workspace_bytes": ([_P, _i, _i, _i], _sz),
     "fear_irb_scratch_floats": ([_P, _i, _i, _i], _sz),
@@ -106,7 +111,17 @@ class FearSepGrads(ctypes.Structure):
     _fields_ = [("w_dw", _P), ("w_pw", _P), ("gamma", _P), ("beta", _P)]
 
 
-_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p)
+FEAR_OPT_ADAM, FEAR_OPT_ADAMW, FEAR_OPT_SGD = 0, 1, 2
+FEAR_GRAD_SUMSQ_CHUNK = 4096      # floats per partial sum of fear_grad_sumsq
+
+
+class FearOptim(ctypes.Structure):
+    """include/fear_train.h: the rule and hyper-parameters of one fear_optim_step."""
+    _fields_ = [("kind", _i), ("nesterov", _i), ("lr", _d), ("beta1", _d), ("beta2", _d), ("eps", _d), ("weight_decay", _d),
+                ("momentum", _d), ("dampening", _d)]
+
+
+_ALLREDUCE_FN =ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p)
 FEAR_SYNC_BUF_BYTES = 16384
 
 

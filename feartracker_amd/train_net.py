@@ -768,6 +768,31 @@ class FEARNetTrainHIP(_TrainPlumbing):
         out.update({k: v.cpu().clone() for k, v in self.running_stats().items()})
         return out
 
+    @torch.no_grad()
+    def load_state_dict(self, state_dict: Dict[str, "np.ndarray | torch.Tensor"]) -> None:
+        """The inverse of `state_dict` on a live instance: parameters and running statistics in the reference's layouts are written
+        INTO the existing storage (the views of `param_flat`, the running-statistics tensors), so every address a ctypes
+        descriptor or an optimiser holds stays valid.  Every parameter and statistic must be present; other keys
+        (`num_batches_tracked`) are ignored."""
+        slots, stats = self.parameter_slots(), self.running_stats()
+        missing = [k for k in list(slots) + list(stats) if k not in state_dict]
+        if missing:
+            raise KeyError(f"state has no {missing[:3]}{'...' if len(missing) > 3 else ''}")
+        as_dev = lambda v: torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v.detach()).to(self.device, torch.float32)
+        laid = []
+        for name, (param, to_storage, _) in slots.items():
+            t = to_storage(as_dev(state_dict[name]))
+            if t.shape != param.shape:
+                raise ValueError(f"{name}: {tuple(state_dict[name].shape)} does not fit parameter storage {tuple(param.shape)}")
+            laid.append((param, t))
+        for name, dst in stats.items():
+            t = as_dev(state_dict[name]).reshape(-1)
+            if t.shape != dst.shape:
+                raise ValueError(f"{name}: {tuple(state_dict[name].shape)} does not fit {tuple(dst.shape)}")
+            laid.append((dst, t))
+        for dst, t in laid:
+            dst.copy_(t)
+
     def running_stats(self) -> Dict[str, torch.Tensor]:
         """{"<bn>.running_mean" / "<bn>.running_var": device tensor} of every BatchNorm, as updated by the `step` calls so far
         (template pass first, then the search pass, like two forward calls of the shared trunk) — what `export.py` folds."""

@@ -184,6 +184,45 @@ int fear_add(const float* a, const float* b, float* out, long n, void* stream);
 int fear_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, double lr, double beta1, double beta2,
                    double eps, double weight_decay, int step, void* stream);
 
+/* ---- the optimiser family and gradient-norm clipping (csrc/fear_train_optim.h) ---------------------------------------------------
+ * The reference's config/optimizer/{adam,adamw,sgd}.yaml and `gradient_clip_val` (train/trainer.py:59: Lightning's clip_grad_norm_
+ * over all parameters) on flat fp32 buffers, without a host round trip: sum of squares -> norm and coefficient -> update.
+ *
+ * The 2-norm in a fixed order: each workgroup adds the squares of one chunk of FEAR_GRAD_SUMSQ_CHUNK consecutive floats in float64
+ * (16-byte loads from the first 16-byte boundary on, the head and the tail scalar) and writes one partial; the count of partials for n
+ * elements comes from the first function (0 for n <= 0).  No floating-point atomics: the same input gives the same bits.  `grad`
+ * must be 4-byte aligned. */
+#define FEAR_GRAD_SUMSQ_CHUNK 4096
+long fear_grad_sumsq_partials(long n);
+int fear_grad_sumsq(const float* grad, long n, double* partials, void* stream);
+/* One workgroup adds `count` partials in a fixed order — they may come from several sum-of-squares calls that wrote consecutive
+ * ranges (a model updated tensor by tensor) — and writes out2[0] = norm = (float)sqrt(sum) and out2[1] = the clipping coefficient
+ * min(1, max_norm / (norm + 1e-6)) in fp32, as torch.nn.utils.clip_grad_norm_(norm_type = 2) forms it (the reciprocal of the fp32
+ * sum, times max_norm); max_norm <= 0 writes 1.
+ * A non-finite norm gives a NaN coefficient, as in torch. */
+int fear_grad_norm_finalize(const double* partials, long count, double max_norm, float* out2, void* stream);
+
+#define FEAR_OPT_ADAM 0
+#define FEAR_OPT_ADAMW 1
+#define FEAR_OPT_SGD 2
+typedef struct {
+    int kind;                 /* FEAR_OPT_ADAM | FEAR_OPT_ADAMW | FEAR_OPT_SGD */
+    int nesterov;             /* SGD */
+    double lr, beta1, beta2, eps, weight_decay, momentum, dampening;
+} FearOptim;
+/* One update of n parameters in place by torch.optim.Adam / AdamW / SGD's rule (no amsgrad; the fp32 operations in torch's
+ * order; scalars formed in double on the host).  `step` counts from 1.  `clip_coef`: device pointer to the coefficient (out2 + 1
+ * above) or NULL; the kernel forms g = grad * coef in a register and does NOT write the gradient buffer (torch scales it in place).
+ *   ADAM    as fear_adam_step: state1 = exp_avg, state2 = exp_avg_sq (same bits with clip_coef NULL)
+ *   ADAMW   p *= 1 - lr * weight_decay, then Adam without the L2 term
+ *   SGD     g += weight_decay * p; buf = g at step 1, else momentum * buf + (1 - dampening) * g; g = g + momentum * buf with
+ *           nesterov, else buf; p -= lr * g.  state1 = the momentum buffer (may be NULL when momentum == 0), state2 unused.
+ * FEAR_TRAIN_ERR_SHAPE, before anything is launched: an unknown kind, step < 1, n < 0, betas outside [0, 1), momentum < 0, nesterov
+ * with momentum <= 0 or dampening != 0 (torch's rule); FEAR_TRAIN_ERR_NULL: a missing descriptor, parameter, gradient or required
+ * state.  Four elements per lane where all bases are 16-byte aligned, element by element otherwise. */
+int fear_optim_step(const FearOptim* o, float* param, const float* grad, float* state1, float* state2, long n, int step,
+                    const float* clip_coef, void* stream);
+
 /* ---- block-fused operators of the trunk's training step (round 5; csrc/fear_train_block.h) --------------------------------------
  * One call per inverted-residual block and direction — model_training/model/blocks.py:22-35 over mobile_cv's conv-BN-ReLU units:
  * expand 1x1 + BN + ReLU (absent when `expand` = 0: cexp = cin), depthwise kxk stride s + BN + ReLU, project 1x1 + BN [+ input when
