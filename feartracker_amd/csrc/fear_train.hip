@@ -2090,7 +2090,10 @@ int fear_xcorr_backward(const float* ds, int ldds, const float* x, int ldx, cons
     // dx[b][p][c] = dx_add[b][p][c] + sum_j ds[b][p][j] z[b][c][j];   dz[b][c][j] = sum_p x[b][p][c] ds[b][p][j]
     if (B == 0) return FEAR_TRAIN_OK;
     if (!ds || !x || !z_nchw || !dx || !dz_nchw) return FEAR_TRAIN_ERR_NULL;
-    if (B < 0 || P < 1 || P % 128 || C % 4 || J % 4) return FEAR_TRAIN_ERR_SHAPE;      // a 128-row tile must not straddle crops
+    // a 128-row tile must not straddle crops; every operand row is read or written as float4s (the forward's rules)
+    if (B < 0 || P < 1 || P % 128 || C < 4 || J < 4 || C % 4 || J % 4 || !ld_ok(ldds, J) || !ld_ok(ldx, C) || !ld_ok(lddx, C) ||
+        (dx_add && !ld_ok(ldadd, C)))
+        return FEAR_TRAIN_ERR_SHAPE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     PwArgs a{};
     a.X = ds; a.ldx = ldds; a.W = z_nchw; a.Y = dx; a.ldy = lddx; a.M = B * P; a.K = J; a.N = C;

@@ -146,7 +146,11 @@ int fear_dw_backward_weight_act(const float* dy, int lddy, const float* x, int l
                                 float* dw_taps, float* workspace, size_t ws_bytes, int B, int H, int W, int C, int k, int stride,
                                 void* stream);
 
-/* MobileCorrelation (blocks.py:121-123): s[b][p][j] = sum_c x[b][p][c] z[b][c][j]; z_nchw = (B, C, J) as the reference holds it */
+/* MobileCorrelation (blocks.py:121-123): s[b][p][j] = sum_c x[b][p][c] z[b][c][j]; z_nchw = (B, C, J) as the reference holds it.
+ * Both directions return FEAR_TRAIN_ERR_SHAPE before anything is launched unless C >= 4, J >= 4, C % 4 == J % 4 == 0 and every
+ * leading dimension is a multiple of 4 floats that covers its row (ldx >= C, lds / ldds >= J, lddx >= C, ldadd >= C where
+ * dx_add is given): rows are read and written as float4s.  P % 32 == 0 forward (a wave's 32 rows share one crop's z),
+ * P % 128 == 0 backward (a 128-row tile must not straddle crops).  s_out may be columns of x's own buffer past column C. */
 int fear_xcorr_forward(const float* x, int ldx, const float* z_nchw, float* s_out, int lds, int B, int P, int C, int J,
                        void* stream);
 /* dx[b][p][c] = (dx_add ? dx_add[b][p][c] : 0) + sum_j ds[b][p][j] z[b][c][j];   dz[b][c][j] = sum_p x[b][p][c] ds[b][p][j] */
