@@ -86,13 +86,16 @@ struct PairGeom {            // the layout of FearPairGeom (include/fear_train.h
     double inv[4];
 };
 
+// Out = float: the crops leave normalised, fp32 NCHW (fear_train_pairs).  Out = uint8_t: they leave as the colour stage made them,
+// uint8 NHWC, for the photometric stage behind (fear_train_pairs_u8).
+template <typename Out>
 struct PairArgs {
     const CropFrame* frames;
     const uint8_t* border;   // [n_frames][3]
     const PairGeom* geom;    // [n]
     const uint8_t* lut;      // [n][3][256]
-    float* tmpl;             // [n][3][128][128]
-    float* search;           // [n][3][256][256]
+    Out* tmpl;               // float [n][3][128][128] | uint8 [n][128][128][3]
+    Out* search;             // float [n][3][256][256] | uint8 [n][256][256][3]
     float* gt_reg;           // [n][4][16][16]
     float* gt_cls;           // [n][1][16][16]
     float* gt_weight;        // [n][16][16]
@@ -111,7 +114,8 @@ struct PairFrame {
     int pad[3];
 };
 
-__device__ __forceinline__ PairFrame pair_frame(const PairArgs& a, int fi) {
+template <typename Out>
+__device__ __forceinline__ PairFrame pair_frame(const PairArgs<Out>& a, int fi) {
     PairFrame p;
     if ((unsigned)fi < (unsigned)a.n_frames) {
         p.f = a.frames[fi];
@@ -175,8 +179,10 @@ __device__ __forceinline__ void crop_rgb(const PairFrame& p, const int32_t* ctx,
     }
 }
 
-// Colour stage on a uint8 RGB pixel, then normalisation -> the three fp32 outputs of one pixel (plane stride `plane`).
-__device__ __forceinline__ void colour_normalise_store(const PairArgs& a, int pair, int tone, int* rgb, float* out, long plane) {
+// Colour stage on a uint8 RGB pixel, then the store policy of Out for pixel `px` of a crop of `plane` pixels: normalisation into the
+// three fp32 planes, or the three bytes of the uint8 HWC pixel.
+template <typename Out>
+__device__ __forceinline__ void colour_store(const PairArgs<Out>& a, int pair, int tone, int* rgb, Out* crop, long px, long plane) {
 #pragma clang fp contract(off)      // every product and sum rounded on its own (the pragma covers only the operators written here:
                                     // __fmul_rn / __fadd_rn are plain operators in the HIP headers and would still fuse into fmas)
     if (tone == 1) {                              // cv2 COLOR_RGB2GRAY on 8u: 14-bit fixed point
@@ -197,10 +203,15 @@ __device__ __forceinline__ void colour_normalise_store(const PairArgs& a, int pa
     const uint8_t* lut = a.lut + (long)pair * 768;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        float f = (float)lut[c * 256 + rgb[c]];
-        f = f - a.mean[c];
-        f = f * a.inv_std[c];
-        out[c * plane] = f;
+        const uint8_t v = lut[c * 256 + rgb[c]];
+        if constexpr (sizeof(Out) == 1) {
+            crop[px * 3 + c] = v;
+        } else {
+            float f = (float)v;
+            f = f - a.mean[c];
+            f = f * a.inv_std[c];
+            crop[c * plane + px] = f;
+        }
     }
 }
 
@@ -218,7 +229,8 @@ __device__ __forceinline__ int warp_y(const double* inv, int y) {
     return ((int)rint((inv[2] * (double)y + inv[3]) * 1024.0) + 16) >> 5;
 }
 
-__global__ __launch_bounds__(256) void train_pairs_kernel(PairArgs a) {
+template <typename Out>
+__global__ __launch_bounds__(256) void train_pairs_kernel(PairArgs<Out> a) {
     const int pair = blockIdx.y;
     const int blk = blockIdx.x;
     const PairGeom& g = a.geom[pair];
@@ -251,7 +263,7 @@ __global__ __launch_bounds__(256) void train_pairs_kernel(PairArgs a) {
         int rgb[3];
         for (int c = 0; c < 3; ++c) rgb[c] = (acc[c] + (1 << 14)) >> 15;
         const long plane = (long)kTpSearch * kTpSearch;
-        colour_normalise_store(a, pair, g.tone, rgb, a.search + (long)pair * 3 * plane + dy * kTpSearch + dx, plane);
+        colour_store(a, pair, g.tone, rgb, a.search + (long)pair * 3 * plane, (long)dy * kTpSearch + dx, plane);
     } else if (blk < kSearchBlocks + kTemplateBlocks) {
         // ---- template pixel: crop_resize_normalize_kernel's crop, the colour stage in front of the normalisation
         const int px = (blk - kSearchBlocks) * 256 + threadIdx.x;
@@ -262,7 +274,7 @@ __global__ __launch_bounds__(256) void train_pairs_kernel(PairArgs a) {
         int rgb[3];
         crop_rgb(p, g.t_ctx, kTpTemplate, dx, dy, tx, ty, rgb);
         const long plane = (long)kTpTemplate * kTpTemplate;
-        colour_normalise_store(a, pair, g.tone, rgb, a.tmpl + (long)pair * 3 * plane + px, plane);
+        colour_store(a, pair, g.tone, rgb, a.tmpl + (long)pair * 3 * plane, (long)px, plane);
     } else {
         // ---- target cell (i, j): ltrb against the float64 grid, positive where min(ltrb) > 0, weight 1 within L1 distance 2 of the
         // box centre's cell (r_neg = 0: no 0.5 ring); zeros when the search target is absent
@@ -286,6 +298,239 @@ __global__ __launch_bounds__(256) void train_pairs_kernel(PairArgs a) {
     }
 }
 
+// ---- photometric stage ------------------------------------------------------------------------------------------------------------
+// PHOTOMETRIC_AUGMENTATIONS of the reference (dataset/aug.py:8-25) on one uint8 HWC crop, then the normalisation: blur -> noise ->
+// Downscale(0.5, INTER_NEAREST), the members and their integer / fp32 forms as DESIGN.md section 11 states them.  One workgroup per
+// (32 x 32 output tile, crop); the record is uniform per workgroup, so every member branch is a scalar branch.  A blurred crop stages
+// its tile plus a halo of 3 into LDS once, the border rule applied while staging (BORDER_REFLECT_101, BORDER_REPLICATE for the
+// median), so the blur loops index LDS without a bounds test.
+struct PhotoOp {             // the layout of FearPhotoOp (include/fear_train.h)
+    int32_t blur, ksize, noise;
+    float scale;
+    uint32_t key[2];
+    int32_t downscale, tap_row;
+};
+
+struct PhotoArgs {
+    const uint8_t* in;       // [n][H][W][3]
+    const PhotoOp* ops;      // [n]
+    const float* taps;       // [m][49], may be null
+    const float* q;          // [4096]
+    float* out;              // [n][3][H][W]
+    int H, W;
+    float mean[3], inv_std[3];
+};
+
+constexpr int kPhTile = 32, kPhHalo = 3, kPhSide = kPhTile + 2 * kPhHalo, kPhPitch = kPhSide * 3, kPhBytes = kPhSide * kPhPitch;
+static_assert(kPhBytes % 4 == 0, "the tile is staged in 4-byte words");
+
+// Source index of coordinate i on an axis of n >= 4 pixels, |overshoot| <= 3 where it matters: one reflection about the edge pixel
+// (BORDER_REFLECT_101) or the edge pixel itself (BORDER_REPLICATE).  Columns of a ragged tile further out feed no output pixel; the
+// clamp keeps their address inside the crop.
+__device__ __forceinline__ int photo_border(int i, int n, bool replicate) {
+    if (!replicate) i = i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i);
+    return min(max(i, 0), n - 1);
+}
+
+template <int K>
+__device__ __forceinline__ int gauss_weight(int i) {       // OpenCV's small-kernel tables for sigma = 0, as 8-bit weights (sum 256)
+    if constexpr (K == 3) return i == 1 ? 128 : 64;
+    else if constexpr (K == 5) return i == 2 ? 96 : ((i == 1 || i == 3) ? 64 : 16);
+    else return i == 3 ? 72 : ((i == 2 || i == 4) ? 56 : ((i == 1 || i == 5) ? 28 : 8));
+}
+
+// One blurred pixel: `win` points at channel 0 of the window's centre in the staged tile.
+template <int KIND, int K>
+__device__ __forceinline__ void blur_px(const uint8_t* win, int* v) {
+    constexpr int R = K / 2;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if constexpr (KIND == 1) {                          // Blur: (sum + k k / 2) / (k k) in integers
+            int s = 0;
+#pragma unroll
+            for (int dy = -R; dy <= R; ++dy)
+#pragma unroll
+                for (int dx = -R; dx <= R; ++dx) s += win[dy * kPhPitch + dx * 3 + c];
+            v[c] = (s + K * K / 2) / (K * K);
+        } else if constexpr (KIND == 2) {                   // GaussianBlur, sigma 0: 8-bit weights on both axes, one rounding
+            int s = 0;
+#pragma unroll
+            for (int dy = -R; dy <= R; ++dy) {
+                int row = 0;
+#pragma unroll
+                for (int dx = -R; dx <= R; ++dx) row += gauss_weight<K>(dx + R) * win[dy * kPhPitch + dx * 3 + c];
+                s += gauss_weight<K>(dy + R) * row;
+            }
+            v[c] = (s + 32768) >> 16;
+        } else {                                            // MedianBlur: the largest m with #(window >= m) >= (k k + 1) / 2, bit by bit
+            int m = 0;
+#pragma unroll
+            for (int bit = 7; bit >= 0; --bit) {
+                const int cand = m | (1 << bit);
+                int cnt = 0;
+#pragma unroll
+                for (int dy = -R; dy <= R; ++dy)
+#pragma unroll
+                    for (int dx = -R; dx <= R; ++dx) cnt += win[dy * kPhPitch + dx * 3 + c] >= cand ? 1 : 0;
+                m = cnt >= (K * K + 1) / 2 ? cand : m;
+            }
+            v[c] = m;
+        }
+    }
+}
+
+template <int KIND>
+__device__ __forceinline__ void blur_px_k(int k, const uint8_t* win, int* v) {
+    if (k == 3) blur_px<KIND, 3>(win, v);
+    else if (k == 5) blur_px<KIND, 5>(win, v);
+    else blur_px<KIND, 7>(win, v);
+}
+
+// MotionBlur: cv2.filter2D on uint8 with the crop's 7 x 7 row of the tap table (a k x k kernel sits centred in it): correlation, anchor
+// at the centre, fp32 accumulation over the non-zero taps in row-major order, rint half to even, saturate.
+__device__ __forceinline__ void motion_px(const float* taps, const uint8_t* win, int* v) {
+#pragma clang fp contract(off)
+    float acc[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 49; ++t) {
+        const float w = taps[t];                            // uniform: a scalar load and a scalar branch
+        if (w != 0.f) {
+            const uint8_t* p = win + (t / 7 - 3) * kPhPitch + (t % 7 - 3) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] = acc[c] + w * (float)p[c];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = (int)fminf(fmaxf(rintf(acc[c]), 0.f), 255.f);
+}
+
+// Philox4x32-10 (Salmon et al., Random123) of counter (c0, c1, 0, 0) and key (k0, k1): words 0, 1, 2.
+__device__ __forceinline__ void philox3(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t* out) {
+    uint32_t c2 = 0u, c3 = 0u;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2;
+}
+
+__global__ __launch_bounds__(256) void photometric_kernel(PhotoArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[kPhBytes];
+    const int crop = blockIdx.z, x0 = blockIdx.x * kPhTile, y0 = blockIdx.y * kPhTile;
+    const int H = a.H, W = a.W, tid = threadIdx.x;
+    const PhotoOp op = a.ops[crop];
+    // a record the host could not have drawn (unknown kind, ksize outside {3, 5, 7}, a motion blur without its taps) means "none"
+    int blur = op.blur;
+    const int k = op.ksize;
+    if (blur < 1 || blur > 4 || !(k == 3 || k == 5 || k == 7) || (blur == 4 && (a.taps == nullptr || op.tap_row < 0))) blur = 0;
+    const int noise = (op.noise == 1 || op.noise == 2) ? op.noise : 0;
+    const bool down = op.downscale != 0;
+    const uint8_t* src = a.in + (long)crop * H * W * 3;
+    if (blur != 0) {
+        // stage rows y0 - 3 .. y0 + 34, columns x0 - 3 .. x0 + 34: a 4-byte word whose pixels all lie inside the row is one load
+        // (the 3-byte pitch leaves it unaligned), a word that touches the border or wraps to the next row goes byte by byte
+        const bool rep = blur == 3;
+        for (int w = tid; w < kPhBytes / 4; w += 256) {
+            const int i = w * 4, r = i / kPhPitch, b = i - r * kPhPitch;
+            const int gx0 = x0 - kPhHalo + b / 3, gx1 = x0 - kPhHalo + (b + 3) / 3;
+            uint32_t word = 0u;
+            if (b + 3 < kPhPitch && gx0 >= 0 && gx1 < W) {
+                const int gy = photo_border(y0 - kPhHalo + r, H, rep);
+                __builtin_memcpy(&word, src + ((long)gy * W + (x0 - kPhHalo)) * 3 + b, 4);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int rr = (i + j) / kPhPitch, bb = (i + j) - rr * kPhPitch;
+                    const int gy = photo_border(y0 - kPhHalo + rr, H, rep), gx = photo_border(x0 - kPhHalo + bb / 3, W, rep);
+                    word |= (uint32_t)src[((long)gy * W + gx) * 3 + bb % 3] << (8 * j);
+                }
+            }
+            reinterpret_cast<uint32_t*>(tile)[w] = word;
+        }
+        __syncthreads();
+    }
+    const float* taps = blur == 4 ? a.taps + (long)op.tap_row * 49 : nullptr;
+#pragma unroll 1
+    for (int it = 0; it < kPhTile * kPhTile / 256; ++it) {
+        const int ly = it * 8 + (tid >> 5), lx = tid & 31;
+        const int x = x0 + lx, y = y0 + ly;
+        if (x >= W || y >= H) continue;
+        // Downscale(0.5, INTER_NEAREST) and back: the whole chain at the even pixel (H and W are even, tiles start even)
+        const int sx = down ? (x & ~1) : x, sy = down ? (y & ~1) : y;
+        int v[3];
+        if (blur == 0) {
+            const uint8_t* p = src + ((long)sy * W + sx) * 3;
+            v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
+        } else {
+            const uint8_t* win = tile + (sy - y0 + kPhHalo) * kPhPitch + (sx - x0 + kPhHalo) * 3;
+            if (blur == 1) blur_px_k<1>(k, win, v);
+            else if (blur == 2) blur_px_k<2>(k, win, v);
+            else if (blur == 3) blur_px_k<3>(k, win, v);
+            else motion_px(taps, win, v);
+        }
+        {
+#pragma clang fp contract(off)      // every product and sum rounded on its own, as in colour_store
+            if (noise == 1) {                               // MultiplicativeNoise, one multiplier per crop
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c] = (int)fminf(fmaxf((float)v[c] * op.scale, 0.f), 255.f);
+            } else if (noise == 2) {                        // GaussNoise: sigma times a table quantile picked by 12 Philox bits
+                uint32_t rnd[3];
+                philox3((uint32_t)sx, (uint32_t)sy, op.key[0], op.key[1], rnd);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    float f = op.scale * a.q[rnd[c] >> 20];
+                    f = (float)v[c] + f;
+                    v[c] = (int)fminf(fmaxf(f, 0.f), 255.f);
+                }
+            }
+            float* o = a.out + (long)crop * 3 * H * W + (long)y * W + x;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float f = (float)v[c];
+                f = f - a.mean[c];
+                f = f * a.inv_std[c];
+                o[(long)c * H * W] = f;
+            }
+        }
+    }
+}
+
+// fear_normalize_u8's constants
+template <typename Args>
+void set_normalisation(Args& a) {
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    for (int c = 0; c < 3; ++c) {
+        a.mean[c] = mean[c] * 255.0f;
+        a.inv_std[c] = 1.0f / (stdv[c] * 255.0f);
+    }
+}
+
+template <typename Out>
+int launch_train_pairs(const fear_frame* frames, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom, const uint8_t* lut,
+                       int n, Out* template_out, Out* search_out, float* gt_reg, float* gt_cls, float* gt_weight, void* stream) {
+    static_assert(sizeof(FearPairGeom) == sizeof(PairGeom) && offsetof(FearPairGeom, inv) == offsetof(PairGeom, inv) &&
+                  offsetof(FearPairGeom, presence) == offsetof(PairGeom, presence), "FearPairGeom and PairGeom must share one layout");
+    if (n < 0 || n_frames < 0 || n > 65535) return FEAR_TRAIN_ERR_SHAPE;
+    if (n == 0) return FEAR_TRAIN_OK;
+    if (!geom || !lut || !template_out || !search_out || !gt_reg || !gt_cls || !gt_weight) return FEAR_TRAIN_ERR_NULL;
+    if (n_frames > 0 && (!frames || !border_rgb)) return FEAR_TRAIN_ERR_NULL;
+    PairArgs<Out> a{};
+    a.frames = reinterpret_cast<const CropFrame*>(frames);
+    a.border = border_rgb;
+    a.geom = reinterpret_cast<const PairGeom*>(geom);
+    a.lut = lut;
+    a.tmpl = template_out; a.search = search_out;
+    a.gt_reg = gt_reg; a.gt_cls = gt_cls; a.gt_weight = gt_weight;
+    a.n_frames = n_frames;
+    set_normalisation(a);
+    hipLaunchKernelGGL(train_pairs_kernel<Out>, dim3(kPairBlocks, (unsigned)n), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    LAUNCH_CHECK();
+    return FEAR_TRAIN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -304,26 +549,35 @@ int fear_frame_border_u8(const fear_frame* frames, int n_frames, uint8_t* out_rg
 
 int fear_train_pairs(const fear_frame* frames, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom, const uint8_t* lut,
                      int n, float* template_out, float* search_out, float* gt_reg, float* gt_cls, float* gt_weight, void* stream) {
-    static_assert(sizeof(FearPairGeom) == sizeof(PairGeom) && offsetof(FearPairGeom, inv) == offsetof(PairGeom, inv) &&
-                  offsetof(FearPairGeom, presence) == offsetof(PairGeom, presence), "FearPairGeom and PairGeom must share one layout");
-    if (n < 0 || n_frames < 0 || n > 65535) return FEAR_TRAIN_ERR_SHAPE;
+    return launch_train_pairs<float>(frames, n_frames, border_rgb, geom, lut, n, template_out, search_out, gt_reg, gt_cls, gt_weight,
+                                     stream);
+}
+
+int fear_train_pairs_u8(const fear_frame* frames, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom, const uint8_t* lut,
+                        int n, uint8_t* template_u8, uint8_t* search_u8, float* gt_reg, float* gt_cls, float* gt_weight, void* stream) {
+    return launch_train_pairs<uint8_t>(frames, n_frames, border_rgb, geom, lut, n, template_u8, search_u8, gt_reg, gt_cls, gt_weight,
+                                       stream);
+}
+
+int fear_photometric_u8(const uint8_t* crops_u8, int n, int H, int W, const FearPhotoOp* ops, const float* taps, const float* qtable,
+                        float* out_f32, void* stream) {
+    static_assert(sizeof(FearPhotoOp) == sizeof(PhotoOp) && offsetof(FearPhotoOp, scale) == offsetof(PhotoOp, scale) &&
+                  offsetof(FearPhotoOp, key) == offsetof(PhotoOp, key) && offsetof(FearPhotoOp, tap_row) == offsetof(PhotoOp, tap_row),
+                  "FearPhotoOp and PhotoOp must share one layout");
+    if (n < 0 || n > 65535 || H < 4 || W < 4 || (H & 1) || (W & 1) || (long)H * W > 0x7fffffffL / 3) return FEAR_TRAIN_ERR_SHAPE;
     if (n == 0) return FEAR_TRAIN_OK;
-    if (!geom || !lut || !template_out || !search_out || !gt_reg || !gt_cls || !gt_weight) return FEAR_TRAIN_ERR_NULL;
-    if (n_frames > 0 && (!frames || !border_rgb)) return FEAR_TRAIN_ERR_NULL;
-    PairArgs a{};
-    a.frames = reinterpret_cast<const CropFrame*>(frames);
-    a.border = border_rgb;
-    a.geom = reinterpret_cast<const PairGeom*>(geom);
-    a.lut = lut;
-    a.tmpl = template_out; a.search = search_out;
-    a.gt_reg = gt_reg; a.gt_cls = gt_cls; a.gt_weight = gt_weight;
-    a.n_frames = n_frames;
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    for (int c = 0; c < 3; ++c) {                 // fear_normalize_u8's constants
-        a.mean[c] = mean[c] * 255.0f;
-        a.inv_std[c] = 1.0f / (stdv[c] * 255.0f);
-    }
-    hipLaunchKernelGGL(train_pairs_kernel, dim3(kPairBlocks, (unsigned)n), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    if (!crops_u8 || !ops || !qtable || !out_f32) return FEAR_TRAIN_ERR_NULL;      // taps may be null: no record may then point at one
+    const unsigned gx = (unsigned)((W + kPhTile - 1) / kPhTile), gy = (unsigned)((H + kPhTile - 1) / kPhTile);
+    if (gy > 65535u) return FEAR_TRAIN_ERR_SHAPE;
+    PhotoArgs a{};
+    a.in = crops_u8;
+    a.ops = reinterpret_cast<const PhotoOp*>(ops);
+    a.taps = taps;
+    a.q = qtable;
+    a.out = out_f32;
+    a.H = H; a.W = W;
+    set_normalisation(a);
+    hipLaunchKernelGGL(photometric_kernel, dim3(gx, gy, (unsigned)n), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }

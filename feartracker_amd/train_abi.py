@@ -78,6 +78,9 @@ TRAIN_SYMBOLS = {
     # training pairs from frames (train_data.TrainPairBuilder)
     "fear_frame_border_u8": ([_P, _i, _P, _P], _i),
     "fear_train_pairs": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _P, _P], _i),
+    # the photometric stage behind the pairs (FearPhotoOp below)
+    "fear_train_pairs_u8": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _P, _P], _i),
+    "fear_photometric_u8": ([_P, _i, _i, _i, _P, _P, _P, _P, _P], _i),
     # step metrics (metrics.TrainMetrics)
     "fear_train_metrics": ([_P, _P, _P, _P, _P, _i, _i, _P, _P, _P, _P], _i),
 }
@@ -120,6 +123,14 @@ class FearOptim(ctypes.Structure):
     _fields_ = [("kind", _i), ("nesterov", _i), ("lr", _d), ("beta1", _d), ("beta2", _d), ("eps", _d), ("weight_decay", _d),
                 ("momentum", _d), ("dampening", _d)]
 
+
+class FearPhotoOp(ctypes.Structure):
+    """include/fear_train.h: one crop's photometric record (train_data.PHOTO_DTYPE is its numpy form)."""
+    _fields_ = [("blur", ctypes.c_int32), ("ksize", ctypes.c_int32), ("noise", ctypes.c_int32), ("scale", _f),
+                ("key", ctypes.c_uint32 * 2), ("downscale", ctypes.c_int32), ("tap_row", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(FearPhotoOp) == 32
 
 _ALLREDUCE_FN =ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p)
 FEAR_SYNC_BUF_BYTES = 16384

@@ -9,6 +9,9 @@
             aug.py:52-143); the box follows through `apply_to_bbox`, `ensure_bbox_boundaries`, `handle_empty_bbox`
 * colour    `OneOf([ToGray, ToSepia], p=0.05)` and, at p = 0.5, one of RandomBrightnessContrast / RandomGamma / RGBShift — drawn once
             per pair and applied to both crops (siam_dataset.py:64-67; the subset is DESIGN.md section 11's)
+* photometric  (`photometric=True`, off by default) `PHOTOMETRIC_AUGMENTATIONS` on each crop on its own, between the colour stage and
+            the normalisation: a blur group, a noise group and Downscale(0.5), each at p = 0.2 (aug.py:8-25, tracking_dataset.py:
+            158-175; the members built are DESIGN.md section 11's); `photometric_host` restates the device's `fear_photometric_u8`
 * targets   `FEARBoxCoder.encode(search_bbox)` and `get_regression_weight_label(search_bbox, 256, 16)`, zeros without presence
 
 Every scalar per-pair step runs here on the host, vectorised over the batch: the draws (`draw`), the context boxes (`extend_bbox`,
@@ -24,6 +27,7 @@ Python run on recorded draws (tests/golden/train_pairs_geometry.npz, tools/make_
 from __future__ import annotations
 
 import ctypes
+import statistics
 from collections import namedtuple
 from dataclasses import dataclass
 from typing import Any, Dict, Optional, Sequence, Tuple
@@ -46,10 +50,21 @@ DEFAULT_TRAIN_DATA_CONFIG: Dict[str, Any] = dict(
     tone_p=0.05,                 # OneOf([ToGray, ToSepia])
     colour_p=0.5,                # OneOf([RandomBrightnessContrast, RandomGamma, RGBShift])
     brightness_limit=0.2, contrast_limit=0.2, gamma_limit=(0.8, 1.2), rgb_shift_limit=20.0,
+    # PHOTOMETRIC_AUGMENTATIONS (dataset/aug.py:8-25), per crop, off unless asked for
+    photometric=False,
+    blur_p=0.2,                  # OneOf([Blur, GaussianBlur, MedianBlur, MotionBlur])
+    noise_p=0.2,                 # OneOf([MultiplicativeNoise, GaussNoise])
+    downscale_p=0.2,             # Downscale(0.5, 0.5)
+    blur_limit=7, gauss_var_limit=(10, 35), multiplier=(0.9, 1.1),
 )
 
 TONE_NONE, TONE_GRAY, TONE_SEPIA = 0, 1, 2
 COLOUR_NONE, COLOUR_BRIGHTNESS_CONTRAST, COLOUR_GAMMA, COLOUR_RGB_SHIFT = 0, 1, 2, 3
+
+BLUR_NONE, BLUR_BOX, BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_MOTION = 0, 1, 2, 3, 4
+NOISE_NONE, NOISE_MULTIPLICATIVE, NOISE_GAUSS = 0, 1, 2
+N_QUANTILES = 4096
+GAUSS_WEIGHTS = {3: (64, 128, 64), 5: (16, 64, 96, 64, 16), 7: (8, 28, 56, 72, 56, 28, 8)}
 
 # columns of the pairs table
 PAIR_COLUMNS = ("template_frame", "tx", "ty", "tw", "th", "search_frame", "sx", "sy", "sw", "sh", "presence")
@@ -62,6 +77,23 @@ GEOM_DTYPE = np.dtype([("t_frame", "<i4"), ("s_frame", "<i4"), ("t_ctx", "<i4", 
                        ("presence", "<i4"), ("tone", "<i4"), ("inv", "<f8", 4)])
 assert GEOM_DTYPE.itemsize == 96
 FRAME_DTYPE = np.dtype([("data", "<u8"), ("h", "<i4"), ("w", "<i4")])        # fear_frame
+PHOTO_DTYPE = np.dtype([("blur", "<i4"), ("ksize", "<i4"), ("noise", "<i4"), ("scale", "<f4"), ("key", "<u4", 2),
+                        ("downscale", "<i4"), ("tap_row", "<i4")])             # FearPhotoOp
+assert PHOTO_DTYPE.itemsize == 32
+
+
+@dataclass
+class PhotoParams:
+    """The photometric draws of one batch, every array shaped (B, 2, ...): [:, 0] the template crop, [:, 1] the search crop.  The
+    values of all members are drawn; only the drawn member's are used."""
+    blur: np.ndarray             # int32, BLUR_*
+    ksize: np.ndarray            # int32, 3 / 5 / 7
+    line: np.ndarray             # (B, 2, 4) int32: MotionBlur's end points xs, ys, xe, ye
+    noise: np.ndarray            # int32, NOISE_*
+    var: np.ndarray              # float64, GaussNoise's variance
+    mult: np.ndarray             # float64, MultiplicativeNoise's multiplier
+    key: np.ndarray              # (B, 2, 2) uint32, the Philox key of GaussNoise
+    downscale: np.ndarray        # int32, 0 / 1
 
 
 @dataclass
@@ -78,6 +110,7 @@ class TrainPairParams:
     gamma: np.ndarray            # (B,)
     shift: np.ndarray            # (B, 3) RGB shift
     frame_shapes: Tuple[Tuple[int, int], ...]
+    photo: Optional[PhotoParams] = None      # the photometric draws, None with the stage off
 
 
 def _pairs_array(pairs) -> np.ndarray:
@@ -291,13 +324,165 @@ def apply_tone(rgb: np.ndarray, tone: int) -> np.ndarray:
     return rgb
 
 
+def _colour_u8(rgb: np.ndarray, tone: int, lut: np.ndarray) -> np.ndarray:
+    """(H, W, 3) uint8 -> tone -> lut -> (H, W, 3) uint8: fear_train_pairs_u8's crop."""
+    v = apply_tone(rgb, tone)
+    return np.stack([lut[c][v[..., c]] for c in range(3)], axis=-1)
+
+
 def _colour_normalise(rgb: np.ndarray, tone: int, lut: np.ndarray) -> np.ndarray:
     """(H, W, 3) uint8 -> tone -> lut -> normalised fp32 (3, H, W)."""
-    v = apply_tone(rgb, tone)
-    v = np.stack([lut[c][v[..., c]] for c in range(3)], axis=-1).astype(np.float32)
+    v = _colour_u8(rgb, tone, lut).astype(np.float32)
     v -= _MEAN
     v *= _INV_STD
     return np.ascontiguousarray(v.transpose(2, 0, 1))
+
+
+# ------------------------------------------------------------------------------------------------------------------- photometric
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32_10(counter: np.ndarray, key: np.ndarray) -> np.ndarray:
+    """Philox4x32-10 (Salmon et al., Random123) over rows: counter (..., 4), key (..., 2) uint32 -> (..., 4) uint32."""
+    c = np.asarray(counter).astype(np.uint64)
+    k = np.asarray(key).astype(np.uint64)
+    c0, c1, c2, c3 = (c[..., i] for i in range(4))
+    k0, k1 = k[..., 0], k[..., 1]
+    mask = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0 = np.uint64(_PHILOX_M0) * c0
+        p1 = np.uint64(_PHILOX_M1) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & mask, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & mask
+        k0 = (k0 + np.uint64(_PHILOX_W0)) & mask
+        k1 = (k1 + np.uint64(_PHILOX_W1)) & mask
+    return np.stack(np.broadcast_arrays(c0, c1, c2, c3), axis=-1).astype(np.uint32)
+
+
+_QUANTILES = None
+
+
+def normal_quantiles() -> np.ndarray:
+    """GaussNoise's normal variates: (4096,) fp32, entry i = the standard normal's quantile at (i + 0.5) / 4096.  A table lookup has
+    the same bits on the host and on the device, which logf / cosf do not.  Tails end at +-3.67, the variance is 0.9997."""
+    global _QUANTILES
+    if _QUANTILES is None:
+        nd = statistics.NormalDist()
+        _QUANTILES = np.array([nd.inv_cdf((i + 0.5) / N_QUANTILES) for i in range(N_QUANTILES)], dtype=np.float32)
+    return _QUANTILES
+
+
+def line_u8(k: int, xs: int, ys: int, xe: int, ye: int) -> np.ndarray:
+    """cv2.line(zeros((k, k), uint8), (xs, ys), (xe, ye), 1, thickness=1): OpenCV's 8-connected LineIterator, left to right (the end
+    points swap when xe < xs), one pixel per step of the longer axis, the error term deciding the steps of the shorter one."""
+    img = np.zeros((k, k), dtype=np.uint8)
+    x, y, dx, dy = int(xs), int(ys), int(xe) - int(xs), int(ye) - int(ys)
+    if dx < 0:
+        x, y, dx, dy = int(xe), int(ye), -dx, -dy
+    step_y = -1 if dy < 0 else 1
+    dy = abs(dy)
+    steep = dy > dx
+    major, minor = (dy, dx) if steep else (dx, dy)
+    err = major - 2 * minor
+    for _ in range(major + 1):
+        img[y, x] = 1
+        diag = err < 0
+        err += -2 * minor + (2 * major if diag else 0)
+        if steep:
+            y += step_y
+            x += 1 if diag else 0
+        else:
+            x += 1
+            y += step_y if diag else 0
+    return img
+
+
+def motion_kernel(k: int, xs: int, ys: int, xe: int, ye: int) -> np.ndarray:
+    """MotionBlur.get_params' kernel for drawn end points: the line divided by its sum, (k, k) fp32."""
+    line = line_u8(k, xs, ys, xe, ye)
+    return line.astype(np.float32) / np.float32(line.sum())
+
+
+def motion_taps(kernel: np.ndarray) -> np.ndarray:
+    """A (k, k) kernel as one row of the device's tap table: centred in 7 x 7, row-major, (49,) fp32."""
+    k = kernel.shape[0]
+    full = np.zeros((7, 7), dtype=np.float32)
+    o = (7 - k) // 2
+    full[o:o + k, o:o + k] = kernel
+    return full.reshape(49)
+
+
+def photo_tables(photo: PhotoParams) -> Tuple[np.ndarray, np.ndarray]:
+    """FearPhotoOp records (B, 2) and the tap table (m, 49) fp32 of the drawn MotionBlurs (m may be 0), in record order."""
+    B = photo.blur.shape[0]
+    ops = np.zeros((B, 2), dtype=PHOTO_DTYPE)
+    ops["blur"], ops["ksize"], ops["noise"] = photo.blur, photo.ksize, photo.noise
+    sigma = np.sqrt(np.asarray(photo.var, dtype=np.float64)).astype(np.float32)
+    ops["scale"] = np.where(photo.noise == NOISE_GAUSS, sigma, np.asarray(photo.mult).astype(np.float32))
+    ops["key"] = photo.key
+    ops["downscale"] = (np.asarray(photo.downscale) != 0).astype(np.int32)
+    ops["tap_row"] = -1
+    taps = []
+    for b, j in np.argwhere(photo.blur == BLUR_MOTION):
+        ops["tap_row"][b, j] = len(taps)
+        taps.append(motion_taps(motion_kernel(int(photo.ksize[b, j]), *(int(v) for v in photo.line[b, j]))))
+    return ops, np.stack(taps) if taps else np.zeros((0, 49), dtype=np.float32)
+
+
+def _windows(img: np.ndarray, r: int, mode: str) -> np.ndarray:
+    """(H, W, 3) -> (H, W, 3, k, k) windows of the image padded by r (`reflect` = BORDER_REFLECT_101, `edge` = BORDER_REPLICATE)."""
+    padded = np.pad(img, ((r, r), (r, r), (0, 0)), mode=mode)
+    return np.lib.stride_tricks.sliding_window_view(padded, (2 * r + 1, 2 * r + 1), axis=(0, 1))
+
+
+def photometric_u8_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray) -> np.ndarray:
+    """fear_photometric_u8's uint8 result for one (H, W, 3) crop and its FearPhotoOp record `op` (a PHOTO_DTYPE scalar), before the
+    normalisation: blur, then noise, then Downscale(0.5).  Records the device treats as "none" are "none" here too."""
+    v = np.asarray(crop_u8)
+    H, W = v.shape[:2]
+    if H < 4 or W < 4 or H % 2 or W % 2:
+        raise ValueError("the photometric stage takes even sides of at least 4")
+    blur, k, noise, row = int(op["blur"]), int(op["ksize"]), int(op["noise"]), int(op["tap_row"])
+    if k not in (3, 5, 7) or (blur == BLUR_MOTION and (taps is None or row < 0)):
+        blur = BLUR_NONE
+    r = k // 2
+    if blur == BLUR_BOX:
+        s = _windows(v, r, "reflect").astype(np.int64).sum(axis=(-1, -2))
+        v = ((s + k * k // 2) // (k * k)).astype(np.uint8)
+    elif blur == BLUR_GAUSSIAN:
+        w = np.asarray(GAUSS_WEIGHTS[k], dtype=np.int64)
+        s = (_windows(v, r, "reflect").astype(np.int64) * (w[:, None] * w[None, :])).sum(axis=(-1, -2))
+        v = ((s + 32768) >> 16).astype(np.uint8)
+    elif blur == BLUR_MEDIAN:
+        win = _windows(v, r, "edge").reshape(H, W, 3, k * k)
+        v = np.sort(win, axis=-1)[..., k * k // 2]
+    elif blur == BLUR_MOTION:
+        win = _windows(v, 3, "reflect")
+        acc = np.zeros((H, W, 3), dtype=np.float32)
+        for t, wt in enumerate(np.asarray(taps[row], dtype=np.float32)):
+            if wt != 0:
+                acc = acc + wt * win[..., t // 7, t % 7].astype(np.float32)
+        v = np.clip(np.rint(acc), 0, 255).astype(np.uint8)
+    if noise == NOISE_MULTIPLICATIVE:
+        v = np.clip(v.astype(np.float32) * np.float32(op["scale"]), 0, 255).astype(np.uint8)
+    elif noise == NOISE_GAUSS:
+        yy, xx = np.mgrid[0:H, 0:W]
+        counter = np.stack([xx, yy, np.zeros_like(xx), np.zeros_like(xx)], axis=-1)
+        idx = philox4x32_10(counter, np.asarray(op["key"]))[..., :3] >> np.uint32(20)
+        f = np.float32(op["scale"]) * np.asarray(q, dtype=np.float32)[idx]
+        f = v.astype(np.float32) + f
+        v = np.clip(f, 0, 255).astype(np.uint8)
+    if int(op["downscale"]) != 0:
+        v = np.repeat(np.repeat(v[::2, ::2], 2, axis=0), 2, axis=1)
+    return np.ascontiguousarray(v)
+
+
+def photometric_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray) -> np.ndarray:
+    """numpy restatement of fear_photometric_u8 for one crop: (H, W, 3) uint8 -> normalised fp32 (3, H, W)."""
+    v = photometric_u8_host(crop_u8, op, taps, q).astype(np.float32)
+    v -= _MEAN
+    v *= _INV_STD
+    return np.ascontiguousarray(v.transpose(2, 0, 1))
+
 
 
 def encode_targets(search_bbox: np.ndarray, presence: np.ndarray, r_pos: int = 2):
@@ -335,6 +520,7 @@ class TrainPairBuilder:
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.generator = np.random.default_rng(seed)
         self._lib = None
+        self._qtable = None
 
     # ------------------------------------------------------------------ draws
     def draw(self, pairs, frame_shapes: Sequence[Tuple[int, ...]], generator: Optional[np.random.Generator] = None) -> TrainPairParams:
@@ -357,7 +543,38 @@ class TrainPairBuilder:
         gamma = rng.uniform(cfg["gamma_limit"][0], cfg["gamma_limit"][1], size=B)
         shift = rng.uniform(-cfg["rgb_shift_limit"], cfg["rgb_shift_limit"], size=(B, 3))
         shapes = tuple((int(s[0]), int(s[1])) for s in frame_shapes)
-        return TrainPairParams(context, jitter, tone, colour, alpha, beta, gamma, shift, shapes)
+        photo = self._draw_photo(B, rng) if cfg["photometric"] else None       # after every other draw: off consumes nothing
+        return TrainPairParams(context, jitter, tone, colour, alpha, beta, gamma, shift, shapes, photo)
+
+    def _draw_photo(self, B: int, rng: np.random.Generator) -> PhotoParams:
+        """The photometric draws, (B, 2): each group at its p, uniform over its members (aug.py:8-25); ksize uniform over the odd
+        sizes up to blur_limit; MotionBlur's end points as MotionBlur.get_params draws them (two x, then two y, distinct when the x
+        are equal); var and the multiplier uniform over their limits; a fresh 64-bit Philox key per crop."""
+        cfg = self.config
+        n_k = (int(cfg["blur_limit"]) - 3) // 2 + 1
+        if n_k < 1 or n_k > 3:
+            raise ValueError("blur_limit must be 3, 5 or 7")
+        blur = np.where(rng.random((B, 2)) < cfg["blur_p"], 1 + rng.integers(0, 4, size=(B, 2)), BLUR_NONE).astype(np.int32)
+        ksize = (3 + 2 * rng.integers(0, n_k, size=(B, 2))).astype(np.int32)
+        xs, xe, ys, ye = (rng.integers(0, ksize) for _ in range(4))
+        other = (ys + 1 + rng.integers(0, ksize - 1)) % ksize                  # random.sample(range(k), 2)'s second value
+        line = np.stack([xs, ys, xe, np.where(xs == xe, other, ye)], axis=-1).astype(np.int32)
+        noise = np.where(rng.random((B, 2)) < cfg["noise_p"], 1 + rng.integers(0, 2, size=(B, 2)), NOISE_NONE).astype(np.int32)
+        var = rng.uniform(cfg["gauss_var_limit"][0], cfg["gauss_var_limit"][1], size=(B, 2))
+        mult = rng.uniform(cfg["multiplier"][0], cfg["multiplier"][1], size=(B, 2))
+        key = rng.integers(0, 2 ** 32, size=(B, 2, 2), dtype=np.uint64).astype(np.uint32)
+        downscale = (rng.random((B, 2)) < cfg["downscale_p"]).astype(np.int32)
+        return PhotoParams(blur, ksize, line, noise, var, mult, key, downscale)
+
+    def _photo(self, params: TrainPairParams, B: int) -> Optional[PhotoParams]:
+        """The batch's photometric draws when the stage is on, None when it is off."""
+        if not self.config["photometric"]:
+            return None
+        if params.photo is None:
+            raise ValueError("the photometric stage is on, but params carry no photometric draws (drawn with it off?)")
+        if params.photo.blur.shape != (B, 2):
+            raise ValueError(f"photometric draws are shaped {params.photo.blur.shape}, the table has {B} pairs")
+        return params.photo
 
     # ------------------------------------------------------------------ host tables
     def tables(self, pairs, params: TrainPairParams) -> Dict[str, np.ndarray]:
@@ -407,6 +624,15 @@ class TrainPairBuilder:
         B = len(geom)
         tmpl = np.empty((B, 3, TEMPLATE_SIZE, TEMPLATE_SIZE), dtype=np.float32)
         srch = np.empty((B, 3, SEARCH_SIZE, SEARCH_SIZE), dtype=np.float32)
+        photo = self._photo(params, B)
+        if photo is not None:
+            ops, taps = photo_tables(photo)
+            q = normal_quantiles()
+
+        def finish(crop, k, which):          # colour stage -> (photometric stage) -> normalised fp32
+            if photo is None:
+                return _colour_normalise(crop, int(geom["tone"][k]), lut[k])
+            return photometric_host(_colour_u8(crop, int(geom["tone"][k]), lut[k]), ops[k, which], taps, q)
 
         def frame_of(i):
             if 0 <= i < len(host):
@@ -416,11 +642,11 @@ class TrainPairBuilder:
         for k in range(B):
             f, pad = frame_of(int(geom["t_frame"][k]))
             t = crop_u8(f, pad, geom["t_ctx"][k], TEMPLATE_SIZE)
-            tmpl[k] = _colour_normalise(t, int(geom["tone"][k]), lut[k])
+            tmpl[k] = finish(t, k, 0)
             f, pad = frame_of(int(geom["s_frame"][k]))
             c512 = crop_u8(f, pad, geom["s_ctx"][k], CONTEXT_SIZE)
             s = remap_affine_u8(c512, tab["Minv"][k], (SEARCH_SIZE, SEARCH_SIZE))
-            srch[k] = _colour_normalise(s, int(geom["tone"][k]), lut[k])
+            srch[k] = finish(s, k, 1)
         reg, cls, wgt = encode_targets(tab["search_bbox"], geom["presence"], int(self.config["r_pos"]))
         return TrainBatch(tmpl, srch, reg, cls, wgt, tab["search_bbox"].astype(np.int32))
 
@@ -443,14 +669,19 @@ class TrainPairBuilder:
         tab = self.tables(pairs, params)
         geom, lut = tab["geom"], tab["lut"]
         B, F = len(geom), len(frames)
+        photo = self._photo(params, B)
+        if photo is not None:
+            ops, taps = photo_tables(photo)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
             dframes = [self._frame_on_device(f) for f in frames]
-            # one staging buffer, one transfer: frame table | geometry | lookup tables | search_bbox
+            # one staging buffer, one transfer: frame table | geometry | lookup tables | search_bbox | photometric records | taps
             o_geom = 16 * F
             o_lut = o_geom + 96 * B
             o_box = o_lut + 768 * B
-            total = o_box + 16 * B
+            o_ops = o_box + 16 * B
+            o_taps = o_ops + (64 * B if photo is not None else 0)
+            total = o_taps + (taps.size * 4 if photo is not None else 0)
             pinned = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True)
             hv = pinned.numpy()
             ftab = np.zeros(F, dtype=FRAME_DTYPE)
@@ -459,7 +690,10 @@ class TrainPairBuilder:
             hv[:o_geom] = ftab.view(np.uint8)
             hv[o_geom:o_lut] = geom.view(np.uint8)
             hv[o_lut:o_box] = lut.reshape(-1)
-            hv[o_box:total] = tab["search_bbox"].astype(np.int32).view(np.uint8).reshape(-1)
+            hv[o_box:o_ops] = tab["search_bbox"].astype(np.int32).view(np.uint8).reshape(-1)
+            if photo is not None:              # templates' records first, then the searches': one call each
+                hv[o_ops:o_taps] = np.ascontiguousarray(ops.T).view(np.uint8).reshape(-1)
+                hv[o_taps:total] = taps.view(np.uint8).reshape(-1)
             staged = pinned.to(dev, non_blocking=True)
             base = staged.data_ptr()
             border = torch.empty((max(F, 1), 3), dtype=torch.uint8, device=dev)
@@ -472,16 +706,40 @@ class TrainPairBuilder:
             rc = lib.fear_frame_border_u8(ctypes.c_void_p(base), F, ctypes.c_void_p(border.data_ptr()), st)
             if rc != 0:
                 raise RuntimeError(f"fear_frame_border_u8 failed with status {rc}")
-            rc = lib.fear_train_pairs(ctypes.c_void_p(base), F, ctypes.c_void_p(border.data_ptr()), ctypes.c_void_p(base + o_geom),
-                                      ctypes.c_void_p(base + o_lut), B, ctypes.c_void_p(tmpl.data_ptr()),
-                                      ctypes.c_void_p(srch.data_ptr()), ctypes.c_void_p(reg.data_ptr()),
-                                      ctypes.c_void_p(cls.data_ptr()), ctypes.c_void_p(wgt.data_ptr()), st)
+            if photo is None:
+                pairs_fn, t_out, s_out = "fear_train_pairs", tmpl, srch
+            else:                              # the crops leave the colour stage as uint8 HWC and pass through the photometric stage
+                pairs_fn = "fear_train_pairs_u8"
+                t_out = torch.empty((B, TEMPLATE_SIZE, TEMPLATE_SIZE, 3), dtype=torch.uint8, device=dev)
+                s_out = torch.empty((B, SEARCH_SIZE, SEARCH_SIZE, 3), dtype=torch.uint8, device=dev)
+            rc = getattr(lib, pairs_fn)(ctypes.c_void_p(base), F, ctypes.c_void_p(border.data_ptr()), ctypes.c_void_p(base + o_geom),
+                                        ctypes.c_void_p(base + o_lut), B, ctypes.c_void_p(t_out.data_ptr()),
+                                        ctypes.c_void_p(s_out.data_ptr()), ctypes.c_void_p(reg.data_ptr()),
+                                        ctypes.c_void_p(cls.data_ptr()), ctypes.c_void_p(wgt.data_ptr()), st)
             if rc != 0:
-                raise RuntimeError(f"fear_train_pairs failed with status {rc}")
+                raise RuntimeError(f"{pairs_fn} failed with status {rc}")
+            if photo is not None:
+                q = self._quantiles_on_device()
+                d_taps = ctypes.c_void_p(base + o_taps) if taps.size else None
+                for which, (crops, out, side) in enumerate(((t_out, tmpl, TEMPLATE_SIZE), (s_out, srch, SEARCH_SIZE))):
+                    rc = lib.fear_photometric_u8(ctypes.c_void_p(crops.data_ptr()), B, side, side,
+                                                 ctypes.c_void_p(base + o_ops + 32 * B * which), d_taps, ctypes.c_void_p(q.data_ptr()),
+                                                 ctypes.c_void_p(out.data_ptr()), st)
+                    if rc != 0:
+                        raise RuntimeError(f"fear_photometric_u8 failed with status {rc}")
             for f in dframes:                          # host frames were allocated here; device frames may live on another stream
                 f.record_stream(stream)
-            box = staged[o_box:total].view(torch.int32).view(B, 4)
+            box = staged[o_box:o_ops].view(torch.int32).view(B, 4)
         return TrainBatch(tmpl, srch, reg, cls, wgt, box)
+
+    def _quantiles_on_device(self) -> torch.Tensor:
+        """GaussNoise's quantile table on the device: uploaded once per builder, non-blocking from pinned memory.  Later builds on
+        other streams of the device find it complete only if they are ordered behind the first one, as stream users are."""
+        if self._qtable is None:
+            pinned = torch.empty(N_QUANTILES, dtype=torch.float32, pin_memory=True)
+            np.copyto(pinned.numpy(), normal_quantiles())
+            self._qtable = (pinned.to(self.device, non_blocking=True), pinned)     # (the pinned source lives as long as its copy)
+        return self._qtable[0]
 
     def _frame_on_device(self, f) -> torch.Tensor:
         if isinstance(f, torch.Tensor):

@@ -411,6 +411,64 @@ int fear_frame_border_u8(const fear_frame* frames, int n_frames, uint8_t* out_rg
 int fear_train_pairs(const fear_frame* frames, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom, const uint8_t* lut,
                      int n, float* template_out, float* search_out, float* gt_reg, float* gt_cls, float* gt_weight, void* stream);
 
+/* fear_train_pairs with the crops left as the colour stage made them — after the tone and the lookup table, before the normalisation —
+ * as uint8 HWC, the input of fear_photometric_u8.  The same kernel body with another store policy; the targets are fear_train_pairs'.
+ *   template_u8 (n, 128, 128, 3), search_u8 (n, 256, 256, 3) uint8, device                                                          */
+int fear_train_pairs_u8(const fear_frame* frames, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom, const uint8_t* lut,
+                        int n, uint8_t* template_u8, uint8_t* search_u8, float* gt_reg, float* gt_cls, float* gt_weight, void* stream);
+
+/* ---- the photometric stage: PHOTOMETRIC_AUGMENTATIONS of the reference (model_training/dataset/aug.py:8-25) on each crop on its
+ * own, between the colour stage and the normalisation.  Per crop, in this order:
+ *   blur       1 Blur          (sum of the k x k window + k k / 2) / (k k) in integers, BORDER_REFLECT_101
+ *              2 GaussianBlur  sigma 0: 8-bit weights [64,128,64] / [16,64,96,64,16] / [8,28,56,72,56,28,8] on both axes,
+ *                              (sum_y sum_x w_y w_x p + 32768) >> 16, BORDER_REFLECT_101
+ *              3 MedianBlur    the exact median of the k x k window per channel, BORDER_REPLICATE
+ *              4 MotionBlur    cv2.filter2D with row `tap_row` of `taps`: a 7 x 7 fp32 kernel, row-major (a k x k kernel sits centred
+ *                              in it, zeros around): correlation, anchor at the centre, fp32 accumulation over the non-zero taps in
+ *                              row-major order, every product and sum rounded on its own, rint half to even, saturated,
+ *                              BORDER_REFLECT_101
+ *   noise      1 MultiplicativeNoise  trunc(clip(fp32(v) * scale, 0, 255)), one multiplier per crop
+ *              2 GaussNoise           trunc(clip(fp32(v) + scale * qtable[i], 0, 255)) per channel, scale = sigma; i = the top 12 bits of
+ *                                     word c of Philox4x32-10(counter (x, y, 0, 0), key) for channel c = 0, 1, 2
+ *   downscale  Downscale(0.5, INTER_NEAREST) and back: pixel (y, x) takes the value of (2 floor(y / 2), 2 floor(x / 2)); blur and
+ *              noise — the noise counter included — are evaluated at that even pixel, so a 2 x 2 block shares one value
+ * then fear_train_pairs' normalisation.  `qtable` is the caller's table of 4096 normal quantiles (train_data.normal_quantiles).
+ * The records live in device memory, where the call cannot read them: a record with an unknown blur or noise kind, a ksize outside
+ * {3, 5, 7}, or a MotionBlur with tap_row < 0 or a null `taps` has that member treated as "none" by the kernel.  A tap_row past the
+ * table's last row is the caller's error (the call does not know the table's length).  H and W must be even and >= 4 (one reflection
+ * at radius 3 stays inside), n <= 65535: FEAR_TRAIN_ERR_SHAPE otherwise.  n == 0 returns FEAR_TRAIN_OK without a launch.  A null
+ * crops_u8, ops, qtable or out_f32 returns FEAR_TRAIN_ERR_NULL; `taps` may be null.
+ *   crops_u8 : (n, H, W, 3) uint8, device      ops : (n) FearPhotoOp, device        taps : (m, 49) fp32, device, or NULL
+ *   qtable : (4096) fp32, device               out_f32 : (n, 3, H, W) fp32, device                                                 */
+#define FEAR_PHOTO_BLUR_NONE 0
+#define FEAR_PHOTO_BLUR_BOX 1
+#define FEAR_PHOTO_BLUR_GAUSSIAN 2
+#define FEAR_PHOTO_BLUR_MEDIAN 3
+#define FEAR_PHOTO_BLUR_MOTION 4
+#define FEAR_PHOTO_NOISE_NONE 0
+#define FEAR_PHOTO_NOISE_MULTIPLICATIVE 1
+#define FEAR_PHOTO_NOISE_GAUSS 2
+#define FEAR_PHOTO_QUANTILES 4096
+
+/* One crop.  32 bytes, no padding. */
+typedef struct FearPhotoOp {
+    int32_t blur;               /* FEAR_PHOTO_BLUR_*                                                                  */
+    int32_t ksize;              /* 3, 5 or 7 (read only with a blur)                                                  */
+    int32_t noise;              /* FEAR_PHOTO_NOISE_*                                                                 */
+    float scale;                /* the multiplier m, or sigma = fp32(sqrt(var))                                       */
+    uint32_t key[2];            /* the crop's Philox key (GaussNoise)                                                 */
+    int32_t downscale;          /* non-zero: Downscale(0.5)                                                           */
+    int32_t tap_row;            /* MotionBlur's row of `taps`, -1 otherwise                                           */
+} FearPhotoOp;
+#ifdef __cplusplus
+static_assert(sizeof(FearPhotoOp) == 32, "FearPhotoOp is 32 bytes");
+#else
+_Static_assert(sizeof(FearPhotoOp) == 32, "FearPhotoOp is 32 bytes");
+#endif
+
+int fear_photometric_u8(const uint8_t* crops_u8, int n, int H, int W, const FearPhotoOp* ops, const float* taps, const float* qtable,
+                        float* out_f32, void* stream);
+
 /* ---- step metrics: the training telemetry of the reference's `_training_step` (train/fear_lightning_model.py:66-87) on the device
  * (feartracker_amd/metrics.py).  Per pair: FEARBoxCoder.decode of the step's own output maps (fear_decode's
  * arithmetic: fp32 sigmoid, first maximum, float64 grid), box_convert(xywh -> xyxy) of the decoded and the ground-truth box, and

@@ -1,0 +1,258 @@
+"""The photometric stage on the GPU (include/fear_train.h: fear_photometric_u8, fear_train_pairs_u8): the operator through the C ABI,
+bit for bit against `photometric_host`, and `TrainPairBuilder` with the stage on against the stage-less path and `build_host`."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from feartracker_amd.train_data import (BLUR_BOX, BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_MOTION, BLUR_NONE, NOISE_GAUSS, NOISE_MULTIPLICATIVE,
+                                        NOISE_NONE, PHOTO_DTYPE, TrainPairBuilder, motion_kernel, motion_taps, normal_quantiles,
+                                        photometric_host)
+
+pytestmark = pytest.mark.gpu
+
+P = ctypes.c_void_p
+GUARD = 4096                       # floats of sentinel on either side of the output
+SENTINEL = -12345.0
+SMALL_SHAPES = [(4, 4), (8, 8), (34, 70)]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from feartracker_amd.train_abi import load_train_library
+    return load_train_library()
+
+
+@pytest.fixture(scope="module")
+def qtable():
+    return torch.from_numpy(normal_quantiles().copy()).cuda()
+
+
+def _ops(n, **fields):
+    ops = np.zeros(n, dtype=PHOTO_DTYPE)
+    ops["ksize"], ops["scale"], ops["tap_row"] = 3, 1.0, -1
+    for name, value in fields.items():
+        ops[name] = value
+    return ops
+
+
+def _images(h, w, seed=0):
+    """A seeded random crop and a checkerboard of 0 and 255 (saturation, ties between the channels' medians)."""
+    rnd = np.random.default_rng(seed).integers(0, 256, (h, w, 3), dtype=np.uint8)
+    yy, xx = np.mgrid[0:h, 0:w]
+    checker = np.repeat((((yy + xx) & 1) * 255).astype(np.uint8)[..., None], 3, axis=-1)
+    return np.stack([rnd, checker])
+
+
+def _taps_for(ops, lines):
+    """A tap table with one row per motion record (lines: record index -> end points), rows assigned in reverse record order so that
+    a row index is not its record's index."""
+    rows = [i for i in range(len(ops)) if ops["blur"][i] == BLUR_MOTION][::-1]
+    taps = np.zeros((len(rows), 49), dtype=np.float32)
+    for row, i in enumerate(rows):
+        ops["tap_row"][i] = row
+        taps[row] = motion_taps(motion_kernel(int(ops["ksize"][i]), *lines[i]))
+    return taps if len(rows) else None
+
+
+def _run(lib, qtable, crops, ops, taps):
+    """fear_photometric_u8 on (n, H, W, 3) uint8 crops -> (n, 3, H, W) fp32, the guard band around the output checked."""
+    n, h, w = crops.shape[:3]
+    d_in = torch.from_numpy(np.ascontiguousarray(crops)).cuda()
+    d_ops = torch.from_numpy(ops.view(np.uint8).copy()).cuda()
+    d_taps = torch.from_numpy(taps.copy()).cuda() if taps is not None else None
+    count = n * 3 * h * w
+    buf = torch.full((count + 2 * GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
+    st = P(torch.cuda.current_stream().cuda_stream)
+    rc = lib.fear_photometric_u8(P(d_in.data_ptr()), n, h, w, P(d_ops.data_ptr()), P(d_taps.data_ptr()) if d_taps is not None else None,
+                                 P(qtable.data_ptr()), P(buf.data_ptr() + 4 * GUARD), st)
+    assert rc == 0
+    torch.cuda.synchronize()
+    out = buf.cpu().numpy()
+    assert np.all(out[:GUARD] == np.float32(SENTINEL)) and np.all(out[GUARD + count:] == np.float32(SENTINEL)), "guard band written"
+    return out[GUARD:GUARD + count].reshape(n, 3, h, w)
+
+
+def _check(lib, qtable, crops, ops, taps):
+    out = _run(lib, qtable, crops, ops, taps)
+    q = normal_quantiles()
+    for i in range(len(crops)):
+        ref = photometric_host(crops[i], ops[i], taps, q)
+        bad = np.argwhere(out[i] != ref)
+        assert bad.size == 0, (f"crop {i} {ops[i]}: {len(bad)} of {ref.size} values differ, first at {bad[0].tolist()}: "
+                               f"{out[i][tuple(bad[0])]} vs {ref[tuple(bad[0])]}")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------- operator
+@pytest.mark.parametrize("k", [3, 5, 7])
+@pytest.mark.parametrize("blur", [BLUR_BOX, BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_MOTION])
+def test_blur_members(lib, qtable, blur, k):
+    for h, w in SMALL_SHAPES:
+        crops = _images(h, w, seed=10 * blur + k)
+        ops = _ops(2, blur=blur, ksize=k)
+        taps = _taps_for(ops, {0: (0, 0, k - 1, k - 2), 1: (k - 1, 0, k - 2, k - 1)})
+        _check(lib, qtable, crops, ops, taps)
+
+
+@pytest.mark.parametrize("noise,scale", [(NOISE_MULTIPLICATIVE, 0.9), (NOISE_MULTIPLICATIVE, 1.1), (NOISE_GAUSS, np.sqrt(10.0)),
+                                         (NOISE_GAUSS, np.sqrt(35.0))])
+def test_noise_members(lib, qtable, noise, scale):
+    for h, w in SMALL_SHAPES:
+        ops = _ops(2, noise=noise, scale=scale)
+        ops["key"] = [[0x1234 + h, 0xdeadbeef], [0xffffffff, w]]
+        _check(lib, qtable, _images(h, w, seed=h), ops, None)
+
+
+def test_downscale_alone(lib, qtable):
+    for h, w in SMALL_SHAPES:
+        out = _check(lib, qtable, _images(h, w, seed=3), _ops(2, downscale=1), None)
+        assert np.array_equal(out, np.repeat(np.repeat(out[:, :, ::2, ::2], 2, 2), 2, 3))
+
+
+def test_none_record_is_the_normalisation(lib, qtable):
+    mean = np.array([0.485, 0.456, 0.406], np.float32) * np.float32(255.0)
+    inv = np.reciprocal(np.array([0.229, 0.224, 0.225], np.float32) * np.float32(255.0), dtype=np.float32)
+    for h, w in SMALL_SHAPES:
+        crops = _images(h, w, seed=4)
+        out = _run(lib, qtable, crops, _ops(2), None)
+        ref = ((crops.astype(np.float32) - mean) * inv).transpose(0, 3, 1, 2)       # fear_train_pairs' normalisation
+        assert np.array_equal(out, ref)
+    # records the host cannot have drawn are "none" as well, a motion blur without a tap table included
+    crops = _images(8, 8, seed=5)
+    ref = _run(lib, qtable, crops, _ops(2), None)
+    for ops in (_ops(2, blur=9), _ops(2, blur=BLUR_BOX, ksize=4), _ops(2, blur=BLUR_MEDIAN, ksize=9), _ops(2, noise=5, scale=2.0),
+                _ops(2, blur=BLUR_MOTION, ksize=5, tap_row=0), _ops(2, blur=BLUR_MOTION, ksize=5, tap_row=-1)):
+        assert np.array_equal(_run(lib, qtable, crops, ops, None), ref)
+
+
+def _chain_records(seed):
+    """Five crops, a different record each: every blur member, both noises, downscale on and off, two motion rows."""
+    ops = _ops(5)
+    ops["blur"] = [BLUR_MOTION, BLUR_MEDIAN, BLUR_BOX, BLUR_MOTION, BLUR_GAUSSIAN]
+    ops["ksize"] = [7, 5, 3, 3, 7]
+    ops["noise"] = [NOISE_GAUSS, NOISE_MULTIPLICATIVE, NOISE_GAUSS, NOISE_NONE, NOISE_GAUSS]
+    ops["scale"] = [np.sqrt(35.0), 1.07, np.sqrt(10.0), 1.0, np.sqrt(20.0)]
+    ops["key"] = np.random.default_rng(seed).integers(0, 2 ** 32, (5, 2), dtype=np.uint64).astype(np.uint32)
+    ops["downscale"] = [1, 1, 0, 1, 1]
+    taps = _taps_for(ops, {0: (6, 1, 0, 5), 3: (1, 0, 1, 2)})
+    return ops, taps
+
+
+def _five(h, w, seed):
+    a, b = _images(h, w, seed), _images(h, w, seed + 1)
+    return np.concatenate([a, b, a[1:]])
+
+
+@pytest.mark.parametrize("shape", SMALL_SHAPES + [(128, 128), (256, 256)])
+def test_chains_with_a_record_per_crop(lib, qtable, shape):
+    ops, taps = _chain_records(shape[0])
+    out = _check(lib, qtable, _five(*shape, seed=shape[1]), ops, taps)
+    for i in np.flatnonzero(ops["downscale"]):                                   # a 2 x 2 block shares one noisy value
+        assert np.array_equal(out[i], np.repeat(np.repeat(out[i][:, ::2, ::2], 2, 1), 2, 2))
+    assert not np.array_equal(out[2], np.repeat(np.repeat(out[2][:, ::2, ::2], 2, 1), 2, 2))
+
+
+def test_single_crop(lib, qtable):
+    ops, taps = _chain_records(1)
+    crops = _five(34, 70, seed=6)
+    for i in (0, 3):                                                              # n = 1, a tap row other than 0
+        _check(lib, qtable, crops[i:i + 1], ops[i:i + 1], taps)
+
+
+def test_argument_checks(lib, qtable):
+    crops = torch.zeros((2, 8, 8, 3), dtype=torch.uint8, device="cuda")
+    ops = torch.from_numpy(_ops(2).view(np.uint8).copy()).cuda()
+    out = torch.full((2, 3, 8, 8), SENTINEL, device="cuda")
+    st = P(torch.cuda.current_stream().cuda_stream)
+
+    def call(**kw):
+        return lib.fear_photometric_u8(kw.get("crops", P(crops.data_ptr())), kw.get("n", 2), kw.get("h", 8), kw.get("w", 8),
+                                       kw.get("ops", P(ops.data_ptr())), None, kw.get("q", P(qtable.data_ptr())),
+                                       kw.get("out", P(out.data_ptr())), st)
+
+    for bad in (dict(h=7), dict(w=7), dict(w=2), dict(h=2), dict(h=0), dict(n=-1)):
+        assert call(**bad) == -2, bad
+    for name in ("crops", "ops", "q", "out"):
+        assert call(**{name: None}) == -1, name
+    assert call(n=0, crops=None, ops=None, out=None) == 0
+    torch.cuda.synchronize()
+    assert bool((out == SENTINEL).all())                                         # refused calls and n = 0 write nothing
+    assert call() == 0
+    torch.cuda.synchronize()
+    assert not bool((out == SENTINEL).any())
+
+
+# ----------------------------------------------------------------------------------------------------------------------- builder
+def _frames(seed=0):
+    rng = np.random.default_rng(seed)
+    out = []
+    for h, w in ((48, 64), (256, 480)):
+        yy, xx = np.mgrid[0:h, 0:w]
+        base = np.stack([xx * 255 // (w - 1), yy * 255 // (h - 1), (xx + yy) % 256], axis=-1)
+        out.append(np.clip(base + rng.integers(0, 64, (h, w, 3)) - 32, 0, 255).astype(np.uint8))
+    return out
+
+
+def _pairs(B, seed=1):
+    rng = np.random.default_rng(seed)
+    p = np.zeros((B, 11))
+    for k in range(B):
+        for col, f in ((0, k % 2), (5, (k + 1) % 2)):
+            h, w = ((48, 64), (256, 480))[f]
+            bw, bh = rng.integers(4, w // 3), rng.integers(4, h // 3)
+            p[k, col:col + 5] = [f, rng.integers(0, w - bw + 1), rng.integers(0, h - bh + 1), bw, bh]
+        p[k, 10] = 1
+    return p
+
+
+def _equal(dev, host):
+    for name in ("template", "search", "gt_reg", "gt_cls", "gt_weight", "search_bbox"):
+        d = getattr(dev, name)
+        d = d.cpu().numpy() if isinstance(d, torch.Tensor) else d
+        h = getattr(host, name)
+        h = h.cpu().numpy() if isinstance(h, torch.Tensor) else h
+        assert d.shape == h.shape and d.dtype == h.dtype, name
+        bad = np.argwhere(d != h)
+        assert bad.size == 0, f"{name}: {len(bad)} values differ, first at {bad[:3].tolist()}"
+
+
+def test_all_none_equals_the_stage_less_path():
+    """fear_train_pairs_u8 + fear_photometric_u8 with "none" records against fear_train_pairs: the same draws, every tone branch."""
+    frames = _frames(1)
+    pairs = _pairs(3)
+    off, on = TrainPairBuilder(device=0), TrainPairBuilder(dict(photometric=True), device=0)
+    params = on.draw(pairs, [f.shape for f in frames], np.random.default_rng(2))
+    params.tone[:] = [0, 1, 2]
+    params.colour[:] = [1, 2, 3]
+    params.photo.blur[:], params.photo.noise[:], params.photo.downscale[:] = BLUR_NONE, NOISE_NONE, 0
+    a = off.build(frames, pairs, params)
+    b = on.build(frames, pairs, params)
+    torch.cuda.synchronize()
+    _equal(b, a)
+
+
+def test_enabled_build_equals_build_host():
+    frames = _frames(3)
+    pairs = _pairs(4, seed=4)
+    builder = TrainPairBuilder(dict(photometric=True), device=0)
+    params = builder.draw(pairs, [f.shape for f in frames], np.random.default_rng(5))
+    params.tone[:] = [0, 1, 2, 0]
+    ph = params.photo                              # (pair, crop): every member appears, alone and in chains
+    ph.blur[:] = [[BLUR_BOX, BLUR_GAUSSIAN], [BLUR_MEDIAN, BLUR_MOTION], [BLUR_MOTION, BLUR_NONE], [BLUR_NONE, BLUR_MEDIAN]]
+    ph.ksize[:] = [[3, 5], [7, 7], [3, 5], [3, 3]]
+    ph.line[1, 1], ph.line[2, 0] = (0, 6, 5, 0), (2, 0, 2, 2)
+    ph.noise[:] = [[NOISE_GAUSS, NOISE_MULTIPLICATIVE], [NOISE_NONE, NOISE_GAUSS], [NOISE_NONE, NOISE_NONE], [NOISE_NONE, NOISE_MULTIPLICATIVE]]
+    ph.downscale[:] = [[0, 1], [0, 1], [0, 1], [0, 0]]
+    host = builder.build_host(frames, pairs, params)
+    dev_frames = [torch.from_numpy(f).cuda() for f in frames]
+    _equal(builder.build(frames, pairs, params), host)                 # host frames (and the allocators warm)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        dev = builder.build(dev_frames, pairs, params)                 # device frames: no wait for the GPU
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    torch.cuda.synchronize()
+    _equal(dev, host)

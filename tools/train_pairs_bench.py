@@ -9,7 +9,18 @@ can cost):
   step_with_build_ms builder.build + step per iteration, the same way
 Prints one JSON object; with --out also writes it there.
 
+With --photometric it reports the photometric stage instead (same pairs and frames):
+  build_off_ms       TrainPairBuilder.build with the stage off, wall time per call (synchronised at the end of `--iters` calls), one
+                     figure per fresh process (`--repeats`); with --parent-root DIR the same for the checkout at DIR, the processes
+                     of the two trees taking turns, so that both see the same box in the same minutes
+  build_on_ms        the same with photometric=True at the reference's probabilities, fresh draws per call
+  median7_ms         fear_photometric_u8 alone on the batch's 128 templates and 128 searches (two calls), every crop forced to the
+                     7 x 7 median, HIP events
+  step_ms            FEARNetTrainHIP.step on fixed inputs, for the shares
+--build-only is the child mode of the above: it times `build` of the package under --root and prints {"build_ms": ...}.
+
 Usage: python tools/train_pairs_bench.py [--pairs 128] [--frames 256] [--steps 20] [--iters 50] [--out FILE]
+       python tools/train_pairs_bench.py --photometric [--parent-root DIR] [--repeats 3] [--out FILE]
 """
 from __future__ import annotations
 
@@ -17,29 +28,17 @@ import argparse
 import ctypes
 import json
 import os
+import subprocess
 import sys
 import time
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--pairs", type=int, default=128)
-    ap.add_argument("--frames", type=int, default=256)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    from feartracker_amd.train_data import FRAME_DTYPE, TrainPairBuilder
-    from feartracker_amd.train_head import load_train_library
-    from feartracker_amd.train_net import FEARNetTrainHIP, random_init_state
-
-    dev = torch.device("cuda", 0)
-    B, F = args.pairs, args.frames
+def _inputs(B, F, dev):
     g = torch.Generator(device=dev).manual_seed(0)
     frames = [torch.randint(0, 256, (1080, 1920, 3), generator=g, device=dev, dtype=torch.uint8) for _ in range(F)]
     rng = np.random.default_rng(0)
@@ -50,6 +49,131 @@ def main():
     w2, h2 = rng.integers(40, 400, B), rng.integers(40, 400, B)
     pairs[:, 6], pairs[:, 7], pairs[:, 8], pairs[:, 9] = rng.integers(0, 1920 - w2), rng.integers(0, 1080 - h2), w2, h2
     pairs[:, 10] = 1
+    return frames, pairs
+
+
+def _time_build(builder, frames, pairs, iters):
+    for _ in range(5):
+        builder.build(frames, pairs)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        builder.build(frames, pairs)
+    torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t0) / iters
+
+
+def build_only(args):
+    """Child mode: `build` of the package under args.root (a checkout with its library built), stage off or on."""
+    sys.path.insert(0, os.path.abspath(args.root))
+    from feartracker_amd.train_data import TrainPairBuilder
+    frames, pairs = _inputs(args.pairs, args.frames, torch.device("cuda", 0))
+    builder = TrainPairBuilder(dict(photometric=True) if args.stage_on else None, device=0, seed=0)
+    print(json.dumps({"build_ms": round(_time_build(builder, frames, pairs, args.iters), 4)}))
+
+
+def _child(root, args, stage_on=False):
+    cmd = [sys.executable, os.path.abspath(__file__), "--build-only", "--root", root, "--pairs", str(args.pairs), "--frames",
+           str(args.frames), "--iters", str(args.iters)] + (["--stage-on"] if stage_on else [])
+    res = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300)
+    return json.loads(res.stdout.strip().splitlines()[-1])["build_ms"]
+
+
+def photometric(args):
+    # the fresh processes first, one at a time, before this process opens the GPU
+    off, parent, on = [], [], []
+    for _ in range(args.repeats):
+        off.append(_child(ROOT, args))
+        if args.parent_root:
+            parent.append(_child(args.parent_root, args))
+        on.append(_child(ROOT, args, stage_on=True))
+    sys.path.insert(0, ROOT)
+    from feartracker_amd.train_abi import load_train_library
+    from feartracker_amd.train_data import BLUR_MEDIAN, PHOTO_DTYPE, TrainPairBuilder, normal_quantiles
+    from feartracker_amd.train_net import FEARNetTrainHIP, random_init_state
+    dev = torch.device("cuda", 0)
+    B = args.pairs
+    lib = load_train_library()
+    P = ctypes.c_void_p
+    st = P(torch.cuda.current_stream(dev).cuda_stream)
+    ops = np.zeros(B, dtype=PHOTO_DTYPE)
+    ops["blur"], ops["ksize"], ops["tap_row"] = BLUR_MEDIAN, 7, -1
+    d_ops = torch.from_numpy(ops.view(np.uint8).copy()).to(dev)
+    q = torch.from_numpy(normal_quantiles().copy()).to(dev)
+    g = torch.Generator(device=dev).manual_seed(1)
+    crops = [torch.randint(0, 256, (B, s, s, 3), generator=g, device=dev, dtype=torch.uint8) for s in (128, 256)]
+    outs = [torch.empty((B, 3, s, s), device=dev) for s in (128, 256)]
+
+    def median7():
+        for c, o, s in zip(crops, outs, (128, 256)):
+            assert lib.fear_photometric_u8(P(c.data_ptr()), B, s, s, P(d_ops.data_ptr()), None, P(q.data_ptr()), P(o.data_ptr()), st) == 0
+
+    for _ in range(5):
+        median7()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.iters):
+        median7()
+    e1.record()
+    torch.cuda.synchronize()
+    median7_ms = e0.elapsed_time(e1) / args.iters
+
+    frames, pairs = _inputs(B, args.frames, dev)
+    net = FEARNetTrainHIP(random_init_state(0), device=0)
+    fixed = [t.clone() for t in TrainPairBuilder(device=0, seed=0).build(frames, pairs)[:5]]
+    steps = []
+    for _ in range(2):
+        for _ in range(3):
+            net.step(*fixed)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            net.step(*fixed)
+        torch.cuda.synchronize()
+        steps.append(1e3 * (time.perf_counter() - t0) / args.steps)
+    step_ms = min(steps)
+    med = lambda v: round(float(np.median(v)), 4) if v else None
+    report = {
+        "pairs": B, "frames": args.frames, "frame_hw": [1080, 1920], "iters": args.iters,
+        "build_off_ms": med(off), "build_off_runs": off,
+        "parent_build_ms": med(parent), "parent_build_runs": parent,
+        "build_on_ms": med(on), "build_on_runs": on,
+        "median7_ms": round(median7_ms, 4),
+        "step_ms": round(step_ms, 3), "step_ms_runs": [round(v, 3) for v in steps],
+        "stage_ms": round(med(on) - med(off), 4),
+        "stage_pct_of_step": round(100.0 * (med(on) - med(off)) / step_ms, 2),
+        "median7_pct_of_step": round(100.0 * median7_ms / step_ms, 2),
+        "device": torch.cuda.get_device_name(0),
+    }
+    return report
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=128)
+    ap.add_argument("--frames", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--photometric", action="store_true")
+    ap.add_argument("--parent-root", default=None)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--build-only", action="store_true")
+    ap.add_argument("--stage-on", action="store_true")
+    ap.add_argument("--root", default=ROOT)
+    args = ap.parse_args()
+    if args.build_only:
+        return build_only(args)
+    if args.photometric:
+        return emit(photometric(args), args)
+    sys.path.insert(0, ROOT)
+    from feartracker_amd.train_data import FRAME_DTYPE, TrainPairBuilder
+    from feartracker_amd.train_head import load_train_library
+    from feartracker_amd.train_net import FEARNetTrainHIP, random_init_state
+
+    dev = torch.device("cuda", 0)
+    B, F = args.pairs, args.frames
+    frames, pairs = _inputs(B, F, dev)
     shapes = [tuple(f.shape) for f in frames]
     builder = TrainPairBuilder(device=0, seed=0)
 
@@ -126,6 +250,10 @@ def main():
         "losses_finite": bool(np.all(np.isfinite(loss))),
         "device": torch.cuda.get_device_name(0),
     }
+    emit(report, args)
+
+
+def emit(report, args):
     line = json.dumps(report)
     print(line)
     if args.out:
