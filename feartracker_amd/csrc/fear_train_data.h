@@ -498,6 +498,20 @@ __global__ __launch_bounds__(256) void photometric_kernel(PhotoArgs a) {
     }
 }
 
+// ---- colour stage, the members that are no lookup table ------------------------------------------------------------------------------
+// fear_colour_u8: Equalize, HueSaturationValue, ColorJitter and Emboss on uint8 HWC crops (fear_train_colour.h holds the body).  One
+// workgroup of 1024 lanes per crop, 3.8 KB of LDS; no global atomics.
+#include "fear_train_colour.h"
+
+constexpr int kColourThreads = 1024;
+
+__global__ __launch_bounds__(kColourThreads) void colour_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int H, int W,
+                                                                const ColourOp* __restrict__ ops, const uint8_t* __restrict__ aux) {
+    __shared__ ColourShared sh;
+    const long crop = blockIdx.x, bytes = (long)H * W * 3;
+    colour_crop(in + crop * bytes, out + crop * bytes, H, W, ops + crop, aux + crop * 768, sh, (int)threadIdx.x, kColourThreads);
+}
+
 // fear_normalize_u8's constants
 template <typename Args>
 void set_normalisation(Args& a) {
@@ -578,6 +592,21 @@ int fear_photometric_u8(const uint8_t* crops_u8, int n, int H, int W, const Fear
     a.H = H; a.W = W;
     set_normalisation(a);
     hipLaunchKernelGGL(photometric_kernel, dim3(gx, gy, (unsigned)n), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    LAUNCH_CHECK();
+    return FEAR_TRAIN_OK;
+}
+
+int fear_colour_u8(const uint8_t* crops_in, int n, int H, int W, const FearColourOp* ops, const uint8_t* aux_lut, uint8_t* crops_out,
+                   void* stream) {
+    static_assert(sizeof(FearColourOp) == sizeof(ColourOp) && offsetof(FearColourOp, order) == offsetof(ColourOp, order) &&
+                  offsetof(FearColourOp, contrast) == offsetof(ColourOp, contrast) && offsetof(FearColourOp, alpha) == offsetof(ColourOp, alpha) &&
+                  offsetof(FearColourOp, taps) == offsetof(ColourOp, taps), "FearColourOp and ColourOp must share one layout");
+    if (n < 0 || n > 65535 || H < 4 || W < 4 || (H & 1) || (W & 1) || (long)H * W > 0x7fffffffL / 3) return FEAR_TRAIN_ERR_SHAPE;
+    if (n == 0) return FEAR_TRAIN_OK;
+    if (!crops_in || !ops || !aux_lut || !crops_out) return FEAR_TRAIN_ERR_NULL;
+    if (crops_in == crops_out) return FEAR_TRAIN_ERR_SHAPE;                          // Emboss reads its neighbours: not in place
+    hipLaunchKernelGGL(colour_kernel, dim3((unsigned)n), dim3(kColourThreads), 0, static_cast<hipStream_t>(stream), crops_in, crops_out,
+                       H, W, reinterpret_cast<const ColourOp*>(ops), aux_lut);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }

@@ -81,6 +81,8 @@ TRAIN_SYMBOLS = {
     # the photometric stage behind the pairs (FearPhotoOp below)
     "fear_train_pairs_u8": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _P, _P], _i),
     "fear_photometric_u8": ([_P, _i, _i, _i, _P, _P, _P, _P, _P], _i),
+    # the colour stage's members that are no lookup table (FearColourOp below)
+    "fear_colour_u8": ([_P, _i, _i, _i, _P, _P, _P, _P], _i),
     # step metrics (metrics.TrainMetrics)
     "fear_train_metrics": ([_P, _P, _P, _P, _P, _i, _i, _P, _P, _P, _P], _i),
 }
@@ -131,6 +133,15 @@ class FearPhotoOp(ctypes.Structure):
 
 
 assert ctypes.sizeof(FearPhotoOp) == 32
+
+
+class FearColourOp(ctypes.Structure):
+    """include/fear_train.h: one crop's colour record (train_data.COLOUR_DTYPE is its numpy form)."""
+    _fields_ = [("kind", ctypes.c_int32), ("order", ctypes.c_uint8 * 4), ("contrast", _d), ("alpha", _f), ("beta", _f),
+                ("taps", _f * 9), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(FearColourOp) == 64 and FearColourOp.contrast.offset == 8 and FearColourOp.taps.offset == 24
 
 _ALLREDUCE_FN =ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p)
 FEAR_SYNC_BUF_BYTES = 16384

@@ -8,7 +8,9 @@
             shift 48): a jittered square of the 512 crop warped to 256 x 256 by `cv2.warpAffine` (tracking_dataset.py:107-137,
             aug.py:52-143); the box follows through `apply_to_bbox`, `ensure_bbox_boundaries`, `handle_empty_bbox`
 * colour    `OneOf([ToGray, ToSepia], p=0.05)` and, at p = 0.5, one of RandomBrightnessContrast / RandomGamma / RGBShift — drawn once
-            per pair and applied to both crops (siam_dataset.py:64-67; the subset is DESIGN.md section 11's)
+            per pair and applied to both crops (siam_dataset.py:64-67; the subset is DESIGN.md section 11's).  `colour_members`
+            widens the group to RandomToneCurve (one more lookup table), Equalize, HueSaturationValue, ColorJitter and Emboss, which
+            the device's `fear_colour_u8` applies per crop behind the tables; `colour_u8_host` restates it
 * photometric  (`photometric=True`, off by default) `PHOTOMETRIC_AUGMENTATIONS` on each crop on its own, between the colour stage and
             the normalisation: a blur group, a noise group and Downscale(0.5), each at p = 0.2 (aug.py:8-25, tracking_dataset.py:
             158-175; the members built are DESIGN.md section 11's); `photometric_host` restates the device's `fear_photometric_u8`
@@ -48,7 +50,10 @@ DEFAULT_TRAIN_DATA_CONFIG: Dict[str, Any] = dict(
     search_image_shift=48,
     r_pos=2,
     tone_p=0.05,                 # OneOf([ToGray, ToSepia])
-    colour_p=0.5,                # OneOf([RandomBrightnessContrast, RandomGamma, RGBShift])
+    colour_p=0.5,                # OneOf([RandomBrightnessContrast, RandomGamma, RGBShift]), or the members named below
+    # the members of the colour OneOf, a subset of COLOUR_MEMBERS in its order; "all" = every one of COLOUR_MEMBERS (8 of the
+    # reference's 9: CLAHE is not built)
+    colour_members=("brightness_contrast", "gamma", "rgb_shift"),
     brightness_limit=0.2, contrast_limit=0.2, gamma_limit=(0.8, 1.2), rgb_shift_limit=20.0,
     # PHOTOMETRIC_AUGMENTATIONS (dataset/aug.py:8-25), per crop, off unless asked for
     photometric=False,
@@ -60,6 +65,12 @@ DEFAULT_TRAIN_DATA_CONFIG: Dict[str, Any] = dict(
 
 TONE_NONE, TONE_GRAY, TONE_SEPIA = 0, 1, 2
 COLOUR_NONE, COLOUR_BRIGHTNESS_CONTRAST, COLOUR_GAMMA, COLOUR_RGB_SHIFT = 0, 1, 2, 3
+COLOUR_TONE_CURVE, COLOUR_EQUALIZE, COLOUR_HSV, COLOUR_JITTER, COLOUR_EMBOSS = 4, 5, 6, 7, 8
+COLOUR_MEMBERS = {"brightness_contrast": COLOUR_BRIGHTNESS_CONTRAST, "gamma": COLOUR_GAMMA, "rgb_shift": COLOUR_RGB_SHIFT,
+                  "tone_curve": COLOUR_TONE_CURVE, "equalize": COLOUR_EQUALIZE, "hsv": COLOUR_HSV, "colour_jitter": COLOUR_JITTER,
+                  "emboss": COLOUR_EMBOSS}                                      # (in the order `colour_members` keeps)
+DEVICE_COLOUR_KINDS = (COLOUR_EQUALIZE, COLOUR_HSV, COLOUR_JITTER, COLOUR_EMBOSS)   # fear_colour_u8's; the others are lookup tables
+JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE = 0, 1, 2, 3       # ColorJitter's operations, as `order` names them
 
 BLUR_NONE, BLUR_BOX, BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_MOTION = 0, 1, 2, 3, 4
 NOISE_NONE, NOISE_MULTIPLICATIVE, NOISE_GAUSS = 0, 1, 2
@@ -80,6 +91,9 @@ FRAME_DTYPE = np.dtype([("data", "<u8"), ("h", "<i4"), ("w", "<i4")])        # f
 PHOTO_DTYPE = np.dtype([("blur", "<i4"), ("ksize", "<i4"), ("noise", "<i4"), ("scale", "<f4"), ("key", "<u4", 2),
                         ("downscale", "<i4"), ("tap_row", "<i4")])             # FearPhotoOp
 assert PHOTO_DTYPE.itemsize == 32
+COLOUR_DTYPE = np.dtype([("kind", "<i4"), ("order", "u1", 4), ("contrast", "<f8"), ("alpha", "<f4"), ("beta", "<f4"),
+                         ("taps", "<f4", 9), ("reserved", "<i4")])             # FearColourOp
+assert COLOUR_DTYPE.itemsize == 64
 
 
 @dataclass
@@ -111,6 +125,12 @@ class TrainPairParams:
     shift: np.ndarray            # (B, 3) RGB shift
     frame_shapes: Tuple[Tuple[int, int], ...]
     photo: Optional[PhotoParams] = None      # the photometric draws, None with the stage off
+    # the values of the members `colour_members` adds, each None unless its member is configured
+    tone_curve: Optional[np.ndarray] = None      # (B, 2) low_y, high_y
+    hsv: Optional[np.ndarray] = None             # (B, 3) hue, saturation and value shifts
+    colour_jitter: Optional[np.ndarray] = None   # (B, 4) ColorJitter's brightness, contrast, saturation factors and hue shift
+    colour_jitter_order: Optional[np.ndarray] = None   # (B, 4) int32, a permutation of JITTER_* per pair
+    emboss: Optional[np.ndarray] = None          # (B, 2) alpha, strength
 
 
 def _pairs_array(pairs) -> np.ndarray:
@@ -284,7 +304,8 @@ def colour_luts(params: TrainPairParams) -> np.ndarray:
     brightness / contrast  trunc(clip(fp32(v) * fp32(alpha) + fp32(beta * 255), 0, 255))
     gamma                  trunc((v / 255) ** gamma * 255), float64
     RGB shift              trunc(clip(fp32(v) + fp32(shift_c), 0, 255))
-    and the identity where no member was drawn."""
+    tone curve             rint(bezier(v / 255) * 255), float64 (`tone_curve_lut`), the same table for the three channels
+    and the identity where no member was drawn or the drawn one is fear_colour_u8's."""
     B = len(params.colour)
     v32 = np.arange(256, dtype=np.float32)
     lut = np.broadcast_to(np.arange(256, dtype=np.uint8), (B, 3, 256)).copy()
@@ -302,7 +323,205 @@ def colour_luts(params: TrainPairParams) -> np.ndarray:
     if sel.any():
         t = v32[None, None, :] + params.shift[sel].astype(np.float32)[:, :, None]
         lut[sel] = np.clip(t, 0, 255).astype(np.uint8)
+    for k in np.flatnonzero(kind == COLOUR_TONE_CURVE):
+        lut[k] = tone_curve_lut(*_member_values(params, "tone_curve")[k])[None, :]
     return lut
+
+
+def _member_values(params: TrainPairParams, name: str) -> np.ndarray:
+    v = getattr(params, name)
+    if v is None:
+        raise ValueError(f"a pair drew a colour member whose values ({name}) the params do not carry (drawn without it in colour_members?)")
+    return v
+
+
+def tone_curve_lut(low_y: float, high_y: float) -> np.ndarray:
+    """RandomToneCurve's table: the cubic Bezier through (0, 0), (0.25, low_y), (0.75, high_y), (1, 1) evaluated at t = v / 255 in
+    float64, rint(... * 255) as uint8 (256,)."""
+    t = np.linspace(0.0, 1.0, 256)
+    curve = 3 * (1 - t) ** 2 * t * low_y + 3 * (1 - t) * t ** 2 * high_y + t ** 3
+    return np.rint(curve * 255).astype(np.uint8)
+
+
+# cv2's 8-bit RGB -> HSV division tables (hsv_shift 12): rint((255 << 12) / i) and rint((180 << 12) / (6 i)), entry 0 = 0
+_SDIV = np.concatenate([[0], np.rint(1044480 / np.arange(1, 256))]).astype(np.int64)
+_HDIV = np.concatenate([[0], np.rint(737280 / (6 * np.arange(1, 256)))]).astype(np.int64)
+# HSV -> RGB: which of (v, v (1 - s), v (1 - s f), v (1 - s (1 - f))) is b, g, r in each sector
+_SECTOR_BGR = np.array([[1, 3, 0], [1, 0, 2], [3, 0, 1], [0, 2, 1], [0, 1, 3], [2, 1, 0]])
+
+
+def _gray_u8(rgb: np.ndarray) -> np.ndarray:
+    """cv2 COLOR_RGB2GRAY on uint8 (..., 3): 14-bit fixed point, int64 (...)."""
+    v = rgb.astype(np.int64)
+    return (4899 * v[..., 0] + 9617 * v[..., 1] + 1868 * v[..., 2] + 8192) >> 14
+
+
+def _round_u8(x: np.ndarray) -> np.ndarray:
+    return np.clip(np.rint(x), 0, 255).astype(np.uint8)
+
+
+def rgb_to_hsv_u8(rgb: np.ndarray) -> np.ndarray:
+    """cv2.cvtColor(COLOR_RGB2HSV) on uint8 (..., 3), H in [0, 180): v = max, s = (d sdiv[v] + 2048) >> 12, h from the channel that is
+    the maximum (r first, then g), (h' hdiv[d] + 2048) >> 12, + 180 when negative."""
+    c = rgb.astype(np.int64)
+    r, g, b = c[..., 0], c[..., 1], c[..., 2]
+    v = np.maximum(np.maximum(r, g), b)
+    d = v - np.minimum(np.minimum(r, g), b)
+    s = (d * _SDIV[v] + 2048) >> 12
+    hp = np.where(v == r, g - b, np.where(v == g, b - r + 2 * d, r - g + 4 * d))
+    h = (hp * _HDIV[d] + 2048) >> 12
+    h = h + np.where(h < 0, 180, 0)
+    return np.stack([h, s, v], axis=-1).astype(np.uint8)
+
+
+def hsv_to_rgb_u8(hsv: np.ndarray) -> np.ndarray:
+    """cv2.cvtColor(COLOR_HSV2RGB) on uint8 (..., 3) with H in [0, 180): through fp32, every product and sum rounded on its own;
+    a sector outside 0..5 becomes 0 with f = 0; s == 0 is gray."""
+    one = np.float32(1.0)
+    hf = hsv[..., 0].astype(np.float32) * np.float32(6.0 / 180.0)
+    sf = hsv[..., 1].astype(np.float32) * np.float32(1.0 / 255.0)
+    vf = hsv[..., 2].astype(np.float32) * np.float32(1.0 / 255.0)
+    sector = np.floor(hf)
+    f = hf - sector
+    outside = (sector < 0) | (sector > 5)
+    f = np.where(outside, np.float32(0.0), f)
+    k = np.where(outside, 0, sector).astype(np.int64)
+    tab = np.stack([vf, vf * (one - sf), vf * (one - sf * f), vf * (one - sf * (one - f))], axis=-1)
+    bgr = np.take_along_axis(tab, _SECTOR_BGR[k], axis=-1)
+    rgb = np.where((hsv[..., 1] == 0)[..., None], vf[..., None], bgr[..., ::-1])
+    assert rgb.dtype == np.float32
+    return _round_u8(rgb * np.float32(255.0))
+
+
+def equalize_u8(img: np.ndarray) -> np.ndarray:
+    """cv2.equalizeHist on each channel of a uint8 (H, W, C) crop: i0 the first non-empty bin; a channel of one value keeps it;
+    otherwise lut[i] = saturate(rint(fp32(sum of hist(i0, i]) * (fp32(255) / fp32(H W - hist[i0]))))."""
+    out = np.empty_like(img)
+    total = img.shape[0] * img.shape[1]
+    for c in range(img.shape[2]):
+        hist = np.bincount(img[..., c].reshape(-1), minlength=256)
+        i0 = int(np.flatnonzero(hist)[0])
+        if hist[i0] == total:
+            out[..., c] = img[..., c]
+            continue
+        scale = np.float32(255.0) / np.float32(total - hist[i0])
+        sums = np.cumsum(np.where(np.arange(256) > i0, hist, 0))
+        lut = _round_u8(sums.astype(np.float32) * scale)
+        out[..., c] = lut[img[..., c]]
+    return out
+
+
+def jitter_brightness_lut(factor: float) -> np.ndarray:
+    return np.clip(np.arange(256, dtype=np.float64) * float(factor), 0, 255).astype(np.uint8)
+
+
+def jitter_hue_lut(hue: float) -> np.ndarray:
+    return np.mod(np.arange(256, dtype=np.float64) + 180.0 * float(hue), 180.0).astype(np.uint8)
+
+
+def jitter_brightness_u8(img: np.ndarray, factor: float) -> np.ndarray:
+    """ColorJitter's brightness on uint8: trunc(clip(v * factor, 0, 255)), float64."""
+    return jitter_brightness_lut(factor)[img]
+
+
+def jitter_contrast_u8(img: np.ndarray, factor: float) -> np.ndarray:
+    """ColorJitter's contrast on a uint8 (H, W, 3) crop: trunc(clip(v * factor + mean * (1 - factor), 0, 255)) in float64, mean = the
+    crop's gray plane's (an exact integer sum over H W)."""
+    factor = float(factor)
+    mean = float(int(_gray_u8(img).sum())) / float(img.shape[0] * img.shape[1])
+    lut = np.clip(np.arange(256, dtype=np.float64) * factor + mean * (1.0 - factor), 0, 255).astype(np.uint8)
+    return lut[img]
+
+
+def jitter_saturation_u8(img: np.ndarray, alpha, beta) -> np.ndarray:
+    """ColorJitter's saturation on uint8 (..., 3): rint(fp32(c) * alpha + fp32(gray) * beta), alpha = fp32(factor), beta = fp32(1 -
+    factor), the products and the sum rounded on their own."""
+    g = _gray_u8(img).astype(np.float32) * np.float32(beta)
+    return _round_u8(img.astype(np.float32) * np.float32(alpha) + g[..., None])
+
+
+def jitter_hue_u8(img: np.ndarray, lh: np.ndarray) -> np.ndarray:
+    """ColorJitter's hue on uint8 (..., 3): RGB -> HSV, the table `lh` on H, HSV -> RGB."""
+    hsv = rgb_to_hsv_u8(img)
+    hsv[..., 0] = lh[hsv[..., 0]]
+    return hsv_to_rgb_u8(hsv)
+
+
+def emboss_taps(alpha: float, strength: float) -> np.ndarray:
+    """Emboss's kernel (1 - alpha) [centre] + alpha [[-1 - s, -s, 0], [-s, 1, s], [0, s, 1 + s]] in float64, as nine fp32 taps."""
+    a, s = float(alpha), float(strength)
+    nochange = np.array([[0, 0, 0], [0, 1, 0], [0, 0, 0]], dtype=np.float64)
+    effect = np.array([[-1 - s, -s, 0], [-s, 1, s], [0, s, 1 + s]], dtype=np.float64)
+    return ((1 - a) * nochange + a * effect).astype(np.float32).reshape(9)
+
+
+def emboss_u8(img: np.ndarray, taps: np.ndarray) -> np.ndarray:
+    """cv2.filter2D(img, -1, taps) on a uint8 (H, W, 3) crop as MotionBlur's is defined: correlation, BORDER_REFLECT_101, the non-zero
+    taps in row-major order accumulated in fp32, rint half to even, saturate."""
+    win = _windows(img, 1, "reflect")
+    acc = np.zeros(img.shape, dtype=np.float32)
+    for t, wt in enumerate(np.asarray(taps, dtype=np.float32).reshape(9)):
+        if wt != 0:
+            acc = acc + wt * win[..., t // 3, t % 3].astype(np.float32)
+    return _round_u8(acc)
+
+
+def colour_tables(params: TrainPairParams) -> Tuple[np.ndarray, np.ndarray]:
+    """FearColourOp records (B,) and the tables `aux_lut` (B, 3, 256) uint8 of the pairs that drew one of fear_colour_u8's members
+    (kind 0 and zeros for the others).  HueSaturationValue: lh = trunc(mod(i + hue, 180)), ls = trunc(clip(i + sat, 0, 255)), lv the same
+    with val.  ColorJitter: row 0 the brightness table, row 1 lh = trunc(mod(i + 180 hue, 180))."""
+    kind = np.asarray(params.colour)
+    B = len(kind)
+    ops = np.zeros(B, dtype=COLOUR_DTYPE)
+    aux = np.zeros((B, 3, 256), dtype=np.uint8)
+    ramp = np.arange(256, dtype=np.float64)
+    ops["kind"] = np.where(np.isin(kind, DEVICE_COLOUR_KINDS), kind, 0)
+    for k in np.flatnonzero(kind == COLOUR_HSV):
+        hue, sat, val = (float(v) for v in _member_values(params, "hsv")[k])
+        aux[k, 0] = np.mod(ramp + hue, 180.0).astype(np.uint8)
+        aux[k, 1] = np.clip(ramp + sat, 0, 255).astype(np.uint8)
+        aux[k, 2] = np.clip(ramp + val, 0, 255).astype(np.uint8)
+    for k in np.flatnonzero(kind == COLOUR_JITTER):
+        brightness, contrast, saturation, hue = (float(v) for v in _member_values(params, "colour_jitter")[k])
+        ops["order"][k] = _member_values(params, "colour_jitter_order")[k]
+        ops["contrast"][k] = contrast
+        ops["alpha"][k], ops["beta"][k] = np.float32(saturation), np.float32(1.0 - saturation)
+        aux[k, 0], aux[k, 1] = jitter_brightness_lut(brightness), jitter_hue_lut(hue)
+    for k in np.flatnonzero(kind == COLOUR_EMBOSS):
+        ops["taps"][k] = emboss_taps(*_member_values(params, "emboss")[k])
+    return ops, aux
+
+
+def colour_u8_host(crop_u8: np.ndarray, op, aux: np.ndarray) -> np.ndarray:
+    """fear_colour_u8's result for one (H, W, 3) uint8 crop, its FearColourOp record `op` (a COLOUR_DTYPE scalar) and its tables `aux`
+    (3, 256).  A record the device copies the crop for (an unknown kind, a ColorJitter order that is no permutation) copies it here."""
+    v = np.ascontiguousarray(crop_u8)
+    H, W = v.shape[:2]
+    if H < 4 or W < 4 or H % 2 or W % 2:
+        raise ValueError("the colour stage takes even sides of at least 4")
+    kind = int(op["kind"])
+    if kind == COLOUR_EQUALIZE:
+        return equalize_u8(v)
+    if kind == COLOUR_HSV:
+        hsv = rgb_to_hsv_u8(v)
+        return hsv_to_rgb_u8(np.stack([aux[c][hsv[..., c]] for c in range(3)], axis=-1))
+    if kind == COLOUR_JITTER:
+        order = [int(o) for o in op["order"]]
+        if sorted(order) != [0, 1, 2, 3]:
+            return v.copy()
+        for o in order:
+            if o == JITTER_BRIGHTNESS:
+                v = aux[0][v]
+            elif o == JITTER_CONTRAST:
+                v = jitter_contrast_u8(v, float(op["contrast"]))
+            elif o == JITTER_SATURATION:
+                v = jitter_saturation_u8(v, op["alpha"], op["beta"])
+            else:
+                v = jitter_hue_u8(v, aux[1])
+        return np.ascontiguousarray(v)
+    if kind == COLOUR_EMBOSS:
+        return emboss_u8(v, op["taps"])
+    return v.copy()
 
 
 def apply_tone(rgb: np.ndarray, tone: int) -> np.ndarray:
@@ -330,12 +549,17 @@ def _colour_u8(rgb: np.ndarray, tone: int, lut: np.ndarray) -> np.ndarray:
     return np.stack([lut[c][v[..., c]] for c in range(3)], axis=-1)
 
 
-def _colour_normalise(rgb: np.ndarray, tone: int, lut: np.ndarray) -> np.ndarray:
-    """(H, W, 3) uint8 -> tone -> lut -> normalised fp32 (3, H, W)."""
-    v = _colour_u8(rgb, tone, lut).astype(np.float32)
+def _normalise_u8(rgb: np.ndarray) -> np.ndarray:
+    """(H, W, 3) uint8 -> normalised fp32 (3, H, W)."""
+    v = rgb.astype(np.float32)
     v -= _MEAN
     v *= _INV_STD
     return np.ascontiguousarray(v.transpose(2, 0, 1))
+
+
+def _colour_normalise(rgb: np.ndarray, tone: int, lut: np.ndarray) -> np.ndarray:
+    """(H, W, 3) uint8 -> tone -> lut -> normalised fp32 (3, H, W)."""
+    return _normalise_u8(_colour_u8(rgb, tone, lut))
 
 
 # ------------------------------------------------------------------------------------------------------------------- photometric
@@ -517,10 +741,26 @@ class TrainPairBuilder:
             if unknown:
                 raise KeyError(f"unknown train-data config keys {sorted(unknown)}")
             self.config.update(config)
+        self.colour_members = self._members(self.config["colour_members"])
+        self._device_colour = any(COLOUR_MEMBERS[m] in DEVICE_COLOUR_KINDS for m in self.colour_members)
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.generator = np.random.default_rng(seed)
         self._lib = None
         self._qtable = None
+
+    @staticmethod
+    def _members(value) -> Tuple[str, ...]:
+        """`colour_members` as a tuple of names in COLOUR_MEMBERS' order: "all", or any non-empty subset (KeyError for a name that is
+        no member)."""
+        if isinstance(value, str):
+            value = tuple(COLOUR_MEMBERS) if value == "all" else (value,)
+        names = tuple(value)
+        unknown = [m for m in names if m not in COLOUR_MEMBERS]
+        if unknown:
+            raise KeyError(f"unknown colour members {unknown}: the members are {list(COLOUR_MEMBERS)}")
+        if not names or len(set(names)) != len(names):
+            raise ValueError("colour_members must name at least one member, each once")
+        return tuple(m for m in COLOUR_MEMBERS if m in names)
 
     # ------------------------------------------------------------------ draws
     def draw(self, pairs, frame_shapes: Sequence[Tuple[int, ...]], generator: Optional[np.random.Generator] = None) -> TrainPairParams:
@@ -537,14 +777,41 @@ class TrainPairBuilder:
         sc, sh = float(cfg["search_image_scale"]), float(cfg["search_image_shift"])
         jitter = np.concatenate([rng.uniform(-sc, sc, size=(B, 2)), rng.uniform(-sh, sh, size=(B, 2))], axis=1)
         tone = np.where(rng.random(B) < cfg["tone_p"], 1 + rng.integers(0, 2, size=B), TONE_NONE).astype(np.int32)
-        colour = np.where(rng.random(B) < cfg["colour_p"], 1 + rng.integers(0, 3, size=B), COLOUR_NONE).astype(np.int32)
+        kinds = np.array([COLOUR_MEMBERS[m] for m in self.colour_members])
+        colour = np.where(rng.random(B) < cfg["colour_p"], kinds[rng.integers(0, len(kinds), size=B)], COLOUR_NONE).astype(np.int32)
         alpha = 1.0 + rng.uniform(-cfg["contrast_limit"], cfg["contrast_limit"], size=B)
         beta = rng.uniform(-cfg["brightness_limit"], cfg["brightness_limit"], size=B)
         gamma = rng.uniform(cfg["gamma_limit"][0], cfg["gamma_limit"][1], size=B)
         shift = rng.uniform(-cfg["rgb_shift_limit"], cfg["rgb_shift_limit"], size=(B, 3))
         shapes = tuple((int(s[0]), int(s[1])) for s in frame_shapes)
         photo = self._draw_photo(B, rng) if cfg["photometric"] else None       # after every other draw: off consumes nothing
-        return TrainPairParams(context, jitter, tone, colour, alpha, beta, gamma, shift, shapes, photo)
+        # the members colour_members adds, after every other draw: the default members consume nothing more
+        return TrainPairParams(context, jitter, tone, colour, alpha, beta, gamma, shift, shapes, photo, **self._draw_colour(B, rng))
+
+    def _draw_colour(self, B: int, rng: np.random.Generator) -> Dict[str, np.ndarray]:
+        """The values of the configured members beyond the first three (aug.py:35-48), every one for every pair: RandomToneCurve's
+        two control heights, HueSaturationValue's three shifts, ColorJitter's three factors, hue shift and the order of its four
+        operations (a uniformly random permutation), Emboss's alpha and strength.  Equalize has none."""
+        out: Dict[str, np.ndarray] = {}
+        if "tone_curve" in self.colour_members:
+            out["tone_curve"] = np.stack([rng.uniform(0.15, 0.35, size=B), rng.uniform(0.65, 0.85, size=B)], axis=1)
+        if "hsv" in self.colour_members:
+            out["hsv"] = np.stack([rng.uniform(-20, 20, size=B), rng.uniform(-30, 30, size=B), rng.uniform(-20, 20, size=B)], axis=1)
+        if "colour_jitter" in self.colour_members:
+            out["colour_jitter"] = np.concatenate([rng.uniform(0.8, 1.2, size=(B, 3)), rng.uniform(-0.2, 0.2, size=(B, 1))], axis=1)
+            out["colour_jitter_order"] = rng.permuted(np.tile(np.arange(4, dtype=np.int32), (B, 1)), axis=1)
+        if "emboss" in self.colour_members:
+            out["emboss"] = np.stack([rng.uniform(0.2, 0.5, size=B), rng.uniform(0.2, 0.7, size=B)], axis=1)
+        return out
+
+    def _colour_ops(self, params: TrainPairParams):
+        """The batch's FearColourOp records and tables when a member of fear_colour_u8's is configured, None otherwise."""
+        drawn = np.isin(np.asarray(params.colour), DEVICE_COLOUR_KINDS)
+        if not self._device_colour:
+            if drawn.any():
+                raise ValueError("a pair drew a member of fear_colour_u8's, but colour_members configures none of them")
+            return None
+        return colour_tables(params)
 
     def _draw_photo(self, B: int, rng: np.random.Generator) -> PhotoParams:
         """The photometric draws, (B, 2): each group at its p, uniform over its members (aug.py:8-25); ksize uniform over the odd
@@ -628,11 +895,15 @@ class TrainPairBuilder:
         if photo is not None:
             ops, taps = photo_tables(photo)
             q = normal_quantiles()
+        colour = self._colour_ops(params)
 
         def finish(crop, k, which):          # colour stage -> (photometric stage) -> normalised fp32
+            v = _colour_u8(crop, int(geom["tone"][k]), lut[k])
+            if colour is not None:
+                v = colour_u8_host(v, colour[0][k], colour[1][k])
             if photo is None:
-                return _colour_normalise(crop, int(geom["tone"][k]), lut[k])
-            return photometric_host(_colour_u8(crop, int(geom["tone"][k]), lut[k]), ops[k, which], taps, q)
+                return _normalise_u8(v)
+            return photometric_host(v, ops[k, which], taps, q)
 
         def frame_of(i):
             if 0 <= i < len(host):
@@ -670,18 +941,25 @@ class TrainPairBuilder:
         geom, lut = tab["geom"], tab["lut"]
         B, F = len(geom), len(frames)
         photo = self._photo(params, B)
+        colour = self._colour_ops(params)
         if photo is not None:
             ops, taps = photo_tables(photo)
+        elif colour is not None:               # the crops still leave through fear_photometric_u8: all-"none" records, the normalisation
+            ops, taps = np.zeros((B, 2), dtype=PHOTO_DTYPE), np.zeros((0, 49), dtype=np.float32)
+        staged_u8 = photo is not None or colour is not None
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
             dframes = [self._frame_on_device(f) for f in frames]
-            # one staging buffer, one transfer: frame table | geometry | lookup tables | search_bbox | photometric records | taps
+            # one staging buffer, one transfer: frame table | geometry | lookup tables | search_bbox | photometric records | taps |
+            # colour records (8-byte aligned: they hold a double) | colour tables
             o_geom = 16 * F
             o_lut = o_geom + 96 * B
             o_box = o_lut + 768 * B
             o_ops = o_box + 16 * B
-            o_taps = o_ops + (64 * B if photo is not None else 0)
-            total = o_taps + (taps.size * 4 if photo is not None else 0)
+            o_taps = o_ops + (64 * B if staged_u8 else 0)
+            o_cops = (o_taps + (taps.size * 4 if staged_u8 else 0) + 7) // 8 * 8
+            o_aux = o_cops + (64 * B if colour is not None else 0)
+            total = o_aux + (768 * B if colour is not None else 0)
             pinned = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True)
             hv = pinned.numpy()
             ftab = np.zeros(F, dtype=FRAME_DTYPE)
@@ -691,9 +969,12 @@ class TrainPairBuilder:
             hv[o_geom:o_lut] = geom.view(np.uint8)
             hv[o_lut:o_box] = lut.reshape(-1)
             hv[o_box:o_ops] = tab["search_bbox"].astype(np.int32).view(np.uint8).reshape(-1)
-            if photo is not None:              # templates' records first, then the searches': one call each
+            if staged_u8:                      # templates' records first, then the searches': one call each
                 hv[o_ops:o_taps] = np.ascontiguousarray(ops.T).view(np.uint8).reshape(-1)
-                hv[o_taps:total] = taps.view(np.uint8).reshape(-1)
+                hv[o_taps:o_taps + taps.size * 4] = taps.view(np.uint8).reshape(-1)
+            if colour is not None:             # one record per pair, shared by its two crops
+                hv[o_cops:o_aux] = colour[0].view(np.uint8)
+                hv[o_aux:total] = colour[1].reshape(-1)
             staged = pinned.to(dev, non_blocking=True)
             base = staged.data_ptr()
             border = torch.empty((max(F, 1), 3), dtype=torch.uint8, device=dev)
@@ -706,9 +987,9 @@ class TrainPairBuilder:
             rc = lib.fear_frame_border_u8(ctypes.c_void_p(base), F, ctypes.c_void_p(border.data_ptr()), st)
             if rc != 0:
                 raise RuntimeError(f"fear_frame_border_u8 failed with status {rc}")
-            if photo is None:
+            if not staged_u8:
                 pairs_fn, t_out, s_out = "fear_train_pairs", tmpl, srch
-            else:                              # the crops leave the colour stage as uint8 HWC and pass through the photometric stage
+            else:                              # the crops leave the table stage as uint8 HWC for fear_colour_u8 / fear_photometric_u8
                 pairs_fn = "fear_train_pairs_u8"
                 t_out = torch.empty((B, TEMPLATE_SIZE, TEMPLATE_SIZE, 3), dtype=torch.uint8, device=dev)
                 s_out = torch.empty((B, SEARCH_SIZE, SEARCH_SIZE, 3), dtype=torch.uint8, device=dev)
@@ -718,7 +999,15 @@ class TrainPairBuilder:
                                         ctypes.c_void_p(cls.data_ptr()), ctypes.c_void_p(wgt.data_ptr()), st)
             if rc != 0:
                 raise RuntimeError(f"{pairs_fn} failed with status {rc}")
-            if photo is not None:
+            if colour is not None:             # the members that are no table: once for the templates, once for the searches
+                t_in, s_in = t_out, s_out
+                t_out, s_out = torch.empty_like(t_in), torch.empty_like(s_in)
+                for crops, out, side in ((t_in, t_out, TEMPLATE_SIZE), (s_in, s_out, SEARCH_SIZE)):
+                    rc = lib.fear_colour_u8(ctypes.c_void_p(crops.data_ptr()), B, side, side, ctypes.c_void_p(base + o_cops),
+                                            ctypes.c_void_p(base + o_aux), ctypes.c_void_p(out.data_ptr()), st)
+                    if rc != 0:
+                        raise RuntimeError(f"fear_colour_u8 failed with status {rc}")
+            if staged_u8:
                 q = self._quantiles_on_device()
                 d_taps = ctypes.c_void_p(base + o_taps) if taps.size else None
                 for which, (crops, out, side) in enumerate(((t_out, tmpl, TEMPLATE_SIZE), (s_out, srch, SEARCH_SIZE))):

@@ -469,6 +469,47 @@ _Static_assert(sizeof(FearPhotoOp) == 32, "FearPhotoOp is 32 bytes");
 int fear_photometric_u8(const uint8_t* crops_u8, int n, int H, int W, const FearPhotoOp* ops, const float* taps, const float* qtable,
                         float* out_f32, void* stream);
 
+/* ---- the colour stage's members that are no lookup table: Equalize, HueSaturationValue, ColorJitter and Emboss of the reference's
+ * p = 0.5 OneOf (model_training/dataset/aug.py:35-48), on uint8 HWC crops between fear_train_pairs_u8 (tone, then the lookup-table
+ * members) and fear_photometric_u8 (DESIGN.md section 11 states every contract; train_data.colour_u8_host restates them in numpy and the
+ * two agree bit for bit).  Per crop, by the record's kind:
+ *   5 Equalize            cv2.equalizeHist per channel over the crop: i0 the first non-empty bin, lut[i] = saturate(rint(fp32(sum of
+ *                         hist(i0, i]) * (fp32(255) / fp32(H W - hist[i0])))), a channel with a single value keeps it
+ *   6 HueSaturationValue  RGB -> HSV (cv2's 8-bit path, H in [0, 180)), aux_lut rows lh | ls | lv, HSV -> RGB (cv2's fp32 path)
+ *   7 ColorJitter         `order` is a permutation of 0 brightness (aux_lut row 0), 1 contrast (trunc(clip(i contrast + mean (1 -
+ *                         contrast), 0, 255)) in float64, mean = that of the gray plane of the crop as the operations in front left
+ *                         it), 2 saturation (rint(fp32(c) alpha + fp32(gray) beta)), 3 hue (RGB -> HSV, aux_lut row 1 on H, HSV -> RGB);
+ *                         each operation works on the previous one's uint8 result
+ *   8 Emboss              cv2.filter2D with the nine `taps` (row-major 3 x 3): correlation, anchor at the centre, BORDER_REFLECT_101,
+ *                         the non-zero taps in row-major order, fp32 accumulation, rint half to even, saturated
+ * Any other kind, and a ColorJitter whose order is no permutation, copies the crop (the records live in device memory, where the call
+ * cannot read them).  Per-crop statistics are per crop: one workgroup per crop, integer sums in LDS, no global atomics.
+ * H and W must be even and >= 4, n <= 65535, crops_in != crops_out (Emboss reads neighbours): FEAR_TRAIN_ERR_SHAPE otherwise.  n == 0
+ * returns FEAR_TRAIN_OK without a launch.  A null crops_in, ops, aux_lut or crops_out returns FEAR_TRAIN_ERR_NULL.
+ *   crops_in, crops_out : (n, H, W, 3) uint8, device, distinct      ops : (n) FearColourOp, device      aux_lut : (n, 3, 256) uint8, device */
+#define FEAR_COLOUR_EQUALIZE 5
+#define FEAR_COLOUR_HSV 6
+#define FEAR_COLOUR_JITTER 7
+#define FEAR_COLOUR_EMBOSS 8
+
+/* One crop.  64 bytes. */
+typedef struct FearColourOp {
+    int32_t kind;               /* FEAR_COLOUR_*, anything else: copy                                                  */
+    uint8_t order[4];           /* ColorJitter: the operations in the order they run                                   */
+    double contrast;            /* ColorJitter: the contrast factor                                                    */
+    float alpha, beta;          /* ColorJitter: fp32(saturation), fp32(1 - saturation) (the difference in float64)     */
+    float taps[9];              /* Emboss: the 3 x 3 kernel, row-major                                                 */
+    int32_t reserved;
+} FearColourOp;
+#ifdef __cplusplus
+static_assert(sizeof(FearColourOp) == 64, "FearColourOp is 64 bytes");
+#else
+_Static_assert(sizeof(FearColourOp) == 64, "FearColourOp is 64 bytes");
+#endif
+
+int fear_colour_u8(const uint8_t* crops_in, int n, int H, int W, const FearColourOp* ops, const uint8_t* aux_lut, uint8_t* crops_out,
+                   void* stream);
+
 /* ---- step metrics: the training telemetry of the reference's `_training_step` (train/fear_lightning_model.py:66-87) on the device
  * (feartracker_amd/metrics.py).  Per pair: FEARBoxCoder.decode of the step's own output maps (fear_decode's
  * arithmetic: fp32 sigmoid, first maximum, float64 grid), box_convert(xywh -> xyxy) of the decoded and the ground-truth box, and

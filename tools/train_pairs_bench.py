@@ -17,10 +17,18 @@ With --photometric it reports the photometric stage instead (same pairs and fram
   median7_ms         fear_photometric_u8 alone on the batch's 128 templates and 128 searches (two calls), every crop forced to the
                      7 x 7 median, HIP events
   step_ms            FEARNetTrainHIP.step on fixed inputs, for the shares
+With --colour all it reports the colour members behind `colour_members` (same pairs and frames):
+  build_default_ms   `build` with the default members, one figure per fresh process; with --parent-root DIR against that checkout's
+                     `build` in alternating processes, as above: the same code path, so a difference beyond the spread is a finding
+  build_all_ms       `build` with colour_members="all" at the reference's probabilities, fresh draws per call
+  colour_u8_ms       fear_colour_u8 alone on the batch's 128 templates and 128 searches (two calls), every crop forced to one member,
+                     per member, HIP events; worst_member names the slowest
+  step_ms            FEARNetTrainHIP.step on fixed inputs, for the shares
 --build-only is the child mode of the above: it times `build` of the package under --root and prints {"build_ms": ...}.
 
 Usage: python tools/train_pairs_bench.py [--pairs 128] [--frames 256] [--steps 20] [--iters 50] [--out FILE]
        python tools/train_pairs_bench.py --photometric [--parent-root DIR] [--repeats 3] [--out FILE]
+       python tools/train_pairs_bench.py --colour all [--parent-root DIR] [--repeats 3] [--out profiles/train_pairs_colour_bench.json]
 """
 from __future__ import annotations
 
@@ -68,13 +76,16 @@ def build_only(args):
     sys.path.insert(0, os.path.abspath(args.root))
     from feartracker_amd.train_data import TrainPairBuilder
     frames, pairs = _inputs(args.pairs, args.frames, torch.device("cuda", 0))
-    builder = TrainPairBuilder(dict(photometric=True) if args.stage_on else None, device=0, seed=0)
+    config = dict(photometric=True) if args.stage_on else {}
+    if args.colour:                                    # (only ever passed for a tree that knows the key)
+        config["colour_members"] = args.colour
+    builder = TrainPairBuilder(config or None, device=0, seed=0)
     print(json.dumps({"build_ms": round(_time_build(builder, frames, pairs, args.iters), 4)}))
 
 
-def _child(root, args, stage_on=False):
+def _child(root, args, stage_on=False, colour=None):
     cmd = [sys.executable, os.path.abspath(__file__), "--build-only", "--root", root, "--pairs", str(args.pairs), "--frames",
-           str(args.frames), "--iters", str(args.iters)] + (["--stage-on"] if stage_on else [])
+           str(args.frames), "--iters", str(args.iters)] + (["--stage-on"] if stage_on else []) + (["--colour", colour] if colour else [])
     res = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300)
     return json.loads(res.stdout.strip().splitlines()[-1])["build_ms"]
 
@@ -148,6 +159,87 @@ def photometric(args):
     return report
 
 
+def _step_ms(args, frames, pairs):
+    """FEARNetTrainHIP.step on fixed inputs, wall time per step: (the smaller of two runs, both runs)."""
+    from feartracker_amd.train_data import TrainPairBuilder
+    from feartracker_amd.train_net import FEARNetTrainHIP, random_init_state
+    net = FEARNetTrainHIP(random_init_state(0), device=0)
+    fixed = [t.clone() for t in TrainPairBuilder(device=0, seed=0).build(frames, pairs)[:5]]
+    steps = []
+    for _ in range(2):
+        for _ in range(3):
+            net.step(*fixed)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            net.step(*fixed)
+        torch.cuda.synchronize()
+        steps.append(1e3 * (time.perf_counter() - t0) / args.steps)
+    return min(steps), steps
+
+
+def colour(args):
+    # the fresh processes first, one at a time, before this process opens the GPU
+    default, parent, wide = [], [], []
+    for _ in range(args.repeats):
+        default.append(_child(ROOT, args))
+        if args.parent_root:
+            parent.append(_child(args.parent_root, args))
+        wide.append(_child(ROOT, args, colour=args.colour))
+    sys.path.insert(0, ROOT)
+    from feartracker_amd.train_abi import load_train_library
+    from feartracker_amd.train_data import (COLOUR_EMBOSS, COLOUR_EQUALIZE, COLOUR_HSV, COLOUR_JITTER, TrainPairParams, colour_tables)
+    dev = torch.device("cuda", 0)
+    B = args.pairs
+    lib = load_train_library()
+    P = ctypes.c_void_p
+    st = P(torch.cuda.current_stream(dev).cuda_stream)
+    g = torch.Generator(device=dev).manual_seed(1)
+    crops = [torch.randint(0, 256, (B, s, s, 3), generator=g, device=dev, dtype=torch.uint8) for s in (128, 256)]
+    outs = [torch.empty_like(c) for c in crops]
+    rng = np.random.default_rng(2)
+    member_ms = {}
+    for name, kind in (("equalize", COLOUR_EQUALIZE), ("hsv", COLOUR_HSV), ("colour_jitter", COLOUR_JITTER), ("emboss", COLOUR_EMBOSS)):
+        params = TrainPairParams(context=np.zeros(B), jitter=np.zeros((B, 4)), tone=np.zeros(B, np.int32), colour=np.full(B, kind, np.int32),
+                                 alpha=np.ones(B), beta=np.zeros(B), gamma=np.ones(B), shift=np.zeros((B, 3)), frame_shapes=(),
+                                 hsv=rng.uniform(-20, 20, (B, 3)),
+                                 colour_jitter=np.concatenate([rng.uniform(0.8, 1.2, (B, 3)), rng.uniform(-0.2, 0.2, (B, 1))], axis=1),
+                                 colour_jitter_order=rng.permuted(np.tile(np.arange(4, dtype=np.int32), (B, 1)), axis=1),
+                                 emboss=np.stack([rng.uniform(0.2, 0.5, B), rng.uniform(0.2, 0.7, B)], axis=1))
+        ops, aux = colour_tables(params)
+        d_ops, d_aux = torch.from_numpy(ops.view(np.uint8).copy()).to(dev), torch.from_numpy(aux).to(dev)
+
+        def both():
+            for c, o, s in zip(crops, outs, (128, 256)):
+                assert lib.fear_colour_u8(P(c.data_ptr()), B, s, s, P(d_ops.data_ptr()), P(d_aux.data_ptr()), P(o.data_ptr()), st) == 0
+
+        for _ in range(5):
+            both()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.iters):
+            both()
+        e1.record()
+        torch.cuda.synchronize()
+        member_ms[name] = round(e0.elapsed_time(e1) / args.iters, 4)
+    frames, pairs = _inputs(B, args.frames, dev)
+    step_ms, steps = _step_ms(args, frames, pairs)
+    med = lambda v: round(float(np.median(v)), 4) if v else None
+    worst = max(member_ms, key=member_ms.get)
+    return {
+        "pairs": B, "frames": args.frames, "frame_hw": [1080, 1920], "iters": args.iters, "colour_members": args.colour,
+        "build_default_ms": med(default), "build_default_runs": default,
+        "parent_build_ms": med(parent), "parent_build_runs": parent,
+        "build_all_ms": med(wide), "build_all_runs": wide,
+        "colour_u8_ms": member_ms, "worst_member": worst,
+        "step_ms": round(step_ms, 3), "step_ms_runs": [round(v, 3) for v in steps],
+        "members_ms": round(med(wide) - med(default), 4),
+        "members_pct_of_step": round(100.0 * (med(wide) - med(default)) / step_ms, 2),
+        "worst_member_pct_of_step": round(100.0 * member_ms[worst] / step_ms, 2),
+        "device": torch.cuda.get_device_name(0),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=128)
@@ -156,6 +248,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--out", default=None)
     ap.add_argument("--photometric", action="store_true")
+    ap.add_argument("--colour", default=None, help='"all": report the members behind colour_members')
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--build-only", action="store_true")
@@ -166,6 +259,8 @@ def main():
         return build_only(args)
     if args.photometric:
         return emit(photometric(args), args)
+    if args.colour:
+        return emit(colour(args), args)
     sys.path.insert(0, ROOT)
     from feartracker_amd.train_data import FRAME_DTYPE, TrainPairBuilder
     from feartracker_amd.train_head import load_train_library
