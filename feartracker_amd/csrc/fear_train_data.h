@@ -311,12 +311,15 @@ struct PhotoOp {             // the layout of FearPhotoOp (include/fear_train.h)
     int32_t downscale, tap_row;
 };
 
+// Out = float: the crops leave normalised, fp32 NCHW (fear_photometric_u8).  Out = uint8_t: they leave as the chain made them, uint8
+// NHWC, for fear_jpeg_u8 behind (fear_photometric_stage_u8).
+template <typename Out>
 struct PhotoArgs {
     const uint8_t* in;       // [n][H][W][3]
     const PhotoOp* ops;      // [n]
     const float* taps;       // [m][49], may be null
     const float* q;          // [4096]
-    float* out;              // [n][3][H][W]
+    Out* out;                // float [n][3][H][W] | uint8 [n][H][W][3]
     int H, W;
     float mean[3], inv_std[3];
 };
@@ -417,7 +420,8 @@ __device__ __forceinline__ void philox3(uint32_t c0, uint32_t c1, uint32_t k0, u
     out[0] = c0; out[1] = c1; out[2] = c2;
 }
 
-__global__ __launch_bounds__(256) void photometric_kernel(PhotoArgs a) {
+template <typename Out>
+__global__ __launch_bounds__(256) void photometric_kernel(PhotoArgs<Out> a) {
     __shared__ __attribute__((aligned(16))) uint8_t tile[kPhBytes];
     const int crop = blockIdx.z, x0 = blockIdx.x * kPhTile, y0 = blockIdx.y * kPhTile;
     const int H = a.H, W = a.W, tid = threadIdx.x;
@@ -486,13 +490,19 @@ __global__ __launch_bounds__(256) void photometric_kernel(PhotoArgs a) {
                     v[c] = (int)fminf(fmaxf(f, 0.f), 255.f);
                 }
             }
-            float* o = a.out + (long)crop * 3 * H * W + (long)y * W + x;
+            if constexpr (sizeof(Out) == 1) {
+                Out* o = a.out + ((long)crop * H * W + (long)y * W + x) * 3;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float f = (float)v[c];
-                f = f - a.mean[c];
-                f = f * a.inv_std[c];
-                o[(long)c * H * W] = f;
+                for (int c = 0; c < 3; ++c) o[c] = (uint8_t)v[c];
+            } else {
+                Out* o = a.out + (long)crop * 3 * H * W + (long)y * W + x;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    float f = (float)v[c];
+                    f = f - a.mean[c];
+                    f = f * a.inv_std[c];
+                    o[(long)c * H * W] = f;
+                }
             }
         }
     }
@@ -545,6 +555,33 @@ int launch_train_pairs(const fear_frame* frames, int n_frames, const uint8_t* bo
     return FEAR_TRAIN_OK;
 }
 
+template <typename Out>
+int launch_photometric(const uint8_t* crops_u8, int n, int H, int W, const FearPhotoOp* ops, const float* taps, const float* qtable,
+                       Out* out, void* stream) {
+    static_assert(sizeof(FearPhotoOp) == sizeof(PhotoOp) && offsetof(FearPhotoOp, scale) == offsetof(PhotoOp, scale) &&
+                  offsetof(FearPhotoOp, key) == offsetof(PhotoOp, key) && offsetof(FearPhotoOp, tap_row) == offsetof(PhotoOp, tap_row),
+                  "FearPhotoOp and PhotoOp must share one layout");
+    if (n < 0 || n > 65535 || H < 4 || W < 4 || (H & 1) || (W & 1) || (long)H * W > 0x7fffffffL / 3) return FEAR_TRAIN_ERR_SHAPE;
+    if (n == 0) return FEAR_TRAIN_OK;
+    if (!crops_u8 || !ops || !qtable || !out) return FEAR_TRAIN_ERR_NULL;          // taps may be null: no record may then point at one
+    if constexpr (sizeof(Out) == 1) {
+        if (crops_u8 == out) return FEAR_TRAIN_ERR_SHAPE;                              // a blur reads its neighbours: not in place
+    }
+    const unsigned gx = (unsigned)((W + kPhTile - 1) / kPhTile), gy = (unsigned)((H + kPhTile - 1) / kPhTile);
+    if (gy > 65535u) return FEAR_TRAIN_ERR_SHAPE;
+    PhotoArgs<Out> a{};
+    a.in = crops_u8;
+    a.ops = reinterpret_cast<const PhotoOp*>(ops);
+    a.taps = taps;
+    a.q = qtable;
+    a.out = out;
+    a.H = H; a.W = W;
+    set_normalisation(a);
+    hipLaunchKernelGGL(photometric_kernel<Out>, dim3(gx, gy, (unsigned)n), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    LAUNCH_CHECK();
+    return FEAR_TRAIN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -575,25 +612,12 @@ int fear_train_pairs_u8(const fear_frame* frames, int n_frames, const uint8_t* b
 
 int fear_photometric_u8(const uint8_t* crops_u8, int n, int H, int W, const FearPhotoOp* ops, const float* taps, const float* qtable,
                         float* out_f32, void* stream) {
-    static_assert(sizeof(FearPhotoOp) == sizeof(PhotoOp) && offsetof(FearPhotoOp, scale) == offsetof(PhotoOp, scale) &&
-                  offsetof(FearPhotoOp, key) == offsetof(PhotoOp, key) && offsetof(FearPhotoOp, tap_row) == offsetof(PhotoOp, tap_row),
-                  "FearPhotoOp and PhotoOp must share one layout");
-    if (n < 0 || n > 65535 || H < 4 || W < 4 || (H & 1) || (W & 1) || (long)H * W > 0x7fffffffL / 3) return FEAR_TRAIN_ERR_SHAPE;
-    if (n == 0) return FEAR_TRAIN_OK;
-    if (!crops_u8 || !ops || !qtable || !out_f32) return FEAR_TRAIN_ERR_NULL;      // taps may be null: no record may then point at one
-    const unsigned gx = (unsigned)((W + kPhTile - 1) / kPhTile), gy = (unsigned)((H + kPhTile - 1) / kPhTile);
-    if (gy > 65535u) return FEAR_TRAIN_ERR_SHAPE;
-    PhotoArgs a{};
-    a.in = crops_u8;
-    a.ops = reinterpret_cast<const PhotoOp*>(ops);
-    a.taps = taps;
-    a.q = qtable;
-    a.out = out_f32;
-    a.H = H; a.W = W;
-    set_normalisation(a);
-    hipLaunchKernelGGL(photometric_kernel, dim3(gx, gy, (unsigned)n), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    LAUNCH_CHECK();
-    return FEAR_TRAIN_OK;
+    return launch_photometric<float>(crops_u8, n, H, W, ops, taps, qtable, out_f32, stream);
+}
+
+int fear_photometric_stage_u8(const uint8_t* crops_u8, int n, int H, int W, const FearPhotoOp* ops, const float* taps, const float* qtable,
+                              uint8_t* out_u8, void* stream) {
+    return launch_photometric<uint8_t>(crops_u8, n, H, W, ops, taps, qtable, out_u8, stream);
 }
 
 int fear_colour_u8(const uint8_t* crops_in, int n, int H, int W, const FearColourOp* ops, const uint8_t* aux_lut, uint8_t* crops_out,

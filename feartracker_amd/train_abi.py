@@ -81,6 +81,10 @@ TRAIN_SYMBOLS = {
     # the photometric stage behind the pairs (FearPhotoOp below)
     "fear_train_pairs_u8": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _P, _P], _i),
     "fear_photometric_u8": ([_P, _i, _i, _i, _P, _P, _P, _P, _P], _i),
+    "fear_photometric_stage_u8": ([_P, _i, _i, _i, _P, _P, _P, _P, _P], _i),
+    # ImageCompression: the JPEG round trip between the stage above and fear_photometric_u8
+    "fear_jpeg_u8": ([_P, _i, _i, _i, _P, _P, _sz, _P, _P], _i),
+    "fear_jpeg_workspace_bytes": ([_i, _i, _i], _sz),
     # the colour stage's members that are no lookup table (FearColourOp below)
     "fear_colour_u8": ([_P, _i, _i, _i, _P, _P, _P, _P], _i),
     # step metrics (metrics.TrainMetrics)

@@ -13,7 +13,9 @@
             the device's `fear_colour_u8` applies per crop behind the tables; `colour_u8_host` restates it
 * photometric  (`photometric=True`, off by default) `PHOTOMETRIC_AUGMENTATIONS` on each crop on its own, between the colour stage and
             the normalisation: a blur group, a noise group and Downscale(0.5), each at p = 0.2 (aug.py:8-25, tracking_dataset.py:
-            158-175; the members built are DESIGN.md section 11's); `photometric_host` restates the device's `fear_photometric_u8`
+            158-175; the members built are DESIGN.md section 11's); `photometric_host` restates the device's `fear_photometric_u8`.
+            `noise_members` widens the noise group to ImageCompression: a JPEG round trip without its entropy coding
+            (`fear_jpeg_u8`), which `jpeg_roundtrip_u8_host` restates and the tests hold to Pillow's libjpeg-turbo byte for byte
 * targets   `FEARBoxCoder.encode(search_bbox)` and `get_regression_weight_label(search_bbox, 256, 16)`, zeros without presence
 
 Every scalar per-pair step runs here on the host, vectorised over the batch: the draws (`draw`), the context boxes (`extend_bbox`,
@@ -58,7 +60,11 @@ DEFAULT_TRAIN_DATA_CONFIG: Dict[str, Any] = dict(
     # PHOTOMETRIC_AUGMENTATIONS (dataset/aug.py:8-25), per crop, off unless asked for
     photometric=False,
     blur_p=0.2,                  # OneOf([Blur, GaussianBlur, MedianBlur, MotionBlur])
-    noise_p=0.2,                 # OneOf([MultiplicativeNoise, GaussNoise])
+    noise_p=0.2,                 # OneOf([MultiplicativeNoise, GaussNoise]), or the members named below
+    # the members of the noise OneOf, a subset of NOISE_MEMBERS in its order; "all" adds ImageCompression (3 of the reference's 4:
+    # ISONoise is not built)
+    noise_members=("multiplicative", "gauss"),
+    jpeg_quality=(50, 100),      # ImageCompression(quality_lower=50): the quality is uniform over these, both ends included
     downscale_p=0.2,             # Downscale(0.5, 0.5)
     blur_limit=7, gauss_var_limit=(10, 35), multiplier=(0.9, 1.1),
 )
@@ -73,7 +79,8 @@ DEVICE_COLOUR_KINDS = (COLOUR_EQUALIZE, COLOUR_HSV, COLOUR_JITTER, COLOUR_EMBOSS
 JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE = 0, 1, 2, 3       # ColorJitter's operations, as `order` names them
 
 BLUR_NONE, BLUR_BOX, BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_MOTION = 0, 1, 2, 3, 4
-NOISE_NONE, NOISE_MULTIPLICATIVE, NOISE_GAUSS = 0, 1, 2
+NOISE_NONE, NOISE_MULTIPLICATIVE, NOISE_GAUSS, NOISE_JPEG = 0, 1, 2, 3
+NOISE_MEMBERS = {"multiplicative": NOISE_MULTIPLICATIVE, "gauss": NOISE_GAUSS, "jpeg": NOISE_JPEG}   # (in the order `noise_members` keeps)
 N_QUANTILES = 4096
 GAUSS_WEIGHTS = {3: (64, 128, 64), 5: (16, 64, 96, 64, 16), 7: (8, 28, 56, 72, 56, 28, 8)}
 
@@ -131,6 +138,9 @@ class TrainPairParams:
     colour_jitter: Optional[np.ndarray] = None   # (B, 4) ColorJitter's brightness, contrast, saturation factors and hue shift
     colour_jitter_order: Optional[np.ndarray] = None   # (B, 4) int32, a permutation of JITTER_* per pair
     emboss: Optional[np.ndarray] = None          # (B, 2) alpha, strength
+    # ImageCompression's quality per crop, (B, 2) int32 like the arrays of `photo`; None unless "jpeg" is a configured noise member and
+    # the photometric stage is on
+    jpeg_quality: Optional[np.ndarray] = None
 
 
 def _pairs_array(pairs) -> np.ndarray:
@@ -658,9 +668,11 @@ def _windows(img: np.ndarray, r: int, mode: str) -> np.ndarray:
     return np.lib.stride_tricks.sliding_window_view(padded, (2 * r + 1, 2 * r + 1), axis=(0, 1))
 
 
-def photometric_u8_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray) -> np.ndarray:
+def photometric_u8_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray, quality: int = 0) -> np.ndarray:
     """fear_photometric_u8's uint8 result for one (H, W, 3) crop and its FearPhotoOp record `op` (a PHOTO_DTYPE scalar), before the
-    normalisation: blur, then noise, then Downscale(0.5).  Records the device treats as "none" are "none" here too."""
+    normalisation: blur, then noise, then Downscale(0.5).  Records the device treats as "none" are "none" here too.  A record whose
+    noise is NOISE_JPEG takes `jpeg_roundtrip_u8_host` at `quality` in the noise's place (the builder's three-launch path); with a
+    quality outside 1..100 — the default — that noise is "none", as it is to fear_photometric_u8 and fear_jpeg_u8."""
     v = np.asarray(crop_u8)
     H, W = v.shape[:2]
     if H < 4 or W < 4 or H % 2 or W % 2:
@@ -695,18 +707,149 @@ def photometric_u8_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: 
         f = np.float32(op["scale"]) * np.asarray(q, dtype=np.float32)[idx]
         f = v.astype(np.float32) + f
         v = np.clip(f, 0, 255).astype(np.uint8)
+    elif noise == NOISE_JPEG and 1 <= int(quality) <= 100:
+        v = jpeg_roundtrip_u8_host(np.ascontiguousarray(v), int(quality))
     if int(op["downscale"]) != 0:
         v = np.repeat(np.repeat(v[::2, ::2], 2, axis=0), 2, axis=1)
     return np.ascontiguousarray(v)
 
 
-def photometric_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray) -> np.ndarray:
+def photometric_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray, quality: int = 0) -> np.ndarray:
     """numpy restatement of fear_photometric_u8 for one crop: (H, W, 3) uint8 -> normalised fp32 (3, H, W)."""
-    v = photometric_u8_host(crop_u8, op, taps, q).astype(np.float32)
+    v = photometric_u8_host(crop_u8, op, taps, q, quality).astype(np.float32)
     v -= _MEAN
     v *= _INV_STD
     return np.ascontiguousarray(v.transpose(2, 0, 1))
 
+
+
+# -------------------------------------------------------------------------------------------------------------------------- JPEG
+# ImageCompression: the lossy part of a baseline JPEG round trip (libjpeg: 4:2:0, jpeg_set_quality(q, force_baseline), islow DCT both
+# ways, fancy upsampling), in integers.  The entropy coding is lossless and is left out.  DESIGN.md section 11 states the contract;
+# tests/test_jpeg_host.py holds it to Pillow's libjpeg-turbo byte for byte.
+JPEG_LUMA_BASE = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+                           14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+                           49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99], dtype=np.int64)
+JPEG_CHROMA_BASE = np.array([17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+                             47, 66, 99, 99, 99, 99, 99, 99] + [99] * 32, dtype=np.int64)
+# jfdctint / jidctint's constants: FIX(x) = rint(x * 2 ** 13)
+_F0_298, _F0_390, _F0_541, _F0_765, _F0_899, _F1_175 = 2446, 3196, 4433, 6270, 7373, 9633
+_F1_501, _F1_847, _F1_961, _F2_053, _F2_562, _F3_072 = 12299, 15137, 16069, 16819, 20995, 25172
+
+
+def jpeg_quant_tables(quality: int) -> Tuple[np.ndarray, np.ndarray]:
+    """jpeg_set_quality(quality, force_baseline)'s luminance and chrominance tables, (64,) int64 each in natural (row-major) order:
+    scale = 5000 / quality below 50, else 200 - 2 quality; q = clamp((base scale + 50) / 100, 1, 255), integer divisions."""
+    quality = int(quality)
+    if not 1 <= quality <= 100:
+        raise ValueError("a JPEG quality lies in 1..100")
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    return tuple(np.clip((base * scale + 50) // 100, 1, 255) for base in (JPEG_LUMA_BASE, JPEG_CHROMA_BASE))
+
+
+def _descale(x, n: int):
+    return (x + (1 << (n - 1))) >> n
+
+
+def _fdct_pass(d, first: bool):
+    """One pass of jfdctint over eight int64 arrays (a row's or a column's samples): rows first (scaled up by 2 ** PASS1_BITS), then
+    columns (PASS1_BITS removed, the factor 8 of the DCT kept)."""
+    t0, t7, t1, t6, t2, t5, t3, t4 = d[0] + d[7], d[0] - d[7], d[1] + d[6], d[1] - d[6], d[2] + d[5], d[2] - d[5], d[3] + d[4], d[3] - d[4]
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    n = 11 if first else 15                       # CONST_BITS - PASS1_BITS | CONST_BITS + PASS1_BITS
+    out = [None] * 8
+    out[0] = (t10 + t11) << 2 if first else _descale(t10 + t11, 2)
+    out[4] = (t10 - t11) << 2 if first else _descale(t10 - t11, 2)
+    z1 = (t12 + t13) * _F0_541
+    out[2] = _descale(z1 + t13 * _F0_765, n)
+    out[6] = _descale(z1 - t12 * _F1_847, n)
+    z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
+    z5 = (z3 + z4) * _F1_175
+    t4, t5, t6, t7 = t4 * _F0_298, t5 * _F2_053, t6 * _F3_072, t7 * _F1_501
+    z1, z2, z3, z4 = -z1 * _F0_899, -z2 * _F2_562, -z3 * _F1_961 + z5, -z4 * _F0_390 + z5
+    out[7], out[5], out[3], out[1] = _descale(t4 + z1 + z3, n), _descale(t5 + z2 + z4, n), _descale(t6 + z2 + z3, n), _descale(t7 + z1 + z4, n)
+    return out
+
+
+def _idct_pass(d, first: bool):
+    """One pass of jidctint (islow) over eight int64 arrays: columns first, then rows with the final DESCALE by CONST_BITS +
+    PASS1_BITS + 3."""
+    z1 = (d[2] + d[6]) * _F0_541
+    t2, t3 = z1 - d[6] * _F1_847, z1 + d[2] * _F0_765
+    t0, t1 = (d[0] + d[4]) << 13, (d[0] - d[4]) << 13
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    t0, t1, t2, t3 = d[7], d[5], d[3], d[1]
+    z1, z2, z3, z4 = t0 + t3, t1 + t2, t0 + t2, t1 + t3
+    z5 = (z3 + z4) * _F1_175
+    t0, t1, t2, t3 = t0 * _F0_298, t1 * _F2_053, t2 * _F3_072, t3 * _F1_501
+    z1, z2, z3, z4 = -z1 * _F0_899, -z2 * _F2_562, -z3 * _F1_961 + z5, -z4 * _F0_390 + z5
+    t0, t1, t2, t3 = t0 + z1 + z3, t1 + z2 + z4, t2 + z2 + z3, t3 + z1 + z4
+    n = 11 if first else 18
+    return [_descale(v, n) for v in (t10 + t3, t11 + t2, t12 + t1, t13 + t0, t13 - t0, t12 - t1, t11 - t2, t10 - t3)]
+
+
+def jpeg_fdct_islow(blocks: np.ndarray) -> np.ndarray:
+    """jfdctint on level-shifted samples (..., 8, 8) -> int64 coefficients (..., 8, 8), 8 times the orthonormal DCT."""
+    b = np.asarray(blocks).astype(np.int64)
+    b = np.stack(_fdct_pass([b[..., i] for i in range(8)], True), axis=-1)                 # rows
+    return np.stack(_fdct_pass([b[..., i, :] for i in range(8)], False), axis=-2)          # columns
+
+
+def jpeg_idct_islow(coef: np.ndarray) -> np.ndarray:
+    """jidctint on dequantised coefficients (..., 8, 8) -> int64 samples (..., 8, 8) before the level shift and the clamp."""
+    c = np.asarray(coef).astype(np.int64)
+    c = np.stack(_idct_pass([c[..., i, :] for i in range(8)], True), axis=-2)              # columns
+    return np.stack(_idct_pass([c[..., i] for i in range(8)], False), axis=-1)             # rows
+
+
+def _jpeg_plane(plane: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """One component through FDCT, quantiser, dequantiser and IDCT: int64 (h, w) in 0..255 -> int64 (h, w) in 0..255."""
+    h, w = plane.shape
+    blocks = (plane - 128).reshape(h // 8, 8, w // 8, 8).transpose(0, 2, 1, 3)
+    v = jpeg_fdct_islow(blocks)
+    div = (q << 3).reshape(8, 8)
+    coef = np.sign(v) * ((np.abs(v) + (div >> 1)) // div)
+    out = np.clip(jpeg_idct_islow(coef * q.reshape(8, 8)) + 128, 0, 255)
+    return out.transpose(0, 2, 1, 3).reshape(h, w)
+
+
+def _jpeg_upsample(c: np.ndarray) -> np.ndarray:
+    """h2v2 fancy upsampling of a chroma plane (h, w) -> (2 h, 2 w): 3 near + far vertically (the first and last rows are their own
+    far rows), then (3 this + neighbour + 8 | 7) >> 4 horizontally (the first and last columns are their own neighbours)."""
+    up, down = np.concatenate([c[:1], c[:-1]]), np.concatenate([c[1:], c[-1:]])
+    v = np.stack([3 * c + up, 3 * c + down], axis=1).reshape(2 * c.shape[0], c.shape[1])
+    left, right = np.concatenate([v[:, :1], v[:, :-1]], axis=1), np.concatenate([v[:, 1:], v[:, -1:]], axis=1)
+    return np.stack([(3 * v + left + 8) >> 4, (3 * v + right + 7) >> 4], axis=2).reshape(v.shape[0], 2 * v.shape[1])
+
+
+def jpeg_roundtrip_u8_host(crop_u8: np.ndarray, quality: int) -> np.ndarray:
+    """ImageCompression at one quality on a uint8 (H, W, 3) crop, H and W multiples of 16: what cv2.imdecode(cv2.imencode(".jpg", crop,
+    quality)) returns, computed without the entropy coding.  cv2 reads the crop as BGR, so libjpeg's R is channel 2 and its B is
+    channel 0 (albumentations hands over its RGB crop unconverted)."""
+    v = np.asarray(crop_u8)
+    if v.ndim != 3 or v.shape[2] != 3 or v.dtype != np.uint8:
+        raise ValueError("the crop must be uint8 (H, W, 3)")
+    H, W = v.shape[:2]
+    if H < 16 or W < 16 or H % 16 or W % 16:
+        raise ValueError("the JPEG round trip takes sides that are positive multiples of 16 (whole MCUs)")
+    q_luma, q_chroma = jpeg_quant_tables(quality)
+    p = v.astype(np.int64)
+    r, g, b = p[..., 2], p[..., 1], p[..., 0]
+    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
+    cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16
+    cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16
+    bias = np.tile(np.array([1, 2], dtype=np.int64), W // 4)              # alternates along a row of the downsampled plane
+
+    def down(c):
+        return (c[0::2, 0::2] + c[0::2, 1::2] + c[1::2, 0::2] + c[1::2, 1::2] + bias[None, :]) >> 2
+
+    y = _jpeg_plane(y, q_luma)
+    cb = _jpeg_upsample(_jpeg_plane(down(cb), q_chroma)) - 128
+    cr = _jpeg_upsample(_jpeg_plane(down(cr), q_chroma)) - 128
+    r = y + ((91881 * cr + 32768) >> 16)
+    b = y + ((116130 * cb + 32768) >> 16)
+    g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
+    return np.clip(np.stack([b, g, r], axis=-1), 0, 255).astype(np.uint8)
 
 
 def encode_targets(search_bbox: np.ndarray, presence: np.ndarray, r_pos: int = 2):
@@ -742,6 +885,10 @@ class TrainPairBuilder:
                 raise KeyError(f"unknown train-data config keys {sorted(unknown)}")
             self.config.update(config)
         self.colour_members = self._members(self.config["colour_members"])
+        self.noise_members = self._members(self.config["noise_members"], NOISE_MEMBERS, "noise")
+        lo, hi = (int(v) for v in self.config["jpeg_quality"])
+        if not 1 <= lo <= hi <= 100:
+            raise ValueError("jpeg_quality must be (low, high) with 1 <= low <= high <= 100")
         self._device_colour = any(COLOUR_MEMBERS[m] in DEVICE_COLOUR_KINDS for m in self.colour_members)
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.generator = np.random.default_rng(seed)
@@ -749,18 +896,19 @@ class TrainPairBuilder:
         self._qtable = None
 
     @staticmethod
-    def _members(value) -> Tuple[str, ...]:
-        """`colour_members` as a tuple of names in COLOUR_MEMBERS' order: "all", or any non-empty subset (KeyError for a name that is
-        no member)."""
+    def _members(value, table: Optional[Dict[str, int]] = None, group: str = "colour") -> Tuple[str, ...]:
+        """`colour_members` (or, with NOISE_MEMBERS as `table`, `noise_members`) as a tuple of names in the table's order: "all", or any
+        non-empty subset (KeyError for a name that is no member)."""
+        table = COLOUR_MEMBERS if table is None else table
         if isinstance(value, str):
-            value = tuple(COLOUR_MEMBERS) if value == "all" else (value,)
+            value = tuple(table) if value == "all" else (value,)
         names = tuple(value)
-        unknown = [m for m in names if m not in COLOUR_MEMBERS]
+        unknown = [m for m in names if m not in table]
         if unknown:
-            raise KeyError(f"unknown colour members {unknown}: the members are {list(COLOUR_MEMBERS)}")
+            raise KeyError(f"unknown {group} members {unknown}: the members are {list(table)}")
         if not names or len(set(names)) != len(names):
-            raise ValueError("colour_members must name at least one member, each once")
-        return tuple(m for m in COLOUR_MEMBERS if m in names)
+            raise ValueError(f"{group}_members must name at least one member, each once")
+        return tuple(m for m in table if m in names)
 
     # ------------------------------------------------------------------ draws
     def draw(self, pairs, frame_shapes: Sequence[Tuple[int, ...]], generator: Optional[np.random.Generator] = None) -> TrainPairParams:
@@ -786,7 +934,11 @@ class TrainPairBuilder:
         shapes = tuple((int(s[0]), int(s[1])) for s in frame_shapes)
         photo = self._draw_photo(B, rng) if cfg["photometric"] else None       # after every other draw: off consumes nothing
         # the members colour_members adds, after every other draw: the default members consume nothing more
-        return TrainPairParams(context, jitter, tone, colour, alpha, beta, gamma, shift, shapes, photo, **self._draw_colour(B, rng))
+        extra = self._draw_colour(B, rng)
+        if photo is not None and "jpeg" in self.noise_members:          # last of all: configurations without it keep their stream
+            lo, hi = (int(v) for v in cfg["jpeg_quality"])
+            extra["jpeg_quality"] = rng.integers(lo, hi + 1, size=(B, 2)).astype(np.int32)
+        return TrainPairParams(context, jitter, tone, colour, alpha, beta, gamma, shift, shapes, photo, **extra)
 
     def _draw_colour(self, B: int, rng: np.random.Generator) -> Dict[str, np.ndarray]:
         """The values of the configured members beyond the first three (aug.py:35-48), every one for every pair: RandomToneCurve's
@@ -816,7 +968,8 @@ class TrainPairBuilder:
     def _draw_photo(self, B: int, rng: np.random.Generator) -> PhotoParams:
         """The photometric draws, (B, 2): each group at its p, uniform over its members (aug.py:8-25); ksize uniform over the odd
         sizes up to blur_limit; MotionBlur's end points as MotionBlur.get_params draws them (two x, then two y, distinct when the x
-        are equal); var and the multiplier uniform over their limits; a fresh 64-bit Philox key per crop."""
+        are equal); var and the multiplier uniform over their limits; a fresh 64-bit Philox key per crop.  ImageCompression's quality
+        is drawn by `draw`, behind every other draw (`TrainPairParams.jpeg_quality`)."""
         cfg = self.config
         n_k = (int(cfg["blur_limit"]) - 3) // 2 + 1
         if n_k < 1 or n_k > 3:
@@ -826,7 +979,8 @@ class TrainPairBuilder:
         xs, xe, ys, ye = (rng.integers(0, ksize) for _ in range(4))
         other = (ys + 1 + rng.integers(0, ksize - 1)) % ksize                  # random.sample(range(k), 2)'s second value
         line = np.stack([xs, ys, xe, np.where(xs == xe, other, ye)], axis=-1).astype(np.int32)
-        noise = np.where(rng.random((B, 2)) < cfg["noise_p"], 1 + rng.integers(0, 2, size=(B, 2)), NOISE_NONE).astype(np.int32)
+        kinds = np.array([NOISE_MEMBERS[m] for m in self.noise_members])
+        noise = np.where(rng.random((B, 2)) < cfg["noise_p"], kinds[rng.integers(0, len(kinds), size=(B, 2))], NOISE_NONE).astype(np.int32)
         var = rng.uniform(cfg["gauss_var_limit"][0], cfg["gauss_var_limit"][1], size=(B, 2))
         mult = rng.uniform(cfg["multiplier"][0], cfg["multiplier"][1], size=(B, 2))
         key = rng.integers(0, 2 ** 32, size=(B, 2, 2), dtype=np.uint64).astype(np.uint32)
@@ -841,6 +995,11 @@ class TrainPairBuilder:
             raise ValueError("the photometric stage is on, but params carry no photometric draws (drawn with it off?)")
         if params.photo.blur.shape != (B, 2):
             raise ValueError(f"photometric draws are shaped {params.photo.blur.shape}, the table has {B} pairs")
+        if (np.asarray(params.photo.noise) == NOISE_JPEG).any():
+            if "jpeg" not in self.noise_members:
+                raise ValueError("a crop drew ImageCompression, but noise_members does not configure it")
+            if params.jpeg_quality is None or np.shape(params.jpeg_quality) != (B, 2):
+                raise ValueError("a crop drew ImageCompression, but the params carry no quality for it (drawn without it in noise_members?)")
         return params.photo
 
     # ------------------------------------------------------------------ host tables
@@ -903,7 +1062,8 @@ class TrainPairBuilder:
                 v = colour_u8_host(v, colour[0][k], colour[1][k])
             if photo is None:
                 return _normalise_u8(v)
-            return photometric_host(v, ops[k, which], taps, q)
+            quality = int(params.jpeg_quality[k, which]) if ops["noise"][k, which] == NOISE_JPEG else 0
+            return photometric_host(v, ops[k, which], taps, q, quality)
 
         def frame_of(i):
             if 0 <= i < len(host):
@@ -947,11 +1107,21 @@ class TrainPairBuilder:
         elif colour is not None:               # the crops still leave through fear_photometric_u8: all-"none" records, the normalisation
             ops, taps = np.zeros((B, 2), dtype=PHOTO_DTYPE), np.zeros((0, 49), dtype=np.float32)
         staged_u8 = photo is not None or colour is not None
+        # a batch in which a crop drew ImageCompression (the host knows from the draws) runs three launches per side: the chain up to
+        # the noise as uint8 (`ops`, the JPEG crops without noise and Downscale), fear_jpeg_u8 (quality 0, a copy, for the other
+        # crops), then the JPEG crops' Downscale and everybody's normalisation (`tail`)
+        jpeg = photo is not None and bool((ops["noise"] == NOISE_JPEG).any())
+        if jpeg:
+            drew = ops["noise"] == NOISE_JPEG
+            tail = np.zeros((B, 2), dtype=PHOTO_DTYPE)
+            tail["downscale"], tail["tap_row"] = np.where(drew, ops["downscale"], 0), -1
+            quality = np.where(drew, params.jpeg_quality, 0).astype(np.int32)
+            ops["noise"][drew], ops["downscale"][drew] = NOISE_NONE, 0
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
             dframes = [self._frame_on_device(f) for f in frames]
             # one staging buffer, one transfer: frame table | geometry | lookup tables | search_bbox | photometric records | taps |
-            # colour records (8-byte aligned: they hold a double) | colour tables
+            # colour records (8-byte aligned: they hold a double) | colour tables | the JPEG path's last records | its qualities
             o_geom = 16 * F
             o_lut = o_geom + 96 * B
             o_box = o_lut + 768 * B
@@ -959,7 +1129,11 @@ class TrainPairBuilder:
             o_taps = o_ops + (64 * B if staged_u8 else 0)
             o_cops = (o_taps + (taps.size * 4 if staged_u8 else 0) + 7) // 8 * 8
             o_aux = o_cops + (64 * B if colour is not None else 0)
-            total = o_aux + (768 * B if colour is not None else 0)
+            o_tail = o_aux + (768 * B if colour is not None else 0)
+            if jpeg:
+                o_tail = (o_tail + 3) // 4 * 4
+            o_quality = o_tail + (64 * B if jpeg else 0)
+            total = o_quality + (8 * B if jpeg else 0)
             pinned = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True)
             hv = pinned.numpy()
             ftab = np.zeros(F, dtype=FRAME_DTYPE)
@@ -974,7 +1148,10 @@ class TrainPairBuilder:
                 hv[o_taps:o_taps + taps.size * 4] = taps.view(np.uint8).reshape(-1)
             if colour is not None:             # one record per pair, shared by its two crops
                 hv[o_cops:o_aux] = colour[0].view(np.uint8)
-                hv[o_aux:total] = colour[1].reshape(-1)
+                hv[o_aux:o_aux + 768 * B] = colour[1].reshape(-1)
+            if jpeg:                           # templates first, then the searches, as the records in front
+                hv[o_tail:o_quality] = np.ascontiguousarray(tail.T).view(np.uint8).reshape(-1)
+                hv[o_quality:total] = np.ascontiguousarray(quality.T).view(np.uint8).reshape(-1)
             staged = pinned.to(dev, non_blocking=True)
             base = staged.data_ptr()
             border = torch.empty((max(F, 1), 3), dtype=torch.uint8, device=dev)
@@ -1010,9 +1187,26 @@ class TrainPairBuilder:
             if staged_u8:
                 q = self._quantiles_on_device()
                 d_taps = ctypes.c_void_p(base + o_taps) if taps.size else None
+                if jpeg:
+                    ws_bytes = lib.fear_jpeg_workspace_bytes(B, SEARCH_SIZE, SEARCH_SIZE)      # the larger side's serves both
+                    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
                 for which, (crops, out, side) in enumerate(((t_out, tmpl, TEMPLATE_SIZE), (s_out, srch, SEARCH_SIZE))):
+                    o_last = o_ops
+                    if jpeg:
+                        mid, crops_in = torch.empty_like(crops), crops
+                        crops = torch.empty_like(crops)
+                        rc = lib.fear_photometric_stage_u8(ctypes.c_void_p(crops_in.data_ptr()), B, side, side,
+                                                           ctypes.c_void_p(base + o_ops + 32 * B * which), d_taps,
+                                                           ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(mid.data_ptr()), st)
+                        if rc != 0:
+                            raise RuntimeError(f"fear_photometric_stage_u8 failed with status {rc}")
+                        rc = lib.fear_jpeg_u8(ctypes.c_void_p(mid.data_ptr()), B, side, side, ctypes.c_void_p(base + o_quality + 4 * B * which),
+                                              ctypes.c_void_p(ws.data_ptr()), ws_bytes, ctypes.c_void_p(crops.data_ptr()), st)
+                        if rc != 0:
+                            raise RuntimeError(f"fear_jpeg_u8 failed with status {rc}")
+                        o_last = o_tail
                     rc = lib.fear_photometric_u8(ctypes.c_void_p(crops.data_ptr()), B, side, side,
-                                                 ctypes.c_void_p(base + o_ops + 32 * B * which), d_taps, ctypes.c_void_p(q.data_ptr()),
+                                                 ctypes.c_void_p(base + o_last + 32 * B * which), d_taps, ctypes.c_void_p(q.data_ptr()),
                                                  ctypes.c_void_p(out.data_ptr()), st)
                     if rc != 0:
                         raise RuntimeError(f"fear_photometric_u8 failed with status {rc}")

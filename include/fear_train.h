@@ -448,6 +448,7 @@ int fear_train_pairs_u8(const fear_frame* frames, int n_frames, const uint8_t* b
 #define FEAR_PHOTO_NOISE_NONE 0
 #define FEAR_PHOTO_NOISE_MULTIPLICATIVE 1
 #define FEAR_PHOTO_NOISE_GAUSS 2
+#define FEAR_PHOTO_NOISE_JPEG 3          /* ImageCompression: "none" to fear_photometric_u8, applied by fear_jpeg_u8 (below) */
 #define FEAR_PHOTO_QUANTILES 4096
 
 /* One crop.  32 bytes, no padding. */
@@ -468,6 +469,40 @@ _Static_assert(sizeof(FearPhotoOp) == 32, "FearPhotoOp is 32 bytes");
 
 int fear_photometric_u8(const uint8_t* crops_u8, int n, int H, int W, const FearPhotoOp* ops, const float* taps, const float* qtable,
                         float* out_f32, void* stream);
+
+/* fear_photometric_u8 with the crops left as the chain made them — after blur, noise and Downscale, before the normalisation — as uint8
+ * HWC, the input of fear_jpeg_u8.  The same kernel body with another store policy, the same records and argument checks; and
+ * crops_u8 != out_u8 (a blur reads its neighbours): FEAR_TRAIN_ERR_SHAPE.
+ *   out_u8 : (n, H, W, 3) uint8, device                                                                                              */
+int fear_photometric_stage_u8(const uint8_t* crops_u8, int n, int H, int W, const FearPhotoOp* ops, const float* taps, const float* qtable,
+                              uint8_t* out_u8, void* stream);
+
+/* ---- ImageCompression, the third member of the reference's noise group (model_training/dataset/aug.py:19-22): the lossy part of a
+ * baseline JPEG round trip on uint8 HWC crops, as libjpeg computes it and without the entropy coding, which is lossless (DESIGN.md
+ * section 11 states the contract; train_data.jpeg_roundtrip_u8_host restates it in numpy, the two agree bit for bit, and the numpy
+ * form equals Pillow's libjpeg-turbo byte for byte).  cv2 reads albumentations' RGB crop as BGR: libjpeg's R is channel 2, its B channel 0.
+ *   forward colour   Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *                    Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *                    Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ *   downsample       Cb, Cr 4:2:0: (a + b + c + d + bias) >> 2, bias 1, 2, 1, 2, ... along a row of the downsampled plane
+ *   forward DCT      level shift -128, jfdctint (CONST_BITS 13, PASS1_BITS 2, rows then columns, output scaled by 8)
+ *   quantise         q[k] = clamp((base[k] scale + 50) / 100, 1, 255), scale = 5000 / quality below 50, else 200 - 2 quality, base the
+ *                    standard luminance / chrominance table; coef = sign(v) ((|v| + (q[k] << 3 >> 1)) / (q[k] << 3))
+ *   inverse DCT      coef q[k], jidctint islow (columns then rows, descale by CONST_BITS + PASS1_BITS + 3), + 128, clamp to 0..255
+ *   upsample         h2v2 fancy: 3 near + far vertically (the first and last rows are their own far rows), then (3 this + left + 8) >> 4
+ *                    and (3 this + right + 7) >> 4 (the first and last columns are their own neighbours), across block and MCU borders
+ *   colour back      R = Y + ((91881 (Cr - 128) + 32768) >> 16), B = Y + ((116130 (Cb - 128) + 32768) >> 16),
+ *                    G = Y + ((-22554 (Cb - 128) - 46802 (Cr - 128) + 32768) >> 16), each clamped to 0..255
+ * `quality` lives in device memory, where the call cannot read it: the kernels copy a crop whose quality is outside 1..100.  Two launches
+ * inside the call (fancy upsampling reads chroma across MCU borders): the first leaves the decoded Y, Cb and Cr planes in `workspace`
+ * (fear_jpeg_workspace_bytes: 1.5 H W bytes per crop and 16 for alignment; 0 for a shape the call refuses), the second upsamples,
+ * converts back and stores.  No atomics.  H and W must be positive multiples of 16 (whole MCUs), n <= 65535, crops_in != crops_out:
+ * FEAR_TRAIN_ERR_SHAPE otherwise.  n == 0 returns FEAR_TRAIN_OK without a launch.  A null crops_in, quality or crops_out returns
+ * FEAR_TRAIN_ERR_NULL, a null or too small workspace FEAR_TRAIN_ERR_WORKSPACE.
+ *   crops_in, crops_out : (n, H, W, 3) uint8, device, distinct      quality : (n) int32, device                                     */
+int fear_jpeg_u8(const uint8_t* crops_in, int n, int H, int W, const int32_t* quality, void* workspace, size_t workspace_bytes,
+                 uint8_t* crops_out, void* stream);
+size_t fear_jpeg_workspace_bytes(int n, int H, int W);
 
 /* ---- the colour stage's members that are no lookup table: Equalize, HueSaturationValue, ColorJitter and Emboss of the reference's
  * p = 0.5 OneOf (model_training/dataset/aug.py:35-48), on uint8 HWC crops between fear_train_pairs_u8 (tone, then the lookup-table

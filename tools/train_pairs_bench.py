@@ -24,11 +24,19 @@ With --colour all it reports the colour members behind `colour_members` (same pa
   colour_u8_ms       fear_colour_u8 alone on the batch's 128 templates and 128 searches (two calls), every crop forced to one member,
                      per member, HIP events; worst_member names the slowest
   step_ms            FEARNetTrainHIP.step on fixed inputs, for the shares
+With --noise all it reports ImageCompression, the member behind `noise_members` (same pairs and frames, the photometric stage on):
+  build_default_ms   `build` with photometric=True and the default members, one figure per fresh process; with --parent-root DIR against
+                     that checkout's `build` in alternating processes, as above: the same launches, so a difference beyond the spread
+                     is a finding
+  build_all_ms       `build` with noise_members="all" at the reference's probabilities, fresh draws per call
+  jpeg_u8_ms         fear_jpeg_u8 alone on the batch's 128 templates and 128 searches (two calls), every crop at quality 50, HIP events
+  step_ms            FEARNetTrainHIP.step on fixed inputs, for the shares
 --build-only is the child mode of the above: it times `build` of the package under --root and prints {"build_ms": ...}.
 
 Usage: python tools/train_pairs_bench.py [--pairs 128] [--frames 256] [--steps 20] [--iters 50] [--out FILE]
        python tools/train_pairs_bench.py --photometric [--parent-root DIR] [--repeats 3] [--out FILE]
        python tools/train_pairs_bench.py --colour all [--parent-root DIR] [--repeats 3] [--out profiles/train_pairs_colour_bench.json]
+       python tools/train_pairs_bench.py --noise all [--parent-root DIR] [--repeats 3] [--out profiles/train_pairs_jpeg_bench.json]
 """
 from __future__ import annotations
 
@@ -79,13 +87,16 @@ def build_only(args):
     config = dict(photometric=True) if args.stage_on else {}
     if args.colour:                                    # (only ever passed for a tree that knows the key)
         config["colour_members"] = args.colour
+    if args.noise:
+        config["noise_members"] = args.noise
     builder = TrainPairBuilder(config or None, device=0, seed=0)
     print(json.dumps({"build_ms": round(_time_build(builder, frames, pairs, args.iters), 4)}))
 
 
-def _child(root, args, stage_on=False, colour=None):
+def _child(root, args, stage_on=False, colour=None, noise=None):
     cmd = [sys.executable, os.path.abspath(__file__), "--build-only", "--root", root, "--pairs", str(args.pairs), "--frames",
            str(args.frames), "--iters", str(args.iters)] + (["--stage-on"] if stage_on else []) + (["--colour", colour] if colour else [])
+    cmd += ["--noise", noise] if noise else []
     res = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300)
     return json.loads(res.stdout.strip().splitlines()[-1])["build_ms"]
 
@@ -240,6 +251,58 @@ def colour(args):
     }
 
 
+def noise(args):
+    # the fresh processes first, one at a time, before this process opens the GPU
+    default, parent, wide = [], [], []
+    for _ in range(args.repeats):
+        default.append(_child(ROOT, args, stage_on=True))
+        if args.parent_root:
+            parent.append(_child(args.parent_root, args, stage_on=True))
+        wide.append(_child(ROOT, args, stage_on=True, noise=args.noise))
+    sys.path.insert(0, ROOT)
+    from feartracker_amd.train_abi import load_train_library
+    dev = torch.device("cuda", 0)
+    B = args.pairs
+    lib = load_train_library()
+    P = ctypes.c_void_p
+    st = P(torch.cuda.current_stream(dev).cuda_stream)
+    g = torch.Generator(device=dev).manual_seed(1)
+    crops = [torch.randint(0, 256, (B, s, s, 3), generator=g, device=dev, dtype=torch.uint8) for s in (128, 256)]
+    outs = [torch.empty_like(c) for c in crops]
+    quality = torch.full((B,), 50, dtype=torch.int32, device=dev)
+    ws_bytes = lib.fear_jpeg_workspace_bytes(B, 256, 256)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+
+    def both():
+        for c, o, s in zip(crops, outs, (128, 256)):
+            assert lib.fear_jpeg_u8(P(c.data_ptr()), B, s, s, P(quality.data_ptr()), P(ws.data_ptr()), ws_bytes, P(o.data_ptr()), st) == 0
+
+    for _ in range(5):
+        both()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.iters):
+        both()
+    e1.record()
+    torch.cuda.synchronize()
+    jpeg_ms = e0.elapsed_time(e1) / args.iters
+    frames, pairs = _inputs(B, args.frames, dev)
+    step_ms, steps = _step_ms(args, frames, pairs)
+    med = lambda v: round(float(np.median(v)), 4) if v else None
+    return {
+        "pairs": B, "frames": args.frames, "frame_hw": [1080, 1920], "iters": args.iters, "noise_members": args.noise,
+        "build_default_ms": med(default), "build_default_runs": default,
+        "parent_build_ms": med(parent), "parent_build_runs": parent,
+        "build_all_ms": med(wide), "build_all_runs": wide,
+        "jpeg_u8_ms": round(jpeg_ms, 4),
+        "step_ms": round(step_ms, 3), "step_ms_runs": [round(v, 3) for v in steps],
+        "member_ms": round(med(wide) - med(default), 4),
+        "member_pct_of_step": round(100.0 * (med(wide) - med(default)) / step_ms, 2),
+        "jpeg_u8_pct_of_step": round(100.0 * jpeg_ms / step_ms, 2),
+        "device": torch.cuda.get_device_name(0),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=128)
@@ -249,6 +312,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--photometric", action="store_true")
     ap.add_argument("--colour", default=None, help='"all": report the members behind colour_members')
+    ap.add_argument("--noise", default=None, help='"all": report ImageCompression, the member behind noise_members')
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--build-only", action="store_true")
@@ -261,6 +325,9 @@ def main():
         return emit(photometric(args), args)
     if args.colour:
         return emit(colour(args), args)
+    if args.noise:
+        args.out = args.out or os.path.join(ROOT, "profiles", "train_pairs_jpeg_bench.json")
+        return emit(noise(args), args)
     sys.path.insert(0, ROOT)
     from feartracker_amd.train_data import FRAME_DTYPE, TrainPairBuilder
     from feartracker_amd.train_head import load_train_library
