@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .geometry import make_grid
-from .train_abi import TrainError, load_train_library
+from .train_abi import launch, load_train_library
 
 SCORE_SIZE, TOTAL_STRIDE, INSTANCE_SIZE = 16, 16, 256
 MAX_DATASETS = 64           # FEAR_METRICS_MAX_DATASETS
@@ -149,10 +149,8 @@ class TrainMetrics:
                 self._iou = torch.empty(B, dtype=torch.float64, device=self.device)
             st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             p = lambda t: ctypes.c_void_p(t.data_ptr())
-            rc = self.lib.fear_train_metrics(p(cls), p(bbox), p(gt), p(vis), p(ds), B, len(self.datasets), p(self._iou),
-                                             p(self._step), p(self._accum), st)
-        if rc != 0:
-            raise TrainError(f"fear_train_metrics failed with status {rc}")
+            launch(self.lib, "fear_train_metrics", p(cls), p(bbox), p(gt), p(vis), p(ds), B, len(self.datasets), p(self._iou),
+                   p(self._step), p(self._accum), st)
 
     @property
     def last_iou(self) -> torch.Tensor:

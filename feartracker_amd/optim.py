@@ -32,7 +32,7 @@ from typing import Any, Dict, List, Mapping, Optional, Tuple
 
 import torch
 
-from .train_abi import FEAR_OPT_ADAM, FEAR_OPT_ADAMW, FEAR_OPT_SGD, FearOptim, TrainError, _p, load_train_library
+from .train_abi import FEAR_OPT_ADAM, FEAR_OPT_ADAMW, FEAR_OPT_SGD, FearOptim, TrainError, _p, launch, load_train_library
 
 
 class _OptimHIP:
@@ -98,13 +98,9 @@ class _OptimHIP:
             self._norm2 = torch.zeros(2, dtype=torch.float32, device=dev)
         off = 0
         for g, c in zip(pieces, counts):
-            rc = self.lib.fear_grad_sumsq(_p(g), g.numel(), ctypes.c_void_p(self._partials.data_ptr() + 8 * off), st)
-            if rc != 0:
-                raise TrainError(f"fear_grad_sumsq failed with status {rc}")
+            launch(self.lib, "fear_grad_sumsq", _p(g), g.numel(), ctypes.c_void_p(self._partials.data_ptr() + 8 * off), st)
             off += c
-        rc = self.lib.fear_grad_norm_finalize(_p(self._partials), total, self.max_grad_norm, _p(self._norm2), st)
-        if rc != 0:
-            raise TrainError(f"fear_grad_norm_finalize failed with status {rc}")
+        launch(self.lib, "fear_grad_norm_finalize", _p(self._partials), total, self.max_grad_norm, _p(self._norm2), st)
         self.last_grad_norm = self._norm2[0]
         return _p(self._norm2, 1)
 

@@ -130,8 +130,25 @@ class FearOptim(ctypes.Structure):
                 ("momentum", _d), ("dampening", _d)]
 
 
+class FearFrame(ctypes.Structure):
+    """include/fear_hip.h `fear_frame`: one uint8 RGB (h, w, 3) device frame (train_data.records.FRAME_DTYPE is its numpy form)."""
+    _fields_ = [("data", ctypes.c_uint64), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(FearFrame) == 16 and ctypes.sizeof(ctypes.c_void_p) == 8
+
+
+class FearPairGeom(ctypes.Structure):
+    """include/fear_train.h: one pair's geometry record (train_data.records.GEOM_DTYPE is its numpy form)."""
+    _fields_ = [("t_frame", ctypes.c_int32), ("s_frame", ctypes.c_int32), ("t_ctx", ctypes.c_int32 * 4), ("s_ctx", ctypes.c_int32 * 4),
+                ("box", ctypes.c_int32 * 4), ("presence", ctypes.c_int32), ("tone", ctypes.c_int32), ("inv", _d * 4)]
+
+
+assert ctypes.sizeof(FearPairGeom) == 96 and FearPairGeom.inv.offset == 64
+
+
 class FearPhotoOp(ctypes.Structure):
-    """include/fear_train.h: one crop's photometric record (train_data.PHOTO_DTYPE is its numpy form)."""
+    """include/fear_train.h: one crop's photometric record (train_data.records.PHOTO_DTYPE is its numpy form)."""
     _fields_ = [("blur", ctypes.c_int32), ("ksize", ctypes.c_int32), ("noise", ctypes.c_int32), ("scale", _f),
                 ("key", ctypes.c_uint32 * 2), ("downscale", ctypes.c_int32), ("tap_row", ctypes.c_int32)]
 
@@ -140,7 +157,7 @@ assert ctypes.sizeof(FearPhotoOp) == 32
 
 
 class FearColourOp(ctypes.Structure):
-    """include/fear_train.h: one crop's colour record (train_data.COLOUR_DTYPE is its numpy form)."""
+    """include/fear_train.h: one crop's colour record (train_data.records.COLOUR_DTYPE is its numpy form)."""
     _fields_ = [("kind", ctypes.c_int32), ("order", ctypes.c_uint8 * 4), ("contrast", _d), ("alpha", _f), ("beta", _f),
                 ("taps", _f * 9), ("reserved", ctypes.c_int32)]
 
@@ -173,6 +190,13 @@ def load_train_library() -> ctypes.CDLL:
 
 class TrainError(RuntimeError):
     pass
+
+
+def launch(lib: ctypes.CDLL, name: str, *args) -> None:
+    """Call the operator `name` of the library; a non-zero status is a TrainError."""
+    rc = getattr(lib, name)(*args)
+    if rc != 0:
+        raise TrainError(f"{name} failed with status {rc}")
 
 
 def _p(t: Optional[torch.Tensor], offset: int = 0):

@@ -1,0 +1,116 @@
+"""The data stage's records: sizes, the default configuration, the members' enums and tables, the numpy forms of the ABI's structs
+(train_abi) and the replayable draws of a batch."""
+from __future__ import annotations
+
+from collections import namedtuple
+from dataclasses import dataclass
+from typing import Any, Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from ..train_abi import FearColourOp, FearFrame, FearPairGeom, FearPhotoOp
+
+TEMPLATE_SIZE, CONTEXT_SIZE, SEARCH_SIZE, SCORE_SIZE, TOTAL_STRIDE = 128, 512, 256, 16, 16
+
+# (the values of config/dataset/got10k_train.yaml and config/tracker/siam_tracker.yaml)
+DEFAULT_TRAIN_DATA_CONFIG: Dict[str, Any] = dict(
+    template_bbox_offset=0.2,
+    search_context=2,            # the dataset doubles it: offsets u in [2 * 2 - 3 / 2, 2 * 2 + 3 / 2)
+    context_range=3,
+    search_image_scale=0.35,
+    search_image_shift=48,
+    r_pos=2,
+    tone_p=0.05,                 # OneOf([ToGray, ToSepia])
+    colour_p=0.5,                # OneOf([RandomBrightnessContrast, RandomGamma, RGBShift]), or the members named below
+    # the members of the colour OneOf, a subset of COLOUR_MEMBERS in its order; "all" = every one of COLOUR_MEMBERS (8 of the
+    # reference's 9: CLAHE is not built)
+    colour_members=("brightness_contrast", "gamma", "rgb_shift"),
+    brightness_limit=0.2, contrast_limit=0.2, gamma_limit=(0.8, 1.2), rgb_shift_limit=20.0,
+    # PHOTOMETRIC_AUGMENTATIONS (dataset/aug.py:8-25), per crop, off unless asked for
+    photometric=False,
+    blur_p=0.2,                  # OneOf([Blur, GaussianBlur, MedianBlur, MotionBlur])
+    noise_p=0.2,                 # OneOf([MultiplicativeNoise, GaussNoise]), or the members named below
+    # the members of the noise OneOf, a subset of NOISE_MEMBERS in its order; "all" adds ImageCompression (3 of the reference's 4:
+    # ISONoise is not built)
+    noise_members=("multiplicative", "gauss"),
+    jpeg_quality=(50, 100),      # ImageCompression(quality_lower=50): the quality is uniform over these, both ends included
+    downscale_p=0.2,             # Downscale(0.5, 0.5)
+    blur_limit=7, gauss_var_limit=(10, 35), multiplier=(0.9, 1.1),
+)
+
+TONE_NONE, TONE_GRAY, TONE_SEPIA = 0, 1, 2
+COLOUR_NONE, COLOUR_BRIGHTNESS_CONTRAST, COLOUR_GAMMA, COLOUR_RGB_SHIFT = 0, 1, 2, 3
+COLOUR_TONE_CURVE, COLOUR_EQUALIZE, COLOUR_HSV, COLOUR_JITTER, COLOUR_EMBOSS = 4, 5, 6, 7, 8
+COLOUR_MEMBERS = {"brightness_contrast": COLOUR_BRIGHTNESS_CONTRAST, "gamma": COLOUR_GAMMA, "rgb_shift": COLOUR_RGB_SHIFT,
+                  "tone_curve": COLOUR_TONE_CURVE, "equalize": COLOUR_EQUALIZE, "hsv": COLOUR_HSV, "colour_jitter": COLOUR_JITTER,
+                  "emboss": COLOUR_EMBOSS}                                      # (in the order `colour_members` keeps)
+DEVICE_COLOUR_KINDS = (COLOUR_EQUALIZE, COLOUR_HSV, COLOUR_JITTER, COLOUR_EMBOSS)   # fear_colour_u8's; the others are lookup tables
+JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE = 0, 1, 2, 3       # ColorJitter's operations, as `order` names them
+
+BLUR_NONE, BLUR_BOX, BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_MOTION = 0, 1, 2, 3, 4
+NOISE_NONE, NOISE_MULTIPLICATIVE, NOISE_GAUSS, NOISE_JPEG = 0, 1, 2, 3
+NOISE_MEMBERS = {"multiplicative": NOISE_MULTIPLICATIVE, "gauss": NOISE_GAUSS, "jpeg": NOISE_JPEG}   # (in the order `noise_members` keeps)
+N_QUANTILES = 4096
+GAUSS_WEIGHTS = {3: (64, 128, 64), 5: (16, 64, 96, 64, 16), 7: (8, 28, 56, 72, 56, 28, 8)}
+
+# columns of the pairs table
+PAIR_COLUMNS = ("template_frame", "tx", "ty", "tw", "th", "search_frame", "sx", "sy", "sw", "sh", "presence")
+
+TrainBatch = namedtuple("TrainBatch", ["template", "search", "gt_reg", "gt_cls", "gt_weight", "search_bbox"])
+
+
+# the numpy forms of the device's records, derived from the ctypes mirrors of include/fear_train.h
+GEOM_DTYPE, FRAME_DTYPE = np.dtype(FearPairGeom), np.dtype(FearFrame)
+PHOTO_DTYPE, COLOUR_DTYPE = np.dtype(FearPhotoOp), np.dtype(FearColourOp)
+
+
+@dataclass
+class PhotoParams:
+    """The photometric draws of one batch, every array shaped (B, 2, ...): [:, 0] the template crop, [:, 1] the search crop.  The
+    values of all members are drawn; only the drawn member's are used."""
+    blur: np.ndarray             # int32, BLUR_*
+    ksize: np.ndarray            # int32, 3 / 5 / 7
+    line: np.ndarray             # (B, 2, 4) int32: MotionBlur's end points xs, ys, xe, ye
+    noise: np.ndarray            # int32, NOISE_*
+    var: np.ndarray              # float64, GaussNoise's variance
+    mult: np.ndarray             # float64, MultiplicativeNoise's multiplier
+    key: np.ndarray              # (B, 2, 2) uint32, the Philox key of GaussNoise
+    downscale: np.ndarray        # int32, 0 / 1
+
+
+@dataclass
+class TrainPairParams:
+    """Every random parameter of one batch (a replayable host record).  Per pair: the search context offset, the jitter
+    (scale_x, scale_y, shift_x, shift_y), the tone branch, the colour branch and the values of all three colour members (only the
+    drawn branch's are used)."""
+    context: np.ndarray          # (B,) float64
+    jitter: np.ndarray           # (B, 4) float64
+    tone: np.ndarray             # (B,) int32, TONE_*
+    colour: np.ndarray           # (B,) int32, COLOUR_*
+    alpha: np.ndarray            # (B,) contrast
+    beta: np.ndarray             # (B,) brightness
+    gamma: np.ndarray            # (B,)
+    shift: np.ndarray            # (B, 3) RGB shift
+    frame_shapes: Tuple[Tuple[int, int], ...]
+    photo: Optional[PhotoParams] = None      # the photometric draws, None with the stage off
+    # the values of the members `colour_members` adds, each None unless its member is configured
+    tone_curve: Optional[np.ndarray] = None      # (B, 2) low_y, high_y
+    hsv: Optional[np.ndarray] = None             # (B, 3) hue, saturation and value shifts
+    colour_jitter: Optional[np.ndarray] = None   # (B, 4) ColorJitter's brightness, contrast, saturation factors and hue shift
+    colour_jitter_order: Optional[np.ndarray] = None   # (B, 4) int32, a permutation of JITTER_* per pair
+    emboss: Optional[np.ndarray] = None          # (B, 2) alpha, strength
+    # ImageCompression's quality per crop, (B, 2) int32 like the arrays of `photo`; None unless "jpeg" is a configured noise member and
+    # the photometric stage is on
+    jpeg_quality: Optional[np.ndarray] = None
+
+
+def _pairs_array(pairs) -> np.ndarray:
+    p = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
+    p = np.asarray(p, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != len(PAIR_COLUMNS):
+        raise ValueError(f"pairs must be (B, {len(PAIR_COLUMNS)}): {', '.join(PAIR_COLUMNS)}")
+    return p
+
+
+__all__ = [name for name in dir() if name.isupper()] + ["PhotoParams", "TrainPairParams", "TrainBatch"]     # (every constant above)

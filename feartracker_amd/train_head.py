@@ -23,7 +23,7 @@ import torch
 
 # (the declaration of the training ABI lives in train_abi; its names stay importable from this module)
 from .train_abi import (FEAR_SYNC_BUF_BYTES, TRAIN_SYMBOLS, FearBnRunning, FearIrbBlock, FearIrbGrads, FearIrbSaved,  # noqa: F401
-                        FearSepGrads, FearSepLayer, FearSync, TrainError, _ALLREDUCE_FN, _p, load_train_library)
+                        FearSepGrads, FearSepLayer, FearSync, TrainError, _ALLREDUCE_FN, _p, launch, load_train_library)
 
 
 class GradDict(dict):
@@ -119,9 +119,7 @@ class SyncHook:
                         fs = FearSync(hook._cb, None, buf.data_ptr(), FEAR_SYNC_BUF_BYTES, int(hook.sync.world))
                         slot = hook._slots[h] = [st, buf, fs, 0]
                     if slot[3] == 0:
-                        rc = hook.lib.fear_train_sync_bind(ctypes.c_void_p(h), ctypes.byref(slot[2]))
-                        if rc != 0:
-                            raise TrainError(f"fear_train_sync_bind failed with status {rc}")
+                        launch(hook.lib, "fear_train_sync_bind", ctypes.c_void_p(h), ctypes.byref(slot[2]))
                     slot[3] += 1
                     self_inner.handles.append(h)
                 return hook

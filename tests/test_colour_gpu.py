@@ -1,21 +1,18 @@
 """The colour members that are no lookup table on the GPU (include/fear_train.h: fear_colour_u8): the operator through the C ABI, bit for
 bit against `colour_u8_host`, and `TrainPairBuilder` with `colour_members` against `build_host` and against the two-launch path."""
-import ctypes
 import itertools
 
 import numpy as np
 import pytest
 import torch
 
+from dataops import P, SENTINEL_U8 as SENTINEL, equal as _equal, frames as _frames, pairs as _pairs, run_colour as _run
 from feartracker_amd.train_data import (BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_NONE, COLOUR_DTYPE, COLOUR_EMBOSS, COLOUR_EQUALIZE, COLOUR_HSV,
                                         COLOUR_JITTER, COLOUR_TONE_CURVE, FRAME_DTYPE, NOISE_GAUSS, NOISE_NONE, TrainPairBuilder,
                                         TrainPairParams, colour_tables, colour_u8_host)
 
 pytestmark = pytest.mark.gpu
 
-P = ctypes.c_void_p
-GUARD = 4096                       # bytes of sentinel on either side of the output
-SENTINEL = 0xA5
 SHAPES = [(4, 4), (8, 8), (34, 70), (128, 128), (256, 256)]
 
 
@@ -46,24 +43,6 @@ def _records(kinds, seed=0):
                              colour_jitter_order=rng.permuted(np.tile(np.arange(4, dtype=np.int32), (n, 1)), axis=1),
                              emboss=np.stack([rng.uniform(0.2, 0.5, n), rng.uniform(0.2, 0.7, n)], axis=1))
     return (params,) + colour_tables(params)
-
-
-def _run(lib, crops, ops, aux):
-    """fear_colour_u8 on (n, H, W, 3) uint8 crops, the guard band around the output checked."""
-    n, h, w = crops.shape[:3]
-    d_in = torch.from_numpy(np.ascontiguousarray(crops)).cuda()
-    d_ops = torch.from_numpy(ops.view(np.uint8).copy()).cuda()
-    d_aux = torch.from_numpy(np.ascontiguousarray(aux)).cuda()
-    count = n * h * w * 3
-    buf = torch.full((count + 2 * GUARD,), SENTINEL, dtype=torch.uint8, device="cuda")
-    rc = lib.fear_colour_u8(P(d_in.data_ptr()), n, h, w, P(d_ops.data_ptr()), P(d_aux.data_ptr()), P(buf.data_ptr() + GUARD),
-                            P(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0
-    torch.cuda.synchronize()
-    out = buf.cpu().numpy()
-    assert np.all(out[:GUARD] == SENTINEL) and np.all(out[GUARD + count:] == SENTINEL), "guard band written"
-    assert np.array_equal(d_in.cpu().numpy(), crops), "input written"
-    return out[GUARD:GUARD + count].reshape(n, h, w, 3)
 
 
 def _check(lib, crops, ops, aux):
@@ -159,39 +138,6 @@ def test_argument_checks(lib):
 
 
 # ----------------------------------------------------------------------------------------------------------------------- builder
-def _frames(seed=0):
-    rng = np.random.default_rng(seed)
-    out = []
-    for h, w in ((48, 64), (256, 480)):
-        yy, xx = np.mgrid[0:h, 0:w]
-        base = np.stack([xx * 255 // (w - 1), yy * 255 // (h - 1), (xx + yy) % 256], axis=-1)
-        out.append(np.clip(base + rng.integers(0, 64, (h, w, 3)) - 32, 0, 255).astype(np.uint8))
-    return out
-
-
-def _pairs(B, seed=1):
-    rng = np.random.default_rng(seed)
-    p = np.zeros((B, 11))
-    for k in range(B):
-        for col, f in ((0, k % 2), (5, (k + 1) % 2)):
-            h, w = ((48, 64), (256, 480))[f]
-            bw, bh = rng.integers(4, w // 3), rng.integers(4, h // 3)
-            p[k, col:col + 5] = [f, rng.integers(0, w - bw + 1), rng.integers(0, h - bh + 1), bw, bh]
-        p[k, 10] = 1
-    return p
-
-
-def _equal(dev, host):
-    for name in ("template", "search", "gt_reg", "gt_cls", "gt_weight", "search_bbox"):
-        d = getattr(dev, name)
-        d = d.cpu().numpy() if isinstance(d, torch.Tensor) else d
-        h = getattr(host, name)
-        h = h.cpu().numpy() if isinstance(h, torch.Tensor) else h
-        assert d.shape == h.shape and d.dtype == h.dtype, name
-        bad = np.argwhere(d != h)
-        assert bad.size == 0, f"{name}: {len(bad)} values differ, first at {bad[:3].tolist()}"
-
-
 @pytest.mark.parametrize("photometric", [False, True])
 def test_all_members_build_equals_build_host(photometric):
     """B = 8, every member once (the tone-curve member runs here only: it is a table of the first stage), every tone branch."""

@@ -1,4 +1,4 @@
-"""The colour members behind `colour_members` on the host (feartracker_amd/train_data.py): each restatement of
+"""The colour members behind `colour_members` on the host (feartracker_amd/train_data/colour.py): each restatement of
 `colour_u8_host` against an independent formulation, and the draws.  The references here are written out in this file; none of them is
 the code under test."""
 import dataclasses

@@ -1,22 +1,19 @@
 """ImageCompression on the GPU (include/fear_train.h: fear_jpeg_u8, fear_photometric_stage_u8): the operators through the C ABI, bit for
 bit against `jpeg_roundtrip_u8_host` and `photometric_u8_host`, and `TrainPairBuilder` with crops that drew the member against
 `build_host`."""
-import ctypes
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from dataops import P, SENTINEL_U8 as SENTINEL, equal as _equal, frames as _frames, pairs as _pairs, run_jpeg as _run_jpeg, run_stage as _run_stage
 from feartracker_amd.train_data import (BLUR_BOX, BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_MOTION, BLUR_NONE, NOISE_GAUSS, NOISE_JPEG,
                                         NOISE_MULTIPLICATIVE, NOISE_NONE, PHOTO_DTYPE, TrainPairBuilder, jpeg_roundtrip_u8_host,
                                         motion_kernel, motion_taps, normal_quantiles, photometric_u8_host)
 
 pytestmark = pytest.mark.gpu
 
-P = ctypes.c_void_p
-GUARD = 4096                       # bytes of sentinel on either side of the output and of the workspace
-SENTINEL = 0xA5
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jpeg_roundtrip.npz")
 
 
@@ -29,33 +26,6 @@ def lib():
 @pytest.fixture(scope="module")
 def qtable():
     return torch.from_numpy(normal_quantiles().copy()).cuda()
-
-
-def _guarded(count):
-    return torch.full((count + 2 * GUARD,), SENTINEL, dtype=torch.uint8, device="cuda")
-
-
-def _inside(buf, count, what):
-    host = buf.cpu().numpy()
-    assert np.all(host[:GUARD] == SENTINEL) and np.all(host[GUARD + count:] == SENTINEL), f"guard band of the {what} written"
-    return host[GUARD:GUARD + count]
-
-
-def _run_jpeg(lib, crops, quality):
-    """fear_jpeg_u8 on (n, H, W, 3) uint8 crops and (n,) qualities, the guard bands around the output and the workspace checked."""
-    n, h, w = crops.shape[:3]
-    d_in = torch.from_numpy(np.ascontiguousarray(crops)).cuda()
-    d_q = torch.from_numpy(np.asarray(quality, dtype=np.int32)).cuda()
-    count = n * h * w * 3
-    ws_bytes = lib.fear_jpeg_workspace_bytes(n, h, w)
-    assert ws_bytes >= n * h * w * 3 // 2
-    out, ws = _guarded(count), _guarded(ws_bytes)
-    rc = lib.fear_jpeg_u8(P(d_in.data_ptr()), n, h, w, P(d_q.data_ptr()), P(ws.data_ptr() + GUARD), ws_bytes, P(out.data_ptr() + GUARD),
-                          P(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0
-    torch.cuda.synchronize()
-    _inside(ws, ws_bytes, "workspace")
-    return _inside(out, count, "output").reshape(n, h, w, 3)
 
 
 def _check_jpeg(lib, crops, quality):
@@ -165,20 +135,6 @@ def _chain_records(seed):
     return ops, taps
 
 
-def _run_stage(lib, qtable, crops, ops, taps):
-    n, h, w = crops.shape[:3]
-    d_in = torch.from_numpy(np.ascontiguousarray(crops)).cuda()
-    d_ops = torch.from_numpy(ops.view(np.uint8).copy()).cuda()
-    d_taps = torch.from_numpy(taps.copy()).cuda() if taps is not None else None
-    count = n * h * w * 3
-    out = _guarded(count)
-    rc = lib.fear_photometric_stage_u8(P(d_in.data_ptr()), n, h, w, P(d_ops.data_ptr()), P(d_taps.data_ptr()) if d_taps is not None else None,
-                                       P(qtable.data_ptr()), P(out.data_ptr() + GUARD), P(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0
-    torch.cuda.synchronize()
-    return _inside(out, count, "output").reshape(n, h, w, 3)
-
-
 @pytest.mark.parametrize("shape", [(8, 8), (34, 70)])
 def test_stage_u8_equals_photometric_u8_host(lib, qtable, shape):
     ops, taps = _chain_records(shape[0])
@@ -219,39 +175,6 @@ def test_stage_u8_argument_checks(lib, qtable):
 
 
 # ----------------------------------------------------------------------------------------------------------------------- builder
-def _frames(seed=0):
-    rng = np.random.default_rng(seed)
-    out = []
-    for h, w in ((48, 64), (256, 480)):
-        yy, xx = np.mgrid[0:h, 0:w]
-        base = np.stack([xx * 255 // (w - 1), yy * 255 // (h - 1), (xx + yy) % 256], axis=-1)
-        out.append(np.clip(base + rng.integers(0, 64, (h, w, 3)) - 32, 0, 255).astype(np.uint8))
-    return out
-
-
-def _pairs(B, seed=1):
-    rng = np.random.default_rng(seed)
-    p = np.zeros((B, 11))
-    for k in range(B):
-        for col, f in ((0, k % 2), (5, (k + 1) % 2)):
-            h, w = ((48, 64), (256, 480))[f]
-            bw, bh = rng.integers(4, w // 3), rng.integers(4, h // 3)
-            p[k, col:col + 5] = [f, rng.integers(0, w - bw + 1), rng.integers(0, h - bh + 1), bw, bh]
-        p[k, 10] = 1
-    return p
-
-
-def _equal(dev, host):
-    for name in ("template", "search", "gt_reg", "gt_cls", "gt_weight", "search_bbox"):
-        d = getattr(dev, name)
-        d = d.cpu().numpy() if isinstance(d, torch.Tensor) else d
-        h = getattr(host, name)
-        h = h.cpu().numpy() if isinstance(h, torch.Tensor) else h
-        assert d.shape == h.shape and d.dtype == h.dtype, name
-        bad = np.argwhere(d != h)
-        assert bad.size == 0, f"{name}: {len(bad)} values differ, first at {bad[:3].tolist()}"
-
-
 def _forced_params(builder, frames, pairs, seed):
     """B = 8 draws with ImageCompression forced on some crops — a blur in front and a Downscale behind among them — while the other
     crops keep chains of their own."""

@@ -1,20 +1,16 @@
 """The photometric stage on the GPU (include/fear_train.h: fear_photometric_u8, fear_train_pairs_u8): the operator through the C ABI,
 bit for bit against `photometric_host`, and `TrainPairBuilder` with the stage on against the stage-less path and `build_host`."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
+from dataops import P, SENTINEL_F32 as SENTINEL, equal as _equal, frames as _frames, pairs as _pairs, run_photometric as _run
 from feartracker_amd.train_data import (BLUR_BOX, BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_MOTION, BLUR_NONE, NOISE_GAUSS, NOISE_MULTIPLICATIVE,
                                         NOISE_NONE, PHOTO_DTYPE, TrainPairBuilder, motion_kernel, motion_taps, normal_quantiles,
                                         photometric_host)
 
 pytestmark = pytest.mark.gpu
 
-P = ctypes.c_void_p
-GUARD = 4096                       # floats of sentinel on either side of the output
-SENTINEL = -12345.0
 SMALL_SHAPES = [(4, 4), (8, 8), (34, 70)]
 
 
@@ -54,24 +50,6 @@ def _taps_for(ops, lines):
         ops["tap_row"][i] = row
         taps[row] = motion_taps(motion_kernel(int(ops["ksize"][i]), *lines[i]))
     return taps if len(rows) else None
-
-
-def _run(lib, qtable, crops, ops, taps):
-    """fear_photometric_u8 on (n, H, W, 3) uint8 crops -> (n, 3, H, W) fp32, the guard band around the output checked."""
-    n, h, w = crops.shape[:3]
-    d_in = torch.from_numpy(np.ascontiguousarray(crops)).cuda()
-    d_ops = torch.from_numpy(ops.view(np.uint8).copy()).cuda()
-    d_taps = torch.from_numpy(taps.copy()).cuda() if taps is not None else None
-    count = n * 3 * h * w
-    buf = torch.full((count + 2 * GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
-    st = P(torch.cuda.current_stream().cuda_stream)
-    rc = lib.fear_photometric_u8(P(d_in.data_ptr()), n, h, w, P(d_ops.data_ptr()), P(d_taps.data_ptr()) if d_taps is not None else None,
-                                 P(qtable.data_ptr()), P(buf.data_ptr() + 4 * GUARD), st)
-    assert rc == 0
-    torch.cuda.synchronize()
-    out = buf.cpu().numpy()
-    assert np.all(out[:GUARD] == np.float32(SENTINEL)) and np.all(out[GUARD + count:] == np.float32(SENTINEL)), "guard band written"
-    return out[GUARD:GUARD + count].reshape(n, 3, h, w)
 
 
 def _check(lib, qtable, crops, ops, taps):
@@ -185,39 +163,6 @@ def test_argument_checks(lib, qtable):
 
 
 # ----------------------------------------------------------------------------------------------------------------------- builder
-def _frames(seed=0):
-    rng = np.random.default_rng(seed)
-    out = []
-    for h, w in ((48, 64), (256, 480)):
-        yy, xx = np.mgrid[0:h, 0:w]
-        base = np.stack([xx * 255 // (w - 1), yy * 255 // (h - 1), (xx + yy) % 256], axis=-1)
-        out.append(np.clip(base + rng.integers(0, 64, (h, w, 3)) - 32, 0, 255).astype(np.uint8))
-    return out
-
-
-def _pairs(B, seed=1):
-    rng = np.random.default_rng(seed)
-    p = np.zeros((B, 11))
-    for k in range(B):
-        for col, f in ((0, k % 2), (5, (k + 1) % 2)):
-            h, w = ((48, 64), (256, 480))[f]
-            bw, bh = rng.integers(4, w // 3), rng.integers(4, h // 3)
-            p[k, col:col + 5] = [f, rng.integers(0, w - bw + 1), rng.integers(0, h - bh + 1), bw, bh]
-        p[k, 10] = 1
-    return p
-
-
-def _equal(dev, host):
-    for name in ("template", "search", "gt_reg", "gt_cls", "gt_weight", "search_bbox"):
-        d = getattr(dev, name)
-        d = d.cpu().numpy() if isinstance(d, torch.Tensor) else d
-        h = getattr(host, name)
-        h = h.cpu().numpy() if isinstance(h, torch.Tensor) else h
-        assert d.shape == h.shape and d.dtype == h.dtype, name
-        bad = np.argwhere(d != h)
-        assert bad.size == 0, f"{name}: {len(bad)} values differ, first at {bad[:3].tolist()}"
-
-
 def test_all_none_equals_the_stage_less_path():
     """fear_train_pairs_u8 + fear_photometric_u8 with "none" records against fear_train_pairs: the same draws, every tone branch."""
     frames = _frames(1)

@@ -1,4 +1,4 @@
-"""The photometric stage's host side (feartracker_amd/train_data.py): Philox against the Random123 known
+"""The photometric stage's host side (feartracker_amd/train_data/photometric.py): Philox against the Random123 known
 answers, every member of `photometric_u8_host` against an independent formulation, GaussNoise's statistics, and the draws."""
 import ctypes
 

@@ -1,4 +1,4 @@
-"""Host side of the training-pair builder (feartracker_amd/train_data.py): geometry and targets against the reference's own Python
+"""Host side of the training-pair builder (feartracker_amd/train_data/): geometry and targets against the reference's own Python
 (tests/golden/train_pairs_geometry.npz, tools/make_train_pairs_golden.py), the vectorised warpAffine against an independent
 scalar restatement of OpenCV's remap, and the colour draws.  No GPU."""
 import os

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the training-pair builder (feartracker_amd/train_data.py) on one GPU.
+"""Cost of the training-pair builder (feartracker_amd/train_data/) on one GPU.
 
 Reports, for 128 pairs out of 1080p device frames (two frames of their own per pair: 256 distinct frames, the most the frame means
 can cost):
