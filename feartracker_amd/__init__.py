@@ -2,7 +2,8 @@
 
 Hot path only: `FEARTracker.initialize()/update()` — and `FEARMultiTracker` for many targets per frame — on top of
 `FEARNetHIP.get_features()/track()`, whose arithmetic runs in hand-written gfx950 HIP kernels
-behind the C ABI of include/fear_hip.h.  Both trackers take packed RGB frames or NV12 / I420 video frames (`YUVFrame`).
+behind the C ABI of include/fear_hip.h.  Both trackers take packed RGB frames or NV12 / I420 video frames (`YUVFrame`);
+`JpegDecoder` decodes baseline JPEG files into such RGB frames on the device.
 """
 from .constants import DEFAULT_TRACKING_CONFIG, TARGET_CLASSIFICATION_KEY, TARGET_REGRESSION_LABEL_KEY
 from .box_coder import FEARBoxCoder, TrackerDecodeResult, TrackerEncodeResult
@@ -10,10 +11,12 @@ from .frames import YUVFrame
 from .tracker import FEARTracker, Tracker, TrackingState
 from .multi_tracker import FEARMultiTracker, PendingBoxes
 from .hip_backend import FEARNetHIP, FearError, load_library, DEFAULT_WEIGHTS, LIB_PATH
+from .jpeg_frames import JpegDecoder, MalformedJPEG, UnsupportedJPEG, jpeg_decode_host, jpeg_info
 
 __all__ = [
     "DEFAULT_TRACKING_CONFIG", "TARGET_CLASSIFICATION_KEY", "TARGET_REGRESSION_LABEL_KEY",
     "FEARBoxCoder", "TrackerDecodeResult", "TrackerEncodeResult", "FEARTracker", "Tracker", "TrackingState",
     "FEARMultiTracker", "PendingBoxes", "YUVFrame",
     "FEARNetHIP", "FearError", "load_library", "DEFAULT_WEIGHTS", "LIB_PATH",
+    "JpegDecoder", "MalformedJPEG", "UnsupportedJPEG", "jpeg_decode_host", "jpeg_info",
 ]

@@ -1,0 +1,455 @@
+"""Baseline JPEG frames decoded for the training and validation pipelines.
+
+`jpeg_decode_host` is the contract: a numpy and pure-Python decoder of baseline sequential JPEG that equals libjpeg with its defaults
+(islow IDCT, fancy upsampling — what the reference's cv2.imread runs) byte for byte; tests/test_jpeg_decode_host.py holds it to Pillow's
+libjpeg-turbo.  `JpegDecoder` is the product: the parser and the Huffman stage run on host threads in the library
+(csrc/fear_jpeg_entropy.h), the packed coefficients go up in one transfer and `fear_jpeg_decode_u8` does the rest on the device."""
+from __future__ import annotations
+
+import ctypes
+import os
+from concurrent.futures import ThreadPoolExecutor
+from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from .train_data.jpeg import _jpeg_upsample, jpeg_idct_islow
+
+MAX_SIDE = 8192
+ERR_FORMAT, ERR_UNSUPPORTED = -9, -10     # include/fear_train.h FEAR_TRAIN_ERR_FORMAT, FEAR_TRAIN_ERR_UNSUPPORTED
+
+# zigzag position -> natural (row-major) index
+ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
+
+
+class MalformedJPEG(ValueError):
+    """The bytes are no complete baseline JPEG: truncated, a code in no table, a bad restart marker, a bad segment."""
+
+
+class UnsupportedJPEG(ValueError):
+    """A valid JPEG of a kind the decoder declines: progressive, arithmetic, 12-bit, other sampling factors, 2 or 4 components, RGB."""
+
+
+# ------------------------------------------------------------------------------------------------------------------ the host contract
+class _Huffman:
+    """One table of a DHT segment: canonical codes of T.81 annex C, decoded bit by bit (F.2.2.3)."""
+
+    def __init__(self, counts: Sequence[int], values: bytes):
+        self.first, self.index, self.counts, self.values = [0] * 17, [0] * 17, [0] + list(counts), values
+        code = k = 0
+        for length in range(1, 17):
+            self.first[length], self.index[length] = code, k
+            if code + self.counts[length] > (1 << length):
+                raise MalformedJPEG(f"over-subscribed Huffman table at code length {length}")
+            code = (code + self.counts[length]) << 1
+            k += self.counts[length]
+
+
+class _Header:
+    pass
+
+
+def _parse(data: bytes) -> _Header:
+    """The segments up to and including SOS.  Mirrors csrc/fear_jpeg_entropy.h check for check, in the same order."""
+    n = len(data)
+    if n < 2 or data[0] != 0xFF or data[1] != 0xD8:
+        raise MalformedJPEG("no SOI marker")
+    hd = _Header()
+    hd.q, hd.dc, hd.ac, hd.restart, hd.adobe, sof = {}, {}, {}, 0, -1, False
+    p = 2
+    while True:
+        if p >= n or data[p] != 0xFF:
+            raise MalformedJPEG("a marker was expected" if p < n else "truncated before the scan")
+        while p < n and data[p] == 0xFF:            # fill bytes
+            p += 1
+        if p >= n:
+            raise MalformedJPEG("truncated in a marker")
+        m = data[p]
+        p += 1
+        if m == 0x01:                               # TEM stands alone
+            continue
+        if m == 0x00 or 0xD0 <= m <= 0xD9:
+            raise MalformedJPEG(f"marker FF{m:02X} in front of the scan")
+        if p + 2 > n:
+            raise MalformedJPEG("truncated in a segment length")
+        L = (data[p] << 8) | data[p + 1]
+        if L < 2 or p + L > n:
+            raise MalformedJPEG("a segment length runs past the end")
+        seg = data[p + 2:p + L]
+        p += L
+        if m == 0xC0:
+            if sof:
+                raise MalformedJPEG("a second frame header")
+            if len(seg) < 6:
+                raise MalformedJPEG("short SOF0")
+            if seg[0] != 8:
+                raise UnsupportedJPEG(f"{seg[0]}-bit samples")
+            hd.height, hd.width, nf = (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
+            if hd.width == 0:
+                raise MalformedJPEG("zero width")
+            if hd.height == 0:
+                raise UnsupportedJPEG("zero height: the frame's height comes in a DNL segment")
+            if hd.width > MAX_SIDE or hd.height > MAX_SIDE:
+                raise UnsupportedJPEG(f"sides above {MAX_SIDE}")
+            if nf == 0:
+                raise MalformedJPEG("a frame without components")
+            if nf not in (1, 3):
+                raise UnsupportedJPEG(f"{nf} components")
+            if len(seg) != 6 + 3 * nf:
+                raise MalformedJPEG("SOF0 length")
+            hd.ids, hd.h, hd.v, hd.tq = [], [], [], []
+            for i in range(nf):
+                cid, hv, tq = seg[6 + 3 * i:9 + 3 * i]
+                h, v = hv >> 4, hv & 15
+                if not (1 <= h <= 4 and 1 <= v <= 4) or tq > 3 or cid in hd.ids:
+                    raise MalformedJPEG("a component's sampling factors, table or id")
+                hd.ids.append(cid); hd.h.append(h); hd.v.append(v); hd.tq.append(tq)
+            if nf == 1:
+                hd.h, hd.v = [1], [1]               # one component: the scan is not interleaved, its sampling factors mean nothing
+            elif (hd.h[0], hd.v[0]) not in ((1, 1), (2, 1), (2, 2)) or (hd.h[1], hd.v[1], hd.h[2], hd.v[2]) != (1, 1, 1, 1):
+                raise UnsupportedJPEG("sampling factors other than 4:4:4, 4:2:2 and 4:2:0")
+            sof = True
+        elif 0xC1 <= m <= 0xCF and m not in (0xC4, 0xCC):
+            raise UnsupportedJPEG({0xC1: "extended sequential", 0xC2: "progressive"}.get(m, f"SOF{m - 0xC0}") + " frame")
+        elif m == 0xCC:
+            raise UnsupportedJPEG("arithmetic coding")
+        elif m == 0xC4:
+            s = 0
+            while s < len(seg):
+                tc, th = seg[s] >> 4, seg[s] & 15
+                if tc > 1 or th > 3 or s + 17 > len(seg):
+                    raise MalformedJPEG("DHT header")
+                counts = list(seg[s + 1:s + 17])
+                total = sum(counts)
+                if total > 256 or s + 17 + total > len(seg):
+                    raise MalformedJPEG("DHT symbol count")
+                (hd.ac if tc else hd.dc)[th] = _Huffman(counts, seg[s + 17:s + 17 + total])
+                s += 17 + total
+        elif m == 0xDB:
+            s = 0
+            while s < len(seg):
+                pq, tq = seg[s] >> 4, seg[s] & 15
+                if pq == 1:
+                    raise UnsupportedJPEG("16-bit quantiser table")
+                if pq > 1 or tq > 3 or s + 65 > len(seg):
+                    raise MalformedJPEG("DQT header")
+                table = np.zeros(64, dtype=np.int64)
+                table[ZIGZAG] = np.frombuffer(seg[s + 1:s + 65], dtype=np.uint8)
+                hd.q[tq] = table
+                s += 65
+        elif m == 0xDD:
+            if len(seg) != 2:
+                raise MalformedJPEG("DRI length")
+            hd.restart = (seg[0] << 8) | seg[1]
+        elif m == 0xDC:
+            raise UnsupportedJPEG("DNL segment")
+        elif m == 0xEE:
+            if len(seg) >= 12 and seg[:5] == b"Adobe":
+                hd.adobe = seg[11]
+        elif m == 0xDA:
+            if not sof:
+                raise MalformedJPEG("SOS in front of SOF")
+            nf = len(hd.ids)
+            if len(seg) < 1 or seg[0] == 0 or seg[0] > 4:
+                raise MalformedJPEG("SOS component count")
+            if seg[0] != nf:
+                raise UnsupportedJPEG("a scan with part of the components (a second scan follows)")
+            if len(seg) != 4 + 2 * nf:
+                raise MalformedJPEG("SOS length")
+            hd.td, hd.ta = [], []
+            for i in range(nf):
+                cs, t = seg[1 + 2 * i], seg[2 + 2 * i]
+                if cs != hd.ids[i]:
+                    if cs in hd.ids:
+                        raise UnsupportedJPEG("scan components out of frame order")
+                    raise MalformedJPEG("a scan component the frame does not have")
+                if (t >> 4) > 3 or (t & 15) > 3:
+                    raise MalformedJPEG("Huffman table selector")
+                hd.td.append(t >> 4); hd.ta.append(t & 15)
+            if tuple(seg[1 + 2 * nf:4 + 2 * nf]) != (0, 63, 0):
+                raise MalformedJPEG("spectral selection of a baseline scan")
+            if nf == 3 and hd.adobe == 0:
+                raise UnsupportedJPEG("Adobe transform 0: RGB samples")
+            for i in range(nf):
+                if hd.tq[i] not in hd.q or hd.td[i] not in hd.dc or hd.ta[i] not in hd.ac:
+                    raise MalformedJPEG("a component selects a table no segment defined")
+            hd.scan = p
+            break
+        # APPn, COM and the reserved markers carry nothing the decoder needs
+    hd.mcus_x = -(-hd.width // (8 * hd.h[0]))
+    hd.mcus_y = -(-hd.height // (8 * hd.v[0]))
+    hd.blocks_w = [hd.mcus_x * h for h in hd.h]
+    hd.blocks_h = [hd.mcus_y * v for v in hd.v]
+    return hd
+
+
+def jpeg_info(data: bytes) -> Dict[str, object]:
+    """What the frame and scan headers say: size, components, sampling, block and MCU counts, restart interval, quantiser tables."""
+    hd = _parse(bytes(data))
+    return dict(width=hd.width, height=hd.height, components=len(hd.ids), h=list(hd.h), v=list(hd.v), mcus_x=hd.mcus_x, mcus_y=hd.mcus_y,
+                blocks_w=list(hd.blocks_w), blocks_h=list(hd.blocks_h), restart_interval=hd.restart,
+                qt=np.stack([hd.q[t] for t in hd.tq]).astype(np.uint16))
+
+
+class _Bits:
+    """The entropy-coded segment bit by bit: FF 00 is a data byte FF, any other FF xx ends the data."""
+
+    def __init__(self, data: bytes, pos: int):
+        self.data, self.pos, self.cur, self.left = data, pos, 0, 0
+
+    def bit(self) -> int:
+        if self.left == 0:
+            d, p = self.data, self.pos
+            if p >= len(d):
+                raise MalformedJPEG("truncated entropy data")
+            self.cur = d[p]
+            if self.cur == 0xFF:
+                if p + 1 >= len(d):
+                    raise MalformedJPEG("truncated entropy data")
+                if d[p + 1] != 0:
+                    raise MalformedJPEG(f"marker FF{d[p + 1]:02X} inside an MCU")
+                p += 1
+            self.pos, self.left = p + 1, 8
+        self.left -= 1
+        return (self.cur >> self.left) & 1
+
+    def bits(self, count: int) -> int:
+        v = 0
+        for _ in range(count):
+            v = (v << 1) | self.bit()
+        return v
+
+    def symbol(self, t: _Huffman) -> int:
+        code = 0
+        for length in range(1, 17):
+            code = (code << 1) | self.bit()
+            k = code - t.first[length]
+            if 0 <= k < t.counts[length]:
+                return t.values[t.index[length] + k]
+        raise MalformedJPEG("a code in no Huffman table")
+
+    def restart(self, expected: int) -> None:
+        self.left = 0                               # the rest of the byte is padding
+        d, p = self.data, self.pos
+        if p + 1 >= len(d) or d[p] != 0xFF or d[p + 1] != 0xD0 + expected:
+            raise MalformedJPEG("a restart marker is missing or out of order")
+        self.pos = p + 2
+
+
+def _extend(v: int, t: int) -> int:
+    return v if t == 0 or v >= (1 << (t - 1)) else v - (1 << t) + 1
+
+
+def _wrap16(v: int) -> int:
+    return ((v + 32768) & 0xFFFF) - 32768
+
+
+def jpeg_coefficients_host(data: bytes) -> Tuple[_Header, List[np.ndarray]]:
+    """Headers and, per component, the quantised coefficients (blocks_h, blocks_w, 64) int16 in zigzag order (T.81 F.2)."""
+    data = bytes(data)
+    hd = _parse(data)
+    nf = len(hd.ids)
+    coef = [np.zeros((hd.blocks_h[c], hd.blocks_w[c], 64), dtype=np.int16) for c in range(nf)]
+    bits, pred = _Bits(data, hd.scan), [0] * nf
+    for mcu in range(hd.mcus_x * hd.mcus_y):
+        if hd.restart and mcu and mcu % hd.restart == 0:
+            bits.restart((mcu // hd.restart - 1) & 7)
+            pred = [0] * nf
+        my, mx = divmod(mcu, hd.mcus_x)
+        for c in range(nf):
+            dc, ac = hd.dc[hd.td[c]], hd.ac[hd.ta[c]]
+            for j in range(hd.v[c]):
+                for i in range(hd.h[c]):
+                    block = coef[c][my * hd.v[c] + j, mx * hd.h[c] + i]
+                    t = bits.symbol(dc)
+                    if t > 15:
+                        raise MalformedJPEG("a DC size above 15")
+                    pred[c] = _wrap16(pred[c] + _extend(bits.bits(t), t))          # JCOEF is 16 bits wide
+                    block[0] = pred[c]
+                    k = 1
+                    while k < 64:
+                        rs = bits.symbol(ac)
+                        r, s = rs >> 4, rs & 15
+                        if s == 0:
+                            if r != 15:
+                                break                                              # EOB
+                            k += 16                                                # ZRL: a coefficient follows
+                            if k > 63:
+                                raise MalformedJPEG("a coefficient index past 63")
+                            continue
+                        k += r
+                        if k > 63:
+                            raise MalformedJPEG("a coefficient index past 63")
+                        block[k] = _extend(bits.bits(s), s)
+                        k += 1
+    return hd, coef
+
+
+def _upsample_h2v1(c: np.ndarray) -> np.ndarray:
+    left, right = np.concatenate([c[:, :1], c[:, :-1]], axis=1), np.concatenate([c[:, 1:], c[:, -1:]], axis=1)
+    return np.stack([(3 * c + left + 1) >> 2, (3 * c + right + 2) >> 2], axis=2).reshape(c.shape[0], 2 * c.shape[1])
+
+
+def jpeg_decode_host(data: bytes) -> np.ndarray:
+    """A baseline JPEG file -> uint8 (H, W, 3) RGB, as libjpeg decodes it with its defaults.  Slow; the statement the device is held to."""
+    hd, coef = jpeg_coefficients_host(data)
+    H, W, nf = hd.height, hd.width, len(hd.ids)
+    planes = []
+    for c in range(nf):
+        q = hd.q[hd.tq[c]]
+        nat = np.zeros(coef[c].shape, dtype=np.int64)
+        nat[..., ZIGZAG] = coef[c]
+        bh, bw = coef[c].shape[:2]
+        px = np.clip(jpeg_idct_islow((nat * q).reshape(bh, bw, 8, 8)) + 128, 0, 255)
+        plane = px.transpose(0, 2, 1, 3).reshape(bh * 8, bw * 8)
+        ch, cw = -(-H * hd.v[c] // hd.v[0]), -(-W * hd.h[c] // hd.h[0])
+        plane = plane[:ch, :cw]                                                    # the true edges, not the padded blocks'
+        if hd.h[c] < hd.h[0]:
+            if cw <= 2:                                                            # libjpeg replicates planes this narrow
+                plane = np.repeat(plane, 2, axis=1) if hd.v[c] == hd.v[0] else np.repeat(np.repeat(plane, 2, axis=0), 2, axis=1)
+            else:
+                plane = _upsample_h2v1(plane) if hd.v[c] == hd.v[0] else _jpeg_upsample(plane)
+        planes.append(plane[:H, :W])
+    y = planes[0]
+    if nf == 1:
+        return np.repeat(y[..., None], 3, axis=2).astype(np.uint8)
+    cb, cr = planes[1] - 128, planes[2] - 128
+    r = y + ((91881 * cr + 32768) >> 16)
+    g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
+    b = y + ((116130 * cb + 32768) >> 16)
+    return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------------------------------ the product
+Item = Union[bytes, bytearray, memoryview, str, os.PathLike]
+
+
+def _raise_as_python(data: bytes, rc: int):
+    """The library's verdict as the exception of the Python decoder, whose message says which check it was."""
+    try:
+        jpeg_coefficients_host(data)
+    except (MalformedJPEG, UnsupportedJPEG) as exc:
+        if isinstance(exc, UnsupportedJPEG) == (rc == ERR_UNSUPPORTED):
+            raise
+    raise (UnsupportedJPEG if rc == ERR_UNSUPPORTED else MalformedJPEG)(f"the library declined the file with status {rc}")
+
+
+class JpegDecoder:
+    """Baseline JPEG files -> uint8 (H, W, 3) RGB device tensors, byte for byte what libjpeg (cv2.imread, Pillow) decodes.
+
+    `decode` parses and Huffman-decodes on `threads` host threads (the library's C++ through ctypes, which releases the GIL), packs the
+    coefficients of all images into one pinned buffer, uploads it non-blocking and runs `fear_jpeg_decode_u8` once.  It never waits for
+    the GPU.  The tensors go unchanged into `TrainPairBuilder.build`, `FEARMultiTracker` and `SequenceValidator`."""
+    MAX_THREADS = 16
+
+    def __init__(self, device: int = 0, threads: Optional[int] = None):
+        import torch
+        from .train_abi import load_train_library
+        if threads is None:
+            threads = min(8, len(os.sched_getaffinity(0)))            # the CPUs this process may use, never the machine's count
+        self.threads = max(1, min(int(threads), self.MAX_THREADS))
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        self._lib = load_train_library()
+        self._pool = ThreadPoolExecutor(max_workers=self.threads, thread_name_prefix="fear-jpeg")
+        self._pinned: List = []                                       # the last calls' staging buffers: each outlives its copy
+
+    def close(self) -> None:
+        self._pool.shutdown(wait=True)
+
+    def entropy_decode(self, data: bytes):
+        """One file through fear_jpeg_parse and fear_jpeg_entropy_decode: (FearJpegInfo, packed int16 coefficients, uint32 block_start),
+        or the library's status for a file it declines.  Host only."""
+        from .train_abi import FearJpegInfo
+        lib, info = self._lib, FearJpegInfo()
+        rc = lib.fear_jpeg_parse(data, len(data), ctypes.byref(info))
+        if rc != 0:
+            return rc
+        coef = np.empty(lib.fear_jpeg_packed_bound(ctypes.byref(info)), dtype=np.int16)
+        start = np.empty(info.total_blocks + 1, dtype=np.uint32)
+        used = ctypes.c_size_t(0)
+        rc = lib.fear_jpeg_entropy_decode(data, len(data), ctypes.byref(info), coef.ctypes.data, coef.size, start.ctypes.data, ctypes.byref(used))
+        if rc != 0:
+            return rc
+        return info, coef[:used.value], start
+
+    def decode(self, items: Sequence[Item], fallback: Optional[Callable[[bytes], np.ndarray]] = None) -> List:
+        import torch
+        from .train_abi import (FEAR_JPEG_GROUP_BLOCKS, FEAR_JPEG_GROUP_PIXELS, FearJpegImage, FearJpegInfo, launch)
+        from .train_data.staging import Staging
+        blobs = []
+        for item in items:
+            if isinstance(item, (bytes, bytearray, memoryview)):
+                blobs.append(bytes(item))
+            else:
+                with open(item, "rb") as fh:
+                    blobs.append(fh.read())
+        n_items = len(blobs)
+        if n_items == 0:
+            return []
+        # the host stage: every file is judged before anything is launched
+        decoded = list(self._pool.map(self.entropy_decode, blobs))
+        stage, jpegs, raw = Staging(), [], {}
+        for i, (data, res) in enumerate(zip(blobs, decoded)):
+            if isinstance(res, tuple):
+                jpegs.append(i)
+            elif res == ERR_UNSUPPORTED and fallback is not None:
+                px = np.ascontiguousarray(fallback(data))
+                if px.ndim != 3 or px.shape[2] != 3 or px.dtype != np.uint8:
+                    raise ValueError("the fallback must return uint8 (H, W, 3)")
+                raw[i] = px
+            else:
+                _raise_as_python(data, res)
+        n = len(jpegs)
+        if n > 65535:
+            raise ValueError("at most 65535 JPEG files per call")
+        records = (FearJpegImage * max(n, 1))()
+        infos = (FearJpegInfo * max(n, 1))()
+        prefix = np.zeros((2, n + 1), dtype=np.uint32)
+        out_at, out_bytes, plane_at = [], 0, 0
+        for k, i in enumerate(jpegs):
+            info, coef, start = decoded[i]
+            infos[k] = info
+            rec = records[k]
+            rec.width, rec.height, rec.components, rec.h, rec.v = info.width, info.height, info.components, info.h[0], info.v[0]
+            ctypes.memmove(rec.qt, info.qt, ctypes.sizeof(rec.qt))
+            rec.plane_offset = plane_at
+            plane_at += int(info.total_blocks) * 64
+            prefix[0, k + 1] = prefix[0, k] + -(-int(info.total_blocks) // FEAR_JPEG_GROUP_BLOCKS)
+            prefix[1, k + 1] = prefix[1, k] + -(-info.width * info.height // FEAR_JPEG_GROUP_PIXELS)
+            stage.add(f"coef{k}", coef)
+            stage.add(f"start{k}", start)
+            out_at.append(out_bytes)
+            out_bytes += -(-info.width * info.height * 3 // 16) * 16
+        for i, px in raw.items():
+            stage.add(f"raw{i}", px)
+        table = np.zeros(-(-prefix.nbytes // 16) * 16 + ctypes.sizeof(records), dtype=np.uint8)
+        table[:prefix.nbytes] = prefix.reshape(-1).view(np.uint8)
+        stage.add("table", table)
+        with torch.cuda.device(self.device):
+            pinned = torch.empty(stage.nbytes, dtype=torch.uint8, pin_memory=True)
+            dev = torch.empty(stage.nbytes, dtype=torch.uint8, device=self.device)
+            out = torch.empty(max(out_bytes, 16), dtype=torch.uint8, device=self.device)
+            base, out_base = dev.data_ptr(), out.data_ptr()
+            for k in range(n):
+                records[k].coef = base + stage.sections[f"coef{k}"][0]
+                records[k].block_start = base + stage.sections[f"start{k}"][0]
+                records[k].out = out_base + out_at[k]
+            if n:
+                table[-ctypes.sizeof(records):] = np.frombuffer(records, dtype=np.uint8)
+            stage.write(pinned.numpy())
+            dev.copy_(pinned, non_blocking=True)
+            self._pinned = self._pinned[-1:] + [pinned]
+            if n:
+                ws_bytes = self._lib.fear_jpeg_decode_workspace_bytes(infos, n)
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+                launch(self._lib, "fear_jpeg_decode_u8", records, n, ctypes.c_void_p(base + stage.sections["table"][0]),
+                       ctypes.c_void_p(ws.data_ptr()), ws_bytes, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        frames: List = [None] * n_items
+        for k, i in enumerate(jpegs):
+            h, w = records[k].height, records[k].width
+            frames[i] = out[out_at[k]:out_at[k] + h * w * 3].view(h, w, 3)
+        for i, px in raw.items():
+            at = stage.sections[f"raw{i}"][0]
+            frames[i] = dev[at:at + px.nbytes].view(px.shape)
+        return frames

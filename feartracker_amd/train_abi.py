@@ -85,6 +85,12 @@ TRAIN_SYMBOLS = {
     # ImageCompression: the JPEG round trip between the stage above and fear_photometric_u8
     "fear_jpeg_u8": ([_P, _i, _i, _i, _P, _P, _sz, _P, _P], _i),
     "fear_jpeg_workspace_bytes": ([_i, _i, _i], _sz),
+    # JPEG frames (jpeg_frames.JpegDecoder; FearJpegInfo and FearJpegImage below): the host's parser and Huffman stage, the device's rest
+    "fear_jpeg_parse": ([_P, _sz, _P], _i),
+    "fear_jpeg_packed_bound": ([_P], _sz),
+    "fear_jpeg_entropy_decode": ([_P, _sz, _P, _P, _sz, _P, _P], _i),
+    "fear_jpeg_decode_u8": ([_P, _i, _P, _P, _sz, _P], _i),
+    "fear_jpeg_decode_workspace_bytes": ([_P, _i], _sz),
     # the colour stage's members that are no lookup table (FearColourOp below)
     "fear_colour_u8": ([_P, _i, _i, _i, _P, _P, _P, _P], _i),
     # step metrics (metrics.TrainMetrics)
@@ -163,6 +169,27 @@ class FearColourOp(ctypes.Structure):
 
 
 assert ctypes.sizeof(FearColourOp) == 64 and FearColourOp.contrast.offset == 8 and FearColourOp.taps.offset == 24
+
+
+class FearJpegInfo(ctypes.Structure):
+    """include/fear_train.h: what fear_jpeg_parse reads from a file's headers."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("components", ctypes.c_int32), ("restart_interval", ctypes.c_int32),
+                ("mcus_x", ctypes.c_int32), ("mcus_y", ctypes.c_int32), ("h", ctypes.c_int32 * 3), ("v", ctypes.c_int32 * 3),
+                ("blocks_w", ctypes.c_int32 * 3), ("blocks_h", ctypes.c_int32 * 3), ("total_blocks", ctypes.c_uint32),
+                ("reserved", ctypes.c_int32), ("qt", (ctypes.c_uint16 * 64) * 3)]
+
+
+class FearJpegImage(ctypes.Structure):
+    """include/fear_train.h: one image of a fear_jpeg_decode_u8 call (device pointers as integers)."""
+    _fields_ = [("coef", ctypes.c_uint64), ("block_start", ctypes.c_uint64), ("out", ctypes.c_uint64), ("plane_offset", ctypes.c_uint64),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("components", ctypes.c_int32), ("h", ctypes.c_int32),
+                ("v", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3), ("qt", (ctypes.c_uint16 * 64) * 3)]
+
+
+assert ctypes.sizeof(FearJpegInfo) == 464 and FearJpegInfo.qt.offset == 80
+assert ctypes.sizeof(FearJpegImage) == 448 and FearJpegImage.qt.offset == 64
+FEAR_TRAIN_ERR_WORKSPACE, FEAR_TRAIN_ERR_FORMAT, FEAR_TRAIN_ERR_UNSUPPORTED = -7, -9, -10
+FEAR_JPEG_GROUP_BLOCKS, FEAR_JPEG_GROUP_PIXELS = 32, 256
 
 _ALLREDUCE_FN =ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p)
 FEAR_SYNC_BUF_BYTES = 16384

@@ -35,6 +35,8 @@ extern "C" {
 #define FEAR_TRAIN_ERR_HIP (-4)
 #define FEAR_TRAIN_ERR_WORKSPACE (-7)   /* workspace missing or too small */
 #define FEAR_TRAIN_ERR_SYNC (-8)        /* the SyncBatchNorm all-reduce callback failed, or its buffer is too small (fear_train_sync_bind) */
+#define FEAR_TRAIN_ERR_FORMAT (-9)      /* fear_jpeg_parse, fear_jpeg_entropy_decode: the bytes are no complete baseline JPEG */
+#define FEAR_TRAIN_ERR_UNSUPPORTED (-10) /* the same two: a valid JPEG of a kind the decoder declines */
 /* After FEAR_TRAIN_ERR_SYNC a caller may rely on this: the call returned right after the failed all-reduce, without launching what
  * would have read the un-reduced buffer — running_mean, running_var and `vec` of the failed BatchNorm and of every BatchNorm behind it
  * in the call are NOT written (a block's BatchNorms that completed before it keep their update); every other output of the call
@@ -503,6 +505,98 @@ int fear_photometric_stage_u8(const uint8_t* crops_u8, int n, int H, int W, cons
 int fear_jpeg_u8(const uint8_t* crops_in, int n, int H, int W, const int32_t* quality, void* workspace, size_t workspace_bytes,
                  uint8_t* crops_out, void* stream);
 size_t fear_jpeg_workspace_bytes(int n, int H, int W);
+
+/* ---- JPEG frames: what the reference reads with cv2.imread (model_training/dataset/utils.py:35-43) — libjpeg with its defaults, islow
+ * IDCT and fancy upsampling — decoded for the stages above (DESIGN.md section 14 states the contract; jpeg_frames.jpeg_decode_host restates
+ * it in numpy and equals Pillow's libjpeg-turbo byte for byte).  The host parses the file and runs the Huffman stage; the device does the
+ * arithmetic and never sees the bitstream.
+ * Accepted: SOF0 (baseline sequential, 8-bit), one component or three in one interleaved scan, chroma sampling 1 x 1 and luma sampling
+ * (h, v) of (1, 1), (2, 1) or (2, 2), 8-bit DQT, up to four DC and four AC Huffman tables, DRI with RST0-7, sides of 1..8192; APPn, COM and
+ * fill bytes are skipped, EXIF orientation is ignored.  FEAR_TRAIN_ERR_UNSUPPORTED: the other SOF kinds, arithmetic coding, 12-bit samples,
+ * 16-bit DQT, other sampling factors, 2 or 4 components, a scan with part of the components, Adobe APP14 with transform 0 (RGB), DNL.
+ * FEAR_TRAIN_ERR_FORMAT: a truncated stream, a code in no table, a coefficient index past 63, a missing or out-of-order restart marker, a
+ * table a component selects but no segment defined, a segment length past the end, a Huffman table with more than 256 symbols or an
+ * over-subscribed code length.  A file whose entropy data is complete decodes without its EOI.
+ *
+ * fear_jpeg_parse reads the segments up to the scan and fills `info`.  Component i has blocks_w[i] x blocks_h[i] = mcus_x h[i] x mcus_y v[i]
+ * blocks, mcus_x = ceil(width / (8 h[0])); a single component has h = v = 1 whatever the file says (its scan is not interleaved).
+ * fear_jpeg_entropy_decode runs T.81 F.2 over the scan (DC prediction per component; at a restart interval the bits are dropped to the byte
+ * boundary, the marker checked, the predictions reset) and writes the quantised coefficients PACKED: blocks component by component,
+ * row-major within a component; block b owns coef[block_start[b] .. block_start[b + 1]), its coefficients in zigzag order from the DC term
+ * through its last non-zero one (at least the DC term, at most 64 values), the rest of the block is zero.  `block_start` takes
+ * total_blocks + 1 entries, `coef` up to fear_jpeg_packed_bound(info) = 64 total_blocks values; a shorter coef_cap that the file overruns
+ * returns FEAR_TRAIN_ERR_WORKSPACE, an `info` that is not the file's FEAR_TRAIN_ERR_SHAPE.  Both calls are host code (no HIP call, no
+ * global state; any number of threads may run them at once), check every read against `n` and every write against `coef_cap`.      */
+#define FEAR_JPEG_MAX_SIDE 8192
+typedef struct FearJpegInfo {
+    int32_t width, height;
+    int32_t components;          /* 1 or 3                                                                               */
+    int32_t restart_interval;    /* MCUs between restart markers, 0: none                                                */
+    int32_t mcus_x, mcus_y;
+    int32_t h[3], v[3];          /* sampling factors; h[0], v[0] are the largest                                         */
+    int32_t blocks_w[3], blocks_h[3];
+    uint32_t total_blocks;       /* the sum over the components                                                          */
+    int32_t reserved;
+    uint16_t qt[3][64];          /* each component's quantiser table, natural (row-major) order                          */
+} FearJpegInfo;
+#ifdef __cplusplus
+static_assert(sizeof(FearJpegInfo) == 464, "FearJpegInfo is 464 bytes");
+#else
+_Static_assert(sizeof(FearJpegInfo) == 464, "FearJpegInfo is 464 bytes");
+#endif
+
+int fear_jpeg_parse(const uint8_t* data, size_t n, FearJpegInfo* info);
+size_t fear_jpeg_packed_bound(const FearJpegInfo* info);
+int fear_jpeg_entropy_decode(const uint8_t* data, size_t n, const FearJpegInfo* info, int16_t* coef, size_t coef_cap, uint32_t* block_start,
+                             size_t* coef_used);
+
+/* The device half: n images of any sizes and sampling modes in one call, two launches.
+ *   per block   the stored values un-zigzagged into a zeroed block, coef q in natural order, jidctint islow (columns, then rows), + 128,
+ *               clamp to 0..255 — the clamp is the contract: libjpeg's C range-limit table wraps beyond +-512 of the centre where its
+ *               SIMD paths saturate, and ordinary encoders stay inside — stored to the component's padded plane in `workspace`
+ *   upsample    on the true [ch, cw] part of a chroma plane, cw = ceil(width / 2), ch = ceil(height / 2) for (2, 2): the edge rules apply at
+ *               those edges, not at the padded blocks'.  (2, 2): fear_jpeg_u8's h2v2 rule.  (2, 1): (3 this + left + 1) >> 2 and
+ *               (3 this + right + 2) >> 2, the first and last columns are their own neighbours.  A plane with cw <= 2 is replicated
+ *               instead, as libjpeg does (jdsample.c)
+ *   colour      fear_jpeg_u8's "colour back", stored in R, G, B order (fear_jpeg_u8 reverses it, this call does not); one component
+ *               gives R = G = B = Y.  Only pixels inside [height, width] are stored.
+ * `images` is a HOST array of n records holding device pointers; the call reads it for its checks, the grid sizes and nothing else.  The
+ * kernels read `group_start`, a DEVICE table the caller uploads with the coefficients:
+ *     uint32 [n + 1]  prefix sums of ceil(total_blocks / FEAR_JPEG_GROUP_BLOCKS) per image (jpeg_decode_blocks_kernel's workgroups)
+ *     uint32 [n + 1]  prefix sums of ceil(height width / FEAR_JPEG_GROUP_PIXELS) per image (jpeg_decode_merge_kernel's)
+ *     padding to FEAR_JPEG_TABLE_RECORDS(n) bytes, then a copy of the n records
+ * A workgroup finds its image by a bounded binary search of its prefix table (uniform: scalar loads).  A device copy that differs from
+ * `images` is the caller's error, as a wrong `block_start` is.  An image's planes lie at workspace + 16-byte alignment + plane_offset:
+ * component i takes 64 blocks_w[i] blocks_h[i] bytes, an image the sum rounded up to 16 (what fear_jpeg_decode_workspace_bytes adds up,
+ * plus 16).  No atomics, bounded loops only.
+ * FEAR_TRAIN_ERR_SHAPE: n < 0 or n > 65535, sides outside 1..8192, components other than 1 or 3, another sampling mode, a plane_offset
+ * that is no multiple of 16.  n == 0 returns FEAR_TRAIN_OK without a launch.  A null images, group_start or a null pointer in a record
+ * returns FEAR_TRAIN_ERR_NULL; a null workspace, or one too short for a record's planes, FEAR_TRAIN_ERR_WORKSPACE.                   */
+#define FEAR_JPEG_GROUP_BLOCKS 32
+#define FEAR_JPEG_GROUP_PIXELS 256
+#define FEAR_JPEG_TABLE_RECORDS(n) (((size_t)(n) * 8 + 8 + 15) & ~(size_t)15)
+
+/* One image.  448 bytes. */
+typedef struct FearJpegImage {
+    const int16_t* coef;         /* device: the packed coefficients                                                      */
+    const uint32_t* block_start; /* device: total_blocks + 1 offsets into coef                                           */
+    uint8_t* out;                /* device: (height, width, 3) uint8, contiguous                                         */
+    uint64_t plane_offset;       /* bytes from the aligned workspace to this image's planes, a multiple of 16            */
+    int32_t width, height;
+    int32_t components;          /* 1 or 3                                                                               */
+    int32_t h, v;                /* the luma sampling factors: (1, 1), (2, 1) or (2, 2); (1, 1) with one component       */
+    int32_t reserved[3];
+    uint16_t qt[3][64];          /* FearJpegInfo's                                                                       */
+} FearJpegImage;
+#ifdef __cplusplus
+static_assert(sizeof(FearJpegImage) == 448, "FearJpegImage is 448 bytes");
+#else
+_Static_assert(sizeof(FearJpegImage) == 448, "FearJpegImage is 448 bytes");
+#endif
+
+int fear_jpeg_decode_u8(const FearJpegImage* images, int n, const uint32_t* group_start, void* workspace, size_t workspace_bytes,
+                        void* stream);
+size_t fear_jpeg_decode_workspace_bytes(const FearJpegInfo* infos, int n);
 
 /* ---- the colour stage's members that are no lookup table: Equalize, HueSaturationValue, ColorJitter and Emboss of the reference's
  * p = 0.5 OneOf (model_training/dataset/aug.py:35-48), on uint8 HWC crops between fear_train_pairs_u8 (tone, then the lookup-table

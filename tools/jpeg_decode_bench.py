@@ -1,0 +1,143 @@
+"""Measures the JPEG frame decoder (jpeg_frames.JpegDecoder) on 256 synthetic 1280 x 720, quality 90, 4:2:0 files
+and writes profiles/jpeg_decode_bench.json.
+
+    python tools/jpeg_decode_bench.py --make --dir DIR      # needs Pillow: writes the files (any machine)
+    python tools/jpeg_decode_bench.py --dir DIR             # needs the GPU: measures
+
+  entropy_ms_per_frame    fear_jpeg_parse + fear_jpeg_entropy_decode, one thread, mean over the files
+  entropy_fps             the same on 1, 4, 8 and 16 threads (ctypes releases the GIL)
+  device_ms               fear_jpeg_decode_u8 alone on the 256 frames, HIP events, coefficients already on the device
+  decode_fps              JpegDecoder.decode end to end on 16 threads (files in memory -> frames on the device, one synchronise per batch)
+  upload_bytes_per_frame  the packed coefficients and block_start, against 3 H W
+  pillow_fps              where Pillow is importable: Image.open(...).convert("RGB") on the same thread counts plus the pinned,
+                          non-blocking upload TrainPairBuilder gives host frames — the baseline to compare with
+Every timing is the median of --repeats runs after one warm-up run."""
+import argparse
+import glob
+import io
+import json
+import os
+import statistics
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+W, H, COUNT, QUALITY = 1280, 720, 256, 90
+THREADS = (1, 4, 8, 16)
+
+
+def make(directory):
+    from PIL import Image
+    os.makedirs(directory, exist_ok=True)
+    rng = np.random.default_rng(11)
+    yy, xx = np.mgrid[0:H, 0:W]
+    for i in range(COUNT):
+        # a smooth scene, a few hundred rectangles and mild noise: file sizes near a video frame's at this quality
+        img = np.stack([(xx * (i % 7 + 1) // 5 + yy) % 256, (yy * 2 + 3 * i) % 256, (xx + 2 * yy) // 3 % 256], axis=-1).astype(np.int16)
+        for _ in range(300):
+            x0, y0 = rng.integers(0, W - 8), rng.integers(0, H - 8)
+            img[y0:y0 + rng.integers(8, 160), x0:x0 + rng.integers(8, 160)] = rng.integers(0, 256, 3)
+        img += rng.integers(-6, 7, img.shape, dtype=np.int16)
+        Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(os.path.join(directory, f"frame{i:03d}.jpg"), quality=QUALITY, subsampling=2)
+    print("wrote", COUNT, "files to", directory)
+
+
+def median_seconds(fn, repeats):
+    fn()
+    times = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        fn()
+        times.append(time.perf_counter() - t0)
+    return statistics.median(times)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dir", required=True)
+    ap.add_argument("--make", action="store_true")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode_bench.json"))
+    args = ap.parse_args()
+    if args.make:
+        return make(args.dir)
+    import torch
+    from feartracker_amd import JpegDecoder
+    blobs = [open(p, "rb").read() for p in sorted(glob.glob(os.path.join(args.dir, "*.jpg")))]
+    assert blobs, "no files: run with --make first"
+    n = len(blobs)
+    dec = JpegDecoder(device=0, threads=16)
+    res = {"files": n, "width": W, "height": H, "quality": QUALITY, "file_bytes_per_frame": sum(map(len, blobs)) / n,
+           "cpus_available": len(os.sched_getaffinity(0)), "repeats": args.repeats}
+
+    # the host stage
+    res["entropy_ms_per_frame"] = round(1e3 * median_seconds(lambda: [dec.entropy_decode(b) for b in blobs], args.repeats) / n, 4)
+    res["entropy_fps"] = {}
+    for t in THREADS:
+        with ThreadPoolExecutor(max_workers=t) as pool:
+            res["entropy_fps"][str(t)] = round(n / median_seconds(lambda: list(pool.map(dec.entropy_decode, blobs)), args.repeats), 1)
+    decoded = [dec.entropy_decode(b) for b in blobs]
+    packed = sum(c.nbytes + s.nbytes for _, c, s in decoded) / n
+    res["upload_bytes_per_frame"] = {"packed": round(packed, 1), "decoded": 3 * H * W, "ratio": round(packed / (3 * H * W), 4)}
+
+    # end to end, and the device call alone (the decoder's own call, timed between HIP events around a second launch of it)
+    def end_to_end():
+        frames = dec.decode(blobs)
+        torch.cuda.synchronize()
+        return frames
+    res["decode_fps"] = round(n / median_seconds(end_to_end, args.repeats), 1)
+    from feartracker_amd import train_abi as abi
+    captured = {}
+    real = abi.launch
+
+    def spy(lib, name, *a):
+        captured["args"] = a
+        return real(lib, name, *a)
+    abi.launch = spy
+    frames = dec.decode(blobs)
+    abi.launch = real
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = []
+    for _ in range(args.repeats + 1):
+        e0.record()
+        assert dec._lib.fear_jpeg_decode_u8(*captured["args"]) == 0     # (the buffers are alive: `frames` and the allocator's cache)
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1))
+    res["device_ms"] = round(statistics.median(times[1:]), 4)
+    res["device_fps"] = round(n / (res["device_ms"] * 1e-3), 1)
+    del frames
+
+    # the baseline: Pillow on the host plus the upload of the decoded frames
+    try:
+        from PIL import Image
+    except ImportError:
+        res["pillow_fps"] = None
+    else:
+        def pillow(b):
+            return np.asarray(Image.open(io.BytesIO(b)).convert("RGB"))
+
+        def upload(frames):
+            for f in frames:
+                pinned = torch.empty(f.shape, dtype=torch.uint8, pin_memory=True)
+                pinned.numpy()[...] = f
+                pinned.to("cuda", non_blocking=True)
+            torch.cuda.synchronize()
+        res["pillow_fps"] = {}
+        for t in THREADS:
+            with ThreadPoolExecutor(max_workers=t) as pool:
+                res["pillow_fps"][str(t)] = round(n / median_seconds(lambda: upload(list(pool.map(pillow, blobs))), args.repeats), 1)
+    dec.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

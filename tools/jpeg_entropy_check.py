@@ -1,0 +1,108 @@
+"""Builds tools/jpeg_entropy_host.cpp with the address and undefined-behaviour sanitizers and runs it — a stand-alone host program, no
+Python extension and no GPU — on the fixture's files (tests/golden/jpeg_decode.npz) and on the malformed set of
+tests/test_jpeg_decode_host.py: every prefix and every flipped entropy byte of the 16 x 16 4:2:0 file, and the header faults.  Each line
+of its output is compared with the Python decoder's verdict and packed stream.  Expect "0 sanitizer reports, 0 mismatches".
+
+    python tools/jpeg_entropy_check.py [--dir SCRATCH] [--cxx g++]
+"""
+import argparse
+import os
+import struct
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import jpegdec                                                   # noqa: E402
+import test_jpeg_decode_host as host_tests                       # noqa: E402
+from feartracker_amd import jpeg_frames as jf                    # noqa: E402
+
+
+def fnv(h, data):
+    for b in data:
+        h = ((h ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def expected(name, data):
+    """The program's line for one file, from the Python decoder."""
+    try:
+        hd, coef = jf.jpeg_coefficients_host(data)
+    except jf.UnsupportedJPEG:
+        try:
+            jf.jpeg_info(data)
+        except jf.UnsupportedJPEG:
+            return f"{name} {jf.ERR_UNSUPPORTED}"
+        return f"{name} 0 {jf.ERR_UNSUPPORTED}"
+    except jf.MalformedJPEG:
+        try:
+            jf.jpeg_info(data)
+        except jf.MalformedJPEG:
+            return f"{name} {jf.ERR_FORMAT}"
+        return f"{name} 0 {jf.ERR_FORMAT}"
+    packed, start = [], [0]
+    for plane in coef:
+        for block in plane.reshape(-1, 64):
+            nz = np.flatnonzero(block)
+            count = max(1, int(nz[-1]) + 1) if nz.size else 1
+            packed.append(block[:count])
+            start.append(start[-1] + count)
+    packed = np.concatenate(packed).astype("<i2")
+    h = fnv(fnv(14695981039346656037, np.array(start, dtype="<u4").tobytes()), packed.tobytes())
+    return f"{name} 0 0 {hd.width} {hd.height} {len(hd.ids)} {len(start) - 1} {packed.size} {h:016x}"
+
+
+def files():
+    out = {f"case{i:02d}.jpg": data for i, (_, data, _) in enumerate(jpegdec.cases())}
+    F = jpegdec.case("16x16_420")[1]
+    for k in range(len(F)):
+        out[f"prefix{k:04d}.jpg"] = F[:k]
+    scan = F.index(b"\xff\xda")
+    first = scan + 2 + struct.unpack(">H", F[scan + 2:scan + 4])[0]
+    for k in range(first, len(F) - 2):
+        bad = bytearray(F)
+        bad[k] ^= 0xFF
+        out[f"flip{k:04d}.jpg"] = bytes(bad)
+    for i, (what, (data, _)) in enumerate(host_tests._header_faults().items()):
+        out[f"fault{i:02d}.jpg"] = data
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dir", default=None, help="scratch directory (a temporary one by default)")
+    ap.add_argument("--cxx", default="g++")
+    args = ap.parse_args()
+    scratch = args.dir or tempfile.mkdtemp(prefix="jpeg_entropy_")
+    os.makedirs(scratch, exist_ok=True)
+    exe = os.path.join(scratch, "jpeg_entropy_host")
+    cmd = [args.cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
+           os.path.join(ROOT, "tools", "jpeg_entropy_host.cpp")]
+    print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    made = files()
+    for name, data in made.items():
+        with open(os.path.join(scratch, name), "wb") as fh:
+            fh.write(data)
+    names = sorted(made)
+    res = subprocess.run([exe] + [os.path.join(scratch, n) for n in names], capture_output=True, text=True)
+    reports = res.stderr.count("ERROR: AddressSanitizer") + res.stderr.count("runtime error")
+    lines = res.stdout.splitlines()
+    mismatches = 0 if len(lines) == len(names) else 1
+    for name, line in zip(names, lines):
+        want = expected(name, made[name])
+        if line != want:
+            mismatches += 1
+            print(f"MISMATCH {name}: program '{line}', Python '{want}'")
+    if res.stderr:
+        print(res.stderr[-4000:])
+    print(f"{len(names)} files, exit status {res.returncode}: {reports} sanitizer reports, {mismatches} mismatches")
+    return 0 if res.returncode == 0 and reports == 0 and mismatches == 0 else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

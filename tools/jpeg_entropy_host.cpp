@@ -1,0 +1,75 @@
+// jpeg_entropy_host.cpp — the host half of the JPEG frame decoder (feartracker_amd/csrc/fear_jpeg_entropy.h) as a stand-alone program, so
+// that it can run under the address and undefined-behaviour sanitizers without Python or a GPU:
+//
+//     g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o jpeg_entropy_host tools/jpeg_entropy_host.cpp
+//     ./jpeg_entropy_host FILE...
+//
+// Per file one line: name, status of fear_jpeg_parse, status of fear_jpeg_entropy_decode, width, height, components, total_blocks, values
+// stored, FNV-1a of block_start and the packed coefficients.  Every buffer is allocated at exactly the size the call is told, a second call
+// gets exactly the values the first one used, and a third one value less (it must return FEAR_TRAIN_ERR_WORKSPACE).
+// tools/jpeg_entropy_check.py writes the files, runs the program and compares each line with the Python decoder's.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../feartracker_amd/csrc/fear_jpeg_entropy.h"
+
+static uint64_t fnv(uint64_t h, const void* p, size_t n) {
+    const unsigned char* b = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
+    return h;
+}
+
+int main(int argc, char** argv) {
+    int failures = 0;
+    for (int f = 1; f < argc; ++f) {
+        FILE* fp = std::fopen(argv[f], "rb");
+        if (!fp) { std::printf("%s unreadable\n", argv[f]); ++failures; continue; }
+        std::fseek(fp, 0, SEEK_END);
+        const long size = std::ftell(fp);
+        std::fseek(fp, 0, SEEK_SET);
+        // an exact-size heap copy: a read past the end is the sanitizer's to report
+        unsigned char* data = static_cast<unsigned char*>(std::malloc(size > 0 ? (size_t)size : 1));
+        const size_t n = std::fread(data, 1, (size_t)size, fp);
+        std::fclose(fp);
+        const char* name = std::strrchr(argv[f], '/');
+        name = name ? name + 1 : argv[f];
+        FearJpegInfo info;
+        const int rc = fear_jpeg_parse(data, n, &info);
+        if (rc != FEAR_TRAIN_OK) {
+            std::printf("%s %d\n", name, rc);
+            std::free(data);
+            continue;
+        }
+        const size_t cap = fear_jpeg_packed_bound(&info);
+        int16_t* coef = static_cast<int16_t*>(std::malloc(cap * sizeof(int16_t)));
+        uint32_t* start = static_cast<uint32_t*>(std::malloc(((size_t)info.total_blocks + 1) * sizeof(uint32_t)));
+        size_t used = 0;
+        const int rd = fear_jpeg_entropy_decode(data, n, &info, coef, cap, start, &used);
+        if (rd != FEAR_TRAIN_OK) {
+            std::printf("%s %d %d\n", name, rc, rd);
+        } else {
+            uint64_t h = fnv(14695981039346656037ull, start, ((size_t)info.total_blocks + 1) * sizeof(uint32_t));
+            h = fnv(h, coef, used * sizeof(int16_t));
+            std::printf("%s %d %d %d %d %d %u %zu %016llx\n", name, rc, rd, info.width, info.height, info.components, info.total_blocks, used,
+                        (unsigned long long)h);
+            int16_t* exact = static_cast<int16_t*>(std::malloc(used * sizeof(int16_t)));
+            size_t again = 0;
+            if (fear_jpeg_entropy_decode(data, n, &info, exact, used, start, &again) != FEAR_TRAIN_OK || again != used ||
+                std::memcmp(exact, coef, used * sizeof(int16_t)) != 0) {
+                std::printf("%s: the call at the exact capacity differs\n", name);
+                ++failures;
+            }
+            if (fear_jpeg_entropy_decode(data, n, &info, exact, used - 1, start, &again) != FEAR_TRAIN_ERR_WORKSPACE) {
+                std::printf("%s: a capacity one value short was not refused\n", name);
+                ++failures;
+            }
+            std::free(exact);
+        }
+        std::free(coef);
+        std::free(start);
+        std::free(data);
+    }
+    return failures ? 1 : 0;
+}
