@@ -368,6 +368,72 @@ int fear_jpeg_entropy_decode(const uint8_t* data, size_t n, const FearJpegInfo* 
     return FEAR_TRAIN_OK;
 }
 
+// The scan for the device's Huffman stage (fear_jpeg_huffman.h): the entropy-coded bytes without their stuffing, split at the restart
+// markers, and the tables the scan's components select.  One pass at memchr's speed; nothing is decoded.
+int fear_jpeg_scan_prepare(const uint8_t* data, size_t n, const FearJpegInfo* info, uint8_t* bytes_out, size_t bytes_cap,
+                           uint32_t* seg_start, size_t seg_cap, FearJpegScan* scan) {
+    using namespace fear_jpeg;
+    if (!data || !info || !bytes_out || !seg_start || !scan) return FEAR_TRAIN_ERR_NULL;
+    Header* hd = new (std::nothrow) Header();
+    if (!hd) return FEAR_TRAIN_ERR_WORKSPACE;
+    struct Guard { Header* h; ~Guard() { delete h; } } guard{hd};
+    const int rc = parse(data, n, *hd);
+    if (rc != FEAR_TRAIN_OK) return rc;
+    const FearJpegInfo& in = hd->info;
+    if (std::memcmp(&in, info, sizeof(in)) != 0) return FEAR_TRAIN_ERR_SHAPE;     // `info` is not this file's
+    if (n - hd->scan > 0xFFFFFFFFu) return FEAR_TRAIN_ERR_UNSUPPORTED;            // the offsets are 32 bits wide
+    const uint32_t n_mcu = (uint32_t)in.mcus_x * (uint32_t)in.mcus_y;
+    const uint32_t want = in.restart_interval ? (n_mcu + (uint32_t)in.restart_interval - 1) / (uint32_t)in.restart_interval : 1;
+    if (seg_cap < (size_t)want + 1) return FEAR_TRAIN_ERR_WORKSPACE;
+    size_t p = hd->scan, out = 0;
+    uint32_t seg = 0, longest = 0;
+    seg_start[0] = 0;
+    for (;;) {
+        const void* ff = p < n ? std::memchr(data + p, 0xFF, n - p) : nullptr;
+        const size_t q = ff ? (size_t)(static_cast<const uint8_t*>(ff) - data) : n;
+        if (q - p > bytes_cap - out) return FEAR_TRAIN_ERR_WORKSPACE;
+        if (q > p) std::memcpy(bytes_out + out, data + p, q - p);
+        out += q - p;
+        if (q + 1 >= n) break;                                            // the file ends, perhaps inside a marker
+        const int m = data[q + 1];
+        if (m == 0) {                                                     // a stuffed FF
+            if (out >= bytes_cap) return FEAR_TRAIN_ERR_WORKSPACE;
+            bytes_out[out++] = 0xFF;
+            p = q + 2;
+            continue;
+        }
+        if (seg + 1 == want) break;                                       // any marker ends the last segment
+        if (m != 0xD0 + (int)(seg & 7)) return FEAR_TRAIN_ERR_FORMAT;
+        if ((uint32_t)out - seg_start[seg] > longest) longest = (uint32_t)out - seg_start[seg];
+        seg_start[++seg] = (uint32_t)out;
+        p = q + 2;
+    }
+    if (seg + 1 != want) return FEAR_TRAIN_ERR_FORMAT;                    // a restart marker is missing
+    if ((uint32_t)out - seg_start[seg] > longest) longest = (uint32_t)out - seg_start[seg];
+    seg_start[want] = (uint32_t)out;
+    std::memset(scan, 0, sizeof(*scan));
+    scan->n_bytes = (uint32_t)out;
+    scan->n_seg = want;
+    scan->max_seg_bytes = longest;
+    scan->total_blocks = in.total_blocks;
+    scan->components = in.components;
+    scan->h = in.h[0];
+    scan->v = in.v[0];
+    scan->mcus_x = in.mcus_x;
+    scan->mcus_y = in.mcus_y;
+    scan->restart_interval = in.restart_interval;
+    for (int c = 0; c < in.components; ++c)
+        for (int k = 0; k < 2; ++k) {
+            const Huffman& t = k ? hd->ac[hd->ta[c]] : hd->dc[hd->td[c]];
+            FearJpegHuff& o = k ? scan->ac[c] : scan->dc[c];
+            std::memcpy(o.look, t.look, sizeof(o.look));
+            std::memcpy(o.values, t.values, sizeof(o.values));
+            std::memcpy(o.counts, t.counts, sizeof(o.counts));
+            for (int len = 1; len <= 16; ++len) { o.first[len] = t.first[len]; o.index[len] = t.index[len]; }
+        }
+    return FEAR_TRAIN_OK;
+}
+
 }  // extern "C"
 
 #endif  // FEAR_JPEG_ENTROPY_H

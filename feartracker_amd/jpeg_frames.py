@@ -3,7 +3,8 @@
 `jpeg_decode_host` is the contract: a numpy and pure-Python decoder of baseline sequential JPEG that equals libjpeg with its defaults
 (islow IDCT, fancy upsampling — what the reference's cv2.imread runs) byte for byte; tests/test_jpeg_decode_host.py holds it to Pillow's
 libjpeg-turbo.  `JpegDecoder` is the product: the parser and the Huffman stage run on host threads in the library
-(csrc/fear_jpeg_entropy.h), the packed coefficients go up in one transfer and `fear_jpeg_decode_u8` does the rest on the device."""
+(csrc/fear_jpeg_entropy.h), the packed coefficients go up in one transfer and `fear_jpeg_decode_u8` does the rest on the device.  With
+`entropy="device"` the Huffman stage runs on the device as well (`fear_jpeg_huffman`; jpeg_huffman.py states its contract)."""
 from __future__ import annotations
 
 import ctypes
@@ -16,6 +17,7 @@ import numpy as np
 from .train_data.jpeg import _jpeg_upsample, jpeg_idct_islow
 
 MAX_SIDE = 8192
+DEVICE_SCAN_MAX = 16 << 20                # include/fear_train.h FEAR_JPEG_DEVICE_SCAN_MAX: a longer restart segment is decoded on the host
 ERR_FORMAT, ERR_UNSUPPORTED = -9, -10     # include/fear_train.h FEAR_TRAIN_ERR_FORMAT, FEAR_TRAIN_ERR_UNSUPPORTED
 
 # zigzag position -> natural (row-major) index
@@ -340,10 +342,24 @@ class JpegDecoder:
 
     `decode` parses and Huffman-decodes on `threads` host threads (the library's C++ through ctypes, which releases the GIL), packs the
     coefficients of all images into one pinned buffer, uploads it non-blocking and runs `fear_jpeg_decode_u8` once.  It never waits for
-    the GPU.  The tensors go unchanged into `TrainPairBuilder.build`, `FEARMultiTracker` and `SequenceValidator`."""
-    MAX_THREADS = 16
+    the GPU.  The tensors go unchanged into `TrainPairBuilder.build`, `FEARMultiTracker` and `SequenceValidator`.
 
-    def __init__(self, device: int = 0, threads: Optional[int] = None):
+    `entropy="device"` moves the Huffman stage to the device.  The host threads then only parse the headers and prepare the scans
+    (`fear_jpeg_scan_prepare`: the stuffing removed, the bytes split at the restart markers — a header or marker fault still raises inside
+    `decode`, before any launch); the unstuffed bytes, the scan records and their tables go up in the one pinned transfer, about the
+    files' size; `fear_jpeg_huffman` (`subsequence_bytes` per lane) writes dense coefficients and `fear_jpeg_decode_u8` reads them.  A file
+    with a restart segment above DEVICE_SCAN_MAX goes through the host's Huffman stage in the same call, an unsupported file with a
+    `fallback` rides along as before.  A call whose dense coefficients (128 bytes per block: 4.1 MB for a 720p 4:2:0 frame) exceed
+    `workspace_limit` bytes is split into groups on the same stream; a single image above the limit is a group of its own.
+    An error the device finds — a code in no table, truncated entropy data: jpeg_huffman.jpeg_entropy_parallel_host lists them — cannot
+    raise inside a call that does not wait: `decode` copies the statuses to pinned memory and records an event, and `check()` waits for
+    the calls not yet checked and raises `MalformedJPEG` naming the call's item index; `decode(..., check=True)` does both.  The pixels of
+    a failed image are unspecified.  The statuses of the last PENDING_CALLS unchecked calls are kept."""
+    MAX_THREADS = 16
+    PENDING_CALLS = 64
+
+    def __init__(self, device: int = 0, threads: Optional[int] = None, entropy: str = "host", workspace_limit: int = 1 << 30,
+                 subsequence_bytes: int = 128):
         import torch
         from .train_abi import load_train_library
         if threads is None:
@@ -353,6 +369,13 @@ class JpegDecoder:
         self._lib = load_train_library()
         self._pool = ThreadPoolExecutor(max_workers=self.threads, thread_name_prefix="fear-jpeg")
         self._pinned: List = []                                       # the last calls' staging buffers: each outlives its copy
+        if entropy not in ("host", "device"):
+            raise ValueError('entropy is "host" or "device"')
+        if subsequence_bytes % 4 or not 4 <= subsequence_bytes <= 1024:
+            raise ValueError("subsequence_bytes is a multiple of 4 in 4..1024")
+        self.entropy, self.workspace_limit, self.subsequence_bytes = entropy, int(workspace_limit), int(subsequence_bytes)
+        self._pending: List = []                                      # device mode: (event, pinned statuses, [(item index, file)]) per group
+        self.last_paths: List[str] = []                               # device mode: "device" or "host" per JPEG file of the last call
 
     def close(self) -> None:
         self._pool.shutdown(wait=True)
@@ -373,7 +396,167 @@ class JpegDecoder:
             return rc
         return info, coef[:used.value], start
 
-    def decode(self, items: Sequence[Item], fallback: Optional[Callable[[bytes], np.ndarray]] = None) -> List:
+    def scan_prepare(self, data: bytes):
+        """One file through fear_jpeg_parse and fear_jpeg_scan_prepare: (FearJpegInfo, unstuffed bytes, uint32 seg_start, FearJpegScan),
+        or the library's status for a file it declines.  Host only."""
+        from .train_abi import FearJpegInfo, FearJpegScan
+        lib, info, scan = self._lib, FearJpegInfo(), FearJpegScan()
+        rc = lib.fear_jpeg_parse(data, len(data), ctypes.byref(info))
+        if rc != 0:
+            return rc
+        n_mcu = info.mcus_x * info.mcus_y
+        out = np.empty(len(data), dtype=np.uint8)
+        seg = np.empty((-(-n_mcu // info.restart_interval) if info.restart_interval else 1) + 1, dtype=np.uint32)
+        rc = lib.fear_jpeg_scan_prepare(data, len(data), ctypes.byref(info), out.ctypes.data, out.size, seg.ctypes.data, seg.size, ctypes.byref(scan))
+        if rc != 0:
+            return rc
+        return info, out[:scan.n_bytes], seg, scan
+
+    def _prepare(self, data: bytes):
+        res = self.scan_prepare(data)
+        if isinstance(res, tuple) and res[3].max_seg_bytes > DEVICE_SCAN_MAX:
+            return self.entropy_decode(data)                          # too long for one workgroup's bounded walk: the host's stage
+        return res
+
+    def check(self) -> None:
+        """Device mode: wait for the calls not yet checked and raise MalformedJPEG for the first image the device refused."""
+        pending, self._pending = self._pending, []
+        for k, (event, status, items) in enumerate(pending):
+            event.synchronize()
+            bad = np.flatnonzero(status.numpy())
+            if bad.size:
+                self._pending = pending[k + 1:]
+                index, data = items[int(bad[0])]
+                try:
+                    _raise_as_python(data, int(status[int(bad[0])]))
+                except MalformedJPEG as exc:
+                    raise MalformedJPEG(f"item {index}: {exc}") from None
+
+    def _decode_device(self, blobs: List[bytes], fallback) -> List:
+        prepared = list(self._pool.map(self._prepare, blobs))
+        jpegs, raw = [], {}
+        for i, (data, res) in enumerate(zip(blobs, prepared)):
+            if isinstance(res, tuple):
+                jpegs.append(i)
+            elif res == ERR_UNSUPPORTED and fallback is not None:
+                px = np.ascontiguousarray(fallback(data))
+                if px.ndim != 3 or px.shape[2] != 3 or px.dtype != np.uint8:
+                    raise ValueError("the fallback must return uint8 (H, W, 3)")
+                raw[i] = px
+            else:
+                _raise_as_python(data, res)
+        self.last_paths = ["device" if len(prepared[i]) == 4 else "host" for i in jpegs]
+        groups, dense = [[]], 0
+        for i in jpegs:
+            need = 128 * int(prepared[i][0].total_blocks) if len(prepared[i]) == 4 else 0
+            if groups[-1] and dense + need > self.workspace_limit:
+                groups.append([])
+                dense = 0
+            groups[-1].append(i)
+            dense += need
+        frames: List = [None] * len(blobs)
+        for g, group in enumerate(groups):
+            if len(group) > 65535:
+                raise ValueError("at most 65535 JPEG files per call")
+            self._decode_group(blobs, prepared, group, raw if g == 0 else {}, frames)
+        return frames
+
+    def _decode_group(self, blobs, prepared, group, raw, frames) -> None:
+        """One upload, fear_jpeg_huffman over the group's device-path images and fear_jpeg_decode_u8 over all of them.  The layout of
+        `decode`'s host mode with the scans added; host mode keeps its own code so that its bytes and launches stay what they were."""
+        import torch
+        from .train_abi import (FEAR_JPEG_GROUP_BLOCKS, FEAR_JPEG_GROUP_PIXELS, FearJpegImage, FearJpegInfo, FearJpegScan, launch)
+        from .train_data.staging import Staging
+        n = len(group)
+        on_device = [k for k in range(n) if len(prepared[group[k]]) == 4]
+        nd, place = len(on_device), {k: d for d, k in enumerate(on_device)}
+        stage = Staging()
+        records, infos, scans = (FearJpegImage * max(n, 1))(), (FearJpegInfo * max(n, 1))(), (FearJpegScan * max(nd, 1))()
+        prefix, seg_prefix = np.zeros((2, n + 1), dtype=np.uint32), np.zeros(nd + 1, dtype=np.uint32)
+        out_at, out_bytes, plane_at, values, most = [], 0, 0, 0, 0
+        for k, i in enumerate(group):
+            info = prepared[i][0]
+            infos[k] = info
+            rec = records[k]
+            rec.width, rec.height, rec.components, rec.h, rec.v = info.width, info.height, info.components, info.h[0], info.v[0]
+            ctypes.memmove(rec.qt, info.qt, ctypes.sizeof(rec.qt))
+            rec.plane_offset = plane_at
+            plane_at += int(info.total_blocks) * 64
+            prefix[0, k + 1] = prefix[0, k] + -(-int(info.total_blocks) // FEAR_JPEG_GROUP_BLOCKS)
+            prefix[1, k + 1] = prefix[1, k] + -(-info.width * info.height // FEAR_JPEG_GROUP_PIXELS)
+            if len(prepared[i]) == 4:
+                d = place[k]
+                ctypes.memmove(ctypes.byref(scans[d]), ctypes.byref(prepared[i][3]), ctypes.sizeof(FearJpegScan))
+                scans[d].coef_offset = values
+                values += 64 * int(info.total_blocks)
+                most = max(most, int(info.total_blocks))
+                seg_prefix[d + 1] = seg_prefix[d] + scans[d].n_seg
+                stage.add(f"bytes{k}", prepared[i][1])
+                stage.add(f"seg{k}", prepared[i][2])
+            else:
+                stage.add(f"coef{k}", prepared[i][1])
+                stage.add(f"start{k}", prepared[i][2])
+            out_at.append(out_bytes)
+            out_bytes += -(-info.width * info.height * 3 // 16) * 16
+        for i, px in raw.items():
+            stage.add(f"raw{i}", px)
+        table = np.zeros(-(-prefix.nbytes // 16) * 16 + ctypes.sizeof(records), dtype=np.uint8)
+        table[:prefix.nbytes] = prefix.reshape(-1).view(np.uint8)
+        stage.add("table", table)
+        scan_table = np.zeros(-(-seg_prefix.nbytes // 16) * 16 + ctypes.sizeof(scans), dtype=np.uint8)
+        scan_table[:seg_prefix.nbytes] = seg_prefix.view(np.uint8)
+        if nd:
+            stage.add("scans", scan_table)
+        with torch.cuda.device(self.device):
+            pinned = torch.empty(stage.nbytes, dtype=torch.uint8, pin_memory=True)
+            dev = torch.empty(stage.nbytes, dtype=torch.uint8, device=self.device)
+            out = torch.empty(max(out_bytes, 16), dtype=torch.uint8, device=self.device)
+            coef = torch.empty(max(values, 8), dtype=torch.int16, device=self.device)
+            dense_start = torch.empty(most + 1, dtype=torch.int32, device=self.device)
+            status = torch.empty(max(nd, 1), dtype=torch.int32, device=self.device)
+            base, out_base = dev.data_ptr(), out.data_ptr()
+            for k in range(n):
+                if k in place:
+                    d = place[k]
+                    scans[d].bytes = base + stage.sections[f"bytes{k}"][0]
+                    scans[d].seg_start = base + stage.sections[f"seg{k}"][0]
+                    records[k].coef = coef.data_ptr() + 2 * scans[d].coef_offset
+                    records[k].block_start = dense_start.data_ptr()
+                else:
+                    records[k].coef = base + stage.sections[f"coef{k}"][0]
+                    records[k].block_start = base + stage.sections[f"start{k}"][0]
+                records[k].out = out_base + out_at[k]
+            if n:
+                table[-ctypes.sizeof(records):] = np.frombuffer(records, dtype=np.uint8)
+            if nd:
+                scan_table[-ctypes.sizeof(scans):] = np.frombuffer(scans, dtype=np.uint8)
+            stage.write(pinned.numpy())
+            dev.copy_(pinned, non_blocking=True)
+            self._pinned = self._pinned[-1:] + [pinned]
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if nd:
+                launch(self._lib, "fear_jpeg_dense_block_start", ctypes.c_void_p(dense_start.data_ptr()), most, stream)
+                launch(self._lib, "fear_jpeg_huffman", scans, nd, ctypes.c_void_p(base + stage.sections["scans"][0]),
+                       ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(status.data_ptr()), self.subsequence_bytes, stream)
+            if n:
+                ws_bytes = self._lib.fear_jpeg_decode_workspace_bytes(infos, n)
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+                launch(self._lib, "fear_jpeg_decode_u8", records, n, ctypes.c_void_p(base + stage.sections["table"][0]),
+                       ctypes.c_void_p(ws.data_ptr()), ws_bytes, stream)
+            if nd:
+                verdict = torch.empty(nd, dtype=torch.int32, pin_memory=True)
+                verdict.copy_(status[:nd], non_blocking=True)
+                event = torch.cuda.Event()
+                event.record()
+                self._pending = (self._pending + [(event, verdict, [(group[k], blobs[group[k]]) for k in on_device])])[-self.PENDING_CALLS:]
+        for k, i in enumerate(group):
+            h, w = records[k].height, records[k].width
+            frames[i] = out[out_at[k]:out_at[k] + h * w * 3].view(h, w, 3)
+        for i, px in raw.items():
+            at = stage.sections[f"raw{i}"][0]
+            frames[i] = dev[at:at + px.nbytes].view(px.shape)
+
+    def decode(self, items: Sequence[Item], fallback: Optional[Callable[[bytes], np.ndarray]] = None, check: bool = False) -> List:
         import torch
         from .train_abi import (FEAR_JPEG_GROUP_BLOCKS, FEAR_JPEG_GROUP_PIXELS, FearJpegImage, FearJpegInfo, launch)
         from .train_data.staging import Staging
@@ -387,6 +570,11 @@ class JpegDecoder:
         n_items = len(blobs)
         if n_items == 0:
             return []
+        if self.entropy == "device":
+            frames = self._decode_device(blobs, fallback)
+            if check:
+                self.check()
+            return frames
         # the host stage: every file is judged before anything is launched
         decoded = list(self._pool.map(self.entropy_decode, blobs))
         stage, jpegs, raw = Staging(), [], {}

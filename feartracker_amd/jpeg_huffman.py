@@ -1,0 +1,253 @@
+"""The device's Huffman stage of the JPEG frame decoder, stated in numpy and plain Python ("The Huffman stage on the
+device").  `jpeg_scan_prepare_host` restates `fear_jpeg_scan_prepare` (csrc/fear_jpeg_entropy.h): the entropy-coded bytes with the FF 00
+stuffing removed, split at the restart markers.  `jpeg_entropy_parallel_host` restates `fear_jpeg_huffman` (csrc/fear_jpeg_huffman.h): the
+self-synchronising parallel decode of Weissenberger and Schmidt, in the variant that is exact with bounded work — the same steps in the
+same order as the kernel, lane by lane.  tests/test_jpeg_huffman_host.py holds it to `jpeg_coefficients_host`, coefficient for coefficient
+and verdict for verdict."""
+from __future__ import annotations
+
+from typing import List, Tuple
+
+import numpy as np
+
+from .jpeg_frames import ERR_FORMAT, MalformedJPEG, _Header, _Huffman, _parse
+
+
+def scan_segments(hd: _Header) -> int:
+    """The restart segments of the scan: ceil(MCUs / restart interval), one without an interval."""
+    n_mcu = hd.mcus_x * hd.mcus_y
+    return -(-n_mcu // hd.restart) if hd.restart else 1
+
+
+def jpeg_scan_prepare_host(data: bytes, hd: _Header = None) -> Tuple[bytes, List[int]]:
+    """The scan's bytes without their stuffing and the offsets of its segments: segment s owns bytes[start[s]:start[s + 1]].  In front of
+    the last segment marker k must be RST(k mod 8); the last segment ends at any marker or with the file, as Bits::fill ends the data."""
+    data = bytes(data)
+    if hd is None:
+        hd = _parse(data)
+    n, p, want = len(data), hd.scan, scan_segments(hd)
+    out, start = bytearray(), [0]
+    while True:
+        q = data.find(b"\xff", p)
+        if q < 0:
+            q = n
+        out += data[p:q]
+        if q + 1 >= n:                              # the file ends, perhaps inside a marker
+            break
+        m = data[q + 1]
+        if m == 0:
+            out.append(0xFF)
+            p = q + 2
+            continue
+        if len(start) == want:                      # any marker ends the last segment
+            break
+        if m != 0xD0 + ((len(start) - 1) & 7):
+            raise MalformedJPEG("a restart marker is missing or out of order")
+        start.append(len(out))
+        p = q + 2
+    if len(start) != want:
+        raise MalformedJPEG("a restart marker is missing or out of order")
+    start.append(len(out))
+    return bytes(out), start
+
+
+_look_cache: dict = {}
+
+
+def _look16(t: _Huffman) -> list:
+    """(length << 8 | symbol) for every 16-bit prefix, 0 where no code matches: the kernel's 9-bit table and slow path in one."""
+    key = (tuple(t.counts), bytes(t.values))
+    if key in _look_cache:
+        return _look_cache[key]
+    if len(_look_cache) >= 64:
+        _look_cache.clear()
+    look = np.zeros(1 << 16, dtype=np.int32)
+    for length in range(1, 17):
+        for k in range(t.counts[length]):
+            base = (t.first[length] + k) << (16 - length)
+            look[base:base + (1 << (16 - length))] = length << 8 | t.values[t.index[length] + k]
+    _look_cache[key] = look.tolist()
+    return _look_cache[key]
+
+
+class _Geometry:
+    """What a lane needs of the header: the slots of an MCU, their components and tables, and where a block goes."""
+
+    def __init__(self, hd: _Header):
+        nf = len(hd.ids)
+        self.nf, self.h, self.v, self.mcus_x, self.n_mcu = nf, hd.h[0], hd.v[0], hd.mcus_x, hd.mcus_x * hd.mcus_y
+        self.comp = [0] * (self.h * self.v) + [1, 2] if nf == 3 else [0]
+        self.nslots = len(self.comp)
+        cache = {}
+        self.dc = [cache.setdefault(("dc", hd.td[c]), _look16(hd.dc[hd.td[c]])) for c in range(nf)]
+        self.ac = [cache.setdefault(("ac", hd.ta[c]), _look16(hd.ac[hd.ta[c]])) for c in range(nf)]
+        self.blocks_w = list(hd.blocks_w)
+        sizes = [hd.blocks_w[c] * hd.blocks_h[c] for c in range(nf)]
+        self.comp_first = [sum(sizes[:c]) for c in range(nf)]
+        self.total_blocks = sum(sizes)
+
+    def block(self, first_mcu: int, ordinal: int, slot: int) -> int:
+        """The component-major, row-major index of the block with this ordinal in its segment."""
+        my, mx = divmod(first_mcu + ordinal // self.nslots, self.mcus_x)
+        c = self.comp[slot]
+        j, i = divmod(slot, self.h) if c == 0 else (0, 0)
+        hc, vc = (self.h, self.v) if c == 0 else (1, 1)
+        return self.comp_first[c] + (my * vc + j) * self.blocks_w[c] + mx * hc + i
+
+
+_ERR, _DC, _ZEROS, _AC, _END = range(5)
+
+
+def _decode(buf: bytes, L: int, state, end: int, g: _Geometry, ev):
+    """Symbols from `state` = (bit position, slot, z) until the position reaches `end` or the segment's end `L`; the exit state.  Bits
+    past L read as zero.  A code in no table, a DC size above 15 or an index past 63: advance one bit, z = 0.  `ev` takes what was
+    decoded: (_DC, slot, difference, position behind), (_ZEROS, z from, z to, position behind), (_AC, z, value, position behind),
+    (_END, position behind) when a block is complete, (_ERR,)."""
+    p, slot, z = state
+    stop = min(end, L)
+    comp, nslots = g.comp, g.nslots
+    while p < stop:
+        at = p >> 3
+        w = (int.from_bytes(buf[at:at + 5], "big") >> (8 - (p & 7))) & 0xFFFFFFFF
+        if p + 32 > L:
+            w &= ~(0xFFFFFFFF >> (L - p))
+        c = comp[slot]
+        if z == 0:
+            e = g.dc[c][w >> 16]
+            n, t = e >> 8, e & 255
+            if e == 0 or t > 15:
+                if ev is not None:
+                    ev.append((_ERR,))
+                p += 1
+                continue
+            v = ((w << n) & 0xFFFFFFFF) >> (32 - t) if t else 0
+            p += n + t
+            z = 1
+            if ev is not None:
+                ev.append((_DC, slot, v if t == 0 or v >= 1 << (t - 1) else v - (1 << t) + 1, p))
+            continue
+        e = g.ac[c][w >> 16]
+        n, r, s = e >> 8, (e >> 4) & 15, e & 15
+        if e == 0 or z + r > (63 if s else 62 if r == 15 else 99):    # no code | an index past 63, a ZRL that runs past it included
+            if ev is not None:
+                ev.append((_ERR,))
+            p += 1
+            z = 0
+            continue
+        if s == 0:
+            p += n
+            if r == 15:                                 # ZRL: sixteen zeros, a coefficient follows
+                if ev is not None:
+                    ev.append((_ZEROS, z, z + 16, p))
+                z += 16
+                continue
+            if ev is not None:                          # EOB: zeros to the end of the block
+                ev.append((_ZEROS, z, 64, p))
+            z = 64
+        else:
+            v = ((w << n) & 0xFFFFFFFF) >> (32 - s)
+            p += n + s
+            if ev is not None:
+                if r:
+                    ev.append((_ZEROS, z, z + r, p))
+                ev.append((_AC, z + r, v if v >= 1 << (s - 1) else v - (1 << s) + 1, p))
+            z += r + 1
+        if z == 64:
+            z = 0
+            slot = slot + 1 if slot + 1 < nslots else 0
+            if ev is not None:
+                ev.append((_END, p))
+    return p, slot, z
+
+
+def jpeg_entropy_parallel_host(data: bytes, subsequence_bytes: int = 128, lanes: int = 256):
+    """The contract of `fear_jpeg_huffman`: (header, coefficients per component as jpeg_coefficients_host returns them, status, rounds).
+    `status` is 0 or ERR_FORMAT; a header or restart-marker fault raises as `_parse` and `jpeg_scan_prepare_host` do, before any decoding.
+    `rounds` lists, per sequence, how many synchronisation rounds ran (the first, every lane on its own subsequence, included).  The
+    coefficients of a file whose status is not 0 are unspecified."""
+    if subsequence_bytes % 4 or not 4 <= subsequence_bytes <= 1024 or lanes < 1:
+        raise ValueError("subsequence_bytes is a multiple of 4 in 4..1024")
+    data = bytes(data)
+    hd = _parse(data)
+    stream, seg_start = jpeg_scan_prepare_host(data, hd)
+    g = _Geometry(hd)
+    dense = np.zeros(64 * g.total_blocks, dtype=np.int16)
+    writes = np.zeros(64 * g.total_blocks, dtype=np.uint8)
+    SB, status, rounds = 8 * subsequence_bytes, 0, []
+    per_segment = (hd.restart if hd.restart else g.n_mcu)
+    for s in range(len(seg_start) - 1):
+        buf = stream[seg_start[s]:seg_start[s + 1]] + bytes(8)
+        L = 8 * (seg_start[s + 1] - seg_start[s])
+        first_mcu = s * per_segment
+        expected = min(per_segment, g.n_mcu - first_mcu) * g.nslots
+        last_segment = s == len(seg_start) - 2
+        n_sub = -(-L // SB)
+        carry, begun, pred = (0, 0, 0), 0, [0, 0, 0]
+        for q in range(0, n_sub, lanes):
+            m = min(lanes, n_sub - q)                                   # the lanes with a subsequence inside the segment
+            # synchronisation: lane 0 holds the true state, the others guess; stored[j] is the exit of subsequence q + j
+            carried = [carry] + [((q + i) * SB, 0, 0) for i in range(1, m)]
+            carried = [_decode(buf, L, carried[i], (q + i + 1) * SB, g, None) for i in range(m)]
+            stored, active, r = list(carried), [True] * m, 1
+            while r < lanes and any(active):
+                for i in range(m):
+                    j = i + r
+                    if not active[i]:
+                        continue
+                    if j >= m:
+                        active[i] = False
+                        continue
+                    out = _decode(buf, L, carried[i], (q + j + 1) * SB, g, None)
+                    if out == stored[j]:
+                        active[i] = False
+                    else:
+                        stored[j] = carried[i] = out
+                r += 1
+            rounds.append(r)
+            entry = [carry] + stored[:m - 1]
+            # count and write.  The kernel decodes twice more: once to count the blocks that begin in each subsequence and to sum its DC
+            # differences, and, after an exclusive prefix over the lanes, once to write.  Walking the lanes in order is that prefix.
+            for i in range(m):
+                ev = []
+                out = _decode(buf, L, entry[i], (q + i + 1) * SB, g, ev)
+                assert out == stored[i]
+                slot, is_open = entry[i][1], entry[i][2] != 0            # a block begun in an earlier subsequence is still open
+                for e in ev:
+                    kind = e[0]
+                    if kind == _ERR:
+                        if begun - is_open < expected:                   # in the open block, or in the one that would begin here
+                            status = ERR_FORMAT
+                        is_open = False
+                        continue
+                    if kind == _END:
+                        is_open = False
+                        if begun == expected and not last_segment and L - e[1] >= 8:
+                            status = ERR_FORMAT                          # whole bytes in front of the marker: Bits::restart
+                        continue
+                    if kind == _DC:
+                        slot, c = e[1], g.comp[e[1]]
+                        pred[c] = (pred[c] + e[2]) & 0xFFFF              # JCOEF is 16 bits wide
+                        begun, is_open = begun + 1, True
+                        z0, z1, value = 0, 1, pred[c] - 0x10000 if pred[c] >= 0x8000 else pred[c]
+                    elif kind == _ZEROS:
+                        z0, z1, value = e[1], e[2], 0
+                    else:
+                        z0, z1, value = e[1], e[1] + 1, e[2]
+                    if 1 <= begun <= expected:                           # blocks past the segment's count are dropped
+                        if e[-1] > L:                                    # the symbol or its magnitude bits run past the segment
+                            status = ERR_FORMAT
+                        b = g.block(first_mcu, begun - 1, slot)
+                        if b < g.total_blocks:
+                            dense[64 * b + z0:64 * b + z1] = value
+                            writes[64 * b + z0:64 * b + z1] += 1
+            carry = stored[m - 1]
+        if begun - (carry[2] != 0) < expected:                           # fewer complete blocks than the segment owes
+            status = ERR_FORMAT
+    if status == 0:
+        assert np.all(writes == 1), "every position of every block is written exactly once"
+    coef, at = [], 0
+    for c in range(g.nf):
+        size = hd.blocks_w[c] * hd.blocks_h[c]
+        coef.append(dense[64 * at:64 * (at + size)].reshape(hd.blocks_h[c], hd.blocks_w[c], 64))
+        at += size
+    return hd, coef, status, rounds

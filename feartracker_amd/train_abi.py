@@ -91,6 +91,10 @@ TRAIN_SYMBOLS = {
     "fear_jpeg_entropy_decode": ([_P, _sz, _P, _P, _sz, _P, _P], _i),
     "fear_jpeg_decode_u8": ([_P, _i, _P, _P, _sz, _P], _i),
     "fear_jpeg_decode_workspace_bytes": ([_P, _i], _sz),
+    # the Huffman stage on the device (FearJpegScan below): the host's scan preparation, the decode, the dense block_start table
+    "fear_jpeg_scan_prepare": ([_P, _sz, _P, _P, _sz, _P, _sz, _P], _i),
+    "fear_jpeg_huffman": ([_P, _i, _P, _P, _P, _i, _P], _i),
+    "fear_jpeg_dense_block_start": ([_P, ctypes.c_uint32, _P], _i),
     # the colour stage's members that are no lookup table (FearColourOp below)
     "fear_colour_u8": ([_P, _i, _i, _i, _P, _P, _P, _P], _i),
     # step metrics (metrics.TrainMetrics)
@@ -186,10 +190,26 @@ class FearJpegImage(ctypes.Structure):
                 ("v", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3), ("qt", (ctypes.c_uint16 * 64) * 3)]
 
 
+class FearJpegHuff(ctypes.Structure):
+    """include/fear_train.h: one Huffman table, fear_jpeg::Huffman's layout."""
+    _fields_ = [("look", ctypes.c_uint16 * 512), ("first", ctypes.c_int32 * 17), ("index", ctypes.c_int32 * 17), ("values", ctypes.c_uint8 * 256),
+                ("counts", ctypes.c_uint8 * 17), ("reserved", ctypes.c_uint8 * 7)]
+
+
+class FearJpegScan(ctypes.Structure):
+    """include/fear_train.h: one image's scan of a fear_jpeg_huffman call (device pointers as integers)."""
+    _fields_ = [("bytes", ctypes.c_uint64), ("seg_start", ctypes.c_uint64), ("coef_offset", ctypes.c_uint64), ("n_bytes", ctypes.c_uint32),
+                ("n_seg", ctypes.c_uint32), ("max_seg_bytes", ctypes.c_uint32), ("total_blocks", ctypes.c_uint32), ("components", ctypes.c_int32),
+                ("h", ctypes.c_int32), ("v", ctypes.c_int32), ("mcus_x", ctypes.c_int32), ("mcus_y", ctypes.c_int32),
+                ("restart_interval", ctypes.c_int32), ("dc", FearJpegHuff * 3), ("ac", FearJpegHuff * 3)]
+
+
 assert ctypes.sizeof(FearJpegInfo) == 464 and FearJpegInfo.qt.offset == 80
+assert ctypes.sizeof(FearJpegHuff) == 1440 and ctypes.sizeof(FearJpegScan) == 8704 and FearJpegScan.dc.offset == 64
 assert ctypes.sizeof(FearJpegImage) == 448 and FearJpegImage.qt.offset == 64
 FEAR_TRAIN_ERR_WORKSPACE, FEAR_TRAIN_ERR_FORMAT, FEAR_TRAIN_ERR_UNSUPPORTED = -7, -9, -10
 FEAR_JPEG_GROUP_BLOCKS, FEAR_JPEG_GROUP_PIXELS = 32, 256
+FEAR_JPEG_DEVICE_SCAN_MAX = 16 << 20
 
 _ALLREDUCE_FN =ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p)
 FEAR_SYNC_BUF_BYTES = 16384

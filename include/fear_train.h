@@ -598,6 +598,86 @@ int fear_jpeg_decode_u8(const FearJpegImage* images, int n, const uint32_t* grou
                         void* stream);
 size_t fear_jpeg_decode_workspace_bytes(const FearJpegInfo* infos, int n);
 
+/* ---- the Huffman stage on the device (jpeg_huffman.jpeg_entropy_parallel_host restates it in Python, step for
+ * step).  A baseline scan has no index, but Huffman streams re-synchronise by themselves: the self-synchronising parallel decode of
+ * Weissenberger and Schmidt (ICPP 2018; 2021), in a variant that is exact with bounded work and in which no workgroup waits for another.
+ *
+ * fear_jpeg_scan_prepare is the host's part, all it does per file besides fear_jpeg_parse: from the first byte of the scan it copies the
+ * entropy-coded bytes to `bytes_out` with the FF 00 stuffing removed and splits them at the restart markers; segment s owns
+ * bytes_out[seg_start[s] .. seg_start[s + 1]).  Without a restart interval there is one segment; with one there are ceil(MCUs / interval),
+ * and the marker behind segment k < last must be RST(k mod 8): a missing, surplus or out-of-order marker, or a file cut in front of or
+ * inside one, is FEAR_TRAIN_ERR_FORMAT.  The last segment ends at any FF xx with xx != 0 or with the file, which is where
+ * fear_jpeg_entropy_decode's reader ends the data (a marker that cuts it short is found by the device: blocks are missing).  It fills
+ * `scan` with the geometry and the Huffman tables the scan's components select (component c decodes with dc[c] and ac[c]); the caller
+ * sets the three device addresses.  `bytes_cap` bytes and `seg_cap` entries are the capacities: the file's length and segments + 1
+ * always do; FEAR_TRAIN_ERR_WORKSPACE where the file needs more.  A file whose `info` is not its own: FEAR_TRAIN_ERR_SHAPE.  Host code, no
+ * HIP call, no global state, every read checked against `n` and every write against the capacities.
+ *
+ * fear_jpeg_huffman decodes n scans: one workgroup of 256 lanes per segment.  The segment's bits are cut into subsequences of
+ * 8 subsequence_bytes bits, 256 consecutive subsequences are a sequence, and the workgroup walks its sequences in order.  A state is
+ * (bit position, slot = block within the MCU, z = zigzag index, 0: a DC code is next).  Per sequence: lane 0 enters with the true state,
+ * every other lane i guesses (start of subsequence i, 0, 0); each lane decodes its subsequence and stores the exit state; in round r a
+ * lane still active decodes subsequence i + r from the state it carries, stops if its exit equals the one stored there and overwrites it
+ * otherwise — after at most 255 rounds every stored state is the true one, whatever the file.  Then each lane decodes its subsequence
+ * again and counts the blocks that begin in it and the DC differences per component modulo 2^16; an exclusive prefix carried from
+ * sequence to sequence gives it the ordinal of its first block and the predictors at its entry; a last decode writes the coefficients
+ * DENSE: block b (fear_jpeg_entropy_decode's component-major, row-major index) owns coef[coef_offset + 64 b ..+ 64) in zigzag order, the
+ * DC term as its predicted value, every position written by exactly one lane.  Blocks past the segment's count are dropped.
+ * status_dev[i] is FEAR_TRAIN_OK or FEAR_TRAIN_ERR_FORMAT: on the true chain and inside the segment's blocks a code in no table, a DC size
+ * above 15, an index past 63, a symbol or its magnitude bits not wholly inside the segment; fewer blocks than the segment owes; whole
+ * bytes between the last block and a restart marker — the verdict of fear_jpeg_entropy_decode, file by file.  The coefficients of a
+ * failed image are unspecified; nothing is read or written out of range for it.
+ * Two launches (the statuses' zeros, the decode), only workgroup barriers, no atomics; every loop is bounded by the segment's length.
+ * `scans` is a HOST array the call reads for its checks and the grid size; the kernels read `table_dev`, a DEVICE copy the caller uploads:
+ *     uint32 [n + 1]  prefix sums of n_seg per image
+ *     padding to FEAR_JPEG_SCAN_TABLE_RECORDS(n) bytes, then a copy of the n records
+ * `bytes` of a record is 4-byte aligned and readable up to n_bytes rounded up to 4.
+ * FEAR_TRAIN_ERR_SHAPE: n < 0 or n > 65535, subsequence_bytes no multiple of 4 in 4..1024, a record whose geometry is not one
+ * fear_jpeg_parse gives, whose n_seg or total_blocks do not follow from it, whose bytes are misaligned or whose largest segment exceeds
+ * FEAR_JPEG_DEVICE_SCAN_MAX (such a file goes through fear_jpeg_entropy_decode).  n == 0 returns FEAR_TRAIN_OK without a launch.  A null
+ * scans, table_dev, coef, status_dev or address in a record: FEAR_TRAIN_ERR_NULL.
+ * fear_jpeg_dense_block_start writes 0, 64, 128, ... 64 total_blocks to `block_start`: the table every dense image's FearJpegImage record
+ * points at, so that the dense coefficients feed fear_jpeg_decode_u8 as they are.                                                     */
+#define FEAR_JPEG_DEVICE_SCAN_MAX (16u << 20)
+#define FEAR_JPEG_SCAN_TABLE_RECORDS(n) (((size_t)(n) * 4 + 4 + 15) & ~(size_t)15)
+
+/* One Huffman table in fear_jpeg::Huffman's layout.  1440 bytes. */
+typedef struct FearJpegHuff {
+    uint16_t look[512];          /* (length << 8 | symbol) for codes of at most 9 bits, 0 otherwise                      */
+    int32_t first[17], index[17];/* the first code of a length and its place in `values`                                 */
+    uint8_t values[256];
+    uint8_t counts[17];          /* codes of each length 1..16                                                           */
+    uint8_t reserved[7];
+} FearJpegHuff;
+
+/* One image's scan.  8704 bytes. */
+typedef struct FearJpegScan {
+    const uint8_t* bytes;        /* device: the unstuffed bytes of all segments                                          */
+    const uint32_t* seg_start;   /* device: n_seg + 1 offsets into bytes                                                 */
+    uint64_t coef_offset;        /* values from `coef` to this image's 64 total_blocks dense coefficients                */
+    uint32_t n_bytes, n_seg;
+    uint32_t max_seg_bytes;      /* the longest segment                                                                  */
+    uint32_t total_blocks;
+    int32_t components;          /* 1 or 3                                                                               */
+    int32_t h, v;                /* the luma sampling factors, as in FearJpegImage                                       */
+    int32_t mcus_x, mcus_y;
+    int32_t restart_interval;
+    FearJpegHuff dc[3], ac[3];   /* by component                                                                         */
+} FearJpegScan;
+#ifdef __cplusplus
+static_assert(sizeof(FearJpegHuff) == 1440, "FearJpegHuff is 1440 bytes");
+static_assert(sizeof(FearJpegScan) == 8704, "FearJpegScan is 8704 bytes");
+#else
+_Static_assert(sizeof(FearJpegHuff) == 1440, "FearJpegHuff is 1440 bytes");
+_Static_assert(sizeof(FearJpegScan) == 8704, "FearJpegScan is 8704 bytes");
+#endif
+
+int fear_jpeg_scan_prepare(const uint8_t* data, size_t n, const FearJpegInfo* info, uint8_t* bytes_out, size_t bytes_cap,
+                           uint32_t* seg_start, size_t seg_cap, FearJpegScan* scan);
+int fear_jpeg_huffman(const FearJpegScan* scans, int n, const void* table_dev, int16_t* coef, int32_t* status_dev, int subsequence_bytes,
+                      void* stream);
+int fear_jpeg_dense_block_start(uint32_t* block_start, uint32_t total_blocks, void* stream);
+
 /* ---- the colour stage's members that are no lookup table: Equalize, HueSaturationValue, ColorJitter and Emboss of the reference's
  * p = 0.5 OneOf (model_training/dataset/aug.py:35-48), on uint8 HWC crops between fear_train_pairs_u8 (tone, then the lookup-table
  * members) and fear_photometric_u8 (DESIGN.md section 11 states every contract; train_data.colour_u8_host restates them in numpy and the

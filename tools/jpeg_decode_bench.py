@@ -3,6 +3,8 @@ and writes profiles/jpeg_decode_bench.json.
 
     python tools/jpeg_decode_bench.py --make --dir DIR      # needs Pillow: writes the files (any machine)
     python tools/jpeg_decode_bench.py --dir DIR             # needs the GPU: measures
+    python tools/jpeg_decode_bench.py --dir DIR --entropy both      # the host and the device Huffman stage in the same run
+    python tools/jpeg_decode_bench.py --dir DIR --rounds 4  # no GPU: synchronisation rounds of the first files, from the Python model
 
   entropy_ms_per_frame    fear_jpeg_parse + fear_jpeg_entropy_decode, one thread, mean over the files
   entropy_fps             the same on 1, 4, 8 and 16 threads (ctypes releases the GIL)
@@ -11,7 +13,14 @@ and writes profiles/jpeg_decode_bench.json.
   upload_bytes_per_frame  the packed coefficients and block_start, against 3 H W
   pillow_fps              where Pillow is importable: Image.open(...).convert("RGB") on the same thread counts plus the pinned,
                           non-blocking upload TrainPairBuilder gives host frames — the baseline to compare with
-Every timing is the median of --repeats runs after one warm-up run."""
+With --entropy device or both, under "device_entropy" (the host figures above stay the baseline: entropy="host" at 16 threads, unchanged):
+  decode_fps              JpegDecoder(entropy="device").decode end to end, check() included, by subsequence_bytes 32, 64, 128, 256
+  huffman_ms              fear_jpeg_huffman alone between HIP events, by subsequence_bytes; `subsequence_bytes` names the fastest
+  device_ms_dense         fear_jpeg_decode_u8 alone on the dense coefficients (device_ms above is the packed input)
+  upload_bytes_per_frame  the unstuffed bytes, seg_start and the scan record
+  scan_prepare_ms_per_frame   fear_jpeg_parse + fear_jpeg_scan_prepare, one thread (entropy_ms_per_frame above is the host's Huffman stage)
+  ratio_to_host           decode_fps at the fastest subsequence_bytes over the host mode's decode_fps
+Every timing is the median of --repeats runs after one warm-up run; each entry carries the minimum and maximum of the runs as well."""
 import argparse
 import glob
 import io
@@ -28,6 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 W, H, COUNT, QUALITY = 1280, 720, 256, 90
 THREADS = (1, 4, 8, 16)
+SWEEP = (32, 64, 128, 256)
 
 
 def make(directory):
@@ -46,14 +56,94 @@ def make(directory):
     print("wrote", COUNT, "files to", directory)
 
 
-def median_seconds(fn, repeats):
+def run_seconds(fn, repeats):
     fn()
     times = []
     for _ in range(repeats):
         t0 = time.perf_counter()
         fn()
         times.append(time.perf_counter() - t0)
-    return statistics.median(times)
+    return times
+
+
+def median_seconds(fn, repeats):
+    return statistics.median(run_seconds(fn, repeats))
+
+
+def spread(values, scale=1.0, digits=4):
+    return {"median": round(statistics.median(values) * scale, digits), "min": round(min(values) * scale, digits),
+            "max": round(max(values) * scale, digits)}
+
+
+def event_ms(torch, call, repeats):
+    """`call` between HIP events: the runs behind one warm-up run, in milliseconds."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = []
+    for _ in range(repeats + 1):
+        e0.record()
+        assert call() == 0
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return times[1:]
+
+
+def rounds(blobs, count):
+    """The synchronisation rounds per sequence of the first `count` files at the sweep's subsequence lengths, from the Python model."""
+    from feartracker_amd.jpeg_huffman import jpeg_entropy_parallel_host
+    out = {}
+    for sb in SWEEP:
+        seen = []
+        for b in blobs[:count]:
+            _, _, status, r = jpeg_entropy_parallel_host(b, sb, 256)
+            assert status == 0
+            seen += r
+        seen.sort()
+        out[str(sb)] = {"sequences": len(seen), "median": seen[len(seen) // 2], "p90": seen[len(seen) * 9 // 10], "max": seen[-1]}
+    return out
+
+
+def device_entropy(torch, blobs, repeats, host_fps):
+    """The figures of JpegDecoder(entropy="device") on the same files."""
+    from feartracker_amd import JpegDecoder
+    from feartracker_amd import train_abi as abi
+    n, res = len(blobs), {"decode_fps": {}, "huffman_ms": {}}
+    probe = JpegDecoder(device=0, threads=16, entropy="device")
+    res["scan_prepare_ms_per_frame"] = round(1e3 * median_seconds(lambda: [probe.scan_prepare(b) for b in blobs], repeats) / n, 4)
+    prepared = [probe.scan_prepare(b) for b in blobs]
+    up = sum(p[1].nbytes + p[2].nbytes + abi.ctypes.sizeof(p[3]) for p in prepared) / n
+    res["upload_bytes_per_frame"] = {"scan": round(up, 1), "decoded": 3 * H * W, "ratio": round(up / (3 * H * W), 4)}
+    probe.close()
+    for sb in SWEEP:
+        dec = JpegDecoder(device=0, threads=16, entropy="device", subsequence_bytes=sb)
+
+        def end_to_end():
+            frames = dec.decode(blobs, check=True)
+            torch.cuda.synchronize()
+            return frames
+        res["decode_fps"][str(sb)] = spread([n / t for t in run_seconds(end_to_end, repeats)], digits=1)
+        captured, real = {}, abi.launch
+
+        def spy(lib, name, *a):
+            captured[name] = a
+            return real(lib, name, *a)
+        abi.launch = spy
+        frames = dec.decode(blobs, check=True)
+        abi.launch = real
+        torch.cuda.synchronize()
+        res["huffman_ms"][str(sb)] = spread(event_ms(torch, lambda: dec._lib.fear_jpeg_huffman(*captured["fear_jpeg_huffman"]), repeats))
+        if sb == SWEEP[-1]:
+            # the pixel stage on the dense coefficients the call above left (the buffers are alive in the allocator's cache)
+            assert dec._lib.fear_jpeg_huffman(*captured["fear_jpeg_huffman"]) == 0
+            res["device_ms_dense"] = spread(event_ms(torch, lambda: dec._lib.fear_jpeg_decode_u8(*captured["fear_jpeg_decode_u8"]), repeats))
+        del frames
+        dec.close()
+    best = min(SWEEP, key=lambda sb: res["huffman_ms"][str(sb)]["median"])
+    res["subsequence_bytes"] = best
+    res["huffman_fps"] = round(n / (res["huffman_ms"][str(best)]["median"] * 1e-3), 1)
+    res["ratio_to_host"] = round(res["decode_fps"][str(best)]["median"] / host_fps, 3)
+    res["training_step_fps"] = 17600
+    return res
 
 
 def main():
@@ -61,14 +151,23 @@ def main():
     ap.add_argument("--dir", required=True)
     ap.add_argument("--make", action="store_true")
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--entropy", choices=("host", "device", "both"), default="host")
+    ap.add_argument("--rounds", type=int, default=0, help="no GPU: the model's synchronisation rounds on the first N files, merged into --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode_bench.json"))
     args = ap.parse_args()
     if args.make:
         return make(args.dir)
-    import torch
-    from feartracker_amd import JpegDecoder
     blobs = [open(p, "rb").read() for p in sorted(glob.glob(os.path.join(args.dir, "*.jpg")))]
     assert blobs, "no files: run with --make first"
+    if args.rounds:
+        res = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        res.setdefault("device_entropy", {})["rounds_per_sequence"] = dict(files=args.rounds, **rounds(blobs, args.rounds))
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+        print(json.dumps(res["device_entropy"]["rounds_per_sequence"]))
+        return
+    import torch
+    from feartracker_amd import JpegDecoder
     n = len(blobs)
     dec = JpegDecoder(device=0, threads=16)
     res = {"files": n, "width": W, "height": H, "quality": QUALITY, "file_bytes_per_frame": sum(map(len, blobs)) / n,
@@ -133,6 +232,11 @@ def main():
             with ThreadPoolExecutor(max_workers=t) as pool:
                 res["pillow_fps"][str(t)] = round(n / median_seconds(lambda: upload(list(pool.map(pillow, blobs))), args.repeats), 1)
     dec.close()
+    if args.entropy != "host":
+        kept = json.load(open(args.out)).get("device_entropy", {}).get("rounds_per_sequence") if os.path.exists(args.out) else None
+        res["device_entropy"] = device_entropy(torch, blobs, args.repeats, res["decode_fps"])
+        if kept:
+            res["device_entropy"]["rounds_per_sequence"] = kept
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as fh:
         json.dump(res, fh, indent=1)

@@ -1,7 +1,8 @@
 """Builds tools/jpeg_entropy_host.cpp with the address and undefined-behaviour sanitizers and runs it — a stand-alone host program, no
 Python extension and no GPU — on the fixture's files (tests/golden/jpeg_decode.npz) and on the malformed set of
 tests/test_jpeg_decode_host.py: every prefix and every flipped entropy byte of the 16 x 16 4:2:0 file, and the header faults.  Each line
-of its output is compared with the Python decoder's verdict and packed stream.  Expect "0 sanitizer reports, 0 mismatches".
+of its output is compared with the Python decoder's verdict and packed stream; a file whose headers parse has a second line, fear_jpeg_scan_prepare's, compared with
+jpeg_huffman.jpeg_scan_prepare_host.  Expect "0 sanitizer reports, 0 mismatches".
 
     python tools/jpeg_entropy_check.py [--dir SCRATCH] [--cxx g++]
 """
@@ -20,6 +21,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import jpegdec                                                   # noqa: E402
 import test_jpeg_decode_host as host_tests                       # noqa: E402
 from feartracker_amd import jpeg_frames as jf                    # noqa: E402
+from feartracker_amd import jpeg_huffman as jh                   # noqa: E402
 
 
 def fnv(h, data):
@@ -56,6 +58,20 @@ def expected(name, data):
     return f"{name} 0 0 {hd.width} {hd.height} {len(hd.ids)} {len(start) - 1} {packed.size} {h:016x}"
 
 
+def expected_scan(name, data):
+    """The program's second line for one file, or None where the headers do not parse."""
+    try:
+        hd = jf._parse(data)
+    except (jf.MalformedJPEG, jf.UnsupportedJPEG):
+        return None
+    try:
+        out, start = jh.jpeg_scan_prepare_host(data, hd)
+    except jf.MalformedJPEG:
+        return f"{name} scan {jf.ERR_FORMAT}"
+    h = fnv(fnv(14695981039346656037, np.array(start, dtype="<u4").tobytes()), out)
+    return f"{name} scan 0 {len(out)} {len(start) - 1} {h:016x}"
+
+
 def files():
     out = {f"case{i:02d}.jpg": data for i, (_, data, _) in enumerate(jpegdec.cases())}
     F = jpegdec.case("16x16_420")[1]
@@ -69,6 +85,16 @@ def files():
         out[f"flip{k:04d}.jpg"] = bytes(bad)
     for i, (what, (data, _)) in enumerate(host_tests._header_faults().items()):
         out[f"fault{i:02d}.jpg"] = data
+    import jpeghuff
+    for i, (_, data, _) in enumerate(jpeghuff.entropy_cases()):
+        out[f"entropy{i:02d}.jpg"] = data
+    # restart files: every prefix, and every marker byte replaced
+    R = jpegdec.case("15x50_420_random_q100_rst3")[1]
+    for k in range(R.index(b"\xff\xda"), len(R)):
+        out[f"rprefix{k:04d}.jpg"] = R[:k]
+        if R[k] == 0xFF and 0xD0 <= R[k + 1] <= 0xD7:
+            out[f"rmark{k:04d}.jpg"] = R[:k + 1] + bytes([0xD0 + (R[k + 1] + 1) % 8]) + R[k + 2:]
+            out[f"rgone{k:04d}.jpg"] = R[:k] + R[k + 2:]
     return out
 
 
@@ -92,9 +118,13 @@ def main():
     res = subprocess.run([exe] + [os.path.join(scratch, n) for n in names], capture_output=True, text=True)
     reports = res.stderr.count("ERROR: AddressSanitizer") + res.stderr.count("runtime error")
     lines = res.stdout.splitlines()
-    mismatches = 0 if len(lines) == len(names) else 1
-    for name, line in zip(names, lines):
-        want = expected(name, made[name])
+    wanted = []
+    for name in names:
+        scan = expected_scan(name, made[name])
+        wanted += [(name, scan)] if scan else []
+        wanted.append((name, expected(name, made[name])))
+    mismatches = 0 if len(lines) == len(wanted) else 1
+    for (name, want), line in zip(wanted, lines):
         if line != want:
             mismatches += 1
             print(f"MISMATCH {name}: program '{line}', Python '{want}'")

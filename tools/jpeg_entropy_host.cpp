@@ -7,6 +7,9 @@
 // Per file one line: name, status of fear_jpeg_parse, status of fear_jpeg_entropy_decode, width, height, components, total_blocks, values
 // stored, FNV-1a of block_start and the packed coefficients.  Every buffer is allocated at exactly the size the call is told, a second call
 // gets exactly the values the first one used, and a third one value less (it must return FEAR_TRAIN_ERR_WORKSPACE).
+// A file whose headers parse gets a second line for fear_jpeg_scan_prepare: name, "scan", its status, and where it accepts the bytes, the
+// segments and FNV-1a of seg_start and the unstuffed bytes — the first call with the file's length and segments + 1 as capacities, a
+// second with exactly the bytes the first one wrote, a third with one byte less (FEAR_TRAIN_ERR_WORKSPACE).
 // tools/jpeg_entropy_check.py writes the files, runs the program and compares each line with the Python decoder's.
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +22,45 @@ static uint64_t fnv(uint64_t h, const void* p, size_t n) {
     const unsigned char* b = static_cast<const unsigned char*>(p);
     for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
     return h;
+}
+
+static int scan_line(const char* name, const unsigned char* data, size_t n, const FearJpegInfo& info) {
+    int failures = 0;
+    const size_t n_mcu = (size_t)info.mcus_x * (size_t)info.mcus_y;
+    const size_t seg_cap = (info.restart_interval ? (n_mcu + info.restart_interval - 1) / info.restart_interval : 1) + 1;
+    unsigned char* bytes = static_cast<unsigned char*>(std::malloc(n ? n : 1));
+    uint32_t* seg = static_cast<uint32_t*>(std::malloc(seg_cap * sizeof(uint32_t)));
+    FearJpegScan* scan = static_cast<FearJpegScan*>(std::malloc(sizeof(FearJpegScan)));
+    const int rc = fear_jpeg_scan_prepare(data, n, &info, bytes, n, seg, seg_cap, scan);
+    if (rc != FEAR_TRAIN_OK) {
+        std::printf("%s scan %d\n", name, rc);
+    } else {
+        uint64_t h = fnv(14695981039346656037ull, seg, ((size_t)scan->n_seg + 1) * sizeof(uint32_t));
+        h = fnv(h, bytes, scan->n_bytes);
+        std::printf("%s scan %d %u %u %016llx\n", name, rc, scan->n_bytes, scan->n_seg, (unsigned long long)h);
+        const size_t used = scan->n_bytes;
+        unsigned char* exact = static_cast<unsigned char*>(std::malloc(used ? used : 1));
+        FearJpegScan* again = static_cast<FearJpegScan*>(std::malloc(sizeof(FearJpegScan)));
+        if (fear_jpeg_scan_prepare(data, n, &info, exact, used, seg, seg_cap, again) != FEAR_TRAIN_OK || again->n_bytes != used ||
+            std::memcmp(exact, bytes, used) != 0 || std::memcmp(again, scan, sizeof(FearJpegScan)) != 0) {
+            std::printf("%s: the scan at the exact capacity differs\n", name);
+            ++failures;
+        }
+        if (used > 0 && fear_jpeg_scan_prepare(data, n, &info, exact, used - 1, seg, seg_cap, again) != FEAR_TRAIN_ERR_WORKSPACE) {
+            std::printf("%s: a scan capacity one byte short was not refused\n", name);
+            ++failures;
+        }
+        if (fear_jpeg_scan_prepare(data, n, &info, exact, used, seg, seg_cap - 1, again) != FEAR_TRAIN_ERR_WORKSPACE) {
+            std::printf("%s: a segment capacity one entry short was not refused\n", name);
+            ++failures;
+        }
+        std::free(again);
+        std::free(exact);
+    }
+    std::free(scan);
+    std::free(seg);
+    std::free(bytes);
+    return failures;
 }
 
 int main(int argc, char** argv) {
@@ -42,6 +84,7 @@ int main(int argc, char** argv) {
             std::free(data);
             continue;
         }
+        failures += scan_line(name, data, n, info);
         const size_t cap = fear_jpeg_packed_bound(&info);
         int16_t* coef = static_cast<int16_t*>(std::malloc(cap * sizeof(int16_t)));
         uint32_t* start = static_cast<uint32_t*>(std::malloc(((size_t)info.total_blocks + 1) * sizeof(uint32_t)));
