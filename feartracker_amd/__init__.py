@@ -12,7 +12,8 @@ from .tracker import FEARTracker, Tracker, TrackingState
 from .multi_tracker import FEARMultiTracker, PendingBoxes
 from .hip_backend import FEARNetHIP, FearError, load_library, DEFAULT_WEIGHTS, LIB_PATH
 from .jpeg_frames import JpegDecoder, MalformedJPEG, UnsupportedJPEG, jpeg_decode_host, jpeg_info
-from .jpeg_huffman import jpeg_entropy_parallel_host, jpeg_scan_prepare_host
+from .jpeg_huffman import jpeg_entropy_indexed_host, jpeg_entropy_parallel_host, jpeg_scan_index_host, jpeg_scan_prepare_host
+from .jpeg_store import JpegStore, StoreFull, plan_decode
 
 __all__ = [
     "DEFAULT_TRACKING_CONFIG", "TARGET_CLASSIFICATION_KEY", "TARGET_REGRESSION_LABEL_KEY",
@@ -20,4 +21,5 @@ __all__ = [
     "FEARMultiTracker", "PendingBoxes", "YUVFrame",
     "FEARNetHIP", "FearError", "load_library", "DEFAULT_WEIGHTS", "LIB_PATH",
     "JpegDecoder", "MalformedJPEG", "UnsupportedJPEG", "jpeg_decode_host", "jpeg_info", "jpeg_entropy_parallel_host", "jpeg_scan_prepare_host",
+    "jpeg_scan_index_host", "jpeg_entropy_indexed_host", "JpegStore", "StoreFull", "plan_decode",
 ]

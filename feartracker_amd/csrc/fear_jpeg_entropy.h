@@ -434,6 +434,25 @@ int fear_jpeg_scan_prepare(const uint8_t* data, size_t n, const FearJpegInfo* in
     return FEAR_TRAIN_OK;
 }
 
+// The subsequences of a prepared scan, for its index (fear_jpeg_store.h): segment s has ceil(bytes / subsequence_bytes) of them, and
+// sub_start holds the prefix sums.  Reads seg_start[0 .. n_seg], writes sub_start[0 .. n_seg] where it is given.
+int fear_jpeg_sub_start(const uint32_t* seg_start, uint32_t n_seg, uint32_t n_bytes, int subsequence_bytes, uint32_t* sub_start,
+                        size_t sub_cap, uint32_t* n_sub) {
+    if (!seg_start || !n_sub) return FEAR_TRAIN_ERR_NULL;
+    if (subsequence_bytes < 4 || subsequence_bytes > 1024 || (subsequence_bytes & 3) != 0) return FEAR_TRAIN_ERR_SHAPE;
+    if (sub_start && sub_cap < (size_t)n_seg + 1) return FEAR_TRAIN_ERR_WORKSPACE;
+    if (n_seg == 0 || seg_start[0] != 0 || seg_start[n_seg] != n_bytes) return FEAR_TRAIN_ERR_SHAPE;   // not this scan's offsets
+    uint64_t total = 0;
+    for (uint32_t s = 0; s < n_seg; ++s) {
+        if (seg_start[s + 1] < seg_start[s]) return FEAR_TRAIN_ERR_SHAPE;
+        if (sub_start) sub_start[s] = (uint32_t)total;
+        total += ((uint64_t)(seg_start[s + 1] - seg_start[s]) + (uint32_t)subsequence_bytes - 1) / (uint32_t)subsequence_bytes;
+    }
+    if (sub_start) sub_start[n_seg] = (uint32_t)total;                   // at most 2^32 - 1 bytes in all, at least 4 per subsequence
+    *n_sub = (uint32_t)total;
+    return FEAR_TRAIN_OK;
+}
+
 }  // extern "C"
 
 #endif  // FEAR_JPEG_ENTROPY_H

@@ -26,6 +26,7 @@ struct JpegHuffArgs {
     int16_t* coef;
     int32_t* status;
     int n, subsequence_bits;
+    const FearJpegIndex* indexes;   // fear_jpeg_index_build alone (fear_jpeg_store.h): the device copy of the n index records
 };
 
 // What is the same for every lane of a workgroup: its segment and its image's geometry.
@@ -204,6 +205,19 @@ __device__ __forceinline__ JhState jh_decode(const JhSegment& s, const FearJpegH
     return out;
 }
 
+// The entry of subsequence `sub` of segment `seg`: the state and the lane with which its write pass starts, one 16-byte store, checked
+// against the index's capacity.
+__device__ __forceinline__ void jh_store_entry(const FearJpegIndex& ix, uint32_t seg, uint32_t sub, JhState entry, const JhLane& lane) {
+    const uint64_t at = (uint64_t)ix.sub_start[seg] + sub;
+    if (at >= ix.n_sub) return;
+    uint4 e;
+    e.x = entry.p;
+    e.y = lane.begun;
+    e.z = (entry.sz & 0xFFFFu) | lane.dc0 << 16;
+    e.w = (lane.dc1 & 0xFFFFu) | lane.dc2 << 16;
+    reinterpret_cast<uint4*>(ix.index)[at] = e;
+}
+
 __global__ __launch_bounds__(kJhLanes) void jpeg_huffman_status_kernel(int32_t* status, int n) {
     const int i = blockIdx.x * kJhLanes + threadIdx.x;
     if (i < n) status[i] = FEAR_TRAIN_OK;
@@ -214,6 +228,8 @@ __global__ __launch_bounds__(kJhLanes) void jpeg_dense_block_start_kernel(uint32
     if (i <= total_blocks) block_start[i] = i * 64u;
 }
 
+// INDEX: fear_jpeg_index_build's instantiation, which also stores every lane's entry in front of its write pass (fear_jpeg_store.h).
+template <bool INDEX>
 __global__ __launch_bounds__(kJhLanes) void jpeg_huffman_kernel(JpegHuffArgs a) {
     __shared__ __attribute__((aligned(16))) FearJpegHuff tabs[6];        // dc by component, then ac by component
     __shared__ uint32_t st_p[kJhLanes], st_sz[kJhLanes];                 // the exit state of each subsequence of the sequence
@@ -320,6 +336,7 @@ __global__ __launch_bounds__(kJhLanes) void jpeg_huffman_kernel(JpegHuffArgs a) 
         lane.dc0 = (pred[0] + scan[cur][1][tid] - own[1]) & 0xFFFFu;
         lane.dc1 = (pred[1] + scan[cur][2][tid] - own[2]) & 0xFFFFu;
         lane.dc2 = (pred[2] + scan[cur][3][tid] - own[3]) & 0xFFFFu;
+        if (INDEX && on) jh_store_entry(a.indexes[img], seg, sub, entry, lane);
         if (on) jh_decode<2>(s, tabs, entry, (sub + 1) * SB, coef, lane);
         begun += total[0];
 #pragma unroll
@@ -372,7 +389,7 @@ int fear_jpeg_huffman(const FearJpegScan* scans, int n, const void* table_dev, i
     hipLaunchKernelGGL(jpeg_huffman_status_kernel, dim3((unsigned)((n + kJhLanes - 1) / kJhLanes)), dim3(kJhLanes), 0,
                        static_cast<hipStream_t>(stream), status_dev, n);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(jpeg_huffman_kernel, dim3((unsigned)groups), dim3(kJhLanes), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(jpeg_huffman_kernel<false>, dim3((unsigned)groups), dim3(kJhLanes), 0, static_cast<hipStream_t>(stream), a);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }

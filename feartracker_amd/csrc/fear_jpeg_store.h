@@ -1,0 +1,173 @@
+// fear_jpeg_store.h — scans resident on the device and the index a baseline scan lacks (include/fear_train.h: fear_jpeg_index_build,
+// fear_jpeg_huffman_indexed; DESIGN.md section 14, "The resident store").  fear_jpeg_index_build is the second instantiation of
+// jpeg_huffman_kernel (fear_jpeg_huffman.h), which stores every lane's true entry in front of its write pass.  With those entries a later
+// decode is the write pass alone: jpeg_huffman_indexed_kernel gives every subsequence of an image a lane of its own, whatever segment it
+// lies in.  jpeg_huffman.jpeg_scan_index_host and jpeg_entropy_indexed_host restate both in Python.
+// Included by fear_train.hip behind fear_jpeg_huffman.h, whose jh_decode, jh_peek, jh_block_base and JhSegment it uses, and
+// fear_jpeg_decode.h's jd_find_image.
+
+namespace {
+
+struct JpegIndexedArgs {
+    const uint32_t* table;   // the caller's device table: n + 1 prefix sums of workgroups, padding, n FearJpegIndexed records
+    int16_t* coef;
+    int32_t* status;
+    int n, subsequence_bits;
+};
+
+__device__ __forceinline__ const FearJpegIndexed* ji_records(const JpegIndexedArgs& a) {
+    return reinterpret_cast<const FearJpegIndexed*>(reinterpret_cast<const char*>(a.table) + FEAR_JPEG_SCAN_TABLE_RECORDS(a.n));
+}
+
+// The statuses' zeros; an image without a subsequence has no lane to judge it and owes blocks: it fails here.
+__global__ __launch_bounds__(kJhLanes) void jpeg_indexed_status_kernel(JpegIndexedArgs a) {
+    const int i = blockIdx.x * kJhLanes + threadIdx.x;
+    if (i < a.n) a.status[i] = ji_records(a)[i].n_sub == 0 ? FEAR_TRAIN_ERR_FORMAT : FEAR_TRAIN_OK;
+}
+
+__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_kernel(JpegIndexedArgs a) {
+    __shared__ __attribute__((aligned(16))) FearJpegHuff tabs[6];        // dc by component, then ac by component
+    const int tid = threadIdx.x;
+    const int img = jd_find_image(a.table, a.n, blockIdx.x);             // the same for the whole workgroup
+    const FearJpegIndexed* im = ji_records(a) + img;
+    const FearJpegScan* rec = im->scan;
+    {
+        const uint4* src = reinterpret_cast<const uint4*>(rec->dc);      // the record is 16-byte aligned, the tables lie 64 bytes in
+        uint4* dst = reinterpret_cast<uint4*>(tabs);
+        for (int i = tid; i < (int)(sizeof(tabs) / 16); i += kJhLanes) dst[i] = src[i];
+    }
+    __syncthreads();                                                     // the only barrier
+    const uint32_t n_sub = im->n_sub, n_seg = rec->n_seg;
+    const uint64_t sub64 = (uint64_t)(blockIdx.x - a.table[img]) * kJhLanes + (uint32_t)tid;
+    if (sub64 >= n_sub || n_seg == 0) return;
+    const uint32_t sub = (uint32_t)sub64;
+    const uint4 e = reinterpret_cast<const uint4*>(im->index)[sub];
+    // the last segment that starts at or in front of `sub`: n_seg <= 2^20
+    const uint32_t* sub_start = im->sub_start;
+    uint32_t seg = 0, hi = n_seg;
+#pragma unroll 1
+    for (int step = 0; step < 21 && hi - seg > 1; ++step) {
+        const uint32_t mid = (seg + hi) >> 1;
+        if (sub_start[mid] <= sub) seg = mid; else hi = mid;
+    }
+    const uint32_t first = sub_start[seg];
+    const uint32_t SB = (uint32_t)a.subsequence_bits;
+    JhSegment s;
+    {
+        const uint32_t n_bytes = rec->n_bytes;
+        const uint32_t b0 = min(rec->seg_start[seg], n_bytes), b1 = min(max(rec->seg_start[seg + 1], b0), n_bytes);
+        s.words = reinterpret_cast<const uint32_t*>(rec->bytes);
+        s.n_words = (n_bytes + 3) >> 2;
+        s.byte0 = b0;
+        s.bits = min(b1 - b0, FEAR_JPEG_DEVICE_SCAN_MAX) * 8u;
+        const int nf = rec->components;
+        s.h = max(rec->h, 1);
+        s.v = max(rec->v, 1);
+        s.hv = nf == 3 ? min(s.h * s.v, 4) : 1;
+        s.nslots = nf == 3 ? s.hv + 2 : 1;
+        s.mcus_x = max(rec->mcus_x, 1);
+        const uint32_t n_mcu = (uint32_t)s.mcus_x * (uint32_t)max(rec->mcus_y, 1);
+        s.n0 = n_mcu * (uint32_t)s.hv;
+        s.nc = n_mcu;
+        s.total_blocks = rec->total_blocks;
+        const uint32_t interval = rec->restart_interval > 0 ? (uint32_t)rec->restart_interval : n_mcu;
+        const uint64_t first_mcu = (uint64_t)seg * interval;
+        s.first_mcu = first_mcu < n_mcu ? (uint32_t)first_mcu : n_mcu;
+        s.expected = min(interval, n_mcu - s.first_mcu) * (uint32_t)s.nslots;
+        s.last = seg + 1 == n_seg;
+    }
+    int32_t* status = a.status + img;
+    const uint64_t k = (uint64_t)sub - first;                            // the subsequence within its segment
+    if (first > sub || k * SB >= s.bits) {                               // an index that is not this scan's
+        *status = FEAR_TRAIN_ERR_FORMAT;
+        return;
+    }
+    JhState entry;
+    entry.p = e.x;
+    entry.sz = min((e.z >> 8) & 0xFFu, (uint32_t)s.nslots - 1u) << 8 | min(e.z & 0xFFu, 63u);
+    JhLane lane{};
+    lane.begun = e.y;
+    lane.dc0 = e.z >> 16;
+    lane.dc1 = e.w & 0xFFFFu;
+    lane.dc2 = e.w >> 16;
+    const uint32_t end = ((uint32_t)k + 1u) * SB;                        // k SB < bits <= 2^27 (8 FEAR_JPEG_DEVICE_SCAN_MAX), SB <= 2^13: no overflow
+    const JhState out = jh_decode<2>(s, tabs, entry, end, a.coef + im->coef_offset, lane);
+    bool failed = lane.error;
+    // the segment's last subsequence: fewer complete blocks than the segment owes, as jpeg_huffman_kernel judges its true chain's end
+    if (end >= s.bits && (lane.begun - ((out.sz & 255) != 0 ? 1u : 0u) < s.expected || (lane.begun == 0 && s.expected > 0))) failed = true;
+    if (k == 0 && seg > 0 && sub_start[seg - 1] == first) failed = true;  // an empty segment in front owes blocks
+    if (sub + 1 == n_sub && !s.last) failed = true;                       // empty segments behind the image's last subsequence
+    if (failed) *status = FEAR_TRAIN_ERR_FORMAT;                          // every lane that stores stores the same value
+}
+
+}  // namespace
+
+extern "C" {
+
+int fear_jpeg_index_build(const FearJpegScan* scans, int n, const void* table_dev, const FearJpegIndex* indexes, const void* index_table_dev,
+                          int16_t* coef, int32_t* status_dev, int subsequence_bytes, void* stream) {
+    if (n < 0 || n > 65535 || subsequence_bytes < 4 || subsequence_bytes > 1024 || (subsequence_bytes & 3) != 0) return FEAR_TRAIN_ERR_SHAPE;
+    if (n == 0) return FEAR_TRAIN_OK;
+    if (!scans || !table_dev || !indexes || !index_table_dev || !coef || !status_dev) return FEAR_TRAIN_ERR_NULL;
+    uint64_t groups = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!scans[i].bytes || !scans[i].seg_start) return FEAR_TRAIN_ERR_NULL;
+        if (!jh_scan_ok(scans[i])) return FEAR_TRAIN_ERR_SHAPE;
+        groups += scans[i].n_seg;
+    }
+    if (groups > 0x7fffffffu) return FEAR_TRAIN_ERR_SHAPE;
+    for (int i = 0; i < n; ++i) {
+        const FearJpegIndex& ix = indexes[i];
+        if (!ix.sub_start || !ix.seg_start_host || (!ix.index && ix.n_sub != 0)) return FEAR_TRAIN_ERR_NULL;
+        if ((reinterpret_cast<uintptr_t>(ix.index) & 15) != 0 || (reinterpret_cast<uintptr_t>(ix.sub_start) & 3) != 0) return FEAR_TRAIN_ERR_SHAPE;
+        uint32_t n_sub = 0;                                               // the host's count (fear_jpeg_entropy.h), from the host's seg_start
+        if (fear_jpeg_sub_start(ix.seg_start_host, scans[i].n_seg, scans[i].n_bytes, subsequence_bytes, nullptr, 0, &n_sub) != FEAR_TRAIN_OK ||
+            n_sub != ix.n_sub)
+            return FEAR_TRAIN_ERR_SHAPE;
+    }
+    JpegHuffArgs a{};
+    a.table = static_cast<const uint32_t*>(table_dev);
+    a.coef = coef;
+    a.status = status_dev;
+    a.n = n;
+    a.subsequence_bits = subsequence_bytes * 8;
+    a.indexes = static_cast<const FearJpegIndex*>(index_table_dev);
+    hipLaunchKernelGGL(jpeg_huffman_status_kernel, dim3((unsigned)((n + kJhLanes - 1) / kJhLanes)), dim3(kJhLanes), 0,
+                       static_cast<hipStream_t>(stream), status_dev, n);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(jpeg_huffman_kernel<true>, dim3((unsigned)groups), dim3(kJhLanes), 0, static_cast<hipStream_t>(stream), a);
+    LAUNCH_CHECK();
+    return FEAR_TRAIN_OK;
+}
+
+int fear_jpeg_huffman_indexed(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
+                              int subsequence_bytes, void* stream) {
+    if (n < 0 || n > 65535 || subsequence_bytes < 4 || subsequence_bytes > 1024 || (subsequence_bytes & 3) != 0) return FEAR_TRAIN_ERR_SHAPE;
+    if (n == 0) return FEAR_TRAIN_OK;
+    if (!images || !table_dev || !coef || !status_dev) return FEAR_TRAIN_ERR_NULL;
+    uint64_t groups = 0;
+    for (int i = 0; i < n; ++i) {
+        const FearJpegIndexed& im = images[i];
+        if (!im.scan || !im.sub_start || (!im.index && im.n_sub != 0)) return FEAR_TRAIN_ERR_NULL;
+        if ((reinterpret_cast<uintptr_t>(im.index) & 15) != 0 || (reinterpret_cast<uintptr_t>(im.scan) & 15) != 0 ||
+            (reinterpret_cast<uintptr_t>(im.sub_start) & 3) != 0)
+            return FEAR_TRAIN_ERR_SHAPE;
+        groups += ((uint64_t)im.n_sub + kJhLanes - 1) / kJhLanes;
+    }
+    if (groups > 0x7fffffffu) return FEAR_TRAIN_ERR_SHAPE;
+    JpegIndexedArgs a{};
+    a.table = static_cast<const uint32_t*>(table_dev);
+    a.coef = coef;
+    a.status = status_dev;
+    a.n = n;
+    a.subsequence_bits = subsequence_bytes * 8;
+    hipLaunchKernelGGL(jpeg_indexed_status_kernel, dim3((unsigned)((n + kJhLanes - 1) / kJhLanes)), dim3(kJhLanes), 0,
+                       static_cast<hipStream_t>(stream), a);
+    LAUNCH_CHECK();
+    if (groups == 0) return FEAR_TRAIN_OK;
+    hipLaunchKernelGGL(jpeg_huffman_indexed_kernel, dim3((unsigned)groups), dim3(kJhLanes), 0, static_cast<hipStream_t>(stream), a);
+    LAUNCH_CHECK();
+    return FEAR_TRAIN_OK;
+}
+
+}  // extern "C"

@@ -2226,5 +2226,6 @@ int fear_adam_step(float* param, const float* grad, float* exp_avg, float* exp_a
 #include "fear_jpeg_entropy.h"
 #include "fear_jpeg_decode.h"
 #include "fear_jpeg_huffman.h"
+#include "fear_jpeg_store.h"
 #include "fear_train_metrics.h"
 #include "fear_train_optim.h"

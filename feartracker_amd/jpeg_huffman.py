@@ -251,3 +251,145 @@ def jpeg_entropy_parallel_host(data: bytes, subsequence_bytes: int = 128, lanes:
         coef.append(dense[64 * at:64 * (at + size)].reshape(hd.blocks_h[c], hd.blocks_w[c], 64))
         at += size
     return hd, coef, status, rounds
+
+
+# ------------------------------------------------------------------------------------------------------- the index of a resident scan
+# One entry per subsequence, 16 bytes: include/fear_train.h FearJpegSubseq.  `p` is the true entry bit position in the segment (it may
+# lie up to 30 bits behind the subsequence's first bit: the last symbol of the subsequence in front ends there), `sz` is slot << 8 | z,
+# `begun` the blocks begun in the segment in front of the subsequence, `dc` the three predictors at its entry modulo 2^16 — the JhState
+# and JhLane with which the write pass of jpeg_huffman_kernel starts the lane.
+SUBSEQ_DTYPE = np.dtype([("p", "<u4"), ("begun", "<u4"), ("sz", "<u2"), ("dc", "<u2", (3,))])
+assert SUBSEQ_DTYPE.itemsize == 16
+
+
+def scan_sub_start(seg_start, subsequence_bytes: int) -> np.ndarray:
+    """uint32 [n_seg + 1]: segment s owns the subsequences sub_start[s] .. sub_start[s + 1]) of its image, ceil(bytes / subsequence_bytes)
+    of them."""
+    seg = np.asarray(seg_start, dtype=np.int64)
+    out = np.zeros(seg.size, dtype=np.uint32)
+    np.cumsum(-(-(seg[1:] - seg[:-1]) // int(subsequence_bytes)), out=out[1:])
+    return out
+
+
+class _Segment:
+    """What a lane of the write pass knows of its segment (JhSegment)."""
+
+    def __init__(self, hd: _Header, g: _Geometry, stream: bytes, seg_start, s: int):
+        per_segment = hd.restart if hd.restart else g.n_mcu
+        self.buf = stream[seg_start[s]:seg_start[s + 1]] + bytes(8)
+        self.L = 8 * (seg_start[s + 1] - seg_start[s])
+        self.first_mcu = s * per_segment
+        self.expected = min(per_segment, g.n_mcu - self.first_mcu) * g.nslots
+        self.last = s == len(seg_start) - 2
+
+
+def _write_pass(sg: _Segment, g: _Geometry, entry, end: int, begun: int, pred: list, dense, writes):
+    """One lane of the write pass: decode from the true `entry` = (p, slot, z) to `end`, `begun` blocks of the segment begun in front
+    and `pred` the predictors (updated in place).  Stores what it decodes, judges it, and returns (exit state, begun, failed)."""
+    ev, failed = [], False
+    out = _decode(sg.buf, sg.L, entry, end, g, ev)
+    slot, is_open = entry[1], entry[2] != 0                              # a block begun in an earlier subsequence is still open
+    for e in ev:
+        kind = e[0]
+        if kind == _ERR:
+            if begun - is_open < sg.expected:                            # in the open block, or in the one that would begin here
+                failed = True
+            is_open = False
+            continue
+        if kind == _END:
+            is_open = False
+            if begun == sg.expected and not sg.last and sg.L - e[1] >= 8:
+                failed = True                                            # whole bytes in front of the marker: Bits::restart
+            continue
+        if kind == _DC:
+            slot, c = e[1], g.comp[e[1]]
+            pred[c] = (pred[c] + e[2]) & 0xFFFF                          # JCOEF is 16 bits wide
+            begun, is_open = begun + 1, True
+            z0, z1, value = 0, 1, pred[c] - 0x10000 if pred[c] >= 0x8000 else pred[c]
+        elif kind == _ZEROS:
+            z0, z1, value = e[1], e[2], 0
+        else:
+            z0, z1, value = e[1], e[1] + 1, e[2]
+        if 1 <= begun <= sg.expected:                                    # blocks past the segment's count are dropped
+            if e[-1] > sg.L:                                             # the symbol or its magnitude bits run past the segment
+                failed = True
+            b = g.block(sg.first_mcu, begun - 1, slot)
+            if dense is not None and b < g.total_blocks:
+                dense[64 * b + z0:64 * b + z1] = value
+                writes[64 * b + z0:64 * b + z1] += 1
+    return out, begun, failed
+
+
+def _check_subsequence_bytes(subsequence_bytes: int) -> None:
+    if subsequence_bytes % 4 or not 4 <= subsequence_bytes <= 1024:
+        raise ValueError("subsequence_bytes is a multiple of 4 in 4..1024")
+
+
+def jpeg_scan_index_host(data: bytes, subsequence_bytes: int = 128):
+    """The contract of `fear_jpeg_index_build`: (header, sub_start, index, status).  Subsequences are numbered per image, segment after
+    segment; `index[sub_start[s] + i]` is the true entry of subsequence i of segment s (SUBSEQ_DTYPE); `status` is
+    `jpeg_entropy_parallel_host`'s verdict, judged on the way.  What the kernel finds by synchronising, counting and a prefix, the
+    sequential walk here finds directly: the true chain is the same."""
+    _check_subsequence_bytes(subsequence_bytes)
+    data = bytes(data)
+    hd = _parse(data)
+    stream, seg_start = jpeg_scan_prepare_host(data, hd)
+    g = _Geometry(hd)
+    SB, status = 8 * subsequence_bytes, 0
+    sub_start = scan_sub_start(seg_start, subsequence_bytes)
+    index = np.zeros(int(sub_start[-1]), dtype=SUBSEQ_DTYPE)
+    for s in range(len(seg_start) - 1):
+        sg = _Segment(hd, g, stream, seg_start, s)
+        state, begun, pred = (0, 0, 0), 0, [0, 0, 0]
+        for i in range(-(-sg.L // SB)):
+            index[int(sub_start[s]) + i] = (state[0], begun, state[1] << 8 | state[2], tuple(pred))
+            state, begun, failed = _write_pass(sg, g, state, (i + 1) * SB, begun, pred, None, None)
+            if failed:
+                status = ERR_FORMAT
+        if begun - (state[2] != 0) < sg.expected:                        # fewer complete blocks than the segment owes
+            status = ERR_FORMAT
+    return hd, sub_start, index, status
+
+
+def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: int, order=None):
+    """The contract of `fear_jpeg_huffman_indexed`: (coefficients per component, status).  Every subsequence is decoded from its index
+    entry alone, in `order` (any permutation of the image's subsequences; the natural one by default), as one lane of
+    jpeg_huffman_indexed_kernel does it: the segment by a search of `sub_start`, the write pass's rules, and the verdict — the lane of a
+    segment's last subsequence judges the segment's block count, the lane of its first an empty segment in front, the lane of the
+    image's last subsequence empty segments behind, and an image without a subsequence fails.  Asserts that every position is written
+    exactly once when the status is 0."""
+    _check_subsequence_bytes(subsequence_bytes)
+    data = bytes(data)
+    hd = _parse(data)
+    stream, seg_start = jpeg_scan_prepare_host(data, hd)
+    g = _Geometry(hd)
+    n_seg, n_sub, SB = len(seg_start) - 1, len(index), 8 * subsequence_bytes
+    sub_start = np.asarray(sub_start, dtype=np.int64)
+    assert sub_start.size == n_seg + 1 and int(sub_start[-1]) == n_sub
+    dense = np.zeros(64 * g.total_blocks, dtype=np.int16)
+    writes = np.zeros(64 * g.total_blocks, dtype=np.uint8)
+    segs = [_Segment(hd, g, stream, seg_start, s) for s in range(n_seg)]
+    status = ERR_FORMAT if n_sub == 0 else 0
+    for sub in (range(n_sub) if order is None else order):
+        sub = int(sub)
+        s = int(np.searchsorted(sub_start[:n_seg], sub, side="right")) - 1   # the last segment that starts at or in front of `sub`
+        sg, i, e = segs[s], sub - int(sub_start[s]), index[sub]
+        slot, z = min(int(e["sz"]) >> 8, g.nslots - 1), min(int(e["sz"]) & 255, 63)
+        pred = [int(v) for v in e["dc"]]
+        state, begun, failed = _write_pass(sg, g, (int(e["p"]), slot, z), (i + 1) * SB, int(e["begun"]), pred, dense, writes)
+        if (i + 1) * SB >= sg.L and begun - (state[2] != 0) < sg.expected:    # the segment's last subsequence: its block count
+            failed = True
+        if i == 0 and s > 0 and sub_start[s - 1] == sub_start[s]:            # an empty segment in front owes blocks
+            failed = True
+        if sub == n_sub - 1 and s != n_seg - 1:                              # empty segments behind the last subsequence
+            failed = True
+        if failed:
+            status = ERR_FORMAT
+    if status == 0:
+        assert np.all(writes == 1), "every position of every block is written exactly once"
+    coef, at = [], 0
+    for c in range(g.nf):
+        size = hd.blocks_w[c] * hd.blocks_h[c]
+        coef.append(dense[64 * at:64 * (at + size)].reshape(hd.blocks_h[c], hd.blocks_w[c], 64))
+        at += size
+    return coef, status

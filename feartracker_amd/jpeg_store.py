@@ -1,0 +1,422 @@
+"""JPEG files resident on the device ("The resident store").
+
+A training run decodes the same files every epoch.  `JpegStore.add` prepares them once — `fear_jpeg_parse` and `fear_jpeg_scan_prepare` on
+host threads, the unstuffed bytes uploaded into device slabs — and builds once the index that a baseline scan lacks
+(`fear_jpeg_index_build`: the true entry of every subsequence, 16 bytes each, kept next to the bytes).  `JpegStore.decode` then runs
+`fear_jpeg_huffman_indexed`, a single write pass with one lane per subsequence, and the unchanged `fear_jpeg_decode_u8`; the host's share
+of a call is a few numpy gathers over the ids (`plan_decode`) and one small pinned upload.  jpeg_huffman.jpeg_scan_index_host and
+jpeg_entropy_indexed_host state the two device calls in Python."""
+from __future__ import annotations
+
+import ctypes
+from typing import Callable, List, Optional, Sequence
+
+import numpy as np
+
+from . import jpeg_frames
+from .jpeg_frames import ERR_UNSUPPORTED, Item, JpegDecoder, MalformedJPEG, UnsupportedJPEG, _raise_as_python
+from .jpeg_huffman import _check_subsequence_bytes
+
+KIND_SCAN, KIND_PIXELS = 0, 1
+KIND_NAMES = np.array(["scan", "pixels"])
+LANES = 256                                   # csrc/fear_jpeg_store.h: subsequences per workgroup of jpeg_huffman_indexed_kernel
+COLUMNS = np.dtype([("n_seg", "<u4"), ("n_sub", "<u4"), ("total_blocks", "<u4"), ("H", "<i4"), ("W", "<i4"), ("kind", "u1")])
+
+
+class StoreFull(MemoryError):
+    """An `add` would take the store above its `capacity_bytes`; nothing of the call was stored."""
+
+
+def _up(x, to):
+    return -(-x // to) * to
+
+
+def _exclusive(a):
+    out = np.zeros(a.size + 1, dtype=np.int64)
+    np.cumsum(a, out=out[1:])
+    return out
+
+
+def plan_decode(columns: np.ndarray, ids, workspace_limit: int, max_group: int = 65535) -> List[dict]:
+    """The host's share of `JpegStore.decode` but the records: a pure function of the mirror's integer columns (COLUMNS, one row per
+    entry) and the ids, any order, repeats allowed.  The call is cut into groups of consecutive positions lo..hi as JpegDecoder cuts it:
+    a group takes positions while the dense coefficients of its "scan" entries (128 bytes per block) stay within `workspace_limit`, at
+    least one and at most `max_group`.  Per group, over its "scan" positions `scan` (relative to lo):
+        sub_prefix    uint32 [nd + 1]  prefix sums of ceil(n_sub / 256): fear_jpeg_huffman_indexed's workgroups
+        block_prefix, pixel_prefix     fear_jpeg_decode_u8's two prefix tables
+        coef_offset   values from the group's coefficient buffer to each image's 64 total_blocks; `values` their sum
+        plane_offset  bytes from the workspace to each image's planes, multiples of 16; `workspace_bytes` what the pixel stage needs
+        most          the largest total_blocks
+    and over all its positions `out_offset`, multiples of 16, and `out_bytes`.  No loop over the files: gathers and prefix sums."""
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    rows = columns[ids]
+    is_scan = rows["kind"] == KIND_SCAN
+    blocks = rows["total_blocks"].astype(np.int64)
+    pixels = rows["H"].astype(np.int64) * rows["W"].astype(np.int64)
+    need = _exclusive(np.where(is_scan, 128 * blocks, 0))
+    groups, lo, n = [], 0, ids.size
+    while lo < n:                                                       # one turn per group
+        hi = int(np.searchsorted(need, need[lo] + max(int(workspace_limit), 0), side="right")) - 1
+        hi = min(max(hi, lo + 1), n, lo + max_group)
+        scan = np.flatnonzero(is_scan[lo:hi])
+        b, px = blocks[lo:hi][scan], pixels[lo:hi][scan]
+        dense = _exclusive(64 * b)
+        out = _exclusive(_up(3 * pixels[lo:hi], 16))
+        groups.append(dict(
+            lo=lo, hi=hi, scan=scan,
+            sub_prefix=_exclusive(-(-rows["n_sub"][lo:hi][scan].astype(np.int64) // LANES)).astype(np.uint32),
+            block_prefix=_exclusive(-(-b // 32)).astype(np.uint32), pixel_prefix=_exclusive(-(-px // 256)).astype(np.uint32),
+            coef_offset=dense[:-1].astype(np.uint64), values=int(dense[-1]),
+            plane_offset=dense[:-1].astype(np.uint64), workspace_bytes=16 + int(dense[-1]),
+            most=int(b.max()) if b.size else 0,
+            out_offset=out[:-1], out_bytes=int(out[-1])))
+        lo = hi
+    return groups
+
+
+class JpegStore:
+    """Baseline JPEG files kept on the device, decoded by id: uint8 (H, W, 3) RGB device tensors, byte for byte what `JpegDecoder` and
+    libjpeg decode.
+
+        store = JpegStore(device=0)
+        ids = store.add(paths_or_bytes)            # np.int64 ids, in order
+        frames = store.decode(ids[perm])           # as JpegDecoder.decode returns them
+
+    `add` is set-up and SYNCHRONISES: it parses and prepares the files on `threads` host threads, judges every file before anything is
+    stored (a header or marker fault raises `JpegDecoder`'s exception, naming the item), uploads each file's unstuffed bytes, its
+    `seg_start`, its `sub_start` and its `FearJpegScan` record into slabs of `slab_bytes` (uint8 tensors that are never reallocated, so
+    addresses stay valid; a file never straddles a slab, a larger file gets a slab of its own), runs `fear_jpeg_index_build` over the
+    call's files in groups bounded by `workspace_limit`, and waits for the verdicts: a file the device refuses raises
+    `MalformedJPEG("item i: ...")`.  A call that raises commits nothing — `len(store)`, `nbytes` and every earlier id are as before; above
+    `capacity_bytes` (counted as `nbytes` counts: the files' aligned resident bytes) it raises `StoreFull`.
+    `store.kinds[id]` is "scan" or "pixels": an unsupported file with a `fallback` (without one: `UnsupportedJPEG`) and a file whose
+    largest restart segment exceeds DEVICE_SCAN_MAX (decoded once through the host's Huffman stage) are kept as decoded pixels, which
+    `decode` copies device to device.  Every returned frame is a private tensor, never an alias of the store.
+
+    `decode` runs on the current stream and never waits for the GPU: no file bytes go up, only about 0.5 kB of records per image in one
+    pinned transfer; `fear_jpeg_dense_block_start` (only when the store's largest image grew), `fear_jpeg_huffman_indexed`,
+    `fear_jpeg_decode_u8`; split by `workspace_limit` as the decoder splits.  Ids come in any order and may repeat; one out of range is
+    an IndexError before any launch.  The statuses are kept and `check()` raises as `JpegDecoder.check` does — with a resident, verified
+    store it should never fire.  The statuses of every group of the current call are kept, however small `workspace_limit` makes them,
+    and those of the last PENDING_CALLS groups of earlier unchecked calls.  `decode` may be called on any stream (the shared block_start
+    table is handed from stream to stream by an event); `add` ends with a synchronise, so what it stored is complete for all of them.
+    Out of scope: eviction and `remove`, saving a store to disk, sharding over ranks, progressive files, and `JpegDecoder`'s default."""
+    PENDING_CALLS = 64
+
+    def __init__(self, device: int = 0, capacity_bytes: Optional[int] = None, subsequence_bytes: int = 128, slab_bytes: int = 256 << 20,
+                 workspace_limit: int = 1 << 30, threads: Optional[int] = None, initial_rows: int = 1024):
+        from .train_abi import FearJpegImage, FearJpegIndexed
+        _check_subsequence_bytes(subsequence_bytes)
+        if slab_bytes < 16 or initial_rows < 1:
+            raise ValueError("slab_bytes is at least 16 and initial_rows at least 1")
+        self._host = JpegDecoder(device=device, threads=threads)   # the pool, sized as JpegDecoder sizes it: never by the machine's CPUs, at most 16
+        self.threads, self.device, self._lib = self._host.threads, self._host.device, self._host._lib
+        self.capacity_bytes = None if capacity_bytes is None else int(capacity_bytes)
+        self.subsequence_bytes, self.slab_bytes, self.workspace_limit = int(subsequence_bytes), _up(int(slab_bytes), 16), int(workspace_limit)
+        self._dtypes = (np.dtype(FearJpegIndexed), np.dtype(FearJpegImage), COLUMNS)
+        self._initial_rows = int(initial_rows)
+        self._pending: List = []
+        self._pinned: List = []
+        self.clear()
+
+    # ------------------------------------------------------------------------------------------------------------------ bookkeeping
+    def clear(self) -> None:
+        """Forget every entry and free the slabs.  Ids start at 0 again."""
+        self._n, self.nbytes = 0, 0
+        self.resident = dict(bytes=0, index=0, records=0, pixels=0)      # what nbytes is made of
+        self._indexed, self._image, self._columns = (np.zeros(self._initial_rows, dtype=d) for d in self._dtypes)
+        self._slabs: List = []
+        self._open, self._cursor = None, 0                               # the slab that is being filled
+        self._pixels: dict = {}
+        self._most, self._dense_start, self._dense_blocks, self._dense_event = 0, None, -1, None
+        self._dense_retired: List = []                                   # earlier block_start tables: a decode in flight may still read one
+        self._records = None                                             # the last group's host records, alive as long as the addresses are
+
+    def close(self) -> None:
+        self._host.close()
+        self.clear()
+
+    def __len__(self) -> int:
+        return self._n
+
+    @property
+    def kinds(self) -> np.ndarray:
+        return KIND_NAMES[self._columns["kind"][:self._n]]
+
+    def shape(self, ids) -> np.ndarray:
+        """(len(ids), 2) int32: height and width."""
+        rows = self._columns[self._checked(ids)]
+        return np.stack([rows["H"], rows["W"]], axis=1)
+
+    def _checked(self, ids) -> np.ndarray:
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= self._n):
+            raise IndexError(f"an id outside 0..{self._n - 1}")
+        return ids
+
+    def _grow(self, rows: int) -> None:
+        """The mirrors double until `rows` fit; old rows keep their place, so old ids stay valid."""
+        have = self._columns.size
+        if rows <= have:
+            return
+        while have < rows:
+            have *= 2
+        grown = []
+        for old in (self._indexed, self._image, self._columns):
+            new = np.zeros(have, dtype=old.dtype)
+            new[:self._n] = old[:self._n]
+            grown.append(new)
+        self._indexed, self._image, self._columns = grown
+
+    # -------------------------------------------------------------------------------------------------------------------------- add
+    def add(self, items: Sequence[Item], fallback: Optional[Callable[[bytes], np.ndarray]] = None) -> np.ndarray:
+        import torch
+        from . import train_abi as abi
+        blobs = []
+        for item in items:
+            if isinstance(item, (bytes, bytearray, memoryview)):
+                blobs.append(bytes(item))
+            else:
+                with open(item, "rb") as fh:
+                    blobs.append(fh.read())
+        n = len(blobs)
+        if n == 0:
+            return np.zeros(0, dtype=np.int64)
+        SBY, limit = self.subsequence_bytes, jpeg_frames.DEVICE_SCAN_MAX
+        prepared = list(self._host._pool.map(self._host.scan_prepare, blobs))
+        # every file is judged before anything is stored
+        scans, through_host, raw = [], [], {}
+        for i, (data, res) in enumerate(zip(blobs, prepared)):
+            if isinstance(res, tuple):
+                (through_host if res[3].max_seg_bytes > limit else scans).append(i)
+            elif res == ERR_UNSUPPORTED and fallback is not None:
+                px = np.ascontiguousarray(fallback(data))
+                if px.ndim != 3 or px.shape[2] != 3 or px.dtype != np.uint8:
+                    raise ValueError("the fallback must return uint8 (H, W, 3)")
+                raw[i] = px
+            else:
+                try:
+                    _raise_as_python(data, res)
+                except (MalformedJPEG, UnsupportedJPEG) as exc:
+                    raise type(exc)(f"item {i}: {exc}") from None
+        # the resident layout of every "scan" file, from its base: bytes | seg_start | sub_start | index | FearJpegScan, each at 16 bytes
+        layout, split, need = {}, dict(bytes=0, index=0, records=0, pixels=0), 0
+        for i in scans:
+            info, data, seg, scan = prepared[i]
+            sub, count = np.empty(seg.size, dtype=np.uint32), ctypes.c_uint32(0)
+            rc = self._lib.fear_jpeg_sub_start(seg.ctypes.data, scan.n_seg, scan.n_bytes, SBY, sub.ctypes.data, sub.size, ctypes.byref(count))
+            if rc != 0 or count.value != int(sub[-1]):
+                raise abi.TrainError(f"fear_jpeg_sub_start failed with status {rc}")
+            at_seg = _up(max(data.nbytes, 1), 16)
+            at_sub = at_seg + _up(seg.nbytes, 16)
+            at_index = at_sub + _up(sub.nbytes, 16)
+            at_record = at_index + 16 * int(sub[-1])
+            layout[i] = (sub, at_seg, at_sub, at_index, at_record, at_record + ctypes.sizeof(abi.FearJpegScan))
+            split["bytes"] += at_index
+            split["index"] += at_record - at_index
+            split["records"] += ctypes.sizeof(abi.FearJpegScan)
+        for i in through_host:
+            split["pixels"] += 3 * prepared[i][0].width * prepared[i][0].height
+        for px in raw.values():
+            split["pixels"] += px.nbytes
+        need = sum(split.values())
+        if self.capacity_bytes is not None and self.nbytes + need > self.capacity_bytes:
+            raise StoreFull(f"{need} bytes more on top of {self.nbytes} exceed the capacity of {self.capacity_bytes}")
+        with torch.cuda.device(self.device):
+            # place: tentative cursors, committed at the end
+            new_slabs, open_slab, cursor, base, runs = [], self._open, self._cursor, {}, []
+            for i in scans:
+                size = layout[i][5]
+                if size > self.slab_bytes:                               # a slab of its own; the open slab stays open
+                    slab, at = torch.empty(size, dtype=torch.uint8, device=self.device), 0
+                    new_slabs.append(slab)
+                else:
+                    if open_slab is None or cursor + size > self.slab_bytes:
+                        open_slab, cursor = torch.empty(self.slab_bytes, dtype=torch.uint8, device=self.device), 0
+                        new_slabs.append(open_slab)
+                    slab, at = open_slab, cursor
+                    cursor += size
+                assert slab.data_ptr() % 16 == 0
+                base[i] = slab.data_ptr() + at
+                if runs and runs[-1][0] is slab and runs[-1][1] + runs[-1][2] == at:
+                    runs[-1][2] += size
+                    runs[-1][3].append(i)
+                else:
+                    runs.append([slab, at, size, [i]])
+            # upload: one copy per run of neighbours in a slab
+            for slab, at, size, members in runs:
+                host, w = np.zeros(size, dtype=np.uint8), 0
+                for i in members:
+                    info, data, seg, scan = prepared[i]
+                    sub, at_seg, at_sub, at_index, at_record, end = layout[i]
+                    scan.bytes, scan.seg_start, scan.coef_offset = base[i], base[i] + at_seg, 0
+                    host[w:w + data.nbytes] = data
+                    host[w + at_seg:w + at_seg + seg.nbytes] = seg.view(np.uint8)
+                    host[w + at_sub:w + at_sub + sub.nbytes] = sub.view(np.uint8)
+                    host[w + at_record:w + end] = np.frombuffer(scan, dtype=np.uint8)
+                    w += end
+                slab[at:at + size].copy_(torch.from_numpy(host))
+            # the index, in groups bounded by the scratch coefficients
+            groups, dense = [[]], 0
+            for i in scans:
+                want = 128 * int(prepared[i][0].total_blocks)
+                if groups[-1] and (dense + want > self.workspace_limit or len(groups[-1]) == 65535):
+                    groups.append([])
+                    dense = 0
+                groups[-1].append(i)
+                dense += want
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            verdicts = []
+            for group in groups:
+                m = len(group)
+                if m == 0:
+                    continue
+                records, indexes = (abi.FearJpegScan * m)(), (abi.FearJpegIndex * m)()
+                prefix, values = np.zeros(m + 1, dtype=np.uint32), 0
+                for k, i in enumerate(group):
+                    info, data, seg, scan = prepared[i]
+                    sub, at_seg, at_sub, at_index, at_record, end = layout[i]
+                    ctypes.memmove(ctypes.byref(records[k]), ctypes.byref(scan), ctypes.sizeof(scan))
+                    records[k].coef_offset = values
+                    values += 64 * int(info.total_blocks)
+                    prefix[k + 1] = prefix[k] + scan.n_seg
+                    ix = indexes[k]
+                    ix.index, ix.sub_start, ix.seg_start_host, ix.n_sub = base[i] + at_index, base[i] + at_sub, seg.ctypes.data, int(sub[-1])
+                records_at = _up(prefix.nbytes, 16)
+                index_at = records_at + ctypes.sizeof(records)
+                table = np.zeros(index_at + ctypes.sizeof(indexes), dtype=np.uint8)
+                table[:prefix.nbytes] = prefix.view(np.uint8)
+                table[records_at:index_at] = np.frombuffer(records, dtype=np.uint8)
+                table[index_at:] = np.frombuffer(indexes, dtype=np.uint8)
+                dev = torch.from_numpy(table).to(self.device)
+                coef = torch.empty(max(values, 8), dtype=torch.int16, device=self.device)
+                status = torch.empty(m, dtype=torch.int32, device=self.device)
+                abi.launch(self._lib, "fear_jpeg_index_build", records, m, ctypes.c_void_p(dev.data_ptr()), indexes,
+                           ctypes.c_void_p(dev.data_ptr() + index_at), ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(status.data_ptr()),
+                           SBY, stream)
+                verdicts.append((group, status, dev, coef))
+            for group, status, _, _ in verdicts:
+                got = status.cpu().numpy()                               # add waits: set-up
+                for k in np.flatnonzero(got):
+                    i = group[int(k)]
+                    try:
+                        _raise_as_python(blobs[i], int(got[k]))
+                    except MalformedJPEG as exc:
+                        raise MalformedJPEG(f"item {i}: {exc}") from None
+            pixels = {}
+            for i in through_host:                                       # once through the host's Huffman stage; it judges the file itself
+                try:
+                    pixels[i] = self._host.decode([blobs[i]])[0].clone()
+                except (MalformedJPEG, UnsupportedJPEG) as exc:
+                    raise type(exc)(f"item {i}: {exc}") from None
+            for i, px in raw.items():
+                pixels[i] = torch.from_numpy(px.copy()).to(self.device)         # (the fallback's array may be read-only)
+            torch.cuda.current_stream().synchronize()                    # what was stored is complete for a decode on any stream
+        # commit
+        first = self._n
+        self._grow(first + n)
+        ids = np.arange(first, first + n, dtype=np.int64)
+        for i in scans:
+            info, data, seg, scan = prepared[i]
+            sub, at_seg, at_sub, at_index, at_record, end = layout[i]
+            row, img, col = self._indexed[first + i], self._image[first + i], self._columns[first + i]
+            row["scan"], row["index"], row["sub_start"], row["n_sub"] = base[i] + at_record, base[i] + at_index, base[i] + at_sub, int(sub[-1])
+            img["width"], img["height"], img["components"], img["h"], img["v"] = info.width, info.height, info.components, info.h[0], info.v[0]
+            img["qt"] = np.ctypeslib.as_array(info.qt)
+            col["n_seg"], col["n_sub"], col["total_blocks"], col["H"], col["W"], col["kind"] = (
+                scan.n_seg, int(sub[-1]), info.total_blocks, info.height, info.width, KIND_SCAN)
+            self._most = max(self._most, int(info.total_blocks))
+        for i, px in pixels.items():
+            col = self._columns[first + i]
+            col["H"], col["W"], col["kind"] = px.shape[0], px.shape[1], KIND_PIXELS
+            self._pixels[first + i] = px
+        self._slabs += new_slabs
+        self._open, self._cursor = open_slab, cursor
+        self._n, self.nbytes = first + n, self.nbytes + need
+        for key, v in split.items():
+            self.resident[key] += v
+        return ids
+
+    # ----------------------------------------------------------------------------------------------------------------------- decode
+    def decode(self, ids, check: bool = False) -> List:
+        ids = self._checked(ids)
+        frames: List = [None] * ids.size
+        self._pending = self._pending[-self.PENDING_CALLS:]              # of earlier calls; every group of this call is kept
+        for plan in plan_decode(self._columns, ids, self.workspace_limit):
+            self._decode_group(ids, plan, frames)
+        if check:
+            self.check()
+        return frames
+
+    def _decode_group(self, ids: np.ndarray, plan: dict, frames: List) -> None:
+        import torch
+        from . import train_abi as abi
+        lo, hi, scan = plan["lo"], plan["hi"], plan["scan"]
+        group = ids[lo:hi]
+        sids, nd = group[scan], scan.size
+        with torch.cuda.device(self.device):
+            out = torch.empty(max(plan["out_bytes"], 16), dtype=torch.uint8, device=self.device)
+            out_offset = plan["out_offset"]
+            if nd:
+                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                if self._dense_blocks < self._most:                      # the store's largest image grew
+                    self._dense_retired.append(self._dense_start)
+                    self._dense_start = torch.empty(self._most + 1, dtype=torch.int32, device=self.device)
+                    abi.launch(self._lib, "fear_jpeg_dense_block_start", ctypes.c_void_p(self._dense_start.data_ptr()), self._most, stream)
+                    self._dense_blocks, self._dense_event = self._most, torch.cuda.Event()
+                    self._dense_event.record()
+                else:                                                    # written on whatever stream was current then: this one waits for it
+                    torch.cuda.current_stream().wait_event(self._dense_event)
+                coef = torch.empty(max(plan["values"], 8), dtype=torch.int16, device=self.device)
+                ws = torch.empty(plan["workspace_bytes"], dtype=torch.uint8, device=self.device)
+                status = torch.empty(nd, dtype=torch.int32, device=self.device)
+                indexed, images = self._indexed[sids], self._image[sids]  # gathers: private copies
+                indexed["coef_offset"] = plan["coef_offset"]
+                images["coef"] = np.uint64(coef.data_ptr()) + np.uint64(2) * plan["coef_offset"]
+                images["block_start"] = self._dense_start.data_ptr()
+                images["out"] = np.uint64(out.data_ptr()) + out_offset[scan].astype(np.uint64)
+                images["plane_offset"] = plan["plane_offset"]
+                # one pinned upload: prefix | FearJpegIndexed records, then two prefixes | FearJpegImage records
+                prefixes = np.concatenate([plan["block_prefix"], plan["pixel_prefix"]])
+                at_indexed = _up(plan["sub_prefix"].nbytes, 16)
+                at_table = at_indexed + indexed.nbytes
+                at_images = at_table + _up(prefixes.nbytes, 16)
+                pinned = torch.empty(at_images + images.nbytes, dtype=torch.uint8, pin_memory=True)
+                host = pinned.numpy()
+                host[:at_indexed].view(np.uint32)[:nd + 1] = plan["sub_prefix"]
+                host[at_indexed:at_table] = indexed.view(np.uint8)
+                host[at_table:at_images].view(np.uint32)[:2 * nd + 2] = prefixes
+                host[at_images:] = images.view(np.uint8)
+                dev = torch.empty(pinned.numel(), dtype=torch.uint8, device=self.device)
+                dev.copy_(pinned, non_blocking=True)
+                self._pinned = self._pinned[-1:] + [pinned]
+                self._records = (indexed, images)                        # the calls below get their addresses
+                self.last_upload_bytes = pinned.numel()
+                abi.launch(self._lib, "fear_jpeg_huffman_indexed", ctypes.c_void_p(indexed.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr()),
+                           ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(status.data_ptr()), self.subsequence_bytes, stream)
+                abi.launch(self._lib, "fear_jpeg_decode_u8", ctypes.c_void_p(images.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr() + at_table),
+                           ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"], stream)
+                verdict = torch.empty(nd, dtype=torch.int32, pin_memory=True)
+                verdict.copy_(status, non_blocking=True)
+                event = torch.cuda.Event()
+                event.record()
+                self._pending.append((event, verdict, lo + scan, sids))
+            rows = self._columns[group]
+            sizes = 3 * rows["H"].astype(np.int64) * rows["W"]
+            for k in np.flatnonzero(rows["kind"] == KIND_PIXELS):        # the entries kept as pixels: a copy, never an alias
+                out[out_offset[k]:out_offset[k] + sizes[k]].copy_(self._pixels[int(group[k])].view(-1), non_blocking=True)
+        for k, (at, size, h, w) in enumerate(zip(out_offset.tolist(), sizes.tolist(), rows["H"].tolist(), rows["W"].tolist())):
+            frames[lo + k] = out[at:at + size].view(h, w, 3)
+
+    def check(self) -> None:
+        """Wait for the calls not yet checked and raise MalformedJPEG for the first image the device refused, naming the position in its
+        call's ids and the id."""
+        pending, self._pending = self._pending, []
+        for k, (event, status, positions, sids) in enumerate(pending):
+            event.synchronize()
+            bad = np.flatnonzero(status.numpy())
+            if bad.size:
+                self._pending = pending[k + 1:]
+                j = int(bad[0])
+                raise MalformedJPEG(f"item {int(positions[j])}: the device refused the resident scan of id {int(sids[j])} "
+                                    f"with status {int(status[j])}")

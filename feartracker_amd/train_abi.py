@@ -95,6 +95,10 @@ TRAIN_SYMBOLS = {
     "fear_jpeg_scan_prepare": ([_P, _sz, _P, _P, _sz, _P, _sz, _P], _i),
     "fear_jpeg_huffman": ([_P, _i, _P, _P, _P, _i, _P], _i),
     "fear_jpeg_dense_block_start": ([_P, ctypes.c_uint32, _P], _i),
+    # scans resident on the device (jpeg_store.JpegStore; FearJpegSubseq, FearJpegIndex and FearJpegIndexed below)
+    "fear_jpeg_sub_start": ([_P, ctypes.c_uint32, ctypes.c_uint32, _i, _P, _sz, _P], _i),
+    "fear_jpeg_index_build": ([_P, _i, _P, _P, _P, _P, _P, _i, _P], _i),
+    "fear_jpeg_huffman_indexed": ([_P, _i, _P, _P, _P, _i, _P], _i),
     # the colour stage's members that are no lookup table (FearColourOp below)
     "fear_colour_u8": ([_P, _i, _i, _i, _P, _P, _P, _P], _i),
     # step metrics (metrics.TrainMetrics)
@@ -204,6 +208,24 @@ class FearJpegScan(ctypes.Structure):
                 ("restart_interval", ctypes.c_int32), ("dc", FearJpegHuff * 3), ("ac", FearJpegHuff * 3)]
 
 
+class FearJpegSubseq(ctypes.Structure):
+    """include/fear_train.h: the true entry of one subsequence of a resident scan (jpeg_huffman.SUBSEQ_DTYPE is its numpy form)."""
+    _fields_ = [("p", ctypes.c_uint32), ("begun", ctypes.c_uint32), ("sz", ctypes.c_uint16), ("dc", ctypes.c_uint16 * 3)]
+
+
+class FearJpegIndex(ctypes.Structure):
+    """include/fear_train.h: one image of a fear_jpeg_index_build call (device pointers as integers; seg_start_host is a host address)."""
+    _fields_ = [("index", ctypes.c_uint64), ("sub_start", ctypes.c_uint64), ("seg_start_host", ctypes.c_uint64), ("n_sub", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class FearJpegIndexed(ctypes.Structure):
+    """include/fear_train.h: one image of a fear_jpeg_huffman_indexed call (device pointers as integers)."""
+    _fields_ = [("scan", ctypes.c_uint64), ("index", ctypes.c_uint64), ("sub_start", ctypes.c_uint64), ("coef_offset", ctypes.c_uint64),
+                ("n_sub", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7)]
+
+
+assert ctypes.sizeof(FearJpegSubseq) == 16 and ctypes.sizeof(FearJpegIndex) == 32 and ctypes.sizeof(FearJpegIndexed) == 64
 assert ctypes.sizeof(FearJpegInfo) == 464 and FearJpegInfo.qt.offset == 80
 assert ctypes.sizeof(FearJpegHuff) == 1440 and ctypes.sizeof(FearJpegScan) == 8704 and FearJpegScan.dc.offset == 64
 assert ctypes.sizeof(FearJpegImage) == 448 and FearJpegImage.qt.offset == 64

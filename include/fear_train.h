@@ -678,6 +678,86 @@ int fear_jpeg_huffman(const FearJpegScan* scans, int n, const void* table_dev, i
                       void* stream);
 int fear_jpeg_dense_block_start(uint32_t* block_start, uint32_t total_blocks, void* stream);
 
+/* ---- scans resident on the device, with the index a baseline scan lacks ("The resident store";
+ * jpeg_huffman.jpeg_scan_index_host and jpeg_entropy_indexed_host restate the two calls in Python; jpeg_store.JpegStore is their user).
+ * A file that is decoded again and again is prepared and uploaded once, and the true entry of every subsequence — what fear_jpeg_huffman
+ * finds anew in every call by synchronising, counting and a prefix — is stored next to its bytes: FearJpegSubseq, 16 bytes per
+ * subsequence.  Subsequences are numbered per image, segment after segment: segment s owns the entries sub_start[s] .. sub_start[s + 1]),
+ * ceil(segment bytes / subsequence_bytes) of them; sub_start has n_seg + 1 entries.  fear_jpeg_sub_start computes it on the host from
+ * the seg_start that fear_jpeg_scan_prepare wrote: it reads seg_start[0 .. n_seg], writes sub_start[0 .. n_seg] (sub_cap entries are the
+ * capacity: FEAR_TRAIN_ERR_WORKSPACE below n_seg + 1; a null sub_start only counts) and the total to *n_sub.  FEAR_TRAIN_ERR_SHAPE: a bad
+ * subsequence_bytes, n_seg == 0, offsets that do not start at 0, decrease or do not end at n_bytes; FEAR_TRAIN_ERR_NULL: a null seg_start
+ * or n_sub.  Host code, no HIP call, no global state.
+ *
+ * fear_jpeg_index_build is fear_jpeg_huffman with one more output: the same kernel in a second instantiation, the same algorithm, the
+ * same coefficients (to `coef`, a scratch buffer the caller may throw away) and the same verdict in status_dev; in front of its write
+ * pass each lane stores its entry, one 16-byte store checked against n_sub.  `indexes` is a HOST array the call reads for its checks,
+ * `index_table_dev` a DEVICE copy of the same n records for the kernel.  The checks are fear_jpeg_huffman's, and the index's capacity:
+ * seg_start_host of a record is the HOST copy of the scan's seg_start (what fear_jpeg_scan_prepare wrote), non-decreasing and ending at
+ * n_bytes, and n_sub must equal the sum of ceil((seg_start[s + 1] - seg_start[s]) / subsequence_bytes), else FEAR_TRAIN_ERR_SHAPE; an
+ * index not 16-byte aligned or a sub_start not 4-byte aligned is FEAR_TRAIN_ERR_SHAPE too, a null index, sub_start, seg_start_host,
+ * indexes or index_table_dev FEAR_TRAIN_ERR_NULL (an image with n_sub == 0 may have a null index).  A refused call launches nothing.
+ *
+ * fear_jpeg_huffman_indexed decodes n resident scans from their indexes: 256 lanes, ceil(n_sub / 256) workgroups per image, one lane
+ * per subsequence.  A workgroup copies its image's six tables to LDS and meets one barrier; each lane then loads its entry, finds its
+ * segment by a search of sub_start bounded by 21 steps, decodes once from the entry to the subsequence's end with the write pass's
+ * rules and stores what it decodes: no rounds, no count pass, no prefix, no atomics, no workgroup waits for another, every coefficient
+ * position is stored by exactly one lane.  The verdict is fear_jpeg_huffman's: a lane that finds a fault stores FEAR_TRAIN_ERR_FORMAT to
+ * its image's status (the lane of a segment's last subsequence judges the segment's block count, the lane of its first an empty segment
+ * in front, the lane of the image's last subsequence empty segments behind; an image with n_sub == 0 fails in the first launch).
+ * `images` is a HOST array of per-call records the call reads for its checks and the grid size; `scan` of a record is a DEVICE-resident
+ * FearJpegScan whose own coef_offset is ignored.  The kernel reads `table_dev`, a DEVICE copy the caller uploads:
+ *     uint32 [n + 1]  prefix sums of ceil(n_sub / 256) per image
+ *     padding to FEAR_JPEG_SCAN_TABLE_RECORDS(n) bytes, then a copy of the n records
+ * Two launches: the statuses' zeros and the decode.  n == 0 returns FEAR_TRAIN_OK without a launch.  FEAR_TRAIN_ERR_SHAPE: n < 0 or
+ * n > 65535, subsequence_bytes no multiple of 4 in 4..1024, an index or a scan not 16-byte aligned, a sub_start not 4-byte aligned, more
+ * than 2^31 - 1 workgroups; FEAR_TRAIN_ERR_NULL: a null images, table_dev, coef, status_dev, or scan, index (unless n_sub == 0) or
+ * sub_start of a record.  The scan's geometry was checked when its index was built and lives in device memory, where the call cannot
+ * read it: a wrong index, sub_start or resident record is the caller's error, as a wrong block_start is to fear_jpeg_decode_u8.  Even
+ * so every read stays inside the segment and the image's n_bytes, every write inside the image's 64 total_blocks values from its
+ * coef_offset, an entry's slot and z are clamped to the tables, and every loop is bounded by the subsequence's length.                */
+typedef struct FearJpegSubseq {
+    uint32_t p;                  /* the true entry bit position in the segment, up to 30 bits behind the subsequence's first: < 2^27 + 31 */
+    uint32_t begun;              /* blocks begun in the segment in front of the subsequence                              */
+    uint16_t sz;                 /* slot << 8 | z at the entry                                                           */
+    uint16_t dc[3];              /* the predictors at the entry, modulo 2^16, by component                               */
+} FearJpegSubseq;
+
+/* One image of a fear_jpeg_index_build call.  32 bytes. */
+typedef struct FearJpegIndex {
+    FearJpegSubseq* index;           /* device: n_sub entries, 16-byte aligned                                           */
+    const uint32_t* sub_start;       /* device: n_seg + 1 prefix sums of the segments' subsequence counts                */
+    const uint32_t* seg_start_host;  /* HOST: the scan's seg_start, for the call's checks; the kernel does not read it   */
+    uint32_t n_sub;
+    uint32_t reserved;
+} FearJpegIndex;
+
+/* One image of a fear_jpeg_huffman_indexed call.  64 bytes. */
+typedef struct FearJpegIndexed {
+    const FearJpegScan* scan;        /* device: the resident record; its coef_offset is ignored                          */
+    const FearJpegSubseq* index;     /* device                                                                           */
+    const uint32_t* sub_start;       /* device                                                                           */
+    uint64_t coef_offset;            /* values from `coef` to this image's 64 total_blocks dense coefficients            */
+    uint32_t n_sub;
+    uint32_t reserved[7];
+} FearJpegIndexed;
+#ifdef __cplusplus
+static_assert(sizeof(FearJpegSubseq) == 16, "FearJpegSubseq is 16 bytes");
+static_assert(sizeof(FearJpegIndex) == 32, "FearJpegIndex is 32 bytes");
+static_assert(sizeof(FearJpegIndexed) == 64, "FearJpegIndexed is 64 bytes");
+#else
+_Static_assert(sizeof(FearJpegSubseq) == 16, "FearJpegSubseq is 16 bytes");
+_Static_assert(sizeof(FearJpegIndex) == 32, "FearJpegIndex is 32 bytes");
+_Static_assert(sizeof(FearJpegIndexed) == 64, "FearJpegIndexed is 64 bytes");
+#endif
+
+int fear_jpeg_sub_start(const uint32_t* seg_start, uint32_t n_seg, uint32_t n_bytes, int subsequence_bytes, uint32_t* sub_start,
+                        size_t sub_cap, uint32_t* n_sub);
+int fear_jpeg_index_build(const FearJpegScan* scans, int n, const void* table_dev, const FearJpegIndex* indexes, const void* index_table_dev,
+                          int16_t* coef, int32_t* status_dev, int subsequence_bytes, void* stream);
+int fear_jpeg_huffman_indexed(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
+                              int subsequence_bytes, void* stream);
+
 /* ---- the colour stage's members that are no lookup table: Equalize, HueSaturationValue, ColorJitter and Emboss of the reference's
  * p = 0.5 OneOf (model_training/dataset/aug.py:35-48), on uint8 HWC crops between fear_train_pairs_u8 (tone, then the lookup-table
  * members) and fear_photometric_u8 (DESIGN.md section 11 states every contract; train_data.colour_u8_host restates them in numpy and the

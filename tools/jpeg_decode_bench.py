@@ -20,7 +20,21 @@ With --entropy device or both, under "device_entropy" (the host figures above st
   upload_bytes_per_frame  the unstuffed bytes, seg_start and the scan record
   scan_prepare_ms_per_frame   fear_jpeg_parse + fear_jpeg_scan_prepare, one thread (entropy_ms_per_frame above is the host's Huffman stage)
   ratio_to_host           decode_fps at the fastest subsequence_bytes over the host mode's decode_fps
-Every timing is the median of --repeats runs after one warm-up run; each entry carries the minimum and maximum of the runs as well."""
+Every timing is the median of --repeats runs after one warm-up run; each entry carries the minimum and maximum of the runs as well.
+
+    python tools/jpeg_decode_bench.py --dir DIR --store     # needs the GPU: the resident store, writes profiles/jpeg_store_bench.json
+
+--store measures jpeg_store.JpegStore against JpegDecoder(entropy="device") on the same files in ONE run, every shape warmed first, medians
+of 5 with minimum and maximum:
+  decoder_fps             (a) JpegDecoder(entropy="device").decode end to end with check(), 16 threads: the baseline
+  store_fps               (b) store.decode of the 256 ids in a seeded permutation with check(), a host clock around work that ends in a
+                          synchronise; `faster_than_decoder` says whether its slowest run beats the baseline's fastest
+  stage_ms                (c) fear_jpeg_huffman alone and fear_jpeg_huffman_indexed alone between HIP events at 64, 128 and 256 bytes
+  host_ms_per_call, upload_bytes_per_image      (d) store.decode until it returns (it does not wait), and its one pinned transfer
+  add_files_per_s         (e) JpegStore.add of the 256 files into a fresh store, 16 threads, verdicts awaited
+  resident_bytes_per_file (f) by subsequence_bytes: bytes (with seg_start and sub_start), index, records
+  training_step_fps       what the 128-pair step consumes, to read store_fps against
+Before anything is timed the store's frames are compared with the decoder's at every subsequence length (`frames_equal_decoder`)."""
 import argparse
 import glob
 import io
@@ -146,6 +160,106 @@ def device_entropy(torch, blobs, repeats, host_fps):
     return res
 
 
+def store_bench(torch, blobs, out):
+    """JpegStore against JpegDecoder(entropy="device") in one run."""
+    from feartracker_amd import JpegDecoder, JpegStore
+    from feartracker_amd import train_abi as abi
+    n, repeats, sweep = len(blobs), 5, (64, 128, 256)
+    res = {"files": n, "width": W, "height": H, "quality": QUALITY, "file_bytes_per_frame": sum(map(len, blobs)) / n,
+           "cpus_available": len(os.sched_getaffinity(0)), "repeats": repeats, "training_step_fps": 17600}
+    perm = np.random.default_rng(17).permutation(n)
+    decoders = {sb: JpegDecoder(device=0, threads=16, entropy="device", subsequence_bytes=sb) for sb in sweep}
+    stores, ids = {}, {}
+    for sb in sweep:
+        stores[sb] = JpegStore(device=0, subsequence_bytes=sb, threads=16)
+        ids[sb] = stores[sb].add(blobs)
+    default = JpegStore(device=0, threads=16).subsequence_bytes
+    res["subsequence_bytes"] = default
+    dec, store = decoders[default], stores[default]
+
+    def decoder_end_to_end():
+        frames = dec.decode(blobs, check=True)
+        torch.cuda.synchronize()
+        return frames
+
+    def store_end_to_end():
+        frames = store.decode(ids[default][perm], check=True)
+        torch.cuda.synchronize()
+        return frames
+
+    def captured_call(fn, name):
+        captured, real = {}, abi.launch
+
+        def spy(lib, called, *a):
+            captured[called] = a
+            return real(lib, called, *a)
+        abi.launch = spy
+        try:
+            keep = fn()
+        finally:
+            abi.launch = real
+        torch.cuda.synchronize()
+        return keep, captured[name]
+
+    for sb in sweep:                                                     # every shape warm before anything is timed
+        decoders[sb].decode(blobs, check=True)
+        stores[sb].decode(ids[sb][perm], check=True)
+    torch.cuda.synchronize()
+    for sb in sweep:                                                     # faster and different is not faster: the same frames, byte for byte
+        same = all(torch.equal(x, y) for x, y in zip(decoders[sb].decode(blobs, check=True), stores[sb].decode(ids[sb], check=True)))
+        assert same, f"the store's frames differ from the decoder's at {sb} bytes"
+    res["frames_equal_decoder"] = True
+    a = run_seconds(decoder_end_to_end, repeats)
+    b = run_seconds(store_end_to_end, repeats)
+    res["decoder_fps"] = spread([n / t for t in a], digits=1)
+    res["store_fps"] = spread([n / t for t in b], digits=1)
+    res["decoder_ms_per_call"], res["store_ms_per_call"] = spread(a, 1e3), spread(b, 1e3)
+    res["faster_than_decoder"] = bool(max(b) < min(a))
+    res["stage_ms"] = {}
+    for sb in sweep:
+        keep_a, plain = captured_call(lambda: decoders[sb].decode(blobs, check=True), "fear_jpeg_huffman")
+        keep_b, indexed = captured_call(lambda: stores[sb].decode(ids[sb][perm], check=True), "fear_jpeg_huffman_indexed")
+        # the replays read what the captured addresses point at: the decoder's ctypes records are in `plain` itself, the store keeps its
+        # last call's host records (`_records`) until its next decode, and the device buffers are alive in the frames and the allocator's cache
+        lib = dec._lib
+        assert stores[sb]._records[0].ctypes.data == indexed[0].value
+        one = event_ms(torch, lambda: lib.fear_jpeg_huffman(*plain), repeats)
+        two = event_ms(torch, lambda: lib.fear_jpeg_huffman_indexed(*indexed), repeats)
+        res["stage_ms"][str(sb)] = {"fear_jpeg_huffman": spread(one), "fear_jpeg_huffman_indexed": spread(two),
+                                    "indexed_faster": bool(max(two) < min(one))}
+        del keep_a, keep_b
+
+    def host_only():
+        t0 = time.perf_counter()
+        frames = store.decode(ids[default][perm])
+        t = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        store.check()
+        return t, frames
+    host_only()
+    res["host_ms_per_call"] = spread([host_only()[0] for _ in range(repeats)], 1e3)
+    res["upload_bytes_per_image"] = round(store.last_upload_bytes / n, 1)
+
+    def add_once():
+        fresh = JpegStore(device=0, subsequence_bytes=default, threads=16)
+        t0 = time.perf_counter()
+        fresh.add(blobs)
+        t = time.perf_counter() - t0
+        fresh.close()
+        return t
+    add_once()
+    res["add_files_per_s"] = spread([n / add_once() for _ in range(repeats)], digits=1)
+    res["resident_bytes_per_file"] = {str(sb): dict({k: round(v / n, 1) for k, v in stores[sb].resident.items() if k != "pixels"},
+                                                    total=round(stores[sb].nbytes / n, 1)) for sb in sweep}
+    for sb in sweep:
+        decoders[sb].close()
+        stores[sb].close()
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dir", required=True)
@@ -153,8 +267,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--entropy", choices=("host", "device", "both"), default="host")
     ap.add_argument("--rounds", type=int, default=0, help="no GPU: the model's synchronisation rounds on the first N files, merged into --out")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode_bench.json"))
+    ap.add_argument("--store", action="store_true", help="the resident store against the device decoder, to profiles/jpeg_store_bench.json")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "jpeg_store_bench.json" if args.store else "jpeg_decode_bench.json")
     if args.make:
         return make(args.dir)
     blobs = [open(p, "rb").read() for p in sorted(glob.glob(os.path.join(args.dir, "*.jpg")))]
@@ -167,6 +284,8 @@ def main():
         print(json.dumps(res["device_entropy"]["rounds_per_sequence"]))
         return
     import torch
+    if args.store:
+        return store_bench(torch, blobs, args.out)
     from feartracker_amd import JpegDecoder
     n = len(blobs)
     dec = JpegDecoder(device=0, threads=16)

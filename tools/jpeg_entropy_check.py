@@ -2,7 +2,8 @@
 Python extension and no GPU — on the fixture's files (tests/golden/jpeg_decode.npz) and on the malformed set of
 tests/test_jpeg_decode_host.py: every prefix and every flipped entropy byte of the 16 x 16 4:2:0 file, and the header faults.  Each line
 of its output is compared with the Python decoder's verdict and packed stream; a file whose headers parse has a second line, fear_jpeg_scan_prepare's, compared with
-jpeg_huffman.jpeg_scan_prepare_host.  Expect "0 sanitizer reports, 0 mismatches".
+jpeg_huffman.jpeg_scan_prepare_host, and where the scan is accepted a third, fear_jpeg_sub_start's at 4 and 128 bytes, compared with
+jpeg_huffman.scan_sub_start.  Expect "0 sanitizer reports, 0 mismatches".
 
     python tools/jpeg_entropy_check.py [--dir SCRATCH] [--cxx g++]
 """
@@ -69,7 +70,9 @@ def expected_scan(name, data):
     except jf.MalformedJPEG:
         return f"{name} scan {jf.ERR_FORMAT}"
     h = fnv(fnv(14695981039346656037, np.array(start, dtype="<u4").tobytes()), out)
-    return f"{name} scan 0 {len(out)} {len(start) - 1} {h:016x}"
+    subs = [jh.scan_sub_start(start, b) for b in (4, 128)]
+    third = f"{name} sub" + "".join(f" 0 {int(s[-1])} {fnv(14695981039346656037, s.astype('<u4').tobytes()):016x}" for s in subs)
+    return f"{name} scan 0 {len(out)} {len(start) - 1} {h:016x}", third
 
 
 def files():
@@ -121,7 +124,7 @@ def main():
     wanted = []
     for name in names:
         scan = expected_scan(name, made[name])
-        wanted += [(name, scan)] if scan else []
+        wanted += [(name, line) for line in ((scan,) if isinstance(scan, str) else scan or ())]
         wanted.append((name, expected(name, made[name])))
     mismatches = 0 if len(lines) == len(wanted) else 1
     for (name, want), line in zip(wanted, lines):

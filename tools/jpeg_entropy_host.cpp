@@ -10,6 +10,9 @@
 // A file whose headers parse gets a second line for fear_jpeg_scan_prepare: name, "scan", its status, and where it accepts the bytes, the
 // segments and FNV-1a of seg_start and the unstuffed bytes — the first call with the file's length and segments + 1 as capacities, a
 // second with exactly the bytes the first one wrote, a third with one byte less (FEAR_TRAIN_ERR_WORKSPACE).
+// A file whose scan is accepted gets a third line for fear_jpeg_sub_start: name, "sub", and per subsequence length 4 and 128 the status, n_sub
+// and FNV-1a of sub_start — seg_start in an exact-size heap copy, sub_start at exactly n_seg + 1 entries; a count-only call must give the
+// same n_sub, a capacity one entry short FEAR_TRAIN_ERR_WORKSPACE, offsets that do not end at n_bytes FEAR_TRAIN_ERR_SHAPE.
 // tools/jpeg_entropy_check.py writes the files, runs the program and compares each line with the Python decoder's.
 #include <cstdio>
 #include <cstdlib>
@@ -22,6 +25,30 @@ static uint64_t fnv(uint64_t h, const void* p, size_t n) {
     const unsigned char* b = static_cast<const unsigned char*>(p);
     for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
     return h;
+}
+
+static int sub_line(const char* name, const uint32_t* seg_start, const FearJpegScan& scan) {
+    int failures = 0;
+    const size_t entries = (size_t)scan.n_seg + 1;
+    uint32_t* seg = static_cast<uint32_t*>(std::malloc(entries * sizeof(uint32_t)));
+    uint32_t* sub = static_cast<uint32_t*>(std::malloc(entries * sizeof(uint32_t)));
+    std::memcpy(seg, seg_start, entries * sizeof(uint32_t));
+    std::printf("%s sub", name);
+    for (int bytes : {4, 128}) {
+        uint32_t n_sub = 0, counted = 0;
+        const int rc = fear_jpeg_sub_start(seg, scan.n_seg, scan.n_bytes, bytes, sub, entries, &n_sub);
+        std::printf(" %d %u %016llx", rc, n_sub, (unsigned long long)fnv(14695981039346656037ull, sub, entries * sizeof(uint32_t)));
+        if (fear_jpeg_sub_start(seg, scan.n_seg, scan.n_bytes, bytes, nullptr, 0, &counted) != rc || counted != n_sub ||
+            fear_jpeg_sub_start(seg, scan.n_seg, scan.n_bytes, bytes, sub, entries - 1, &counted) != FEAR_TRAIN_ERR_WORKSPACE ||
+            fear_jpeg_sub_start(seg, scan.n_seg, scan.n_bytes + 1, bytes, sub, entries, &counted) != FEAR_TRAIN_ERR_SHAPE) {
+            std::printf("\n%s: fear_jpeg_sub_start at %d bytes: the count-only call, a short capacity or foreign offsets\n", name, bytes);
+            ++failures;
+        }
+    }
+    std::printf("\n");
+    std::free(sub);
+    std::free(seg);
+    return failures;
 }
 
 static int scan_line(const char* name, const unsigned char* data, size_t n, const FearJpegInfo& info) {
@@ -56,6 +83,7 @@ static int scan_line(const char* name, const unsigned char* data, size_t n, cons
         }
         std::free(again);
         std::free(exact);
+        failures += sub_line(name, seg, *scan);
     }
     std::free(scan);
     std::free(seg);
