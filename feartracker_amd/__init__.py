@@ -11,9 +11,10 @@ from .frames import YUVFrame
 from .tracker import FEARTracker, Tracker, TrackingState
 from .multi_tracker import FEARMultiTracker, PendingBoxes
 from .hip_backend import FEARNetHIP, FearError, load_library, DEFAULT_WEIGHTS, LIB_PATH
-from .jpeg_frames import JpegDecoder, MalformedJPEG, UnsupportedJPEG, jpeg_decode_host, jpeg_info
-from .jpeg_huffman import jpeg_entropy_indexed_host, jpeg_entropy_parallel_host, jpeg_scan_index_host, jpeg_scan_prepare_host
-from .jpeg_store import JpegStore, StoreFull, plan_decode
+from .jpeg_frames import JpegDecoder, MalformedJPEG, UnsupportedJPEG, jpeg_decode_host, jpeg_info, jpeg_pixels_host
+from .jpeg_huffman import (jpeg_entropy_indexed_host, jpeg_entropy_parallel_host, jpeg_scan_index_host, jpeg_scan_prepare_host,
+                           scan_row_sub)
+from .jpeg_store import JpegStore, StoreFull, plan_decode, plan_decode_rows
 
 __all__ = [
     "DEFAULT_TRACKING_CONFIG", "TARGET_CLASSIFICATION_KEY", "TARGET_REGRESSION_LABEL_KEY",
@@ -21,5 +22,5 @@ __all__ = [
     "FEARMultiTracker", "PendingBoxes", "YUVFrame",
     "FEARNetHIP", "FearError", "load_library", "DEFAULT_WEIGHTS", "LIB_PATH",
     "JpegDecoder", "MalformedJPEG", "UnsupportedJPEG", "jpeg_decode_host", "jpeg_info", "jpeg_entropy_parallel_host", "jpeg_scan_prepare_host",
-    "jpeg_scan_index_host", "jpeg_entropy_indexed_host", "JpegStore", "StoreFull", "plan_decode",
+    "jpeg_scan_index_host", "jpeg_entropy_indexed_host", "JpegStore", "StoreFull", "plan_decode", "plan_decode_rows", "scan_row_sub", "jpeg_pixels_host",
 ]

@@ -41,6 +41,7 @@ struct JhSegment {
     uint32_t first_mcu;
     uint32_t expected;       // the blocks the segment owes
     bool last;
+    uint32_t band_row0, band_rows;   // MODE 3 alone (fear_jpeg_store.h): the MCU rows whose blocks are stored, inside the image
 };
 
 struct JhState {
@@ -100,6 +101,28 @@ __device__ __forceinline__ long jh_block_base(const JhSegment& s, uint32_t ordin
     return b < s.total_blocks ? (long)b * 64 : -1;
 }
 
+// MODE 3: the same for an image that consists of the MCU rows band_row0 .. band_row0 + band_rows) alone; -1 for a block of another row.
+__device__ __forceinline__ long jh_band_base(const JhSegment& s, uint32_t ordinal, int slot) {
+    if (ordinal >= s.expected) return -1;
+    const uint32_t mcu = s.first_mcu + ordinal / (uint32_t)s.nslots;
+    const uint32_t my = mcu / (uint32_t)s.mcus_x, mx = mcu - my * (uint32_t)s.mcus_x;
+    if (my < s.band_row0 || my >= s.band_row0 + s.band_rows) return -1;   // band_row0 + band_rows <= mcus_y <= 1024
+    const uint32_t ry = my - s.band_row0, band_mcus = s.band_rows * (uint32_t)s.mcus_x;
+    uint32_t b;
+    if (slot < s.hv) {
+        const uint32_t j = (uint32_t)slot / (uint32_t)s.h, i = (uint32_t)slot - j * (uint32_t)s.h;
+        b = (ry * (uint32_t)s.v + j) * ((uint32_t)s.mcus_x * (uint32_t)s.h) + mx * (uint32_t)s.h + i;
+    } else {
+        b = band_mcus * (uint32_t)s.hv + (uint32_t)(slot - s.hv) * band_mcus + ry * (uint32_t)s.mcus_x + mx;
+    }
+    return b < band_mcus * (uint32_t)s.nslots ? (long)b * 64 : -1;
+}
+
+template <int MODE>
+__device__ __forceinline__ long jh_base(const JhSegment& s, uint32_t ordinal, int slot) {
+    return MODE == 3 ? jh_band_base(s, ordinal, slot) : jh_block_base(s, ordinal, slot);
+}
+
 // What the count pass gathers and the write pass starts from.
 struct JhLane {
     uint32_t begun;          // blocks begun: in this subsequence (count) | in the segment so far (write)
@@ -118,6 +141,7 @@ __device__ __forceinline__ uint32_t jh_add_dc(JhLane& lane, int comp, uint32_t v
 }
 
 // Symbols from `st` until the position reaches `end` or the segment's end.  MODE 0: the exit state and nothing else.  1: count.  2: write.
+// 3: write, but only the blocks of the band's MCU rows are stored (jh_band_base); every judgement is mode 2's.
 // A code in no table, a DC size above 15 or an index past 63: advance one bit, z = 0.
 template <int MODE>
 __device__ __forceinline__ JhState jh_decode(const JhSegment& s, const FearJpegHuff* tabs, JhState st, uint32_t end, int16_t* coef, JhLane& io) {
@@ -125,10 +149,10 @@ __device__ __forceinline__ JhState jh_decode(const JhSegment& s, const FearJpegH
     uint32_t p = st.p;
     int slot = (int)(st.sz >> 8), z = (int)(st.sz & 255);
     const uint32_t stop = min(end, s.bits);
-    long base = -1;                                                      // MODE 2: the open block's place, -1 if it is dropped
-    bool judged = false;                                                 // MODE 2: the open block, or the next one, is one the segment owes
-    if (MODE == 2) {
-        if (z != 0 && lane.begun > 0) base = jh_block_base(s, lane.begun - 1, slot);
+    long base = -1;                                                      // MODE 2, 3: the open block's place, -1 if it is dropped
+    bool judged = false;                                                 // MODE 2, 3: the open block, or the next one, is one the segment owes
+    if (MODE >= 2) {
+        if (z != 0 && lane.begun > 0) base = jh_base<MODE>(s, lane.begun - 1, slot);
         judged = (z != 0 ? lane.begun - 1 : lane.begun) < s.expected && (z == 0 || lane.begun > 0);
     }
 #pragma unroll 1
@@ -139,7 +163,7 @@ __device__ __forceinline__ JhState jh_decode(const JhSegment& s, const FearJpegH
         if (z == 0) {
             const int t = jh_symbol(tabs[comp], win, &len);
             if (t < 0 || t > 15) {
-                if (MODE == 2 && judged) lane.error = true;
+                if (MODE >= 2 && judged) lane.error = true;
                 p += 1;
                 continue;
             }
@@ -150,9 +174,9 @@ __device__ __forceinline__ JhState jh_decode(const JhSegment& s, const FearJpegH
                 lane.begun += 1;
                 jh_add_dc(lane, comp, (uint32_t)diff);
             }
-            if (MODE == 2) {
+            if (MODE >= 2) {
                 const uint32_t dc = jh_add_dc(lane, comp, (uint32_t)diff);      // the predictor; JCOEF is 16 bits wide
-                base = jh_block_base(s, lane.begun, slot);
+                base = jh_base<MODE>(s, lane.begun, slot);
                 judged = lane.begun < s.expected;
                 lane.begun += 1;
                 if (judged && p > s.bits) lane.error = true;              // the code or its magnitude bits run past the segment
@@ -163,10 +187,10 @@ __device__ __forceinline__ JhState jh_decode(const JhSegment& s, const FearJpegH
         const int rs = jh_symbol(tabs[3 + comp], win, &len);
         const int r = rs >> 4, size = rs & 15;
         if (rs < 0 || z + r > (size ? 63 : (r == 15 ? 62 : 99))) {        // an index past 63, a ZRL that runs past it included
-            if (MODE == 2 && judged) lane.error = true;
+            if (MODE >= 2 && judged) lane.error = true;
             p += 1;
             z = 0;
-            if (MODE == 2) { base = -1; judged = lane.begun < s.expected; }
+            if (MODE >= 2) { base = -1; judged = lane.begun < s.expected; }
             continue;
         }
         int zeros_to, value = 0;
@@ -178,7 +202,7 @@ __device__ __forceinline__ JhState jh_decode(const JhSegment& s, const FearJpegH
             p += (uint32_t)(len + size);
             zeros_to = z + r;
         }
-        if (MODE == 2) {
+        if (MODE >= 2) {
             if (judged && p > s.bits) lane.error = true;
             if (base >= 0) {
 #pragma unroll 1
@@ -190,7 +214,7 @@ __device__ __forceinline__ JhState jh_decode(const JhSegment& s, const FearJpegH
         if (z == 64) {
             z = 0;
             slot = slot + 1 < s.nslots ? slot + 1 : 0;
-            if (MODE == 2) {
+            if (MODE >= 2) {
                 // the segment's last block is complete: in front of a restart marker no whole byte may be left (Bits::restart)
                 if (lane.begun == s.expected && judged && !s.last && p <= s.bits && s.bits - p >= 8) lane.error = true;
                 base = -1;

@@ -1,8 +1,10 @@
 // fear_jpeg_store.h — scans resident on the device and the index a baseline scan lacks (include/fear_train.h: fear_jpeg_index_build,
-// fear_jpeg_huffman_indexed; DESIGN.md section 14, "The resident store").  fear_jpeg_index_build is the second instantiation of
+// fear_jpeg_huffman_indexed, fear_jpeg_huffman_indexed_rows; DESIGN.md section 14, "The resident store").  fear_jpeg_index_build is the second instantiation of
 // jpeg_huffman_kernel (fear_jpeg_huffman.h), which stores every lane's true entry in front of its write pass.  With those entries a later
 // decode is the write pass alone: jpeg_huffman_indexed_kernel gives every subsequence of an image a lane of its own, whatever segment it
-// lies in.  jpeg_huffman.jpeg_scan_index_host and jpeg_entropy_indexed_host restate both in Python.
+// lies in.  jpeg_huffman.jpeg_scan_index_host and jpeg_entropy_indexed_host restate both in Python.  fear_jpeg_huffman_indexed_rows is
+// the same lane for a band of MCU rows: only the subsequences in which the band's blocks lie get a lane (the caller's row_sub table,
+// jpeg_huffman.scan_row_sub), and only the band's blocks are stored, as the dense coefficients of an image of those rows alone.
 // Included by fear_train.hip behind fear_jpeg_huffman.h, whose jh_decode, jh_peek, jh_block_base and JhSegment it uses, and
 // fear_jpeg_decode.h's jd_find_image.
 
@@ -25,7 +27,10 @@ __global__ __launch_bounds__(kJhLanes) void jpeg_indexed_status_kernel(JpegIndex
     if (i < a.n) a.status[i] = ji_records(a)[i].n_sub == 0 ? FEAR_TRAIN_ERR_FORMAT : FEAR_TRAIN_OK;
 }
 
-__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_kernel(JpegIndexedArgs a) {
+// One lane of the indexed decode.  ROWS: fear_jpeg_huffman_indexed_rows' instantiation, whose lanes are the record's sub_count
+// subsequences from sub0 and which stores only the blocks of the record's band of MCU rows, band-dense (jh_band_base).
+template <bool ROWS>
+__device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a) {
     __shared__ __attribute__((aligned(16))) FearJpegHuff tabs[6];        // dc by component, then ac by component
     const int tid = threadIdx.x;
     const int img = jd_find_image(a.table, a.n, blockIdx.x);             // the same for the whole workgroup
@@ -38,7 +43,11 @@ __global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_kernel(JpegInde
     }
     __syncthreads();                                                     // the only barrier
     const uint32_t n_sub = im->n_sub, n_seg = rec->n_seg;
-    const uint64_t sub64 = (uint64_t)(blockIdx.x - a.table[img]) * kJhLanes + (uint32_t)tid;
+    uint64_t sub64 = (uint64_t)(blockIdx.x - a.table[img]) * kJhLanes + (uint32_t)tid;
+    if (ROWS) {
+        if (sub64 >= im->sub_count) return;                              // lanes that do not run judge nothing
+        sub64 += im->sub0;
+    }
     if (sub64 >= n_sub || n_seg == 0) return;
     const uint32_t sub = (uint32_t)sub64;
     const uint4 e = reinterpret_cast<const uint4*>(im->index)[sub];
@@ -75,6 +84,11 @@ __global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_kernel(JpegInde
         s.first_mcu = first_mcu < n_mcu ? (uint32_t)first_mcu : n_mcu;
         s.expected = min(interval, n_mcu - s.first_mcu) * (uint32_t)s.nslots;
         s.last = seg + 1 == n_seg;
+        if (ROWS) {                                                      // the band inside the image: an explicit range, no wrap-around
+            const uint32_t mcus_y = (uint32_t)max(rec->mcus_y, 1);
+            s.band_row0 = min(im->mcu_row0, mcus_y);
+            s.band_rows = min(im->mcu_rows, mcus_y - s.band_row0);
+        }
     }
     int32_t* status = a.status + img;
     const uint64_t k = (uint64_t)sub - first;                            // the subsequence within its segment
@@ -91,7 +105,7 @@ __global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_kernel(JpegInde
     lane.dc1 = e.w & 0xFFFFu;
     lane.dc2 = e.w >> 16;
     const uint32_t end = ((uint32_t)k + 1u) * SB;                        // k SB < bits <= 2^27 (8 FEAR_JPEG_DEVICE_SCAN_MAX), SB <= 2^13: no overflow
-    const JhState out = jh_decode<2>(s, tabs, entry, end, a.coef + im->coef_offset, lane);
+    const JhState out = jh_decode<ROWS ? 3 : 2>(s, tabs, entry, end, a.coef + im->coef_offset, lane);
     bool failed = lane.error;
     // the segment's last subsequence: fewer complete blocks than the segment owes, as jpeg_huffman_kernel judges its true chain's end
     if (end >= s.bits && (lane.begun - ((out.sz & 255) != 0 ? 1u : 0u) < s.expected || (lane.begun == 0 && s.expected > 0))) failed = true;
@@ -99,6 +113,10 @@ __global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_kernel(JpegInde
     if (sub + 1 == n_sub && !s.last) failed = true;                       // empty segments behind the image's last subsequence
     if (failed) *status = FEAR_TRAIN_ERR_FORMAT;                          // every lane that stores stores the same value
 }
+
+__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_kernel(JpegIndexedArgs a) { ji_lane<false>(a); }
+
+__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_rows_kernel(JpegIndexedArgs a) { ji_lane<true>(a); }
 
 }  // namespace
 
@@ -166,6 +184,38 @@ int fear_jpeg_huffman_indexed(const FearJpegIndexed* images, int n, const void* 
     LAUNCH_CHECK();
     if (groups == 0) return FEAR_TRAIN_OK;
     hipLaunchKernelGGL(jpeg_huffman_indexed_kernel, dim3((unsigned)groups), dim3(kJhLanes), 0, static_cast<hipStream_t>(stream), a);
+    LAUNCH_CHECK();
+    return FEAR_TRAIN_OK;
+}
+
+int fear_jpeg_huffman_indexed_rows(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
+                                   int subsequence_bytes, void* stream) {
+    if (n < 0 || n > 65535 || subsequence_bytes < 4 || subsequence_bytes > 1024 || (subsequence_bytes & 3) != 0) return FEAR_TRAIN_ERR_SHAPE;
+    if (n == 0) return FEAR_TRAIN_OK;
+    if (!images || !table_dev || !coef || !status_dev) return FEAR_TRAIN_ERR_NULL;
+    uint64_t groups = 0;
+    for (int i = 0; i < n; ++i) {
+        const FearJpegIndexed& im = images[i];
+        if (!im.scan || !im.sub_start || (!im.index && im.n_sub != 0)) return FEAR_TRAIN_ERR_NULL;
+        if ((reinterpret_cast<uintptr_t>(im.index) & 15) != 0 || (reinterpret_cast<uintptr_t>(im.scan) & 15) != 0 ||
+            (reinterpret_cast<uintptr_t>(im.sub_start) & 3) != 0)
+            return FEAR_TRAIN_ERR_SHAPE;
+        if (im.sub_count != 0 && (im.sub0 >= im.n_sub || im.sub_count > im.n_sub - im.sub0)) return FEAR_TRAIN_ERR_SHAPE;
+        if (im.mcu_row0 > FEAR_JPEG_MAX_SIDE / 8 || im.mcu_rows > FEAR_JPEG_MAX_SIDE / 8 - im.mcu_row0) return FEAR_TRAIN_ERR_SHAPE;
+        groups += ((uint64_t)im.sub_count + kJhLanes - 1) / kJhLanes;
+    }
+    if (groups > 0x7fffffffu) return FEAR_TRAIN_ERR_SHAPE;
+    JpegIndexedArgs a{};
+    a.table = static_cast<const uint32_t*>(table_dev);
+    a.coef = coef;
+    a.status = status_dev;
+    a.n = n;
+    a.subsequence_bits = subsequence_bytes * 8;
+    hipLaunchKernelGGL(jpeg_indexed_status_kernel, dim3((unsigned)((n + kJhLanes - 1) / kJhLanes)), dim3(kJhLanes), 0,
+                       static_cast<hipStream_t>(stream), a);
+    LAUNCH_CHECK();
+    if (groups == 0) return FEAR_TRAIN_OK;
+    hipLaunchKernelGGL(jpeg_huffman_indexed_rows_kernel, dim3((unsigned)groups), dim3(kJhLanes), 0, static_cast<hipStream_t>(stream), a);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }

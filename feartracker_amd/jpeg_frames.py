@@ -295,8 +295,15 @@ def _upsample_h2v1(c: np.ndarray) -> np.ndarray:
 
 def jpeg_decode_host(data: bytes) -> np.ndarray:
     """A baseline JPEG file -> uint8 (H, W, 3) RGB, as libjpeg decodes it with its defaults.  Slow; the statement the device is held to."""
-    hd, coef = jpeg_coefficients_host(data)
-    H, W, nf = hd.height, hd.width, len(hd.ids)
+    return jpeg_pixels_host(*jpeg_coefficients_host(data))
+
+
+def jpeg_pixels_host(hd: _Header, coef: List[np.ndarray], height: Optional[int] = None) -> np.ndarray:
+    """The pixel stage of `jpeg_decode_host` on coefficients: dequantisation, islow IDCT, fancy upsampling at the true edges, colour.
+    `height` (the header's by default) makes it the decode of a BAND image, as `JpegStore.decode_rows` hands one to
+    `fear_jpeg_decode_u8`: `coef` holds the blocks of some consecutive MCU rows alone and `height` is the pixel rows they cover, so the
+    edge rules apply at the band's edges."""
+    H, W, nf = hd.height if height is None else int(height), hd.width, len(hd.ids)
     planes = []
     for c in range(nf):
         q = hd.q[hd.tq[c]]

@@ -94,6 +94,19 @@ class _Geometry:
         hc, vc = (self.h, self.v) if c == 0 else (1, 1)
         return self.comp_first[c] + (my * vc + j) * self.blocks_w[c] + mx * hc + i
 
+    def band_block(self, first_mcu: int, ordinal: int, slot: int, row0: int, rows: int) -> int:
+        """The same index in an image that consists of the MCU rows row0 .. row0 + rows) alone (jh_band_base): -1 for a block of another
+        row, by an explicit range test."""
+        my, mx = divmod(first_mcu + ordinal // self.nslots, self.mcus_x)
+        if my < row0 or my >= row0 + rows:
+            return -1
+        c = self.comp[slot]
+        j, i = divmod(slot, self.h) if c == 0 else (0, 0)
+        hc, vc = (self.h, self.v) if c == 0 else (1, 1)
+        band_mcus = rows * self.mcus_x
+        first = 0 if c == 0 else band_mcus * self.h * self.v + (c - 1) * band_mcus
+        return first + ((my - row0) * vc + j) * self.blocks_w[c] + mx * hc + i
+
 
 _ERR, _DC, _ZEROS, _AC, _END = range(5)
 
@@ -283,9 +296,11 @@ class _Segment:
         self.last = s == len(seg_start) - 2
 
 
-def _write_pass(sg: _Segment, g: _Geometry, entry, end: int, begun: int, pred: list, dense, writes):
+def _write_pass(sg: _Segment, g: _Geometry, entry, end: int, begun: int, pred: list, dense, writes, band=None, record=None):
     """One lane of the write pass: decode from the true `entry` = (p, slot, z) to `end`, `begun` blocks of the segment begun in front
-    and `pred` the predictors (updated in place).  Stores what it decodes, judges it, and returns (exit state, begun, failed)."""
+    and `pred` the predictors (updated in place).  Stores what it decodes, judges it, and returns (exit state, begun, failed).  With
+    `band` = (row0, rows) only the blocks of those MCU rows are stored, band-dense (`dense` holds 64 values per block of the band); the
+    judgements are the same.  `record`, a list, takes every store the lane would make in any layout: (MCU, slot, z from, z to, value)."""
     ev, failed = [], False
     out = _decode(sg.buf, sg.L, entry, end, g, ev)
     slot, is_open = entry[1], entry[2] != 0                              # a block begun in an earlier subsequence is still open
@@ -313,8 +328,15 @@ def _write_pass(sg: _Segment, g: _Geometry, entry, end: int, begun: int, pred: l
         if 1 <= begun <= sg.expected:                                    # blocks past the segment's count are dropped
             if e[-1] > sg.L:                                             # the symbol or its magnitude bits run past the segment
                 failed = True
-            b = g.block(sg.first_mcu, begun - 1, slot)
-            if dense is not None and b < g.total_blocks:
+            if record is not None:
+                record.append((sg.first_mcu + (begun - 1) // g.nslots, slot, z0, z1, value))
+            if band is None:
+                b = g.block(sg.first_mcu, begun - 1, slot)
+                inside = b < g.total_blocks
+            else:
+                b = g.band_block(sg.first_mcu, begun - 1, slot, band[0], band[1])
+                inside = 0 <= b < band[1] * g.mcus_x * g.nslots
+            if dense is not None and inside:
                 dense[64 * b + z0:64 * b + z1] = value
                 writes[64 * b + z0:64 * b + z1] += 1
     return out, begun, failed
@@ -351,13 +373,41 @@ def jpeg_scan_index_host(data: bytes, subsequence_bytes: int = 128):
     return hd, sub_start, index, status
 
 
-def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: int, order=None):
+def scan_row_sub(header: _Header, sub_start, index) -> np.ndarray:
+    """uint32 [mcus_y + 1], the row table of a resident scan: row_sub[r] is the image-numbered subsequence in which the first block of
+    MCU row r begins — the last subsequence of that block's restart segment whose entry has `begun` less than or equal to the block's
+    ordinal in the segment (the entries of a segment count the blocks begun in front of them, so the block begins in that subsequence
+    and no later one) — and row_sub[mcus_y] = n_sub.  The blocks of the MCU rows a .. b) then lie wholly in the subsequences
+    row_sub[a] .. min(row_sub[b], n_sub - 1): the last block of row b - 1 ends where the first of row b begins, or with its segment.
+    From the index `fear_jpeg_index_build` wrote, `sub_start`, the restart interval, mcus_x and the slots per MCU; no loop over rows."""
+    sub_start = np.asarray(sub_start, dtype=np.int64)
+    n_seg, n_sub = sub_start.size - 1, int(sub_start[-1])
+    assert len(index) == n_sub
+    nslots = 1 if len(header.ids) == 1 else header.h[0] * header.v[0] + 2
+    n_mcu = header.mcus_x * header.mcus_y
+    interval = header.restart if header.restart else n_mcu
+    mcu = np.arange(header.mcus_y, dtype=np.int64) * header.mcus_x
+    seg = np.minimum(mcu // interval, n_seg - 1)
+    ordinal = (mcu - seg * interval) * nslots
+    # (segment, begun) is non-decreasing over an image's subsequences: one search for all rows
+    of_sub = np.searchsorted(sub_start[1:], np.arange(n_sub), side="right")
+    key = (of_sub.astype(np.int64) << 32) | np.asarray(index["begun"], dtype=np.int64)
+    at = np.searchsorted(key, (seg << 32) | ordinal, side="right") - 1
+    at = np.minimum(np.maximum(at, sub_start[seg]), n_sub)                     # (a segment without a subsequence: its place)
+    return np.concatenate([at, [n_sub]]).astype(np.uint32)
+
+
+def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: int, order=None, band=None, row_sub=None):
     """The contract of `fear_jpeg_huffman_indexed`: (coefficients per component, status).  Every subsequence is decoded from its index
     entry alone, in `order` (any permutation of the image's subsequences; the natural one by default), as one lane of
     jpeg_huffman_indexed_kernel does it: the segment by a search of `sub_start`, the write pass's rules, and the verdict — the lane of a
     segment's last subsequence judges the segment's block count, the lane of its first an empty segment in front, the lane of the
     image's last subsequence empty segments behind, and an image without a subsequence fails.  Asserts that every position is written
-    exactly once when the status is 0."""
+    exactly once when the status is 0.
+    With `band` = (a, b), MCU rows a .. b) clipped to the image, it is the contract of `fear_jpeg_huffman_indexed_rows`: only the
+    subsequences row_sub[a] .. min(row_sub[b], n_sub - 1) are decoded (`row_sub` is `scan_row_sub`'s table, computed when None; `order`
+    permutes those), only the blocks of the band's rows are stored, and the coefficients are the band's: per component the rows of an
+    image that consists of those MCU rows alone.  Lanes that do not run judge nothing."""
     _check_subsequence_bytes(subsequence_bytes)
     data = bytes(data)
     hd = _parse(data)
@@ -366,17 +416,25 @@ def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: 
     n_seg, n_sub, SB = len(seg_start) - 1, len(index), 8 * subsequence_bytes
     sub_start = np.asarray(sub_start, dtype=np.int64)
     assert sub_start.size == n_seg + 1 and int(sub_start[-1]) == n_sub
-    dense = np.zeros(64 * g.total_blocks, dtype=np.int16)
-    writes = np.zeros(64 * g.total_blocks, dtype=np.uint8)
+    lanes, rows_band, n_values = range(n_sub), None, 64 * g.total_blocks
+    if band is not None:
+        a = min(max(int(band[0]), 0), hd.mcus_y)
+        b = min(max(int(band[1]), a), hd.mcus_y)
+        if row_sub is None:
+            row_sub = scan_row_sub(hd, sub_start, index)
+        rows_band, n_values = (a, b - a), 64 * (b - a) * g.mcus_x * g.nslots
+        lanes = range(int(row_sub[a]), min(int(row_sub[b]), n_sub - 1) + 1) if b > a else range(0)
+    dense = np.zeros(n_values, dtype=np.int16)
+    writes = np.zeros(n_values, dtype=np.uint8)
     segs = [_Segment(hd, g, stream, seg_start, s) for s in range(n_seg)]
     status = ERR_FORMAT if n_sub == 0 else 0
-    for sub in (range(n_sub) if order is None else order):
+    for sub in (lanes if order is None else [lanes[int(k)] for k in order]):
         sub = int(sub)
         s = int(np.searchsorted(sub_start[:n_seg], sub, side="right")) - 1   # the last segment that starts at or in front of `sub`
         sg, i, e = segs[s], sub - int(sub_start[s]), index[sub]
         slot, z = min(int(e["sz"]) >> 8, g.nslots - 1), min(int(e["sz"]) & 255, 63)
         pred = [int(v) for v in e["dc"]]
-        state, begun, failed = _write_pass(sg, g, (int(e["p"]), slot, z), (i + 1) * SB, int(e["begun"]), pred, dense, writes)
+        state, begun, failed = _write_pass(sg, g, (int(e["p"]), slot, z), (i + 1) * SB, int(e["begun"]), pred, dense, writes, rows_band)
         if (i + 1) * SB >= sg.L and begun - (state[2] != 0) < sg.expected:    # the segment's last subsequence: its block count
             failed = True
         if i == 0 and s > 0 and sub_start[s - 1] == sub_start[s]:            # an empty segment in front owes blocks
@@ -389,7 +447,81 @@ def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: 
         assert np.all(writes == 1), "every position of every block is written exactly once"
     coef, at = [], 0
     for c in range(g.nf):
-        size = hd.blocks_w[c] * hd.blocks_h[c]
-        coef.append(dense[64 * at:64 * (at + size)].reshape(hd.blocks_h[c], hd.blocks_w[c], 64))
+        high = hd.blocks_h[c] if rows_band is None else rows_band[1] * (g.v if c == 0 else 1)
+        size = hd.blocks_w[c] * high
+        coef.append(dense[64 * at:64 * (at + size)].reshape(high, hd.blocks_w[c], 64))
         at += size
     return coef, status
+
+
+def jpeg_entropy_bands_host(data: bytes, sub_start, index, subsequence_bytes: int, bands, row_sub=None):
+    """`jpeg_entropy_indexed_host(..., band=(a, b))` for many bands of one file at once: [(coefficients per component, status)] in the
+    order of `bands`.  Every lane decodes and judges once, whatever the band (its decode does not depend on it), and records what it
+    would store; per band the stores of the lanes that run, row_sub[a] .. min(row_sub[b], n_sub - 1), whose MCU row passes the explicit
+    range test a <= row < b are placed band-dense, and the lanes that do not run judge nothing.  Asserts that every position of a band
+    is written exactly once when its status is 0."""
+    _check_subsequence_bytes(subsequence_bytes)
+    data = bytes(data)
+    hd = _parse(data)
+    stream, seg_start = jpeg_scan_prepare_host(data, hd)
+    g = _Geometry(hd)
+    n_seg, n_sub, SB = len(seg_start) - 1, len(index), 8 * subsequence_bytes
+    sub_start = np.asarray(sub_start, dtype=np.int64)
+    if row_sub is None:
+        row_sub = scan_row_sub(hd, sub_start, index)
+    segs = [_Segment(hd, g, stream, seg_start, s) for s in range(n_seg)]
+    lane_failed = np.zeros(n_sub, dtype=bool)
+    lane_of, mcu_of, slot_of, z_of, value_of = [], [], [], [], []
+    for sub in range(n_sub):
+        s = int(np.searchsorted(sub_start[:n_seg], sub, side="right")) - 1
+        sg, i, e = segs[s], sub - int(sub_start[s]), index[sub]
+        slot, z = min(int(e["sz"]) >> 8, g.nslots - 1), min(int(e["sz"]) & 255, 63)
+        record = []
+        state, begun, failed = _write_pass(sg, g, (int(e["p"]), slot, z), (i + 1) * SB, int(e["begun"]), [int(v) for v in e["dc"]], None, None,
+                                           record=record)
+        if (i + 1) * SB >= sg.L and begun - (state[2] != 0) < sg.expected:
+            failed = True
+        if i == 0 and s > 0 and sub_start[s - 1] == sub_start[s]:
+            failed = True
+        if sub == n_sub - 1 and s != n_seg - 1:
+            failed = True
+        lane_failed[sub] = failed
+        for mcu, slot, z0, z1, value in record:
+            lane_of += [sub] * (z1 - z0)
+            mcu_of += [mcu] * (z1 - z0)
+            slot_of += [slot] * (z1 - z0)
+            z_of += range(z0, z1)
+            value_of += [value] * (z1 - z0)
+    lane_of, mcu_of, slot_of, z_of = (np.array(v, dtype=np.int64) for v in (lane_of, mcu_of, slot_of, z_of))
+    value_of = np.array(value_of, dtype=np.int64).astype(np.int16)
+    my, mx = mcu_of // g.mcus_x, mcu_of % g.mcus_x
+    comp = np.array(g.comp, dtype=np.int64)[slot_of]
+    luma = comp == 0
+    j, i = np.where(luma, slot_of // g.h, 0), np.where(luma, slot_of % g.h, 0)
+    out = []
+    for band in bands:
+        a = min(max(int(band[0]), 0), hd.mcus_y)
+        b = min(max(int(band[1]), a), hd.mcus_y)
+        band_mcus = (b - a) * g.mcus_x
+        n_values = 64 * band_mcus * g.nslots
+        first, last = (int(row_sub[a]), min(int(row_sub[b]), n_sub - 1)) if b > a else (0, -1)
+        ran = (lane_of >= first) & (lane_of <= last)
+        keep = ran & (my >= a) & (my < b)
+        ry = my[keep] - a
+        block = np.where(luma[keep], (ry * g.v + j[keep]) * (g.mcus_x * g.h) + mx[keep] * g.h + i[keep],
+                         band_mcus * g.h * g.v + (comp[keep] - 1) * band_mcus + ry * g.mcus_x + mx[keep])
+        at = 64 * block + z_of[keep]
+        status = ERR_FORMAT if n_sub == 0 or bool(lane_failed[first:last + 1].any()) else 0
+        dense = np.zeros(n_values, dtype=np.int16)
+        dense[at] = value_of[keep]
+        if status == 0:
+            assert np.array_equal(np.bincount(at, minlength=n_values), np.ones(n_values, dtype=np.int64)), \
+                "every position of the band is written exactly once"
+        coef, where = [], 0
+        for c in range(g.nf):
+            high = (b - a) * (g.v if c == 0 else 1)
+            size = hd.blocks_w[c] * high
+            coef.append(dense[64 * where:64 * (where + size)].reshape(high, hd.blocks_w[c], 64))
+            where += size
+        out.append((coef, status))
+    return out

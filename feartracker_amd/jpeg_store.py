@@ -5,7 +5,13 @@ host threads, the unstuffed bytes uploaded into device slabs — and builds once
 (`fear_jpeg_index_build`: the true entry of every subsequence, 16 bytes each, kept next to the bytes).  `JpegStore.decode` then runs
 `fear_jpeg_huffman_indexed`, a single write pass with one lane per subsequence, and the unchanged `fear_jpeg_decode_u8`; the host's share
 of a call is a few numpy gathers over the ids (`plan_decode`) and one small pinned upload.  jpeg_huffman.jpeg_scan_index_host and
-jpeg_entropy_indexed_host state the two device calls in Python."""
+jpeg_entropy_indexed_host state the two device calls in Python.
+
+A training pair reads only the rows of its context boxes.  `add` therefore also keeps, per file, the row table `row_sub` (the
+subsequence in which each MCU row begins, `jpeg_huffman.scan_row_sub`, from the index it has just built) and the frame's border colour
+(`fear_frame_border_u8` of the full decode, in a device table that `borders(ids)` gathers), and `JpegStore.decode_rows` decodes a band of
+rows per frame: `plan_decode_rows` on the host, `fear_jpeg_huffman_indexed_rows` with lanes for the band's subsequences alone, and the
+unchanged `fear_jpeg_decode_u8` on the band as an image of its own ("Bands of rows")."""
 from __future__ import annotations
 
 import ctypes
@@ -15,12 +21,15 @@ import numpy as np
 
 from . import jpeg_frames
 from .jpeg_frames import ERR_UNSUPPORTED, Item, JpegDecoder, MalformedJPEG, UnsupportedJPEG, _raise_as_python
-from .jpeg_huffman import _check_subsequence_bytes
+from .jpeg_huffman import SUBSEQ_DTYPE, _check_subsequence_bytes, scan_row_sub
 
 KIND_SCAN, KIND_PIXELS = 0, 1
 KIND_NAMES = np.array(["scan", "pixels"])
 LANES = 256                                   # csrc/fear_jpeg_store.h: subsequences per workgroup of jpeg_huffman_indexed_kernel
-COLUMNS = np.dtype([("n_seg", "<u4"), ("n_sub", "<u4"), ("total_blocks", "<u4"), ("H", "<i4"), ("W", "<i4"), ("kind", "u1")])
+# one row per entry; the second line is what a band needs: the MCU grid, an MCU's height in pixels, its blocks, 1 where the fancy
+# upsampling reads a chroma row above and below (v == 2), and where the entry's mcus_y + 1 values of the ragged row_sub array begin
+COLUMNS = np.dtype([("n_seg", "<u4"), ("n_sub", "<u4"), ("total_blocks", "<u4"), ("H", "<i4"), ("W", "<i4"), ("kind", "u1"),
+                    ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("mcu_h", "<i4"), ("nslots", "<i4"), ("halo", "u1"), ("row_at", "<i8")])
 
 
 class StoreFull(MemoryError):
@@ -74,6 +83,74 @@ def plan_decode(columns: np.ndarray, ids, workspace_limit: int, max_group: int =
     return groups
 
 
+def scan_columns(col, info, n_seg: int, n_sub: int, row_at: int) -> None:
+    """Fill one row of the mirror (COLUMNS) for a "scan" entry from its FearJpegInfo."""
+    col["n_seg"], col["n_sub"], col["total_blocks"], col["H"], col["W"], col["kind"] = n_seg, n_sub, info.total_blocks, info.height, info.width, KIND_SCAN
+    col["mcus_x"], col["mcus_y"], col["mcu_h"], col["halo"] = info.mcus_x, info.mcus_y, 8 * info.v[0], info.v[0] == 2
+    col["nslots"], col["row_at"] = (info.h[0] * info.v[0] + 2 if info.components == 3 else 1), row_at
+
+
+def plan_decode_rows(columns: np.ndarray, row_sub: np.ndarray, ids, rows, workspace_limit: int, max_group: int = 65535) -> List[dict]:
+    """The host's share of `JpegStore.decode_rows`, as `plan_decode` a pure function without a loop over the files: of the mirror's
+    columns, the ragged row table (`columns["row_at"]` is where an entry's mcus_y + 1 values begin in `row_sub`), the ids and `rows`,
+    (n, 2) pixel rows [y0, y1) per position, clipped to [0, H].  The band of a "scan" position is the MCU rows a .. b),
+    a = y0 // mcu_h and b = ceil(y1 / mcu_h), one more on each side, clipped to the image, where `halo` is set (the fancy upsampling of
+    v == 2 reads one chroma row above and below); y0 >= y1 is the empty band.  Groups are cut as `plan_decode` cuts them, by the BAND's
+    dense coefficients (128 bytes per block of the band).  Per group, over its "scan" positions with a band, `scan` (relative to lo):
+        sub0, sub_count       the lanes: subsequences row_sub[a] .. min(row_sub[b], n_sub - 1)
+        sub_prefix            uint32 [nd + 1] prefix sums of ceil(sub_count / 256): fear_jpeg_huffman_indexed_rows' workgroups
+        mcu_row0, mcu_rows    the band; `band_y0` = a mcu_h its first pixel row and `band_height` its rows: mcu_rows mcu_h, or what is left
+                              of the image when the band reaches its last MCU row, so that libjpeg's edge rules apply at the true edges
+        block_prefix, pixel_prefix, coef_offset, values, plane_offset, workspace_bytes, most
+                              plan_decode's, of the band as an image of its own
+        band_out              bytes from the position's frame to the band's first row, 3 W band_y0
+    and over all its positions `out_offset` and `out_bytes`: whole frames, as plan_decode's."""
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 2)
+    col = columns[ids]
+    is_scan = col["kind"] == KIND_SCAN
+    H, W, mcu_h = col["H"].astype(np.int64), col["W"].astype(np.int64), np.maximum(col["mcu_h"].astype(np.int64), 1)
+    mcus_y = col["mcus_y"].astype(np.int64)
+    y0, y1 = np.clip(rows[:, 0], 0, H), np.clip(rows[:, 1], 0, H)
+    some = is_scan & (y0 < y1)
+    halo = col["halo"].astype(np.int64)
+    a = np.where(some, np.maximum(y0 // mcu_h - halo, 0), 0)
+    b = np.where(some, np.minimum(-(-y1 // mcu_h) + halo, mcus_y), 0)
+    blocks = (b - a) * col["mcus_x"].astype(np.int64) * col["nslots"].astype(np.int64)
+    band_y0 = a * mcu_h
+    band_h = np.minimum(b * mcu_h, H) - band_y0
+    n_sub = col["n_sub"].astype(np.int64)
+    at = np.where(some, col["row_at"], 0)
+    first = np.where(some, row_sub[at + a].astype(np.int64), 0) if row_sub.size else np.zeros(ids.size, np.int64)
+    last = np.where(some, np.minimum(row_sub[at + b].astype(np.int64), n_sub - 1), -1) if row_sub.size else np.full(ids.size, -1, np.int64)
+    count = np.maximum(last - first + 1, 0)
+    pixels = H * W
+    need = _exclusive(128 * blocks)
+    groups, lo, n = [], 0, ids.size
+    while lo < n:                                                       # one turn per group
+        hi = int(np.searchsorted(need, need[lo] + max(int(workspace_limit), 0), side="right")) - 1
+        hi = min(max(hi, lo + 1), n, lo + max_group)
+        scan = np.flatnonzero(some[lo:hi])
+        pick = lo + scan
+        bl = blocks[pick]
+        dense = _exclusive(64 * bl)
+        out = _exclusive(_up(3 * pixels[lo:hi], 16))
+        groups.append(dict(
+            lo=lo, hi=hi, scan=scan,
+            sub0=first[pick].astype(np.uint32), sub_count=count[pick].astype(np.uint32),
+            sub_prefix=_exclusive(-(-count[pick] // LANES)).astype(np.uint32),
+            mcu_row0=a[pick].astype(np.uint32), mcu_rows=(b - a)[pick].astype(np.uint32),
+            band_y0=band_y0[pick], band_height=band_h[pick].astype(np.int32), band_out=3 * W[pick] * band_y0[pick],
+            block_prefix=_exclusive(-(-bl // 32)).astype(np.uint32),
+            pixel_prefix=_exclusive(-(-(band_h[pick] * W[pick]) // 256)).astype(np.uint32),
+            coef_offset=dense[:-1].astype(np.uint64), values=int(dense[-1]),
+            plane_offset=dense[:-1].astype(np.uint64), workspace_bytes=16 + int(dense[-1]),
+            most=int(bl.max()) if bl.size else 0,
+            out_offset=out[:-1], out_bytes=int(out[-1])))
+        lo = hi
+    return groups
+
+
 class JpegStore:
     """Baseline JPEG files kept on the device, decoded by id: uint8 (H, W, 3) RGB device tensors, byte for byte what `JpegDecoder` and
     libjpeg decode.
@@ -100,7 +177,12 @@ class JpegStore:
     store it should never fire.  The statuses of every group of the current call are kept, however small `workspace_limit` makes them,
     and those of the last PENDING_CALLS groups of earlier unchecked calls.  `decode` may be called on any stream (the shared block_start
     table is handed from stream to stream by an event); `add` ends with a synchronise, so what it stored is complete for all of them.
-    Out of scope: eviction and `remove`, saving a store to disk, sharding over ranks, progressive files, and `JpegDecoder`'s default."""
+    `decode_rows(ids, rows)` decodes a band of rows per frame and `borders(ids)` gathers the frames' border colours, which `add` computed
+    once: together they feed `TrainPairBuilder.build(..., borders=)` with entropy and pixel work for the rows the pairs read alone.  Per
+    file the store keeps mcus_y + 1 row-table values on the host and 3 bytes of the device's border table more (`resident["rows"]`,
+    `resident["border"]`, both counted in `nbytes`).
+    Out of scope: eviction and `remove`, saving a store to disk, sharding over ranks, progressive files, `JpegDecoder`'s default, compact
+    band frames and a window-aware frame record (`decode_rows` returns frames of the full shape)."""
     PENDING_CALLS = 64
 
     def __init__(self, device: int = 0, capacity_bytes: Optional[int] = None, subsequence_bytes: int = 128, slab_bytes: int = 256 << 20,
@@ -123,7 +205,9 @@ class JpegStore:
     def clear(self) -> None:
         """Forget every entry and free the slabs.  Ids start at 0 again."""
         self._n, self.nbytes = 0, 0
-        self.resident = dict(bytes=0, index=0, records=0, pixels=0)      # what nbytes is made of
+        self.resident = dict(bytes=0, index=0, records=0, pixels=0, rows=0, border=0)      # what nbytes is made of
+        self._row_sub, self._row_used = np.zeros(4 * self._initial_rows, dtype=np.uint32), 0   # ragged: COLUMNS["row_at"] indexes it
+        self._border = None                                              # (capacity, 3) uint8 on the device, grown with the mirrors
         self._indexed, self._image, self._columns = (np.zeros(self._initial_rows, dtype=d) for d in self._dtypes)
         self._slabs: List = []
         self._open, self._cursor = None, 0                               # the slab that is being filled
@@ -142,6 +226,20 @@ class JpegStore:
     @property
     def kinds(self) -> np.ndarray:
         return KIND_NAMES[self._columns["kind"][:self._n]]
+
+    def borders(self, ids):
+        """(len(ids), 3) uint8 on the device: `fear_frame_border_u8` of each file's full decode, computed once in `add` — what
+        `TrainPairBuilder.build(..., borders=)` takes.  A gather on the current stream; the ids go up non-blocking, it never waits."""
+        import torch
+        ids = self._checked(ids)
+        with torch.cuda.device(self.device):
+            if ids.size == 0 or self._border is None:
+                return torch.empty((0, 3), dtype=torch.uint8, device=self.device)
+            pinned = torch.empty(ids.size, dtype=torch.int64, pin_memory=True)
+            np.copyto(pinned.numpy(), ids)
+            index = pinned.to(self.device, non_blocking=True)
+            self._pinned = self._pinned[-1:] + [pinned]
+            return self._border.index_select(0, index)
 
     def shape(self, ids) -> np.ndarray:
         """(len(ids), 2) int32: height and width."""
@@ -200,7 +298,7 @@ class JpegStore:
                 except (MalformedJPEG, UnsupportedJPEG) as exc:
                     raise type(exc)(f"item {i}: {exc}") from None
         # the resident layout of every "scan" file, from its base: bytes | seg_start | sub_start | index | FearJpegScan, each at 16 bytes
-        layout, split, need = {}, dict(bytes=0, index=0, records=0, pixels=0), 0
+        layout, split, need = {}, dict(bytes=0, index=0, records=0, pixels=0, rows=0, border=3 * n), 0
         for i in scans:
             info, data, seg, scan = prepared[i]
             sub, count = np.empty(seg.size, dtype=np.uint32), ctypes.c_uint32(0)
@@ -215,6 +313,7 @@ class JpegStore:
             split["bytes"] += at_index
             split["index"] += at_record - at_index
             split["records"] += ctypes.sizeof(abi.FearJpegScan)
+            split["rows"] += 4 * (int(info.mcus_y) + 1)
         for i in through_host:
             split["pixels"] += 3 * prepared[i][0].width * prepared[i][0].height
         for px in raw.values():
@@ -224,7 +323,7 @@ class JpegStore:
             raise StoreFull(f"{need} bytes more on top of {self.nbytes} exceed the capacity of {self.capacity_bytes}")
         with torch.cuda.device(self.device):
             # place: tentative cursors, committed at the end
-            new_slabs, open_slab, cursor, base, runs = [], self._open, self._cursor, {}, []
+            new_slabs, open_slab, cursor, base, runs, placed, first_new = [], self._open, self._cursor, {}, [], {}, self._n
             for i in scans:
                 size = layout[i][5]
                 if size > self.slab_bytes:                               # a slab of its own; the open slab stays open
@@ -238,6 +337,7 @@ class JpegStore:
                     cursor += size
                 assert slab.data_ptr() % 16 == 0
                 base[i] = slab.data_ptr() + at
+                placed[i] = (slab, at)
                 if runs and runs[-1][0] is slab and runs[-1][1] + runs[-1][2] == at:
                     runs[-1][2] += size
                     runs[-1][3].append(i)
@@ -266,7 +366,8 @@ class JpegStore:
                 groups[-1].append(i)
                 dense += want
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            verdicts = []
+            verdicts, index_back = [], []
+            new_borders = torch.zeros((n, 3), dtype=torch.uint8, device=self.device)
             for group in groups:
                 m = len(group)
                 if m == 0:
@@ -295,6 +396,8 @@ class JpegStore:
                            ctypes.c_void_p(dev.data_ptr() + index_at), ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(status.data_ptr()),
                            SBY, stream)
                 verdicts.append((group, status, dev, coef))
+                new_borders[group] = self._group_borders([prepared[i][0] for i in group], records, coef, stream)
+                index_back.append((group, [base[i] for i in group]))
             for group, status, _, _ in verdicts:
                 got = status.cpu().numpy()                               # add waits: set-up
                 for k in np.flatnonzero(got):
@@ -311,6 +414,27 @@ class JpegStore:
                     raise type(exc)(f"item {i}: {exc}") from None
             for i, px in raw.items():
                 pixels[i] = torch.from_numpy(px.copy()).to(self.device)         # (the fallback's array may be read-only)
+            if pixels:                                                   # the border colour of the entries kept as pixels
+                kept = sorted(pixels)
+                new_borders[kept] = self._frame_borders([pixels[i] for i in kept], stream)
+            # the row tables, from the index the device has just written: copied back once, add waits anyway
+            row_tables = {}
+            for i in scans:
+                sub, at_seg, at_sub, at_index, at_record, end = layout[i]
+                slab, at = placed[i]
+                index = slab[at + at_index:at + at_record].cpu().numpy().view(SUBSEQ_DTYPE)
+                row_tables[i] = self._row_table(prepared[i][0], sub, index)
+            border = self._border                                        # grown here, committed below
+            if border is None or border.shape[0] < first_new + n:
+                have = max(self._initial_rows, 1) if border is None else border.shape[0]
+                while have < first_new + n:
+                    have *= 2
+                border = torch.zeros((have, 3), dtype=torch.uint8, device=self.device)
+                if self._border is not None and first_new:
+                    border[:first_new] = self._border[:first_new]
+                grown_border = True
+            else:
+                grown_border = False
             torch.cuda.current_stream().synchronize()                    # what was stored is complete for a decode on any stream
         # commit
         first = self._n
@@ -323,19 +447,82 @@ class JpegStore:
             row["scan"], row["index"], row["sub_start"], row["n_sub"] = base[i] + at_record, base[i] + at_index, base[i] + at_sub, int(sub[-1])
             img["width"], img["height"], img["components"], img["h"], img["v"] = info.width, info.height, info.components, info.h[0], info.v[0]
             img["qt"] = np.ctypeslib.as_array(info.qt)
-            col["n_seg"], col["n_sub"], col["total_blocks"], col["H"], col["W"], col["kind"] = (
-                scan.n_seg, int(sub[-1]), info.total_blocks, info.height, info.width, KIND_SCAN)
+            table = row_tables[i]
+            scan_columns(col, info, scan.n_seg, int(sub[-1]), self._row_used)
+            if self._row_used + table.size > self._row_sub.size:
+                grown = np.zeros(max(2 * self._row_sub.size, self._row_used + table.size), dtype=np.uint32)
+                grown[:self._row_used] = self._row_sub[:self._row_used]
+                self._row_sub = grown
+            self._row_sub[self._row_used:self._row_used + table.size] = table
+            self._row_used += table.size
             self._most = max(self._most, int(info.total_blocks))
         for i, px in pixels.items():
             col = self._columns[first + i]
             col["H"], col["W"], col["kind"] = px.shape[0], px.shape[1], KIND_PIXELS
             self._pixels[first + i] = px
+        with torch.cuda.device(self.device):                             # on the stream add has just waited for; a decode on another
+            border[first:first + n] = new_borders                        # stream is ordered behind the synchronise below
+            torch.cuda.current_stream().synchronize()
+        self._border = border
         self._slabs += new_slabs
         self._open, self._cursor = open_slab, cursor
         self._n, self.nbytes = first + n, self.nbytes + need
         for key, v in split.items():
             self.resident[key] += v
         return ids
+
+    def _row_table(self, info, sub: np.ndarray, index: np.ndarray) -> np.ndarray:
+        """`jpeg_huffman.scan_row_sub` from the library's header."""
+        class Header:
+            ids = list(range(info.components))
+            h, v, mcus_x, mcus_y, restart = list(info.h), list(info.v), info.mcus_x, info.mcus_y, info.restart_interval
+        return scan_row_sub(Header, sub, index)
+
+    def _frame_borders(self, frames: List, stream):
+        """(len(frames), 3) uint8 on the device: fear_frame_border_u8 of uint8 (H, W, 3) device frames."""
+        import torch
+        from . import train_abi as abi
+        table = np.zeros(len(frames), dtype=np.dtype(abi.FearFrame))
+        for k, f in enumerate(frames):
+            table[k] = (f.data_ptr(), f.shape[0], f.shape[1])
+        dev = torch.from_numpy(table.view(np.uint8)).to(self.device)
+        out = torch.empty((len(frames), 3), dtype=torch.uint8, device=self.device)
+        abi.launch(self._lib, "fear_frame_border_u8", ctypes.c_void_p(dev.data_ptr()), len(frames), ctypes.c_void_p(out.data_ptr()), stream)
+        return out
+
+    def _group_borders(self, infos: List, records, coef, stream):
+        """The border colours of one group of `add`: the dense coefficients fear_jpeg_index_build has just left in `coef` (record k's at
+        its coef_offset) through the unchanged fear_jpeg_decode_u8 and fear_frame_border_u8."""
+        import torch
+        from . import train_abi as abi
+        m = len(infos)
+        images = np.zeros(m, dtype=self._dtypes[1])
+        blocks = np.array([int(i.total_blocks) for i in infos], dtype=np.int64)
+        pixels = np.array([int(i.width) * int(i.height) for i in infos], dtype=np.int64)
+        dense, out_at = _exclusive(64 * blocks), _exclusive(_up(3 * pixels, 16))
+        start = torch.empty(int(blocks.max()) + 1, dtype=torch.int32, device=self.device)
+        abi.launch(self._lib, "fear_jpeg_dense_block_start", ctypes.c_void_p(start.data_ptr()), int(blocks.max()), stream)
+        out = torch.empty(max(int(out_at[-1]), 16), dtype=torch.uint8, device=self.device)
+        ws_bytes = 16 + int(dense[-1])
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+        for k, info in enumerate(infos):
+            img = images[k]
+            img["width"], img["height"], img["components"], img["h"], img["v"] = info.width, info.height, info.components, info.h[0], info.v[0]
+            img["qt"] = np.ctypeslib.as_array(info.qt)
+            img["coef"] = coef.data_ptr() + 2 * int(records[k].coef_offset)
+        images["block_start"] = start.data_ptr()
+        images["out"] = np.uint64(out.data_ptr()) + out_at[:-1].astype(np.uint64)
+        images["plane_offset"] = dense[:-1].astype(np.uint64)
+        prefixes = np.concatenate([_exclusive(-(-blocks // 32)), _exclusive(-(-pixels // 256))]).astype(np.uint32)
+        at_images = _up(prefixes.nbytes, 16)
+        table = np.zeros(at_images + images.nbytes, dtype=np.uint8)
+        table[:prefixes.nbytes] = prefixes.view(np.uint8)
+        table[at_images:] = images.view(np.uint8)
+        dev = torch.from_numpy(table).to(self.device)
+        abi.launch(self._lib, "fear_jpeg_decode_u8", ctypes.c_void_p(images.ctypes.data), m, ctypes.c_void_p(dev.data_ptr()),
+                   ctypes.c_void_p(ws.data_ptr()), ws_bytes, stream)
+        frames = [out[int(out_at[k]):int(out_at[k]) + 3 * int(pixels[k])].view(int(infos[k].height), int(infos[k].width), 3) for k in range(m)]
+        return self._frame_borders(frames, stream)
 
     # ----------------------------------------------------------------------------------------------------------------------- decode
     def decode(self, ids, check: bool = False) -> List:
@@ -406,6 +593,94 @@ class JpegStore:
             for k in np.flatnonzero(rows["kind"] == KIND_PIXELS):        # the entries kept as pixels: a copy, never an alias
                 out[out_offset[k]:out_offset[k] + sizes[k]].copy_(self._pixels[int(group[k])].view(-1), non_blocking=True)
         for k, (at, size, h, w) in enumerate(zip(out_offset.tolist(), sizes.tolist(), rows["H"].tolist(), rows["W"].tolist())):
+            frames[lo + k] = out[at:at + size].view(h, w, 3)
+
+    # ------------------------------------------------------------------------------------------------------------------ decode_rows
+    def decode_rows(self, ids, rows=None, check: bool = False) -> List:
+        """`decode` for the rows a consumer reads.  `rows` is (len(ids), 2) integers, the pixel rows [y0, y1) per position, clipped to
+        [0, H]; the result is what `decode` returns — private uint8 (H, W, 3) tensors of the FULL frame shape — of which only the rows
+        [y0, y1) are defined: they are byte for byte `decode`'s.  ALL OTHER ROWS HOLD UNSPECIFIED BYTES (a row that is never read costs
+        an allocation, no traffic).  Per "scan" position the band of MCU rows that covers [y0, y1) — one more on each side where the
+        vertical chroma upsampling reads a neighbour row — is Huffman-decoded by `fear_jpeg_huffman_indexed_rows`, whose lanes are the
+        band's subsequences alone, and goes through `fear_jpeg_decode_u8` as an image of its own that ends where the band ends;
+        y0 >= y1 decodes nothing for the position; an entry kept as pixels is copied whole; `rows=None` is `decode`.  A `rows` of another
+        shape is a ValueError and a bad id an IndexError, both before any launch.  Like `decode` it never waits, the statuses (of the
+        lanes that ran; the files were judged in full by `add`) go to `check()`, and `workspace_limit` splits the call, by the bands'
+        dense coefficients."""
+        if rows is None:
+            return self.decode(ids, check=check)
+        ids = self._checked(ids)
+        rows = np.asarray(rows)
+        if rows.shape != (ids.size, 2) or not np.issubdtype(rows.dtype, np.integer):
+            raise ValueError(f"rows must be ({ids.size}, 2) integers, one [y0, y1) per id")
+        frames: List = [None] * ids.size
+        self._pending = self._pending[-self.PENDING_CALLS:]
+        for plan in plan_decode_rows(self._columns, self._row_sub, ids, rows, self.workspace_limit):
+            self._decode_rows_group(ids, plan, frames)
+        if check:
+            self.check()
+        return frames
+
+    def _decode_rows_group(self, ids: np.ndarray, plan: dict, frames: List) -> None:
+        import torch
+        from . import train_abi as abi
+        lo, hi, scan = plan["lo"], plan["hi"], plan["scan"]
+        group = ids[lo:hi]
+        sids, nd = group[scan], scan.size
+        with torch.cuda.device(self.device):
+            out = torch.empty(max(plan["out_bytes"], 16), dtype=torch.uint8, device=self.device)
+            out_offset = plan["out_offset"]
+            if nd:
+                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                if self._dense_blocks < self._most:                      # the store's largest image grew; a band has no more blocks
+                    self._dense_retired.append(self._dense_start)
+                    self._dense_start = torch.empty(self._most + 1, dtype=torch.int32, device=self.device)
+                    abi.launch(self._lib, "fear_jpeg_dense_block_start", ctypes.c_void_p(self._dense_start.data_ptr()), self._most, stream)
+                    self._dense_blocks, self._dense_event = self._most, torch.cuda.Event()
+                    self._dense_event.record()
+                else:
+                    torch.cuda.current_stream().wait_event(self._dense_event)
+                coef = torch.empty(max(plan["values"], 8), dtype=torch.int16, device=self.device)
+                ws = torch.empty(plan["workspace_bytes"], dtype=torch.uint8, device=self.device)
+                status = torch.empty(nd, dtype=torch.int32, device=self.device)
+                indexed, images = self._indexed[sids], self._image[sids]  # gathers: private copies
+                indexed["coef_offset"] = plan["coef_offset"]
+                indexed["sub0"], indexed["sub_count"] = plan["sub0"], plan["sub_count"]
+                indexed["mcu_row0"], indexed["mcu_rows"] = plan["mcu_row0"], plan["mcu_rows"]
+                images["coef"] = np.uint64(coef.data_ptr()) + np.uint64(2) * plan["coef_offset"]
+                images["block_start"] = self._dense_start.data_ptr()
+                images["height"] = plan["band_height"]                   # the band as an image of its own, written into its frame's rows
+                images["out"] = np.uint64(out.data_ptr()) + (out_offset[scan] + plan["band_out"]).astype(np.uint64)
+                images["plane_offset"] = plan["plane_offset"]
+                prefixes = np.concatenate([plan["block_prefix"], plan["pixel_prefix"]])
+                at_indexed = _up(plan["sub_prefix"].nbytes, 16)
+                at_table = at_indexed + indexed.nbytes
+                at_images = at_table + _up(prefixes.nbytes, 16)
+                pinned = torch.empty(at_images + images.nbytes, dtype=torch.uint8, pin_memory=True)
+                host = pinned.numpy()
+                host[:at_indexed].view(np.uint32)[:nd + 1] = plan["sub_prefix"]
+                host[at_indexed:at_table] = indexed.view(np.uint8)
+                host[at_table:at_images].view(np.uint32)[:2 * nd + 2] = prefixes
+                host[at_images:] = images.view(np.uint8)
+                dev = torch.empty(pinned.numel(), dtype=torch.uint8, device=self.device)
+                dev.copy_(pinned, non_blocking=True)
+                self._pinned = self._pinned[-1:] + [pinned]
+                self._records = (indexed, images)
+                self.last_upload_bytes = pinned.numel()
+                abi.launch(self._lib, "fear_jpeg_huffman_indexed_rows", ctypes.c_void_p(indexed.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr()),
+                           ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(status.data_ptr()), self.subsequence_bytes, stream)
+                abi.launch(self._lib, "fear_jpeg_decode_u8", ctypes.c_void_p(images.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr() + at_table),
+                           ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"], stream)
+                verdict = torch.empty(nd, dtype=torch.int32, pin_memory=True)
+                verdict.copy_(status, non_blocking=True)
+                event = torch.cuda.Event()
+                event.record()
+                self._pending.append((event, verdict, lo + scan, sids))
+            cols = self._columns[group]
+            sizes = 3 * cols["H"].astype(np.int64) * cols["W"]
+            for k in np.flatnonzero(cols["kind"] == KIND_PIXELS):        # the entries kept as pixels: a whole copy, never an alias
+                out[out_offset[k]:out_offset[k] + sizes[k]].copy_(self._pixels[int(group[k])].view(-1), non_blocking=True)
+        for k, (at, size, h, w) in enumerate(zip(out_offset.tolist(), sizes.tolist(), cols["H"].tolist(), cols["W"].tolist())):
             frames[lo + k] = out[at:at + size].view(h, w, 3)
 
     def check(self) -> None:

@@ -99,6 +99,7 @@ TRAIN_SYMBOLS = {
     "fear_jpeg_sub_start": ([_P, ctypes.c_uint32, ctypes.c_uint32, _i, _P, _sz, _P], _i),
     "fear_jpeg_index_build": ([_P, _i, _P, _P, _P, _P, _P, _i, _P], _i),
     "fear_jpeg_huffman_indexed": ([_P, _i, _P, _P, _P, _i, _P], _i),
+    "fear_jpeg_huffman_indexed_rows": ([_P, _i, _P, _P, _P, _i, _P], _i),
     # the colour stage's members that are no lookup table (FearColourOp below)
     "fear_colour_u8": ([_P, _i, _i, _i, _P, _P, _P, _P], _i),
     # step metrics (metrics.TrainMetrics)
@@ -220,9 +221,10 @@ class FearJpegIndex(ctypes.Structure):
 
 
 class FearJpegIndexed(ctypes.Structure):
-    """include/fear_train.h: one image of a fear_jpeg_huffman_indexed call (device pointers as integers)."""
+    """include/fear_train.h: one image of a fear_jpeg_huffman_indexed or fear_jpeg_huffman_indexed_rows call (device pointers as integers)."""
     _fields_ = [("scan", ctypes.c_uint64), ("index", ctypes.c_uint64), ("sub_start", ctypes.c_uint64), ("coef_offset", ctypes.c_uint64),
-                ("n_sub", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7)]
+                ("n_sub", ctypes.c_uint32), ("sub0", ctypes.c_uint32), ("sub_count", ctypes.c_uint32), ("mcu_row0", ctypes.c_uint32),
+                ("mcu_rows", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
 
 
 assert ctypes.sizeof(FearJpegSubseq) == 16 and ctypes.sizeof(FearJpegIndex) == 32 and ctypes.sizeof(FearJpegIndexed) == 64

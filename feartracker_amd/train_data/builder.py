@@ -174,6 +174,27 @@ class TrainPairBuilder:
         return dict(t_ctx=t_ctx, s_ctx=s_ctx, box512=box512, crop=crop, moved=moved, search_bbox=search_bbox, M=M, Minv=Minv,
                     lut=colour_luts(params), geom=geom)
 
+    def frame_rows(self, pairs, params: TrainPairParams, frame_shapes: Sequence[Tuple[int, ...]]) -> np.ndarray:
+        """(F, 2) int64: per frame the pixel rows [y0, y1) a `build` of these pairs reads — the union (as one range) over the pairs that
+        use the frame of the rows of their template context box and of their search context box, cut to the frame; (0, 0) for a frame no
+        pair uses or touches.  The boxes are `tables()`'s; a crop samples the frame where 0 <= cy + y < fh for y in [0, ch) (warp.crop_u8)
+        and nowhere else, whatever the pair's presence.  What `JpegStore.decode_rows` takes."""
+        tab = self.tables(pairs, params)
+        geom = tab["geom"]
+        F = len(frame_shapes)
+        heights = np.array([int(s[0]) for s in frame_shapes], dtype=np.int64).reshape(F)
+        lo, hi = np.full(F, np.iinfo(np.int64).max), np.full(F, np.iinfo(np.int64).min)
+        for frame, ctx in ((geom["t_frame"], tab["t_ctx"]), (geom["s_frame"], tab["s_ctx"])):
+            frame, cy, ch = frame.astype(np.int64), ctx[:, 1].astype(np.int64), ctx[:, 3].astype(np.int64)
+            ok = (frame >= 0) & (frame < F)
+            # a box without height still clamps its taps to the rows cy - 1 and cy
+            np.minimum.at(lo, frame[ok], (cy + np.minimum(ch - 1, 0))[ok])
+            np.maximum.at(hi, frame[ok], (cy + np.maximum(ch, 1))[ok])
+        lo, hi = np.clip(lo, 0, heights), np.clip(hi, 0, heights)
+        rows = np.stack([lo, hi], axis=1)
+        rows[lo >= hi] = 0
+        return rows
+
     def _params(self, pairs, frames, params):
         shapes = tuple((int(f.shape[0]), int(f.shape[1])) for f in frames)
         if params is None:
@@ -183,14 +204,18 @@ class TrainPairBuilder:
         return params
 
     # ------------------------------------------------------------------ host restatement
-    def build_host(self, frames: Sequence, pairs, params: Optional[TrainPairParams] = None) -> TrainBatch:
-        """numpy restatement of `build` (same arithmetic, term for term): the reference `build` is tested against."""
+    def build_host(self, frames: Sequence, pairs, params: Optional[TrainPairParams] = None, borders=None) -> TrainBatch:
+        """numpy restatement of `build` (same arithmetic, term for term): the reference `build` is tested against.  `borders`, (F, 3)
+        uint8, are used as the frames' border colours in place of their means (`build`'s `borders`)."""
         host = [f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f) for f in frames]
         params = self._params(pairs, host, params)
         tab = self.tables(pairs, params)
         geom, lut = tab["geom"], tab["lut"]
-        borders = [border_color_u8(np.mean(f[:, :, :3], axis=(0, 1))) if f.shape[0] > 0 and f.shape[1] > 0 else np.zeros(3, np.uint8)
-                   for f in host]
+        if borders is None:
+            borders = [border_color_u8(np.mean(f[:, :, :3], axis=(0, 1))) if f.shape[0] > 0 and f.shape[1] > 0 else np.zeros(3, np.uint8)
+                       for f in host]
+        else:
+            borders = self._given_borders(borders, len(host))
         B = len(geom)
         tmpl = np.empty((B, 3, TEMPLATE_SIZE, TEMPLATE_SIZE), dtype=np.float32)
         srch = np.empty((B, 3, SEARCH_SIZE, SEARCH_SIZE), dtype=np.float32)
@@ -227,11 +252,14 @@ class TrainPairBuilder:
 
     # ------------------------------------------------------------------ device
     @torch.no_grad()
-    def build(self, frames: Sequence, pairs, params: Optional[TrainPairParams] = None) -> TrainBatch:
+    def build(self, frames: Sequence, pairs, params: Optional[TrainPairParams] = None, borders=None) -> TrainBatch:
         """The batch on the GPU: template (B,3,128,128), search (B,3,256,256), gt_reg (B,4,16,16), gt_cls (B,1,16,16),
         gt_weight (B,16,16) fp32 and search_bbox (B,4) int32, on the current stream, in the layouts `FEARNetTrainHIP.step` takes.
         Frames are uint8 (H, W, 3) numpy arrays or device tensors.  Host frames and the per-pair tables go up non-blocking from
-        pinned memory; with device frames the call never waits for the GPU."""
+        pinned memory; with device frames the call never waits for the GPU.
+        `borders`, an (F, 3) uint8 device tensor or array, gives the frames' border colours (`JpegStore.borders`, computed once per
+        file): the call then skips the `fear_frame_border_u8` launch, the only reader of every pixel of a frame, so that frames of
+        which only `frame_rows` is defined (`JpegStore.decode_rows`) give the same batch.  None keeps the launch."""
         lib, dev = load_train_library(), self.device
         params = self._params(pairs, frames, params)
         tab = self.tables(pairs, params)
@@ -271,13 +299,25 @@ class TrainPairBuilder:
                 stage.add("colour_ops", colour[0])
                 stage.add("colour_aux", colour[1])
             stage.upload(dev)
-            border = torch.empty((max(F, 1), 3), dtype=torch.uint8, device=dev)
+            if borders is None:
+                border = torch.empty((max(F, 1), 3), dtype=torch.uint8, device=dev)
+            elif isinstance(borders, torch.Tensor):
+                if borders.dtype != torch.uint8 or tuple(borders.shape) != (F, 3):
+                    raise ValueError(f"borders must be uint8 ({F}, 3)")
+                border = borders.to(dev).contiguous()
+                if F == 0:
+                    border = torch.empty((1, 3), dtype=torch.uint8, device=dev)
+            else:
+                pinned_border = torch.empty((max(F, 1), 3), dtype=torch.uint8, pin_memory=True)
+                pinned_border.numpy()[:F] = self._given_borders(borders, F)
+                border = pinned_border.to(dev, non_blocking=True)
             tmpl = torch.empty((B, 3, TEMPLATE_SIZE, TEMPLATE_SIZE), dtype=torch.float32, device=dev)
             srch = torch.empty((B, 3, SEARCH_SIZE, SEARCH_SIZE), dtype=torch.float32, device=dev)
             reg = torch.empty((B, 4, SCORE_SIZE, SCORE_SIZE), dtype=torch.float32, device=dev)
             cls = torch.empty((B, 1, SCORE_SIZE, SCORE_SIZE), dtype=torch.float32, device=dev)
             wgt = torch.empty((B, SCORE_SIZE, SCORE_SIZE), dtype=torch.float32, device=dev)
-            launch(lib, "fear_frame_border_u8", stage.ptr("frames"), F, ptr(border), st)
+            if borders is None:
+                launch(lib, "fear_frame_border_u8", stage.ptr("frames"), F, ptr(border), st)
             if not staged_u8:
                 pairs_fn, t_out, s_out = "fear_train_pairs", tmpl, srch
             else:                              # the crops leave the table stage as uint8 HWC for the chain below
@@ -312,8 +352,19 @@ class TrainPairBuilder:
                 finish(s_out, srch, SEARCH_SIZE, 1)
             for f in dframes:                          # host frames were allocated here; device frames may live on another stream
                 f.record_stream(stream)
+            if borders is not None:
+                border.record_stream(stream)
             box = stage.view("search_bbox", torch.int32, (B, 4))
         return TrainBatch(tmpl, srch, reg, cls, wgt, box)
+
+    @staticmethod
+    def _given_borders(borders, F: int) -> np.ndarray:
+        if isinstance(borders, torch.Tensor):
+            borders = borders.detach().cpu().numpy()
+        arr = np.asarray(borders)
+        if arr.dtype != np.uint8 or arr.shape != (F, 3):
+            raise ValueError(f"borders must be uint8 ({F}, 3)")
+        return arr
 
     def _quantiles_on_device(self) -> torch.Tensor:
         """GaussNoise's quantile table on the device: uploaded once per builder, non-blocking from pinned memory.  Later builds on

@@ -715,7 +715,20 @@ int fear_jpeg_dense_block_start(uint32_t* block_start, uint32_t total_blocks, vo
  * sub_start of a record.  The scan's geometry was checked when its index was built and lives in device memory, where the call cannot
  * read it: a wrong index, sub_start or resident record is the caller's error, as a wrong block_start is to fear_jpeg_decode_u8.  Even
  * so every read stays inside the segment and the image's n_bytes, every write inside the image's 64 total_blocks values from its
- * coef_offset, an entry's slot and z are clamped to the tables, and every loop is bounded by the subsequence's length.                */
+ * coef_offset, an entry's slot and z are clamped to the tables, and every loop is bounded by the subsequence's length.
+ *
+ * fear_jpeg_huffman_indexed_rows is fear_jpeg_huffman_indexed for a band of MCU rows per image, [mcu_row0, mcu_row0 + mcu_rows) clipped
+ * to the image (JpegStore.decode_rows; jpeg_huffman.jpeg_entropy_indexed_host with a band restates it).  Only the record's subsequences
+ * sub0 .. sub0 + sub_count) get a lane: ceil(sub_count / 256) workgroups per image, which is what the prefix sums of `table_dev` count.
+ * The caller takes them from the file's row table (jpeg_huffman.scan_row_sub: row_sub[r] is the subsequence in which the first block of
+ * MCU row r begins, row_sub[mcus_y] = n_sub): row_sub[mcu_row0] .. min(row_sub[mcu_row0 + mcu_rows], n_sub - 1), so that every block of
+ * the band lies wholly in lanes that run.  A lane decodes exactly as fear_jpeg_huffman_indexed's and judges all that lane judges; a block
+ * whose MCU row lies outside the band (an explicit range test) is decoded and not stored.  The band's blocks are stored BAND-DENSE: the
+ * component-major, row-major layout of an image that consists of those MCU rows alone, 64 (mcu_rows mcus_x blocks-per-MCU) values from
+ * coef_offset, every position written by exactly one lane, nothing outside them.  Lanes that do not run judge nothing: status_dev[i] is
+ * the verdict of the lanes that ran (an image with n_sub == 0 fails as above), and a band without rows or lanes leaves FEAR_TRAIN_OK.
+ * The checks are fear_jpeg_huffman_indexed's, and FEAR_TRAIN_ERR_SHAPE for sub_count > 0 with sub0 + sub_count > n_sub, or
+ * mcu_row0 + mcu_rows > FEAR_JPEG_MAX_SIDE / 8.  Two launches, no atomics, one barrier, plain vector stores.                          */
 typedef struct FearJpegSubseq {
     uint32_t p;                  /* the true entry bit position in the segment, up to 30 bits behind the subsequence's first: < 2^27 + 31 */
     uint32_t begun;              /* blocks begun in the segment in front of the subsequence                              */
@@ -739,7 +752,9 @@ typedef struct FearJpegIndexed {
     const uint32_t* sub_start;       /* device                                                                           */
     uint64_t coef_offset;            /* values from `coef` to this image's 64 total_blocks dense coefficients            */
     uint32_t n_sub;
-    uint32_t reserved[7];
+    uint32_t sub0, sub_count;        /* fear_jpeg_huffman_indexed_rows alone: the subsequences that get a lane, sub0 .. sub0 + sub_count) */
+    uint32_t mcu_row0, mcu_rows;     /* fear_jpeg_huffman_indexed_rows alone: the band of MCU rows whose blocks are stored             */
+    uint32_t reserved[3];
 } FearJpegIndexed;
 #ifdef __cplusplus
 static_assert(sizeof(FearJpegSubseq) == 16, "FearJpegSubseq is 16 bytes");
@@ -757,6 +772,8 @@ int fear_jpeg_index_build(const FearJpegScan* scans, int n, const void* table_de
                           int16_t* coef, int32_t* status_dev, int subsequence_bytes, void* stream);
 int fear_jpeg_huffman_indexed(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
                               int subsequence_bytes, void* stream);
+int fear_jpeg_huffman_indexed_rows(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
+                                   int subsequence_bytes, void* stream);
 
 /* ---- the colour stage's members that are no lookup table: Equalize, HueSaturationValue, ColorJitter and Emboss of the reference's
  * p = 0.5 OneOf (model_training/dataset/aug.py:35-48), on uint8 HWC crops between fear_train_pairs_u8 (tone, then the lookup-table

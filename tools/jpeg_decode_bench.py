@@ -34,7 +34,23 @@ of 5 with minimum and maximum:
   add_files_per_s         (e) JpegStore.add of the 256 files into a fresh store, 16 threads, verdicts awaited
   resident_bytes_per_file (f) by subsequence_bytes: bytes (with seg_start and sub_start), index, records
   training_step_fps       what the 128-pair step consumes, to read store_fps against
-Before anything is timed the store's frames are compared with the decoder's at every subsequence length (`frames_equal_decoder`)."""
+Before anything is timed the store's frames are compared with the decoder's at every subsequence length (`frames_equal_decoder`).
+
+    python tools/jpeg_decode_bench.py --dir DIR --store --rows      # needs the GPU: bands of rows, writes profiles/jpeg_rows_bench.json
+
+--store --rows measures JpegStore.decode_rows against JpegStore.decode on the same 256 files in ONE run, at band heights 1.0, 0.5 and 0.25
+of H with seeded random positions (one window per file), every shape warmed first, medians of 5 with minimum and maximum:
+  decode_ms_per_call       store.decode of the 256 ids in a seeded permutation with check(), a host clock around work that ends in a
+                           synchronise
+  decode_rows_ms_per_call  the same for store.decode_rows, by band height; `rows_decoded` is the mean number of pixel rows per frame the
+                           pixel stage writes (the window's MCU rows and their halo)
+  stage_ms                 fear_jpeg_huffman_indexed alone and fear_jpeg_huffman_indexed_rows alone by band height, between HIP events;
+                           `lanes` the subsequences that get a lane
+  conditions               full_band_within_spread: at 1.0 the slowest decode_rows run is no slower than the slowest decode run by more
+                           than decode's own minimum-to-maximum spread; quarter_band_faster: at 0.25 the slowest decode_rows run is below
+                           the fastest decode run
+  borders_ms, host_ms_per_call      store.borders(ids) between HIP events; decode_rows at 0.25 until it returns (it does not wait)
+Before anything is timed the rows asked for are compared with `decode`'s at every band height (`rows_equal_decode`)."""
 import argparse
 import glob
 import io
@@ -260,6 +276,105 @@ def store_bench(torch, blobs, out):
     print(json.dumps(res))
 
 
+def rows_bench(torch, blobs, out):
+    """JpegStore.decode_rows against JpegStore.decode in one run."""
+    from feartracker_amd import JpegStore
+    from feartracker_amd import train_abi as abi
+    n, repeats, fractions = len(blobs), 5, (1.0, 0.5, 0.25)
+    res = {"files": n, "width": W, "height": H, "quality": QUALITY, "file_bytes_per_frame": sum(map(len, blobs)) / n,
+           "cpus_available": len(os.sched_getaffinity(0)), "repeats": repeats}
+    # (a workspace that holds the 256 frames' dense coefficients, 1.06 GB, in one group: the stage replays below replay the whole call)
+    store = JpegStore(device=0, threads=16, workspace_limit=2 << 30)
+    ids = store.add(blobs)[np.random.default_rng(17).permutation(n)]
+    res["subsequence_bytes"], res["workspace_limit"] = store.subsequence_bytes, store.workspace_limit
+    res["resident_bytes_per_file"] = dict({k: round(v / n, 1) for k, v in store.resident.items() if k != "pixels"}, total=round(store.nbytes / n, 1))
+    rng = np.random.default_rng(29)
+    heights = store.shape(ids)[:, 0].astype(np.int64)
+    windows = {}
+    for f in fractions:
+        high = np.maximum((heights * f).astype(np.int64), 1)
+        y0 = rng.integers(0, heights - high + 1)
+        windows[f] = np.stack([y0, y0 + high], axis=1)
+
+    def whole():
+        frames = store.decode(ids, check=True)
+        torch.cuda.synchronize()
+        return frames
+
+    def bands(f):
+        frames = store.decode_rows(ids, windows[f], check=True)
+        torch.cuda.synchronize()
+        return frames
+
+    def captured_call(fn, name):
+        captured, real = {}, abi.launch
+
+        def spy(lib, called, *a):
+            captured[called] = a
+            return real(lib, called, *a)
+        abi.launch = spy
+        try:
+            keep = fn()
+        finally:
+            abi.launch = real
+        torch.cuda.synchronize()
+        return keep, captured[name], store._records
+
+    full = whole()                                                       # every shape warm, and the same rows before anything is timed
+    for f in fractions:
+        for x, y, (a, b) in zip(bands(f), full, windows[f].tolist()):
+            assert torch.equal(x[a:b], y[a:b]), f"decode_rows differs from decode at band height {f}"
+    del full
+    res["rows_equal_decode"] = True
+    a = run_seconds(whole, repeats)
+    res["decode_ms_per_call"] = spread(a, 1e3)
+    res["decode_rows_ms_per_call"], res["stage_ms"], timed = {}, {}, {}
+    for f in fractions:
+        timed[f] = run_seconds(lambda: bands(f), repeats)
+        plan = store._records[1]                                         # the call's FearJpegImage records: the bands' heights
+        assert plan.size == n
+        res["decode_rows_ms_per_call"][str(f)] = dict(spread(timed[f], 1e3), rows_asked=int(windows[f][0, 1] - windows[f][0, 0]),
+                                                      rows_decoded=round(float(plan["height"].mean()), 1))
+    lib = store._lib
+    keep, indexed, records = captured_call(whole, "fear_jpeg_huffman_indexed")
+    one = event_ms(torch, lambda: lib.fear_jpeg_huffman_indexed(*indexed), repeats)
+    res["stage_ms"]["fear_jpeg_huffman_indexed"] = dict(spread(one), lanes=int(records[0]["n_sub"].sum()))
+    del keep
+    for f in fractions:
+        keep, rows, records = captured_call(lambda: bands(f), "fear_jpeg_huffman_indexed_rows")
+        two = event_ms(torch, lambda: lib.fear_jpeg_huffman_indexed_rows(*rows), repeats)
+        res["stage_ms"][f"fear_jpeg_huffman_indexed_rows {f}"] = dict(spread(two), lanes=int(records[0]["sub_count"].sum()))
+        del keep
+    res["conditions"] = {
+        "full_band_within_spread": bool(max(timed[1.0]) <= max(a) + (max(a) - min(a))),
+        "quarter_band_faster": bool(max(timed[0.25]) < min(a)),
+    }
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    gathers = []
+    for _ in range(repeats + 1):
+        e0.record()
+        store.borders(ids)
+        e1.record()
+        torch.cuda.synchronize()
+        gathers.append(e0.elapsed_time(e1))
+    res["borders_ms"] = spread(gathers[1:])
+
+    def host_only():
+        t0 = time.perf_counter()
+        frames = store.decode_rows(ids, windows[0.25])
+        t = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        store.check()
+        return t, frames
+    host_only()
+    res["host_ms_per_call"] = spread([host_only()[0] for _ in range(repeats)], 1e3)
+    store.close()
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dir", required=True)
@@ -268,10 +383,12 @@ def main():
     ap.add_argument("--entropy", choices=("host", "device", "both"), default="host")
     ap.add_argument("--rounds", type=int, default=0, help="no GPU: the model's synchronisation rounds on the first N files, merged into --out")
     ap.add_argument("--store", action="store_true", help="the resident store against the device decoder, to profiles/jpeg_store_bench.json")
+    ap.add_argument("--rows", action="store_true", help="with --store: decode_rows against decode, to profiles/jpeg_rows_bench.json")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "jpeg_store_bench.json" if args.store else "jpeg_decode_bench.json")
+        name = "jpeg_decode_bench.json" if not args.store else ("jpeg_rows_bench.json" if args.rows else "jpeg_store_bench.json")
+        args.out = os.path.join(ROOT, "profiles", name)
     if args.make:
         return make(args.dir)
     blobs = [open(p, "rb").read() for p in sorted(glob.glob(os.path.join(args.dir, "*.jpg")))]
@@ -284,6 +401,8 @@ def main():
         print(json.dumps(res["device_entropy"]["rounds_per_sequence"]))
         return
     import torch
+    if args.store and args.rows:
+        return rows_bench(torch, blobs, args.out)
     if args.store:
         return store_bench(torch, blobs, args.out)
     from feartracker_amd import JpegDecoder

@@ -31,12 +31,21 @@ With --noise all it reports ImageCompression, the member behind `noise_members` 
   build_all_ms       `build` with noise_members="all" at the reference's probabilities, fresh draws per call
   jpeg_u8_ms         fear_jpeg_u8 alone on the batch's 128 templates and 128 searches (two calls), every crop at quality 50, HIP events
   step_ms            FEARNetTrainHIP.step on fixed inputs, for the shares
+With --store DIR it reports the resident JPEG store in front of the builder (DIR holds the files of tools/jpeg_decode_bench.py --make,
+256 synthetic 1280 x 720 files; 128 pairs, two frames of their own per pair), in ONE run, medians of `--repeats` + 2 runs with minimum and
+maximum, a host clock around work that ends in a synchronise:
+  decode_build_ms        store.decode(ids) + builder.build(frames, pairs, params)
+  rows_build_ms          store.decode_rows(ids, builder.frame_rows(...)) + builder.build(frames, pairs, params, borders=store.borders(ids))
+  decode_ms, decode_rows_ms, build_ms, build_borders_ms     the parts alone
+  boxes                  the seeded boxes: sides uniform in [lo, hi) pixels; rows_per_frame is the mean of what frame_rows asks for
+The two builds are compared with torch.equal before anything is timed (`batches_equal`).  It sets no gate: the gain depends on the boxes.
 --build-only is the child mode of the above: it times `build` of the package under --root and prints {"build_ms": ...}.
 
 Usage: python tools/train_pairs_bench.py [--pairs 128] [--frames 256] [--steps 20] [--iters 50] [--out FILE]
        python tools/train_pairs_bench.py --photometric [--parent-root DIR] [--repeats 3] [--out FILE]
        python tools/train_pairs_bench.py --colour all [--parent-root DIR] [--repeats 3] [--out profiles/train_pairs_colour_bench.json]
        python tools/train_pairs_bench.py --noise all [--parent-root DIR] [--repeats 3] [--out profiles/train_pairs_jpeg_bench.json]
+       python tools/train_pairs_bench.py --store DIR [--repeats 3] [--out profiles/train_pairs_store_bench.json]
 """
 from __future__ import annotations
 
@@ -303,6 +312,71 @@ def noise(args):
     }
 
 
+def store_mode(args):
+    """decode + build against decode_rows + build(borders=) out of a resident store."""
+    import glob
+    sys.path.insert(0, ROOT)
+    from feartracker_amd import JpegStore
+    from feartracker_amd.train_data import TrainPairBuilder
+    blobs = [open(p, "rb").read() for p in sorted(glob.glob(os.path.join(args.store, "*.jpg")))]
+    B = args.pairs
+    assert len(blobs) >= 2 * B, "the store mode takes two frames of their own per pair: run tools/jpeg_decode_bench.py --make first"
+    store = JpegStore(device=0, threads=16)
+    ids = store.add(blobs[:2 * B])
+    shapes = store.shape(ids)
+    Hf, Wf = int(shapes[0, 0]), int(shapes[0, 1])
+    lo, hi = 40, 300
+    rng = np.random.default_rng(0)
+    pairs = np.zeros((B, 11))
+    pairs[:, 0], pairs[:, 5], pairs[:, 10] = 2 * np.arange(B), 2 * np.arange(B) + 1, 1
+    for col in (1, 6):
+        w, h = rng.integers(lo, hi, B), rng.integers(lo, hi, B)
+        pairs[:, col], pairs[:, col + 1], pairs[:, col + 2], pairs[:, col + 3] = rng.integers(0, Wf - w), rng.integers(0, Hf - h), w, h
+    builder = TrainPairBuilder(device=0, seed=0)
+    params = builder.draw(pairs, shapes, np.random.default_rng(1))
+    rows = builder.frame_rows(pairs, params, shapes)
+
+    def whole():
+        return builder.build(store.decode(ids), pairs, params)
+
+    def bands():
+        return builder.build(store.decode_rows(ids, builder.frame_rows(pairs, params, shapes)), pairs, params, borders=store.borders(ids))
+
+    frames = store.decode(ids)
+    parts = {"decode_ms": lambda: store.decode(ids), "decode_rows_ms": lambda: store.decode_rows(ids, rows),
+             "build_ms": lambda: builder.build(frames, pairs, params),
+             "build_borders_ms": lambda: builder.build(frames, pairs, params, borders=store.borders(ids))}
+    x, y = whole(), bands()
+    store.check()
+    torch.cuda.synchronize()
+    equal = all(torch.equal(a, b) for a, b in zip(x, y))
+    assert equal, "build on band frames differs from build on whole frames"
+
+    def runs(fn):
+        out = []
+        for k in range(args.repeats + 3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            keep = fn()
+            torch.cuda.synchronize()
+            out.append(1e3 * (time.perf_counter() - t0))
+            del keep
+        out = out[1:]                                   # the first run warms
+        return {"median": round(float(np.median(out)), 4), "min": round(min(out), 4), "max": round(max(out), 4)}
+
+    report = {"pairs": B, "frames": 2 * B, "frame_hw": [Hf, Wf], "repeats": args.repeats + 2, "batches_equal": equal,
+              "boxes": {"side_lo": lo, "side_hi": hi, "distribution": "uniform integers, template and search boxes alike, seed 0",
+                        "context": "the builder's defaults, drawn with seed 1",
+                        "rows_per_frame": round(float((rows[:, 1] - rows[:, 0]).mean()), 1)},
+              "decode_build_ms": runs(whole), "rows_build_ms": runs(bands)}
+    for name, fn in parts.items():
+        report[name] = runs(fn)
+    store.check()
+    report["device"] = torch.cuda.get_device_name(0)
+    store.close()
+    return report
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=128)
@@ -313,6 +387,7 @@ def main():
     ap.add_argument("--photometric", action="store_true")
     ap.add_argument("--colour", default=None, help='"all": report the members behind colour_members')
     ap.add_argument("--noise", default=None, help='"all": report ImageCompression, the member behind noise_members')
+    ap.add_argument("--store", default=None, help="DIR of the synthetic 720p files: the resident store in front of the builder")
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--build-only", action="store_true")
@@ -321,6 +396,9 @@ def main():
     args = ap.parse_args()
     if args.build_only:
         return build_only(args)
+    if args.store:
+        args.out = args.out or os.path.join(ROOT, "profiles", "train_pairs_store_bench.json")
+        return emit(store_mode(args), args)
     if args.photometric:
         return emit(photometric(args), args)
     if args.colour:
