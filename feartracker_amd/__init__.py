@@ -14,6 +14,7 @@ from .hip_backend import FEARNetHIP, FearError, load_library, DEFAULT_WEIGHTS, L
 from .jpeg_frames import JpegDecoder, MalformedJPEG, UnsupportedJPEG, jpeg_decode_host, jpeg_info, jpeg_pixels_host
 from .jpeg_huffman import (jpeg_entropy_indexed_host, jpeg_entropy_parallel_host, jpeg_scan_index_host, jpeg_scan_prepare_host,
                            scan_row_sub)
+from .jpeg_progressive import jpeg_to_baseline_host
 from .jpeg_store import JpegStore, StoreFull, plan_decode, plan_decode_rows
 
 __all__ = [
@@ -23,4 +24,5 @@ __all__ = [
     "FEARNetHIP", "FearError", "load_library", "DEFAULT_WEIGHTS", "LIB_PATH",
     "JpegDecoder", "MalformedJPEG", "UnsupportedJPEG", "jpeg_decode_host", "jpeg_info", "jpeg_entropy_parallel_host", "jpeg_scan_prepare_host",
     "jpeg_scan_index_host", "jpeg_entropy_indexed_host", "JpegStore", "StoreFull", "plan_decode", "plan_decode_rows", "scan_row_sub", "jpeg_pixels_host",
+    "jpeg_to_baseline_host",
 ]

@@ -2224,6 +2224,7 @@ int fear_adam_step(float* param, const float* grad, float* exp_avg, float* exp_a
 #include "fear_train_data.h"
 #include "fear_train_jpeg.h"
 #include "fear_jpeg_entropy.h"
+#include "fear_jpeg_progressive.h"
 #include "fear_jpeg_decode.h"
 #include "fear_jpeg_huffman.h"
 #include "fear_jpeg_store.h"

@@ -186,9 +186,26 @@ def _parse(data: bytes) -> _Header:
     return hd
 
 
-def jpeg_info(data: bytes) -> Dict[str, object]:
-    """What the frame and scan headers say: size, components, sampling, block and MCU counts, restart interval, quantiser tables."""
-    hd = _parse(bytes(data))
+def _either(data: bytes, progressive: bool, baseline, of_progressive):
+    """`baseline(data)`; with `progressive`, a file the baseline rules decline goes to `of_progressive` (jpeg_progressive.py), and one whose
+    frame is not SOF2 keeps the baseline verdict."""
+    try:
+        return baseline(data)
+    except UnsupportedJPEG as first:
+        if not progressive:
+            raise
+        from .jpeg_progressive import NotProgressive
+        try:
+            return of_progressive(data)
+        except NotProgressive:
+            raise first from None
+
+
+def jpeg_info(data: bytes, progressive: bool = False) -> Dict[str, object]:
+    """What the frame and scan headers say: size, components, sampling, block and MCU counts, restart interval, quantiser tables.
+    `progressive=True` reads a progressive file's as well: those of its baseline twin, without a restart interval."""
+    from . import jpeg_progressive
+    hd = _either(bytes(data), progressive, _parse, jpeg_progressive.progressive_info)
     return dict(width=hd.width, height=hd.height, components=len(hd.ids), h=list(hd.h), v=list(hd.v), mcus_x=hd.mcus_x, mcus_y=hd.mcus_y,
                 blocks_w=list(hd.blocks_w), blocks_h=list(hd.blocks_h), restart_interval=hd.restart,
                 qt=np.stack([hd.q[t] for t in hd.tq]).astype(np.uint16))
@@ -247,8 +264,12 @@ def _wrap16(v: int) -> int:
     return ((v + 32768) & 0xFFFF) - 32768
 
 
-def jpeg_coefficients_host(data: bytes) -> Tuple[_Header, List[np.ndarray]]:
-    """Headers and, per component, the quantised coefficients (blocks_h, blocks_w, 64) int16 in zigzag order (T.81 F.2)."""
+def jpeg_coefficients_host(data: bytes, progressive: bool = False) -> Tuple[_Header, List[np.ndarray]]:
+    """Headers and, per component, the quantised coefficients (blocks_h, blocks_w, 64) int16 in zigzag order (T.81 F.2).
+    `progressive=True` decodes a progressive file's scans as well (T.81 G.1, jpeg_progressive.py)."""
+    if progressive:
+        from . import jpeg_progressive
+        return _either(bytes(data), True, jpeg_coefficients_host, jpeg_progressive.progressive_coefficients_host)
     data = bytes(data)
     hd = _parse(data)
     nf = len(hd.ids)
@@ -293,9 +314,10 @@ def _upsample_h2v1(c: np.ndarray) -> np.ndarray:
     return np.stack([(3 * c + left + 1) >> 2, (3 * c + right + 2) >> 2], axis=2).reshape(c.shape[0], 2 * c.shape[1])
 
 
-def jpeg_decode_host(data: bytes) -> np.ndarray:
-    """A baseline JPEG file -> uint8 (H, W, 3) RGB, as libjpeg decodes it with its defaults.  Slow; the statement the device is held to."""
-    return jpeg_pixels_host(*jpeg_coefficients_host(data))
+def jpeg_decode_host(data: bytes, progressive: bool = False) -> np.ndarray:
+    """A baseline JPEG file -> uint8 (H, W, 3) RGB, as libjpeg decodes it with its defaults.  Slow; the statement the device is held to.
+    `progressive=True` takes a complete progressive file as well."""
+    return jpeg_pixels_host(*jpeg_coefficients_host(data, progressive))
 
 
 def jpeg_pixels_host(hd: _Header, coef: List[np.ndarray], height: Optional[int] = None) -> np.ndarray:
@@ -334,10 +356,10 @@ def jpeg_pixels_host(hd: _Header, coef: List[np.ndarray], height: Optional[int] 
 Item = Union[bytes, bytearray, memoryview, str, os.PathLike]
 
 
-def _raise_as_python(data: bytes, rc: int):
+def _raise_as_python(data: bytes, rc: int, progressive: bool = False):
     """The library's verdict as the exception of the Python decoder, whose message says which check it was."""
     try:
-        jpeg_coefficients_host(data)
+        jpeg_coefficients_host(data, progressive)
     except (MalformedJPEG, UnsupportedJPEG) as exc:
         if isinstance(exc, UnsupportedJPEG) == (rc == ERR_UNSUPPORTED):
             raise
@@ -361,12 +383,17 @@ class JpegDecoder:
     An error the device finds — a code in no table, truncated entropy data: jpeg_huffman.jpeg_entropy_parallel_host lists them — cannot
     raise inside a call that does not wait: `decode` copies the statuses to pinned memory and records an event, and `check()` waits for
     the calls not yet checked and raises `MalformedJPEG` naming the call's item index; `decode(..., check=True)` does both.  The pixels of
-    a failed image are unspecified.  The statuses of the last PENDING_CALLS unchecked calls are kept."""
+    a failed image are unspecified.  The statuses of the last PENDING_CALLS unchecked calls are kept.
+
+    `progressive=True` takes progressive files (SOF2) as well: the pool decodes all of a file's scans (`fear_jpeg_progressive_decode`,
+    T.81 G.1; jpeg_progressive.py states it) and its packed coefficients ride in the call as a host-path item's do, in both entropy
+    modes (`last_paths` says "host").  A file that decoder declines — an incomplete or inconsistent progression — reaches the
+    `fallback` or raises; baseline files in the same call go the way they went."""
     MAX_THREADS = 16
     PENDING_CALLS = 64
 
     def __init__(self, device: int = 0, threads: Optional[int] = None, entropy: str = "host", workspace_limit: int = 1 << 30,
-                 subsequence_bytes: int = 128):
+                 subsequence_bytes: int = 128, progressive: bool = False):
         import torch
         from .train_abi import load_train_library
         if threads is None:
@@ -381,6 +408,7 @@ class JpegDecoder:
         if subsequence_bytes % 4 or not 4 <= subsequence_bytes <= 1024:
             raise ValueError("subsequence_bytes is a multiple of 4 in 4..1024")
         self.entropy, self.workspace_limit, self.subsequence_bytes = entropy, int(workspace_limit), int(subsequence_bytes)
+        self.progressive = bool(progressive)
         self._pending: List = []                                      # device mode: (event, pinned statuses, [(item index, file)]) per group
         self.last_paths: List[str] = []                               # device mode: "device" or "host" per JPEG file of the last call
 
@@ -393,6 +421,8 @@ class JpegDecoder:
         from .train_abi import FearJpegInfo
         lib, info = self._lib, FearJpegInfo()
         rc = lib.fear_jpeg_parse(data, len(data), ctypes.byref(info))
+        if rc == ERR_UNSUPPORTED and self.progressive:
+            return self.progressive_decode(data)
         if rc != 0:
             return rc
         coef = np.empty(lib.fear_jpeg_packed_bound(ctypes.byref(info)), dtype=np.int16)
@@ -402,6 +432,36 @@ class JpegDecoder:
         if rc != 0:
             return rc
         return info, coef[:used.value], start
+
+    def progressive_decode(self, data: bytes):
+        """One file through fear_jpeg_progressive_parse and fear_jpeg_progressive_decode: what `entropy_decode` returns for a baseline
+        file, or the library's status — FEAR_TRAIN_ERR_UNSUPPORTED also for a file whose frame is not SOF2.  Host only."""
+        from .train_abi import FearJpegInfo
+        lib, info = self._lib, FearJpegInfo()
+        rc = lib.fear_jpeg_progressive_parse(data, len(data), ctypes.byref(info))
+        if rc != 0:
+            return rc
+        coef = np.empty(lib.fear_jpeg_packed_bound(ctypes.byref(info)), dtype=np.int16)
+        start = np.empty(info.total_blocks + 1, dtype=np.uint32)
+        used = ctypes.c_size_t(0)
+        rc = lib.fear_jpeg_progressive_decode(data, len(data), ctypes.byref(info), coef.ctypes.data, coef.size, start.ctypes.data, ctypes.byref(used))
+        if rc != 0:
+            return rc
+        return info, coef[:used.value], start
+
+    def to_baseline(self, data: bytes):
+        """One progressive file through fear_jpeg_progressive_to_baseline: the baseline file's bytes, or the library's status.  Host only."""
+        from .train_abi import FearJpegInfo
+        lib, info = self._lib, FearJpegInfo()
+        rc = lib.fear_jpeg_progressive_parse(data, len(data), ctypes.byref(info))
+        if rc != 0:
+            return rc
+        out = np.empty(lib.fear_jpeg_baseline_bound(ctypes.byref(info)), dtype=np.uint8)
+        used = ctypes.c_size_t(0)
+        rc = lib.fear_jpeg_progressive_to_baseline(data, len(data), out.ctypes.data, out.size, ctypes.byref(used))
+        if rc != 0:
+            return rc
+        return out[:used.value].tobytes()
 
     def scan_prepare(self, data: bytes):
         """One file through fear_jpeg_parse and fear_jpeg_scan_prepare: (FearJpegInfo, unstuffed bytes, uint32 seg_start, FearJpegScan),
@@ -421,6 +481,8 @@ class JpegDecoder:
 
     def _prepare(self, data: bytes):
         res = self.scan_prepare(data)
+        if res == ERR_UNSUPPORTED and self.progressive:
+            return self.progressive_decode(data)                      # every scan on the host; the coefficients ride as a host-path item's
         if isinstance(res, tuple) and res[3].max_seg_bytes > DEVICE_SCAN_MAX:
             return self.entropy_decode(data)                          # too long for one workgroup's bounded walk: the host's stage
         return res
@@ -451,7 +513,7 @@ class JpegDecoder:
                     raise ValueError("the fallback must return uint8 (H, W, 3)")
                 raw[i] = px
             else:
-                _raise_as_python(data, res)
+                _raise_as_python(data, res, self.progressive)
         self.last_paths = ["device" if len(prepared[i]) == 4 else "host" for i in jpegs]
         groups, dense = [[]], 0
         for i in jpegs:
@@ -594,7 +656,7 @@ class JpegDecoder:
                     raise ValueError("the fallback must return uint8 (H, W, 3)")
                 raw[i] = px
             else:
-                _raise_as_python(data, res)
+                _raise_as_python(data, res, self.progressive)
         n = len(jpegs)
         if n > 65535:
             raise ValueError("at most 65535 JPEG files per call")

@@ -169,6 +169,10 @@ class JpegStore:
     `store.kinds[id]` is "scan" or "pixels": an unsupported file with a `fallback` (without one: `UnsupportedJPEG`) and a file whose
     largest restart segment exceeds DEVICE_SCAN_MAX (decoded once through the host's Huffman stage) are kept as decoded pixels, which
     `decode` copies device to device.  Every returned frame is a private tensor, never an alias of the store.
+    With `progressive=True` a progressive file (SOF2) is first replaced, on the pool, by its lossless baseline transcode
+    (`fear_jpeg_progressive_to_baseline`: the same coefficients in one interleaved scan with a restart marker after every MCU row) and is
+    from there a "scan" entry like any other — indexed, decoded by rows, judged by `check()` on the transcoded bytes; one the transcoder
+    declines (an incomplete or inconsistent progression) goes to the `fallback` or raises, naming the item.
 
     `decode` runs on the current stream and never waits for the GPU: no file bytes go up, only about 0.5 kB of records per image in one
     pinned transfer; `fear_jpeg_dense_block_start` (only when the store's largest image grew), `fear_jpeg_huffman_indexed`,
@@ -181,17 +185,18 @@ class JpegStore:
     once: together they feed `TrainPairBuilder.build(..., borders=)` with entropy and pixel work for the rows the pairs read alone.  Per
     file the store keeps mcus_y + 1 row-table values on the host and 3 bytes of the device's border table more (`resident["rows"]`,
     `resident["border"]`, both counted in `nbytes`).
-    Out of scope: eviction and `remove`, saving a store to disk, sharding over ranks, progressive files, `JpegDecoder`'s default, compact
+    Out of scope: eviction and `remove`, saving a store to disk, sharding over ranks, `JpegDecoder`'s default, compact
     band frames and a window-aware frame record (`decode_rows` returns frames of the full shape)."""
     PENDING_CALLS = 64
 
     def __init__(self, device: int = 0, capacity_bytes: Optional[int] = None, subsequence_bytes: int = 128, slab_bytes: int = 256 << 20,
-                 workspace_limit: int = 1 << 30, threads: Optional[int] = None, initial_rows: int = 1024):
+                 workspace_limit: int = 1 << 30, threads: Optional[int] = None, initial_rows: int = 1024, progressive: bool = False):
         from .train_abi import FearJpegImage, FearJpegIndexed
         _check_subsequence_bytes(subsequence_bytes)
         if slab_bytes < 16 or initial_rows < 1:
             raise ValueError("slab_bytes is at least 16 and initial_rows at least 1")
-        self._host = JpegDecoder(device=device, threads=threads)   # the pool, sized as JpegDecoder sizes it: never by the machine's CPUs, at most 16
+        self.progressive = bool(progressive)
+        self._host = JpegDecoder(device=device, threads=threads, progressive=progressive)   # the pool, sized as JpegDecoder sizes it: never by the machine's CPUs, at most 16
         self.threads, self.device, self._lib = self._host.threads, self._host.device, self._host._lib
         self.capacity_bytes = None if capacity_bytes is None else int(capacity_bytes)
         self.subsequence_bytes, self.slab_bytes, self.workspace_limit = int(subsequence_bytes), _up(int(slab_bytes), 16), int(workspace_limit)
@@ -281,20 +286,27 @@ class JpegStore:
         if n == 0:
             return np.zeros(0, dtype=np.int64)
         SBY, limit = self.subsequence_bytes, jpeg_frames.DEVICE_SCAN_MAX
+        declined = {}
+        if self.progressive:                                             # a progressive file is replaced by its baseline transcode
+            for i, res in enumerate(self._host._pool.map(self._transcode, blobs)):
+                if isinstance(res, bytes):
+                    blobs[i] = res
+                elif res is not None:
+                    declined[i] = res                                    # the original goes to the fallback, or raises
         prepared = list(self._host._pool.map(self._host.scan_prepare, blobs))
         # every file is judged before anything is stored
         scans, through_host, raw = [], [], {}
         for i, (data, res) in enumerate(zip(blobs, prepared)):
             if isinstance(res, tuple):
                 (through_host if res[3].max_seg_bytes > limit else scans).append(i)
-            elif res == ERR_UNSUPPORTED and fallback is not None:
+            elif declined.get(i, res) == ERR_UNSUPPORTED and fallback is not None:
                 px = np.ascontiguousarray(fallback(data))
                 if px.ndim != 3 or px.shape[2] != 3 or px.dtype != np.uint8:
                     raise ValueError("the fallback must return uint8 (H, W, 3)")
                 raw[i] = px
             else:
                 try:
-                    _raise_as_python(data, res)
+                    _raise_as_python(data, declined.get(i, res), self.progressive)
                 except (MalformedJPEG, UnsupportedJPEG) as exc:
                     raise type(exc)(f"item {i}: {exc}") from None
         # the resident layout of every "scan" file, from its base: bytes | seg_start | sub_start | index | FearJpegScan, each at 16 bytes
@@ -470,6 +482,14 @@ class JpegStore:
         for key, v in split.items():
             self.resident[key] += v
         return ids
+
+    def _transcode(self, data: bytes):
+        """None for a file the baseline parser does not decline; else the baseline transcode of a progressive file, or the status with
+        which `fear_jpeg_progressive_to_baseline` declines it (FEAR_TRAIN_ERR_UNSUPPORTED also for a frame that is not SOF2)."""
+        from .train_abi import FearJpegInfo
+        if self._lib.fear_jpeg_parse(data, len(data), ctypes.byref(FearJpegInfo())) != ERR_UNSUPPORTED:
+            return None
+        return self._host.to_baseline(data)
 
     def _row_table(self, info, sub: np.ndarray, index: np.ndarray) -> np.ndarray:
         """`jpeg_huffman.scan_row_sub` from the library's header."""

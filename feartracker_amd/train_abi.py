@@ -89,6 +89,11 @@ TRAIN_SYMBOLS = {
     "fear_jpeg_parse": ([_P, _sz, _P], _i),
     "fear_jpeg_packed_bound": ([_P], _sz),
     "fear_jpeg_entropy_decode": ([_P, _sz, _P, _P, _sz, _P, _P], _i),
+    # progressive files, host only (jpeg_progressive.py): the scans to packed coefficients, or to a baseline file with a restart per MCU row
+    "fear_jpeg_progressive_parse": ([_P, _sz, _P], _i),
+    "fear_jpeg_progressive_decode": ([_P, _sz, _P, _P, _sz, _P, _P], _i),
+    "fear_jpeg_baseline_bound": ([_P], _sz),
+    "fear_jpeg_progressive_to_baseline": ([_P, _sz, _P, _sz, _P], _i),
     "fear_jpeg_decode_u8": ([_P, _i, _P, _P, _sz, _P], _i),
     "fear_jpeg_decode_workspace_bytes": ([_P, _i], _sz),
     # the Huffman stage on the device (FearJpegScan below): the host's scan preparation, the decode, the dense block_start table

@@ -550,6 +550,35 @@ size_t fear_jpeg_packed_bound(const FearJpegInfo* info);
 int fear_jpeg_entropy_decode(const uint8_t* data, size_t n, const FearJpegInfo* info, int16_t* coef, size_t coef_cap, uint32_t* block_start,
                              size_t* coef_used);
 
+/* Progressive files (SOF2), host code as the three calls above (csrc/fear_jpeg_progressive.h; DESIGN.md section 14, "Progressive files";
+ * jpeg_progressive.py restates them in Python).  Opt-in: fear_jpeg_parse keeps answering FEAR_TRAIN_ERR_UNSUPPORTED for SOF2.
+ * Accepted: what fear_jpeg_parse accepts of a frame header, with SOF2 in place of SOF0 (any other SOF: FEAR_TRAIN_ERR_UNSUPPORTED), and up
+ * to 100 scans by T.81 G.1: a scan's components are a subset of the frame's in frame order; a DC scan (Ss = Se = 0) may interleave, an AC
+ * scan (1 <= Ss <= Se <= 63) has one component; Al <= 13 and Ah is 0 or Al + 1; a first scan needs its DC or AC table (anything else:
+ * FEAR_TRAIN_ERR_FORMAT).  DHT and DRI between scans are honoured.  A scan of one component walks that component's own
+ * ceil(ceil(width h / h[0]) / 8) x ceil(ceil(height v / v[0]) / 8) blocks and its restart interval counts them.  After the last block the
+ * next marker follows the padded byte at once.  Truncated entropy data, a missing EOI, a code in no table, a run past Se, a refinement
+ * symbol of a size other than 1: FEAR_TRAIN_ERR_FORMAT.
+ * FEAR_TRAIN_ERR_UNSUPPORTED: a DQT after the first SOS; an inconsistent progression (a refinement whose Ah is not the Al the coefficient
+ * has reached, a first scan of a coefficient already coded, an AC scan in front of the component's DC scan); an incomplete one (at EOI
+ * some coefficient has not reached Al = 0: libjpeg would smooth such blocks); a 101st scan; coefficients beyond the baseline alphabet (an
+ * AC term outside +-1023, or a DC difference outside +-2047 in the layout fear_jpeg_progressive_to_baseline writes) - one rule for both
+ * calls, so they always give one verdict.
+ *
+ * fear_jpeg_progressive_parse fills the FearJpegInfo a baseline file of that frame gets, restart_interval 0.
+ * fear_jpeg_progressive_decode decodes every scan and writes fear_jpeg_entropy_decode's packed stream, which fear_jpeg_decode_u8 reads
+ * unchanged; statuses and capacities as fear_jpeg_entropy_decode's.  The padded blocks a scan of one component does not visit stay zero.
+ * fear_jpeg_progressive_to_baseline writes the same coefficients as a complete baseline file of at most fear_jpeg_baseline_bound(info)
+ * bytes (a shorter out_cap that the file overruns: FEAR_TRAIN_ERR_WORKSPACE): SOI, the source's JFIF APP0 and Adobe APP14 segments from in
+ * front of its first SOS, one DQT per table a component selects, SOF0 with the source's component ids, sampling factors and table
+ * selectors, four DHT (two for one component: DC and AC for luma, then for chroma; T.81 K.2 on this file's symbol counts), DRI = mcus_x,
+ * one interleaved SOS, the entropy data with RSTn after every MCU row, EOI.  EXIF, COM and the other APPn segments are dropped. */
+int fear_jpeg_progressive_parse(const uint8_t* data, size_t n, FearJpegInfo* info);
+int fear_jpeg_progressive_decode(const uint8_t* data, size_t n, const FearJpegInfo* info, int16_t* coef, size_t coef_cap,
+                                 uint32_t* block_start, size_t* coef_used);
+size_t fear_jpeg_baseline_bound(const FearJpegInfo* info);
+int fear_jpeg_progressive_to_baseline(const uint8_t* data, size_t n, uint8_t* out, size_t out_cap, size_t* out_used);
+
 /* The device half: n images of any sizes and sampling modes in one call, two launches.
  *   per block   the stored values un-zigzagged into a zeroed block, coef q in natural order, jidctint islow (columns, then rows), + 128,
  *               clamp to 0..255 — the clamp is the contract: libjpeg's C range-limit table wraps beyond +-512 of the centre where its

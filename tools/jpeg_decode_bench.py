@@ -70,9 +70,8 @@ THREADS = (1, 4, 8, 16)
 SWEEP = (32, 64, 128, 256)
 
 
-def make(directory):
-    from PIL import Image
-    os.makedirs(directory, exist_ok=True)
+def images():
+    """The COUNT synthetic frames, uint8 (H, W, 3), in order."""
     rng = np.random.default_rng(11)
     yy, xx = np.mgrid[0:H, 0:W]
     for i in range(COUNT):
@@ -82,7 +81,14 @@ def make(directory):
             x0, y0 = rng.integers(0, W - 8), rng.integers(0, H - 8)
             img[y0:y0 + rng.integers(8, 160), x0:x0 + rng.integers(8, 160)] = rng.integers(0, 256, 3)
         img += rng.integers(-6, 7, img.shape, dtype=np.int16)
-        Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(os.path.join(directory, f"frame{i:03d}.jpg"), quality=QUALITY, subsampling=2)
+        yield np.clip(img, 0, 255).astype(np.uint8)
+
+
+def make(directory):
+    from PIL import Image
+    os.makedirs(directory, exist_ok=True)
+    for i, img in enumerate(images()):
+        Image.fromarray(img).save(os.path.join(directory, f"frame{i:03d}.jpg"), quality=QUALITY, subsampling=2)
     print("wrote", COUNT, "files to", directory)
 
 
