@@ -9,13 +9,13 @@ from .constants import DEFAULT_TRACKING_CONFIG, TARGET_CLASSIFICATION_KEY, TARGE
 from .box_coder import FEARBoxCoder, TrackerDecodeResult, TrackerEncodeResult
 from .frames import YUVFrame
 from .tracker import FEARTracker, Tracker, TrackingState
-from .multi_tracker import FEARMultiTracker, PendingBoxes
+from .multi_tracker import FEARMultiTracker, PendingBoxes, search_rows_host
 from .hip_backend import FEARNetHIP, FearError, load_library, DEFAULT_WEIGHTS, LIB_PATH
 from .jpeg_frames import JpegDecoder, MalformedJPEG, UnsupportedJPEG, jpeg_decode_host, jpeg_info, jpeg_pixels_host
-from .jpeg_huffman import (jpeg_entropy_indexed_host, jpeg_entropy_parallel_host, jpeg_scan_index_host, jpeg_scan_prepare_host,
-                           scan_row_sub)
+from .jpeg_huffman import (jpeg_entropy_indexed_host, jpeg_entropy_parallel_host, jpeg_entropy_rows_device_host, jpeg_rows_device_host,
+                           jpeg_scan_index_host, jpeg_scan_prepare_host, scan_row_sub)
 from .jpeg_progressive import jpeg_to_baseline_host
-from .jpeg_store import JpegStore, StoreFull, plan_decode, plan_decode_rows
+from .jpeg_store import JpegStore, StoreFrames, StoreFull, plan_decode, plan_decode_rows
 
 __all__ = [
     "DEFAULT_TRACKING_CONFIG", "TARGET_CLASSIFICATION_KEY", "TARGET_REGRESSION_LABEL_KEY",
@@ -24,5 +24,6 @@ __all__ = [
     "FEARNetHIP", "FearError", "load_library", "DEFAULT_WEIGHTS", "LIB_PATH",
     "JpegDecoder", "MalformedJPEG", "UnsupportedJPEG", "jpeg_decode_host", "jpeg_info", "jpeg_entropy_parallel_host", "jpeg_scan_prepare_host",
     "jpeg_scan_index_host", "jpeg_entropy_indexed_host", "JpegStore", "StoreFull", "plan_decode", "plan_decode_rows", "scan_row_sub", "jpeg_pixels_host",
-    "jpeg_to_baseline_host",
+    "jpeg_to_baseline_host", "jpeg_entropy_rows_device_host", "jpeg_rows_device_host",
+    "StoreFrames", "search_rows_host",
 ]

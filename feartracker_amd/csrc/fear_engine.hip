@@ -2209,6 +2209,19 @@ int fear_tracker_step(fear_handle* h, const float* cls, const float* bbox, int n
     return FEAR_OK;
 }
 
+int fear_tracker_rows(fear_handle* h, const int32_t* ctx_xywh, const int32_t* frame_idx, int n, int n_streams, int out_hw,
+                      int32_t* rows, void* stream) {
+    if (!h) return FEAR_ERR_NULL;
+    if (n < 0 || n_streams < 0 || n_streams > 65535 || out_hw < 1 || out_hw > 4096) return FEAR_ERR_SHAPE;
+    if (n_streams == 0) return FEAR_OK;
+    if (!rows || (n > 0 && (!ctx_xywh || !frame_idx))) return FEAR_ERR_NULL;
+    HIP_TRY(h, hipSetDevice(h->device));
+    TrackerRowsArgs a{ctx_xywh, frame_idx, rows, n, n_streams, out_hw};
+    hipLaunchKernelGGL(tracker_rows_kernel, dim3(n_streams), dim3(64), 0, static_cast<hipStream_t>(stream), a);
+    HIP_TRY(h, hipGetLastError());
+    return FEAR_OK;
+}
+
 int fear_plan_size(fear_handle* h, int hw, int with_head) {
     if (!h) return FEAR_ERR_NULL;
     Plan* p = nullptr;

@@ -41,7 +41,7 @@ struct JhSegment {
     uint32_t first_mcu;
     uint32_t expected;       // the blocks the segment owes
     bool last;
-    uint32_t band_row0, band_rows;   // MODE 3 alone (fear_jpeg_store.h): the MCU rows whose blocks are stored, inside the image
+    uint32_t band_row0, band_rows;   // MODE 3, 4 alone (fear_jpeg_store.h): the MCU rows whose blocks are stored, inside the image
 };
 
 struct JhState {
@@ -118,9 +118,17 @@ __device__ __forceinline__ long jh_band_base(const JhSegment& s, uint32_t ordina
     return b < band_mcus * (uint32_t)s.nslots ? (long)b * 64 : -1;
 }
 
+// MODE 4: the block's place in the WHOLE image (jh_block_base), but -1 for a block whose MCU row lies outside the band.
+__device__ __forceinline__ long jh_rows_base(const JhSegment& s, uint32_t ordinal, int slot) {
+    if (ordinal >= s.expected) return -1;
+    const uint32_t my = (s.first_mcu + ordinal / (uint32_t)s.nslots) / (uint32_t)s.mcus_x;
+    if (my < s.band_row0 || my >= s.band_row0 + s.band_rows) return -1;   // band_row0 + band_rows <= mcus_y <= 1024
+    return jh_block_base(s, ordinal, slot);
+}
+
 template <int MODE>
 __device__ __forceinline__ long jh_base(const JhSegment& s, uint32_t ordinal, int slot) {
-    return MODE == 3 ? jh_band_base(s, ordinal, slot) : jh_block_base(s, ordinal, slot);
+    return MODE == 4 ? jh_rows_base(s, ordinal, slot) : (MODE == 3 ? jh_band_base(s, ordinal, slot) : jh_block_base(s, ordinal, slot));
 }
 
 // What the count pass gathers and the write pass starts from.
@@ -142,6 +150,7 @@ __device__ __forceinline__ uint32_t jh_add_dc(JhLane& lane, int comp, uint32_t v
 
 // Symbols from `st` until the position reaches `end` or the segment's end.  MODE 0: the exit state and nothing else.  1: count.  2: write.
 // 3: write, but only the blocks of the band's MCU rows are stored (jh_band_base); every judgement is mode 2's.
+// 4: write, only the blocks of the band's MCU rows, at their place in the whole image (jh_rows_base); every judgement is mode 2's.
 // A code in no table, a DC size above 15 or an index past 63: advance one bit, z = 0.
 template <int MODE>
 __device__ __forceinline__ JhState jh_decode(const JhSegment& s, const FearJpegHuff* tabs, JhState st, uint32_t end, int16_t* coef, JhLane& io) {

@@ -1,12 +1,12 @@
 // fear_jpeg_store.h — scans resident on the device and the index a baseline scan lacks (include/fear_train.h: fear_jpeg_index_build,
-// fear_jpeg_huffman_indexed, fear_jpeg_huffman_indexed_rows; DESIGN.md section 14, "The resident store").  fear_jpeg_index_build is the second instantiation of
+// fear_jpeg_huffman_indexed, fear_jpeg_huffman_indexed_rows, fear_jpeg_huffman_indexed_rows_dev; DESIGN.md section 14, "The resident store").  fear_jpeg_index_build is the second instantiation of
 // jpeg_huffman_kernel (fear_jpeg_huffman.h), which stores every lane's true entry in front of its write pass.  With those entries a later
 // decode is the write pass alone: jpeg_huffman_indexed_kernel gives every subsequence of an image a lane of its own, whatever segment it
 // lies in.  jpeg_huffman.jpeg_scan_index_host and jpeg_entropy_indexed_host restate both in Python.  fear_jpeg_huffman_indexed_rows is
 // the same lane for a band of MCU rows: only the subsequences in which the band's blocks lie get a lane (the caller's row_sub table,
 // jpeg_huffman.scan_row_sub), and only the band's blocks are stored, as the dense coefficients of an image of those rows alone.
 // Included by fear_train.hip behind fear_jpeg_huffman.h, whose jh_decode, jh_peek, jh_block_base and JhSegment it uses, and
-// fear_jpeg_decode.h's jd_find_image.
+// fear_jpeg_decode.h's jd_find_image and jr_band.
 
 namespace {
 
@@ -27,15 +27,32 @@ __global__ __launch_bounds__(kJhLanes) void jpeg_indexed_status_kernel(JpegIndex
     if (i < a.n) a.status[i] = ji_records(a)[i].n_sub == 0 ? FEAR_TRAIN_ERR_FORMAT : FEAR_TRAIN_OK;
 }
 
-// One lane of the indexed decode.  ROWS: fear_jpeg_huffman_indexed_rows' instantiation, whose lanes are the record's sub_count
-// subsequences from sub0 and which stores only the blocks of the record's band of MCU rows, band-dense (jh_band_base).
-template <bool ROWS>
-__device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a) {
+// One lane of the indexed decode.  FORM 1: fear_jpeg_huffman_indexed_rows' instantiation, whose lanes are the record's sub_count
+// subsequences from sub0 and which stores only the blocks of the record's band of MCU rows, band-dense (jh_band_base).  FORM 2:
+// fear_jpeg_huffman_indexed_rows_dev's, whose band comes from `rows_dev` (device memory; null in the other forms): the grid is the whole
+// image's, a workgroup outside the band's subsequences returns in front of the table copy, a lane outside them behind the barrier, and
+// the band's blocks are stored at their place in the whole image (jh_rows_base).
+template <int FORM>
+__device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a, const int32_t* rows_dev) {
+    constexpr bool ROWS = FORM == 1, DEV = FORM == 2;
     __shared__ __attribute__((aligned(16))) FearJpegHuff tabs[6];        // dc by component, then ac by component
     const int tid = threadIdx.x;
     const int img = jd_find_image(a.table, a.n, blockIdx.x);             // the same for the whole workgroup
     const FearJpegIndexed* im = ji_records(a) + img;
     const FearJpegScan* rec = im->scan;
+    uint32_t dev_first = 0, dev_last = 0, dev_row0 = 0, dev_rows = 0;    // DEV: the lanes that run, inclusive, and the band
+    if (DEV) {                                                           // everything here is the same for the whole workgroup
+        const int mcus_y = min(max(rec->mcus_y, 1), FEAR_JPEG_MAX_SIDE / 8), v = rec->v == 2 ? 2 : 1;
+        int ba, bb;
+        if (!jr_band(rows_dev[2 * img], rows_dev[2 * img + 1], 8 * v * mcus_y, 8 * v, mcus_y, v == 2, &ba, &bb)) return;
+        if (im->n_sub == 0) return;
+        dev_first = im->row_sub[ba];                                     // the table has mcus_y + 1 values and 0 <= ba < bb <= mcus_y
+        dev_last = min(im->row_sub[bb], im->n_sub - 1u);
+        const uint64_t lane0 = (uint64_t)(blockIdx.x - a.table[img]) * kJhLanes;
+        if (lane0 > dev_last || lane0 + (kJhLanes - 1) < dev_first) return;   // an idle workgroup: a few loads, no table copy, no barrier
+        dev_row0 = (uint32_t)ba;
+        dev_rows = (uint32_t)(bb - ba);
+    }
     {
         const uint4* src = reinterpret_cast<const uint4*>(rec->dc);      // the record is 16-byte aligned, the tables lie 64 bytes in
         uint4* dst = reinterpret_cast<uint4*>(tabs);
@@ -48,6 +65,7 @@ __device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a) {
         if (sub64 >= im->sub_count) return;                              // lanes that do not run judge nothing
         sub64 += im->sub0;
     }
+    if (DEV && (sub64 < dev_first || sub64 > dev_last)) return;          // lanes that do not run judge nothing
     if (sub64 >= n_sub || n_seg == 0) return;
     const uint32_t sub = (uint32_t)sub64;
     const uint4 e = reinterpret_cast<const uint4*>(im->index)[sub];
@@ -89,6 +107,10 @@ __device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a) {
             s.band_row0 = min(im->mcu_row0, mcus_y);
             s.band_rows = min(im->mcu_rows, mcus_y - s.band_row0);
         }
+        if (DEV) {                                                       // 0 <= row0 < row0 + rows <= mcus_y by jr_band
+            s.band_row0 = dev_row0;
+            s.band_rows = dev_rows;
+        }
     }
     int32_t* status = a.status + img;
     const uint64_t k = (uint64_t)sub - first;                            // the subsequence within its segment
@@ -105,7 +127,7 @@ __device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a) {
     lane.dc1 = e.w & 0xFFFFu;
     lane.dc2 = e.w >> 16;
     const uint32_t end = ((uint32_t)k + 1u) * SB;                        // k SB < bits <= 2^27 (8 FEAR_JPEG_DEVICE_SCAN_MAX), SB <= 2^13: no overflow
-    const JhState out = jh_decode<ROWS ? 3 : 2>(s, tabs, entry, end, a.coef + im->coef_offset, lane);
+    const JhState out = jh_decode<DEV ? 4 : (ROWS ? 3 : 2)>(s, tabs, entry, end, a.coef + im->coef_offset, lane);
     bool failed = lane.error;
     // the segment's last subsequence: fewer complete blocks than the segment owes, as jpeg_huffman_kernel judges its true chain's end
     if (end >= s.bits && (lane.begun - ((out.sz & 255) != 0 ? 1u : 0u) < s.expected || (lane.begun == 0 && s.expected > 0))) failed = true;
@@ -114,9 +136,13 @@ __device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a) {
     if (failed) *status = FEAR_TRAIN_ERR_FORMAT;                          // every lane that stores stores the same value
 }
 
-__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_kernel(JpegIndexedArgs a) { ji_lane<false>(a); }
+__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_kernel(JpegIndexedArgs a) { ji_lane<0>(a, nullptr); }
 
-__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_rows_kernel(JpegIndexedArgs a) { ji_lane<true>(a); }
+__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_rows_kernel(JpegIndexedArgs a) { ji_lane<1>(a, nullptr); }
+
+__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_rows_dev_kernel(JpegIndexedArgs a, const int32_t* rows_dev) {
+    ji_lane<2>(a, rows_dev);
+}
 
 }  // namespace
 
@@ -216,6 +242,37 @@ int fear_jpeg_huffman_indexed_rows(const FearJpegIndexed* images, int n, const v
     LAUNCH_CHECK();
     if (groups == 0) return FEAR_TRAIN_OK;
     hipLaunchKernelGGL(jpeg_huffman_indexed_rows_kernel, dim3((unsigned)groups), dim3(kJhLanes), 0, static_cast<hipStream_t>(stream), a);
+    LAUNCH_CHECK();
+    return FEAR_TRAIN_OK;
+}
+
+int fear_jpeg_huffman_indexed_rows_dev(const FearJpegIndexed* images, int n, const void* table_dev, const int32_t* rows_dev, int16_t* coef,
+                                       int32_t* status_dev, int subsequence_bytes, void* stream) {
+    if (n < 0 || n > 65535 || subsequence_bytes < 4 || subsequence_bytes > 1024 || (subsequence_bytes & 3) != 0) return FEAR_TRAIN_ERR_SHAPE;
+    if (n == 0) return FEAR_TRAIN_OK;
+    if (!images || !table_dev || !rows_dev || !coef || !status_dev) return FEAR_TRAIN_ERR_NULL;
+    uint64_t groups = 0;
+    for (int i = 0; i < n; ++i) {
+        const FearJpegIndexed& im = images[i];
+        if (!im.scan || !im.sub_start || !im.row_sub || (!im.index && im.n_sub != 0)) return FEAR_TRAIN_ERR_NULL;
+        if ((reinterpret_cast<uintptr_t>(im.index) & 15) != 0 || (reinterpret_cast<uintptr_t>(im.scan) & 15) != 0 ||
+            (reinterpret_cast<uintptr_t>(im.sub_start) & 3) != 0 || (reinterpret_cast<uintptr_t>(im.row_sub) & 3) != 0)
+            return FEAR_TRAIN_ERR_SHAPE;
+        groups += ((uint64_t)im.n_sub + kJhLanes - 1) / kJhLanes;
+    }
+    if (groups > 0x7fffffffu) return FEAR_TRAIN_ERR_SHAPE;
+    JpegIndexedArgs a{};
+    a.table = static_cast<const uint32_t*>(table_dev);
+    a.coef = coef;
+    a.status = status_dev;
+    a.n = n;
+    a.subsequence_bits = subsequence_bytes * 8;
+    hipLaunchKernelGGL(jpeg_indexed_status_kernel, dim3((unsigned)((n + kJhLanes - 1) / kJhLanes)), dim3(kJhLanes), 0,
+                       static_cast<hipStream_t>(stream), a);
+    LAUNCH_CHECK();
+    if (groups == 0) return FEAR_TRAIN_OK;
+    hipLaunchKernelGGL(jpeg_huffman_indexed_rows_dev_kernel, dim3((unsigned)groups), dim3(kJhLanes), 0, static_cast<hipStream_t>(stream), a,
+                       rows_dev);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }

@@ -850,6 +850,42 @@ __global__ __launch_bounds__(256) void crop_resize_normalize_kernel(CropArgs a) 
     }
 }
 
+// The frame rows the next crop_resize_normalize_kernel launch samples, per stream (fear_tracker_rows; multi_tracker.search_rows_host
+// restates it).  A crop with the context box (., cy, ., ch) taps, over its S output rows, the rows cy + i0(0) .. cy + i1(S - 1) of
+// linear_tap<false> — the taps move monotonically with the output row, and the same and half paths read exactly cy .. cy + ch - 1, which
+// is what the two taps give for ch == S and ch == 2 S.  A degenerate box, ch <= 0, pins both indices to ch - 1 (the min against src - 1
+// is applied last): the single row cy + ch - 1.  One wavefront per stream walks the targets and reduces; no atomics.
+struct TrackerRowsArgs {
+    const int* ctx;          // [n][4] the context boxes of the next crop launch
+    const int* frame_idx;    // [n] the stream of each target
+    int* rows;               // [n_streams][2] out: [y0, y1), unclipped; (0, 0) for a stream without a target
+    int n, n_streams, S;
+};
+
+__global__ __launch_bounds__(64) void tracker_rows_kernel(TrackerRowsArgs a) {
+    const int s = blockIdx.x;
+    long long lo = (1LL << 40), hi = -(1LL << 40);
+    for (int t = threadIdx.x; t < a.n; t += 64) {
+        if (a.frame_idx[t] != s) continue;
+        const int cy = a.ctx[t * 4 + 1], ch = a.ctx[t * 4 + 3];
+        int i0, i1, j0, j1, w0, w1;
+        linear_tap<false>(0, a.S, ch, i0, i1, w0, w1);
+        linear_tap<false>(a.S - 1, a.S, ch, j0, j1, w0, w1);
+        lo = min(lo, (long long)cy + min(i0, j0));
+        hi = max(hi, (long long)cy + max(i1, j1) + 1);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        lo = min(lo, __shfl_xor(lo, d, 64));
+        hi = max(hi, __shfl_xor(hi, d, 64));
+    }
+    if (threadIdx.x != 0) return;
+    const long long far = 1LL << 30;                          // int32 contexts: the sums fit 64 bits, the result is pinned to 32
+    const bool any = lo < hi;
+    a.rows[s * 2] = any ? (int)min(max(lo, -far), far) : 0;
+    a.rows[s * 2 + 1] = any ? (int)min(max(hi, -far), far) : 0;
+}
+
 // ================================================================================================
 // Fused block kernels.  (The first generation — ir16_fused_kernel / ir_tile_fused_kernel, weights loaded from
 // global per chunk — was replaced by the v2 kernels below after the tools/kbench.hip ablation; see DESIGN.md.)

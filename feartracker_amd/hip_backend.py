@@ -89,6 +89,8 @@ def load_library() -> ctypes.CDLL:
     lib.fear_tracker_step.argtypes = [vp, f32p, f32p, i32, vp, vp, vp, vp, i32, vp, f64, f64, f64, i32, i32, i32, f64, vp, f32p,
                                       vp]
     lib.fear_tracker_step.restype = i32
+    lib.fear_tracker_rows.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
+    lib.fear_tracker_rows.restype = i32
     lib.fear_set_option.argtypes = [vp, i32, i64]
     lib.fear_set_option.restype = i32
     lib.fear_get_option.argtypes = [vp, i32]
@@ -115,7 +117,7 @@ def load_library() -> ctypes.CDLL:
 
 EXPORTED_SYMBOLS = (
     "fear_create", "fear_destroy", "fear_features", "fear_track", "fear_track_packed", "fear_decode", "fear_decode_smooth", "fear_normalize_u8",
-    "fear_crop_normalize", "fear_crop_normalize_frames", "fear_tracker_step", "fear_yuv_to_rgb", "fear_crop_normalize_planar",
+    "fear_crop_normalize", "fear_crop_normalize_frames", "fear_tracker_step", "fear_tracker_rows", "fear_yuv_to_rgb", "fear_crop_normalize_planar",
     "fear_set_option", "fear_get_option", "fear_plan_size", "fear_plan_op", "fear_profile_read",
     "fear_profile_reset", "fear_workspace_bytes", "fear_strerror", "fear_last_hip_error", "fear_version",
 )
@@ -704,6 +706,23 @@ class FEARNetHIP:
                 prev_size.data_ptr(), 1 if smooth else 0, window.data_ptr(), float(penalty_k), float(window_influence), float(lr),
                 int(score_size), int(total_stride), int(instance_size), float(search_context),
                 xywh.data_ptr() if xywh is not None else None, score.data_ptr(), self._stream()))
+
+    @torch.no_grad()
+    def tracker_rows(self, ctx_xywh: torch.Tensor, frame_idx: torch.Tensor, n_streams: int, out_hw: int = 256) -> torch.Tensor:
+        """fear_tracker_rows on device tensors: the frame rows [y0, y1) per stream that the next `crop_normalize_frames` launch over
+        `ctx_xywh` (n,4) int32 and `frame_idx` (n,) int32 samples -> (n_streams, 2) int32 on the device, unclipped.  One launch; the
+        call does not wait for the GPU."""
+        n = int(frame_idx.shape[0])
+        for t, dt, shape in ((frame_idx, torch.int32, (n,)), (ctx_xywh, torch.int32, (n, 4))):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"expected a contiguous {dt} {shape} tensor on the engine's device")
+        if not 0 <= int(n_streams) <= 65535:
+            raise ValueError("n_streams must lie in 0..65535")
+        rows = torch.empty((int(n_streams), 2), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self._lib.fear_tracker_rows(self._h, ctx_xywh.data_ptr() if n else None, frame_idx.data_ptr() if n else None, n,
+                                                    int(n_streams), int(out_hw), rows.data_ptr() if n_streams else None, self._stream()))
+        return rows
 
     # ------------------------------------------------------------------ measurement
     def plan(self, hw: int = 256, with_head: bool = True):

@@ -454,12 +454,10 @@ def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: 
     return coef, status
 
 
-def jpeg_entropy_bands_host(data: bytes, sub_start, index, subsequence_bytes: int, bands, row_sub=None):
-    """`jpeg_entropy_indexed_host(..., band=(a, b))` for many bands of one file at once: [(coefficients per component, status)] in the
-    order of `bands`.  Every lane decodes and judges once, whatever the band (its decode does not depend on it), and records what it
-    would store; per band the stores of the lanes that run, row_sub[a] .. min(row_sub[b], n_sub - 1), whose MCU row passes the explicit
-    range test a <= row < b are placed band-dense, and the lanes that do not run judge nothing.  Asserts that every position of a band
-    is written exactly once when its status is 0."""
+def _record_lanes(data: bytes, sub_start, index, subsequence_bytes: int, row_sub=None):
+    """Every lane of the indexed decode once, whatever band is wanted (a lane's decode does not depend on it): the header, the geometry,
+    n_sub, the row table, each lane's verdict, and every store any lane would make, one array entry per coefficient position — the
+    lane, the MCU row and column, the slot, z and the value."""
     _check_subsequence_bytes(subsequence_bytes)
     data = bytes(data)
     hd = _parse(data)
@@ -494,7 +492,17 @@ def jpeg_entropy_bands_host(data: bytes, sub_start, index, subsequence_bytes: in
             value_of += [value] * (z1 - z0)
     lane_of, mcu_of, slot_of, z_of = (np.array(v, dtype=np.int64) for v in (lane_of, mcu_of, slot_of, z_of))
     value_of = np.array(value_of, dtype=np.int64).astype(np.int16)
-    my, mx = mcu_of // g.mcus_x, mcu_of % g.mcus_x
+    return hd, g, n_sub, row_sub, lane_failed, (lane_of, mcu_of // g.mcus_x, mcu_of % g.mcus_x, slot_of, z_of, value_of)
+
+
+def jpeg_entropy_bands_host(data: bytes, sub_start, index, subsequence_bytes: int, bands, row_sub=None):
+    """`jpeg_entropy_indexed_host(..., band=(a, b))` for many bands of one file at once: [(coefficients per component, status)] in the
+    order of `bands`.  Every lane decodes and judges once, whatever the band (its decode does not depend on it), and records what it
+    would store; per band the stores of the lanes that run, row_sub[a] .. min(row_sub[b], n_sub - 1), whose MCU row passes the explicit
+    range test a <= row < b are placed band-dense, and the lanes that do not run judge nothing.  Asserts that every position of a band
+    is written exactly once when its status is 0."""
+    hd, g, n_sub, row_sub, lane_failed, (lane_of, my, mx, slot_of, z_of, value_of) = _record_lanes(data, sub_start, index, subsequence_bytes,
+                                                                                                     row_sub)
     comp = np.array(g.comp, dtype=np.int64)[slot_of]
     luma = comp == 0
     j, i = np.where(luma, slot_of // g.h, 0), np.where(luma, slot_of % g.h, 0)
@@ -525,3 +533,87 @@ def jpeg_entropy_bands_host(data: bytes, sub_start, index, subsequence_bytes: in
             where += size
         out.append((coef, status))
     return out
+
+
+# -------------------------------------------------------------------------------------------------- the band of rows taken from the device
+def rows_band(y0: int, y1: int, limit: int, mcu_h: int, mcus_y: int, halo: bool):
+    """The band of MCU rows (a, b) that covers the pixel rows [y0, y1) clipped to [0, limit], one MCU row more on each side with `halo`,
+    clipped to mcus_y; None for the empty band y0 >= y1 (jr_band in csrc/fear_jpeg_decode.h; `plan_decode_rows` states the same rule)."""
+    y0, y1 = min(max(int(y0), 0), limit), min(max(int(y1), 0), limit)
+    if y0 >= y1:
+        return None
+    a, b = max(y0 // mcu_h - bool(halo), 0), min(-(-y1 // mcu_h) + bool(halo), mcus_y)
+    return (a, b) if a < b else None
+
+
+def jpeg_entropy_rows_device_many_host(data: bytes, sub_start, index, subsequence_bytes: int, windows, row_sub=None):
+    """The contract of `fear_jpeg_huffman_indexed_rows_dev` for many windows [y0, y1) of one file: per window
+    (lanes, coefficients, mask, status).  The band is `rows_band` with the rows of the MCU grid as the limit (the resident record does
+    not hold the height) and the halo where v == 2; `lanes` is the range of subsequences that run, row_sub[a] .. min(row_sub[b],
+    n_sub - 1), empty for the empty band; `coefficients` are per component in the FULL-IMAGE layout, as `jpeg_coefficients_host` returns
+    them, zero where nothing was stored; `mask` has their shapes and counts the stores to each position: 1 on the band's blocks, 0
+    elsewhere.  A lane that runs decodes and judges as `jpeg_entropy_indexed_host`'s, a block whose MCU row lies outside the band (an
+    explicit range test) is not stored, and lanes that do not run judge nothing."""
+    hd, g, n_sub, row_sub, lane_failed, (lane_of, my, mx, slot_of, z_of, value_of) = _record_lanes(data, sub_start, index, subsequence_bytes,
+                                                                                                     row_sub)
+    comp = np.array(g.comp, dtype=np.int64)[slot_of]
+    luma = comp == 0
+    j, i = np.where(luma, slot_of // g.h, 0), np.where(luma, slot_of % g.h, 0)
+    first_of = np.array(g.comp_first, dtype=np.int64)[comp]
+    wide = np.array(g.blocks_w, dtype=np.int64)[comp]
+    block = first_of + np.where(luma, (my * g.v + j) * wide + mx * g.h + i, my * wide + mx)     # jh_block_base
+    at_all = 64 * block + z_of
+    mcu_h, n_values = 8 * g.v, 64 * g.total_blocks
+    out = []
+    for y0, y1 in windows:
+        band = rows_band(y0, y1, mcu_h * hd.mcus_y, mcu_h, hd.mcus_y, g.v == 2)
+        dense, writes = np.zeros(n_values, dtype=np.int16), np.zeros(n_values, dtype=np.int64)
+        lanes, status = range(0), (ERR_FORMAT if n_sub == 0 else 0)
+        if band is not None and n_sub:
+            a, b = band
+            lanes = range(int(row_sub[a]), min(int(row_sub[b]), n_sub - 1) + 1)
+            keep = (lane_of >= lanes.start) & (lane_of < lanes.stop) & (my >= a) & (my < b) & (block < g.total_blocks)
+            dense[at_all[keep]] = value_of[keep]
+            writes = np.bincount(at_all[keep], minlength=n_values)
+            if lane_failed[lanes.start:lanes.stop].any():
+                status = ERR_FORMAT
+        coef, mask, at = [], [], 0
+        for c in range(g.nf):
+            size = hd.blocks_w[c] * hd.blocks_h[c]
+            coef.append(dense[64 * at:64 * (at + size)].reshape(hd.blocks_h[c], hd.blocks_w[c], 64))
+            mask.append(writes[64 * at:64 * (at + size)].reshape(hd.blocks_h[c], hd.blocks_w[c], 64))
+            at += size
+        out.append((lanes, coef, mask, status))
+    return out
+
+
+def jpeg_entropy_rows_device_host(data: bytes, sub_start, index, subsequence_bytes: int, y0: int, y1: int, row_sub=None):
+    """`jpeg_entropy_rows_device_many_host` for one window: (lanes, coefficients, mask, status)."""
+    return jpeg_entropy_rows_device_many_host(data, sub_start, index, subsequence_bytes, [(y0, y1)], row_sub)[0]
+
+
+def jpeg_rows_device_host(data: bytes, y0: int, y1: int, subsequence_bytes: int = 128, fill=None):
+    """The contract of `JpegStore.decode_rows(ids, rows)` with `rows` on the device, for one file and one window: (lanes, coefficients,
+    mask, frame).  The index is `jpeg_scan_index_host`'s; lanes, coefficients and mask are `jpeg_entropy_rows_device_host`'s; `frame` is
+    uint8 (H, W, 3) of which the rows [y0, y1) clipped to [0, H] are defined — `fear_jpeg_decode_u8_rows_dev` on those coefficients: the
+    pixel stage of the whole image, in which the positions that were never stored hold `fill` (an int16 array of 64 total_blocks values:
+    what the buffer held; zeros by default) — and all other rows are zero here and unspecified on the device.  Whatever `fill` holds, the
+    defined rows are `jpeg_decode_host`'s: their luma lies in the band without its halo and their chroma rows in the band with it."""
+    from .jpeg_frames import jpeg_pixels_host
+    hd, sub_start, index, status = jpeg_scan_index_host(data, subsequence_bytes)
+    if status != 0:
+        raise MalformedJPEG("the scan does not decode")
+    lanes, coef, mask, status = jpeg_entropy_rows_device_host(data, sub_start, index, subsequence_bytes, y0, y1)
+    if fill is not None:
+        fill, at = np.asarray(fill, dtype=np.int16).reshape(-1), 0
+        held = []
+        for c, m in zip(coef, mask):
+            held.append(np.where(m > 0, c, fill[at:at + c.size].reshape(c.shape)))
+            at += c.size
+    else:
+        held = coef
+    frame = np.zeros((hd.height, hd.width, 3), dtype=np.uint8)
+    lo, hi = min(max(int(y0), 0), hd.height), min(max(int(y1), 0), hd.height)
+    if lo < hi:
+        frame[lo:hi] = jpeg_pixels_host(hd, held)[lo:hi]
+    return lanes, coef, mask, frame

@@ -11,7 +11,12 @@ A training pair reads only the rows of its context boxes.  `add` therefore also 
 subsequence in which each MCU row begins, `jpeg_huffman.scan_row_sub`, from the index it has just built) and the frame's border colour
 (`fear_frame_border_u8` of the full decode, in a device table that `borders(ids)` gathers), and `JpegStore.decode_rows` decodes a band of
 rows per frame: `plan_decode_rows` on the host, `fear_jpeg_huffman_indexed_rows` with lanes for the band's subsequences alone, and the
-unchanged `fear_jpeg_decode_u8` on the band as an image of its own ("Bands of rows")."""
+unchanged `fear_jpeg_decode_u8` on the band as an image of its own ("Bands of rows").
+
+A tracker knows the rows of its next search window only on the device.  `decode_rows` therefore also takes `rows` as a device tensor that
+only kernels read: `plan_decode`'s full-image plan, `fear_jpeg_huffman_indexed_rows_dev` and `fear_jpeg_decode_u8_rows_dev`, whose
+workgroups outside the band return early — for which `add` keeps each file's row table on the device as well ("Rows
+from the device").  `StoreFrames(store, ids)` names a sequence of frames kept in a store, for `SequenceValidator`."""
 from __future__ import annotations
 
 import ctypes
@@ -184,7 +189,8 @@ class JpegStore:
     `decode_rows(ids, rows)` decodes a band of rows per frame and `borders(ids)` gathers the frames' border colours, which `add` computed
     once: together they feed `TrainPairBuilder.build(..., borders=)` with entropy and pixel work for the rows the pairs read alone.  Per
     file the store keeps mcus_y + 1 row-table values on the host and 3 bytes of the device's border table more (`resident["rows"]`,
-    `resident["border"]`, both counted in `nbytes`).
+    `resident["border"]`, both counted in `nbytes`); the row table is also resident on the device (one tensor per `add`, the same
+    4 (mcus_y + 1) bytes per file that `resident["rows"]` counts), for `decode_rows` with `rows` on the device.
     Out of scope: eviction and `remove`, saving a store to disk, sharding over ranks, `JpegDecoder`'s default, compact
     band frames and a window-aware frame record (`decode_rows` returns frames of the full shape)."""
     PENDING_CALLS = 64
@@ -215,6 +221,7 @@ class JpegStore:
         self._border = None                                              # (capacity, 3) uint8 on the device, grown with the mirrors
         self._indexed, self._image, self._columns = (np.zeros(self._initial_rows, dtype=d) for d in self._dtypes)
         self._slabs: List = []
+        self._row_slabs: List = []                                       # the row tables on the device, one uint32 tensor per `add`, never reallocated
         self._open, self._cursor = None, 0                               # the slab that is being filled
         self._pixels: dict = {}
         self._most, self._dense_start, self._dense_blocks, self._dense_event = 0, None, -1, None
@@ -436,6 +443,11 @@ class JpegStore:
                 slab, at = placed[i]
                 index = slab[at + at_index:at + at_record].cpu().numpy().view(SUBSEQ_DTYPE)
                 row_tables[i] = self._row_table(prepared[i][0], sub, index)
+            row_at, row_dev = {}, None                                   # and once more on the device, for rows that only the device knows
+            if scans:
+                at = _exclusive(np.array([row_tables[i].size for i in scans], dtype=np.int64))
+                row_dev = torch.from_numpy(np.concatenate([row_tables[i] for i in scans]).astype(np.uint32).view(np.int32)).to(self.device)
+                row_at = {i: row_dev.data_ptr() + 4 * int(at[k]) for k, i in enumerate(scans)}
             border = self._border                                        # grown here, committed below
             if border is None or border.shape[0] < first_new + n:
                 have = max(self._initial_rows, 1) if border is None else border.shape[0]
@@ -457,6 +469,7 @@ class JpegStore:
             sub, at_seg, at_sub, at_index, at_record, end = layout[i]
             row, img, col = self._indexed[first + i], self._image[first + i], self._columns[first + i]
             row["scan"], row["index"], row["sub_start"], row["n_sub"] = base[i] + at_record, base[i] + at_index, base[i] + at_sub, int(sub[-1])
+            row["row_sub"] = row_at[i]
             img["width"], img["height"], img["components"], img["h"], img["v"] = info.width, info.height, info.components, info.h[0], info.v[0]
             img["qt"] = np.ctypeslib.as_array(info.qt)
             table = row_tables[i]
@@ -477,6 +490,8 @@ class JpegStore:
             torch.cuda.current_stream().synchronize()
         self._border = border
         self._slabs += new_slabs
+        if row_dev is not None:
+            self._row_slabs.append(row_dev)
         self._open, self._cursor = open_slab, cursor
         self._n, self.nbytes = first + n, self.nbytes + need
         for key, v in split.items():
@@ -555,7 +570,21 @@ class JpegStore:
             self.check()
         return frames
 
-    def _decode_group(self, ids: np.ndarray, plan: dict, frames: List) -> None:
+    def _decode_rows_device(self, ids: np.ndarray, rows, check: bool) -> List:
+        import torch
+        mine = torch.device(self.device)
+        if rows.device.index != (mine.index or 0) or rows.dtype != torch.int32 or tuple(rows.shape) != (ids.size, 2):
+            raise ValueError(f"rows on a device must be ({ids.size}, 2) int32 on {mine}, one [y0, y1) per id")
+        frames: List = [None] * ids.size
+        self._pending = self._pending[-self.PENDING_CALLS:]
+        for plan in plan_decode(self._columns, ids, self.workspace_limit):
+            self._decode_group(ids, plan, frames, rows)
+        if check:
+            self.check()
+        return frames
+
+    def _decode_group(self, ids: np.ndarray, plan: dict, frames: List, rows=None) -> None:
+        """One group of `decode`; with `rows`, the call's device tensor, one group of `decode_rows` with the rows on the device."""
         import torch
         from . import train_abi as abi
         lo, hi, scan = plan["lo"], plan["hi"], plan["scan"]
@@ -588,21 +617,36 @@ class JpegStore:
                 at_indexed = _up(plan["sub_prefix"].nbytes, 16)
                 at_table = at_indexed + indexed.nbytes
                 at_images = at_table + _up(prefixes.nbytes, 16)
-                pinned = torch.empty(at_images + images.nbytes, dtype=torch.uint8, pin_memory=True)
+                # with rows on the device and a group that is no run of positions: the positions, to gather the group's rows with
+                whole = rows is None or nd == hi - lo
+                at_pick = at_images + images.nbytes
+                pinned = torch.empty(at_pick + (0 if whole else 8 * nd), dtype=torch.uint8, pin_memory=True)
                 host = pinned.numpy()
                 host[:at_indexed].view(np.uint32)[:nd + 1] = plan["sub_prefix"]
                 host[at_indexed:at_table] = indexed.view(np.uint8)
                 host[at_table:at_images].view(np.uint32)[:2 * nd + 2] = prefixes
-                host[at_images:] = images.view(np.uint8)
+                host[at_images:at_pick] = images.view(np.uint8)
+                if not whole:
+                    host[at_pick:].view(np.int64)[:] = lo + scan
                 dev = torch.empty(pinned.numel(), dtype=torch.uint8, device=self.device)
                 dev.copy_(pinned, non_blocking=True)
                 self._pinned = self._pinned[-1:] + [pinned]
                 self._records = (indexed, images)                        # the calls below get their addresses
                 self.last_upload_bytes = pinned.numel()
-                abi.launch(self._lib, "fear_jpeg_huffman_indexed", ctypes.c_void_p(indexed.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr()),
-                           ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(status.data_ptr()), self.subsequence_bytes, stream)
-                abi.launch(self._lib, "fear_jpeg_decode_u8", ctypes.c_void_p(images.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr() + at_table),
-                           ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"], stream)
+                if rows is None:
+                    abi.launch(self._lib, "fear_jpeg_huffman_indexed", ctypes.c_void_p(indexed.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr()),
+                               ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(status.data_ptr()), self.subsequence_bytes, stream)
+                    abi.launch(self._lib, "fear_jpeg_decode_u8", ctypes.c_void_p(images.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr() + at_table),
+                               ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"], stream)
+                else:                                                    # the group's rows: a slice, or a gather on the device; no wait
+                    mine = rows[lo:hi] if whole else rows.index_select(0, dev[at_pick:].view(torch.int64))
+                    mine = mine.contiguous()
+                    abi.launch(self._lib, "fear_jpeg_huffman_indexed_rows_dev", ctypes.c_void_p(indexed.ctypes.data), nd,
+                               ctypes.c_void_p(dev.data_ptr()), ctypes.c_void_p(mine.data_ptr()), ctypes.c_void_p(coef.data_ptr()),
+                               ctypes.c_void_p(status.data_ptr()), self.subsequence_bytes, stream)
+                    abi.launch(self._lib, "fear_jpeg_decode_u8_rows_dev", ctypes.c_void_p(images.ctypes.data), nd,
+                               ctypes.c_void_p(dev.data_ptr() + at_table), ctypes.c_void_p(mine.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                               plan["workspace_bytes"], stream)
                 verdict = torch.empty(nd, dtype=torch.int32, pin_memory=True)
                 verdict.copy_(status, non_blocking=True)
                 event = torch.cuda.Event()
@@ -626,10 +670,23 @@ class JpegStore:
         y0 >= y1 decodes nothing for the position; an entry kept as pixels is copied whole; `rows=None` is `decode`.  A `rows` of another
         shape is a ValueError and a bad id an IndexError, both before any launch.  Like `decode` it never waits, the statuses (of the
         lanes that ran; the files were judged in full by `add`) go to `check()`, and `workspace_limit` splits the call, by the bands'
-        dense coefficients."""
+        dense coefficients.
+
+        `rows` may also be a CUDA tensor on the store's device, (len(ids), 2) int32 — `FEARMultiTracker.search_rows()` returns one.
+        Its values are read ONLY BY KERNELS and may still be in flight on the current stream: the call does not synchronise and does not
+        copy them to the host.  They are clipped to [0, H] on the device (a negative y0 and y1 > H included), y0 >= y1 decodes nothing
+        for the position, and the result is the same list of private full-shape frames, rows [y0, y1) byte for byte `decode`'s, all
+        other rows unspecified.  The host cannot know the band, so this form runs `decode`'s plan (`plan_decode`: full grids, the
+        full-image layout of the dense coefficients and the planes, `workspace_limit` splitting the call by full-image coefficients,
+        each group taking its slice of `rows` by device indexing with indices the host knows); the work is saved in the kernels:
+        `fear_jpeg_huffman_indexed_rows_dev` runs only the lanes of the band's subsequences and `fear_jpeg_decode_u8_rows_dev` only the
+        band's blocks and the window's pixels, and a workgroup outside them returns after a few loads.  A CUDA tensor of another
+        shape, dtype or device is a ValueError before any launch (a CPU tensor is host rows, as any array)."""
         if rows is None:
             return self.decode(ids, check=check)
         ids = self._checked(ids)
+        if type(rows).__module__.split(".")[0] == "torch" and rows.is_cuda:         # (a CPU tensor is host rows, as before)
+            return self._decode_rows_device(ids, rows, check)
         rows = np.asarray(rows)
         if rows.shape != (ids.size, 2) or not np.issubdtype(rows.dtype, np.integer):
             raise ValueError(f"rows must be ({ids.size}, 2) integers, one [y0, y1) per id")
@@ -715,3 +772,19 @@ class JpegStore:
                 j = int(bad[0])
                 raise MalformedJPEG(f"item {int(positions[j])}: the device refused the resident scan of id {int(sids[j])} "
                                     f"with status {int(status[j])}")
+
+
+class StoreFrames:
+    """The frames of one sequence kept in a `JpegStore`: `store.decode([ids[t]])[0]` is frame t.  `SequenceValidator.run` takes it in
+    place of a sequence's frames and decodes, from the second frame on, only the rows the tracker's next search window reads."""
+
+    def __init__(self, store: JpegStore, ids) -> None:
+        self.store = store
+        self.ids = store._checked(ids)
+
+    def __len__(self) -> int:
+        return int(self.ids.size)
+
+    def __iter__(self):
+        for i in self.ids:
+            yield self.store.decode([int(i)])[0]

@@ -49,6 +49,35 @@ from .tracker import FEARTracker
 PLANAR_CROP_MAX_TARGETS = 32
 
 
+def search_rows_host(ctx, stream, n_streams: int, out_hw: int = 256) -> np.ndarray:
+    """`FEARMultiTracker.search_rows` in numpy (fear_tracker_rows): (n_streams, 2) int32, per stream the frame rows [y0, y1) that the
+    search crops of its targets sample, as one range; (0, 0) for a stream without a target.  `ctx` is (K, 4) context boxes x, y, w, h
+    and `stream` (K,) their streams.  The rule is the crop kernel's (crop_resize_normalize_kernel, `geometry.resize_bilinear_u8`): output
+    row d of a crop taps the box's rows clip(i, 0, h - 1) and clip(i + 1, 0, h - 1), i = floor(float32((d + 0.5) h / out_hw - 0.5)),
+    which move monotonically with d — so a crop taps y + (first tap of row 0) .. y + (second tap of row out_hw - 1).  For 1 <= h <=
+    out_hw, and on the identity and 2 x 2 paths, that is every row y .. y + h - 1; a strong reduction starts behind y and ends in front
+    of y + h - 1.  A degenerate box, h <= 0, has both taps pinned to h - 1 (the upper clip is applied last): the single row y + h - 1,
+    which lies above the box.  The rows are not clipped to the frame, and a target whose columns miss its frame counts all the same."""
+    ctx = np.asarray(ctx, dtype=np.int64).reshape(-1, 4)
+    stream = np.asarray(stream, dtype=np.int64).reshape(-1)
+    out = np.zeros((int(n_streams), 2), dtype=np.int32)
+    S = int(out_hw)
+    for s in range(int(n_streams)):
+        lo = hi = None
+        for x, y, w, h in ctx[stream == s]:
+            with np.errstate(divide="ignore"):
+                scale = np.float64(1.0) / (np.float64(S) / np.float64(h))
+            taps = []
+            for d in (0, S - 1):
+                i = int(np.floor(np.float32((np.float64(d) + 0.5) * scale - 0.5)))
+                taps += [min(max(i, 0), int(h) - 1), min(max(i + 1, 0), int(h) - 1)]
+            first, last = int(y) + min(taps), int(y) + max(taps) + 1
+            lo, hi = (first, last) if lo is None else (min(lo, first), max(hi, last))
+        if lo is not None and lo < hi:
+            out[s] = np.clip([lo, hi], -(1 << 30), 1 << 30)
+    return out
+
+
 class PendingBoxes:
     """The boxes of one `submit`, possibly still being computed: `result()` waits for that frame's copy only."""
 
@@ -275,6 +304,27 @@ class FEARMultiTracker:
         for f in frames:
             self._check_frame(f)
         return frames
+
+    def search_rows(self, n_streams: Optional[int] = None) -> torch.Tensor:
+        """(S, 2) int32 on the device: per stream the frame rows [y0, y1) that the NEXT `submit` reads — the union, as one range, of
+        the rows the search crop of every target on that stream samples (`search_rows_host` states the rule: for a context box
+        (x, y, w, h) the rows y + clip(i, 0, h - 1) of the crop's bilinear row table, which for 1 <= h <= instance_size are
+        y .. y + h - 1; the single row y + h - 1 for a degenerate box).  UNCLIPPED — `JpegStore.decode_rows` clips them to its
+        frames; a stream without targets gets (0, 0).  `n_streams` defaults to the highest stream with a target plus one.  One small
+        launch (`fear_tracker_rows`) over the state `add` and `fear_tracker_step` left on the device; it never waits for the GPU, so
+
+            rows   = tracker.search_rows()
+            frames = store.decode_rows(ids_t, rows)          # only the rows the tracker is about to read are decoded
+            boxes  = tracker.submit(frames)
+
+        runs without a synchronisation.  `add` still takes a fully decoded frame (it reads the frame's mean colour), and the host
+        path, whose state lives on the host, raises."""
+        if not self.device_path or not hasattr(self.net, "tracker_rows"):
+            raise RuntimeError("search_rows needs the device path (a model with the device entry points, device_crop and "
+                               "device_postprocess on): the host path keeps its state on the host")
+        if n_streams is None:
+            n_streams = int(self._stream.max()) + 1 if len(self._stream) else 0
+        return self.net.tracker_rows(self._ctx, self._fidx, int(n_streams), int(self.tracking_config["instance_size"]))
 
     def submit(self, images) -> PendingBoxes:
         """Track every target on its stream's frame (`images`: one frame, or a sequence indexed by stream).  On the device

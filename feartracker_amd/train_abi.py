@@ -105,6 +105,9 @@ TRAIN_SYMBOLS = {
     "fear_jpeg_index_build": ([_P, _i, _P, _P, _P, _P, _P, _i, _P], _i),
     "fear_jpeg_huffman_indexed": ([_P, _i, _P, _P, _P, _i, _P], _i),
     "fear_jpeg_huffman_indexed_rows": ([_P, _i, _P, _P, _P, _i, _P], _i),
+    # the band of rows taken from device memory (JpegStore.decode_rows with a device tensor)
+    "fear_jpeg_huffman_indexed_rows_dev": ([_P, _i, _P, _P, _P, _P, _i, _P], _i),
+    "fear_jpeg_decode_u8_rows_dev": ([_P, _i, _P, _P, _P, _sz, _P], _i),
     # the colour stage's members that are no lookup table (FearColourOp below)
     "fear_colour_u8": ([_P, _i, _i, _i, _P, _P, _P, _P], _i),
     # step metrics (metrics.TrainMetrics)
@@ -226,13 +229,15 @@ class FearJpegIndex(ctypes.Structure):
 
 
 class FearJpegIndexed(ctypes.Structure):
-    """include/fear_train.h: one image of a fear_jpeg_huffman_indexed or fear_jpeg_huffman_indexed_rows call (device pointers as integers)."""
+    """include/fear_train.h: one image of a fear_jpeg_huffman_indexed, fear_jpeg_huffman_indexed_rows or fear_jpeg_huffman_indexed_rows_dev
+    call (device pointers as integers)."""
     _fields_ = [("scan", ctypes.c_uint64), ("index", ctypes.c_uint64), ("sub_start", ctypes.c_uint64), ("coef_offset", ctypes.c_uint64),
                 ("n_sub", ctypes.c_uint32), ("sub0", ctypes.c_uint32), ("sub_count", ctypes.c_uint32), ("mcu_row0", ctypes.c_uint32),
-                ("mcu_rows", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+                ("mcu_rows", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("row_sub", ctypes.c_uint64)]
 
 
 assert ctypes.sizeof(FearJpegSubseq) == 16 and ctypes.sizeof(FearJpegIndex) == 32 and ctypes.sizeof(FearJpegIndexed) == 64
+assert FearJpegIndexed.row_sub.offset == 56
 assert ctypes.sizeof(FearJpegInfo) == 464 and FearJpegInfo.qt.offset == 80
 assert ctypes.sizeof(FearJpegHuff) == 1440 and ctypes.sizeof(FearJpegScan) == 8704 and FearJpegScan.dc.offset == 64
 assert ctypes.sizeof(FearJpegImage) == 448 and FearJpegImage.qt.offset == 64

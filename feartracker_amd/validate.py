@@ -12,6 +12,11 @@ Sequences are ragged: a sequence that has ended has its target removed, and its 
 added for the IoU: `submit` already lands every frame's boxes in pinned host memory, and `get_iou` on K integer boxes is host
 work of microseconds; the boxes of frame t are read after frame t + 1 has been submitted, so the device never idles on it.
 
+A sequence whose frames are JPEG files resident in a `JpegStore` is given as `StoreFrames(store, ids)`.  Its first frame is decoded
+whole (`add` reads the frame's mean colour); from then on each time step asks the tracker for the rows its next search windows read
+(`FEARMultiTracker.search_rows`, a device tensor) and decodes only those — one `store.decode_rows` call per step for the live streams,
+nothing waits for the GPU — with the same boxes as on frames decoded whole (tests/test_multi_tracker_store_gpu.py).
+
     val = SequenceValidator.from_training_state(train_net.state_dict())          # or SequenceValidator(FEARNetHIP(path))
     log = val.run([(frames, annotations, "got10k"), ...])
     schedule.step(log["valid/metrics/box_iou"])
@@ -59,12 +64,18 @@ class SequenceValidator:
 
     def run(self, sequences: Iterable[Tuple[Any, Any, str]]) -> Dict[str, Any]:
         """sequences: items (frames, annotations (T,4) xywh, dataset name); frames is indexable or iterable and yields what the
-        tracker takes (uint8 arrays, device tensors, `YUVFrame`s).  Returns the reduced values under the reference's logging keys
+        tracker takes (uint8 arrays, device tensors, `YUVFrame`s), or is a `StoreFrames` — then every sequence of the run must be one, of
+        the same store: a mix is a ValueError before any launch.  Returns the reduced values under the reference's logging keys
         — "valid/metrics/box_iou", "valid/metrics/<dataset>_box_iou", "valid/metrics/<dataset>_failure_rate" — and, under
         "sequences", per sequence {"dataset", "ious" (float64 array), "box_iou", "failure_rate"}."""
         items = list(sequences)
         if not items:
             raise ValueError("no validation sequence")
+        from .jpeg_store import StoreFrames
+        backed = [isinstance(frames, StoreFrames) for frames, _, _ in items]
+        store = items[0][0].store if all(backed) else None
+        if any(backed) and (store is None or any(frames.store is not store for frames, _, _ in items)):
+            raise ValueError("a run takes sequences kept in ONE JpegStore (StoreFrames of the same store), or none: not a mix")
         anns, counts, names, iters = [], [], [], []
         for frames, ann, name in items:
             ann = np.asarray(ann)
@@ -75,11 +86,14 @@ class SequenceValidator:
             anns.append(ann)
             counts.append(n)
             names.append(str(name))
-            iters.append(iter(frames))
+            if store is not None and len(frames) < n:
+                raise ValueError(f"sequence {len(iters)} has an annotation for frame {len(frames)} but no such frame")
+            iters.append(None if store is not None else iter(frames))
         mt = FEARMultiTracker(self.net, self._cuda_id, **self.tracking_config)
         current, ids = [], []
+        firsts = store.decode([int(frames.ids[0]) for frames, _, _ in items]) if store is not None else None
         for s, (it, ann) in enumerate(zip(iters, anns)):
-            frame = self._next(it, s, 0)
+            frame = firsts[s] if store is not None else self._next(it, s, 0)
             (i,) = mt.add(frame, list(map(int, ann[0])), stream=s)      # tracker.initialize(read_img(files[0]), list(map(int, ann[0])))
             current.append(frame)
             ids.append(i)
@@ -93,8 +107,16 @@ class SequenceValidator:
         waiting = None
         for t in range(1, max(counts)):
             live = [s for s, n in enumerate(counts) if t < n]
-            for s in live:
-                current[s] = self._next(iters[s], s, t)
+            if store is not None:                                      # only the rows the tracker is about to read; no wait
+                rows = mt.search_rows(len(items))
+                if len(live) < len(items):
+                    rows = rows.index_select(0, self._indices(tuple(live), rows.device))
+                band = store.decode_rows([int(items[s][0].ids[t]) for s in live], rows)
+                for k, s in enumerate(live):
+                    current[s] = band[k]
+            else:
+                for s in live:
+                    current[s] = self._next(iters[s], s, t)
             pending = mt.submit(current)
             if waiting is not None:
                 score(*waiting)                                        # frame t - 1, read behind frame t's submit
@@ -104,6 +126,13 @@ class SequenceValidator:
                 mt.remove(ended)
         score(*waiting)
         return self._reduce(names, ious)
+
+    def _indices(self, live: Tuple[int, ...], device) -> torch.Tensor:
+        """The live streams as a device index tensor, uploaded from pinned memory without waiting; kept while the set does not change."""
+        if getattr(self, "_live", (None, None))[0] != live:
+            pinned = torch.tensor(live, dtype=torch.int64).pin_memory()
+            self._live = (live, pinned.to(device, non_blocking=True), pinned)
+        return self._live[1]
 
     @staticmethod
     def _next(it, s: int, t: int):

@@ -176,6 +176,19 @@ int fear_tracker_step(fear_handle* h, const float* cls, const float* bbox, int n
                       double window_influence, double lr, int score_size, int total_stride, int instance_size,
                       double search_context, double* xywh, float* score, void* stream);
 
+/* The frame rows the NEXT fear_crop_normalize_frames launch over the same state will sample, per stream (FEARMultiTracker.search_rows;
+ * multi_tracker.search_rows_host restates it): rows[s] = [y0, y1), the union as one range, over the targets t with frame_idx[t] == s, of
+ * the rows crop t taps.  With the context box (x, y, w, h) and out_hw output rows those are y + i0(0) .. y + i1(out_hw - 1) of OpenCV's
+ * 8u INTER_LINEAR row table for h -> out_hw (the indices are clipped to 0 .. h - 1, so for h >= 1 the range lies inside y .. y + h - 1
+ * and is exactly that for h <= out_hw and for the identity and 2 x 2 paths; a strong reduction skips the box's first and last rows);
+ * a degenerate box, h <= 0, taps the single row y + h - 1.  The values are not clipped to any frame, and the columns play no part: a
+ * target whose columns miss its frame still counts.  A stream without a target gets (0, 0).  One launch, one wavefront per stream.
+ *   ctx_xywh  : (n, 4) int32, device    frame_idx : (n) int32, device    rows : (n_streams, 2) int32, device, out
+ * FEAR_ERR_SHAPE: n < 0, n_streams outside 0..65535, out_hw outside 1..4096; n_streams == 0 returns FEAR_OK without a launch;
+ * FEAR_ERR_NULL: a null rows, or a null ctx_xywh or frame_idx with n > 0.                                                        */
+int fear_tracker_rows(fear_handle* h, const int32_t* ctx_xywh, const int32_t* frame_idx, int n, int n_streams, int out_hw,
+                      int32_t* rows, void* stream);
+
 /* ---- engine options ------------------------------------------------------------------------- */
 #define FEAR_OPT_MAX_BATCH 1   /* crops processed per internal pass (workspace is sized for it)  */
 #define FEAR_OPT_PROFILE 2     /* 1: bracket kernel launches with hipEvents (fear_profile_*)     */

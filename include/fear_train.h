@@ -625,6 +625,18 @@ _Static_assert(sizeof(FearJpegImage) == 448, "FearJpegImage is 448 bytes");
 
 int fear_jpeg_decode_u8(const FearJpegImage* images, int n, const uint32_t* group_start, void* workspace, size_t workspace_bytes,
                         void* stream);
+/* fear_jpeg_decode_u8 for the pixel rows [y0, y1) of each image, taken from DEVICE memory: `rows_dev` holds n pairs of int32 that only
+ * the kernels read (they may still be in flight on `stream`), clipped there to [0, height]; y0 >= y1 stores nothing for the image.  The
+ * records, the table, the grids and the workspace are fear_jpeg_decode_u8's, of the whole images.  jpeg_decode_blocks_kernel skips a
+ * block whose MCU row lies outside the band a .. b), a = y0 / (8 v), b = ceil(y1 / (8 v)), one more on each side where v == 2 (the
+ * fancy upsampling reads a chroma row above and below), clipped to the image; a workgroup all of whose 32 blocks are skipped returns in
+ * front of its work.  jpeg_decode_merge_kernel stores the pixels of the rows [y0, y1) alone: their luma lies in the MCU rows of the
+ * band without its halo and the chroma rows they read in the band with it, so every plane byte that is read was written by this call,
+ * and the image keeps its true size, so the edge rules apply at the true edges.  The rows [y0, y1) of `out` are fear_jpeg_decode_u8's
+ * byte for byte when the coefficients of the band's blocks are; all other rows of `out` keep what they held.
+ * The checks are fear_jpeg_decode_u8's; a null rows_dev is FEAR_TRAIN_ERR_NULL.                                                       */
+int fear_jpeg_decode_u8_rows_dev(const FearJpegImage* images, int n, const uint32_t* group_start, const int32_t* rows_dev, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 size_t fear_jpeg_decode_workspace_bytes(const FearJpegInfo* infos, int n);
 
 /* ---- the Huffman stage on the device (jpeg_huffman.jpeg_entropy_parallel_host restates it in Python, step for
@@ -757,7 +769,23 @@ int fear_jpeg_dense_block_start(uint32_t* block_start, uint32_t total_blocks, vo
  * coef_offset, every position written by exactly one lane, nothing outside them.  Lanes that do not run judge nothing: status_dev[i] is
  * the verdict of the lanes that ran (an image with n_sub == 0 fails as above), and a band without rows or lanes leaves FEAR_TRAIN_OK.
  * The checks are fear_jpeg_huffman_indexed's, and FEAR_TRAIN_ERR_SHAPE for sub_count > 0 with sub0 + sub_count > n_sub, or
- * mcu_row0 + mcu_rows > FEAR_JPEG_MAX_SIDE / 8.  Two launches, no atomics, one barrier, plain vector stores.                          */
+ * mcu_row0 + mcu_rows > FEAR_JPEG_MAX_SIDE / 8.  Two launches, no atomics, one barrier, plain vector stores.
+ *
+ * fear_jpeg_huffman_indexed_rows_dev is the band of rows taken from DEVICE memory (JpegStore.decode_rows with a device tensor;
+ * jpeg_huffman.jpeg_entropy_rows_device_host restates it in Python): `rows_dev` holds n pairs of int32, the pixel rows [y0, y1) of
+ * image i at rows_dev[2 i], and only kernels read them — they may still be in flight on `stream` when the call is made.  The host does
+ * not know the band, so the grid, `table_dev` and coef_offset are fear_jpeg_huffman_indexed's: ceil(n_sub / 256) workgroups per image
+ * and the FULL-IMAGE dense layout.  Per image the kernel clips y0 and y1 to [0, 8 v mcus_y] (the rows of the MCU grid: the resident
+ * record does not hold the height; fear_jpeg_decode_u8_rows_dev, which does, clips to it), y0 >= y1 is the empty band; else the band is
+ * the MCU rows a .. b), a = y0 / (8 v), b = ceil(y1 / (8 v)), one more on each side where v == 2, clipped to mcus_y — the halo rule of
+ * JpegStore.decode_rows.  A lane runs only if its subsequence lies in row_sub[a] .. min(row_sub[b], n_sub - 1); `row_sub` of a record is
+ * the file's row table resident on the device, mcus_y + 1 values (jpeg_huffman.scan_row_sub).  A workgroup none of whose 256
+ * subsequences lies in that interval returns in front of its copy of the tables and its barrier: it costs a few loads.  A lane that
+ * runs decodes and judges as fear_jpeg_huffman_indexed's; a block of the band is stored at its FULL-IMAGE place, a block of another row
+ * is decoded, judged and not stored.  Every stored position is written by exactly one lane, nothing is written outside the image's
+ * 64 total_blocks values, all other positions keep what the buffer held, and every loop bound is independent of the data.  The checks
+ * are fear_jpeg_huffman_indexed's; a null rows_dev, or a null row_sub in a record, is FEAR_TRAIN_ERR_NULL, a row_sub not 4-byte
+ * aligned FEAR_TRAIN_ERR_SHAPE.                                                                                                      */
 typedef struct FearJpegSubseq {
     uint32_t p;                  /* the true entry bit position in the segment, up to 30 bits behind the subsequence's first: < 2^27 + 31 */
     uint32_t begun;              /* blocks begun in the segment in front of the subsequence                              */
@@ -783,16 +811,17 @@ typedef struct FearJpegIndexed {
     uint32_t n_sub;
     uint32_t sub0, sub_count;        /* fear_jpeg_huffman_indexed_rows alone: the subsequences that get a lane, sub0 .. sub0 + sub_count) */
     uint32_t mcu_row0, mcu_rows;     /* fear_jpeg_huffman_indexed_rows alone: the band of MCU rows whose blocks are stored             */
-    uint32_t reserved[3];
+    uint32_t reserved;
+    const uint32_t* row_sub;         /* fear_jpeg_huffman_indexed_rows_dev alone: device, the file's row table, mcus_y + 1 values; offset 56 */
 } FearJpegIndexed;
 #ifdef __cplusplus
 static_assert(sizeof(FearJpegSubseq) == 16, "FearJpegSubseq is 16 bytes");
 static_assert(sizeof(FearJpegIndex) == 32, "FearJpegIndex is 32 bytes");
-static_assert(sizeof(FearJpegIndexed) == 64, "FearJpegIndexed is 64 bytes");
+static_assert(sizeof(FearJpegIndexed) == 64 && offsetof(FearJpegIndexed, row_sub) == 56, "FearJpegIndexed is 64 bytes, row_sub at 56");
 #else
 _Static_assert(sizeof(FearJpegSubseq) == 16, "FearJpegSubseq is 16 bytes");
 _Static_assert(sizeof(FearJpegIndex) == 32, "FearJpegIndex is 32 bytes");
-_Static_assert(sizeof(FearJpegIndexed) == 64, "FearJpegIndexed is 64 bytes");
+_Static_assert(sizeof(FearJpegIndexed) == 64 && offsetof(FearJpegIndexed, row_sub) == 56, "FearJpegIndexed is 64 bytes, row_sub at 56");
 #endif
 
 int fear_jpeg_sub_start(const uint32_t* seg_start, uint32_t n_seg, uint32_t n_bytes, int subsequence_bytes, uint32_t* sub_start,
@@ -803,6 +832,8 @@ int fear_jpeg_huffman_indexed(const FearJpegIndexed* images, int n, const void* 
                               int subsequence_bytes, void* stream);
 int fear_jpeg_huffman_indexed_rows(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
                                    int subsequence_bytes, void* stream);
+int fear_jpeg_huffman_indexed_rows_dev(const FearJpegIndexed* images, int n, const void* table_dev, const int32_t* rows_dev, int16_t* coef,
+                                       int32_t* status_dev, int subsequence_bytes, void* stream);
 
 /* ---- the colour stage's members that are no lookup table: Equalize, HueSaturationValue, ColorJitter and Emboss of the reference's
  * p = 0.5 OneOf (model_training/dataset/aug.py:35-48), on uint8 HWC crops between fear_train_pairs_u8 (tone, then the lookup-table

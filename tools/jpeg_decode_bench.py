@@ -50,7 +50,21 @@ of H with seeded random positions (one window per file), every shape warmed firs
                            than decode's own minimum-to-maximum spread; quarter_band_faster: at 0.25 the slowest decode_rows run is below
                            the fastest decode run
   borders_ms, host_ms_per_call      store.borders(ids) between HIP events; decode_rows at 0.25 until it returns (it does not wait)
-Before anything is timed the rows asked for are compared with `decode`'s at every band height (`rows_equal_decode`)."""
+Before anything is timed the rows asked for are compared with `decode`'s at every band height (`rows_equal_decode`).
+
+    python tools/jpeg_decode_bench.py --dir DIR --store --rows-device   # needs the GPU: writes profiles/jpeg_rows_device_bench.json
+
+--store --rows-device measures, in ONE run on the same 256 files and the same seeded windows as --rows, `decode` (the baseline),
+`decode_rows` with the rows on the host (planned on the host) and `decode_rows` with the rows in a device tensor (planned on the device:
+full grids, workgroups outside the band return early), medians of 5 with minimum and maximum:
+  decode_ms_per_call, decode_rows_host_ms_per_call, decode_rows_device_ms_per_call      a host clock around work that ends in a synchronise
+  stage_ms                 between HIP events: fear_jpeg_huffman_indexed and fear_jpeg_decode_u8 of `decode`, and by band height
+                           fear_jpeg_huffman_indexed_rows_dev and fear_jpeg_decode_u8_rows_dev alone
+  conditions               quarter_band_faster: at 0.25 the slowest device-planned run is below the fastest decode run;
+                           full_band_excess_ms / full_band_ratio: at 1.0, the device-planned median over decode's (the idle exits and the
+                           full workspace)
+  host_ms_per_call         decode_rows with device rows at 0.25 until it returns (it does not wait)
+Before anything is timed both forms' rows are compared with `decode`'s at every band height (`rows_equal_decode`)."""
 import argparse
 import glob
 import io
@@ -381,6 +395,102 @@ def rows_bench(torch, blobs, out):
     print(json.dumps(res))
 
 
+def rows_device_bench(torch, blobs, out):
+    """decode, host-planned decode_rows and device-planned decode_rows in one run."""
+    from feartracker_amd import JpegStore
+    from feartracker_amd import train_abi as abi
+    n, repeats, fractions = len(blobs), 5, (1.0, 0.5, 0.25)
+    res = {"files": n, "width": W, "height": H, "quality": QUALITY, "file_bytes_per_frame": sum(map(len, blobs)) / n,
+           "cpus_available": len(os.sched_getaffinity(0)), "repeats": repeats}
+    store = JpegStore(device=0, threads=16, workspace_limit=2 << 30)      # (one group, as --rows: the stage replays replay the whole call)
+    ids = store.add(blobs)[np.random.default_rng(17).permutation(n)]
+    res["subsequence_bytes"], res["workspace_limit"] = store.subsequence_bytes, store.workspace_limit
+    rng = np.random.default_rng(29)                                       # the windows of --rows
+    heights = store.shape(ids)[:, 0].astype(np.int64)
+    windows, on_device = {}, {}
+    for f in fractions:
+        high = np.maximum((heights * f).astype(np.int64), 1)
+        y0 = rng.integers(0, heights - high + 1)
+        windows[f] = np.stack([y0, y0 + high], axis=1)
+        on_device[f] = torch.from_numpy(windows[f].astype(np.int32)).cuda()
+
+    def whole():
+        frames = store.decode(ids, check=True)
+        torch.cuda.synchronize()
+        return frames
+
+    def hosted(f):
+        frames = store.decode_rows(ids, windows[f], check=True)
+        torch.cuda.synchronize()
+        return frames
+
+    def device(f):
+        frames = store.decode_rows(ids, on_device[f], check=True)
+        torch.cuda.synchronize()
+        return frames
+
+    def captured_calls(fn):
+        captured, real = {}, abi.launch
+
+        def spy(lib, called, *a):
+            captured[called] = a
+            return real(lib, called, *a)
+        abi.launch = spy
+        try:
+            keep = fn()
+        finally:
+            abi.launch = real
+        torch.cuda.synchronize()
+        return keep, captured, store._records
+
+    full = whole()                                                       # every shape warm, and the same rows before anything is timed
+    for f in fractions:
+        for form in (hosted, device):
+            for x, y, (a, b) in zip(form(f), full, windows[f].tolist()):
+                assert torch.equal(x[a:b], y[a:b]), f"{form.__name__} decode_rows differs from decode at band height {f}"
+    del full
+    res["rows_equal_decode"] = True
+    a = run_seconds(whole, repeats)
+    res["decode_ms_per_call"] = spread(a, 1e3)
+    res["decode_rows_host_ms_per_call"], res["decode_rows_device_ms_per_call"], timed = {}, {}, {}
+    for f in fractions:
+        rows_asked = int(windows[f][0, 1] - windows[f][0, 0])
+        res["decode_rows_host_ms_per_call"][str(f)] = dict(spread(run_seconds(lambda: hosted(f), repeats), 1e3), rows_asked=rows_asked)
+        timed[f] = run_seconds(lambda: device(f), repeats)
+        res["decode_rows_device_ms_per_call"][str(f)] = dict(spread(timed[f], 1e3), rows_asked=rows_asked)
+    lib, res["stage_ms"] = store._lib, {}
+    keep, calls, records = captured_calls(whole)
+    for name in ("fear_jpeg_huffman_indexed", "fear_jpeg_decode_u8"):
+        res["stage_ms"][name] = spread(event_ms(torch, lambda: getattr(lib, name)(*calls[name]), repeats))
+    del keep
+    for f in fractions:
+        keep, calls, records = captured_calls(lambda: device(f))        # (the rows are a slice of on_device[f]: alive)
+        for name in ("fear_jpeg_huffman_indexed_rows_dev", "fear_jpeg_decode_u8_rows_dev"):
+            res["stage_ms"][f"{name} {f}"] = spread(event_ms(torch, lambda: getattr(lib, name)(*calls[name]), repeats))
+        del keep
+    med = statistics.median
+    res["conditions"] = {
+        "quarter_band_faster": bool(max(timed[0.25]) < min(a)),
+        "full_band_excess_ms": round(1e3 * (med(timed[1.0]) - med(a)), 4),
+        "full_band_ratio": round(med(timed[1.0]) / med(a), 4),
+    }
+
+    def host_only():
+        t0 = time.perf_counter()
+        frames = store.decode_rows(ids, on_device[0.25])
+        t = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        store.check()
+        return t, frames
+    host_only()
+    res["host_ms_per_call"] = spread([host_only()[0] for _ in range(repeats)], 1e3)
+    store.close()
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dir", required=True)
@@ -390,10 +500,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=0, help="no GPU: the model's synchronisation rounds on the first N files, merged into --out")
     ap.add_argument("--store", action="store_true", help="the resident store against the device decoder, to profiles/jpeg_store_bench.json")
     ap.add_argument("--rows", action="store_true", help="with --store: decode_rows against decode, to profiles/jpeg_rows_bench.json")
+    ap.add_argument("--rows-device", action="store_true",
+                    help="with --store: decode_rows with the rows on the device against the host-planned form and decode, to "
+                         "profiles/jpeg_rows_device_bench.json")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        name = "jpeg_decode_bench.json" if not args.store else ("jpeg_rows_bench.json" if args.rows else "jpeg_store_bench.json")
+        name = "jpeg_decode_bench.json" if not args.store else ("jpeg_rows_device_bench.json" if args.rows_device else
+                                                                "jpeg_rows_bench.json" if args.rows else "jpeg_store_bench.json")
         args.out = os.path.join(ROOT, "profiles", name)
     if args.make:
         return make(args.dir)
@@ -407,6 +521,8 @@ def main():
         print(json.dumps(res["device_entropy"]["rounds_per_sequence"]))
         return
     import torch
+    if args.store and args.rows_device:
+        return rows_device_bench(torch, blobs, args.out)
     if args.store and args.rows:
         return rows_bench(torch, blobs, args.out)
     if args.store:

@@ -17,6 +17,16 @@ per frame, then the RGB path.  It then times the crop launches alone at each K w
 the RGB frame, fear_crop_normalize_planar on the NV12 and I420 frames, fear_yuv_to_rgb of one frame.  Default output
 profiles/multi_track_yuv_bench.json (with --out: that file).
        python tools/multi_track_bench.py --format rgb,nv12,i420 --device-frames [--ks 1,16,64,256] [--frames 40]
+
+Frames kept in a JpegStore ("Rows from the device"): `--store DIR` takes the JPEG files of DIR (the 256 files
+of tools/jpeg_decode_bench.py --make) and tracks S streams with one target each, S = 1, 16, 64, stream s reading every S-th file.  In ONE
+run, medians of 5 with minimum and maximum, it reports frames per second (streams x steps / time, pipelined: a step's boxes are read
+behind the next step's submit) of
+  decode_submit     store.decode(ids) + submit: whole frames, the baseline
+  rows_submit       search_rows + store.decode_rows(ids, rows) + submit: only the rows the tracker is about to read
+and `band_rows_mean`, the mean number of frame rows per stream and step that search_rows asks for (clipped to the frame).  The boxes of
+both loops are compared before anything is timed.  Default output profiles/multi_track_store_bench.json.
+       python tools/multi_track_bench.py --store DIR [--ks 1,16,64] [--frames 40]
 """
 import argparse
 import json
@@ -149,9 +159,86 @@ def yuv_main(args):
         json.dump(res, fh, indent=1)
 
 
+def store_main(args):
+    """--store: decode + submit against search_rows + decode_rows + submit on frames kept in a JpegStore."""
+    import glob
+    import statistics
+    from feartracker_amd import JpegStore
+    blobs = [open(p, "rb").read() for p in sorted(glob.glob(os.path.join(args.store, "*.jpg")))]
+    assert blobs, "no .jpg files in --store DIR"
+    net = FEARNetHIP(DEFAULT_WEIGHTS, device=0, max_batch=args.max_batch)
+    cfg, repeats, steps = DEFAULT_TRACKING_CONFIG, 5, args.frames
+    store = JpegStore(device=0, threads=16)
+    all_ids = store.add(blobs)
+    (h, w), n = store.shape(all_ids[:1])[0].tolist(), len(all_ids)
+    res = {"files": n, "frame_shape": [h, w, 3], "steps_timed": steps, "repeats": repeats, "max_batch": args.max_batch,
+           "device": torch.cuda.get_device_name(0), "subsequence_bytes": store.subsequence_bytes, "per_streams": []}
+
+    def spread(values, digits=1):
+        return {"median": round(statistics.median(values), digits), "min": round(min(values), digits), "max": round(max(values), digits)}
+
+    for S in (int(v) for v in args.ks.split(",")):
+        ids_at = lambda t: all_ids[(np.arange(S) + S * t) % n]               # stream s reads file s, s + S, s + 2 S, ...
+        boxes = target_boxes(S + 6, h, w)[6:]                                # one target per stream, inside the frame
+
+        def fresh():
+            mt = FEARMultiTracker(net, cuda_id=0, **cfg)
+            first = store.decode(ids_at(0))
+            for s in range(S):
+                mt.add(first[s], boxes[s], stream=s)
+            return mt
+
+        def loop(mt, rows_form, keep_rows=None, keep_boxes=None):
+            """`steps` pipelined steps; seconds."""
+            pending = None
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for t in range(1, steps + 1):
+                if rows_form:
+                    rows = mt.search_rows(S)
+                    frames = store.decode_rows(ids_at(t), rows)
+                    if keep_rows is not None:
+                        keep_rows.append(rows)
+                else:
+                    frames = store.decode(ids_at(t))
+                nxt = mt.submit(frames)
+                if pending is not None:
+                    got = pending.result()
+                    if keep_boxes is not None:
+                        keep_boxes.append(got)
+                pending = nxt
+            got = pending.result()
+            if keep_boxes is not None:
+                keep_boxes.append(got)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+
+        # warm, and the same boxes from both loops before anything is timed
+        rows_seen, boxes_a, boxes_b = [], [], []
+        loop(fresh(), False, keep_boxes=boxes_a)
+        loop(fresh(), True, keep_rows=rows_seen, keep_boxes=boxes_b)
+        store.check()
+        assert all(np.array_equal(x[i], y[i]) for x, y in zip(boxes_a, boxes_b) for i in x), "the two loops track differently"
+        band = torch.stack(rows_seen).clamp(0, h).cpu().numpy()
+        row = {"streams": S, "boxes_equal": True, "band_rows_mean": round(float((band[..., 1] - band[..., 0]).clip(min=0).mean()), 1)}
+        a = [loop(fresh(), False) for _ in range(repeats)]
+        b = [loop(fresh(), True) for _ in range(repeats)]
+        row["decode_submit_fps"] = spread([S * steps / t for t in a])
+        row["rows_submit_fps"] = spread([S * steps / t for t in b])
+        row["decode_submit_ms_per_step"] = spread([1e3 * t / steps for t in a], 4)
+        row["rows_submit_ms_per_step"] = spread([1e3 * t / steps for t in b], 4)
+        row["rows_faster"] = bool(max(b) < min(a))
+        res["per_streams"].append(row)
+        print(json.dumps(row), flush=True)
+    store.close()
+    out = args.out or os.path.join(ROOT, "profiles", "multi_track_store_bench.json")
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--ks", default="1,16,64,256,1024")
+    ap.add_argument("--ks", default="")
     ap.add_argument("--frames", type=int, default=40)
     ap.add_argument("--max-batch", type=int, default=256)
     ap.add_argument("--no-singles", action="store_true")
@@ -159,7 +246,11 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--format", default="", help="rgb,nv12,i420: time video frames (see the module docstring)")
     ap.add_argument("--device-frames", action="store_true", help="with --format: device frames too")
+    ap.add_argument("--store", default="", help="a directory of JPEG files: track on frames kept in a JpegStore (see the module docstring)")
     args = ap.parse_args()
+    args.ks = args.ks or ("1,16,64" if args.store else "1,16,64,256,1024")
+    if args.store:
+        return store_main(args)
     if args.format:
         return yuv_main(args)
     sync = torch.cuda.synchronize
