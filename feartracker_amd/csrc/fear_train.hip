@@ -1598,6 +1598,32 @@ struct WgradCall {
     const BnbIn* bn;                                      // optional: dY' = the BatchNorm backward of dY, formed on load
     const StemIn* stem;                                   // optional: X' = the stem's im2col rows of an NCHW image
 };
+// Which kernel one such problem takes, its output tiles and its row slices — from the shapes and from what the operands carry (stem: X'
+// gathered from the image; dy_masked: a BatchNorm backward on dY with a ReLU mask; dy_lin: one without its raw tensor, BnbIn.E = null):
+// wgrad_impl launches by it, the plan queries (fear_irb_plan_info, fear_pwbn_plan_info) report it.
+struct WgradLaunch { bool swapped, lds_tile; int n_tiles, k_tiles; WgradPlan plan; };
+static WgradLaunch wgrad_launch_plan(long M, int K, int N, int crops, bool stem, bool dy_masked, bool dy_lin, size_t ws_bytes) {
+    WgradLaunch w{};
+    // a narrow dY against a wide X (the projections of the large maps): the operands trade places in pw_wgrad_smallk_kernel<., 2>
+    w.swapped = crops == 1 && N <= 32 && K > 32 && !stem && !dy_masked && !dy_lin;
+    // 128 x 128 tiles with the rows staged through LDS (wgrad_lds_kernel, fear_train_gemm.h) where both sides are wide enough for
+    // the sharing to matter and the launch is one problem, not a batch of per-crop ones
+    // (launches of a few thousand rows are a handful of stages per workgroup: the staged kernel's prologue and its two
+    //  barriers-per-stage floor — 29 us measured — lose against the 14 us of the register-only kernel there)
+    w.lds_tile = !w.swapped && crops == 1 && K > 32 && N >= 32 && M >= 16384;
+    w.n_tiles = (N + 63) / 64; w.k_tiles = (K + 63) / 64;
+    if (w.lds_tile) { w.n_tiles = (N + 127) / 128; w.k_tiles = (K + 127) / 128; }
+    if (w.swapped) { w.n_tiles = (K + 63) / 64; w.k_tiles = 1; }
+    // (per-crop problems are one slice each; one problem is cut by wgrad_plan)
+    // at most 256 slices — 1 024 where the partial is small (N * K <= 8 192: the stem and the 16-32-channel layers of the
+    // 128 x 128 / 64 x 64 maps) or the operands are swapped: those layers have millions of rows and ONE or two output tiles, 256
+    // workgroups streamed them at 1.1 TB/s (the stem's weight gradient: 425 us for 500 MB)
+    w.plan = crops > 1 ? WgradPlan{M, 1}
+                       : wgrad_plan(M, K <= 32 ? w.n_tiles : (long)w.n_tiles * w.k_tiles, (size_t)N * K,
+                                    w.swapped || (long)N * K <= 8192 ? 1024 : 256, ws_bytes);
+    return w;
+}
+
 static int wgrad_impl(const WgradCall& c) {
     const long M = c.M;
     const int K = c.K, N = c.N, crops = c.crops;
@@ -1615,26 +1641,11 @@ static int wgrad_impl(const WgradCall& c) {
         a.bn = *bn;
     }
     a.dy_crop_stride = c.dy_crop_stride; a.x_crop_stride = c.x_crop_stride;
-    // a narrow dY against a wide X (the projections of the large maps): the operands trade places in pw_wgrad_smallk_kernel<., 2>
-    const bool swapped = crops == 1 && N <= 32 && K > 32 && !stem && !(bn && bn->mask_a) && (!bn || bn->E);
-    // 128 x 128 tiles with the rows staged through LDS (wgrad_lds_kernel, fear_train_gemm.h) where both sides are wide enough for
-    // the sharing to matter and the launch is one problem, not a batch of per-crop ones
-    // (launches of a few thousand rows are a handful of stages per workgroup: the staged kernel's prologue and its two
-    //  barriers-per-stage floor — 29 us measured — lose against the 14 us of the register-only kernel there)
-    const bool lds_tile = !swapped && crops == 1 && K > 32 && N >= 32 && M >= 16384;
-    a.n_tiles = (N + 63) / 64; a.k_tiles = (K + 63) / 64;
-    if (lds_tile) { a.n_tiles = (N + 127) / 128; a.k_tiles = (K + 127) / 128; }
-    if (swapped) {
-        a.dY = c.x; a.lddy = c.ldx; a.N = K; a.X = c.dy; a.ldx = c.lddy; a.K = N;
-        a.n_tiles = (K + 63) / 64; a.k_tiles = 1;
-    }
-    // (per-crop problems are one slice each; one problem is cut by wgrad_plan)
-    // at most 256 slices — 1 024 where the partial is small (N * K <= 8 192: the stem and the 16-32-channel layers of the
-    // 128 x 128 / 64 x 64 maps) or the operands are swapped: those layers have millions of rows and ONE or two output tiles, 256
-    // workgroups streamed them at 1.1 TB/s (the stem's weight gradient: 425 us for 500 MB)
-    const WgradPlan plan = crops > 1 ? WgradPlan{M, 1}
-                                     : wgrad_plan(M, K <= 32 ? a.n_tiles : (long)a.n_tiles * a.k_tiles, (size_t)N * K,
-                                                  swapped || (long)N * K <= 8192 ? 1024 : 256, workspace ? ws_bytes : 0);
+    const WgradLaunch wl = wgrad_launch_plan(M, K, N, crops, stem != nullptr, bn && bn->mask_a, bn && !bn->E, workspace ? ws_bytes : 0);
+    const bool swapped = wl.swapped, lds_tile = wl.lds_tile;
+    a.n_tiles = wl.n_tiles; a.k_tiles = wl.k_tiles;
+    if (swapped) { a.dY = c.x; a.lddy = c.ldx; a.N = K; a.X = c.dy; a.ldx = c.lddy; a.K = N; }
+    const WgradPlan plan = wl.plan;
     a.rows_per_slice = plan.rows_per_slice;
     const int slices = plan.slices;
     const size_t need = (size_t)slices * crops * N * K * sizeof(float);

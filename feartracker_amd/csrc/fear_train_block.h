@@ -78,7 +78,9 @@ int dw_bwd_sq(int C) { return C >= 64 ? 8 : 4; }
 struct DwGeom {
     int sq, nslab, max_wps;
     bool small_map;
-    int ts, tiles_x, tiles_y, wgs_per_slab;
+    int ts, tiles_x, tiles_y, n_items, wgs_per_slab;      // (n_items = B * tiles_x * tiles_y)
+    // the most tiles one workgroup walks (items slot, slot + wgs_per_slab, ...)
+    int items_per_wg() const { return wgs_per_slab ? (n_items + wgs_per_slab - 1) / wgs_per_slab : 0; }
     dim3 grid() const { return dim3((unsigned)(wgs_per_slab * nslab)); }
 };
 DwGeom dw_geom(int cexp, int k, int stride, bool expand, int B, int H, int W, bool backward) {
@@ -90,7 +92,8 @@ DwGeom dw_geom(int cexp, int k, int stride, bool expand, int B, int H, int W, bo
     g.small_map = k == 5 && stride == 1 && g.sq == 8 && h <= 8 && w <= 8 && (expand || !backward);
     g.ts = g.small_map || (!backward && stride == 2) ? 8 : 16;
     g.tiles_x = (w + g.ts - 1) / g.ts; g.tiles_y = (h + g.ts - 1) / g.ts;
-    g.wgs_per_slab = dw_bwd_wgs_per_slab(B * g.tiles_x * g.tiles_y, g.nslab);
+    g.n_items = B * g.tiles_x * g.tiles_y;
+    g.wgs_per_slab = dw_bwd_wgs_per_slab(g.n_items, g.nslab);
     return g;
 }
 DwGeom dw_slabs(int cexp) { return dw_geom(cexp, 3, 1, false, 0, 0, 0, false); }      // sq, nslab, max_wps only
@@ -223,6 +226,18 @@ dim3 stat_grid(long M, int K, int N, int* nt, int* row_tiles) {
     return g;
 }
 
+// Which kernel a row-tiled pointwise GEMM of the block operators takes, and the first generation's grid: with a statistics epilogue
+// (`stats`: the forward producers, the masked gradient) stat_grid's, else dgrad_grid's.  pw_forward_unit and launch_bnb_gemm launch by
+// it, the plan queries report it.
+struct PwGemmPlan { bool lds; int nt, row_tiles; dim3 grid; };
+PwGemmPlan pw_gemm_plan(long M, int K, int N, bool stats) {
+    PwGemmPlan p{};
+    p.nt = 1; p.row_tiles = 1;
+    p.lds = gemm_lds_applies(M, K, N);      // few row blocks: the LDS-staged, pipelined GEMM (fear_train_gemm.h), same epilogue
+    if (!p.lds) p.grid = stats ? stat_grid(M, K, N, &p.nt, &p.row_tiles) : dgrad_grid(M, K, N, &p.nt);
+    return p;
+}
+
 template <int KS, int S>
 void launch_dw_fwd_ks(const DwFwdArgs& a, int sq, dim3 grid, hipStream_t s) {
     if (sq == 8) hipLaunchKernelGGL((dw_fwd_kernel<KS, S, 8>), grid, dim3(256), 0, s, a);
@@ -234,7 +249,8 @@ void launch_dw_fwd_ks(const DwFwdArgs& a, int sq, dim3 grid, hipStream_t s) {
                      const float* beta, float* vec, float* rm, float* rv, double momentum, double eps, double* col, hipStream_t s,
                      const float* mean_shift = nullptr) {
     int blocks = 0;
-    if (gemm_lds_applies(M, K, N)) {      // few row blocks: the LDS-staged, pipelined GEMM (fear_train_gemm.h), same epilogue
+    const PwGemmPlan plan = pw_gemm_plan(M, K, N, true);
+    if (plan.lds) {
         GemmArgs g{};
         g.X = x; g.ldx = ldx; g.W = w; g.Y = y; g.ldy = N; g.M = (int)M; g.K = K; g.N = N; g.partial = col;
         if (in_vec) { g.in.a = in_vec + 2 * K; g.in.b = in_vec + 3 * K; g.in.relu = in_relu; }
@@ -244,10 +260,9 @@ void launch_dw_fwd_ks(const DwFwdArgs& a, int sq, dim3 grid, hipStream_t s) {
         a.X = x; a.ldx = ldx; a.W = w; a.Y = y; a.ldy = N; a.M = (int)M; a.K = K; a.N = N;
         if (in_vec) { a.in.a = in_vec + 2 * K; a.in.b = in_vec + 3 * K; a.in.relu = in_relu; }
         a.partial = col;
-        int nt = 1;
-        const dim3 grid = stat_grid(M, K, N, &nt, &a.row_tiles);
-        launch_pw_stat(a, grid, nt, s);
-        blocks = (int)grid.x;
+        a.row_tiles = plan.row_tiles;
+        launch_pw_stat(a, plan.grid, plan.nt, s);
+        blocks = (int)plan.grid.x;
     }
     return finalize_forward(col, blocks, N, (double)M, gamma, beta, vec, rm, rv, momentum, eps, s, mean_shift);
 }
@@ -352,16 +367,25 @@ bool irb_virtual_shape(const FearIrbBlock* b) {
     return b->expand && b->cin >= 16 && b->cin <= 32 && b->stride == 2 && b->cexp >= 64 && b->cexp % 16 == 0 && !(b->flags & FEAR_IRB_NO_LINEAR_BN1);
 }
 bool irb_virtual(const FearIrbBlock* b) { return (b->flags & FEAR_IRB_VIRTUAL_E) != 0; }
+// BN1's backward without its input (the E-free form, see fear_irb_train_backward): where it applies and pays, or is asked for
+// (cexp % 16: a GEMM stage of 16 reduction columns must not straddle g1 and x.)  Always true for a virtual expansion: irb_virtual_shape.
+bool irb_lin(const FearIrbBlock* b) {
+    return b->expand && b->cexp % 16 == 0 && b->cin <= 128 && !(b->flags & FEAR_IRB_NO_LINEAR_BN1) && (b->cin <= 32 || (b->flags & FEAR_IRB_LINEAR_BN1));
+}
 
 // a virtual expansion's kernels by (kernel size, NC = 1 or 2 chunks of 16 input channels): the {3, 5} x {1, 2} of dispatch_ks's (k, stride)
 template <class F>
 void dispatch_k_nc(int k, int cin, F&& f) { dispatch_ks(k, cin <= 16 ? 1 : 2, f); }
 
+// rows per gram_kernel workgroup: 512 workgroups (one round), in whole steps of 128 rows
+long gram_rows_per_wg(long rows) {
+    const long rpw = (rows + 511) / 512;
+    return (rpw + 127) / 128 * 128;
+}
 // G = x^T x and the column sums of x (cin <= 32) in one pass: gram_kernel's per-workgroup partials in `wg`, their fixed-order sum
 // in `out` as [KP][KP] | [KP].  Returns the row pitch KP = 16 or 32, or FEAR_TRAIN_ERR_WORKSPACE before anything is launched.
 int launch_gram(const float* x, long rows, int cin, float* wg, size_t wg_bytes, float* out, hipStream_t s) {
-    long rpw = (rows + 511) / 512;      // (512 workgroups: one round)
-    rpw = (rpw + 127) / 128 * 128;
+    const long rpw = gram_rows_per_wg(rows);
     const int wgs = (int)((rows + rpw - 1) / rpw);
     const int nc = cin > 16 ? 2 : 1, kp = 16 * nc, per = kp * kp + kp;
     if ((size_t)wgs * per * sizeof(float) > wg_bytes) return FEAR_TRAIN_ERR_WORKSPACE;
@@ -386,8 +410,11 @@ struct BnbGemm {
     const float* D; int ldd; const float* dvec; double* partial; size_t partial_bytes;
     float* p3;
 };
+// (the masked-gradient pass has room for the projection's weight gradient: every column tile in one pass, at most 2 048 partials)
+bool w3g_fits(const PwGemmPlan& p, int N) { return !p.lds && p.grid.y == 1 && p.nt == (N + 15) / 16 && p.grid.x <= 2048; }
 int launch_bnb_gemm(const BnbGemm& d, hipStream_t s, int* p3_rows = nullptr) {
-    if (gemm_lds_applies(d.M, d.K, d.N)) {
+    const PwGemmPlan plan = pw_gemm_plan(d.M, d.K, d.N, d.D != nullptr);
+    if (plan.lds) {
         GemmArgs g{};
         g.X = d.X; g.ldx = d.ldx; g.bn = d.bn; g.W = d.W; g.X2 = d.X2; g.ldx2 = d.ldx2; g.K1 = d.K1; g.R = d.R; g.ldr = d.ldr; g.Y = d.Y; g.ldy = d.ldy;
         g.D = d.D; g.ldd = d.ldd; g.dvec = d.dvec; g.partial = d.partial; g.M = (int)d.M; g.K = d.K; g.N = d.N;
@@ -402,15 +429,16 @@ int launch_bnb_gemm(const BnbGemm& d, hipStream_t s, int* p3_rows = nullptr) {
     PwBwdArgs a{};
     a.G = d.X; a.ldg = d.ldx; a.bn = d.bn; a.W = d.W; a.X2 = d.X2; a.ldx2 = d.ldx2; a.K1 = d.K1; a.R = d.R; a.ldr = d.ldr; a.Y = d.Y; a.ldy = d.ldy;
     a.D = d.D; a.ldd = d.ldd; a.dvec = d.dvec; a.partial = d.partial; a.M = (int)d.M; a.Kred = d.K; a.Nout = d.N;
-    int nt = 1;
+    const int nt = plan.nt;
+    const dim3 grid = plan.grid;
     if (!d.D) {
-        launch_pw_bwd<false>(a, dgrad_grid(d.M, d.K, d.N, &nt), nt, s);
+        launch_pw_bwd<false>(a, grid, nt, s);
         return 0;
     }
-    const dim3 grid = stat_grid(d.M, d.K, d.N, &nt, &a.row_tiles);
+    a.row_tiles = plan.row_tiles;
     if ((size_t)grid.x * 2 * d.N * sizeof(double) > d.partial_bytes) return FEAR_TRAIN_ERR_WORKSPACE;
     // the narrow blocks (16 / 24 channels throughout, the 128 x 128 / 64 x 64 maps): the projection's weight gradient in the same pass
-    if (d.p3 && p3_rows && grid.y == 1 && nt == (d.N + 15) / 16 && grid.x <= 2048) {
+    if (d.p3 && p3_rows && w3g_fits(plan, d.N)) {
         a.p3 = d.p3; *p3_rows = (int)grid.x;
         hipLaunchKernelGGL((nt == 1 ? pw_bwd_kernel<1, true, true> : pw_bwd_kernel<2, true, true>), grid, dim3(256), 0, s, a);
     } else {
@@ -427,6 +455,31 @@ void launch_bn_act(const float* raw, const float* residual, float* out, const fl
     k.M = M; k.C = C; k.ldx = ldx; k.ldr = ldr; k.ldy = ldy;
     const long n4 = M * (C / 4);
     hipLaunchKernelGGL(bn_act_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, k);
+}
+
+// ---- the plan queries (fear_irb_plan_info, fear_pwbn_plan_info): the helpers above, asked what they would launch
+FearGemmPlan gemm_info(long M, int K, int N, bool stats, bool x2) {
+    const PwGemmPlan p = pw_gemm_plan(M, K, N, stats);
+    FearGemmPlan g{};
+    g.present = 1; g.lds = p.lds; g.rows = (int32_t)M; g.k = K; g.n = N; g.x2 = x2;
+    if (!p.lds) { g.row_tiles = p.row_tiles; g.grid_x = (int32_t)p.grid.x; g.grid_y = (int32_t)p.grid.y; g.nt = p.nt; }
+    return g;
+}
+FearWgradPlan wgrad_info(long M, int K, int N, bool stem, bool dy_masked, bool dy_lin, size_t ws_bytes) {
+    const WgradLaunch w = wgrad_launch_plan(M, K, N, 1, stem, dy_masked, dy_lin, ws_bytes);
+    FearWgradPlan g{};
+    g.present = 1; g.rows = (int32_t)M; g.k = K; g.n = N; g.swapped = w.swapped; g.lds_tile = w.lds_tile;
+    g.rows_per_slice = (int32_t)w.plan.rows_per_slice; g.slices = w.plan.slices;
+    return g;
+}
+FearWgradPlan wgrad_fused_info(long M, int K, int N, int partials) {
+    FearWgradPlan g{};
+    g.present = 2; g.rows = (int32_t)M; g.k = K; g.n = N; g.slices = partials;
+    return g;
+}
+void dw_info(const DwGeom& geo, FearDwPlan* out) {
+    out->tiles_x = geo.tiles_x; out->tiles_y = geo.tiles_y; out->tile_side = geo.ts; out->nslab = geo.nslab; out->wgs_per_slab = geo.wgs_per_slab;
+    out->items_per_wg = geo.items_per_wg(); out->small_map = geo.small_map;
 }
 
 }  // namespace
@@ -464,6 +517,37 @@ int fear_irb_virtual_ok(const FearIrbBlock* b) { return b && irb_virtual_shape(b
 size_t fear_irb_scratch_floats(const FearIrbBlock* b, int B, int H, int W) {
     if (!b || !irb_shape_ok(b, B, H, W)) return 0;
     return irb_scratch(b, B, H, W, nullptr).total;
+}
+
+int fear_irb_plan_info(const FearIrbBlock* b, int B, int H, int W, FearIrbPlanInfo* out) {
+    if (!b || !out) return FEAR_TRAIN_ERR_NULL;
+    if (!irb_shape_ok(b, B, H, W) || (irb_virtual(b) && !irb_virtual_shape(b))) return FEAR_TRAIN_ERR_SHAPE;
+    const long rows_in = (long)B * H * W, rows_out = rows_in / (b->stride * b->stride);
+    const int cin = b->cin, cexp = b->cexp, cout = b->cout;
+    const BlockWs ws = block_ws(rows_in, rows_out, cin, cexp, cout, b->k, nullptr);
+    const bool virt = irb_virtual(b), lin = irb_lin(b);
+    FearIrbPlanInfo r{};
+    r.rows_in = (int32_t)rows_in; r.rows_out = (int32_t)rows_out; r.lin = lin; r.virtual_e = virt;
+    // forward: expansion (unless virtual), depthwise, projection
+    if (b->expand && !virt) r.expand = gemm_info(rows_in, cin, cexp, true, false);
+    dw_info(dw_fwd_geom(b, B, H, W), &r.dw_fwd);
+    r.project = gemm_info(rows_out, cexp, cout, true, false);
+    // backward: BatchNorm3's sums, masked gradient (+ dW3), depthwise (+ dW1 of a virtual 3 x 3), dW1, dx
+    r.col_rows_in = col_rows_per_block(rows_in); r.col_rows_out = col_rows_per_block(rows_out);
+    r.wgrad_rows_per_slice = (int32_t)wgrad_rows_per_slice(rows_in);
+    const PwGemmPlan g2 = pw_gemm_plan(rows_out, cout, cexp, true);
+    r.g2 = gemm_info(rows_out, cout, cexp, true, false);
+    r.w3 = irb_w3g(b) && w3g_fits(g2, cexp) ? wgrad_fused_info(rows_out, cexp, cout, (int)g2.grid.x)
+                                            : wgrad_info(rows_out, cexp, cout, false, false, false, ws.wg_bytes);
+    const DwGeom bwd = dw_bwd_geom(b, B, H, W);
+    dw_info(bwd, &r.dw_bwd);
+    if (b->expand) {
+        r.w1 = irb_w1g(b) ? wgrad_fused_info(rows_in, cin, cexp, bwd.wgs_per_slab) : wgrad_info(rows_in, cin, cexp, false, false, lin, ws.wg_bytes);
+        r.dx = gemm_info(rows_in, lin ? cexp + cin : cexp, cin, false, lin);
+        if (virt || (lin && cin <= 32)) r.gram_rows_per_wg = (int32_t)gram_rows_per_wg(rows_in);
+    }
+    *out = r;
+    return FEAR_TRAIN_OK;
 }
 
 int fear_irb_train_forward(const FearIrbBlock* b, const FearIrbSaved* sv, const float* x, float* out, int B, int H, int W, double momentum,
@@ -613,9 +697,7 @@ int fear_irb_train_backward(const FearIrbBlock* b, const FearIrbSaved* sv, const
         // where it pays — 16-32 input channels, the expansions of the 128 x 128 ... 32 x 32 maps: bandwidth-bound launches that read
         // 0.1-0.8 GB less each (16.71 -> 16.49 ms per step).  With 64 / 112 input channels (the 16 x 16 maps) the T kernel on the
         // chain, the Gram matrix and the correction cost more than the lighter loads save: 16.64 / 16.80 ms with those included.
-        // (cexp % 16: a GEMM stage of 16 reduction columns must not straddle g1 and x.)
-        const bool lin = cexp % 16 == 0 && cin <= 128 && !(b->flags & FEAR_IRB_NO_LINEAR_BN1) &&
-                         (cin <= 32 || (b->flags & FEAR_IRB_LINEAR_BN1));      // (always true for a virtual expansion: irb_virtual_shape)
+        const bool lin = irb_lin(b);
         BnbIn bn1{};
         bn1.coef = sc.coef1; bn1.C = cexp;
         if (!lin) { bn1.E = sv->e; bn1.lde = cexp; }
@@ -685,6 +767,27 @@ int fear_bn_running_update_multi(const FearBnRunning* items, int n, double momen
 size_t fear_pwbn_workspace_bytes(long M, int K, int N) {
     if (M < 1 || K < 4 || N < 4) return 0;
     return block_ws(M, M, K, N, N, 3, nullptr).total;
+}
+
+int fear_pwbn_plan_info(long M, int K, int N, int relu, int stem, FearPwbnPlanInfo* out) {
+    if (!out) return FEAR_TRAIN_ERR_NULL;
+    if (!pw_shape_ok(M, K, N) || N > 1024 || M > 0x7fffffffL || (stem && (K != 28 || N != 16 || !relu))) return FEAR_TRAIN_ERR_SHAPE;
+    const BlockWs ws = block_ws(M, M, K, N, N, 3, nullptr);
+    FearPwbnPlanInfo r{};
+    r.rows = (int32_t)M;
+    if (stem) {      // fear_stem_train_forward: pw_stat_kernel on stat_grid whatever the shape, and no input gradient
+        int nt = 1, row_tiles = 1;
+        const dim3 grid = stat_grid(M, K, N, &nt, &row_tiles);
+        r.forward.present = 1; r.forward.rows = (int32_t)M; r.forward.k = K; r.forward.n = N;
+        r.forward.row_tiles = row_tiles; r.forward.grid_x = (int32_t)grid.x; r.forward.grid_y = (int32_t)grid.y; r.forward.nt = nt;
+    } else {
+        r.forward = gemm_info(M, K, N, true, false);
+        r.dx = gemm_info(M, N, K, false, false);
+    }
+    r.col_rows = col_rows_per_block(M);
+    r.w = wgrad_info(M, K, N, stem != 0, relu != 0, false, ws.wg_bytes);
+    *out = r;
+    return FEAR_TRAIN_OK;
 }
 
 int fear_pwbn_train_forward(const float* x, int ldx, const float* w, const float* gamma, const float* beta, float* running_mean,

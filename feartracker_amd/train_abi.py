@@ -59,6 +59,8 @@ TRAIN_SYMBOLS = {
     "fear_irb_workspace_bytes": ([_P, _i, _i, _i], _sz),
     "fear_irb_scratch_floats": ([_P, _i, _i, _i], _sz),
     "fear_irb_virtual_ok": ([_P], _i),
+    "fear_irb_plan_info": ([_P, _i, _i, _i, _P], _i),            # host only: FearIrbPlanInfo below
+    "fear_pwbn_plan_info": ([_l, _i, _i, _i, _i, _P], _i),       # host only: FearPwbnPlanInfo below
     "fear_irb_train_forward": ([_P, _P, _P, _P, _i, _i, _i, _d, _d, _P, _sz, _P], _i),
     "fear_irb_train_backward": ([_P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _P, _sz, _P, _P], _i),
     "fear_bn_running_update": ([_P, _d, _P, _P, _d, _d, _i, _P], _i),
@@ -127,6 +129,36 @@ class FearIrbSaved(ctypes.Structure):
 
 class FearIrbGrads(ctypes.Structure):
     _fields_ = [("w_pw", _P), ("w_dw", _P), ("w_pwl", _P), ("gamma", _P * 3), ("beta", _P * 3)]
+
+
+_i32 = ctypes.c_int32
+
+
+class FearGemmPlan(ctypes.Structure):
+    """include/fear_train.h: one row-tiled pointwise GEMM of a plan query."""
+    _fields_ = [(n, _i32) for n in ("present", "lds", "rows", "k", "n", "x2", "row_tiles", "grid_x", "grid_y", "nt")]
+
+
+class FearWgradPlan(ctypes.Structure):
+    """include/fear_train.h: one pointwise weight gradient of a plan query."""
+    _fields_ = [(n, _i32) for n in ("present", "rows", "k", "n", "swapped", "lds_tile", "rows_per_slice", "slices")]
+
+
+class FearDwPlan(ctypes.Structure):
+    """include/fear_train.h: one depthwise launch of a plan query."""
+    _fields_ = [(n, _i32) for n in ("tiles_x", "tiles_y", "tile_side", "nslab", "wgs_per_slab", "items_per_wg", "small_map")]
+
+
+class FearIrbPlanInfo(ctypes.Structure):
+    """include/fear_train.h: what fear_irb_train_forward / _backward would launch (fear_irb_plan_info; host only)."""
+    _fields_ = [("rows_in", _i32), ("rows_out", _i32), ("lin", _i32), ("virtual_e", _i32), ("expand", FearGemmPlan), ("project", FearGemmPlan),
+                ("g2", FearGemmPlan), ("dx", FearGemmPlan), ("col_rows_in", _i32), ("col_rows_out", _i32), ("wgrad_rows_per_slice", _i32),
+                ("w3", FearWgradPlan), ("w1", FearWgradPlan), ("dw_fwd", FearDwPlan), ("dw_bwd", FearDwPlan), ("gram_rows_per_wg", _i32)]
+
+
+class FearPwbnPlanInfo(ctypes.Structure):
+    """include/fear_train.h: what fear_pwbn_train_* / fear_stem_train_* would launch (fear_pwbn_plan_info; host only)."""
+    _fields_ = [("rows", _i32), ("forward", FearGemmPlan), ("dx", FearGemmPlan), ("col_rows", _i32), ("w", FearWgradPlan)]
 
 
 class FearBnRunning(ctypes.Structure):

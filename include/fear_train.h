@@ -277,7 +277,10 @@ typedef struct FearIrbGrads {      /* parameter gradients, kernel layouts of Fea
 } FearIrbGrads;
 size_t fear_irb_workspace_bytes(const FearIrbBlock* blk, int B, int H, int W);     /* 0: unsupported shape */
 int fear_irb_virtual_ok(const FearIrbBlock* blk);                                   /* 1: FEAR_IRB_VIRTUAL_E may be set for this block */
-size_t fear_irb_scratch_floats(const FearIrbBlock* blk, int B, int H, int W);      /* `scratch` of the backward */
+size_t fear_irb_scratch_floats(const FearIrbBlock* blk, int B, int H, int W);      /* `scratch` of the backward; it begins with the two
+                                                                                       masked gradients, exact zeros where a ReLU is shut:
+                                                                                       g2 [B*(H/s)*(W/s)][cexp], then with an expansion
+                                                                                       g1 [B*H*W][cexp] */
 /* x [B*H*W][cin] -> out [B*(H/s)*(W/s)][cout] */
 int fear_irb_train_forward(const FearIrbBlock* blk, const FearIrbSaved* saved, const float* x, float* out, int B, int H, int W,
                            double momentum, double eps, float* workspace, size_t ws_bytes, void* stream);
@@ -289,6 +292,52 @@ int fear_irb_train_forward(const FearIrbBlock* blk, const FearIrbSaved* saved, c
 int fear_irb_train_backward(const FearIrbBlock* blk, const FearIrbSaved* saved, const FearIrbGrads* grads, const float* x, const float* dout,
                             float* dx, float* scratch, int B, int H, int W, float* workspace, size_t ws_bytes, void* stream,
                             void* wgrad_stream);
+/* What the two calls above would launch for this block and shape — host only: nothing is launched and no device is needed.  The
+ * kernels and grids are chosen from the row counts B*H*W and B*(H/s)*(W/s) (csrc/fear_train_block.h: gemm_lds_applies, stat_grid,
+ * dgrad_grid, col_rows_per_block, wgrad_plan, dw_geom, gram_rows_per_wg); the query asks the same helpers the launches ask, so that a
+ * test can state which of them its shapes reach (tests/test_train_block.py::test_cases_reach_the_paths_they_claim). */
+typedef struct FearGemmPlan {      /* one row-tiled pointwise GEMM */
+    int32_t present;               /* 0: the block has no such launch (every other field is 0) */
+    int32_t lds;                   /* 1: the LDS-staged kernel (csrc/fear_train_gemm.h); 0: the first generation, on the grid below */
+    int32_t rows, k, n;            /* rows, reduction length (both operands), output columns */
+    int32_t x2;                    /* 1: the reduction runs over two operands (the E-free input gradient: [g1 | x]) */
+    int32_t row_tiles;             /* first generation: 128-row tiles per workgroup */
+    int32_t grid_x, grid_y, nt;    /* first generation: row blocks, column passes, 16-column tiles per pass */
+} FearGemmPlan;
+typedef struct FearWgradPlan {     /* one pointwise weight gradient dW[n][k] over `rows` rows */
+    int32_t present;               /* 0: none; 1: a launch of its own; 2: summed inside another kernel's pass (FEAR_IRB_FUSE_W3 in the
+                                      masked-gradient GEMM; a virtual 3 x 3 expansion's in the depthwise backward): `slices` partials */
+    int32_t rows, k, n;
+    int32_t swapped, lds_tile;     /* the kernel variant: operands traded / 128 x 128 tiles staged through LDS */
+    int32_t rows_per_slice, slices;
+} FearWgradPlan;
+typedef struct FearDwPlan {        /* one depthwise launch: persistent workgroups walk tiles of the map */
+    int32_t tiles_x, tiles_y, tile_side, nslab, wgs_per_slab;
+    int32_t items_per_wg;          /* the most tiles a workgroup walks */
+    int32_t small_map;             /* 1: the 8 x 8-tile kernel of the 5 x 5 stride-1 blocks on maps of at most 8 x 8 */
+} FearDwPlan;
+typedef struct FearIrbPlanInfo {
+    int32_t rows_in, rows_out;
+    int32_t lin, virtual_e;        /* BatchNorm1's backward in the E-free form / the expansion never written */
+    FearGemmPlan expand, project;  /* forward (expand: absent without an expansion or with a virtual one) */
+    FearGemmPlan g2, dx;           /* backward: the masked gradient; the input gradient of an expansion (what a non-NULL dx launches) */
+    int32_t col_rows_in, col_rows_out;      /* rows per column-reduction workgroup at either row count (the block's own column
+                                               reduction, BatchNorm3's backward sums, runs over rows_out) */
+    int32_t wgrad_rows_per_slice;  /* the coarse weight-gradient slice the workspace is sized by; a launch may cut finer: w3, w1 */
+    FearWgradPlan w3, w1;          /* the projection's / the expansion's weight gradient */
+    FearDwPlan dw_fwd, dw_bwd;
+    int32_t gram_rows_per_wg;      /* rows per workgroup of the input's Gram matrix (virtual forward; E-free backward up to 32 input
+                                      channels); 0: no such launch */
+} FearIrbPlanInfo;
+int fear_irb_plan_info(const FearIrbBlock* blk, int B, int H, int W, FearIrbPlanInfo* out);
+/* ... and of fear_pwbn_train_* over M rows, or (stem = 1: K = 28, N = 16, relu = 1) of fear_stem_train_* over M = n*(H/2)*(W/2) rows */
+typedef struct FearPwbnPlanInfo {
+    int32_t rows;
+    FearGemmPlan forward, dx;      /* (dx: what a non-NULL dx launches; absent for the stem) */
+    int32_t col_rows;
+    FearWgradPlan w;
+} FearPwbnPlanInfo;
+int fear_pwbn_plan_info(long M, int K, int N, int relu, int stem, FearPwbnPlanInfo* out);
 /* The running statistics of one BatchNorm from the `vec` its forward saved (mean | rstd | a | b), for forwards that ran with
  * running_mean = NULL: the shared trunk's two passes (template, search: model/fear_net.py:83-88) may then overlap on two streams,
  * and torch's update order — template pass first — is restored by applying the search pass's update afterwards. */

@@ -24,10 +24,13 @@ def test_struct_mirrors_have_the_headers_layout(tmp_path):
     struct-taking entry points need no GPU."""
     import ctypes
     import subprocess
-    from feartracker_amd import train_head as th
+    from feartracker_amd import train_abi, train_head as th
     from feartracker_amd.train_net import FEAR_IRB_VIRTUAL_E
     structs = {"FearIrbBlock": th.FearIrbBlock, "FearIrbSaved": th.FearIrbSaved, "FearIrbGrads": th.FearIrbGrads,
-               "FearSepLayer": th.FearSepLayer, "FearSepGrads": th.FearSepGrads}
+               "FearSepLayer": th.FearSepLayer, "FearSepGrads": th.FearSepGrads,
+               # the plan queries' records (fear_irb_plan_info, fear_pwbn_plan_info)
+               "FearGemmPlan": train_abi.FearGemmPlan, "FearWgradPlan": train_abi.FearWgradPlan, "FearDwPlan": train_abi.FearDwPlan,
+               "FearIrbPlanInfo": train_abi.FearIrbPlanInfo, "FearPwbnPlanInfo": train_abi.FearPwbnPlanInfo}
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT}/include/fear_train.h"', 'int main(void) {']
     for name, cls in structs.items():
         lines.append(f'  printf("{name} size %zu\\n", sizeof({name}));')
@@ -60,6 +63,17 @@ def test_struct_mirrors_have_the_headers_layout(tmp_path):
     blk.stride = 1
     assert lib.fear_irb_virtual_ok(ctypes.byref(blk)) == 0                             # (the stride-1 kernels keep their saved expansion)
     assert lib.fear_irb_train_forward(ctypes.byref(blk), None, None, None, 2, 32, 32, 0.1, 1e-5, None, 0, None) == -1
+    # the plan query: host only; null and shape errors like the calls it describes (a virtual expansion at stride 1 is no shape)
+    info = train_abi.FearIrbPlanInfo()
+    assert lib.fear_irb_plan_info(ctypes.byref(blk), 2, 32, 32, None) == -1 and lib.fear_irb_plan_info(None, 2, 32, 32, ctypes.byref(info)) == -1
+    assert lib.fear_irb_plan_info(ctypes.byref(blk), 2, 32, 32, ctypes.byref(info)) == 0 and (info.rows_in, info.rows_out, info.expand.present) == (2048, 2048, 1)
+    assert lib.fear_irb_plan_info(ctypes.byref(blk), 2, 33, 32, ctypes.byref(info)) == 0 and lib.fear_irb_plan_info(ctypes.byref(blk), 0, 32, 32, ctypes.byref(info)) == -2
+    blk.flags = FEAR_IRB_VIRTUAL_E
+    assert lib.fear_irb_plan_info(ctypes.byref(blk), 2, 32, 32, ctypes.byref(info)) == -2
+    blk.flags = 0
+    pw = train_abi.FearPwbnPlanInfo()
+    assert lib.fear_pwbn_plan_info(1024, 28, 16, 1, 0, None) == -1 and lib.fear_pwbn_plan_info(1024, 27, 16, 1, 0, ctypes.byref(pw)) == -2
+    assert lib.fear_pwbn_plan_info(1024, 28, 16, 1, 1, ctypes.byref(pw)) == 0 and (pw.rows, pw.forward.present, pw.dx.present, pw.w.present) == (1024, 1, 0, 1)
     sep = th.FearSepLayer()
     assert lib.fear_sepbn_workspace_bytes(ctypes.byref(sep), 2, 16, 16) == 0
     sep.cin, sep.cout = 320, 256
