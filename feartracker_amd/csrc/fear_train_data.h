@@ -522,6 +522,19 @@ __global__ __launch_bounds__(kColourThreads) void colour_kernel(const uint8_t* _
     colour_crop(in + crop * bytes, out + crop * bytes, H, W, ops + crop, aux + crop * 768, sh, (int)threadIdx.x, kColourThreads);
 }
 
+// ---- the members that work in HLS --------------------------------------------------------------------------------------------------
+// fear_hls_u8: ISONoise, RandomRain and RandomShadow on uint8 HWC crops (fear_train_hls.h holds the body).  One workgroup of 1024 lanes
+// per crop, 9.3 KB of LDS (the 256 x 256-bit mask, the CDF, two sums); no global atomics.
+#include "fear_train_hls.h"
+
+__global__ __launch_bounds__(kColourThreads) void hls_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int H, int W,
+                                                             const HlsOp* __restrict__ ops, const int16_t* __restrict__ seg,
+                                                             const float* __restrict__ q, const double* __restrict__ exp_table) {
+    __shared__ HlsShared sh;
+    const long crop = blockIdx.x, bytes = (long)H * W * 3;
+    hls_crop(in + crop * bytes, out + crop * bytes, H, W, ops + crop, seg, q, exp_table, sh, (int)threadIdx.x, kColourThreads);
+}
+
 // fear_normalize_u8's constants
 template <typename Args>
 void set_normalisation(Args& a) {
@@ -631,6 +644,22 @@ int fear_colour_u8(const uint8_t* crops_in, int n, int H, int W, const FearColou
     if (crops_in == crops_out) return FEAR_TRAIN_ERR_SHAPE;                          // Emboss reads its neighbours: not in place
     hipLaunchKernelGGL(colour_kernel, dim3((unsigned)n), dim3(kColourThreads), 0, static_cast<hipStream_t>(stream), crops_in, crops_out,
                        H, W, reinterpret_cast<const ColourOp*>(ops), aux_lut);
+    LAUNCH_CHECK();
+    return FEAR_TRAIN_OK;
+}
+
+int fear_hls_u8(const uint8_t* crops_in, int n, int H, int W, const FearHlsOp* ops, const int16_t* segments, const float* qtable,
+                const double* exp_table, uint8_t* crops_out, void* stream) {
+    static_assert(sizeof(FearHlsOp) == sizeof(HlsOp) && offsetof(FearHlsOp, seg_count) == offsetof(HlsOp, seg_count) &&
+                  offsetof(FearHlsOp, hue_scale) == offsetof(HlsOp, hue_scale) && offsetof(FearHlsOp, intensity) == offsetof(HlsOp, intensity) &&
+                  offsetof(FearHlsOp, key) == offsetof(HlsOp, key), "FearHlsOp and HlsOp must share one layout");
+    static_assert(FEAR_HLS_MAX_SIDE == kHlsMaxSide, "the mask in LDS holds FEAR_HLS_MAX_SIDE squared bits");
+    if (n < 0 || n > 65535 || H < 4 || W < 4 || (H & 1) || (W & 1) || H > FEAR_HLS_MAX_SIDE || W > FEAR_HLS_MAX_SIDE) return FEAR_TRAIN_ERR_SHAPE;
+    if (n == 0) return FEAR_TRAIN_OK;
+    if (!crops_in || !ops || !segments || !qtable || !exp_table || !crops_out) return FEAR_TRAIN_ERR_NULL;
+    if (crops_in == crops_out) return FEAR_TRAIN_ERR_SHAPE;                          // rain reads its neighbours: not in place
+    hipLaunchKernelGGL(hls_kernel, dim3((unsigned)n), dim3(kColourThreads), 0, static_cast<hipStream_t>(stream), crops_in, crops_out, H, W,
+                       reinterpret_cast<const HlsOp*>(ops), segments, qtable, exp_table);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }

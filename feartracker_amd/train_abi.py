@@ -112,6 +112,8 @@ TRAIN_SYMBOLS = {
     "fear_jpeg_decode_u8_rows_dev": ([_P, _i, _P, _P, _P, _sz, _P], _i),
     # the colour stage's members that are no lookup table (FearColourOp below)
     "fear_colour_u8": ([_P, _i, _i, _i, _P, _P, _P, _P], _i),
+    # ISONoise, RandomRain and RandomShadow of the photometric stage (FearHlsOp below)
+    "fear_hls_u8": ([_P, _i, _i, _i, _P, _P, _P, _P, _P, _P], _i),
     # step metrics (metrics.TrainMetrics)
     "fear_train_metrics": ([_P, _P, _P, _P, _P, _i, _i, _P, _P, _P, _P], _i),
 }
@@ -218,6 +220,15 @@ class FearColourOp(ctypes.Structure):
 
 
 assert ctypes.sizeof(FearColourOp) == 64 and FearColourOp.contrast.offset == 8 and FearColourOp.taps.offset == 24
+
+
+class FearHlsOp(ctypes.Structure):
+    """include/fear_train.h: one crop's record of fear_hls_u8 (train_data.records.HLS_DTYPE is its numpy form)."""
+    _fields_ = [("kind", ctypes.c_int32), ("seg_offset", ctypes.c_int32), ("seg_count", ctypes.c_int32), ("hue_scale", _f),
+                ("intensity", _d), ("key", ctypes.c_uint32 * 2)]
+
+
+assert ctypes.sizeof(FearHlsOp) == 32 and FearHlsOp.intensity.offset == 16 and FearHlsOp.key.offset == 24
 
 
 class FearJpegInfo(ctypes.Structure):

@@ -10,10 +10,12 @@ import torch
 from ..geometry import border_color_u8
 from ..train_abi import launch, load_train_library
 from .colour import _colour_u8, _normalise_u8, colour_luts, colour_tables, colour_u8_host
+from .hls import hls_tables, iso_exp_table, rain_drop_count
 from .photometric import normal_quantiles, photo_tables, photometric_host, split_jpeg_records
 from .records import (COLOUR_MEMBERS, COLOUR_NONE, CONTEXT_SIZE, DEFAULT_TRAIN_DATA_CONFIG, DEVICE_COLOUR_KINDS, BLUR_NONE, FRAME_DTYPE,
-                      GEOM_DTYPE, N_QUANTILES, NOISE_JPEG, NOISE_MEMBERS, NOISE_NONE, PHOTO_DTYPE, SCORE_SIZE, SEARCH_SIZE, TEMPLATE_SIZE,
-                      TONE_NONE, PhotoParams, TrainBatch, TrainPairParams, _pairs_array)
+                      GEOM_DTYPE, HLS_COPY, N_QUANTILES, NOISE_ISO, NOISE_JPEG, NOISE_MEMBERS, NOISE_NONE, PHOTO_DTYPE, SCORE_SIZE,
+                      SEARCH_SIZE, SHADOW_POLYGONS, SHADOW_VERTICES, TEMPLATE_SIZE, TONE_NONE, WEATHER_MEMBERS, WEATHER_NONE, PhotoParams,
+                      TrainBatch, TrainPairParams, _pairs_array)
 from .staging import Staging
 from .warp import (_box_in_crop, _ensure, _extend, apply_to_bbox, crop_u8, encode_targets, invert_affine, jittered_crop, remap_affine_u8,
                    warp_matrix)
@@ -32,26 +34,31 @@ class TrainPairBuilder:
             self.config.update(config)
         self.colour_members = self._members(self.config["colour_members"], COLOUR_MEMBERS, "colour")
         self.noise_members = self._members(self.config["noise_members"], NOISE_MEMBERS, "noise")
+        self.weather_members = self._members(self.config["weather_members"], WEATHER_MEMBERS, "weather", empty=True)
+        for name in ("iso_color_shift", "iso_intensity"):
+            low, high = (float(v) for v in self.config[name])
+            if not 0.0 <= low <= high or (name == "iso_intensity" and high > 0.5):
+                raise ValueError(f"{name} must be (low, high) with 0 <= low <= high" + (" <= 0.5" if name == "iso_intensity" else ""))
         lo, hi = (int(v) for v in self.config["jpeg_quality"])
         if not 1 <= lo <= hi <= 100:
             raise ValueError("jpeg_quality must be (low, high) with 1 <= low <= high <= 100")
         self._device_colour = any(COLOUR_MEMBERS[m] in DEVICE_COLOUR_KINDS for m in self.colour_members)
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.generator = np.random.default_rng(seed)
-        self._qtable = None
+        self._qtable = self._exp_table = None
 
     @staticmethod
-    def _members(value, table: Dict[str, int], group: str) -> Tuple[str, ...]:
-        """`colour_members` or `noise_members` as a tuple of names in the order of its table (COLOUR_MEMBERS, NOISE_MEMBERS): "all", or
-        any non-empty subset (KeyError for a name that is no member)."""
+    def _members(value, table: Dict[str, int], group: str, empty: bool = False) -> Tuple[str, ...]:
+        """`colour_members`, `noise_members` or `weather_members` as a tuple of names in the order of its table (COLOUR_MEMBERS,
+        NOISE_MEMBERS, WEATHER_MEMBERS): "all", or any subset (KeyError for a name that is no member), non-empty unless `empty`."""
         if isinstance(value, str):
             value = tuple(table) if value == "all" else (value,)
         names = tuple(value)
         unknown = [m for m in names if m not in table]
         if unknown:
             raise KeyError(f"unknown {group} members {unknown}: the members are {list(table)}")
-        if not names or len(set(names)) != len(names):
-            raise ValueError(f"{group}_members must name at least one member, each once")
+        if (not names and not empty) or len(set(names)) != len(names):
+            raise ValueError(f"{group}_members must name {'its members' if empty else 'at least one member,'} each once")
         return tuple(m for m in table if m in names)
 
     # ------------------------------------------------------------------ draws
@@ -82,6 +89,8 @@ class TrainPairBuilder:
         if photo is not None and "jpeg" in self.noise_members:          # last of all: configurations without it keep their stream
             lo, hi = (int(v) for v in cfg["jpeg_quality"])
             extra["jpeg_quality"] = rng.integers(lo, hi + 1, size=(B, 2)).astype(np.int32)
+        if photo is not None:                                           # behind every draw there was before these members
+            extra.update(self._draw_hls(B, rng, photo))
         return TrainPairParams(context, jitter, tone, colour, alpha, beta, gamma, shift, shapes, photo, **extra)
 
     def _draw_colour(self, B: int, rng: np.random.Generator) -> Dict[str, np.ndarray]:
@@ -130,6 +139,62 @@ class TrainPairBuilder:
         key = rng.integers(0, 2 ** 32, size=(B, 2, 2), dtype=np.uint64).astype(np.uint32)
         downscale = (rng.random((B, 2)) < cfg["downscale_p"]).astype(np.int32)
         return PhotoParams(blur, ksize, line, noise, var, mult, key, downscale)
+
+    def _draw_hls(self, B: int, rng: np.random.Generator, photo: PhotoParams) -> Dict[str, np.ndarray]:
+        """The draws of fear_hls_u8's members, (B, 2, ...), each set only when configured.  ISONoise: a uniform u, color_shift and
+        intensity uniform over their limits, a Philox key; a crop on which the noise group fired takes ISONoise in the picked member's
+        place when u < 1 / (len(noise_members) + 1) (`photo.noise` becomes NOISE_ISO there).  Weather: a uniform against weather_p and a
+        pick among the members; then RandomRain's slant, integers in [-10, 10], and its H W // 600 drops, x an integer in [slant, W] for a
+        negative slant and in [0, W - slant] otherwise, y in [0, H - 20]; then RandomShadow's number of polygons, 1 or 2, and five
+        vertices for each of two, x an integer in [0, W], y in [H // 2, H].  Every interval includes both of its ends, as Python's
+        random.randint does, which albumentations draws these with."""
+        cfg, out = self.config, {}
+        if cfg["iso_noise"]:
+            u = rng.random((B, 2))
+            out["iso_color_shift"] = rng.uniform(cfg["iso_color_shift"][0], cfg["iso_color_shift"][1], size=(B, 2))
+            out["iso_intensity"] = rng.uniform(cfg["iso_intensity"][0], cfg["iso_intensity"][1], size=(B, 2))
+            out["iso_key"] = rng.integers(0, 2 ** 32, size=(B, 2, 2), dtype=np.uint64).astype(np.uint32)
+            photo.noise[(photo.noise != NOISE_NONE) & (u < 1.0 / (len(self.noise_members) + 1))] = NOISE_ISO
+        if self.weather_members:
+            kinds = np.array([WEATHER_MEMBERS[m] for m in self.weather_members])
+            fired = rng.random((B, 2)) < cfg["weather_p"]
+            out["weather"] = np.where(fired, kinds[rng.integers(0, len(kinds), size=(B, 2))], WEATHER_NONE).astype(np.int32)
+            sides = np.array([TEMPLATE_SIZE, SEARCH_SIZE], dtype=np.int64)
+            slant = rng.integers(-10, 11, size=(B, 2))
+            drops = np.zeros((B, 2, rain_drop_count(SEARCH_SIZE), 2), dtype=np.int32)
+            for j, side in enumerate(sides):
+                n = rain_drop_count(int(side))
+                low, high = np.minimum(slant[:, j], 0)[:, None], (side - np.maximum(slant[:, j], 0))[:, None]
+                drops[:, j, :n, 0] = rng.integers(low, high + 1, size=(B, n))
+                drops[:, j, :n, 1] = rng.integers(0, side - 20 + 1, size=(B, n))
+            out["rain_slant"], out["rain_drops"] = slant.astype(np.int32), drops
+            out["shadow_num"] = rng.integers(1, SHADOW_POLYGONS + 1, size=(B, 2)).astype(np.int32)
+            shape = (B, 2, SHADOW_POLYGONS, SHADOW_VERTICES)
+            x = rng.integers(0, sides[None, :, None, None] + 1, size=shape)
+            y = rng.integers(sides[None, :, None, None] // 2, sides[None, :, None, None] + 1, size=shape)
+            out["shadow_vertices"] = np.stack([x, y], axis=-1).astype(np.int32)
+        return out
+
+    def _hls(self, params: TrainPairParams, photo: Optional[PhotoParams], B: int):
+        """The batch's FearHlsOp records (`hls_tables`) when a crop drew ISONoise or a weather member, None otherwise."""
+        if photo is None:
+            return None
+        drew_iso = (np.asarray(photo.noise) == NOISE_ISO).any()
+        drew_weather = params.weather is not None and (np.asarray(params.weather) != WEATHER_NONE).any()
+        if drew_iso and not self.config["iso_noise"]:
+            raise ValueError("a crop drew ISONoise, but iso_noise is not configured")
+        if drew_weather:
+            if np.shape(params.weather) != (B, 2):
+                raise ValueError(f"weather draws are shaped {np.shape(params.weather)}, the table has {B} pairs")
+            if params.rain_drops is None or params.rain_slant is None or params.shadow_num is None or params.shadow_vertices is None:
+                raise ValueError("a crop drew a weather member, but the params carry no values for it (drawn without weather_members?)")
+            names = {v: k for k, v in WEATHER_MEMBERS.items()}
+            for kind in np.unique(np.asarray(params.weather)[np.asarray(params.weather) != WEATHER_NONE]):
+                if names.get(int(kind)) not in self.weather_members:
+                    raise ValueError(f"a crop drew the weather member {int(kind)}, but weather_members does not configure it")
+        if not (drew_iso or drew_weather):
+            return None
+        return hls_tables(params, (TEMPLATE_SIZE, SEARCH_SIZE))
 
     def _photo(self, params: TrainPairParams, B: int) -> Optional[PhotoParams]:
         """The batch's photometric draws when the stage is on, None when it is off."""
@@ -224,6 +289,18 @@ class TrainPairBuilder:
             ops, taps = photo_tables(photo)
             q = normal_quantiles()
         colour = self._colour_ops(params)
+        hls = self._hls(params, photo, B)
+        if hls is not None:
+            exp_table = iso_exp_table()
+
+        def hls_of(k, which):                # the crop's FearHlsOp records, the ISONoise one and the weather one
+            if hls is None:
+                return None
+            first, second, segments = hls
+            if second is None:               # one set of records: each crop's is the one or the other
+                rec = first[k, which]
+                return (rec, None, segments, exp_table) if ops["noise"][k, which] == NOISE_ISO else (None, rec, segments, exp_table)
+            return first[k, which], second[k, which], segments, exp_table
 
         def finish(crop, k, which):          # colour stage -> (photometric stage) -> normalised fp32
             v = _colour_u8(crop, int(geom["tone"][k]), lut[k])
@@ -232,7 +309,7 @@ class TrainPairBuilder:
             if photo is None:
                 return _normalise_u8(v)
             quality = int(params.jpeg_quality[k, which]) if ops["noise"][k, which] == NOISE_JPEG else 0
-            return photometric_host(v, ops[k, which], taps, q, quality)
+            return photometric_host(v, ops[k, which], taps, q, quality, hls_of(k, which))
 
         def frame_of(i):
             if 0 <= i < len(host):
@@ -275,6 +352,9 @@ class TrainPairBuilder:
         # the noise as uint8 (`ops`, the JPEG crops without noise and Downscale), fear_jpeg_u8 (quality 0, a copy, for the other
         # crops), then the JPEG crops' Downscale and everybody's normalisation (`tail`)
         jpeg = photo is not None and bool((ops["noise"] == NOISE_JPEG).any())
+        # a batch in which a crop drew ISONoise or a weather member takes the same path, with fear_hls_u8 behind fear_jpeg_u8: once, or
+        # twice (the ISONoise records, then the weather ones) when some crop drew both
+        hls = self._hls(params, photo, B)
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
@@ -289,10 +369,17 @@ class TrainPairBuilder:
             stage.add("lut", tab["lut"])
             stage.add("search_bbox", tab["search_bbox"].astype(np.int32))
             if staged_u8:                      # per-crop records go up transposed: the templates' first, then the searches', one call each
-                if jpeg:
-                    ops, tail, quality = split_jpeg_records(ops, params.jpeg_quality)
+                hls_records = {} if hls is None else {name: rec for name, rec in zip(("hls_first", "hls_second"), hls[:2]) if rec is not None}
+                if jpeg or hls_records:
+                    later = np.logical_or.reduce([rec["kind"] != HLS_COPY for rec in hls_records.values()]) if hls_records else None
+                    ops, tail, quality = split_jpeg_records(ops, params.jpeg_quality if jpeg else None, later)
                     stage.add("tail", tail.T)
+                if jpeg:
                     stage.add("quality", quality.T)
+                for name, rec in hls_records.items():
+                    stage.add(name, rec.T)
+                if hls_records:
+                    stage.add("segments", hls[2])
                 stage.add("ops", ops.T)
                 stage.add("taps", taps)
             if colour is not None:             # one record per pair, shared by its two crops
@@ -328,24 +415,33 @@ class TrainPairBuilder:
                    ptr(reg), ptr(cls), ptr(wgt), st)
             if staged_u8:
                 q = ptr(self._quantiles_on_device())
+                if hls is not None:
+                    exp_table = ptr(self._exp_table_on_device())
                 d_taps = stage.ptr("taps") if taps.size else None
                 if jpeg:
                     ws_bytes = lib.fear_jpeg_workspace_bytes(B, SEARCH_SIZE, SEARCH_SIZE)      # the larger side's serves both
                     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
 
                 def finish(crops, out, side, which):
-                    """One side's chain behind the table stage: [fear_colour_u8] -> [fear_photometric_stage_u8 -> fear_jpeg_u8] ->
-                    fear_photometric_u8, `which` 0 for the templates and 1 for the searches (the second half of the per-crop records)."""
+                    """One side's chain behind the table stage: [fear_colour_u8] -> [fear_photometric_stage_u8 -> [fear_jpeg_u8] ->
+                    [fear_hls_u8, once or twice]] -> fear_photometric_u8, `which` 0 for the templates and 1 for the searches (the second
+                    half of the per-crop records)."""
                     if colour is not None:     # the members that are no table
                         src, crops = crops, torch.empty_like(crops)
                         launch(lib, "fear_colour_u8", ptr(src), B, side, side, stage.ptr("colour_ops"), stage.ptr("colour_aux"), ptr(crops), st)
                     half, last = which * B * ops.itemsize, "ops"
-                    if jpeg:
-                        mid, src, crops = torch.empty_like(crops), crops, torch.empty_like(crops)
-                        launch(lib, "fear_photometric_stage_u8", ptr(src), B, side, side, stage.ptr("ops", half), d_taps, q, ptr(mid), st)
-                        launch(lib, "fear_jpeg_u8", ptr(mid), B, side, side, stage.ptr("quality", which * B * quality.itemsize), ptr(ws),
-                               ws_bytes, ptr(crops), st)
+                    if jpeg or hls is not None:
+                        src, crops = crops, torch.empty_like(crops)
+                        launch(lib, "fear_photometric_stage_u8", ptr(src), B, side, side, stage.ptr("ops", half), d_taps, q, ptr(crops), st)
                         last = "tail"
+                    if jpeg:
+                        src, crops = crops, torch.empty_like(crops)
+                        launch(lib, "fear_jpeg_u8", ptr(src), B, side, side, stage.ptr("quality", which * B * quality.itemsize), ptr(ws),
+                               ws_bytes, ptr(crops), st)
+                    for name, rec in hls_records.items():
+                        src, crops = crops, torch.empty_like(crops)
+                        launch(lib, "fear_hls_u8", ptr(src), B, side, side, stage.ptr(name, which * B * rec.itemsize), stage.ptr("segments"),
+                               q, exp_table, ptr(crops), st)
                     launch(lib, "fear_photometric_u8", ptr(crops), B, side, side, stage.ptr(last, half), d_taps, q, ptr(out), st)
 
                 finish(t_out, tmpl, TEMPLATE_SIZE, 0)
@@ -374,6 +470,15 @@ class TrainPairBuilder:
             np.copyto(pinned.numpy(), normal_quantiles())
             self._qtable = (pinned.to(self.device, non_blocking=True), pinned)     # (the pinned source lives as long as its copy)
         return self._qtable[0]
+
+    def _exp_table_on_device(self) -> torch.Tensor:
+        """ISONoise's table of exp(-i / 16) on the device, uploaded once per builder as the quantile table is."""
+        if self._exp_table is None:
+            table = iso_exp_table()
+            pinned = torch.empty(len(table), dtype=torch.float64, pin_memory=True)
+            np.copyto(pinned.numpy(), table)
+            self._exp_table = (pinned.to(self.device, non_blocking=True), pinned)
+        return self._exp_table[0]
 
     def _frame_on_device(self, f) -> torch.Tensor:
         if isinstance(f, torch.Tensor):

@@ -9,8 +9,8 @@ import numpy as np
 
 from .colour import _even_sides, _normalise_u8, _windows, filter2d_u8
 from .jpeg import jpeg_roundtrip_u8_host
-from .records import (BLUR_BOX, BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_MOTION, BLUR_NONE, GAUSS_WEIGHTS, N_QUANTILES, NOISE_GAUSS, NOISE_JPEG,
-                      NOISE_MULTIPLICATIVE, NOISE_NONE, PHOTO_DTYPE, PhotoParams)
+from .records import (BLUR_BOX, BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_MOTION, BLUR_NONE, GAUSS_WEIGHTS, N_QUANTILES, NOISE_GAUSS, NOISE_ISO,
+                      NOISE_JPEG, NOISE_MULTIPLICATIVE, NOISE_NONE, PHOTO_DTYPE, PhotoParams)
 
 _PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 
@@ -101,23 +101,31 @@ def photo_tables(photo: PhotoParams) -> Tuple[np.ndarray, np.ndarray]:
     return ops, np.stack(taps) if taps else np.zeros((0, 49), dtype=np.float32)
 
 
-def split_jpeg_records(ops: np.ndarray, quality: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """The three-launch path's records for a batch in which crops drew ImageCompression, from the FearPhotoOp records `ops` and the
-    drawn qualities, both (B, 2): (first, tail, quality).  `first` is fear_photometric_stage_u8's: `ops` with the noise and the Downscale
-    of the JPEG crops taken off.  `quality` is fear_jpeg_u8's: int32, 0 (a copy) for the other crops.  `tail` is fear_photometric_u8's
-    behind it: the JPEG crops' Downscale, "none" otherwise, and everybody's normalisation.  `ops` is left as it is."""
+def split_jpeg_records(ops: np.ndarray, quality: Optional[np.ndarray], later: Optional[np.ndarray] = None
+                       ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The records of the path with launches between fear_photometric_stage_u8 and fear_photometric_u8, for a batch in which crops drew
+    ImageCompression, ISONoise or a weather member, from the FearPhotoOp records `ops` and the drawn qualities, both (B, 2) (`quality`
+    None without ImageCompression): (first, tail, quality).  `later`, (B, 2) bool, marks the crops fear_hls_u8 works on.  `first` is
+    fear_photometric_stage_u8's: `ops` with the noise of the JPEG and the ISONoise crops and the Downscale of every crop with a launch
+    of its own behind taken off.  `quality` is fear_jpeg_u8's: int32, 0 (a copy) for the other crops.  `tail` is fear_photometric_u8's
+    behind them: those crops' Downscale, "none" otherwise, and everybody's normalisation.  `ops` is left as it is."""
     drew = ops["noise"] == NOISE_JPEG
+    moved = drew if later is None else drew | np.asarray(later, dtype=bool)
     first, tail = ops.copy(), np.zeros(ops.shape, dtype=PHOTO_DTYPE)
-    first["noise"][drew], first["downscale"][drew] = NOISE_NONE, 0
-    tail["downscale"], tail["tap_row"] = np.where(drew, ops["downscale"], 0), -1
-    return first, tail, np.where(drew, quality, 0).astype(np.int32)
+    first["noise"][drew | (ops["noise"] == NOISE_ISO)] = NOISE_NONE
+    first["downscale"][moved] = 0
+    tail["downscale"], tail["tap_row"] = np.where(moved, ops["downscale"], 0), -1
+    return first, tail, np.where(drew, 0 if quality is None else quality, 0).astype(np.int32)
 
 
-def photometric_u8_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray, quality: int = 0) -> np.ndarray:
+def photometric_u8_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray, quality: int = 0, hls=None) -> np.ndarray:
     """fear_photometric_u8's uint8 result for one (H, W, 3) crop and its FearPhotoOp record `op` (a PHOTO_DTYPE scalar), before the
     normalisation: blur, then noise, then Downscale(0.5).  Records the device treats as "none" are "none" here too.  A record whose
     noise is NOISE_JPEG takes `jpeg_roundtrip_u8_host` at `quality` in the noise's place (the builder's three-launch path); with a
-    quality outside 1..100 — the default — that noise is "none", as it is to fear_photometric_u8 and fear_jpeg_u8."""
+    quality outside 1..100 — the default — that noise is "none", as it is to fear_photometric_u8 and fear_jpeg_u8.
+    `hls` = (iso, weather, segments, exp_table) brings in fear_hls_u8's members (hls.hls_u8_host): the FearHlsOp record `iso` in the
+    noise's place when the noise is NOISE_ISO, the record `weather` between the noise and the Downscale; either may be None.  Without
+    `hls` a NOISE_ISO is "none", as it is to fear_photometric_u8."""
     v = np.asarray(crop_u8)
     H, W = v.shape[:2]
     _even_sides(v, "photometric")
@@ -148,11 +156,18 @@ def photometric_u8_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: 
         v = np.clip(f, 0, 255).astype(np.uint8)
     elif noise == NOISE_JPEG and 1 <= int(quality) <= 100:
         v = jpeg_roundtrip_u8_host(np.ascontiguousarray(v), int(quality))
+    if hls is not None:
+        from .hls import hls_u8_host
+        iso, weather, segments, exp_table = hls
+        if noise == NOISE_ISO and iso is not None:
+            v = hls_u8_host(np.ascontiguousarray(v), iso, segments, q, exp_table)
+        if weather is not None:
+            v = hls_u8_host(np.ascontiguousarray(v), weather, segments, q, exp_table)
     if int(op["downscale"]) != 0:
         v = np.repeat(np.repeat(v[::2, ::2], 2, axis=0), 2, axis=1)
     return np.ascontiguousarray(v)
 
 
-def photometric_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray, quality: int = 0) -> np.ndarray:
+def photometric_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray, quality: int = 0, hls=None) -> np.ndarray:
     """numpy restatement of fear_photometric_u8 for one crop: (H, W, 3) uint8 -> normalised fp32 (3, H, W)."""
-    return _normalise_u8(photometric_u8_host(crop_u8, op, taps, q, quality))
+    return _normalise_u8(photometric_u8_host(crop_u8, op, taps, q, quality, hls))

@@ -9,7 +9,7 @@ from typing import Any, Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from ..train_abi import FearColourOp, FearFrame, FearPairGeom, FearPhotoOp
+from ..train_abi import FearColourOp, FearFrame, FearHlsOp, FearPairGeom, FearPhotoOp
 
 TEMPLATE_SIZE, CONTEXT_SIZE, SEARCH_SIZE, SCORE_SIZE, TOTAL_STRIDE = 128, 512, 256, 16, 16
 
@@ -31,12 +31,16 @@ DEFAULT_TRAIN_DATA_CONFIG: Dict[str, Any] = dict(
     photometric=False,
     blur_p=0.2,                  # OneOf([Blur, GaussianBlur, MedianBlur, MotionBlur])
     noise_p=0.2,                 # OneOf([MultiplicativeNoise, GaussNoise]), or the members named below
-    # the members of the noise OneOf, a subset of NOISE_MEMBERS in its order; "all" adds ImageCompression (3 of the reference's 4:
-    # ISONoise is not built)
+    # the members of the noise OneOf, a subset of NOISE_MEMBERS in its order; "all" adds ImageCompression.  ISONoise, the reference's
+    # fourth, is `iso_noise` below: no name of this list
     noise_members=("multiplicative", "gauss"),
     jpeg_quality=(50, 100),      # ImageCompression(quality_lower=50): the quality is uniform over these, both ends included
     downscale_p=0.2,             # Downscale(0.5, 0.5)
     blur_limit=7, gauss_var_limit=(10, 35), multiplier=(0.9, 1.1),
+    # ISONoise as one more member of the noise OneOf: a crop on which the group fired takes it at 1 / (len(noise_members) + 1)
+    iso_noise=False, iso_color_shift=(0.01, 0.05), iso_intensity=(0.1, 0.5),
+    # OneOf([RandomRain, RandomShadow], p=0.05) behind the noise: a subset of WEATHER_MEMBERS in its order, "all" = both, () = off
+    weather_members=(), weather_p=0.05,
 )
 
 TONE_NONE, TONE_GRAY, TONE_SEPIA = 0, 1, 2
@@ -51,6 +55,11 @@ JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE = 0, 1, 2, 3  
 BLUR_NONE, BLUR_BOX, BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_MOTION = 0, 1, 2, 3, 4
 NOISE_NONE, NOISE_MULTIPLICATIVE, NOISE_GAUSS, NOISE_JPEG = 0, 1, 2, 3
 NOISE_MEMBERS = {"multiplicative": NOISE_MULTIPLICATIVE, "gauss": NOISE_GAUSS, "jpeg": NOISE_JPEG}   # (in the order `noise_members` keeps)
+NOISE_ISO = 4                                   # ISONoise (`iso_noise`): recorded in PhotoParams.noise, applied by fear_hls_u8
+WEATHER_NONE, WEATHER_RAIN, WEATHER_SHADOW = 0, 1, 2
+WEATHER_MEMBERS = {"rain": WEATHER_RAIN, "shadow": WEATHER_SHADOW}                                  # (in the order `weather_members` keeps)
+HLS_COPY, HLS_ISO, HLS_RAIN, HLS_SHADOW = 0, 1, 2, 3                                                # FearHlsOp's kinds
+SHADOW_POLYGONS, SHADOW_VERTICES = 2, 5         # RandomShadow's defaults: at most two polygons of five vertices
 N_QUANTILES = 4096
 GAUSS_WEIGHTS = {3: (64, 128, 64), 5: (16, 64, 96, 64, 16), 7: (8, 28, 56, 72, 56, 28, 8)}
 
@@ -62,7 +71,7 @@ TrainBatch = namedtuple("TrainBatch", ["template", "search", "gt_reg", "gt_cls",
 
 # the numpy forms of the device's records, derived from the ctypes mirrors of include/fear_train.h
 GEOM_DTYPE, FRAME_DTYPE = np.dtype(FearPairGeom), np.dtype(FearFrame)
-PHOTO_DTYPE, COLOUR_DTYPE = np.dtype(FearPhotoOp), np.dtype(FearColourOp)
+PHOTO_DTYPE, COLOUR_DTYPE, HLS_DTYPE = np.dtype(FearPhotoOp), np.dtype(FearColourOp), np.dtype(FearHlsOp)
 
 
 @dataclass
@@ -100,6 +109,18 @@ class TrainPairParams:
     colour_jitter: Optional[np.ndarray] = None   # (B, 4) ColorJitter's brightness, contrast, saturation factors and hue shift
     colour_jitter_order: Optional[np.ndarray] = None   # (B, 4) int32, a permutation of JITTER_* per pair
     emboss: Optional[np.ndarray] = None          # (B, 2) alpha, strength
+    # ISONoise's values per crop, (B, 2, ...); None unless `iso_noise` and the photometric stage are on.  The crops that drew it carry
+    # NOISE_ISO in `photo.noise`.  (These
+    # fields stand in front of `jpeg_quality`, which stays the last one; their draws come behind its draw.)
+    iso_color_shift: Optional[np.ndarray] = None     # (B, 2) float64
+    iso_intensity: Optional[np.ndarray] = None       # (B, 2) float64
+    iso_key: Optional[np.ndarray] = None             # (B, 2, 2) uint32, the Philox key
+    # the weather group per crop, (B, 2, ...); None unless `weather_members` names a member and the photometric stage is on
+    weather: Optional[np.ndarray] = None             # (B, 2) int32, WEATHER_*
+    rain_slant: Optional[np.ndarray] = None          # (B, 2) int32
+    rain_drops: Optional[np.ndarray] = None          # (B, 2, 109, 2) int32: (x, y) per drop; a crop of side s uses the first s s // 600
+    shadow_num: Optional[np.ndarray] = None          # (B, 2) int32, 1 or 2 polygons
+    shadow_vertices: Optional[np.ndarray] = None     # (B, 2, 2, 5, 2) int32: (x, y) per vertex of both polygons
     # ImageCompression's quality per crop, (B, 2) int32 like the arrays of `photo`; None unless "jpeg" is a configured noise member and
     # the photometric stage is on
     jpeg_quality: Optional[np.ndarray] = None

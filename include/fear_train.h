@@ -500,6 +500,7 @@ int fear_train_pairs_u8(const fear_frame* frames, int n_frames, const uint8_t* b
 #define FEAR_PHOTO_NOISE_MULTIPLICATIVE 1
 #define FEAR_PHOTO_NOISE_GAUSS 2
 #define FEAR_PHOTO_NOISE_JPEG 3          /* ImageCompression: "none" to fear_photometric_u8, applied by fear_jpeg_u8 (below) */
+#define FEAR_PHOTO_NOISE_ISO 4           /* ISONoise: "none" to fear_photometric_u8, applied by fear_hls_u8 (below)            */
 #define FEAR_PHOTO_QUANTILES 4096
 
 /* One crop.  32 bytes, no padding. */
@@ -924,6 +925,56 @@ _Static_assert(sizeof(FearColourOp) == 64, "FearColourOp is 64 bytes");
 
 int fear_colour_u8(const uint8_t* crops_in, int n, int H, int W, const FearColourOp* ops, const uint8_t* aux_lut, uint8_t* crops_out,
                    void* stream);
+
+/* ---- the photometric stage's members that work in HLS: ISONoise, the fourth member of the reference's noise group, and its weather
+ * group OneOf([RandomRain, RandomShadow]) (model_training/dataset/aug.py:8-25), on uint8 HWC crops between fear_photometric_stage_u8 (or
+ * fear_jpeg_u8) and fear_photometric_u8 (DESIGN.md section 11 states every contract; train_data.hls_u8_host restates them in numpy and the
+ * two agree bit for bit).  RGB <-> HLS is cv2's, through fp32 with every operation rounded on its own.  Per crop, by the record's kind:
+ *   1 ISONoise      S1 = sum(max + min), S2 = sum((max + min)^2) over the crop's pixels in integers; in float64 sigma_L = sqrt(max(S2 / N
+ *                   - (S1 / N)^2, 0)) / 510, lambda = sigma_L intensity 255, quantised to rint(16 lambda) / 16 and cut to [0, 64]; the CDF
+ *                   p_0 = exp_table[16 lambda], p_j = p_{j-1} lambda / j over 160 terms, summed in order.  Per pixel, Philox4x32-10 at
+ *                   counter (x, y, 0, 0) with `key`: k = the number of CDF entries <= word 0 / 2^32 (at most 159), noise = qtable[word 1
+ *                   >> 20] hue_scale.  On the fp32 HLS of the crop times fp32(1 / 255): h += noise, + 360 when negative, then - 360 when
+ *                   above 360; l += (fp32(k) fp32(1 / 255)) (1 - l); back to RGB, times 255, trunc(clip(., 0, 255))
+ *   2 RandomRain    rows seg_offset .. + seg_count of `segments` are drops (x0, y0, x1, y1): 200 in all channels along each one's raster
+ *                   (OpenCV's 8-connected line, clipped to the crop), fear_photometric_u8's Blur at k = 7, then on every pixel RGB -> HLS
+ *                   (8-bit), L = trunc(fp32(L) fp32(0.7)), HLS -> RGB
+ *   3 RandomShadow  those rows are polygons: a row (n, 0, 0, 0), then the polygon's n edges (x0, y0, x1, y1).  A pixel is in shadow when
+ *                   it lies on the raster of an edge or inside a polygon by the even-odd rule on integer pixel coordinates (an edge counts
+ *                   when y0 <= y < y1, its ends ordered by y, and (x - x0) (y1 - y0) < (y - y0) (x1 - x0)); there RGB -> HLS (8-bit),
+ *                   L = L >> 1, HLS -> RGB
+ * Any other kind, and a rain or shadow record with a negative seg_offset or seg_count, copies the crop (the records live in device
+ * memory, where the call cannot read them); rows past the table's end are the caller's error.  One workgroup per crop: the mask, the
+ * sums and the CDF live in LDS, no global atomics.
+ * H and W must be even, >= 4 and <= 256 (the mask holds 256 x 256 bits), n <= 65535, crops_in != crops_out (rain reads neighbours):
+ * FEAR_TRAIN_ERR_SHAPE otherwise.  n == 0 returns FEAR_TRAIN_OK without a launch.  A null crops_in, ops, segments, qtable, exp_table or
+ * crops_out returns FEAR_TRAIN_ERR_NULL.
+ *   crops_in, crops_out : (n, H, W, 3) uint8, device, distinct      ops : (n) FearHlsOp, device      segments : (m, 4) int16, device
+ *   qtable : (4096) fp32, device (train_data.normal_quantiles)     exp_table : (1025) float64, device: exp(-i / 16)                 */
+#define FEAR_HLS_COPY 0
+#define FEAR_HLS_ISO 1
+#define FEAR_HLS_RAIN 2
+#define FEAR_HLS_SHADOW 3
+#define FEAR_HLS_MAX_SIDE 256
+#define FEAR_HLS_EXP_ENTRIES 1025
+
+/* One crop.  32 bytes, no padding. */
+typedef struct FearHlsOp {
+    int32_t kind;               /* FEAR_HLS_*, anything else: copy                                                     */
+    int32_t seg_offset;         /* rain, shadow: the first row of `segments`                                           */
+    int32_t seg_count;          /* rain: the drops; shadow: the rows of all polygons, their count rows included        */
+    float hue_scale;            /* ISONoise: fp32(color_shift 360 intensity)                                           */
+    double intensity;           /* ISONoise                                                                            */
+    uint32_t key[2];            /* ISONoise: the crop's Philox key                                                     */
+} FearHlsOp;
+#ifdef __cplusplus
+static_assert(sizeof(FearHlsOp) == 32, "FearHlsOp is 32 bytes");
+#else
+_Static_assert(sizeof(FearHlsOp) == 32, "FearHlsOp is 32 bytes");
+#endif
+
+int fear_hls_u8(const uint8_t* crops_in, int n, int H, int W, const FearHlsOp* ops, const int16_t* segments, const float* qtable,
+                const double* exp_table, uint8_t* crops_out, void* stream);
 
 /* ---- step metrics: the training telemetry of the reference's `_training_step` (train/fear_lightning_model.py:66-87) on the device
  * (feartracker_amd/metrics.py).  Per pair: FEARBoxCoder.decode of the step's own output maps (fear_decode's

@@ -31,6 +31,14 @@ With --noise all it reports ImageCompression, the member behind `noise_members` 
   build_all_ms       `build` with noise_members="all" at the reference's probabilities, fresh draws per call
   jpeg_u8_ms         fear_jpeg_u8 alone on the batch's 128 templates and 128 searches (two calls), every crop at quality 50, HIP events
   step_ms            FEARNetTrainHIP.step on fixed inputs, for the shares
+With --iso and / or --weather all it reports ISONoise and the weather group, the members behind `iso_noise` and `weather_members` (same
+pairs and frames, the photometric stage on), in ONE run on one commit:
+  build_default_ms   `build` with photometric=True alone, one figure per fresh process
+  build_on_ms        `build` with the keys on at the reference's probabilities, fresh draws per call, the processes of the two arms
+                     taking turns.  The figure to report is this one against build_default_ms; no target is set
+  hls_u8_ms          fear_hls_u8 alone on the batch's 128 templates and 128 searches (two calls), every crop forced to one member, per
+                     member (ISONoise, rain with its H W // 600 drops, a shadow of two polygons), HIP events
+  step_ms            FEARNetTrainHIP.step on fixed inputs, for the shares
 With --store DIR it reports the resident JPEG store in front of the builder (DIR holds the files of tools/jpeg_decode_bench.py --make,
 256 synthetic 1280 x 720 files; 128 pairs, two frames of their own per pair), in ONE run, medians of `--repeats` + 2 runs with minimum and
 maximum, a host clock around work that ends in a synchronise:
@@ -45,6 +53,7 @@ Usage: python tools/train_pairs_bench.py [--pairs 128] [--frames 256] [--steps 2
        python tools/train_pairs_bench.py --photometric [--parent-root DIR] [--repeats 3] [--out FILE]
        python tools/train_pairs_bench.py --colour all [--parent-root DIR] [--repeats 3] [--out profiles/train_pairs_colour_bench.json]
        python tools/train_pairs_bench.py --noise all [--parent-root DIR] [--repeats 3] [--out profiles/train_pairs_jpeg_bench.json]
+       python tools/train_pairs_bench.py --iso --weather all [--repeats 3] [--out profiles/train_pairs_hls_bench.json]
        python tools/train_pairs_bench.py --store DIR [--repeats 3] [--out profiles/train_pairs_store_bench.json]
 """
 from __future__ import annotations
@@ -98,14 +107,19 @@ def build_only(args):
         config["colour_members"] = args.colour
     if args.noise:
         config["noise_members"] = args.noise
+    if args.iso:
+        config["iso_noise"] = True
+    if args.weather:
+        config["weather_members"] = args.weather
     builder = TrainPairBuilder(config or None, device=0, seed=0)
     print(json.dumps({"build_ms": round(_time_build(builder, frames, pairs, args.iters), 4)}))
 
 
-def _child(root, args, stage_on=False, colour=None, noise=None):
+def _child(root, args, stage_on=False, colour=None, noise=None, iso=False, weather=None):
     cmd = [sys.executable, os.path.abspath(__file__), "--build-only", "--root", root, "--pairs", str(args.pairs), "--frames",
            str(args.frames), "--iters", str(args.iters)] + (["--stage-on"] if stage_on else []) + (["--colour", colour] if colour else [])
     cmd += ["--noise", noise] if noise else []
+    cmd += (["--iso"] if iso else []) + (["--weather", weather] if weather else [])
     res = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300)
     return json.loads(res.stdout.strip().splitlines()[-1])["build_ms"]
 
@@ -312,6 +326,80 @@ def noise(args):
     }
 
 
+def hls(args):
+    # the fresh processes first, one at a time, before this process opens the GPU
+    default, on = [], []
+    for _ in range(args.repeats):
+        default.append(_child(ROOT, args, stage_on=True))
+        on.append(_child(ROOT, args, stage_on=True, iso=args.iso, weather=args.weather))
+    sys.path.insert(0, ROOT)
+    from feartracker_amd.train_abi import load_train_library
+    from feartracker_amd.train_data import (HLS_DTYPE, HLS_ISO, HLS_RAIN, HLS_SHADOW, iso_exp_table, normal_quantiles, rain_drop_count,
+                                            rain_segments, shadow_segments)
+    dev = torch.device("cuda", 0)
+    B = args.pairs
+    lib = load_train_library()
+    P = ctypes.c_void_p
+    st = P(torch.cuda.current_stream(dev).cuda_stream)
+    g = torch.Generator(device=dev).manual_seed(1)
+    sides = (128, 256)
+    crops = [torch.randint(0, 256, (B, s, s, 3), generator=g, device=dev, dtype=torch.uint8) for s in sides]
+    outs = [torch.empty_like(c) for c in crops]
+    q, table = torch.from_numpy(normal_quantiles().copy()).to(dev), torch.from_numpy(iso_exp_table().copy()).to(dev)
+    rng = np.random.default_rng(2)
+    member_ms = {}
+    for name, kind in (("iso_noise", HLS_ISO), ("rain", HLS_RAIN), ("shadow", HLS_SHADOW)):
+        d_ops, d_seg = [], []
+        for s in sides:                                    # a record and segments per crop, drawn as the builder draws them
+            ops = np.zeros(B, dtype=HLS_DTYPE)
+            ops["kind"], ops["intensity"], ops["key"] = kind, rng.uniform(0.1, 0.5, B), rng.integers(0, 2 ** 32, (B, 2))
+            ops["hue_scale"] = rng.uniform(0.01, 0.05, B) * 360.0 * ops["intensity"]
+            rows, n_rows = [np.zeros((1, 4), np.int16)], 1
+            for b in range(B):
+                if kind == HLS_RAIN:
+                    slant, n = int(rng.integers(-10, 11)), rain_drop_count(s)
+                    seg = rain_segments(slant, np.stack([rng.integers(min(slant, 0), s - max(slant, 0) + 1, n),
+                                                         rng.integers(0, s - 19, n)], axis=1))
+                else:
+                    seg = shadow_segments([np.stack([rng.integers(0, s + 1, 5), rng.integers(s // 2, s + 1, 5)], axis=1) for _ in range(2)])
+                ops["seg_offset"][b], ops["seg_count"][b] = n_rows, len(seg)
+                rows.append(seg)
+                n_rows += len(seg)
+            d_ops.append(torch.from_numpy(ops.view(np.uint8).copy()).to(dev))
+            d_seg.append(torch.from_numpy(np.concatenate(rows)).to(dev))
+
+        def both():
+            for c, o, s, r, sg in zip(crops, outs, sides, d_ops, d_seg):
+                assert lib.fear_hls_u8(P(c.data_ptr()), B, s, s, P(r.data_ptr()), P(sg.data_ptr()), P(q.data_ptr()), P(table.data_ptr()),
+                                       P(o.data_ptr()), st) == 0
+
+        for _ in range(5):
+            both()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.iters):
+            both()
+        e1.record()
+        torch.cuda.synchronize()
+        member_ms[name] = round(e0.elapsed_time(e1) / args.iters, 4)
+    frames, pairs = _inputs(B, args.frames, dev)
+    step_ms, steps = _step_ms(args, frames, pairs)
+    med = lambda v: round(float(np.median(v)), 4) if v else None
+    worst = max(member_ms, key=member_ms.get)
+    return {
+        "pairs": B, "frames": args.frames, "frame_hw": [1080, 1920], "iters": args.iters, "iso_noise": bool(args.iso),
+        "weather_members": args.weather or "",
+        "build_default_ms": med(default), "build_default_runs": default,
+        "build_on_ms": med(on), "build_on_runs": on,
+        "hls_u8_ms": member_ms, "worst_member": worst,
+        "step_ms": round(step_ms, 3), "step_ms_runs": [round(v, 3) for v in steps],
+        "members_ms": round(med(on) - med(default), 4),
+        "members_pct_of_step": round(100.0 * (med(on) - med(default)) / step_ms, 2),
+        "worst_member_pct_of_step": round(100.0 * member_ms[worst] / step_ms, 2),
+        "device": torch.cuda.get_device_name(0),
+    }
+
+
 def store_mode(args):
     """decode + build against decode_rows + build(borders=) out of a resident store."""
     import glob
@@ -387,6 +475,8 @@ def main():
     ap.add_argument("--photometric", action="store_true")
     ap.add_argument("--colour", default=None, help='"all": report the members behind colour_members')
     ap.add_argument("--noise", default=None, help='"all": report ImageCompression, the member behind noise_members')
+    ap.add_argument("--iso", action="store_true", help="report ISONoise, the member behind iso_noise")
+    ap.add_argument("--weather", default=None, help='"all": report RandomRain and RandomShadow, the members behind weather_members')
     ap.add_argument("--store", default=None, help="DIR of the synthetic 720p files: the resident store in front of the builder")
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--repeats", type=int, default=3)
@@ -399,6 +489,9 @@ def main():
     if args.store:
         args.out = args.out or os.path.join(ROOT, "profiles", "train_pairs_store_bench.json")
         return emit(store_mode(args), args)
+    if args.iso or args.weather:
+        args.out = args.out or os.path.join(ROOT, "profiles", "train_pairs_hls_bench.json")
+        return emit(hls(args), args)
     if args.photometric:
         return emit(photometric(args), args)
     if args.colour:
