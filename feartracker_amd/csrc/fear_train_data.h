@@ -535,6 +535,22 @@ __global__ __launch_bounds__(kColourThreads) void hls_kernel(const uint8_t* __re
     hls_crop(in + crop * bytes, out + crop * bytes, H, W, ops + crop, seg, q, exp_table, sh, (int)threadIdx.x, kColourThreads);
 }
 
+// ---- GlassBlur -----------------------------------------------------------------------------------------------------------------------
+// fear_glass_u8: the blur group's fifth member on uint8 HWC crops (fear_train_glass.h holds the body).  One workgroup of 256 lanes per
+// 32 x 32 tile of a crop, 21.4 KB of LDS (two buffers of three 56 x 56 byte planes and the offsets' plane); no atomics.
+#include "fear_train_glass.h"
+
+constexpr int kGlassThreads = 256;
+
+__global__ __launch_bounds__(kGlassThreads) void glass_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int H, int W,
+                                                              const PhotoOp* __restrict__ ops) {
+    __shared__ GlassShared sh;
+    const long crop = blockIdx.z, bytes = (long)H * W * 3;
+    const PhotoOp op = ops[crop];
+    const GlassTile t{(int)blockIdx.x * kGlTile, (int)blockIdx.y * kGlTile, H, W};
+    glass_tile(in + crop * bytes, out + crop * bytes, t, op.blur == kGlassBlur, op.key[0], op.key[1], sh, (int)threadIdx.x, kGlassThreads);
+}
+
 // fear_normalize_u8's constants
 template <typename Args>
 void set_normalisation(Args& a) {
@@ -660,6 +676,19 @@ int fear_hls_u8(const uint8_t* crops_in, int n, int H, int W, const FearHlsOp* o
     if (crops_in == crops_out) return FEAR_TRAIN_ERR_SHAPE;                          // rain reads its neighbours: not in place
     hipLaunchKernelGGL(hls_kernel, dim3((unsigned)n), dim3(kColourThreads), 0, static_cast<hipStream_t>(stream), crops_in, crops_out, H, W,
                        reinterpret_cast<const HlsOp*>(ops), segments, qtable, exp_table);
+    LAUNCH_CHECK();
+    return FEAR_TRAIN_OK;
+}
+
+int fear_glass_u8(const uint8_t* crops_u8, int n, int H, int W, const FearPhotoOp* ops, uint8_t* out_u8, void* stream) {
+    static_assert(FEAR_PHOTO_BLUR_GLASS == kGlassBlur, "the record's kind of GlassBlur");
+    if (n < 0 || n > 65535 || H < 4 || W < 4 || (H & 1) || (W & 1) || H > FEAR_HLS_MAX_SIDE || W > FEAR_HLS_MAX_SIDE) return FEAR_TRAIN_ERR_SHAPE;
+    if (n == 0) return FEAR_TRAIN_OK;
+    if (!crops_u8 || !ops || !out_u8) return FEAR_TRAIN_ERR_NULL;
+    if (crops_u8 == out_u8) return FEAR_TRAIN_ERR_SHAPE;                             // every stage reads its neighbours: not in place
+    const unsigned gx = (unsigned)((W + kGlTile - 1) / kGlTile), gy = (unsigned)((H + kGlTile - 1) / kGlTile);
+    hipLaunchKernelGGL(glass_kernel, dim3(gx, gy, (unsigned)n), dim3(kGlassThreads), 0, static_cast<hipStream_t>(stream), crops_u8, out_u8,
+                       H, W, reinterpret_cast<const PhotoOp*>(ops));
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }

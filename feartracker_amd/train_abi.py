@@ -114,6 +114,8 @@ TRAIN_SYMBOLS = {
     "fear_colour_u8": ([_P, _i, _i, _i, _P, _P, _P, _P], _i),
     # ISONoise, RandomRain and RandomShadow of the photometric stage (FearHlsOp below)
     "fear_hls_u8": ([_P, _i, _i, _i, _P, _P, _P, _P, _P, _P], _i),
+    # GlassBlur of the photometric stage's blur group, in front of fear_photometric_u8 (FearPhotoOp's records)
+    "fear_glass_u8": ([_P, _i, _i, _i, _P, _P, _P], _i),
     # step metrics (metrics.TrainMetrics)
     "fear_train_metrics": ([_P, _P, _P, _P, _P, _i, _i, _P, _P, _P, _P], _i),
 }

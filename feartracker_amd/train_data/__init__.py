@@ -18,7 +18,8 @@
             (`fear_jpeg_u8`), which `jpeg_roundtrip_u8_host` restates and the tests hold to Pillow's libjpeg-turbo byte for byte
             `iso_noise` adds ISONoise to the noise group and `weather_members` the group OneOf([RandomRain, RandomShadow], p=0.05)
             behind it: the members that work in HLS, one operator with a workgroup per crop (`fear_hls_u8`), which `hls_u8_host`
-            restates (hls.py)
+            restates (hls.py).  `glass_blur` adds GlassBlur to the blur group: `fear_glass_u8` in front of the other launches, a
+            workgroup per tile, which `glass_u8_host` restates (glass.py)
 * targets   `FEARBoxCoder.encode(search_bbox)` and `get_regression_weight_label(search_bbox, 256, 16)`, zeros without presence
 
 Every scalar per-pair step runs here on the host, vectorised over the batch: the draws (`draw`), the context boxes (`extend_bbox`,
@@ -36,6 +37,7 @@ from .builder import TrainPairBuilder  # noqa: F401
 from .colour import (_colour_normalise, _colour_u8, _normalise_u8, apply_tone, colour_luts, colour_tables, colour_u8_host,  # noqa: F401
                      emboss_taps, emboss_u8, equalize_u8, filter2d_u8, hsv_to_rgb_u8, jitter_brightness_lut, jitter_brightness_u8,
                      jitter_contrast_u8, jitter_hue_lut, jitter_hue_u8, jitter_saturation_u8, rgb_to_hsv_u8, tone_curve_lut)
+from .glass import *  # noqa: F401,F403  (GlassBlur's contract: glass.__all__)
 from .hls import *  # noqa: F401,F403  (the HLS members' contracts: hls.__all__)
 from .jpeg import (JPEG_CHROMA_BASE, JPEG_LUMA_BASE, jpeg_fdct_islow, jpeg_idct_islow, jpeg_quant_tables,  # noqa: F401
                    jpeg_roundtrip_u8_host)

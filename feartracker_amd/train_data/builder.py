@@ -12,7 +12,7 @@ from ..train_abi import launch, load_train_library
 from .colour import _colour_u8, _normalise_u8, colour_luts, colour_tables, colour_u8_host
 from .hls import hls_tables, iso_exp_table, rain_drop_count
 from .photometric import normal_quantiles, photo_tables, photometric_host, split_jpeg_records
-from .records import (COLOUR_MEMBERS, COLOUR_NONE, CONTEXT_SIZE, DEFAULT_TRAIN_DATA_CONFIG, DEVICE_COLOUR_KINDS, BLUR_NONE, FRAME_DTYPE,
+from .records import (COLOUR_MEMBERS, COLOUR_NONE, CONTEXT_SIZE, DEFAULT_TRAIN_DATA_CONFIG, DEVICE_COLOUR_KINDS, BLUR_GLASS, BLUR_NONE, FRAME_DTYPE,
                       GEOM_DTYPE, HLS_COPY, N_QUANTILES, NOISE_ISO, NOISE_JPEG, NOISE_MEMBERS, NOISE_NONE, PHOTO_DTYPE, SCORE_SIZE,
                       SEARCH_SIZE, SHADOW_POLYGONS, SHADOW_VERTICES, TEMPLATE_SIZE, TONE_NONE, WEATHER_MEMBERS, WEATHER_NONE, PhotoParams,
                       TrainBatch, TrainPairParams, _pairs_array)
@@ -91,6 +91,9 @@ class TrainPairBuilder:
             extra["jpeg_quality"] = rng.integers(lo, hi + 1, size=(B, 2)).astype(np.int32)
         if photo is not None:                                           # behind every draw there was before these members
             extra.update(self._draw_hls(B, rng, photo))
+        if photo is not None and cfg["glass_blur"]:                     # GlassBlur, behind those again: a blur becomes it at 1 / 5
+            u = rng.random((B, 2))
+            photo.blur[(photo.blur != BLUR_NONE) & (u < 1.0 / 5)] = BLUR_GLASS
         return TrainPairParams(context, jitter, tone, colour, alpha, beta, gamma, shift, shapes, photo, **extra)
 
     def _draw_colour(self, B: int, rng: np.random.Generator) -> Dict[str, np.ndarray]:
@@ -204,6 +207,8 @@ class TrainPairBuilder:
             raise ValueError("the photometric stage is on, but params carry no photometric draws (drawn with it off?)")
         if params.photo.blur.shape != (B, 2):
             raise ValueError(f"photometric draws are shaped {params.photo.blur.shape}, the table has {B} pairs")
+        if (np.asarray(params.photo.blur) == BLUR_GLASS).any() and not self.config["glass_blur"]:
+            raise ValueError("a crop drew GlassBlur, but glass_blur is not configured")
         if (np.asarray(params.photo.noise) == NOISE_JPEG).any():
             if "jpeg" not in self.noise_members:
                 raise ValueError("a crop drew ImageCompression, but noise_members does not configure it")
@@ -309,7 +314,7 @@ class TrainPairBuilder:
             if photo is None:
                 return _normalise_u8(v)
             quality = int(params.jpeg_quality[k, which]) if ops["noise"][k, which] == NOISE_JPEG else 0
-            return photometric_host(v, ops[k, which], taps, q, quality, hls_of(k, which))
+            return photometric_host(v, ops[k, which], taps, q, quality, hls_of(k, which), bool(self.config["glass_blur"]))
 
         def frame_of(i):
             if 0 <= i < len(host):
@@ -355,6 +360,8 @@ class TrainPairBuilder:
         # a batch in which a crop drew ISONoise or a weather member takes the same path, with fear_hls_u8 behind fear_jpeg_u8: once, or
         # twice (the ISONoise records, then the weather ones) when some crop drew both
         hls = self._hls(params, photo, B)
+        # a side on which a crop drew GlassBlur runs fear_glass_u8 in front of those launches, to which its records are "none"
+        glass = (ops["blur"] == BLUR_GLASS).any(axis=0) if photo is not None else (False, False)
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
@@ -423,13 +430,16 @@ class TrainPairBuilder:
                     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
 
                 def finish(crops, out, side, which):
-                    """One side's chain behind the table stage: [fear_colour_u8] -> [fear_photometric_stage_u8 -> [fear_jpeg_u8] ->
-                    [fear_hls_u8, once or twice]] -> fear_photometric_u8, `which` 0 for the templates and 1 for the searches (the second
-                    half of the per-crop records)."""
+                    """One side's chain behind the table stage: [fear_colour_u8] -> [fear_glass_u8] -> [fear_photometric_stage_u8 ->
+                    [fear_jpeg_u8] -> [fear_hls_u8, once or twice]] -> fear_photometric_u8, `which` 0 for the templates and 1 for the
+                    searches (the second half of the per-crop records)."""
                     if colour is not None:     # the members that are no table
                         src, crops = crops, torch.empty_like(crops)
                         launch(lib, "fear_colour_u8", ptr(src), B, side, side, stage.ptr("colour_ops"), stage.ptr("colour_aux"), ptr(crops), st)
                     half, last = which * B * ops.itemsize, "ops"
+                    if glass[which]:
+                        src, crops = crops, torch.empty_like(crops)
+                        launch(lib, "fear_glass_u8", ptr(src), B, side, side, stage.ptr("ops", half), ptr(crops), st)
                     if jpeg or hls is not None:
                         src, crops = crops, torch.empty_like(crops)
                         launch(lib, "fear_photometric_stage_u8", ptr(src), B, side, side, stage.ptr("ops", half), d_taps, q, ptr(crops), st)

@@ -9,7 +9,7 @@ import numpy as np
 
 from .colour import _even_sides, _normalise_u8, _windows, filter2d_u8
 from .jpeg import jpeg_roundtrip_u8_host
-from .records import (BLUR_BOX, BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_MOTION, BLUR_NONE, GAUSS_WEIGHTS, N_QUANTILES, NOISE_GAUSS, NOISE_ISO,
+from .records import (BLUR_BOX, BLUR_GAUSSIAN, BLUR_GLASS, BLUR_MEDIAN, BLUR_MOTION, BLUR_NONE, GAUSS_WEIGHTS, N_QUANTILES, NOISE_GAUSS, NOISE_ISO,
                       NOISE_JPEG, NOISE_MULTIPLICATIVE, NOISE_NONE, PHOTO_DTYPE, PhotoParams)
 
 _PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -118,14 +118,17 @@ def split_jpeg_records(ops: np.ndarray, quality: Optional[np.ndarray], later: Op
     return first, tail, np.where(drew, 0 if quality is None else quality, 0).astype(np.int32)
 
 
-def photometric_u8_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray, quality: int = 0, hls=None) -> np.ndarray:
+def photometric_u8_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray, quality: int = 0, hls=None,
+                        glass: bool = False) -> np.ndarray:
     """fear_photometric_u8's uint8 result for one (H, W, 3) crop and its FearPhotoOp record `op` (a PHOTO_DTYPE scalar), before the
     normalisation: blur, then noise, then Downscale(0.5).  Records the device treats as "none" are "none" here too.  A record whose
     noise is NOISE_JPEG takes `jpeg_roundtrip_u8_host` at `quality` in the noise's place (the builder's three-launch path); with a
     quality outside 1..100 — the default — that noise is "none", as it is to fear_photometric_u8 and fear_jpeg_u8.
     `hls` = (iso, weather, segments, exp_table) brings in fear_hls_u8's members (hls.hls_u8_host): the FearHlsOp record `iso` in the
     noise's place when the noise is NOISE_ISO, the record `weather` between the noise and the Downscale; either may be None.  Without
-    `hls` a NOISE_ISO is "none", as it is to fear_photometric_u8."""
+    `hls` a NOISE_ISO is "none", as it is to fear_photometric_u8.
+    `glass` brings in fear_glass_u8's member (glass.glass_u8_host) in the blur's place when the blur is BLUR_GLASS; without it a
+    BLUR_GLASS is "none", as it is to fear_photometric_u8."""
     v = np.asarray(crop_u8)
     H, W = v.shape[:2]
     _even_sides(v, "photometric")
@@ -133,6 +136,11 @@ def photometric_u8_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: 
     if k not in (3, 5, 7) or (blur == BLUR_MOTION and (taps is None or row < 0)):
         blur = BLUR_NONE
     r = k // 2
+    if int(op["blur"]) == BLUR_GLASS:                      # (whatever the record's ksize)
+        blur = BLUR_NONE
+        if glass:
+            from .glass import glass_u8_host
+            v = glass_u8_host(v, op)
     if blur == BLUR_BOX:
         s = _windows(v, r, "reflect").astype(np.int64).sum(axis=(-1, -2))
         v = ((s + k * k // 2) // (k * k)).astype(np.uint8)
@@ -168,6 +176,7 @@ def photometric_u8_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: 
     return np.ascontiguousarray(v)
 
 
-def photometric_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray, quality: int = 0, hls=None) -> np.ndarray:
+def photometric_host(crop_u8: np.ndarray, op, taps: Optional[np.ndarray], q: np.ndarray, quality: int = 0, hls=None,
+                     glass: bool = False) -> np.ndarray:
     """numpy restatement of fear_photometric_u8 for one crop: (H, W, 3) uint8 -> normalised fp32 (3, H, W)."""
-    return _normalise_u8(photometric_u8_host(crop_u8, op, taps, q, quality, hls))
+    return _normalise_u8(photometric_u8_host(crop_u8, op, taps, q, quality, hls, glass))

@@ -29,7 +29,7 @@ DEFAULT_TRAIN_DATA_CONFIG: Dict[str, Any] = dict(
     brightness_limit=0.2, contrast_limit=0.2, gamma_limit=(0.8, 1.2), rgb_shift_limit=20.0,
     # PHOTOMETRIC_AUGMENTATIONS (dataset/aug.py:8-25), per crop, off unless asked for
     photometric=False,
-    blur_p=0.2,                  # OneOf([Blur, GaussianBlur, MedianBlur, MotionBlur])
+    blur_p=0.2,                  # OneOf([Blur, GaussianBlur, MedianBlur, MotionBlur]), and GlassBlur with `glass_blur` below
     noise_p=0.2,                 # OneOf([MultiplicativeNoise, GaussNoise]), or the members named below
     # the members of the noise OneOf, a subset of NOISE_MEMBERS in its order; "all" adds ImageCompression.  ISONoise, the reference's
     # fourth, is `iso_noise` below: no name of this list
@@ -41,6 +41,9 @@ DEFAULT_TRAIN_DATA_CONFIG: Dict[str, Any] = dict(
     iso_noise=False, iso_color_shift=(0.01, 0.05), iso_intensity=(0.1, 0.5),
     # OneOf([RandomRain, RandomShadow], p=0.05) behind the noise: a subset of WEATHER_MEMBERS in its order, "all" = both, () = off
     weather_members=(), weather_p=0.05,
+    # GlassBlur (defaults: sigma 0.7, max_delta 4, two iterations, mode "fast") as the fifth member of the blur OneOf: a crop on which
+    # the group fired takes it at 1 / 5
+    glass_blur=False,
 )
 
 TONE_NONE, TONE_GRAY, TONE_SEPIA = 0, 1, 2
@@ -53,6 +56,9 @@ DEVICE_COLOUR_KINDS = (COLOUR_EQUALIZE, COLOUR_HSV, COLOUR_JITTER, COLOUR_EMBOSS
 JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE = 0, 1, 2, 3       # ColorJitter's operations, as `order` names them
 
 BLUR_NONE, BLUR_BOX, BLUR_GAUSSIAN, BLUR_MEDIAN, BLUR_MOTION = 0, 1, 2, 3, 4
+BLUR_GLASS = 5                                  # GlassBlur (`glass_blur`): recorded in PhotoParams.blur, applied by fear_glass_u8
+GLASS_MAX_DELTA, GLASS_ITERATIONS = 4, 2        # GlassBlur's defaults; its sigma of 0.7 gives cv2's 8-bit kernel GLASS_WEIGHTS
+GLASS_WEIGHTS = (2, 53, 146, 53, 2)
 NOISE_NONE, NOISE_MULTIPLICATIVE, NOISE_GAUSS, NOISE_JPEG = 0, 1, 2, 3
 NOISE_MEMBERS = {"multiplicative": NOISE_MULTIPLICATIVE, "gauss": NOISE_GAUSS, "jpeg": NOISE_JPEG}   # (in the order `noise_members` keeps)
 NOISE_ISO = 4                                   # ISONoise (`iso_noise`): recorded in PhotoParams.noise, applied by fear_hls_u8
@@ -78,7 +84,7 @@ PHOTO_DTYPE, COLOUR_DTYPE, HLS_DTYPE = np.dtype(FearPhotoOp), np.dtype(FearColou
 class PhotoParams:
     """The photometric draws of one batch, every array shaped (B, 2, ...): [:, 0] the template crop, [:, 1] the search crop.  The
     values of all members are drawn; only the drawn member's are used."""
-    blur: np.ndarray             # int32, BLUR_*
+    blur: np.ndarray             # int32, BLUR_* (BLUR_GLASS only with `glass_blur`)
     ksize: np.ndarray            # int32, 3 / 5 / 7
     line: np.ndarray             # (B, 2, 4) int32: MotionBlur's end points xs, ys, xe, ye
     noise: np.ndarray            # int32, NOISE_*

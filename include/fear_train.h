@@ -496,6 +496,7 @@ int fear_train_pairs_u8(const fear_frame* frames, int n_frames, const uint8_t* b
 #define FEAR_PHOTO_BLUR_GAUSSIAN 2
 #define FEAR_PHOTO_BLUR_MEDIAN 3
 #define FEAR_PHOTO_BLUR_MOTION 4
+#define FEAR_PHOTO_BLUR_GLASS 5          /* GlassBlur: "none" to fear_photometric_u8, applied by fear_glass_u8 (below)         */
 #define FEAR_PHOTO_NOISE_NONE 0
 #define FEAR_PHOTO_NOISE_MULTIPLICATIVE 1
 #define FEAR_PHOTO_NOISE_GAUSS 2
@@ -509,7 +510,7 @@ typedef struct FearPhotoOp {
     int32_t ksize;              /* 3, 5 or 7 (read only with a blur)                                                  */
     int32_t noise;              /* FEAR_PHOTO_NOISE_*                                                                 */
     float scale;                /* the multiplier m, or sigma = fp32(sqrt(var))                                       */
-    uint32_t key[2];            /* the crop's Philox key (GaussNoise)                                                 */
+    uint32_t key[2];            /* the crop's Philox key (GaussNoise, GlassBlur)                                      */
     int32_t downscale;          /* non-zero: Downscale(0.5)                                                           */
     int32_t tap_row;            /* MotionBlur's row of `taps`, -1 otherwise                                           */
 } FearPhotoOp;
@@ -975,6 +976,25 @@ _Static_assert(sizeof(FearHlsOp) == 32, "FearHlsOp is 32 bytes");
 
 int fear_hls_u8(const uint8_t* crops_in, int n, int H, int W, const FearHlsOp* ops, const int16_t* segments, const float* qtable,
                 const double* exp_table, uint8_t* crops_out, void* stream);
+
+/* ---- GlassBlur, the fifth member of the reference's blur group (model_training/dataset/aug.py:8-25), with albumentations' defaults
+ * (sigma 0.7, max_delta 4, iterations 2, mode "fast"), on uint8 HWC crops in front of fear_photometric_stage_u8 / fear_photometric_u8,
+ * to which a record of this kind is "none" (DESIGN.md section 11 states the contract; train_data.glass_u8_host restates it in numpy
+ * and the two agree bit for bit).  A crop whose record's blur is FEAR_PHOTO_BLUR_GLASS takes, all three channels alike:
+ *   1  cv2.GaussianBlur(ksize (0, 0), sigma 0.7) on 8 bits: 5 x 5, the weights (2, 53, 146, 53, 2) on both axes,
+ *      (sum_y sum_x w_y w_x p + 32768) >> 16, BORDER_REFLECT_101
+ *   2  for i = 0, 1: over the pixels h in [5, H - 4], w in [5, W - 4], element n = (H - 4 - h) + (H - 8) (W - 4 - w), with dy = (word & 7)
+ *      - 4 and dx = ((word >> 3) & 7) - 4 of word 0 of Philox4x32-10(counter (w, h, 1 + i, 0), the record's key):
+ *      x[h, w], x[h + dy, w + dx] = x[h + dy, w + dx], x[h, w], both right-hand sides read before the iteration, the first assignment
+ *      made for every n before the second, and the largest n winning where the second assignment's targets repeat.  No such pixel
+ *      when H <= 8 or W <= 8
+ *   3  the Gaussian of 1 again
+ * Every other crop is copied.  One workgroup per 32 x 32 tile with its neighbourhood of 12 pixels in LDS; the scatter of 2 is a gather
+ * over the 8 x 8 sources that can reach a pixel: no atomics, no workspace.
+ * H and W must be even, >= 4 and <= 256, n <= 65535, crops_u8 != out_u8: FEAR_TRAIN_ERR_SHAPE otherwise (fear_hls_u8's checks).  n == 0
+ * returns FEAR_TRAIN_OK without a launch.  A null crops_u8, ops or out_u8 returns FEAR_TRAIN_ERR_NULL.
+ *   crops_u8, out_u8 : (n, H, W, 3) uint8, device, distinct      ops : (n) FearPhotoOp, device (blur and key are read)               */
+int fear_glass_u8(const uint8_t* crops_u8, int n, int H, int W, const FearPhotoOp* ops, uint8_t* out_u8, void* stream);
 
 /* ---- step metrics: the training telemetry of the reference's `_training_step` (train/fear_lightning_model.py:66-87) on the device
  * (feartracker_amd/metrics.py).  Per pair: FEARBoxCoder.decode of the step's own output maps (fear_decode's

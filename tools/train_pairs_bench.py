@@ -39,6 +39,14 @@ pairs and frames, the photometric stage on), in ONE run on one commit:
   hls_u8_ms          fear_hls_u8 alone on the batch's 128 templates and 128 searches (two calls), every crop forced to one member, per
                      member (ISONoise, rain with its H W // 600 drops, a shadow of two polygons), HIP events
   step_ms            FEARNetTrainHIP.step on fixed inputs, for the shares
+With --glass it reports GlassBlur, the member behind `glass_blur` (same pairs and frames, the photometric stage on):
+  build_default_ms   `build` with photometric=True and the default members, one figure per fresh process; with --parent-root DIR against
+                     that checkout's `build` in alternating processes, as above: the same launches, so a difference beyond the spread
+                     is a finding
+  build_on_ms        `build` with glass_blur=True at the reference's probabilities, fresh draws per call
+  glass_u8_ms        fear_glass_u8 alone on the batch's 128 templates and 128 searches (two calls), every crop forced to the member, HIP
+                     events
+  step_ms            FEARNetTrainHIP.step on fixed inputs, for the shares
 With --store DIR it reports the resident JPEG store in front of the builder (DIR holds the files of tools/jpeg_decode_bench.py --make,
 256 synthetic 1280 x 720 files; 128 pairs, two frames of their own per pair), in ONE run, medians of `--repeats` + 2 runs with minimum and
 maximum, a host clock around work that ends in a synchronise:
@@ -54,6 +62,7 @@ Usage: python tools/train_pairs_bench.py [--pairs 128] [--frames 256] [--steps 2
        python tools/train_pairs_bench.py --colour all [--parent-root DIR] [--repeats 3] [--out profiles/train_pairs_colour_bench.json]
        python tools/train_pairs_bench.py --noise all [--parent-root DIR] [--repeats 3] [--out profiles/train_pairs_jpeg_bench.json]
        python tools/train_pairs_bench.py --iso --weather all [--repeats 3] [--out profiles/train_pairs_hls_bench.json]
+       python tools/train_pairs_bench.py --glass [--parent-root DIR] [--repeats 3] [--out profiles/train_pairs_glass_bench.json]
        python tools/train_pairs_bench.py --store DIR [--repeats 3] [--out profiles/train_pairs_store_bench.json]
 """
 from __future__ import annotations
@@ -111,15 +120,17 @@ def build_only(args):
         config["iso_noise"] = True
     if args.weather:
         config["weather_members"] = args.weather
+    if args.glass:
+        config["glass_blur"] = True
     builder = TrainPairBuilder(config or None, device=0, seed=0)
     print(json.dumps({"build_ms": round(_time_build(builder, frames, pairs, args.iters), 4)}))
 
 
-def _child(root, args, stage_on=False, colour=None, noise=None, iso=False, weather=None):
+def _child(root, args, stage_on=False, colour=None, noise=None, iso=False, weather=None, glass=False):
     cmd = [sys.executable, os.path.abspath(__file__), "--build-only", "--root", root, "--pairs", str(args.pairs), "--frames",
            str(args.frames), "--iters", str(args.iters)] + (["--stage-on"] if stage_on else []) + (["--colour", colour] if colour else [])
     cmd += ["--noise", noise] if noise else []
-    cmd += (["--iso"] if iso else []) + (["--weather", weather] if weather else [])
+    cmd += (["--iso"] if iso else []) + (["--weather", weather] if weather else []) + (["--glass"] if glass else [])
     res = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300)
     return json.loads(res.stdout.strip().splitlines()[-1])["build_ms"]
 
@@ -400,6 +411,59 @@ def hls(args):
     }
 
 
+def glass(args):
+    # the fresh processes first, one at a time, before this process opens the GPU
+    default, parent, on = [], [], []
+    for _ in range(args.repeats):
+        default.append(_child(ROOT, args, stage_on=True))
+        if args.parent_root:
+            parent.append(_child(args.parent_root, args, stage_on=True))
+        on.append(_child(ROOT, args, stage_on=True, glass=True))
+    sys.path.insert(0, ROOT)
+    from feartracker_amd.train_abi import load_train_library
+    from feartracker_amd.train_data import BLUR_GLASS, PHOTO_DTYPE
+    dev = torch.device("cuda", 0)
+    B = args.pairs
+    lib = load_train_library()
+    P = ctypes.c_void_p
+    st = P(torch.cuda.current_stream(dev).cuda_stream)
+    g = torch.Generator(device=dev).manual_seed(1)
+    crops = [torch.randint(0, 256, (B, s, s, 3), generator=g, device=dev, dtype=torch.uint8) for s in (128, 256)]
+    outs = [torch.empty_like(c) for c in crops]
+    ops = np.zeros(B, dtype=PHOTO_DTYPE)
+    ops["blur"], ops["tap_row"], ops["key"] = BLUR_GLASS, -1, np.random.default_rng(2).integers(0, 2 ** 32, (B, 2))
+    d_ops = torch.from_numpy(ops.view(np.uint8).copy()).to(dev)
+
+    def both():
+        for c, o, s in zip(crops, outs, (128, 256)):
+            assert lib.fear_glass_u8(P(c.data_ptr()), B, s, s, P(d_ops.data_ptr()), P(o.data_ptr()), st) == 0
+
+    for _ in range(5):
+        both()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.iters):
+        both()
+    e1.record()
+    torch.cuda.synchronize()
+    glass_ms = e0.elapsed_time(e1) / args.iters
+    frames, pairs = _inputs(B, args.frames, dev)
+    step_ms, steps = _step_ms(args, frames, pairs)
+    med = lambda v: round(float(np.median(v)), 4) if v else None
+    return {
+        "pairs": B, "frames": args.frames, "frame_hw": [1080, 1920], "iters": args.iters, "glass_blur": True,
+        "build_default_ms": med(default), "build_default_runs": default,
+        "parent_build_ms": med(parent), "parent_build_runs": parent,
+        "build_on_ms": med(on), "build_on_runs": on,
+        "glass_u8_ms": round(glass_ms, 4),
+        "step_ms": round(step_ms, 3), "step_ms_runs": [round(v, 3) for v in steps],
+        "member_ms": round(med(on) - med(default), 4),
+        "member_pct_of_step": round(100.0 * (med(on) - med(default)) / step_ms, 2),
+        "glass_u8_pct_of_step": round(100.0 * glass_ms / step_ms, 2),
+        "device": torch.cuda.get_device_name(0),
+    }
+
+
 def store_mode(args):
     """decode + build against decode_rows + build(borders=) out of a resident store."""
     import glob
@@ -477,6 +541,7 @@ def main():
     ap.add_argument("--noise", default=None, help='"all": report ImageCompression, the member behind noise_members')
     ap.add_argument("--iso", action="store_true", help="report ISONoise, the member behind iso_noise")
     ap.add_argument("--weather", default=None, help='"all": report RandomRain and RandomShadow, the members behind weather_members')
+    ap.add_argument("--glass", action="store_true", help="report GlassBlur, the member behind glass_blur")
     ap.add_argument("--store", default=None, help="DIR of the synthetic 720p files: the resident store in front of the builder")
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--repeats", type=int, default=3)
@@ -489,6 +554,9 @@ def main():
     if args.store:
         args.out = args.out or os.path.join(ROOT, "profiles", "train_pairs_store_bench.json")
         return emit(store_mode(args), args)
+    if args.glass:
+        args.out = args.out or os.path.join(ROOT, "profiles", "train_pairs_glass_bench.json")
+        return emit(glass(args), args)
     if args.iso or args.weather:
         args.out = args.out or os.path.join(ROOT, "profiles", "train_pairs_hls_bench.json")
         return emit(hls(args), args)
