@@ -205,6 +205,11 @@ __global__ __launch_bounds__(256) void pw_mfma_kernel(PwArgs a) {
 // vertical strip of RO output pixels, so consecutive lanes walk (channel-group, x): every global
 // load/store instruction of a wavefront covers one contiguous 1 KiB run, and each input row is loaded
 // once per strip and reused by all output rows it contributes to.
+// The depthwise kernels address a tensor with buffer loads (a tap outside the map = an out-of-range offset = zero, no branch) while its
+// span fits a buffer resource's 32-bit offsets, and with plain loads behind a branch from this many bytes on.  One constant for
+// dw_conv_kernel, dw_stat_kernel, dw_dgrad_kernel and for the host's plan query (fear_layer_plan_info).
+constexpr long FEAR_DW_PLAIN_SPAN = 1L << 31;
+
 struct DwArgs {
     const float* X;   // [B][H][W][ldx]
     const float* Wt;  // [KS*KS][C]  (tap-major, channel-contiguous)
@@ -243,7 +248,7 @@ __global__ __launch_bounds__(256) void dw_conv_kernel(DwArgs a) {
     const int iy0 = oy0 * S - P;
     const int ix0 = ox * S - P;
     const long xbytes = (long)a.B * a.H * a.W * a.ldx * 4;
-    if (xbytes < (1L << 31)) {
+    if (xbytes < FEAR_DW_PLAIN_SPAN) {
         // Branch-free taps: a tap outside the map is a buffer load with an out-of-range offset, which returns the zero padding
         // without a memory access.  With a branch around every load (the form below) the compiler emitted load, wait, FMA one
         // tap after the other — IR x KS dependent memory round trips per thread; the training step's depthwise forward ran at

@@ -694,6 +694,9 @@ struct DwWgradArgs {
     int act_relu;
 };
 
+// output pixels of one row a lane takes as one run where the row divides into runs (Wo % T == 0): the kernel's T and the plan query's
+constexpr int dw_wgrad_run(int stride) { return stride == 1 ? 8 : 4; }
+
 template <int KS, int S>
 __global__ __launch_bounds__(256) void dw_wgrad_kernel(DwWgradArgs a) {
     constexpr int P = KS / 2, KK = KS * KS;
@@ -706,7 +709,7 @@ __global__ __launch_bounds__(256) void dw_wgrad_kernel(DwWgradArgs a) {
     for (int t = 0; t < KK; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const long p0 = (long)blockIdx.x * a.rpb;
     const long p1 = p0 + a.rpb < a.pixels ? p0 + a.rpb : a.pixels;
-    constexpr int T = S == 1 ? 8 : 4, WIN = S * (T - 1) + KS;
+    constexpr int T = dw_wgrad_run(S), WIN = S * (T - 1) + KS;
     const bool act = a.act_a != nullptr;
     f32x4 ia = (f32x4){0.f, 0.f, 0.f, 0.f}, ib = ia;
     if (act && rl < R) { ia = *reinterpret_cast<const f32x4*>(a.act_a + cq * 4); ib = *reinterpret_cast<const f32x4*>(a.act_b + cq * 4); }
@@ -798,7 +801,7 @@ __global__ __launch_bounds__(256) void dw_dgrad_kernel(DwDgradArgs a) {
     const long b = idx / a.H;
     f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
     const long dybytes = (a.total / ((long)a.H * a.W * c4n)) * a.Ho * a.Wo * a.lddy * 4;      // B x Ho x Wo x lddy floats
-    if (dybytes < (1L << 31)) {
+    if (dybytes < FEAR_DW_PLAIN_SPAN) {
         // Branch-free: only the taps whose parity matches the stride are visited (ky = ky0 + S j), and one that falls outside the
         // map is a buffer load with an out-of-range offset (returns zero, no memory access) — all loads of a thread are in flight
         // together.  With a branch around every tap the stride-2 kernels ran at 2.8-3.4 TB/s (profiles/r04_train_traffic_before.txt).
@@ -1386,7 +1389,7 @@ __global__ __launch_bounds__(256) void dw_stat_kernel(DwStatArgs a) {
         const int iy0 = oy0 * S - P;
         const int ix0 = ox * S - P;
         const long xbytes = (long)a.B * a.H * a.W * a.ldx * 4;
-        if (xbytes < (1L << 31)) {
+        if (xbytes < FEAR_DW_PLAIN_SPAN) {
             // branch-free taps (dw_conv_kernel's form, fear_kernels.h): a tap outside the map is a buffer load with an out-of-range
             // offset — no memory access, and all KS loads of a row are in flight together; its ACTIVATION is forced to zero
             // (act(0) = max(b, 0) is not the padding).  Same products in the same order as the branchy form below.
@@ -1522,6 +1525,27 @@ __global__ __launch_bounds__(256) void bn_act_kernel(BnActArgs a) {
     *reinterpret_cast<f32x4*>(a.Y + r * a.ldy + c) = y;
 }
 
+// fear_pw_forward_stats' launch: one workgroup (one partial row of sums) per 128 rows, every output tile in passes of nt
+struct PwStatShape { int blocks, nt; };
+PwStatShape pw_stat_shape(long M, int N) { return PwStatShape{(int)((M + 127) / 128), train_pick_nt((N + 15) / 16)}; }
+
+// The depthwise forward's launch (dw_conv_kernel, dw_stat_kernel): a thread = 4 channels of a strip of 4 output rows of one column;
+// and whether those kernels and dw_dgrad_kernel address the tensor with plain loads: the kernels' own test against
+// FEAR_DW_PLAIN_SPAN (fear_kernels.h), over the span the kernels form (`xbytes`, `dybytes`).
+struct DwFwdShape { long strips, total, blocks; };
+DwFwdShape dw_fwd_shape(int B, int Ho, int Wo, int C) {
+    DwFwdShape g{};
+    g.strips = (Ho + 3) / 4;
+    g.total = (long)B * g.strips * Wo * (C / 4);
+    g.blocks = (g.total + 255) / 256;
+    return g;
+}
+// dw_dgrad_kernel: one thread per input pixel and channel quad
+long dw_dgrad_threads(int B, int H, int W, int C) { return (long)B * H * W * (C / 4); }
+bool dw_plain_loads(long B, long H, long W, long ld) { return !(B * H * W * ld * 4 < FEAR_DW_PLAIN_SPAN); }
+// ... and the weight gradient's row-run path (dw_wgrad_kernel: runs of T output pixels of one row)
+bool dw_wgrad_row_run(int Wo, int stride) { return Wo % dw_wgrad_run(stride) == 0; }
+
 void launch_pw_stat(const PwStatArgs& a, dim3 grid, int nt, hipStream_t s) {
     dispatch_nt(nt, [&](auto NT) { hipLaunchKernelGGL((pw_stat_kernel<NT()>), grid, dim3(256), 0, s, a); });
 }
@@ -1601,7 +1625,7 @@ struct WgradCall {
 // Which kernel one such problem takes, its output tiles and its row slices — from the shapes and from what the operands carry (stem: X'
 // gathered from the image; dy_masked: a BatchNorm backward on dY with a ReLU mask; dy_lin: one without its raw tensor, BnbIn.E = null):
 // wgrad_impl launches by it, the plan queries (fear_irb_plan_info, fear_pwbn_plan_info) report it.
-struct WgradLaunch { bool swapped, lds_tile; int n_tiles, k_tiles; WgradPlan plan; };
+struct WgradLaunch { bool swapped, lds_tile; int n_tiles, k_tiles; WgradPlan plan; int kb; };
 static WgradLaunch wgrad_launch_plan(long M, int K, int N, int crops, bool stem, bool dy_masked, bool dy_lin, size_t ws_bytes) {
     WgradLaunch w{};
     // a narrow dY against a wide X (the projections of the large maps): the operands trade places in pw_wgrad_smallk_kernel<., 2>
@@ -1614,6 +1638,8 @@ static WgradLaunch wgrad_launch_plan(long M, int K, int N, int crops, bool stem,
     w.n_tiles = (N + 63) / 64; w.k_tiles = (K + 63) / 64;
     if (w.lds_tile) { w.n_tiles = (N + 127) / 128; w.k_tiles = (K + 127) / 128; }
     if (w.swapped) { w.n_tiles = (K + 63) / 64; w.k_tiles = 1; }
+    // the 16-column k-blocks of pw_wgrad_smallk_kernel's narrow side (swapped: that side is dY's N columns); 0: a 64 x 64 or staged tile
+    w.kb = w.swapped ? (N <= 16 ? 1 : 2) : K <= 16 ? 1 : K <= 32 ? 2 : 0;
     // (per-crop problems are one slice each; one problem is cut by wgrad_plan)
     // at most 256 slices — 1 024 where the partial is small (N * K <= 8 192: the stem and the 16-32-channel layers of the
     // 128 x 128 / 64 x 64 maps) or the operands are swapped: those layers have millions of rows and ONE or two output tiles, 256
@@ -1655,11 +1681,11 @@ static int wgrad_impl(const WgradCall& c) {
         if (!workspace || ws_bytes < need) return FEAR_TRAIN_ERR_WORKSPACE;
         a.P = workspace;
     }
-    if (swapped && N <= 16) hipLaunchKernelGGL((pw_wgrad_smallk_kernel<1, 2>), dim3(a.n_tiles, slices, 1), dim3(256), 0, s, a);
+    if (swapped && wl.kb == 1) hipLaunchKernelGGL((pw_wgrad_smallk_kernel<1, 2>), dim3(a.n_tiles, slices, 1), dim3(256), 0, s, a);
     else if (swapped) hipLaunchKernelGGL((pw_wgrad_smallk_kernel<2, 2>), dim3(a.n_tiles, slices, 1), dim3(256), 0, s, a);
-    else if (K <= 16) hipLaunchKernelGGL(pw_wgrad_smallk_kernel<1>, dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
-    else if (K <= 32 && stem) hipLaunchKernelGGL((pw_wgrad_smallk_kernel<2, 1>), dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
-    else if (K <= 32) hipLaunchKernelGGL(pw_wgrad_smallk_kernel<2>, dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
+    else if (wl.kb == 1) hipLaunchKernelGGL(pw_wgrad_smallk_kernel<1>, dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
+    else if (wl.kb == 2 && stem) hipLaunchKernelGGL((pw_wgrad_smallk_kernel<2, 1>), dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
+    else if (wl.kb == 2) hipLaunchKernelGGL(pw_wgrad_smallk_kernel<2>, dim3(a.n_tiles, slices, crops), dim3(256), 0, s, a);
     else if (lds_tile) hipLaunchKernelGGL(wgrad_lds_kernel<0>, dim3(a.n_tiles * a.k_tiles, slices), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(pw_wgrad_kernel, dim3(a.n_tiles * a.k_tiles, slices, crops), dim3(256), 0, s, a);
     if (slices > 1) launch_slice_sum(workspace, dw, (long)crops * N * K, slices, s);
@@ -1669,6 +1695,7 @@ static int wgrad_impl(const WgradCall& c) {
 
 int fear_pw_backward_weight(const float* dy, int lddy, const float* x, int ldx, float* dw, float* workspace, size_t ws_bytes,
                             long M, int K, int N, void* stream) {
+    if (M == 0) return FEAR_TRAIN_OK;
     if (!dy || !x || !dw) return FEAR_TRAIN_ERR_NULL;
     if (!pw_shape_ok(M, K, N) || !ld_ok(lddy, N) || !ld_ok(ldx, K)) return FEAR_TRAIN_ERR_SHAPE;    // float4 loads of both operands
     return wgrad_impl({.dy = dy, .lddy = lddy, .x = x, .ldx = ldx, .dw = dw, .workspace = workspace, .ws_bytes = ws_bytes, .M = M, .K = K, .N = N,
@@ -1676,6 +1703,7 @@ int fear_pw_backward_weight(const float* dy, int lddy, const float* x, int ldx, 
 }
 
 int fear_col_sum(const float* dy, int lddy, float* out, float* workspace, size_t ws_bytes, long M, int C, void* stream) {
+    if (M == 0) return FEAR_TRAIN_OK;
     if (!dy || !out || !workspace) return FEAR_TRAIN_ERR_NULL;
     if (!bn_shape_ok(M, C)) return FEAR_TRAIN_ERR_SHAPE;
     if (!ld_ok(lddy, C)) return FEAR_TRAIN_ERR_SHAPE;      // float4 rows
@@ -1696,9 +1724,7 @@ static int dw_impl(const float* x, int ldx, const float* w, const float* bias, f
     DwArgs a{};
     a.X = x; a.ldx = ldx; a.Wt = w; a.bias = bias; a.Y = y; a.ldy = ldy;
     a.B = B; a.H = H; a.W = W; a.C = C; a.Ho = H / stride; a.Wo = W / stride; a.relu = 0;
-    const long strips = (a.Ho + 3) / 4;
-    const long total = (long)B * strips * a.Wo * (C / 4);
-    dim3 grid((unsigned)((total + 255) / 256));
+    dim3 grid((unsigned)dw_fwd_shape(B, a.Ho, a.Wo, C).blocks);
     dispatch_ks(k, stride, [&](auto KS, auto S) { hipLaunchKernelGGL((dw_conv_kernel<KS(), S(), 4>), grid, dim3(256), 0, s, a); });
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
@@ -1722,7 +1748,7 @@ static int dw_dgrad_impl(const float* dy, int lddy, const float* w_taps, float* 
                          hipStream_t s) {
     DwDgradArgs a{};
     a.dY = dy; a.Wt = w_taps; a.dX = dx; a.H = H; a.W = W; a.Ho = H / stride; a.Wo = W / stride; a.C = C; a.lddy = lddy; a.lddx = lddx;
-    a.total = (long)B * H * W * (C / 4);
+    a.total = dw_dgrad_threads(B, H, W, C);
     dim3 grid((unsigned)((a.total + 255) / 256));
     dispatch_ks(k, stride, [&](auto KS, auto S) { hipLaunchKernelGGL((dw_dgrad_kernel<KS(), S()>), grid, dim3(256), 0, s, a); });
     LAUNCH_CHECK();
@@ -1756,6 +1782,7 @@ static int dw_wgrad_impl(const float* dy, int lddy, const float* x, int ldx, flo
 
 int fear_dw_backward_weight(const float* dy, int lddy, const float* x, int ldx, float* dw_taps, float* workspace,
                             size_t ws_bytes, int B, int H, int W, int C, int k, int stride, void* stream) {
+    if (B == 0) return FEAR_TRAIN_OK;
     if (!dy || !x || !dw_taps || !workspace) return FEAR_TRAIN_ERR_NULL;
     if (B < 1 || !dw_shape_ok(B, H, W, C, k, stride)) return FEAR_TRAIN_ERR_SHAPE;
     if (!ld_ok(lddy, C) || !ld_ok(ldx, C)) return FEAR_TRAIN_ERR_SHAPE;      // float4 rows
@@ -1777,6 +1804,7 @@ int fear_stem_im2col(const float* x_nchw, float* rows28, long n, int H, int W, v
 int fear_bn_train_forward(const float* x, int ldx, const float* gamma, const float* beta, float* y, int ldy, float* mean,
                           float* rstd, float* running_mean, float* running_var, double momentum, double eps, long M, int C,
                           int relu, float* workspace, size_t ws_bytes, void* stream) {
+    if (M == 0) return FEAR_TRAIN_OK;
     if (!x || !gamma || !beta || !y || !mean || !rstd || !workspace) return FEAR_TRAIN_ERR_NULL;
     if (!bn_shape_ok(M, C)) return FEAR_TRAIN_ERR_SHAPE;
     if (!ld_ok(ldx, C) || !ld_ok(ldy, C)) return FEAR_TRAIN_ERR_SHAPE;      // float4 rows
@@ -1800,6 +1828,7 @@ int fear_bn_train_forward(const float* x, int ldx, const float* gamma, const flo
 int fear_bn_train_backward(const float* dy, int lddy, const float* y_act, int ldy, const float* x, int ldx, const float* mean,
                            const float* rstd, const float* gamma, float* dx, int lddx, float* dgamma, float* dbeta, long M,
                            int C, float* workspace, size_t ws_bytes, void* stream) {
+    if (M == 0) return FEAR_TRAIN_OK;
     if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || !workspace) return FEAR_TRAIN_ERR_NULL;
     if (!bn_shape_ok(M, C)) return FEAR_TRAIN_ERR_SHAPE;
     if (!ld_ok(lddy, C) || !ld_ok(ldx, C) || !ld_ok(lddx, C) || (y_act && !ld_ok(ldy, C))) return FEAR_TRAIN_ERR_SHAPE;      // float4 rows
@@ -1823,9 +1852,11 @@ int fear_bn_train_backward(const float* dy, int lddy, const float* y_act, int ld
 // ---- fused conv + BatchNorm operators (see "Fused conv + BatchNorm operators" above) ----------------------------------------
 int fear_pw_forward_stats(const float* x, int ldx, const float* in_a, const float* in_b, int in_relu, const float* w, float* y,
                           int ldy, long M, int K, int N, double* sums, float* workspace, size_t ws_bytes, void* stream) {
+    if (M == 0) return FEAR_TRAIN_OK;
     if (!x || !w || !y || !sums || !workspace || (in_a && !in_b)) return FEAR_TRAIN_ERR_NULL;
     if (!pw_shape_ok(M, K, N) || N > 1024 || M > 0x7fffffffL || !ld_ok(ldx, K) || !ld_ok(ldy, N)) return FEAR_TRAIN_ERR_SHAPE;
-    const int blocks = (int)((M + 127) / 128);
+    const PwStatShape shape = pw_stat_shape(M, N);
+    const int blocks = shape.blocks;
     if (ws_bytes < (size_t)blocks * 2 * N * sizeof(double)) return FEAR_TRAIN_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     PwStatArgs a{};
@@ -1833,7 +1864,7 @@ int fear_pw_forward_stats(const float* x, int ldx, const float* in_a, const floa
     a.in.a = in_a; a.in.b = in_b; a.in.relu = in_relu;
     a.partial = reinterpret_cast<double*>(workspace);
     dim3 grid((unsigned)blocks);
-    launch_pw_stat(a, grid, train_pick_nt((N + 15) / 16), s);
+    launch_pw_stat(a, grid, shape.nt, s);
     finalize_sums(a.partial, blocks, N, sums, s);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
@@ -1842,14 +1873,13 @@ int fear_pw_forward_stats(const float* x, int ldx, const float* in_a, const floa
 int fear_dw_forward_stats(const float* x, int ldx, const float* in_a, const float* in_b, int in_relu, const float* w_taps, float* y,
                           int ldy, int B, int H, int W, int C, int k, int stride, double* sums, float* workspace, size_t ws_bytes,
                           void* stream) {
+    if (B == 0) return FEAR_TRAIN_OK;
     if (!x || !w_taps || !y || !sums || !workspace || (in_a && !in_b)) return FEAR_TRAIN_ERR_NULL;
     if (B < 1 || !dw_shape_ok(B, H, W, C, k, stride) || !ld_ok(ldx, C) || !ld_ok(ldy, C)) return FEAR_TRAIN_ERR_SHAPE;
     DwStatArgs a{};
     a.X = x; a.ldx = ldx; a.Wt = w_taps; a.Y = y; a.ldy = ldy; a.B = B; a.H = H; a.W = W; a.C = C; a.Ho = H / stride; a.Wo = W / stride;
     a.in.a = in_a; a.in.b = in_b; a.in.relu = in_relu;
-    const long strips = (a.Ho + 3) / 4;
-    const long total = (long)B * strips * a.Wo * (C / 4);
-    const long blocks = (total + 255) / 256;
+    const long blocks = dw_fwd_shape(B, a.Ho, a.Wo, C).blocks;
     if (blocks > 0x7fffffffL) return FEAR_TRAIN_ERR_SHAPE;
     if (ws_bytes < (size_t)blocks * 2 * C * sizeof(double)) return FEAR_TRAIN_ERR_WORKSPACE;
     a.partial = reinterpret_cast<double*>(workspace);
@@ -1897,6 +1927,7 @@ int fear_bn_act(const float* x, int ldx, const float* a, const float* b, int rel
 int fear_bn_backward_reduce_x(const float* dy, int lddy, const float* x, int ldx, const float* act_a, const float* act_b, int relu,
                               const float* mean, const float* rstd, double* sums, long M, int C, float* workspace, size_t ws_bytes,
                               void* stream) {
+    if (M == 0) return FEAR_TRAIN_OK;
     if (!dy || !x || !mean || !rstd || !sums || !workspace || (relu && (!act_a || !act_b))) return FEAR_TRAIN_ERR_NULL;
     if (!bn_shape_ok(M, C) || !ld_ok(lddy, C) || !ld_ok(ldx, C)) return FEAR_TRAIN_ERR_SHAPE;
     if (ws_bytes < col_partial_bytes(M, C)) return FEAR_TRAIN_ERR_WORKSPACE;
@@ -1914,6 +1945,7 @@ int fear_bn_backward_apply_x(const float* dy, int lddy, const float* x, int ldx,
                              const float* mean, const float* rstd, const float* gamma, const double* sums_all, double count,
                              const double* sums_local, float* dx, int lddx, float* dgamma, float* dbeta, float* workspace,
                              size_t ws_bytes, long M, int C, void* stream) {
+    if (M == 0) return FEAR_TRAIN_OK;
     if (!dy || !x || !mean || !rstd || !gamma || !sums_all || !sums_local || !dx || !dgamma || !dbeta || !workspace ||
         (relu && (!act_a || !act_b)))
         return FEAR_TRAIN_ERR_NULL;
@@ -1937,6 +1969,7 @@ int fear_bn_backward_apply_x(const float* dy, int lddy, const float* x, int ldx,
 
 int fear_pw_backward_weight_act(const float* dy, int lddy, const float* x, int ldx, const float* in_a, const float* in_b, int in_relu,
                                 float* dw, float* workspace, size_t ws_bytes, long M, int K, int N, void* stream) {
+    if (M == 0) return FEAR_TRAIN_OK;
     if (!dy || !x || !dw || (in_a && !in_b)) return FEAR_TRAIN_ERR_NULL;
     if (!pw_shape_ok(M, K, N) || !ld_ok(lddy, N) || !ld_ok(ldx, K)) return FEAR_TRAIN_ERR_SHAPE;
     return wgrad_impl({.dy = dy, .lddy = lddy, .x = x, .ldx = ldx, .dw = dw, .workspace = workspace, .ws_bytes = ws_bytes, .M = M, .K = K, .N = N,
@@ -1946,6 +1979,7 @@ int fear_pw_backward_weight_act(const float* dy, int lddy, const float* x, int l
 int fear_dw_backward_weight_act(const float* dy, int lddy, const float* x, int ldx, const float* in_a, const float* in_b, int in_relu,
                                 float* dw_taps, float* workspace, size_t ws_bytes, int B, int H, int W, int C, int k, int stride,
                                 void* stream) {
+    if (B == 0) return FEAR_TRAIN_OK;
     if (!dy || !x || !dw_taps || !workspace || (in_a && !in_b)) return FEAR_TRAIN_ERR_NULL;
     if (B < 1 || !dw_shape_ok(B, H, W, C, k, stride) || !ld_ok(lddy, C) || !ld_ok(ldx, C)) return FEAR_TRAIN_ERR_SHAPE;
     return dw_wgrad_impl(dy, lddy, x, ldx, dw_taps, workspace, ws_bytes, B, H, W, C, k, stride, static_cast<hipStream_t>(stream), in_a,
@@ -1960,6 +1994,7 @@ int fear_bn_train_forward_ab(const float* x, int ldx, const float* gamma, const 
                              float* y, int ldy, float* mean, float* rstd, float* a_out, float* b_out, float* running_mean,
                              float* running_var, double momentum, double eps, long M, int C, float* workspace, size_t ws_bytes,
                              void* stream) {
+    if (M == 0) return FEAR_TRAIN_OK;
     if (!x || !gamma || !beta || !y || !mean || !rstd || !a_out || !b_out || !workspace) return FEAR_TRAIN_ERR_NULL;
     if (!bn_shape_ok(M, C) || !ld_ok(ldx, C) || !ld_ok(ldy, C) || (residual && !ld_ok(ldr, C))) return FEAR_TRAIN_ERR_SHAPE;
     if (ws_bytes < col_partial_bytes(M, C)) return FEAR_TRAIN_ERR_WORKSPACE;
@@ -1982,6 +2017,7 @@ int fear_bn_train_forward_ab(const float* x, int ldx, const float* gamma, const 
 int fear_bn_train_backward_x(const float* dy, int lddy, const float* x, int ldx, const float* act_a, const float* act_b, int relu,
                              const float* mean, const float* rstd, const float* gamma, float* dx, int lddx, float* dgamma, float* dbeta,
                              long M, int C, float* workspace, size_t ws_bytes, void* stream) {
+    if (M == 0) return FEAR_TRAIN_OK;
     if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || !workspace || (relu && (!act_a || !act_b)))
         return FEAR_TRAIN_ERR_NULL;
     if (!bn_shape_ok(M, C) || !ld_ok(lddy, C) || !ld_ok(ldx, C) || !ld_ok(lddx, C)) return FEAR_TRAIN_ERR_SHAPE;
@@ -2226,6 +2262,56 @@ int fear_adam_step(float* param, const float* grad, float* exp_avg, float* exp_a
     a.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, step));
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     LAUNCH_CHECK();
+    return FEAR_TRAIN_OK;
+}
+
+// What the layer operators above would launch — host only.  Every figure comes from the helper the launch itself asks: gemm_lds_applies,
+// gemm_lds_shape, train_pw_grid, pw_stat_shape, wgrad_launch_plan, col_rows_per_block / col_blocks, dw_fwd_shape, dw_dgrad_threads.
+static FearLayerGemmPlan layer_gemm_info(long M, int Kred, int Nout) {
+    FearLayerGemmPlan g{};
+    if (gemm_lds_applies(M, Kred, Nout)) {
+        const GemmLdsShape sh = gemm_lds_shape(M, Nout);
+        g.lds = 1; g.row_tile = sh.mt2 ? 128 : 64; g.ntw = sh.ntw; g.col_blocks = sh.col_blocks;
+    } else {
+        int nt = 1;
+        const dim3 grid = train_pw_grid(M, (Nout + 15) / 16, &nt);
+        g.grid_x = (int32_t)grid.x; g.grid_y = (int32_t)grid.y; g.nt = nt;
+    }
+    return g;
+}
+static FearLayerWgradPlan layer_wgrad_info(long M, int K, int N, size_t ws_bytes) {
+    const WgradLaunch w = wgrad_launch_plan(M, K, N, 1, false, false, false, ws_bytes);
+    FearLayerWgradPlan g{};
+    g.swapped = w.swapped; g.lds_tile = w.lds_tile; g.small_k = w.kb; g.n_tiles = w.n_tiles; g.k_tiles = w.k_tiles;
+    g.rows_per_slice = (int32_t)w.plan.rows_per_slice; g.slices = w.plan.slices;
+    return g;
+}
+
+int fear_layer_plan_info(long M, int K, int N, size_t ws_bytes, const FearLayerDwShape* dw, FearLayerPlanInfo* out) {
+    if (!out) return FEAR_TRAIN_ERR_NULL;
+    if (!pw_shape_ok(M, K, N) || M > 0x7fffffffL) return FEAR_TRAIN_ERR_SHAPE;
+    if (dw && (dw->B < 1 || !dw_shape_ok(dw->B, dw->H, dw->W, dw->C, dw->k, dw->stride) || !ld_ok(dw->ld, dw->C))) return FEAR_TRAIN_ERR_SHAPE;
+    FearLayerPlanInfo r{};
+    r.forward = layer_gemm_info(M, K, N);
+    r.dx = layer_gemm_info(M, N, K);
+    const PwStatShape st = pw_stat_shape(M, N);
+    r.stats_blocks = st.blocks; r.stats_nt = st.nt;
+    // (the activation of the _act form is applied to an operand on load: it does not enter the choice of kernel or slices)
+    r.w = layer_wgrad_info(M, K, N, ws_bytes);
+    r.w_act = r.w;
+    r.col_rows = col_rows_per_block(M); r.col_blocks = col_blocks(M);
+    if (dw) {
+        const int Ho = dw->H / dw->stride, Wo = dw->W / dw->stride;
+        const DwFwdShape f = dw_fwd_shape(dw->B, Ho, Wo, dw->C);
+        const long pixels = (long)dw->B * Ho * Wo;
+        r.dw.strips = (int32_t)f.strips; r.dw.workgroups = (int32_t)f.blocks;
+        r.dw.dgrad_workgroups = (int32_t)((dw_dgrad_threads(dw->B, dw->H, dw->W, dw->C) + 255) / 256);
+        r.dw.wgrad_rows = col_rows_per_block(pixels); r.dw.wgrad_workgroups = col_blocks(pixels);
+        r.dw.wgrad_row_run = dw_wgrad_row_run(Wo, dw->stride);
+        r.dw.fwd_plain = dw_plain_loads(dw->B, dw->H, dw->W, dw->ld);
+        r.dw.dgrad_plain = dw_plain_loads(dw->B, Ho, Wo, dw->ld);
+    }
+    *out = r;
     return FEAR_TRAIN_OK;
 }
 

@@ -281,15 +281,25 @@ int gemm_lds_ntw(int n_tiles) {
     return n_tiles < 4 ? 4 : 8;
 }
 
+// The launch shape of gemm_lds_kernel over M rows and N output columns: launch_gemm_lds launches by it, fear_layer_plan_info reports it.
+struct GemmLdsShape { int ntw, col_blocks; bool mt2; };
+GemmLdsShape gemm_lds_shape(long M, int N) {
+    const int n_tiles = (N + 15) / 16;
+    GemmLdsShape g{};
+    g.ntw = gemm_lds_ntw(n_tiles);
+    g.col_blocks = (n_tiles + g.ntw - 1) / g.ntw;
+    // 128-row tiles when that still gives every CU two workgroups, else 64-row tiles
+    g.mt2 = (long)((M + 127) / 128) * g.col_blocks >= 512;
+    return g;
+}
+
 template <int XT, int EPI, bool WKN>
 int launch_gemm_lds(const GemmArgs& a, hipStream_t s, int* row_blocks) {
-    const int n_tiles = (a.N + 15) / 16;
-    const int ntw = gemm_lds_ntw(n_tiles);
-    const int col_blocks_ = (n_tiles + ntw - 1) / ntw;
-    // 128-row tiles when that still gives every CU two workgroups, else 64-row tiles
-    const bool mt2 = (long)((a.M + 127) / 128) * col_blocks_ >= 512;
+    const GemmLdsShape shape = gemm_lds_shape(a.M, a.N);
+    const int ntw = shape.ntw;
+    const bool mt2 = shape.mt2;
     const int bm = mt2 ? 128 : 64;
-    const dim3 grid((unsigned)((a.M + bm - 1) / bm), (unsigned)col_blocks_);
+    const dim3 grid((unsigned)((a.M + bm - 1) / bm), (unsigned)shape.col_blocks);
     if (row_blocks) *row_blocks = (int)grid.x;
 #define FEAR_GEMM_CASE(NTW_)                                                                                          \
     case NTW_:                                                                                                        \

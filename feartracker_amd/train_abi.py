@@ -61,6 +61,7 @@ TRAIN_SYMBOLS = {
     "fear_irb_virtual_ok": ([_P], _i),
     "fear_irb_plan_info": ([_P, _i, _i, _i, _P], _i),            # host only: FearIrbPlanInfo below
     "fear_pwbn_plan_info": ([_l, _i, _i, _i, _i, _P], _i),       # host only: FearPwbnPlanInfo below
+    "fear_layer_plan_info": ([_l, _i, _i, _sz, _P, _P], _i),      # host only: FearLayerPlanInfo below
     "fear_irb_train_forward": ([_P, _P, _P, _P, _i, _i, _i, _d, _d, _P, _sz, _P], _i),
     "fear_irb_train_backward": ([_P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _P, _sz, _P, _P], _i),
     "fear_bn_running_update": ([_P, _d, _P, _P, _d, _d, _i, _P], _i),
@@ -163,6 +164,30 @@ class FearIrbPlanInfo(ctypes.Structure):
 class FearPwbnPlanInfo(ctypes.Structure):
     """include/fear_train.h: what fear_pwbn_train_* / fear_stem_train_* would launch (fear_pwbn_plan_info; host only)."""
     _fields_ = [("rows", _i32), ("forward", FearGemmPlan), ("dx", FearGemmPlan), ("col_rows", _i32), ("w", FearWgradPlan)]
+
+
+class FearLayerGemmPlan(ctypes.Structure):
+    """include/fear_train.h: fear_pw_forward's or fear_pw_backward_data's launch (fear_layer_plan_info)."""
+    _fields_ = [(n, _i32) for n in ("lds", "row_tile", "ntw", "col_blocks", "grid_x", "grid_y", "nt")]
+
+
+class FearLayerWgradPlan(ctypes.Structure):
+    _fields_ = [(n, _i32) for n in ("swapped", "lds_tile", "small_k", "n_tiles", "k_tiles", "rows_per_slice", "slices")]
+
+
+class FearLayerDwShape(ctypes.Structure):
+    _fields_ = [(n, _i32) for n in ("B", "H", "W", "C", "k", "stride", "ld")]
+
+
+class FearLayerDwPlan(ctypes.Structure):
+    _fields_ = [(n, _i32) for n in ("strips", "workgroups", "dgrad_workgroups", "wgrad_rows", "wgrad_workgroups", "wgrad_row_run",
+                                    "fwd_plain", "dgrad_plain")]
+
+
+class FearLayerPlanInfo(ctypes.Structure):
+    """include/fear_train.h: what the layer operators would launch for (M, K, N) and one depthwise shape (fear_layer_plan_info; host only)."""
+    _fields_ = [("forward", FearLayerGemmPlan), ("dx", FearLayerGemmPlan), ("stats_blocks", _i32), ("stats_nt", _i32),
+                ("w", FearLayerWgradPlan), ("w_act", FearLayerWgradPlan), ("col_rows", _i32), ("col_blocks", _i32), ("dw", FearLayerDwPlan)]
 
 
 class FearBnRunning(ctypes.Structure):

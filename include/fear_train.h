@@ -48,6 +48,9 @@ size_t fear_train_workspace_bytes(long rows, int max_channels);
 /* Layout rules for every operator below: activations are row-major [rows][ld] fp32 with 16-byte-aligned bases; channel
  * counts and leading dimensions are multiples of 4 floats (rows are read and written as float4s), ld >= the row's width;
  * violations return FEAR_TRAIN_ERR_SHAPE. */
+/* Empty calls: every operator from here to fear_dw_backward_weight_act returns FEAR_TRAIN_OK for M == 0 (B == 0 for the depthwise ones)
+ * before it looks at any other argument, launches nothing and writes nothing — not even the zeros of an empty sum; negative counts are
+ * FEAR_TRAIN_ERR_SHAPE.  (fear_bn_finalize takes no rows: count < 1 is FEAR_TRAIN_ERR_SHAPE.) */
 /* nn.Conv2d(K, N, 1): y[m][n] = sum_k x[m][k] w[n][k] (+ bias[n]); K, N multiples of 4 (v_mfma_f32_16x16x4_f32) */
 int fear_pw_forward(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, long M, int K, int N,
                     void* stream);
@@ -116,7 +119,10 @@ int fear_pw_forward_stats(const float* x, int ldx, const float* in_a, const floa
 int fear_dw_forward_stats(const float* x, int ldx, const float* in_a, const float* in_b, int in_relu, const float* w_taps, float* y,
                           int ldy, int B, int H, int W, int C, int k, int stride, double* sums, float* workspace, size_t ws_bytes,
                           void* stream);
-/* bytes of workspace the two producers need for `rows` output rows of `channels` channels (partial sums per workgroup) */
+/* bytes of workspace the two producers need for `rows` output rows of `channels` channels (partial sums per workgroup).  The depthwise
+ * producer deals one thread a strip of four output rows: for maps of ONE output row with rows x channels / 4 > 32 768 it launches more
+ * workgroups than this allows for and returns FEAR_TRAIN_ERR_WORKSPACE before launching anything; it then needs
+ * ceil(B * ceil(Ho / 4) * Wo * (C / 4) / 256) * 2 * C doubles (tests/test_train_layer_ops_gpu.py pins both). */
 size_t fear_train_stats_workspace_bytes(long rows, int channels);
 int fear_bn_finalize(const double* sums, double count, const float* gamma, const float* beta, float* mean, float* rstd, float* a_out,
                      float* b_out, float* running_mean, float* running_var, double momentum, double eps, int C, void* stream);
@@ -338,6 +344,34 @@ typedef struct FearPwbnPlanInfo {
     FearWgradPlan w;
 } FearPwbnPlanInfo;
 int fear_pwbn_plan_info(long M, int K, int N, int relu, int stem, FearPwbnPlanInfo* out);
+/* ... and of the layer operators at the top of this file (fear_pw_forward ... fear_dw_backward_weight_act) for M rows, K input and N
+ * output channels — and, when `dw` is given, for one depthwise shape.  Host only; a record of its own (FearGemmPlan's layout is held by
+ * the block tests).  tests/test_train_layer_ops_gpu.py::test_cases_reach_the_branches_they_claim holds every case of that file to it. */
+typedef struct FearLayerGemmPlan {     /* fear_pw_forward (reduction K, N columns) or fear_pw_backward_data (reduction N, K columns) */
+    int32_t lds;                       /* 1: gemm_lds_kernel (csrc/fear_train_gemm.h); 0: the first generation, pw_mfma_kernel */
+    int32_t row_tile, ntw, col_blocks; /* LDS: rows per workgroup (64 or 128), 16-column tiles per workgroup, column blocks (gridDim.y) */
+    int32_t grid_x, grid_y, nt;        /* first generation: row workgroups, column passes dealt over gridDim.y, tiles per pass */
+} FearLayerGemmPlan;
+typedef struct FearLayerWgradPlan {    /* fear_pw_backward_weight[_act] with `ws_bytes` of workspace */
+    int32_t swapped, lds_tile;         /* operands traded (narrow dY) / 128 x 128 tiles staged through LDS */
+    int32_t small_k;                   /* 16-column k-blocks of pw_wgrad_smallk_kernel (1 or 2); 0: a 64 x 64 or staged tile */
+    int32_t n_tiles, k_tiles, rows_per_slice, slices;
+} FearLayerWgradPlan;
+typedef struct FearLayerDwShape { int32_t B, H, W, C, k, stride, ld; } FearLayerDwShape;      /* ld: pitch of x (forward), of dy (input gradient) */
+typedef struct FearLayerDwPlan {
+    int32_t strips, workgroups;        /* forward and _stats: 4-row strips per image column, workgroups (= partial rows of _stats) */
+    int32_t dgrad_workgroups;
+    int32_t wgrad_rows, wgrad_workgroups, wgrad_row_run;      /* output pixels per workgroup, workgroups, 1: runs of T pixels (Wo % T == 0) */
+    int32_t fwd_plain, dgrad_plain;    /* 1: the tensor's span reaches 2^31 bytes, plain loads instead of buffer loads */
+} FearLayerDwPlan;
+typedef struct FearLayerPlanInfo {
+    FearLayerGemmPlan forward, dx;
+    int32_t stats_blocks, stats_nt;    /* fear_pw_forward_stats: workgroups (partial rows), tiles per pass */
+    FearLayerWgradPlan w, w_act;
+    int32_t col_rows, col_blocks;      /* the column reductions over M rows: rows per workgroup, workgroups */
+    FearLayerDwPlan dw;                /* zeros without `dw` */
+} FearLayerPlanInfo;
+int fear_layer_plan_info(long M, int K, int N, size_t ws_bytes, const FearLayerDwShape* dw, FearLayerPlanInfo* out);
 /* The running statistics of one BatchNorm from the `vec` its forward saved (mean | rstd | a | b), for forwards that ran with
  * running_mean = NULL: the shared trunk's two passes (template, search: model/fear_net.py:83-88) may then overlap on two streams,
  * and torch's update order — template pass first — is restored by applying the search pass's update afterwards. */

@@ -30,7 +30,11 @@ def test_struct_mirrors_have_the_headers_layout(tmp_path):
                "FearSepLayer": th.FearSepLayer, "FearSepGrads": th.FearSepGrads,
                # the plan queries' records (fear_irb_plan_info, fear_pwbn_plan_info)
                "FearGemmPlan": train_abi.FearGemmPlan, "FearWgradPlan": train_abi.FearWgradPlan, "FearDwPlan": train_abi.FearDwPlan,
-               "FearIrbPlanInfo": train_abi.FearIrbPlanInfo, "FearPwbnPlanInfo": train_abi.FearPwbnPlanInfo}
+               "FearIrbPlanInfo": train_abi.FearIrbPlanInfo, "FearPwbnPlanInfo": train_abi.FearPwbnPlanInfo,
+               # ... and the layer operators' (fear_layer_plan_info)
+               "FearLayerGemmPlan": train_abi.FearLayerGemmPlan, "FearLayerWgradPlan": train_abi.FearLayerWgradPlan,
+               "FearLayerDwShape": train_abi.FearLayerDwShape, "FearLayerDwPlan": train_abi.FearLayerDwPlan,
+               "FearLayerPlanInfo": train_abi.FearLayerPlanInfo}
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT}/include/fear_train.h"', 'int main(void) {']
     for name, cls in structs.items():
         lines.append(f'  printf("{name} size %zu\\n", sizeof({name}));')
@@ -74,6 +78,12 @@ def test_struct_mirrors_have_the_headers_layout(tmp_path):
     pw = train_abi.FearPwbnPlanInfo()
     assert lib.fear_pwbn_plan_info(1024, 28, 16, 1, 0, None) == -1 and lib.fear_pwbn_plan_info(1024, 27, 16, 1, 0, ctypes.byref(pw)) == -2
     assert lib.fear_pwbn_plan_info(1024, 28, 16, 1, 1, ctypes.byref(pw)) == 0 and (pw.rows, pw.forward.present, pw.dx.present, pw.w.present) == (1024, 1, 0, 1)
+    lay, shape = train_abi.FearLayerPlanInfo(), train_abi.FearLayerDwShape(1, 8, 8, 8, 3, 1, 8)
+    assert lib.fear_layer_plan_info(1024, 32, 16, 0, None, None) == -1 and lib.fear_layer_plan_info(1024, 30, 16, 0, None, ctypes.byref(lay)) == -2
+    assert lib.fear_layer_plan_info(1024, 32, 16, 0, None, ctypes.byref(lay)) == 0 and (lay.forward.lds, lay.forward.row_tile, lay.dw.workgroups) == (1, 64, 0)
+    assert lib.fear_layer_plan_info(1024, 32, 16, 0, ctypes.byref(shape), ctypes.byref(lay)) == 0 and (lay.dw.strips, lay.dw.workgroups) == (2, 1)
+    shape.ld = 6
+    assert lib.fear_layer_plan_info(1024, 32, 16, 0, ctypes.byref(shape), ctypes.byref(lay)) == -2
     sep = th.FearSepLayer()
     assert lib.fear_sepbn_workspace_bytes(ctypes.byref(sep), 2, 16, 16) == 0
     sep.cin, sep.cout = 320, 256
