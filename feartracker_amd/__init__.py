@@ -16,6 +16,7 @@ from .jpeg_huffman import (jpeg_entropy_indexed_host, jpeg_entropy_parallel_host
                            jpeg_scan_index_host, jpeg_scan_prepare_host, scan_row_sub)
 from .jpeg_progressive import jpeg_to_baseline_host
 from .jpeg_store import JpegStore, StoreFrames, StoreFull, plan_decode, plan_decode_rows
+from .visuals import BestWorstMiner, draw_boxes, draw_boxes_host, miner_host
 
 __all__ = [
     "DEFAULT_TRACKING_CONFIG", "TARGET_CLASSIFICATION_KEY", "TARGET_REGRESSION_LABEL_KEY",
@@ -26,4 +27,5 @@ __all__ = [
     "jpeg_scan_index_host", "jpeg_entropy_indexed_host", "JpegStore", "StoreFull", "plan_decode", "plan_decode_rows", "scan_row_sub", "jpeg_pixels_host",
     "jpeg_to_baseline_host", "jpeg_entropy_rows_device_host", "jpeg_rows_device_host",
     "StoreFrames", "search_rows_host",
+    "BestWorstMiner", "draw_boxes", "draw_boxes_host", "miner_host",
 ]

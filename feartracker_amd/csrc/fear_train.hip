@@ -2326,4 +2326,5 @@ int fear_layer_plan_info(long M, int K, int N, size_t ws_bytes, const FearLayerD
 #include "fear_jpeg_huffman.h"
 #include "fear_jpeg_store.h"
 #include "fear_train_metrics.h"
+#include "fear_train_visuals.h"
 #include "fear_train_optim.h"

@@ -326,6 +326,28 @@ class FEARMultiTracker:
             n_streams = int(self._stream.max()) + 1 if len(self._stream) else 0
         return self.net.tracker_rows(self._ctx, self._fidx, int(n_streams), int(self.tracking_config["instance_size"]))
 
+    def draw(self, frames, colour=(0, 255, 0), thickness: int = 5) -> None:
+        """Draw every target's latest box into its stream's frame, in place (`frames`: one frame, or a sequence indexed by stream):
+        `visuals.draw_boxes` on the boxes and frame indices the last `submit` left on the device, on the current stream.  Nothing
+        waits and no box reaches the host, so it may be called before the submit's `PendingBoxes` is read.  `colour` is one colour or
+        one per target, in `ids` order.  The frames must be contiguous uint8 (H, W, 3) device tensors — the frames given to `submit`,
+        or copies of them; a `YUVFrame` or a host frame raises TypeError, and the host path, whose boxes live on the host, raises as
+        `search_rows` does."""
+        from .visuals import draw_boxes
+        if not self.device_path:
+            raise RuntimeError("draw needs the device path (a model with the device entry points, device_crop and "
+                               "device_postprocess on): the host path keeps its boxes on the host")
+        frames = list(frames) if isinstance(frames, (list, tuple)) else [frames]
+        for f in frames:
+            if not isinstance(f, torch.Tensor) or not f.is_cuda:
+                raise TypeError("draw takes uint8 (H, W, 3) RGB frames on the device; convert a YUVFrame with yuv_to_rgb first")
+        if len(self._stream) and int(self._stream.max()) >= len(frames):
+            raise ValueError(f"targets on stream {int(self._stream.max())} but only {len(frames)} frame(s) given")
+        k = len(self._ids)
+        if k == 0:
+            return
+        draw_boxes(frames, self._out[: 16 * k].view(torch.int32).view(k, 4), self._fidx, colour, thickness)
+
     def submit(self, images) -> PendingBoxes:
         """Track every target on its stream's frame (`images`: one frame, or a sequence indexed by stream).  On the device
         path nothing waits for the GPU — every upload is a non-blocking copy from pinned memory, every launch asynchronous

@@ -119,6 +119,9 @@ TRAIN_SYMBOLS = {
     "fear_glass_u8": ([_P, _i, _i, _i, _P, _P, _P], _i),
     # step metrics (metrics.TrainMetrics)
     "fear_train_metrics": ([_P, _P, _P, _P, _P, _i, _i, _P, _P, _P, _P], _i),
+    # boxes drawn into frames, and the best / worst batch miner (visuals.py; FearMinerState below)
+    "fear_draw_boxes_u8": ([_P, _i, _P, _P, _P, _i, _i, _P], _i),
+    "fear_miner_update": ([_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _d, _i, _P, _P, _P], _i),
 }
 
 
@@ -256,6 +259,18 @@ class FearHlsOp(ctypes.Structure):
 
 
 assert ctypes.sizeof(FearHlsOp) == 32 and FearHlsOp.intensity.offset == 16 and FearHlsOp.key.offset == 24
+
+
+FEAR_MINER_MAX_IMAGES = 64
+
+
+class FearMinerState(ctypes.Structure):
+    """include/fear_train.h: the best / worst miner's device state (visuals.MINER_STATE_DTYPE is its numpy form)."""
+    _fields_ = [("has", ctypes.c_int32 * 2), ("step", ctypes.c_int32 * 2), ("score", _d * 2), ("take", ctypes.c_int32 * 2),
+                ("reserved", ctypes.c_int32 * 2), ("pred", (ctypes.c_int32 * 4) * FEAR_MINER_MAX_IMAGES)]
+
+
+assert ctypes.sizeof(FearMinerState) == 1072 and FearMinerState.score.offset == 16 and FearMinerState.pred.offset == 48
 
 
 class FearJpegInfo(ctypes.Structure):

@@ -1047,6 +1047,72 @@ int fear_glass_u8(const uint8_t* crops_u8, int n, int H, int W, const FearPhotoO
 int fear_train_metrics(const float* cls, const float* bbox, const int32_t* gt_box, const int32_t* visible, const int32_t* dataset_id,
                        int B, int n_datasets, double* iou, double* step3, double* accum, void* stream);
 
+/* ---- pictures made on the device (csrc/fear_train_visuals.h; feartracker_amd/visuals.py restates both calls in
+ * numpy, `draw_boxes_host` and `miner_host`, and the two agree byte for byte).
+ *
+ * The rectangle contract.  A box is (x, y, w, h) int32 with corners x0 = min(x, x + w), x1 = max(x, x + w), likewise y0, y1: pt2 =
+ * (x + w, y + h) is inclusive.  For thickness t, o = t / 2 and i = (t - 1) / 2: a pixel belongs to the box's band iff it lies in the outer
+ * rectangle [x0 - o, x1 + o] x [y0 - o, y1 + o] and not in the inner rectangle [x0 + i + 1, x1 - i - 1] x [y0 + i + 1, y1 - i - 1], which is
+ * empty when either range is reversed.  The outline is t pixels wide with square corners, the band is clipped to the image, a box wholly
+ * outside draws nothing, a box thinner than the band is filled.  Boxes on one frame are drawn in index order: the LAST box in index order
+ * whose band holds a pixel gives it its colour.  This is the project's own statement, not cv2.rectangle's thick lines.
+ *
+ * fear_draw_boxes_u8 draws K boxes into uint8 frames in place.  Every argument is read on the device only:
+ *   frames : (n_frames) fear_frame, device: contiguous (h, w, 3) uint8, any sizes; the pixels are WRITTEN (a frame with h <= 0, w <= 0 or
+ *            a null pointer is skipped)
+ *   boxes : (K, 4) int32, device      frame_of : (K) int32, device: the frame of each box, outside [0, n_frames) the box is skipped
+ *   colours : (K, 3) uint8, device
+ * One workgroup of 256 lanes per (box, side): the top and bottom strips over the outer rectangle's width, the left and right strips of
+ * the rows between.  "The last box wins" is a gather: a workgroup first compacts into LDS the later boxes of its frame whose outer
+ * rectangle meets its strip (flags and popcounts, up to 512 boxes; where more meet it, the rest are read from memory per pixel), then a
+ * lane skips a pixel that one of them holds.  Two strips of one box may store the same value to a shared pixel.  No atomics, no order
+ * between workgroups, the same bytes on every run.  Every workgroup reads the K - k - 1 later boxes: the call is meant for hundreds of
+ * boxes, not for 65535 on one frame.
+ * FEAR_TRAIN_ERR_SHAPE: K < 0 or K > 65535, n_frames < 0, thickness outside 1..32.  K == 0 or n_frames == 0 returns FEAR_TRAIN_OK
+ * without a launch.  A null frames, boxes, frame_of or colours returns FEAR_TRAIN_ERR_NULL.                                          */
+int fear_draw_boxes_u8(const fear_frame* frames, int n_frames, const int32_t* boxes, const int32_t* frame_of, const uint8_t* colours, int K,
+                       int thickness, void* stream);
+
+/* The best / worst batch miner: BestWorstMinerCallback of the reference (model_training/train/callbacks.py:95-230) with get_visuals
+ * (train/fear_lightning_model.py:217-258), one call per training step, two launches, nothing read by the host.
+ *   decide   one wave.  s = (double)(fp32 score_a[0] (+ score_b[0] when score_b is given)).  For each side, [0] best and [1] worst: a
+ *            side with has == 0 takes the step; otherwise, mode min (mode_max == 0), best takes s <= score - min_delta and worst takes
+ *            s >= score + min_delta; mode max mirrors them.  A NaN on either side of a comparison takes nothing, so a NaN enters only
+ *            as a first step and then stays.  take[side] is written for every call; a side that takes sets has, score, step =
+ *            step_index.  When either side takes, the first n = min(B, n_images) pairs are decoded (fear_train_metrics's decode), each of
+ *            x, y, w, h truncated toward zero (a NaN is 0, a magnitude above 2^20 is cut to it), into pred.
+ *   render   grid (16, n, 2); a workgroup of a side with take == 0 returns after that load.  Otherwise item k fills rows 256 k ..
+ *            256 k + 255 of the side's sheet: the template in columns 0..127 of the top 128 rows, zeros below it, the search crop in
+ *            columns 128..383.  A normalised value x of channel c becomes 255.0 * ((double)x * std_c + mean_c) in float64, every
+ *            operation rounded on its own, truncated toward zero and cut to 0..255 (a NaN is 0).  On the search crop, clipped to it,
+ *            at thickness 2 by the contract above: first pred[k] in (0, 250, 0), then gt_box[k] in (250, 0, 0) where visible[k] != 0,
+ *            else (0, 0, 250).
+ *   templ (B,3,128,128), search (B,3,256,256) fp32 normalised      cls (B,1,16,16), bbox (B,4,16,16) fp32: the step's outputs
+ *   gt_box (B,4) int32, visible (B) int32      score_a, score_b : device scalars, score_b may be null
+ *   state : device, zeroed to start an epoch      sheets : (2, n 256, 384, 3) uint8, device: [0] best, [1] worst
+ * FEAR_TRAIN_ERR_SHAPE: B < 0 or B > 65535, n_images outside 1..FEAR_MINER_MAX_IMAGES.  B == 0 returns FEAR_TRAIN_OK without a launch.
+ * A null pointer other than score_b returns FEAR_TRAIN_ERR_NULL.                                                                       */
+#define FEAR_MINER_MAX_IMAGES 64
+
+/* The miner's state.  1072 bytes. */
+typedef struct FearMinerState {
+    int32_t has[2];             /* [0] best, [1] worst: the side holds a batch                                          */
+    int32_t step[2];            /* the step_index of that batch                                                        */
+    double score[2];            /* its score                                                                           */
+    int32_t take[2];            /* the last call's decision                                                            */
+    int32_t reserved[2];
+    int32_t pred[FEAR_MINER_MAX_IMAGES][4];   /* the decoded boxes x, y, w, h of the last step that was taken          */
+} FearMinerState;
+#ifdef __cplusplus
+static_assert(sizeof(FearMinerState) == 1072, "FearMinerState is 1072 bytes");
+#else
+_Static_assert(sizeof(FearMinerState) == 1072, "FearMinerState is 1072 bytes");
+#endif
+
+int fear_miner_update(const float* templ, const float* search, const float* cls, const float* bbox, const int32_t* gt_box,
+                      const int32_t* visible, const float* score_a, const float* score_b, int B, int n_images, int mode_max, double min_delta,
+                      int step_index, FearMinerState* state, uint8_t* sheets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
