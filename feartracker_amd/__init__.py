@@ -3,7 +3,7 @@
 Hot path only: `FEARTracker.initialize()/update()` — and `FEARMultiTracker` for many targets per frame — on top of
 `FEARNetHIP.get_features()/track()`, whose arithmetic runs in hand-written gfx950 HIP kernels
 behind the C ABI of include/fear_hip.h.  Both trackers take packed RGB frames or NV12 / I420 video frames (`YUVFrame`);
-`JpegDecoder` decodes baseline JPEG files into such RGB frames on the device.
+`JpegDecoder` decodes baseline JPEG files into such RGB frames on the device, `JpegEncoder` writes such frames out as JPEG files.
 """
 from .constants import DEFAULT_TRACKING_CONFIG, TARGET_CLASSIFICATION_KEY, TARGET_REGRESSION_LABEL_KEY
 from .box_coder import FEARBoxCoder, TrackerDecodeResult, TrackerEncodeResult
@@ -15,6 +15,7 @@ from .jpeg_frames import JpegDecoder, MalformedJPEG, UnsupportedJPEG, jpeg_decod
 from .jpeg_huffman import (jpeg_entropy_indexed_host, jpeg_entropy_parallel_host, jpeg_entropy_rows_device_host, jpeg_rows_device_host,
                            jpeg_scan_index_host, jpeg_scan_prepare_host, scan_row_sub)
 from .jpeg_progressive import jpeg_to_baseline_host
+from .jpeg_encode import JpegEncoder, JpegOverflow, PendingJpegs, jpeg_encode_host, write_mjpeg_avi
 from .jpeg_store import JpegStore, StoreFrames, StoreFull, plan_decode, plan_decode_rows
 from .visuals import BestWorstMiner, draw_boxes, draw_boxes_host, miner_host
 
@@ -28,4 +29,5 @@ __all__ = [
     "jpeg_to_baseline_host", "jpeg_entropy_rows_device_host", "jpeg_rows_device_host",
     "StoreFrames", "search_rows_host",
     "BestWorstMiner", "draw_boxes", "draw_boxes_host", "miner_host",
+    "JpegEncoder", "JpegOverflow", "PendingJpegs", "jpeg_encode_host", "write_mjpeg_avi",
 ]

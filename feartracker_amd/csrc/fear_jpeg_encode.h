@@ -1,0 +1,676 @@
+// fear_jpeg_encode.h — baseline JPEG files written on gfx950 from uint8 RGB frames: the counterpart of fear_jpeg_decode.h and
+// fear_jpeg_huffman.h (include/fear_train.h states the ABI and the passes, DESIGN.md section 14 "Writing JPEG files" the contract;
+// jpeg_encode.jpeg_encode_host restates it in numpy and equals Pillow's libjpeg-turbo byte for byte).  The forward transform shares
+// jpeg_fdct, kJpegBase and the LDS pitch with fear_train_jpeg.h; what is new is frames of any size, the Huffman coder in parallel and
+// the byte stream.
+//
+// Why each launch boundary is there: every one is a dependency across workgroups.
+//   transform | sizes      a block's DC difference reads the block before it, which another workgroup may have transformed
+//   sizes | segments       a block's bit offset is the sum of all bit counts before it in its restart segment
+//   segments | offsets     a segment's byte offset is the sum of all segment lengths before it in its image
+//   offsets | write        a block's place in the stream is its segment's offset plus its own
+//   write | count          a chunk of the stream is complete when every block that touches it has been written
+//   count | lengths        the file's length, and whether it fits, is the sum over all chunks
+//   lengths | assemble     a byte's place in the file is the sum over all chunks before its own; nothing is stored before the file is
+//                          known to fit
+// Included by fear_train.hip behind fear_jpeg_store.h.
+
+#include <algorithm>
+#include <initializer_list>
+
+namespace {
+
+constexpr int kEncMcus = kJpMcus;                              // MCUs per workgroup of the transform: fear_train_jpeg.h's LDS layout
+constexpr int kEncGroup = FEAR_JPEG_ENC_GROUP_BLOCKS;          // blocks per workgroup of sizes and write
+constexpr int kEncChunk = FEAR_JPEG_ENC_CHUNK_BYTES;           // stream bytes per workgroup of count and assemble
+static_assert(kEncGroup == 256 && kEncChunk == 4096, "one lane per block; one lane per 16 bytes of a chunk");
+constexpr uint32_t kEncMcuBytes = 1244;                        // 4 (9 + 11 + 63 x 26) + 2 (11 + 11 + 63 x 26) bits: the longest MCU
+
+// zigzag position -> natural index
+constexpr uint8_t kEncZigzagHost[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                        41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                        30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+__device__ const uint8_t kEncZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                           41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                           30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+constexpr uint8_t kEncBaseHost[128] = {
+    16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
+    18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,  49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99,
+    17, 18, 24, 47, 99,  99,  99,  99,  18, 21, 26, 66, 99,  99,  99,  99,  24, 26, 56, 99, 99,  99,  99,  99,  47, 66, 99, 99, 99,  99,  99,  99,
+    99, 99, 99, 99, 99,  99,  99,  99,  99, 99, 99, 99, 99,  99,  99,  99,  99, 99, 99, 99, 99,  99,  99,  99,  99, 99, 99, 99, 99,  99,  99,  99};
+
+// T.81 tables K.3 to K.6 in the order of the file's DHT segments and of the code table below: DC 0, AC 0, DC 1, AC 1
+struct EncStdTable {
+    uint8_t counts[16];
+    int total;
+    uint8_t values[162];
+};
+constexpr EncStdTable kEncStd[4] = {
+    {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}},
+    {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125}, 162,
+     {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+      0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+      0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+      0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+      0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+      0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+      0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+      0xfa}},
+    {{0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}},
+    {{0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}, 162,
+     {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+      0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+      0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+      0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+      0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+      0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+      0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+      0xfa}},
+};
+
+// symbol -> length << 16 | code (T.81 annex C), per table in kEncStd's order; 0 for a symbol the table lacks
+struct EncCodes {
+    uint32_t v[4 * 256];
+};
+constexpr EncCodes enc_make_codes() {
+    EncCodes c{};
+    for (int t = 0; t < 4; ++t) {
+        uint32_t code = 0;
+        int k = 0;
+        for (int len = 1; len <= 16; ++len) {
+            for (int i = 0; i < kEncStd[t].counts[len - 1]; ++i, ++k) c.v[t * 256 + kEncStd[t].values[k]] = (uint32_t)len << 16 | code++;
+            code <<= 1;
+        }
+    }
+    return c;
+}
+__device__ const EncCodes kEncCodes = enc_make_codes();
+
+// One image's geometry and the layout of its scratch behind work_offset: int16 coefficients [n_blocks][64] | uint32 bits [n_blocks] (a
+// block's bit count, then its bit offset in its segment) | uint32 seg [n_seg + 1] (a segment's bytes, then its byte offset) | uint32 chunk
+// [n_chunks + 1] (a chunk's FF bytes, then the FF bytes before it) | uint32 state [4] (the stream's length, 1 if it exceeds stream_cap)
+struct EncGeom {
+    int mw, mh;
+    uint32_t n_mcu, n_blocks, interval, n_seg, n_chunks;
+    size_t bits_at, seg_at, chunk_at, state_at, bytes;
+};
+
+__host__ __device__ inline EncGeom enc_geom(int W, int H, int restart_interval, uint32_t stream_cap) {
+    EncGeom g;
+    g.mw = (W + 15) >> 4;
+    g.mh = (H + 15) >> 4;
+    g.n_mcu = (uint32_t)g.mw * (uint32_t)g.mh;
+    g.n_blocks = g.n_mcu * 6;
+    g.interval = restart_interval > 0 && (uint32_t)restart_interval < g.n_mcu ? (uint32_t)restart_interval : g.n_mcu;
+    g.n_seg = (g.n_mcu + g.interval - 1) / g.interval;
+    g.n_chunks = (stream_cap + kEncChunk - 1) / kEncChunk;
+    g.bits_at = (size_t)g.n_blocks * 128;
+    g.seg_at = g.bits_at + (size_t)g.n_blocks * 4;
+    g.chunk_at = g.seg_at + ((size_t)g.n_seg + 1) * 4;
+    g.state_at = g.chunk_at + ((size_t)g.n_chunks + 1) * 4;
+    g.bytes = (g.state_at + 16 + 15) & ~(size_t)15;
+    return g;
+}
+
+struct EncArgs {
+    const FearJpegEncImage* rec;   // the workspace's first bytes: the caller's device copy of the records
+    uint8_t* ws;
+    int32_t* length;
+    int32_t* status;
+    int n;
+};
+
+// the image whose workgroups of `pass` include `unit`: the last record whose start[pass] is not above it (every image has workgroups)
+__device__ __forceinline__ int enc_find(const FearJpegEncImage* rec, int n, int pass, uint32_t unit) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (rec[mid].start[pass] <= unit) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// Exclusive scan of one value per lane over the 256 lanes of a workgroup; `total` is the sum.  Wave-64 shuffles, then the four waves'
+// sums through LDS.  Every lane of the workgroup calls it.
+__device__ __forceinline__ uint32_t enc_wg_exscan(uint32_t v, uint32_t* lds4, uint32_t* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    __syncthreads();                                          // the previous call's readers are done with lds4
+    if (lane == 63) lds4[wave] = inc;
+    __syncthreads();
+    uint32_t base = 0, sum = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t s = lds4[i];
+        if (i < wave) base += s;
+        sum += s;
+    }
+    *total = sum;
+    return base + inc - v;
+}
+
+__global__ __launch_bounds__(256) void jpeg_enc_transform_kernel(EncArgs a) {
+    __shared__ __attribute__((aligned(16))) int blk[kJpBlocks * kJpPitch];
+    __shared__ int qt[128];
+    const int tid = threadIdx.x;
+    const int img = enc_find(a.rec, a.n, 0, blockIdx.x);
+    const FearJpegEncImage* r = a.rec + img;
+    const int W = r->width, H = r->height, quality = r->quality;
+    const int mw = (W + 15) >> 4, mh = (H + 15) >> 4, n_mcu = mw * mh;
+    const int group = (int)(blockIdx.x - r->start[0]);
+    if (tid < 128) {                                          // jpeg_set_quality(quality, force_baseline)
+        const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+        qt[tid] = min(max(((int)kJpegBase[tid] * scale + 50) / 100, 1), 255);
+    }
+    {
+        // one 2 x 2 quad of one MCU per lane.  Luma clamps its coordinates to the frame (replication right and down).  Chroma clamps the
+        // full-size column, and the full-size rows of the last downsampled row that exists: rows below it repeat THAT row.
+        const int g = tid >> 6, qy = (tid >> 3) & 7, qx = tid & 7;
+        const int mcu = group * kEncMcus + g;
+        int* yb = blk + (g * 6 + (qy >> 2) * 2 + (qx >> 2)) * kJpPitch + ((2 * qy) & 7) * 8 + ((2 * qx) & 7);
+        int cb = 0, cr = 0;
+        if (mcu < n_mcu) {
+            const int my = mcu / mw, mx = mcu - my * mw;
+            const int cy = min(my * 8 + qy, ((H + 1) >> 1) - 1);
+            const uint8_t* src = r->src;
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy) {
+                const int yl = min(my * 16 + 2 * qy + dy, H - 1), yc = min(2 * cy + dy, H - 1);
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx) {
+                    const int x = min(mx * 16 + 2 * qx + dx, W - 1);
+                    const uint8_t* p = src + ((size_t)yl * W + x) * 3;
+                    int rr = p[0], gg = p[1], bb = p[2];
+                    yb[dy * 8 + dx] = ((19595 * rr + 38470 * gg + 7471 * bb + 32768) >> 16) - 128;
+                    if (yc != yl) {
+                        p = src + ((size_t)yc * W + x) * 3;
+                        rr = p[0]; gg = p[1]; bb = p[2];
+                    }
+                    cb += (-11059 * rr - 21709 * gg + 32768 * bb + (128 << 16) + 32767) >> 16;
+                    cr += (32768 * rr - 27439 * gg - 5329 * bb + (128 << 16) + 32767) >> 16;
+                }
+            }
+            const int bias = 1 + (qx & 1);                    // 1, 2, 1, 2 along a row of the downsampled plane
+            cb = ((cb + bias) >> 2) - 128;
+            cr = ((cr + bias) >> 2) - 128;
+        } else {
+            yb[0] = yb[1] = yb[8] = yb[9] = 0;
+        }
+        blk[(g * 6 + 4) * kJpPitch + qy * 8 + qx] = cb;
+        blk[(g * 6 + 5) * kJpPitch + qy * 8 + qx] = cr;
+    }
+    __syncthreads();
+    const bool lane_on = tid < kJpBlocks * 8;                 // eight lanes per block
+    const int b = tid >> 3, k = tid & 7;
+    int* row = blk + (lane_on ? b * kJpPitch + k * 8 : 0);
+    int* col = blk + (lane_on ? b * kJpPitch + k : 0);
+    int d[8];
+    if (lane_on) {                                            // FDCT, rows
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = row[i];
+        jpeg_fdct<true>(d);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) row[i] = d[i];
+    }
+    __syncthreads();
+    if (lane_on) {                                            // FDCT columns, quantiser
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = col[i * 8];
+        jpeg_fdct<false>(d);
+        const int* q = qt + ((b % 6) >= 4 ? 64 : 0) + k;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const unsigned div = (unsigned)q[i * 8] << 3;
+            const int mag = (int)(((unsigned)abs(d[i]) + (div >> 1)) / div);
+            col[i * 8] = d[i] < 0 ? -mag : mag;
+        }
+    }
+    __syncthreads();
+    // zigzag int16 in MCU order: two coefficients per store, the workgroup's 24 blocks contiguous.  A luma block outside the component
+    // takes the DC term of the block before it in MCU order and no AC terms.
+    const int by = (H + 7) >> 3, bx = (W + 7) >> 3;
+    uint32_t* dst = reinterpret_cast<uint32_t*>(a.ws + r->work_offset) + (size_t)group * (kJpBlocks * 32);
+    for (int e = tid; e < kJpBlocks * 32; e += 256) {
+        const int bl = e >> 5, z = (e & 31) * 2;
+        const int g = bl / 6, kk = bl - g * 6;
+        const int mcu = group * kEncMcus + g;
+        if (mcu >= n_mcu) continue;
+        const int my = mcu / mw, mx = mcu - my * mw;
+        const bool R = mx == mw - 1 && (bx & 1), B = my == mh - 1 && (by & 1);
+        const int s1 = R ? 0 : 1, s2 = B ? s1 : 2, s3 = (R || B) ? s2 : 3;
+        const int from = kk == 1 ? s1 : kk == 2 ? s2 : kk == 3 ? s3 : kk;
+        const int* sb = blk + (g * 6 + from) * kJpPitch;
+        int v0, v1;
+        if (from != kk) {
+            v0 = z == 0 ? sb[0] : 0;
+            v1 = 0;
+        } else {
+            v0 = sb[kEncZigzag[z]];
+            v1 = sb[kEncZigzag[z + 1]];
+        }
+        dst[e] = ((uint32_t)v0 & 0xFFFFu) | ((uint32_t)v1 << 16);
+    }
+}
+
+// the block in front of block k of MCU `mcu` in its component, in MCU order; -1 at the start of a restart segment
+__device__ __forceinline__ long enc_prev_block(uint32_t mcu, int k, uint32_t interval) {
+    if (k >= 1 && k <= 3) return (long)mcu * 6 + k - 1;
+    if (mcu % interval == 0) return -1;
+    return (long)(mcu - 1) * 6 + (k == 0 ? 3 : k);
+}
+
+struct EncCount {
+    uint32_t bits = 0;
+    __device__ __forceinline__ void put(uint32_t, int len) { bits += (uint32_t)len; }
+};
+
+// MSB first into 32-bit words of the little-endian byte stream.  A word this block covers whole is stored; the first word (other blocks'
+// bits may lie in front) and the last (others' may follow) are merged with an OR into the zeroed stream.
+struct EncWrite {
+    uint32_t* words;
+    size_t w;
+    uint64_t acc = 0;
+    int fill;
+    bool first = true;
+    __device__ __forceinline__ void word(uint32_t v, bool merge) {
+        v = __builtin_bswap32(v);
+        if (merge) atomicOr(words + w, v);
+        else words[w] = v;
+        ++w;
+    }
+    __device__ __forceinline__ void put(uint32_t v, int len) {          // len <= 16, v < 2^len
+        acc = acc << len | v;
+        fill += len;
+        if (fill >= 32) {
+            fill -= 32;
+            word((uint32_t)(acc >> fill), first);
+            first = false;
+            acc &= (1ull << fill) - 1;
+        }
+    }
+    __device__ __forceinline__ void finish() {
+        if (fill > 0) word((uint32_t)(acc << (32 - fill)), true);
+    }
+};
+
+// T.81 F.1.2 over one block's 64 zigzag coefficients: `codes` is kEncCodes in LDS, `t` 0 for luma and 1 for chroma
+template <class Sink>
+__device__ __forceinline__ void enc_block(const uint4* cp, int pred, const uint32_t* codes, int t, Sink& sink) {
+    const uint32_t* dc = codes + t * 512;
+    const uint32_t* ac = dc + 256;
+    int run = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint4 q = cp[j];
+        const uint32_t w4[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            int v = (int)(int16_t)(w4[i >> 1] >> (16 * (i & 1)));
+            if (j == 0 && i == 0) {
+                v -= pred;
+                const int s = 32 - __clz(abs(v));
+                const uint32_t c = dc[s];
+                sink.put(c & 0xFFFFu, (int)(c >> 16));
+                sink.put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1), s);
+            } else if (v == 0) {
+                ++run;
+            } else {
+                for (; run > 15; run -= 16) {
+                    const uint32_t c = ac[0xF0];
+                    sink.put(c & 0xFFFFu, (int)(c >> 16));
+                }
+                const int s = 32 - __clz(abs(v));
+                const uint32_t c = ac[(run << 4 | s) & 255];
+                sink.put(c & 0xFFFFu, (int)(c >> 16));
+                sink.put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1), s);
+                run = 0;
+            }
+        }
+    }
+    if (run) {
+        const uint32_t c = ac[0];
+        sink.put(c & 0xFFFFu, (int)(c >> 16));
+    }
+}
+
+// sizes (WRITE false) and write (WRITE true): one lane per block
+template <bool WRITE>
+__global__ __launch_bounds__(256) void jpeg_enc_code_kernel(EncArgs a) {
+    __shared__ uint32_t codes[4 * 256];
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) codes[tid + 256 * i] = kEncCodes.v[tid + 256 * i];
+    __syncthreads();
+    const int img = enc_find(a.rec, a.n, 1, blockIdx.x);
+    const FearJpegEncImage* r = a.rec + img;
+    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap);
+    uint8_t* work = a.ws + r->work_offset;
+    const uint32_t* state = reinterpret_cast<const uint32_t*>(work + g.state_at);
+    if (WRITE && state[1]) return;                            // the stream alone exceeds the slot: nothing of this image is written
+    const uint32_t b = (blockIdx.x - r->start[1]) * kEncGroup + tid;
+    if (b >= g.n_blocks) return;
+    const uint32_t mcu = b / 6;
+    const int k = (int)(b - mcu * 6);
+    const int16_t* coef = reinterpret_cast<const int16_t*>(work);
+    const long prev = enc_prev_block(mcu, k, g.interval);
+    const int pred = prev < 0 ? 0 : coef[prev * 64];
+    const uint4* cp = reinterpret_cast<const uint4*>(coef + (size_t)b * 64);
+    uint32_t* bits = reinterpret_cast<uint32_t*>(work + g.bits_at);
+    if (!WRITE) {
+        EncCount sink;
+        enc_block(cp, pred, codes, k >= 4, sink);
+        bits[b] = sink.bits;
+    } else {
+        const uint32_t seg = mcu / g.interval;
+        const uint32_t* seg_at = reinterpret_cast<const uint32_t*>(work + g.seg_at);
+        const uint64_t pos = (uint64_t)seg_at[seg] * 8 + bits[b];
+        EncWrite sink;
+        sink.words = reinterpret_cast<uint32_t*>(a.ws + r->stream_offset);
+        sink.w = (size_t)(pos >> 5);
+        sink.fill = (int)(pos & 31);
+        enc_block(cp, pred, codes, k >= 4, sink);
+        const uint32_t seg_last = min((seg + 1) * g.interval, g.n_mcu) * 6 - 1;
+        if (b == seg_last) {                                  // ones up to the byte
+            const int pad = (32 - sink.fill) & 7;
+            sink.put((1u << pad) - 1, pad);
+        }
+        sink.finish();
+    }
+}
+
+// segments: one workgroup per restart segment.  bits[] becomes each block's bit offset in its segment, seg[s] the segment's bytes.
+__global__ __launch_bounds__(256) void jpeg_enc_segments_kernel(EncArgs a) {
+    __shared__ uint32_t lds4[4];
+    const int img = enc_find(a.rec, a.n, 2, blockIdx.x);
+    const FearJpegEncImage* r = a.rec + img;
+    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap);
+    uint8_t* work = a.ws + r->work_offset;
+    uint32_t* bits = reinterpret_cast<uint32_t*>(work + g.bits_at);
+    const uint32_t s = blockIdx.x - r->start[2];
+    const uint32_t first = s * g.interval * 6, last = min((s + 1) * g.interval, g.n_mcu) * 6;
+    uint32_t carry = 0;
+    for (uint32_t at = first; at < last; at += 256) {
+        const uint32_t i = at + threadIdx.x;
+        const uint32_t v = i < last ? bits[i] : 0u;
+        uint32_t sum;
+        const uint32_t ex = enc_wg_exscan(v, lds4, &sum);
+        if (i < last) bits[i] = carry + ex;
+        carry += sum;
+    }
+    if (threadIdx.x == 0) reinterpret_cast<uint32_t*>(work + g.seg_at)[s] = (carry + 7) >> 3;
+}
+
+// offsets (LENGTHS false): one workgroup per image; seg[] becomes each segment's byte offset in the unstuffed stream, seg[n_seg] and
+// state[0] its length, state[1] whether that exceeds the stream's capacity.
+// lengths (LENGTHS true): chunk[] becomes the FF bytes in front of each chunk; the file's length and the verdict.
+template <bool LENGTHS>
+__global__ __launch_bounds__(256) void jpeg_enc_image_scan_kernel(EncArgs a) {
+    __shared__ uint32_t lds4[4];
+    const int img = blockIdx.x;
+    const FearJpegEncImage* r = a.rec + img;
+    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap);
+    uint8_t* work = a.ws + r->work_offset;
+    uint32_t* state = reinterpret_cast<uint32_t*>(work + g.state_at);
+    uint32_t* v = reinterpret_cast<uint32_t*>(work + (LENGTHS ? g.chunk_at : g.seg_at));
+    const bool over = LENGTHS && state[1];
+    const uint32_t count = LENGTHS ? (over ? 0u : (state[0] + kEncChunk - 1) / kEncChunk) : g.n_seg;
+    uint32_t carry = 0;
+    for (uint32_t at = 0; at < count; at += 256) {
+        const uint32_t i = at + threadIdx.x;
+        const uint32_t x = i < count ? v[i] : 0u;
+        uint32_t sum;
+        const uint32_t ex = enc_wg_exscan(x, lds4, &sum);
+        if (i < count) v[i] = carry + ex;
+        carry += sum;
+    }
+    if (threadIdx.x != 0) return;
+    if (!LENGTHS) {
+        v[g.n_seg] = carry;
+        state[0] = carry;
+        state[1] = carry > r->stream_cap ? 1u : 0u;
+    } else {
+        // header, stream, a 00 per FF, two bytes per restart marker, EOI
+        const uint64_t total = (uint64_t)r->header_bytes + state[0] + carry + 2ull * (g.n_seg - 1) + 2;
+        const bool fits = !over && total <= r->out_cap;
+        a.length[img] = fits ? (int32_t)total : 0;
+        a.status[img] = fits ? FEAR_TRAIN_OK : FEAR_JPEG_ENC_OVERFLOW;
+    }
+}
+
+__device__ __forceinline__ uint32_t enc_count_ff(uint32_t w) {
+    return (uint32_t)((w & 0xFFu) == 0xFFu) + (uint32_t)((w & 0xFF00u) == 0xFF00u) + (uint32_t)((w & 0xFF0000u) == 0xFF0000u) +
+           (uint32_t)((w & 0xFF000000u) == 0xFF000000u);
+}
+
+// count (STORE false) and assemble (STORE true): one workgroup per chunk of the unstuffed stream, 16 bytes per lane.  The bytes behind
+// the stream's end are the memset's zeros: they count as no FF and are not stored.
+template <bool STORE>
+__global__ __launch_bounds__(256) void jpeg_enc_stuff_kernel(EncArgs a) {
+    __shared__ uint32_t lds4[4];
+    const int img = enc_find(a.rec, a.n, 3, blockIdx.x);
+    const FearJpegEncImage* r = a.rec + img;
+    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap);
+    uint8_t* work = a.ws + r->work_offset;
+    const uint32_t* state = reinterpret_cast<const uint32_t*>(work + g.state_at);
+    const uint32_t U = state[0], c = blockIdx.x - r->start[3];
+    if (state[1] || c * (uint32_t)kEncChunk >= U) return;     // the same for the whole workgroup
+    if (STORE && a.status[img] != FEAR_TRAIN_OK) return;
+    uint32_t* chunk = reinterpret_cast<uint32_t*>(work + g.chunk_at);
+    const uint32_t i0 = c * kEncChunk + threadIdx.x * 16;
+    const uint4 q = i0 < U ? reinterpret_cast<const uint4*>(a.ws + r->stream_offset)[i0 >> 4] : make_uint4(0u, 0u, 0u, 0u);
+    const uint32_t w4[4] = {q.x, q.y, q.z, q.w};
+    uint32_t sum;
+    const uint32_t ex = enc_wg_exscan(enc_count_ff(q.x) + enc_count_ff(q.y) + enc_count_ff(q.z) + enc_count_ff(q.w), lds4, &sum);
+    if (!STORE) {
+        if (threadIdx.x == 0) chunk[c] = sum;
+        return;
+    }
+    uint8_t* out = r->out;
+    const uint32_t hb = r->header_bytes;
+    if (c == 0)
+        for (uint32_t i = threadIdx.x; i < hb; i += 256) out[i] = r->header[i];
+    if (i0 >= U) return;
+    // the segment of byte i0: the last one whose offset is not above it
+    const uint32_t* seg_at = reinterpret_cast<const uint32_t*>(work + g.seg_at);
+    uint32_t s = 0;
+    if (g.n_seg > 1) {
+        uint32_t lo = 0, hi = g.n_seg - 1;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi + 1) >> 1;
+            if (seg_at[mid] <= i0) lo = mid;
+            else hi = mid - 1;
+        }
+        s = lo;
+    }
+    uint32_t ff = chunk[c] + ex;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const uint32_t i = i0 + j;
+        if (i >= U) break;
+        while (s + 1 < g.n_seg && seg_at[s + 1] <= i) ++s;
+        size_t at = (size_t)hb + i + ff + 2 * (size_t)s;
+        if (s > 0 && seg_at[s] == i) {                        // the restart marker in front of segment s
+            out[at - 2] = 0xFF;
+            out[at - 1] = (uint8_t)(0xD0 + ((s - 1) & 7));
+        }
+        const uint8_t byte = (uint8_t)(w4[j >> 2] >> (8 * (j & 3)));
+        out[at++] = byte;
+        if (byte == 0xFF) {
+            out[at++] = 0;
+            ++ff;
+        }
+        if (i == U - 1) {
+            out[at] = 0xFF;
+            out[at + 1] = 0xD9;
+        }
+    }
+}
+
+bool enc_record_ok(const FearJpegEncImage& r) {
+    return r.width >= 1 && r.width <= FEAR_JPEG_MAX_SIDE && r.height >= 1 && r.height <= FEAR_JPEG_MAX_SIDE && r.quality >= 1 &&
+           r.quality <= 100 && r.restart_interval >= 0 && r.restart_interval <= 65535 && r.header_bytes >= 1 && r.header_bytes <= 4096;
+}
+
+uint32_t enc_stream_bound(int W, int H, int restart_interval) {
+    const EncGeom g = enc_geom(W, H, restart_interval, 0);
+    return g.n_mcu * kEncMcuBytes + g.n_seg;                  // 8192 x 8192: 326 MB
+}
+
+// The plan of a call: per image what fear_jpeg_encode_plan writes; the workspace's size and the four grids.  False for a call the
+// operator refuses by its shape.
+struct EncPlan {
+    size_t stream_bytes, bytes;
+    uint64_t grid[4];
+};
+
+bool enc_plan(const FearJpegEncImage* images, int n, FearJpegEncImage* fill, EncPlan* plan) {
+    if (n < 0 || n > 65535) return false;
+    for (int i = 0; i < n; ++i)
+        if (!enc_record_ok(images[i])) return false;
+    EncPlan p{};
+    size_t at = FEAR_JPEG_ENC_TABLE_BYTES(n);
+    const size_t stream0 = at;
+    for (int pass = 0; pass < 2; ++pass) {                    // all streams first (one memset), then every image's scratch
+        for (int i = 0; i < n; ++i) {
+            const FearJpegEncImage& r = images[i];
+            const uint32_t cap = (std::min(enc_stream_bound(r.width, r.height, r.restart_interval), r.out_cap) + 4 + 15) & ~15u;
+            const EncGeom g = enc_geom(r.width, r.height, r.restart_interval, cap);
+            if (pass == 0) {
+                if (fill) {
+                    fill[i].stream_offset = at;
+                    fill[i].stream_cap = cap;
+                }
+                at += cap;
+            } else {
+                if (fill) {
+                    fill[i].work_offset = at;
+                    fill[i].start[0] = (uint32_t)p.grid[0];
+                    fill[i].start[1] = (uint32_t)p.grid[1];
+                    fill[i].start[2] = (uint32_t)p.grid[2];
+                    fill[i].start[3] = (uint32_t)p.grid[3];
+                    fill[i].reserved[0] = fill[i].reserved[1] = fill[i].reserved[2] = 0;
+                }
+                at += g.bytes;
+                p.grid[0] += (g.n_mcu + kEncMcus - 1) / kEncMcus;
+                p.grid[1] += (g.n_blocks + kEncGroup - 1) / kEncGroup;
+                p.grid[2] += g.n_seg;
+                p.grid[3] += g.n_chunks;
+            }
+        }
+        if (pass == 0) p.stream_bytes = at - stream0;
+    }
+    p.bytes = at;
+    for (int k = 0; k < 4; ++k)
+        if (p.grid[k] > 0x7fffffffull) return false;
+    *plan = p;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fear_jpeg_encode_header(int width, int height, int quality, int restart_interval, uint8_t* out, size_t out_cap, size_t* out_used) {
+    if (!out || !out_used) return FEAR_TRAIN_ERR_NULL;
+    if (width < 1 || width > FEAR_JPEG_MAX_SIDE || height < 1 || height > FEAR_JPEG_MAX_SIDE || quality < 1 || quality > 100 ||
+        restart_interval < 0 || restart_interval > 65535)
+        return FEAR_TRAIN_ERR_SHAPE;
+    uint8_t h[FEAR_JPEG_ENC_HEADER_MAX];
+    size_t at = 0;
+    auto put = [&](std::initializer_list<int> v) { for (int b : v) h[at++] = (uint8_t)b; };
+    put({0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int t = 0; t < 2; ++t) {
+        put({0xFF, 0xDB, 0, 67, t});
+        for (int z = 0; z < 64; ++z) h[at++] = (uint8_t)std::min(std::max(((int)kEncBaseHost[t * 64 + kEncZigzagHost[z]] * scale + 50) / 100, 1), 255);
+    }
+    put({0xFF, 0xC0, 0, 17, 8, height >> 8, height & 255, width >> 8, width & 255, 3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1});
+    for (int t = 0; t < 4; ++t) {
+        const int total = kEncStd[t].total;
+        put({0xFF, 0xC4, (19 + total) >> 8, (19 + total) & 255, (t & 1) << 4 | t >> 1});
+        for (int i = 0; i < 16; ++i) h[at++] = kEncStd[t].counts[i];
+        for (int i = 0; i < total; ++i) h[at++] = kEncStd[t].values[i];
+    }
+    if (restart_interval) put({0xFF, 0xDD, 0, 4, restart_interval >> 8, restart_interval & 255});
+    put({0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
+    if (at > out_cap) return FEAR_TRAIN_ERR_WORKSPACE;
+    std::memcpy(out, h, at);
+    *out_used = at;
+    return FEAR_TRAIN_OK;
+}
+
+size_t fear_jpeg_encode_bound(int width, int height, int restart_interval) {
+    if (width < 1 || width > FEAR_JPEG_MAX_SIDE || height < 1 || height > FEAR_JPEG_MAX_SIDE || restart_interval < 0 || restart_interval > 65535)
+        return 0;
+    const EncGeom g = enc_geom(width, height, restart_interval, 0);
+    // the header with or without DRI; every stream byte stuffed; a marker in front of every segment but the first; EOI
+    return (size_t)(restart_interval ? 629 : 623) + 2 * (size_t)enc_stream_bound(width, height, restart_interval) + 2 * ((size_t)g.n_seg - 1) + 2;
+}
+
+int fear_jpeg_encode_plan(FearJpegEncImage* images, int n) {
+    if (n < 0 || n > 65535) return FEAR_TRAIN_ERR_SHAPE;
+    if (n == 0) return FEAR_TRAIN_OK;
+    if (!images) return FEAR_TRAIN_ERR_NULL;
+    EncPlan plan;
+    return enc_plan(images, n, images, &plan) ? FEAR_TRAIN_OK : FEAR_TRAIN_ERR_SHAPE;
+}
+
+size_t fear_jpeg_encode_workspace_bytes(const FearJpegEncImage* images, int n) {
+    EncPlan plan;
+    if (!images || n <= 0 || !enc_plan(images, n, nullptr, &plan)) return 0;
+    return plan.bytes;
+}
+
+int fear_jpeg_encode_u8(const FearJpegEncImage* images, int n, void* workspace, size_t workspace_bytes, int32_t* length_dev,
+                        int32_t* status_dev, void* stream) {
+    if (n < 0 || n > 65535) return FEAR_TRAIN_ERR_SHAPE;
+    if (n == 0) return FEAR_TRAIN_OK;
+    if (!images || !length_dev || !status_dev) return FEAR_TRAIN_ERR_NULL;
+    for (int i = 0; i < n; ++i)
+        if (!images[i].src || !images[i].out || !images[i].header) return FEAR_TRAIN_ERR_NULL;
+    EncPlan plan;
+    std::vector<FearJpegEncImage> want(images, images + n);
+    if (!enc_plan(images, n, want.data(), &plan)) return FEAR_TRAIN_ERR_SHAPE;
+    if (std::memcmp(want.data(), images, (size_t)n * sizeof(FearJpegEncImage)) != 0) return FEAR_TRAIN_ERR_SHAPE;   // not fear_jpeg_encode_plan's
+    for (int i = 0; i < n; ++i) {                             // a source that a slot overlaps (its own or another's)
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(images[i].src), s1 = s0 + (size_t)images[i].width * images[i].height * 3;
+        for (int j = 0; j < n; ++j) {
+            const uintptr_t o0 = reinterpret_cast<uintptr_t>(images[j].out), o1 = o0 + images[j].out_cap;
+            if (s0 < o1 && o0 < s1) return FEAR_TRAIN_ERR_SHAPE;
+        }
+    }
+    if (!workspace || workspace_bytes < plan.bytes) return FEAR_TRAIN_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    EncArgs a{};
+    a.rec = static_cast<const FearJpegEncImage*>(workspace);
+    a.ws = static_cast<uint8_t*>(workspace);
+    a.length = length_dev;
+    a.status = status_dev;
+    a.n = n;
+    if (hipMemsetAsync(a.ws + FEAR_JPEG_ENC_TABLE_BYTES(n), 0, plan.stream_bytes, st) != hipSuccess) return FEAR_TRAIN_ERR_HIP;
+    hipLaunchKernelGGL(jpeg_enc_transform_kernel, dim3((unsigned)plan.grid[0]), dim3(256), 0, st, a);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(jpeg_enc_code_kernel<false>, dim3((unsigned)plan.grid[1]), dim3(256), 0, st, a);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(jpeg_enc_segments_kernel, dim3((unsigned)plan.grid[2]), dim3(256), 0, st, a);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(jpeg_enc_image_scan_kernel<false>, dim3((unsigned)n), dim3(256), 0, st, a);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(jpeg_enc_code_kernel<true>, dim3((unsigned)plan.grid[1]), dim3(256), 0, st, a);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(jpeg_enc_stuff_kernel<false>, dim3((unsigned)plan.grid[3]), dim3(256), 0, st, a);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(jpeg_enc_image_scan_kernel<true>, dim3((unsigned)n), dim3(256), 0, st, a);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(jpeg_enc_stuff_kernel<true>, dim3((unsigned)plan.grid[3]), dim3(256), 0, st, a);
+    LAUNCH_CHECK();
+    return FEAR_TRAIN_OK;
+}
+
+}  // extern "C"

@@ -2325,6 +2325,7 @@ int fear_layer_plan_info(long M, int K, int N, size_t ws_bytes, const FearLayerD
 #include "fear_jpeg_decode.h"
 #include "fear_jpeg_huffman.h"
 #include "fear_jpeg_store.h"
+#include "fear_jpeg_encode.h"
 #include "fear_train_metrics.h"
 #include "fear_train_visuals.h"
 #include "fear_train_optim.h"

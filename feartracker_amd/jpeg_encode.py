@@ -1,0 +1,414 @@
+"""Baseline JPEG files written from uint8 RGB frames ("Writing JPEG files").
+
+`jpeg_encode_host` is the contract: numpy and plain Python that produce, byte for byte, the file libjpeg writes with its defaults for a
+three-component frame (`PIL.Image.fromarray(rgb).save(f, "JPEG", quality=q)`): baseline SOF0, 4:2:0, islow FDCT, the standard Huffman
+tables of T.81 annex K, optionally a restart interval of whole MCU rows.  tests/test_jpeg_encode_host.py holds it to Pillow's
+libjpeg-turbo.  `JpegEncoder` is the product: `fear_jpeg_encode_u8` (csrc/fear_jpeg_encode.h) runs every stage on the device and
+`PendingJpegs.result()` downloads the files' bytes alone.  `write_mjpeg_avi` puts equal-sized files into a Motion-JPEG AVI."""
+from __future__ import annotations
+
+import ctypes
+import struct
+from typing import List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from .jpeg_frames import MAX_SIDE, ZIGZAG
+from .train_data.jpeg import jpeg_fdct_islow, jpeg_quant_tables
+
+# T.81 tables K.3 to K.6: the code counts per length 1..16 and the symbols in code order, as (class, id) of their DHT segment
+STD_HUFFMAN = {
+    (0, 0): ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), bytes(range(12))),
+    (1, 0): ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125), bytes.fromhex(
+        "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a434445464748"
+        "494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3"
+        "c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")),
+    (0, 1): ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), bytes(range(12))),
+    (1, 1): ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119), bytes.fromhex(
+        "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a4344454647"
+        "48494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9ba"
+        "c2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")),
+}
+ENC_OVERFLOW = 1                          # include/fear_train.h FEAR_JPEG_ENC_OVERFLOW
+
+
+class JpegOverflow(ValueError):
+    """Some files of an `encode` call did not fit their slots; `.items` lists their indexes."""
+
+    def __init__(self, items: Sequence[int]):
+        self.items = list(items)
+        super().__init__(f"the JPEG files of items {self.items} exceed their slots")
+
+
+def _codes(counts: Sequence[int], values: bytes):
+    """Canonical codes of T.81 annex C: symbol -> (code, length)."""
+    table, code, k = {}, 0, 0
+    for length in range(1, 17):
+        for _ in range(counts[length - 1]):
+            table[values[k]] = (code, length)
+            code += 1
+            k += 1
+        code <<= 1
+    return table
+
+
+_STD_CODES = {key: _codes(*tab) for key, tab in STD_HUFFMAN.items()}
+
+
+def _check_rgb(rgb) -> np.ndarray:
+    v = np.asarray(rgb)
+    if v.dtype != np.uint8:
+        raise TypeError("a frame is uint8")
+    if v.ndim != 3 or v.shape[2] != 3:
+        raise ValueError("a frame is (H, W, 3)")
+    if not (1 <= v.shape[0] <= MAX_SIDE and 1 <= v.shape[1] <= MAX_SIDE):
+        raise ValueError(f"a frame's sides lie in 1..{MAX_SIDE}")
+    return v
+
+
+def _check_quality(quality) -> int:
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)):
+        raise TypeError("a JPEG quality is an int")
+    if not 1 <= int(quality) <= 100:
+        raise ValueError("a JPEG quality lies in 1..100")
+    return int(quality)
+
+
+def _restart_interval(restart_rows, mcus_x: int) -> int:
+    if isinstance(restart_rows, bool) or not isinstance(restart_rows, (int, np.integer)):
+        raise TypeError("restart_rows is an int")
+    interval = int(restart_rows) * mcus_x
+    if restart_rows < 0 or interval > 65535:
+        raise ValueError("restart_rows is not negative and restart_rows mcus_x fits 16 bits")
+    return interval
+
+
+def _edge(plane: np.ndarray, rows: int, cols: int) -> np.ndarray:
+    """Replicate the last column out to `cols` columns and the last row down to `rows` rows."""
+    return np.pad(plane, ((0, rows - plane.shape[0]), (0, cols - plane.shape[1])), mode="edge")
+
+
+def _quantise(plane: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """(8 bh, 8 bw) samples -> (bh, bw, 64) int64 coefficients in zigzag order."""
+    h, w = plane.shape
+    v = jpeg_fdct_islow((plane - 128).reshape(h // 8, 8, w // 8, 8).transpose(0, 2, 1, 3))
+    div = (q << 3).reshape(8, 8)
+    coef = np.sign(v) * ((np.abs(v) + (div >> 1)) // div)
+    return coef.reshape(h // 8, w // 8, 64)[..., ZIGZAG]
+
+
+def jpeg_forward_coefficients_host(rgb: np.ndarray, quality: int = 75) -> List[np.ndarray]:
+    """The quantised coefficients libjpeg codes for an RGB frame of any size: per component (blocks_h, blocks_w, 64) int16 in zigzag
+    order, padded to whole MCUs (`jpeg_coefficients_host`'s shape), the dummy blocks of the luma component included."""
+    v = _check_rgb(rgb)
+    q_luma, q_chroma = jpeg_quant_tables(_check_quality(quality))
+    H, W = v.shape[:2]
+    p = v.astype(np.int64)
+    r, g, b = p[..., 0], p[..., 1], p[..., 2]
+    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
+    cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16
+    cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16
+    by, bx = -(-H // 8), -(-W // 8)
+    mcus_y, mcus_x = -(-H // 16), -(-W // 16)
+    luma = np.zeros((2 * mcus_y, 2 * mcus_x, 64), dtype=np.int64)
+    luma[:by, :bx] = _quantise(_edge(y, 8 * by, 8 * bx), q_luma)
+    # dummy blocks: no AC terms, the DC term of the previous block in MCU order (Y00 Y01 Y10 Y11)
+    for my in range(mcus_y):
+        for mx in range(mcus_x):
+            order = [(2 * my, 2 * mx), (2 * my, 2 * mx + 1), (2 * my + 1, 2 * mx), (2 * my + 1, 2 * mx + 1)]
+            for k in range(1, 4):
+                if order[k][0] >= by or order[k][1] >= bx:
+                    luma[order[k]][0] = luma[order[k - 1]][0]
+    out = [luma.astype(np.int16)]
+    ch, cw = -(-H // 2), 8 * mcus_x                                          # cw = 8 ceil(ceil(W / 2) / 8)
+    bias = np.tile(np.array([1, 2], dtype=np.int64), cw // 2)
+    for c in (cb, cr):
+        full = _edge(c, 2 * ch, 2 * cw)                                      # the last row only as far as an even height
+        down = (full[0::2, 0::2] + full[0::2, 1::2] + full[1::2, 0::2] + full[1::2, 1::2] + bias[None, :]) >> 2
+        out.append(_quantise(_edge(down, 8 * mcus_y, cw), q_chroma).astype(np.int16))   # then the last downsampled row
+    return out
+
+
+def jpeg_header_host(width: int, height: int, quality: int = 75, restart_interval: int = 0) -> bytes:
+    """Everything in front of the scan: SOI, JFIF APP0, the two DQT, SOF0, the four standard DHT, DRI if there is an interval, SOS."""
+    if not (1 <= width <= MAX_SIDE and 1 <= height <= MAX_SIDE):
+        raise ValueError(f"a frame's sides lie in 1..{MAX_SIDE}")
+    if not 0 <= restart_interval <= 65535:
+        raise ValueError("a restart interval fits 16 bits")
+    out = bytearray(b"\xFF\xD8\xFF\xE0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    for t, q in enumerate(jpeg_quant_tables(_check_quality(quality))):
+        out += b"\xFF\xDB\x00\x43" + bytes([t]) + bytes(int(x) for x in q[ZIGZAG])
+    out += b"\xFF\xC0\x00\x11\x08" + struct.pack(">HH", height, width) + b"\x03\x01\x22\x00\x02\x11\x01\x03\x11\x01"
+    for (tc, th) in ((0, 0), (1, 0), (0, 1), (1, 1)):
+        counts, values = STD_HUFFMAN[(tc, th)]
+        out += b"\xFF\xC4" + struct.pack(">H", 19 + len(values)) + bytes([tc << 4 | th]) + bytes(counts) + values
+    if restart_interval:
+        out += b"\xFF\xDD\x00\x04" + struct.pack(">H", restart_interval)
+    out += b"\xFF\xDA\x00\x0C\x03\x01\x00\x02\x11\x03\x11\x00\x3F\x00"
+    return bytes(out)
+
+
+class _BitWriter:
+    def __init__(self):
+        self.out, self.acc, self.have = bytearray(), 0, 0
+
+    def put(self, value: int, count: int) -> None:
+        self.acc = (self.acc << count) | (value & ((1 << count) - 1))
+        self.have += count
+        while self.have >= 8:
+            byte = (self.acc >> (self.have - 8)) & 255
+            self.out.append(byte)
+            if byte == 0xFF:
+                self.out.append(0)
+            self.have -= 8
+        self.acc &= (1 << self.have) - 1
+
+    def flush(self) -> None:
+        if self.have:
+            self.put((1 << (8 - self.have)) - 1, 8 - self.have)             # ones up to the byte; stuffed like any other byte
+
+
+def jpeg_entropy_encode_host(coefficients: Sequence[np.ndarray], mcus_x: int, mcus_y: int, restart_interval: int = 0) -> bytes:
+    """T.81 F.1.2 over one interleaved 4:2:0 scan: the stuffed bytes between SOS and EOI, restart markers included."""
+    w = _BitWriter()
+    pred = [0, 0, 0]
+    for mcu in range(mcus_x * mcus_y):
+        if restart_interval and mcu and mcu % restart_interval == 0:
+            w.flush()
+            w.out += bytes([0xFF, 0xD0 + ((mcu // restart_interval - 1) & 7)])
+            pred = [0, 0, 0]
+        my, mx = divmod(mcu, mcus_x)
+        blocks = [(0, 2 * my, 2 * mx), (0, 2 * my, 2 * mx + 1), (0, 2 * my + 1, 2 * mx), (0, 2 * my + 1, 2 * mx + 1), (1, my, mx), (2, my, mx)]
+        for c, j, i in blocks:
+            blk = [int(x) for x in coefficients[c][j, i]]
+            dc, ac = _STD_CODES[(0, 1 if c else 0)], _STD_CODES[(1, 1 if c else 0)]
+            diff = blk[0] - pred[c]
+            pred[c] = blk[0]
+            s = abs(diff).bit_length()
+            w.put(*dc[s])
+            w.put(diff if diff >= 0 else diff + (1 << s) - 1, s)
+            run = 0
+            for k in range(1, 64):
+                v = blk[k]
+                if v == 0:
+                    run += 1
+                    continue
+                while run > 15:
+                    w.put(*ac[0xF0])
+                    run -= 16
+                s = abs(v).bit_length()
+                w.put(*ac[run << 4 | s])
+                w.put(v if v >= 0 else v + (1 << s) - 1, s)
+                run = 0
+            if run:
+                w.put(*ac[0x00])
+    w.flush()
+    return bytes(w.out)
+
+
+def jpeg_encode_host(rgb: np.ndarray, quality: int = 75, restart_rows: int = 0) -> bytes:
+    """A uint8 (H, W, 3) RGB frame -> the baseline JPEG file libjpeg writes for it at `quality`, with a restart marker every
+    `restart_rows` MCU rows if that is not 0.  Slow; the statement the device is held to."""
+    v = _check_rgb(rgb)
+    H, W = v.shape[:2]
+    mcus_x, mcus_y = -(-W // 16), -(-H // 16)
+    interval = _restart_interval(restart_rows, mcus_x)
+    coef = jpeg_forward_coefficients_host(v, quality)
+    return jpeg_header_host(W, H, quality, interval) + jpeg_entropy_encode_host(coef, mcus_x, mcus_y, interval) + b"\xFF\xD9"
+
+
+# ------------------------------------------------------------------------------------------------------------------------ the product
+class PendingJpegs:
+    """The files of one `JpegEncoder.encode` call, still on the device and possibly still being written.  `buffer` (uint8) holds one
+    slot per item at `offsets` (int64 bytes), `lengths` (int32) the files' lengths — 0 for an item that did not fit — and `status`
+    (int32) 0 or ENC_OVERFLOW: device tensors, ordered on the stream `encode` ran on, for consumers that stay on the device."""
+
+    def __init__(self, buffer, offsets, lengths, status, host_offsets: Sequence[int], keep=()):
+        self.buffer, self.offsets, self.lengths, self.status = buffer, offsets, lengths, status
+        self._host_offsets, self._keep = list(host_offsets), keep         # (the frames and the staging buffers outlive the kernels)
+
+    def __len__(self) -> int:
+        return len(self._host_offsets)
+
+    def result(self) -> List[bytes]:
+        """Wait, download the lengths and then the used bytes alone; `JpegOverflow` names the items whose files exceed their slots."""
+        import torch
+        n = len(self._host_offsets)
+        if n == 0:
+            return []
+        verdict = torch.stack([self.lengths, self.status]).cpu().numpy()   # one copy, which waits for the stream
+        self._keep = ()
+        bad = np.flatnonzero(verdict[1])
+        if bad.size:
+            raise JpegOverflow([int(i) for i in bad])
+        at = np.concatenate([[0], np.cumsum(verdict[0], dtype=np.int64)])
+        host = torch.empty(max(int(at[-1]), 1), dtype=torch.uint8, pin_memory=True)
+        for i, off in enumerate(self._host_offsets):
+            host[int(at[i]):int(at[i + 1])].copy_(self.buffer[off:off + int(verdict[0, i])], non_blocking=True)
+        torch.cuda.current_stream(self.buffer.device).synchronize()
+        data = host.numpy()
+        return [data[int(at[i]):int(at[i + 1])].tobytes() for i in range(n)]
+
+
+class JpegEncoder:
+    """uint8 (H, W, 3) RGB device tensors -> baseline JPEG files, byte for byte what Pillow's `save(f, "JPEG", quality=q)` writes
+    (`restart_rows=r`: what `save(..., restart_marker_rows=r)` writes).
+
+    `encode` builds the headers and the records on the host, uploads them from pinned memory in one non-blocking transfer and runs
+    `fear_jpeg_encode_u8` once for the whole call: frames of different sizes and qualities in a fixed number of launches.  It never
+    waits for the GPU.  Every file gets a slot of `slot_bytes` in one device buffer: by default 1024 + 3 (16 mcus_x) (16 mcus_y) bytes,
+    a little above the raw pixels; `"bound"` takes `fear_jpeg_encode_bound`, the longest file the frame's size can give, and an int is
+    the slot of every frame.  A file that exceeds its slot is not written: its length is 0 and `PendingJpegs.result()` raises
+    `JpegOverflow`; the other files of the call are unaffected.  `guard_bytes` are left unused behind every slot."""
+
+    def __init__(self, device: int = 0, quality: int = 75, restart_rows: int = 0, slot_bytes: Union[None, int, str] = None,
+                 guard_bytes: int = 0):
+        import torch
+        from .train_abi import load_train_library
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        self.quality = _check_quality(quality)
+        _restart_interval(restart_rows, 1)
+        self.restart_rows = int(restart_rows)
+        if not (slot_bytes is None or slot_bytes == "bound" or (isinstance(slot_bytes, (int, np.integer)) and not isinstance(slot_bytes, bool))):
+            raise TypeError('slot_bytes is None, "bound" or an int')
+        if isinstance(slot_bytes, (int, np.integer)) and not 0 < slot_bytes < 1 << 32:
+            raise ValueError("slot_bytes is positive and fits 32 bits")
+        if guard_bytes < 0:
+            raise ValueError("guard_bytes is not negative")
+        self.slot_bytes, self.guard_bytes = slot_bytes, int(guard_bytes)
+        self._lib = load_train_library()
+
+    def _frames(self, frames) -> List:
+        import torch
+        if isinstance(frames, torch.Tensor):
+            if frames.ndim != 4:
+                raise ValueError("a batch of frames is (n, H, W, 3)")
+            frames = list(frames.unbind(0))
+        out = list(frames)
+        for f in out:
+            if not isinstance(f, torch.Tensor):
+                raise TypeError("a frame is a torch tensor on the device")
+            if f.dtype != torch.uint8:
+                raise TypeError("a frame is uint8")
+            if f.ndim != 3 or f.shape[2] != 3:
+                raise ValueError("a frame is (H, W, 3)")
+            if not f.is_cuda or f.device != self.device:
+                raise ValueError(f"a frame lives on {self.device}")
+            if not f.is_contiguous():
+                raise ValueError("a frame is contiguous")
+            if not (1 <= f.shape[0] <= MAX_SIDE and 1 <= f.shape[1] <= MAX_SIDE):
+                raise ValueError(f"a frame's sides lie in 1..{MAX_SIDE}")
+        if len(out) > 65535:
+            raise ValueError("at most 65535 frames per call")
+        return out
+
+    def encode(self, frames, quality: Union[None, int, Sequence[int]] = None) -> PendingJpegs:
+        import torch
+        from .train_abi import (FEAR_JPEG_ENC_HEADER_MAX, FEAR_JPEG_ENC_TABLE_BYTES, FearJpegEncImage, launch)
+        frames = self._frames(frames)
+        n = len(frames)
+        if quality is None:
+            qualities = [self.quality] * n
+        elif isinstance(quality, (int, np.integer)) and not isinstance(quality, bool):
+            qualities = [_check_quality(quality)] * n
+        else:
+            qualities = [_check_quality(q) for q in quality]
+            if len(qualities) != n:
+                raise ValueError("one quality per frame")
+        lib = self._lib
+        records = (FearJpegEncImage * max(n, 1))()
+        headers, header_at, slot_at, at, out_at = [], [], [], 0, 0
+        scratch, used = (ctypes.c_uint8 * FEAR_JPEG_ENC_HEADER_MAX)(), ctypes.c_size_t(0)
+        for k, f in enumerate(frames):
+            H, W = int(f.shape[0]), int(f.shape[1])
+            mcus_x, mcus_y = -(-W // 16), -(-H // 16)
+            interval = _restart_interval(self.restart_rows, mcus_x)
+            launch(lib, "fear_jpeg_encode_header", W, H, qualities[k], interval, scratch, len(scratch), ctypes.byref(used))
+            headers.append(bytes(scratch[:used.value]))
+            header_at.append(at)
+            at += -(-used.value // 16) * 16
+            if self.slot_bytes is None:
+                slot = 1024 + 3 * (16 * mcus_x) * (16 * mcus_y)
+            elif self.slot_bytes == "bound":
+                slot = int(lib.fear_jpeg_encode_bound(W, H, interval))
+            else:
+                slot = int(self.slot_bytes)
+            if slot >= 1 << 32:
+                raise ValueError("a slot fits 32 bits")
+            rec = records[k]
+            rec.width, rec.height, rec.quality, rec.restart_interval = W, H, qualities[k], interval
+            rec.out_cap, rec.header_bytes = slot, used.value
+            slot_at.append(out_at)
+            out_at += -(-(slot + self.guard_bytes) // 16) * 16
+        with torch.cuda.device(self.device):
+            if n == 0:
+                empty = torch.empty(0, dtype=torch.int32, device=self.device)
+                return PendingJpegs(torch.empty(0, dtype=torch.uint8, device=self.device), torch.empty(0, dtype=torch.int64, device=self.device),
+                                    empty, empty, [])
+            launch(lib, "fear_jpeg_encode_plan", records, n)
+            ws_bytes = int(lib.fear_jpeg_encode_workspace_bytes(records, n))
+            table_bytes = FEAR_JPEG_ENC_TABLE_BYTES(n)
+            # one device allocation: the headers, then the workspace, whose first bytes are the records; both go up in one transfer
+            dev = torch.empty(at + ws_bytes, dtype=torch.uint8, device=self.device)
+            if self.guard_bytes:
+                buffer = torch.full((out_at,), 0xA5, dtype=torch.uint8, device=self.device)
+            else:
+                buffer = torch.empty(out_at, dtype=torch.uint8, device=self.device)
+            for k, f in enumerate(frames):
+                records[k].src, records[k].out, records[k].header = f.data_ptr(), buffer.data_ptr() + slot_at[k], dev.data_ptr() + header_at[k]
+            pinned = torch.empty(at + table_bytes + 8 * n, dtype=torch.uint8, pin_memory=True)
+            host = pinned.numpy()
+            for k, h in enumerate(headers):
+                host[header_at[k]:header_at[k] + len(h)] = np.frombuffer(h, dtype=np.uint8)
+            host[at:at + 96 * n] = np.frombuffer(records, dtype=np.uint8)[:96 * n]
+            host[at + table_bytes:].view(np.int64)[:] = slot_at
+            dev[:at + table_bytes].copy_(pinned[:at + table_bytes], non_blocking=True)
+            offsets = torch.empty(n, dtype=torch.int64, device=self.device)
+            offsets.view(torch.uint8).copy_(pinned[at + table_bytes:], non_blocking=True)
+            verdict = torch.empty((2, n), dtype=torch.int32, device=self.device)
+            launch(lib, "fear_jpeg_encode_u8", records, n, ctypes.c_void_p(dev.data_ptr() + at), ws_bytes,
+                   ctypes.c_void_p(verdict[0].data_ptr()), ctypes.c_void_p(verdict[1].data_ptr()),
+                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        return PendingJpegs(buffer, offsets, verdict[0], verdict[1], slot_at, keep=(frames, dev, pinned))
+
+
+# ---------------------------------------------------------------------------------------------------------------------- Motion-JPEG AVI
+def write_mjpeg_avi(path, files: Sequence[bytes], fps: float) -> None:
+    """JPEG files of one frame size as a Motion-JPEG AVI: RIFF 'AVI ', LIST hdrl (avih, LIST strl (strh, strf: MJPG)), LIST movi of
+    00dc chunks (an odd payload is padded to an even length), idx1.  Plain host code; players read it without a codec library of ours."""
+    from fractions import Fraction
+    from .jpeg_frames import jpeg_info
+    files = [bytes(f) for f in files]
+    if not files:
+        raise ValueError("an AVI needs at least one frame")
+    if not fps > 0:
+        raise ValueError("fps is positive")
+    info = jpeg_info(files[0])
+    width, height = info["width"], info["height"]
+    for f in files[1:]:
+        other = jpeg_info(f)
+        if (other["width"], other["height"]) != (width, height):
+            raise ValueError("every frame of an AVI has the same size")
+    rate = Fraction(fps).limit_denominator(100000)
+    largest = max(len(f) for f in files)
+
+    def chunk(tag: bytes, payload: bytes) -> bytes:
+        return tag + struct.pack("<I", len(payload)) + payload + (b"\0" if len(payload) & 1 else b"")
+
+    def listed(kind: bytes, payload: bytes) -> bytes:
+        return b"LIST" + struct.pack("<I", 4 + len(payload)) + kind + payload
+
+    avih = struct.pack("<14I", round(1e6 / fps), int(largest * fps) + 1, 0, 0x10, len(files), 0, 1, largest, width, height, 0, 0, 0, 0)
+    strh = b"vidsMJPG" + struct.pack("<IHHIIIIIIiI4h", 0, 0, 0, 0, rate.denominator, rate.numerator, 0, len(files), largest, -1, 0,
+                                     0, 0, width, height)
+    strf = struct.pack("<IiiHH4sIiiII", 40, width, height, 1, 24, b"MJPG", width * height * 3, 0, 0, 0, 0)
+    hdrl = listed(b"hdrl", chunk(b"avih", avih) + listed(b"strl", chunk(b"strh", strh) + chunk(b"strf", strf)))
+    movi, index, at = bytearray(), bytearray(), 4                          # idx1 offsets count from the 'movi' tag
+    for f in files:
+        index += b"00dc" + struct.pack("<III", 0x10, at, len(f))
+        piece = chunk(b"00dc", f)
+        movi += piece
+        at += len(piece)
+    body = b"AVI " + hdrl + listed(b"movi", bytes(movi)) + chunk(b"idx1", bytes(index))
+    with open(path, "wb") as fh:
+        fh.write(b"RIFF" + struct.pack("<I", len(body)) + body)

@@ -122,6 +122,12 @@ TRAIN_SYMBOLS = {
     # boxes drawn into frames, and the best / worst batch miner (visuals.py; FearMinerState below)
     "fear_draw_boxes_u8": ([_P, _i, _P, _P, _P, _i, _i, _P], _i),
     "fear_miner_update": ([_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _d, _i, _P, _P, _P], _i),
+    # JPEG files written on the device (jpeg_encode.JpegEncoder; FearJpegEncImage below): the host's header, bound and plan, the encode
+    "fear_jpeg_encode_header": ([_i, _i, _i, _i, _P, _sz, _P], _i),
+    "fear_jpeg_encode_bound": ([_i, _i, _i], _sz),
+    "fear_jpeg_encode_plan": ([_P, _i], _i),
+    "fear_jpeg_encode_workspace_bytes": ([_P, _i], _sz),
+    "fear_jpeg_encode_u8": ([_P, _i, _P, _sz, _P, _P, _P], _i),
 }
 
 
@@ -326,6 +332,29 @@ assert FearJpegIndexed.row_sub.offset == 56
 assert ctypes.sizeof(FearJpegInfo) == 464 and FearJpegInfo.qt.offset == 80
 assert ctypes.sizeof(FearJpegHuff) == 1440 and ctypes.sizeof(FearJpegScan) == 8704 and FearJpegScan.dc.offset == 64
 assert ctypes.sizeof(FearJpegImage) == 448 and FearJpegImage.qt.offset == 64
+
+
+class FearJpegEncImage(ctypes.Structure):
+    """include/fear_train.h: one image of a fear_jpeg_encode_u8 call (device pointers as integers; fear_jpeg_encode_plan fills
+    stream_offset, work_offset, stream_cap and start)."""
+    _fields_ = [("src", ctypes.c_uint64), ("out", ctypes.c_uint64), ("header", ctypes.c_uint64), ("stream_offset", ctypes.c_uint64),
+                ("work_offset", ctypes.c_uint64), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("quality", ctypes.c_int32),
+                ("restart_interval", ctypes.c_int32), ("out_cap", ctypes.c_uint32), ("header_bytes", ctypes.c_uint32),
+                ("stream_cap", ctypes.c_uint32), ("start", ctypes.c_uint32 * 4), ("reserved", ctypes.c_uint32 * 3)]
+
+
+assert ctypes.sizeof(FearJpegEncImage) == 96 and FearJpegEncImage.width.offset == 40 and FearJpegEncImage.stream_cap.offset == 64
+FEAR_JPEG_ENC_OVERFLOW = 1
+FEAR_JPEG_ENC_HEADER_MAX = 640
+FEAR_JPEG_ENC_GROUP_BLOCKS = 256      # blocks per workgroup of fear_jpeg_encode_u8's sizes and write passes
+FEAR_JPEG_ENC_CHUNK_BYTES = 4096      # unstuffed stream bytes per workgroup of its count and assemble passes
+FEAR_JPEG_ENC_MCUS = 4                # MCUs per workgroup of its transform pass
+
+
+def FEAR_JPEG_ENC_TABLE_BYTES(n: int) -> int:
+    return (n * 96 + 15) & ~15
+
+
 FEAR_TRAIN_ERR_WORKSPACE, FEAR_TRAIN_ERR_FORMAT, FEAR_TRAIN_ERR_UNSUPPORTED = -7, -9, -10
 FEAR_JPEG_GROUP_BLOCKS, FEAR_JPEG_GROUP_PIXELS = 32, 256
 FEAR_JPEG_DEVICE_SCAN_MAX = 16 << 20

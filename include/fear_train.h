@@ -1113,6 +1113,77 @@ int fear_miner_update(const float* templ, const float* search, const float* cls,
                       const int32_t* visible, const float* score_a, const float* score_b, int B, int n_images, int mode_max, double min_delta,
                       int step_index, FearMinerState* state, uint8_t* sheets, void* stream);
 
+/* ---- JPEG files written on the device (csrc/fear_jpeg_encode.h; DESIGN.md section 14, "Writing JPEG files"; jpeg_encode.jpeg_encode_host
+ * restates the whole call in numpy and equals Pillow's libjpeg-turbo byte for byte).  uint8 RGB frames of any size 1..FEAR_JPEG_MAX_SIDE
+ * become baseline SOF0 files: 8-bit, three components, 4:2:0, jpeg_set_quality(quality, force_baseline)'s tables, the islow FDCT, the
+ * standard Huffman tables of T.81 K.3 to K.6, a restart interval in MCUs if restart_interval != 0.  Channel 0 is R (fear_jpeg_u8 keeps
+ * cv2's reading, in which it is B).
+ *
+ * A record is host data.  The caller fills src, out, out_cap, header, header_bytes, width, height, quality (1..100) and restart_interval
+ * (0..65535); fear_jpeg_encode_plan fills the rest: where the image's scratch lies in the workspace and at which workgroup of each pass
+ * the image begins.  The header — everything from SOI to the end of the SOS segment — is built on the host: fear_jpeg_encode_header
+ * writes it (at most FEAR_JPEG_ENC_HEADER_MAX bytes; a smaller out_cap that it overruns: FEAR_TRAIN_ERR_WORKSPACE; a side, quality or
+ * interval out of range: FEAR_TRAIN_ERR_SHAPE).  The first FEAR_JPEG_ENC_TABLE_BYTES(n) bytes of the workspace are the CALLER's to write:
+ * a device copy of the n planned records, uploaded with the header bytes before the call, so that the call itself transfers nothing
+ * and never waits.
+ *
+ * fear_jpeg_encode_u8: a memset of the bit streams and eight launches, whatever n is.
+ *   transform  4 MCUs per workgroup: colour conversion, the edge rules (luma replicated right and down to whole blocks; chroma columns
+ *              replicated at full size, the last row only to an even height, then the last DOWNSAMPLED row replicated down), h2v2
+ *              downsampling, FDCT, quantiser; int16 coefficients in zigzag order, blocks in MCU order (Y00 Y01 Y10 Y11 Cb Cr).  A luma
+ *              block outside the component has no AC terms and the DC term of the block before it in that order.
+ *   sizes      one lane per block, FEAR_JPEG_ENC_GROUP_BLOCKS per workgroup: the DC difference to the previous block of the component
+ *              (0 at a restart boundary) and the block's exact bit count.
+ *   segments   one workgroup per restart segment: the exclusive scan of its blocks' bit counts, its length in bytes.
+ *   offsets    one workgroup per image: the exclusive scan of the segments' bytes; the length of the unstuffed stream.
+ *   write      one lane per block: the codes into the image's unstuffed byte stream, MSB first.  Words a block covers whole are stored;
+ *              its first and last words are merged with an integer OR into the zeroed stream, which does not depend on arrival order.
+ *              The pad bits of a segment's last byte are 1.
+ *   count      one workgroup per FEAR_JPEG_ENC_CHUNK_BYTES of the stream: its FF bytes.
+ *   lengths    one workgroup per image: the exclusive scan of the chunks' counts; the file's length, and whether it fits the slot.
+ *   assemble   one workgroup per chunk: byte i of the stream lands at header_bytes + i + (FF bytes before it) + 2 (restart markers before
+ *              it), a 00 behind each FF; the markers FF D0+((k-1)&7), the header's copy and the EOI.
+ * length_dev[i] is the file's length and status_dev[i] FEAR_TRAIN_OK, or 0 and FEAR_JPEG_ENC_OVERFLOW for a file longer than out_cap: its
+ * slot is then not written at all, and no byte at or past a slot's end is ever written.  The other images are unaffected.
+ * fear_jpeg_encode_bound is the longest file a frame can give: header, 1244 bytes per MCU and one of padding per segment, every byte
+ * stuffed, the markers and the EOI; 0 for arguments out of range.  fear_jpeg_encode_workspace_bytes is 0 for a call that would be refused.
+ * FEAR_TRAIN_ERR_SHAPE: n < 0 or n > 65535, a side outside 1..FEAR_JPEG_MAX_SIDE, a quality outside 1..100, a restart_interval outside
+ * 0..65535, header_bytes outside 1..4096, a source that overlaps its or another image's slot, plan fields that are not
+ * fear_jpeg_encode_plan's.  n == 0 returns FEAR_TRAIN_OK without a launch.  A null images, length_dev, status_dev, src, out or header:
+ * FEAR_TRAIN_ERR_NULL.  A null workspace or one below fear_jpeg_encode_workspace_bytes: FEAR_TRAIN_ERR_WORKSPACE.
+ * fear_jpeg_encode_header, _plan, _workspace_bytes and _bound are host code.                                                          */
+#define FEAR_JPEG_ENC_OVERFLOW 1
+#define FEAR_JPEG_ENC_HEADER_MAX 640
+#define FEAR_JPEG_ENC_GROUP_BLOCKS 256
+#define FEAR_JPEG_ENC_CHUNK_BYTES 4096
+#define FEAR_JPEG_ENC_TABLE_BYTES(n) (((size_t)(n) * 96 + 15) & ~(size_t)15)
+
+/* One image of a fear_jpeg_encode_u8 call.  96 bytes. */
+typedef struct FearJpegEncImage {
+    const uint8_t* src;              /* device: (height, width, 3) uint8 RGB, contiguous                                    */
+    uint8_t* out;                    /* device: the file's slot                                                            */
+    const uint8_t* header;           /* device: header_bytes bytes, SOI to the end of SOS                                  */
+    uint64_t stream_offset;          /* plan: the unstuffed stream, bytes from the workspace's start; offset 24             */
+    uint64_t work_offset;            /* plan: coefficients, bit offsets, segment and chunk tables                          */
+    int32_t width, height, quality, restart_interval;        /* offset 40                                                  */
+    uint32_t out_cap, header_bytes;  /* offset 56                                                                          */
+    uint32_t stream_cap;             /* plan: the stream's capacity in bytes; offset 64                                    */
+    uint32_t start[4];               /* plan: the image's first workgroup of transform, sizes / write, segments, count / assemble */
+    uint32_t reserved[3];
+} FearJpegEncImage;
+#ifdef __cplusplus
+static_assert(sizeof(FearJpegEncImage) == 96, "FearJpegEncImage is 96 bytes");
+#else
+_Static_assert(sizeof(FearJpegEncImage) == 96, "FearJpegEncImage is 96 bytes");
+#endif
+
+int fear_jpeg_encode_header(int width, int height, int quality, int restart_interval, uint8_t* out, size_t out_cap, size_t* out_used);
+size_t fear_jpeg_encode_bound(int width, int height, int restart_interval);
+int fear_jpeg_encode_plan(FearJpegEncImage* images, int n);
+size_t fear_jpeg_encode_workspace_bytes(const FearJpegEncImage* images, int n);
+int fear_jpeg_encode_u8(const FearJpegEncImage* images, int n, void* workspace, size_t workspace_bytes, int32_t* length_dev,
+                        int32_t* status_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
