@@ -35,6 +35,11 @@ is a bf16 GEMM only in the throughput plan: the small-batch plans run it on the 
 with `pw_split`: `pw_mfma_kernel` before the `h->math` branch).  So is the neck there when its 16-channel tile count is even
 (OP_PW: `op.pw_split && n_tiles % 2 == 0`; 16 tiles for the shipped 256-channel necks); with an odd count it takes
 `launch_pw_h`, bf16 in mode 2.
+
+Head in modes 0 and 1: the same launches with `MatOps<0>` / `MatOps<1>` (mode 0 in the throughput plan: headchain_kernel, or the
+sep16 launches with the correlation / prediction epilogues); the neck and the correlation follow the same plan rules with the
+fp16 split in place of bf16.  The `Rounding` settings for these modes are MUTANTS only (an operand that keeps just its hi half,
+a correlation without its cross terms, an fp32-mode operand rounded to fp16 / bf16): the defaults are the exact kernels.
 """
 from __future__ import annotations
 
@@ -83,8 +88,9 @@ def split_fp16(x: torch.Tensor):
 # ------------------------------------------------------------------------------------------------------------ rounding plan
 @dataclass(frozen=True)
 class Rounding:
-    """Where a mode-2 evaluation rounds.  The defaults are the kernels' rounding points; every other setting is a MUTANT (a
-    defect a kernel could have), used to show that the GPU tests' tolerances would catch it (tests/test_ref64_cpu.py)."""
+    """Where an evaluation rounds.  The defaults are the kernels' rounding points; every other setting is a MUTANT (a
+    defect a kernel could have), used to show that the GPU tests' tolerances would catch it (tests/test_ref64_cpu.py).
+    The first eight settings act in arithmetic 2, the split settings in arithmetic 1, `fp32_operand` in arithmetic 0."""
     op: str = "rne"               # "rne" | "trunc": how the depthwise output is rounded
     dw_out: bool = True           # round the depthwise output (the projection / pointwise operand)
     weights: bool = True          # round the GEMM weights
@@ -93,6 +99,10 @@ class Rounding:
     residual_after: bool = False  # MUTANT: round the block output before the residual is added
     corr_tmpl: bool = True        # round the template operand of the correlation
     storage: bool = True          # round the tensors the plan stores as bf16 (FEAR_OPT_BF16_STORE)
+    split_lo: bool = True         # arithmetic 1: a GEMM activation operand is hi + lo (False, MUTANT: hi only)
+    corr_cross: bool = True       # arithmetic 1: the correlation keeps its hi x lo and lo x hi products (False, MUTANT: hi x hi only)
+    corr_lolo: bool = False       # MUTANT, arithmetic 1: the correlation adds lo x lo (~2^-22: not separable, not claimed)
+    fp32_operand: str = ""        # MUTANT, arithmetic 0: "fp16" | "bf16": the neck / pointwise operand rounded to that format
 
     def dw(self, x: torch.Tensor) -> torch.Tensor:
         if not self.dw_out:
@@ -111,17 +121,31 @@ MUTANTS: Dict[str, Rounding] = {
     "residual_after_rounding": Rounding(residual_after=True),
     "corr_template_not_rounded": Rounding(corr_tmpl=False),
     "no_storage_rounding": Rounding(storage=False),
+    # arithmetic 1 (fp16 hi + lo split)
+    "split_lo_dropped": Rounding(split_lo=False),
+    "corr_cross_dropped": Rounding(corr_cross=False),
+    "corr_lolo_kept": Rounding(corr_lolo=True),
+    # arithmetic 0 (exact fp32): a reduced-precision kernel launched in fp32 mode
+    "operand_fp16": Rounding(fp32_operand="fp16"),
+    "operand_bf16": Rounding(fp32_operand="bf16"),
 }
+
+
+def _fp32_operand(x: torch.Tensor, rnd: Rounding) -> torch.Tensor:
+    """An arithmetic-0 GEMM operand: the fp32 value itself; rounded only by the `fp32_operand` MUTANTS."""
+    if rnd.fp32_operand:
+        return {"fp16": round_fp16, "bf16": round_bf16}[rnd.fp32_operand](x)
+    return x
 
 
 def operand(x: torch.Tensor, arith: int, rnd: Rounding = EXACT) -> torch.Tensor:
     """The activation operand of a matrix-pipe GEMM in arithmetic mode `arith`, as the kernel multiplies it."""
     if arith == 1:
         hi, lo = split_fp16(x)
-        return hi + lo
-    if arith == 2 and rnd.gemm_in:
-        return round_bf16(x)
-    return x
+        return hi + lo if rnd.split_lo else hi
+    if arith == 2:
+        return round_bf16(x) if rnd.gemm_in else x
+    return _fp32_operand(x, rnd)
 
 
 # --------------------------------------------------------------------------------------------------------- op-name parsing
@@ -181,8 +205,8 @@ class Ref64Net:
         """A depthwise output as the following pointwise GEMM takes it."""
         if arith == 1:
             hi, lo = split_fp16(d)
-            return hi + lo
-        return rnd.dw(d) if arith == 2 else d
+            return hi + lo if rnd.split_lo else hi
+        return rnd.dw(d) if arith == 2 else _fp32_operand(d, rnd)
 
     # -- trunk
     def stem_block1(self, img: torch.Tensor) -> torch.Tensor:
@@ -257,7 +281,11 @@ class Ref64Net:
         if arith == 1:
             zh, zl = split_fp16(z)
             xh, xl = split_fp16(x)
-            s = zf(zh) @ xf(xh) + zf(zh) @ xf(xl) + zf(zl) @ xf(xh)          # lo x lo dropped (MatOps<1>::mma2)
+            s = zf(zh) @ xf(xh)
+            if rnd.split_lo and rnd.corr_cross:
+                s = s + zf(zh) @ xf(xl) + zf(zl) @ xf(xh)                    # lo x lo dropped (MatOps<1>::mma2)
+            if rnd.corr_lolo:
+                s = s + zf(zl) @ xf(xl)
         else:
             if arith == 2:
                 x = round_bf16(x)

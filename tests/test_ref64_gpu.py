@@ -1,15 +1,21 @@
-"""Each fused block, and the bf16 head, against the float64 reference that rounds where the kernels round (oracle/fear_ref64.py).
+"""Each fused block, and the neck and head in every arithmetic mode, against the float64 reference that rounds where the kernels
+round (oracle/fear_ref64.py).
 
 The end-to-end tests compare the whole network with the fp32 oracle; there a block that is wrong by a few bf16 roundings is
-diluted by 28 blocks and a head, and the bf16 mode is held only to an 8e-2 band against fp32.  Here:
+diluted by 28 blocks and a head, the bf16 mode is held only to an 8e-2 band against fp32, and the fp32 and fp16-split modes to
+1e-3, three orders of magnitude above what fp32 accumulation costs.  Here:
 
 * every trunk block is tapped through a truncated model with an identity neck (tests/blocktaps.py) and compared with the
   reference evaluated on the DEVICE's own input tap: only block k's own arithmetic is compared, errors do not build up;
 * the mode-2 head (sep16 `*_h` launches, headchain_b) is compared with the reference neck + head on the device's trunk output;
+* so are the mode-0 and mode-1 neck and head, on every launch plan and with every option that puts another mode-0 kernel
+  behind them (head chain, dual head, tiny SepConv slices, the neck inside a trunk chain kernel), at fp32 bounds;
+* the template branch's neck (`get_features`, fp32 in every mode) is compared with the reference neck on the twin's output;
 * the bf16 storage of the trunk's front is shown to be the rounding the reference models.
 
 Deviations are element-wise, in units of the tensor's own scale (max |reference| per crop): |got - ref| <= TOL * scale.
-Runtime on one MI355X: 18 s for the module (the 44 truncated models of the block taps included).
+Runtime on one MI355X: 31 s for the module (the 44 truncated models of the block taps included; 13 s of it the mode-0 / mode-1
+head and template-neck tests).
 """
 import numpy as np
 import pytest
@@ -25,6 +31,14 @@ FRAC_BLOCK2 = 6.5e-2          # mode 2: fraction of a block's output elements of
 TOL_HEAD2 = 1e-2              # mode-2 neck + head, maps: max deviation
 # mode-2 neck + head, maps: median deviation (what separates the head mutants), by plan
 TOL_HEAD2_MEDIAN = {"small": 8.5e-5, "throughput": 1e-6}
+# mode-0 / mode-1 neck + head, maps, by mode and plan kind ("throughput_fused": the mode-0 throughput plan whose neck is inside
+# a trunk chain kernel; the compared unit is then that chain op + the head): max and median deviation.  At most 4x the worst
+# measured on the MI355X (test_fp32_and_split_head_against_the_float64_reference)
+TOL_HEAD01 = {0: {"tiny": 8e-6, "small": 8e-6, "throughput": 1e-5, "throughput_fused": 9e-6},
+              1: {"tiny": 6.5e-6, "small": 7e-6, "throughput": 7e-6}}
+TOL_HEAD01_MEDIAN = {0: {"tiny": 8e-7, "small": 7e-7, "throughput": 1e-6, "throughput_fused": 6e-7},
+                     1: {"tiny": 6e-7, "small": 6e-7, "throughput": 7e-7}}
+TOL_NECK_TEMPLATE = 2e-6      # the template branch's neck, max deviation (measured worst 5.24e-7)
 STORAGE_RATIO = 0.8           # whole FEAR-M network: distance to the reference with storage rounding / without
 STORAGE_MEASURED = 1.74e-2    # the kernels' measured distance to the reference with storage rounding
 PASS_SIZES = (1, 3, 16, 17, 96, 97)     # tiny <= 16 < small <= 96 < throughput (FEAR_TINY_PASS, FEAR_OPT_SMALL_PASS defaults)
@@ -222,6 +236,224 @@ def test_bf16_head_against_the_float64_reference(tmp_path_factory, plan):
             assert err <= TOL_HEAD2 and median <= tol_median, \
                 f"{plan} {what} update={upd is not None}: max {err:.3e}, median {median:.3e} of scale"
     print(f"REF64 head bf16 {plan}: max {worst:.3e} median {worst_median:.3e}")
+
+
+# ---------------------------------------------------------------------------------- the fp32 and fp16-split neck and head
+def _head_models():
+    from conftest import WEIGHTS, WEIGHTS_DEMO
+    from feartracker_amd.hip_backend import WEIGHTS_FEAR_M
+    return {"fear_xs": WEIGHTS, "fear_xs_demo": WEIGHTS_DEMO, "fear_m": WEIGHTS_FEAR_M}
+
+
+class HeadNets:
+    """The full net, the float64 reference and the identity-neck twins (one per cut) of each weight file: built on first use,
+    kept for the module."""
+
+    def __init__(self, directory):
+        self.dir, self.nets, self.refs, self.twins = directory, {}, {}, {}
+
+    def net(self, model):
+        from feartracker_amd import FEARNetHIP
+        if model not in self.nets:
+            self.nets[model] = FEARNetHIP(_head_models()[model], device=0, max_batch=MAX_BATCH)
+        return self.nets[model]
+
+    def ref(self, model):
+        from oracle.fear_ref64 import Ref64Net
+        if model not in self.refs:
+            self.refs[model] = Ref64Net(_head_models()[model])
+        return self.refs[model]
+
+    def twin(self, model, k):
+        """stem + blocks 1..k of the model + an identity neck."""
+        from feartracker_amd import FEARNetHIP
+        if (model, k) not in self.twins:
+            cut = str(self.dir / f"{model}_{k}.fearw")
+            write_truncated(_head_models()[model], k, cut)
+            self.twins[(model, k)] = FEARNetHIP(cut, device=0, max_batch=MAX_BATCH)
+        return self.twins[(model, k)]
+
+
+@pytest.fixture(scope="module")
+def head_nets(tmp_path_factory):
+    nets = HeadNets(tmp_path_factory.mktemp("head_twins"))
+    yield nets
+    nets.nets.clear()
+    nets.twins.clear()
+
+
+def head01_arith(mode: int, plan: str, neck_tiles: int):
+    """(neck, correlation) arithmetic the engine gives a plan in `mode` (fear_engine.hip run_plan).  OP_PW: the small-batch
+    plans run the neck on the split-column fp32 kernel when its 16-channel tile count is even (`pw_split && n_tiles % 2 == 0`),
+    every other neck of a search plan takes `launch_pw_h` in modes 1 / 2.  OP_CORR: `pw_split` -> the fp32 kernel, else
+    `launch_pw_h`."""
+    throughput = plan == "throughput"
+    return (mode if throughput or neck_tiles % 2 else 0), (mode if throughput else 0)
+
+
+def head01_variants(mode: int, plan: str):
+    """The option sets one case runs: trunk chain kernels, head chain and dual head in the mode-0 throughput plan, the tiny
+    SepConv slice kernel in the mode-0 tiny plan (the options that change a mode-0 kernel; modes 1 / 2 have none of them)."""
+    if mode == 0 and plan == "throughput":
+        return [dict(chain=c, head_chain=hc, dual=d) for c in (True, False) for hc in (True, False) for d in (False, True)]
+    if mode == 0 and plan == "tiny":
+        return [dict(tiny_sep=True), dict(tiny_sep=False)]
+    return [dict()]
+
+
+def _head01_cases():
+    cases = []
+    for mode in (0, 1):
+        for plan, n in (("tiny", 3), ("tiny", 16), ("small", 17), ("small", 96), ("throughput", 97), ("throughput", 6)):
+            cases.append((mode, plan, n, "fear_xs"))
+        for model in ("fear_xs_demo", "fear_m"):
+            for plan, n in (("tiny", 3), ("small", 17), ("throughput", 6)):
+                cases.append((mode, plan, n, model))
+    return cases
+
+
+@pytest.mark.parametrize("mode,plan,n,model", _head01_cases(), ids=lambda v: str(v))
+def test_fp32_and_split_head_against_the_float64_reference(head_nets, crops, mode, plan, n, model):
+    """FEAR_OPT_MATH = 0 and 1: neck + head of `track_maps` vs the float64 reference neck + head (arithmetic per plan:
+    `head01_arith`) evaluated on the device's own trunk output (the identity-neck twin's `get_features`; same trunk ops,
+    asserted from the op names, else the test fails with both lists) and template features, with and without `update=`, on
+    the checked crops of a pass of n: n = 3, 16 (tiny plan), 17, 96 (small plan), 97 and 6 with FEAR_OPT_SMALL_PASS = 0
+    (throughput plan); FEAR-XS at every size, the demo FEAR-XS weights and FEAR-M at one size per plan.
+    Kernels, asserted from `plan()`: mode 0, throughput plan: headchain_boxtower (head chain on) or the sep16 launches with
+    the correlation / prediction epilogues (off), each with one and two head streams; mode 0, tiny plan: the `nsplit` slices
+    and pred16 launches with the row-split slice kernel on and off (the op names are the same either way, so the flag's
+    witness is that the two runs' maps are not bit-identical); mode 1: sep16 `*_h` / pred16 launches and the `pw_h`
+    correlation, never a head chain.  FEAR_OPT_DUAL_HEAD changes no op name (it only puts the bbox branch on a second
+    stream): it is run, it cannot be witnessed from the plan.
+    The neck inside a trunk chain kernel (mode 0, throughput plan with FEAR_OPT_CHAIN on: chain16_7blocks_neck at 97 crops,
+    chain32_16_11blocks_neck with FEAR_OPT_SMALL_PASS = 0).  An identity-neck twin cannot show that op: `get_features` runs
+    the template-branch plan, which has no chain kernels, and the chain kernel takes a 256-channel neck only.  The twin is
+    therefore cut in FRONT of the chain op (its ops = the search plan's ops ahead of the chain, asserted), and the reference
+    evaluates the chain's own blocks, the neck (arithmetic 0) and the head on that tap: the compared unit is chain op + head
+    (plan kind "throughput_fused").  With FEAR_OPT_CHAIN and FEAR_OPT_CHAIN32 off the neck is an op of its own and the twin
+    is the whole trunk.  FEAR_OPT_E1_PAIR is off throughout: the template-branch plan has no e1pair kernel either, and the
+    pair lies ahead of every tap.
+    Bounds, in map scale, per map (TOL_HEAD01 / TOL_HEAD01_MEDIAN, at most 4x the measured worst; the mutants of
+    tests/test_ref64_cpu.py lie at least 3x above the median bounds).  Measured worst (MI355X) over all cases of a mode and
+    plan kind, max / median -> bounds:
+      mode 0  tiny              2.18e-6 / 2.27e-7 (FEAR-M)  -> 8e-6 / 8e-7      small  2.20e-6 / 1.82e-7 -> 8e-6 / 7e-7
+              throughput        2.85e-6 / 2.90e-7 (FEAR-M)  -> 1e-5 / 1e-6
+              throughput_fused  2.36e-6 / 1.61e-7           -> 9e-6 / 6e-7
+      mode 1  tiny  1.72e-6 / 1.66e-7 -> 6.5e-6 / 6e-7      small  1.86e-6 / 1.67e-7 -> 7e-6 / 6e-7
+              throughput  1.83e-6 / 1.79e-7 -> 7e-6 / 7e-7
+    (FEAR-XS alone: max 2.36e-6, median 1.6e-7 fused and at most 8.6e-8 elsewhere.)  torch's own fp32 evaluation of the same
+    head sits 1.2e-6 / 4.4e-8 from float64 (tests/test_ref64_cpu.py): every kernel is within 2.5x of that in the max, and
+    within 7x in the median (FEAR-M, random weights); nothing near the 50x that would make it a finding.  The nearest mutant
+    median is 1.2e-5 (correlation cross terms dropped, mode 1 throughput: 17x the bound); the fp16 / split-lo mutants are
+    at 3.2e-5 and above, the bf16 one at 2.7e-4.  Head chain on / off and one / two head streams give identical figures
+    (the same products in the same order); the row-split tiny slices do not (6.5e-7 against 1.97e-6 max)."""
+    net, ref = head_nets.net(model), head_nets.ref(model)
+    length = trunk_length(_head_models()[model])
+    throughput = plan == "throughput"
+    assert plan_kind(n) == plan or (throughput and n <= 96)
+    neck_tiles = (ref.convs[ref.neck["conv"][0]]["w"].shape[0] + 15) // 16
+    neck_arith, corr_arith = head01_arith(mode, plan, neck_tiles)
+    sel = checked_crops(n)
+    x = crops[256][:n].cuda()
+    t = crops[128][:n].cuda()
+    failures, maps = [], {}
+    for opt in head01_variants(mode, plan):
+        chain, head_chain = opt.get("chain", True), opt.get("head_chain", True)
+        dual, tiny_sep = opt.get("dual", False), opt.get("tiny_sep", True)
+        label = f"{model} n={n}" + "".join(f" {k}={int(v)}" for k, v in opt.items())
+
+        def configure(h):
+            h.set_math(mode)
+            h.set_small_pass(0 if throughput and n <= 96 else 96)
+            h.set_chain(chain)
+            h.set_chain32(2 if chain else 0)
+            h.set_e1_pair(False)
+            h.set_head_chain(head_chain)
+            h.set_dual_head(dual)
+            h.set_tiny_sep(tiny_sep)
+            h.set_plan_crops(n)
+
+        configure(net)
+        search = [o for o, _, _ in net.plan(256, True)]
+        at = next(i for i, o in enumerate(search) if "neck_" in o)
+        fused = not search[at].startswith("neck_")                      # the neck inside a trunk chain op
+        k = (at if search[0].startswith("stem_irt") else at - 1) if fused else length - 1
+        twin = head_nets.twin(model, k)
+        configure(twin)
+        twin_ops = [o for o, _, _ in twin.plan(256, False)]
+        assert twin_ops[-1].startswith("neck_") and twin_ops[:-1] == search[:at], \
+            f"{label}: the twin cut at block {k} does not run the search plan's trunk ops\n twin: {twin_ops}\n full: {search}"
+        head_ops = search[at + 1:]
+        if model != "fear_m":          # (the FEAR-XS block table is the one the trunk chain kernels are written for)
+            assert fused == (mode == 0 and throughput and chain), (label, search)
+        assert fused == search[at].startswith(("chain16_", "chain32_16_")), (label, search)
+        chain_head = mode == 0 and throughput and head_chain
+        assert any(o.startswith("headchain_boxtower_") for o in head_ops) == chain_head, (label, head_ops)
+        if not chain_head:
+            assert not any(o.startswith("headchain") for o in search), (label, search)
+            assert any(o.startswith("sep16") for o in head_ops) and any("pred" in o for o in head_ops), (label, head_ops)
+        if plan == "tiny" and mode == 0:
+            assert any("nsplit" in o for o in head_ops) and any("pred16" in o for o in head_ops), (label, head_ops)
+        z = net.get_features(t)
+        zu = net.get_features(torch.flip(t, dims=(0,)))
+        trunk = twin.get_features(x)[sel].cpu()
+        for kk in range(k + 1, length):                               # the blocks inside the chain op
+            trunk = ref.ir_block(kk, trunk, 0)
+        feat = ref.neck_out(trunk, 0 if fused else neck_arith)
+        kind = "throughput_fused" if fused else plan
+        worst = worst_median = 0.0
+        for upd in (None, zu):
+            bbox, cls = net.track_maps(x, z, update=upd)
+            assert torch.isfinite(bbox).all() and torch.isfinite(cls).all(), label
+            maps[(tiny_sep, upd is not None)] = (bbox.cpu(), cls.cpu())
+            rb, rc = ref.head_maps(feat, z[sel].cpu(), None if upd is None else upd[sel].cpu(), mode, corr_arith)
+            for got, want, what in ((bbox[sel].cpu(), rb, "bbox"), (cls[sel].cpu(), rc, "cls")):
+                err, _ = deviation(got, want)
+                median = median_deviation(got, want)
+                worst, worst_median = max(worst, err), max(worst_median, median)
+                if err > TOL_HEAD01[mode][kind] or median > TOL_HEAD01_MEDIAN[mode][kind]:
+                    failures.append(f"{label} {kind} {what} update={upd is not None}: max {err:.3e}, median {median:.3e} of scale")
+        print(f"REF64 head mode {mode} {kind} {label}: max {worst:.3e} median {worst_median:.3e}")
+    if plan == "tiny" and mode == 0:
+        for u in (False, True):
+            assert not all(torch.equal(a, b) for a, b in zip(maps[(True, u)], maps[(False, u)])), \
+                f"{model} n={n}: FEAR_OPT_TINY_SEP changed nothing"
+    assert not failures, "\n".join(failures)
+
+
+@pytest.mark.parametrize("mode", (0, 1, 2))
+@pytest.mark.parametrize("model", ("fear_xs", "fear_m"))
+def test_template_neck_against_the_float64_reference(head_nets, crops, model, mode):
+    """`get_features` on 128-pixel crops runs the template-branch plan, whose neck is the fp32 `pw_mfma_kernel` in every mode
+    (run_plan, OP_PW: `launch_pw_h` only with a head): the full model's features vs the float64 reference neck (arithmetic 0)
+    on the identity-neck twin's output (same trunk ops, asserted), at pass sizes either side of the plan thresholds.  Max
+    deviation only.  The checked
+    crops go through the reference; every crop of the pass must be finite, and for n <= 17 equal, bit for bit, the same crop
+    of a pass of the same size (the same plan) with the crops in reverse order: the engine computes a crop the same way
+    whatever its neighbours.  Measured worst (MI355X): FEAR-XS 4.26e-7, FEAR-M 5.24e-7, the same in every mode (the kernel is
+    the same) -> TOL_NECK_TEMPLATE = 2e-6 (at most 4x)."""
+    net, ref = head_nets.net(model), head_nets.ref(model)
+    twin = head_nets.twin(model, trunk_length(_head_models()[model]) - 1)
+    worst = 0.0
+    for n in PASS_SIZES:
+        for h in (net, twin):
+            h.set_math(mode)
+            h.set_small_pass(96)
+            h.set_plan_crops(n)
+        ops = [o for o, _, _ in net.plan(128, False)]
+        twin_ops = [o for o, _, _ in twin.plan(128, False)]
+        assert ops[-1].startswith("neck_") and twin_ops[:-1] == ops[:-1], f"n={n}\n twin: {twin_ops}\n full: {ops}"
+        x = crops[128][:n].cuda()
+        got = net.get_features(x)
+        assert torch.isfinite(got).all(), n
+        if n <= 17:
+            again = net.get_features(torch.flip(x, dims=(0,)))
+            assert torch.equal(torch.flip(again, dims=(0,)), got), n
+        sel = checked_crops(n)
+        err, _ = deviation(got[sel].cpu(), ref.neck_out(twin.get_features(x)[sel].cpu(), 0))
+        worst = max(worst, err)
+        assert err <= TOL_NECK_TEMPLATE, f"{model} mode {mode} n={n}: {err:.3e} of scale"
+    print(f"REF64 template neck {model} mode {mode}: max {worst:.3e}")
 
 
 # ------------------------------------------------------------------------------------------------------------ bf16 storage
