@@ -1,4 +1,4 @@
-// fear_jpeg_encode.h — baseline JPEG files written on gfx950 from uint8 RGB frames: the counterpart of fear_jpeg_decode.h and
+// fear_jpeg_encode.h — baseline JPEG files (4:2:0, 4:2:2, 4:4:4 or one gray component) written on gfx950 from uint8 frames: the counterpart of fear_jpeg_decode.h and
 // fear_jpeg_huffman.h (include/fear_train.h states the ABI and the passes, DESIGN.md section 14 "Writing JPEG files" the contract;
 // jpeg_encode.jpeg_encode_host restates it in numpy and equals Pillow's libjpeg-turbo byte for byte).  The forward transform shares
 // jpeg_fdct, kJpegBase and the LDS pitch with fear_train_jpeg.h; what is new is frames of any size, the Huffman coder in parallel and
@@ -24,7 +24,19 @@ constexpr int kEncMcus = kJpMcus;                              // MCUs per workg
 constexpr int kEncGroup = FEAR_JPEG_ENC_GROUP_BLOCKS;          // blocks per workgroup of sizes and write
 constexpr int kEncChunk = FEAR_JPEG_ENC_CHUNK_BYTES;           // stream bytes per workgroup of count and assemble
 static_assert(kEncGroup == 256 && kEncChunk == 4096, "one lane per block; one lane per 16 bytes of a chunk");
-constexpr uint32_t kEncMcuBytes = 1244;                        // 4 (9 + 11 + 63 x 26) + 2 (11 + 11 + 63 x 26) bits: the longest MCU
+constexpr uint32_t kEncLumaBits = 9 + 11 + 63 * 26, kEncChromaBits = 11 + 11 + 63 * 26;   // the longest block; 4:2:0's MCU: 1244 bytes
+
+// A record's sampling: FEAR_JPEG_ENC_420 .. _GRAY in the low byte.  Per layout the MCU's side shifts, its blocks B, of which the first
+// L are luma, and the MCUs per workgroup of the transform: B x MCUS is the 24 blocks of the LDS tile in every layout.
+__host__ __device__ inline int enc_mode(uint32_t sampling) { return (int)(sampling & 0xFFu); }
+__host__ __device__ inline bool enc_gray_rgb(uint32_t sampling) { return (sampling & FEAR_JPEG_ENC_GRAY_RGB) != 0; }
+__host__ __device__ inline int enc_blocks(int mode) { return mode == 0 ? 6 : mode == 1 ? 4 : mode == 2 ? 3 : 1; }
+__host__ __device__ inline int enc_luma(int mode) { return mode == 0 ? 4 : mode == 1 ? 2 : 1; }
+__host__ __device__ inline int enc_mcus(int mode) { return mode == 0 ? kEncMcus : mode == 1 ? 6 : mode == 2 ? 8 : 24; }
+static_assert(kEncMcus * 6 == kJpBlocks && kJpBlocks == 24, "the tile is 24 blocks: 4, 6, 8 or 24 MCUs");
+inline bool enc_sampling_ok(uint32_t sampling) {
+    return sampling <= FEAR_JPEG_ENC_GRAY || sampling == (FEAR_JPEG_ENC_GRAY | FEAR_JPEG_ENC_GRAY_RGB);
+}
 
 // zigzag position -> natural index
 constexpr uint8_t kEncZigzagHost[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -90,17 +102,19 @@ __device__ const EncCodes kEncCodes = enc_make_codes();
 // block's bit count, then its bit offset in its segment) | uint32 seg [n_seg + 1] (a segment's bytes, then its byte offset) | uint32 chunk
 // [n_chunks + 1] (a chunk's FF bytes, then the FF bytes before it) | uint32 state [4] (the stream's length, 1 if it exceeds stream_cap)
 struct EncGeom {
-    int mw, mh;
+    int mw, mh, B;
     uint32_t n_mcu, n_blocks, interval, n_seg, n_chunks;
     size_t bits_at, seg_at, chunk_at, state_at, bytes;
 };
 
-__host__ __device__ inline EncGeom enc_geom(int W, int H, int restart_interval, uint32_t stream_cap) {
+__host__ __device__ inline EncGeom enc_geom(int W, int H, int restart_interval, uint32_t stream_cap, uint32_t sampling) {
     EncGeom g;
-    g.mw = (W + 15) >> 4;
-    g.mh = (H + 15) >> 4;
+    const int mode = enc_mode(sampling), sx = mode < 2 ? 4 : 3, sy = mode == 0 ? 4 : 3;
+    g.mw = (W + (1 << sx) - 1) >> sx;
+    g.mh = (H + (1 << sy) - 1) >> sy;
+    g.B = enc_blocks(mode);
     g.n_mcu = (uint32_t)g.mw * (uint32_t)g.mh;
-    g.n_blocks = g.n_mcu * 6;
+    g.n_blocks = g.n_mcu * (uint32_t)g.B;
     g.interval = restart_interval > 0 && (uint32_t)restart_interval < g.n_mcu ? (uint32_t)restart_interval : g.n_mcu;
     g.n_seg = (g.n_mcu + g.interval - 1) / g.interval;
     g.n_chunks = (stream_cap + kEncChunk - 1) / kEncChunk;
@@ -155,56 +169,183 @@ __device__ __forceinline__ uint32_t enc_wg_exscan(uint32_t v, uint32_t* lds4, ui
     return base + inc - v;
 }
 
+// The transform's two layout-dependent stages, one body per sampling: enc_fill puts the workgroup's MCUs into the 24-block LDS tile
+// (level-shifted samples, blocks in MCU order), enc_store writes the tile's quantised blocks in zigzag order.  A workgroup belongs to
+// one image, so the choice between the bodies is uniform.
+struct EncTile {
+    int W, H, mw, mh, n_mcu, group;
+};
+
+__device__ __forceinline__ int enc_y(int r, int g, int b) { return ((19595 * r + 38470 * g + 7471 * b + 32768) >> 16) - 128; }
+__device__ __forceinline__ int enc_cb(int r, int g, int b) { return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16; }
+__device__ __forceinline__ int enc_cr(int r, int g, int b) { return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16; }
+
+// 4:2:0: four MCUs of 16 x 16, blocks Y00 Y01 Y10 Y11 Cb Cr
+__device__ __forceinline__ void enc_fill_420(int* blk, const uint8_t* __restrict__ src, const EncTile& t, int tid) {
+    // one 2 x 2 quad of one MCU per lane.  Luma clamps its coordinates to the frame (replication right and down).  Chroma clamps the
+    // full-size column, and the full-size rows of the last downsampled row that exists: rows below it repeat THAT row.
+    const int W = t.W, H = t.H;
+    const int g = tid >> 6, qy = (tid >> 3) & 7, qx = tid & 7;
+    const int mcu = t.group * kEncMcus + g;
+    int* yb = blk + (g * 6 + (qy >> 2) * 2 + (qx >> 2)) * kJpPitch + ((2 * qy) & 7) * 8 + ((2 * qx) & 7);
+    int cb = 0, cr = 0;
+    if (mcu < t.n_mcu) {
+        const int my = mcu / t.mw, mx = mcu - my * t.mw;
+        const int cy = min(my * 8 + qy, ((H + 1) >> 1) - 1);
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            const int yl = min(my * 16 + 2 * qy + dy, H - 1), yc = min(2 * cy + dy, H - 1);
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const int x = min(mx * 16 + 2 * qx + dx, W - 1);
+                const uint8_t* p = src + ((size_t)yl * W + x) * 3;
+                int rr = p[0], gg = p[1], bb = p[2];
+                yb[dy * 8 + dx] = ((19595 * rr + 38470 * gg + 7471 * bb + 32768) >> 16) - 128;
+                if (yc != yl) {
+                    p = src + ((size_t)yc * W + x) * 3;
+                    rr = p[0]; gg = p[1]; bb = p[2];
+                }
+                cb += (-11059 * rr - 21709 * gg + 32768 * bb + (128 << 16) + 32767) >> 16;
+                cr += (32768 * rr - 27439 * gg - 5329 * bb + (128 << 16) + 32767) >> 16;
+            }
+        }
+        const int bias = 1 + (qx & 1);                    // 1, 2, 1, 2 along a row of the downsampled plane
+        cb = ((cb + bias) >> 2) - 128;
+        cr = ((cr + bias) >> 2) - 128;
+    } else {
+        yb[0] = yb[1] = yb[8] = yb[9] = 0;
+    }
+    blk[(g * 6 + 4) * kJpPitch + qy * 8 + qx] = cb;
+    blk[(g * 6 + 5) * kJpPitch + qy * 8 + qx] = cr;
+}
+
+// 4:2:2 (h2v1): six MCUs of 16 x 8, blocks Y0 Y1 Cb Cr.  One horizontal pair of one MCU per step: 384 pairs.  Every component clamps
+// its full-size coordinates to the frame; the bias is 0, 1, 0, 1 along a row of the downsampled plane.
+__device__ __forceinline__ void enc_fill_422(int* blk, const uint8_t* __restrict__ src, const EncTile& t, int tid) {
+    for (int p = tid; p < 6 * 64; p += 256) {
+        const int g = p >> 6, py = (p >> 3) & 7, qx = p & 7;
+        const int mcu = t.group * 6 + g;
+        int* yb = blk + (g * 4 + (qx >> 2)) * kJpPitch + py * 8 + ((2 * qx) & 7);
+        int cb = 0, cr = 0;
+        if (mcu < t.n_mcu) {
+            const int my = mcu / t.mw, mx = mcu - my * t.mw;
+            const uint8_t* row = src + (size_t)min(my * 8 + py, t.H - 1) * t.W * 3;
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const uint8_t* q = row + (size_t)min(mx * 16 + 2 * qx + dx, t.W - 1) * 3;
+                const int rr = q[0], gg = q[1], bb = q[2];
+                yb[dx] = enc_y(rr, gg, bb);
+                cb += enc_cb(rr, gg, bb);
+                cr += enc_cr(rr, gg, bb);
+            }
+            cb = ((cb + (qx & 1)) >> 1) - 128;
+            cr = ((cr + (qx & 1)) >> 1) - 128;
+        } else {
+            yb[0] = yb[1] = 0;
+        }
+        blk[(g * 4 + 2) * kJpPitch + py * 8 + qx] = cb;
+        blk[(g * 4 + 3) * kJpPitch + py * 8 + qx] = cr;
+    }
+}
+
+// 4:4:4: eight MCUs of 8 x 8, blocks Y Cb Cr.  Two pixels of one MCU per lane, replicated right and down.
+__device__ __forceinline__ void enc_fill_444(int* blk, const uint8_t* __restrict__ src, const EncTile& t, int tid) {
+    const int g = tid >> 5, py = (tid >> 2) & 7, px = (tid & 3) * 2;
+    const int mcu = t.group * 8 + g;
+    int* yb = blk + (g * 3) * kJpPitch + py * 8 + px;
+    if (mcu < t.n_mcu) {
+        const int my = mcu / t.mw, mx = mcu - my * t.mw;
+        const uint8_t* row = src + (size_t)min(my * 8 + py, t.H - 1) * t.W * 3;
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+            const uint8_t* q = row + (size_t)min(mx * 8 + px + dx, t.W - 1) * 3;
+            const int rr = q[0], gg = q[1], bb = q[2];
+            yb[dx] = enc_y(rr, gg, bb);
+            yb[kJpPitch + dx] = enc_cb(rr, gg, bb) - 128;
+            yb[2 * kJpPitch + dx] = enc_cr(rr, gg, bb) - 128;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) yb[c * kJpPitch] = yb[c * kJpPitch + 1] = 0;
+    }
+}
+
+// gray: 24 MCUs of one block.  The source has one channel, or three of which the luma is taken (RGB true).
+template <bool RGB>
+__device__ __forceinline__ void enc_fill_gray(int* blk, const uint8_t* __restrict__ src, const EncTile& t, int tid) {
+    for (int e = tid; e < kJpBlocks * 64; e += 256) {
+        const int g = e >> 6, py = (e >> 3) & 7, px = e & 7;
+        const int mcu = t.group * kJpBlocks + g;
+        int v = 0;
+        if (mcu < t.n_mcu) {
+            const int my = mcu / t.mw, mx = mcu - my * t.mw;
+            const size_t at = (size_t)min(my * 8 + py, t.H - 1) * t.W + min(mx * 8 + px, t.W - 1);
+            if (RGB) v = enc_y(src[at * 3], src[at * 3 + 1], src[at * 3 + 2]);
+            else v = (int)src[at] - 128;
+        }
+        blk[g * kJpPitch + py * 8 + px] = v;
+    }
+}
+
+// zigzag int16 in MCU order: two coefficients per store, the workgroup's 24 blocks contiguous.  A luma block outside the component
+// takes the DC term of the block before it in MCU order and no AC terms: MODE 0 has them right and below, MODE 1 to the right.
+template <int MODE>
+__device__ __forceinline__ void enc_store(const int* blk, uint32_t* dst, const EncTile& t, int tid) {
+    constexpr int B = MODE == 0 ? 6 : MODE == 1 ? 4 : MODE == 2 ? 3 : 1, PER = kJpBlocks / B;
+    const int by = (t.H + 7) >> 3, bx = (t.W + 7) >> 3;
+    for (int e = tid; e < kJpBlocks * 32; e += 256) {
+        const int bl = e >> 5, z = (e & 31) * 2;
+        const int g = bl / B, kk = bl - g * B;
+        const int mcu = t.group * PER + g;
+        if (mcu >= t.n_mcu) continue;
+        int from = kk;
+        if (MODE == 0) {
+            const int my = mcu / t.mw, mx = mcu - my * t.mw;
+            const bool R = mx == t.mw - 1 && (bx & 1), D = my == t.mh - 1 && (by & 1);
+            const int s1 = R ? 0 : 1, s2 = D ? s1 : 2, s3 = (R || D) ? s2 : 3;
+            from = kk == 1 ? s1 : kk == 2 ? s2 : kk == 3 ? s3 : kk;
+        } else if (MODE == 1) {
+            if (kk == 1 && (bx & 1) && mcu % t.mw == t.mw - 1) from = 0;
+        }
+        const int* sb = blk + (g * B + from) * kJpPitch;
+        int v0, v1;
+        if (from != kk) {
+            v0 = z == 0 ? sb[0] : 0;
+            v1 = 0;
+        } else {
+            v0 = sb[kEncZigzag[z]];
+            v1 = sb[kEncZigzag[z + 1]];
+        }
+        dst[e] = ((uint32_t)v0 & 0xFFFFu) | ((uint32_t)v1 << 16);
+    }
+}
+
 __global__ __launch_bounds__(256) void jpeg_enc_transform_kernel(EncArgs a) {
     __shared__ __attribute__((aligned(16))) int blk[kJpBlocks * kJpPitch];
     __shared__ int qt[128];
     const int tid = threadIdx.x;
     const int img = enc_find(a.rec, a.n, 0, blockIdx.x);
     const FearJpegEncImage* r = a.rec + img;
-    const int W = r->width, H = r->height, quality = r->quality;
-    const int mw = (W + 15) >> 4, mh = (H + 15) >> 4, n_mcu = mw * mh;
-    const int group = (int)(blockIdx.x - r->start[0]);
+    const int quality = r->quality;
+    const uint32_t sampling = r->sampling;
+    const int mode = enc_mode(sampling);
+    const uint8_t* src = r->src;
+    EncTile t;
+    t.W = r->width;
+    t.H = r->height;
+    t.mw = (t.W + (mode < 2 ? 15 : 7)) >> (mode < 2 ? 4 : 3);
+    t.mh = (t.H + (mode == 0 ? 15 : 7)) >> (mode == 0 ? 4 : 3);
+    t.n_mcu = t.mw * t.mh;
+    t.group = (int)(blockIdx.x - r->start[0]);
     if (tid < 128) {                                          // jpeg_set_quality(quality, force_baseline)
         const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
         qt[tid] = min(max(((int)kJpegBase[tid] * scale + 50) / 100, 1), 255);
     }
-    {
-        // one 2 x 2 quad of one MCU per lane.  Luma clamps its coordinates to the frame (replication right and down).  Chroma clamps the
-        // full-size column, and the full-size rows of the last downsampled row that exists: rows below it repeat THAT row.
-        const int g = tid >> 6, qy = (tid >> 3) & 7, qx = tid & 7;
-        const int mcu = group * kEncMcus + g;
-        int* yb = blk + (g * 6 + (qy >> 2) * 2 + (qx >> 2)) * kJpPitch + ((2 * qy) & 7) * 8 + ((2 * qx) & 7);
-        int cb = 0, cr = 0;
-        if (mcu < n_mcu) {
-            const int my = mcu / mw, mx = mcu - my * mw;
-            const int cy = min(my * 8 + qy, ((H + 1) >> 1) - 1);
-            const uint8_t* src = r->src;
-#pragma unroll
-            for (int dy = 0; dy < 2; ++dy) {
-                const int yl = min(my * 16 + 2 * qy + dy, H - 1), yc = min(2 * cy + dy, H - 1);
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx) {
-                    const int x = min(mx * 16 + 2 * qx + dx, W - 1);
-                    const uint8_t* p = src + ((size_t)yl * W + x) * 3;
-                    int rr = p[0], gg = p[1], bb = p[2];
-                    yb[dy * 8 + dx] = ((19595 * rr + 38470 * gg + 7471 * bb + 32768) >> 16) - 128;
-                    if (yc != yl) {
-                        p = src + ((size_t)yc * W + x) * 3;
-                        rr = p[0]; gg = p[1]; bb = p[2];
-                    }
-                    cb += (-11059 * rr - 21709 * gg + 32768 * bb + (128 << 16) + 32767) >> 16;
-                    cr += (32768 * rr - 27439 * gg - 5329 * bb + (128 << 16) + 32767) >> 16;
-                }
-            }
-            const int bias = 1 + (qx & 1);                    // 1, 2, 1, 2 along a row of the downsampled plane
-            cb = ((cb + bias) >> 2) - 128;
-            cr = ((cr + bias) >> 2) - 128;
-        } else {
-            yb[0] = yb[1] = yb[8] = yb[9] = 0;
-        }
-        blk[(g * 6 + 4) * kJpPitch + qy * 8 + qx] = cb;
-        blk[(g * 6 + 5) * kJpPitch + qy * 8 + qx] = cr;
-    }
+    if (mode == 0) enc_fill_420(blk, src, t, tid);
+    else if (mode == 1) enc_fill_422(blk, src, t, tid);
+    else if (mode == 2) enc_fill_444(blk, src, t, tid);
+    else if (enc_gray_rgb(sampling)) enc_fill_gray<true>(blk, src, t, tid);
+    else enc_fill_gray<false>(blk, src, t, tid);
     __syncthreads();
     const bool lane_on = tid < kJpBlocks * 8;                 // eight lanes per block
     const int b = tid >> 3, k = tid & 7;
@@ -223,7 +364,8 @@ __global__ __launch_bounds__(256) void jpeg_enc_transform_kernel(EncArgs a) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) d[i] = col[i * 8];
         jpeg_fdct<false>(d);
-        const int* q = qt + ((b % 6) >= 4 ? 64 : 0) + k;
+        const bool chroma = mode == 0 ? (b % 6) >= 4 : mode == 1 ? (b & 3) >= 2 : mode == 2 ? (b % 3) != 0 : false;
+        const int* q = qt + (chroma ? 64 : 0) + k;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const unsigned div = (unsigned)q[i * 8] << 3;
@@ -232,37 +374,18 @@ __global__ __launch_bounds__(256) void jpeg_enc_transform_kernel(EncArgs a) {
         }
     }
     __syncthreads();
-    // zigzag int16 in MCU order: two coefficients per store, the workgroup's 24 blocks contiguous.  A luma block outside the component
-    // takes the DC term of the block before it in MCU order and no AC terms.
-    const int by = (H + 7) >> 3, bx = (W + 7) >> 3;
-    uint32_t* dst = reinterpret_cast<uint32_t*>(a.ws + r->work_offset) + (size_t)group * (kJpBlocks * 32);
-    for (int e = tid; e < kJpBlocks * 32; e += 256) {
-        const int bl = e >> 5, z = (e & 31) * 2;
-        const int g = bl / 6, kk = bl - g * 6;
-        const int mcu = group * kEncMcus + g;
-        if (mcu >= n_mcu) continue;
-        const int my = mcu / mw, mx = mcu - my * mw;
-        const bool R = mx == mw - 1 && (bx & 1), B = my == mh - 1 && (by & 1);
-        const int s1 = R ? 0 : 1, s2 = B ? s1 : 2, s3 = (R || B) ? s2 : 3;
-        const int from = kk == 1 ? s1 : kk == 2 ? s2 : kk == 3 ? s3 : kk;
-        const int* sb = blk + (g * 6 + from) * kJpPitch;
-        int v0, v1;
-        if (from != kk) {
-            v0 = z == 0 ? sb[0] : 0;
-            v1 = 0;
-        } else {
-            v0 = sb[kEncZigzag[z]];
-            v1 = sb[kEncZigzag[z + 1]];
-        }
-        dst[e] = ((uint32_t)v0 & 0xFFFFu) | ((uint32_t)v1 << 16);
-    }
+    uint32_t* dst = reinterpret_cast<uint32_t*>(a.ws + r->work_offset) + (size_t)t.group * (kJpBlocks * 32);
+    if (mode == 0) enc_store<0>(blk, dst, t, tid);
+    else if (mode == 1) enc_store<1>(blk, dst, t, tid);
+    else if (mode == 2) enc_store<2>(blk, dst, t, tid);
+    else enc_store<3>(blk, dst, t, tid);
 }
 
 // the block in front of block k of MCU `mcu` in its component, in MCU order; -1 at the start of a restart segment
-__device__ __forceinline__ long enc_prev_block(uint32_t mcu, int k, uint32_t interval) {
-    if (k >= 1 && k <= 3) return (long)mcu * 6 + k - 1;
+__device__ __forceinline__ long enc_prev_block(uint32_t mcu, int k, uint32_t interval, int B, int L) {
+    if (k >= 1 && k < L) return (long)mcu * B + k - 1;
     if (mcu % interval == 0) return -1;
-    return (long)(mcu - 1) * 6 + (k == 0 ? 3 : k);
+    return (long)(mcu - 1) * B + (k == 0 ? L - 1 : k);
 }
 
 struct EncCount {
@@ -349,22 +472,23 @@ __global__ __launch_bounds__(256) void jpeg_enc_code_kernel(EncArgs a) {
     __syncthreads();
     const int img = enc_find(a.rec, a.n, 1, blockIdx.x);
     const FearJpegEncImage* r = a.rec + img;
-    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap);
+    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap, r->sampling);
     uint8_t* work = a.ws + r->work_offset;
     const uint32_t* state = reinterpret_cast<const uint32_t*>(work + g.state_at);
     if (WRITE && state[1]) return;                            // the stream alone exceeds the slot: nothing of this image is written
     const uint32_t b = (blockIdx.x - r->start[1]) * kEncGroup + tid;
     if (b >= g.n_blocks) return;
-    const uint32_t mcu = b / 6;
-    const int k = (int)(b - mcu * 6);
+    const int B = g.B, L = enc_luma(enc_mode(r->sampling));
+    const uint32_t mcu = B == 6 ? b / 6 : B == 4 ? b >> 2 : B == 3 ? b / 3 : b;   // (divisions by constants)
+    const int k = (int)(b - mcu * (uint32_t)B);
     const int16_t* coef = reinterpret_cast<const int16_t*>(work);
-    const long prev = enc_prev_block(mcu, k, g.interval);
+    const long prev = enc_prev_block(mcu, k, g.interval, B, L);
     const int pred = prev < 0 ? 0 : coef[prev * 64];
     const uint4* cp = reinterpret_cast<const uint4*>(coef + (size_t)b * 64);
     uint32_t* bits = reinterpret_cast<uint32_t*>(work + g.bits_at);
     if (!WRITE) {
         EncCount sink;
-        enc_block(cp, pred, codes, k >= 4, sink);
+        enc_block(cp, pred, codes, k >= L, sink);
         bits[b] = sink.bits;
     } else {
         const uint32_t seg = mcu / g.interval;
@@ -374,8 +498,8 @@ __global__ __launch_bounds__(256) void jpeg_enc_code_kernel(EncArgs a) {
         sink.words = reinterpret_cast<uint32_t*>(a.ws + r->stream_offset);
         sink.w = (size_t)(pos >> 5);
         sink.fill = (int)(pos & 31);
-        enc_block(cp, pred, codes, k >= 4, sink);
-        const uint32_t seg_last = min((seg + 1) * g.interval, g.n_mcu) * 6 - 1;
+        enc_block(cp, pred, codes, k >= L, sink);
+        const uint32_t seg_last = min((seg + 1) * g.interval, g.n_mcu) * (uint32_t)B - 1;
         if (b == seg_last) {                                  // ones up to the byte
             const int pad = (32 - sink.fill) & 7;
             sink.put((1u << pad) - 1, pad);
@@ -389,11 +513,11 @@ __global__ __launch_bounds__(256) void jpeg_enc_segments_kernel(EncArgs a) {
     __shared__ uint32_t lds4[4];
     const int img = enc_find(a.rec, a.n, 2, blockIdx.x);
     const FearJpegEncImage* r = a.rec + img;
-    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap);
+    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap, r->sampling);
     uint8_t* work = a.ws + r->work_offset;
     uint32_t* bits = reinterpret_cast<uint32_t*>(work + g.bits_at);
     const uint32_t s = blockIdx.x - r->start[2];
-    const uint32_t first = s * g.interval * 6, last = min((s + 1) * g.interval, g.n_mcu) * 6;
+    const uint32_t first = s * g.interval * (uint32_t)g.B, last = min((s + 1) * g.interval, g.n_mcu) * (uint32_t)g.B;
     uint32_t carry = 0;
     for (uint32_t at = first; at < last; at += 256) {
         const uint32_t i = at + threadIdx.x;
@@ -414,7 +538,7 @@ __global__ __launch_bounds__(256) void jpeg_enc_image_scan_kernel(EncArgs a) {
     __shared__ uint32_t lds4[4];
     const int img = blockIdx.x;
     const FearJpegEncImage* r = a.rec + img;
-    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap);
+    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap, r->sampling);
     uint8_t* work = a.ws + r->work_offset;
     uint32_t* state = reinterpret_cast<uint32_t*>(work + g.state_at);
     uint32_t* v = reinterpret_cast<uint32_t*>(work + (LENGTHS ? g.chunk_at : g.seg_at));
@@ -455,7 +579,7 @@ __global__ __launch_bounds__(256) void jpeg_enc_stuff_kernel(EncArgs a) {
     __shared__ uint32_t lds4[4];
     const int img = enc_find(a.rec, a.n, 3, blockIdx.x);
     const FearJpegEncImage* r = a.rec + img;
-    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap);
+    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap, r->sampling);
     uint8_t* work = a.ws + r->work_offset;
     const uint32_t* state = reinterpret_cast<const uint32_t*>(work + g.state_at);
     const uint32_t U = state[0], c = blockIdx.x - r->start[3];
@@ -514,12 +638,21 @@ __global__ __launch_bounds__(256) void jpeg_enc_stuff_kernel(EncArgs a) {
 
 bool enc_record_ok(const FearJpegEncImage& r) {
     return r.width >= 1 && r.width <= FEAR_JPEG_MAX_SIDE && r.height >= 1 && r.height <= FEAR_JPEG_MAX_SIDE && r.quality >= 1 &&
-           r.quality <= 100 && r.restart_interval >= 0 && r.restart_interval <= 65535 && r.header_bytes >= 1 && r.header_bytes <= 4096;
+           r.quality <= 100 && r.restart_interval >= 0 && r.restart_interval <= 65535 && r.header_bytes >= 1 && r.header_bytes <= 4096 &&
+           enc_sampling_ok(r.sampling);
 }
 
-uint32_t enc_stream_bound(int W, int H, int restart_interval) {
-    const EncGeom g = enc_geom(W, H, restart_interval, 0);
-    return g.n_mcu * kEncMcuBytes + g.n_seg;                  // 8192 x 8192: 326 MB
+// the longest unstuffed stream: every block at its longest, and up to a byte of padding per segment
+uint32_t enc_stream_bound(int W, int H, int restart_interval, uint32_t sampling) {
+    const EncGeom g = enc_geom(W, H, restart_interval, 0, sampling);
+    const int L = enc_luma(enc_mode(sampling));
+    const uint64_t mcu_bits = (uint64_t)L * kEncLumaBits + (uint64_t)(g.B - L) * kEncChromaBits;   // 9952, 6636, 4978, 1658
+    return (uint32_t)((g.n_mcu * mcu_bits + 7) / 8 + g.n_seg);          // 8192 x 8192: 326 MB in 4:2:0, 652 MB in 4:4:4
+}
+
+size_t enc_source_bytes(const FearJpegEncImage& r) {
+    const bool one = enc_mode(r.sampling) == FEAR_JPEG_ENC_GRAY && !enc_gray_rgb(r.sampling);
+    return (size_t)r.width * r.height * (one ? 1 : 3);
 }
 
 // The plan of a call: per image what fear_jpeg_encode_plan writes; the workspace's size and the four grids.  False for a call the
@@ -539,8 +672,8 @@ bool enc_plan(const FearJpegEncImage* images, int n, FearJpegEncImage* fill, Enc
     for (int pass = 0; pass < 2; ++pass) {                    // all streams first (one memset), then every image's scratch
         for (int i = 0; i < n; ++i) {
             const FearJpegEncImage& r = images[i];
-            const uint32_t cap = (std::min(enc_stream_bound(r.width, r.height, r.restart_interval), r.out_cap) + 4 + 15) & ~15u;
-            const EncGeom g = enc_geom(r.width, r.height, r.restart_interval, cap);
+            const uint32_t cap = (std::min(enc_stream_bound(r.width, r.height, r.restart_interval, r.sampling), r.out_cap) + 4 + 15) & ~15u;
+            const EncGeom g = enc_geom(r.width, r.height, r.restart_interval, cap, r.sampling);
             if (pass == 0) {
                 if (fill) {
                     fill[i].stream_offset = at;
@@ -554,10 +687,12 @@ bool enc_plan(const FearJpegEncImage* images, int n, FearJpegEncImage* fill, Enc
                     fill[i].start[1] = (uint32_t)p.grid[1];
                     fill[i].start[2] = (uint32_t)p.grid[2];
                     fill[i].start[3] = (uint32_t)p.grid[3];
-                    fill[i].reserved[0] = fill[i].reserved[1] = fill[i].reserved[2] = 0;
+                    fill[i].plan_sampling = r.sampling;               // (sampling itself is the caller's and stays)
+                    fill[i].reserved = 0;
                 }
                 at += g.bytes;
-                p.grid[0] += (g.n_mcu + kEncMcus - 1) / kEncMcus;
+                const uint32_t per = (uint32_t)enc_mcus(enc_mode(r.sampling));
+                p.grid[0] += (g.n_mcu + per - 1) / per;
                 p.grid[1] += (g.n_blocks + kEncGroup - 1) / kEncGroup;
                 p.grid[2] += g.n_seg;
                 p.grid[3] += g.n_chunks;
@@ -576,41 +711,58 @@ bool enc_plan(const FearJpegEncImage* images, int n, FearJpegEncImage* fill, Enc
 
 extern "C" {
 
-int fear_jpeg_encode_header(int width, int height, int quality, int restart_interval, uint8_t* out, size_t out_cap, size_t* out_used) {
+int fear_jpeg_encode_header_mode(int width, int height, int quality, int restart_interval, int sampling, uint8_t* out, size_t out_cap,
+                                 size_t* out_used) {
     if (!out || !out_used) return FEAR_TRAIN_ERR_NULL;
     if (width < 1 || width > FEAR_JPEG_MAX_SIDE || height < 1 || height > FEAR_JPEG_MAX_SIDE || quality < 1 || quality > 100 ||
-        restart_interval < 0 || restart_interval > 65535)
+        restart_interval < 0 || restart_interval > 65535 || sampling < FEAR_JPEG_ENC_420 || sampling > FEAR_JPEG_ENC_GRAY)
         return FEAR_TRAIN_ERR_SHAPE;
+    const bool gray = sampling == FEAR_JPEG_ENC_GRAY;
+    const int tables = gray ? 1 : 2;
     uint8_t h[FEAR_JPEG_ENC_HEADER_MAX];
     size_t at = 0;
     auto put = [&](std::initializer_list<int> v) { for (int b : v) h[at++] = (uint8_t)b; };
     put({0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});
     const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
-    for (int t = 0; t < 2; ++t) {
+    for (int t = 0; t < tables; ++t) {
         put({0xFF, 0xDB, 0, 67, t});
         for (int z = 0; z < 64; ++z) h[at++] = (uint8_t)std::min(std::max(((int)kEncBaseHost[t * 64 + kEncZigzagHost[z]] * scale + 50) / 100, 1), 255);
     }
-    put({0xFF, 0xC0, 0, 17, 8, height >> 8, height & 255, width >> 8, width & 255, 3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1});
-    for (int t = 0; t < 4; ++t) {
+    if (gray) put({0xFF, 0xC0, 0, 11, 8, height >> 8, height & 255, width >> 8, width & 255, 1, 1, 0x11, 0});
+    else
+        put({0xFF, 0xC0, 0, 17, 8, height >> 8, height & 255, width >> 8, width & 255, 3, 1,
+             sampling == FEAR_JPEG_ENC_420 ? 0x22 : sampling == FEAR_JPEG_ENC_422 ? 0x21 : 0x11, 0, 2, 0x11, 1, 3, 0x11, 1});
+    for (int t = 0; t < 2 * tables; ++t) {
         const int total = kEncStd[t].total;
         put({0xFF, 0xC4, (19 + total) >> 8, (19 + total) & 255, (t & 1) << 4 | t >> 1});
         for (int i = 0; i < 16; ++i) h[at++] = kEncStd[t].counts[i];
         for (int i = 0; i < total; ++i) h[at++] = kEncStd[t].values[i];
     }
     if (restart_interval) put({0xFF, 0xDD, 0, 4, restart_interval >> 8, restart_interval & 255});
-    put({0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
+    if (gray) put({0xFF, 0xDA, 0, 8, 1, 1, 0x00, 0, 63, 0});
+    else put({0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
     if (at > out_cap) return FEAR_TRAIN_ERR_WORKSPACE;
     std::memcpy(out, h, at);
     *out_used = at;
     return FEAR_TRAIN_OK;
 }
 
-size_t fear_jpeg_encode_bound(int width, int height, int restart_interval) {
-    if (width < 1 || width > FEAR_JPEG_MAX_SIDE || height < 1 || height > FEAR_JPEG_MAX_SIDE || restart_interval < 0 || restart_interval > 65535)
+int fear_jpeg_encode_header(int width, int height, int quality, int restart_interval, uint8_t* out, size_t out_cap, size_t* out_used) {
+    return fear_jpeg_encode_header_mode(width, height, quality, restart_interval, FEAR_JPEG_ENC_420, out, out_cap, out_used);
+}
+
+size_t fear_jpeg_encode_bound_mode(int width, int height, int restart_interval, int sampling) {
+    if (width < 1 || width > FEAR_JPEG_MAX_SIDE || height < 1 || height > FEAR_JPEG_MAX_SIDE || restart_interval < 0 ||
+        restart_interval > 65535 || sampling < FEAR_JPEG_ENC_420 || sampling > FEAR_JPEG_ENC_GRAY)
         return 0;
-    const EncGeom g = enc_geom(width, height, restart_interval, 0);
+    const EncGeom g = enc_geom(width, height, restart_interval, 0, (uint32_t)sampling);
+    const size_t header = (sampling == FEAR_JPEG_ENC_GRAY ? 328 : 623) + (restart_interval ? 6 : 0);
     // the header with or without DRI; every stream byte stuffed; a marker in front of every segment but the first; EOI
-    return (size_t)(restart_interval ? 629 : 623) + 2 * (size_t)enc_stream_bound(width, height, restart_interval) + 2 * ((size_t)g.n_seg - 1) + 2;
+    return header + 2 * (size_t)enc_stream_bound(width, height, restart_interval, (uint32_t)sampling) + 2 * ((size_t)g.n_seg - 1) + 2;
+}
+
+size_t fear_jpeg_encode_bound(int width, int height, int restart_interval) {
+    return fear_jpeg_encode_bound_mode(width, height, restart_interval, FEAR_JPEG_ENC_420);
 }
 
 int fear_jpeg_encode_plan(FearJpegEncImage* images, int n) {
@@ -639,7 +791,7 @@ int fear_jpeg_encode_u8(const FearJpegEncImage* images, int n, void* workspace, 
     if (!enc_plan(images, n, want.data(), &plan)) return FEAR_TRAIN_ERR_SHAPE;
     if (std::memcmp(want.data(), images, (size_t)n * sizeof(FearJpegEncImage)) != 0) return FEAR_TRAIN_ERR_SHAPE;   // not fear_jpeg_encode_plan's
     for (int i = 0; i < n; ++i) {                             // a source that a slot overlaps (its own or another's)
-        const uintptr_t s0 = reinterpret_cast<uintptr_t>(images[i].src), s1 = s0 + (size_t)images[i].width * images[i].height * 3;
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(images[i].src), s1 = s0 + enc_source_bytes(images[i]);
         for (int j = 0; j < n; ++j) {
             const uintptr_t o0 = reinterpret_cast<uintptr_t>(images[j].out), o1 = o0 + images[j].out_cap;
             if (s0 < o1 && o0 < s1) return FEAR_TRAIN_ERR_SHAPE;

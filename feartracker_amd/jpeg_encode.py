@@ -2,9 +2,10 @@
 
 `jpeg_encode_host` is the contract: numpy and plain Python that produce, byte for byte, the file libjpeg writes with its defaults for a
 three-component frame (`PIL.Image.fromarray(rgb).save(f, "JPEG", quality=q)`): baseline SOF0, 4:2:0, islow FDCT, the standard Huffman
-tables of T.81 annex K, optionally a restart interval of whole MCU rows.  tests/test_jpeg_encode_host.py holds it to Pillow's
-libjpeg-turbo.  `JpegEncoder` is the product: `fear_jpeg_encode_u8` (csrc/fear_jpeg_encode.h) runs every stage on the device and
-`PendingJpegs.result()` downloads the files' bytes alone.  `write_mjpeg_avi` puts equal-sized files into a Motion-JPEG AVI."""
+tables of T.81 annex K, optionally a restart interval of whole MCU rows — and, with `subsampling=`, the 4:2:2, 4:4:4 and
+single-component files Pillow writes with `subsampling=1`, `subsampling=0` and for a mode-L image.  tests/test_jpeg_encode_host.py and
+tests/test_jpeg_encode_modes_host.py hold it to Pillow's libjpeg-turbo.  `JpegEncoder` is the product: `fear_jpeg_encode_u8`
+(csrc/fear_jpeg_encode.h) runs every stage on the device and `PendingJpegs.result()` downloads the files' bytes alone.  `write_mjpeg_avi` puts equal-sized files into a Motion-JPEG AVI."""
 from __future__ import annotations
 
 import ctypes
@@ -30,6 +31,13 @@ STD_HUFFMAN = {
         "c2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")),
 }
 ENC_OVERFLOW = 1                          # include/fear_train.h FEAR_JPEG_ENC_OVERFLOW
+# The layouts a file can have, by name: include/fear_train.h's FEAR_JPEG_ENC_420 .. _GRAY, the MCU's (width, height) in pixels, the
+# (horizontal, vertical) luma sampling factors and Pillow's `subsampling=` (None: a single-component file)
+SUBSAMPLINGS = ("4:2:0", "4:2:2", "4:4:4", "gray")
+_MODE = {"4:2:0": 0, "4:2:2": 1, "4:4:4": 2, "gray": 3}
+_MCU = {"4:2:0": (16, 16), "4:2:2": (16, 8), "4:4:4": (8, 8), "gray": (8, 8)}
+_LUMA = {"4:2:0": (2, 2), "4:2:2": (2, 1), "4:4:4": (1, 1), "gray": (1, 1)}
+_SLOT_FACTOR = {"4:2:0": 3, "4:2:2": 4, "4:4:4": 6, "gray": 3}
 
 
 class JpegOverflow(ValueError):
@@ -55,11 +63,20 @@ def _codes(counts: Sequence[int], values: bytes):
 _STD_CODES = {key: _codes(*tab) for key, tab in STD_HUFFMAN.items()}
 
 
-def _check_rgb(rgb) -> np.ndarray:
+def _check_subsampling(subsampling) -> str:
+    if not isinstance(subsampling, str) or subsampling not in _MODE:
+        raise ValueError(f"subsampling is one of {', '.join(SUBSAMPLINGS)}")
+    return subsampling
+
+
+def _check_rgb(rgb, subsampling: str = "4:2:0") -> np.ndarray:
     v = np.asarray(rgb)
     if v.dtype != np.uint8:
         raise TypeError("a frame is uint8")
-    if v.ndim != 3 or v.shape[2] != 3:
+    if subsampling == "gray":
+        if v.ndim != 2 and (v.ndim != 3 or v.shape[2] != 3):
+            raise ValueError('a frame is (H, W) or (H, W, 3) with "gray"')
+    elif v.ndim != 3 or v.shape[2] != 3:
         raise ValueError("a frame is (H, W, 3)")
     if not (1 <= v.shape[0] <= MAX_SIDE and 1 <= v.shape[1] <= MAX_SIDE):
         raise ValueError(f"a frame's sides lie in 1..{MAX_SIDE}")
@@ -97,18 +114,37 @@ def _quantise(plane: np.ndarray, q: np.ndarray) -> np.ndarray:
     return coef.reshape(h // 8, w // 8, 64)[..., ZIGZAG]
 
 
-def jpeg_forward_coefficients_host(rgb: np.ndarray, quality: int = 75) -> List[np.ndarray]:
+def jpeg_forward_coefficients_host(rgb: np.ndarray, quality: int = 75, subsampling: str = "4:2:0") -> List[np.ndarray]:
     """The quantised coefficients libjpeg codes for an RGB frame of any size: per component (blocks_h, blocks_w, 64) int16 in zigzag
-    order, padded to whole MCUs (`jpeg_coefficients_host`'s shape), the dummy blocks of the luma component included."""
-    v = _check_rgb(rgb)
+    order, padded to whole MCUs (`jpeg_coefficients_host`'s shape), the dummy blocks of the luma component included.  `subsampling`
+    is the file's layout: with "gray" the frame is (H, W), or (H, W, 3) of which the luma is coded, and there is one component."""
+    v = _check_rgb(rgb, _check_subsampling(subsampling))
     q_luma, q_chroma = jpeg_quant_tables(_check_quality(quality))
     H, W = v.shape[:2]
     p = v.astype(np.int64)
+    by, bx = -(-H // 8), -(-W // 8)
+    if p.ndim == 2:
+        return [_quantise(_edge(p, 8 * by, 8 * bx), q_luma).astype(np.int16)]
     r, g, b = p[..., 0], p[..., 1], p[..., 2]
     y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
+    if subsampling == "gray":
+        return [_quantise(_edge(y, 8 * by, 8 * bx), q_luma).astype(np.int16)]
     cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16
     cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16
-    by, bx = -(-H // 8), -(-W // 8)
+    if subsampling == "4:4:4":                                               # replication right and down, no dummy blocks
+        return [_quantise(_edge(c, 8 * by, 8 * bx), q).astype(np.int16) for c, q in ((y, q_luma), (cb, q_chroma), (cr, q_chroma))]
+    if subsampling == "4:2:2":
+        mcus_x = -(-W // 16)
+        luma = np.zeros((by, 2 * mcus_x, 64), dtype=np.int64)
+        luma[:, :bx] = _quantise(_edge(y, 8 * by, 8 * bx), q_luma)
+        if bx & 1:                                                           # Y1 of the last MCU column: the DC term of Y0, no AC terms
+            luma[:, bx, 0] = luma[:, bx - 1, 0]
+        out = [luma.astype(np.int16)]
+        bias = np.tile(np.array([0, 1], dtype=np.int64), 4 * mcus_x)
+        for c in (cb, cr):
+            full = _edge(c, 8 * by, 16 * mcus_x)                             # every row and column replicated at full size
+            out.append(_quantise((full[:, 0::2] + full[:, 1::2] + bias[None, :]) >> 1, q_chroma).astype(np.int16))
+        return out
     mcus_y, mcus_x = -(-H // 16), -(-W // 16)
     luma = np.zeros((2 * mcus_y, 2 * mcus_x, 64), dtype=np.int64)
     luma[:by, :bx] = _quantise(_edge(y, 8 * by, 8 * bx), q_luma)
@@ -129,22 +165,28 @@ def jpeg_forward_coefficients_host(rgb: np.ndarray, quality: int = 75) -> List[n
     return out
 
 
-def jpeg_header_host(width: int, height: int, quality: int = 75, restart_interval: int = 0) -> bytes:
-    """Everything in front of the scan: SOI, JFIF APP0, the two DQT, SOF0, the four standard DHT, DRI if there is an interval, SOS."""
+def jpeg_header_host(width: int, height: int, quality: int = 75, restart_interval: int = 0, subsampling: str = "4:2:0") -> bytes:
+    """Everything in front of the scan: SOI, JFIF APP0, the two DQT, SOF0, the four standard DHT, DRI if there is an interval, SOS.
+    "gray" has one DQT, one component and the two luma DHT."""
+    gray = _check_subsampling(subsampling) == "gray"
     if not (1 <= width <= MAX_SIDE and 1 <= height <= MAX_SIDE):
         raise ValueError(f"a frame's sides lie in 1..{MAX_SIDE}")
     if not 0 <= restart_interval <= 65535:
         raise ValueError("a restart interval fits 16 bits")
     out = bytearray(b"\xFF\xD8\xFF\xE0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
-    for t, q in enumerate(jpeg_quant_tables(_check_quality(quality))):
+    for t, q in enumerate(jpeg_quant_tables(_check_quality(quality))[:1 if gray else 2]):
         out += b"\xFF\xDB\x00\x43" + bytes([t]) + bytes(int(x) for x in q[ZIGZAG])
-    out += b"\xFF\xC0\x00\x11\x08" + struct.pack(">HH", height, width) + b"\x03\x01\x22\x00\x02\x11\x01\x03\x11\x01"
-    for (tc, th) in ((0, 0), (1, 0), (0, 1), (1, 1)):
+    if gray:
+        out += b"\xFF\xC0\x00\x0B\x08" + struct.pack(">HH", height, width) + b"\x01\x01\x11\x00"
+    else:
+        h, v = _LUMA[subsampling]
+        out += b"\xFF\xC0\x00\x11\x08" + struct.pack(">HH", height, width) + bytes([3, 1, h << 4 | v, 0, 2, 0x11, 1, 3, 0x11, 1])
+    for (tc, th) in ((0, 0), (1, 0)) if gray else ((0, 0), (1, 0), (0, 1), (1, 1)):
         counts, values = STD_HUFFMAN[(tc, th)]
         out += b"\xFF\xC4" + struct.pack(">H", 19 + len(values)) + bytes([tc << 4 | th]) + bytes(counts) + values
     if restart_interval:
         out += b"\xFF\xDD\x00\x04" + struct.pack(">H", restart_interval)
-    out += b"\xFF\xDA\x00\x0C\x03\x01\x00\x02\x11\x03\x11\x00\x3F\x00"
+    out += b"\xFF\xDA\x00\x08\x01\x01\x00\x00\x3F\x00" if gray else b"\xFF\xDA\x00\x0C\x03\x01\x00\x02\x11\x03\x11\x00\x3F\x00"
     return bytes(out)
 
 
@@ -168,8 +210,11 @@ class _BitWriter:
             self.put((1 << (8 - self.have)) - 1, 8 - self.have)             # ones up to the byte; stuffed like any other byte
 
 
-def jpeg_entropy_encode_host(coefficients: Sequence[np.ndarray], mcus_x: int, mcus_y: int, restart_interval: int = 0) -> bytes:
-    """T.81 F.1.2 over one interleaved 4:2:0 scan: the stuffed bytes between SOS and EOI, restart markers included."""
+def jpeg_entropy_encode_host(coefficients: Sequence[np.ndarray], mcus_x: int, mcus_y: int, restart_interval: int = 0,
+                             subsampling: str = "4:2:0") -> bytes:
+    """T.81 F.1.2 over one scan: the stuffed bytes between SOS and EOI, restart markers included.  The scan is interleaved, an MCU's
+    luma blocks row by row and then Cb and Cr; "gray" is one component, an MCU one block."""
+    hs, vs = _LUMA[_check_subsampling(subsampling)]
     w = _BitWriter()
     pred = [0, 0, 0]
     for mcu in range(mcus_x * mcus_y):
@@ -178,7 +223,9 @@ def jpeg_entropy_encode_host(coefficients: Sequence[np.ndarray], mcus_x: int, mc
             w.out += bytes([0xFF, 0xD0 + ((mcu // restart_interval - 1) & 7)])
             pred = [0, 0, 0]
         my, mx = divmod(mcu, mcus_x)
-        blocks = [(0, 2 * my, 2 * mx), (0, 2 * my, 2 * mx + 1), (0, 2 * my + 1, 2 * mx), (0, 2 * my + 1, 2 * mx + 1), (1, my, mx), (2, my, mx)]
+        blocks = [(0, vs * my + j, hs * mx + i) for j in range(vs) for i in range(hs)]
+        if subsampling != "gray":
+            blocks += [(1, my, mx), (2, my, mx)]
         for c, j, i in blocks:
             blk = [int(x) for x in coefficients[c][j, i]]
             dc, ac = _STD_CODES[(0, 1 if c else 0)], _STD_CODES[(1, 1 if c else 0)]
@@ -206,15 +253,19 @@ def jpeg_entropy_encode_host(coefficients: Sequence[np.ndarray], mcus_x: int, mc
     return bytes(w.out)
 
 
-def jpeg_encode_host(rgb: np.ndarray, quality: int = 75, restart_rows: int = 0) -> bytes:
+def jpeg_encode_host(rgb: np.ndarray, quality: int = 75, restart_rows: int = 0, subsampling: str = "4:2:0") -> bytes:
     """A uint8 (H, W, 3) RGB frame -> the baseline JPEG file libjpeg writes for it at `quality`, with a restart marker every
-    `restart_rows` MCU rows if that is not 0.  Slow; the statement the device is held to."""
-    v = _check_rgb(rgb)
+    `restart_rows` MCU rows if that is not 0, in the layout `subsampling` names: Pillow's `subsampling=` 2, 1 and 0, or with "gray"
+    the single-component file of an (H, W) frame, or of an (H, W, 3) frame's luma (Pillow's `convert("L")`).  Slow; the statement the
+    device is held to."""
+    v = _check_rgb(rgb, _check_subsampling(subsampling))
     H, W = v.shape[:2]
-    mcus_x, mcus_y = -(-W // 16), -(-H // 16)
+    mcu_w, mcu_h = _MCU[subsampling]
+    mcus_x, mcus_y = -(-W // mcu_w), -(-H // mcu_h)
     interval = _restart_interval(restart_rows, mcus_x)
-    coef = jpeg_forward_coefficients_host(v, quality)
-    return jpeg_header_host(W, H, quality, interval) + jpeg_entropy_encode_host(coef, mcus_x, mcus_y, interval) + b"\xFF\xD9"
+    coef = jpeg_forward_coefficients_host(v, quality, subsampling)
+    return (jpeg_header_host(W, H, quality, interval, subsampling) + jpeg_entropy_encode_host(coef, mcus_x, mcus_y, interval, subsampling)
+            + b"\xFF\xD9")
 
 
 # ------------------------------------------------------------------------------------------------------------------------ the product
@@ -252,21 +303,24 @@ class PendingJpegs:
 
 class JpegEncoder:
     """uint8 (H, W, 3) RGB device tensors -> baseline JPEG files, byte for byte what Pillow's `save(f, "JPEG", quality=q)` writes
-    (`restart_rows=r`: what `save(..., restart_marker_rows=r)` writes).
+    (`restart_rows=r`: what `save(..., restart_marker_rows=r)` writes).  `subsampling` names the file's layout: "4:2:0" (the default),
+    "4:2:2" and "4:4:4" are Pillow's `subsampling=` 2, 1 and 0; "gray" writes a single-component file from an (H, W) tensor, or from
+    the luma of an (H, W, 3) one (Pillow's `convert("L")`).  `encode` takes a name for the call or one per frame.
 
     `encode` builds the headers and the records on the host, uploads them from pinned memory in one non-blocking transfer and runs
     `fear_jpeg_encode_u8` once for the whole call: frames of different sizes and qualities in a fixed number of launches.  It never
-    waits for the GPU.  Every file gets a slot of `slot_bytes` in one device buffer: by default 1024 + 3 (16 mcus_x) (16 mcus_y) bytes,
-    a little above the raw pixels; `"bound"` takes `fear_jpeg_encode_bound`, the longest file the frame's size can give, and an int is
+    waits for the GPU.  Every file gets a slot of `slot_bytes` in one device buffer: by default 1024 + c times the frame's pixels with
+    its sides padded to whole MCUs, where c is 3 for "4:2:0" and "gray", 4 for "4:2:2" and 6 for "4:4:4": a little above the raw pixels; `"bound"` takes `fear_jpeg_encode_bound`, the longest file the frame's size can give, and an int is
     the slot of every frame.  A file that exceeds its slot is not written: its length is 0 and `PendingJpegs.result()` raises
     `JpegOverflow`; the other files of the call are unaffected.  `guard_bytes` are left unused behind every slot."""
 
     def __init__(self, device: int = 0, quality: int = 75, restart_rows: int = 0, slot_bytes: Union[None, int, str] = None,
-                 guard_bytes: int = 0):
+                 guard_bytes: int = 0, subsampling: str = "4:2:0"):
         import torch
         from .train_abi import load_train_library
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.quality = _check_quality(quality)
+        self.subsampling = _check_subsampling(subsampling)
         _restart_interval(restart_rows, 1)
         self.restart_rows = int(restart_rows)
         if not (slot_bytes is None or slot_bytes == "bound" or (isinstance(slot_bytes, (int, np.integer)) and not isinstance(slot_bytes, bool))):
@@ -278,19 +332,33 @@ class JpegEncoder:
         self.slot_bytes, self.guard_bytes = slot_bytes, int(guard_bytes)
         self._lib = load_train_library()
 
-    def _frames(self, frames) -> List:
+    def _frames(self, frames, subsampling) -> Tuple[List, List[str]]:
         import torch
+        if subsampling is None:
+            subsampling = self.subsampling
+        if not isinstance(subsampling, (str, list, tuple)):
+            raise ValueError(f"subsampling is one of {', '.join(SUBSAMPLINGS)}, or a sequence of them with one per frame")
+        each = None if isinstance(subsampling, str) else [_check_subsampling(m) for m in subsampling]
+        if each is None:
+            _check_subsampling(subsampling)
         if isinstance(frames, torch.Tensor):
-            if frames.ndim != 4:
-                raise ValueError("a batch of frames is (n, H, W, 3)")
+            all_gray = subsampling == "gray" if each is None else all(m == "gray" for m in each)
+            if frames.ndim != 4 and not (frames.ndim == 3 and all_gray):
+                raise ValueError('a batch of frames is (n, H, W, 3), or (n, H, W) with "gray"')
             frames = list(frames.unbind(0))
         out = list(frames)
-        for f in out:
+        modes = [subsampling] * len(out) if each is None else each
+        if len(modes) != len(out):
+            raise ValueError("one subsampling per frame")
+        for f, mode in zip(out, modes):
             if not isinstance(f, torch.Tensor):
                 raise TypeError("a frame is a torch tensor on the device")
             if f.dtype != torch.uint8:
                 raise TypeError("a frame is uint8")
-            if f.ndim != 3 or f.shape[2] != 3:
+            if mode == "gray":
+                if f.ndim != 2 and (f.ndim != 3 or f.shape[2] != 3):
+                    raise ValueError('a frame is (H, W) or (H, W, 3) with "gray"')
+            elif f.ndim != 3 or f.shape[2] != 3:
                 raise ValueError("a frame is (H, W, 3)")
             if not f.is_cuda or f.device != self.device:
                 raise ValueError(f"a frame lives on {self.device}")
@@ -300,12 +368,13 @@ class JpegEncoder:
                 raise ValueError(f"a frame's sides lie in 1..{MAX_SIDE}")
         if len(out) > 65535:
             raise ValueError("at most 65535 frames per call")
-        return out
+        return out, modes
 
-    def encode(self, frames, quality: Union[None, int, Sequence[int]] = None) -> PendingJpegs:
+    def encode(self, frames, quality: Union[None, int, Sequence[int]] = None,
+               subsampling: Union[None, str, Sequence[str]] = None) -> PendingJpegs:
         import torch
-        from .train_abi import (FEAR_JPEG_ENC_HEADER_MAX, FEAR_JPEG_ENC_TABLE_BYTES, FearJpegEncImage, launch)
-        frames = self._frames(frames)
+        from .train_abi import (FEAR_JPEG_ENC_GRAY_RGB, FEAR_JPEG_ENC_HEADER_MAX, FEAR_JPEG_ENC_TABLE_BYTES, FearJpegEncImage, launch)
+        frames, modes = self._frames(frames, subsampling)
         n = len(frames)
         if quality is None:
             qualities = [self.quality] * n
@@ -321,16 +390,17 @@ class JpegEncoder:
         scratch, used = (ctypes.c_uint8 * FEAR_JPEG_ENC_HEADER_MAX)(), ctypes.c_size_t(0)
         for k, f in enumerate(frames):
             H, W = int(f.shape[0]), int(f.shape[1])
-            mcus_x, mcus_y = -(-W // 16), -(-H // 16)
+            mode, (mcu_w, mcu_h) = _MODE[modes[k]], _MCU[modes[k]]
+            mcus_x, mcus_y = -(-W // mcu_w), -(-H // mcu_h)
             interval = _restart_interval(self.restart_rows, mcus_x)
-            launch(lib, "fear_jpeg_encode_header", W, H, qualities[k], interval, scratch, len(scratch), ctypes.byref(used))
+            launch(lib, "fear_jpeg_encode_header_mode", W, H, qualities[k], interval, mode, scratch, len(scratch), ctypes.byref(used))
             headers.append(bytes(scratch[:used.value]))
             header_at.append(at)
             at += -(-used.value // 16) * 16
             if self.slot_bytes is None:
-                slot = 1024 + 3 * (16 * mcus_x) * (16 * mcus_y)
+                slot = 1024 + _SLOT_FACTOR[modes[k]] * (mcu_w * mcus_x) * (mcu_h * mcus_y)
             elif self.slot_bytes == "bound":
-                slot = int(lib.fear_jpeg_encode_bound(W, H, interval))
+                slot = int(lib.fear_jpeg_encode_bound_mode(W, H, interval, mode))
             else:
                 slot = int(self.slot_bytes)
             if slot >= 1 << 32:
@@ -338,6 +408,7 @@ class JpegEncoder:
             rec = records[k]
             rec.width, rec.height, rec.quality, rec.restart_interval = W, H, qualities[k], interval
             rec.out_cap, rec.header_bytes = slot, used.value
+            rec.sampling = mode | (FEAR_JPEG_ENC_GRAY_RGB if modes[k] == "gray" and f.ndim == 3 else 0)
             slot_at.append(out_at)
             out_at += -(-(slot + self.guard_bytes) // 16) * 16
         with torch.cuda.device(self.device):

@@ -125,6 +125,8 @@ TRAIN_SYMBOLS = {
     # JPEG files written on the device (jpeg_encode.JpegEncoder; FearJpegEncImage below): the host's header, bound and plan, the encode
     "fear_jpeg_encode_header": ([_i, _i, _i, _i, _P, _sz, _P], _i),
     "fear_jpeg_encode_bound": ([_i, _i, _i], _sz),
+    "fear_jpeg_encode_header_mode": ([_i, _i, _i, _i, _i, _P, _sz, _P], _i),
+    "fear_jpeg_encode_bound_mode": ([_i, _i, _i, _i], _sz),
     "fear_jpeg_encode_plan": ([_P, _i], _i),
     "fear_jpeg_encode_workspace_bytes": ([_P, _i], _sz),
     "fear_jpeg_encode_u8": ([_P, _i, _P, _sz, _P, _P, _P], _i),
@@ -336,14 +338,18 @@ assert ctypes.sizeof(FearJpegImage) == 448 and FearJpegImage.qt.offset == 64
 
 class FearJpegEncImage(ctypes.Structure):
     """include/fear_train.h: one image of a fear_jpeg_encode_u8 call (device pointers as integers; fear_jpeg_encode_plan fills
-    stream_offset, work_offset, stream_cap and start)."""
+    stream_offset, work_offset, stream_cap, start and plan_sampling and keeps sampling)."""
     _fields_ = [("src", ctypes.c_uint64), ("out", ctypes.c_uint64), ("header", ctypes.c_uint64), ("stream_offset", ctypes.c_uint64),
                 ("work_offset", ctypes.c_uint64), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("quality", ctypes.c_int32),
                 ("restart_interval", ctypes.c_int32), ("out_cap", ctypes.c_uint32), ("header_bytes", ctypes.c_uint32),
-                ("stream_cap", ctypes.c_uint32), ("start", ctypes.c_uint32 * 4), ("reserved", ctypes.c_uint32 * 3)]
+                ("stream_cap", ctypes.c_uint32), ("start", ctypes.c_uint32 * 4), ("sampling", ctypes.c_uint32), ("plan_sampling", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
 
 
 assert ctypes.sizeof(FearJpegEncImage) == 96 and FearJpegEncImage.width.offset == 40 and FearJpegEncImage.stream_cap.offset == 64
+assert FearJpegEncImage.sampling.offset == 84
+FEAR_JPEG_ENC_420, FEAR_JPEG_ENC_422, FEAR_JPEG_ENC_444, FEAR_JPEG_ENC_GRAY = 0, 1, 2, 3     # a record's sampling
+FEAR_JPEG_ENC_GRAY_RGB = 0x100        # or-ed into FEAR_JPEG_ENC_GRAY: the source is (height, width, 3) RGB
 FEAR_JPEG_ENC_OVERFLOW = 1
 FEAR_JPEG_ENC_HEADER_MAX = 640
 FEAR_JPEG_ENC_GROUP_BLOCKS = 256      # blocks per workgroup of fear_jpeg_encode_u8's sizes and write passes

@@ -1151,16 +1151,36 @@ int fear_miner_update(const float* templ, const float* search, const float* cls,
  * 0..65535, header_bytes outside 1..4096, a source that overlaps its or another image's slot, plan fields that are not
  * fear_jpeg_encode_plan's.  n == 0 returns FEAR_TRAIN_OK without a launch.  A null images, length_dev, status_dev, src, out or header:
  * FEAR_TRAIN_ERR_NULL.  A null workspace or one below fear_jpeg_encode_workspace_bytes: FEAR_TRAIN_ERR_WORKSPACE.
- * fear_jpeg_encode_header, _plan, _workspace_bytes and _bound are host code.                                                          */
+ * fear_jpeg_encode_header, _plan, _workspace_bytes and _bound are host code.
+ *
+ * The other layouts.  A record's `sampling` (0 in a zeroed record: 4:2:0 from RGB, all of the above) selects 4:2:2, 4:4:4 or one gray
+ * component; fear_jpeg_encode_plan keeps it and refuses any other value as FEAR_TRAIN_ERR_SHAPE.  Per layout: the MCU in pixels, its
+ * blocks in scan order, MCUs per transform workgroup, the longest MCU in bits.
+ *   4:2:0  16 x 16  Y00 Y01 Y10 Y11 Cb Cr  4   9952      4:2:2  16 x 8  Y0 Y1 Cb Cr  6   6636
+ *   4:4:4   8 x 8   Y Cb Cr                8   4978      gray    8 x 8  Y            24  1658
+ * 4:2:2 is h2v1: chroma is (a + b + bias) >> 1 with bias 0, 1, 0, 1 along a row, columns replicated at full size, rows below the frame
+ * repeat the last row; Y1 of the last MCU column is a dummy block (the DC term of Y0, no AC terms) when ceil(width / 8) is odd.  4:4:4
+ * and gray replicate right and down and have no dummy blocks.  Gray is one non-interleaved component with table 0 only; its header is
+ * 328 bytes (334 with DRI), the colour layouts' 623 (629).  A restart interval counts the layout's MCUs.  A gray source is width x height
+ * bytes unless FEAR_JPEG_ENC_GRAY_RGB is set.  fear_jpeg_encode_header and fear_jpeg_encode_bound mean 4:2:0; the _mode forms take the
+ * sampling (for the header without FEAR_JPEG_ENC_GRAY_RGB, which does not change the file's layout) and are FEAR_TRAIN_ERR_SHAPE or 0
+ * for an unknown one.                                                                                                                */
 #define FEAR_JPEG_ENC_OVERFLOW 1
 #define FEAR_JPEG_ENC_HEADER_MAX 640
 #define FEAR_JPEG_ENC_GROUP_BLOCKS 256
 #define FEAR_JPEG_ENC_CHUNK_BYTES 4096
 #define FEAR_JPEG_ENC_TABLE_BYTES(n) (((size_t)(n) * 96 + 15) & ~(size_t)15)
+/* A record's sampling: the file's layout.  FEAR_JPEG_ENC_GRAY writes one component from a (height, width) uint8 source, or, with
+ * FEAR_JPEG_ENC_GRAY_RGB or-ed in, from the luma of a (height, width, 3) RGB source. */
+#define FEAR_JPEG_ENC_420 0
+#define FEAR_JPEG_ENC_422 1
+#define FEAR_JPEG_ENC_444 2
+#define FEAR_JPEG_ENC_GRAY 3
+#define FEAR_JPEG_ENC_GRAY_RGB 0x100
 
 /* One image of a fear_jpeg_encode_u8 call.  96 bytes. */
 typedef struct FearJpegEncImage {
-    const uint8_t* src;              /* device: (height, width, 3) uint8 RGB, contiguous                                    */
+    const uint8_t* src;              /* device: (height, width, 3) uint8 RGB, contiguous; (height, width) for plain gray    */
     uint8_t* out;                    /* device: the file's slot                                                            */
     const uint8_t* header;           /* device: header_bytes bytes, SOI to the end of SOS                                  */
     uint64_t stream_offset;          /* plan: the unstuffed stream, bytes from the workspace's start; offset 24             */
@@ -1169,7 +1189,9 @@ typedef struct FearJpegEncImage {
     uint32_t out_cap, header_bytes;  /* offset 56                                                                          */
     uint32_t stream_cap;             /* plan: the stream's capacity in bytes; offset 64                                    */
     uint32_t start[4];               /* plan: the image's first workgroup of transform, sizes / write, segments, count / assemble */
-    uint32_t reserved[3];
+    uint32_t sampling;               /* FEAR_JPEG_ENC_420 .. _GRAY, | FEAR_JPEG_ENC_GRAY_RGB; 0: 4:2:0 from RGB; offset 84      */
+    uint32_t plan_sampling;          /* plan: the sampling the plan was made for, so that a later change of it is refused     */
+    uint32_t reserved;
 } FearJpegEncImage;
 #ifdef __cplusplus
 static_assert(sizeof(FearJpegEncImage) == 96, "FearJpegEncImage is 96 bytes");
@@ -1179,6 +1201,9 @@ _Static_assert(sizeof(FearJpegEncImage) == 96, "FearJpegEncImage is 96 bytes");
 
 int fear_jpeg_encode_header(int width, int height, int quality, int restart_interval, uint8_t* out, size_t out_cap, size_t* out_used);
 size_t fear_jpeg_encode_bound(int width, int height, int restart_interval);
+int fear_jpeg_encode_header_mode(int width, int height, int quality, int restart_interval, int sampling, uint8_t* out, size_t out_cap,
+                                 size_t* out_used);
+size_t fear_jpeg_encode_bound_mode(int width, int height, int restart_interval, int sampling);
 int fear_jpeg_encode_plan(FearJpegEncImage* images, int n);
 size_t fear_jpeg_encode_workspace_bytes(const FearJpegEncImage* images, int n);
 int fear_jpeg_encode_u8(const FearJpegEncImage* images, int n, void* workspace, size_t workspace_bytes, int32_t* length_dev,

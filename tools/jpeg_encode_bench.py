@@ -1,7 +1,11 @@
 """Measures the JPEG encoder (jpeg_encode.JpegEncoder, DESIGN.md section 14 "Writing JPEG files") on the 256 synthetic 1280 x 720 frames of
 tools/jpeg_decode_bench.py at quality 90 and writes profiles/jpeg_encode_bench.json.  Needs the GPU; Pillow only for the baseline.
 
-    python tools/jpeg_encode_bench.py [--frames 256] [--repeats 5]
+    python tools/jpeg_encode_bench.py [--frames 256] [--repeats 5] [--subsampling MODE]
+
+Without --subsampling the run and its output file are those of the first encoder (4:2:0).  With it the same frames are written in that
+layout ("gray": the luma of the RGB frames, Pillow's convert("L")) and the result goes under the layout's name into
+profiles/jpeg_encode_modes_bench.json, beside what other runs have put there.
 
   encode_fps              JpegEncoder.encode + PendingJpegs.result() end to end: frames on the device -> files' bytes on the host
   kernels_ms              fear_jpeg_encode_u8 alone between HIP events (the memset and the eight launches of the 256 frames); the split
@@ -37,8 +41,12 @@ def main():
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--kernels-only", action="store_true", help="three encode calls and nothing else: the run to put under a kernel trace")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_encode_bench.json"))
+    ap.add_argument("--subsampling", default=None, choices=("4:2:0", "4:2:2", "4:4:4", "gray"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    mode = args.subsampling
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "jpeg_encode_bench.json" if mode is None else "jpeg_encode_modes_bench.json")
     import torch
     from feartracker_amd import JpegEncoder
     from feartracker_amd import train_abi as abi
@@ -46,7 +54,7 @@ def main():
     host = [img for img, _ in zip(db.images(), range(args.frames))]
     n = len(host)
     frames = [torch.from_numpy(f).cuda() for f in host]
-    enc = JpegEncoder(0, quality=QUALITY)
+    enc = JpegEncoder(0, quality=QUALITY) if mode is None else JpegEncoder(0, quality=QUALITY, subsampling=mode)
     if args.kernels_only:
         for _ in range(3):
             enc.encode(frames).result()
@@ -81,19 +89,31 @@ def main():
     else:
         def save(f):
             buf = io.BytesIO()
-            Image.fromarray(f).save(buf, "JPEG", quality=QUALITY)
+            if mode is None:
+                Image.fromarray(f).save(buf, "JPEG", quality=QUALITY)
+            elif mode == "gray":
+                Image.fromarray(f).convert("L").save(buf, "JPEG", quality=QUALITY)
+            else:
+                Image.fromarray(f).save(buf, "JPEG", quality=QUALITY, subsampling={"4:2:0": 2, "4:2:2": 1, "4:4:4": 0}[mode])
             return buf.getvalue()
 
         with ThreadPoolExecutor(max_workers=16) as pool:
             def baseline():
                 stack = torch.stack(frames).cpu().numpy()                  # the raw pixels come down first
                 return list(pool.map(save, stack))
-            assert baseline()[0] == files[0], "the encoder's file differs from Pillow's"
+            assert baseline() == files, "the encoder's files differ from Pillow's"
             res["pillow_fps"] = db.spread([n / t for t in db.run_seconds(baseline, args.repeats)], digits=1)
         res["files_equal_pillow"] = True
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    whole = res
+    if mode is not None:                                                   # one entry per layout in a file other runs add to
+        whole = {}
+        if os.path.exists(args.out):
+            with open(args.out) as fh:
+                whole = json.load(fh)
+        whole.setdefault("modes", {})[mode] = res
     with open(args.out, "w") as fh:
-        json.dump(res, fh, indent=1)
+        json.dump(whole, fh, indent=1)
     print(json.dumps(res))
 
 

@@ -2,6 +2,7 @@
 
     python tools/track_demo.py FRAMES_DIR X Y W H --out OUT_DIR            # numbered .jpg files
     python tools/track_demo.py FRAMES_DIR X Y W H --out clip.avi --fps 25  # one .avi
+    python tools/track_demo.py FRAMES_DIR X Y W H --out OUT_DIR --subsampling 4:4:4
 
 FRAMES_DIR holds baseline JPEG files, read in sorted order; X Y W H is the target's box in the first frame.  Every stage runs on the GPU:
 `JpegDecoder` -> `FEARMultiTracker.submit` -> `FEARMultiTracker.draw` -> `JpegEncoder`; only the files' bytes come back to the host.  The
@@ -24,6 +25,8 @@ def main():
     ap.add_argument("--out", required=True, help="a directory for numbered .jpg files, or a path ending in .avi")
     ap.add_argument("--fps", type=float, default=25.0)
     ap.add_argument("--quality", type=int, default=90)
+    ap.add_argument("--subsampling", default="4:2:0", choices=("4:2:0", "4:2:2", "4:4:4", "gray"),
+                    help="the files' layout: 4:4:4 keeps the outline's colour, 4:2:0 (the default) halves its chroma both ways")
     ap.add_argument("--thickness", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32, help="frames decoded and encoded per call")
     ap.add_argument("--weights", default=None)
@@ -35,7 +38,7 @@ def main():
         raise SystemExit("the directory needs at least two .jpg frames")
     net = FEARNetHIP(args.weights or DEFAULT_WEIGHTS, device=0, max_batch=8)
     tracker = FEARMultiTracker(net, cuda_id=0, **DEFAULT_TRACKING_CONFIG)
-    decoder, encoder = JpegDecoder(device=0), JpegEncoder(0, quality=args.quality)
+    decoder, encoder = JpegDecoder(device=0), JpegEncoder(0, quality=args.quality, subsampling=args.subsampling)
     files, started = [], False
     for at in range(0, len(paths), args.batch):
         frames = decoder.decode(paths[at:at + args.batch])
