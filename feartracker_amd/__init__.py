@@ -15,7 +15,8 @@ from .jpeg_frames import JpegDecoder, MalformedJPEG, UnsupportedJPEG, jpeg_decod
 from .jpeg_huffman import (jpeg_entropy_indexed_host, jpeg_entropy_parallel_host, jpeg_entropy_rows_device_host, jpeg_rows_device_host,
                            jpeg_scan_index_host, jpeg_scan_prepare_host, scan_row_sub)
 from .jpeg_progressive import jpeg_to_baseline_host
-from .jpeg_encode import SUBSAMPLINGS, JpegEncoder, JpegOverflow, PendingJpegs, jpeg_encode_host, write_mjpeg_avi
+from .jpeg_encode import (SUBSAMPLINGS, JpegEncoder, JpegHuffmanDepth, JpegOverflow, PendingJpegs, jpeg_encode_host,
+                          jpeg_optimal_table_host, jpeg_symbol_histograms_host, write_mjpeg_avi)
 from .jpeg_store import JpegStore, StoreFrames, StoreFull, plan_decode, plan_decode_rows
 from .visuals import BestWorstMiner, draw_boxes, draw_boxes_host, miner_host
 
@@ -30,4 +31,5 @@ __all__ = [
     "StoreFrames", "search_rows_host",
     "BestWorstMiner", "draw_boxes", "draw_boxes_host", "miner_host",
     "JpegEncoder", "JpegOverflow", "PendingJpegs", "jpeg_encode_host", "write_mjpeg_avi", "SUBSAMPLINGS",
+    "JpegHuffmanDepth", "jpeg_symbol_histograms_host", "jpeg_optimal_table_host",
 ]

@@ -6,6 +6,8 @@
 //
 // Why each launch boundary is there: every one is a dependency across workgroups.
 //   transform | sizes      a block's DC difference reads the block before it, which another workgroup may have transformed
+//   transform | stats      (calls with an optimised record only) the same; stats | tables: a table is built from the counts of all of
+//                          the image's workgroups; tables | sizes: a block's bit count needs the image's own code lengths
 //   sizes | segments       a block's bit offset is the sum of all bit counts before it in its restart segment
 //   segments | offsets     a segment's byte offset is the sum of all segment lengths before it in its image
 //   offsets | write        a block's place in the stream is its segment's offset plus its own
@@ -18,6 +20,8 @@
 #include <algorithm>
 #include <initializer_list>
 
+#include "fear_jpeg_huff_build.h"
+
 namespace {
 
 constexpr int kEncMcus = kJpMcus;                              // MCUs per workgroup of the transform: fear_train_jpeg.h's LDS layout
@@ -25,6 +29,17 @@ constexpr int kEncGroup = FEAR_JPEG_ENC_GROUP_BLOCKS;          // blocks per wor
 constexpr int kEncChunk = FEAR_JPEG_ENC_CHUNK_BYTES;           // stream bytes per workgroup of count and assemble
 static_assert(kEncGroup == 256 && kEncChunk == 4096, "one lane per block; one lane per 16 bytes of a chunk");
 constexpr uint32_t kEncLumaBits = 9 + 11 + 63 * 26, kEncChromaBits = 11 + 11 + 63 * 26;   // the longest block; 4:2:0's MCU: 1244 bytes
+constexpr uint32_t kEncOptBits = 16 + 11 + 63 * 26;           // with per-file tables any code may be 16 bits long: 1665 for every block
+
+// An optimised record's scratch.  Its symbol counts stand in FRONT of its stream, so that the call's one memset zeroes them:
+// uint32 [4][256] at stream_offset - kEncCountBytes, tables in kEncStd's order.  Behind its plain scratch (EncGeom::bytes): uint32
+// codes [4][256] in kEncCodes' form | per table its DHT segment, kEncDhtPitch bytes apart | uint32 dht_bytes [4] (0 for a table the
+// layout lacks) | uint32 deep [4] (1: the table's tree is deeper than 32).  The file's header is the record's header with the DHT
+// segments put in at enc_dht_at: its length is a device value.
+constexpr uint32_t kEncCountBytes = 4 * 256 * 4, kEncDhtPitch = 288, kEncDhtMax = 5 + 16 + 256;
+constexpr size_t kEncOptDhtAt = 4 * 256 * 4, kEncOptInfoAt = kEncOptDhtAt + 4 * kEncDhtPitch, kEncOptBytes = kEncOptInfoAt + 32;
+static_assert(kEncDhtMax <= kEncDhtPitch && kEncOptBytes % 16 == 0 && kEncCountBytes % 16 == 0, "the scratch keeps 16-byte alignment");
+__host__ __device__ inline bool enc_optimized(uint32_t flags) { return (flags & FEAR_JPEG_ENC_OPTIMIZE) != 0; }
 
 // A record's sampling: FEAR_JPEG_ENC_420 .. _GRAY in the low byte.  Per layout the MCU's side shifts, its blocks B, of which the first
 // L are luma, and the MCUs per workgroup of the transform: B x MCUS is the 24 blocks of the LDS tile in every layout.
@@ -37,6 +52,8 @@ static_assert(kEncMcus * 6 == kJpBlocks && kJpBlocks == 24, "the tile is 24 bloc
 inline bool enc_sampling_ok(uint32_t sampling) {
     return sampling <= FEAR_JPEG_ENC_GRAY || sampling == (FEAR_JPEG_ENC_GRAY | FEAR_JPEG_ENC_GRAY_RGB);
 }
+// where the DHT segments stand in a header: behind SOI, APP0, the DQT segments and SOF0
+__host__ __device__ inline uint32_t enc_dht_at(int mode) { return mode == FEAR_JPEG_ENC_GRAY ? 20 + 69 + 13 : 20 + 2 * 69 + 19; }
 
 // zigzag position -> natural index
 constexpr uint8_t kEncZigzagHost[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -391,6 +408,13 @@ __device__ __forceinline__ long enc_prev_block(uint32_t mcu, int k, uint32_t int
 struct EncCount {
     uint32_t bits = 0;
     __device__ __forceinline__ void put(uint32_t, int len) { bits += (uint32_t)len; }
+    __device__ __forceinline__ void symbol(const uint32_t* table, int s) { bits += table[s] >> 16; }
+};
+
+// stats: a symbol counts in the workgroup's histogram; the extra bits do not matter
+struct EncStat {
+    __device__ __forceinline__ void put(uint32_t, int) {}
+    __device__ __forceinline__ void symbol(uint32_t* table, int s) { atomicAdd(table + s, 1u); }
 };
 
 // MSB first into 32-bit words of the little-endian byte stream.  A word this block covers whole is stored; the first word (other blocks'
@@ -417,16 +441,21 @@ struct EncWrite {
             acc &= (1ull << fill) - 1;
         }
     }
+    __device__ __forceinline__ void symbol(const uint32_t* table, int s) {
+        const uint32_t c = table[s];
+        put(c & 0xFFFFu, (int)(c >> 16));
+    }
     __device__ __forceinline__ void finish() {
         if (fill > 0) word((uint32_t)(acc << (32 - fill)), true);
     }
 };
 
-// T.81 F.1.2 over one block's 64 zigzag coefficients: `codes` is kEncCodes in LDS, `t` 0 for luma and 1 for chroma
+// T.81 F.1.2 over one block's 64 zigzag coefficients: `codes` is the code table (kEncCodes' form) in LDS, or for EncStat the
+// histogram of the same shape; `t` 0 for luma and 1 for chroma.  The sink takes each Huffman symbol with its table, and the extra bits.
 template <class Sink>
-__device__ __forceinline__ void enc_block(const uint4* cp, int pred, const uint32_t* codes, int t, Sink& sink) {
-    const uint32_t* dc = codes + t * 512;
-    const uint32_t* ac = dc + 256;
+__device__ __forceinline__ void enc_block(const uint4* cp, int pred, uint32_t* codes, int t, Sink& sink) {
+    uint32_t* dc = codes + t * 512;
+    uint32_t* ac = dc + 256;
     int run = 0;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -438,28 +467,20 @@ __device__ __forceinline__ void enc_block(const uint4* cp, int pred, const uint3
             if (j == 0 && i == 0) {
                 v -= pred;
                 const int s = 32 - __clz(abs(v));
-                const uint32_t c = dc[s];
-                sink.put(c & 0xFFFFu, (int)(c >> 16));
+                sink.symbol(dc, s);
                 sink.put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1), s);
             } else if (v == 0) {
                 ++run;
             } else {
-                for (; run > 15; run -= 16) {
-                    const uint32_t c = ac[0xF0];
-                    sink.put(c & 0xFFFFu, (int)(c >> 16));
-                }
+                for (; run > 15; run -= 16) sink.symbol(ac, 0xF0);
                 const int s = 32 - __clz(abs(v));
-                const uint32_t c = ac[(run << 4 | s) & 255];
-                sink.put(c & 0xFFFFu, (int)(c >> 16));
+                sink.symbol(ac, (run << 4 | s) & 255);
                 sink.put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1), s);
                 run = 0;
             }
         }
     }
-    if (run) {
-        const uint32_t c = ac[0];
-        sink.put(c & 0xFFFFu, (int)(c >> 16));
-    }
+    if (run) sink.symbol(ac, 0);
 }
 
 // sizes (WRITE false) and write (WRITE true): one lane per block
@@ -467,13 +488,15 @@ template <bool WRITE>
 __global__ __launch_bounds__(256) void jpeg_enc_code_kernel(EncArgs a) {
     __shared__ uint32_t codes[4 * 256];
     const int tid = threadIdx.x;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) codes[tid + 256 * i] = kEncCodes.v[tid + 256 * i];
-    __syncthreads();
     const int img = enc_find(a.rec, a.n, 1, blockIdx.x);
     const FearJpegEncImage* r = a.rec + img;
     const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap, r->sampling);
     uint8_t* work = a.ws + r->work_offset;
+    // the image's own tables if it is optimised, otherwise the standard ones
+    const uint32_t* table = enc_optimized(r->flags) ? reinterpret_cast<const uint32_t*>(work + g.bytes) : kEncCodes.v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) codes[tid + 256 * i] = table[tid + 256 * i];
+    __syncthreads();
     const uint32_t* state = reinterpret_cast<const uint32_t*>(work + g.state_at);
     if (WRITE && state[1]) return;                            // the stream alone exceeds the slot: nothing of this image is written
     const uint32_t b = (blockIdx.x - r->start[1]) * kEncGroup + tid;
@@ -506,6 +529,152 @@ __global__ __launch_bounds__(256) void jpeg_enc_code_kernel(EncArgs a) {
         }
         sink.finish();
     }
+}
+
+// stats: sizes' grid, one lane per block of an optimised image.  The workgroup's symbols are counted in LDS, and what it saw is added to
+// the image's counts: integer sums, the same whatever the order.  A workgroup's blocks belong to one image; a plain image's return.
+__global__ __launch_bounds__(256) void jpeg_enc_stats_kernel(EncArgs a) {
+    __shared__ uint32_t hist[4 * 256];
+    const int tid = threadIdx.x;
+    const int img = enc_find(a.rec, a.n, 1, blockIdx.x);
+    const FearJpegEncImage* r = a.rec + img;
+    if (!enc_optimized(r->flags)) return;                     // the same for the whole workgroup
+#pragma unroll
+    for (int i = 0; i < 4; ++i) hist[tid + 256 * i] = 0u;
+    __syncthreads();
+    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap, r->sampling);
+    const uint8_t* work = a.ws + r->work_offset;
+    const uint32_t b = (blockIdx.x - r->start[1]) * kEncGroup + tid;
+    if (b < g.n_blocks) {
+        const int B = g.B, L = enc_luma(enc_mode(r->sampling));
+        const uint32_t mcu = B == 6 ? b / 6 : B == 4 ? b >> 2 : B == 3 ? b / 3 : b;
+        const int k = (int)(b - mcu * (uint32_t)B);
+        const int16_t* coef = reinterpret_cast<const int16_t*>(work);
+        const long prev = enc_prev_block(mcu, k, g.interval, B, L);
+        const int pred = prev < 0 ? 0 : coef[prev * 64];
+        EncStat sink;
+        enc_block(reinterpret_cast<const uint4*>(coef + (size_t)b * 64), pred, hist, k >= L, sink);
+    }
+    __syncthreads();
+    uint32_t* counts = reinterpret_cast<uint32_t*>(a.ws + r->stream_offset - kEncCountBytes);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t v = hist[tid + 256 * i];
+        if (v) atomicAdd(counts + tid + 256 * i, v);
+    }
+}
+
+// The smallest non-zero frequency other than `skip`'s over the 257 symbols, the larger symbol in a tie: every lane of the wave gets the
+// symbol, or -1.  A key is frequency << 9 | (256 - symbol), so that the smallest key is the answer; frequencies stay below 2^41.
+__device__ __forceinline__ int enc_huff_smallest(const HuffWork& w, int skip, int lane) {
+    uint64_t best = ~0ull;
+    for (int i = lane; i < kHuffSymbols; i += 64) {
+        const uint64_t f = w.freq[i];
+        const uint64_t key = f << 9 | (uint64_t)(kHuffSymbols - 1 - i);
+        if (f && i != skip && key < best) best = key;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint64_t other = __shfl_xor(best, d, 64);
+        best = other < best ? other : best;
+    }
+    return best == ~0ull ? -1 : kHuffSymbols - 1 - (int)(best & 511u);
+}
+
+// One wave builds one table from 256 counts (fear_jpeg_huff_build.h's rule): the frequencies, depths and chains live in LDS, each merge
+// takes two wave-wide searches, lane 0 walks the chains and, at the end, limits the lengths, sorts and writes.  Returns on lane 0 whether
+// the tree was shallow enough; the other lanes' result is not meaningful.
+__device__ __forceinline__ bool enc_huff_table(HuffWork& w, const uint32_t* freq, uint8_t* counts, uint8_t* values, int32_t* n_values,
+                                               uint32_t* codes, int32_t* depth) {
+    const int lane = threadIdx.x;
+    for (int i = lane; i < kHuffSymbols; i += 64) huff_init_one(w, i, i < 256 ? freq[i] : 0u);
+    __syncthreads();
+    for (int round = 0; round < kHuffSymbols; ++round) {      // at most 256 merges
+        const int c1 = enc_huff_smallest(w, -1, lane), c2 = enc_huff_smallest(w, c1, lane);
+        if (c2 < 0) break;                                    // the same in every lane
+        if (lane == 0) huff_merge(w, c1, c2);
+        __syncthreads();
+    }
+    bool ok = true;
+    if (lane == 0) ok = huff_finish(w, counts, values, n_values, codes, depth);
+    return ok;
+}
+
+// tables: one wave per (image, table) of an optimised image: the code table for sizes and write, and the table's DHT segment
+__global__ __launch_bounds__(64) void jpeg_enc_tables_kernel(EncArgs a) {
+    __shared__ HuffWork w;
+    const int img = blockIdx.x >> 2, t = blockIdx.x & 3;
+    const FearJpegEncImage* r = a.rec + img;
+    if (!enc_optimized(r->flags)) return;
+    const EncGeom g = enc_geom(r->width, r->height, r->restart_interval, r->stream_cap, r->sampling);
+    uint8_t* opt = a.ws + r->work_offset + g.bytes;
+    uint32_t* info = reinterpret_cast<uint32_t*>(opt + kEncOptInfoAt);
+    if (enc_mode(r->sampling) == FEAR_JPEG_ENC_GRAY && t >= 2) {         // gray has table 0 alone: no segment, and no code, so that
+        uint32_t* codes = reinterpret_cast<uint32_t*>(opt) + t * 256;     // sizes and write copy zeros and not what the workspace held
+        for (int i = threadIdx.x; i < 256; i += 64) codes[i] = 0u;
+        if (threadIdx.x == 0) info[t] = info[4 + t] = 0u;
+        return;
+    }
+    const uint32_t* freq = reinterpret_cast<const uint32_t*>(a.ws + r->stream_offset - kEncCountBytes) + t * 256;
+    uint8_t* dht = opt + kEncOptDhtAt + (size_t)t * kEncDhtPitch;
+    int32_t n_values = 0, depth = 0;
+    const bool ok = enc_huff_table(w, freq, dht + 5, dht + 21, &n_values, reinterpret_cast<uint32_t*>(opt) + t * 256, &depth);
+    if (threadIdx.x != 0) return;
+    dht[0] = 0xFF;
+    dht[1] = 0xC4;
+    dht[2] = (uint8_t)((19 + n_values) >> 8);
+    dht[3] = (uint8_t)((19 + n_values) & 255);
+    dht[4] = (uint8_t)((t & 1) << 4 | t >> 1);
+    info[t] = ok ? (uint32_t)(21 + n_values) : 0u;
+    info[4 + t] = ok ? 0u : 1u;
+}
+
+// fear_jpeg_huff_optimal: the same table stage on histograms of the caller's
+struct EncHuffArgs {
+    const uint32_t* freq;
+    uint8_t* counts;
+    uint8_t* values;
+    int32_t* n_values;
+    uint32_t* codes;
+    int32_t* status;
+};
+
+__global__ __launch_bounds__(64) void jpeg_enc_huff_optimal_kernel(EncHuffArgs a) {
+    __shared__ HuffWork w;
+    const size_t i = blockIdx.x;
+    int32_t n_values = 0, depth = 0;
+    const bool ok = enc_huff_table(w, a.freq + i * 256, a.counts + i * 16, a.values + i * 256, &n_values, a.codes + i * 256, &depth);
+    if (threadIdx.x != 0) return;
+    a.n_values[i] = n_values;
+    a.status[i] = ok ? FEAR_TRAIN_OK : FEAR_JPEG_ENC_HUFF_DEPTH;
+}
+
+// An optimised image's header: the record's bytes with the tables' DHT segments put in at enc_dht_at.  `deep`: a table was refused.
+struct EncHeader {
+    const uint8_t* head;
+    const uint8_t* dht;                  // null for a plain image
+    uint32_t split, dht_bytes[4], bytes;
+    bool deep;
+};
+
+__device__ __forceinline__ EncHeader enc_header(const FearJpegEncImage* r, const uint8_t* work, const EncGeom& g) {
+    EncHeader h;
+    h.head = r->header;
+    h.dht = nullptr;
+    h.split = h.bytes = r->header_bytes;
+    h.deep = false;
+    if (enc_optimized(r->flags)) {
+        const uint32_t* info = reinterpret_cast<const uint32_t*>(work + g.bytes + kEncOptInfoAt);
+        h.dht = work + g.bytes + kEncOptDhtAt;
+        h.split = enc_dht_at(enc_mode(r->sampling));
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            h.dht_bytes[t] = min(info[t], kEncDhtMax);
+            h.bytes += h.dht_bytes[t];
+            h.deep = h.deep || info[4 + t] != 0;
+        }
+    }
+    return h;
 }
 
 // segments: one workgroup per restart segment.  bits[] becomes each block's bit offset in its segment, seg[s] the segment's bytes.
@@ -554,16 +723,17 @@ __global__ __launch_bounds__(256) void jpeg_enc_image_scan_kernel(EncArgs a) {
         carry += sum;
     }
     if (threadIdx.x != 0) return;
+    const EncHeader h = enc_header(r, work, g);
     if (!LENGTHS) {
         v[g.n_seg] = carry;
         state[0] = carry;
-        state[1] = carry > r->stream_cap ? 1u : 0u;
+        state[1] = carry > r->stream_cap || h.deep ? 1u : 0u;   // (a refused table: nothing of the image is written either)
     } else {
         // header, stream, a 00 per FF, two bytes per restart marker, EOI
-        const uint64_t total = (uint64_t)r->header_bytes + state[0] + carry + 2ull * (g.n_seg - 1) + 2;
+        const uint64_t total = (uint64_t)h.bytes + state[0] + carry + 2ull * (g.n_seg - 1) + 2;
         const bool fits = !over && total <= r->out_cap;
         a.length[img] = fits ? (int32_t)total : 0;
-        a.status[img] = fits ? FEAR_TRAIN_OK : FEAR_JPEG_ENC_OVERFLOW;
+        a.status[img] = fits ? FEAR_TRAIN_OK : h.deep ? FEAR_JPEG_ENC_HUFF_DEPTH : FEAR_JPEG_ENC_OVERFLOW;
     }
 }
 
@@ -596,9 +766,20 @@ __global__ __launch_bounds__(256) void jpeg_enc_stuff_kernel(EncArgs a) {
         return;
     }
     uint8_t* out = r->out;
-    const uint32_t hb = r->header_bytes;
-    if (c == 0)
-        for (uint32_t i = threadIdx.x; i < hb; i += 256) out[i] = r->header[i];
+    const EncHeader h = enc_header(r, work, g);
+    const uint32_t hb = h.bytes;
+    if (c == 0) {
+        for (uint32_t i = threadIdx.x; i < h.split; i += 256) out[i] = h.head[i];
+        if (h.dht) {                                          // the image's own tables, then the rest of the record's header
+            uint32_t at = h.split;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                for (uint32_t i = threadIdx.x; i < h.dht_bytes[t]; i += 256) out[at + i] = h.dht[t * kEncDhtPitch + i];
+                at += h.dht_bytes[t];
+            }
+            for (uint32_t i = h.split + threadIdx.x; i < r->header_bytes; i += 256) out[at + i - h.split] = h.head[i];
+        }
+    }
     if (i0 >= U) return;
     // the segment of byte i0: the last one whose offset is not above it
     const uint32_t* seg_at = reinterpret_cast<const uint32_t*>(work + g.seg_at);
@@ -639,14 +820,16 @@ __global__ __launch_bounds__(256) void jpeg_enc_stuff_kernel(EncArgs a) {
 bool enc_record_ok(const FearJpegEncImage& r) {
     return r.width >= 1 && r.width <= FEAR_JPEG_MAX_SIDE && r.height >= 1 && r.height <= FEAR_JPEG_MAX_SIDE && r.quality >= 1 &&
            r.quality <= 100 && r.restart_interval >= 0 && r.restart_interval <= 65535 && r.header_bytes >= 1 && r.header_bytes <= 4096 &&
-           enc_sampling_ok(r.sampling);
+           enc_sampling_ok(r.sampling) && (r.flags & ~(uint32_t)FEAR_JPEG_ENC_OPTIMIZE) == 0 &&
+           (!enc_optimized(r.flags) || r.header_bytes > enc_dht_at(enc_mode(r.sampling)));
 }
 
 // the longest unstuffed stream: every block at its longest, and up to a byte of padding per segment
-uint32_t enc_stream_bound(int W, int H, int restart_interval, uint32_t sampling) {
+uint32_t enc_stream_bound(int W, int H, int restart_interval, uint32_t sampling, uint32_t flags = 0) {
     const EncGeom g = enc_geom(W, H, restart_interval, 0, sampling);
     const int L = enc_luma(enc_mode(sampling));
-    const uint64_t mcu_bits = (uint64_t)L * kEncLumaBits + (uint64_t)(g.B - L) * kEncChromaBits;   // 9952, 6636, 4978, 1658
+    uint64_t mcu_bits = (uint64_t)L * kEncLumaBits + (uint64_t)(g.B - L) * kEncChromaBits;   // 9952, 6636, 4978, 1658
+    if (enc_optimized(flags)) mcu_bits = (uint64_t)g.B * kEncOptBits;  // 9990, 6660, 4995, 1665
     return (uint32_t)((g.n_mcu * mcu_bits + 7) / 8 + g.n_seg);          // 8192 x 8192: 326 MB in 4:2:0, 652 MB in 4:4:4
 }
 
@@ -660,6 +843,7 @@ size_t enc_source_bytes(const FearJpegEncImage& r) {
 struct EncPlan {
     size_t stream_bytes, bytes;
     uint64_t grid[4];
+    bool optimized;                      // some record is: the call runs stats and tables
 };
 
 bool enc_plan(const FearJpegEncImage* images, int n, FearJpegEncImage* fill, EncPlan* plan) {
@@ -667,14 +851,17 @@ bool enc_plan(const FearJpegEncImage* images, int n, FearJpegEncImage* fill, Enc
     for (int i = 0; i < n; ++i)
         if (!enc_record_ok(images[i])) return false;
     EncPlan p{};
+    for (int i = 0; i < n; ++i) p.optimized = p.optimized || enc_optimized(images[i].flags);
     size_t at = FEAR_JPEG_ENC_TABLE_BYTES(n);
     const size_t stream0 = at;
     for (int pass = 0; pass < 2; ++pass) {                    // all streams first (one memset), then every image's scratch
         for (int i = 0; i < n; ++i) {
             const FearJpegEncImage& r = images[i];
-            const uint32_t cap = (std::min(enc_stream_bound(r.width, r.height, r.restart_interval, r.sampling), r.out_cap) + 4 + 15) & ~15u;
+            const uint32_t cap = (std::min(enc_stream_bound(r.width, r.height, r.restart_interval, r.sampling, r.flags), r.out_cap) + 4 + 15) & ~15u;
             const EncGeom g = enc_geom(r.width, r.height, r.restart_interval, cap, r.sampling);
+            const bool opt = enc_optimized(r.flags);
             if (pass == 0) {
+                if (opt) at += kEncCountBytes;                // the symbol counts, in the memset's reach
                 if (fill) {
                     fill[i].stream_offset = at;
                     fill[i].stream_cap = cap;
@@ -687,10 +874,9 @@ bool enc_plan(const FearJpegEncImage* images, int n, FearJpegEncImage* fill, Enc
                     fill[i].start[1] = (uint32_t)p.grid[1];
                     fill[i].start[2] = (uint32_t)p.grid[2];
                     fill[i].start[3] = (uint32_t)p.grid[3];
-                    fill[i].plan_sampling = r.sampling;               // (sampling itself is the caller's and stays)
-                    fill[i].reserved = 0;
+                    fill[i].plan_sampling = r.sampling | r.flags << 16;   // (sampling and flags themselves are the caller's and stay)
                 }
-                at += g.bytes;
+                at += g.bytes + (opt ? kEncOptBytes : 0);
                 const uint32_t per = (uint32_t)enc_mcus(enc_mode(r.sampling));
                 p.grid[0] += (g.n_mcu + per - 1) / per;
                 p.grid[1] += (g.n_blocks + kEncGroup - 1) / kEncGroup;
@@ -711,9 +897,10 @@ bool enc_plan(const FearJpegEncImage* images, int n, FearJpegEncImage* fill, Enc
 
 extern "C" {
 
-int fear_jpeg_encode_header_mode(int width, int height, int quality, int restart_interval, int sampling, uint8_t* out, size_t out_cap,
-                                 size_t* out_used) {
+int fear_jpeg_encode_header_flags(int width, int height, int quality, int restart_interval, int sampling, uint32_t flags, uint8_t* out,
+                                  size_t out_cap, size_t* out_used) {
     if (!out || !out_used) return FEAR_TRAIN_ERR_NULL;
+    if ((flags & ~(uint32_t)FEAR_JPEG_ENC_OPTIMIZE) != 0) return FEAR_TRAIN_ERR_SHAPE;
     if (width < 1 || width > FEAR_JPEG_MAX_SIDE || height < 1 || height > FEAR_JPEG_MAX_SIDE || quality < 1 || quality > 100 ||
         restart_interval < 0 || restart_interval > 65535 || sampling < FEAR_JPEG_ENC_420 || sampling > FEAR_JPEG_ENC_GRAY)
         return FEAR_TRAIN_ERR_SHAPE;
@@ -732,7 +919,7 @@ int fear_jpeg_encode_header_mode(int width, int height, int quality, int restart
     else
         put({0xFF, 0xC0, 0, 17, 8, height >> 8, height & 255, width >> 8, width & 255, 3, 1,
              sampling == FEAR_JPEG_ENC_420 ? 0x22 : sampling == FEAR_JPEG_ENC_422 ? 0x21 : 0x11, 0, 2, 0x11, 1, 3, 0x11, 1});
-    for (int t = 0; t < 2 * tables; ++t) {
+    for (int t = 0; t < 2 * tables && !enc_optimized(flags); ++t) {      // (an optimised file's tables are the device's to put here)
         const int total = kEncStd[t].total;
         put({0xFF, 0xC4, (19 + total) >> 8, (19 + total) & 255, (t & 1) << 4 | t >> 1});
         for (int i = 0; i < 16; ++i) h[at++] = kEncStd[t].counts[i];
@@ -747,18 +934,29 @@ int fear_jpeg_encode_header_mode(int width, int height, int quality, int restart
     return FEAR_TRAIN_OK;
 }
 
+int fear_jpeg_encode_header_mode(int width, int height, int quality, int restart_interval, int sampling, uint8_t* out, size_t out_cap,
+                                 size_t* out_used) {
+    return fear_jpeg_encode_header_flags(width, height, quality, restart_interval, sampling, 0, out, out_cap, out_used);
+}
+
 int fear_jpeg_encode_header(int width, int height, int quality, int restart_interval, uint8_t* out, size_t out_cap, size_t* out_used) {
     return fear_jpeg_encode_header_mode(width, height, quality, restart_interval, FEAR_JPEG_ENC_420, out, out_cap, out_used);
 }
 
-size_t fear_jpeg_encode_bound_mode(int width, int height, int restart_interval, int sampling) {
+size_t fear_jpeg_encode_bound_flags(int width, int height, int restart_interval, int sampling, uint32_t flags) {
     if (width < 1 || width > FEAR_JPEG_MAX_SIDE || height < 1 || height > FEAR_JPEG_MAX_SIDE || restart_interval < 0 ||
-        restart_interval > 65535 || sampling < FEAR_JPEG_ENC_420 || sampling > FEAR_JPEG_ENC_GRAY)
+        restart_interval > 65535 || sampling < FEAR_JPEG_ENC_420 || sampling > FEAR_JPEG_ENC_GRAY ||
+        (flags & ~(uint32_t)FEAR_JPEG_ENC_OPTIMIZE) != 0)
         return 0;
     const EncGeom g = enc_geom(width, height, restart_interval, 0, (uint32_t)sampling);
     const size_t header = (sampling == FEAR_JPEG_ENC_GRAY ? 328 : 623) + (restart_interval ? 6 : 0);
     // the header with or without DRI; every stream byte stuffed; a marker in front of every segment but the first; EOI
-    return header + 2 * (size_t)enc_stream_bound(width, height, restart_interval, (uint32_t)sampling) + 2 * ((size_t)g.n_seg - 1) + 2;
+    // (an optimised file's header is never longer: a table lists the symbols its scan has, at most the standard table's 12 or 162)
+    return header + 2 * (size_t)enc_stream_bound(width, height, restart_interval, (uint32_t)sampling, flags) + 2 * ((size_t)g.n_seg - 1) + 2;
+}
+
+size_t fear_jpeg_encode_bound_mode(int width, int height, int restart_interval, int sampling) {
+    return fear_jpeg_encode_bound_flags(width, height, restart_interval, sampling, 0);
 }
 
 size_t fear_jpeg_encode_bound(int width, int height, int restart_interval) {
@@ -808,6 +1006,12 @@ int fear_jpeg_encode_u8(const FearJpegEncImage* images, int n, void* workspace, 
     if (hipMemsetAsync(a.ws + FEAR_JPEG_ENC_TABLE_BYTES(n), 0, plan.stream_bytes, st) != hipSuccess) return FEAR_TRAIN_ERR_HIP;
     hipLaunchKernelGGL(jpeg_enc_transform_kernel, dim3((unsigned)plan.grid[0]), dim3(256), 0, st, a);
     LAUNCH_CHECK();
+    if (plan.optimized) {                                     // (the memset above has zeroed the counts)
+        hipLaunchKernelGGL(jpeg_enc_stats_kernel, dim3((unsigned)plan.grid[1]), dim3(256), 0, st, a);
+        LAUNCH_CHECK();
+        hipLaunchKernelGGL(jpeg_enc_tables_kernel, dim3(4u * (unsigned)n), dim3(64), 0, st, a);
+        LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(jpeg_enc_code_kernel<false>, dim3((unsigned)plan.grid[1]), dim3(256), 0, st, a);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(jpeg_enc_segments_kernel, dim3((unsigned)plan.grid[2]), dim3(256), 0, st, a);
@@ -821,6 +1025,17 @@ int fear_jpeg_encode_u8(const FearJpegEncImage* images, int n, void* workspace, 
     hipLaunchKernelGGL(jpeg_enc_image_scan_kernel<true>, dim3((unsigned)n), dim3(256), 0, st, a);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(jpeg_enc_stuff_kernel<true>, dim3((unsigned)plan.grid[3]), dim3(256), 0, st, a);
+    LAUNCH_CHECK();
+    return FEAR_TRAIN_OK;
+}
+
+int fear_jpeg_huff_optimal(const uint32_t* freq_dev, int n, uint8_t* counts_dev, uint8_t* values_dev, int32_t* nvalues_dev,
+                           uint32_t* codes_dev, int32_t* status_dev, void* stream) {
+    if (n < 0 || n > 65535 * 4) return FEAR_TRAIN_ERR_SHAPE;
+    if (n == 0) return FEAR_TRAIN_OK;
+    if (!freq_dev || !counts_dev || !values_dev || !nvalues_dev || !codes_dev || !status_dev) return FEAR_TRAIN_ERR_NULL;
+    const EncHuffArgs a{freq_dev, counts_dev, values_dev, nvalues_dev, codes_dev, status_dev};
+    hipLaunchKernelGGL(jpeg_enc_huff_optimal_kernel, dim3((unsigned)n), dim3(64), 0, static_cast<hipStream_t>(stream), a);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }

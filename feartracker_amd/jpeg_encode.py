@@ -4,7 +4,9 @@
 three-component frame (`PIL.Image.fromarray(rgb).save(f, "JPEG", quality=q)`): baseline SOF0, 4:2:0, islow FDCT, the standard Huffman
 tables of T.81 annex K, optionally a restart interval of whole MCU rows — and, with `subsampling=`, the 4:2:2, 4:4:4 and
 single-component files Pillow writes with `subsampling=1`, `subsampling=0` and for a mode-L image.  tests/test_jpeg_encode_host.py and
-tests/test_jpeg_encode_modes_host.py hold it to Pillow's libjpeg-turbo.  `JpegEncoder` is the product: `fear_jpeg_encode_u8`
+tests/test_jpeg_encode_modes_host.py hold it to Pillow's libjpeg-turbo.  With `optimize=True` the file is the one Pillow writes with
+`optimize=True`: per-file Huffman tables, stated by `jpeg_symbol_histograms_host` and `jpeg_optimal_table_host`
+(tests/test_jpeg_encode_optimize_host.py).  `JpegEncoder` is the product: `fear_jpeg_encode_u8`
 (csrc/fear_jpeg_encode.h) runs every stage on the device and `PendingJpegs.result()` downloads the files' bytes alone.  `write_mjpeg_avi` puts equal-sized files into a Motion-JPEG AVI."""
 from __future__ import annotations
 
@@ -31,6 +33,8 @@ STD_HUFFMAN = {
         "c2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")),
 }
 ENC_OVERFLOW = 1                          # include/fear_train.h FEAR_JPEG_ENC_OVERFLOW
+ENC_HUFF_DEPTH = 2                        # include/fear_train.h FEAR_JPEG_ENC_HUFF_DEPTH
+HUFF_MAX_DEPTH = 32                       # libjpeg's MAX_CLEN: an unlimited Huffman depth above it is refused
 # The layouts a file can have, by name: include/fear_train.h's FEAR_JPEG_ENC_420 .. _GRAY, the MCU's (width, height) in pixels, the
 # (horizontal, vertical) luma sampling factors and Pillow's `subsampling=` (None: a single-component file)
 SUBSAMPLINGS = ("4:2:0", "4:2:2", "4:4:4", "gray")
@@ -46,6 +50,17 @@ class JpegOverflow(ValueError):
     def __init__(self, items: Sequence[int]):
         self.items = list(items)
         super().__init__(f"the JPEG files of items {self.items} exceed their slots")
+
+
+class JpegHuffmanDepth(ValueError):
+    """The symbol statistics of some optimised files of an `encode` call give a Huffman tree deeper than 32 before limiting, which
+    libjpeg refuses (JERR_HUFF_CLEN_OVERFLOW); `.items` lists their indexes.  It is raised in preference to `JpegOverflow`: `.overflow`
+    lists the items of the same call whose files exceed their slots, so that neither kind goes unnamed."""
+
+    def __init__(self, items: Sequence[int], overflow: Sequence[int] = ()):
+        self.items, self.overflow = list(items), list(overflow)
+        also = f"; the files of items {self.overflow} exceed their slots" if self.overflow else ""
+        super().__init__(f"the Huffman trees of items {self.items} are deeper than {HUFF_MAX_DEPTH}{also}")
 
 
 def _codes(counts: Sequence[int], values: bytes):
@@ -165,9 +180,12 @@ def jpeg_forward_coefficients_host(rgb: np.ndarray, quality: int = 75, subsampli
     return out
 
 
-def jpeg_header_host(width: int, height: int, quality: int = 75, restart_interval: int = 0, subsampling: str = "4:2:0") -> bytes:
+def jpeg_header_host(width: int, height: int, quality: int = 75, restart_interval: int = 0, subsampling: str = "4:2:0",
+                     tables=None) -> bytes:
     """Everything in front of the scan: SOI, JFIF APP0, the two DQT, SOF0, the four standard DHT, DRI if there is an interval, SOS.
-    "gray" has one DQT, one component and the two luma DHT."""
+    "gray" has one DQT, one component and the two luma DHT.  `tables` are per-file tables in STD_HUFFMAN's form, {(class, id): (counts,
+    values)}: they take the standard ones' place, in the same order."""
+    tables = STD_HUFFMAN if tables is None else tables
     gray = _check_subsampling(subsampling) == "gray"
     if not (1 <= width <= MAX_SIDE and 1 <= height <= MAX_SIDE):
         raise ValueError(f"a frame's sides lie in 1..{MAX_SIDE}")
@@ -182,8 +200,10 @@ def jpeg_header_host(width: int, height: int, quality: int = 75, restart_interva
         h, v = _LUMA[subsampling]
         out += b"\xFF\xC0\x00\x11\x08" + struct.pack(">HH", height, width) + bytes([3, 1, h << 4 | v, 0, 2, 0x11, 1, 3, 0x11, 1])
     for (tc, th) in ((0, 0), (1, 0)) if gray else ((0, 0), (1, 0), (0, 1), (1, 1)):
-        counts, values = STD_HUFFMAN[(tc, th)]
-        out += b"\xFF\xC4" + struct.pack(">H", 19 + len(values)) + bytes([tc << 4 | th]) + bytes(counts) + values
+        counts, values = tables[(tc, th)]
+        if len(counts) != 16 or sum(counts) != len(values) or len(values) > 256:
+            raise ValueError("a Huffman table is 16 counts and as many values as they sum to")
+        out += b"\xFF\xC4" + struct.pack(">H", 19 + len(values)) + bytes([tc << 4 | th]) + bytes(int(c) for c in counts) + bytes(values)
     if restart_interval:
         out += b"\xFF\xDD\x00\x04" + struct.pack(">H", restart_interval)
     out += b"\xFF\xDA\x00\x08\x01\x01\x00\x00\x3F\x00" if gray else b"\xFF\xDA\x00\x0C\x03\x01\x00\x02\x11\x03\x11\x00\x3F\x00"
@@ -210,69 +230,163 @@ class _BitWriter:
             self.put((1 << (8 - self.have)) - 1, 8 - self.have)             # ones up to the byte; stuffed like any other byte
 
 
-def jpeg_entropy_encode_host(coefficients: Sequence[np.ndarray], mcus_x: int, mcus_y: int, restart_interval: int = 0,
-                             subsampling: str = "4:2:0") -> bytes:
-    """T.81 F.1.2 over one scan: the stuffed bytes between SOS and EOI, restart markers included.  The scan is interleaved, an MCU's
-    luma blocks row by row and then Cb and Cr; "gray" is one component, an MCU one block."""
+def _scan_walk(coefficients: Sequence[np.ndarray], mcus_x: int, mcus_y: int, restart_interval: int, subsampling: str, symbol, extra,
+               restart) -> None:
+    """T.81 F.1.2's walk over one interleaved scan, an MCU's luma blocks row by row and then Cb and Cr ("gray": one block): calls
+    `symbol(class, table, value)` for every Huffman symbol, `extra(value, bits)` for the bits behind it and `restart(k)` at the k-th
+    restart boundary, where the DC predictions return to 0."""
     hs, vs = _LUMA[_check_subsampling(subsampling)]
-    w = _BitWriter()
     pred = [0, 0, 0]
     for mcu in range(mcus_x * mcus_y):
         if restart_interval and mcu and mcu % restart_interval == 0:
-            w.flush()
-            w.out += bytes([0xFF, 0xD0 + ((mcu // restart_interval - 1) & 7)])
+            restart(mcu // restart_interval - 1)
             pred = [0, 0, 0]
         my, mx = divmod(mcu, mcus_x)
         blocks = [(0, vs * my + j, hs * mx + i) for j in range(vs) for i in range(hs)]
         if subsampling != "gray":
             blocks += [(1, my, mx), (2, my, mx)]
         for c, j, i in blocks:
-            blk = [int(x) for x in coefficients[c][j, i]]
-            dc, ac = _STD_CODES[(0, 1 if c else 0)], _STD_CODES[(1, 1 if c else 0)]
-            diff = blk[0] - pred[c]
-            pred[c] = blk[0]
+            blk = coefficients[c][j, i]
+            t = 1 if c else 0
+            diff = int(blk[0]) - pred[c]
+            pred[c] = int(blk[0])
             s = abs(diff).bit_length()
-            w.put(*dc[s])
-            w.put(diff if diff >= 0 else diff + (1 << s) - 1, s)
-            run = 0
-            for k in range(1, 64):
-                v = blk[k]
-                if v == 0:
-                    run += 1
-                    continue
+            symbol(0, t, s)
+            extra(diff if diff >= 0 else diff + (1 << s) - 1, s)
+            at = 0                                                          # the last coefficient coded
+            for k in np.flatnonzero(blk[1:]).tolist():
+                k += 1
+                run, v = k - at - 1, int(blk[k])
                 while run > 15:
-                    w.put(*ac[0xF0])
+                    symbol(1, t, 0xF0)
                     run -= 16
                 s = abs(v).bit_length()
-                w.put(*ac[run << 4 | s])
-                w.put(v if v >= 0 else v + (1 << s) - 1, s)
-                run = 0
-            if run:
-                w.put(*ac[0x00])
+                symbol(1, t, run << 4 | s)
+                extra(v if v >= 0 else v + (1 << s) - 1, s)
+                at = k
+            if at != 63:
+                symbol(1, t, 0x00)
+
+
+def jpeg_entropy_encode_host(coefficients: Sequence[np.ndarray], mcus_x: int, mcus_y: int, restart_interval: int = 0,
+                             subsampling: str = "4:2:0", tables=None) -> bytes:
+    """T.81 F.1.2 over one scan: the stuffed bytes between SOS and EOI, restart markers included.  The scan is interleaved, an MCU's
+    luma blocks row by row and then Cb and Cr; "gray" is one component, an MCU one block.  `tables`: per-file tables in STD_HUFFMAN's
+    form in place of the standard ones."""
+    codes = _STD_CODES if tables is None else {key: _codes(*tab) for key, tab in tables.items()}
+    w = _BitWriter()
+
+    def restart(k: int) -> None:
+        w.flush()
+        w.out += bytes([0xFF, 0xD0 + (k & 7)])
+
+    _scan_walk(coefficients, mcus_x, mcus_y, restart_interval, subsampling, lambda tc, th, v: w.put(*codes[(tc, th)][v]), w.put, restart)
     w.flush()
     return bytes(w.out)
 
 
-def jpeg_encode_host(rgb: np.ndarray, quality: int = 75, restart_rows: int = 0, subsampling: str = "4:2:0") -> bytes:
+def jpeg_symbol_histograms_host(coefficients: Sequence[np.ndarray], mcus_x: int, mcus_y: int, restart_interval: int = 0,
+                                subsampling: str = "4:2:0") -> np.ndarray:
+    """How often the entropy coder emits each Huffman symbol over the scan: int64 (4, 256), rows DC 0, AC 0, DC 1, AC 1 (the order of
+    the file's DHT segments).  Exactly `jpeg_entropy_encode_host`'s symbols: the dummy blocks, ZRL and EOB count, and the DC differences
+    start from 0 again at every restart boundary.  "gray" leaves rows 2 and 3 at 0."""
+    hist = np.zeros((4, 256), dtype=np.int64)
+
+    def symbol(tc: int, th: int, v: int) -> None:
+        hist[2 * th + tc, v] += 1
+
+    _scan_walk(coefficients, mcus_x, mcus_y, restart_interval, subsampling, symbol, lambda v, s: None, lambda k: None)
+    return hist
+
+
+def jpeg_optimal_table_host(freq) -> Tuple[Tuple[int, ...], bytes, int]:
+    """The Huffman table libjpeg's jpeg_gen_optimal_table builds from 256 symbol counts (T.81 K.2): (the 16 counts of codes per length,
+    the symbols in code order, the tree's depth before limiting).  A reserved 257th symbol of frequency 1 keeps any code from being all
+    ones.  The two smallest non-zero frequencies are merged until one is left, in a tie the larger symbol number first; lengths above
+    16 are brought down by Adjust_BITS; the reserved symbol leaves the longest length in use; symbols are sorted by their length in
+    the tree, then by value.  A depth above 32 is refused as libjpeg refuses it: `JpegHuffmanDepth`.  Frequencies are exact integers
+    of any size (libjpeg's sentinel of 10^9 is above every count a frame of the largest size can give)."""
+    f = [int(x) for x in np.asarray(freq).reshape(-1)]
+    if len(f) != 256 or min(f) < 0:
+        raise ValueError("256 counts, none negative")
+    f.append(1)
+    size, others = [0] * 257, [-1] * 257
+    while True:
+        c1 = c2 = -1
+        for i in range(257):                                                # the smallest, the larger symbol in a tie
+            if f[i] and (c1 < 0 or f[i] <= f[c1]):
+                c1 = i
+        for i in range(257):
+            if f[i] and i != c1 and (c2 < 0 or f[i] <= f[c2]):
+                c2 = i
+        if c2 < 0:
+            break
+        f[c1] += f[c2]
+        f[c2] = 0
+        size[c1] += 1                                                       # every symbol of both subtrees is one level deeper
+        while others[c1] >= 0:
+            c1 = others[c1]
+            size[c1] += 1
+        others[c1] = c2                                                     # the second subtree's chain behind the first's
+        size[c2] += 1
+        while others[c2] >= 0:
+            c2 = others[c2]
+            size[c2] += 1
+    depth = max(size)
+    if depth > HUFF_MAX_DEPTH:
+        raise JpegHuffmanDepth([0])
+    bits = [0] * (HUFF_MAX_DEPTH + 1)
+    for s in size:
+        if s:
+            bits[s] += 1
+    for i in range(HUFF_MAX_DEPTH, 16, -1):                                 # Adjust_BITS: a pair of the longest codes becomes one
+        while bits[i] > 0:                                                  # a bit shorter, a shorter code two codes a bit longer
+            j = i - 2
+            while bits[j] == 0:
+                j -= 1
+            bits[i] -= 2
+            bits[i - 1] += 1
+            bits[j + 1] += 2
+            bits[j] -= 1
+    i = 16
+    while i > 0 and bits[i] == 0:
+        i -= 1
+    if i:
+        bits[i] -= 1                                                        # the reserved symbol
+    values = bytes(sorted((j for j in range(256) if size[j]), key=lambda j: (size[j], j)))
+    return tuple(bits[1:17]), values, depth
+
+
+def jpeg_optimal_tables_host(coefficients: Sequence[np.ndarray], mcus_x: int, mcus_y: int, restart_interval: int = 0,
+                             subsampling: str = "4:2:0"):
+    """The per-file tables of a scan in STD_HUFFMAN's form: those of the tables the layout uses, built from its symbol counts."""
+    hist = jpeg_symbol_histograms_host(coefficients, mcus_x, mcus_y, restart_interval, subsampling)
+    keys = ((0, 0), (1, 0)) if subsampling == "gray" else ((0, 0), (1, 0), (0, 1), (1, 1))
+    return {(tc, th): jpeg_optimal_table_host(hist[2 * th + tc])[:2] for tc, th in keys}
+
+
+def jpeg_encode_host(rgb: np.ndarray, quality: int = 75, restart_rows: int = 0, subsampling: str = "4:2:0", optimize: bool = False) -> bytes:
     """A uint8 (H, W, 3) RGB frame -> the baseline JPEG file libjpeg writes for it at `quality`, with a restart marker every
     `restart_rows` MCU rows if that is not 0, in the layout `subsampling` names: Pillow's `subsampling=` 2, 1 and 0, or with "gray"
-    the single-component file of an (H, W) frame, or of an (H, W, 3) frame's luma (Pillow's `convert("L")`).  Slow; the statement the
-    device is held to."""
+    the single-component file of an (H, W) frame, or of an (H, W, 3) frame's luma (Pillow's `convert("L")`).  `optimize`: the file of
+    Pillow's `optimize=True`, whose Huffman tables are built from the scan's own symbol counts (`jpeg_optimal_table_host`).  Slow; the
+    statement the device is held to."""
     v = _check_rgb(rgb, _check_subsampling(subsampling))
     H, W = v.shape[:2]
     mcu_w, mcu_h = _MCU[subsampling]
     mcus_x, mcus_y = -(-W // mcu_w), -(-H // mcu_h)
     interval = _restart_interval(restart_rows, mcus_x)
     coef = jpeg_forward_coefficients_host(v, quality, subsampling)
-    return (jpeg_header_host(W, H, quality, interval, subsampling) + jpeg_entropy_encode_host(coef, mcus_x, mcus_y, interval, subsampling)
-            + b"\xFF\xD9")
+    tables = jpeg_optimal_tables_host(coef, mcus_x, mcus_y, interval, subsampling) if optimize else None
+    return (jpeg_header_host(W, H, quality, interval, subsampling, tables)
+            + jpeg_entropy_encode_host(coef, mcus_x, mcus_y, interval, subsampling, tables) + b"\xFF\xD9")
 
 
 # ------------------------------------------------------------------------------------------------------------------------ the product
 class PendingJpegs:
     """The files of one `JpegEncoder.encode` call, still on the device and possibly still being written.  `buffer` (uint8) holds one
     slot per item at `offsets` (int64 bytes), `lengths` (int32) the files' lengths — 0 for an item that did not fit — and `status`
-    (int32) 0 or ENC_OVERFLOW: device tensors, ordered on the stream `encode` ran on, for consumers that stay on the device."""
+    (int32) 0, ENC_OVERFLOW or ENC_HUFF_DEPTH: device tensors, ordered on the stream `encode` ran on, for consumers that stay on the device."""
 
     def __init__(self, buffer, offsets, lengths, status, host_offsets: Sequence[int], keep=()):
         self.buffer, self.offsets, self.lengths, self.status = buffer, offsets, lengths, status
@@ -282,14 +396,18 @@ class PendingJpegs:
         return len(self._host_offsets)
 
     def result(self) -> List[bytes]:
-        """Wait, download the lengths and then the used bytes alone; `JpegOverflow` names the items whose files exceed their slots."""
+        """Wait, download the lengths and then the used bytes alone; `JpegOverflow` names the items whose files exceed their slots,
+        `JpegHuffmanDepth` those whose own Huffman trees libjpeg would refuse (and, in `.overflow`, the former, if a call has both)."""
         import torch
         n = len(self._host_offsets)
         if n == 0:
             return []
         verdict = torch.stack([self.lengths, self.status]).cpu().numpy()   # one copy, which waits for the stream
         self._keep = ()
-        bad = np.flatnonzero(verdict[1])
+        deep = np.flatnonzero(verdict[1] == ENC_HUFF_DEPTH)
+        bad = np.flatnonzero((verdict[1] != 0) & (verdict[1] != ENC_HUFF_DEPTH))
+        if deep.size:
+            raise JpegHuffmanDepth([int(i) for i in deep], [int(i) for i in bad])
         if bad.size:
             raise JpegOverflow([int(i) for i in bad])
         at = np.concatenate([[0], np.cumsum(verdict[0], dtype=np.int64)])
@@ -312,10 +430,16 @@ class JpegEncoder:
     waits for the GPU.  Every file gets a slot of `slot_bytes` in one device buffer: by default 1024 + c times the frame's pixels with
     its sides padded to whole MCUs, where c is 3 for "4:2:0" and "gray", 4 for "4:2:2" and 6 for "4:4:4": a little above the raw pixels; `"bound"` takes `fear_jpeg_encode_bound`, the longest file the frame's size can give, and an int is
     the slot of every frame.  A file that exceeds its slot is not written: its length is 0 and `PendingJpegs.result()` raises
-    `JpegOverflow`; the other files of the call are unaffected.  `guard_bytes` are left unused behind every slot."""
+    `JpegOverflow`; the other files of the call are unaffected.  `guard_bytes` are left unused behind every slot.
+
+    `optimize=True` writes what Pillow's `save(..., optimize=True)` writes: Huffman tables built from the file's own symbol counts, on
+    the device between the transform and the size pass, so that `encode` still never waits.  `encode` takes a bool for the call or one
+    per frame, and likewise `restart_rows`; optimised and plain frames mix freely in one call.  With `"bound"` an optimised frame's slot
+    is `fear_jpeg_encode_bound_flags`.  An image whose Huffman tree is deeper than 32 before limiting, which libjpeg refuses, is not
+    written: `result()` raises `JpegHuffmanDepth`."""
 
     def __init__(self, device: int = 0, quality: int = 75, restart_rows: int = 0, slot_bytes: Union[None, int, str] = None,
-                 guard_bytes: int = 0, subsampling: str = "4:2:0"):
+                 guard_bytes: int = 0, subsampling: str = "4:2:0", optimize: bool = False):
         import torch
         from .train_abi import load_train_library
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
@@ -323,6 +447,9 @@ class JpegEncoder:
         self.subsampling = _check_subsampling(subsampling)
         _restart_interval(restart_rows, 1)
         self.restart_rows = int(restart_rows)
+        if not isinstance(optimize, (bool, np.bool_)):
+            raise TypeError("optimize is a bool")
+        self.optimize = bool(optimize)
         if not (slot_bytes is None or slot_bytes == "bound" or (isinstance(slot_bytes, (int, np.integer)) and not isinstance(slot_bytes, bool))):
             raise TypeError('slot_bytes is None, "bound" or an int')
         if isinstance(slot_bytes, (int, np.integer)) and not 0 < slot_bytes < 1 << 32:
@@ -371,11 +498,31 @@ class JpegEncoder:
         return out, modes
 
     def encode(self, frames, quality: Union[None, int, Sequence[int]] = None,
-               subsampling: Union[None, str, Sequence[str]] = None) -> PendingJpegs:
+               subsampling: Union[None, str, Sequence[str]] = None, optimize: Union[None, bool, Sequence[bool]] = None,
+               restart_rows: Union[None, int, Sequence[int]] = None) -> PendingJpegs:
         import torch
-        from .train_abi import (FEAR_JPEG_ENC_GRAY_RGB, FEAR_JPEG_ENC_HEADER_MAX, FEAR_JPEG_ENC_TABLE_BYTES, FearJpegEncImage, launch)
+        from .train_abi import (FEAR_JPEG_ENC_GRAY_RGB, FEAR_JPEG_ENC_HEADER_MAX, FEAR_JPEG_ENC_OPTIMIZE, FEAR_JPEG_ENC_TABLE_BYTES,
+                                FearJpegEncImage, launch)
         frames, modes = self._frames(frames, subsampling)
         n = len(frames)
+        if optimize is None:
+            optimize = self.optimize
+        if isinstance(optimize, (bool, np.bool_)):
+            flags = [FEAR_JPEG_ENC_OPTIMIZE if optimize else 0] * n
+        elif isinstance(optimize, (list, tuple, np.ndarray)) and all(isinstance(o, (bool, np.bool_)) for o in optimize):
+            flags = [FEAR_JPEG_ENC_OPTIMIZE if o else 0 for o in optimize]
+            if len(flags) != n:
+                raise ValueError("one optimize per frame")
+        else:
+            raise TypeError("optimize is a bool, or a sequence of them with one per frame")
+        if restart_rows is None:
+            restart_rows = self.restart_rows
+        if isinstance(restart_rows, (list, tuple, np.ndarray)):
+            rows = list(restart_rows)
+            if len(rows) != n:
+                raise ValueError("one restart_rows per frame")
+        else:
+            rows = [restart_rows] * n
         if quality is None:
             qualities = [self.quality] * n
         elif isinstance(quality, (int, np.integer)) and not isinstance(quality, bool):
@@ -392,15 +539,16 @@ class JpegEncoder:
             H, W = int(f.shape[0]), int(f.shape[1])
             mode, (mcu_w, mcu_h) = _MODE[modes[k]], _MCU[modes[k]]
             mcus_x, mcus_y = -(-W // mcu_w), -(-H // mcu_h)
-            interval = _restart_interval(self.restart_rows, mcus_x)
-            launch(lib, "fear_jpeg_encode_header_mode", W, H, qualities[k], interval, mode, scratch, len(scratch), ctypes.byref(used))
+            interval = _restart_interval(rows[k], mcus_x)
+            # (an optimised frame's header goes up without its DHT segments: the device puts its own in)
+            launch(lib, "fear_jpeg_encode_header_flags", W, H, qualities[k], interval, mode, flags[k], scratch, len(scratch), ctypes.byref(used))
             headers.append(bytes(scratch[:used.value]))
             header_at.append(at)
             at += -(-used.value // 16) * 16
             if self.slot_bytes is None:
                 slot = 1024 + _SLOT_FACTOR[modes[k]] * (mcu_w * mcus_x) * (mcu_h * mcus_y)
             elif self.slot_bytes == "bound":
-                slot = int(lib.fear_jpeg_encode_bound_mode(W, H, interval, mode))
+                slot = int(lib.fear_jpeg_encode_bound_flags(W, H, interval, mode, flags[k]))
             else:
                 slot = int(self.slot_bytes)
             if slot >= 1 << 32:
@@ -409,6 +557,7 @@ class JpegEncoder:
             rec.width, rec.height, rec.quality, rec.restart_interval = W, H, qualities[k], interval
             rec.out_cap, rec.header_bytes = slot, used.value
             rec.sampling = mode | (FEAR_JPEG_ENC_GRAY_RGB if modes[k] == "gray" and f.ndim == 3 else 0)
+            rec.flags = flags[k]
             slot_at.append(out_at)
             out_at += -(-(slot + self.guard_bytes) // 16) * 16
         with torch.cuda.device(self.device):

@@ -130,6 +130,10 @@ TRAIN_SYMBOLS = {
     "fear_jpeg_encode_plan": ([_P, _i], _i),
     "fear_jpeg_encode_workspace_bytes": ([_P, _i], _sz),
     "fear_jpeg_encode_u8": ([_P, _i, _P, _sz, _P, _P, _P], _i),
+    # per-file Huffman tables: the header without its DHT segments and the bound of an optimised record; the table stage on its own
+    "fear_jpeg_encode_header_flags": ([_i, _i, _i, _i, _i, ctypes.c_uint32, _P, _sz, _P], _i),
+    "fear_jpeg_encode_bound_flags": ([_i, _i, _i, _i, ctypes.c_uint32], _sz),
+    "fear_jpeg_huff_optimal": ([_P, _i, _P, _P, _P, _P, _P, _P], _i),
 }
 
 
@@ -343,14 +347,16 @@ class FearJpegEncImage(ctypes.Structure):
                 ("work_offset", ctypes.c_uint64), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("quality", ctypes.c_int32),
                 ("restart_interval", ctypes.c_int32), ("out_cap", ctypes.c_uint32), ("header_bytes", ctypes.c_uint32),
                 ("stream_cap", ctypes.c_uint32), ("start", ctypes.c_uint32 * 4), ("sampling", ctypes.c_uint32), ("plan_sampling", ctypes.c_uint32),
-                ("reserved", ctypes.c_uint32)]
+                ("flags", ctypes.c_uint32)]
 
 
 assert ctypes.sizeof(FearJpegEncImage) == 96 and FearJpegEncImage.width.offset == 40 and FearJpegEncImage.stream_cap.offset == 64
-assert FearJpegEncImage.sampling.offset == 84
+assert FearJpegEncImage.sampling.offset == 84 and FearJpegEncImage.flags.offset == 92
 FEAR_JPEG_ENC_420, FEAR_JPEG_ENC_422, FEAR_JPEG_ENC_444, FEAR_JPEG_ENC_GRAY = 0, 1, 2, 3     # a record's sampling
 FEAR_JPEG_ENC_GRAY_RGB = 0x100        # or-ed into FEAR_JPEG_ENC_GRAY: the source is (height, width, 3) RGB
 FEAR_JPEG_ENC_OVERFLOW = 1
+FEAR_JPEG_ENC_HUFF_DEPTH = 2          # a status: the image's Huffman tree is deeper than 32 before limiting
+FEAR_JPEG_ENC_OPTIMIZE = 1            # a record's flags: per-file Huffman tables
 FEAR_JPEG_ENC_HEADER_MAX = 640
 FEAR_JPEG_ENC_GROUP_BLOCKS = 256      # blocks per workgroup of fear_jpeg_encode_u8's sizes and write passes
 FEAR_JPEG_ENC_CHUNK_BYTES = 4096      # unstuffed stream bytes per workgroup of its count and assemble passes

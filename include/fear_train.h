@@ -1164,8 +1164,36 @@ int fear_miner_update(const float* templ, const float* search, const float* cls,
  * 328 bytes (334 with DRI), the colour layouts' 623 (629).  A restart interval counts the layout's MCUs.  A gray source is width x height
  * bytes unless FEAR_JPEG_ENC_GRAY_RGB is set.  fear_jpeg_encode_header and fear_jpeg_encode_bound mean 4:2:0; the _mode forms take the
  * sampling (for the header without FEAR_JPEG_ENC_GRAY_RGB, which does not change the file's layout) and are FEAR_TRAIN_ERR_SHAPE or 0
- * for an unknown one.                                                                                                                */
+ * for an unknown one.
+ *
+ * Per-file Huffman tables.  A record whose `flags` have FEAR_JPEG_ENC_OPTIMIZE gets the file libjpeg writes with optimize_coding: its
+ * tables are built from the scan's own symbol counts by T.81 K.2 as jpeg_gen_optimal_table does it (a reserved 257th symbol of
+ * frequency 1; the two smallest non-zero frequencies merged, in a tie the larger symbol first; lengths limited to 16 by Adjust_BITS; the
+ * reserved symbol taken from the longest length in use; symbols sorted by depth, then value; codes by annex C).  All-zero flags are the
+ * record described above, unknown bits FEAR_TRAIN_ERR_SHAPE, and flags changed after fear_jpeg_encode_plan are refused like a changed
+ * sampling.  For such a record the caller passes the header WITHOUT its DHT segments (fear_jpeg_encode_header_flags); they belong
+ * 177 bytes in (gray: 102), behind SOF0, where the device puts the segments it built: DC 0, AC 0 and, but for gray, DC 1, AC 1; DRI and
+ * SOS follow.  The header's length is then a device value; it never exceeds the standard header's, since a table lists the symbols its
+ * scan has.  A call with at least one such record runs two more launches between transform and sizes:
+ *   stats      sizes' grid, one lane per block: the symbols the coder will emit (dummy blocks, ZRL and EOB included, DC differences
+ *              restarting at segment boundaries) counted in LDS per workgroup and added to the image's 4 x 256 uint32 counts with integer
+ *              atomics: the sums do not depend on the order.  The counts stand in front of the image's stream, where the call's one
+ *              memset zeroes them.  Workgroups of plain images return.
+ *   tables     one wave per (image, table): the rule above, each merge two wave-wide searches for the smallest frequency; the image's
+ *              code table, which sizes and write then read in place of the standard one, and the table's DHT segment.
+ * A call without such a record is the memset and the eight launches above, unchanged.  A tree deeper than 32 before limiting is what
+ * libjpeg refuses (JERR_HUFF_CLEN_OVERFLOW): the image's status is FEAR_JPEG_ENC_HUFF_DEPTH, its length 0 and its slot untouched; the
+ * other images are unaffected.  fear_jpeg_encode_bound_flags is the bound of a record with these flags: with per-file tables any code
+ * may be 16 bits long, so a block is at most 16 + 11 + 63 x 26 = 1665 bits, luma or chroma (MCUs of 9990, 6660, 4995 and 1665 bits), and
+ * the header at most the standard one.
+ * fear_jpeg_huff_optimal runs the table stage alone on n histograms of 256 uint32 counts on the device: counts_dev (n, 16) codes per
+ * length, values_dev (n, 256) of which nvalues_dev[i] are written, codes_dev (n, 256) length << 16 | code per symbol (0: no code),
+ * status_dev[i] FEAR_TRAIN_OK or FEAR_JPEG_ENC_HUFF_DEPTH (counts, codes and nvalues zeroed).  Any counts are safe.  n outside
+ * 0..4 x 65535 (the tables of the largest encode call): FEAR_TRAIN_ERR_SHAPE; n == 0 returns FEAR_TRAIN_OK without a launch; a null
+ * pointer with n > 0: FEAR_TRAIN_ERR_NULL.                                                                                        */
 #define FEAR_JPEG_ENC_OVERFLOW 1
+#define FEAR_JPEG_ENC_HUFF_DEPTH 2
+#define FEAR_JPEG_ENC_OPTIMIZE 1u        /* a record's flags: per-file Huffman tables */
 #define FEAR_JPEG_ENC_HEADER_MAX 640
 #define FEAR_JPEG_ENC_GROUP_BLOCKS 256
 #define FEAR_JPEG_ENC_CHUNK_BYTES 4096
@@ -1190,8 +1218,8 @@ typedef struct FearJpegEncImage {
     uint32_t stream_cap;             /* plan: the stream's capacity in bytes; offset 64                                    */
     uint32_t start[4];               /* plan: the image's first workgroup of transform, sizes / write, segments, count / assemble */
     uint32_t sampling;               /* FEAR_JPEG_ENC_420 .. _GRAY, | FEAR_JPEG_ENC_GRAY_RGB; 0: 4:2:0 from RGB; offset 84      */
-    uint32_t plan_sampling;          /* plan: the sampling the plan was made for, so that a later change of it is refused     */
-    uint32_t reserved;
+    uint32_t plan_sampling;          /* plan: the sampling | flags << 16 the plan was made for: a later change is refused     */
+    uint32_t flags;                  /* 0 or FEAR_JPEG_ENC_OPTIMIZE; offset 92                                                 */
 } FearJpegEncImage;
 #ifdef __cplusplus
 static_assert(sizeof(FearJpegEncImage) == 96, "FearJpegEncImage is 96 bytes");
@@ -1204,10 +1232,15 @@ size_t fear_jpeg_encode_bound(int width, int height, int restart_interval);
 int fear_jpeg_encode_header_mode(int width, int height, int quality, int restart_interval, int sampling, uint8_t* out, size_t out_cap,
                                  size_t* out_used);
 size_t fear_jpeg_encode_bound_mode(int width, int height, int restart_interval, int sampling);
+int fear_jpeg_encode_header_flags(int width, int height, int quality, int restart_interval, int sampling, uint32_t flags, uint8_t* out,
+                                  size_t out_cap, size_t* out_used);
+size_t fear_jpeg_encode_bound_flags(int width, int height, int restart_interval, int sampling, uint32_t flags);
 int fear_jpeg_encode_plan(FearJpegEncImage* images, int n);
 size_t fear_jpeg_encode_workspace_bytes(const FearJpegEncImage* images, int n);
 int fear_jpeg_encode_u8(const FearJpegEncImage* images, int n, void* workspace, size_t workspace_bytes, int32_t* length_dev,
                         int32_t* status_dev, void* stream);
+int fear_jpeg_huff_optimal(const uint32_t* freq_dev, int n, uint8_t* counts_dev, uint8_t* values_dev, int32_t* nvalues_dev,
+                           uint32_t* codes_dev, int32_t* status_dev, void* stream);
 
 #ifdef __cplusplus
 }

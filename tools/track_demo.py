@@ -27,6 +27,7 @@ def main():
     ap.add_argument("--quality", type=int, default=90)
     ap.add_argument("--subsampling", default="4:2:0", choices=("4:2:0", "4:2:2", "4:4:4", "gray"),
                     help="the files' layout: 4:4:4 keeps the outline's colour, 4:2:0 (the default) halves its chroma both ways")
+    ap.add_argument("--optimize", action="store_true", help="per-file Huffman tables, built on the device: smaller files, equal pixels")
     ap.add_argument("--thickness", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32, help="frames decoded and encoded per call")
     ap.add_argument("--weights", default=None)
@@ -38,7 +39,7 @@ def main():
         raise SystemExit("the directory needs at least two .jpg frames")
     net = FEARNetHIP(args.weights or DEFAULT_WEIGHTS, device=0, max_batch=8)
     tracker = FEARMultiTracker(net, cuda_id=0, **DEFAULT_TRACKING_CONFIG)
-    decoder, encoder = JpegDecoder(device=0), JpegEncoder(0, quality=args.quality, subsampling=args.subsampling)
+    decoder, encoder = JpegDecoder(device=0), JpegEncoder(0, quality=args.quality, subsampling=args.subsampling, optimize=args.optimize)
     files, started = [], False
     for at in range(0, len(paths), args.batch):
         frames = decoder.decode(paths[at:at + args.batch])
