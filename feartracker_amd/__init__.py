@@ -11,7 +11,8 @@ from .frames import YUVFrame
 from .tracker import FEARTracker, Tracker, TrackingState
 from .multi_tracker import FEARMultiTracker, PendingBoxes, search_rows_host
 from .hip_backend import FEARNetHIP, FearError, load_library, DEFAULT_WEIGHTS, LIB_PATH
-from .jpeg_frames import JpegDecoder, MalformedJPEG, UnsupportedJPEG, jpeg_decode_host, jpeg_info, jpeg_pixels_host
+from .jpeg_frames import (JpegDecoder, MalformedJPEG, UnsupportedJPEG, jpeg_decode_host, jpeg_info, jpeg_pixels_host, jpeg_scaled_shape,
+                          jpeg_scaled_transforms)
 from .jpeg_huffman import (jpeg_entropy_indexed_host, jpeg_entropy_parallel_host, jpeg_entropy_rows_device_host, jpeg_rows_device_host,
                            jpeg_scan_index_host, jpeg_scan_prepare_host, scan_row_sub)
 from .jpeg_progressive import jpeg_to_baseline_host
@@ -26,7 +27,8 @@ __all__ = [
     "FEARMultiTracker", "PendingBoxes", "YUVFrame",
     "FEARNetHIP", "FearError", "load_library", "DEFAULT_WEIGHTS", "LIB_PATH",
     "JpegDecoder", "MalformedJPEG", "UnsupportedJPEG", "jpeg_decode_host", "jpeg_info", "jpeg_entropy_parallel_host", "jpeg_scan_prepare_host",
-    "jpeg_scan_index_host", "jpeg_entropy_indexed_host", "JpegStore", "StoreFull", "plan_decode", "plan_decode_rows", "scan_row_sub", "jpeg_pixels_host",
+    "jpeg_scan_index_host", "jpeg_entropy_indexed_host", "JpegStore", "StoreFull", "plan_decode", "plan_decode_rows", "scan_row_sub", "jpeg_pixels_host", "jpeg_scaled_shape",
+    "jpeg_scaled_transforms",
     "jpeg_to_baseline_host", "jpeg_entropy_rows_device_host", "jpeg_rows_device_host",
     "StoreFrames", "search_rows_host",
     "BestWorstMiner", "draw_boxes", "draw_boxes_host", "miner_host",

@@ -2323,6 +2323,7 @@ int fear_layer_plan_info(long M, int K, int N, size_t ws_bytes, const FearLayerD
 #include "fear_jpeg_entropy.h"
 #include "fear_jpeg_progressive.h"
 #include "fear_jpeg_decode.h"
+#include "fear_jpeg_scaled.h"
 #include "fear_jpeg_huffman.h"
 #include "fear_jpeg_store.h"
 #include "fear_jpeg_encode.h"

@@ -314,17 +314,93 @@ def _upsample_h2v1(c: np.ndarray) -> np.ndarray:
     return np.stack([(3 * c + left + 1) >> 2, (3 * c + right + 2) >> 2], axis=2).reshape(c.shape[0], 2 * c.shape[1])
 
 
-def jpeg_decode_host(data: bytes, progressive: bool = False) -> np.ndarray:
+SCALES = (1, 2, 4, 8)
+
+
+def _check_scale(scale) -> int:
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or int(scale) not in SCALES:
+        raise ValueError(f"scale is one of {SCALES}, not {scale!r}")
+    return int(scale)
+
+
+def jpeg_scaled_shape(height: int, width: int, scale: int) -> Tuple[int, int, int]:
+    """The shape of a frame of `height` x `width` decoded at 1 / `scale`: (ceil(H m / 8), ceil(W m / 8), 3) with m = 8 // scale."""
+    m = 8 // _check_scale(scale)
+    return -(-int(height) * m // 8), -(-int(width) * m // 8), 3
+
+
+def jpeg_scaled_transforms(h: Sequence[int], v: Sequence[int], scale: int) -> List[int]:
+    """The side `ss` of each component's inverse transform at 1 / `scale` (libjpeg's jdmaster.c): it starts at m = 8 // scale and doubles
+    while it is below 8 and the component's plane would still be no larger than the frame on either axis.  A component the frame
+    subsamples therefore takes the next larger transform in place of the upsampling: 4:2:0 chroma 2 m on both axes; 4:2:2 chroma stays at
+    m (its rows are the frame's) and is upsampled horizontally."""
+    m = 8 // _check_scale(scale)
+    h_max, v_max, out = max(h), max(v), []
+    for hc, vc in zip(h, v):
+        ss = m
+        while ss < 8 and (h_max * m) % (hc * ss * 2) == 0 and (v_max * m) % (vc * ss * 2) == 0:
+            ss *= 2
+        out.append(ss)
+    return out
+
+
+def _descale(x: np.ndarray, n: int) -> np.ndarray:
+    return (x + (1 << (n - 1))) >> n
+
+
+def _idct_4x4_pass(x: Dict[int, np.ndarray], n: int) -> List[np.ndarray]:
+    t0 = x[0] << 14
+    t2 = 15137 * x[2] - 6270 * x[6]
+    t10, t12 = t0 + t2, t0 - t2
+    o0 = -1730 * x[7] + 11893 * x[5] - 17799 * x[3] + 8697 * x[1]
+    o2 = -4176 * x[7] - 4926 * x[5] + 7373 * x[3] + 20995 * x[1]
+    return [_descale(t10 + o2, n), _descale(t12 + o0, n), _descale(t12 - o0, n), _descale(t10 - o2, n)]
+
+
+def _idct_2x2_pass(x: Dict[int, np.ndarray], n: int) -> List[np.ndarray]:
+    t10 = x[0] << 15
+    t0 = -5906 * x[7] + 6967 * x[5] - 10426 * x[3] + 29692 * x[1]
+    return [_descale(t10 + t0, n), _descale(t10 - t0, n)]
+
+
+def jpeg_idct_scaled(blocks: np.ndarray, ss: int) -> np.ndarray:
+    """libjpeg's reduced inverse transforms (jidctred.c) on dequantised int64 blocks [..., 8, 8] -> [..., ss, ss], before the level shift:
+    ss 8 is the islow transform, 4 and 2 run columns first and then rows and never read row and column 4 (ss 2: nor 2 and 6), 1 is
+    DESCALE(dc, 3).  64-bit integers, as libjpeg's; the device computes in 32 bits, which agree while |dequantised value| < 2^13 or so."""
+    blocks = np.asarray(blocks, dtype=np.int64)
+    if ss == 8:
+        return jpeg_idct_islow(blocks)
+    if ss == 1:
+        return _descale(blocks[..., :1, :1], 3)
+    one_pass, keep = (_idct_4x4_pass, (0, 1, 2, 3, 5, 6, 7)) if ss == 4 else (_idct_2x2_pass, (0, 1, 3, 5, 7))
+    first, second = (12, 19) if ss == 4 else (13, 20)
+    # columns: out[..., i, c] for the kept columns c
+    cols = one_pass({r: blocks[..., r, :] for r in range(8)}, first)                  # ss arrays [..., 8]: the rows of the intermediate
+    mid = np.stack(cols, axis=-2)                                                     # [..., ss, 8]
+    rows = one_pass({c: mid[..., c] for c in keep}, second)                           # ss arrays [..., ss]
+    return np.stack(rows, axis=-1)
+
+
+def jpeg_decode_host(data: bytes, progressive: bool = False, scale: int = 1) -> np.ndarray:
     """A baseline JPEG file -> uint8 (H, W, 3) RGB, as libjpeg decodes it with its defaults.  Slow; the statement the device is held to.
-    `progressive=True` takes a complete progressive file as well."""
-    return jpeg_pixels_host(*jpeg_coefficients_host(data, progressive))
+    `progressive=True` takes a complete progressive file as well.  `scale` 2, 4 or 8 decodes at 1/2, 1/4 or 1/8 of the size in the DCT
+    domain, as libjpeg's scale_denom (Pillow's `draft`) does: `jpeg_scaled_shape` is the frame's."""
+    scale = _check_scale(scale)
+    return jpeg_pixels_host(*jpeg_coefficients_host(data, progressive), scale=scale)
 
 
-def jpeg_pixels_host(hd: _Header, coef: List[np.ndarray], height: Optional[int] = None) -> np.ndarray:
+def jpeg_pixels_host(hd: _Header, coef: List[np.ndarray], height: Optional[int] = None, scale: int = 1) -> np.ndarray:
     """The pixel stage of `jpeg_decode_host` on coefficients: dequantisation, islow IDCT, fancy upsampling at the true edges, colour.
     `height` (the header's by default) makes it the decode of a BAND image, as `JpegStore.decode_rows` hands one to
     `fear_jpeg_decode_u8`: `coef` holds the blocks of some consecutive MCU rows alone and `height` is the pixel rows they cover, so the
-    edge rules apply at the band's edges."""
+    edge rules apply at the band's edges.
+    `scale` 2, 4 or 8 (m = 8 // scale): component c runs the ss x ss transform of `jpeg_scaled_transforms`, its plane is blocks_h ss x
+    blocks_w ss of which ceil(H v_c ss / (8 v_max)) x ceil(W h_c ss / (8 h_max)) is true, and the only upsampling left is 4:2:2's h2v1 —
+    fancy when m > 1 and the true chroma width is above 2, replication otherwise (libjpeg turns fancy upsampling off at 1/8).  `height`
+    stays the band's FULL-size height."""
+    scale = _check_scale(scale)
+    if scale > 1:
+        return _pixels_scaled(hd, coef, hd.height if height is None else int(height), scale)
     H, W, nf = hd.height if height is None else int(height), hd.width, len(hd.ids)
     planes = []
     for c in range(nf):
@@ -352,8 +428,63 @@ def jpeg_pixels_host(hd: _Header, coef: List[np.ndarray], height: Optional[int] 
     return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
 
 
+def _pixels_scaled(hd: _Header, coef: List[np.ndarray], H: int, scale: int) -> np.ndarray:
+    m, W, nf = 8 // scale, hd.width, len(hd.ids)
+    out_h, out_w, _ = jpeg_scaled_shape(H, W, scale)
+    sizes = jpeg_scaled_transforms(hd.h, hd.v, scale)
+    planes = []
+    for c in range(nf):
+        q, ss = hd.q[hd.tq[c]], sizes[c]
+        nat = np.zeros(coef[c].shape, dtype=np.int64)
+        nat[..., ZIGZAG] = coef[c]
+        bh, bw = coef[c].shape[:2]
+        px = np.clip(jpeg_idct_scaled((nat * q).reshape(bh, bw, 8, 8), ss) + 128, 0, 255)
+        plane = px.transpose(0, 2, 1, 3).reshape(bh * ss, bw * ss)
+        ch, cw = -(-H * hd.v[c] * ss // (hd.v[0] * 8)), -(-W * hd.h[c] * ss // (hd.h[0] * 8))
+        plane = plane[:ch, :cw]                                                    # the true edges
+        if hd.h[0] * m == 2 * hd.h[c] * ss:                                        # half the frame's width (4:2:2 chroma): h2v1
+            plane = _upsample_h2v1(plane) if m > 1 and cw > 2 else np.repeat(plane, 2, axis=1)
+        planes.append(plane[:out_h, :out_w])
+    y = planes[0]
+    if nf == 1:
+        return np.repeat(y[..., None], 3, axis=2).astype(np.uint8)
+    cb, cr = planes[1] - 128, planes[2] - 128
+    r = y + ((91881 * cr + 32768) >> 16)
+    g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
+    b = y + ((116130 * cb + 32768) >> 16)
+    return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
+
+
 # ------------------------------------------------------------------------------------------------------------------------ the product
 Item = Union[bytes, bytearray, memoryview, str, os.PathLike]
+
+
+def _frame_size(data: bytes) -> Optional[Tuple[int, int]]:
+    """(height, width) of the first frame header of any kind, or None where the segments cannot be walked that far."""
+    p, n = 2, len(data)
+    while p + 4 <= n and data[p] == 0xFF:
+        m = data[p + 1]
+        if m == 0xFF:
+            p += 1
+            continue
+        if m == 0x01 or 0xD0 <= m <= 0xD9:
+            p += 2
+            continue
+        L = (data[p + 2] << 8) | data[p + 3]
+        if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            return ((data[p + 5] << 8) | data[p + 6], (data[p + 7] << 8) | data[p + 8]) if p + 9 <= n else None
+        if m == 0xDA or L < 2:
+            return None
+        p += 2 + L
+    return None
+
+
+def _check_fallback_shape(index: int, data: bytes, px: np.ndarray, scale: int) -> None:
+    """At a scale the fallback decodes at that scale too: its pixels have the scaled shape of the file's frame header."""
+    size = _frame_size(data)
+    if size is not None and tuple(px.shape) != jpeg_scaled_shape(size[0], size[1], scale):
+        raise ValueError(f"item {index}: the fallback returned {tuple(px.shape)} where scale={scale} of a {size[0]} x {size[1]} file is "
+                         f"{jpeg_scaled_shape(size[0], size[1], scale)}")
 
 
 def _raise_as_python(data: bytes, rc: int, progressive: bool = False):
@@ -501,7 +632,7 @@ class JpegDecoder:
                 except MalformedJPEG as exc:
                     raise MalformedJPEG(f"item {index}: {exc}") from None
 
-    def _decode_device(self, blobs: List[bytes], fallback) -> List:
+    def _decode_device(self, blobs: List[bytes], fallback, scale: int = 1) -> List:
         prepared = list(self._pool.map(self._prepare, blobs))
         jpegs, raw = [], {}
         for i, (data, res) in enumerate(zip(blobs, prepared)):
@@ -511,6 +642,8 @@ class JpegDecoder:
                 px = np.ascontiguousarray(fallback(data))
                 if px.ndim != 3 or px.shape[2] != 3 or px.dtype != np.uint8:
                     raise ValueError("the fallback must return uint8 (H, W, 3)")
+                if scale > 1:
+                    _check_fallback_shape(i, data, px, scale)
                 raw[i] = px
             else:
                 _raise_as_python(data, res, self.progressive)
@@ -527,10 +660,10 @@ class JpegDecoder:
         for g, group in enumerate(groups):
             if len(group) > 65535:
                 raise ValueError("at most 65535 JPEG files per call")
-            self._decode_group(blobs, prepared, group, raw if g == 0 else {}, frames)
+            self._decode_group(blobs, prepared, group, raw if g == 0 else {}, frames, scale)
         return frames
 
-    def _decode_group(self, blobs, prepared, group, raw, frames) -> None:
+    def _decode_group(self, blobs, prepared, group, raw, frames, scale: int = 1) -> None:
         """One upload, fear_jpeg_huffman over the group's device-path images and fear_jpeg_decode_u8 over all of them.  The layout of
         `decode`'s host mode with the scans added; host mode keeps its own code so that its bytes and launches stay what they were."""
         import torch
@@ -552,7 +685,8 @@ class JpegDecoder:
             rec.plane_offset = plane_at
             plane_at += int(info.total_blocks) * 64
             prefix[0, k + 1] = prefix[0, k] + -(-int(info.total_blocks) // FEAR_JPEG_GROUP_BLOCKS)
-            prefix[1, k + 1] = prefix[1, k] + -(-info.width * info.height // FEAR_JPEG_GROUP_PIXELS)
+            sh, sw, _ = jpeg_scaled_shape(info.height, info.width, scale)          # the frame's size: the file's at scale 1
+            prefix[1, k + 1] = prefix[1, k] + -(-sw * sh // FEAR_JPEG_GROUP_PIXELS)
             if len(prepared[i]) == 4:
                 d = place[k]
                 ctypes.memmove(ctypes.byref(scans[d]), ctypes.byref(prepared[i][3]), ctypes.sizeof(FearJpegScan))
@@ -566,7 +700,7 @@ class JpegDecoder:
                 stage.add(f"coef{k}", prepared[i][1])
                 stage.add(f"start{k}", prepared[i][2])
             out_at.append(out_bytes)
-            out_bytes += -(-info.width * info.height * 3 // 16) * 16
+            out_bytes += -(-sw * sh * 3 // 16) * 16
         for i, px in raw.items():
             stage.add(f"raw{i}", px)
         table = np.zeros(-(-prefix.nbytes // 16) * 16 + ctypes.sizeof(records), dtype=np.uint8)
@@ -610,8 +744,12 @@ class JpegDecoder:
             if n:
                 ws_bytes = self._lib.fear_jpeg_decode_workspace_bytes(infos, n)
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-                launch(self._lib, "fear_jpeg_decode_u8", records, n, ctypes.c_void_p(base + stage.sections["table"][0]),
-                       ctypes.c_void_p(ws.data_ptr()), ws_bytes, stream)
+                if scale == 1:
+                    launch(self._lib, "fear_jpeg_decode_u8", records, n, ctypes.c_void_p(base + stage.sections["table"][0]),
+                           ctypes.c_void_p(ws.data_ptr()), ws_bytes, stream)
+                else:
+                    launch(self._lib, "fear_jpeg_decode_scaled_u8", records, n, ctypes.c_void_p(base + stage.sections["table"][0]), scale,
+                           ctypes.c_void_p(ws.data_ptr()), ws_bytes, stream)
             if nd:
                 verdict = torch.empty(nd, dtype=torch.int32, pin_memory=True)
                 verdict.copy_(status[:nd], non_blocking=True)
@@ -619,14 +757,21 @@ class JpegDecoder:
                 event.record()
                 self._pending = (self._pending + [(event, verdict, [(group[k], blobs[group[k]]) for k in on_device])])[-self.PENDING_CALLS:]
         for k, i in enumerate(group):
-            h, w = records[k].height, records[k].width
+            h, w, _ = jpeg_scaled_shape(records[k].height, records[k].width, scale)
             frames[i] = out[out_at[k]:out_at[k] + h * w * 3].view(h, w, 3)
         for i, px in raw.items():
             at = stage.sections[f"raw{i}"][0]
             frames[i] = dev[at:at + px.nbytes].view(px.shape)
 
-    def decode(self, items: Sequence[Item], fallback: Optional[Callable[[bytes], np.ndarray]] = None, check: bool = False) -> List:
+    def decode(self, items: Sequence[Item], fallback: Optional[Callable[[bytes], np.ndarray]] = None, check: bool = False,
+               scale: int = 1) -> List:
+        """`scale` 2, 4 or 8 decodes every file of the call at 1/2, 1/4 or 1/8 of its size in the DCT domain, as libjpeg's scale_denom
+        and Pillow's `draft` do (`jpeg_decode_host(scale=)` is the statement, `jpeg_scaled_shape` the frames' shape): the coefficient
+        stage is untouched, in both entropy modes and with `progressive=True`, and `fear_jpeg_decode_scaled_u8` takes the place of
+        `fear_jpeg_decode_u8`.  A `fallback`'s pixels must then have the scaled shape (ValueError naming the item).  Another value of
+        `scale` is a ValueError before anything is parsed."""
         import torch
+        scale = _check_scale(scale)
         from .train_abi import (FEAR_JPEG_GROUP_BLOCKS, FEAR_JPEG_GROUP_PIXELS, FearJpegImage, FearJpegInfo, launch)
         from .train_data.staging import Staging
         blobs = []
@@ -640,7 +785,7 @@ class JpegDecoder:
         if n_items == 0:
             return []
         if self.entropy == "device":
-            frames = self._decode_device(blobs, fallback)
+            frames = self._decode_device(blobs, fallback, scale)
             if check:
                 self.check()
             return frames
@@ -654,6 +799,8 @@ class JpegDecoder:
                 px = np.ascontiguousarray(fallback(data))
                 if px.ndim != 3 or px.shape[2] != 3 or px.dtype != np.uint8:
                     raise ValueError("the fallback must return uint8 (H, W, 3)")
+                if scale > 1:
+                    _check_fallback_shape(i, data, px, scale)
                 raw[i] = px
             else:
                 _raise_as_python(data, res, self.progressive)
@@ -673,11 +820,12 @@ class JpegDecoder:
             rec.plane_offset = plane_at
             plane_at += int(info.total_blocks) * 64
             prefix[0, k + 1] = prefix[0, k] + -(-int(info.total_blocks) // FEAR_JPEG_GROUP_BLOCKS)
-            prefix[1, k + 1] = prefix[1, k] + -(-info.width * info.height // FEAR_JPEG_GROUP_PIXELS)
+            sh, sw, _ = jpeg_scaled_shape(info.height, info.width, scale)          # the frame's size: the file's at scale 1
+            prefix[1, k + 1] = prefix[1, k] + -(-sw * sh // FEAR_JPEG_GROUP_PIXELS)
             stage.add(f"coef{k}", coef)
             stage.add(f"start{k}", start)
             out_at.append(out_bytes)
-            out_bytes += -(-info.width * info.height * 3 // 16) * 16
+            out_bytes += -(-sw * sh * 3 // 16) * 16
         for i, px in raw.items():
             stage.add(f"raw{i}", px)
         table = np.zeros(-(-prefix.nbytes // 16) * 16 + ctypes.sizeof(records), dtype=np.uint8)
@@ -700,11 +848,16 @@ class JpegDecoder:
             if n:
                 ws_bytes = self._lib.fear_jpeg_decode_workspace_bytes(infos, n)
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-                launch(self._lib, "fear_jpeg_decode_u8", records, n, ctypes.c_void_p(base + stage.sections["table"][0]),
-                       ctypes.c_void_p(ws.data_ptr()), ws_bytes, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                if scale == 1:
+                    launch(self._lib, "fear_jpeg_decode_u8", records, n, ctypes.c_void_p(base + stage.sections["table"][0]),
+                           ctypes.c_void_p(ws.data_ptr()), ws_bytes, stream)
+                else:
+                    launch(self._lib, "fear_jpeg_decode_scaled_u8", records, n, ctypes.c_void_p(base + stage.sections["table"][0]), scale,
+                           ctypes.c_void_p(ws.data_ptr()), ws_bytes, stream)
         frames: List = [None] * n_items
         for k, i in enumerate(jpegs):
-            h, w = records[k].height, records[k].width
+            h, w, _ = jpeg_scaled_shape(records[k].height, records[k].width, scale)
             frames[i] = out[out_at[k]:out_at[k] + h * w * 3].view(h, w, 3)
         for i, px in raw.items():
             at = stage.sections[f"raw{i}"][0]

@@ -16,7 +16,11 @@ unchanged `fear_jpeg_decode_u8` on the band as an image of its own (DESIGN.md se
 A tracker knows the rows of its next search window only on the device.  `decode_rows` therefore also takes `rows` as a device tensor that
 only kernels read: `plan_decode`'s full-image plan, `fear_jpeg_huffman_indexed_rows_dev` and `fear_jpeg_decode_u8_rows_dev`, whose
 workgroups outside the band return early — for which `add` keeps each file's row table on the device as well ("Rows
-from the device").  `StoreFrames(store, ids)` names a sequence of frames kept in a store, for `SequenceValidator`."""
+from the device").  `StoreFrames(store, ids)` names a sequence of frames kept in a store, for `SequenceValidator`.
+
+`decode`, `decode_rows` (rows on the host), `shape` and the two plans take `scale` 2, 4 or 8: the frames at 1/2, 1/4 or 1/8 size, decoded
+in the DCT domain as libjpeg's scale_denom does, with `fear_jpeg_decode_scaled_u8` in place of `fear_jpeg_decode_u8` behind the same
+Huffman stage ("Reduced-size decoding")."""
 from __future__ import annotations
 
 import ctypes
@@ -25,7 +29,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import jpeg_frames
-from .jpeg_frames import ERR_UNSUPPORTED, Item, JpegDecoder, MalformedJPEG, UnsupportedJPEG, _raise_as_python
+from .jpeg_frames import ERR_UNSUPPORTED, Item, JpegDecoder, MalformedJPEG, UnsupportedJPEG, _check_scale, _raise_as_python
 from .jpeg_huffman import SUBSEQ_DTYPE, _check_subsequence_bytes, scan_row_sub
 
 KIND_SCAN, KIND_PIXELS = 0, 1
@@ -51,7 +55,7 @@ def _exclusive(a):
     return out
 
 
-def plan_decode(columns: np.ndarray, ids, workspace_limit: int, max_group: int = 65535) -> List[dict]:
+def plan_decode(columns: np.ndarray, ids, workspace_limit: int, max_group: int = 65535, scale: int = 1) -> List[dict]:
     """The host's share of `JpegStore.decode` but the records: a pure function of the mirror's integer columns (COLUMNS, one row per
     entry) and the ids, any order, repeats allowed.  The call is cut into groups of consecutive positions lo..hi as JpegDecoder cuts it:
     a group takes positions while the dense coefficients of its "scan" entries (128 bytes per block) stay within `workspace_limit`, at
@@ -61,12 +65,16 @@ def plan_decode(columns: np.ndarray, ids, workspace_limit: int, max_group: int =
         coef_offset   values from the group's coefficient buffer to each image's 64 total_blocks; `values` their sum
         plane_offset  bytes from the workspace to each image's planes, multiples of 16; `workspace_bytes` what the pixel stage needs
         most          the largest total_blocks
-    and over all its positions `out_offset`, multiples of 16, and `out_bytes`.  No loop over the files: gathers and prefix sums."""
+    and over all its positions `out_offset`, multiples of 16, and `out_bytes`.  No loop over the files: gathers and prefix sums.
+    At `scale` 2, 4 or 8 the frames are the scaled ones (`jpeg_scaled_shape`): `pixel_prefix` counts scaled pixels, as
+    fear_jpeg_decode_scaled_u8 reads it, and `out_offset` and `out_bytes` lay out scaled frames; the blocks, the coefficients and the
+    workspace are what they are at scale 1."""
+    m = 8 // _check_scale(scale)
     ids = np.asarray(ids, dtype=np.int64).reshape(-1)
     rows = columns[ids]
     is_scan = rows["kind"] == KIND_SCAN
     blocks = rows["total_blocks"].astype(np.int64)
-    pixels = rows["H"].astype(np.int64) * rows["W"].astype(np.int64)
+    pixels = -(-rows["H"].astype(np.int64) * m // 8) * -(-rows["W"].astype(np.int64) * m // 8)
     need = _exclusive(np.where(is_scan, 128 * blocks, 0))
     groups, lo, n = [], 0, ids.size
     while lo < n:                                                       # one turn per group
@@ -95,7 +103,8 @@ def scan_columns(col, info, n_seg: int, n_sub: int, row_at: int) -> None:
     col["nslots"], col["row_at"] = (info.h[0] * info.v[0] + 2 if info.components == 3 else 1), row_at
 
 
-def plan_decode_rows(columns: np.ndarray, row_sub: np.ndarray, ids, rows, workspace_limit: int, max_group: int = 65535) -> List[dict]:
+def plan_decode_rows(columns: np.ndarray, row_sub: np.ndarray, ids, rows, workspace_limit: int, max_group: int = 65535,
+                     scale: int = 1) -> List[dict]:
     """The host's share of `JpegStore.decode_rows`, as `plan_decode` a pure function without a loop over the files: of the mirror's
     columns, the ragged row table (`columns["row_at"]` is where an entry's mcus_y + 1 values begin in `row_sub`), the ids and `rows`,
     (n, 2) pixel rows [y0, y1) per position, clipped to [0, H].  The band of a "scan" position is the MCU rows a .. b),
@@ -109,21 +118,28 @@ def plan_decode_rows(columns: np.ndarray, row_sub: np.ndarray, ids, rows, worksp
         block_prefix, pixel_prefix, coef_offset, values, plane_offset, workspace_bytes, most
                               plan_decode's, of the band as an image of its own
         band_out              bytes from the position's frame to the band's first row, 3 W band_y0
-    and over all its positions `out_offset` and `out_bytes`: whole frames, as plan_decode's."""
+    and over all its positions `out_offset` and `out_bytes`: whole frames, as plan_decode's.
+    At `scale` 2, 4 or 8 (m = 8 // scale) `rows` are rows of the SCALED frame, clipped to its height ceil(H m / 8); a scaled MCU row is
+    mcu_h m / 8 = v m of them, and no supported mode upsamples vertically at a scale, so there is no halo.  `band_height` stays the
+    band's FULL-size height, what the record of fear_jpeg_decode_scaled_u8 holds; `band_y0`, `band_out`, `pixel_prefix`, `out_offset` and
+    `out_bytes` are the scaled frame's."""
+    m = 8 // _check_scale(scale)
     ids = np.asarray(ids, dtype=np.int64).reshape(-1)
     rows = np.asarray(rows, dtype=np.int64).reshape(-1, 2)
     col = columns[ids]
     is_scan = col["kind"] == KIND_SCAN
-    H, W, mcu_h = col["H"].astype(np.int64), col["W"].astype(np.int64), np.maximum(col["mcu_h"].astype(np.int64), 1)
+    full_h, full_mcu_h = col["H"].astype(np.int64), np.maximum(col["mcu_h"].astype(np.int64), 1)
+    H, W, mcu_h = -(-full_h * m // 8), -(-col["W"].astype(np.int64) * m // 8), np.maximum(full_mcu_h * m // 8, 1)
     mcus_y = col["mcus_y"].astype(np.int64)
     y0, y1 = np.clip(rows[:, 0], 0, H), np.clip(rows[:, 1], 0, H)
     some = is_scan & (y0 < y1)
-    halo = col["halo"].astype(np.int64)
+    halo = col["halo"].astype(np.int64) if m == 8 else np.zeros(ids.size, dtype=np.int64)
     a = np.where(some, np.maximum(y0 // mcu_h - halo, 0), 0)
     b = np.where(some, np.minimum(-(-y1 // mcu_h) + halo, mcus_y), 0)
     blocks = (b - a) * col["mcus_x"].astype(np.int64) * col["nslots"].astype(np.int64)
     band_y0 = a * mcu_h
     band_h = np.minimum(b * mcu_h, H) - band_y0
+    band_full = np.minimum(b * full_mcu_h, full_h) - a * full_mcu_h
     n_sub = col["n_sub"].astype(np.int64)
     at = np.where(some, col["row_at"], 0)
     first = np.where(some, row_sub[at + a].astype(np.int64), 0) if row_sub.size else np.zeros(ids.size, np.int64)
@@ -145,7 +161,7 @@ def plan_decode_rows(columns: np.ndarray, row_sub: np.ndarray, ids, rows, worksp
             sub0=first[pick].astype(np.uint32), sub_count=count[pick].astype(np.uint32),
             sub_prefix=_exclusive(-(-count[pick] // LANES)).astype(np.uint32),
             mcu_row0=a[pick].astype(np.uint32), mcu_rows=(b - a)[pick].astype(np.uint32),
-            band_y0=band_y0[pick], band_height=band_h[pick].astype(np.int32), band_out=3 * W[pick] * band_y0[pick],
+            band_y0=band_y0[pick], band_height=band_full[pick].astype(np.int32), band_out=3 * W[pick] * band_y0[pick],
             block_prefix=_exclusive(-(-bl // 32)).astype(np.uint32),
             pixel_prefix=_exclusive(-(-(band_h[pick] * W[pick]) // 256)).astype(np.uint32),
             coef_offset=dense[:-1].astype(np.uint64), values=int(dense[-1]),
@@ -241,7 +257,7 @@ class JpegStore:
 
     def borders(self, ids):
         """(len(ids), 3) uint8 on the device: `fear_frame_border_u8` of each file's full decode, computed once in `add` — what
-        `TrainPairBuilder.build(..., borders=)` takes.  A gather on the current stream; the ids go up non-blocking, it never waits."""
+        `TrainPairBuilder.build(..., borders=)` takes.  It stays the FULL-size decode's colour whatever `scale` the frames are decoded at.  A gather on the current stream; the ids go up non-blocking, it never waits."""
         import torch
         ids = self._checked(ids)
         with torch.cuda.device(self.device):
@@ -253,10 +269,17 @@ class JpegStore:
             self._pinned = self._pinned[-1:] + [pinned]
             return self._border.index_select(0, index)
 
-    def shape(self, ids) -> np.ndarray:
-        """(len(ids), 2) int32: height and width."""
+    def shape(self, ids, scale: int = 1) -> np.ndarray:
+        """(len(ids), 2) int32: height and width, of the frames `decode(ids, scale=scale)` returns."""
+        m = 8 // _check_scale(scale)
         rows = self._columns[self._checked(ids)]
-        return np.stack([rows["H"], rows["W"]], axis=1)
+        return np.stack([-(-rows["H"] * m // 8), -(-rows["W"] * m // 8)], axis=1).astype(np.int32)
+
+    def _scan_only(self, ids: np.ndarray, scale: int) -> None:
+        """At a scale every id is a "scan" entry: decoded pixels cannot be decoded again."""
+        kept = np.flatnonzero(self._columns["kind"][ids] == KIND_PIXELS)
+        if scale > 1 and kept.size:
+            raise UnsupportedJPEG(f"id {int(ids[kept[0]])} is kept as decoded pixels, which scale={scale} cannot decode")
 
     def _checked(self, ids) -> np.ndarray:
         ids = np.asarray(ids, dtype=np.int64).reshape(-1)
@@ -560,12 +583,17 @@ class JpegStore:
         return self._frame_borders(frames, stream)
 
     # ----------------------------------------------------------------------------------------------------------------------- decode
-    def decode(self, ids, check: bool = False) -> List:
+    def decode(self, ids, check: bool = False, scale: int = 1) -> List:
+        """`scale` 2, 4 or 8: the frames at 1/2, 1/4 or 1/8 size (`shape(ids, scale)`), byte for byte `JpegDecoder.decode(scale=)`'s and
+        libjpeg's: the same plan and Huffman stage, `fear_jpeg_decode_scaled_u8` for the pixels.  An id kept as pixels is then an
+        `UnsupportedJPEG` naming it, another `scale` a ValueError, both before any launch."""
+        scale = _check_scale(scale)
         ids = self._checked(ids)
+        self._scan_only(ids, scale)
         frames: List = [None] * ids.size
         self._pending = self._pending[-self.PENDING_CALLS:]              # of earlier calls; every group of this call is kept
-        for plan in plan_decode(self._columns, ids, self.workspace_limit):
-            self._decode_group(ids, plan, frames)
+        for plan in plan_decode(self._columns, ids, self.workspace_limit, scale=scale):
+            self._decode_group(ids, plan, frames, scale=scale)
         if check:
             self.check()
         return frames
@@ -583,7 +611,7 @@ class JpegStore:
             self.check()
         return frames
 
-    def _decode_group(self, ids: np.ndarray, plan: dict, frames: List, rows=None) -> None:
+    def _decode_group(self, ids: np.ndarray, plan: dict, frames: List, rows=None, scale: int = 1) -> None:
         """One group of `decode`; with `rows`, the call's device tensor, one group of `decode_rows` with the rows on the device."""
         import torch
         from . import train_abi as abi
@@ -636,8 +664,13 @@ class JpegStore:
                 if rows is None:
                     abi.launch(self._lib, "fear_jpeg_huffman_indexed", ctypes.c_void_p(indexed.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr()),
                                ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(status.data_ptr()), self.subsequence_bytes, stream)
-                    abi.launch(self._lib, "fear_jpeg_decode_u8", ctypes.c_void_p(images.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr() + at_table),
-                               ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"], stream)
+                    if scale == 1:
+                        abi.launch(self._lib, "fear_jpeg_decode_u8", ctypes.c_void_p(images.ctypes.data), nd,
+                                   ctypes.c_void_p(dev.data_ptr() + at_table), ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"], stream)
+                    else:
+                        abi.launch(self._lib, "fear_jpeg_decode_scaled_u8", ctypes.c_void_p(images.ctypes.data), nd,
+                                   ctypes.c_void_p(dev.data_ptr() + at_table), scale, ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"],
+                                   stream)
                 else:                                                    # the group's rows: a slice, or a gather on the device; no wait
                     mine = rows[lo:hi] if whole else rows.index_select(0, dev[at_pick:].view(torch.int64))
                     mine = mine.contiguous()
@@ -653,14 +686,15 @@ class JpegStore:
                 event.record()
                 self._pending.append((event, verdict, lo + scan, sids))
             rows = self._columns[group]
-            sizes = 3 * rows["H"].astype(np.int64) * rows["W"]
+            high, wide = -(-rows["H"].astype(np.int64) * (8 // scale) // 8), -(-rows["W"].astype(np.int64) * (8 // scale) // 8)
+            sizes = 3 * high * wide
             for k in np.flatnonzero(rows["kind"] == KIND_PIXELS):        # the entries kept as pixels: a copy, never an alias
                 out[out_offset[k]:out_offset[k] + sizes[k]].copy_(self._pixels[int(group[k])].view(-1), non_blocking=True)
-        for k, (at, size, h, w) in enumerate(zip(out_offset.tolist(), sizes.tolist(), rows["H"].tolist(), rows["W"].tolist())):
+        for k, (at, size, h, w) in enumerate(zip(out_offset.tolist(), sizes.tolist(), high.tolist(), wide.tolist())):
             frames[lo + k] = out[at:at + size].view(h, w, 3)
 
     # ------------------------------------------------------------------------------------------------------------------ decode_rows
-    def decode_rows(self, ids, rows=None, check: bool = False) -> List:
+    def decode_rows(self, ids, rows=None, check: bool = False, scale: int = 1) -> List:
         """`decode` for the rows a consumer reads.  `rows` is (len(ids), 2) integers, the pixel rows [y0, y1) per position, clipped to
         [0, H]; the result is what `decode` returns — private uint8 (H, W, 3) tensors of the FULL frame shape — of which only the rows
         [y0, y1) are defined: they are byte for byte `decode`'s.  ALL OTHER ROWS HOLD UNSPECIFIED BYTES (a row that is never read costs
@@ -681,24 +715,35 @@ class JpegStore:
         each group taking its slice of `rows` by device indexing with indices the host knows); the work is saved in the kernels:
         `fear_jpeg_huffman_indexed_rows_dev` runs only the lanes of the band's subsequences and `fear_jpeg_decode_u8_rows_dev` only the
         band's blocks and the window's pixels, and a workgroup outside them returns after a few loads.  A CUDA tensor of another
-        shape, dtype or device is a ValueError before any launch (a CPU tensor is host rows, as any array)."""
+        shape, dtype or device is a ValueError before any launch (a CPU tensor is host rows, as any array).
+
+        `scale` 2, 4 or 8, for rows given on the HOST: `rows` are rows of the scaled frame (`shape(ids, scale)`), the frames have that
+        shape and the rows [y0, y1) are byte for byte `decode(ids, scale=scale)`'s.  The band is the MCU rows that cover them — a scaled
+        MCU row is v m pixel rows, m = 8 // scale — without a halo: at a scale no supported mode upsamples vertically.  The band goes
+        through `fear_jpeg_decode_scaled_u8` as an image of its own: the record's height is the band's full-size height and `out` its
+        first scaled row.  An id kept as pixels is an `UnsupportedJPEG`; `rows` on the device with `scale` > 1 is a ValueError (out of
+        scope)."""
+        scale = _check_scale(scale)
         if rows is None:
-            return self.decode(ids, check=check)
+            return self.decode(ids, check=check, scale=scale)
         ids = self._checked(ids)
         if type(rows).__module__.split(".")[0] == "torch" and rows.is_cuda:         # (a CPU tensor is host rows, as before)
+            if scale > 1:
+                raise ValueError("decode_rows takes rows on the device at scale=1 only")
             return self._decode_rows_device(ids, rows, check)
+        self._scan_only(ids, scale)
         rows = np.asarray(rows)
         if rows.shape != (ids.size, 2) or not np.issubdtype(rows.dtype, np.integer):
             raise ValueError(f"rows must be ({ids.size}, 2) integers, one [y0, y1) per id")
         frames: List = [None] * ids.size
         self._pending = self._pending[-self.PENDING_CALLS:]
-        for plan in plan_decode_rows(self._columns, self._row_sub, ids, rows, self.workspace_limit):
-            self._decode_rows_group(ids, plan, frames)
+        for plan in plan_decode_rows(self._columns, self._row_sub, ids, rows, self.workspace_limit, scale=scale):
+            self._decode_rows_group(ids, plan, frames, scale)
         if check:
             self.check()
         return frames
 
-    def _decode_rows_group(self, ids: np.ndarray, plan: dict, frames: List) -> None:
+    def _decode_rows_group(self, ids: np.ndarray, plan: dict, frames: List, scale: int = 1) -> None:
         import torch
         from . import train_abi as abi
         lo, hi, scan = plan["lo"], plan["hi"], plan["scan"]
@@ -746,18 +791,23 @@ class JpegStore:
                 self.last_upload_bytes = pinned.numel()
                 abi.launch(self._lib, "fear_jpeg_huffman_indexed_rows", ctypes.c_void_p(indexed.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr()),
                            ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(status.data_ptr()), self.subsequence_bytes, stream)
-                abi.launch(self._lib, "fear_jpeg_decode_u8", ctypes.c_void_p(images.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr() + at_table),
-                           ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"], stream)
+                if scale == 1:
+                    abi.launch(self._lib, "fear_jpeg_decode_u8", ctypes.c_void_p(images.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr() + at_table),
+                               ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"], stream)
+                else:
+                    abi.launch(self._lib, "fear_jpeg_decode_scaled_u8", ctypes.c_void_p(images.ctypes.data), nd,
+                               ctypes.c_void_p(dev.data_ptr() + at_table), scale, ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"], stream)
                 verdict = torch.empty(nd, dtype=torch.int32, pin_memory=True)
                 verdict.copy_(status, non_blocking=True)
                 event = torch.cuda.Event()
                 event.record()
                 self._pending.append((event, verdict, lo + scan, sids))
             cols = self._columns[group]
-            sizes = 3 * cols["H"].astype(np.int64) * cols["W"]
+            high, wide = -(-cols["H"].astype(np.int64) * (8 // scale) // 8), -(-cols["W"].astype(np.int64) * (8 // scale) // 8)
+            sizes = 3 * high * wide
             for k in np.flatnonzero(cols["kind"] == KIND_PIXELS):        # the entries kept as pixels: a whole copy, never an alias
                 out[out_offset[k]:out_offset[k] + sizes[k]].copy_(self._pixels[int(group[k])].view(-1), non_blocking=True)
-        for k, (at, size, h, w) in enumerate(zip(out_offset.tolist(), sizes.tolist(), cols["H"].tolist(), cols["W"].tolist())):
+        for k, (at, size, h, w) in enumerate(zip(out_offset.tolist(), sizes.tolist(), high.tolist(), wide.tolist())):
             frames[lo + k] = out[at:at + size].view(h, w, 3)
 
     def check(self) -> None:

@@ -111,6 +111,7 @@ TRAIN_SYMBOLS = {
     # the band of rows taken from device memory (JpegStore.decode_rows with a device tensor)
     "fear_jpeg_huffman_indexed_rows_dev": ([_P, _i, _P, _P, _P, _P, _i, _P], _i),
     "fear_jpeg_decode_u8_rows_dev": ([_P, _i, _P, _P, _P, _sz, _P], _i),
+    "fear_jpeg_decode_scaled_u8": ([_P, _i, _P, _i, _P, _sz, _P], _i),
     # the colour stage's members that are no lookup table (FearColourOp below)
     "fear_colour_u8": ([_P, _i, _i, _i, _P, _P, _P, _P], _i),
     # ISONoise, RandomRain and RandomShadow of the photometric stage (FearHlsOp below)

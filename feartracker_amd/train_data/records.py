@@ -140,4 +140,16 @@ def _pairs_array(pairs) -> np.ndarray:
     return p
 
 
-__all__ = [name for name in dir() if name.isupper()] + ["PhotoParams", "TrainPairParams", "TrainBatch"]     # (every constant above)
+def scale_pairs(pairs, scale: int) -> np.ndarray:
+    """A (B, 11) pair table for frames decoded at 1 / `scale` (`JpegStore.decode(ids, scale=)`, `decode_rows(..., scale=)`): a float64
+    copy with the template box and the search box (x, y, w, h each) divided by `scale`, the frame indices and the presence as they are.
+    `frame_rows`, `draw` and `build` then run unchanged on the smaller frames."""
+    from ..jpeg_frames import _check_scale
+    scale = _check_scale(scale)
+    p = _pairs_array(pairs).copy()
+    p[:, 1:5] /= scale
+    p[:, 6:10] /= scale
+    return p
+
+
+__all__ = [name for name in dir() if name.isupper()] + ["PhotoParams", "TrainPairParams", "TrainBatch", "scale_pairs"]     # (every constant above)

@@ -723,6 +723,23 @@ int fear_jpeg_decode_u8(const FearJpegImage* images, int n, const uint32_t* grou
 int fear_jpeg_decode_u8_rows_dev(const FearJpegImage* images, int n, const uint32_t* group_start, const int32_t* rows_dev, void* workspace,
                                  size_t workspace_bytes, void* stream);
 size_t fear_jpeg_decode_workspace_bytes(const FearJpegInfo* infos, int n);
+/* fear_jpeg_decode_u8 at 1 / scale of the size, scale 2, 4 or 8, as libjpeg decodes with scale_denom (Pillow's Image.draft): two
+ * launches whatever n is.  With m = 8 / scale, `out` is the SCALED frame, (ceil(height m / 8), ceil(width m / 8), 3); width, height and
+ * the sampling of a record stay the file's.  Component c runs an ss x ss inverse transform (jidctred.c: 4 x 4, 2 x 2, 1 x 1; ss == 8 is
+ * islow): ss starts at m and doubles while ss < 8 and (h_max m) % (h_c ss 2) == 0 and (v_max m) % (v_c ss 2) == 0 — luma m; 4:2:0 chroma
+ * 2 m, and no upsampling; 4:2:2 chroma m, upsampled horizontally by the (2, 1) rule above on its true width ceil(width m / 16) when
+ * m > 1 and that width is above 2, replicated otherwise (libjpeg turns fancy upsampling off at 1/8).  Dequantisation, + 128, clamp and
+ * colour are fear_jpeg_decode_u8's.  The transforms run in 32-bit integers where libjpeg uses `long`: equal while the dequantised
+ * coefficients stay within +-2^13, as an encoder's do.
+ * The table is fear_jpeg_decode_u8's: its first prefix table is the same (32 blocks per workgroup), the second counts SCALED pixels,
+ * ceil(ceil(height m / 8) ceil(width m / 8) / FEAR_JPEG_GROUP_PIXELS).  An image's planes lie one after another at plane_offset, ss ss
+ * bytes per block: never more than the 64 bytes per block of fear_jpeg_decode_workspace_bytes, which stays the bound to allocate and
+ * is what the call checks.  A band of MCU rows is decoded as fear_jpeg_decode_u8 decodes one: `height` the band's full-size height,
+ * `out` at the band's first scaled row.
+ * FEAR_TRAIN_ERR_SHAPE: a scale other than 2, 4 or 8; every other check is fear_jpeg_decode_u8's; n == 0 returns FEAR_TRAIN_OK
+ * without a launch.  No atomics, bounded loops only, a block reads at most 64 stored values.                                          */
+int fear_jpeg_decode_scaled_u8(const FearJpegImage* images, int n, const uint32_t* group_start, int scale, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 /* ---- the Huffman stage on the device (jpeg_huffman.jpeg_entropy_parallel_host restates it in Python, step for
  * step).  A baseline scan has no index, but Huffman streams re-synchronise by themselves: the self-synchronising parallel decode of
