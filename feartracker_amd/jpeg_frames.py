@@ -14,7 +14,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from .train_data.jpeg import _jpeg_upsample, jpeg_idct_islow
+from .train_data.jpeg import _jpeg_upsample, _jpeg_ycc_to_rgb, jpeg_idct_islow
 
 MAX_SIDE = 8192
 DEVICE_SCAN_MAX = 16 << 20                # include/fear_train.h FEAR_JPEG_DEVICE_SCAN_MAX: a longer restart segment is decoded on the host
@@ -399,39 +399,9 @@ def jpeg_pixels_host(hd: _Header, coef: List[np.ndarray], height: Optional[int] 
     fancy when m > 1 and the true chroma width is above 2, replication otherwise (libjpeg turns fancy upsampling off at 1/8).  `height`
     stays the band's FULL-size height."""
     scale = _check_scale(scale)
-    if scale > 1:
-        return _pixels_scaled(hd, coef, hd.height if height is None else int(height), scale)
-    H, W, nf = hd.height if height is None else int(height), hd.width, len(hd.ids)
-    planes = []
-    for c in range(nf):
-        q = hd.q[hd.tq[c]]
-        nat = np.zeros(coef[c].shape, dtype=np.int64)
-        nat[..., ZIGZAG] = coef[c]
-        bh, bw = coef[c].shape[:2]
-        px = np.clip(jpeg_idct_islow((nat * q).reshape(bh, bw, 8, 8)) + 128, 0, 255)
-        plane = px.transpose(0, 2, 1, 3).reshape(bh * 8, bw * 8)
-        ch, cw = -(-H * hd.v[c] // hd.v[0]), -(-W * hd.h[c] // hd.h[0])
-        plane = plane[:ch, :cw]                                                    # the true edges, not the padded blocks'
-        if hd.h[c] < hd.h[0]:
-            if cw <= 2:                                                            # libjpeg replicates planes this narrow
-                plane = np.repeat(plane, 2, axis=1) if hd.v[c] == hd.v[0] else np.repeat(np.repeat(plane, 2, axis=0), 2, axis=1)
-            else:
-                plane = _upsample_h2v1(plane) if hd.v[c] == hd.v[0] else _jpeg_upsample(plane)
-        planes.append(plane[:H, :W])
-    y = planes[0]
-    if nf == 1:
-        return np.repeat(y[..., None], 3, axis=2).astype(np.uint8)
-    cb, cr = planes[1] - 128, planes[2] - 128
-    r = y + ((91881 * cr + 32768) >> 16)
-    g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
-    b = y + ((116130 * cb + 32768) >> 16)
-    return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
-
-
-def _pixels_scaled(hd: _Header, coef: List[np.ndarray], H: int, scale: int) -> np.ndarray:
-    m, W, nf = 8 // scale, hd.width, len(hd.ids)
+    m, H, W, nf = 8 // scale, hd.height if height is None else int(height), hd.width, len(hd.ids)
     out_h, out_w, _ = jpeg_scaled_shape(H, W, scale)
-    sizes = jpeg_scaled_transforms(hd.h, hd.v, scale)
+    sizes = jpeg_scaled_transforms(hd.h, hd.v, scale)                              # 8 for every component at scale 1
     planes = []
     for c in range(nf):
         q, ss = hd.q[hd.tq[c]], sizes[c]
@@ -441,18 +411,17 @@ def _pixels_scaled(hd: _Header, coef: List[np.ndarray], H: int, scale: int) -> n
         px = np.clip(jpeg_idct_scaled((nat * q).reshape(bh, bw, 8, 8), ss) + 128, 0, 255)
         plane = px.transpose(0, 2, 1, 3).reshape(bh * ss, bw * ss)
         ch, cw = -(-H * hd.v[c] * ss // (hd.v[0] * 8)), -(-W * hd.h[c] * ss // (hd.h[0] * 8))
-        plane = plane[:ch, :cw]                                                    # the true edges
-        if hd.h[0] * m == 2 * hd.h[c] * ss:                                        # half the frame's width (4:2:2 chroma): h2v1
-            plane = _upsample_h2v1(plane) if m > 1 and cw > 2 else np.repeat(plane, 2, axis=1)
+        plane = plane[:ch, :cw]                                                    # the true edges, not the padded blocks'
+        if hd.h[0] * m == 2 * hd.h[c] * ss:                                        # half the frame's width: chroma of 4:2:2, or of 4:2:0 at scale 1
+            fancy = m > 1 and cw > 2                                               # libjpeg replicates planes this narrow, and all of them at 1/8
+            if hd.v[0] * m == 2 * hd.v[c] * ss:                                    # and half its height: h2v2, at scale 1 alone
+                plane = _jpeg_upsample(plane) if fancy else np.repeat(np.repeat(plane, 2, axis=0), 2, axis=1)
+            else:
+                plane = _upsample_h2v1(plane) if fancy else np.repeat(plane, 2, axis=1)
         planes.append(plane[:out_h, :out_w])
-    y = planes[0]
     if nf == 1:
-        return np.repeat(y[..., None], 3, axis=2).astype(np.uint8)
-    cb, cr = planes[1] - 128, planes[2] - 128
-    r = y + ((91881 * cr + 32768) >> 16)
-    g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
-    b = y + ((116130 * cb + 32768) >> 16)
-    return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
+        return np.repeat(planes[0][..., None], 3, axis=2).astype(np.uint8)
+    return _jpeg_ycc_to_rgb(planes[0], planes[1] - 128, planes[2] - 128)
 
 
 # ------------------------------------------------------------------------------------------------------------------------ the product
@@ -495,6 +464,60 @@ def _raise_as_python(data: bytes, rc: int, progressive: bool = False):
         if isinstance(exc, UnsupportedJPEG) == (rc == ERR_UNSUPPORTED):
             raise
     raise (UnsupportedJPEG if rc == ERR_UNSUPPORTED else MalformedJPEG)(f"the library declined the file with status {rc}")
+
+
+def _read_items(items: Sequence[Item]) -> List[bytes]:
+    """The files' bytes: an item is the bytes themselves or a path."""
+    blobs = []
+    for item in items:
+        if isinstance(item, (bytes, bytearray, memoryview)):
+            blobs.append(bytes(item))
+        else:
+            with open(item, "rb") as fh:
+                blobs.append(fh.read())
+    return blobs
+
+
+def _judge(blobs: List[bytes], results: List, fallback, progressive: bool, scale: int = 1, name_item: bool = False):
+    """Every file is judged before anything is launched or stored.  `results` holds per file the pool's tuple, a JPEG to decode, or the
+    library's status: ERR_UNSUPPORTED with a `fallback` becomes the fallback's pixels, every other status raises as the Python decoder
+    does (`name_item`: with "item i: " in front).  Returns the positions of the JPEGs and {position: pixels}."""
+    jpegs, raw = [], {}
+    for i, (data, res) in enumerate(zip(blobs, results)):
+        if isinstance(res, tuple):
+            jpegs.append(i)
+        elif res == ERR_UNSUPPORTED and fallback is not None:
+            px = np.ascontiguousarray(fallback(data))
+            if px.ndim != 3 or px.shape[2] != 3 or px.dtype != np.uint8:
+                raise ValueError("the fallback must return uint8 (H, W, 3)")
+            if scale > 1:
+                _check_fallback_shape(i, data, px, scale)
+            raw[i] = px
+        else:
+            try:
+                _raise_as_python(data, res, progressive)
+            except (MalformedJPEG, UnsupportedJPEG) as exc:
+                if not name_item:
+                    raise
+                raise type(exc)(f"item {i}: {exc}") from None
+    return jpegs, raw
+
+
+def _fill_header(rec, info) -> None:
+    """What a FearJpegImage record takes from the file's FearJpegInfo."""
+    rec.width, rec.height, rec.components, rec.h, rec.v = info.width, info.height, info.components, info.h[0], info.v[0]
+    ctypes.memmove(rec.qt, info.qt, ctypes.sizeof(rec.qt))
+
+
+def _launch_pixels(lib, records, n: int, table: int, workspace: int, workspace_bytes: int, scale: int, stream) -> None:
+    """The pixel stage over `n` FearJpegImage records whose prefix tables are at the device address `table`: fear_jpeg_decode_u8, at a
+    scale fear_jpeg_decode_scaled_u8."""
+    from .train_abi import launch
+    table, workspace = ctypes.c_void_p(table), ctypes.c_void_p(workspace)
+    if scale == 1:
+        launch(lib, "fear_jpeg_decode_u8", records, n, table, workspace, workspace_bytes, stream)
+    else:
+        launch(lib, "fear_jpeg_decode_scaled_u8", records, n, table, scale, workspace, workspace_bytes, stream)
 
 
 class JpegDecoder:
@@ -549,33 +572,27 @@ class JpegDecoder:
     def entropy_decode(self, data: bytes):
         """One file through fear_jpeg_parse and fear_jpeg_entropy_decode: (FearJpegInfo, packed int16 coefficients, uint32 block_start),
         or the library's status for a file it declines.  Host only."""
+        return self._packed_coefficients(data, self._lib.fear_jpeg_parse, self._lib.fear_jpeg_entropy_decode, self.progressive)
+
+    def progressive_decode(self, data: bytes):
+        """One file through fear_jpeg_progressive_parse and fear_jpeg_progressive_decode: what `entropy_decode` returns for a baseline
+        file, or the library's status — FEAR_TRAIN_ERR_UNSUPPORTED also for a file whose frame is not SOF2.  Host only."""
+        return self._packed_coefficients(data, self._lib.fear_jpeg_progressive_parse, self._lib.fear_jpeg_progressive_decode, False)
+
+    def _packed_coefficients(self, data: bytes, parse, decode, progressive: bool):
+        """`parse` and then `decode` of the library on one file; with `progressive`, a file that `parse` declines as unsupported goes
+        to `progressive_decode`."""
         from .train_abi import FearJpegInfo
         lib, info = self._lib, FearJpegInfo()
-        rc = lib.fear_jpeg_parse(data, len(data), ctypes.byref(info))
-        if rc == ERR_UNSUPPORTED and self.progressive:
+        rc = parse(data, len(data), ctypes.byref(info))
+        if rc == ERR_UNSUPPORTED and progressive:
             return self.progressive_decode(data)
         if rc != 0:
             return rc
         coef = np.empty(lib.fear_jpeg_packed_bound(ctypes.byref(info)), dtype=np.int16)
         start = np.empty(info.total_blocks + 1, dtype=np.uint32)
         used = ctypes.c_size_t(0)
-        rc = lib.fear_jpeg_entropy_decode(data, len(data), ctypes.byref(info), coef.ctypes.data, coef.size, start.ctypes.data, ctypes.byref(used))
-        if rc != 0:
-            return rc
-        return info, coef[:used.value], start
-
-    def progressive_decode(self, data: bytes):
-        """One file through fear_jpeg_progressive_parse and fear_jpeg_progressive_decode: what `entropy_decode` returns for a baseline
-        file, or the library's status — FEAR_TRAIN_ERR_UNSUPPORTED also for a file whose frame is not SOF2.  Host only."""
-        from .train_abi import FearJpegInfo
-        lib, info = self._lib, FearJpegInfo()
-        rc = lib.fear_jpeg_progressive_parse(data, len(data), ctypes.byref(info))
-        if rc != 0:
-            return rc
-        coef = np.empty(lib.fear_jpeg_packed_bound(ctypes.byref(info)), dtype=np.int16)
-        start = np.empty(info.total_blocks + 1, dtype=np.uint32)
-        used = ctypes.c_size_t(0)
-        rc = lib.fear_jpeg_progressive_decode(data, len(data), ctypes.byref(info), coef.ctypes.data, coef.size, start.ctypes.data, ctypes.byref(used))
+        rc = decode(data, len(data), ctypes.byref(info), coef.ctypes.data, coef.size, start.ctypes.data, ctypes.byref(used))
         if rc != 0:
             return rc
         return info, coef[:used.value], start
@@ -632,40 +649,10 @@ class JpegDecoder:
                 except MalformedJPEG as exc:
                     raise MalformedJPEG(f"item {index}: {exc}") from None
 
-    def _decode_device(self, blobs: List[bytes], fallback, scale: int = 1) -> List:
-        prepared = list(self._pool.map(self._prepare, blobs))
-        jpegs, raw = [], {}
-        for i, (data, res) in enumerate(zip(blobs, prepared)):
-            if isinstance(res, tuple):
-                jpegs.append(i)
-            elif res == ERR_UNSUPPORTED and fallback is not None:
-                px = np.ascontiguousarray(fallback(data))
-                if px.ndim != 3 or px.shape[2] != 3 or px.dtype != np.uint8:
-                    raise ValueError("the fallback must return uint8 (H, W, 3)")
-                if scale > 1:
-                    _check_fallback_shape(i, data, px, scale)
-                raw[i] = px
-            else:
-                _raise_as_python(data, res, self.progressive)
-        self.last_paths = ["device" if len(prepared[i]) == 4 else "host" for i in jpegs]
-        groups, dense = [[]], 0
-        for i in jpegs:
-            need = 128 * int(prepared[i][0].total_blocks) if len(prepared[i]) == 4 else 0
-            if groups[-1] and dense + need > self.workspace_limit:
-                groups.append([])
-                dense = 0
-            groups[-1].append(i)
-            dense += need
-        frames: List = [None] * len(blobs)
-        for g, group in enumerate(groups):
-            if len(group) > 65535:
-                raise ValueError("at most 65535 JPEG files per call")
-            self._decode_group(blobs, prepared, group, raw if g == 0 else {}, frames, scale)
-        return frames
-
     def _decode_group(self, blobs, prepared, group, raw, frames, scale: int = 1) -> None:
-        """One upload, fear_jpeg_huffman over the group's device-path images and fear_jpeg_decode_u8 over all of them.  The layout of
-        `decode`'s host mode with the scans added; host mode keeps its own code so that its bytes and launches stay what they were."""
+        """One group of `decode`, in either entropy mode: one upload, fear_jpeg_huffman over the group's device-path images (a
+        prepared scan, four values) and the pixel stage over all of them; a host-path image (packed coefficients, three values) brings
+        its coefficients and block_start in the upload.  A group without a device-path image launches the pixel stage alone."""
         import torch
         from .train_abi import (FEAR_JPEG_GROUP_BLOCKS, FEAR_JPEG_GROUP_PIXELS, FearJpegImage, FearJpegInfo, FearJpegScan, launch)
         from .train_data.staging import Staging
@@ -680,8 +667,7 @@ class JpegDecoder:
             info = prepared[i][0]
             infos[k] = info
             rec = records[k]
-            rec.width, rec.height, rec.components, rec.h, rec.v = info.width, info.height, info.components, info.h[0], info.v[0]
-            ctypes.memmove(rec.qt, info.qt, ctypes.sizeof(rec.qt))
+            _fill_header(rec, info)
             rec.plane_offset = plane_at
             plane_at += int(info.total_blocks) * 64
             prefix[0, k + 1] = prefix[0, k] + -(-int(info.total_blocks) // FEAR_JPEG_GROUP_BLOCKS)
@@ -701,22 +687,26 @@ class JpegDecoder:
                 stage.add(f"start{k}", prepared[i][2])
             out_at.append(out_bytes)
             out_bytes += -(-sw * sh * 3 // 16) * 16
+            # the staging is now the buffers' only holder and releases them in the order they were allocated; the list would release
+            # them from its end, where malloc trims its heap at every free (25 ms more per call on 256 files of 1280 x 720)
+            prepared[i] = None
         for i, px in raw.items():
             stage.add(f"raw{i}", px)
         table = np.zeros(-(-prefix.nbytes // 16) * 16 + ctypes.sizeof(records), dtype=np.uint8)
         table[:prefix.nbytes] = prefix.reshape(-1).view(np.uint8)
         stage.add("table", table)
-        scan_table = np.zeros(-(-seg_prefix.nbytes // 16) * 16 + ctypes.sizeof(scans), dtype=np.uint8)
-        scan_table[:seg_prefix.nbytes] = seg_prefix.view(np.uint8)
         if nd:
+            scan_table = np.zeros(-(-seg_prefix.nbytes // 16) * 16 + ctypes.sizeof(scans), dtype=np.uint8)
+            scan_table[:seg_prefix.nbytes] = seg_prefix.view(np.uint8)
             stage.add("scans", scan_table)
         with torch.cuda.device(self.device):
             pinned = torch.empty(stage.nbytes, dtype=torch.uint8, pin_memory=True)
             dev = torch.empty(stage.nbytes, dtype=torch.uint8, device=self.device)
             out = torch.empty(max(out_bytes, 16), dtype=torch.uint8, device=self.device)
-            coef = torch.empty(max(values, 8), dtype=torch.int16, device=self.device)
-            dense_start = torch.empty(most + 1, dtype=torch.int32, device=self.device)
-            status = torch.empty(max(nd, 1), dtype=torch.int32, device=self.device)
+            if nd:                                                    # the dense coefficients, their block_start table and the verdicts
+                coef = torch.empty(values, dtype=torch.int16, device=self.device)
+                dense_start = torch.empty(most + 1, dtype=torch.int32, device=self.device)
+                status = torch.empty(nd, dtype=torch.int32, device=self.device)
             base, out_base = dev.data_ptr(), out.data_ptr()
             for k in range(n):
                 if k in place:
@@ -744,15 +734,10 @@ class JpegDecoder:
             if n:
                 ws_bytes = self._lib.fear_jpeg_decode_workspace_bytes(infos, n)
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-                if scale == 1:
-                    launch(self._lib, "fear_jpeg_decode_u8", records, n, ctypes.c_void_p(base + stage.sections["table"][0]),
-                           ctypes.c_void_p(ws.data_ptr()), ws_bytes, stream)
-                else:
-                    launch(self._lib, "fear_jpeg_decode_scaled_u8", records, n, ctypes.c_void_p(base + stage.sections["table"][0]), scale,
-                           ctypes.c_void_p(ws.data_ptr()), ws_bytes, stream)
+                _launch_pixels(self._lib, records, n, base + stage.sections["table"][0], ws.data_ptr(), ws_bytes, scale, stream)
             if nd:
                 verdict = torch.empty(nd, dtype=torch.int32, pin_memory=True)
-                verdict.copy_(status[:nd], non_blocking=True)
+                verdict.copy_(status, non_blocking=True)
                 event = torch.cuda.Event()
                 event.record()
                 self._pending = (self._pending + [(event, verdict, [(group[k], blobs[group[k]]) for k in on_device])])[-self.PENDING_CALLS:]
@@ -770,96 +755,31 @@ class JpegDecoder:
         stage is untouched, in both entropy modes and with `progressive=True`, and `fear_jpeg_decode_scaled_u8` takes the place of
         `fear_jpeg_decode_u8`.  A `fallback`'s pixels must then have the scaled shape (ValueError naming the item).  Another value of
         `scale` is a ValueError before anything is parsed."""
-        import torch
         scale = _check_scale(scale)
-        from .train_abi import (FEAR_JPEG_GROUP_BLOCKS, FEAR_JPEG_GROUP_PIXELS, FearJpegImage, FearJpegInfo, launch)
-        from .train_data.staging import Staging
-        blobs = []
-        for item in items:
-            if isinstance(item, (bytes, bytearray, memoryview)):
-                blobs.append(bytes(item))
-            else:
-                with open(item, "rb") as fh:
-                    blobs.append(fh.read())
-        n_items = len(blobs)
-        if n_items == 0:
+        blobs = _read_items(items)
+        if not blobs:
             return []
-        if self.entropy == "device":
-            frames = self._decode_device(blobs, fallback, scale)
-            if check:
-                self.check()
-            return frames
-        # the host stage: every file is judged before anything is launched
-        decoded = list(self._pool.map(self.entropy_decode, blobs))
-        stage, jpegs, raw = Staging(), [], {}
-        for i, (data, res) in enumerate(zip(blobs, decoded)):
-            if isinstance(res, tuple):
-                jpegs.append(i)
-            elif res == ERR_UNSUPPORTED and fallback is not None:
-                px = np.ascontiguousarray(fallback(data))
-                if px.ndim != 3 or px.shape[2] != 3 or px.dtype != np.uint8:
-                    raise ValueError("the fallback must return uint8 (H, W, 3)")
-                if scale > 1:
-                    _check_fallback_shape(i, data, px, scale)
-                raw[i] = px
-            else:
-                _raise_as_python(data, res, self.progressive)
-        n = len(jpegs)
-        if n > 65535:
-            raise ValueError("at most 65535 JPEG files per call")
-        records = (FearJpegImage * max(n, 1))()
-        infos = (FearJpegInfo * max(n, 1))()
-        prefix = np.zeros((2, n + 1), dtype=np.uint32)
-        out_at, out_bytes, plane_at = [], 0, 0
-        for k, i in enumerate(jpegs):
-            info, coef, start = decoded[i]
-            infos[k] = info
-            rec = records[k]
-            rec.width, rec.height, rec.components, rec.h, rec.v = info.width, info.height, info.components, info.h[0], info.v[0]
-            ctypes.memmove(rec.qt, info.qt, ctypes.sizeof(rec.qt))
-            rec.plane_offset = plane_at
-            plane_at += int(info.total_blocks) * 64
-            prefix[0, k + 1] = prefix[0, k] + -(-int(info.total_blocks) // FEAR_JPEG_GROUP_BLOCKS)
-            sh, sw, _ = jpeg_scaled_shape(info.height, info.width, scale)          # the frame's size: the file's at scale 1
-            prefix[1, k + 1] = prefix[1, k] + -(-sw * sh // FEAR_JPEG_GROUP_PIXELS)
-            stage.add(f"coef{k}", coef)
-            stage.add(f"start{k}", start)
-            out_at.append(out_bytes)
-            out_bytes += -(-sw * sh * 3 // 16) * 16
-        for i, px in raw.items():
-            stage.add(f"raw{i}", px)
-        table = np.zeros(-(-prefix.nbytes // 16) * 16 + ctypes.sizeof(records), dtype=np.uint8)
-        table[:prefix.nbytes] = prefix.reshape(-1).view(np.uint8)
-        stage.add("table", table)
-        with torch.cuda.device(self.device):
-            pinned = torch.empty(stage.nbytes, dtype=torch.uint8, pin_memory=True)
-            dev = torch.empty(stage.nbytes, dtype=torch.uint8, device=self.device)
-            out = torch.empty(max(out_bytes, 16), dtype=torch.uint8, device=self.device)
-            base, out_base = dev.data_ptr(), out.data_ptr()
-            for k in range(n):
-                records[k].coef = base + stage.sections[f"coef{k}"][0]
-                records[k].block_start = base + stage.sections[f"start{k}"][0]
-                records[k].out = out_base + out_at[k]
-            if n:
-                table[-ctypes.sizeof(records):] = np.frombuffer(records, dtype=np.uint8)
-            stage.write(pinned.numpy())
-            dev.copy_(pinned, non_blocking=True)
-            self._pinned = self._pinned[-1:] + [pinned]
-            if n:
-                ws_bytes = self._lib.fear_jpeg_decode_workspace_bytes(infos, n)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-                if scale == 1:
-                    launch(self._lib, "fear_jpeg_decode_u8", records, n, ctypes.c_void_p(base + stage.sections["table"][0]),
-                           ctypes.c_void_p(ws.data_ptr()), ws_bytes, stream)
-                else:
-                    launch(self._lib, "fear_jpeg_decode_scaled_u8", records, n, ctypes.c_void_p(base + stage.sections["table"][0]), scale,
-                           ctypes.c_void_p(ws.data_ptr()), ws_bytes, stream)
-        frames: List = [None] * n_items
-        for k, i in enumerate(jpegs):
-            h, w, _ = jpeg_scaled_shape(records[k].height, records[k].width, scale)
-            frames[i] = out[out_at[k]:out_at[k] + h * w * 3].view(h, w, 3)
-        for i, px in raw.items():
-            at = stage.sections[f"raw{i}"][0]
-            frames[i] = dev[at:at + px.nbytes].view(px.shape)
+        # the pool: the host's Huffman stage, or in device mode the scans prepared (a file too long for the device: the host's stage)
+        device = self.entropy == "device"
+        prepared = list(self._pool.map(self._prepare if device else self.entropy_decode, blobs))
+        jpegs, raw = _judge(blobs, prepared, fallback, self.progressive, scale)
+        if device:
+            self.last_paths = ["device" if len(prepared[i]) == 4 else "host" for i in jpegs]
+        # groups by the dense coefficients of the device-path images, 128 bytes per block; a host-path image needs none, so host
+        # mode is one group
+        groups, dense = [[]], 0
+        for i in jpegs:
+            need = 128 * int(prepared[i][0].total_blocks) if len(prepared[i]) == 4 else 0
+            if groups[-1] and dense + need > self.workspace_limit:
+                groups.append([])
+                dense = 0
+            groups[-1].append(i)
+            dense += need
+        frames: List = [None] * len(blobs)
+        for g, group in enumerate(groups):
+            if len(group) > 65535:
+                raise ValueError("at most 65535 JPEG files per call")
+            self._decode_group(blobs, prepared, group, raw if g == 0 else {}, frames, scale)
+        if device and check:
+            self.check()
         return frames

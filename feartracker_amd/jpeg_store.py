@@ -29,7 +29,8 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import jpeg_frames
-from .jpeg_frames import ERR_UNSUPPORTED, Item, JpegDecoder, MalformedJPEG, UnsupportedJPEG, _check_scale, _raise_as_python
+from .jpeg_frames import (ERR_UNSUPPORTED, Item, JpegDecoder, MalformedJPEG, UnsupportedJPEG, _check_scale, _fill_header, _judge,
+                          _launch_pixels, _raise_as_python, _read_items)
 from .jpeg_huffman import SUBSEQ_DTYPE, _check_subsequence_bytes, scan_row_sub
 
 KIND_SCAN, KIND_PIXELS = 0, 1
@@ -69,31 +70,48 @@ def plan_decode(columns: np.ndarray, ids, workspace_limit: int, max_group: int =
     At `scale` 2, 4 or 8 the frames are the scaled ones (`jpeg_scaled_shape`): `pixel_prefix` counts scaled pixels, as
     fear_jpeg_decode_scaled_u8 reads it, and `out_offset` and `out_bytes` lay out scaled frames; the blocks, the coefficients and the
     workspace are what they are at scale 1."""
-    m = 8 // _check_scale(scale)
     ids = np.asarray(ids, dtype=np.int64).reshape(-1)
     rows = columns[ids]
     is_scan = rows["kind"] == KIND_SCAN
     blocks = rows["total_blocks"].astype(np.int64)
-    pixels = -(-rows["H"].astype(np.int64) * m // 8) * -(-rows["W"].astype(np.int64) * m // 8)
-    need = _exclusive(np.where(is_scan, 128 * blocks, 0))
-    groups, lo, n = [], 0, ids.size
-    while lo < n:                                                       # one turn per group
+    high, wide = _scaled_sides(rows["H"], rows["W"], scale)
+    pixels, n_sub = high * wide, rows["n_sub"].astype(np.int64)
+    groups = []
+    for lo, hi in _cut(np.where(is_scan, 128 * blocks, 0), workspace_limit, max_group):
+        scan = np.flatnonzero(is_scan[lo:hi])
+        pick = lo + scan
+        groups.append(dict(lo=lo, hi=hi, scan=scan, sub_prefix=_exclusive(-(-n_sub[pick] // LANES)).astype(np.uint32),
+                           **_layout(blocks[pick], pixels[pick], pixels[lo:hi])))
+    return groups
+
+
+def _scaled_sides(H, W, scale: int):
+    """`jpeg_frames.jpeg_scaled_shape` over arrays of heights and widths: int64 ceil(H m / 8) and ceil(W m / 8), m = 8 // scale."""
+    m = 8 // _check_scale(scale)
+    return -(-np.asarray(H, dtype=np.int64) * m // 8), -(-np.asarray(W, dtype=np.int64) * m // 8)
+
+
+def _cut(need_bytes: np.ndarray, workspace_limit: int, max_group: int):
+    """The groups lo..hi of a call whose position k needs `need_bytes[k]` of dense coefficients: a group takes positions while their sum
+    stays within `workspace_limit`, at least one and at most `max_group`.  One turn per group, none per file."""
+    need, lo, n = _exclusive(need_bytes), 0, need_bytes.size
+    while lo < n:
         hi = int(np.searchsorted(need, need[lo] + max(int(workspace_limit), 0), side="right")) - 1
         hi = min(max(hi, lo + 1), n, lo + max_group)
-        scan = np.flatnonzero(is_scan[lo:hi])
-        b, px = blocks[lo:hi][scan], pixels[lo:hi][scan]
-        dense = _exclusive(64 * b)
-        out = _exclusive(_up(3 * pixels[lo:hi], 16))
-        groups.append(dict(
-            lo=lo, hi=hi, scan=scan,
-            sub_prefix=_exclusive(-(-rows["n_sub"][lo:hi][scan].astype(np.int64) // LANES)).astype(np.uint32),
-            block_prefix=_exclusive(-(-b // 32)).astype(np.uint32), pixel_prefix=_exclusive(-(-px // 256)).astype(np.uint32),
-            coef_offset=dense[:-1].astype(np.uint64), values=int(dense[-1]),
-            plane_offset=dense[:-1].astype(np.uint64), workspace_bytes=16 + int(dense[-1]),
-            most=int(b.max()) if b.size else 0,
-            out_offset=out[:-1], out_bytes=int(out[-1])))
+        yield lo, hi
         lo = hi
-    return groups
+
+
+def _layout(blocks: np.ndarray, pixels: np.ndarray, frame_pixels: np.ndarray) -> dict:
+    """What both plans lay out for the images the pixel stage decodes, of `blocks` blocks and `pixels` pixels each — the two prefix
+    tables, the dense coefficients and the planes — and for all the group's frames, of `frame_pixels` pixels, the output."""
+    dense = _exclusive(64 * blocks)
+    out = _exclusive(_up(3 * frame_pixels, 16))
+    return dict(block_prefix=_exclusive(-(-blocks // 32)).astype(np.uint32), pixel_prefix=_exclusive(-(-pixels // 256)).astype(np.uint32),
+                coef_offset=dense[:-1].astype(np.uint64), values=int(dense[-1]),
+                plane_offset=dense[:-1].astype(np.uint64), workspace_bytes=16 + int(dense[-1]),
+                most=int(blocks.max()) if blocks.size else 0,
+                out_offset=out[:-1], out_bytes=int(out[-1]))
 
 
 def scan_columns(col, info, n_seg: int, n_sub: int, row_at: int) -> None:
@@ -129,7 +147,7 @@ def plan_decode_rows(columns: np.ndarray, row_sub: np.ndarray, ids, rows, worksp
     col = columns[ids]
     is_scan = col["kind"] == KIND_SCAN
     full_h, full_mcu_h = col["H"].astype(np.int64), np.maximum(col["mcu_h"].astype(np.int64), 1)
-    H, W, mcu_h = -(-full_h * m // 8), -(-col["W"].astype(np.int64) * m // 8), np.maximum(full_mcu_h * m // 8, 1)
+    (H, W), mcu_h = _scaled_sides(full_h, col["W"], scale), np.maximum(full_mcu_h * m // 8, 1)
     mcus_y = col["mcus_y"].astype(np.int64)
     y0, y1 = np.clip(rows[:, 0], 0, H), np.clip(rows[:, 1], 0, H)
     some = is_scan & (y0 < y1)
@@ -146,30 +164,32 @@ def plan_decode_rows(columns: np.ndarray, row_sub: np.ndarray, ids, rows, worksp
     last = np.where(some, np.minimum(row_sub[at + b].astype(np.int64), n_sub - 1), -1) if row_sub.size else np.full(ids.size, -1, np.int64)
     count = np.maximum(last - first + 1, 0)
     pixels = H * W
-    need = _exclusive(128 * blocks)
-    groups, lo, n = [], 0, ids.size
-    while lo < n:                                                       # one turn per group
-        hi = int(np.searchsorted(need, need[lo] + max(int(workspace_limit), 0), side="right")) - 1
-        hi = min(max(hi, lo + 1), n, lo + max_group)
+    groups = []
+    for lo, hi in _cut(128 * blocks, workspace_limit, max_group):
         scan = np.flatnonzero(some[lo:hi])
         pick = lo + scan
-        bl = blocks[pick]
-        dense = _exclusive(64 * bl)
-        out = _exclusive(_up(3 * pixels[lo:hi], 16))
         groups.append(dict(
             lo=lo, hi=hi, scan=scan,
             sub0=first[pick].astype(np.uint32), sub_count=count[pick].astype(np.uint32),
             sub_prefix=_exclusive(-(-count[pick] // LANES)).astype(np.uint32),
             mcu_row0=a[pick].astype(np.uint32), mcu_rows=(b - a)[pick].astype(np.uint32),
             band_y0=band_y0[pick], band_height=band_full[pick].astype(np.int32), band_out=3 * W[pick] * band_y0[pick],
-            block_prefix=_exclusive(-(-bl // 32)).astype(np.uint32),
-            pixel_prefix=_exclusive(-(-(band_h[pick] * W[pick]) // 256)).astype(np.uint32),
-            coef_offset=dense[:-1].astype(np.uint64), values=int(dense[-1]),
-            plane_offset=dense[:-1].astype(np.uint64), workspace_bytes=16 + int(dense[-1]),
-            most=int(bl.max()) if bl.size else 0,
-            out_offset=out[:-1], out_bytes=int(out[-1])))
-        lo = hi
+            **_layout(blocks[pick], band_h[pick] * W[pick], pixels[lo:hi])))
     return groups
+
+
+def _place_images(images: np.ndarray, coef, coef_offset: np.ndarray, block_start, out, out_offset: np.ndarray, plane_offset: np.ndarray) -> None:
+    """The addresses of a group's FearJpegImage records: each image's dense coefficients in `coef` (an int16 tensor, `coef_offset` in
+    values), the dense `block_start` table they share, where its pixels go in `out` and its planes in the workspace."""
+    images["coef"] = np.uint64(coef.data_ptr()) + np.uint64(2) * coef_offset
+    images["block_start"] = block_start.data_ptr()
+    images["out"] = np.uint64(out.data_ptr()) + out_offset.astype(np.uint64)
+    images["plane_offset"] = plane_offset
+
+
+def _frame_views(out, out_offset: np.ndarray, high: np.ndarray, wide: np.ndarray) -> List:
+    """The frames in a group's output: frame k is `high[k]` x `wide[k]` x 3 bytes from `out_offset[k]`."""
+    return [out[at:at + 3 * h * w].view(h, w, 3) for at, h, w in zip(out_offset.tolist(), high.tolist(), wide.tolist())]
 
 
 class JpegStore:
@@ -271,9 +291,9 @@ class JpegStore:
 
     def shape(self, ids, scale: int = 1) -> np.ndarray:
         """(len(ids), 2) int32: height and width, of the frames `decode(ids, scale=scale)` returns."""
-        m = 8 // _check_scale(scale)
+        _check_scale(scale)
         rows = self._columns[self._checked(ids)]
-        return np.stack([-(-rows["H"] * m // 8), -(-rows["W"] * m // 8)], axis=1).astype(np.int32)
+        return np.stack(_scaled_sides(rows["H"], rows["W"], scale), axis=1).astype(np.int32)
 
     def _scan_only(self, ids: np.ndarray, scale: int) -> None:
         """At a scale every id is a "scan" entry: decoded pixels cannot be decoded again."""
@@ -305,13 +325,7 @@ class JpegStore:
     def add(self, items: Sequence[Item], fallback: Optional[Callable[[bytes], np.ndarray]] = None) -> np.ndarray:
         import torch
         from . import train_abi as abi
-        blobs = []
-        for item in items:
-            if isinstance(item, (bytes, bytearray, memoryview)):
-                blobs.append(bytes(item))
-            else:
-                with open(item, "rb") as fh:
-                    blobs.append(fh.read())
+        blobs = _read_items(items)
         n = len(blobs)
         if n == 0:
             return np.zeros(0, dtype=np.int64)
@@ -324,21 +338,10 @@ class JpegStore:
                 elif res is not None:
                     declined[i] = res                                    # the original goes to the fallback, or raises
         prepared = list(self._host._pool.map(self._host.scan_prepare, blobs))
-        # every file is judged before anything is stored
-        scans, through_host, raw = [], [], {}
-        for i, (data, res) in enumerate(zip(blobs, prepared)):
-            if isinstance(res, tuple):
-                (through_host if res[3].max_seg_bytes > limit else scans).append(i)
-            elif declined.get(i, res) == ERR_UNSUPPORTED and fallback is not None:
-                px = np.ascontiguousarray(fallback(data))
-                if px.ndim != 3 or px.shape[2] != 3 or px.dtype != np.uint8:
-                    raise ValueError("the fallback must return uint8 (H, W, 3)")
-                raw[i] = px
-            else:
-                try:
-                    _raise_as_python(data, declined.get(i, res), self.progressive)
-                except (MalformedJPEG, UnsupportedJPEG) as exc:
-                    raise type(exc)(f"item {i}: {exc}") from None
+        # every file is judged before anything is stored (a file the transcoder declined: by the transcoder's status)
+        jpegs, raw = _judge(blobs, [declined.get(i, res) for i, res in enumerate(prepared)], fallback, self.progressive, name_item=True)
+        scans = [i for i in jpegs if prepared[i][3].max_seg_bytes <= limit]
+        through_host = [i for i in jpegs if prepared[i][3].max_seg_bytes > limit]
         # the resident layout of every "scan" file, from its base: bytes | seg_start | sub_start | index | FearJpegScan, each at 16 bytes
         layout, split, need = {}, dict(bytes=0, index=0, records=0, pixels=0, rows=0, border=3 * n), 0
         for i in scans:
@@ -490,11 +493,10 @@ class JpegStore:
         for i in scans:
             info, data, seg, scan = prepared[i]
             sub, at_seg, at_sub, at_index, at_record, end = layout[i]
-            row, img, col = self._indexed[first + i], self._image[first + i], self._columns[first + i]
+            row, col = self._indexed[first + i], self._columns[first + i]
             row["scan"], row["index"], row["sub_start"], row["n_sub"] = base[i] + at_record, base[i] + at_index, base[i] + at_sub, int(sub[-1])
             row["row_sub"] = row_at[i]
-            img["width"], img["height"], img["components"], img["h"], img["v"] = info.width, info.height, info.components, info.h[0], info.v[0]
-            img["qt"] = np.ctypeslib.as_array(info.qt)
+            _fill_header(abi.FearJpegImage.from_buffer(self._image, (first + i) * self._image.itemsize), info)
             table = row_tables[i]
             scan_columns(col, info, scan.n_seg, int(sub[-1]), self._row_used)
             if self._row_used + table.size > self._row_sub.size:
@@ -555,32 +557,22 @@ class JpegStore:
         from . import train_abi as abi
         m = len(infos)
         images = np.zeros(m, dtype=self._dtypes[1])
+        for rec, info in zip((abi.FearJpegImage * m).from_buffer(images), infos):
+            _fill_header(rec, info)
         blocks = np.array([int(i.total_blocks) for i in infos], dtype=np.int64)
-        pixels = np.array([int(i.width) * int(i.height) for i in infos], dtype=np.int64)
-        dense, out_at = _exclusive(64 * blocks), _exclusive(_up(3 * pixels, 16))
-        start = torch.empty(int(blocks.max()) + 1, dtype=torch.int32, device=self.device)
-        abi.launch(self._lib, "fear_jpeg_dense_block_start", ctypes.c_void_p(start.data_ptr()), int(blocks.max()), stream)
-        out = torch.empty(max(int(out_at[-1]), 16), dtype=torch.uint8, device=self.device)
-        ws_bytes = 16 + int(dense[-1])
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-        for k, info in enumerate(infos):
-            img = images[k]
-            img["width"], img["height"], img["components"], img["h"], img["v"] = info.width, info.height, info.components, info.h[0], info.v[0]
-            img["qt"] = np.ctypeslib.as_array(info.qt)
-            img["coef"] = coef.data_ptr() + 2 * int(records[k].coef_offset)
-        images["block_start"] = start.data_ptr()
-        images["out"] = np.uint64(out.data_ptr()) + out_at[:-1].astype(np.uint64)
-        images["plane_offset"] = dense[:-1].astype(np.uint64)
-        prefixes = np.concatenate([_exclusive(-(-blocks // 32)), _exclusive(-(-pixels // 256))]).astype(np.uint32)
-        at_images = _up(prefixes.nbytes, 16)
-        table = np.zeros(at_images + images.nbytes, dtype=np.uint8)
-        table[:prefixes.nbytes] = prefixes.view(np.uint8)
-        table[at_images:] = images.view(np.uint8)
-        dev = torch.from_numpy(table).to(self.device)
-        abi.launch(self._lib, "fear_jpeg_decode_u8", ctypes.c_void_p(images.ctypes.data), m, ctypes.c_void_p(dev.data_ptr()),
-                   ctypes.c_void_p(ws.data_ptr()), ws_bytes, stream)
-        frames = [out[int(out_at[k]):int(out_at[k]) + 3 * int(pixels[k])].view(int(infos[k].height), int(infos[k].width), 3) for k in range(m)]
-        return self._frame_borders(frames, stream)
+        high, wide = images["height"].astype(np.int64), images["width"].astype(np.int64)
+        plan = _layout(blocks, high * wide, high * wide)                 # plan_decode's, of a group that is all "scan" entries
+        # a table of its own: `add` commits the store's largest image, which sizes the shared one, only at its end
+        start = torch.empty(plan["most"] + 1, dtype=torch.int32, device=self.device)
+        abi.launch(self._lib, "fear_jpeg_dense_block_start", ctypes.c_void_p(start.data_ptr()), plan["most"], stream)
+        out = torch.empty(max(plan["out_bytes"], 16), dtype=torch.uint8, device=self.device)
+        ws = torch.empty(plan["workspace_bytes"], dtype=torch.uint8, device=self.device)
+        offsets = np.array([int(r.coef_offset) for r in records], dtype=np.uint64)
+        _place_images(images, coef, offsets, start, out, plan["out_offset"], plan["plane_offset"])
+        dev, at = self._upload([np.concatenate([plan["block_prefix"], plan["pixel_prefix"]]), images], pinned=False)
+        _launch_pixels(self._lib, ctypes.c_void_p(images.ctypes.data), m, dev.data_ptr() + at[0], ws.data_ptr(), plan["workspace_bytes"], 1,
+                       stream)
+        return self._frame_borders(_frame_views(out, plan["out_offset"], high, wide), stream)
 
     # ----------------------------------------------------------------------------------------------------------------------- decode
     def decode(self, ids, check: bool = False, scale: int = 1) -> List:
@@ -590,108 +582,120 @@ class JpegStore:
         scale = _check_scale(scale)
         ids = self._checked(ids)
         self._scan_only(ids, scale)
-        frames: List = [None] * ids.size
-        self._pending = self._pending[-self.PENDING_CALLS:]              # of earlier calls; every group of this call is kept
-        for plan in plan_decode(self._columns, ids, self.workspace_limit, scale=scale):
-            self._decode_group(ids, plan, frames, scale=scale)
-        if check:
-            self.check()
-        return frames
+        return self._decode_groups(ids, plan_decode(self._columns, ids, self.workspace_limit, scale=scale), check, scale=scale)
 
     def _decode_rows_device(self, ids: np.ndarray, rows, check: bool) -> List:
         import torch
         mine = torch.device(self.device)
         if rows.device.index != (mine.index or 0) or rows.dtype != torch.int32 or tuple(rows.shape) != (ids.size, 2):
             raise ValueError(f"rows on a device must be ({ids.size}, 2) int32 on {mine}, one [y0, y1) per id")
+        return self._decode_groups(ids, plan_decode(self._columns, ids, self.workspace_limit), check, rows)
+
+    def _decode_groups(self, ids: np.ndarray, plans: List[dict], check: bool, rows=None, scale: int = 1) -> List:
+        """The frames of one call, group by group."""
         frames: List = [None] * ids.size
-        self._pending = self._pending[-self.PENDING_CALLS:]
-        for plan in plan_decode(self._columns, ids, self.workspace_limit):
-            self._decode_group(ids, plan, frames, rows)
+        self._pending = self._pending[-self.PENDING_CALLS:]              # of earlier calls; every group of this call is kept
+        for plan in plans:
+            self._decode_group(ids, plan, frames, rows, scale)
         if check:
             self.check()
         return frames
 
     def _decode_group(self, ids: np.ndarray, plan: dict, frames: List, rows=None, scale: int = 1) -> None:
-        """One group of `decode`; with `rows`, the call's device tensor, one group of `decode_rows` with the rows on the device."""
+        """One group of `decode` and of both forms of `decode_rows`: the shared block_start table, the gathered records with the
+        group's addresses, one pinned upload, the Huffman kernel, the pixel stage, the verdicts, the frames.  What the plan carries
+        and `rows` select the kernels: a plan of `plan_decode_rows` carries the bands (sub0, sub_count, mcu_row0, mcu_rows, band_height,
+        band_out), which go into the records for `fear_jpeg_huffman_indexed_rows`; `rows`, the call's device tensor, goes with
+        `plan_decode`'s full-image plan to the two kernels that read the bands on the device."""
         import torch
         from . import train_abi as abi
+        P = ctypes.c_void_p
         lo, hi, scan = plan["lo"], plan["hi"], plan["scan"]
         group = ids[lo:hi]
-        sids, nd = group[scan], scan.size
+        sids, nd, banded = group[scan], scan.size, "sub0" in plan
         with torch.cuda.device(self.device):
             out = torch.empty(max(plan["out_bytes"], 16), dtype=torch.uint8, device=self.device)
             out_offset = plan["out_offset"]
             if nd:
-                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-                if self._dense_blocks < self._most:                      # the store's largest image grew
-                    self._dense_retired.append(self._dense_start)
-                    self._dense_start = torch.empty(self._most + 1, dtype=torch.int32, device=self.device)
-                    abi.launch(self._lib, "fear_jpeg_dense_block_start", ctypes.c_void_p(self._dense_start.data_ptr()), self._most, stream)
-                    self._dense_blocks, self._dense_event = self._most, torch.cuda.Event()
-                    self._dense_event.record()
-                else:                                                    # written on whatever stream was current then: this one waits for it
-                    torch.cuda.current_stream().wait_event(self._dense_event)
+                stream = P(torch.cuda.current_stream().cuda_stream)
+                block_start = self._block_start(stream)
                 coef = torch.empty(max(plan["values"], 8), dtype=torch.int16, device=self.device)
                 ws = torch.empty(plan["workspace_bytes"], dtype=torch.uint8, device=self.device)
                 status = torch.empty(nd, dtype=torch.int32, device=self.device)
                 indexed, images = self._indexed[sids], self._image[sids]  # gathers: private copies
                 indexed["coef_offset"] = plan["coef_offset"]
-                images["coef"] = np.uint64(coef.data_ptr()) + np.uint64(2) * plan["coef_offset"]
-                images["block_start"] = self._dense_start.data_ptr()
-                images["out"] = np.uint64(out.data_ptr()) + out_offset[scan].astype(np.uint64)
-                images["plane_offset"] = plan["plane_offset"]
-                # one pinned upload: prefix | FearJpegIndexed records, then two prefixes | FearJpegImage records
-                prefixes = np.concatenate([plan["block_prefix"], plan["pixel_prefix"]])
-                at_indexed = _up(plan["sub_prefix"].nbytes, 16)
-                at_table = at_indexed + indexed.nbytes
-                at_images = at_table + _up(prefixes.nbytes, 16)
-                # with rows on the device and a group that is no run of positions: the positions, to gather the group's rows with
+                at_out = out_offset[scan]
+                if banded:                                               # the band as an image of its own, written into its frame's rows
+                    for field in ("sub0", "sub_count", "mcu_row0", "mcu_rows"):
+                        indexed[field] = plan[field]
+                    images["height"] = plan["band_height"]
+                    at_out = at_out + plan["band_out"]
+                _place_images(images, coef, plan["coef_offset"], block_start, out, at_out, plan["plane_offset"])
+                # one pinned upload: prefix | FearJpegIndexed records, then two prefixes | FearJpegImage records; with rows on the
+                # device and a group that is no run of positions also the positions, to gather the group's rows with
+                parts = [plan["sub_prefix"], indexed, np.concatenate([plan["block_prefix"], plan["pixel_prefix"]]), images]
                 whole = rows is None or nd == hi - lo
-                at_pick = at_images + images.nbytes
-                pinned = torch.empty(at_pick + (0 if whole else 8 * nd), dtype=torch.uint8, pin_memory=True)
-                host = pinned.numpy()
-                host[:at_indexed].view(np.uint32)[:nd + 1] = plan["sub_prefix"]
-                host[at_indexed:at_table] = indexed.view(np.uint8)
-                host[at_table:at_images].view(np.uint32)[:2 * nd + 2] = prefixes
-                host[at_images:at_pick] = images.view(np.uint8)
                 if not whole:
-                    host[at_pick:].view(np.int64)[:] = lo + scan
-                dev = torch.empty(pinned.numel(), dtype=torch.uint8, device=self.device)
-                dev.copy_(pinned, non_blocking=True)
-                self._pinned = self._pinned[-1:] + [pinned]
+                    parts.append(lo + scan)
+                dev, at = self._upload(parts)
+                table = dev.data_ptr() + at[2]
                 self._records = (indexed, images)                        # the calls below get their addresses
-                self.last_upload_bytes = pinned.numel()
+                self.last_upload_bytes = dev.numel()
                 if rows is None:
-                    abi.launch(self._lib, "fear_jpeg_huffman_indexed", ctypes.c_void_p(indexed.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr()),
-                               ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(status.data_ptr()), self.subsequence_bytes, stream)
-                    if scale == 1:
-                        abi.launch(self._lib, "fear_jpeg_decode_u8", ctypes.c_void_p(images.ctypes.data), nd,
-                                   ctypes.c_void_p(dev.data_ptr() + at_table), ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"], stream)
-                    else:
-                        abi.launch(self._lib, "fear_jpeg_decode_scaled_u8", ctypes.c_void_p(images.ctypes.data), nd,
-                                   ctypes.c_void_p(dev.data_ptr() + at_table), scale, ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"],
-                                   stream)
+                    abi.launch(self._lib, "fear_jpeg_huffman_indexed_rows" if banded else "fear_jpeg_huffman_indexed", P(indexed.ctypes.data), nd,
+                               P(dev.data_ptr()), P(coef.data_ptr()), P(status.data_ptr()), self.subsequence_bytes, stream)
+                    _launch_pixels(self._lib, P(images.ctypes.data), nd, table, ws.data_ptr(), plan["workspace_bytes"], scale, stream)
                 else:                                                    # the group's rows: a slice, or a gather on the device; no wait
-                    mine = rows[lo:hi] if whole else rows.index_select(0, dev[at_pick:].view(torch.int64))
+                    mine = rows[lo:hi] if whole else rows.index_select(0, dev[at[4]:].view(torch.int64))
                     mine = mine.contiguous()
-                    abi.launch(self._lib, "fear_jpeg_huffman_indexed_rows_dev", ctypes.c_void_p(indexed.ctypes.data), nd,
-                               ctypes.c_void_p(dev.data_ptr()), ctypes.c_void_p(mine.data_ptr()), ctypes.c_void_p(coef.data_ptr()),
-                               ctypes.c_void_p(status.data_ptr()), self.subsequence_bytes, stream)
-                    abi.launch(self._lib, "fear_jpeg_decode_u8_rows_dev", ctypes.c_void_p(images.ctypes.data), nd,
-                               ctypes.c_void_p(dev.data_ptr() + at_table), ctypes.c_void_p(mine.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                               plan["workspace_bytes"], stream)
+                    abi.launch(self._lib, "fear_jpeg_huffman_indexed_rows_dev", P(indexed.ctypes.data), nd, P(dev.data_ptr()), P(mine.data_ptr()),
+                               P(coef.data_ptr()), P(status.data_ptr()), self.subsequence_bytes, stream)
+                    abi.launch(self._lib, "fear_jpeg_decode_u8_rows_dev", P(images.ctypes.data), nd, P(table), P(mine.data_ptr()),
+                               P(ws.data_ptr()), plan["workspace_bytes"], stream)
                 verdict = torch.empty(nd, dtype=torch.int32, pin_memory=True)
                 verdict.copy_(status, non_blocking=True)
                 event = torch.cuda.Event()
                 event.record()
                 self._pending.append((event, verdict, lo + scan, sids))
-            rows = self._columns[group]
-            high, wide = -(-rows["H"].astype(np.int64) * (8 // scale) // 8), -(-rows["W"].astype(np.int64) * (8 // scale) // 8)
-            sizes = 3 * high * wide
-            for k in np.flatnonzero(rows["kind"] == KIND_PIXELS):        # the entries kept as pixels: a copy, never an alias
-                out[out_offset[k]:out_offset[k] + sizes[k]].copy_(self._pixels[int(group[k])].view(-1), non_blocking=True)
-        for k, (at, size, h, w) in enumerate(zip(out_offset.tolist(), sizes.tolist(), high.tolist(), wide.tolist())):
-            frames[lo + k] = out[at:at + size].view(h, w, 3)
+            cols = self._columns[group]
+            high, wide = _scaled_sides(cols["H"], cols["W"], scale)
+            for k in np.flatnonzero(cols["kind"] == KIND_PIXELS):        # the entries kept as pixels: a whole copy, never an alias
+                out[out_offset[k]:out_offset[k] + 3 * high[k] * wide[k]].copy_(self._pixels[int(group[k])].view(-1), non_blocking=True)
+        frames[lo:hi] = _frame_views(out, out_offset, high, wide)
+
+    def _block_start(self, stream):
+        """The dense block_start table that every record of `decode` points at, long enough for the store's largest image (a band has
+        no more blocks): written again when that grew, else waited for — it was written on whatever stream was current then."""
+        import torch
+        from . import train_abi as abi
+        if self._dense_blocks < self._most:
+            self._dense_retired.append(self._dense_start)
+            self._dense_start = torch.empty(self._most + 1, dtype=torch.int32, device=self.device)
+            abi.launch(self._lib, "fear_jpeg_dense_block_start", ctypes.c_void_p(self._dense_start.data_ptr()), self._most, stream)
+            self._dense_blocks, self._dense_event = self._most, torch.cuda.Event()
+            self._dense_event.record()
+        else:
+            torch.cuda.current_stream().wait_event(self._dense_event)
+        return self._dense_start
+
+    def _upload(self, parts: List[np.ndarray], pinned: bool = True):
+        """`parts` one after the other in one transfer, each at a multiple of 16 bytes: the device tensor and where each part begins.
+        Pinned and non-blocking, the staging buffer kept while the copy may run; `pinned=False` is `add`'s, which waits."""
+        import torch
+        at, end = [], 0
+        for part in parts:
+            at.append(_up(end, 16))
+            end = at[-1] + part.nbytes
+        staged = torch.empty(end, dtype=torch.uint8, pin_memory=pinned)
+        host = staged.numpy()
+        for a, part in zip(at, parts):
+            host[a:a + part.nbytes] = part.view(np.uint8)
+        if not pinned:
+            return staged.to(self.device), at
+        dev = torch.empty(end, dtype=torch.uint8, device=self.device)
+        dev.copy_(staged, non_blocking=True)
+        self._pinned = self._pinned[-1:] + [staged]
+        return dev, at
 
     # ------------------------------------------------------------------------------------------------------------------ decode_rows
     def decode_rows(self, ids, rows=None, check: bool = False, scale: int = 1) -> List:
@@ -735,80 +739,8 @@ class JpegStore:
         rows = np.asarray(rows)
         if rows.shape != (ids.size, 2) or not np.issubdtype(rows.dtype, np.integer):
             raise ValueError(f"rows must be ({ids.size}, 2) integers, one [y0, y1) per id")
-        frames: List = [None] * ids.size
-        self._pending = self._pending[-self.PENDING_CALLS:]
-        for plan in plan_decode_rows(self._columns, self._row_sub, ids, rows, self.workspace_limit, scale=scale):
-            self._decode_rows_group(ids, plan, frames, scale)
-        if check:
-            self.check()
-        return frames
-
-    def _decode_rows_group(self, ids: np.ndarray, plan: dict, frames: List, scale: int = 1) -> None:
-        import torch
-        from . import train_abi as abi
-        lo, hi, scan = plan["lo"], plan["hi"], plan["scan"]
-        group = ids[lo:hi]
-        sids, nd = group[scan], scan.size
-        with torch.cuda.device(self.device):
-            out = torch.empty(max(plan["out_bytes"], 16), dtype=torch.uint8, device=self.device)
-            out_offset = plan["out_offset"]
-            if nd:
-                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-                if self._dense_blocks < self._most:                      # the store's largest image grew; a band has no more blocks
-                    self._dense_retired.append(self._dense_start)
-                    self._dense_start = torch.empty(self._most + 1, dtype=torch.int32, device=self.device)
-                    abi.launch(self._lib, "fear_jpeg_dense_block_start", ctypes.c_void_p(self._dense_start.data_ptr()), self._most, stream)
-                    self._dense_blocks, self._dense_event = self._most, torch.cuda.Event()
-                    self._dense_event.record()
-                else:
-                    torch.cuda.current_stream().wait_event(self._dense_event)
-                coef = torch.empty(max(plan["values"], 8), dtype=torch.int16, device=self.device)
-                ws = torch.empty(plan["workspace_bytes"], dtype=torch.uint8, device=self.device)
-                status = torch.empty(nd, dtype=torch.int32, device=self.device)
-                indexed, images = self._indexed[sids], self._image[sids]  # gathers: private copies
-                indexed["coef_offset"] = plan["coef_offset"]
-                indexed["sub0"], indexed["sub_count"] = plan["sub0"], plan["sub_count"]
-                indexed["mcu_row0"], indexed["mcu_rows"] = plan["mcu_row0"], plan["mcu_rows"]
-                images["coef"] = np.uint64(coef.data_ptr()) + np.uint64(2) * plan["coef_offset"]
-                images["block_start"] = self._dense_start.data_ptr()
-                images["height"] = plan["band_height"]                   # the band as an image of its own, written into its frame's rows
-                images["out"] = np.uint64(out.data_ptr()) + (out_offset[scan] + plan["band_out"]).astype(np.uint64)
-                images["plane_offset"] = plan["plane_offset"]
-                prefixes = np.concatenate([plan["block_prefix"], plan["pixel_prefix"]])
-                at_indexed = _up(plan["sub_prefix"].nbytes, 16)
-                at_table = at_indexed + indexed.nbytes
-                at_images = at_table + _up(prefixes.nbytes, 16)
-                pinned = torch.empty(at_images + images.nbytes, dtype=torch.uint8, pin_memory=True)
-                host = pinned.numpy()
-                host[:at_indexed].view(np.uint32)[:nd + 1] = plan["sub_prefix"]
-                host[at_indexed:at_table] = indexed.view(np.uint8)
-                host[at_table:at_images].view(np.uint32)[:2 * nd + 2] = prefixes
-                host[at_images:] = images.view(np.uint8)
-                dev = torch.empty(pinned.numel(), dtype=torch.uint8, device=self.device)
-                dev.copy_(pinned, non_blocking=True)
-                self._pinned = self._pinned[-1:] + [pinned]
-                self._records = (indexed, images)
-                self.last_upload_bytes = pinned.numel()
-                abi.launch(self._lib, "fear_jpeg_huffman_indexed_rows", ctypes.c_void_p(indexed.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr()),
-                           ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(status.data_ptr()), self.subsequence_bytes, stream)
-                if scale == 1:
-                    abi.launch(self._lib, "fear_jpeg_decode_u8", ctypes.c_void_p(images.ctypes.data), nd, ctypes.c_void_p(dev.data_ptr() + at_table),
-                               ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"], stream)
-                else:
-                    abi.launch(self._lib, "fear_jpeg_decode_scaled_u8", ctypes.c_void_p(images.ctypes.data), nd,
-                               ctypes.c_void_p(dev.data_ptr() + at_table), scale, ctypes.c_void_p(ws.data_ptr()), plan["workspace_bytes"], stream)
-                verdict = torch.empty(nd, dtype=torch.int32, pin_memory=True)
-                verdict.copy_(status, non_blocking=True)
-                event = torch.cuda.Event()
-                event.record()
-                self._pending.append((event, verdict, lo + scan, sids))
-            cols = self._columns[group]
-            high, wide = -(-cols["H"].astype(np.int64) * (8 // scale) // 8), -(-cols["W"].astype(np.int64) * (8 // scale) // 8)
-            sizes = 3 * high * wide
-            for k in np.flatnonzero(cols["kind"] == KIND_PIXELS):        # the entries kept as pixels: a whole copy, never an alias
-                out[out_offset[k]:out_offset[k] + sizes[k]].copy_(self._pixels[int(group[k])].view(-1), non_blocking=True)
-        for k, (at, size, h, w) in enumerate(zip(out_offset.tolist(), sizes.tolist(), high.tolist(), wide.tolist())):
-            frames[lo + k] = out[at:at + size].view(h, w, 3)
+        return self._decode_groups(ids, plan_decode_rows(self._columns, self._row_sub, ids, rows, self.workspace_limit, scale=scale), check,
+                                   scale=scale)
 
     def check(self) -> None:
         """Wait for the calls not yet checked and raise MalformedJPEG for the first image the device refused, naming the position in its

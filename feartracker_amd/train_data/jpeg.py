@@ -82,6 +82,14 @@ def jpeg_idct_islow(coef: np.ndarray) -> np.ndarray:
     return np.stack(_idct_pass([c[..., i] for i in range(8)], False), axis=-1)             # rows
 
 
+def _jpeg_ycc_to_rgb(y: np.ndarray, cb: np.ndarray, cr: np.ndarray) -> np.ndarray:
+    """jdcolor's YCbCr -> RGB on int64 planes (h, w), `cb` and `cr` less 128: uint8 (h, w, 3), clamped."""
+    r = y + ((91881 * cr + 32768) >> 16)
+    g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
+    b = y + ((116130 * cb + 32768) >> 16)
+    return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
+
+
 def _jpeg_plane(plane: np.ndarray, q: np.ndarray) -> np.ndarray:
     """One component through FDCT, quantiser, dequantiser and IDCT: int64 (h, w) in 0..255 -> int64 (h, w) in 0..255."""
     h, w = plane.shape
@@ -126,7 +134,4 @@ def jpeg_roundtrip_u8_host(crop_u8: np.ndarray, quality: int) -> np.ndarray:
     y = _jpeg_plane(y, q_luma)
     cb = _jpeg_upsample(_jpeg_plane(down(cb), q_chroma)) - 128
     cr = _jpeg_upsample(_jpeg_plane(down(cr), q_chroma)) - 128
-    r = y + ((91881 * cr + 32768) >> 16)
-    b = y + ((116130 * cb + 32768) >> 16)
-    g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
-    return np.clip(np.stack([b, g, r], axis=-1), 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(_jpeg_ycc_to_rgb(y, cb, cr)[..., ::-1])                 # libjpeg's R, G, B back into cv2's B, G, R
