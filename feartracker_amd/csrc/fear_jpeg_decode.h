@@ -10,20 +10,21 @@
 //   jpeg_decode_merge_kernel   one pixel per lane: upsampling by the image's mode at the true edges of the chroma planes, YCbCr -> RGB,
 //                              store; pixels past the image's last are not stored
 // The device never sees the bitstream: every loop is bounded by a constant, and a block reads at most 64 values whatever its offsets say.
-// fear_jpeg_decode_u8_rows_dev runs the same two kernels for the pixel rows [y0, y1) of each image, read from device memory (jr_band,
-// jpeg_decode_blocks_rows_dev_kernel, jpeg_decode_merge_rows_dev_kernel; DESIGN.md section 14, "Rows from the device").
+// fear_jpeg_decode_u8_rows_dev runs the same two bodies (jd_blocks<true>, jd_merge<true>: the tests on the band are the only difference)
+// for the pixel rows [y0, y1) of each image, read from device memory (jr_band; DESIGN.md section 14, "Rows from the device").
+// The pieces every pixel kernel is made of are written once, here, and fear_jpeg_scaled.h uses them too: the block load (jd_load_block),
+// the block's home (jd_home), the sample pack (js_sample, jd_pack4), the upsampling filters (jd_taps, jd_h2v1, jd_h2v2), the colour conversion and
+// store (jd_store_rgb), and on the host the one check of records and workspace (jd_check).
 // Included by fear_train.hip behind fear_train_jpeg.h, whose transforms and LDS pitch it uses.
 
 namespace {
-
-__device__ const uint8_t kJdZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                          41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                          30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 struct JpegDecodeArgs {
     const uint32_t* table;   // the caller's device table: two prefix tables of n + 1 entries, padding, n FearJpegImage records
     uint8_t* planes;         // the workspace, 16-byte aligned
     int n;
+    int m;                   // the side of a block in frame pixels: 8, and 8 / scale = 4, 2 or 1 in fear_jpeg_scaled.h, whose second
+                             // prefix table counts scaled pixels
 };
 
 // The image a workgroup belongs to: the i in [0, n) with start[i] <= group < start[i + 1].  n <= 65535: at most 16 halvings.
@@ -71,20 +72,33 @@ __device__ __forceinline__ bool jr_band(int y0, int y1, int limit, int mcu_h, in
     return *a < *b;
 }
 
-__global__ __launch_bounds__(256) void jpeg_decode_blocks_kernel(JpegDecodeArgs a) {
-    __shared__ __attribute__((aligned(16))) int blk[FEAR_JPEG_GROUP_BLOCKS * kJpPitch];
-    const int tid = threadIdx.x, lb = tid >> 3, k = tid & 7;
-    const int img = jd_find_image(a.table, a.n, blockIdx.x);
-    const FearJpegImage* im = jd_records(a) + img;
-    const JdGeom g = jd_geom(im->width, im->height, im->components, im->h, im->v);
-    const long b = (long)(blockIdx.x - a.table[img]) * FEAR_JPEG_GROUP_BLOCKS + lb;
-    const bool on = b < g.n0 + 2 * g.nc;
-    const int comp = b < g.n0 ? 0 : (b < g.n0 + g.nc ? 1 : 2);
-    int* base = blk + lb * kJpPitch;
+// The component of block b of an image (the planes' blocks follow one another: luma, Cb, Cr) and the block's home in its plane.
+__device__ __forceinline__ int jd_comp(const JdGeom& g, long b) {
+    return b < g.n0 ? 0 : (b < g.n0 + g.nc ? 1 : 2);
+}
+
+struct JdHome {
+    long rb, by, bx;         // the block within its plane | its row and column of blocks
+    int pw;                  // blocks per row of the plane
+};
+
+__device__ __forceinline__ JdHome jd_home(const JdGeom& g, int comp, long b) {
+    JdHome at;
+    at.rb = b - (comp == 0 ? 0 : (comp == 1 ? g.n0 : g.n0 + g.nc));
+    at.pw = comp == 0 ? g.bw0 : g.bwc;
+    at.by = at.rb / at.pw;
+    at.bx = at.rb - at.by * at.pw;
+    return at;
+}
+
+// Block b of component comp into `base` (the block's 64 ints of LDS; lane k of its eight): zeroed, then — `on` — the stored values from
+// zigzag to natural order, times the quantiser.  At most 64 values are read whatever the offsets say.  Two barriers: every lane of the
+// workgroup calls it.
+__device__ __forceinline__ void jd_load_block(int* base, int k, bool on, const FearJpegImage* im, long b, int comp) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) base[k * 8 + i] = 0;
     __syncthreads();
-    if (on) {                                                 // the stored values: zigzag -> natural order, times the quantiser
+    if (on) {
         const uint32_t s = im->block_start[b], e = im->block_start[b + 1];
         const int cnt = e > s ? (int)min(e - s, 64u) : 0;
         const int16_t* c = im->coef + s;
@@ -93,88 +107,59 @@ __global__ __launch_bounds__(256) void jpeg_decode_blocks_kernel(JpegDecodeArgs 
         for (int j = 0; j < 8; ++j) {
             const int i = k + 8 * j;
             if (i < cnt) {
-                const int nat = kJdZigzag[i];
+                const int nat = fear_jpeg::kZigzagDev.v[i];
                 base[nat] = (int)c[i] * (int)q[nat];
             }
         }
     }
     __syncthreads();
-    int d[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) d[i] = base[i * 8 + k];       // columns
-    jpeg_idct<true>(d);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) base[i * 8 + k] = d[i];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) d[i] = base[k * 8 + i];       // rows, level shift, clamp, one 8-byte store
-    jpeg_idct<false>(d);
-    if (on) {
-        const long rb = b - (comp == 0 ? 0 : (comp == 1 ? g.n0 : g.n0 + g.nc));
-        const int pw = comp == 0 ? g.bw0 : g.bwc;
-        const long by = rb / pw, bx = rb - by * pw;
-        uint32_t lo = 0u, hi = 0u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            lo |= (uint32_t)min(max(d[i] + 128, 0), 255) << (8 * i);
-            hi |= (uint32_t)min(max(d[i + 4] + 128, 0), 255) << (8 * i);
-        }
-        // plane_offset is a multiple of 16, a plane's size one of 64, a row of blocks' one of 8: every block row is 8-byte aligned
-        uint8_t* dst = a.planes + im->plane_offset + (b - rb) * 64 + ((by * 8 + k) * pw + bx) * 8;
-        *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
-    }
 }
 
-__global__ __launch_bounds__(256) void jpeg_decode_merge_kernel(JpegDecodeArgs a) {
-    const uint32_t* start = a.table + (a.n + 1);
-    const int img = jd_find_image(start, a.n, blockIdx.x);
-    const FearJpegImage* im = jd_records(a) + img;
-    const int W = im->width, H = im->height, h = im->h, v = im->v;
-    const long px = (long)(blockIdx.x - start[img]) * FEAR_JPEG_GROUP_PIXELS + threadIdx.x;
-    if (px >= (long)H * W) return;
-    const int y = (int)(px / W), x = (int)(px - (long)y * W);
-    const JdGeom g = jd_geom(W, H, im->components, h, v);
-    const uint8_t* planes = a.planes + im->plane_offset;
-    const int Y = planes[(long)y * (g.bw0 * 8) + x];
-    int r = Y, gg = Y, b = Y;
-    if (im->components == 3) {
-        const uint8_t* pcb = planes + g.n0 * 64;
-        const uint8_t* pcr = pcb + g.nc * 64;
-        const long pwc = g.bwc * 8;
-        const int cw = (W + h - 1) / h, ch = (H + v - 1) / v;  // the true size of a chroma plane
-        int cb, cr;
-        if (h == 1 || cw <= 2) {                               // no upsampling | replication (libjpeg does not filter a plane this narrow)
-            const long at = (long)(y / v) * pwc + x / h;
-            cb = pcb[at]; cr = pcr[at];
-        } else if (v == 1) {                                   // h2v1 fancy: 3 this + neighbour; an edge sample is its own neighbour
-            const int cx = x >> 1, nx = (x & 1) ? min(cx + 1, cw - 1) : max(cx - 1, 0), round = (x & 1) ? 2 : 1;
-            const long row = (long)y * pwc;
-            cb = (3 * pcb[row + cx] + pcb[row + nx] + round) >> 2;
-            cr = (3 * pcr[row + cx] + pcr[row + nx] + round) >> 2;
-        } else {                                               // h2v2 fancy: 3 near + far on both axes, as jpeg_merge_kernel
-            const int cy = y >> 1, cx = x >> 1;
-            const long near = (long)cy * pwc, far = (long)((y & 1) ? min(cy + 1, ch - 1) : max(cy - 1, 0)) * pwc;
-            const int nx = (x & 1) ? min(cx + 1, cw - 1) : max(cx - 1, 0), round = (x & 1) ? 7 : 8;
-            cb = (3 * (3 * pcb[near + cx] + pcb[far + cx]) + 3 * pcb[near + nx] + pcb[far + nx] + round) >> 4;
-            cr = (3 * (3 * pcr[near + cx] + pcr[far + cx]) + 3 * pcr[near + nx] + pcr[far + nx] + round) >> 4;
-        }
-        cb -= 128; cr -= 128;
-        r = Y + ((91881 * cr + 32768) >> 16);
-        b = Y + ((116130 * cb + 32768) >> 16);
-        gg = Y + ((-22554 * cb - 46802 * cr + 32768) >> 16);
-    }
-    uint8_t* dst = im->out + px * 3;
+// Level shift and clamp of one sample | four of them in one word, the first in the low byte.
+__device__ __forceinline__ uint32_t js_sample(int x) {
+    return (uint32_t)min(max(x + 128, 0), 255);
+}
+
+__device__ __forceinline__ uint32_t jd_pack4(const int* d) {
+    return js_sample(d[0]) | js_sample(d[1]) << 8 | js_sample(d[2]) << 16 | js_sample(d[3]) << 24;
+}
+
+// libjpeg's fancy upsampling.  The chroma columns pixel column x reads on a plane of true width cw: its own and the nearer neighbour's
+// (an edge sample is its own neighbour).  h2v1: 3 this + neighbour, in the plane's row that starts at `row`.  h2v2: 3 near + far on
+// both axes (the rows that start at `near` and `far`), as jpeg_merge_kernel.
+struct JdTaps {
+    int cx, nx;
+    bool odd;
+};
+
+__device__ __forceinline__ JdTaps jd_taps(int x, int cw) {
+    const int cx = x >> 1;
+    return JdTaps{cx, (x & 1) ? min(cx + 1, cw - 1) : max(cx - 1, 0), (x & 1) != 0};
+}
+
+__device__ __forceinline__ int jd_h2v1(const uint8_t* plane, long row, const JdTaps& t) {
+    return (3 * plane[row + t.cx] + plane[row + t.nx] + (t.odd ? 2 : 1)) >> 2;
+}
+
+__device__ __forceinline__ int jd_h2v2(const uint8_t* plane, long near, long far, const JdTaps& t) {
+    return (3 * (3 * plane[near + t.cx] + plane[far + t.cx]) + 3 * plane[near + t.nx] + plane[far + t.nx] + (t.odd ? 7 : 8)) >> 4;
+}
+
+// jdcolor's YCbCr -> RGB in 16-bit fixed point, clamp, store.  cb = cr = 128 is gray: every product is 0 and the pixel is Y three times.
+__device__ __forceinline__ void jd_store_rgb(int Y, int cb, int cr, uint8_t* dst) {
+    cb -= 128; cr -= 128;
+    const int r = Y + ((91881 * cr + 32768) >> 16);
+    const int b = Y + ((116130 * cb + 32768) >> 16);
+    const int g = Y + ((-22554 * cb - 46802 * cr + 32768) >> 16);
     dst[0] = (uint8_t)min(max(r, 0), 255);
-    dst[1] = (uint8_t)min(max(gg, 0), 255);
+    dst[1] = (uint8_t)min(max(g, 0), 255);
     dst[2] = (uint8_t)min(max(b, 0), 255);
 }
 
-// The two kernels of fear_jpeg_decode_u8_rows_dev.  They repeat the two above line for line, with the tests on the band added, instead of
-// sharing a template with them: the code of the kernels above is pinned (their disassembly is compared with the last release's, DESIGN.md
-// section 14, "Rows from the device"), and hipcc orders the operands of the IDCT's additions differently once the body is inlined from a
-// template.  A block whose MCU row lies outside the band of `rows_dev` (device memory) is skipped, and a workgroup all of whose blocks are
-// skipped returns in front of its work.
-__global__ __launch_bounds__(256) void jpeg_decode_blocks_rows_dev_kernel(JpegDecodeArgs a, const int32_t* rows_dev) {
+// The block stage at full size.  ROWS: a block whose MCU row lies outside the band of `rows_dev` (device memory; null otherwise) is
+// skipped, and a workgroup all of whose blocks are skipped returns in front of its work.
+template <bool ROWS>
+__device__ __forceinline__ void jd_blocks(const JpegDecodeArgs& a, const int32_t* rows_dev) {
     __shared__ __attribute__((aligned(16))) int blk[FEAR_JPEG_GROUP_BLOCKS * kJpPitch];
     const int tid = threadIdx.x, lb = tid >> 3, k = tid & 7;
     const int img = jd_find_image(a.table, a.n, blockIdx.x);
@@ -182,35 +167,19 @@ __global__ __launch_bounds__(256) void jpeg_decode_blocks_rows_dev_kernel(JpegDe
     const JdGeom g = jd_geom(im->width, im->height, im->components, im->h, im->v);
     const long b = (long)(blockIdx.x - a.table[img]) * FEAR_JPEG_GROUP_BLOCKS + lb;
     bool on = b < g.n0 + 2 * g.nc;
-    const int comp = b < g.n0 ? 0 : (b < g.n0 + g.nc ? 1 : 2);
-    const int v = im->v == 2 ? 2 : 1, mcus_y = (im->height + 8 * v - 1) / (8 * v);
-    int ba, bb;
-    const bool some = jr_band(rows_dev[2 * img], rows_dev[2 * img + 1], im->height, 8 * v, mcus_y, v == 2, &ba, &bb);
-    if (on) {
-        const long rb = b - (comp == 0 ? 0 : (comp == 1 ? g.n0 : g.n0 + g.nc));
-        const long row = rb / (comp == 0 ? g.bw0 : g.bwc) / (comp == 0 ? v : 1);      // the block's MCU row
-        on = some && row >= ba && row < bb;
-    }
-    if (!__syncthreads_or(on)) return;                        // the same for the whole workgroup
-    int* base = blk + lb * kJpPitch;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) base[k * 8 + i] = 0;
-    __syncthreads();
-    if (on) {                                                 // the stored values: zigzag -> natural order, times the quantiser
-        const uint32_t s = im->block_start[b], e = im->block_start[b + 1];
-        const int cnt = e > s ? (int)min(e - s, 64u) : 0;
-        const int16_t* c = im->coef + s;
-        const uint16_t* q = im->qt[comp];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int i = k + 8 * j;
-            if (i < cnt) {
-                const int nat = kJdZigzag[i];
-                base[nat] = (int)c[i] * (int)q[nat];
-            }
+    const int comp = jd_comp(g, b);
+    if (ROWS) {
+        const int v = im->v == 2 ? 2 : 1, mcus_y = (im->height + 8 * v - 1) / (8 * v);
+        int ba, bb;
+        const bool some = jr_band(rows_dev[2 * img], rows_dev[2 * img + 1], im->height, 8 * v, mcus_y, v == 2, &ba, &bb);
+        if (on) {
+            const long row = jd_home(g, comp, b).by / (comp == 0 ? v : 1);            // the block's MCU row
+            on = some && row >= ba && row < bb;
         }
+        if (!__syncthreads_or(on)) return;                    // the same for the whole workgroup
     }
-    __syncthreads();
+    int* base = blk + lb * kJpPitch;
+    jd_load_block(base, k, on, im, b, comp);
     int d[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) d[i] = base[i * 8 + k];       // columns
@@ -222,25 +191,24 @@ __global__ __launch_bounds__(256) void jpeg_decode_blocks_rows_dev_kernel(JpegDe
     for (int i = 0; i < 8; ++i) d[i] = base[k * 8 + i];       // rows, level shift, clamp, one 8-byte store
     jpeg_idct<false>(d);
     if (on) {
-        const long rb = b - (comp == 0 ? 0 : (comp == 1 ? g.n0 : g.n0 + g.nc));
-        const int pw = comp == 0 ? g.bw0 : g.bwc;
-        const long by = rb / pw, bx = rb - by * pw;
-        uint32_t lo = 0u, hi = 0u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            lo |= (uint32_t)min(max(d[i] + 128, 0), 255) << (8 * i);
-            hi |= (uint32_t)min(max(d[i + 4] + 128, 0), 255) << (8 * i);
-        }
+        const JdHome at = jd_home(g, comp, b);
         // plane_offset is a multiple of 16, a plane's size one of 64, a row of blocks' one of 8: every block row is 8-byte aligned
-        uint8_t* dst = a.planes + im->plane_offset + (b - rb) * 64 + ((by * 8 + k) * pw + bx) * 8;
-        *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
+        uint8_t* dst = a.planes + im->plane_offset + (b - at.rb) * 64 + ((at.by * 8 + k) * at.pw + at.bx) * 8;
+        *reinterpret_cast<uint2*>(dst) = make_uint2(jd_pack4(d), jd_pack4(d + 4));
     }
 }
 
-// One pixel per lane, of the rows [y0, y1) of `rows_dev` alone.  Their luma lies in the band's MCU rows without the halo and every chroma
-// row they read — one above and below with v == 2 — in the band with it, or the row is clamped at a true edge of the image: no plane byte
-// is read that jpeg_decode_blocks_rows_dev_kernel has not written in the same call.
-__global__ __launch_bounds__(256) void jpeg_decode_merge_rows_dev_kernel(JpegDecodeArgs a, const int32_t* rows_dev) {
+__global__ __launch_bounds__(256) void jpeg_decode_blocks_kernel(JpegDecodeArgs a) { jd_blocks<false>(a, nullptr); }
+
+__global__ __launch_bounds__(256) void jpeg_decode_blocks_rows_dev_kernel(JpegDecodeArgs a, const int32_t* rows_dev) {
+    jd_blocks<true>(a, rows_dev);
+}
+
+// The pixel stage at full size, one pixel per lane.  ROWS: of the rows [y0, y1) of `rows_dev` alone.  Their luma lies in the band's MCU
+// rows without the halo and every chroma row they read — one above and below with v == 2 — in the band with it, or the row is clamped at
+// a true edge of the image: no plane byte is read that jd_blocks<true> has not written in the same call.
+template <bool ROWS>
+__device__ __forceinline__ void jd_merge(const JpegDecodeArgs& a, const int32_t* rows_dev) {
     const uint32_t* start = a.table + (a.n + 1);
     const int img = jd_find_image(start, a.n, blockIdx.x);
     const FearJpegImage* im = jd_records(a) + img;
@@ -248,41 +216,37 @@ __global__ __launch_bounds__(256) void jpeg_decode_merge_rows_dev_kernel(JpegDec
     const long px = (long)(blockIdx.x - start[img]) * FEAR_JPEG_GROUP_PIXELS + threadIdx.x;
     if (px >= (long)H * W) return;
     const int y = (int)(px / W), x = (int)(px - (long)y * W);
-    if (y < min(max(rows_dev[2 * img], 0), H) || y >= min(max(rows_dev[2 * img + 1], 0), H)) return;   // the clip to [0, H]
+    if (ROWS && (y < min(max(rows_dev[2 * img], 0), H) || y >= min(max(rows_dev[2 * img + 1], 0), H))) return;   // the clip to [0, H]
     const JdGeom g = jd_geom(W, H, im->components, h, v);
     const uint8_t* planes = a.planes + im->plane_offset;
     const int Y = planes[(long)y * (g.bw0 * 8) + x];
-    int r = Y, gg = Y, b = Y;
+    int cb = 128, cr = 128;
     if (im->components == 3) {
         const uint8_t* pcb = planes + g.n0 * 64;
         const uint8_t* pcr = pcb + g.nc * 64;
         const long pwc = g.bwc * 8;
         const int cw = (W + h - 1) / h, ch = (H + v - 1) / v;  // the true size of a chroma plane
-        int cb, cr;
         if (h == 1 || cw <= 2) {                               // no upsampling | replication (libjpeg does not filter a plane this narrow)
             const long at = (long)(y / v) * pwc + x / h;
             cb = pcb[at]; cr = pcr[at];
-        } else if (v == 1) {                                   // h2v1 fancy: 3 this + neighbour; an edge sample is its own neighbour
-            const int cx = x >> 1, nx = (x & 1) ? min(cx + 1, cw - 1) : max(cx - 1, 0), round = (x & 1) ? 2 : 1;
+        } else if (v == 1) {
             const long row = (long)y * pwc;
-            cb = (3 * pcb[row + cx] + pcb[row + nx] + round) >> 2;
-            cr = (3 * pcr[row + cx] + pcr[row + nx] + round) >> 2;
-        } else {                                               // h2v2 fancy: 3 near + far on both axes, as jpeg_merge_kernel
-            const int cy = y >> 1, cx = x >> 1;
+            const JdTaps t = jd_taps(x, cw);
+            cb = jd_h2v1(pcb, row, t); cr = jd_h2v1(pcr, row, t);
+        } else {
+            const int cy = y >> 1;
             const long near = (long)cy * pwc, far = (long)((y & 1) ? min(cy + 1, ch - 1) : max(cy - 1, 0)) * pwc;
-            const int nx = (x & 1) ? min(cx + 1, cw - 1) : max(cx - 1, 0), round = (x & 1) ? 7 : 8;
-            cb = (3 * (3 * pcb[near + cx] + pcb[far + cx]) + 3 * pcb[near + nx] + pcb[far + nx] + round) >> 4;
-            cr = (3 * (3 * pcr[near + cx] + pcr[far + cx]) + 3 * pcr[near + nx] + pcr[far + nx] + round) >> 4;
+            const JdTaps t = jd_taps(x, cw);
+            cb = jd_h2v2(pcb, near, far, t); cr = jd_h2v2(pcr, near, far, t);
         }
-        cb -= 128; cr -= 128;
-        r = Y + ((91881 * cr + 32768) >> 16);
-        b = Y + ((116130 * cb + 32768) >> 16);
-        gg = Y + ((-22554 * cb - 46802 * cr + 32768) >> 16);
     }
-    uint8_t* dst = im->out + px * 3;
-    dst[0] = (uint8_t)min(max(r, 0), 255);
-    dst[1] = (uint8_t)min(max(gg, 0), 255);
-    dst[2] = (uint8_t)min(max(b, 0), 255);
+    jd_store_rgb(Y, cb, cr, im->out + px * 3);
+}
+
+__global__ __launch_bounds__(256) void jpeg_decode_merge_kernel(JpegDecodeArgs a) { jd_merge<false>(a, nullptr); }
+
+__global__ __launch_bounds__(256) void jpeg_decode_merge_rows_dev_kernel(JpegDecodeArgs a, const int32_t* rows_dev) {
+    jd_merge<true>(a, rows_dev);
 }
 
 bool jd_mode_ok(int components, int h, int v) {
@@ -290,23 +254,21 @@ bool jd_mode_ok(int components, int h, int v) {
     return components == 3 && ((h == 1 && v == 1) || (h == 2 && v == 1) || (h == 2 && v == 2));
 }
 
-}  // namespace
+// What the two launches of a pixel stage take: the kernels' argument and the two grids.  block_groups == 0: nothing to launch (n == 0).
+struct JdLaunch {
+    JpegDecodeArgs a;
+    unsigned block_groups, pixel_groups;
+};
 
-extern "C" {
-
-size_t fear_jpeg_decode_workspace_bytes(const FearJpegInfo* infos, int n) {
-    if (!infos || n < 0 || n > 65535) return 0;
-    size_t sum = 16;                                          // the planes start at the next 16-byte boundary
-    for (int i = 0; i < n; ++i) sum += (size_t)infos[i].total_blocks * 64;
-    return sum;
-}
-
-// The checks and the two launches of fear_jpeg_decode_u8 and fear_jpeg_decode_u8_rows_dev (`rows_dev` null: the first).
-static int jd_decode_u8(const FearJpegImage* images, int n, const uint32_t* group_start, const int32_t* rows_dev, bool rows, void* workspace,
-                        size_t workspace_bytes, void* stream) {
+// The one check of the records and the workspace, for frames of m / 8 of the images' sizes (m = 8: full size), in the order the ABI
+// states: n, the null pointers of the call (`missing`: one the entry point has tested itself), each record's, each record's shape, the
+// workspace, the grids.  fear_jpeg_decode_workspace_bytes' bound holds at every m: the scaled planes are no larger.
+int jd_check(const FearJpegImage* images, int n, const uint32_t* group_start, bool missing, int m, void* workspace, size_t workspace_bytes,
+             JdLaunch* out) {
+    *out = JdLaunch{};
     if (n < 0 || n > 65535) return FEAR_TRAIN_ERR_SHAPE;
     if (n == 0) return FEAR_TRAIN_OK;
-    if (!images || !group_start || (rows && !rows_dev)) return FEAR_TRAIN_ERR_NULL;
+    if (!images || !group_start || missing) return FEAR_TRAIN_ERR_NULL;
     uint64_t block_groups = 0, pixel_groups = 0;
     for (int i = 0; i < n; ++i) {
         const FearJpegImage& im = images[i];
@@ -322,26 +284,47 @@ static int jd_decode_u8(const FearJpegImage* images, int n, const uint32_t* grou
         const uint64_t blocks = (uint64_t)(g.n0 + 2 * g.nc);
         if (workspace_bytes < 16 || im.plane_offset > workspace_bytes - 16 || blocks * 64 > workspace_bytes - 16 - im.plane_offset)
             return FEAR_TRAIN_ERR_WORKSPACE;
+        const uint64_t sw = ((uint64_t)im.width * m + 7) / 8, sh = ((uint64_t)im.height * m + 7) / 8;
         block_groups += (blocks + FEAR_JPEG_GROUP_BLOCKS - 1) / FEAR_JPEG_GROUP_BLOCKS;
-        pixel_groups += ((uint64_t)im.width * im.height + FEAR_JPEG_GROUP_PIXELS - 1) / FEAR_JPEG_GROUP_PIXELS;
+        pixel_groups += (sw * sh + FEAR_JPEG_GROUP_PIXELS - 1) / FEAR_JPEG_GROUP_PIXELS;
     }
     if (block_groups > 0x7fffffffu || pixel_groups > 0x7fffffffu) return FEAR_TRAIN_ERR_SHAPE;
-    JpegDecodeArgs a{};
-    a.table = group_start;
-    a.planes = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
-    a.n = n;
+    out->a.table = group_start;
+    out->a.planes = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
+    out->a.n = n;
+    out->a.m = m;
+    out->block_groups = (unsigned)block_groups;
+    out->pixel_groups = (unsigned)pixel_groups;
+    return FEAR_TRAIN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t fear_jpeg_decode_workspace_bytes(const FearJpegInfo* infos, int n) {
+    if (!infos || n < 0 || n > 65535) return 0;
+    size_t sum = 16;                                          // the planes start at the next 16-byte boundary
+    for (int i = 0; i < n; ++i) sum += (size_t)infos[i].total_blocks * 64;
+    return sum;
+}
+
+// The check and the two launches of fear_jpeg_decode_u8 and fear_jpeg_decode_u8_rows_dev (`rows`: the second).
+static int jd_decode_u8(const FearJpegImage* images, int n, const uint32_t* group_start, const int32_t* rows_dev, bool rows, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    JdLaunch l;
+    const int status = jd_check(images, n, group_start, rows && !rows_dev, 8, workspace, workspace_bytes, &l);
+    if (status != FEAR_TRAIN_OK || l.block_groups == 0) return status;
     if (rows) {
-        hipLaunchKernelGGL(jpeg_decode_blocks_rows_dev_kernel, dim3((unsigned)block_groups), dim3(256), 0, static_cast<hipStream_t>(stream), a,
-                           rows_dev);
+        hipLaunchKernelGGL(jpeg_decode_blocks_rows_dev_kernel, dim3(l.block_groups), dim3(256), 0, static_cast<hipStream_t>(stream), l.a, rows_dev);
         LAUNCH_CHECK();
-        hipLaunchKernelGGL(jpeg_decode_merge_rows_dev_kernel, dim3((unsigned)pixel_groups), dim3(256), 0, static_cast<hipStream_t>(stream), a,
-                           rows_dev);
+        hipLaunchKernelGGL(jpeg_decode_merge_rows_dev_kernel, dim3(l.pixel_groups), dim3(256), 0, static_cast<hipStream_t>(stream), l.a, rows_dev);
         LAUNCH_CHECK();
         return FEAR_TRAIN_OK;
     }
-    hipLaunchKernelGGL(jpeg_decode_blocks_kernel, dim3((unsigned)block_groups), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(jpeg_decode_blocks_kernel, dim3(l.block_groups), dim3(256), 0, static_cast<hipStream_t>(stream), l.a);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(jpeg_decode_merge_kernel, dim3((unsigned)pixel_groups), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(jpeg_decode_merge_kernel, dim3(l.pixel_groups), dim3(256), 0, static_cast<hipStream_t>(stream), l.a);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }

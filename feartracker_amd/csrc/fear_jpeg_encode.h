@@ -1,7 +1,7 @@
 // fear_jpeg_encode.h — baseline JPEG files (4:2:0, 4:2:2, 4:4:4 or one gray component) written on gfx950 from uint8 frames: the counterpart of fear_jpeg_decode.h and
 // fear_jpeg_huffman.h (include/fear_train.h states the ABI and the passes, DESIGN.md section 14 "Writing JPEG files" the contract;
 // jpeg_encode.jpeg_encode_host restates it in numpy and equals Pillow's libjpeg-turbo byte for byte).  The forward transform shares
-// jpeg_fdct, kJpegBase and the LDS pitch with fear_train_jpeg.h; what is new is frames of any size, the Huffman coder in parallel and
+// jpeg_fdct and the LDS pitch with fear_train_jpeg.h, and reads the zigzag order and the base quantiser from fear_jpeg_tables.h; what is new is frames of any size, the Huffman coder in parallel and
 // the byte stream.
 //
 // Why each launch boundary is there: every one is a dependency across workgroups.
@@ -54,19 +54,6 @@ inline bool enc_sampling_ok(uint32_t sampling) {
 }
 // where the DHT segments stand in a header: behind SOI, APP0, the DQT segments and SOF0
 __host__ __device__ inline uint32_t enc_dht_at(int mode) { return mode == FEAR_JPEG_ENC_GRAY ? 20 + 69 + 13 : 20 + 2 * 69 + 19; }
-
-// zigzag position -> natural index
-constexpr uint8_t kEncZigzagHost[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                        41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                        30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-__device__ const uint8_t kEncZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                           41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                           30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-constexpr uint8_t kEncBaseHost[128] = {
-    16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
-    18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,  49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99,
-    17, 18, 24, 47, 99,  99,  99,  99,  18, 21, 26, 66, 99,  99,  99,  99,  24, 26, 56, 99, 99,  99,  99,  99,  47, 66, 99, 99, 99,  99,  99,  99,
-    99, 99, 99, 99, 99,  99,  99,  99,  99, 99, 99, 99, 99,  99,  99,  99,  99, 99, 99, 99, 99,  99,  99,  99,  99, 99, 99, 99, 99,  99,  99,  99};
 
 // T.81 tables K.3 to K.6 in the order of the file's DHT segments and of the code table below: DC 0, AC 0, DC 1, AC 1
 struct EncStdTable {
@@ -330,8 +317,8 @@ __device__ __forceinline__ void enc_store(const int* blk, uint32_t* dst, const E
             v0 = z == 0 ? sb[0] : 0;
             v1 = 0;
         } else {
-            v0 = sb[kEncZigzag[z]];
-            v1 = sb[kEncZigzag[z + 1]];
+            v0 = sb[fear_jpeg::kZigzagDev.v[z]];
+            v1 = sb[fear_jpeg::kZigzagDev.v[z + 1]];
         }
         dst[e] = ((uint32_t)v0 & 0xFFFFu) | ((uint32_t)v1 << 16);
     }
@@ -356,7 +343,7 @@ __global__ __launch_bounds__(256) void jpeg_enc_transform_kernel(EncArgs a) {
     t.group = (int)(blockIdx.x - r->start[0]);
     if (tid < 128) {                                          // jpeg_set_quality(quality, force_baseline)
         const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
-        qt[tid] = min(max(((int)kJpegBase[tid] * scale + 50) / 100, 1), 255);
+        qt[tid] = min(max(((int)fear_jpeg::kBaseQuantDev.v[tid] * scale + 50) / 100, 1), 255);
     }
     if (mode == 0) enc_fill_420(blk, src, t, tid);
     else if (mode == 1) enc_fill_422(blk, src, t, tid);
@@ -913,7 +900,7 @@ int fear_jpeg_encode_header_flags(int width, int height, int quality, int restar
     const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
     for (int t = 0; t < tables; ++t) {
         put({0xFF, 0xDB, 0, 67, t});
-        for (int z = 0; z < 64; ++z) h[at++] = (uint8_t)std::min(std::max(((int)kEncBaseHost[t * 64 + kEncZigzagHost[z]] * scale + 50) / 100, 1), 255);
+        for (int z = 0; z < 64; ++z) h[at++] = (uint8_t)std::min(std::max(((int)fear_jpeg::kBaseQuant[t * 64 + fear_jpeg::kZigzag[z]] * scale + 50) / 100, 1), 255);
     }
     if (gray) put({0xFF, 0xC0, 0, 11, 8, height >> 8, height & 255, width >> 8, width & 255, 1, 1, 0x11, 0});
     else

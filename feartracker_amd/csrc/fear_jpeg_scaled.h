@@ -19,20 +19,11 @@
 // term is dc << 14 twice over, 2^13 2^2 2^14 = 2^29), which every file an encoder writes does.
 // As in fear_jpeg_decode.h the device never trusts the data: every loop is bounded by a constant, a block reads at most 64 stored values
 // whatever its offsets say, there are no atomics and every store is a plain vector store.
-// Included by fear_train.hip behind fear_jpeg_decode.h, whose records, geometry and image search it uses.
+// Included by fear_train.hip behind fear_jpeg_decode.h.  Its own are the transforms, their dispatch and the store widths; the argument
+// struct (JpegDecodeArgs with m), the records, geometry and image search, the block load, the block's home, the sample pack, the h2v1
+// filter, the colour conversion and the host's check (jd_check) are fear_jpeg_decode.h's.
 
 namespace {
-
-struct JpegScaledArgs {
-    const uint32_t* table;   // the caller's device table, as JpegDecodeArgs'; the second prefix table counts scaled pixels
-    uint8_t* planes;         // the workspace, 16-byte aligned
-    int n;
-    int m;                   // 8 / scale: 4, 2 or 1
-};
-
-__device__ __forceinline__ const FearJpegImage* js_records(const JpegScaledArgs& a) {
-    return reinterpret_cast<const FearJpegImage*>(reinterpret_cast<const char*>(a.table) + FEAR_JPEG_TABLE_RECORDS(a.n));
-}
 
 // The side of a component's transform (libjpeg's jdmaster.c): m, doubled while it is below 8 and the plane stays within the frame on
 // both axes.  hc, vc: the component's sampling factors; h, v: the largest (the luma's).  At most three doublings.
@@ -66,40 +57,19 @@ __device__ __forceinline__ void js_idct2(int* d) {
     d[1] = jp_descale<N>(t10 - t0);
 }
 
-__device__ __forceinline__ uint32_t js_sample(int x) {
-    return (uint32_t)min(max(x + 128, 0), 255);
-}
-
-__global__ __launch_bounds__(256) void jpeg_scaled_blocks_kernel(JpegScaledArgs a) {
+__global__ __launch_bounds__(256) void jpeg_scaled_blocks_kernel(JpegDecodeArgs a) {
     __shared__ __attribute__((aligned(16))) int blk[FEAR_JPEG_GROUP_BLOCKS * kJpPitch];
     const int tid = threadIdx.x, lb = tid >> 3, k = tid & 7;
     const int img = jd_find_image(a.table, a.n, blockIdx.x);
-    const FearJpegImage* im = js_records(a) + img;
+    const FearJpegImage* im = jd_records(a) + img;
     const JdGeom g = jd_geom(im->width, im->height, im->components, im->h, im->v);
     const long b = (long)(blockIdx.x - a.table[img]) * FEAR_JPEG_GROUP_BLOCKS + lb;
     const bool on = b < g.n0 + 2 * g.nc;
-    const int comp = b < g.n0 ? 0 : (b < g.n0 + g.nc ? 1 : 2);
+    const int comp = jd_comp(g, b);
     const int ss0 = js_transform(a.m, im->h, im->v, im->h, im->v), ssc = js_transform(a.m, im->h, im->v, 1, 1);
     const int ss = comp == 0 ? ss0 : ssc;                      // 1, 2, 4 or 8; the same for the eight lanes of a block
     int* base = blk + lb * kJpPitch;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) base[k * 8 + i] = 0;
-    __syncthreads();
-    if (on) {                                                 // the stored values: zigzag -> natural order, times the quantiser
-        const uint32_t s = im->block_start[b], e = im->block_start[b + 1];
-        const int cnt = e > s ? (int)min(e - s, 64u) : 0;
-        const int16_t* c = im->coef + s;
-        const uint16_t* q = im->qt[comp];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int i = k + 8 * j;
-            if (i < cnt) {
-                const int nat = kJdZigzag[i];
-                base[nat] = (int)c[i] * (int)q[nat];
-            }
-        }
-    }
-    __syncthreads();
+    jd_load_block(base, k, on, im, b, comp);
     int d[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) d[i] = base[i * 8 + k];       // columns: lane k takes column k (one the row pass never reads is wasted work)
@@ -117,18 +87,15 @@ __global__ __launch_bounds__(256) void jpeg_scaled_blocks_kernel(JpegScaledArgs 
     else if (ss == 2) js_idct2<20>(d);
     else d[0] = jp_descale<3>(d[0]);
     if (on && k < ss) {
-        const long rb = b - (comp == 0 ? 0 : (comp == 1 ? g.n0 : g.n0 + g.nc));
-        const int pw = comp == 0 ? g.bw0 : g.bwc;
-        const long by = rb / pw, bx = rb - by * pw;
+        const JdHome at = jd_home(g, comp, b);
         // the planes of an image follow one another: luma n0 ss0^2 bytes, then Cb and Cr of nc ssc^2 bytes each
         const long plane = comp == 0 ? 0 : (long)g.n0 * ss0 * ss0 + (comp == 2 ? (long)g.nc * ssc * ssc : 0);
         // plane_offset is a multiple of 16 and a row of a block starts at a multiple of ss within its plane; a chroma plane starts at a
         // multiple of ssc as well: n0 ss0^2 is one where ssc == ss0, and where ssc == 2 ss0 (4:2:0) n0 is a multiple of 4
-        uint8_t* dst = a.planes + im->plane_offset + plane + ((by * ss + k) * pw + bx) * ss;
-        const uint32_t lo = js_sample(d[0]) | js_sample(d[1]) << 8 | js_sample(d[2]) << 16 | js_sample(d[3]) << 24;
+        uint8_t* dst = a.planes + im->plane_offset + plane + ((at.by * ss + k) * at.pw + at.bx) * ss;
+        const uint32_t lo = jd_pack4(d);
         if (ss == 8) {
-            const uint32_t hi = js_sample(d[4]) | js_sample(d[5]) << 8 | js_sample(d[6]) << 16 | js_sample(d[7]) << 24;
-            *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
+            *reinterpret_cast<uint2*>(dst) = make_uint2(lo, jd_pack4(d + 4));
         } else if (ss == 4) {
             *reinterpret_cast<uint32_t*>(dst) = lo;
         } else if (ss == 2) {
@@ -139,10 +106,10 @@ __global__ __launch_bounds__(256) void jpeg_scaled_blocks_kernel(JpegScaledArgs 
     }
 }
 
-__global__ __launch_bounds__(256) void jpeg_scaled_merge_kernel(JpegScaledArgs a) {
+__global__ __launch_bounds__(256) void jpeg_scaled_merge_kernel(JpegDecodeArgs a) {
     const uint32_t* start = a.table + (a.n + 1);
     const int img = jd_find_image(start, a.n, blockIdx.x);
-    const FearJpegImage* im = js_records(a) + img;
+    const FearJpegImage* im = jd_records(a) + img;
     const int m = a.m, h = im->h, v = im->v;
     const int W = (im->width * m + 7) >> 3, H = (im->height * m + 7) >> 3;      // the scaled frame
     const long px = (long)(blockIdx.x - start[img]) * FEAR_JPEG_GROUP_PIXELS + threadIdx.x;
@@ -152,33 +119,24 @@ __global__ __launch_bounds__(256) void jpeg_scaled_merge_kernel(JpegScaledArgs a
     const int ss0 = js_transform(m, h, v, h, v), ssc = js_transform(m, h, v, 1, 1);
     const uint8_t* planes = a.planes + im->plane_offset;
     const int Y = planes[(long)y * (g.bw0 * ss0) + x];
-    int r = Y, gg = Y, b = Y;
+    int cb = 128, cr = 128;
     if (im->components == 3) {
         const uint8_t* pcb = planes + (long)g.n0 * ss0 * ss0;
         const uint8_t* pcr = pcb + (long)g.nc * ssc * ssc;
         const long row = (long)y * (g.bwc * ssc);              // no supported mode is left with vertical upsampling: h m == ssc or v == 1
-        int cb, cr;
         if (h * m == ssc) {                                    // 4:4:4, and 4:2:0 through the larger transform: no upsampling
             cb = pcb[row + x]; cr = pcr[row + x];
         } else {                                               // 4:2:2: h2v1 on the true width of the scaled chroma plane
-            const int cw = (im->width * ssc + 8 * h - 1) / (8 * h), cx = x >> 1;
-            if (m > 1 && cw > 2) {                             // fancy: 3 this + neighbour; an edge sample is its own neighbour
-                const int nx = (x & 1) ? min(cx + 1, cw - 1) : max(cx - 1, 0), round = (x & 1) ? 2 : 1;
-                cb = (3 * pcb[row + cx] + pcb[row + nx] + round) >> 2;
-                cr = (3 * pcr[row + cx] + pcr[row + nx] + round) >> 2;
+            const int cw = (im->width * ssc + 8 * h - 1) / (8 * h);
+            if (m > 1 && cw > 2) {                             // fancy
+                const JdTaps t = jd_taps(x, cw);
+                cb = jd_h2v1(pcb, row, t); cr = jd_h2v1(pcr, row, t);
             } else {                                           // replication: a plane this narrow, and every plane at 1/8
-                cb = pcb[row + cx]; cr = pcr[row + cx];
+                cb = pcb[row + (x >> 1)]; cr = pcr[row + (x >> 1)];
             }
         }
-        cb -= 128; cr -= 128;
-        r = Y + ((91881 * cr + 32768) >> 16);
-        b = Y + ((116130 * cb + 32768) >> 16);
-        gg = Y + ((-22554 * cb - 46802 * cr + 32768) >> 16);
     }
-    uint8_t* dst = im->out + px * 3;
-    dst[0] = (uint8_t)min(max(r, 0), 255);
-    dst[1] = (uint8_t)min(max(gg, 0), 255);
-    dst[2] = (uint8_t)min(max(b, 0), 255);
+    jd_store_rgb(Y, cb, cr, im->out + px * 3);
 }
 
 }  // namespace
@@ -187,38 +145,13 @@ extern "C" {
 
 int fear_jpeg_decode_scaled_u8(const FearJpegImage* images, int n, const uint32_t* group_start, int scale, void* workspace,
                                size_t workspace_bytes, void* stream) {
-    if (n < 0 || n > 65535 || (scale != 2 && scale != 4 && scale != 8)) return FEAR_TRAIN_ERR_SHAPE;
-    if (n == 0) return FEAR_TRAIN_OK;
-    if (!images || !group_start) return FEAR_TRAIN_ERR_NULL;
-    const int m = 8 / scale;
-    uint64_t block_groups = 0, pixel_groups = 0;
-    for (int i = 0; i < n; ++i) {
-        const FearJpegImage& im = images[i];
-        if (!im.coef || !im.block_start || !im.out) return FEAR_TRAIN_ERR_NULL;
-        if (im.width < 1 || im.width > FEAR_JPEG_MAX_SIDE || im.height < 1 || im.height > FEAR_JPEG_MAX_SIDE ||
-            !jd_mode_ok(im.components, im.h, im.v) || (im.plane_offset & 15) != 0)
-            return FEAR_TRAIN_ERR_SHAPE;
-    }
-    if (!workspace) return FEAR_TRAIN_ERR_WORKSPACE;
-    for (int i = 0; i < n; ++i) {
-        const FearJpegImage& im = images[i];
-        const JdGeom g = jd_geom(im.width, im.height, im.components, im.h, im.v);
-        const uint64_t blocks = (uint64_t)(g.n0 + 2 * g.nc);
-        if (workspace_bytes < 16 || im.plane_offset > workspace_bytes - 16 || blocks * 64 > workspace_bytes - 16 - im.plane_offset)
-            return FEAR_TRAIN_ERR_WORKSPACE;                  // fear_jpeg_decode_u8's bound: the scaled planes are no larger
-        const uint64_t sw = ((uint64_t)im.width * m + 7) / 8, sh = ((uint64_t)im.height * m + 7) / 8;
-        block_groups += (blocks + FEAR_JPEG_GROUP_BLOCKS - 1) / FEAR_JPEG_GROUP_BLOCKS;
-        pixel_groups += (sw * sh + FEAR_JPEG_GROUP_PIXELS - 1) / FEAR_JPEG_GROUP_PIXELS;
-    }
-    if (block_groups > 0x7fffffffu || pixel_groups > 0x7fffffffu) return FEAR_TRAIN_ERR_SHAPE;
-    JpegScaledArgs a{};
-    a.table = group_start;
-    a.planes = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
-    a.n = n;
-    a.m = m;
-    hipLaunchKernelGGL(jpeg_scaled_blocks_kernel, dim3((unsigned)block_groups), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    if (scale != 2 && scale != 4 && scale != 8) return FEAR_TRAIN_ERR_SHAPE;
+    JdLaunch l;
+    const int status = jd_check(images, n, group_start, false, 8 / scale, workspace, workspace_bytes, &l);
+    if (status != FEAR_TRAIN_OK || l.block_groups == 0) return status;
+    hipLaunchKernelGGL(jpeg_scaled_blocks_kernel, dim3(l.block_groups), dim3(256), 0, static_cast<hipStream_t>(stream), l.a);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(jpeg_scaled_merge_kernel, dim3((unsigned)pixel_groups), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(jpeg_scaled_merge_kernel, dim3(l.pixel_groups), dim3(256), 0, static_cast<hipStream_t>(stream), l.a);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }

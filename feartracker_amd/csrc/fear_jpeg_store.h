@@ -5,6 +5,7 @@
 // lies in.  jpeg_huffman.jpeg_scan_index_host and jpeg_entropy_indexed_host restate both in Python.  fear_jpeg_huffman_indexed_rows is
 // the same lane for a band of MCU rows: only the subsequences in which the band's blocks lie get a lane (the caller's row_sub table,
 // jpeg_huffman.scan_row_sub), and only the band's blocks are stored, as the dense coefficients of an image of those rows alone.
+// The three kernels share one lane (ji_lane<FORM>) and the three entry points one host function (ji_launch).
 // Included by fear_train.hip behind fear_jpeg_huffman.h, whose jh_decode, jh_peek, jh_block_base and JhSegment it uses, and
 // fear_jpeg_decode.h's jd_find_image and jr_band.
 
@@ -184,19 +185,26 @@ int fear_jpeg_index_build(const FearJpegScan* scans, int n, const void* table_de
     return FEAR_TRAIN_OK;
 }
 
-int fear_jpeg_huffman_indexed(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
-                              int subsequence_bytes, void* stream) {
+// The checks and the two launches of the three indexed entry points.  form: ji_lane's, 0 the image, 1 the host-planned band (the
+// record's sub0 / sub_count and mcu_row0 / mcu_rows are checked and the grid counts sub_count), 2 the band of `rows_dev` (which, with
+// every record's row_sub, must be there).
+static int ji_launch(int form, const FearJpegIndexed* images, int n, const void* table_dev, const int32_t* rows_dev, int16_t* coef,
+                     int32_t* status_dev, int subsequence_bytes, void* stream) {
     if (n < 0 || n > 65535 || subsequence_bytes < 4 || subsequence_bytes > 1024 || (subsequence_bytes & 3) != 0) return FEAR_TRAIN_ERR_SHAPE;
     if (n == 0) return FEAR_TRAIN_OK;
-    if (!images || !table_dev || !coef || !status_dev) return FEAR_TRAIN_ERR_NULL;
+    if (!images || !table_dev || (form == 2 && !rows_dev) || !coef || !status_dev) return FEAR_TRAIN_ERR_NULL;
     uint64_t groups = 0;
     for (int i = 0; i < n; ++i) {
         const FearJpegIndexed& im = images[i];
-        if (!im.scan || !im.sub_start || (!im.index && im.n_sub != 0)) return FEAR_TRAIN_ERR_NULL;
+        if (!im.scan || !im.sub_start || (form == 2 && !im.row_sub) || (!im.index && im.n_sub != 0)) return FEAR_TRAIN_ERR_NULL;
         if ((reinterpret_cast<uintptr_t>(im.index) & 15) != 0 || (reinterpret_cast<uintptr_t>(im.scan) & 15) != 0 ||
-            (reinterpret_cast<uintptr_t>(im.sub_start) & 3) != 0)
+            (reinterpret_cast<uintptr_t>(im.sub_start) & 3) != 0 || (form == 2 && (reinterpret_cast<uintptr_t>(im.row_sub) & 3) != 0))
             return FEAR_TRAIN_ERR_SHAPE;
-        groups += ((uint64_t)im.n_sub + kJhLanes - 1) / kJhLanes;
+        if (form == 1) {
+            if (im.sub_count != 0 && (im.sub0 >= im.n_sub || im.sub_count > im.n_sub - im.sub0)) return FEAR_TRAIN_ERR_SHAPE;
+            if (im.mcu_row0 > FEAR_JPEG_MAX_SIDE / 8 || im.mcu_rows > FEAR_JPEG_MAX_SIDE / 8 - im.mcu_row0) return FEAR_TRAIN_ERR_SHAPE;
+        }
+        groups += ((uint64_t)(form == 1 ? im.sub_count : im.n_sub) + kJhLanes - 1) / kJhLanes;
     }
     if (groups > 0x7fffffffu) return FEAR_TRAIN_ERR_SHAPE;
     JpegIndexedArgs a{};
@@ -205,76 +213,30 @@ int fear_jpeg_huffman_indexed(const FearJpegIndexed* images, int n, const void* 
     a.status = status_dev;
     a.n = n;
     a.subsequence_bits = subsequence_bytes * 8;
-    hipLaunchKernelGGL(jpeg_indexed_status_kernel, dim3((unsigned)((n + kJhLanes - 1) / kJhLanes)), dim3(kJhLanes), 0,
-                       static_cast<hipStream_t>(stream), a);
+    const dim3 grid((unsigned)groups), lanes(kJhLanes);
+    hipLaunchKernelGGL(jpeg_indexed_status_kernel, dim3((unsigned)((n + kJhLanes - 1) / kJhLanes)), lanes, 0, static_cast<hipStream_t>(stream), a);
     LAUNCH_CHECK();
     if (groups == 0) return FEAR_TRAIN_OK;
-    hipLaunchKernelGGL(jpeg_huffman_indexed_kernel, dim3((unsigned)groups), dim3(kJhLanes), 0, static_cast<hipStream_t>(stream), a);
+    if (form == 0) hipLaunchKernelGGL(jpeg_huffman_indexed_kernel, grid, lanes, 0, static_cast<hipStream_t>(stream), a);
+    else if (form == 1) hipLaunchKernelGGL(jpeg_huffman_indexed_rows_kernel, grid, lanes, 0, static_cast<hipStream_t>(stream), a);
+    else hipLaunchKernelGGL(jpeg_huffman_indexed_rows_dev_kernel, grid, lanes, 0, static_cast<hipStream_t>(stream), a, rows_dev);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
+}
+
+int fear_jpeg_huffman_indexed(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
+                              int subsequence_bytes, void* stream) {
+    return ji_launch(0, images, n, table_dev, nullptr, coef, status_dev, subsequence_bytes, stream);
 }
 
 int fear_jpeg_huffman_indexed_rows(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
                                    int subsequence_bytes, void* stream) {
-    if (n < 0 || n > 65535 || subsequence_bytes < 4 || subsequence_bytes > 1024 || (subsequence_bytes & 3) != 0) return FEAR_TRAIN_ERR_SHAPE;
-    if (n == 0) return FEAR_TRAIN_OK;
-    if (!images || !table_dev || !coef || !status_dev) return FEAR_TRAIN_ERR_NULL;
-    uint64_t groups = 0;
-    for (int i = 0; i < n; ++i) {
-        const FearJpegIndexed& im = images[i];
-        if (!im.scan || !im.sub_start || (!im.index && im.n_sub != 0)) return FEAR_TRAIN_ERR_NULL;
-        if ((reinterpret_cast<uintptr_t>(im.index) & 15) != 0 || (reinterpret_cast<uintptr_t>(im.scan) & 15) != 0 ||
-            (reinterpret_cast<uintptr_t>(im.sub_start) & 3) != 0)
-            return FEAR_TRAIN_ERR_SHAPE;
-        if (im.sub_count != 0 && (im.sub0 >= im.n_sub || im.sub_count > im.n_sub - im.sub0)) return FEAR_TRAIN_ERR_SHAPE;
-        if (im.mcu_row0 > FEAR_JPEG_MAX_SIDE / 8 || im.mcu_rows > FEAR_JPEG_MAX_SIDE / 8 - im.mcu_row0) return FEAR_TRAIN_ERR_SHAPE;
-        groups += ((uint64_t)im.sub_count + kJhLanes - 1) / kJhLanes;
-    }
-    if (groups > 0x7fffffffu) return FEAR_TRAIN_ERR_SHAPE;
-    JpegIndexedArgs a{};
-    a.table = static_cast<const uint32_t*>(table_dev);
-    a.coef = coef;
-    a.status = status_dev;
-    a.n = n;
-    a.subsequence_bits = subsequence_bytes * 8;
-    hipLaunchKernelGGL(jpeg_indexed_status_kernel, dim3((unsigned)((n + kJhLanes - 1) / kJhLanes)), dim3(kJhLanes), 0,
-                       static_cast<hipStream_t>(stream), a);
-    LAUNCH_CHECK();
-    if (groups == 0) return FEAR_TRAIN_OK;
-    hipLaunchKernelGGL(jpeg_huffman_indexed_rows_kernel, dim3((unsigned)groups), dim3(kJhLanes), 0, static_cast<hipStream_t>(stream), a);
-    LAUNCH_CHECK();
-    return FEAR_TRAIN_OK;
+    return ji_launch(1, images, n, table_dev, nullptr, coef, status_dev, subsequence_bytes, stream);
 }
 
 int fear_jpeg_huffman_indexed_rows_dev(const FearJpegIndexed* images, int n, const void* table_dev, const int32_t* rows_dev, int16_t* coef,
                                        int32_t* status_dev, int subsequence_bytes, void* stream) {
-    if (n < 0 || n > 65535 || subsequence_bytes < 4 || subsequence_bytes > 1024 || (subsequence_bytes & 3) != 0) return FEAR_TRAIN_ERR_SHAPE;
-    if (n == 0) return FEAR_TRAIN_OK;
-    if (!images || !table_dev || !rows_dev || !coef || !status_dev) return FEAR_TRAIN_ERR_NULL;
-    uint64_t groups = 0;
-    for (int i = 0; i < n; ++i) {
-        const FearJpegIndexed& im = images[i];
-        if (!im.scan || !im.sub_start || !im.row_sub || (!im.index && im.n_sub != 0)) return FEAR_TRAIN_ERR_NULL;
-        if ((reinterpret_cast<uintptr_t>(im.index) & 15) != 0 || (reinterpret_cast<uintptr_t>(im.scan) & 15) != 0 ||
-            (reinterpret_cast<uintptr_t>(im.sub_start) & 3) != 0 || (reinterpret_cast<uintptr_t>(im.row_sub) & 3) != 0)
-            return FEAR_TRAIN_ERR_SHAPE;
-        groups += ((uint64_t)im.n_sub + kJhLanes - 1) / kJhLanes;
-    }
-    if (groups > 0x7fffffffu) return FEAR_TRAIN_ERR_SHAPE;
-    JpegIndexedArgs a{};
-    a.table = static_cast<const uint32_t*>(table_dev);
-    a.coef = coef;
-    a.status = status_dev;
-    a.n = n;
-    a.subsequence_bits = subsequence_bytes * 8;
-    hipLaunchKernelGGL(jpeg_indexed_status_kernel, dim3((unsigned)((n + kJhLanes - 1) / kJhLanes)), dim3(kJhLanes), 0,
-                       static_cast<hipStream_t>(stream), a);
-    LAUNCH_CHECK();
-    if (groups == 0) return FEAR_TRAIN_OK;
-    hipLaunchKernelGGL(jpeg_huffman_indexed_rows_dev_kernel, dim3((unsigned)groups), dim3(kJhLanes), 0, static_cast<hipStream_t>(stream), a,
-                       rows_dev);
-    LAUNCH_CHECK();
-    return FEAR_TRAIN_OK;
+    return ji_launch(2, images, n, table_dev, rows_dev, coef, status_dev, subsequence_bytes, stream);
 }
 
 }  // extern "C"

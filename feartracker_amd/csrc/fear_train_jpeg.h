@@ -12,18 +12,13 @@
 //   jpeg_merge_kernel   h2v2 fancy upsampling, colour conversion back, store.  A crop whose quality is outside 1..100 is copied here.
 // Included by fear_train.hip behind fear_train_data.h.
 
+#include "fear_jpeg_tables.h"                                  // the base quantiser tables: fear_jpeg::kBaseQuantDev
+
 namespace {
 
 constexpr int kJpMcus = 4, kJpBlocks = kJpMcus * 6;
 // ints per block in LDS: 64 + 8, so that the column reads of four neighbouring blocks (one ds_read_b32 lane group) fall on 32 banks
 constexpr int kJpPitch = 72;
-
-// the standard luminance and chrominance tables (ITU-T T.81 annex K), natural order
-__device__ const uint8_t kJpegBase[128] = {
-    16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
-    18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,  49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99,
-    17, 18, 24, 47, 99,  99,  99,  99,  18, 21, 26, 66, 99,  99,  99,  99,  24, 26, 56, 99, 99,  99,  99,  99,  47, 66, 99, 99, 99,  99,  99,  99,
-    99, 99, 99, 99, 99,  99,  99,  99,  99, 99, 99, 99, 99,  99,  99,  99,  99, 99, 99, 99, 99,  99,  99,  99,  99, 99, 99, 99, 99,  99,  99,  99};
 
 // jfdctint / jidctint: FIX(x) = rint(x * 2^13) (CONST_BITS 13, PASS1_BITS 2)
 constexpr int kF0_298 = 2446, kF0_390 = 3196, kF0_541 = 4433, kF0_765 = 6270, kF0_899 = 7373, kF1_175 = 9633;
@@ -102,7 +97,7 @@ __global__ __launch_bounds__(256) void jpeg_blocks_kernel(JpegArgs a) {
     const long hw = (long)H * W;
     if (tid < 128) {                                          // jpeg_set_quality(quality, force_baseline)
         const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
-        qt[tid] = min(max(((int)kJpegBase[tid] * scale + 50) / 100, 1), 255);
+        qt[tid] = min(max(((int)fear_jpeg::kBaseQuantDev.v[tid] * scale + 50) / 100, 1), 255);
     }
     {
         // one 2 x 2 quad of one MCU per lane: four Y samples and one sample each of Cb and Cr (jccolor, jcsample's h2v2 without smoothing)

@@ -12,7 +12,7 @@ import torch
 import jpegdec
 from dataops import GUARD, P, SENTINEL_U8, guarded, inner, inside
 from jpegdec import ERR_NULL, ERR_SHAPE, ERR_WORKSPACE, OK
-from test_jpeg_store_gpu import RECORD, _Built, _Indexed, _stream
+from test_jpeg_store_gpu import RECORD, _Built, _Indexed, _stream, without_lanes
 from feartracker_amd import JpegStore, scan_row_sub
 from feartracker_amd import jpeg_frames as jf
 from feartracker_amd import train_abi as abi
@@ -250,6 +250,13 @@ def test_the_written_positions_are_the_bands_blocks(lib, subsequence_bytes):
             partial += band[1] - band[0] < info.mcus_y
         assert bool((got == want).all()), f"{cases[k][0]}: rows {y0}..{y1}: {int((got != want).sum())} of {want.size} values differ"
     assert partial > 20
+
+
+def test_an_image_without_a_subsequence_has_no_lane_and_fails(lib):
+    _, data, _ = jpegdec.case("15x50_420_random_q100_rst3")
+    built = _Built(lib, [data], 128)
+    row_sub = [scan_row_sub(jf._parse(data), built.sub[0], built.entries()[0])]
+    assert without_lanes(_RowsDev(built, [0], row_sub, [(10, 30)], run=False), n_sub=0) == jpegdec.ERR_FORMAT
 
 
 def test_argument_checks_of_the_two_entry_points(lib):

@@ -157,6 +157,15 @@ def test_bands_without_rows_or_lanes_and_the_argument_checks(lib):
     assert bool((run.dense()[0] == _band_of(built.infos[0], full.dense()[0], 1, 3)).all())
 
 
+def test_a_call_of_empty_bands_alone_launches_no_lane(lib):
+    _, data, _ = jpegdec.case("15x50_420_random_q100_rst3")
+    built = _Built(lib, [data], 128)
+    R = built.infos[0].mcus_y
+    run = _Rows(built, [(0, 1, 1), (0, R, R)], _row_tables([("rst3", data, None)], built))
+    assert run.groups.tolist() == [0, 0, 0] and run.statuses().tolist() == [OK, OK] and run.values == 0
+    inside(run.coef, 0, "band coefficients")
+
+
 # ------------------------------------------------------------------------------------------------------------------------- JpegStore
 @pytest.fixture(scope="module")
 def resident():

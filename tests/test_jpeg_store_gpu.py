@@ -302,6 +302,27 @@ def test_argument_checks_of_both_calls(lib):
         assert bool((a == c).all())
 
 
+def without_lanes(run, **fields):
+    """The call of `run`, of one image and not yet run, with `fields` of its record set on the host and in the device table and no
+    workgroup in the prefix table — what a call sees whose images leave it no lane to run: OK, the statuses written, nothing stored.
+    The image's status."""
+    for k, v in fields.items():
+        setattr(run.images[0], k, v)
+    table = run.table.cpu().numpy()
+    table[:8] = 0
+    table[16:] = np.frombuffer(run.images, dtype=np.uint8)                             # one image: the records begin at 16
+    run.table = torch.from_numpy(table).cuda()
+    assert run.call() == OK
+    torch.cuda.synchronize()
+    assert bool((inside(run.coef, 2 * run.values) == SENTINEL_U8).all())
+    return run.statuses()[0]
+
+
+def test_an_image_without_a_subsequence_has_no_lane_and_fails(lib):
+    _, data, _ = jpegdec.case("15x50_420_random_q100_rst3")
+    assert without_lanes(_Indexed(_Built(lib, [data], 128), [0], run=False), n_sub=0) == ERR_FORMAT
+
+
 # ------------------------------------------------------------------------------------------------------------------------- JpegStore
 @pytest.fixture(scope="module")
 def host_frames():

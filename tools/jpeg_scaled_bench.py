@@ -11,8 +11,12 @@ them), medians with minimum and maximum, a host clock around work that ends in c
   decode_ms_per_call        store.decode of the 256 ids in a seeded permutation at scales 1, 2, 4 and 8
   decode_rows_ms_per_call   store.decode_rows at a quarter of the (scaled) height, seeded positions, at scales 1 and 2
   bytes_per_frame           what the pixel stage writes per frame: 3 H' W'
-  scale_1_against_parent    with --parent-lib, the parent commit's library: store.decode at scale 1 through both builds, alternating;
-                            `within_parents_spread` says whether this build's median lies within the parent's own minimum..maximum
+  against_parent            with --parent-lib, the parent commit's library: every path whose pixel kernels the two builds may compile
+                            differently, through both builds alternating, the frames compared first — store.decode at scales 1, 2, 4
+                            and 8, decode_rows with the rows on the device at a quarter of the height (where skipped workgroups matter)
+                            and fear_jpeg_decode_u8 alone (timed inside store.decode, between two synchronisations around the call).  Per row
+                            `not_slower_than_parents_slowest`: this build's median <= the parent's maximum in the same run, so the
+                            margin is the parent's own spread; `within_parents_spread`: the median lies within its minimum..maximum
   pixel_kernels_us          with --stats-from: the two pixel kernels' time per launch at each scale, from a separate kernel trace of
                             --kernels-only (rocprofv3 --kernel-trace --stats, its kernel_trace csv)
 The indexed Huffman stage decodes every coefficient at every scale and is not touched by this mode: it bounds the gain.
@@ -45,14 +49,15 @@ def timed(fn):
     return time.perf_counter() - t0
 
 
-def alternating(variants, repeats):
-    """{name: [seconds] * repeats}: one warm-up of every variant, then `repeats` rounds in which each runs once, in order."""
+def alternating(variants, repeats, clock=timed):
+    """{name: [seconds] * repeats}: one warm-up of every variant, then `repeats` rounds in which each runs once, in order.  `clock(fn)`
+    runs a variant and says how long it took: the whole of it by default."""
     for fn in variants.values():
         fn()
     times = {name: [] for name in variants}
     for _ in range(repeats):
         for name, fn in variants.items():
-            times[name].append(timed(fn))
+            times[name].append(clock(fn))
     return times
 
 
@@ -68,6 +73,64 @@ def parent_store(path, blobs):
     store = JpegStore(device=0, threads=16)
     store._lib = store._host._lib = lib
     return store, store.add(blobs)
+
+
+def pixel_stage_alone(store, ids):
+    """Seconds of fear_jpeg_decode_u8 alone within store.decode(ids): the clock runs inside the call itself, from a device that has
+    finished the Huffman stage to one that has finished the pixel stage, summed over the call's groups.  Nothing is launched a second
+    time, so every buffer the call's addresses name is the live one of the decode that made it."""
+    import torch
+    from feartracker_amd import train_abi as abi
+    took, real = [], abi.launch
+
+    def spy(lib, name, *a):
+        if name != "fear_jpeg_decode_u8":
+            return real(lib, name, *a)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rc = real(lib, name, *a)
+        torch.cuda.synchronize()
+        took.append(time.perf_counter() - t0)
+        return rc
+    abi.launch = spy
+    try:
+        store.decode(ids, check=True)
+    finally:
+        abi.launch = real
+    assert took, "store.decode launched no fear_jpeg_decode_u8"
+    return sum(took)
+
+
+def against_parent(path, blobs, store, ids, order, repeats):
+    """The rows of `against_parent`, each {parent_ms_per_call, ms_per_call, frames_equal, the two verdicts}."""
+    import torch
+    theirs, their_ids = parent_store(path, blobs)
+    their_order = their_ids[np.random.default_rng(5).permutation(their_ids.size)]
+    high = db.H // 4
+    y0 = np.random.default_rng(9).integers(0, db.H - high + 1, ids.size)
+    windows = np.stack([y0, y0 + high], axis=1)
+    on_device = torch.from_numpy(windows.astype(np.int32)).cuda()
+    rows = {}
+    for s in SCALES:
+        rows[f"store.decode at scale {s}"] = (
+            lambda s=s: theirs.decode(their_order, check=True, scale=s), lambda s=s: store.decode(order, check=True, scale=s),
+            lambda s=s: zip(theirs.decode(their_ids[:16], check=True, scale=s), store.decode(ids[:16], check=True, scale=s)))
+    rows["decode_rows, rows on the device, at 0.25 H"] = (
+        lambda: theirs.decode_rows(their_order, on_device, check=True), lambda: store.decode_rows(order, on_device, check=True),
+        lambda: ((a[lo:hi], b[lo:hi]) for a, b, (lo, hi) in zip(theirs.decode_rows(their_order, on_device, check=True),
+                                                                 store.decode_rows(order, on_device, check=True), windows.tolist())))
+    alone = "fear_jpeg_decode_u8 alone"
+    rows[alone] = (lambda: pixel_stage_alone(theirs, their_order), lambda: pixel_stage_alone(store, order), rows["store.decode at scale 1"][2])
+    out = {}
+    for name, (parent_fn, this_fn, pairs) in rows.items():
+        same = all(bool(torch.equal(a, b)) for a, b in pairs())
+        times = alternating({"parent": parent_fn, "this": this_fn}, repeats, clock=(lambda fn: fn()) if name == alone else timed)
+        parent, this = db.spread(times["parent"], 1e3), db.spread(times["this"], 1e3)
+        out[name] = {"parent_ms_per_call": parent, "ms_per_call": this, "frames_equal": same,
+                     "within_parents_spread": parent["min"] <= this["median"] <= parent["max"],
+                     "not_slower_than_parents_slowest": this["median"] <= parent["max"]}
+    theirs.close()
+    return out
 
 
 def stats_from(path):
@@ -94,7 +157,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dir", default=os.path.join(ROOT, "jpeg_bench_frames"))
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--parent-lib", default=None, help="the parent commit's library: scale 1 through both builds in the same run")
+    ap.add_argument("--parent-lib", default=None, help="the parent commit's library: the pixel paths through both builds in the same run")
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--stats-from", default=None)
     ap.add_argument("--out", default=OUT)
@@ -140,18 +203,7 @@ def main():
         rows[s] = np.stack([y0, y0 + high // 4], axis=1)
     times = alternating({str(s): (lambda s=s: store.decode_rows(order, rows[s], check=True, scale=s)) for s in (1, 2)}, args.repeats)
     res["decode_rows_ms_per_call"] = {k: db.spread(v, 1e3) for k, v in times.items()}
-    if args.parent_lib:
-        theirs, their_ids = parent_store(args.parent_lib, blobs)
-        their_order = their_ids[np.random.default_rng(5).permutation(their_ids.size)]
-        same = all(bool(torch.equal(a, b)) for a, b in zip(store.decode(ids[:16], check=True), theirs.decode(their_ids[:16], check=True)))
-        times = alternating({"parent": lambda: theirs.decode(their_order, check=True), "this": lambda: store.decode(order, check=True)},
-                            args.repeats)
-        parent, this = db.spread(times["parent"], 1e3), db.spread(times["this"], 1e3)
-        res["scale_1_against_parent"] = {"parent_ms_per_call": parent, "ms_per_call": this, "frames_equal": same,
-                                         "within_parents_spread": parent["min"] <= this["median"] <= parent["max"],
-                                         "not_slower_than_parents_slowest": this["median"] <= parent["max"]}
-    else:
-        res["scale_1_against_parent"] = "not measured"
+    res["against_parent"] = against_parent(args.parent_lib, blobs, store, ids, order, args.repeats) if args.parent_lib else "not measured"
     res["pixel_kernels_us"] = "not measured"
     with open(args.out, "w") as fh:
         json.dump(res, fh, indent=1)
