@@ -41,7 +41,8 @@ struct JhSegment {
     uint32_t first_mcu;
     uint32_t expected;       // the blocks the segment owes
     bool last;
-    uint32_t band_row0, band_rows;   // MODE 3, 4 alone (fear_jpeg_store.h): the MCU rows whose blocks are stored, inside the image
+    uint32_t band_row0, band_rows;   // MODE 3, 4, 5 alone (fear_jpeg_store.h): the MCU rows whose blocks are stored, inside the image
+    uint32_t win_col0, win_cols;     // MODE 5 alone: the MCU columns whose blocks are stored, inside the image
 };
 
 struct JhState {
@@ -126,9 +127,29 @@ __device__ __forceinline__ long jh_rows_base(const JhSegment& s, uint32_t ordina
     return jh_block_base(s, ordinal, slot);
 }
 
+// MODE 5: the block's place in an image that consists of the MCUs of the band's rows and the columns win_col0 .. win_col0 + win_cols)
+// alone (window-dense); -1 for a block of another row or column.
+__device__ __forceinline__ long jh_window_base(const JhSegment& s, uint32_t ordinal, int slot) {
+    if (ordinal >= s.expected) return -1;
+    const uint32_t mcu = s.first_mcu + ordinal / (uint32_t)s.nslots;
+    const uint32_t my = mcu / (uint32_t)s.mcus_x, mx = mcu - my * (uint32_t)s.mcus_x;
+    if (my < s.band_row0 || my >= s.band_row0 + s.band_rows) return -1;   // band_row0 + band_rows <= mcus_y <= 1024
+    if (mx < s.win_col0 || mx >= s.win_col0 + s.win_cols) return -1;      // win_col0 + win_cols <= mcus_x <= 1024
+    const uint32_t ry = my - s.band_row0, rx = mx - s.win_col0, win_mcus = s.band_rows * s.win_cols;
+    uint32_t b;
+    if (slot < s.hv) {
+        const uint32_t j = (uint32_t)slot / (uint32_t)s.h, i = (uint32_t)slot - j * (uint32_t)s.h;
+        b = (ry * (uint32_t)s.v + j) * (s.win_cols * (uint32_t)s.h) + rx * (uint32_t)s.h + i;
+    } else {
+        b = win_mcus * (uint32_t)s.hv + (uint32_t)(slot - s.hv) * win_mcus + ry * s.win_cols + rx;
+    }
+    return b < win_mcus * (uint32_t)s.nslots ? (long)b * 64 : -1;
+}
+
 template <int MODE>
 __device__ __forceinline__ long jh_base(const JhSegment& s, uint32_t ordinal, int slot) {
-    return MODE == 4 ? jh_rows_base(s, ordinal, slot) : (MODE == 3 ? jh_band_base(s, ordinal, slot) : jh_block_base(s, ordinal, slot));
+    return MODE == 5 ? jh_window_base(s, ordinal, slot)
+                     : (MODE == 4 ? jh_rows_base(s, ordinal, slot) : (MODE == 3 ? jh_band_base(s, ordinal, slot) : jh_block_base(s, ordinal, slot)));
 }
 
 // What the count pass gathers and the write pass starts from.
@@ -151,6 +172,7 @@ __device__ __forceinline__ uint32_t jh_add_dc(JhLane& lane, int comp, uint32_t v
 // Symbols from `st` until the position reaches `end` or the segment's end.  MODE 0: the exit state and nothing else.  1: count.  2: write.
 // 3: write, but only the blocks of the band's MCU rows are stored (jh_band_base); every judgement is mode 2's.
 // 4: write, only the blocks of the band's MCU rows, at their place in the whole image (jh_rows_base); every judgement is mode 2's.
+// 5: write, only the blocks of the window's MCU rows and columns, window-dense (jh_window_base); every judgement is mode 2's.
 // A code in no table, a DC size above 15 or an index past 63: advance one bit, z = 0.
 template <int MODE>
 __device__ __forceinline__ JhState jh_decode(const JhSegment& s, const FearJpegHuff* tabs, JhState st, uint32_t end, int16_t* coef, JhLane& io) {

@@ -1,11 +1,13 @@
 // fear_jpeg_store.h — scans resident on the device and the index a baseline scan lacks (include/fear_train.h: fear_jpeg_index_build,
-// fear_jpeg_huffman_indexed, fear_jpeg_huffman_indexed_rows, fear_jpeg_huffman_indexed_rows_dev; DESIGN.md section 14, "The resident store").  fear_jpeg_index_build is the second instantiation of
+// fear_jpeg_huffman_indexed, fear_jpeg_huffman_indexed_rows, fear_jpeg_huffman_indexed_rows_dev, fear_jpeg_huffman_indexed_windows; DESIGN.md section 14, "The resident store").  fear_jpeg_index_build is the second instantiation of
 // jpeg_huffman_kernel (fear_jpeg_huffman.h), which stores every lane's true entry in front of its write pass.  With those entries a later
 // decode is the write pass alone: jpeg_huffman_indexed_kernel gives every subsequence of an image a lane of its own, whatever segment it
 // lies in.  jpeg_huffman.jpeg_scan_index_host and jpeg_entropy_indexed_host restate both in Python.  fear_jpeg_huffman_indexed_rows is
 // the same lane for a band of MCU rows: only the subsequences in which the band's blocks lie get a lane (the caller's row_sub table,
 // jpeg_huffman.scan_row_sub), and only the band's blocks are stored, as the dense coefficients of an image of those rows alone.
-// The three kernels share one lane (ji_lane<FORM>) and the three entry points one host function (ji_launch).
+// fear_jpeg_huffman_indexed_windows is the band's lane for a range of MCU columns as well: a lane of the band that its own entry and the
+// next one show to hold no MCU of those columns returns early, and the blocks are stored window-dense.
+// The four kernels share one lane (ji_lane<FORM>) and the four entry points one host function (ji_launch).
 // Included by fear_train.hip behind fear_jpeg_huffman.h, whose jh_decode, jh_peek, jh_block_base and JhSegment it uses, and
 // fear_jpeg_decode.h's jd_find_image and jr_band.
 
@@ -32,10 +34,13 @@ __global__ __launch_bounds__(kJhLanes) void jpeg_indexed_status_kernel(JpegIndex
 // subsequences from sub0 and which stores only the blocks of the record's band of MCU rows, band-dense (jh_band_base).  FORM 2:
 // fear_jpeg_huffman_indexed_rows_dev's, whose band comes from `rows_dev` (device memory; null in the other forms): the grid is the whole
 // image's, a workgroup outside the band's subsequences returns in front of the table copy, a lane outside them behind the barrier, and
-// the band's blocks are stored at their place in the whole image (jh_rows_base).
+// the band's blocks are stored at their place in the whole image (jh_rows_base).  FORM 3: fear_jpeg_huffman_indexed_windows', FORM 1
+// with the MCU columns of the record's `reserved` word (mcu_col0 | mcu_cols << 16): a lane whose MCUs — known from its entry's `begun`
+// and the next entry's, or the segment's block count — all lie outside those columns returns in front of every judgement, and only the
+// blocks of the band's rows and those columns are stored, window-dense (jh_window_base).
 template <int FORM>
 __device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a, const int32_t* rows_dev) {
-    constexpr bool ROWS = FORM == 1, DEV = FORM == 2;
+    constexpr bool WIN = FORM == 3, ROWS = FORM == 1 || WIN, DEV = FORM == 2;
     __shared__ __attribute__((aligned(16))) FearJpegHuff tabs[6];        // dc by component, then ac by component
     const int tid = threadIdx.x;
     const int img = jd_find_image(a.table, a.n, blockIdx.x);             // the same for the whole workgroup
@@ -112,6 +117,26 @@ __device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a, const int32_t*
             s.band_row0 = dev_row0;
             s.band_rows = dev_rows;
         }
+        if (WIN) {                                                       // the columns inside the image, as the band's rows
+            s.win_col0 = min(im->reserved & 0xFFFFu, (uint32_t)s.mcus_x);
+            s.win_cols = min(im->reserved >> 16, (uint32_t)s.mcus_x - s.win_col0);
+        }
+    }
+    if (WIN) {
+        // The blocks this lane stores have the ordinals lo .. hi) of its segment: from the block open at its entry, or the first it
+        // begins, to the last begun in front of the next subsequence's entry (the segment's count behind its last subsequence; blocks
+        // past that count are dropped).  Their MCUs are consecutive; the lane runs if one of them lies in the window's columns, the
+        // wrap over a row's end included.  Arithmetic on two loaded values: no loop.
+        const bool next_inside = sub + 1 < sub_start[seg + 1] && sub + 1 < n_sub;
+        const uint32_t next_begun = next_inside ? reinterpret_cast<const uint4*>(im->index)[sub + 1].y : s.expected;
+        const uint32_t lo = e.y - ((e.z & 0xFFu) != 0 && e.y > 0 ? 1u : 0u), hi = min(next_begun, s.expected);
+        if (hi <= lo || s.win_cols == 0) return;                         // lanes that do not run judge nothing
+        const uint32_t mcus_x = (uint32_t)s.mcus_x, nslots = (uint32_t)s.nslots;
+        const uint32_t m_lo = s.first_mcu + lo / nslots, count = (hi - 1) / nslots - lo / nslots + 1;
+        const uint32_t x_lo = m_lo % mcus_x, x_end = x_lo + count - 1;   // count < mcus_x below: x_end < 2 mcus_x
+        const uint32_t c0 = s.win_col0, c1 = s.win_col0 + s.win_cols;
+        const bool touches = count >= mcus_x || (x_lo < c1 && x_end >= c0) || (x_end >= mcus_x && x_end - mcus_x >= c0);
+        if (!touches) return;
     }
     int32_t* status = a.status + img;
     const uint64_t k = (uint64_t)sub - first;                            // the subsequence within its segment
@@ -128,7 +153,7 @@ __device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a, const int32_t*
     lane.dc1 = e.w & 0xFFFFu;
     lane.dc2 = e.w >> 16;
     const uint32_t end = ((uint32_t)k + 1u) * SB;                        // k SB < bits <= 2^27 (8 FEAR_JPEG_DEVICE_SCAN_MAX), SB <= 2^13: no overflow
-    const JhState out = jh_decode<DEV ? 4 : (ROWS ? 3 : 2)>(s, tabs, entry, end, a.coef + im->coef_offset, lane);
+    const JhState out = jh_decode<DEV ? 4 : (WIN ? 5 : (ROWS ? 3 : 2))>(s, tabs, entry, end, a.coef + im->coef_offset, lane);
     bool failed = lane.error;
     // the segment's last subsequence: fewer complete blocks than the segment owes, as jpeg_huffman_kernel judges its true chain's end
     if (end >= s.bits && (lane.begun - ((out.sz & 255) != 0 ? 1u : 0u) < s.expected || (lane.begun == 0 && s.expected > 0))) failed = true;
@@ -140,6 +165,8 @@ __device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a, const int32_t*
 __global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_kernel(JpegIndexedArgs a) { ji_lane<0>(a, nullptr); }
 
 __global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_rows_kernel(JpegIndexedArgs a) { ji_lane<1>(a, nullptr); }
+
+__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_windows_kernel(JpegIndexedArgs a) { ji_lane<3>(a, nullptr); }
 
 __global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_rows_dev_kernel(JpegIndexedArgs a, const int32_t* rows_dev) {
     ji_lane<2>(a, rows_dev);
@@ -185,9 +212,9 @@ int fear_jpeg_index_build(const FearJpegScan* scans, int n, const void* table_de
     return FEAR_TRAIN_OK;
 }
 
-// The checks and the two launches of the three indexed entry points.  form: ji_lane's, 0 the image, 1 the host-planned band (the
+// The checks and the two launches of the four indexed entry points.  form: ji_lane's, 0 the image, 1 the host-planned band (the
 // record's sub0 / sub_count and mcu_row0 / mcu_rows are checked and the grid counts sub_count), 2 the band of `rows_dev` (which, with
-// every record's row_sub, must be there).
+// every record's row_sub, must be there), 3 the host-planned window (form 1's checks and the columns of the record's `reserved` word).
 static int ji_launch(int form, const FearJpegIndexed* images, int n, const void* table_dev, const int32_t* rows_dev, int16_t* coef,
                      int32_t* status_dev, int subsequence_bytes, void* stream) {
     if (n < 0 || n > 65535 || subsequence_bytes < 4 || subsequence_bytes > 1024 || (subsequence_bytes & 3) != 0) return FEAR_TRAIN_ERR_SHAPE;
@@ -200,11 +227,15 @@ static int ji_launch(int form, const FearJpegIndexed* images, int n, const void*
         if ((reinterpret_cast<uintptr_t>(im.index) & 15) != 0 || (reinterpret_cast<uintptr_t>(im.scan) & 15) != 0 ||
             (reinterpret_cast<uintptr_t>(im.sub_start) & 3) != 0 || (form == 2 && (reinterpret_cast<uintptr_t>(im.row_sub) & 3) != 0))
             return FEAR_TRAIN_ERR_SHAPE;
-        if (form == 1) {
+        if (form == 1 || form == 3) {
             if (im.sub_count != 0 && (im.sub0 >= im.n_sub || im.sub_count > im.n_sub - im.sub0)) return FEAR_TRAIN_ERR_SHAPE;
             if (im.mcu_row0 > FEAR_JPEG_MAX_SIDE / 8 || im.mcu_rows > FEAR_JPEG_MAX_SIDE / 8 - im.mcu_row0) return FEAR_TRAIN_ERR_SHAPE;
         }
-        groups += ((uint64_t)(form == 1 ? im.sub_count : im.n_sub) + kJhLanes - 1) / kJhLanes;
+        if (form == 3) {
+            const uint32_t col0 = im.reserved & 0xFFFFu, cols = im.reserved >> 16;
+            if (cols == 0 || col0 > FEAR_JPEG_MAX_SIDE / 8 || cols > FEAR_JPEG_MAX_SIDE / 8 - col0) return FEAR_TRAIN_ERR_SHAPE;
+        }
+        groups += ((uint64_t)(form == 1 || form == 3 ? im.sub_count : im.n_sub) + kJhLanes - 1) / kJhLanes;
     }
     if (groups > 0x7fffffffu) return FEAR_TRAIN_ERR_SHAPE;
     JpegIndexedArgs a{};
@@ -219,6 +250,7 @@ static int ji_launch(int form, const FearJpegIndexed* images, int n, const void*
     if (groups == 0) return FEAR_TRAIN_OK;
     if (form == 0) hipLaunchKernelGGL(jpeg_huffman_indexed_kernel, grid, lanes, 0, static_cast<hipStream_t>(stream), a);
     else if (form == 1) hipLaunchKernelGGL(jpeg_huffman_indexed_rows_kernel, grid, lanes, 0, static_cast<hipStream_t>(stream), a);
+    else if (form == 3) hipLaunchKernelGGL(jpeg_huffman_indexed_windows_kernel, grid, lanes, 0, static_cast<hipStream_t>(stream), a);
     else hipLaunchKernelGGL(jpeg_huffman_indexed_rows_dev_kernel, grid, lanes, 0, static_cast<hipStream_t>(stream), a, rows_dev);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
@@ -237,6 +269,11 @@ int fear_jpeg_huffman_indexed_rows(const FearJpegIndexed* images, int n, const v
 int fear_jpeg_huffman_indexed_rows_dev(const FearJpegIndexed* images, int n, const void* table_dev, const int32_t* rows_dev, int16_t* coef,
                                        int32_t* status_dev, int subsequence_bytes, void* stream) {
     return ji_launch(2, images, n, table_dev, rows_dev, coef, status_dev, subsequence_bytes, stream);
+}
+
+int fear_jpeg_huffman_indexed_windows(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
+                                      int subsequence_bytes, void* stream) {
+    return ji_launch(3, images, n, table_dev, nullptr, coef, status_dev, subsequence_bytes, stream);
 }
 
 }  // extern "C"

@@ -88,9 +88,16 @@ struct PairGeom {            // the layout of FearPairGeom (include/fear_train.h
 
 // Out = float: the crops leave normalised, fp32 NCHW (fear_train_pairs).  Out = uint8_t: they leave as the colour stage made them,
 // uint8 NHWC, for the photometric stage behind (fear_train_pairs_u8).
+struct WindowFrame {         // the layout of fear_frame_window (include/fear_train.h)
+    const uint8_t* data;
+    int H, W;                // the frame's shape
+    int y0, x0, wh, ww;      // the rectangle of it that `data` holds
+};
+
 template <typename Out>
 struct PairArgs {
-    const CropFrame* frames;
+    const CropFrame* frames;     // fear_train_pairs, fear_train_pairs_u8
+    const WindowFrame* windows;  // fear_train_pairs_windows, fear_train_pairs_windows_u8 (WIN): in place of `frames`
     const uint8_t* border;   // [n_frames][3]
     const PairGeom* geom;    // [n]
     const uint8_t* lut;      // [n][3][256]
@@ -108,31 +115,59 @@ constexpr int kSearchBlocks = kTpSearch * kTpSearch / 256;          // one block
 constexpr int kTemplateBlocks = kTpTemplate * kTpTemplate / 256;    // one block = two template rows
 constexpr int kPairBlocks = kSearchBlocks + kTemplateBlocks + 1;     // + one block of target cells
 
-// A frame of a pair, with its border colour: an index outside the table reads no pixel and pads with 0.
+// A frame of a pair, with its border colour: an index outside the table reads no pixel and pads with 0.  WIN: the frame-fetch policy
+// of the windows form, in which `f` stays the frame's shape and `data` holds the rectangle (y0, x0, wh, ww) of it.
+template <bool WIN>
 struct PairFrame {
     CropFrame f;
     int pad[3];
 };
 
-template <typename Out>
-__device__ __forceinline__ PairFrame pair_frame(const PairArgs<Out>& a, int fi) {
-    PairFrame p;
+template <>
+struct PairFrame<true> {
+    CropFrame f;
+    int pad[3];
+    int y0, x0, wh, ww;
+};
+
+template <bool WIN, typename Out>
+__device__ __forceinline__ PairFrame<WIN> pair_frame(const PairArgs<Out>& a, int fi) {
+    PairFrame<WIN> p;
     if ((unsigned)fi < (unsigned)a.n_frames) {
-        p.f = a.frames[fi];
+        if constexpr (WIN) {
+            const WindowFrame w = a.windows[fi];
+            p.f = CropFrame{w.data, w.H, w.W};
+            p.y0 = w.y0; p.x0 = w.x0; p.wh = w.wh; p.ww = w.ww;
+        } else {
+            p.f = a.frames[fi];
+        }
         for (int c = 0; c < 3; ++c) p.pad[c] = a.border[fi * 3 + c];
     } else {
         p.f = CropFrame{nullptr, 0, 0};
+        if constexpr (WIN) p.y0 = p.x0 = p.wh = p.ww = 0;
         for (int c = 0; c < 3; ++c) p.pad[c] = 0;
     }
     return p;
 }
 
-__device__ __forceinline__ void frame_rgb(const PairFrame& p, int fx, int fy, int* rgb) {
+template <bool WIN>
+__device__ __forceinline__ void frame_rgb(const PairFrame<WIN>& p, int fx, int fy, int* rgb) {
     if (fx < 0 || fx >= p.f.W || fy < 0 || fy >= p.f.H) {
         rgb[0] = p.pad[0]; rgb[1] = p.pad[1]; rgb[2] = p.pad[2];
         return;
     }
-    const uint8_t* s = p.f.data + ((long)fy * p.f.W + fx) * 3;
+    const uint8_t* s;
+    if constexpr (WIN) {
+        if (!p.f.data || p.wh < 1 || p.ww < 1) {                         // a window without pixels
+            rgb[0] = p.pad[0]; rgb[1] = p.pad[1]; rgb[2] = p.pad[2];
+            return;
+        }
+        // clamped to the window: one that is too small gives wrong pixels, never a read outside it
+        const int wy = min(max(fy - p.y0, 0), p.wh - 1), wx = min(max(fx - p.x0, 0), p.ww - 1);
+        s = p.f.data + ((long)wy * p.ww + wx) * 3;
+    } else {
+        s = p.f.data + ((long)fy * p.f.W + fx) * 3;
+    }
     rgb[0] = s[0]; rgb[1] = s[1]; rgb[2] = s[2];
 }
 
@@ -150,7 +185,8 @@ __device__ __forceinline__ Taps crop_taps(int d, int S, int src) {
 
 // Pixel (column taps tx, row taps ty) of the S x S resize of context box ctx: crop_resize_normalize_kernel's arithmetic — identity,
 // exact 2x decimation (2x2 box mean), or 11-bit bilinear — on all three channels.
-__device__ __forceinline__ void crop_rgb(const PairFrame& p, const int32_t* ctx, int S, int dx, int dy, const Taps& tx, const Taps& ty,
+template <bool WIN>
+__device__ __forceinline__ void crop_rgb(const PairFrame<WIN>& p, const int32_t* ctx, int S, int dx, int dy, const Taps& tx, const Taps& ty,
                                          int* rgb) {
     const int cx = ctx[0], cy = ctx[1], cw = ctx[2], ch = ctx[3];
     if (cw == S && ch == S) {
@@ -229,7 +265,7 @@ __device__ __forceinline__ int warp_y(const double* inv, int y) {
     return ((int)rint((inv[2] * (double)y + inv[3]) * 1024.0) + 16) >> 5;
 }
 
-template <typename Out>
+template <typename Out, bool WIN>
 __global__ __launch_bounds__(256) void train_pairs_kernel(PairArgs<Out> a) {
     const int pair = blockIdx.y;
     const int blk = blockIdx.x;
@@ -237,7 +273,7 @@ __global__ __launch_bounds__(256) void train_pairs_kernel(PairArgs<Out> a) {
     if (blk < kSearchBlocks) {
         // ---- search pixel (dx, dy): warpAffine INTER_LINEAR of the 512 stage-1 crop, BORDER_CONSTANT 0
         const int dy = blk, dx = threadIdx.x;
-        const PairFrame p = pair_frame(a, g.s_frame);
+        const PairFrame<WIN> p = pair_frame<WIN>(a, g.s_frame);
         const int X = warp_x(g.inv, dx), Y = warp_y(g.inv, dy);
         const int sx = X >> 5, sy = Y >> 5, fx = X & 31, fy = Y & 31;
         // initInterTab2D(INTER_LINEAR, fixed point) entry (fy, fx): (vy_k1 vx_k2) * 32768, exact; entry (0, 0) saturates its 32768
@@ -268,7 +304,7 @@ __global__ __launch_bounds__(256) void train_pairs_kernel(PairArgs<Out> a) {
         // ---- template pixel: crop_resize_normalize_kernel's crop, the colour stage in front of the normalisation
         const int px = (blk - kSearchBlocks) * 256 + threadIdx.x;
         const int dy = px / kTpTemplate, dx = px % kTpTemplate;
-        const PairFrame p = pair_frame(a, g.t_frame);
+        const PairFrame<WIN> p = pair_frame<WIN>(a, g.t_frame);
         const Taps tx = crop_taps<true>(dx, kTpTemplate, g.t_ctx[2]);
         const Taps ty = crop_taps<false>(dy, kTpTemplate, g.t_ctx[3]);
         int rgb[3];
@@ -561,8 +597,8 @@ void set_normalisation(Args& a) {
     }
 }
 
-template <typename Out>
-int launch_train_pairs(const fear_frame* frames, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom, const uint8_t* lut,
+template <typename Out, bool WIN = false>
+int launch_train_pairs(const void* frames, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom, const uint8_t* lut,
                        int n, Out* template_out, Out* search_out, float* gt_reg, float* gt_cls, float* gt_weight, void* stream) {
     static_assert(sizeof(FearPairGeom) == sizeof(PairGeom) && offsetof(FearPairGeom, inv) == offsetof(PairGeom, inv) &&
                   offsetof(FearPairGeom, presence) == offsetof(PairGeom, presence), "FearPairGeom and PairGeom must share one layout");
@@ -571,7 +607,11 @@ int launch_train_pairs(const fear_frame* frames, int n_frames, const uint8_t* bo
     if (!geom || !lut || !template_out || !search_out || !gt_reg || !gt_cls || !gt_weight) return FEAR_TRAIN_ERR_NULL;
     if (n_frames > 0 && (!frames || !border_rgb)) return FEAR_TRAIN_ERR_NULL;
     PairArgs<Out> a{};
-    a.frames = reinterpret_cast<const CropFrame*>(frames);
+    static_assert(sizeof(fear_frame_window) == sizeof(WindowFrame) && offsetof(fear_frame_window, h) == offsetof(WindowFrame, H) &&
+                  offsetof(fear_frame_window, y0) == offsetof(WindowFrame, y0) && offsetof(fear_frame_window, ww) == offsetof(WindowFrame, ww),
+                  "fear_frame_window and WindowFrame must share one layout");
+    if constexpr (WIN) a.windows = static_cast<const WindowFrame*>(frames);
+    else a.frames = static_cast<const CropFrame*>(frames);
     a.border = border_rgb;
     a.geom = reinterpret_cast<const PairGeom*>(geom);
     a.lut = lut;
@@ -579,7 +619,7 @@ int launch_train_pairs(const fear_frame* frames, int n_frames, const uint8_t* bo
     a.gt_reg = gt_reg; a.gt_cls = gt_cls; a.gt_weight = gt_weight;
     a.n_frames = n_frames;
     set_normalisation(a);
-    hipLaunchKernelGGL(train_pairs_kernel<Out>, dim3(kPairBlocks, (unsigned)n), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL((train_pairs_kernel<Out, WIN>), dim3(kPairBlocks, (unsigned)n), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }
@@ -637,6 +677,20 @@ int fear_train_pairs_u8(const fear_frame* frames, int n_frames, const uint8_t* b
                         int n, uint8_t* template_u8, uint8_t* search_u8, float* gt_reg, float* gt_cls, float* gt_weight, void* stream) {
     return launch_train_pairs<uint8_t>(frames, n_frames, border_rgb, geom, lut, n, template_u8, search_u8, gt_reg, gt_cls, gt_weight,
                                        stream);
+}
+
+int fear_train_pairs_windows(const fear_frame_window* windows, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom,
+                             const uint8_t* lut, int n, float* template_out, float* search_out, float* gt_reg, float* gt_cls,
+                             float* gt_weight, void* stream) {
+    return launch_train_pairs<float, true>(windows, n_frames, border_rgb, geom, lut, n, template_out, search_out, gt_reg, gt_cls,
+                                           gt_weight, stream);
+}
+
+int fear_train_pairs_windows_u8(const fear_frame_window* windows, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom,
+                                const uint8_t* lut, int n, uint8_t* template_u8, uint8_t* search_u8, float* gt_reg, float* gt_cls,
+                                float* gt_weight, void* stream) {
+    return launch_train_pairs<uint8_t, true>(windows, n_frames, border_rgb, geom, lut, n, template_u8, search_u8, gt_reg, gt_cls,
+                                             gt_weight, stream);
 }
 
 int fear_photometric_u8(const uint8_t* crops_u8, int n, int H, int W, const FearPhotoOp* ops, const float* taps, const float* qtable,

@@ -107,6 +107,19 @@ class _Geometry:
         first = 0 if c == 0 else band_mcus * self.h * self.v + (c - 1) * band_mcus
         return first + ((my - row0) * vc + j) * self.blocks_w[c] + mx * hc + i
 
+    def window_block(self, mcu: int, slot: int, row0: int, rows: int, col0: int, cols: int) -> int:
+        """The index of slot `slot` of MCU `mcu` in an image that consists of the MCUs of the rows row0 .. row0 + rows) and the columns
+        col0 .. col0 + cols) alone (jh_window_base): -1 for a block of another row or column, by explicit range tests."""
+        my, mx = divmod(mcu, self.mcus_x)
+        if my < row0 or my >= row0 + rows or mx < col0 or mx >= col0 + cols:
+            return -1
+        c = self.comp[slot]
+        j, i = divmod(slot, self.h) if c == 0 else (0, 0)
+        hc, vc = (self.h, self.v) if c == 0 else (1, 1)
+        win_mcus = rows * cols
+        first = 0 if c == 0 else win_mcus * self.h * self.v + (c - 1) * win_mcus
+        return first + ((my - row0) * vc + j) * (cols * hc) + (mx - col0) * hc + i
+
 
 _ERR, _DC, _ZEROS, _AC, _END = range(5)
 
@@ -397,7 +410,44 @@ def scan_row_sub(header: _Header, sub_start, index) -> np.ndarray:
     return np.concatenate([at, [n_sub]]).astype(np.uint32)
 
 
-def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: int, order=None, band=None, row_sub=None):
+def window_lanes(header: _Header, sub_start, index, lanes, cols) -> np.ndarray:
+    """The lanes of `lanes` (image-numbered subsequences, a band's) that `fear_jpeg_huffman_indexed_windows` runs for the MCU columns
+    cols = (c0, c1), clipped to mcus_x: int64, in order.  A lane knows its own entry and the next subsequence's, or its segment's block
+    count where the next subsequence lies in another segment (or nowhere).  The blocks it stores have the segment ordinals lo .. hi):
+    lo = begun - (1 if a block is open at its entry), hi = min(the next begun, the segment's count).  Their MCUs are the consecutive
+    first_mcu + lo // nslots .. first_mcu + (hi - 1) // nslots, and the lane runs if one of them has its column in [c0, c1): `count`
+    MCUs from column x_lo cover every column when count >= mcus_x, else the columns x_lo .. x_lo + count - 1, of which the part past
+    mcus_x - 1 wraps to the next row's first columns.  The rows play no part: the rule may run a lane that stores nothing, never the
+    reverse.  Arithmetic on loaded values alone — no loop over blocks, no bound that depends on the data."""
+    sub_start = np.asarray(sub_start, dtype=np.int64)
+    n_seg, n_sub = sub_start.size - 1, int(sub_start[-1])
+    lanes = np.asarray(lanes, dtype=np.int64).reshape(-1)
+    mcus_x = int(header.mcus_x)
+    c0 = min(max(int(cols[0]), 0), mcus_x)
+    c1 = min(max(int(cols[1]), c0), mcus_x)
+    if lanes.size == 0 or c1 == c0:
+        return np.zeros(0, dtype=np.int64)
+    nslots = 1 if len(header.ids) == 1 else header.h[0] * header.v[0] + 2
+    n_mcu = mcus_x * header.mcus_y
+    interval = header.restart if header.restart else n_mcu
+    seg = np.searchsorted(sub_start[:n_seg], lanes, side="right") - 1
+    first_mcu = np.minimum(seg * interval, n_mcu)
+    expected = np.minimum(interval, n_mcu - first_mcu) * nslots
+    begun, z = np.asarray(index["begun"], dtype=np.int64), np.asarray(index["sz"], dtype=np.int64) & 255
+    inside = (lanes + 1 < sub_start[seg + 1]) & (lanes + 1 < n_sub)
+    next_begun = np.where(inside, begun[np.minimum(lanes + 1, n_sub - 1)], expected)
+    lo = begun[lanes] - ((z[lanes] != 0) & (begun[lanes] > 0))
+    hi = np.minimum(next_begun, expected)
+    some = hi > lo
+    m_lo = first_mcu + lo // nslots
+    count = np.where(some, (hi - 1) // nslots - lo // nslots + 1, 0)
+    x_lo = m_lo % mcus_x
+    x_end = x_lo + count - 1
+    touches = (count >= mcus_x) | ((x_lo < c1) & (x_end >= c0)) | ((x_end >= mcus_x) & (x_end - mcus_x >= c0))
+    return lanes[some & touches]
+
+
+def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: int, order=None, band=None, row_sub=None, cols=None):
     """The contract of `fear_jpeg_huffman_indexed`: (coefficients per component, status).  Every subsequence is decoded from its index
     entry alone, in `order` (any permutation of the image's subsequences; the natural one by default), as one lane of
     jpeg_huffman_indexed_kernel does it: the segment by a search of `sub_start`, the write pass's rules, and the verdict — the lane of a
@@ -407,7 +457,12 @@ def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: 
     With `band` = (a, b), MCU rows a .. b) clipped to the image, it is the contract of `fear_jpeg_huffman_indexed_rows`: only the
     subsequences row_sub[a] .. min(row_sub[b], n_sub - 1) are decoded (`row_sub` is `scan_row_sub`'s table, computed when None; `order`
     permutes those), only the blocks of the band's rows are stored, and the coefficients are the band's: per component the rows of an
-    image that consists of those MCU rows alone.  Lanes that do not run judge nothing."""
+    image that consists of those MCU rows alone.  Lanes that do not run judge nothing.
+    With `band` and `cols` = (c0, c1), MCU columns c0 .. c1) clipped to the image, it is the contract of
+    `fear_jpeg_huffman_indexed_windows`: of the band's lanes only those `window_lanes` names run (a lane all of whose MCUs lie outside
+    the columns returns before it judges anything; `order` permutes the lanes that run), a block is stored only when its MCU row is in
+    the band and its MCU column in the range, and the coefficients are the window's: per component the blocks of an image made of those
+    (b - a) x (c1 - c0) MCUs alone."""
     _check_subsequence_bytes(subsequence_bytes)
     data = bytes(data)
     hd = _parse(data)
@@ -417,6 +472,8 @@ def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: 
     sub_start = np.asarray(sub_start, dtype=np.int64)
     assert sub_start.size == n_seg + 1 and int(sub_start[-1]) == n_sub
     lanes, rows_band, n_values = range(n_sub), None, 64 * g.total_blocks
+    if cols is not None and band is None:
+        raise ValueError("cols go with a band")
     if band is not None:
         a = min(max(int(band[0]), 0), hd.mcus_y)
         b = min(max(int(band[1]), a), hd.mcus_y)
@@ -424,6 +481,12 @@ def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: 
             row_sub = scan_row_sub(hd, sub_start, index)
         rows_band, n_values = (a, b - a), 64 * (b - a) * g.mcus_x * g.nslots
         lanes = range(int(row_sub[a]), min(int(row_sub[b]), n_sub - 1) + 1) if b > a else range(0)
+    window = None
+    if cols is not None:
+        c0 = min(max(int(cols[0]), 0), g.mcus_x)
+        c1 = min(max(int(cols[1]), c0), g.mcus_x)
+        window, n_values = (c0, c1 - c0), 64 * rows_band[1] * (c1 - c0) * g.nslots
+        lanes = window_lanes(hd, sub_start, index, np.arange(lanes.start, lanes.stop), (c0, c1)).tolist()
     dense = np.zeros(n_values, dtype=np.int16)
     writes = np.zeros(n_values, dtype=np.uint8)
     segs = [_Segment(hd, g, stream, seg_start, s) for s in range(n_seg)]
@@ -434,7 +497,14 @@ def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: 
         sg, i, e = segs[s], sub - int(sub_start[s]), index[sub]
         slot, z = min(int(e["sz"]) >> 8, g.nslots - 1), min(int(e["sz"]) & 255, 63)
         pred = [int(v) for v in e["dc"]]
-        state, begun, failed = _write_pass(sg, g, (int(e["p"]), slot, z), (i + 1) * SB, int(e["begun"]), pred, dense, writes, rows_band)
+        record = [] if window is not None else None                         # a window's stores are placed below, window-dense
+        state, begun, failed = _write_pass(sg, g, (int(e["p"]), slot, z), (i + 1) * SB, int(e["begun"]), pred,
+                                           None if window is not None else dense, writes, rows_band, record=record)
+        for mcu, at_slot, z0, z1, value in record or ():
+            b = g.window_block(mcu, at_slot, rows_band[0], rows_band[1], window[0], window[1])
+            if 0 <= b < rows_band[1] * window[1] * g.nslots:
+                dense[64 * b + z0:64 * b + z1] = value
+                writes[64 * b + z0:64 * b + z1] += 1
         if (i + 1) * SB >= sg.L and begun - (state[2] != 0) < sg.expected:    # the segment's last subsequence: its block count
             failed = True
         if i == 0 and s > 0 and sub_start[s - 1] == sub_start[s]:            # an empty segment in front owes blocks
@@ -448,8 +518,9 @@ def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: 
     coef, at = [], 0
     for c in range(g.nf):
         high = hd.blocks_h[c] if rows_band is None else rows_band[1] * (g.v if c == 0 else 1)
-        size = hd.blocks_w[c] * high
-        coef.append(dense[64 * at:64 * (at + size)].reshape(high, hd.blocks_w[c], 64))
+        wide = hd.blocks_w[c] if window is None else window[1] * (g.h if c == 0 else 1)
+        size = wide * high
+        coef.append(dense[64 * at:64 * (at + size)].reshape(high, wide, 64))
         at += size
     return coef, status
 

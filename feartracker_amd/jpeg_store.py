@@ -20,7 +20,12 @@ from the device").  `StoreFrames(store, ids)` names a sequence of frames kept in
 
 `decode`, `decode_rows` (rows on the host), `shape` and the two plans take `scale` 2, 4 or 8: the frames at 1/2, 1/4 or 1/8 size, decoded
 in the DCT domain as libjpeg's scale_denom does, with `fear_jpeg_decode_scaled_u8` in place of `fear_jpeg_decode_u8` behind the same
-Huffman stage ("Reduced-size decoding")."""
+Huffman stage ("Reduced-size decoding").
+
+A batch of training pairs reads a rectangle of a frame, not its whole rows.  `JpegStore.decode_windows` decodes per frame the MCUs that
+cover one rectangle — `plan_decode_windows` on the host, `fear_jpeg_huffman_indexed_windows`, whose lanes of the band that cannot touch
+the rectangle's MCU columns return early and which stores the blocks window-dense, and the unchanged pixel kernels on the window as an
+image of its own — and returns COMPACT frames with their origins, a `WindowFrames` ("Windows")."""
 from __future__ import annotations
 
 import ctypes
@@ -32,6 +37,7 @@ from . import jpeg_frames
 from .jpeg_frames import (ERR_UNSUPPORTED, Item, JpegDecoder, MalformedJPEG, UnsupportedJPEG, _check_scale, _fill_header, _judge,
                           _launch_pixels, _raise_as_python, _read_items)
 from .jpeg_huffman import SUBSEQ_DTYPE, _check_subsequence_bytes, scan_row_sub
+from .train_data.records import WindowFrames  # noqa: F401  (what decode_windows returns; the builder takes it)
 
 KIND_SCAN, KIND_PIXELS = 0, 1
 KIND_NAMES = np.array(["scan", "pixels"])
@@ -178,6 +184,86 @@ def plan_decode_rows(columns: np.ndarray, row_sub: np.ndarray, ids, rows, worksp
     return groups
 
 
+def plan_decode_windows(columns: np.ndarray, row_sub: np.ndarray, ids, windows, workspace_limit: int, max_group: int = 65535,
+                        scale: int = 1) -> List[dict]:
+    """The host's share of `JpegStore.decode_windows`, as its two siblings a pure function without a loop over the files.  `windows`
+    is (n, 4) pixel rectangles [y0, y1) x [x0, x1) per position, as (y0, y1, x0, x1), clipped to the frame; one without rows or columns
+    is the empty window.  The rows follow `plan_decode_rows`: the band of MCU rows a .. b) that covers [y0, y1), one more on each
+    side where `halo` is set, at scale 1 alone.  The columns follow the same tap rule: the MCU columns c0 .. c1), c0 = x0 // mcu_w and
+    c1 = ceil(x1 / mcu_w), one more on each side, clipped to the image, where the file subsamples horizontally (mcu_w == 16: the fancy
+    upsampling reads one chroma column to the left and to the right) — at every scale, where it is conservative.  Groups are cut by the
+    WINDOW's dense coefficients (128 bytes per block of its (b - a) (c1 - c0) MCUs).  Per group, over its "scan" positions with a
+    window, `scan` (relative to lo):
+        sub0, sub_count, sub_prefix, mcu_row0, mcu_rows     plan_decode_rows', of the band: the lanes fear_jpeg_huffman_indexed_windows gets
+        cols                  uint32 c0 | (c1 - c0) << 16: the record's `reserved` word
+        band_height, win_width   the FULL-size shape of the window as an image of its own: what is left of the image where the window
+                              reaches its last MCU row or column, so that libjpeg's edge rules apply at the true edges
+        block_prefix, pixel_prefix, coef_offset, values, plane_offset, workspace_bytes, most
+                              plan_decode's, of the window as an image of its own
+        band_out              zeros: a window's pixels begin where its tensor begins
+    and over all its positions
+        origin                int32 (hi - lo, 2): the frame coordinates (y, x) of each tensor's first pixel — (a mcu_h, c0 mcu_w) for a
+                              "scan" position, (y0, x0) for one kept as pixels, (0, 0) for the empty window
+        high, wide            each tensor's shape: the window's MCUs cut to the frame | the rectangle itself | 0, 0
+        window                int64 (hi - lo, 4): the clipped request
+        out_offset, out_bytes the compact tensors, each at a multiple of 16 bytes.
+    At `scale` 2, 4 or 8 (m = 8 // scale) `windows` are rectangles of the SCALED frame; a scaled MCU is (mcu_h m / 8) x (mcu_w m / 8)
+    pixels; `band_height` and `win_width` stay full-size, what the record of fear_jpeg_decode_scaled_u8 holds, and every other
+    quantity is the scaled frame's."""
+    m = 8 // _check_scale(scale)
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    win = np.asarray(windows, dtype=np.int64).reshape(-1, 4)
+    col = columns[ids]
+    is_scan = col["kind"] == KIND_SCAN
+    full_h, full_w = col["H"].astype(np.int64), col["W"].astype(np.int64)
+    full_mcu_h = np.maximum(col["mcu_h"].astype(np.int64), 1)
+    # an MCU's width, from what the mirror holds: a colour MCU has h v + 2 blocks and is 8 v rows high, a gray one is one block
+    nslots = col["nslots"].astype(np.int64)
+    full_mcu_w = np.where(nslots > 1, 8 * np.maximum((nslots - 2) // (full_mcu_h // 8).clip(1), 1), 8)
+    H, W = _scaled_sides(full_h, full_w, scale)
+    mcu_h, mcu_w = np.maximum(full_mcu_h * m // 8, 1), np.maximum(full_mcu_w * m // 8, 1)
+    mcus_y, mcus_x = col["mcus_y"].astype(np.int64), col["mcus_x"].astype(np.int64)
+    y0, y1 = np.clip(win[:, 0], 0, H), np.clip(win[:, 1], 0, H)
+    x0, x1 = np.clip(win[:, 2], 0, W), np.clip(win[:, 3], 0, W)
+    filled = (y0 < y1) & (x0 < x1)
+    some = is_scan & filled
+    halo_y = col["halo"].astype(np.int64) if m == 8 else np.zeros(ids.size, dtype=np.int64)
+    halo_x = (full_mcu_w == 16).astype(np.int64)
+    a = np.where(some, np.maximum(y0 // mcu_h - halo_y, 0), 0)
+    b = np.where(some, np.minimum(-(-y1 // mcu_h) + halo_y, mcus_y), 0)
+    c0 = np.where(some, np.maximum(x0 // mcu_w - halo_x, 0), 0)
+    c1 = np.where(some, np.minimum(-(-x1 // mcu_w) + halo_x, mcus_x), 0)
+    blocks = (b - a) * (c1 - c0) * nslots
+    high = np.minimum(b * mcu_h, H) - a * mcu_h
+    wide = np.minimum(c1 * mcu_w, W) - c0 * mcu_w
+    high_full = np.minimum(b * full_mcu_h, full_h) - a * full_mcu_h
+    wide_full = np.minimum(c1 * full_mcu_w, full_w) - c0 * full_mcu_w
+    n_sub = col["n_sub"].astype(np.int64)
+    at = np.where(some, col["row_at"], 0)
+    first = np.where(some, row_sub[at + a].astype(np.int64), 0) if row_sub.size else np.zeros(ids.size, np.int64)
+    last = np.where(some, np.minimum(row_sub[at + b].astype(np.int64), n_sub - 1), -1) if row_sub.size else np.full(ids.size, -1, np.int64)
+    count = np.maximum(last - first + 1, 0)
+    kept = ~is_scan & filled                                             # an entry kept as pixels hands out the rectangle itself
+    origin = np.stack([np.where(kept, y0, a * mcu_h), np.where(kept, x0, c0 * mcu_w)], axis=1).astype(np.int32)
+    high, wide = np.where(kept, y1 - y0, high), np.where(kept, x1 - x0, wide)
+    window = np.where(filled[:, None], np.stack([y0, y1, x0, x1], axis=1), 0)
+    groups = []
+    for lo, hi in _cut(128 * blocks, workspace_limit, max_group):
+        scan = np.flatnonzero(some[lo:hi])
+        pick = lo + scan
+        groups.append(dict(
+            lo=lo, hi=hi, scan=scan,
+            sub0=first[pick].astype(np.uint32), sub_count=count[pick].astype(np.uint32),
+            sub_prefix=_exclusive(-(-count[pick] // LANES)).astype(np.uint32),
+            mcu_row0=a[pick].astype(np.uint32), mcu_rows=(b - a)[pick].astype(np.uint32),
+            cols=(c0[pick] | (c1 - c0)[pick] << 16).astype(np.uint32),
+            band_height=high_full[pick].astype(np.int32), win_width=wide_full[pick].astype(np.int32),
+            band_out=np.zeros(pick.size, dtype=np.int64),
+            origin=origin[lo:hi], high=high[lo:hi], wide=wide[lo:hi], window=window[lo:hi],
+            **_layout(blocks[pick], high[pick] * wide[pick], (high * wide)[lo:hi])))
+    return groups
+
+
 def _place_images(images: np.ndarray, coef, coef_offset: np.ndarray, block_start, out, out_offset: np.ndarray, plane_offset: np.ndarray) -> None:
     """The addresses of a group's FearJpegImage records: each image's dense coefficients in `coef` (an int16 tensor, `coef_offset` in
     values), the dense `block_start` table they share, where its pixels go in `out` and its planes in the workspace."""
@@ -227,8 +313,10 @@ class JpegStore:
     file the store keeps mcus_y + 1 row-table values on the host and 3 bytes of the device's border table more (`resident["rows"]`,
     `resident["border"]`, both counted in `nbytes`); the row table is also resident on the device (one tensor per `add`, the same
     4 (mcus_y + 1) bytes per file that `resident["rows"]` counts), for `decode_rows` with `rows` on the device.
-    Out of scope: eviction and `remove`, saving a store to disk, sharding over ranks, `JpegDecoder`'s default, compact
-    band frames and a window-aware frame record (`decode_rows` returns frames of the full shape)."""
+    `decode_windows(ids, windows)` decodes per frame the MCUs that cover one rectangle and returns compact tensors with their origins
+    (`WindowFrames`), which `TrainPairBuilder.build` takes in place of the frames.
+    Out of scope: eviction and `remove`, saving a store to disk, sharding over ranks, `JpegDecoder`'s default, windows given on
+    the device."""
     PENDING_CALLS = 64
 
     def __init__(self, device: int = 0, capacity_bytes: Optional[int] = None, subsequence_bytes: int = 128, slab_bytes: int = 256 << 20,
@@ -602,17 +690,19 @@ class JpegStore:
         return frames
 
     def _decode_group(self, ids: np.ndarray, plan: dict, frames: List, rows=None, scale: int = 1) -> None:
-        """One group of `decode` and of both forms of `decode_rows`: the shared block_start table, the gathered records with the
+        """One group of `decode`, of both forms of `decode_rows` and of `decode_windows`: the shared block_start table, the gathered records with the
         group's addresses, one pinned upload, the Huffman kernel, the pixel stage, the verdicts, the frames.  What the plan carries
         and `rows` select the kernels: a plan of `plan_decode_rows` carries the bands (sub0, sub_count, mcu_row0, mcu_rows, band_height,
-        band_out), which go into the records for `fear_jpeg_huffman_indexed_rows`; `rows`, the call's device tensor, goes with
+        band_out), which go into the records for `fear_jpeg_huffman_indexed_rows`; a plan of `plan_decode_windows` carries the MCU
+        columns and the window's width as well (cols, win_width) and the compact tensors' shapes (high, wide, window), for
+        `fear_jpeg_huffman_indexed_windows`; `rows`, the call's device tensor, goes with
         `plan_decode`'s full-image plan to the two kernels that read the bands on the device."""
         import torch
         from . import train_abi as abi
         P = ctypes.c_void_p
         lo, hi, scan = plan["lo"], plan["hi"], plan["scan"]
         group = ids[lo:hi]
-        sids, nd, banded = group[scan], scan.size, "sub0" in plan
+        sids, nd, banded, windowed = group[scan], scan.size, "sub0" in plan, "cols" in plan
         with torch.cuda.device(self.device):
             out = torch.empty(max(plan["out_bytes"], 16), dtype=torch.uint8, device=self.device)
             out_offset = plan["out_offset"]
@@ -630,6 +720,9 @@ class JpegStore:
                         indexed[field] = plan[field]
                     images["height"] = plan["band_height"]
                     at_out = at_out + plan["band_out"]
+                if windowed:                                             # and the band's MCU columns: a compact image of its own
+                    indexed["reserved"] = plan["cols"]
+                    images["width"] = plan["win_width"]
                 _place_images(images, coef, plan["coef_offset"], block_start, out, at_out, plan["plane_offset"])
                 # one pinned upload: prefix | FearJpegIndexed records, then two prefixes | FearJpegImage records; with rows on the
                 # device and a group that is no run of positions also the positions, to gather the group's rows with
@@ -642,7 +735,8 @@ class JpegStore:
                 self._records = (indexed, images)                        # the calls below get their addresses
                 self.last_upload_bytes = dev.numel()
                 if rows is None:
-                    abi.launch(self._lib, "fear_jpeg_huffman_indexed_rows" if banded else "fear_jpeg_huffman_indexed", P(indexed.ctypes.data), nd,
+                    huffman = "fear_jpeg_huffman_indexed_windows" if windowed else ("fear_jpeg_huffman_indexed_rows" if banded else "fear_jpeg_huffman_indexed")
+                    abi.launch(self._lib, huffman, P(indexed.ctypes.data), nd,
                                P(dev.data_ptr()), P(coef.data_ptr()), P(status.data_ptr()), self.subsequence_bytes, stream)
                     _launch_pixels(self._lib, P(images.ctypes.data), nd, table, ws.data_ptr(), plan["workspace_bytes"], scale, stream)
                 else:                                                    # the group's rows: a slice, or a gather on the device; no wait
@@ -658,9 +752,16 @@ class JpegStore:
                 event.record()
                 self._pending.append((event, verdict, lo + scan, sids))
             cols = self._columns[group]
-            high, wide = _scaled_sides(cols["H"], cols["W"], scale)
-            for k in np.flatnonzero(cols["kind"] == KIND_PIXELS):        # the entries kept as pixels: a whole copy, never an alias
-                out[out_offset[k]:out_offset[k] + 3 * high[k] * wide[k]].copy_(self._pixels[int(group[k])].view(-1), non_blocking=True)
+            if windowed:                                                 # compact tensors; an entry kept as pixels gives its rectangle
+                high, wide = plan["high"], plan["wide"]
+                for k in np.flatnonzero((cols["kind"] == KIND_PIXELS) & (high * wide > 0)):
+                    y0, y1, x0, x1 = plan["window"][k].tolist()
+                    out[out_offset[k]:out_offset[k] + 3 * high[k] * wide[k]].view(int(high[k]), int(wide[k]), 3).copy_(
+                        self._pixels[int(group[k])][y0:y1, x0:x1], non_blocking=True)
+            else:
+                high, wide = _scaled_sides(cols["H"], cols["W"], scale)
+                for k in np.flatnonzero(cols["kind"] == KIND_PIXELS):    # the entries kept as pixels: a whole copy, never an alias
+                    out[out_offset[k]:out_offset[k] + 3 * high[k] * wide[k]].copy_(self._pixels[int(group[k])].view(-1), non_blocking=True)
         frames[lo:hi] = _frame_views(out, out_offset, high, wide)
 
     def _block_start(self, stream):
@@ -741,6 +842,35 @@ class JpegStore:
             raise ValueError(f"rows must be ({ids.size}, 2) integers, one [y0, y1) per id")
         return self._decode_groups(ids, plan_decode_rows(self._columns, self._row_sub, ids, rows, self.workspace_limit, scale=scale), check,
                                    scale=scale)
+
+    # --------------------------------------------------------------------------------------------------------------- decode_windows
+    def decode_windows(self, ids, windows, check: bool = False, scale: int = 1) -> WindowFrames:
+        """`decode` for the rectangle of each frame that a consumer reads, as COMPACT tensors.  `windows` is (len(ids), 4) integers on
+        the host, [y0, y1) x [x0, x1) per position as (y0, y1, x0, x1), in pixels of the frame `decode(ids, scale=scale)` returns and
+        clipped to it.  The result is a `WindowFrames`: `frames[i]` is a private uint8 (wh, ww, 3) tensor (cut from one allocation per
+        group) whose first pixel is the frame's pixel `origin[i]`, and
+            frames[i][y0 - oy:y1 - oy, x0 - ox:x1 - ox]  equals  decode(ids, scale=scale)[i][y0:y1, x0:x1]
+        byte for byte; all other bytes of the tensor are unspecified.  `shape` is `shape(ids, scale)` and `window` the clipped request.
+        Per "scan" position the MCUs of the band of rows (`decode_rows`' rule, halo included) and of the MCU columns that cover
+        [x0, x1) — one more on each side where the file subsamples horizontally, at every scale — are Huffman-decoded by
+        `fear_jpeg_huffman_indexed_windows`: the band's lanes, of which those that cannot touch the columns return early, and the
+        blocks stored window-dense.  The window then goes through `fear_jpeg_decode_u8` (at a scale `fear_jpeg_decode_scaled_u8`) as an
+        image of its own that ends where the window ends, so that the edge rules apply at the frame's true right and bottom edges.
+        An empty window gives a (0, 0, 3) tensor and no lanes; an entry kept as pixels gives a device-to-device copy of the rectangle
+        itself at scale 1 and is an `UnsupportedJPEG` at a scale.  A `windows` of another shape is a ValueError and a bad id an
+        IndexError, both before any launch.  Like `decode` it never waits, the statuses (of the lanes that ran) go to `check()`, and
+        `workspace_limit` splits the call, by the windows' dense coefficients.  Windows on the device are out of scope."""
+        scale = _check_scale(scale)
+        ids = self._checked(ids)
+        self._scan_only(ids, scale)
+        windows = np.asarray(windows)
+        if windows.shape != (ids.size, 4) or not np.issubdtype(windows.dtype, np.integer):
+            raise ValueError(f"windows must be ({ids.size}, 4) integers, one (y0, y1, x0, x1) per id")
+        plans = plan_decode_windows(self._columns, self._row_sub, ids, windows, self.workspace_limit, scale=scale)
+        frames = self._decode_groups(ids, plans, check, scale=scale)
+        origin = np.concatenate([np.zeros((0, 2), dtype=np.int32)] + [p["origin"] for p in plans])
+        window = np.concatenate([np.zeros((0, 4), dtype=np.int64)] + [p["window"] for p in plans])
+        return WindowFrames(frames, origin, self.shape(ids, scale), window)
 
     def check(self) -> None:
         """Wait for the calls not yet checked and raise MalformedJPEG for the first image the device refused, naming the position in its

@@ -83,6 +83,9 @@ TRAIN_SYMBOLS = {
     "fear_train_pairs": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _P, _P], _i),
     # the photometric stage behind the pairs (FearPhotoOp below)
     "fear_train_pairs_u8": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _P, _P], _i),
+    # the same two for frames of which a rectangle is stored (FearFrameWindow below; JpegStore.decode_windows)
+    "fear_train_pairs_windows": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _P, _P], _i),
+    "fear_train_pairs_windows_u8": ([_P, _i, _P, _P, _P, _i, _P, _P, _P, _P, _P, _P], _i),
     "fear_photometric_u8": ([_P, _i, _i, _i, _P, _P, _P, _P, _P], _i),
     "fear_photometric_stage_u8": ([_P, _i, _i, _i, _P, _P, _P, _P, _P], _i),
     # ImageCompression: the JPEG round trip between the stage above and fear_photometric_u8
@@ -108,6 +111,8 @@ TRAIN_SYMBOLS = {
     "fear_jpeg_index_build": ([_P, _i, _P, _P, _P, _P, _P, _i, _P], _i),
     "fear_jpeg_huffman_indexed": ([_P, _i, _P, _P, _P, _i, _P], _i),
     "fear_jpeg_huffman_indexed_rows": ([_P, _i, _P, _P, _P, _i, _P], _i),
+    # the band's lanes that touch a range of MCU columns, window-dense (JpegStore.decode_windows)
+    "fear_jpeg_huffman_indexed_windows": ([_P, _i, _P, _P, _P, _i, _P], _i),
     # the band of rows taken from device memory (JpegStore.decode_rows with a device tensor)
     "fear_jpeg_huffman_indexed_rows_dev": ([_P, _i, _P, _P, _P, _P, _i, _P], _i),
     "fear_jpeg_decode_u8_rows_dev": ([_P, _i, _P, _P, _P, _sz, _P], _i),
@@ -236,6 +241,16 @@ class FearFrame(ctypes.Structure):
 
 
 assert ctypes.sizeof(FearFrame) == 16 and ctypes.sizeof(ctypes.c_void_p) == 8
+
+
+class FearFrameWindow(ctypes.Structure):
+    """include/fear_train.h `fear_frame_window`: the rectangle (y0, x0, wh, ww) of a uint8 RGB frame of shape (h, w), stored compactly
+    (train_data.records.WINDOW_DTYPE is its numpy form)."""
+    _fields_ = [("data", ctypes.c_uint64), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("y0", ctypes.c_int32), ("x0", ctypes.c_int32),
+                ("wh", ctypes.c_int32), ("ww", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(FearFrameWindow) == 32
 
 
 class FearPairGeom(ctypes.Structure):

@@ -14,7 +14,7 @@ from .hls import hls_tables, iso_exp_table, rain_drop_count
 from .photometric import normal_quantiles, photo_tables, photometric_host, split_jpeg_records
 from .records import (COLOUR_MEMBERS, COLOUR_NONE, CONTEXT_SIZE, DEFAULT_TRAIN_DATA_CONFIG, DEVICE_COLOUR_KINDS, BLUR_GLASS, BLUR_NONE, FRAME_DTYPE,
                       GEOM_DTYPE, HLS_COPY, N_QUANTILES, NOISE_ISO, NOISE_JPEG, NOISE_MEMBERS, NOISE_NONE, PHOTO_DTYPE, SCORE_SIZE,
-                      SEARCH_SIZE, SHADOW_POLYGONS, SHADOW_VERTICES, TEMPLATE_SIZE, TONE_NONE, WEATHER_MEMBERS, WEATHER_NONE, PhotoParams,
+                      SEARCH_SIZE, SHADOW_POLYGONS, SHADOW_VERTICES, TEMPLATE_SIZE, TONE_NONE, WEATHER_MEMBERS, WEATHER_NONE, WINDOW_DTYPE, PhotoParams, WindowFrames,
                       TrainBatch, TrainPairParams, _pairs_array)
 from .staging import Staging
 from .warp import (_box_in_crop, _ensure, _extend, apply_to_bbox, crop_u8, encode_targets, invert_affine, jittered_crop, remap_affine_u8,
@@ -265,8 +265,35 @@ class TrainPairBuilder:
         rows[lo >= hi] = 0
         return rows
 
+    def frame_windows(self, pairs, params: TrainPairParams, frame_shapes: Sequence[Tuple[int, ...]]) -> np.ndarray:
+        """(F, 4) int64: per frame the rectangle [y0, y1) x [x0, x1), as (y0, y1, x0, x1), that a `build` of these pairs reads —
+        `frame_rows` with the columns added by the same tap rule (a crop samples the frame where 0 <= cx + x < fw for x in [0, cw), and
+        a box without width still clamps its taps to the columns cx - 1 and cx): the union, as one rectangle, over the pairs that use
+        the frame of their template context box and of their search context box, cut to the frame; (0, 0, 0, 0) for a frame no pair
+        uses or touches.  What `JpegStore.decode_windows` takes."""
+        tab = self.tables(pairs, params)
+        geom = tab["geom"]
+        F = len(frame_shapes)
+        sides = np.array([[int(s[0]), int(s[1])] for s in frame_shapes], dtype=np.int64).reshape(F, 2)
+        big = np.iinfo(np.int64)
+        lo, hi = np.full((F, 2), big.max), np.full((F, 2), big.min)              # [:, 0] rows, [:, 1] columns
+        for frame, ctx in ((geom["t_frame"], tab["t_ctx"]), (geom["s_frame"], tab["s_ctx"])):
+            frame = frame.astype(np.int64)
+            ok = (frame >= 0) & (frame < F)
+            for axis, (at, size) in enumerate(((1, 3), (0, 2))):                 # the box's y, h | x, w
+                c, n = ctx[:, at].astype(np.int64), ctx[:, size].astype(np.int64)
+                np.minimum.at(lo[:, axis], frame[ok], (c + np.minimum(n - 1, 0))[ok])
+                np.maximum.at(hi[:, axis], frame[ok], (c + np.maximum(n, 1))[ok])
+        lo, hi = np.clip(lo, 0, sides), np.clip(hi, 0, sides)
+        out = np.stack([lo[:, 0], hi[:, 0], lo[:, 1], hi[:, 1]], axis=1)
+        out[(lo >= hi).any(axis=1)] = 0
+        return out
+
     def _params(self, pairs, frames, params):
-        shapes = tuple((int(f.shape[0]), int(f.shape[1])) for f in frames)
+        if isinstance(frames, WindowFrames):
+            shapes = tuple((int(h), int(w)) for h, w in np.asarray(frames.shape).reshape(-1, 2).tolist())
+        else:
+            shapes = tuple((int(f.shape[0]), int(f.shape[1])) for f in frames)
         if params is None:
             return self.draw(pairs, shapes)
         if params.frame_shapes and tuple(params.frame_shapes) != shapes:
@@ -276,9 +303,24 @@ class TrainPairBuilder:
     # ------------------------------------------------------------------ host restatement
     def build_host(self, frames: Sequence, pairs, params: Optional[TrainPairParams] = None, borders=None) -> TrainBatch:
         """numpy restatement of `build` (same arithmetic, term for term): the reference `build` is tested against.  `borders`, (F, 3)
-        uint8, are used as the frames' border colours in place of their means (`build`'s `borders`)."""
-        host = [f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f) for f in frames]
-        params = self._params(pairs, host, params)
+        uint8, are used as the frames' border colours in place of their means (`build`'s `borders`).  A `WindowFrames` in place of the
+        frames needs them; each of its frames is then read as fear_train_pairs_windows reads it: pixel (y, x) inside the frame's shape
+        at the window's [y - oy, x - ox], both clamped to the window, and an empty window as a frame without pixels."""
+        if isinstance(frames, WindowFrames):
+            if borders is None:
+                raise ValueError("a WindowFrames needs borders: the mean over a window is not the frame's mean")
+            params = self._params(pairs, frames, params)
+            host = []
+            for f, (oy, ox), (H, W) in zip(frames.frames, np.asarray(frames.origin).tolist(), np.asarray(frames.shape).tolist()):
+                w = f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f)
+                if w.shape[0] < 1 or w.shape[1] < 1:
+                    host.append(np.zeros((0, 0, 3), dtype=np.uint8))
+                    continue
+                ys, xs = np.clip(np.arange(H) - oy, 0, w.shape[0] - 1), np.clip(np.arange(W) - ox, 0, w.shape[1] - 1)
+                host.append(w[ys[:, None], xs[None, :], :3])
+        else:
+            host = [f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f) for f in frames]
+            params = self._params(pairs, host, params)
         tab = self.tables(pairs, params)
         geom, lut = tab["geom"], tab["lut"]
         if borders is None:
@@ -341,8 +383,14 @@ class TrainPairBuilder:
         pinned memory; with device frames the call never waits for the GPU.
         `borders`, an (F, 3) uint8 device tensor or array, gives the frames' border colours (`JpegStore.borders`, computed once per
         file): the call then skips the `fear_frame_border_u8` launch, the only reader of every pixel of a frame, so that frames of
-        which only `frame_rows` is defined (`JpegStore.decode_rows`) give the same batch.  None keeps the launch."""
+        which only `frame_rows` is defined (`JpegStore.decode_rows`) give the same batch.  None keeps the launch.
+        `frames` may be a `WindowFrames` (`JpegStore.decode_windows` of `frame_windows`): compact tensors with their origins, read by
+        `fear_train_pairs_windows` — the same kernel body with another frame-fetch policy — and the same batch.  `borders` is then
+        required (ValueError otherwise: the mean over a window is not the frame's mean)."""
         lib, dev = load_train_library(), self.device
+        windowed = isinstance(frames, WindowFrames)
+        if windowed and borders is None:
+            raise ValueError("a WindowFrames needs borders: the mean over a window is not the frame's mean")
         params = self._params(pairs, frames, params)
         tab = self.tables(pairs, params)
         B, F = len(tab["geom"]), len(frames)
@@ -366,10 +414,18 @@ class TrainPairBuilder:
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
             st = ctypes.c_void_p(stream.cuda_stream)
-            dframes = [self._frame_on_device(f) for f in frames]
-            ftab = np.zeros(F, dtype=FRAME_DTYPE)
-            for i, f in enumerate(dframes):
-                ftab[i] = (f.data_ptr(), f.shape[0], f.shape[1])
+            if windowed:                       # fear_frame_window records: the frame's shape, the window's origin and shape
+                dframes = [self._frame_on_device(f) for f in frames.frames]
+                ftab = np.zeros(F, dtype=WINDOW_DTYPE)
+                ftab["data"] = [f.data_ptr() if f.numel() else 0 for f in dframes]
+                ftab["h"], ftab["w"] = np.asarray(frames.shape, dtype=np.int32).reshape(F, 2).T
+                ftab["y0"], ftab["x0"] = np.asarray(frames.origin, dtype=np.int32).reshape(F, 2).T
+                ftab["wh"], ftab["ww"] = [f.shape[0] for f in dframes], [f.shape[1] for f in dframes]
+            else:
+                dframes = [self._frame_on_device(f) for f in frames]
+                ftab = np.zeros(F, dtype=FRAME_DTYPE)
+                for i, f in enumerate(dframes):
+                    ftab[i] = (f.data_ptr(), f.shape[0], f.shape[1])
             stage = Staging()                  # every table of the call: one pinned buffer, one transfer
             stage.add("frames", ftab)
             stage.add("geom", tab["geom"])
@@ -413,9 +469,9 @@ class TrainPairBuilder:
             if borders is None:
                 launch(lib, "fear_frame_border_u8", stage.ptr("frames"), F, ptr(border), st)
             if not staged_u8:
-                pairs_fn, t_out, s_out = "fear_train_pairs", tmpl, srch
+                pairs_fn, t_out, s_out = "fear_train_pairs_windows" if windowed else "fear_train_pairs", tmpl, srch
             else:                              # the crops leave the table stage as uint8 HWC for the chain below
-                pairs_fn = "fear_train_pairs_u8"
+                pairs_fn = "fear_train_pairs_windows_u8" if windowed else "fear_train_pairs_u8"
                 t_out = torch.empty((B, TEMPLATE_SIZE, TEMPLATE_SIZE, 3), dtype=torch.uint8, device=dev)
                 s_out = torch.empty((B, SEARCH_SIZE, SEARCH_SIZE, 3), dtype=torch.uint8, device=dev)
             launch(lib, pairs_fn, stage.ptr("frames"), F, ptr(border), stage.ptr("geom"), stage.ptr("lut"), B, ptr(t_out), ptr(s_out),

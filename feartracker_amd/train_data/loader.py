@@ -1,5 +1,6 @@
 """From annotation tables to the step's tensors: `fill_store` puts a table's files into a `JpegStore`, `PairLoader` iterates over an
-epoch's batches — sample (sampling.py), clip, number the distinct files, `draw`, `frame_rows`, `decode_rows`, `build(borders=)` — and
+epoch's batches — sample (sampling.py), clip, number the distinct files, `draw`, `frame_rows`, `decode_rows`, `build(borders=)` (with
+`windows=True`: `frame_windows`, `decode_windows`, `build(WindowFrames, borders=)`, compact frames of the rectangles the pairs read) — and
 keeps the data stage of the next batch in flight on a stream of its own while the caller trains on the current one.
 
 Stream discipline.  With `prefetch=1` every launch and copy of a batch's data stage is enqueued on the loader's
@@ -71,16 +72,18 @@ class PairLoader:
     """An iterator over the batches of one epoch of `plan`; every `iter()` continues the epoch in progress or, when there is none,
     starts the next one (`EpochPlan.start_epoch`: a fresh permutation).  `row_ids[s][row]` is the store id of row `row` of sampler
     s's table (what `fill_store` returns).  `scale` 2, 4 or 8 decodes the frames at that fraction and divides the boxes
-    (`scale_pairs`); `rows=False` decodes whole frames.  The loader never waits for the GPU and never reads from it; call
+    (`scale_pairs`); `rows=False` decodes whole frames; `windows=True` decodes per frame the rectangle the batch reads, as compact
+    tensors (`JpegStore.decode_windows`), and hands out the same batches.  The loader never waits for the GPU and never reads from it; call
     `store.check()` at the end of an epoch to see the decode statuses.  `datasets` are the tables' dataset names, sorted."""
 
-    def __init__(self, plan: EpochPlan, store, row_ids: Sequence[np.ndarray], builder, scale: int = 1, rows: bool = True, prefetch: int = 1):
+    def __init__(self, plan: EpochPlan, store, row_ids: Sequence[np.ndarray], builder, scale: int = 1, rows: bool = True, prefetch: int = 1,
+                 windows: bool = False):
         if prefetch not in (0, 1):
             raise ValueError("prefetch is 0 or 1")
         if len(row_ids) != len(plan.samplers):
             raise ValueError(f"row_ids has {len(row_ids)} entries, the plan {len(plan.samplers)} samplers")
         self.plan, self.store, self.builder = plan, store, builder
-        self.scale, self.rows, self.prefetch = int(scale), bool(rows), int(prefetch)
+        self.scale, self.rows, self.prefetch, self.windows = int(scale), bool(rows), int(prefetch), bool(windows)
         self.row_ids = [np.asarray(r, dtype=np.int64) for r in row_ids]
         for s, r in zip(plan.samplers, self.row_ids):
             if r.shape != (len(s.table),):
@@ -131,7 +134,9 @@ class PairLoader:
         store, builder = self.store, self.builder
         shapes = store.shape(ids, self.scale)
         params = builder.draw(pairs, shapes)
-        if self.rows:
+        if self.windows:
+            frames = store.decode_windows(ids, builder.frame_windows(pairs, params, shapes), scale=self.scale)
+        elif self.rows:
             frames = store.decode_rows(ids, builder.frame_rows(pairs, params, shapes), scale=self.scale)
         else:
             frames = store.decode(ids, scale=self.scale)

@@ -4,12 +4,12 @@ from __future__ import annotations
 
 from collections import namedtuple
 from dataclasses import dataclass
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
-from ..train_abi import FearColourOp, FearFrame, FearHlsOp, FearPairGeom, FearPhotoOp
+from ..train_abi import FearColourOp, FearFrame, FearFrameWindow, FearHlsOp, FearPairGeom, FearPhotoOp
 
 TEMPLATE_SIZE, CONTEXT_SIZE, SEARCH_SIZE, SCORE_SIZE, TOTAL_STRIDE = 128, 512, 256, 16, 16
 
@@ -76,7 +76,7 @@ TrainBatch = namedtuple("TrainBatch", ["template", "search", "gt_reg", "gt_cls",
 
 
 # the numpy forms of the device's records, derived from the ctypes mirrors of include/fear_train.h
-GEOM_DTYPE, FRAME_DTYPE = np.dtype(FearPairGeom), np.dtype(FearFrame)
+GEOM_DTYPE, FRAME_DTYPE, WINDOW_DTYPE = np.dtype(FearPairGeom), np.dtype(FearFrame), np.dtype(FearFrameWindow)
 PHOTO_DTYPE, COLOUR_DTYPE, HLS_DTYPE = np.dtype(FearPhotoOp), np.dtype(FearColourOp), np.dtype(FearHlsOp)
 
 
@@ -152,4 +152,22 @@ def scale_pairs(pairs, scale: int) -> np.ndarray:
     return p
 
 
-__all__ = [name for name in dir() if name.isupper()] + ["PhotoParams", "TrainPairParams", "TrainBatch", "scale_pairs"]     # (every constant above)
+@dataclass
+class WindowFrames:
+    """What `JpegStore.decode_windows` returns: per position a compact tensor that holds a rectangle of the frame.
+    `frames[i][y - origin[i, 0], x - origin[i, 1]]` is pixel (y, x) of frame i for every (y, x) of `window[i]`; the rest of a tensor (the
+    halo rows and columns, the MCUs' remainder) holds unspecified bytes."""
+    frames: List                     # uint8 (wh, ww, 3) device tensors, private; (0, 0, 3) for the empty window
+    origin: np.ndarray               # (n, 2) int32: the frame coordinates (y, x) of each tensor's first pixel
+    shape: np.ndarray                # (n, 2) int32: the shape of the frames `decode(ids, scale=scale)` returns
+    window: np.ndarray               # (n, 4) int64: the clipped request [y0, y1) x [x0, x1), zeros for the empty window
+
+    def __len__(self) -> int:
+        return len(self.frames)
+
+    @property
+    def nbytes(self) -> int:
+        return int(sum(3 * f.shape[0] * f.shape[1] for f in self.frames))
+
+
+__all__ = [name for name in dir() if name.isupper()] + ["PhotoParams", "TrainPairParams", "TrainBatch", "WindowFrames", "scale_pairs"]     # (every constant above)

@@ -502,6 +502,30 @@ int fear_train_pairs(const fear_frame* frames, int n_frames, const uint8_t* bord
 int fear_train_pairs_u8(const fear_frame* frames, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom, const uint8_t* lut,
                         int n, uint8_t* template_u8, uint8_t* search_u8, float* gt_reg, float* gt_cls, float* gt_weight, void* stream);
 
+/* fear_train_pairs and fear_train_pairs_u8 for frames of which only a rectangle is stored (JpegStore.decode_windows): the same kernel
+ * body with another frame-fetch policy.  `h`, `w` stay the FRAME's shape, so the inside / outside-the-frame test and the border colour
+ * are unchanged; a pixel (x, y) inside the frame is read at data[((y - y0) ww + (x - x0)) 3], with y - y0 clamped to [0, wh) and
+ * x - x0 to [0, ww): a window that does not cover what the pairs read gives wrong pixels, never a read outside its wh ww 3 bytes.  A
+ * window without pixels (null data, wh or ww < 1) reads as the border colour.  The checks are fear_train_pairs'.
+ *   windows : (n_frames) fear_frame_window, device                                                                                  */
+typedef struct fear_frame_window {
+    const uint8_t* data;        /* device: contiguous (wh, ww, 3) uint8, the frame's pixels [y0, y0 + wh) x [x0, x0 + ww)            */
+    int32_t h, w;               /* the frame's shape                                                                                */
+    int32_t y0, x0;             /* the frame coordinates of the window's first pixel                                                */
+    int32_t wh, ww;             /* the window's shape                                                                               */
+} fear_frame_window;
+#ifdef __cplusplus
+static_assert(sizeof(fear_frame_window) == 32, "fear_frame_window is 32 bytes");
+#else
+_Static_assert(sizeof(fear_frame_window) == 32, "fear_frame_window is 32 bytes");
+#endif
+int fear_train_pairs_windows(const fear_frame_window* windows, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom,
+                             const uint8_t* lut, int n, float* template_out, float* search_out, float* gt_reg, float* gt_cls,
+                             float* gt_weight, void* stream);
+int fear_train_pairs_windows_u8(const fear_frame_window* windows, int n_frames, const uint8_t* border_rgb, const FearPairGeom* geom,
+                                const uint8_t* lut, int n, uint8_t* template_u8, uint8_t* search_u8, float* gt_reg, float* gt_cls,
+                                float* gt_weight, void* stream);
+
 /* ---- the photometric stage: PHOTOMETRIC_AUGMENTATIONS of the reference (model_training/dataset/aug.py:8-25) on each crop on its
  * own, between the colour stage and the normalisation.  Per crop, in this order:
  *   blur       1 Blur          (sum of the k x k window + k k / 2) / (k k) in integers, BORDER_REFLECT_101
@@ -887,7 +911,24 @@ int fear_jpeg_dense_block_start(uint32_t* block_start, uint32_t total_blocks, vo
  * is decoded, judged and not stored.  Every stored position is written by exactly one lane, nothing is written outside the image's
  * 64 total_blocks values, all other positions keep what the buffer held, and every loop bound is independent of the data.  The checks
  * are fear_jpeg_huffman_indexed's; a null rows_dev, or a null row_sub in a record, is FEAR_TRAIN_ERR_NULL, a row_sub not 4-byte
- * aligned FEAR_TRAIN_ERR_SHAPE.                                                                                                      */
+ * aligned FEAR_TRAIN_ERR_SHAPE.
+ *
+ * fear_jpeg_huffman_indexed_windows is fear_jpeg_huffman_indexed_rows for a range of MCU columns as well (JpegStore.decode_windows;
+ * jpeg_huffman.jpeg_entropy_indexed_host with a band and `cols` restates it).  The record is fear_jpeg_huffman_indexed_rows' — the band
+ * mcu_row0, mcu_rows and the lanes sub0, sub_count from the row table — and its `reserved` word holds the columns as two 16-bit halves:
+ * mcu_col0 in the low half, mcu_cols in the high one (mcus_x <= 1024), the range [mcu_col0, mcu_col0 + mcu_cols) clipped to mcus_x.
+ * A lane of the band runs only if it can touch the window.  It loads its own entry and the next subsequence's, or takes the segment's
+ * block count where the next subsequence lies in another segment; the blocks it stores have the segment ordinals lo .. hi),
+ * lo = begun - (1 if a block is open at its entry), hi = min(the next begun, the segment's count); they lie in the consecutive MCUs
+ * first_mcu + lo / slots .. first_mcu + (hi - 1) / slots, and the lane runs if one of those has its column in the range — all of a
+ * row's columns if they are mcus_x or more, else the interval of columns from the first MCU's, the part that wraps over the row's end
+ * tested on its own.  No loop, no bound that depends on the data; the rule may run a lane that stores nothing (its MCUs of the range lie
+ * outside the band), never the reverse.  Lanes that do not run judge nothing, as in the rows form.  A lane that runs decodes and judges
+ * exactly as fear_jpeg_huffman_indexed_rows' and stores a block only when its MCU row is in the band and its MCU column in the range,
+ * WINDOW-DENSE: the component-major, row-major layout of an image made of those mcu_rows x mcu_cols MCUs alone,
+ * 64 (mcu_rows mcu_cols blocks-per-MCU) values from coef_offset, every position written by exactly one lane, nothing outside them.
+ * The checks are fear_jpeg_huffman_indexed_rows'; mcu_cols == 0, or mcu_col0 + mcu_cols > FEAR_JPEG_MAX_SIDE / 8, is
+ * FEAR_TRAIN_ERR_SHAPE.  Two launches, no atomics, one barrier, plain vector stores.                                                  */
 typedef struct FearJpegSubseq {
     uint32_t p;                  /* the true entry bit position in the segment, up to 30 bits behind the subsequence's first: < 2^27 + 31 */
     uint32_t begun;              /* blocks begun in the segment in front of the subsequence                              */
@@ -913,7 +954,7 @@ typedef struct FearJpegIndexed {
     uint32_t n_sub;
     uint32_t sub0, sub_count;        /* fear_jpeg_huffman_indexed_rows alone: the subsequences that get a lane, sub0 .. sub0 + sub_count) */
     uint32_t mcu_row0, mcu_rows;     /* fear_jpeg_huffman_indexed_rows alone: the band of MCU rows whose blocks are stored             */
-    uint32_t reserved;
+    uint32_t reserved;               /* fear_jpeg_huffman_indexed_windows alone: mcu_col0 | mcu_cols << 16, the MCU columns whose blocks are stored */
     const uint32_t* row_sub;         /* fear_jpeg_huffman_indexed_rows_dev alone: device, the file's row table, mcus_y + 1 values; offset 56 */
 } FearJpegIndexed;
 #ifdef __cplusplus
@@ -936,6 +977,8 @@ int fear_jpeg_huffman_indexed_rows(const FearJpegIndexed* images, int n, const v
                                    int subsequence_bytes, void* stream);
 int fear_jpeg_huffman_indexed_rows_dev(const FearJpegIndexed* images, int n, const void* table_dev, const int32_t* rows_dev, int16_t* coef,
                                        int32_t* status_dev, int subsequence_bytes, void* stream);
+int fear_jpeg_huffman_indexed_windows(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
+                                      int subsequence_bytes, void* stream);
 
 /* ---- the colour stage's members that are no lookup table: Equalize, HueSaturationValue, ColorJitter and Emboss of the reference's
  * p = 0.5 OneOf (model_training/dataset/aug.py:35-48), on uint8 HWC crops between fear_train_pairs_u8 (tone, then the lookup-table
