@@ -14,7 +14,8 @@
 // for the pixel rows [y0, y1) of each image, read from device memory (jr_band; DESIGN.md section 14, "Rows from the device").
 // The pieces every pixel kernel is made of are written once, here, and fear_jpeg_scaled.h uses them too: the block load (jd_load_block),
 // the block's home (jd_home), the sample pack (js_sample, jd_pack4), the upsampling filters (jd_taps, jd_h2v1, jd_h2v2), the colour conversion and
-// store (jd_store_rgb), and on the host the one check of records and workspace (jd_check).
+// store (jd_store_rgb), the full-size pixel stage of a workgroup that knows its image (jd_merge_image), and on the host the one check of
+// records and workspace (jd_check).
 // Included by fear_train.hip behind fear_train_jpeg.h, whose transforms and LDS pitch it uses.
 
 namespace {
@@ -24,8 +25,14 @@ struct JpegDecodeArgs {
     uint8_t* planes;         // the workspace, 16-byte aligned
     int n;
     int m;                   // the side of a block in frame pixels: 8, and 8 / scale = 4, 2 or 1 in fear_jpeg_scaled.h, whose second
-                             // prefix table counts scaled pixels
+                             // prefix table counts scaled pixels; 0 in fear_jpeg_decode_mixed_u8: every record carries its own
 };
+
+// The m of a record of fear_jpeg_decode_mixed_u8, from the scale in its reserved[0]: 0 and 1 are full size, and so is, on the device,
+// whatever the host's check would have refused (jd_scale_ok) — the side is one of 8, 4, 2, 1 whatever the word holds.
+__host__ __device__ __forceinline__ int jd_record_m(int scale) {
+    return scale == 2 ? 4 : (scale == 4 ? 2 : (scale == 8 ? 1 : 8));
+}
 
 // The image a workgroup belongs to: the i in [0, n) with start[i] <= group < start[i + 1].  n <= 65535: at most 16 halvings.
 __device__ __forceinline__ int jd_find_image(const uint32_t* start, int n, uint32_t group) {
@@ -207,13 +214,12 @@ __global__ __launch_bounds__(256) void jpeg_decode_blocks_rows_dev_kernel(JpegDe
 // The pixel stage at full size, one pixel per lane.  ROWS: of the rows [y0, y1) of `rows_dev` alone.  Their luma lies in the band's MCU
 // rows without the halo and every chroma row they read — one above and below with v == 2 — in the band with it, or the row is clamped at
 // a true edge of the image: no plane byte is read that jd_blocks<true> has not written in the same call.
+// jd_merge_image is the stage for a workgroup that knows its image (`img`, record `im`, `first` its first workgroup); jd_merge finds it.
 template <bool ROWS>
-__device__ __forceinline__ void jd_merge(const JpegDecodeArgs& a, const int32_t* rows_dev) {
-    const uint32_t* start = a.table + (a.n + 1);
-    const int img = jd_find_image(start, a.n, blockIdx.x);
-    const FearJpegImage* im = jd_records(a) + img;
+__device__ __forceinline__ void jd_merge_image(const JpegDecodeArgs& a, const int32_t* rows_dev, const FearJpegImage* im, int img,
+                                               uint32_t first) {
     const int W = im->width, H = im->height, h = im->h, v = im->v;
-    const long px = (long)(blockIdx.x - start[img]) * FEAR_JPEG_GROUP_PIXELS + threadIdx.x;
+    const long px = (long)(blockIdx.x - first) * FEAR_JPEG_GROUP_PIXELS + threadIdx.x;
     if (px >= (long)H * W) return;
     const int y = (int)(px / W), x = (int)(px - (long)y * W);
     if (ROWS && (y < min(max(rows_dev[2 * img], 0), H) || y >= min(max(rows_dev[2 * img + 1], 0), H))) return;   // the clip to [0, H]
@@ -243,6 +249,13 @@ __device__ __forceinline__ void jd_merge(const JpegDecodeArgs& a, const int32_t*
     jd_store_rgb(Y, cb, cr, im->out + px * 3);
 }
 
+template <bool ROWS>
+__device__ __forceinline__ void jd_merge(const JpegDecodeArgs& a, const int32_t* rows_dev) {
+    const uint32_t* start = a.table + (a.n + 1);
+    const int img = jd_find_image(start, a.n, blockIdx.x);
+    jd_merge_image<ROWS>(a, rows_dev, jd_records(a) + img, img, start[img]);
+}
+
 __global__ __launch_bounds__(256) void jpeg_decode_merge_kernel(JpegDecodeArgs a) { jd_merge<false>(a, nullptr); }
 
 __global__ __launch_bounds__(256) void jpeg_decode_merge_rows_dev_kernel(JpegDecodeArgs a, const int32_t* rows_dev) {
@@ -260,7 +273,12 @@ struct JdLaunch {
     unsigned block_groups, pixel_groups;
 };
 
-// The one check of the records and the workspace, for frames of m / 8 of the images' sizes (m = 8: full size), in the order the ABI
+bool jd_scale_ok(int scale) {
+    return scale == 0 || scale == 1 || scale == 2 || scale == 4 || scale == 8;
+}
+
+// The one check of the records and the workspace, for frames of m / 8 of the images' sizes (m = 8: full size; m = 0: each record's own,
+// jd_record_m of its reserved[0], which is then part of the record's shape), in the order the ABI
 // states: n, the null pointers of the call (`missing`: one the entry point has tested itself), each record's, each record's shape, the
 // workspace, the grids.  fear_jpeg_decode_workspace_bytes' bound holds at every m: the scaled planes are no larger.
 int jd_check(const FearJpegImage* images, int n, const uint32_t* group_start, bool missing, int m, void* workspace, size_t workspace_bytes,
@@ -274,7 +292,7 @@ int jd_check(const FearJpegImage* images, int n, const uint32_t* group_start, bo
         const FearJpegImage& im = images[i];
         if (!im.coef || !im.block_start || !im.out) return FEAR_TRAIN_ERR_NULL;
         if (im.width < 1 || im.width > FEAR_JPEG_MAX_SIDE || im.height < 1 || im.height > FEAR_JPEG_MAX_SIDE ||
-            !jd_mode_ok(im.components, im.h, im.v) || (im.plane_offset & 15) != 0)
+            !jd_mode_ok(im.components, im.h, im.v) || (im.plane_offset & 15) != 0 || (m == 0 && !jd_scale_ok(im.reserved[0])))
             return FEAR_TRAIN_ERR_SHAPE;
     }
     if (!workspace) return FEAR_TRAIN_ERR_WORKSPACE;
@@ -284,7 +302,8 @@ int jd_check(const FearJpegImage* images, int n, const uint32_t* group_start, bo
         const uint64_t blocks = (uint64_t)(g.n0 + 2 * g.nc);
         if (workspace_bytes < 16 || im.plane_offset > workspace_bytes - 16 || blocks * 64 > workspace_bytes - 16 - im.plane_offset)
             return FEAR_TRAIN_ERR_WORKSPACE;
-        const uint64_t sw = ((uint64_t)im.width * m + 7) / 8, sh = ((uint64_t)im.height * m + 7) / 8;
+        const uint64_t mi = (uint64_t)(m ? m : jd_record_m(im.reserved[0]));
+        const uint64_t sw = ((uint64_t)im.width * mi + 7) / 8, sh = ((uint64_t)im.height * mi + 7) / 8;
         block_groups += (blocks + FEAR_JPEG_GROUP_BLOCKS - 1) / FEAR_JPEG_GROUP_BLOCKS;
         pixel_groups += (sw * sh + FEAR_JPEG_GROUP_PIXELS - 1) / FEAR_JPEG_GROUP_PIXELS;
     }

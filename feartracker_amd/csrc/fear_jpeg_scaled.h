@@ -14,6 +14,9 @@
 //   jpeg_scaled_merge_kernel   one SCALED pixel per lane (the second prefix table counts scaled pixels): h2v1 upsampling of 4:2:2 at the
 //                              true edge of the scaled chroma plane — fancy when m > 1 and that plane is wider than 2, replication
 //                              otherwise: libjpeg turns fancy upsampling off at 1/8 — YCbCr -> RGB, store
+//   jpeg_mixed_blocks_kernel, jpeg_mixed_merge_kernel   fear_jpeg_decode_mixed_u8: the same block stage (js_blocks) and, by the image's
+//                              own m, this pixel stage (js_merge_image) or the full-size one (jd_merge_image); m from the record's
+//                              reserved[0], the second prefix table counting each image's own scaled pixels
 // Integer width: libjpeg computes these transforms in `long`; the device computes in 32 bits, as the islow pair of fear_train_jpeg.h
 // does.  The two agree while the dequantised coefficients stay within +-2^13 (an 8-bit sample's DCT cannot leave +-2^13; the largest
 // term is dc << 14 twice over, 2^13 2^2 2^14 = 2^29), which every file an encoder writes does.
@@ -57,16 +60,21 @@ __device__ __forceinline__ void js_idct2(int* d) {
     d[1] = jp_descale<N>(t10 - t0);
 }
 
-__global__ __launch_bounds__(256) void jpeg_scaled_blocks_kernel(JpegDecodeArgs a) {
+// The block stage at m / 8 of the size: a workgroup finds its image and takes `m` from the kernel's argument (0: from the image's record,
+// fear_jpeg_decode_mixed_u8).  m is the same for the whole workgroup, which belongs to one image; ss, the transform's side, is the same
+// for the eight lanes of a block.  At m == 8 js_transform gives ss == 8 for every component (its loop needs ss < 8), the planes are 64
+// bytes per block with the chroma at n0 64 and (n0 + nc) 64, and the block's home is jd_blocks': the layout jd_merge_image reads.
+__device__ __forceinline__ void js_blocks(const JpegDecodeArgs& a) {
     __shared__ __attribute__((aligned(16))) int blk[FEAR_JPEG_GROUP_BLOCKS * kJpPitch];
     const int tid = threadIdx.x, lb = tid >> 3, k = tid & 7;
     const int img = jd_find_image(a.table, a.n, blockIdx.x);
     const FearJpegImage* im = jd_records(a) + img;
+    const int m = a.m ? a.m : jd_record_m(im->reserved[0]);
     const JdGeom g = jd_geom(im->width, im->height, im->components, im->h, im->v);
     const long b = (long)(blockIdx.x - a.table[img]) * FEAR_JPEG_GROUP_BLOCKS + lb;
     const bool on = b < g.n0 + 2 * g.nc;
     const int comp = jd_comp(g, b);
-    const int ss0 = js_transform(a.m, im->h, im->v, im->h, im->v), ssc = js_transform(a.m, im->h, im->v, 1, 1);
+    const int ss0 = js_transform(m, im->h, im->v, im->h, im->v), ssc = js_transform(m, im->h, im->v, 1, 1);
     const int ss = comp == 0 ? ss0 : ssc;                      // 1, 2, 4 or 8; the same for the eight lanes of a block
     int* base = blk + lb * kJpPitch;
     jd_load_block(base, k, on, im, b, comp);
@@ -106,13 +114,14 @@ __global__ __launch_bounds__(256) void jpeg_scaled_blocks_kernel(JpegDecodeArgs 
     }
 }
 
-__global__ __launch_bounds__(256) void jpeg_scaled_merge_kernel(JpegDecodeArgs a) {
-    const uint32_t* start = a.table + (a.n + 1);
-    const int img = jd_find_image(start, a.n, blockIdx.x);
-    const FearJpegImage* im = jd_records(a) + img;
-    const int m = a.m, h = im->h, v = im->v;
+__global__ __launch_bounds__(256) void jpeg_scaled_blocks_kernel(JpegDecodeArgs a) { js_blocks(a); }
+
+// The pixel stage at m / 8 of the size, m < 8, for a workgroup that knows its image (`first`: its first workgroup): one scaled pixel
+// per lane.
+__device__ __forceinline__ void js_merge_image(const JpegDecodeArgs& a, const FearJpegImage* im, int m, uint32_t first) {
+    const int h = im->h, v = im->v;
     const int W = (im->width * m + 7) >> 3, H = (im->height * m + 7) >> 3;      // the scaled frame
-    const long px = (long)(blockIdx.x - start[img]) * FEAR_JPEG_GROUP_PIXELS + threadIdx.x;
+    const long px = (long)(blockIdx.x - first) * FEAR_JPEG_GROUP_PIXELS + threadIdx.x;
     if (px >= (long)H * W) return;
     const int y = (int)(px / W), x = (int)(px - (long)y * W);
     const JdGeom g = jd_geom(im->width, im->height, im->components, h, v);
@@ -139,6 +148,26 @@ __global__ __launch_bounds__(256) void jpeg_scaled_merge_kernel(JpegDecodeArgs a
     jd_store_rgb(Y, cb, cr, im->out + px * 3);
 }
 
+__global__ __launch_bounds__(256) void jpeg_scaled_merge_kernel(JpegDecodeArgs a) {
+    const uint32_t* start = a.table + (a.n + 1);
+    const int img = jd_find_image(start, a.n, blockIdx.x);
+    js_merge_image(a, jd_records(a) + img, a.m, start[img]);
+}
+
+// fear_jpeg_decode_mixed_u8: the same two stages with each image's m from its record (a.m == 0).  A workgroup belongs to one image, so
+// m is workgroup-uniform: one scalar load and one uniform branch, in front of the per-lane work, choose between the full-size pixel
+// stage (jd_merge_image: h2v2 and h2v1 at the true chroma edges, replication for cw <= 2) and the scaled one.
+__global__ __launch_bounds__(256) void jpeg_mixed_blocks_kernel(JpegDecodeArgs a) { js_blocks(a); }
+
+__global__ __launch_bounds__(256) void jpeg_mixed_merge_kernel(JpegDecodeArgs a) {
+    const uint32_t* start = a.table + (a.n + 1);
+    const int img = jd_find_image(start, a.n, blockIdx.x);
+    const FearJpegImage* im = jd_records(a) + img;
+    const int m = jd_record_m(im->reserved[0]);
+    if (m == 8) jd_merge_image<false>(a, nullptr, im, img, start[img]);
+    else js_merge_image(a, im, m, start[img]);
+}
+
 }  // namespace
 
 extern "C" {
@@ -152,6 +181,18 @@ int fear_jpeg_decode_scaled_u8(const FearJpegImage* images, int n, const uint32_
     hipLaunchKernelGGL(jpeg_scaled_blocks_kernel, dim3(l.block_groups), dim3(256), 0, static_cast<hipStream_t>(stream), l.a);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(jpeg_scaled_merge_kernel, dim3(l.pixel_groups), dim3(256), 0, static_cast<hipStream_t>(stream), l.a);
+    LAUNCH_CHECK();
+    return FEAR_TRAIN_OK;
+}
+
+int fear_jpeg_decode_mixed_u8(const FearJpegImage* images, int n, const uint32_t* group_start, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    JdLaunch l;
+    const int status = jd_check(images, n, group_start, false, 0, workspace, workspace_bytes, &l);
+    if (status != FEAR_TRAIN_OK || l.block_groups == 0) return status;
+    hipLaunchKernelGGL(jpeg_mixed_blocks_kernel, dim3(l.block_groups), dim3(256), 0, static_cast<hipStream_t>(stream), l.a);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(jpeg_mixed_merge_kernel, dim3(l.pixel_groups), dim3(256), 0, static_cast<hipStream_t>(stream), l.a);
     LAUNCH_CHECK();
     return FEAR_TRAIN_OK;
 }

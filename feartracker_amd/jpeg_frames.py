@@ -323,6 +323,26 @@ def _check_scale(scale) -> int:
     return int(scale)
 
 
+def _check_scales(scale, n: int):
+    """`scale` of a `JpegStore` call over `n` positions: an int of SCALES as it is (the uniform code path), or a sequence or array of
+    `n` of them, returned as an (n,) int64 array.  A wrong length, another value, a bool or a non-integer is a ValueError."""
+    if isinstance(scale, (int, np.integer)) and not isinstance(scale, (bool, np.bool_)):
+        return _check_scale(scale)
+    if isinstance(scale, (str, bytes, bool, np.bool_)) or scale is None or np.ndim(scale) != 1:
+        raise ValueError(f"scale is one of {SCALES} or a sequence of them, one per id, not {scale!r}")
+    if any(isinstance(s, (bool, np.bool_)) for s in scale):
+        raise ValueError(f"scale is one of {SCALES} per id, not a bool")
+    arr = np.asarray(scale)
+    if arr.size and not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"scale is one of {SCALES} per id, not {arr.dtype} values")
+    if arr.size != n:
+        raise ValueError(f"scale has {arr.size} values for {n} ids")
+    arr = arr.astype(np.int64).reshape(-1)
+    if not np.isin(arr, SCALES).all():
+        raise ValueError(f"scale is one of {SCALES} per id, not {int(arr[~np.isin(arr, SCALES)][0])}")
+    return arr
+
+
 def jpeg_scaled_shape(height: int, width: int, scale: int) -> Tuple[int, int, int]:
     """The shape of a frame of `height` x `width` decoded at 1 / `scale`: (ceil(H m / 8), ceil(W m / 8), 3) with m = 8 // scale."""
     m = 8 // _check_scale(scale)
@@ -509,11 +529,17 @@ def _fill_header(rec, info) -> None:
     ctypes.memmove(rec.qt, info.qt, ctypes.sizeof(rec.qt))
 
 
-def _launch_pixels(lib, records, n: int, table: int, workspace: int, workspace_bytes: int, scale: int, stream) -> None:
+def _launch_pixels(lib, records, n: int, table: int, workspace: int, workspace_bytes: int, scale, stream) -> None:
     """The pixel stage over `n` FearJpegImage records whose prefix tables are at the device address `table`: fear_jpeg_decode_u8, at a
-    scale fear_jpeg_decode_scaled_u8."""
+    scale fear_jpeg_decode_scaled_u8.  `scale` may be an array of `n` scales, one per record: where they are all equal the launch is the
+    uniform one at that scale, else fear_jpeg_decode_mixed_u8, whose records carry the scales in reserved[0] (the caller wrote them)."""
     from .train_abi import launch
     table, workspace = ctypes.c_void_p(table), ctypes.c_void_p(workspace)
+    if not isinstance(scale, (int, np.integer)):
+        if scale.size and (scale != scale[0]).any():
+            launch(lib, "fear_jpeg_decode_mixed_u8", records, n, table, workspace, workspace_bytes, stream)
+            return
+        scale = int(scale[0]) if scale.size else 1
     if scale == 1:
         launch(lib, "fear_jpeg_decode_u8", records, n, table, workspace, workspace_bytes, stream)
     else:

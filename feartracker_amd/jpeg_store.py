@@ -20,7 +20,10 @@ from the device").  `StoreFrames(store, ids)` names a sequence of frames kept in
 
 `decode`, `decode_rows` (rows on the host), `shape` and the two plans take `scale` 2, 4 or 8: the frames at 1/2, 1/4 or 1/8 size, decoded
 in the DCT domain as libjpeg's scale_denom does, with `fear_jpeg_decode_scaled_u8` in place of `fear_jpeg_decode_u8` behind the same
-Huffman stage ("Reduced-size decoding").
+Huffman stage ("Reduced-size decoding").  `scale` may also be a sequence, one scale of {1, 2, 4, 8} per
+position of the call: item i is then what the uniform call at its scale returns, a group whose scales differ runs
+`fear_jpeg_decode_mixed_u8` — two pixel launches whatever the mix, each record's scale in its `reserved[0]` — and `decode_windows`
+takes it too ("A scale per position").
 
 A batch of training pairs reads a rectangle of a frame, not its whole rows.  `JpegStore.decode_windows` decodes per frame the MCUs that
 cover one rectangle — `plan_decode_windows` on the host, `fear_jpeg_huffman_indexed_windows`, whose lanes of the band that cannot touch
@@ -34,7 +37,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import jpeg_frames
-from .jpeg_frames import (ERR_UNSUPPORTED, Item, JpegDecoder, MalformedJPEG, UnsupportedJPEG, _check_scale, _fill_header, _judge,
+from .jpeg_frames import (ERR_UNSUPPORTED, Item, JpegDecoder, MalformedJPEG, UnsupportedJPEG, _check_scales, _fill_header, _judge,
                           _launch_pixels, _raise_as_python, _read_items)
 from .jpeg_huffman import SUBSEQ_DTYPE, _check_subsequence_bytes, scan_row_sub
 from .train_data.records import WindowFrames  # noqa: F401  (what decode_windows returns; the builder takes it)
@@ -62,7 +65,7 @@ def _exclusive(a):
     return out
 
 
-def plan_decode(columns: np.ndarray, ids, workspace_limit: int, max_group: int = 65535, scale: int = 1) -> List[dict]:
+def plan_decode(columns: np.ndarray, ids, workspace_limit: int, max_group: int = 65535, scale=1) -> List[dict]:
     """The host's share of `JpegStore.decode` but the records: a pure function of the mirror's integer columns (COLUMNS, one row per
     entry) and the ids, any order, repeats allowed.  The call is cut into groups of consecutive positions lo..hi as JpegDecoder cuts it:
     a group takes positions while the dense coefficients of its "scan" entries (128 bytes per block) stay within `workspace_limit`, at
@@ -75,8 +78,12 @@ def plan_decode(columns: np.ndarray, ids, workspace_limit: int, max_group: int =
     and over all its positions `out_offset`, multiples of 16, and `out_bytes`.  No loop over the files: gathers and prefix sums.
     At `scale` 2, 4 or 8 the frames are the scaled ones (`jpeg_scaled_shape`): `pixel_prefix` counts scaled pixels, as
     fear_jpeg_decode_scaled_u8 reads it, and `out_offset` and `out_bytes` lay out scaled frames; the blocks, the coefficients and the
-    workspace are what they are at scale 1."""
+    workspace are what they are at scale 1.
+    `scale` may also be a sequence of len(ids) scales from {1, 2, 4, 8}, one per position (the same id may come at several): every
+    per-position entry is then the uniform plan's at that position's scale, the groups are cut as ever, and a group carries `scales`,
+    its "scan" positions' scales, for the records' reserved[0] and the choice of the launch (`_launch_pixels`)."""
     ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    scale = _check_scales(scale, ids.size)
     rows = columns[ids]
     is_scan = rows["kind"] == KIND_SCAN
     blocks = rows["total_blocks"].astype(np.int64)
@@ -87,13 +94,19 @@ def plan_decode(columns: np.ndarray, ids, workspace_limit: int, max_group: int =
         scan = np.flatnonzero(is_scan[lo:hi])
         pick = lo + scan
         groups.append(dict(lo=lo, hi=hi, scan=scan, sub_prefix=_exclusive(-(-n_sub[pick] // LANES)).astype(np.uint32),
-                           **_layout(blocks[pick], pixels[pick], pixels[lo:hi])))
+                           **_layout(blocks[pick], pixels[pick], pixels[lo:hi]), **_group_scales(scale, pick)))
     return groups
 
 
-def _scaled_sides(H, W, scale: int):
-    """`jpeg_frames.jpeg_scaled_shape` over arrays of heights and widths: int64 ceil(H m / 8) and ceil(W m / 8), m = 8 // scale."""
-    m = 8 // _check_scale(scale)
+def _group_scales(scale, pick: np.ndarray) -> dict:
+    """What a group of a plan with a scale per position carries more: `scales`, those of its "scan" positions.  Nothing for an int."""
+    return {} if isinstance(scale, int) else dict(scales=scale[pick])
+
+
+def _scaled_sides(H, W, scale):
+    """`jpeg_frames.jpeg_scaled_shape` over arrays of heights and widths: int64 ceil(H m / 8) and ceil(W m / 8), m = 8 // scale; `scale`
+    an int or one per height."""
+    m = 8 // _check_scales(scale, np.size(H))
     return -(-np.asarray(H, dtype=np.int64) * m // 8), -(-np.asarray(W, dtype=np.int64) * m // 8)
 
 
@@ -128,7 +141,7 @@ def scan_columns(col, info, n_seg: int, n_sub: int, row_at: int) -> None:
 
 
 def plan_decode_rows(columns: np.ndarray, row_sub: np.ndarray, ids, rows, workspace_limit: int, max_group: int = 65535,
-                     scale: int = 1) -> List[dict]:
+                     scale=1) -> List[dict]:
     """The host's share of `JpegStore.decode_rows`, as `plan_decode` a pure function without a loop over the files: of the mirror's
     columns, the ragged row table (`columns["row_at"]` is where an entry's mcus_y + 1 values begin in `row_sub`), the ids and `rows`,
     (n, 2) pixel rows [y0, y1) per position, clipped to [0, H].  The band of a "scan" position is the MCU rows a .. b),
@@ -146,9 +159,12 @@ def plan_decode_rows(columns: np.ndarray, row_sub: np.ndarray, ids, rows, worksp
     At `scale` 2, 4 or 8 (m = 8 // scale) `rows` are rows of the SCALED frame, clipped to its height ceil(H m / 8); a scaled MCU row is
     mcu_h m / 8 = v m of them, and no supported mode upsamples vertically at a scale, so there is no halo.  `band_height` stays the
     band's FULL-size height, what the record of fear_jpeg_decode_scaled_u8 holds; `band_y0`, `band_out`, `pixel_prefix`, `out_offset` and
-    `out_bytes` are the scaled frame's."""
-    m = 8 // _check_scale(scale)
+    `out_bytes` are the scaled frame's.
+    With a scale per position (`plan_decode` states the form) `rows[i]` is in rows of position i's own scaled frame, a position at
+    scale 1 keeps its halo and a scaled one has none: every per-position entry is the uniform plan's at that position's scale."""
     ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    scale = _check_scales(scale, ids.size)
+    m = 8 // scale
     rows = np.asarray(rows, dtype=np.int64).reshape(-1, 2)
     col = columns[ids]
     is_scan = col["kind"] == KIND_SCAN
@@ -157,7 +173,7 @@ def plan_decode_rows(columns: np.ndarray, row_sub: np.ndarray, ids, rows, worksp
     mcus_y = col["mcus_y"].astype(np.int64)
     y0, y1 = np.clip(rows[:, 0], 0, H), np.clip(rows[:, 1], 0, H)
     some = is_scan & (y0 < y1)
-    halo = col["halo"].astype(np.int64) if m == 8 else np.zeros(ids.size, dtype=np.int64)
+    halo = col["halo"].astype(np.int64) * (m == 8)
     a = np.where(some, np.maximum(y0 // mcu_h - halo, 0), 0)
     b = np.where(some, np.minimum(-(-y1 // mcu_h) + halo, mcus_y), 0)
     blocks = (b - a) * col["mcus_x"].astype(np.int64) * col["nslots"].astype(np.int64)
@@ -180,12 +196,12 @@ def plan_decode_rows(columns: np.ndarray, row_sub: np.ndarray, ids, rows, worksp
             sub_prefix=_exclusive(-(-count[pick] // LANES)).astype(np.uint32),
             mcu_row0=a[pick].astype(np.uint32), mcu_rows=(b - a)[pick].astype(np.uint32),
             band_y0=band_y0[pick], band_height=band_full[pick].astype(np.int32), band_out=3 * W[pick] * band_y0[pick],
-            **_layout(blocks[pick], band_h[pick] * W[pick], pixels[lo:hi])))
+            **_layout(blocks[pick], band_h[pick] * W[pick], pixels[lo:hi]), **_group_scales(scale, pick)))
     return groups
 
 
 def plan_decode_windows(columns: np.ndarray, row_sub: np.ndarray, ids, windows, workspace_limit: int, max_group: int = 65535,
-                        scale: int = 1) -> List[dict]:
+                        scale=1) -> List[dict]:
     """The host's share of `JpegStore.decode_windows`, as its two siblings a pure function without a loop over the files.  `windows`
     is (n, 4) pixel rectangles [y0, y1) x [x0, x1) per position, as (y0, y1, x0, x1), clipped to the frame; one without rows or columns
     is the empty window.  The rows follow `plan_decode_rows`: the band of MCU rows a .. b) that covers [y0, y1), one more on each
@@ -209,9 +225,12 @@ def plan_decode_windows(columns: np.ndarray, row_sub: np.ndarray, ids, windows, 
         out_offset, out_bytes the compact tensors, each at a multiple of 16 bytes.
     At `scale` 2, 4 or 8 (m = 8 // scale) `windows` are rectangles of the SCALED frame; a scaled MCU is (mcu_h m / 8) x (mcu_w m / 8)
     pixels; `band_height` and `win_width` stay full-size, what the record of fear_jpeg_decode_scaled_u8 holds, and every other
-    quantity is the scaled frame's."""
-    m = 8 // _check_scale(scale)
+    quantity is the scaled frame's.
+    With a scale per position (`plan_decode` states the form) `windows[i]` is in pixels of position i's own scaled frame, and every
+    per-position entry is the uniform plan's at that position's scale."""
     ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    scale = _check_scales(scale, ids.size)
+    m = 8 // scale
     win = np.asarray(windows, dtype=np.int64).reshape(-1, 4)
     col = columns[ids]
     is_scan = col["kind"] == KIND_SCAN
@@ -227,7 +246,7 @@ def plan_decode_windows(columns: np.ndarray, row_sub: np.ndarray, ids, windows, 
     x0, x1 = np.clip(win[:, 2], 0, W), np.clip(win[:, 3], 0, W)
     filled = (y0 < y1) & (x0 < x1)
     some = is_scan & filled
-    halo_y = col["halo"].astype(np.int64) if m == 8 else np.zeros(ids.size, dtype=np.int64)
+    halo_y = col["halo"].astype(np.int64) * (m == 8)
     halo_x = (full_mcu_w == 16).astype(np.int64)
     a = np.where(some, np.maximum(y0 // mcu_h - halo_y, 0), 0)
     b = np.where(some, np.minimum(-(-y1 // mcu_h) + halo_y, mcus_y), 0)
@@ -260,7 +279,7 @@ def plan_decode_windows(columns: np.ndarray, row_sub: np.ndarray, ids, windows, 
             band_height=high_full[pick].astype(np.int32), win_width=wide_full[pick].astype(np.int32),
             band_out=np.zeros(pick.size, dtype=np.int64),
             origin=origin[lo:hi], high=high[lo:hi], wide=wide[lo:hi], window=window[lo:hi],
-            **_layout(blocks[pick], high[pick] * wide[pick], (high * wide)[lo:hi])))
+            **_layout(blocks[pick], high[pick] * wide[pick], (high * wide)[lo:hi]), **_group_scales(scale, pick)))
     return groups
 
 
@@ -377,17 +396,20 @@ class JpegStore:
             self._pinned = self._pinned[-1:] + [pinned]
             return self._border.index_select(0, index)
 
-    def shape(self, ids, scale: int = 1) -> np.ndarray:
-        """(len(ids), 2) int32: height and width, of the frames `decode(ids, scale=scale)` returns."""
-        _check_scale(scale)
-        rows = self._columns[self._checked(ids)]
+    def shape(self, ids, scale=1) -> np.ndarray:
+        """(len(ids), 2) int32: height and width, of the frames `decode(ids, scale=scale)` returns; `scale` an int or one per id."""
+        ids = self._checked(ids)
+        scale = _check_scales(scale, ids.size)
+        rows = self._columns[ids]
         return np.stack(_scaled_sides(rows["H"], rows["W"], scale), axis=1).astype(np.int32)
 
-    def _scan_only(self, ids: np.ndarray, scale: int) -> None:
-        """At a scale every id is a "scan" entry: decoded pixels cannot be decoded again."""
-        kept = np.flatnonzero(self._columns["kind"][ids] == KIND_PIXELS)
-        if scale > 1 and kept.size:
-            raise UnsupportedJPEG(f"id {int(ids[kept[0]])} is kept as decoded pixels, which scale={scale} cannot decode")
+    def _scan_only(self, ids: np.ndarray, scale) -> None:
+        """At a scale every id is a "scan" entry: decoded pixels cannot be decoded again.  With a scale per position an entry kept as
+        pixels is fine at a position whose scale is 1."""
+        kept = np.flatnonzero((self._columns["kind"][ids] == KIND_PIXELS) & (scale > 1))
+        if kept.size:
+            at = scale if isinstance(scale, int) else int(scale[kept[0]])
+            raise UnsupportedJPEG(f"id {int(ids[kept[0]])} is kept as decoded pixels, which scale={at} cannot decode")
 
     def _checked(self, ids) -> np.ndarray:
         ids = np.asarray(ids, dtype=np.int64).reshape(-1)
@@ -663,12 +685,17 @@ class JpegStore:
         return self._frame_borders(_frame_views(out, plan["out_offset"], high, wide), stream)
 
     # ----------------------------------------------------------------------------------------------------------------------- decode
-    def decode(self, ids, check: bool = False, scale: int = 1) -> List:
+    def decode(self, ids, check: bool = False, scale=1) -> List:
         """`scale` 2, 4 or 8: the frames at 1/2, 1/4 or 1/8 size (`shape(ids, scale)`), byte for byte `JpegDecoder.decode(scale=)`'s and
         libjpeg's: the same plan and Huffman stage, `fear_jpeg_decode_scaled_u8` for the pixels.  An id kept as pixels is then an
-        `UnsupportedJPEG` naming it, another `scale` a ValueError, both before any launch."""
-        scale = _check_scale(scale)
+        `UnsupportedJPEG` naming it, another `scale` a ValueError, both before any launch.
+        `scale` may also be a sequence or array of len(ids) scales from {1, 2, 4, 8}, one per POSITION (the same id may come several
+        times at different scales): frame i is `decode([ids[i]], scale=scale[i])[0]` byte for byte.  A group of the call whose scales
+        differ runs `fear_jpeg_decode_mixed_u8` — still two pixel launches — and one whose scales are all equal the uniform launch; a
+        sequence of equal values gives the int's bytes.  A wrong length, another value or a bool is a ValueError, and an id kept as
+        pixels at a position whose scale is not 1 an `UnsupportedJPEG`, before any launch.  (`JpegDecoder.decode` takes an int alone.)"""
         ids = self._checked(ids)
+        scale = _check_scales(scale, ids.size)
         self._scan_only(ids, scale)
         return self._decode_groups(ids, plan_decode(self._columns, ids, self.workspace_limit, scale=scale), check, scale=scale)
 
@@ -679,7 +706,7 @@ class JpegStore:
             raise ValueError(f"rows on a device must be ({ids.size}, 2) int32 on {mine}, one [y0, y1) per id")
         return self._decode_groups(ids, plan_decode(self._columns, ids, self.workspace_limit), check, rows)
 
-    def _decode_groups(self, ids: np.ndarray, plans: List[dict], check: bool, rows=None, scale: int = 1) -> List:
+    def _decode_groups(self, ids: np.ndarray, plans: List[dict], check: bool, rows=None, scale=1) -> List:
         """The frames of one call, group by group."""
         frames: List = [None] * ids.size
         self._pending = self._pending[-self.PENDING_CALLS:]              # of earlier calls; every group of this call is kept
@@ -689,14 +716,15 @@ class JpegStore:
             self.check()
         return frames
 
-    def _decode_group(self, ids: np.ndarray, plan: dict, frames: List, rows=None, scale: int = 1) -> None:
+    def _decode_group(self, ids: np.ndarray, plan: dict, frames: List, rows=None, scale=1) -> None:
         """One group of `decode`, of both forms of `decode_rows` and of `decode_windows`: the shared block_start table, the gathered records with the
         group's addresses, one pinned upload, the Huffman kernel, the pixel stage, the verdicts, the frames.  What the plan carries
         and `rows` select the kernels: a plan of `plan_decode_rows` carries the bands (sub0, sub_count, mcu_row0, mcu_rows, band_height,
         band_out), which go into the records for `fear_jpeg_huffman_indexed_rows`; a plan of `plan_decode_windows` carries the MCU
         columns and the window's width as well (cols, win_width) and the compact tensors' shapes (high, wide, window), for
         `fear_jpeg_huffman_indexed_windows`; `rows`, the call's device tensor, goes with
-        `plan_decode`'s full-image plan to the two kernels that read the bands on the device."""
+        `plan_decode`'s full-image plan to the two kernels that read the bands on the device; a plan with a scale per position
+        carries `scales`, which go into the records' reserved[0] and to `_launch_pixels`, which chooses the pixel stage's entry point."""
         import torch
         from . import train_abi as abi
         P = ctypes.c_void_p
@@ -724,6 +752,8 @@ class JpegStore:
                     indexed["reserved"] = plan["cols"]
                     images["width"] = plan["win_width"]
                 _place_images(images, coef, plan["coef_offset"], block_start, out, at_out, plan["plane_offset"])
+                if "scales" in plan:
+                    images["reserved"][:, 0] = plan["scales"]
                 # one pinned upload: prefix | FearJpegIndexed records, then two prefixes | FearJpegImage records; with rows on the
                 # device and a group that is no run of positions also the positions, to gather the group's rows with
                 parts = [plan["sub_prefix"], indexed, np.concatenate([plan["block_prefix"], plan["pixel_prefix"]]), images]
@@ -738,7 +768,8 @@ class JpegStore:
                     huffman = "fear_jpeg_huffman_indexed_windows" if windowed else ("fear_jpeg_huffman_indexed_rows" if banded else "fear_jpeg_huffman_indexed")
                     abi.launch(self._lib, huffman, P(indexed.ctypes.data), nd,
                                P(dev.data_ptr()), P(coef.data_ptr()), P(status.data_ptr()), self.subsequence_bytes, stream)
-                    _launch_pixels(self._lib, P(images.ctypes.data), nd, table, ws.data_ptr(), plan["workspace_bytes"], scale, stream)
+                    _launch_pixels(self._lib, P(images.ctypes.data), nd, table, ws.data_ptr(), plan["workspace_bytes"],
+                                   plan.get("scales", scale), stream)
                 else:                                                    # the group's rows: a slice, or a gather on the device; no wait
                     mine = rows[lo:hi] if whole else rows.index_select(0, dev[at[4]:].view(torch.int64))
                     mine = mine.contiguous()
@@ -759,7 +790,7 @@ class JpegStore:
                     out[out_offset[k]:out_offset[k] + 3 * high[k] * wide[k]].view(int(high[k]), int(wide[k]), 3).copy_(
                         self._pixels[int(group[k])][y0:y1, x0:x1], non_blocking=True)
             else:
-                high, wide = _scaled_sides(cols["H"], cols["W"], scale)
+                high, wide = _scaled_sides(cols["H"], cols["W"], scale if isinstance(scale, int) else scale[lo:hi])
                 for k in np.flatnonzero(cols["kind"] == KIND_PIXELS):    # the entries kept as pixels: a whole copy, never an alias
                     out[out_offset[k]:out_offset[k] + 3 * high[k] * wide[k]].copy_(self._pixels[int(group[k])].view(-1), non_blocking=True)
         frames[lo:hi] = _frame_views(out, out_offset, high, wide)
@@ -799,7 +830,7 @@ class JpegStore:
         return dev, at
 
     # ------------------------------------------------------------------------------------------------------------------ decode_rows
-    def decode_rows(self, ids, rows=None, check: bool = False, scale: int = 1) -> List:
+    def decode_rows(self, ids, rows=None, check: bool = False, scale=1) -> List:
         """`decode` for the rows a consumer reads.  `rows` is (len(ids), 2) integers, the pixel rows [y0, y1) per position, clipped to
         [0, H]; the result is what `decode` returns — private uint8 (H, W, 3) tensors of the FULL frame shape — of which only the rows
         [y0, y1) are defined: they are byte for byte `decode`'s.  ALL OTHER ROWS HOLD UNSPECIFIED BYTES (a row that is never read costs
@@ -827,13 +858,16 @@ class JpegStore:
         MCU row is v m pixel rows, m = 8 // scale — without a halo: at a scale no supported mode upsamples vertically.  The band goes
         through `fear_jpeg_decode_scaled_u8` as an image of its own: the record's height is the band's full-size height and `out` its
         first scaled row.  An id kept as pixels is an `UnsupportedJPEG`; `rows` on the device with `scale` > 1 is a ValueError (out of
-        scope)."""
-        scale = _check_scale(scale)
+        scope).
+        `scale` may also be one scale per position, as `decode` takes it, for rows on the host: `rows[i]` is then in rows of position
+        i's own scaled frame, a position at scale 1 keeps its chroma halo and a scaled one has none, and an entry kept as pixels is
+        fine where the scale is 1.  Rows on the device take `scale=1` alone, as an int or per position (out of scope otherwise)."""
+        ids = self._checked(ids)
+        scale = _check_scales(scale, ids.size)
         if rows is None:
             return self.decode(ids, check=check, scale=scale)
-        ids = self._checked(ids)
         if type(rows).__module__.split(".")[0] == "torch" and rows.is_cuda:         # (a CPU tensor is host rows, as before)
-            if scale > 1:
+            if np.any(scale > 1):
                 raise ValueError("decode_rows takes rows on the device at scale=1 only")
             return self._decode_rows_device(ids, rows, check)
         self._scan_only(ids, scale)
@@ -844,7 +878,7 @@ class JpegStore:
                                    scale=scale)
 
     # --------------------------------------------------------------------------------------------------------------- decode_windows
-    def decode_windows(self, ids, windows, check: bool = False, scale: int = 1) -> WindowFrames:
+    def decode_windows(self, ids, windows, check: bool = False, scale=1) -> WindowFrames:
         """`decode` for the rectangle of each frame that a consumer reads, as COMPACT tensors.  `windows` is (len(ids), 4) integers on
         the host, [y0, y1) x [x0, x1) per position as (y0, y1, x0, x1), in pixels of the frame `decode(ids, scale=scale)` returns and
         clipped to it.  The result is a `WindowFrames`: `frames[i]` is a private uint8 (wh, ww, 3) tensor (cut from one allocation per
@@ -859,9 +893,11 @@ class JpegStore:
         An empty window gives a (0, 0, 3) tensor and no lanes; an entry kept as pixels gives a device-to-device copy of the rectangle
         itself at scale 1 and is an `UnsupportedJPEG` at a scale.  A `windows` of another shape is a ValueError and a bad id an
         IndexError, both before any launch.  Like `decode` it never waits, the statuses (of the lanes that ran) go to `check()`, and
-        `workspace_limit` splits the call, by the windows' dense coefficients.  Windows on the device are out of scope."""
-        scale = _check_scale(scale)
+        `workspace_limit` splits the call, by the windows' dense coefficients.  Windows on the device are out of scope.
+        `scale` may also be one scale per position, as `decode` takes it: `windows[i]` is then in pixels of position i's own scaled
+        frame, `shape` is `shape(ids, scale)` per position, and an entry kept as pixels is fine where the scale is 1."""
         ids = self._checked(ids)
+        scale = _check_scales(scale, ids.size)
         self._scan_only(ids, scale)
         windows = np.asarray(windows)
         if windows.shape != (ids.size, 4) or not np.issubdtype(windows.dtype, np.integer):

@@ -117,6 +117,7 @@ TRAIN_SYMBOLS = {
     "fear_jpeg_huffman_indexed_rows_dev": ([_P, _i, _P, _P, _P, _P, _i, _P], _i),
     "fear_jpeg_decode_u8_rows_dev": ([_P, _i, _P, _P, _P, _sz, _P], _i),
     "fear_jpeg_decode_scaled_u8": ([_P, _i, _P, _i, _P, _sz, _P], _i),
+    "fear_jpeg_decode_mixed_u8": ([_P, _i, _P, _P, _sz, _P], _i),      # a scale per record, in FearJpegImage.reserved[0]
     # the colour stage's members that are no lookup table (FearColourOp below)
     "fear_colour_u8": ([_P, _i, _i, _i, _P, _P, _P, _P], _i),
     # ISONoise, RandomRain and RandomShadow of the photometric stage (FearHlsOp below)
@@ -354,6 +355,7 @@ assert FearJpegIndexed.row_sub.offset == 56
 assert ctypes.sizeof(FearJpegInfo) == 464 and FearJpegInfo.qt.offset == 80
 assert ctypes.sizeof(FearJpegHuff) == 1440 and ctypes.sizeof(FearJpegScan) == 8704 and FearJpegScan.dc.offset == 64
 assert ctypes.sizeof(FearJpegImage) == 448 and FearJpegImage.qt.offset == 64
+assert FearJpegImage.reserved.offset == 52                               # reserved[0]: the record's scale for fear_jpeg_decode_mixed_u8
 
 
 class FearJpegEncImage(ctypes.Structure):

@@ -65,7 +65,9 @@ class TrainPairBuilder:
     def draw(self, pairs, frame_shapes: Sequence[Tuple[int, ...]], generator: Optional[np.random.Generator] = None) -> TrainPairParams:
         """Every random parameter of a batch, vectorised, from `generator` (the builder's own when None).  The draws mirror the
         reference's: u = U * range + (2 context - range / 2) (tracking_dataset.py:102-105); scale ~ U(-0.35, 0.35), shift ~
-        U(-48, 48) (aug.py:90-93); tone at p = 0.05, colour at p = 0.5, each picking uniformly among its members."""
+        U(-48, 48) (aug.py:90-93); tone at p = 0.05, colour at p = 0.5, each picking uniformly among its members.
+        Of `pairs` the draws read the number of rows B and nothing else, and `frame_shapes` is only recorded: two tables of the same B
+        give equal params from the same generator state (what `frame_scales` and `PairLoader(scale="auto")` rely on)."""
         p = _pairs_array(pairs)
         rng = self.generator if generator is None else generator
         cfg = self.config
@@ -288,6 +290,35 @@ class TrainPairBuilder:
         out = np.stack([lo[:, 0], hi[:, 0], lo[:, 1], hi[:, 1]], axis=1)
         out[(lo >= hi).any(axis=1)] = 0
         return out
+
+    def frame_scales(self, pairs, params: TrainPairParams, frame_shapes: Sequence[Tuple[int, ...]], max_scale: int = 8) -> np.ndarray:
+        """(F,) int64: per frame the largest decode scale of {1, 2, 4, 8}, at most `max_scale`, at which no crop `build` reads from
+        the frame is upsampled that was a reduction at full size.  `pairs` is the FULL-size table and the context boxes are
+        `tables(pairs, params)`'s.  A template use is resized to TEMPLATE_SIZE, a search use to CONTEXT_SIZE (the crop the search
+        context is resized to before the jitter); a use admits the largest s with min(context width, context height) >= s * target,
+        a frame takes the minimum over its uses, and a frame no pair uses takes 1.  With `scale_pairs(pairs, scales)` the scaled
+        context's sides are the full-size ones' divided by a power of two in front of `_extend`'s truncation, so a side that was at least
+        s * target stays at least the target.  `draw` reads of the pairs nothing but their number B (it records `frame_shapes` and
+        consumes the generator by B and the configuration alone), so the params drawn on the full-size table are the params of the
+        scaled one: draw once, `frame_scales`, `scale_pairs`, then `frame_rows` / `frame_windows` on the scaled shapes."""
+        from ..jpeg_frames import _check_scale
+        max_scale = _check_scale(max_scale)
+        tab = self.tables(pairs, params)
+        geom = tab["geom"]
+        F = len(frame_shapes)
+        scales = np.full(F, max_scale, dtype=np.int64)
+        used = np.zeros(F, dtype=bool)
+        for frame, ctx, target in ((geom["t_frame"], tab["t_ctx"], TEMPLATE_SIZE), (geom["s_frame"], tab["s_ctx"], CONTEXT_SIZE)):
+            frame = frame.astype(np.int64)
+            ok = (frame >= 0) & (frame < F)
+            side = np.minimum(ctx[:, 2], ctx[:, 3]).astype(np.int64)
+            admits = np.ones(side.size, dtype=np.int64)
+            for s in (2, 4, 8):
+                admits[side >= s * target] = s
+            np.minimum.at(scales, frame[ok], admits[ok])
+            used[frame[ok]] = True
+        scales[~used] = 1
+        return scales
 
     def _params(self, pairs, frames, params):
         if isinstance(frames, WindowFrames):

@@ -12,7 +12,7 @@ everything runs on the current stream.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Any, Dict, Iterator, List, Optional, Sequence
 
 import numpy as np
@@ -61,11 +61,13 @@ class LoadedBatch:
     batch: TrainBatch                # the builder's six tensors
     visible: torch.Tensor            # (B,) int32 on the device: the search row's presence
     dataset_ids: torch.Tensor        # (B,) int32 on the device, into `loader.datasets`: the search row's dataset
-    pairs: np.ndarray                # (B, 11) float64: the table `build` was given (boxes clipped, then divided by `scale`)
+    pairs: np.ndarray                # (B, 11) float64: the table `build` was given (boxes clipped, then divided by `scale`; with
+                                     # scale="auto" by each frame's own of `scales`)
     params: TrainPairParams          # the draws `build` was given
     ids: np.ndarray                  # the distinct store ids, in `pairs`' frame numbering
     rows: np.ndarray                 # (B, 2) int64: the rows [template, search] of the pair's table
     sampler: np.ndarray              # (B,) which sampler of the plan each pair came from
+    scales: Optional[np.ndarray] = None   # (F,) int64: the decode scale of each frame of `ids`
 
 
 class PairLoader:
@@ -73,13 +75,26 @@ class PairLoader:
     starts the next one (`EpochPlan.start_epoch`: a fresh permutation).  `row_ids[s][row]` is the store id of row `row` of sampler
     s's table (what `fill_store` returns).  `scale` 2, 4 or 8 decodes the frames at that fraction and divides the boxes
     (`scale_pairs`); `rows=False` decodes whole frames; `windows=True` decodes per frame the rectangle the batch reads, as compact
-    tensors (`JpegStore.decode_windows`), and hands out the same batches.  The loader never waits for the GPU and never reads from it; call
+    tensors (`JpegStore.decode_windows`), and hands out the same batches.  `scale="auto"` picks a scale per frame and batch: the draws
+    are made once on the full-size table, `TrainPairBuilder.frame_scales(..., max_scale=)` gives each frame the largest scale that
+    upsamples no crop read from it, `scale_pairs` divides each box by its frame's scale and the store decodes the mixed call
+    (`decode_rows` / `decode_windows` / `decode` with `scale=item.scales`); the draws and the generator stream are those of scale 1,
+    the crops are not (they are resampled from smaller frames), and there is no new generator state, so resuming is unaffected.
+    The loader never waits for the GPU and never reads from it; call
     `store.check()` at the end of an epoch to see the decode statuses.  `datasets` are the tables' dataset names, sorted."""
 
-    def __init__(self, plan: EpochPlan, store, row_ids: Sequence[np.ndarray], builder, scale: int = 1, rows: bool = True, prefetch: int = 1,
-                 windows: bool = False):
+    def __init__(self, plan: EpochPlan, store, row_ids: Sequence[np.ndarray], builder, scale=1, rows: bool = True, prefetch: int = 1,
+                 windows: bool = False, max_scale: int = 8):
         if prefetch not in (0, 1):
             raise ValueError("prefetch is 0 or 1")
+        if max_scale not in (1, 2, 4, 8) or isinstance(max_scale, bool):
+            raise ValueError("max_scale is 1, 2, 4 or 8")
+        self.auto, self.max_scale = isinstance(scale, str), int(max_scale)
+        if self.auto and scale != "auto":
+            raise ValueError(f'scale is 1, 2, 4, 8 or "auto", not {scale!r}')
+        if not self.auto and (isinstance(scale, bool) or scale not in (1, 2, 4, 8)):
+            raise ValueError(f'scale is 1, 2, 4, 8 or "auto", not {scale!r}')
+        scale = 1 if self.auto else scale
         if len(row_ids) != len(plan.samplers):
             raise ValueError(f"row_ids has {len(row_ids)} entries, the plan {len(plan.samplers)} samplers")
         self.plan, self.store, self.builder = plan, store, builder
@@ -132,21 +147,27 @@ class PairLoader:
         """The whole data stage of one batch on the current stream."""
         pairs, ids, visible, dataset, rows, which = self._host(positions)
         store, builder = self.store, self.builder
-        shapes = store.shape(ids, self.scale)
+        scale = self.scale
+        shapes = store.shape(ids, scale)
         params = builder.draw(pairs, shapes)
+        if self.auto:                                          # the draws are the full-size table's; the frames and boxes each frame's own
+            scale = builder.frame_scales(pairs, params, shapes, self.max_scale)
+            pairs, shapes = scale_pairs(pairs, scale), store.shape(ids, scale)
+            params = replace(params, frame_shapes=tuple((int(h), int(w)) for h, w in shapes.tolist()))
         if self.windows:
-            frames = store.decode_windows(ids, builder.frame_windows(pairs, params, shapes), scale=self.scale)
+            frames = store.decode_windows(ids, builder.frame_windows(pairs, params, shapes), scale=scale)
         elif self.rows:
-            frames = store.decode_rows(ids, builder.frame_rows(pairs, params, shapes), scale=self.scale)
+            frames = store.decode_rows(ids, builder.frame_rows(pairs, params, shapes), scale=scale)
         else:
-            frames = store.decode(ids, scale=self.scale)
+            frames = store.decode(ids, scale=scale)
         batch = builder.build(frames, pairs, params, borders=store.borders(ids))
         B = len(visible)
         pinned = torch.empty((2, B), dtype=torch.int32, pin_memory=True)
         np.copyto(pinned.numpy(), np.stack([visible, dataset]))
         with torch.cuda.device(self.device):
             both = pinned.to(self.device, non_blocking=True)
-        return LoadedBatch(batch, both[0], both[1], pairs, params, ids, rows, which)
+        return LoadedBatch(batch, both[0], both[1], pairs, params, ids, rows, which,
+                           scale if self.auto else np.full(ids.size, scale, dtype=np.int64))
 
     def _snapshot(self, number: int) -> Dict[str, Any]:
         """The generator states in front of batch `number`: what is needed to draw it again."""

@@ -140,15 +140,26 @@ def _pairs_array(pairs) -> np.ndarray:
     return p
 
 
-def scale_pairs(pairs, scale: int) -> np.ndarray:
+def scale_pairs(pairs, scale) -> np.ndarray:
     """A (B, 11) pair table for frames decoded at 1 / `scale` (`JpegStore.decode(ids, scale=)`, `decode_rows(..., scale=)`): a float64
     copy with the template box and the search box (x, y, w, h each) divided by `scale`, the frame indices and the presence as they are.
-    `frame_rows`, `draw` and `build` then run unchanged on the smaller frames."""
-    from ..jpeg_frames import _check_scale
-    scale = _check_scale(scale)
+    `frame_rows`, `draw` and `build` then run unchanged on the smaller frames.
+    `scale` may also be an (F,) array of per-FRAME scales (`TrainPairBuilder.frame_scales`): the template box is divided by the scale
+    of frame pairs[:, 0], the search box by that of frame pairs[:, 5] — the two may differ; a constant array equals the int bit for
+    bit.  A frame index outside 0..F-1 is a ValueError."""
+    from ..jpeg_frames import _check_scale, _check_scales
     p = _pairs_array(pairs).copy()
-    p[:, 1:5] /= scale
-    p[:, 6:10] /= scale
+    if isinstance(scale, (int, np.integer)):
+        scale = _check_scale(scale)
+        p[:, 1:5] /= scale
+        p[:, 6:10] /= scale
+        return p
+    scale = _check_scales(scale, len(scale) if hasattr(scale, "__len__") else -1)
+    t, s = p[:, 0].astype(np.int64), p[:, 5].astype(np.int64)
+    if p.shape[0] and (min(t.min(), s.min()) < 0 or max(t.max(), s.max()) >= scale.size):
+        raise ValueError(f"a pair names a frame outside the {scale.size} scales")
+    p[:, 1:5] /= scale[t][:, None]
+    p[:, 6:10] /= scale[s][:, None]
     return p
 
 

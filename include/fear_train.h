@@ -723,8 +723,8 @@ typedef struct FearJpegImage {
     int32_t width, height;
     int32_t components;          /* 1 or 3                                                                               */
     int32_t h, v;                /* the luma sampling factors: (1, 1), (2, 1) or (2, 2); (1, 1) with one component       */
-    int32_t reserved[3];
-    uint16_t qt[3][64];          /* FearJpegInfo's                                                                       */
+    int32_t reserved[3];         /* [0]: the record's scale, read by fear_jpeg_decode_mixed_u8 alone (below); [1..2]: reserved */
+    uint16_t qt[3][64];          /* FearJpegInfo's                                                                    */
 } FearJpegImage;
 #ifdef __cplusplus
 static_assert(sizeof(FearJpegImage) == 448, "FearJpegImage is 448 bytes");
@@ -764,6 +764,20 @@ size_t fear_jpeg_decode_workspace_bytes(const FearJpegInfo* infos, int n);
  * without a launch.  No atomics, bounded loops only, a block reads at most 64 stored values.                                          */
 int fear_jpeg_decode_scaled_u8(const FearJpegImage* images, int n, const uint32_t* group_start, int scale, void* workspace,
                                size_t workspace_bytes, void* stream);
+/* fear_jpeg_decode_scaled_u8 with a scale PER RECORD, full size included: two launches whatever the mix and whatever n is.  Record i
+ * carries its scale s_i in reserved[0] (byte 52 of the record): 0 or 1 is full size, 2, 4 and 8 are the scales, anything else is
+ * FEAR_TRAIN_ERR_SHAPE; reserved[1..2] stay reserved, and the three entry points above go on ignoring the word.  Record i is exactly
+ * the record the uniform call at s_i would carry — width, height and the sampling the file's, or the band's or window's full-size
+ * ones, `out` the scaled frame or the band's first scaled row — and its pixels are that call's, byte for byte: fear_jpeg_decode_u8's at
+ * full size (h2v2 and h2v1 fancy upsampling at the true chroma edges, replication for cw <= 2), fear_jpeg_decode_scaled_u8's otherwise.
+ * The table's first prefix table is unchanged (32 blocks per workgroup); the second counts each image's OWN scaled pixels,
+ * ceil(ceil(height m_i / 8) ceil(width m_i / 8) / FEAR_JPEG_GROUP_PIXELS) with m_i = 8 / max(s_i, 1).  A workgroup belongs to one image
+ * and reads its m once from the record (a scalar load, a uniform branch).  The planes of a full-size record take 64 bytes per block,
+ * those of a scaled one less: fear_jpeg_decode_workspace_bytes stays the bound to allocate and is what the call checks.
+ * The checks and their order are fear_jpeg_decode_u8's, the scale being part of a record's shape; n == 0 returns FEAR_TRAIN_OK without
+ * a launch.  No atomics, bounded loops only, a block reads at most 64 stored values.                                                  */
+int fear_jpeg_decode_mixed_u8(const FearJpegImage* images, int n, const uint32_t* group_start, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /* ---- the Huffman stage on the device (jpeg_huffman.jpeg_entropy_parallel_host restates it in Python, step for
  * step).  A baseline scan has no index, but Huffman streams re-synchronise by themselves: the self-synchronising parallel decode of

@@ -10,6 +10,8 @@ sampler keys        --negative-ratio, --frame-offset, --clip-range, --num-sample
 --val-dir DIR       every sub-directory is a sequence: its *.jpg files in name order and groundtruth.txt with one "x,y,w,h" per line
                     (GOT-10k's layout); validated every --val-every epochs under the dataset name --val-name
 --scale 2|4|8       decode the training frames at that fraction (JpegStore.decode_rows(scale=))
+--scale auto        per batch and frame the largest fraction that upsamples no crop read from the frame (TrainPairBuilder.frame_scales),
+                    at most 1 / --max-scale
 --windows           decode per frame only the rectangle a batch reads, as compact frames (JpegStore.decode_windows)
 Every file is decoded from a JpegStore, so the datasets must fit in --capacity-gb of device memory.  The run writes last.pt (resumed
 from with --resume), the best three .fearw files and history.json under --out.  After every epoch the tool calls `store.check()`: the
@@ -60,7 +62,8 @@ def parse_args(argv=None):
     ap.add_argument("--epochs", type=int, default=50)
     ap.add_argument("--min-epochs", type=int, default=0)
     ap.add_argument("--batch", type=int, default=128)
-    ap.add_argument("--scale", type=int, default=1, choices=(1, 2, 4, 8))
+    ap.add_argument("--scale", type=lambda v: v if v == "auto" else int(v), default=1, choices=(1, 2, 4, 8, "auto"))
+    ap.add_argument("--max-scale", type=int, default=8, choices=(1, 2, 4, 8), help="the largest scale --scale auto picks")
     ap.add_argument("--windows", action="store_true", help="decode the rectangles a batch reads as compact frames")
     ap.add_argument("--photometric", action="store_true", help="the photometric stage of the data builder")
     ap.add_argument("--prefetch", type=int, default=1, choices=(0, 1))
@@ -111,7 +114,8 @@ def main(argv=None):
     row_ids = fill_store(store, tables)
     print(f"{sum(map(len, tables))} rows, {len(store)} files, {store.nbytes / 2 ** 20:.0f} MiB resident")
     builder = TrainPairBuilder(dict(photometric=True) if args.photometric else None, device=args.device, seed=args.seed)
-    loader = PairLoader(plan, store, row_ids, builder, scale=args.scale, prefetch=args.prefetch, windows=args.windows)
+    loader = PairLoader(plan, store, row_ids, builder, scale=args.scale, prefetch=args.prefetch, windows=args.windows,
+                        max_scale=args.max_scale)
     net = FEARNetTrainHIP(random_init_state(args.seed), device=args.device, momentum=args.bn_momentum)
     cfg = {"name": args.optimizer, "lr": args.lr}
     opt = make_optimizer(net, cfg, gradient_clip_val=args.gradient_clip)
