@@ -94,32 +94,6 @@ class _Geometry:
         hc, vc = (self.h, self.v) if c == 0 else (1, 1)
         return self.comp_first[c] + (my * vc + j) * self.blocks_w[c] + mx * hc + i
 
-    def band_block(self, first_mcu: int, ordinal: int, slot: int, row0: int, rows: int) -> int:
-        """The same index in an image that consists of the MCU rows row0 .. row0 + rows) alone (jh_band_base): -1 for a block of another
-        row, by an explicit range test."""
-        my, mx = divmod(first_mcu + ordinal // self.nslots, self.mcus_x)
-        if my < row0 or my >= row0 + rows:
-            return -1
-        c = self.comp[slot]
-        j, i = divmod(slot, self.h) if c == 0 else (0, 0)
-        hc, vc = (self.h, self.v) if c == 0 else (1, 1)
-        band_mcus = rows * self.mcus_x
-        first = 0 if c == 0 else band_mcus * self.h * self.v + (c - 1) * band_mcus
-        return first + ((my - row0) * vc + j) * self.blocks_w[c] + mx * hc + i
-
-    def window_block(self, mcu: int, slot: int, row0: int, rows: int, col0: int, cols: int) -> int:
-        """The index of slot `slot` of MCU `mcu` in an image that consists of the MCUs of the rows row0 .. row0 + rows) and the columns
-        col0 .. col0 + cols) alone (jh_window_base): -1 for a block of another row or column, by explicit range tests."""
-        my, mx = divmod(mcu, self.mcus_x)
-        if my < row0 or my >= row0 + rows or mx < col0 or mx >= col0 + cols:
-            return -1
-        c = self.comp[slot]
-        j, i = divmod(slot, self.h) if c == 0 else (0, 0)
-        hc, vc = (self.h, self.v) if c == 0 else (1, 1)
-        win_mcus = rows * cols
-        first = 0 if c == 0 else win_mcus * self.h * self.v + (c - 1) * win_mcus
-        return first + ((my - row0) * vc + j) * (cols * hc) + (mx - col0) * hc + i
-
 
 _ERR, _DC, _ZEROS, _AC, _END = range(5)
 
@@ -309,11 +283,11 @@ class _Segment:
         self.last = s == len(seg_start) - 2
 
 
-def _write_pass(sg: _Segment, g: _Geometry, entry, end: int, begun: int, pred: list, dense, writes, band=None, record=None):
+def _write_pass(sg: _Segment, g: _Geometry, entry, end: int, begun: int, pred: list, dense, writes, record=None):
     """One lane of the write pass: decode from the true `entry` = (p, slot, z) to `end`, `begun` blocks of the segment begun in front
-    and `pred` the predictors (updated in place).  Stores what it decodes, judges it, and returns (exit state, begun, failed).  With
-    `band` = (row0, rows) only the blocks of those MCU rows are stored, band-dense (`dense` holds 64 values per block of the band); the
-    judgements are the same.  `record`, a list, takes every store the lane would make in any layout: (MCU, slot, z from, z to, value)."""
+    and `pred` the predictors (updated in place).  Stores what it decodes in `dense` (the whole image's layout; None stores nothing),
+    judges it, and returns (exit state, begun, failed).  `record`, a list, takes every store the lane makes, for `_place` to put in any
+    layout: (MCU, slot, z from, z to, value)."""
     ev, failed = [], False
     out = _decode(sg.buf, sg.L, entry, end, g, ev)
     slot, is_open = entry[1], entry[2] != 0                              # a block begun in an earlier subsequence is still open
@@ -343,15 +317,11 @@ def _write_pass(sg: _Segment, g: _Geometry, entry, end: int, begun: int, pred: l
                 failed = True
             if record is not None:
                 record.append((sg.first_mcu + (begun - 1) // g.nslots, slot, z0, z1, value))
-            if band is None:
+            if dense is not None:
                 b = g.block(sg.first_mcu, begun - 1, slot)
-                inside = b < g.total_blocks
-            else:
-                b = g.band_block(sg.first_mcu, begun - 1, slot, band[0], band[1])
-                inside = 0 <= b < band[1] * g.mcus_x * g.nslots
-            if dense is not None and inside:
-                dense[64 * b + z0:64 * b + z1] = value
-                writes[64 * b + z0:64 * b + z1] += 1
+                if b < g.total_blocks:
+                    dense[64 * b + z0:64 * b + z1] = value
+                    writes[64 * b + z0:64 * b + z1] += 1
     return out, begun, failed
 
 
@@ -447,12 +417,105 @@ def window_lanes(header: _Header, sub_start, index, lanes, cols) -> np.ndarray:
     return lanes[some & touches]
 
 
+def _record_lanes(data: bytes, sub_start, index, subsequence_bytes: int, row_sub=None, lanes=None):
+    """The lanes `lanes` of the indexed decode (image-numbered subsequences, run in that order; every one by default), each once and
+    whatever band is wanted (a lane's decode does not depend on it), as one lane of jpeg_huffman_indexed_kernel does it: the segment by
+    a search of `sub_start`, the write pass's rules, and the verdict — the lane of a segment's last subsequence judges the segment's
+    block count, the lane of its first an empty segment in front, the lane of the image's last subsequence empty segments behind.
+    Returns the header, the geometry, n_sub, the row table, each subsequence's verdict (False where its lane did not run), and every
+    store the lanes made, in the order they made them, one array entry per coefficient position — the lane, the MCU row and column,
+    the slot, z and the value."""
+    _check_subsequence_bytes(subsequence_bytes)
+    data = bytes(data)
+    hd = _parse(data)
+    stream, seg_start = jpeg_scan_prepare_host(data, hd)
+    g = _Geometry(hd)
+    n_seg, n_sub, SB = len(seg_start) - 1, len(index), 8 * subsequence_bytes
+    sub_start = np.asarray(sub_start, dtype=np.int64)
+    assert sub_start.size == n_seg + 1 and int(sub_start[-1]) == n_sub
+    if row_sub is None:
+        row_sub = scan_row_sub(hd, sub_start, index)
+    segs = [_Segment(hd, g, stream, seg_start, s) for s in range(n_seg)]
+    lane_failed = np.zeros(n_sub, dtype=bool)
+    lane_of, stores = [], []
+    for sub in (range(n_sub) if lanes is None else lanes):
+        sub = int(sub)
+        s = int(np.searchsorted(sub_start[:n_seg], sub, side="right")) - 1   # the last segment that starts at or in front of `sub`
+        sg, i, e = segs[s], sub - int(sub_start[s]), index[sub]
+        slot, z = min(int(e["sz"]) >> 8, g.nslots - 1), min(int(e["sz"]) & 255, 63)
+        made = []
+        state, begun, failed = _write_pass(sg, g, (int(e["p"]), slot, z), (i + 1) * SB, int(e["begun"]), [int(v) for v in e["dc"]], None, None,
+                                           record=made)
+        if (i + 1) * SB >= sg.L and begun - (state[2] != 0) < sg.expected:    # the segment's last subsequence: its block count
+            failed = True
+        if i == 0 and s > 0 and sub_start[s - 1] == sub_start[s]:            # an empty segment in front owes blocks
+            failed = True
+        if sub == n_sub - 1 and s != n_seg - 1:                              # empty segments behind the last subsequence
+            failed = True
+        lane_failed[sub] = failed
+        lane_of += [sub] * len(made)
+        stores += made
+    mcu, slot, z0, z1, value = np.array(stores, dtype=np.int64).reshape(-1, 5).T
+    each = z1 - z0                                                           # a store of z0 .. z1) is one entry per position
+    z_of = np.arange(int(each.sum())) - np.repeat(np.cumsum(each) - each - z0, each)
+    lane_of, mcu, slot, value = (np.repeat(np.asarray(v, dtype=np.int64), each) for v in (lane_of, mcu, slot, value))
+    return hd, g, n_sub, row_sub, lane_failed, (lane_of, mcu // g.mcus_x, mcu % g.mcus_x, slot, z_of, value.astype(np.int16))
+
+
+def _clipped(pair, count: int):
+    """(lo, hi) of `pair` clipped to 0 .. count, hi at least lo."""
+    lo = min(max(int(pair[0]), 0), count)
+    return lo, min(max(int(pair[1]), lo), count)
+
+
+def _band_lanes(row_sub, band, n_sub: int) -> range:
+    """The lanes of the MCU rows band = (a, b): the subsequences row_sub[a] .. min(row_sub[b], n_sub - 1), none for the empty band."""
+    a, b = band
+    return range(int(row_sub[a]), min(int(row_sub[b]), n_sub - 1) + 1) if b > a else range(0)
+
+
+def _status(n_sub: int, lane_failed, lanes) -> int:
+    """The verdict of the lanes that ran; an image without a subsequence fails."""
+    return ERR_FORMAT if n_sub == 0 or bool(lane_failed[np.asarray(lanes, dtype=np.int64)].any()) else 0
+
+
+def _place(g: _Geometry, stores, lanes=None, band=None, cols=None, own: bool = True):
+    """Where every recorded store goes: (coefficients, write counts), both per component as (blocks high, blocks wide, 64), int16 and
+    int64, zero where nothing was stored.  Of `stores` (`_record_lanes`') those of the range `lanes` (of every lane's stores in the
+    natural order; None takes whatever lanes ran) whose MCU row passes the explicit range test of `band` = (a, b) and whose MCU
+    column that of `cols` = (c0, c1) are stored (None: every row, every column).  The layout is one of three.  `own`: an image that consists of the band's rows and the columns alone, luma first —
+    what jh_band_base and jh_window_base address.  Not `own`, with a band: the whole image, of which only the band's blocks are
+    stored — jh_rows_base.  Not `own`, without one: the whole image in full, which is also `own` of every row and column — what
+    `_Geometry.block` addresses.  A position that several stores reach holds the last one's value."""
+    if lanes is not None:                                                    # (recorded in the natural order: a slice)
+        first, last = np.searchsorted(stores[0], (lanes.start, lanes.stop))
+        stores = [v[first:last] for v in stores]
+    lane_of, my, mx, slot_of, z_of, value_of = stores
+    mcus_y = g.n_mcu // g.mcus_x
+    (a, b), (c0, c1) = band or (0, mcus_y), cols or (0, g.mcus_x)
+    keep = (my >= a) & (my < b) & (mx >= c0) & (mx < c1)
+    row0, rows, col0, wide = (a, b - a, c0, c1 - c0) if own else (0, mcus_y, 0, g.mcus_x)
+    # per slot of an MCU: the block of the image's first MCU, and the blocks from an MCU to the one below it and to its right
+    slots, comp, mcus = np.arange(g.nslots), np.array(g.comp, dtype=np.int64), rows * wide
+    origin = np.where(comp == 0, slots // g.h * (wide * g.h) + slots % g.h, mcus * g.h * g.v + (comp - 1) * mcus)
+    down, right = np.where(comp == 0, g.v * wide * g.h, wide), np.where(comp == 0, g.h, 1)
+    at = (64 * (origin[slot_of] + (my - row0) * down[slot_of] + (mx - col0) * right[slot_of]) + z_of)[keep]
+    dense = np.zeros(64 * mcus * g.nslots, dtype=np.int16)
+    dense[at] = value_of[keep]
+    writes = np.bincount(at, minlength=dense.size)
+    out, first = ([], []), 0
+    for c in range(g.nf):
+        high, across = rows * (g.v if c == 0 else 1), wide * (g.h if c == 0 else 1)
+        for flat, split in zip((dense, writes), out):
+            split.append(flat[64 * first:64 * (first + high * across)].reshape(high, across, 64))
+        first += high * across
+    return out
+
+
 def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: int, order=None, band=None, row_sub=None, cols=None):
     """The contract of `fear_jpeg_huffman_indexed`: (coefficients per component, status).  Every subsequence is decoded from its index
-    entry alone, in `order` (any permutation of the image's subsequences; the natural one by default), as one lane of
-    jpeg_huffman_indexed_kernel does it: the segment by a search of `sub_start`, the write pass's rules, and the verdict — the lane of a
-    segment's last subsequence judges the segment's block count, the lane of its first an empty segment in front, the lane of the
-    image's last subsequence empty segments behind, and an image without a subsequence fails.  Asserts that every position is written
+    entry alone, in `order` (any permutation of the image's subsequences; the natural one by default), as `_record_lanes` states a lane
+    of jpeg_huffman_indexed_kernel and its verdict, and an image without a subsequence fails.  Asserts that every position is written
     exactly once when the status is 0.
     With `band` = (a, b), MCU rows a .. b) clipped to the image, it is the contract of `fear_jpeg_huffman_indexed_rows`: only the
     subsequences row_sub[a] .. min(row_sub[b], n_sub - 1) are decoded (`row_sub` is `scan_row_sub`'s table, computed when None; `order`
@@ -464,106 +527,26 @@ def jpeg_entropy_indexed_host(data: bytes, sub_start, index, subsequence_bytes: 
     the band and its MCU column in the range, and the coefficients are the window's: per component the blocks of an image made of those
     (b - a) x (c1 - c0) MCUs alone."""
     _check_subsequence_bytes(subsequence_bytes)
-    data = bytes(data)
-    hd = _parse(data)
-    stream, seg_start = jpeg_scan_prepare_host(data, hd)
-    g = _Geometry(hd)
-    n_seg, n_sub, SB = len(seg_start) - 1, len(index), 8 * subsequence_bytes
-    sub_start = np.asarray(sub_start, dtype=np.int64)
-    assert sub_start.size == n_seg + 1 and int(sub_start[-1]) == n_sub
-    lanes, rows_band, n_values = range(n_sub), None, 64 * g.total_blocks
+    hd = _parse(bytes(data))
     if cols is not None and band is None:
         raise ValueError("cols go with a band")
+    lanes = range(len(index))
     if band is not None:
-        a = min(max(int(band[0]), 0), hd.mcus_y)
-        b = min(max(int(band[1]), a), hd.mcus_y)
+        band = _clipped(band, hd.mcus_y)
         if row_sub is None:
             row_sub = scan_row_sub(hd, sub_start, index)
-        rows_band, n_values = (a, b - a), 64 * (b - a) * g.mcus_x * g.nslots
-        lanes = range(int(row_sub[a]), min(int(row_sub[b]), n_sub - 1) + 1) if b > a else range(0)
-    window = None
+        lanes = _band_lanes(row_sub, band, len(index))
     if cols is not None:
-        c0 = min(max(int(cols[0]), 0), g.mcus_x)
-        c1 = min(max(int(cols[1]), c0), g.mcus_x)
-        window, n_values = (c0, c1 - c0), 64 * rows_band[1] * (c1 - c0) * g.nslots
-        lanes = window_lanes(hd, sub_start, index, np.arange(lanes.start, lanes.stop), (c0, c1)).tolist()
-    dense = np.zeros(n_values, dtype=np.int16)
-    writes = np.zeros(n_values, dtype=np.uint8)
-    segs = [_Segment(hd, g, stream, seg_start, s) for s in range(n_seg)]
-    status = ERR_FORMAT if n_sub == 0 else 0
-    for sub in (lanes if order is None else [lanes[int(k)] for k in order]):
-        sub = int(sub)
-        s = int(np.searchsorted(sub_start[:n_seg], sub, side="right")) - 1   # the last segment that starts at or in front of `sub`
-        sg, i, e = segs[s], sub - int(sub_start[s]), index[sub]
-        slot, z = min(int(e["sz"]) >> 8, g.nslots - 1), min(int(e["sz"]) & 255, 63)
-        pred = [int(v) for v in e["dc"]]
-        record = [] if window is not None else None                         # a window's stores are placed below, window-dense
-        state, begun, failed = _write_pass(sg, g, (int(e["p"]), slot, z), (i + 1) * SB, int(e["begun"]), pred,
-                                           None if window is not None else dense, writes, rows_band, record=record)
-        for mcu, at_slot, z0, z1, value in record or ():
-            b = g.window_block(mcu, at_slot, rows_band[0], rows_band[1], window[0], window[1])
-            if 0 <= b < rows_band[1] * window[1] * g.nslots:
-                dense[64 * b + z0:64 * b + z1] = value
-                writes[64 * b + z0:64 * b + z1] += 1
-        if (i + 1) * SB >= sg.L and begun - (state[2] != 0) < sg.expected:    # the segment's last subsequence: its block count
-            failed = True
-        if i == 0 and s > 0 and sub_start[s - 1] == sub_start[s]:            # an empty segment in front owes blocks
-            failed = True
-        if sub == n_sub - 1 and s != n_seg - 1:                              # empty segments behind the last subsequence
-            failed = True
-        if failed:
-            status = ERR_FORMAT
+        cols = _clipped(cols, hd.mcus_x)
+        lanes = window_lanes(hd, sub_start, index, np.arange(lanes.start, lanes.stop), cols).tolist()
+    if order is not None:
+        lanes = [lanes[int(k)] for k in order]
+    hd, g, n_sub, row_sub, lane_failed, stores = _record_lanes(data, sub_start, index, subsequence_bytes, row_sub, lanes)
+    coef, writes = _place(g, stores, None, band, cols)
+    status = _status(n_sub, lane_failed, lanes)
     if status == 0:
-        assert np.all(writes == 1), "every position of every block is written exactly once"
-    coef, at = [], 0
-    for c in range(g.nf):
-        high = hd.blocks_h[c] if rows_band is None else rows_band[1] * (g.v if c == 0 else 1)
-        wide = hd.blocks_w[c] if window is None else window[1] * (g.h if c == 0 else 1)
-        size = wide * high
-        coef.append(dense[64 * at:64 * (at + size)].reshape(high, wide, 64))
-        at += size
+        assert all(np.all(w == 1) for w in writes), "every position of every block is written exactly once"
     return coef, status
-
-
-def _record_lanes(data: bytes, sub_start, index, subsequence_bytes: int, row_sub=None):
-    """Every lane of the indexed decode once, whatever band is wanted (a lane's decode does not depend on it): the header, the geometry,
-    n_sub, the row table, each lane's verdict, and every store any lane would make, one array entry per coefficient position — the
-    lane, the MCU row and column, the slot, z and the value."""
-    _check_subsequence_bytes(subsequence_bytes)
-    data = bytes(data)
-    hd = _parse(data)
-    stream, seg_start = jpeg_scan_prepare_host(data, hd)
-    g = _Geometry(hd)
-    n_seg, n_sub, SB = len(seg_start) - 1, len(index), 8 * subsequence_bytes
-    sub_start = np.asarray(sub_start, dtype=np.int64)
-    if row_sub is None:
-        row_sub = scan_row_sub(hd, sub_start, index)
-    segs = [_Segment(hd, g, stream, seg_start, s) for s in range(n_seg)]
-    lane_failed = np.zeros(n_sub, dtype=bool)
-    lane_of, mcu_of, slot_of, z_of, value_of = [], [], [], [], []
-    for sub in range(n_sub):
-        s = int(np.searchsorted(sub_start[:n_seg], sub, side="right")) - 1
-        sg, i, e = segs[s], sub - int(sub_start[s]), index[sub]
-        slot, z = min(int(e["sz"]) >> 8, g.nslots - 1), min(int(e["sz"]) & 255, 63)
-        record = []
-        state, begun, failed = _write_pass(sg, g, (int(e["p"]), slot, z), (i + 1) * SB, int(e["begun"]), [int(v) for v in e["dc"]], None, None,
-                                           record=record)
-        if (i + 1) * SB >= sg.L and begun - (state[2] != 0) < sg.expected:
-            failed = True
-        if i == 0 and s > 0 and sub_start[s - 1] == sub_start[s]:
-            failed = True
-        if sub == n_sub - 1 and s != n_seg - 1:
-            failed = True
-        lane_failed[sub] = failed
-        for mcu, slot, z0, z1, value in record:
-            lane_of += [sub] * (z1 - z0)
-            mcu_of += [mcu] * (z1 - z0)
-            slot_of += [slot] * (z1 - z0)
-            z_of += range(z0, z1)
-            value_of += [value] * (z1 - z0)
-    lane_of, mcu_of, slot_of, z_of = (np.array(v, dtype=np.int64) for v in (lane_of, mcu_of, slot_of, z_of))
-    value_of = np.array(value_of, dtype=np.int64).astype(np.int16)
-    return hd, g, n_sub, row_sub, lane_failed, (lane_of, mcu_of // g.mcus_x, mcu_of % g.mcus_x, slot_of, z_of, value_of)
 
 
 def jpeg_entropy_bands_host(data: bytes, sub_start, index, subsequence_bytes: int, bands, row_sub=None):
@@ -572,36 +555,15 @@ def jpeg_entropy_bands_host(data: bytes, sub_start, index, subsequence_bytes: in
     would store; per band the stores of the lanes that run, row_sub[a] .. min(row_sub[b], n_sub - 1), whose MCU row passes the explicit
     range test a <= row < b are placed band-dense, and the lanes that do not run judge nothing.  Asserts that every position of a band
     is written exactly once when its status is 0."""
-    hd, g, n_sub, row_sub, lane_failed, (lane_of, my, mx, slot_of, z_of, value_of) = _record_lanes(data, sub_start, index, subsequence_bytes,
-                                                                                                     row_sub)
-    comp = np.array(g.comp, dtype=np.int64)[slot_of]
-    luma = comp == 0
-    j, i = np.where(luma, slot_of // g.h, 0), np.where(luma, slot_of % g.h, 0)
+    hd, g, n_sub, row_sub, lane_failed, stores = _record_lanes(data, sub_start, index, subsequence_bytes, row_sub)
     out = []
     for band in bands:
-        a = min(max(int(band[0]), 0), hd.mcus_y)
-        b = min(max(int(band[1]), a), hd.mcus_y)
-        band_mcus = (b - a) * g.mcus_x
-        n_values = 64 * band_mcus * g.nslots
-        first, last = (int(row_sub[a]), min(int(row_sub[b]), n_sub - 1)) if b > a else (0, -1)
-        ran = (lane_of >= first) & (lane_of <= last)
-        keep = ran & (my >= a) & (my < b)
-        ry = my[keep] - a
-        block = np.where(luma[keep], (ry * g.v + j[keep]) * (g.mcus_x * g.h) + mx[keep] * g.h + i[keep],
-                         band_mcus * g.h * g.v + (comp[keep] - 1) * band_mcus + ry * g.mcus_x + mx[keep])
-        at = 64 * block + z_of[keep]
-        status = ERR_FORMAT if n_sub == 0 or bool(lane_failed[first:last + 1].any()) else 0
-        dense = np.zeros(n_values, dtype=np.int16)
-        dense[at] = value_of[keep]
+        band = _clipped(band, hd.mcus_y)
+        lanes = _band_lanes(row_sub, band, n_sub)
+        coef, writes = _place(g, stores, lanes, band)
+        status = _status(n_sub, lane_failed, lanes)
         if status == 0:
-            assert np.array_equal(np.bincount(at, minlength=n_values), np.ones(n_values, dtype=np.int64)), \
-                "every position of the band is written exactly once"
-        coef, where = [], 0
-        for c in range(g.nf):
-            high = (b - a) * (g.v if c == 0 else 1)
-            size = hd.blocks_w[c] * high
-            coef.append(dense[64 * where:64 * (where + size)].reshape(high, hd.blocks_w[c], 64))
-            where += size
+            assert all(np.all(w == 1) for w in writes), "every position of the band is written exactly once"
         out.append((coef, status))
     return out
 
@@ -609,7 +571,7 @@ def jpeg_entropy_bands_host(data: bytes, sub_start, index, subsequence_bytes: in
 # -------------------------------------------------------------------------------------------------- the band of rows taken from the device
 def rows_band(y0: int, y1: int, limit: int, mcu_h: int, mcus_y: int, halo: bool):
     """The band of MCU rows (a, b) that covers the pixel rows [y0, y1) clipped to [0, limit], one MCU row more on each side with `halo`,
-    clipped to mcus_y; None for the empty band y0 >= y1 (jr_band in csrc/fear_jpeg_decode.h; `plan_decode_rows` states the same rule)."""
+    clipped to mcus_y; None for the empty band y0 >= y1 (jr_band in csrc/fear_jpeg_decode.h; `jpeg_store._cover` states the same rule over arrays, for the host's plans)."""
     y0, y1 = min(max(int(y0), 0), limit), min(max(int(y1), 0), limit)
     if y0 >= y1:
         return None
@@ -625,36 +587,13 @@ def jpeg_entropy_rows_device_many_host(data: bytes, sub_start, index, subsequenc
     them, zero where nothing was stored; `mask` has their shapes and counts the stores to each position: 1 on the band's blocks, 0
     elsewhere.  A lane that runs decodes and judges as `jpeg_entropy_indexed_host`'s, a block whose MCU row lies outside the band (an
     explicit range test) is not stored, and lanes that do not run judge nothing."""
-    hd, g, n_sub, row_sub, lane_failed, (lane_of, my, mx, slot_of, z_of, value_of) = _record_lanes(data, sub_start, index, subsequence_bytes,
-                                                                                                     row_sub)
-    comp = np.array(g.comp, dtype=np.int64)[slot_of]
-    luma = comp == 0
-    j, i = np.where(luma, slot_of // g.h, 0), np.where(luma, slot_of % g.h, 0)
-    first_of = np.array(g.comp_first, dtype=np.int64)[comp]
-    wide = np.array(g.blocks_w, dtype=np.int64)[comp]
-    block = first_of + np.where(luma, (my * g.v + j) * wide + mx * g.h + i, my * wide + mx)     # jh_block_base
-    at_all = 64 * block + z_of
-    mcu_h, n_values = 8 * g.v, 64 * g.total_blocks
-    out = []
+    hd, g, n_sub, row_sub, lane_failed, stores = _record_lanes(data, sub_start, index, subsequence_bytes, row_sub)
+    mcu_h, out = 8 * g.v, []
     for y0, y1 in windows:
-        band = rows_band(y0, y1, mcu_h * hd.mcus_y, mcu_h, hd.mcus_y, g.v == 2)
-        dense, writes = np.zeros(n_values, dtype=np.int16), np.zeros(n_values, dtype=np.int64)
-        lanes, status = range(0), (ERR_FORMAT if n_sub == 0 else 0)
-        if band is not None and n_sub:
-            a, b = band
-            lanes = range(int(row_sub[a]), min(int(row_sub[b]), n_sub - 1) + 1)
-            keep = (lane_of >= lanes.start) & (lane_of < lanes.stop) & (my >= a) & (my < b) & (block < g.total_blocks)
-            dense[at_all[keep]] = value_of[keep]
-            writes = np.bincount(at_all[keep], minlength=n_values)
-            if lane_failed[lanes.start:lanes.stop].any():
-                status = ERR_FORMAT
-        coef, mask, at = [], [], 0
-        for c in range(g.nf):
-            size = hd.blocks_w[c] * hd.blocks_h[c]
-            coef.append(dense[64 * at:64 * (at + size)].reshape(hd.blocks_h[c], hd.blocks_w[c], 64))
-            mask.append(writes[64 * at:64 * (at + size)].reshape(hd.blocks_h[c], hd.blocks_w[c], 64))
-            at += size
-        out.append((lanes, coef, mask, status))
+        band = rows_band(y0, y1, mcu_h * hd.mcus_y, mcu_h, hd.mcus_y, g.v == 2) or (0, 0)
+        lanes = _band_lanes(row_sub, band, n_sub)
+        coef, mask = _place(g, stores, lanes, band, own=False)
+        out.append((lanes, coef, mask, _status(n_sub, lane_failed, lanes)))
     return out
 
 

@@ -18,7 +18,7 @@ only kernels read: `plan_decode`'s full-image plan, `fear_jpeg_huffman_indexed_r
 workgroups outside the band return early — for which `add` keeps each file's row table on the device as well ("Rows
 from the device").  `StoreFrames(store, ids)` names a sequence of frames kept in a store, for `SequenceValidator`.
 
-`decode`, `decode_rows` (rows on the host), `shape` and the two plans take `scale` 2, 4 or 8: the frames at 1/2, 1/4 or 1/8 size, decoded
+`decode`, `decode_rows` (rows on the host), `shape` and the plans take `scale` 2, 4 or 8: the frames at 1/2, 1/4 or 1/8 size, decoded
 in the DCT domain as libjpeg's scale_denom does, with `fear_jpeg_decode_scaled_u8` in place of `fear_jpeg_decode_u8` behind the same
 Huffman stage ("Reduced-size decoding").  `scale` may also be a sequence, one scale of {1, 2, 4, 8} per
 position of the call: item i is then what the uniform call at its scale returns, a group whose scales differ runs
@@ -28,10 +28,15 @@ takes it too ("A scale per position").
 A batch of training pairs reads a rectangle of a frame, not its whole rows.  `JpegStore.decode_windows` decodes per frame the MCUs that
 cover one rectangle — `plan_decode_windows` on the host, `fear_jpeg_huffman_indexed_windows`, whose lanes of the band that cannot touch
 the rectangle's MCU columns return early and which stores the blocks window-dense, and the unchanged pixel kernels on the window as an
-image of its own — and returns COMPACT frames with their origins, a `WindowFrames` ("Windows")."""
+image of its own — and returns COMPACT frames with their origins, a `WindowFrames` ("Windows").
+
+The three plans are one plan over shared parts: the units that cover a request (`_cover`, for MCU rows and MCU columns alike), a band's
+lanes (`_band_lanes`), what a run of units spans of the image (`_extent`), and the groups of a call (`_groups`: the cut, the layout and
+what each group carries).  `add` is a sequence of stages over one `_Entry` per file, of which the last alone assigns to the store."""
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -88,19 +93,61 @@ def plan_decode(columns: np.ndarray, ids, workspace_limit: int, max_group: int =
     is_scan = rows["kind"] == KIND_SCAN
     blocks = rows["total_blocks"].astype(np.int64)
     high, wide = _scaled_sides(rows["H"], rows["W"], scale)
-    pixels, n_sub = high * wide, rows["n_sub"].astype(np.int64)
+    pixels = high * wide
+    return _groups(is_scan, np.where(is_scan, blocks, 0), rows["n_sub"].astype(np.int64), pixels, pixels, workspace_limit, max_group, scale)
+
+
+def _groups(some: np.ndarray, blocks: np.ndarray, lanes: np.ndarray, pixels: np.ndarray, frame_pixels: np.ndarray, workspace_limit: int,
+            max_group: int, scale, picked: dict = {}, sliced: dict = {}) -> List[dict]:   # (the defaults are only read)
+    """The groups of all three plans, from per-position arrays.  Position k decodes an image of `blocks[k]` blocks (0 where it decodes
+    none) and `pixels[k]` pixels with `lanes[k]` lanes, where `some[k]`, into a frame of `frame_pixels[k]` pixels.  `_cut` cuts the
+    call by the dense coefficients, 128 bytes per block; a group carries lo, hi, `scan` (its positions with `some`, relative to lo),
+    `sub_prefix`, `_layout`'s entries, `scales` with a scale per position, every array of `picked` (by name) over its "scan" positions
+    and every array of `sliced` over lo:hi."""
     groups = []
-    for lo, hi in _cut(np.where(is_scan, 128 * blocks, 0), workspace_limit, max_group):
-        scan = np.flatnonzero(is_scan[lo:hi])
+    for lo, hi in _cut(128 * blocks, workspace_limit, max_group):
+        scan = np.flatnonzero(some[lo:hi])
         pick = lo + scan
-        groups.append(dict(lo=lo, hi=hi, scan=scan, sub_prefix=_exclusive(-(-n_sub[pick] // LANES)).astype(np.uint32),
-                           **_layout(blocks[pick], pixels[pick], pixels[lo:hi]), **_group_scales(scale, pick)))
+        group = dict(lo=lo, hi=hi, scan=scan, sub_prefix=_exclusive(-(-lanes[pick] // LANES)).astype(np.uint32),
+                     **_layout(blocks[pick], pixels[pick], frame_pixels[lo:hi]))
+        if not isinstance(scale, int):
+            group["scales"] = scale[pick]
+        for name, v in picked.items():
+            group[name] = v[pick]
+        for name, v in sliced.items():
+            group[name] = v[lo:hi]
+        groups.append(group)
     return groups
 
 
-def _group_scales(scale, pick: np.ndarray) -> dict:
-    """What a group of a plan with a scale per position carries more: `scales`, those of its "scan" positions.  Nothing for an int."""
-    return {} if isinstance(scale, int) else dict(scales=scale[pick])
+def _cover(lo: np.ndarray, hi: np.ndarray, size: np.ndarray, count: np.ndarray, halo: np.ndarray, some: np.ndarray):
+    """The units first .. last) of `size` that cover [lo, hi), `halo` (0 or 1) more on each side, clipped to the `count` there are;
+    0, 0 where not `some`.  One rule for MCU rows under pixel rows and MCU columns under pixel columns; `jpeg_huffman.rows_band` is its
+    scalar statement."""
+    return np.where(some, np.maximum(lo // size - halo, 0), 0), np.where(some, np.minimum(-(-hi // size) + halo, count), 0)
+
+
+def _extent(begin: np.ndarray, end: np.ndarray, unit: np.ndarray, limit: np.ndarray) -> np.ndarray:
+    """What the units begin .. end) of `unit` pixels span of a side of `limit` pixels: min(end unit, limit) - begin unit, the run cut
+    at the image's true edge.  With the scaled or the full-size unit and side, of a band's rows or a window's columns."""
+    return np.minimum(end * unit, limit) - begin * unit
+
+
+def _band_lanes(row_sub: np.ndarray, row_at: np.ndarray, a: np.ndarray, b: np.ndarray, n_sub: np.ndarray, some: np.ndarray):
+    """The lanes of the bands a .. b): `first` = row_sub[a] and `count` up to min(row_sub[b], n_sub - 1), of the entries whose row
+    tables begin at `row_at` in the ragged `row_sub`; 0, 0 where not `some`, and everywhere while no entry has a row table."""
+    if not row_sub.size:
+        return np.zeros(a.size, np.int64), np.zeros(a.size, np.int64)
+    at = np.where(some, row_at, 0)
+    first = np.where(some, row_sub[at + a].astype(np.int64), 0)
+    last = np.where(some, np.minimum(row_sub[at + b].astype(np.int64), n_sub - 1), -1)
+    return first, np.maximum(last - first + 1, 0)
+
+
+def _mcu_width(nslots: np.ndarray, mcu_h: np.ndarray) -> np.ndarray:
+    """An MCU's width in pixels from what the mirror holds: a colour MCU has h v + 2 blocks and is `mcu_h` = 8 v rows high, a gray one
+    is one block."""
+    return np.where(nslots > 1, 8 * np.maximum((nslots - 2) // (mcu_h // 8).clip(1), 1), 8)
 
 
 def _scaled_sides(H, W, scale):
@@ -173,31 +220,14 @@ def plan_decode_rows(columns: np.ndarray, row_sub: np.ndarray, ids, rows, worksp
     mcus_y = col["mcus_y"].astype(np.int64)
     y0, y1 = np.clip(rows[:, 0], 0, H), np.clip(rows[:, 1], 0, H)
     some = is_scan & (y0 < y1)
-    halo = col["halo"].astype(np.int64) * (m == 8)
-    a = np.where(some, np.maximum(y0 // mcu_h - halo, 0), 0)
-    b = np.where(some, np.minimum(-(-y1 // mcu_h) + halo, mcus_y), 0)
+    a, b = _cover(y0, y1, mcu_h, mcus_y, col["halo"].astype(np.int64) * (m == 8), some)
     blocks = (b - a) * col["mcus_x"].astype(np.int64) * col["nslots"].astype(np.int64)
+    first, count = _band_lanes(row_sub, col["row_at"], a, b, col["n_sub"].astype(np.int64), some)
     band_y0 = a * mcu_h
-    band_h = np.minimum(b * mcu_h, H) - band_y0
-    band_full = np.minimum(b * full_mcu_h, full_h) - a * full_mcu_h
-    n_sub = col["n_sub"].astype(np.int64)
-    at = np.where(some, col["row_at"], 0)
-    first = np.where(some, row_sub[at + a].astype(np.int64), 0) if row_sub.size else np.zeros(ids.size, np.int64)
-    last = np.where(some, np.minimum(row_sub[at + b].astype(np.int64), n_sub - 1), -1) if row_sub.size else np.full(ids.size, -1, np.int64)
-    count = np.maximum(last - first + 1, 0)
-    pixels = H * W
-    groups = []
-    for lo, hi in _cut(128 * blocks, workspace_limit, max_group):
-        scan = np.flatnonzero(some[lo:hi])
-        pick = lo + scan
-        groups.append(dict(
-            lo=lo, hi=hi, scan=scan,
-            sub0=first[pick].astype(np.uint32), sub_count=count[pick].astype(np.uint32),
-            sub_prefix=_exclusive(-(-count[pick] // LANES)).astype(np.uint32),
-            mcu_row0=a[pick].astype(np.uint32), mcu_rows=(b - a)[pick].astype(np.uint32),
-            band_y0=band_y0[pick], band_height=band_full[pick].astype(np.int32), band_out=3 * W[pick] * band_y0[pick],
-            **_layout(blocks[pick], band_h[pick] * W[pick], pixels[lo:hi]), **_group_scales(scale, pick)))
-    return groups
+    picked = dict(sub0=first.astype(np.uint32), sub_count=count.astype(np.uint32), mcu_row0=a.astype(np.uint32),
+                  mcu_rows=(b - a).astype(np.uint32), band_y0=band_y0, band_height=_extent(a, b, full_mcu_h, full_h).astype(np.int32),
+                  band_out=3 * W * band_y0)
+    return _groups(some, blocks, count, _extent(a, b, mcu_h, H) * W, H * W, workspace_limit, max_group, scale, picked)
 
 
 def plan_decode_windows(columns: np.ndarray, row_sub: np.ndarray, ids, windows, workspace_limit: int, max_group: int = 65535,
@@ -236,9 +266,8 @@ def plan_decode_windows(columns: np.ndarray, row_sub: np.ndarray, ids, windows, 
     is_scan = col["kind"] == KIND_SCAN
     full_h, full_w = col["H"].astype(np.int64), col["W"].astype(np.int64)
     full_mcu_h = np.maximum(col["mcu_h"].astype(np.int64), 1)
-    # an MCU's width, from what the mirror holds: a colour MCU has h v + 2 blocks and is 8 v rows high, a gray one is one block
     nslots = col["nslots"].astype(np.int64)
-    full_mcu_w = np.where(nslots > 1, 8 * np.maximum((nslots - 2) // (full_mcu_h // 8).clip(1), 1), 8)
+    full_mcu_w = _mcu_width(nslots, full_mcu_h)
     H, W = _scaled_sides(full_h, full_w, scale)
     mcu_h, mcu_w = np.maximum(full_mcu_h * m // 8, 1), np.maximum(full_mcu_w * m // 8, 1)
     mcus_y, mcus_x = col["mcus_y"].astype(np.int64), col["mcus_x"].astype(np.int64)
@@ -246,41 +275,21 @@ def plan_decode_windows(columns: np.ndarray, row_sub: np.ndarray, ids, windows, 
     x0, x1 = np.clip(win[:, 2], 0, W), np.clip(win[:, 3], 0, W)
     filled = (y0 < y1) & (x0 < x1)
     some = is_scan & filled
-    halo_y = col["halo"].astype(np.int64) * (m == 8)
-    halo_x = (full_mcu_w == 16).astype(np.int64)
-    a = np.where(some, np.maximum(y0 // mcu_h - halo_y, 0), 0)
-    b = np.where(some, np.minimum(-(-y1 // mcu_h) + halo_y, mcus_y), 0)
-    c0 = np.where(some, np.maximum(x0 // mcu_w - halo_x, 0), 0)
-    c1 = np.where(some, np.minimum(-(-x1 // mcu_w) + halo_x, mcus_x), 0)
+    a, b = _cover(y0, y1, mcu_h, mcus_y, col["halo"].astype(np.int64) * (m == 8), some)
+    c0, c1 = _cover(x0, x1, mcu_w, mcus_x, (full_mcu_w == 16).astype(np.int64), some)
     blocks = (b - a) * (c1 - c0) * nslots
-    high = np.minimum(b * mcu_h, H) - a * mcu_h
-    wide = np.minimum(c1 * mcu_w, W) - c0 * mcu_w
-    high_full = np.minimum(b * full_mcu_h, full_h) - a * full_mcu_h
-    wide_full = np.minimum(c1 * full_mcu_w, full_w) - c0 * full_mcu_w
-    n_sub = col["n_sub"].astype(np.int64)
-    at = np.where(some, col["row_at"], 0)
-    first = np.where(some, row_sub[at + a].astype(np.int64), 0) if row_sub.size else np.zeros(ids.size, np.int64)
-    last = np.where(some, np.minimum(row_sub[at + b].astype(np.int64), n_sub - 1), -1) if row_sub.size else np.full(ids.size, -1, np.int64)
-    count = np.maximum(last - first + 1, 0)
+    first, count = _band_lanes(row_sub, col["row_at"], a, b, col["n_sub"].astype(np.int64), some)
     kept = ~is_scan & filled                                             # an entry kept as pixels hands out the rectangle itself
     origin = np.stack([np.where(kept, y0, a * mcu_h), np.where(kept, x0, c0 * mcu_w)], axis=1).astype(np.int32)
-    high, wide = np.where(kept, y1 - y0, high), np.where(kept, x1 - x0, wide)
+    high, wide = np.where(kept, y1 - y0, _extent(a, b, mcu_h, H)), np.where(kept, x1 - x0, _extent(c0, c1, mcu_w, W))
     window = np.where(filled[:, None], np.stack([y0, y1, x0, x1], axis=1), 0)
-    groups = []
-    for lo, hi in _cut(128 * blocks, workspace_limit, max_group):
-        scan = np.flatnonzero(some[lo:hi])
-        pick = lo + scan
-        groups.append(dict(
-            lo=lo, hi=hi, scan=scan,
-            sub0=first[pick].astype(np.uint32), sub_count=count[pick].astype(np.uint32),
-            sub_prefix=_exclusive(-(-count[pick] // LANES)).astype(np.uint32),
-            mcu_row0=a[pick].astype(np.uint32), mcu_rows=(b - a)[pick].astype(np.uint32),
-            cols=(c0[pick] | (c1 - c0)[pick] << 16).astype(np.uint32),
-            band_height=high_full[pick].astype(np.int32), win_width=wide_full[pick].astype(np.int32),
-            band_out=np.zeros(pick.size, dtype=np.int64),
-            origin=origin[lo:hi], high=high[lo:hi], wide=wide[lo:hi], window=window[lo:hi],
-            **_layout(blocks[pick], high[pick] * wide[pick], (high * wide)[lo:hi]), **_group_scales(scale, pick)))
-    return groups
+    picked = dict(sub0=first.astype(np.uint32), sub_count=count.astype(np.uint32), mcu_row0=a.astype(np.uint32),
+                  mcu_rows=(b - a).astype(np.uint32), cols=(c0 | (c1 - c0) << 16).astype(np.uint32),
+                  band_height=_extent(a, b, full_mcu_h, full_h).astype(np.int32),
+                  win_width=_extent(c0, c1, full_mcu_w, full_w).astype(np.int32), band_out=np.zeros(ids.size, dtype=np.int64))
+    pixels = high * wide
+    return _groups(some, blocks, count, pixels, pixels, workspace_limit, max_group, scale, picked,
+                   dict(origin=origin, high=high, wide=wide, window=window))
 
 
 def _place_images(images: np.ndarray, coef, coef_offset: np.ndarray, block_start, out, out_offset: np.ndarray, plane_offset: np.ndarray) -> None:
@@ -295,6 +304,28 @@ def _place_images(images: np.ndarray, coef, coef_offset: np.ndarray, block_start
 def _frame_views(out, out_offset: np.ndarray, high: np.ndarray, wide: np.ndarray) -> List:
     """The frames in a group's output: frame k is `high[k]` x `wide[k]` x 3 bytes from `out_offset[k]`."""
     return [out[at:at + 3 * h * w].view(h, w, 3) for at, h, w in zip(out_offset.tolist(), high.tolist(), wide.tolist())]
+
+
+@dataclasses.dataclass
+class _Entry:
+    """One "scan" file of an `add` on its way into the store: what `scan_prepare` made of it (info, data, seg, scan), its `sub_start`,
+    its resident layout (where seg_start, sub_start, the index and the FearJpegScan record begin behind the bytes, and the `end`),
+    its place (`at` in `slab`, the address `base`), its row table and the address of the table's copy on the device."""
+    info: object
+    data: np.ndarray
+    seg: np.ndarray
+    scan: object
+    sub: Optional[np.ndarray] = None
+    at_seg: int = 0
+    at_sub: int = 0
+    at_index: int = 0
+    at_record: int = 0
+    end: int = 0
+    base: int = 0
+    slab: object = None
+    at: int = 0
+    row_table: Optional[np.ndarray] = None
+    row_dev_at: int = 0
 
 
 class JpegStore:
@@ -434,188 +465,218 @@ class JpegStore:
     # -------------------------------------------------------------------------------------------------------------------------- add
     def add(self, items: Sequence[Item], fallback: Optional[Callable[[bytes], np.ndarray]] = None) -> np.ndarray:
         import torch
-        from . import train_abi as abi
         blobs = _read_items(items)
         n = len(blobs)
         if n == 0:
             return np.zeros(0, dtype=np.int64)
-        SBY, limit = self.subsequence_bytes, jpeg_frames.DEVICE_SCAN_MAX
+        # every stage in front of `_add_commit` returns values and assigns nothing on self: a call that raises commits nothing
+        entries, through_host, raw = self._add_prepare(blobs, fallback)
+        split = self._add_layout(entries, through_host, raw, n)
+        with torch.cuda.device(self.device):
+            new_slabs, open_slab, cursor, runs = self._add_place(entries)
+            self._add_upload(runs)
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            new_borders = torch.zeros((n, 3), dtype=torch.uint8, device=self.device)
+            self._add_verdicts(self._add_index(entries, new_borders, stream), blobs)
+            pixels = self._add_pixels(blobs, through_host, raw, new_borders, stream)
+            row_dev = self._add_row_tables(entries)
+            border = self._add_border(self._n + n)
+            torch.cuda.current_stream().synchronize()                    # what was stored is complete for a decode on any stream
+        return self._add_commit(n, entries, pixels, split, new_slabs, open_slab, cursor, row_dev, border, new_borders)
+
+    def _add_prepare(self, blobs: List[bytes], fallback):
+        """Stage 1 of `add`: transcode (a progressive file takes its baseline transcode's place in `blobs`) and prepare on the pool, then
+        judge every file before anything is stored.  The "scan" files as {item: _Entry}, the infos of those whose largest restart
+        segment exceeds DEVICE_SCAN_MAX, and the fallback's pixels, by item."""
         declined = {}
-        if self.progressive:                                             # a progressive file is replaced by its baseline transcode
+        if self.progressive:
             for i, res in enumerate(self._host._pool.map(self._transcode, blobs)):
                 if isinstance(res, bytes):
                     blobs[i] = res
                 elif res is not None:
                     declined[i] = res                                    # the original goes to the fallback, or raises
         prepared = list(self._host._pool.map(self._host.scan_prepare, blobs))
-        # every file is judged before anything is stored (a file the transcoder declined: by the transcoder's status)
+        # (a file the transcoder declined is judged by the transcoder's status)
         jpegs, raw = _judge(blobs, [declined.get(i, res) for i, res in enumerate(prepared)], fallback, self.progressive, name_item=True)
-        scans = [i for i in jpegs if prepared[i][3].max_seg_bytes <= limit]
-        through_host = [i for i in jpegs if prepared[i][3].max_seg_bytes > limit]
-        # the resident layout of every "scan" file, from its base: bytes | seg_start | sub_start | index | FearJpegScan, each at 16 bytes
-        layout, split, need = {}, dict(bytes=0, index=0, records=0, pixels=0, rows=0, border=3 * n), 0
-        for i in scans:
-            info, data, seg, scan = prepared[i]
-            sub, count = np.empty(seg.size, dtype=np.uint32), ctypes.c_uint32(0)
-            rc = self._lib.fear_jpeg_sub_start(seg.ctypes.data, scan.n_seg, scan.n_bytes, SBY, sub.ctypes.data, sub.size, ctypes.byref(count))
-            if rc != 0 or count.value != int(sub[-1]):
+        entries = {i: _Entry(*prepared[i]) for i in jpegs if prepared[i][3].max_seg_bytes <= jpeg_frames.DEVICE_SCAN_MAX}
+        return entries, {i: prepared[i][0] for i in jpegs if i not in entries}, raw
+
+    def _add_layout(self, entries: dict, through_host: dict, raw: dict, n: int) -> dict:
+        """Stage 2: every entry's `sub_start` and resident layout from its base — bytes | seg_start | sub_start | index | FearJpegScan,
+        each at 16 bytes — and what the call adds to `resident`, key by key; `StoreFull` where that exceeds the capacity."""
+        from . import train_abi as abi
+        record = ctypes.sizeof(abi.FearJpegScan)
+        split = dict(bytes=0, index=0, records=0, pixels=0, rows=0, border=3 * n)
+        for e in entries.values():
+            e.sub, count = np.empty(e.seg.size, dtype=np.uint32), ctypes.c_uint32(0)
+            rc = self._lib.fear_jpeg_sub_start(e.seg.ctypes.data, e.scan.n_seg, e.scan.n_bytes, self.subsequence_bytes, e.sub.ctypes.data,
+                                               e.sub.size, ctypes.byref(count))
+            if rc != 0 or count.value != int(e.sub[-1]):
                 raise abi.TrainError(f"fear_jpeg_sub_start failed with status {rc}")
-            at_seg = _up(max(data.nbytes, 1), 16)
-            at_sub = at_seg + _up(seg.nbytes, 16)
-            at_index = at_sub + _up(sub.nbytes, 16)
-            at_record = at_index + 16 * int(sub[-1])
-            layout[i] = (sub, at_seg, at_sub, at_index, at_record, at_record + ctypes.sizeof(abi.FearJpegScan))
-            split["bytes"] += at_index
-            split["index"] += at_record - at_index
-            split["records"] += ctypes.sizeof(abi.FearJpegScan)
-            split["rows"] += 4 * (int(info.mcus_y) + 1)
-        for i in through_host:
-            split["pixels"] += 3 * prepared[i][0].width * prepared[i][0].height
-        for px in raw.values():
-            split["pixels"] += px.nbytes
+            e.at_seg = _up(max(e.data.nbytes, 1), 16)
+            e.at_sub = e.at_seg + _up(e.seg.nbytes, 16)
+            e.at_index = e.at_sub + _up(e.sub.nbytes, 16)
+            e.at_record = e.at_index + 16 * int(e.sub[-1])
+            e.end = e.at_record + record
+            split["bytes"] += e.at_index
+            split["index"] += e.at_record - e.at_index
+            split["records"] += record
+            split["rows"] += 4 * (int(e.info.mcus_y) + 1)
+        split["pixels"] = sum(3 * info.width * info.height for info in through_host.values()) + sum(px.nbytes for px in raw.values())
         need = sum(split.values())
         if self.capacity_bytes is not None and self.nbytes + need > self.capacity_bytes:
             raise StoreFull(f"{need} bytes more on top of {self.nbytes} exceed the capacity of {self.capacity_bytes}")
-        with torch.cuda.device(self.device):
-            # place: tentative cursors, committed at the end
-            new_slabs, open_slab, cursor, base, runs, placed, first_new = [], self._open, self._cursor, {}, [], {}, self._n
-            for i in scans:
-                size = layout[i][5]
-                if size > self.slab_bytes:                               # a slab of its own; the open slab stays open
-                    slab, at = torch.empty(size, dtype=torch.uint8, device=self.device), 0
-                    new_slabs.append(slab)
-                else:
-                    if open_slab is None or cursor + size > self.slab_bytes:
-                        open_slab, cursor = torch.empty(self.slab_bytes, dtype=torch.uint8, device=self.device), 0
-                        new_slabs.append(open_slab)
-                    slab, at = open_slab, cursor
-                    cursor += size
-                assert slab.data_ptr() % 16 == 0
-                base[i] = slab.data_ptr() + at
-                placed[i] = (slab, at)
-                if runs and runs[-1][0] is slab and runs[-1][1] + runs[-1][2] == at:
-                    runs[-1][2] += size
-                    runs[-1][3].append(i)
-                else:
-                    runs.append([slab, at, size, [i]])
-            # upload: one copy per run of neighbours in a slab
-            for slab, at, size, members in runs:
-                host, w = np.zeros(size, dtype=np.uint8), 0
-                for i in members:
-                    info, data, seg, scan = prepared[i]
-                    sub, at_seg, at_sub, at_index, at_record, end = layout[i]
-                    scan.bytes, scan.seg_start, scan.coef_offset = base[i], base[i] + at_seg, 0
-                    host[w:w + data.nbytes] = data
-                    host[w + at_seg:w + at_seg + seg.nbytes] = seg.view(np.uint8)
-                    host[w + at_sub:w + at_sub + sub.nbytes] = sub.view(np.uint8)
-                    host[w + at_record:w + end] = np.frombuffer(scan, dtype=np.uint8)
-                    w += end
-                slab[at:at + size].copy_(torch.from_numpy(host))
-            # the index, in groups bounded by the scratch coefficients
-            groups, dense = [[]], 0
-            for i in scans:
-                want = 128 * int(prepared[i][0].total_blocks)
-                if groups[-1] and (dense + want > self.workspace_limit or len(groups[-1]) == 65535):
-                    groups.append([])
-                    dense = 0
-                groups[-1].append(i)
-                dense += want
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            verdicts, index_back = [], []
-            new_borders = torch.zeros((n, 3), dtype=torch.uint8, device=self.device)
-            for group in groups:
-                m = len(group)
-                if m == 0:
-                    continue
-                records, indexes = (abi.FearJpegScan * m)(), (abi.FearJpegIndex * m)()
-                prefix, values = np.zeros(m + 1, dtype=np.uint32), 0
-                for k, i in enumerate(group):
-                    info, data, seg, scan = prepared[i]
-                    sub, at_seg, at_sub, at_index, at_record, end = layout[i]
-                    ctypes.memmove(ctypes.byref(records[k]), ctypes.byref(scan), ctypes.sizeof(scan))
-                    records[k].coef_offset = values
-                    values += 64 * int(info.total_blocks)
-                    prefix[k + 1] = prefix[k] + scan.n_seg
-                    ix = indexes[k]
-                    ix.index, ix.sub_start, ix.seg_start_host, ix.n_sub = base[i] + at_index, base[i] + at_sub, seg.ctypes.data, int(sub[-1])
-                records_at = _up(prefix.nbytes, 16)
-                index_at = records_at + ctypes.sizeof(records)
-                table = np.zeros(index_at + ctypes.sizeof(indexes), dtype=np.uint8)
-                table[:prefix.nbytes] = prefix.view(np.uint8)
-                table[records_at:index_at] = np.frombuffer(records, dtype=np.uint8)
-                table[index_at:] = np.frombuffer(indexes, dtype=np.uint8)
-                dev = torch.from_numpy(table).to(self.device)
-                coef = torch.empty(max(values, 8), dtype=torch.int16, device=self.device)
-                status = torch.empty(m, dtype=torch.int32, device=self.device)
-                abi.launch(self._lib, "fear_jpeg_index_build", records, m, ctypes.c_void_p(dev.data_ptr()), indexes,
-                           ctypes.c_void_p(dev.data_ptr() + index_at), ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(status.data_ptr()),
-                           SBY, stream)
-                verdicts.append((group, status, dev, coef))
-                new_borders[group] = self._group_borders([prepared[i][0] for i in group], records, coef, stream)
-                index_back.append((group, [base[i] for i in group]))
-            for group, status, _, _ in verdicts:
-                got = status.cpu().numpy()                               # add waits: set-up
-                for k in np.flatnonzero(got):
-                    i = group[int(k)]
-                    try:
-                        _raise_as_python(blobs[i], int(got[k]))
-                    except MalformedJPEG as exc:
-                        raise MalformedJPEG(f"item {i}: {exc}") from None
-            pixels = {}
-            for i in through_host:                                       # once through the host's Huffman stage; it judges the file itself
-                try:
-                    pixels[i] = self._host.decode([blobs[i]])[0].clone()
-                except (MalformedJPEG, UnsupportedJPEG) as exc:
-                    raise type(exc)(f"item {i}: {exc}") from None
-            for i, px in raw.items():
-                pixels[i] = torch.from_numpy(px.copy()).to(self.device)         # (the fallback's array may be read-only)
-            if pixels:                                                   # the border colour of the entries kept as pixels
-                kept = sorted(pixels)
-                new_borders[kept] = self._frame_borders([pixels[i] for i in kept], stream)
-            # the row tables, from the index the device has just written: copied back once, add waits anyway
-            row_tables = {}
-            for i in scans:
-                sub, at_seg, at_sub, at_index, at_record, end = layout[i]
-                slab, at = placed[i]
-                index = slab[at + at_index:at + at_record].cpu().numpy().view(SUBSEQ_DTYPE)
-                row_tables[i] = self._row_table(prepared[i][0], sub, index)
-            row_at, row_dev = {}, None                                   # and once more on the device, for rows that only the device knows
-            if scans:
-                at = _exclusive(np.array([row_tables[i].size for i in scans], dtype=np.int64))
-                row_dev = torch.from_numpy(np.concatenate([row_tables[i] for i in scans]).astype(np.uint32).view(np.int32)).to(self.device)
-                row_at = {i: row_dev.data_ptr() + 4 * int(at[k]) for k, i in enumerate(scans)}
-            border = self._border                                        # grown here, committed below
-            if border is None or border.shape[0] < first_new + n:
-                have = max(self._initial_rows, 1) if border is None else border.shape[0]
-                while have < first_new + n:
-                    have *= 2
-                border = torch.zeros((have, 3), dtype=torch.uint8, device=self.device)
-                if self._border is not None and first_new:
-                    border[:first_new] = self._border[:first_new]
-                grown_border = True
+        return split
+
+    def _add_place(self, entries: dict):
+        """Stage 3: a place in a slab for every entry, from tentative cursors, and the runs of neighbours in a slab: the new slabs,
+        the open slab and its cursor as the commit will set them, and the runs, each a list of entries."""
+        import torch
+        new_slabs, open_slab, cursor, runs = [], self._open, self._cursor, []
+        for e in entries.values():
+            if e.end > self.slab_bytes:                                  # a slab of its own; the open slab stays open
+                e.slab, e.at = torch.empty(e.end, dtype=torch.uint8, device=self.device), 0
+                new_slabs.append(e.slab)
             else:
-                grown_border = False
-            torch.cuda.current_stream().synchronize()                    # what was stored is complete for a decode on any stream
-        # commit
+                if open_slab is None or cursor + e.end > self.slab_bytes:
+                    open_slab, cursor = torch.empty(self.slab_bytes, dtype=torch.uint8, device=self.device), 0
+                    new_slabs.append(open_slab)
+                e.slab, e.at = open_slab, cursor
+                cursor += e.end
+            assert e.slab.data_ptr() % 16 == 0
+            e.base = e.slab.data_ptr() + e.at
+            if runs and runs[-1][-1].slab is e.slab and runs[-1][-1].at + runs[-1][-1].end == e.at:
+                runs[-1].append(e)
+            else:
+                runs.append([e])
+        return new_slabs, open_slab, cursor, runs
+
+    def _add_upload(self, runs: List[list]) -> None:
+        """Stage 4: one copy per run of neighbours in a slab."""
+        import torch
+        for run in runs:
+            host, w = np.zeros(sum(e.end for e in run), dtype=np.uint8), 0
+            for e in run:
+                e.scan.bytes, e.scan.seg_start, e.scan.coef_offset = e.base, e.base + e.at_seg, 0
+                host[w:w + e.data.nbytes] = e.data
+                host[w + e.at_seg:w + e.at_seg + e.seg.nbytes] = e.seg.view(np.uint8)
+                host[w + e.at_sub:w + e.at_sub + e.sub.nbytes] = e.sub.view(np.uint8)
+                host[w + e.at_record:w + e.end] = np.frombuffer(e.scan, dtype=np.uint8)
+                w += e.end
+            run[0].slab[run[0].at:run[0].at + host.size].copy_(torch.from_numpy(host))
+
+    def _add_index(self, entries: dict, new_borders, stream) -> List[tuple]:
+        """Stage 5: `fear_jpeg_index_build` over the entries in groups that `_cut` bounds by the scratch coefficients, and each group's
+        border colours into `new_borders`.  Per group its items, its status tensor and what the launch reads, kept alive."""
+        import torch
+        from . import train_abi as abi
+        items, verdicts = list(entries), []
+        dense = np.array([128 * int(e.info.total_blocks) for e in entries.values()], dtype=np.int64)
+        for lo, hi in _cut(dense, self.workspace_limit, 65535):
+            group, m = items[lo:hi], hi - lo
+            records, indexes = (abi.FearJpegScan * m)(), (abi.FearJpegIndex * m)()
+            prefix, values = np.zeros(m + 1, dtype=np.uint32), 0
+            for k, e in enumerate(entries[i] for i in group):
+                ctypes.memmove(ctypes.byref(records[k]), ctypes.byref(e.scan), ctypes.sizeof(e.scan))
+                records[k].coef_offset = values
+                values += 64 * int(e.info.total_blocks)
+                prefix[k + 1] = prefix[k] + e.scan.n_seg
+                ix = indexes[k]
+                ix.index, ix.sub_start, ix.seg_start_host, ix.n_sub = e.base + e.at_index, e.base + e.at_sub, e.seg.ctypes.data, int(e.sub[-1])
+            records_at = _up(prefix.nbytes, 16)
+            index_at = records_at + ctypes.sizeof(records)
+            table = np.zeros(index_at + ctypes.sizeof(indexes), dtype=np.uint8)
+            table[:prefix.nbytes] = prefix.view(np.uint8)
+            table[records_at:index_at] = np.frombuffer(records, dtype=np.uint8)
+            table[index_at:] = np.frombuffer(indexes, dtype=np.uint8)
+            dev = torch.from_numpy(table).to(self.device)
+            coef = torch.empty(max(values, 8), dtype=torch.int16, device=self.device)
+            status = torch.empty(m, dtype=torch.int32, device=self.device)
+            abi.launch(self._lib, "fear_jpeg_index_build", records, m, ctypes.c_void_p(dev.data_ptr()), indexes,
+                       ctypes.c_void_p(dev.data_ptr() + index_at), ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(status.data_ptr()),
+                       self.subsequence_bytes, stream)
+            verdicts.append((group, status, dev, coef))
+            new_borders[group] = self._group_borders([entries[i].info for i in group], records, coef, stream)
+        return verdicts
+
+    def _add_verdicts(self, verdicts: List[tuple], blobs: List[bytes]) -> None:
+        """Stage 6: wait for the verdicts (`add` is set-up); a file the device refuses raises, naming the item."""
+        for group, status, _, _ in verdicts:
+            got = status.cpu().numpy()
+            for k in np.flatnonzero(got):
+                i = group[int(k)]
+                try:
+                    _raise_as_python(blobs[i], int(got[k]))
+                except MalformedJPEG as exc:
+                    raise MalformedJPEG(f"item {i}: {exc}") from None
+
+    def _add_pixels(self, blobs: List[bytes], through_host: dict, raw: dict, new_borders, stream) -> dict:
+        """Stage 7: the entries kept as pixels, by item — a file with too large a restart segment once through the host's Huffman
+        stage, which judges the file itself, and the fallback's arrays — and their border colours into `new_borders`."""
+        import torch
+        pixels = {}
+        for i in through_host:
+            try:
+                pixels[i] = self._host.decode([blobs[i]])[0].clone()
+            except (MalformedJPEG, UnsupportedJPEG) as exc:
+                raise type(exc)(f"item {i}: {exc}") from None
+        for i, px in raw.items():
+            pixels[i] = torch.from_numpy(px.copy()).to(self.device)             # (the fallback's array may be read-only)
+        if pixels:
+            kept = sorted(pixels)
+            new_borders[kept] = self._frame_borders([pixels[i] for i in kept], stream)
+        return pixels
+
+    def _add_row_tables(self, entries: dict):
+        """Stage 8: every entry's row table, from the index the device has just written (copied back once: `add` waits anyway), and
+        all of them once more on the device, for rows that only the device knows: one tensor per `add`, None without an entry."""
+        import torch
+        if not entries:
+            return None
+        for e in entries.values():
+            index = e.slab[e.at + e.at_index:e.at + e.at_record].cpu().numpy().view(SUBSEQ_DTYPE)
+            e.row_table = self._row_table(e.info, e.sub, index)
+        tables = [e.row_table for e in entries.values()]
+        row_dev = torch.from_numpy(np.concatenate(tables).astype(np.uint32).view(np.int32)).to(self.device)
+        for e, at in zip(entries.values(), _exclusive(np.array([t.size for t in tables], dtype=np.int64)).tolist()):
+            e.row_dev_at = row_dev.data_ptr() + 4 * at
+        return row_dev
+
+    def _add_border(self, rows: int):
+        """Stage 9: the border table with room for `rows` entries: the store's, or a doubled one that holds its rows."""
+        import torch
+        border = self._border
+        if border is None or border.shape[0] < rows:
+            have = max(self._initial_rows, 1) if border is None else border.shape[0]
+            while have < rows:
+                have *= 2
+            border = torch.zeros((have, 3), dtype=torch.uint8, device=self.device)
+            if self._border is not None and self._n:
+                border[:self._n] = self._border[:self._n]
+        return border
+
+    def _add_commit(self, n: int, entries: dict, pixels: dict, split: dict, new_slabs: List, open_slab, cursor: int, row_dev, border,
+                    new_borders) -> np.ndarray:
+        """Stage 10, the only one that assigns on self: the mirrors' rows, the row tables, the border colours, the slabs and the
+        counts.  The ids."""
+        import torch
+        from . import train_abi as abi
         first = self._n
         self._grow(first + n)
-        ids = np.arange(first, first + n, dtype=np.int64)
-        for i in scans:
-            info, data, seg, scan = prepared[i]
-            sub, at_seg, at_sub, at_index, at_record, end = layout[i]
-            row, col = self._indexed[first + i], self._columns[first + i]
-            row["scan"], row["index"], row["sub_start"], row["n_sub"] = base[i] + at_record, base[i] + at_index, base[i] + at_sub, int(sub[-1])
-            row["row_sub"] = row_at[i]
-            _fill_header(abi.FearJpegImage.from_buffer(self._image, (first + i) * self._image.itemsize), info)
-            table = row_tables[i]
-            scan_columns(col, info, scan.n_seg, int(sub[-1]), self._row_used)
-            if self._row_used + table.size > self._row_sub.size:
-                grown = np.zeros(max(2 * self._row_sub.size, self._row_used + table.size), dtype=np.uint32)
+        for i, e in entries.items():
+            row, n_sub = self._indexed[first + i], int(e.sub[-1])
+            row["scan"], row["index"], row["sub_start"], row["n_sub"] = e.base + e.at_record, e.base + e.at_index, e.base + e.at_sub, n_sub
+            row["row_sub"] = e.row_dev_at
+            _fill_header(abi.FearJpegImage.from_buffer(self._image, (first + i) * self._image.itemsize), e.info)
+            scan_columns(self._columns[first + i], e.info, e.scan.n_seg, n_sub, self._row_used)
+            used = self._row_used + e.row_table.size
+            if used > self._row_sub.size:
+                grown = np.zeros(max(2 * self._row_sub.size, used), dtype=np.uint32)
                 grown[:self._row_used] = self._row_sub[:self._row_used]
                 self._row_sub = grown
-            self._row_sub[self._row_used:self._row_used + table.size] = table
-            self._row_used += table.size
-            self._most = max(self._most, int(info.total_blocks))
+            self._row_sub[self._row_used:used] = e.row_table
+            self._row_used = used
+            self._most = max(self._most, int(e.info.total_blocks))
         for i, px in pixels.items():
             col = self._columns[first + i]
             col["H"], col["W"], col["kind"] = px.shape[0], px.shape[1], KIND_PIXELS
@@ -628,10 +689,11 @@ class JpegStore:
         if row_dev is not None:
             self._row_slabs.append(row_dev)
         self._open, self._cursor = open_slab, cursor
-        self._n, self.nbytes = first + n, self.nbytes + need
+        self._n, self.nbytes = first + n, self.nbytes + sum(split.values())
         for key, v in split.items():
             self.resident[key] += v
-        return ids
+        return np.arange(first, first + n, dtype=np.int64)
+
 
     def _transcode(self, data: bytes):
         """None for a file the baseline parser does not decline; else the baseline transcode of a progressive file, or the status with
@@ -731,6 +793,8 @@ class JpegStore:
         lo, hi, scan = plan["lo"], plan["hi"], plan["scan"]
         group = ids[lo:hi]
         sids, nd, banded, windowed = group[scan], scan.size, "sub0" in plan, "cols" in plan
+        huffman = ("fear_jpeg_huffman_indexed_rows_dev" if rows is not None else "fear_jpeg_huffman_indexed_windows" if windowed
+                   else "fear_jpeg_huffman_indexed_rows" if banded else "fear_jpeg_huffman_indexed")
         with torch.cuda.device(self.device):
             out = torch.empty(max(plan["out_bytes"], 16), dtype=torch.uint8, device=self.device)
             out_offset = plan["out_offset"]
@@ -765,7 +829,6 @@ class JpegStore:
                 self._records = (indexed, images)                        # the calls below get their addresses
                 self.last_upload_bytes = dev.numel()
                 if rows is None:
-                    huffman = "fear_jpeg_huffman_indexed_windows" if windowed else ("fear_jpeg_huffman_indexed_rows" if banded else "fear_jpeg_huffman_indexed")
                     abi.launch(self._lib, huffman, P(indexed.ctypes.data), nd,
                                P(dev.data_ptr()), P(coef.data_ptr()), P(status.data_ptr()), self.subsequence_bytes, stream)
                     _launch_pixels(self._lib, P(images.ctypes.data), nd, table, ws.data_ptr(), plan["workspace_bytes"],
@@ -773,7 +836,7 @@ class JpegStore:
                 else:                                                    # the group's rows: a slice, or a gather on the device; no wait
                     mine = rows[lo:hi] if whole else rows.index_select(0, dev[at[4]:].view(torch.int64))
                     mine = mine.contiguous()
-                    abi.launch(self._lib, "fear_jpeg_huffman_indexed_rows_dev", P(indexed.ctypes.data), nd, P(dev.data_ptr()), P(mine.data_ptr()),
+                    abi.launch(self._lib, huffman, P(indexed.ctypes.data), nd, P(dev.data_ptr()), P(mine.data_ptr()),
                                P(coef.data_ptr()), P(status.data_ptr()), self.subsequence_bytes, stream)
                     abi.launch(self._lib, "fear_jpeg_decode_u8_rows_dev", P(images.ctypes.data), nd, P(table), P(mine.data_ptr()),
                                P(ws.data_ptr()), plan["workspace_bytes"], stream)
@@ -782,18 +845,24 @@ class JpegStore:
                 event = torch.cuda.Event()
                 event.record()
                 self._pending.append((event, verdict, lo + scan, sids))
-            cols = self._columns[group]
-            if windowed:                                                 # compact tensors; an entry kept as pixels gives its rectangle
-                high, wide = plan["high"], plan["wide"]
-                for k in np.flatnonzero((cols["kind"] == KIND_PIXELS) & (high * wide > 0)):
-                    y0, y1, x0, x1 = plan["window"][k].tolist()
-                    out[out_offset[k]:out_offset[k] + 3 * high[k] * wide[k]].view(int(high[k]), int(wide[k]), 3).copy_(
-                        self._pixels[int(group[k])][y0:y1, x0:x1], non_blocking=True)
-            else:
-                high, wide = _scaled_sides(cols["H"], cols["W"], scale if isinstance(scale, int) else scale[lo:hi])
-                for k in np.flatnonzero(cols["kind"] == KIND_PIXELS):    # the entries kept as pixels: a whole copy, never an alias
-                    out[out_offset[k]:out_offset[k] + 3 * high[k] * wide[k]].copy_(self._pixels[int(group[k])].view(-1), non_blocking=True)
+            high, wide = self._copy_kept(group, plan, out, scale if isinstance(scale, int) else scale[lo:hi])
         frames[lo:hi] = _frame_views(out, out_offset, high, wide)
+
+    def _copy_kept(self, group: np.ndarray, plan: dict, out, scale):
+        """The group's entries kept as pixels, copied into `out` — a whole copy, never an alias; under a plan of `plan_decode_windows`
+        the rectangle itself — and the height and width of every frame of the group."""
+        cols, out_offset = self._columns[group], plan["out_offset"]
+        if "cols" in plan:                                               # compact tensors
+            high, wide = plan["high"], plan["wide"]
+            for k in np.flatnonzero((cols["kind"] == KIND_PIXELS) & (high * wide > 0)):
+                y0, y1, x0, x1 = plan["window"][k].tolist()
+                out[out_offset[k]:out_offset[k] + 3 * high[k] * wide[k]].view(int(high[k]), int(wide[k]), 3).copy_(
+                    self._pixels[int(group[k])][y0:y1, x0:x1], non_blocking=True)
+        else:
+            high, wide = _scaled_sides(cols["H"], cols["W"], scale)
+            for k in np.flatnonzero(cols["kind"] == KIND_PIXELS):
+                out[out_offset[k]:out_offset[k] + 3 * high[k] * wide[k]].copy_(self._pixels[int(group[k])].view(-1), non_blocking=True)
+        return high, wide
 
     def _block_start(self, stream):
         """The dense block_start table that every record of `decode` points at, long enough for the store's largest image (a band has

@@ -455,6 +455,35 @@ def test_store_faults_and_kinds(monkeypatch):
         store.close()
 
 
+def test_an_add_the_device_refuses_commits_nothing(lib):
+    """`add` assigns to the store in its last stage alone: after a call whose second file the device refuses (a status of
+    fear_jpeg_index_build, by when the call's first file is uploaded and indexed) the store is what it was, and the next call goes on
+    from there."""
+    first, second, good = jpegdec.case("16x16_420"), jpegdec.case("80x72_420"), jpegdec.case("15x50_420_random_q100_rst3")
+    refused = next(data for _, data in jpeghuff.corpus()
+                   if not isinstance(jpeghuff.c_prepare(lib, data), int) and isinstance(jpegdec.c_decode(lib, data), int))
+    store, dec = JpegStore(device=0, slab_bytes=40_000, threads=2), JpegDecoder(device=0, threads=2)
+
+    def state():
+        return len(store), store.nbytes, dict(store.resident), store.kinds.tolist(), store.borders([0, 1]).cpu().tolist()
+    try:
+        ids = store.add([first[1], second[1]])
+        frames = [f.clone() for f in store.decode(ids, check=True)]
+        before = state()
+        with pytest.raises(MalformedJPEG, match="^item 1: "):
+            store.add([good[1], refused])
+        assert state() == before and before[0] == 2
+        again = store.decode([0, 1], check=True)
+        assert all(torch.equal(f, was) for f, was in zip(again, frames)) and np.array_equal(again[1].cpu().numpy(), second[2])
+        more = store.add([good[1]])
+        assert more.tolist() == [2] and len(store) == 3 and store.kinds.tolist() == ["scan"] * 3
+        frame = store.decode(more, check=True)[0]
+        assert torch.equal(frame, dec.decode([good[1]])[0]) and np.array_equal(frame.cpu().numpy(), good[2])
+    finally:
+        store.close()
+        dec.close()
+
+
 def test_store_capacity():
     files = [data for _, data, _ in jpegdec.supported()[:6]]
     store = JpegStore(device=0, slab_bytes=40_000, threads=2)

@@ -14,7 +14,8 @@ from feartracker_amd import jpeg_decode_host, jpeg_entropy_indexed_host, jpeg_pi
 from feartracker_amd import train_abi as abi
 from feartracker_amd.geometry import border_color_u8
 from feartracker_amd.jpeg_huffman import _record_lanes, window_lanes
-from feartracker_amd.jpeg_store import COLUMNS, KIND_PIXELS, KIND_SCAN, WindowFrames, plan_decode_windows, scan_columns
+from feartracker_amd.jpeg_store import (COLUMNS, KIND_PIXELS, KIND_SCAN, WindowFrames, plan_decode, plan_decode_rows, plan_decode_windows,
+                                        scan_columns)
 from feartracker_amd.train_data import TrainPairBuilder
 
 SB = 128
@@ -131,6 +132,39 @@ def test_windows_planner_against_a_per_file_loop(limit, scale):
         assert list(zip(g["high"].tolist(), g["wide"].tolist())) == w["shape"]
         assert g["workspace_bytes"] == 16 + w["values"] and not (g["out_offset"] % 16).any()
     assert plan_decode_windows(columns, row_sub, [], np.zeros((0, 4), np.int64), limit, scale=scale) == []
+
+
+@pytest.mark.parametrize("per_position", [False, True])
+@pytest.mark.parametrize("scale", [1, 2, 8])
+def test_the_three_plans_agree_where_their_requests_do(scale, per_position):
+    """The three plans are built from the same parts: a window of a frame's whole width plans the band `plan_decode_rows` plans for its
+    rows, and the rows of a whole frame plan the image `plan_decode` plans — group by group, values and dtypes."""
+    cases, columns, row_sub = _columns()
+    rng = np.random.default_rng(scale)
+    entries = len(columns) if scale == 1 else len(cases)                 # (a "pixels" entry cannot be decoded at a scale)
+    ids = np.concatenate([rng.permutation(entries), rng.integers(0, entries, 40)])
+    scales = np.full(ids.size, scale) if per_position else scale
+    m = 8 // scale
+    H, W = -(-columns["H"][ids].astype(np.int64) * m // 8), -(-columns["W"][ids].astype(np.int64) * m // 8)
+    y0 = rng.integers(-3, H + 3)
+    y1 = np.where(rng.random(ids.size) < 0.15, y0 - 1, rng.integers(-3, H + 6))      # empty, to the edges and out of range among them
+    zeros = np.zeros(ids.size, dtype=np.int64)
+
+    def same(got, want, keys):
+        assert len(got) == len(want) > 0
+        for g, w in zip(got, want):
+            assert (g["lo"], g["hi"]) == (w["lo"], w["hi"]) and np.array_equal(g["scan"], w["scan"])
+            for key in keys:
+                assert type(g[key]) is type(w[key]) and np.array_equal(g[key], w[key]), key
+                assert not isinstance(w[key], np.ndarray) or g[key].dtype == w[key].dtype, key
+
+    for limit in (1 << 30, 20_000):
+        rows = plan_decode_rows(columns, row_sub, ids, np.stack([y0, y1], axis=1), limit, scale=scales)
+        wins = plan_decode_windows(columns, row_sub, ids, np.stack([y0, y1, zeros, W], axis=1), limit, scale=scales)
+        same(wins, rows, ("sub0", "sub_count", "sub_prefix", "mcu_row0", "mcu_rows", "band_height", "block_prefix", "coef_offset"))
+        whole = plan_decode_rows(columns, row_sub, ids, np.stack([zeros, H], axis=1), limit, scale=scales)
+        same(whole, plan_decode(columns, ids, limit, scale=scales), ("block_prefix", "pixel_prefix", "coef_offset", "values", "most"))
+        assert (len(rows) == 1) == (len(whole) == 1) == (limit == 1 << 30)
 
 
 # -------------------------------------------------------------------------------------------- the write pass, the pixels, the lane rule
