@@ -14,7 +14,7 @@ from .hip_backend import FEARNetHIP, FearError, load_library, DEFAULT_WEIGHTS, L
 from .jpeg_frames import (JpegDecoder, MalformedJPEG, UnsupportedJPEG, jpeg_decode_host, jpeg_info, jpeg_pixels_host, jpeg_scaled_shape,
                           jpeg_scaled_transforms)
 from .jpeg_huffman import (jpeg_entropy_indexed_host, jpeg_entropy_parallel_host, jpeg_entropy_rows_device_host, jpeg_rows_device_host,
-                           jpeg_scan_index_host, jpeg_scan_prepare_host, scan_row_sub, window_lanes)
+                           jpeg_scan_index_host, jpeg_scan_prepare_host, scan_row_sub, stage_range_host, window_lanes)
 from .jpeg_progressive import jpeg_to_baseline_host
 from .jpeg_encode import (SUBSAMPLINGS, JpegEncoder, JpegHuffmanDepth, JpegOverflow, PendingJpegs, jpeg_encode_host,
                           jpeg_optimal_table_host, jpeg_symbol_histograms_host, write_mjpeg_avi)
@@ -27,7 +27,7 @@ __all__ = [
     "FEARMultiTracker", "PendingBoxes", "YUVFrame",
     "FEARNetHIP", "FearError", "load_library", "DEFAULT_WEIGHTS", "LIB_PATH",
     "JpegDecoder", "MalformedJPEG", "UnsupportedJPEG", "jpeg_decode_host", "jpeg_info", "jpeg_entropy_parallel_host", "jpeg_scan_prepare_host",
-    "jpeg_scan_index_host", "jpeg_entropy_indexed_host", "JpegStore", "StoreFull", "plan_decode", "plan_decode_rows", "plan_decode_windows", "WindowFrames", "window_lanes", "scan_row_sub", "jpeg_pixels_host", "jpeg_scaled_shape",
+    "jpeg_scan_index_host", "jpeg_entropy_indexed_host", "JpegStore", "StoreFull", "plan_decode", "plan_decode_rows", "plan_decode_windows", "WindowFrames", "window_lanes", "scan_row_sub", "stage_range_host", "jpeg_pixels_host", "jpeg_scaled_shape",
     "jpeg_scaled_transforms",
     "jpeg_to_baseline_host", "jpeg_entropy_rows_device_host", "jpeg_rows_device_host",
     "StoreFrames", "search_rows_host",

@@ -43,6 +43,8 @@ struct JhSegment {
     bool last;
     uint32_t band_row0, band_rows;   // MODE 3, 4, 5 alone (fear_jpeg_store.h): the MCU rows whose blocks are stored, inside the image
     uint32_t win_col0, win_cols;     // MODE 5 alone: the MCU columns whose blocks are stored, inside the image
+    const uint32_t* stage;   // the staged fetch alone (fear_jpeg_store.h): the LDS copy of the words stage_w0 .. stage_w0 + stage_n)
+    uint32_t stage_w0, stage_n;
 };
 
 struct JhState {
@@ -50,12 +52,24 @@ struct JhState {
     uint32_t sz;             // slot << 8 | z
 };
 
+// Word w < n_words of the image's bytes.  STAGED (the byte-fetch policy of fear_jpeg_store.h's staged kernels): from the workgroup's copy
+// in LDS where the word lies in it, from `words` otherwise — whatever a lane reads behind the staged range is exact, only slower.
+template <bool STAGED>
+__device__ __forceinline__ uint32_t jh_word(const JhSegment& s, uint32_t w) {
+    if (STAGED) {
+        const uint32_t i = w - s.stage_w0;                               // a word in front of the range wraps to a large value
+        if (i < s.stage_n) return s.stage[i];
+    }
+    return s.words[w];
+}
+
 // 32 bits from position p, the first in bit 31; bits past the segment's end are zero.
+template <bool STAGED = false>
 __device__ __forceinline__ uint32_t jh_peek(const JhSegment& s, uint32_t p) {
     if (p >= s.bits) return 0u;
     const uint32_t at = s.byte0 + (p >> 3), w = at >> 2;
-    const uint32_t hi = w < s.n_words ? __builtin_bswap32(s.words[w]) : 0u;
-    const uint32_t lo = w + 1 < s.n_words ? __builtin_bswap32(s.words[w + 1]) : 0u;
+    const uint32_t hi = w < s.n_words ? __builtin_bswap32(jh_word<STAGED>(s, w)) : 0u;
+    const uint32_t lo = w + 1 < s.n_words ? __builtin_bswap32(jh_word<STAGED>(s, w + 1)) : 0u;
     const uint32_t shift = (at & 3) * 8 + (p & 7);                       // at most 31: 33 bits of the window are left
     uint32_t win = (uint32_t)((((uint64_t)hi << 32 | lo) << shift) >> 32);
     const uint32_t left = s.bits - p;
@@ -173,8 +187,8 @@ __device__ __forceinline__ uint32_t jh_add_dc(JhLane& lane, int comp, uint32_t v
 // 3: write, but only the blocks of the band's MCU rows are stored (jh_band_base); every judgement is mode 2's.
 // 4: write, only the blocks of the band's MCU rows, at their place in the whole image (jh_rows_base); every judgement is mode 2's.
 // 5: write, only the blocks of the window's MCU rows and columns, window-dense (jh_window_base); every judgement is mode 2's.
-// A code in no table, a DC size above 15 or an index past 63: advance one bit, z = 0.
-template <int MODE>
+// A code in no table, a DC size above 15 or an index past 63: advance one bit, z = 0.  STAGED: jh_word's fetch policy.
+template <int MODE, bool STAGED = false>
 __device__ __forceinline__ JhState jh_decode(const JhSegment& s, const FearJpegHuff* tabs, JhState st, uint32_t end, int16_t* coef, JhLane& io) {
     JhLane lane = io;
     uint32_t p = st.p;
@@ -188,7 +202,7 @@ __device__ __forceinline__ JhState jh_decode(const JhSegment& s, const FearJpegH
     }
 #pragma unroll 1
     for (uint32_t step = 0; step < end - st.p + 32 && p < stop; ++step) {   // a symbol is at least one bit: the count never binds
-        const uint32_t win = jh_peek(s, p);
+        const uint32_t win = jh_peek<STAGED>(s, p);
         const int comp = slot < s.hv ? 0 : slot - s.hv + 1;
         int len = 0;
         if (z == 0) {

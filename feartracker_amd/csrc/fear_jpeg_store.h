@@ -7,7 +7,9 @@
 // jpeg_huffman.scan_row_sub), and only the band's blocks are stored, as the dense coefficients of an image of those rows alone.
 // fear_jpeg_huffman_indexed_windows is the band's lane for a range of MCU columns as well: a lane of the band that its own entry and the
 // next one show to hold no MCU of those columns returns early, and the blocks are stored window-dense.
-// The four kernels share one lane (ji_lane<FORM>) and the four entry points one host function (ji_launch).
+// The four kernels share one lane (ji_lane<FORM, STAGED>) and the four entry points one host function (ji_launch).  The *_host entry
+// points are the same four for bytes in pinned host memory ("Bytes on the host"): the lane's second byte-fetch
+// policy, under which a workgroup copies its lanes' byte range into LDS first (ji_stage_range, fear_jpeg_stage_range).
 // Included by fear_train.hip behind fear_jpeg_huffman.h, whose jh_decode, jh_peek, jh_block_base and JhSegment it uses, and
 // fear_jpeg_decode.h's jd_find_image and jr_band.
 
@@ -18,7 +20,44 @@ struct JpegIndexedArgs {
     int16_t* coef;
     int32_t* status;
     int n, subsequence_bits;
+    int stage_bytes;         // the staged kernels alone: the launch's dynamic LDS, a multiple of 16, at most kJiStageCap
 };
+
+constexpr int kJiStageCap = 64 << 10;   // the most a workgroup stages; what lies behind goes through the direct fetch
+
+// The bytes byte0 .. byte1) that the subsequences sub_first .. sub_first + sub_count) of a prepared scan cover: consecutive
+// subsequences are consecutive bytes, across segments too (an empty segment has no subsequence), so the union of the lanes'
+// [seg_start[seg] + k SB, min(... + SB, seg_start[seg + 1])) is one range, from the first lane's first byte to the last lane's end.
+// Two searches of sub_start side by side, 21 steps at most (n_seg <= 2^20); both ends clamped to n_bytes; 0, 0 for no lane, for
+// n_seg == 0 and for a sub_start that is not this scan's.  The staged kernels and fear_jpeg_stage_range share it;
+// jpeg_huffman.stage_range_host restates it.
+__host__ __device__ inline void ji_stage_range(const uint32_t* seg_start, const uint32_t* sub_start, uint32_t n_seg, uint32_t n_bytes,
+                                               uint32_t sub_first, uint32_t sub_count, uint32_t subsequence_bytes, uint32_t* byte0,
+                                               uint32_t* byte1) {
+    *byte0 = *byte1 = 0;
+    if (sub_count == 0 || n_seg == 0) return;
+    const uint32_t sub_last = sub_first + (sub_count - 1);
+    uint32_t s0 = 0, h0 = n_seg, s1 = 0, h1 = n_seg;                     // the last segment that starts at or in front of each
+    for (int step = 0; step < 21 && (h0 - s0 > 1 || h1 - s1 > 1); ++step) {
+        if (h0 - s0 > 1) {
+            const uint32_t mid = (s0 + h0) >> 1;
+            if (sub_start[mid] <= sub_first) s0 = mid; else h0 = mid;
+        }
+        if (h1 - s1 > 1) {
+            const uint32_t mid = (s1 + h1) >> 1;
+            if (sub_start[mid] <= sub_last) s1 = mid; else h1 = mid;
+        }
+    }
+    const uint32_t f0 = sub_start[s0], f1 = sub_start[s1];
+    if (f0 > sub_first || f1 > sub_last) return;
+    const uint64_t lo = (uint64_t)seg_start[s0] + (uint64_t)(sub_first - f0) * subsequence_bytes;
+    uint64_t hi = (uint64_t)seg_start[s1] + ((uint64_t)(sub_last - f1) + 1) * subsequence_bytes;
+    if (hi > seg_start[s1 + 1]) hi = seg_start[s1 + 1];
+    if (hi > n_bytes) hi = n_bytes;
+    if (lo >= hi) return;
+    *byte0 = (uint32_t)lo;
+    *byte1 = (uint32_t)hi;
+}
 
 __device__ __forceinline__ const FearJpegIndexed* ji_records(const JpegIndexedArgs& a) {
     return reinterpret_cast<const FearJpegIndexed*>(reinterpret_cast<const char*>(a.table) + FEAR_JPEG_SCAN_TABLE_RECORDS(a.n));
@@ -38,7 +77,14 @@ __global__ __launch_bounds__(kJhLanes) void jpeg_indexed_status_kernel(JpegIndex
 // with the MCU columns of the record's `reserved` word (mcu_col0 | mcu_cols << 16): a lane whose MCUs — known from its entry's `begun`
 // and the next entry's, or the segment's block count — all lie outside those columns returns in front of every judgement, and only the
 // blocks of the band's rows and those columns are stored, window-dense (jh_window_base).
-template <int FORM>
+//
+// STAGED is the byte-fetch policy.  false: every lane reads its words from the record's `bytes` (jh_word).  true, for bytes in pinned
+// host memory (the *_host entry points): in front of the barrier the workgroup copies the one byte range its running lanes cover
+// (ji_stage_range; form 2 counts the lanes of the band alone, form 3 all the band's lanes of the workgroup: no vote) into
+// dynamic LDS with 16-byte loads from the 16-byte aligned address at or in front of the range, two words further than its end for the
+// last lane's window, at most stage_bytes, never a word at or behind 4 ceil(n_bytes / 4) nor one in front of `bytes` (the chunks at those
+// two edges are loaded word by word); a lane's fetch takes a word from LDS where it is there and from `bytes` otherwise.
+template <int FORM, bool STAGED>
 __device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a, const int32_t* rows_dev) {
     constexpr bool WIN = FORM == 3, ROWS = FORM == 1 || WIN, DEV = FORM == 2;
     __shared__ __attribute__((aligned(16))) FearJpegHuff tabs[6];        // dc by component, then ac by component
@@ -63,6 +109,54 @@ __device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a, const int32_t*
         const uint4* src = reinterpret_cast<const uint4*>(rec->dc);      // the record is 16-byte aligned, the tables lie 64 bytes in
         uint4* dst = reinterpret_cast<uint4*>(tabs);
         for (int i = tid; i < (int)(sizeof(tabs) / 16); i += kJhLanes) dst[i] = src[i];
+    }
+    const uint32_t* stage = nullptr;
+    uint32_t stage_w0 = 0, stage_n = 0;
+    if constexpr (STAGED) {                                              // everything here is the same for the whole workgroup
+        extern __shared__ __attribute__((aligned(16))) uint4 ji_stage[];
+        const uint64_t lane0 = (uint64_t)(blockIdx.x - a.table[img]) * kJhLanes;
+        uint64_t first = lane0, last = lane0 + (kJhLanes - 1);           // the lanes that run, inclusive
+        if (ROWS) {
+            first += im->sub0;
+            last = min(last, (uint64_t)im->sub_count - 1u) + im->sub0;   // (sub_count > 0: the workgroup exists)
+        }
+        if (DEV) {
+            first = max(first, (uint64_t)dev_first);
+            last = min(last, (uint64_t)dev_last);
+        }
+        const uint32_t all = im->n_sub;
+        uint32_t b0 = 0, b1 = 0;
+        const uint32_t n_bytes = rec->n_bytes;
+        if (all > 0 && first < all && first <= last)
+            ji_stage_range(rec->seg_start, im->sub_start, rec->n_seg, n_bytes, (uint32_t)first, (uint32_t)(min(last, (uint64_t)all - 1u) - first) + 1u,
+                           (uint32_t)a.subsequence_bits >> 3, &b0, &b1);
+        if (b1 > b0) {
+            // offsets from the 16-byte aligned address at or in front of `bytes`, which is 4-byte aligned: `mis` further than the bytes'
+            const uintptr_t addr = reinterpret_cast<uintptr_t>(rec->bytes);
+            const uint64_t mis = addr & 15u, limit = mis + 4u * (((uint64_t)n_bytes + 3u) >> 2);
+            const uint64_t v0 = (b0 + mis) & ~(uint64_t)15, v1 = min(((b1 + mis + 3u) & ~(uint64_t)3) + 8u, limit);
+            const uint32_t chunks = (uint32_t)min((v1 - v0 + 15u) >> 4, (uint64_t)(a.stage_bytes >> 4));
+            const char* base = reinterpret_cast<const char*>(addr - mis);
+            for (uint32_t i = tid; i < chunks; i += kJhLanes) {
+                const uint64_t v = v0 + 16u * (uint64_t)i;
+                uint4 q;
+                if (v >= mis && v + 16u <= limit) {
+                    q = *reinterpret_cast<const uint4*>(base + v);
+                } else {                                                 // the chunk at an edge of the image's words: word by word
+                    uint32_t w[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const uint64_t vv = v + 4u * (uint32_t)j;
+                        w[j] = vv >= mis && vv < limit ? *reinterpret_cast<const uint32_t*>(base + vv) : 0u;
+                    }
+                    q = make_uint4(w[0], w[1], w[2], w[3]);
+                }
+                ji_stage[i] = q;
+            }
+            stage = reinterpret_cast<const uint32_t*>(ji_stage);
+            stage_w0 = (uint32_t)((int64_t)(v0 - mis) >> 2);             // up to three words in front of `bytes`: wraps, as jh_word expects
+            stage_n = 4u * chunks;
+        }
     }
     __syncthreads();                                                     // the only barrier
     const uint32_t n_sub = im->n_sub, n_seg = rec->n_seg;
@@ -91,6 +185,9 @@ __device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a, const int32_t*
         const uint32_t b0 = min(rec->seg_start[seg], n_bytes), b1 = min(max(rec->seg_start[seg + 1], b0), n_bytes);
         s.words = reinterpret_cast<const uint32_t*>(rec->bytes);
         s.n_words = (n_bytes + 3) >> 2;
+        s.stage = stage;
+        s.stage_w0 = stage_w0;
+        s.stage_n = stage_n;
         s.byte0 = b0;
         s.bits = min(b1 - b0, FEAR_JPEG_DEVICE_SCAN_MAX) * 8u;
         const int nf = rec->components;
@@ -153,7 +250,7 @@ __device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a, const int32_t*
     lane.dc1 = e.w & 0xFFFFu;
     lane.dc2 = e.w >> 16;
     const uint32_t end = ((uint32_t)k + 1u) * SB;                        // k SB < bits <= 2^27 (8 FEAR_JPEG_DEVICE_SCAN_MAX), SB <= 2^13: no overflow
-    const JhState out = jh_decode<DEV ? 4 : (WIN ? 5 : (ROWS ? 3 : 2))>(s, tabs, entry, end, a.coef + im->coef_offset, lane);
+    const JhState out = jh_decode<DEV ? 4 : (WIN ? 5 : (ROWS ? 3 : 2)), STAGED>(s, tabs, entry, end, a.coef + im->coef_offset, lane);
     bool failed = lane.error;
     // the segment's last subsequence: fewer complete blocks than the segment owes, as jpeg_huffman_kernel judges its true chain's end
     if (end >= s.bits && (lane.begun - ((out.sz & 255) != 0 ? 1u : 0u) < s.expected || (lane.begun == 0 && s.expected > 0))) failed = true;
@@ -162,14 +259,40 @@ __device__ __forceinline__ void ji_lane(const JpegIndexedArgs& a, const int32_t*
     if (failed) *status = FEAR_TRAIN_ERR_FORMAT;                          // every lane that stores stores the same value
 }
 
-__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_kernel(JpegIndexedArgs a) { ji_lane<0>(a, nullptr); }
+__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_kernel(JpegIndexedArgs a) { ji_lane<0, false>(a, nullptr); }
 
-__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_rows_kernel(JpegIndexedArgs a) { ji_lane<1>(a, nullptr); }
+__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_rows_kernel(JpegIndexedArgs a) { ji_lane<1, false>(a, nullptr); }
 
-__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_windows_kernel(JpegIndexedArgs a) { ji_lane<3>(a, nullptr); }
+__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_windows_kernel(JpegIndexedArgs a) { ji_lane<3, false>(a, nullptr); }
 
 __global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_rows_dev_kernel(JpegIndexedArgs a, const int32_t* rows_dev) {
-    ji_lane<2>(a, rows_dev);
+    ji_lane<2, false>(a, rows_dev);
+}
+
+// The same lane with the staged fetch, one kernel for the four forms (rows_dev is null but in form 2): the same grid and workgroup,
+// stage_bytes of dynamic LDS.
+template <int FORM>
+__global__ __launch_bounds__(kJhLanes) void jpeg_huffman_indexed_staged_kernel(JpegIndexedArgs a, const int32_t* rows_dev) {
+    ji_lane<FORM, true>(a, rows_dev);
+}
+
+using JiStagedKernel = void (*)(JpegIndexedArgs, const int32_t*);
+constexpr JiStagedKernel kJiStaged[4] = {jpeg_huffman_indexed_staged_kernel<0>, jpeg_huffman_indexed_staged_kernel<1>,
+                                         jpeg_huffman_indexed_staged_kernel<2>, jpeg_huffman_indexed_staged_kernel<3>};
+
+// With the six tables a workgroup at the cap holds more than 64 KiB of LDS: the four kernels are told so once per device.
+bool ji_staged_ready() {
+    static std::atomic<uint64_t> done{0};                                // (two threads that both find a bit unset set the same values)
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess || device < 0 || device > 63) return false;
+    if (done.load() >> device & 1u) return true;
+    for (JiStagedKernel k : kJiStaged)
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, kJiStageCap) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+    done.fetch_or((uint64_t)1 << device);
+    return true;
 }
 
 }  // namespace
@@ -215,7 +338,9 @@ int fear_jpeg_index_build(const FearJpegScan* scans, int n, const void* table_de
 // The checks and the two launches of the four indexed entry points.  form: ji_lane's, 0 the image, 1 the host-planned band (the
 // record's sub0 / sub_count and mcu_row0 / mcu_rows are checked and the grid counts sub_count), 2 the band of `rows_dev` (which, with
 // every record's row_sub, must be there), 3 the host-planned window (form 1's checks and the columns of the record's `reserved` word).
-static int ji_launch(int form, const FearJpegIndexed* images, int n, const void* table_dev, const int32_t* rows_dev, int16_t* coef,
+// staged: the *_host entry points' kernels, with min(256 subsequence_bytes + 32, kJiStageCap) bytes of dynamic LDS — a workgroup's
+// range, the bytes in front of it down to a 16-byte address and the last lane's two words behind it.
+static int ji_launch(int form, bool staged, const FearJpegIndexed* images, int n, const void* table_dev, const int32_t* rows_dev, int16_t* coef,
                      int32_t* status_dev, int subsequence_bytes, void* stream) {
     if (n < 0 || n > 65535 || subsequence_bytes < 4 || subsequence_bytes > 1024 || (subsequence_bytes & 3) != 0) return FEAR_TRAIN_ERR_SHAPE;
     if (n == 0) return FEAR_TRAIN_OK;
@@ -244,11 +369,14 @@ static int ji_launch(int form, const FearJpegIndexed* images, int n, const void*
     a.status = status_dev;
     a.n = n;
     a.subsequence_bits = subsequence_bytes * 8;
+    a.stage_bytes = staged ? min(kJhLanes * subsequence_bytes + 32, kJiStageCap) : 0;
+    if (staged && !ji_staged_ready()) return FEAR_TRAIN_ERR_HIP;
     const dim3 grid((unsigned)groups), lanes(kJhLanes);
     hipLaunchKernelGGL(jpeg_indexed_status_kernel, dim3((unsigned)((n + kJhLanes - 1) / kJhLanes)), lanes, 0, static_cast<hipStream_t>(stream), a);
     LAUNCH_CHECK();
     if (groups == 0) return FEAR_TRAIN_OK;
-    if (form == 0) hipLaunchKernelGGL(jpeg_huffman_indexed_kernel, grid, lanes, 0, static_cast<hipStream_t>(stream), a);
+    if (staged) hipLaunchKernelGGL(kJiStaged[form], grid, lanes, (size_t)a.stage_bytes, static_cast<hipStream_t>(stream), a, rows_dev);
+    else if (form == 0) hipLaunchKernelGGL(jpeg_huffman_indexed_kernel, grid, lanes, 0, static_cast<hipStream_t>(stream), a);
     else if (form == 1) hipLaunchKernelGGL(jpeg_huffman_indexed_rows_kernel, grid, lanes, 0, static_cast<hipStream_t>(stream), a);
     else if (form == 3) hipLaunchKernelGGL(jpeg_huffman_indexed_windows_kernel, grid, lanes, 0, static_cast<hipStream_t>(stream), a);
     else hipLaunchKernelGGL(jpeg_huffman_indexed_rows_dev_kernel, grid, lanes, 0, static_cast<hipStream_t>(stream), a, rows_dev);
@@ -258,22 +386,79 @@ static int ji_launch(int form, const FearJpegIndexed* images, int n, const void*
 
 int fear_jpeg_huffman_indexed(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
                               int subsequence_bytes, void* stream) {
-    return ji_launch(0, images, n, table_dev, nullptr, coef, status_dev, subsequence_bytes, stream);
+    return ji_launch(0, false, images, n, table_dev, nullptr, coef, status_dev, subsequence_bytes, stream);
 }
 
 int fear_jpeg_huffman_indexed_rows(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
                                    int subsequence_bytes, void* stream) {
-    return ji_launch(1, images, n, table_dev, nullptr, coef, status_dev, subsequence_bytes, stream);
+    return ji_launch(1, false, images, n, table_dev, nullptr, coef, status_dev, subsequence_bytes, stream);
 }
 
 int fear_jpeg_huffman_indexed_rows_dev(const FearJpegIndexed* images, int n, const void* table_dev, const int32_t* rows_dev, int16_t* coef,
                                        int32_t* status_dev, int subsequence_bytes, void* stream) {
-    return ji_launch(2, images, n, table_dev, rows_dev, coef, status_dev, subsequence_bytes, stream);
+    return ji_launch(2, false, images, n, table_dev, rows_dev, coef, status_dev, subsequence_bytes, stream);
 }
 
 int fear_jpeg_huffman_indexed_windows(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
                                       int subsequence_bytes, void* stream) {
-    return ji_launch(3, images, n, table_dev, nullptr, coef, status_dev, subsequence_bytes, stream);
+    return ji_launch(3, false, images, n, table_dev, nullptr, coef, status_dev, subsequence_bytes, stream);
+}
+
+// The four calls for scans whose `bytes` lie in pinned, mapped host memory (JpegStore(residence="host")): the same records, checks,
+// grids and results, the staged fetch.
+int fear_jpeg_huffman_indexed_host(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
+                                   int subsequence_bytes, void* stream) {
+    return ji_launch(0, true, images, n, table_dev, nullptr, coef, status_dev, subsequence_bytes, stream);
+}
+
+int fear_jpeg_huffman_indexed_rows_host(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
+                                        int subsequence_bytes, void* stream) {
+    return ji_launch(1, true, images, n, table_dev, nullptr, coef, status_dev, subsequence_bytes, stream);
+}
+
+int fear_jpeg_huffman_indexed_rows_dev_host(const FearJpegIndexed* images, int n, const void* table_dev, const int32_t* rows_dev,
+                                            int16_t* coef, int32_t* status_dev, int subsequence_bytes, void* stream) {
+    return ji_launch(2, true, images, n, table_dev, rows_dev, coef, status_dev, subsequence_bytes, stream);
+}
+
+int fear_jpeg_huffman_indexed_windows_host(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
+                                           int subsequence_bytes, void* stream) {
+    return ji_launch(3, true, images, n, table_dev, nullptr, coef, status_dev, subsequence_bytes, stream);
+}
+
+int fear_host_mapped_pointer(const void* host, void** device) {
+    if (!device) return FEAR_TRAIN_ERR_NULL;
+    *device = nullptr;
+    if (!host) return FEAR_TRAIN_ERR_SHAPE;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) {          // no runtime to ask
+        (void)hipGetLastError();
+        return FEAR_TRAIN_ERR_HIP;
+    }
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, host) != hipSuccess) {            // pageable memory the runtime has never seen
+        (void)hipGetLastError();
+        return FEAR_TRAIN_ERR_SHAPE;
+    }
+    if (attr.type != hipMemoryTypeHost || attr.isManaged || !attr.devicePointer) return FEAR_TRAIN_ERR_SHAPE;
+    *device = attr.devicePointer;
+    return FEAR_TRAIN_OK;
+}
+
+int fear_jpeg_stage_range(const uint32_t* seg_start, const uint32_t* sub_start, uint32_t n_seg, uint32_t n_bytes, uint32_t sub_first,
+                          uint32_t sub_count, int subsequence_bytes, uint32_t* byte0, uint32_t* byte1) {
+    if (!seg_start || !sub_start || !byte0 || !byte1) return FEAR_TRAIN_ERR_NULL;
+    uint32_t n_sub = 0;                                                   // seg_start is this scan's, and sub_start its prefix sums
+    const int rc = fear_jpeg_sub_start(seg_start, n_seg, n_bytes, subsequence_bytes, nullptr, 0, &n_sub);
+    if (rc != FEAR_TRAIN_OK) return rc;
+    uint64_t total = 0;
+    for (uint32_t s = 0; s < n_seg; ++s) {
+        if (sub_start[s] != (uint32_t)total) return FEAR_TRAIN_ERR_SHAPE;
+        total += ((uint64_t)(seg_start[s + 1] - seg_start[s]) + (uint32_t)subsequence_bytes - 1) / (uint32_t)subsequence_bytes;
+    }
+    if (sub_start[n_seg] != n_sub || sub_first > n_sub || sub_count > n_sub - sub_first) return FEAR_TRAIN_ERR_SHAPE;
+    ji_stage_range(seg_start, sub_start, n_seg, n_bytes, sub_first, sub_count, (uint32_t)subsequence_bytes, byte0, byte1);
+    return FEAR_TRAIN_OK;
 }
 
 }  // extern "C"

@@ -271,6 +271,22 @@ def scan_sub_start(seg_start, subsequence_bytes: int) -> np.ndarray:
     return out
 
 
+def stage_range_host(seg_start, sub_start, sub_first: int, sub_count: int, subsequence_bytes: int) -> Tuple[int, int]:
+    """The contract of `fear_jpeg_stage_range` (csrc/fear_jpeg_store.h: ji_stage_range): the bytes byte0 .. byte1) of a prepared scan
+    that its subsequences sub_first .. sub_first + sub_count) cover, which a workgroup of the staged kernels copies into LDS.
+    Consecutive subsequences are consecutive bytes, across segments too (an empty segment owns none), so it is one range: from the
+    first subsequence's first byte to the last one's end, which is its segment's end where the segment ends inside it.  Each of the
+    two lies in the last segment that starts at or in front of it.  (0, 0) for sub_count == 0."""
+    seg, sub = np.asarray(seg_start, dtype=np.int64), np.asarray(sub_start, dtype=np.int64)
+    if sub_count <= 0 or seg.size < 2:
+        return 0, 0
+    first, last = int(sub_first), int(sub_first) + int(sub_count) - 1
+    s0, s1 = (min(int(np.searchsorted(sub, x, side="right")) - 1, seg.size - 2) for x in (first, last))
+    lo = int(seg[s0]) + (first - int(sub[s0])) * int(subsequence_bytes)
+    hi = min(int(seg[s1]) + (last - int(sub[s1]) + 1) * int(subsequence_bytes), int(seg[s1 + 1]), int(seg[-1]))
+    return (lo, hi) if 0 <= lo < hi else (0, 0)
+
+
 class _Segment:
     """What a lane of the write pass knows of its segment (JhSegment)."""
 

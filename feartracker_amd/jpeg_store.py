@@ -32,7 +32,11 @@ image of its own — and returns COMPACT frames with their origins, a `WindowFra
 
 The three plans are one plan over shared parts: the units that cover a request (`_cover`, for MCU rows and MCU columns alike), a band's
 lanes (`_band_lanes`), what a run of units spans of the image (`_extent`), and the groups of a call (`_groups`: the cut, the layout and
-what each group carries).  `add` is a sequence of stages over one `_Entry` per file, of which the last alone assigns to the store."""
+what each group carries).  `add` is a sequence of stages over one `_Entry` per file, of which the last alone assigns to the store.
+
+`JpegStore(residence="host")` keeps the scan bytes in pinned host memory, which the Huffman kernels read in place through a staged
+fetch (the `fear_jpeg_huffman_indexed*_host` calls), and the index and tables on the device: every call and every frame is the
+`"device"` store's ("Bytes on the host")."""
 from __future__ import annotations
 
 import ctypes
@@ -57,7 +61,8 @@ COLUMNS = np.dtype([("n_seg", "<u4"), ("n_sub", "<u4"), ("total_blocks", "<u4"),
 
 
 class StoreFull(MemoryError):
-    """An `add` would take the store above its `capacity_bytes`; nothing of the call was stored."""
+    """An `add` would take the store above its `capacity_bytes` or, under residence="host", its `host_capacity_bytes` — the message
+    names which; nothing of the call was stored."""
 
 
 def _up(x, to):
@@ -310,7 +315,10 @@ def _frame_views(out, out_offset: np.ndarray, high: np.ndarray, wide: np.ndarray
 class _Entry:
     """One "scan" file of an `add` on its way into the store: what `scan_prepare` made of it (info, data, seg, scan), its `sub_start`,
     its resident layout (where seg_start, sub_start, the index and the FearJpegScan record begin behind the bytes, and the `end`),
-    its place (`at` in `slab`, the address `base`), its row table and the address of the table's copy on the device."""
+    its place (`at` in `slab`, the address `base`), its row table and the address of the table's copy on the device.  Under
+    residence="host" the bytes lie apart: `host_end` of them at `host_at` in the pinned `host_slab`, which the device reads at
+    `host_base`; the resident layout then begins with seg_start (`at_seg` is 0), and `build_bytes` is where the transient device copy
+    of the bytes lies that `fear_jpeg_index_build` reads."""
     info: object
     data: np.ndarray
     seg: np.ndarray
@@ -326,6 +334,11 @@ class _Entry:
     at: int = 0
     row_table: Optional[np.ndarray] = None
     row_dev_at: int = 0
+    host_slab: object = None
+    host_at: int = 0
+    host_end: int = 0
+    host_base: int = 0
+    build_bytes: int = 0
 
 
 class JpegStore:
@@ -365,16 +378,35 @@ class JpegStore:
     4 (mcus_y + 1) bytes per file that `resident["rows"]` counts), for `decode_rows` with `rows` on the device.
     `decode_windows(ids, windows)` decodes per frame the MCUs that cover one rectangle and returns compact tensors with their origins
     (`WindowFrames`), which `TrainPairBuilder.build` takes in place of the frames.
-    Out of scope: eviction and `remove`, saving a store to disk, sharding over ranks, `JpegDecoder`'s default, windows given on
-    the device."""
+    `residence="host"` keeps each file's unstuffed scan bytes in PINNED HOST memory and everything small — `seg_start`, `sub_start`, the
+    index, the `FearJpegScan` record, the row tables, the borders — on the device: a ninth of a file's footprint, so that the store's
+    capacity is the host's memory ("Bytes on the host").  The bytes lie in pinned slabs of `slab_bytes` under
+    the device slabs' rules (never reallocated, a file never straddles one); a resident record's `bytes` is the slab's device-side
+    address (`fear_host_mapped_pointer`), and every Huffman launch is the `_host` entry point of the same name, whose workgroups copy
+    the byte range of their lanes into LDS with wide loads in front of the decode (zero copy: no file bytes are uploaded by a
+    decode call).  `add` builds the index from a transient device copy of the call's bytes and drops it behind the verdicts; the
+    index, the row tables and the borders are those of a `"device"` store byte for byte, and so is every frame of every call.
+    `nbytes`, `capacity_bytes` and `resident["bytes"]` (then the two tables alone) count device bytes; `host_nbytes`,
+    `host_capacity_bytes` and `resident["host_bytes"]` the pinned ones, and `StoreFull` names the limit that was hit.  Entries kept as
+    pixels stay on the device.  `host_capacity_bytes` without `residence="host"`, or another `residence`, is a ValueError.
+    Out of scope: eviction and `remove`, saving a store to disk, sharding over ranks, pageable or memory-mapped files as the backing
+    of `residence="host"`, `JpegDecoder`'s default, windows given on the device."""
     PENDING_CALLS = 64
 
     def __init__(self, device: int = 0, capacity_bytes: Optional[int] = None, subsequence_bytes: int = 128, slab_bytes: int = 256 << 20,
-                 workspace_limit: int = 1 << 30, threads: Optional[int] = None, initial_rows: int = 1024, progressive: bool = False):
+                 workspace_limit: int = 1 << 30, threads: Optional[int] = None, initial_rows: int = 1024, progressive: bool = False,
+                 residence: str = "device", host_capacity_bytes: Optional[int] = None):
         from .train_abi import FearJpegImage, FearJpegIndexed
         _check_subsequence_bytes(subsequence_bytes)
         if slab_bytes < 16 or initial_rows < 1:
             raise ValueError("slab_bytes is at least 16 and initial_rows at least 1")
+        if residence not in ("device", "host"):
+            raise ValueError(f'residence is "device" or "host", not {residence!r}')
+        if host_capacity_bytes is not None and residence != "host":
+            raise ValueError('host_capacity_bytes limits the pinned bytes of residence="host" alone')
+        self.residence = residence
+        self.host_capacity_bytes = None if host_capacity_bytes is None else int(host_capacity_bytes)
+        self._staged = True                                              # (False: the direct kernels on host bytes, the bench's ablation)
         self.progressive = bool(progressive)
         self._host = JpegDecoder(device=device, threads=threads, progressive=progressive)   # the pool, sized as JpegDecoder sizes it: never by the machine's CPUs, at most 16
         self.threads, self.device, self._lib = self._host.threads, self._host.device, self._host._lib
@@ -388,9 +420,16 @@ class JpegStore:
 
     # ------------------------------------------------------------------------------------------------------------------ bookkeeping
     def clear(self) -> None:
-        """Forget every entry and free the slabs.  Ids start at 0 again."""
+        """Forget every entry and free the slabs.  Ids start at 0 again.  (Pinned slabs are dropped behind a synchronise: a freed pinned
+        block is handed out again at once, whatever kernel still reads it.)"""
+        if getattr(self, "_host_slabs", None):
+            import torch
+            torch.cuda.synchronize(self.device)
         self._n, self.nbytes = 0, 0
-        self.resident = dict(bytes=0, index=0, records=0, pixels=0, rows=0, border=0)      # what nbytes is made of
+        # what nbytes is made of, and `host_bytes`: the pinned bytes of residence="host", which nbytes does not count
+        self.resident = dict(bytes=0, index=0, records=0, pixels=0, rows=0, border=0, host_bytes=0)
+        self._host_slabs: List = []                                      # residence="host": (pinned uint8 tensor, its device-side address)
+        self._host_open, self._host_cursor = None, 0
         self._row_sub, self._row_used = np.zeros(4 * self._initial_rows, dtype=np.uint32), 0   # ragged: COLUMNS["row_at"] indexes it
         self._border = None                                              # (capacity, 3) uint8 on the device, grown with the mirrors
         self._indexed, self._image, self._columns = (np.zeros(self._initial_rows, dtype=d) for d in self._dtypes)
@@ -408,6 +447,11 @@ class JpegStore:
 
     def __len__(self) -> int:
         return self._n
+
+    @property
+    def host_nbytes(self) -> int:
+        """The pinned host bytes the store holds (residence="host"): `resident["host_bytes"]`, what `host_capacity_bytes` limits."""
+        return self.resident["host_bytes"]
 
     @property
     def kinds(self) -> np.ndarray:
@@ -474,15 +518,17 @@ class JpegStore:
         split = self._add_layout(entries, through_host, raw, n)
         with torch.cuda.device(self.device):
             new_slabs, open_slab, cursor, runs = self._add_place(entries)
-            self._add_upload(runs)
+            host_place = self._add_place_host(entries)
+            transient = self._add_upload(runs)
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
             new_borders = torch.zeros((n, 3), dtype=torch.uint8, device=self.device)
             self._add_verdicts(self._add_index(entries, new_borders, stream), blobs)
+            del transient                                                # the build's device copies of host-resident bytes
             pixels = self._add_pixels(blobs, through_host, raw, new_borders, stream)
             row_dev = self._add_row_tables(entries)
             border = self._add_border(self._n + n)
             torch.cuda.current_stream().synchronize()                    # what was stored is complete for a decode on any stream
-        return self._add_commit(n, entries, pixels, split, new_slabs, open_slab, cursor, row_dev, border, new_borders)
+        return self._add_commit(n, entries, pixels, split, new_slabs, open_slab, cursor, row_dev, border, new_borders, host_place)
 
     def _add_prepare(self, blobs: List[bytes], fallback):
         """Stage 1 of `add`: transcode (a progressive file takes its baseline transcode's place in `blobs`) and prepare on the pool, then
@@ -503,10 +549,12 @@ class JpegStore:
 
     def _add_layout(self, entries: dict, through_host: dict, raw: dict, n: int) -> dict:
         """Stage 2: every entry's `sub_start` and resident layout from its base — bytes | seg_start | sub_start | index | FearJpegScan,
-        each at 16 bytes — and what the call adds to `resident`, key by key; `StoreFull` where that exceeds the capacity."""
+        each at 16 bytes — and what the call adds to `resident`, key by key; `StoreFull` where that exceeds the capacity.  Under
+        residence="host" the bytes go to a pinned slab instead (`host_end` of them, counted as `host_bytes` against
+        `host_capacity_bytes`) and the device layout begins with seg_start: `resident["bytes"]` then counts the two tables alone."""
         from . import train_abi as abi
         record = ctypes.sizeof(abi.FearJpegScan)
-        split = dict(bytes=0, index=0, records=0, pixels=0, rows=0, border=3 * n)
+        split, on_host = dict(bytes=0, index=0, records=0, pixels=0, rows=0, border=3 * n, host_bytes=0), self.residence == "host"
         for e in entries.values():
             e.sub, count = np.empty(e.seg.size, dtype=np.uint32), ctypes.c_uint32(0)
             rc = self._lib.fear_jpeg_sub_start(e.seg.ctypes.data, e.scan.n_seg, e.scan.n_bytes, self.subsequence_bytes, e.sub.ctypes.data,
@@ -514,6 +562,9 @@ class JpegStore:
             if rc != 0 or count.value != int(e.sub[-1]):
                 raise abi.TrainError(f"fear_jpeg_sub_start failed with status {rc}")
             e.at_seg = _up(max(e.data.nbytes, 1), 16)
+            if on_host:
+                e.host_end, e.at_seg = e.at_seg, 0
+                split["host_bytes"] += e.host_end
             e.at_sub = e.at_seg + _up(e.seg.nbytes, 16)
             e.at_index = e.at_sub + _up(e.sub.nbytes, 16)
             e.at_record = e.at_index + 16 * int(e.sub[-1])
@@ -523,9 +574,12 @@ class JpegStore:
             split["records"] += record
             split["rows"] += 4 * (int(e.info.mcus_y) + 1)
         split["pixels"] = sum(3 * info.width * info.height for info in through_host.values()) + sum(px.nbytes for px in raw.values())
-        need = sum(split.values())
+        need, host_need = sum(split.values()) - split["host_bytes"], split["host_bytes"]
         if self.capacity_bytes is not None and self.nbytes + need > self.capacity_bytes:
             raise StoreFull(f"{need} bytes more on top of {self.nbytes} exceed the capacity of {self.capacity_bytes}")
+        if self.host_capacity_bytes is not None and self.host_nbytes + host_need > self.host_capacity_bytes:
+            raise StoreFull(f"{host_need} pinned host bytes more on top of {self.host_nbytes} exceed the host capacity of "
+                            f"{self.host_capacity_bytes}")
         return split
 
     def _add_place(self, entries: dict):
@@ -551,19 +605,62 @@ class JpegStore:
                 runs.append([e])
         return new_slabs, open_slab, cursor, runs
 
-    def _add_upload(self, runs: List[list]) -> None:
-        """Stage 4: one copy per run of neighbours in a slab."""
+    def _add_place_host(self, entries: dict):
+        """Stage 3 for the bytes of residence="host": a place in a pinned slab for every entry's bytes, by the rule of the device
+        slabs (never reallocated, a file never straddles one, a larger file gets its own), and the bytes copied there — behind the
+        tentative cursor, where no entry of the store lies.  The new slabs, each with its device-side address
+        (`fear_host_mapped_pointer`, once per slab), the open one and its cursor as the commit will set them; None on the device."""
         import torch
+        from . import train_abi as abi
+        if self.residence != "host":
+            return None
+        new_slabs, open_slab, cursor = [], self._host_open, self._host_cursor
+
+        def pinned(nbytes):
+            slab, mapped = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True), ctypes.c_void_p(0)
+            abi.launch(self._lib, "fear_host_mapped_pointer", ctypes.c_void_p(slab.data_ptr()), ctypes.byref(mapped))
+            assert mapped.value % 16 == 0
+            new_slabs.append((slab, mapped.value))
+            return new_slabs[-1]
+
+        for e in entries.values():
+            if e.host_end > self.slab_bytes:                             # a slab of its own; the open slab stays open
+                (e.host_slab, address), e.host_at = pinned(e.host_end), 0
+            else:
+                if open_slab is None or cursor + e.host_end > self.slab_bytes:
+                    open_slab, cursor = pinned(self.slab_bytes), 0
+                (e.host_slab, address), e.host_at = open_slab, cursor
+                cursor += e.host_end
+            e.host_base = address + e.host_at
+            e.host_slab.numpy()[e.host_at:e.host_at + e.data.nbytes] = e.data
+        return new_slabs, open_slab, cursor
+
+    def _add_upload(self, runs: List[list]) -> List:
+        """Stage 4: one copy per run of neighbours in a slab.  Under residence="host" the resident record points at the pinned bytes,
+        and the run's bytes go up once more into a transient tensor for `fear_jpeg_index_build`, whose synchronisation passes read
+        every byte several times: those tensors, which `add` drops behind the verdicts."""
+        import torch
+        transient = []
         for run in runs:
             host, w = np.zeros(sum(e.end for e in run), dtype=np.uint8), 0
+            if self.residence == "host":
+                at = _exclusive(np.array([e.host_end for e in run], dtype=np.int64))
+                staged = np.zeros(int(at[-1]), dtype=np.uint8)
+                for e, a in zip(run, at.tolist()):
+                    staged[a:a + e.data.nbytes] = e.data
+                transient.append(torch.from_numpy(staged).to(self.device))
+                for e, a in zip(run, at.tolist()):
+                    e.build_bytes = transient[-1].data_ptr() + a
             for e in run:
-                e.scan.bytes, e.scan.seg_start, e.scan.coef_offset = e.base, e.base + e.at_seg, 0
-                host[w:w + e.data.nbytes] = e.data
+                e.scan.bytes, e.scan.seg_start, e.scan.coef_offset = e.host_base or e.base, e.base + e.at_seg, 0
+                if not e.host_end:
+                    host[w:w + e.data.nbytes] = e.data
                 host[w + e.at_seg:w + e.at_seg + e.seg.nbytes] = e.seg.view(np.uint8)
                 host[w + e.at_sub:w + e.at_sub + e.sub.nbytes] = e.sub.view(np.uint8)
                 host[w + e.at_record:w + e.end] = np.frombuffer(e.scan, dtype=np.uint8)
                 w += e.end
             run[0].slab[run[0].at:run[0].at + host.size].copy_(torch.from_numpy(host))
+        return transient
 
     def _add_index(self, entries: dict, new_borders, stream) -> List[tuple]:
         """Stage 5: `fear_jpeg_index_build` over the entries in groups that `_cut` bounds by the scratch coefficients, and each group's
@@ -579,6 +676,8 @@ class JpegStore:
             for k, e in enumerate(entries[i] for i in group):
                 ctypes.memmove(ctypes.byref(records[k]), ctypes.byref(e.scan), ctypes.sizeof(e.scan))
                 records[k].coef_offset = values
+                if e.build_bytes:
+                    records[k].bytes = e.build_bytes                     # the transient device copy; the resident record keeps the host's
                 values += 64 * int(e.info.total_blocks)
                 prefix[k + 1] = prefix[k] + e.scan.n_seg
                 ix = indexes[k]
@@ -656,7 +755,7 @@ class JpegStore:
         return border
 
     def _add_commit(self, n: int, entries: dict, pixels: dict, split: dict, new_slabs: List, open_slab, cursor: int, row_dev, border,
-                    new_borders) -> np.ndarray:
+                    new_borders, host_place=None) -> np.ndarray:
         """Stage 10, the only one that assigns on self: the mirrors' rows, the row tables, the border colours, the slabs and the
         counts.  The ids."""
         import torch
@@ -689,7 +788,10 @@ class JpegStore:
         if row_dev is not None:
             self._row_slabs.append(row_dev)
         self._open, self._cursor = open_slab, cursor
-        self._n, self.nbytes = first + n, self.nbytes + sum(split.values())
+        if host_place is not None:
+            self._host_slabs += host_place[0]
+            self._host_open, self._host_cursor = host_place[1], host_place[2]
+        self._n, self.nbytes = first + n, self.nbytes + sum(split.values()) - split["host_bytes"]
         for key, v in split.items():
             self.resident[key] += v
         return np.arange(first, first + n, dtype=np.int64)
@@ -795,6 +897,8 @@ class JpegStore:
         sids, nd, banded, windowed = group[scan], scan.size, "sub0" in plan, "cols" in plan
         huffman = ("fear_jpeg_huffman_indexed_rows_dev" if rows is not None else "fear_jpeg_huffman_indexed_windows" if windowed
                    else "fear_jpeg_huffman_indexed_rows" if banded else "fear_jpeg_huffman_indexed")
+        if self.residence == "host" and self._staged:                    # the same records and grid, the staged fetch
+            huffman += "_host"
         with torch.cuda.device(self.device):
             out = torch.empty(max(plan["out_bytes"], 16), dtype=torch.uint8, device=self.device)
             out_offset = plan["out_offset"]

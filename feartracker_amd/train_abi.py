@@ -115,6 +115,14 @@ TRAIN_SYMBOLS = {
     "fear_jpeg_huffman_indexed_windows": ([_P, _i, _P, _P, _P, _i, _P], _i),
     # the band of rows taken from device memory (JpegStore.decode_rows with a device tensor)
     "fear_jpeg_huffman_indexed_rows_dev": ([_P, _i, _P, _P, _P, _P, _i, _P], _i),
+    # the same four for scans whose bytes lie in pinned host memory (JpegStore(residence="host")): the staged fetch, the device-side
+    # address of a pinned allocation, and the byte range a run of lanes covers (host only)
+    "fear_jpeg_huffman_indexed_host": ([_P, _i, _P, _P, _P, _i, _P], _i),
+    "fear_jpeg_huffman_indexed_rows_host": ([_P, _i, _P, _P, _P, _i, _P], _i),
+    "fear_jpeg_huffman_indexed_rows_dev_host": ([_P, _i, _P, _P, _P, _P, _i, _P], _i),
+    "fear_jpeg_huffman_indexed_windows_host": ([_P, _i, _P, _P, _P, _i, _P], _i),
+    "fear_host_mapped_pointer": ([_P, _P], _i),
+    "fear_jpeg_stage_range": ([_P, _P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _i, _P, _P], _i),
     "fear_jpeg_decode_u8_rows_dev": ([_P, _i, _P, _P, _P, _sz, _P], _i),
     "fear_jpeg_decode_scaled_u8": ([_P, _i, _P, _i, _P, _sz, _P], _i),
     "fear_jpeg_decode_mixed_u8": ([_P, _i, _P, _P, _sz, _P], _i),      # a scale per record, in FearJpegImage.reserved[0]

@@ -994,6 +994,40 @@ int fear_jpeg_huffman_indexed_rows_dev(const FearJpegIndexed* images, int n, con
 int fear_jpeg_huffman_indexed_windows(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
                                       int subsequence_bytes, void* stream);
 
+/* ---- scans whose bytes lie in pinned host memory ("Bytes on the host"; JpegStore(residence="host")).
+ * The four calls above, each with the STAGED byte fetch: the same records, checks, grids, launch counts and results, but `bytes` of a
+ * record's resident FearJpegScan is the DEVICE-SIDE address of pinned, mapped host memory (fear_host_mapped_pointer), which the kernels
+ * read in place; everything else of the record stays in device memory.  A workgroup's running lanes cover consecutive subsequences,
+ * hence one byte range (fear_jpeg_stage_range).  In front of its barrier the workgroup copies that range into LDS with 16-byte loads:
+ * from the 16-byte aligned address at or in front of the range's first byte to two words behind its end (the last lane's 64-bit
+ * window), at most min(256 subsequence_bytes + 32, 65536) bytes — the launch's dynamic LDS — and never a word at or behind
+ * 4 ceil(n_bytes / 4) bytes from `bytes` nor one in front of it.  A lane takes a word from LDS where it was staged and from `bytes`
+ * otherwise: above subsequence_bytes 256 a range can exceed the cap, its tail is then read directly, slower and as exact.  Form rows_dev
+ * stages the range of the band's lanes alone (an idle workgroup returns in front of it), form windows that of all the band's lanes of
+ * the workgroup, whether or not one of them touches the window.  FEAR_TRAIN_ERR_HIP where the runtime refuses the kernels' LDS size.
+ *
+ * fear_host_mapped_pointer asks hipPointerGetAttributes for the device-side address of `host`, a pointer into a pinned, mapped host
+ * allocation, and stores it to *device.  FEAR_TRAIN_ERR_SHAPE (and a null *device) for anything else: pageable memory, device or managed
+ * memory, a null `host`; FEAR_TRAIN_ERR_NULL for a null `device`; FEAR_TRAIN_ERR_HIP where there is no device to ask.
+ *
+ * fear_jpeg_stage_range is the range rule on the host, before alignment and cap: the bytes byte0 .. byte1) of the scan that the
+ * subsequences sub_first .. sub_first + sub_count) cover — the union of [seg_start[s] + k subsequence_bytes, min(that +
+ * subsequence_bytes, seg_start[s + 1])) over them, one range because consecutive subsequences are consecutive bytes; 0, 0 for
+ * sub_count == 0.  The kernels and this function share one helper; jpeg_huffman.stage_range_host restates it.  Host code, no HIP call.
+ * FEAR_TRAIN_ERR_NULL: a null pointer; FEAR_TRAIN_ERR_SHAPE: fear_jpeg_sub_start's refusals of seg_start, a sub_start that is not
+ * its prefix sums, sub_first + sub_count > n_sub.                                                                                      */
+int fear_jpeg_huffman_indexed_host(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
+                                   int subsequence_bytes, void* stream);
+int fear_jpeg_huffman_indexed_rows_host(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
+                                        int subsequence_bytes, void* stream);
+int fear_jpeg_huffman_indexed_rows_dev_host(const FearJpegIndexed* images, int n, const void* table_dev, const int32_t* rows_dev,
+                                            int16_t* coef, int32_t* status_dev, int subsequence_bytes, void* stream);
+int fear_jpeg_huffman_indexed_windows_host(const FearJpegIndexed* images, int n, const void* table_dev, int16_t* coef, int32_t* status_dev,
+                                           int subsequence_bytes, void* stream);
+int fear_host_mapped_pointer(const void* host, void** device);
+int fear_jpeg_stage_range(const uint32_t* seg_start, const uint32_t* sub_start, uint32_t n_seg, uint32_t n_bytes, uint32_t sub_first,
+                          uint32_t sub_count, int subsequence_bytes, uint32_t* byte0, uint32_t* byte1);
+
 /* ---- the colour stage's members that are no lookup table: Equalize, HueSaturationValue, ColorJitter and Emboss of the reference's
  * p = 0.5 OneOf (model_training/dataset/aug.py:35-48), on uint8 HWC crops between fear_train_pairs_u8 (tone, then the lookup-table
  * members) and fear_photometric_u8 (DESIGN.md section 11 states every contract; train_data.colour_u8_host restates them in numpy and the

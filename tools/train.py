@@ -13,7 +13,10 @@ sampler keys        --negative-ratio, --frame-offset, --clip-range, --num-sample
 --scale auto        per batch and frame the largest fraction that upsamples no crop read from the frame (TrainPairBuilder.frame_scales),
                     at most 1 / --max-scale
 --windows           decode per frame only the rectangle a batch reads, as compact frames (JpegStore.decode_windows)
-Every file is decoded from a JpegStore, so the datasets must fit in --capacity-gb of device memory.  The run writes last.pt (resumed
+--store-residence host   keep the files' scan bytes in pinned host memory (JpegStore(residence="host")): the device holds the indexes and
+                    tables alone, about a ninth of a file's footprint, and --host-capacity-gb limits the pinned bytes
+Every file is decoded from a JpegStore, so the datasets must fit in --capacity-gb of device memory (with --store-residence host: their
+indexes there and their bytes in --host-capacity-gb of pinned host memory).  The run writes last.pt (resumed
 from with --resume), the best three .fearw files and history.json under --out.  After every epoch the tool calls `store.check()`: the
 store keeps the statuses of its last `JpegStore.PENDING_CALLS` (64) decode calls only, so that is a check of the epoch's last batches
 and of the validation's decodes, not of every batch (the files themselves were judged in full when they were added)."""
@@ -73,6 +76,8 @@ def parse_args(argv=None):
     ap.add_argument("--max-val-samples", type=int, default=200)
     ap.add_argument("--early-stopping", type=int, default=20)
     ap.add_argument("--capacity-gb", type=float, default=None)
+    ap.add_argument("--store-residence", default="device", choices=("device", "host"), help="where the store keeps the files' scan bytes")
+    ap.add_argument("--host-capacity-gb", type=float, default=None, help="with --store-residence host: the limit of the pinned host bytes")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--resume", default=None)
@@ -110,9 +115,14 @@ def main(argv=None):
 
     os.makedirs(args.out, exist_ok=True)
     tables, samplers, plan = make_plan(args)
-    store = JpegStore(device=args.device, capacity_bytes=None if args.capacity_gb is None else int(args.capacity_gb * 2 ** 30))
+    if args.host_capacity_gb is not None and args.store_residence != "host":
+        raise SystemExit("--host-capacity-gb goes with --store-residence host")
+    store = JpegStore(device=args.device, capacity_bytes=None if args.capacity_gb is None else int(args.capacity_gb * 2 ** 30),
+                      residence=args.store_residence,
+                      host_capacity_bytes=None if args.host_capacity_gb is None else int(args.host_capacity_gb * 2 ** 30))
     row_ids = fill_store(store, tables)
-    print(f"{sum(map(len, tables))} rows, {len(store)} files, {store.nbytes / 2 ** 20:.0f} MiB resident")
+    print(f"{sum(map(len, tables))} rows, {len(store)} files, {store.nbytes / 2 ** 20:.0f} MiB resident on the device, "
+          f"{store.host_nbytes / 2 ** 20:.0f} MiB in pinned host memory")
     builder = TrainPairBuilder(dict(photometric=True) if args.photometric else None, device=args.device, seed=args.seed)
     loader = PairLoader(plan, store, row_ids, builder, scale=args.scale, prefetch=args.prefetch, windows=args.windows,
                         max_scale=args.max_scale)
